@@ -3,7 +3,9 @@
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0. With N > 1 and no
 torch.distributed environment the script re-launches itself under `python -m torch.distributed.run --nproc-per-node N` (one rank per
-GPU over RCCL); launched by torchrun directly it just checks WORLD_SIZE == N.
+GPU over RCCL); launched by torchrun directly it just checks WORLD_SIZE == N. `ms_per_step` is the wall time of one timed step.
+`--dump-outputs DIR` writes the result images of the last timed step (DIR/pair<i>.npy, float32, at most 64 MB in all; the inputs depend only on
+the arguments), so that two builds can be compared output for output.
 
 A "step" = one full pass of the hot path (VGG19 features, k-means, L=5->1 PatchMatch both ways, BDS votes, kNN graphs, nonlocal +
 WLS colour solves, re-predicts) over one batch of `--inflight` (default 4) synthetic 700x700 source/reference pairs per GPU —
@@ -19,7 +21,7 @@ Extra objects:
   roofline     — the dominant kernel AS THE PIPELINE RUNS IT: the finest PatchMatch level's 41 launches, k_pm_step<1, 1, 2, 2, 8> / k_pm_prop<1, 1, 2, 2, 8> (C = 64, both directions per
                  launch, unit-norm features with the exact row rejection). avg launch time = HIP events recorded on the library's stream around the
                  level's 41 launches of a real pair; `traffic` = fabric-side bytes per launch from rocprofv3 PMC passes (FETCH_SIZE
-                 x2 gfx950 correction + WRITE_SIZE, separate passes) of THIS build — collected live when rocprofv3 is on PATH, else
+                 x2 gfx950 correction + WRITE_SIZE, separate passes) of THIS build — collected live with --pmc when rocprofv3 is on PATH, else
                  read from profiles/ only if the recorded build id equals this libnct.so's; `achieved` = traffic / launch time,
                  `frac` = achieved / 8 TB/s. The SURVEY §8d no-reuse byte model is reported next to it (`algorithmic_GBs`).
   roofline_color — the colour solvers' full-resolution kernels (57 % of a pair in round 3): S1 operator / direction / update and the WLS PCG's finest V-cycle
@@ -27,8 +29,8 @@ Extra objects:
                  (NCT_FLAG_TIME_KERNELS: HIP events on the pair's stream around the launch) and the fraction of the 8 TB/s peak; plus SURVEY §8(d)'s per-iteration
                  byte models over the iteration times.
   roofline_1000 — the same PatchMatch roofline on BASELINE config 4 (1000x1000: the finest level's 512 MB footprint exceeds the 256 MiB Infinity Cache, so its
-                 fabric-side bytes are HBM bytes), from two live counter passes.
-  cpu_baseline — the CPU oracle ("port") end-to-end on a bounded sample of the same workload, on this box's host cores.
+                 fabric-side bytes are HBM bytes), from two live counter passes (--pmc only).
+  cpu_baseline — the CPU oracle ("port") end-to-end on a bounded sample of the same workload, on this box's host cores (--cpu-baseline only).
   stages_ms    — per-stage device time of one extra pair (events on the stream; not part of the timed region).
   natural      — the reference's own demo photographs (the five image pairs of demo/example/pairs.txt, sizes as shipped, synthetic weights), one pair in flight, next to
                  synthetic pairs of the same sizes: ms per pair, pairs/s, the natural/synthetic ratio, WLS iterations (outside the timed region; `available: false` where the
@@ -101,6 +103,24 @@ def natural_extra(ctx, prm, synth):
     return out
 
 
+DUMP_BYTES = 64 * 10 ** 6     # --dump-outputs: at most this many bytes of float32 over all ranks
+
+
+def dump_outputs(d, outs, total_elems):
+    """--dump-outputs: each uint8 result image of `outs` (name -> H x W x 3 BGR) as d/<name>.npy in float32. total_elems = the element count of ALL
+    the step's results over all ranks; if they exceed DUMP_BYTES, every image is cut to the same fraction of its elements, taken at sorted positions
+    of its flattened array drawn from a generator seeded by its name — so the sample depends only on the arguments, never on which rank ran the pair."""
+    os.makedirs(d, exist_ok=True)
+    frac = min(1.0, DUMP_BYTES / 4 / total_elems)
+    for name, img in outs.items():
+        a = np.asarray(img, dtype=np.float32)
+        if frac < 1.0:
+            flat = a.reshape(-1)
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(flat.size, int(flat.size * frac), replace=False))
+            a = flat[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def pm_bytes(evals, n_queries, n_launches, C):
     """candidate tiles + query tile once per launch + NNF/dist read-modify-write."""
     return evals * 9 * C * 4 + n_launches * n_queries * 9 * C * 4 + n_launches * n_queries * 5 * 8
@@ -143,17 +163,28 @@ def main():
                     help="N = 1: run the barrier / MAX-reduce through a ONE-rank RCCL process group as well, so that the code the 8-GPU run depends on executes in every "
                          "1-GPU run (auto: try, fall back to no group and say why in rccl_error; on: fail if RCCL cannot start; off: no group, rounds 1-4)")
     ap.add_argument("--force-dist", action="store_true", help="alias of --dist-single on")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-full", action="store_true", help="time the oracle on the full SxS pair even on a small host (the default from 32 host threads on: ~2 min)")
-    ap.add_argument("--cpu-baseline-sample", action="store_true", help="time the oracle on the bounded 350x350 sample only (seconds) and scale by pixel count")
+    ap.add_argument("--cpu-baseline", action="store_true", help="time the CPU oracle after the GPU runs (key `cpu_baseline`; minutes at 700x700, so off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="no CPU oracle timing (the default; overrides --cpu-baseline*)")
+    ap.add_argument("--cpu-baseline-full", action="store_true", help="--cpu-baseline on the full SxS pair even on a small host (the choice from 32 host threads on: ~2 min)")
+    ap.add_argument("--cpu-baseline-sample", action="store_true", help="--cpu-baseline on the bounded 350x350 sample only (seconds) and scaled by pixel count")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-natural", action="store_true", help="skip the extra single-pair runs on the reference's demo photographs (key `natural`)")
-    ap.add_argument("--no-pmc", action="store_true", help="do not spawn the rocprofv3 PMC passes (traffic falls back to profiles/)")
+    ap.add_argument("--pmc", action="store_true", help="spawn the rocprofv3 counter passes of the rooflines (minutes, so off by default: traffic falls back to profiles/)")
+    ap.add_argument("--no-pmc", action="store_true", help="no rocprofv3 counter passes (the default; overrides --pmc)")
     ap.add_argument("--no-pmc-1000", action="store_true", help="skip the two counter passes on the 1000x1000 pair (roofline_1000)")
     ap.add_argument("--no-vary", action="store_true", help="every step re-runs the same resident pairs (rounds 1-3); default: two resident sets of pairs per GPU, alternating step by step")
     ap.add_argument("--no-latency-flag", action="store_true", help="skip the two extra single-pair runs with NCT_FLAG_LATENCY (kernel-trace runs: keeps the launch count per pair comparable)")
     ap.add_argument("--print-launch", action="store_true", help="[test hook] print the torchrun command --gpus N would re-launch with, and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result images of the last timed step as DIR/pair<i>.npy (float32), so that two builds can be compared "
+                         "output for output. When all together exceed 64 MB each file holds the same fraction of its image's flattened elements, at the sorted "
+                         "positions np.random.default_rng(zlib.crc32(b'pair<i>')).choice(size, n, replace=False)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    # the CPU oracle and the counter passes take minutes next to the timed steps' seconds: only on request
+    args.no_cpu_baseline = args.no_cpu_baseline or not (args.cpu_baseline or args.cpu_baseline_full or args.cpu_baseline_sample)
+    args.no_pmc = args.no_pmc or not args.pmc
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU: re-launch under torchrun (the driver may also do this itself)
@@ -270,6 +301,10 @@ def main():
                 run_workers(lambda k: ctxs[sidx * K + k].pair_run(prm))
         elapsed = timed_region(lambda i: run_workers(lambda k: ctxs[(i % NSETS) * K + k].pair_run(prm)), args.steps, args.warmup, dist=dist, sync=sync,
                                device=torch.device("cuda", local_rank) if rccl_ranks else None)
+        if args.dump_outputs:
+            # the last timed step ran set (warmup + steps - 1) mod NSETS; its results are still resident (the host-to-host pass below overwrites them)
+            last = (args.warmup + args.steps - 1) % NSETS
+            dump_outputs(args.dump_outputs, {f"pair{my_pairs[last * K + k]}": ctxs[last * K + k].pair_download() for k in range(K)}, world * K * S * S * 3)
         pairs_per_step = world * K
         scaling = "weak"
         e2 = timed_region(lambda i: run_workers(lambda k: ctxs[(i % NSETS) * K + k].process_pair(host[(i % NSETS) * K + k][0], host[(i % NSETS) * K + k][1], prm)), args.steps, 0,
@@ -317,6 +352,7 @@ def main():
         store = dist.distributed_c10d._get_default_store() if dist is not None else None
         lock = threading.Lock()
         local = {"next": 0, "step": -1, "done": 0}
+        last_step, last_out = args.warmup + args.steps - 1, {}          # --dump-outputs: the results of the last timed step, by pair index
 
         def ticket(step_id):
             """next unprocessed pair of this step: a shared counter in the rendezvous store (work stealing across ranks, no collective)"""
@@ -343,11 +379,15 @@ def main():
                             return
                         idx = t
                     s_, r_ = images(idx)
-                    ctxs[k].process_pair(s_, r_, prm)
+                    o_ = ctxs[k].process_pair(s_, r_, prm)
                     with lock:
                         local["done"] += 1
+                        if args.dump_outputs and i == last_step:
+                            last_out[f"pair{idx}"] = o_
             run_workers(worker)
         elapsed = timed_region(batch_step, args.steps, args.warmup, dist=dist, sync=sync, device=torch.device("cuda", local_rank) if rccl_ranks else None)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_out, sum(sh * sw * 3 for sh, sw, _, _ in sizes))
         pairs_per_step = nb
         scaling = "strong"
         host_to_host = pairs_per_step * args.steps / elapsed

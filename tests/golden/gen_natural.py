@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 import numpy as np, oracle_bind
 from PIL import Image
 from caffemodel_io import synthetic_vgg19
+import natural_inputs
 orc = oracle_bind.load()
 orc.l.orc_set_threads(min(32, os.cpu_count() or 1))
 ws, bs = synthetic_vgg19(19)
@@ -24,7 +25,7 @@ CASES = {"in1_tar1_2": ("in1", "tar1", 2.0), "in4_tar4_2": ("in4", "tar4", 2.0),
 
 
 def load_bgr(name):
-    return np.ascontiguousarray(np.asarray(Image.open(os.path.join(HERE, "natural", name + ".png")).convert("RGB"))[..., ::-1])
+    return np.ascontiguousarray(np.asarray(Image.open(os.path.join(natural_inputs.require(), name + ".png")).convert("RGB"))[..., ::-1])
 
 
 def crc(a):
@@ -46,7 +47,7 @@ if __name__ == "__main__":
         secs = [t_c]
         if exact_too:
             # NCT_GEN_REUSE_EXACT=1 (a change of the canonical S2 order only; the exact-solve run does not depend on it): keep the stored exact run when the new canonical run has its CRCs
-            fo = os.path.join(HERE, "natural", f"pair_{name}.npz")
+            fo = os.path.join(natural_inputs.STANDIN_DIR, f"pair_{name}.npz")
             old = np.load(fo) if os.environ.get("NCT_GEN_REUSE_EXACT") == "1" and os.path.exists(fo) else None
             if old is not None and "crc_exact" in old and int(old["crc_exact"]) == crc(canon) and [int(v) for v in old["level_crc_exact"]] == [crc(canon_lv[l]) for l in range(5)]:
                 exact, exact_lv = canon, canon_lv; secs.append(float(old["seconds"][1]))
@@ -60,6 +61,6 @@ if __name__ == "__main__":
                        level_linf_exact_vs_canonical=np.array([int(np.abs(exact_lv[l].astype(int) - canon_lv[l].astype(int)).max()) for l in range(5)]),
                        level_ndiff_exact_vs_canonical=np.array([int((exact_lv[l] != canon_lv[l]).sum()) for l in range(5)]))
         rec["seconds"] = np.array(secs)
-        np.savez_compressed(os.path.join(HERE, "natural", f"pair_{name}.npz"), **rec)
+        np.savez_compressed(os.path.join(natural_inputs.STANDIN_DIR, f"pair_{name}.npz"), **rec)
         print(name, src.shape, ref.shape, "bds", bds, "crc", int(rec["crc_canonical"]), "seconds", [round(x, 1) for x in secs],
               ("exact-vs-canonical differing bytes %d, per-level ndiff %s" % (rec["idx"].size, rec["level_ndiff_exact_vs_canonical"].tolist())) if exact_too else "", flush=True)

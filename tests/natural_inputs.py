@@ -1,14 +1,19 @@
-"""The reference's demo photographs (demo/example/in/{in,tar}{0,1,2,3,4}.png: all ten images of demo/example/pairs.txt) as test INPUTS — not committed (third-party images of unknown licence).
+"""Natural-image test inputs.
 
-They are staged, byte for byte, into tests/golden/natural/ (git-ignored, but not gpurun-ignored: like oracle/_ref they travel to the GPU box with the snapshot) by
-`python tests/natural_inputs.py`, which __graft_entry__.build() runs wherever a source directory exists: $NCT_DEMO_DIR, else /root/reference/demo/example/in.
-What IS committed are the derived fixtures tests/golden/natural/pair_*.npz (CRCs of the oracle's results on them, incl. the CRC of the decoded inputs, so a staged file
-that is not the generator's is noticed). Tests call require() and are skipped where the photographs are absent."""
+The tests use committed STAND-INS of the reference's ten demo photographs (demo/example/in/{in,tar}{0,1,2,3,4}.png): tests/golden/standin/*.png, written by
+tests/golden/gen_natural_standin.py with what natural photographs have and cosines + noise do not (large groups of one colour, isolated colours, one-pixel edges),
+the demo's colour types and a third of its sizes, plus the oracle's fixtures on them (tests/golden/standin/pair_<case>.npz, tests/golden/gen_natural.py). require()
+returns that directory and fails when it is incomplete: the tests never depend on files outside the repository.
+
+The photographs themselves (third-party images of unknown licence) are never committed. Where a source directory exists ($NCT_DEMO_DIR, else the reference's
+demo/example/in) stage() copies them byte for byte into tests/golden/natural/ (git-ignored); __graft_entry__.build() runs it, and bench.py's `natural` key measures them
+when they are there."""
 import os
 import shutil
 
 NAMES = ("in0", "in1", "in2", "in3", "in4", "tar0", "tar1", "tar2", "tar3", "tar4")
 DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "natural")
+STANDIN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "standin")
 
 
 def source_dir():
@@ -33,10 +38,11 @@ def stage():
 
 
 def require():
-    if not stage():
-        import pytest
-        pytest.skip("demo photographs not staged (set NCT_DEMO_DIR or run `python tests/natural_inputs.py` where /root/reference is mounted)")
-    return DIR
+    """the committed stand-in directory (images + oracle fixtures); raises when any stand-in image is missing"""
+    missing = [n for n in NAMES if not os.path.exists(os.path.join(STANDIN_DIR, n + ".png"))]
+    if missing:
+        raise FileNotFoundError(f"stand-in images missing from {STANDIN_DIR}: {missing} (python tests/golden/gen_natural_standin.py)")
+    return STANDIN_DIR
 
 
 if __name__ == "__main__":

@@ -34,10 +34,13 @@ def test_gpus_n_relaunches_one_rank_per_gpu():
 
 @pytest.mark.gpu
 def test_bench_emits_contract_json():
+    """The default line (what the driver reads) and, with --cpu-baseline, the CPU oracle's object (the oracle and the counter passes take minutes at 700x700: on request only)."""
     d = _run("--size", "128", "--steps", "2", "--warmup", "1", "--inflight", "2")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
-              "roofline", "cpu_baseline", "host_to_host_pairs_per_s", "build_id"):
+              "roofline", "host_to_host_pairs_per_s", "build_id"):
         assert k in d, k
+    assert "cpu_baseline" not in d
+    d["cpu_baseline"] = _run("--size", "128", "--steps", "1", "--warmup", "0", "--inflight", "1", "--no-roofline", "--cpu-baseline")["cpu_baseline"]
     assert d["unit"] == "pairs/s" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True
     assert d["scaling"] == "weak" and d["vs_baseline"] is None and d["data"] == "synthetic" and d["dtype"] == "f32"
     assert d["config"]["pairs_per_gpu_per_step"] == 2 and "workload" in d["config"] and d["config"]["name"] == "pair700"
@@ -118,3 +121,61 @@ def test_bench_other_workloads(wl):
     assert d["scaling"] == ("weak" if wl == "pair256l5" else "strong")
     if wl == "batch64":
         assert "700x700" in d["config"]["workload"] and d["config"]["pairs_per_gpu_per_step"] == 2 and d["output_checksum"] == _golden_sum_700()
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def test_dump_outputs_sample_is_fixed_and_within_the_budget(tmp_path):
+    """--dump-outputs writes float32 .npy files: whole images while all results of the step fit in 64 MB, else the same seeded sample of every image."""
+    import numpy as np
+    b = _bench_module()
+    imgs = {"pair0": np.arange(5 * 7 * 3, dtype=np.uint8).reshape(5, 7, 3), "pair3": np.full((4, 6, 3), 200, np.uint8)}
+    b.dump_outputs(str(tmp_path / "full"), imgs, 5 * 7 * 3 + 4 * 6 * 3)
+    for name, img in imgs.items():
+        got = np.load(tmp_path / "full" / (name + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, img.astype(np.float32))
+    big = {"pair1": np.random.default_rng(7).integers(0, 256, (400, 500, 3), dtype=np.uint8)}
+    total = 50 * 10 ** 6                       # the step's results over all ranks: 200 MB as float32
+    b.dump_outputs(str(tmp_path / "a"), big, total)
+    b.dump_outputs(str(tmp_path / "b"), big, total)
+    a, c = np.load(tmp_path / "a" / "pair1.npy"), np.load(tmp_path / "b" / "pair1.npy")
+    assert a.dtype == np.float32 and a.size == int(big["pair1"].size * (b.DUMP_BYTES / 4 / total)) and np.array_equal(a, c)
+    assert a.size * 4 / big["pair1"].size <= b.DUMP_BYTES / total
+    assert set(np.unique(a)) <= set(np.unique(big["pair1"]).astype(np.float32))
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path, ctx):
+    """--dump-outputs DIR: the result images of the last timed step. pair workloads alternate two resident sets of pairs, so 1 warm-up + 2 timed steps end on
+    set 0 (pairs 0, 1) and 1 + 3 on set 1 (pairs 2, 3); pair 0 is the pair whose byte sum the line reports. Batch workloads write every pair of the batch."""
+    import numpy as np
+    common = ["--size", "96", "--warmup", "1", "--inflight", "2", "--no-cpu-baseline", "--no-roofline", "--no-latency-flag", "--dist-single", "off"]
+    d = _run("--steps", "2", "--dump-outputs", str(tmp_path / "s2"), *common)
+    assert sorted(os.listdir(tmp_path / "s2")) == ["pair0.npy", "pair1.npy"]
+    p0 = np.load(tmp_path / "s2" / "pair0.npy")
+    assert p0.dtype == np.float32 and p0.shape == (96, 96, 3) and int(p0.sum()) == d["output_checksum"]
+    _run("--steps", "3", "--dump-outputs", str(tmp_path / "s3"), *common)
+    assert sorted(os.listdir(tmp_path / "s3")) == ["pair2.npy", "pair3.npy"]
+    assert not np.array_equal(np.load(tmp_path / "s3" / "pair2.npy"), p0)
+    # every dumped file against the same pair run on its own (bench.py's synthetic VGG19, seeds 1000 + 2i / 1001 + 2i, default parameters)
+    import nct
+    import synth
+    from caffemodel_io import synthetic_vgg19
+    ws, bs = synthetic_vgg19(19)
+    ctx.vgg19_load_raw(ws, bs)
+    for sub, i in (("s2", 0), ("s2", 1), ("s3", 2), ("s3", 3)):
+        exp = ctx.process_pair(synth.image(1000 + 2 * i, 96, 96), synth.image(1001 + 2 * i, 96, 96), nct.Params.default())
+        assert np.array_equal(np.load(tmp_path / sub / f"pair{i}.npy"), exp.astype(np.float32)), (sub, i)
+    m = _run("--workload", "mixed256", "--batch", "3", "--steps", "1", "--warmup", "0", "--inflight", "1", "--no-cpu-baseline", "--no-roofline", "--no-latency-flag",
+             "--dist-single", "off", "--dump-outputs", str(tmp_path / "m"))
+    assert m["config"]["name"] == "mixed256" and sorted(os.listdir(tmp_path / "m")) == ["pair0.npy", "pair1.npy", "pair2.npy"]
+    for i in range(3):
+        sh, sw, rh, rw = (int(v) for v in np.random.default_rng(5000 + i).integers(256, 1001, 4))
+        exp = ctx.process_pair(synth.image(1000 + 2 * i, sh, sw), synth.image(1001 + 2 * i, rh, rw), nct.Params.default())
+        assert np.array_equal(np.load(tmp_path / "m" / f"pair{i}.npy"), exp.astype(np.float32)), i
