@@ -502,7 +502,7 @@ int nctk_s1_solve(nct_ctx* ctx, hipStream_t s, const nct_s1_graph& g, const int*
     const int ogrid = one_xcd ? nbl * 8 : nbl;
     S1Sys S{n, h, w, daa, dab, dbb, gx, gy, knn_id, g, (s1_xcd && n >= 100000) ? 1 : 0, one_xcd};
     const double tol2 = 1e-6 * 1e-6;
-    const int maxit = layer == 4 ? 50 : 100;                       // ColorTransfer.cpp:916-921
+    const int maxit = ctx->s1_maxit > 0 ? ctx->s1_maxit : (layer == 4 ? 50 : 100);    // ColorTransfer.cpp:916-921 (NCT_S1_MAXIT: test hook)
     const bool coop = n >= 100000;                                  // shared in-edge gathers pay off on the bandwidth-bound levels only
     const bool fused = nbl <= S1_FUSE_NB;
     // hub pass: only where the host knows (or cannot exclude) that the level has in-edge lists longer than one block

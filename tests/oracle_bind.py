@@ -150,6 +150,62 @@ class Oracle:
         nl = self.l.orc_wls_hierarchy_stats(lab.reshape(-1), H, W, lamda, alpha, np.ascontiguousarray(rough, np.float64).reshape(-1), out.reshape(-1))
         return out[:nl]
 
+    # the colour stage's single steps (orc_color.c, orc_color_canon.c): what tests/ref64.py restates one by one
+    def local_stats(self, cnt_lab, stl_lab, eps=0.60, patch=3):
+        """T1: (a, b) [h*w][3] from level-size Lab u8 maps"""
+        self._decl_color()
+        c = np.ascontiguousarray(cnt_lab, np.uint8); s = np.ascontiguousarray(stl_lab, np.uint8)
+        h, w = c.shape[:2]
+        a = np.empty((h * w, 3)); b = np.empty((h * w, 3))
+        self.l.orc_local_stats.argtypes = [_u8p, _u8p, I, I, I, C.c_double, _f64p, _f64p]
+        self.l.orc_local_stats(c, s, h, w, patch, eps, a, b)
+        return a, b
+
+    def err_weight(self, err):
+        """T2: confidence weights [n] of a matching-error map"""
+        e = np.ascontiguousarray(err, np.float32).reshape(-1)
+        out = np.empty(e.size)
+        self.l.orc_err_weight.argtypes = [_f32p, I, _f64p]
+        self.l.orc_err_weight(e, e.size, out)
+        return out
+
+    def nonlocal_solve(self, ab, src, ref, weight, knn_id, knn_w, h, w, layer, lamda, alpha, dweight, nl_weight=2.0, k_num=8.0, maxit=0, explicit=False):
+        """S1 from ab [2][n][3] (canonical recurrence, or the literal one on the assembled A when explicit); maxit 0 = the reference's cap. Returns (ab, iters)."""
+        fn = self.l.orc_nonlocal_solve_explicit if explicit else self.l.orc_nonlocal_solve
+        fn.argtypes = [_f64p] * 5 + [_i32p, _f64p] + [I] * 4 + [C.c_float] * 3 + [C.c_double, C.c_double, _i32p, I]
+        ab = np.array(ab, np.float64, order="C", copy=True)
+        a, b = np.ascontiguousarray(ab[0]), np.ascontiguousarray(ab[1])
+        ids = np.ascontiguousarray(knn_id, np.int32)
+        it = np.zeros(3, np.int32)
+        fn(a.reshape(-1), b.reshape(-1), np.ascontiguousarray(src, np.float64).reshape(-1), np.ascontiguousarray(ref, np.float64).reshape(-1),
+           np.ascontiguousarray(weight, np.float64), ids.reshape(-1), np.ascontiguousarray(knn_w, np.float64).reshape(-1), ids.shape[1], h, w, layer,
+           lamda, alpha, dweight, nl_weight, k_num, it, maxit)
+        return np.stack([a, b]), it
+
+    def roughness(self, ab_up, lab_full):
+        ab = np.ascontiguousarray(ab_up, np.float64)
+        lab = np.ascontiguousarray(lab_full, np.float64).reshape(-1, 3)
+        out = np.empty(lab.shape[0])
+        self.l.orc_roughness.argtypes = [_f64p, _f64p, _f64p, I, _f64p]
+        self.l.orc_roughness(np.ascontiguousarray(ab[0]).reshape(-1), np.ascontiguousarray(ab[1]).reshape(-1), lab.reshape(-1), lab.shape[0], out)
+        return out
+
+    def wls_system(self, lab_full, H, W, lamda, alpha, rough):
+        """S2 system: (diag, wx, wy) [H*W]"""
+        self._decl_color()
+        diag, wx, wy = np.empty(H * W), np.empty(H * W), np.empty(H * W)
+        self.l.orc_wls_system(np.ascontiguousarray(lab_full, np.float64).reshape(-1), H, W, lamda, alpha, np.ascontiguousarray(rough, np.float64).reshape(-1), diag, wx, wy)
+        return diag, wx, wy
+
+    def apply_coeffs(self, ab, lab_full):
+        """A1 before Lab -> BGR: Lab u8 [N][3]"""
+        ab = np.ascontiguousarray(ab, np.float64)
+        lab = np.ascontiguousarray(lab_full, np.float64).reshape(-1, 3)
+        out = np.empty(lab.shape, np.uint8)
+        self.l.orc_apply_coeffs.argtypes = [_f64p, _f64p, _f64p, I, _u8p]
+        self.l.orc_apply_coeffs(np.ascontiguousarray(ab[0]).reshape(-1), np.ascontiguousarray(ab[1]).reshape(-1), lab.reshape(-1), lab.shape[0], out.reshape(-1))
+        return out
+
     def resize_u8c3(self, img, dh, dw):
         self._decl_color()
         a = np.ascontiguousarray(img, np.uint8); out = np.empty((dh, dw, 3), np.uint8)

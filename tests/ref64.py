@@ -1,0 +1,411 @@
+"""float64 restatements of the reference's colour stage, votes and PatchMatch distances — an independent check of oracle/ and of the kernels.
+
+Every function is written from the reference sources (code/windows/neural_color_transfer/source/: GeneralizedPatchMatch.cu, ColorTransfer/ColorTransfer.cpp,
+ColorTransfer/SparseSolver_GPU.cu; line numbers in each docstring) and from OpenCV's documented cv::resize mapping — never from oracle/ or csrc/, and this module
+imports neither. It computes in float64 throughout, except where the reference itself computes in float32; there np.float32 emulates it.
+
+Conventions: an NNF entry packs a match as (y << 12) | x (GeneralizedPatchMatch.cu:24-34). Feature maps are CHW, images and Lab maps HWC. Colour coefficients are
+(n, 3) arrays per part (a, b), the first index of a stage array [2][n][3] being the part.
+"""
+import numpy as np
+import scipy.sparse as sp
+import scipy.sparse.linalg as spla
+
+
+def _xy(nnf):
+    v = np.asarray(nnf, np.uint32).astype(np.int64)
+    return v & 0xFFF, (v >> 12) & 0xFFF
+
+
+def _pack(x, y):
+    return ((np.asarray(y, np.int64) << 12) | np.asarray(x, np.int64)).astype(np.uint32)
+
+
+# ---------------------------------------------------------------- N2
+def nnf_upsample(half, ah, aw, bh, bw):
+    """upSample_kernel, GeneralizedPatchMatch.cu:546-580, over the whole map. The ratios are float; `(ax + 0.5) / ratio` is a double division (0.5 is a double
+    literal); `ax + (bx_half - ax_half) * ratio` is float arithmetic to which the double 0.5 is added; int() truncates; clamp(x, max, min) (:9-21)."""
+    half = np.asarray(half, np.uint32)
+    hh, hw = half.shape
+    rw = np.float32(aw) / np.float32(hw)
+    rh = np.float32(ah) / np.float32(hh)
+    ax = np.arange(aw)[None, :].repeat(ah, 0)
+    ay = np.arange(ah)[:, None].repeat(aw, 1)
+    axh = np.clip(np.trunc((ax + 0.5) / np.float64(rw)).astype(np.int64), 0, hw - 1)
+    ayh = np.clip(np.trunc((ay + 0.5) / np.float64(rh)).astype(np.int64), 0, hh - 1)
+    bxh, byh = _xy(half[ayh, axh])
+    fx = ax.astype(np.float32) + (bxh - axh).astype(np.float32) * rw          # float * float, float + float: each rounded to float
+    fy = ay.astype(np.float32) + (byh - ayh).astype(np.float32) * rh
+    bx = np.clip(np.trunc(fx.astype(np.float64) + 0.5).astype(np.int64), 0, bw - 1)
+    by = np.clip(np.trunc(fy.astype(np.float64) + 0.5).astype(np.int64), 0, bh - 1)
+    return _pack(bx, by)
+
+
+# ---------------------------------------------------------------- P1
+def patch_distance(a, b, nnf, patch=3):
+    """dist_compute_single, GeneralizedPatchMatch.cu:355-405, at every pixel of A for the match nnf gives it: minus the sum over the patch taps that lie inside
+    BOTH maps of the channel dot product, divided by the number of such taps (1 when there is none; weight 1, pixel_sum 0). a: [C][ah][aw], b: [C][bh][bw]."""
+    a = np.asarray(a, np.float32)
+    b = np.asarray(b, np.float32)
+    C, ah, aw = a.shape
+    _, bh, bw = b.shape
+    bx, by = _xy(nnf)
+    ax = np.arange(aw)[None, :]
+    ay = np.arange(ah)[:, None]
+    acc = np.zeros((ah, aw))
+    cnt = np.zeros((ah, aw))
+    r = patch // 2
+    for dy in range(-r, r + 1):
+        for dx in range(-r, r + 1):
+            ok = (ay + dy >= 0) & (ay + dy < ah) & (ax + dx >= 0) & (ax + dx < aw) & (by + dy >= 0) & (by + dy < bh) & (bx + dx >= 0) & (bx + dx < bw)
+            yA, xA = np.clip(ay + dy, 0, ah - 1) + 0 * ax, np.clip(ax + dx, 0, aw - 1) + 0 * ay
+            yB, xB = np.clip(by + dy, 0, bh - 1), np.clip(bx + dx, 0, bw - 1)
+            dot = np.zeros((ah, aw))
+            for c0 in range(0, C, 64):
+                dot += np.einsum("chw,chw->hw", a[c0:c0 + 64, yA, xA].astype(np.float64), b[c0:c0 + 64, yB, xB].astype(np.float64))
+            acc -= np.where(ok, dot, 0.0)
+            cnt += ok
+    return np.where(cnt > 0, acc / np.maximum(cnt, 1), 1.0)
+
+
+def feature_distance(a, b):
+    """feature_distance, GeneralizedPatchMatch.cu:833-855: minus the per-pixel channel dot product of two maps of the same size."""
+    return -np.einsum("chw,chw->hw", np.asarray(a, np.float64), np.asarray(b, np.float64))
+
+
+# ---------------------------------------------------------------- B2
+def vote_features(ann, bnn, pin, w_coh, w_comp, patch=3):
+    """avg_vote_bds_a (:1074-1126), avg_vote_bds_b (:1128-1178) and avg_vote_bds (:1180-1202) of GeneralizedPatchMatch.cu in float64. pin: B's features
+    [C][bh][bw]. Coherence: A pixel (ax, ay) gathers, for each tap (dx, dy) inside A, B at ann[ay+dy][ax+dx] - (dx, dy) when that lies inside B, weight
+    w_coh / |A|. Completeness: every B pixel scatters, for each tap inside B whose partner bnn[b] + (dx, dy) lies inside A, B's tap value to that A pixel with
+    weight w_comp / |B|. Returns (pout [C][ah][aw], pw [ah][aw]); pout is divided by pw where pw > 0."""
+    pin = np.asarray(pin, np.float64)
+    C, bh, bw = pin.shape
+    ann = np.asarray(ann, np.uint32)
+    bnn = np.asarray(bnn, np.uint32)
+    ah, aw = ann.shape
+    wa = w_coh / float(aw * ah)
+    wb = w_comp / float(bw * bh)
+    out = np.zeros((C, ah * aw))
+    pw = np.zeros(ah * aw)
+    r = patch // 2
+    axg = np.arange(aw)[None, :] + 0 * np.arange(ah)[:, None]
+    ayg = np.arange(ah)[:, None] + 0 * np.arange(aw)[None, :]
+    pin_flat = pin.reshape(C, -1)
+    for dx in range(-r, r + 1):
+        for dy in range(-r, r + 1):
+            inA = (axg + dx >= 0) & (axg + dx < aw) & (ayg + dy >= 0) & (ayg + dy < ah)
+            xp, yp = _xy(ann[np.clip(ayg + dy, 0, ah - 1), np.clip(axg + dx, 0, aw - 1)])
+            xp, yp = xp - dx, yp - dy
+            ok = (inA & (xp >= 0) & (xp < bw) & (yp >= 0) & (yp < bh)).reshape(-1)
+            src = (np.clip(yp, 0, bh - 1) * bw + np.clip(xp, 0, bw - 1)).reshape(-1)
+            pw += ok * wa
+            out += pin_flat[:, src] * (ok * wa)
+    bxg = np.arange(bw)[None, :] + 0 * np.arange(bh)[:, None]
+    byg = np.arange(bh)[:, None] + 0 * np.arange(bw)[None, :]
+    xq, yq = _xy(bnn)
+    for dx in range(-r, r + 1):
+        for dy in range(-r, r + 1):
+            xb, yb, xa, ya = bxg + dx, byg + dy, xq + dx, yq + dy
+            ok = ((xb >= 0) & (xb < bw) & (yb >= 0) & (yb < bh) & (xa >= 0) & (xa < aw) & (ya >= 0) & (ya < ah)).reshape(-1)
+            aid = (ya * aw + xa).reshape(-1)[ok]
+            bid = (yb * bw + xb).reshape(-1)[ok]
+            scatter = sp.csr_matrix((np.full(aid.size, wb), (aid, bid)), shape=(ah * aw, bh * bw))
+            pw += np.asarray(scatter.sum(1)).ravel()
+            out += (scatter @ pin_flat.T).T
+    pos = pw > 0
+    out[:, pos] /= pw[pos]
+    return out.reshape(C, ah, aw), pw.reshape(ah, aw)
+
+
+# ---------------------------------------------------------------- B1
+def vote_image(a, b, ann, bnn, w_coh, w_comp, patch=3, want_float=False):
+    """reconstruct_bds, GeneralizedPatchMatch.cu:122-235, on u8 BGR images a [ah][aw][3] (only its size is used) and b [bh][bw][3]. Integer colour sums and tap
+    counts per A pixel from both directions, then (sa * wa + sb * wb) / (na * wa + nb * wb) in double with wa = w_coh / |A|, wb = w_comp / |B|, stored into a
+    uchar: truncation toward zero. want_float: also return that double value."""
+    ah, aw = np.asarray(a).shape[:2]
+    b = np.asarray(b, np.uint8)
+    bh, bw = b.shape[:2]
+    ann = np.asarray(ann, np.uint32)
+    bnn = np.asarray(bnn, np.uint32)
+    bflat = b.reshape(-1, 3).astype(np.int64)
+    r = patch // 2
+    left = -(patch // 2)                                          # leftSize = -patch_w / 2, rightSize = patch_w + leftSize - 1
+    right = patch + left - 1
+    ares = np.zeros((ah * aw, 3), np.int64)
+    acnt = np.zeros(ah * aw, np.int64)
+    axg = np.arange(aw)[None, :] + 0 * np.arange(ah)[:, None]
+    ayg = np.arange(ah)[:, None] + 0 * np.arange(aw)[None, :]
+    for dx in range(left, right + 1):
+        for dy in range(left, right + 1):
+            inA = (axg + dx < aw) & (axg + dx >= 0) & (ayg + dy < ah) & (ayg + dy >= 0)
+            xp, yp = _xy(ann[np.clip(ayg + dy, 0, ah - 1), np.clip(axg + dx, 0, aw - 1)])
+            ok = (inA & (xp - dx < bw) & (xp - dx >= 0) & (yp - dy < bh) & (yp - dy >= 0)).reshape(-1)
+            src = (np.clip(yp - dy, 0, bh - 1) * bw + np.clip(xp - dx, 0, bw - 1)).reshape(-1)
+            ares += bflat[src] * ok[:, None]
+            acnt += ok
+    bres = np.zeros((ah * aw, 3), np.int64)
+    bcnt = np.zeros(ah * aw, np.int64)
+    bxg = np.arange(bw)[None, :] + 0 * np.arange(bh)[:, None]
+    byg = np.arange(bh)[:, None] + 0 * np.arange(bw)[None, :]
+    xq, yq = _xy(bnn)
+    for dx in range(-r, r + 1):
+        for dy in range(-r, r + 1):
+            xb, yb, xa, ya = bxg + dx, byg + dy, xq + dx, yq + dy
+            ok = ((xb < bw) & (xb >= 0) & (yb < bh) & (yb >= 0) & (xa < aw) & (xa >= 0) & (ya < ah) & (ya >= 0)).reshape(-1)
+            aid = (ya * aw + xa).reshape(-1)[ok]
+            bid = (yb * bw + xb).reshape(-1)[ok]
+            np.add.at(bres, aid, bflat[bid])
+            np.add.at(bcnt, aid, 1)
+    wa = w_coh / float(aw * ah)
+    wb = w_comp / float(bw * bh)
+    v = (ares * wa + bres * wb) / (acnt * wa + bcnt * wb)[:, None]
+    out = np.trunc(v).astype(np.uint8).reshape(ah, aw, 3)
+    return (out, v.reshape(ah, aw, 3)) if want_float else out
+
+
+# ---------------------------------------------------------------- T1
+def local_stats(cnt_lab, stl_lab, eps, patch=3):
+    """transfer_color_downsample's closed form, ColorTransfer.cpp:1195-1250, with the prefix tables of build_accumTable_downsample (:425-455) and getValue
+    (:46-58) taken literally: 1-D int64 running sums over the row-major raster (table[0] = 0), and per window row y the difference table[y*w + ex] -
+    table[y*w + sx]. Window [x - 1, x + 2) x [y - 1, y + 2) clipped to the map. cnt_lab, stl_lab: level-size Lab u8 [h][w][3]. Returns (a, b) [h*w][3]:
+    a = sigma_stl / (sigma_cnt + eps), b = (mean_stl - mean_cnt * a) / 255."""
+    cnt = np.asarray(cnt_lab, np.uint8)
+    stl = np.asarray(stl_lab, np.uint8)
+    h, w = cnt.shape[:2]
+
+    def tables(img):
+        v = img.reshape(-1, 3).astype(np.int64)
+        t = np.zeros((h * w + 1, 3), np.int64)
+        t2 = np.zeros((h * w + 1, 3), np.int64)
+        t[1:] = np.cumsum(v, 0)
+        t2[1:] = np.cumsum(v * v, 0)
+        return t, t2
+
+    left = -(patch // 2)
+    right = patch + left
+    x = np.arange(w)[None, :] + 0 * np.arange(h)[:, None]
+    y = np.arange(h)[:, None] + 0 * np.arange(w)[None, :]
+    sx, sy = np.maximum(x + left, 0), np.maximum(y + left, 0)
+    ex, ey = np.minimum(x + right, w), np.minimum(y + right, h)
+    csum = ((ex - sx) * (ey - sy)).reshape(-1, 1).astype(np.float64)
+
+    def window(t):
+        val = np.zeros((h, w, 3), np.int64)
+        for k in range(patch):
+            row = sy + k
+            on = (row < ey)[..., None]
+            rr = np.minimum(row, h - 1)
+            val += np.where(on, t[rr * w + ex] - t[rr * w + sx], 0)
+        return val.reshape(-1, 3)
+
+    ct, ct2 = tables(cnt)
+    st, st2 = tables(stl)
+    cm = window(ct) / csum
+    cv = np.sqrt(np.maximum(window(ct2) / csum - cm * cm, 0.0))
+    sm = window(st) / csum
+    sv = np.sqrt(np.maximum(window(st2) / csum - sm * sm, 0.0))
+    a = sv / (cv + eps)
+    b = (sm - cm * a) * (1.0 / 255.0)
+    return a, b
+
+
+# ---------------------------------------------------------------- T2
+def err_weight(err):
+    """ColorTransfer.cpp:1302-1350: the matching error (float) is rescaled by its extremes — found with < and >, so NaNs never become one — and the confidence is
+    max(1 - e, 1e-6) with the Windows max macro ((a) > (b) ? (a) : (b)): a NaN first operand gives 1e-6. A constant map gives 0 / 0, so every weight is 1e-6."""
+    e = np.asarray(err, np.float32).reshape(-1).astype(np.float64)
+    mn, mx = 1e8, -1e8
+    fin = e[~np.isnan(e)]
+    if fin.size:
+        mn, mx = min(mn, fin.min()), max(mx, fin.max())
+    with np.errstate(invalid="ignore", divide="ignore"):
+        t = 1.0 - (e - mn) / (mx - mn)
+    return np.where(t > 1e-6, t, 1e-6)
+
+
+# ---------------------------------------------------------------- S1
+def gradient_weights(lab, h, w, lamda, alpha):
+    """compute_gradientMat, ColorTransfer.cpp:519-546 (the free function; the member :492-517 is the same formula on the full-resolution map): on channel 0,
+    gx = sqrt(lamda / (|L(x+1) - L(x)|^alpha + 1e-4)) where x + 1 is inside the map, else 0; gy likewise downwards. lab: [h*w][3] or [h][w][3] in [0, 1]."""
+    L = np.asarray(lab, np.float64).reshape(h, w, 3)[..., 0]
+    gx = np.zeros((h, w))
+    gy = np.zeros((h, w))
+    gx[:, :-1] = np.sqrt(lamda / (np.abs(L[:, 1:] - L[:, :-1]) ** alpha + 0.0001))
+    gy[:-1, :] = np.sqrt(lamda / (np.abs(L[1:, :] - L[:-1, :]) ** alpha + 0.0001))
+    return gx.reshape(-1), gy.reshape(-1)
+
+
+def s1_system(src, ref, weight, knn_id, knn_w, h, w, lamda, alpha, dweight, nonlocal_weight=2.0, k_num=8.0):
+    """solve_nonlocal_downsample_gpu_gradient, ColorTransfer.cpp:548-911: the rectangular least-squares system over the unknowns x = [a (n), b (n)] of one Lab
+    channel, per channel c a pair (A_c as scipy CSR, rhs_c). src, ref: level Lab in [0, 1], [n][3]; weight: the T2 confidence [n]; knn_id, knn_w: [n][k]
+    (zero-weight entries give zero rows). lamda, alpha, dweight arrive as float in the reference's signature and are rounded to float here; sqrt(dWeight) is the
+    float overload of C++ sqrt.
+      data term (:611-658):  sqrt(weight) * sqrt(dWeight) * (src_c a + b - ref_c)
+      local term (:660-848): for every pixel and each of its four neighbours present, g * (x_nb - x_px) for a and for b, g from gradient_weights of src — so
+                             every edge enters twice
+      nonlocal (:849-911):   sqrt(w_ij) * sqrt(nonlocal_weight / k_num) * (x_min(i,j) - x_max(i,j)) for a and for b"""
+    src = np.asarray(src, np.float64).reshape(-1, 3)
+    ref = np.asarray(ref, np.float64).reshape(-1, 3)
+    n = h * w
+    lamda, alpha = float(np.float32(lamda)), float(np.float32(alpha))
+    sq_dw = float(np.sqrt(np.float32(dweight)))
+    gx, gy = gradient_weights(src, h, w, lamda, alpha)
+    dw = np.sqrt(np.asarray(weight, np.float64).reshape(-1)) * sq_dw
+    idx = np.arange(n)
+    x, y = idx % w, idx // w
+    nrow = n                                       # data rows first: their values depend on the channel
+    # local rows: (minus col, plus col, weight) per edge occurrence, for part a and part b
+    lm, lp, lg = [], [], []
+    for cond, m_off, p_off, g in ((x + 1 < w, 0, 1, gx), (x - 1 >= 0, -1, 0, np.r_[0.0, gx[:-1]]),
+                                  (y + 1 < h, 0, w, gy), (y - 1 >= 0, -w, 0, np.r_[np.zeros(w), gy[:-w]] if n > w else np.zeros(n))):
+        i = idx[cond]
+        for part in (0, n):
+            lm.append(i + m_off + part); lp.append(i + p_off + part); lg.append(g[i])
+    lm, lp, lg = np.concatenate(lm), np.concatenate(lp), np.concatenate(lg)
+    ids = np.asarray(knn_id, np.int64).reshape(n, -1)
+    iw = (np.sqrt(np.asarray(knn_w, np.float64).reshape(n, -1)) * np.sqrt(nonlocal_weight / k_num)).reshape(-1)
+    i0 = np.repeat(idx, ids.shape[1])
+    i1 = ids.reshape(-1)
+    nm, npl, ng = [], [], []
+    for part in (0, n):
+        nm.append(np.minimum(i0, i1) + part); npl.append(np.maximum(i0, i1) + part); ng.append(iw)
+    nm, npl, ng = np.concatenate(nm), np.concatenate(npl), np.concatenate(ng)
+    nl_rows, nn_rows = lm.size, nm.size
+    r_loc = nrow + np.arange(nl_rows)
+    r_nl = nrow + nl_rows + np.arange(nn_rows)
+    m = nrow + nl_rows + nn_rows
+    out = []
+    for c in range(3):
+        rows = np.concatenate([idx, idx, r_loc, r_loc, r_nl, r_nl])
+        cols = np.concatenate([idx, idx + n, lm, lp, nm, npl])
+        vals = np.concatenate([dw * src[:, c], dw, -lg, lg, ng, -ng])
+        A = sp.csr_matrix((vals, (rows, cols)), shape=(m, 2 * n))
+        rhs = np.zeros(m)
+        rhs[:n] = dw * ref[:, c]
+        out.append((A, rhs))
+    return out
+
+
+def s1_cg(A, rhs, x0, maxit, tol=1e-6):
+    """solve_ls_cg_gpu, SparseSolver_GPU.cu:20-159: CG on the normal equations A^T A x = A^T rhs from x0 (Golub & Van Loan 10.2.6), stopped when r.r <= tol^2
+    or after maxit iterations; everything in float64 with A^T A formed explicitly. Returns (x, iterations)."""
+    AtA = (A.T @ A).tocsr()
+    r = A.T @ rhs - AtA @ x0
+    x = np.array(x0, np.float64, copy=True)
+    r1 = r @ r
+    r0 = 0.0
+    p = None
+    k = 1
+    while r1 > tol * tol and k <= maxit:
+        p = r.copy() if k == 1 else (r1 / r0) * p + r
+        Ap = AtA @ p
+        va = r1 / (p @ Ap)
+        x += va * p
+        r -= va * Ap
+        r0 = r1
+        r1 = r @ r
+        k += 1
+    return x, k - 1
+
+
+def s1_objective(A, rhs, x):
+    """f(x) = |A x - rhs|^2, the least-squares energy S1 decreases."""
+    d = A @ x - rhs
+    return float(d @ d)
+
+
+# ---------------------------------------------------------------- U1
+def _resize_coeffs(ssize, dsize, float_coeffs):
+    """cv::resize INTER_LINEAR along one axis (OpenCV's documented mapping): fx = (dx + 0.5) * (ssize / dsize) - 0.5, sx = floor(fx), fx -= sx; sx < 0 gives
+    (0, weight 0 on the right tap), sx >= ssize - 1 gives (ssize - 1, weight 0). float_coeffs: fx is computed and kept in float as OpenCV's tables do for 64F."""
+    scale = ssize / dsize
+    d = np.arange(dsize, dtype=np.float64)
+    fx = (d + 0.5) * scale - 0.5
+    if float_coeffs:
+        fx = fx.astype(np.float32)
+        sx = np.floor(fx).astype(np.int64)
+        fx = fx - sx.astype(np.float32)
+    else:
+        sx = np.floor(fx).astype(np.int64)
+        fx = fx - sx
+    lo = sx < 0
+    fx = np.where(lo, 0, fx); sx = np.where(lo, 0, sx)
+    hi = sx >= ssize - 1
+    fx = np.where(hi, 0, fx); sx = np.where(hi, ssize - 1, sx)
+    one = np.float32(1) if float_coeffs else 1.0
+    c0, c1 = (one - fx), fx
+    return sx, np.minimum(sx + 1, ssize - 1), np.asarray(c0, np.float64), np.asarray(c1, np.float64)
+
+
+def resize_linear_f64(img, dh, dw, float_coeffs=True):
+    """cv::resize(..., INTER_LINEAR) of a 64FC3 map [sh][sw][3] to [dh][dw][3]: horizontal pass S[sx] a0 + S[sx+1] a1, then vertical b0 S0 + b1 S1, in double
+    with OpenCV's float coefficient table (float_coeffs=True) or a pure float64 mapping (float_coeffs=False)."""
+    img = np.asarray(img, np.float64)
+    sh, sw = img.shape[:2]
+    x0, x1, a0, a1 = _resize_coeffs(sw, dw, float_coeffs)
+    y0, y1, b0, b1 = _resize_coeffs(sh, dh, float_coeffs)
+    hz = img[:, x0] * a0[None, :, None] + img[:, x1] * a1[None, :, None]
+    return hz[y0] * b0[:, None, None] + hz[y1] * b1[:, None, None]
+
+
+def roughness(ab_up, lab_full):
+    """upsample_color_coefficients_bilinear, ColorTransfer.cpp:457-489: per pixel the loop over channels overwrites the flag, so only the LAST channel decides:
+    1e-6 when L_2 a_2 + b_2 lies outside [0, 1], else 1. ab_up: [2][N][3]; lab_full: [N][3] in [0, 1]."""
+    ab = np.asarray(ab_up, np.float64)
+    lab = np.asarray(lab_full, np.float64).reshape(-1, 3)
+    nc = lab[:, 2] * ab[0][:, 2] + ab[1][:, 2]
+    return np.where((nc < 0) | (nc > 1), 1e-6, 1.0)
+
+
+# ---------------------------------------------------------------- S2
+def wls_system(lab_full, H, W, lamda, alpha, rough):
+    """solve_WLS_roughness_cpu, ColorTransfer.cpp:951-1125, with the member compute_gradientMat (:492-517) on channel 0 of the full-resolution Lab map: the
+    symmetric system diag(roughness) + the 4-neighbour Laplacian with edge weights gx^2, gy^2. Returns (diag, wx, wy) [H*W] (wx[i]: coupling of i and i + 1,
+    wy[i]: of i and i + W; the matrix holds -wx, -wy off the diagonal)."""
+    gx, gy = gradient_weights(lab_full, H, W, lamda, alpha)
+    wx, wy = gx ** 2, gy ** 2
+    d = np.asarray(rough, np.float64).reshape(-1).copy()
+    wx2, wy2 = wx.reshape(H, W), wy.reshape(H, W)
+    diag = d.reshape(H, W)
+    diag = diag + wx2
+    diag[:, 1:] += wx2[:, :-1]
+    diag = diag + wy2
+    diag[1:, :] += wy2[:-1, :]
+    return diag.reshape(-1), wx, wy
+
+
+def wls_matrix(diag, wx, wy, H, W):
+    n = H * W
+    i = np.arange(n)
+    hx = i[(i % W) + 1 < W]
+    vy = i[i + W < n]
+    rows = np.concatenate([i, hx, hx + 1, vy, vy + W])
+    cols = np.concatenate([i, hx + 1, hx, vy + W, vy])
+    vals = np.concatenate([diag, -wx[hx], -wx[hx], -wy[vy], -wy[vy]])
+    return sp.csc_matrix((vals, (rows, cols)), shape=(n, n))
+
+
+def wls_solve_exact(ab_up, lab_full, H, W, lamda, alpha, rough):
+    """The S2 solve (:1087-1099 and solve_direct_cpu): for each part and channel, M x = roughness * coefficient; a channel whose coefficients are all zero has a
+    zero right-hand side and is not solved (its result stays the zero-initialised buffer). Returns [2][N][3]."""
+    diag, wx, wy = wls_system(lab_full, H, W, lamda, alpha, rough)
+    lu = spla.splu(wls_matrix(diag, wx, wy, H, W))
+    ab = np.asarray(ab_up, np.float64)
+    out = np.zeros_like(ab)
+    r = np.asarray(rough, np.float64).reshape(-1)
+    for p in range(2):
+        for c in range(3):
+            if np.any(ab[p][:, c] != 0):
+                out[p][:, c] = lu.solve(r * ab[p][:, c])
+    return out
+
+
+# ---------------------------------------------------------------- A1
+def apply_coeffs(ab, lab_full):
+    """ColorTransfer.cpp:1440-1478: L a + b clamped to [0, 1] per channel, then convertTo(CV_8U, 255): saturate_cast of v * 255, i.e. cvRound (half to even).
+    Returns Lab u8 [N][3]; the Lab -> BGR step that follows is pinned elsewhere."""
+    ab = np.asarray(ab, np.float64)
+    lab = np.asarray(lab_full, np.float64).reshape(-1, 3)
+    v = np.minimum(np.maximum(lab * ab[0] + ab[1], 0.0), 1.0)
+    return np.rint(v * 255.0).astype(np.uint8)

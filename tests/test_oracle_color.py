@@ -176,6 +176,9 @@ def test_wls_matches_scipy_direct(oracle):
     a0 = rng.random((H * W, 3)); b0 = rng.random((H * W, 3)) - 0.5
     diag = np.empty(H * W); wx = np.empty(H * W); wy = np.empty(H * W)
     oracle.l.orc_wls_system(lab.reshape(-1), H, W, 0.37, 1.2, rough, diag, wx, wy)
+    import ref64                      # the assembly itself, restated from ColorTransfer.cpp:492-517 and :951-1125
+    for got, exp in zip((diag, wx, wy), ref64.wls_system(lab, H, W, 0.37, 1.2, rough)):
+        assert np.allclose(got, exp, rtol=1e-14, atol=0)
     n = H * W
     M = sp.lil_matrix((n, n))
     for i in range(n):
