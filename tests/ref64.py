@@ -1,7 +1,7 @@
 """float64 restatements of the reference's colour stage, votes and PatchMatch distances — an independent check of oracle/ and of the kernels.
 
-Every function is written from the reference sources (code/windows/neural_color_transfer/source/: GeneralizedPatchMatch.cu, ColorTransfer/ColorTransfer.cpp,
-ColorTransfer/SparseSolver_GPU.cu; line numbers in each docstring) and from OpenCV's documented cv::resize mapping — never from oracle/ or csrc/, and this module
+Every function is written from the reference sources (code/windows/neural_color_transfer/source/: main.cu, Classifier.cpp, GeneralizedPatchMatch.cu,
+ColorTransfer/ColorTransfer.cpp, ColorTransfer/SparseSolver_GPU.cu; line numbers in each docstring) and from OpenCV's documented cv::resize mapping — never from oracle/ or csrc/, and this module
 imports neither. It computes in float64 throughout, except where the reference itself computes in float32; there np.float32 emulates it.
 
 Conventions: an NNF entry packs a match as (y << 12) | x (GeneralizedPatchMatch.cu:24-34). Feature maps are CHW, images and Lab maps HWC. Colour coefficients are
@@ -11,6 +11,8 @@ import numpy as np
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
+VGG_MEAN_BGR = (103.939, 116.779, 123.68)          # Classifier.cpp:40
+
 
 def _xy(nnf):
     v = np.asarray(nnf, np.uint32).astype(np.int64)
@@ -19,6 +21,75 @@ def _xy(nnf):
 
 def _pack(x, y):
     return ((np.asarray(y, np.int64) << 12) | np.asarray(x, np.int64)).astype(np.uint32)
+
+
+# ---------------------------------------------------------------- V1, geometry
+def vgg19_taps(bgr, ws, bs, deepest=5):
+    """Classifier::Predict's VGG19 up to relu{deepest}_1, in float64 with torch.nn.functional on the CPU. Preprocess (Classifier.cpp:211-265): the u8 BGR image
+    converted to float and the per-channel mean subtracted by cv::subtract on a CV_32F map (the Scalar is taken to float, the difference rounded to float), no
+    scaling. Then conv1_1 .. conv5_1: every convolution 3x3, pad 1, followed by ReLU; a 2x2 stride-2 max pool after conv1_2, conv2_2, conv3_4 and conv4_4 in
+    Caffe's ceil mode (pooling_layer.cpp:90-93). ws[i]: [Cout][Cin][3][3], bs[i]: [Cout], i = 0 .. 12. Returns the taps relu1_1 .. relu{deepest}_1, CHW."""
+    import torch
+    import torch.nn.functional as F
+    img = np.asarray(bgr, np.uint8)
+    x = img.astype(np.float32) - np.asarray(VGG_MEAN_BGR, np.float32)
+    x = torch.from_numpy(np.ascontiguousarray(x.transpose(2, 0, 1), np.float64))[None]
+    pool_after = {1, 3, 7, 11}
+    tap_at = {0: 0, 2: 1, 4: 2, 8: 3, 12: 4}
+    taps = []
+    for i in range(13):
+        x = F.relu(F.conv2d(x, torch.from_numpy(np.asarray(ws[i], np.float64)), torch.from_numpy(np.asarray(bs[i], np.float64)), padding=1))
+        if i in tap_at:
+            taps.append(x[0].numpy().copy())
+            if len(taps) == deepest:
+                break
+        if i in pool_after:
+            x = F.max_pool2d(x, 2, 2, ceil_mode=True)
+    return taps
+
+
+def pool_out(n):
+    """pooling_layer.cpp:90-93 for kernel 2, stride 2, pad 0: ceil((n - 2) / 2) + 1"""
+    return int(np.ceil((n - 2) / 2.0)) + 1
+
+
+def level_geometry(H, W, RH, RW, nlayer=5):
+    """transfer_color_single_bds's per-level constants (main.cu:47-454), level 0 = conv5_1 (coarsest) .. 4 = conv1_1. Sizes: the feature maps' (data_C_size /
+    data_S_size, main.cu:94,102), the input halved by ceil pooling once per tap below; ah, aw for S (content, A), bh, bw for R (style, B). C: the tap's channels.
+    rs_range: PatchMatch's random-search radius (main.cu:77-83, maxLen over both images). knn_samples = 2^l (findKnns, main.cu:351-359); color_samples =
+    2^(numlayer - 1 - l) (main.cu:360-380)."""
+    maxLen = max(W, H, RW, RH)
+    rng = [maxLen // 16, maxLen // 32, maxLen // 64, 32, 32]
+    chans = [512, 512, 256, 128, 64]
+    out = []
+    for l in range(nlayer):
+        dims = []
+        for n in (H, W, RH, RW):
+            for _ in range(nlayer - 1 - l):
+                n = pool_out(n)
+            dims.append(n)
+        out.append(dict(ah=dims[0], aw=dims[1], bh=dims[2], bw=dims[3], C=chans[l], tap=nlayer - l, rs_range=rng[l],
+                        knn_samples=2 ** l, color_samples=2 ** (nlayer - 1 - l)))
+    return out
+
+
+# ---------------------------------------------------------------- N0, N1
+def normalize(feat):
+    """norm, GeneralizedPatchMatch.cu:237-283: every pixel's channel vector divided by its L2 norm (gemv of the squares, powx 0.5, div). No epsilon: a zero
+    vector gives 0 / 0 = NaN, as in the reference. feat: [C][h][w]; float64."""
+    f = np.asarray(feat, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return f / np.sqrt((f * f).sum(0))[None]
+
+
+def nnf_init(ah, aw, bh, bw):
+    """init_Ann_kernel, GeneralizedPatchMatch.cu:527-545: bx = min(int(float(ax) / float(aw - 1) * (bw - 1)), bw - 1), by likewise; float arithmetic (the int
+    bw - 1 is converted to float for the product), int() truncates. Needs aw, ah >= 2."""
+    ax = np.arange(aw, dtype=np.float32)
+    ay = np.arange(ah, dtype=np.float32)
+    bx = np.minimum((ax / np.float32(aw - 1) * np.float32(bw - 1)).astype(np.int64), bw - 1)
+    by = np.minimum((ay / np.float32(ah - 1) * np.float32(bh - 1)).astype(np.int64), bh - 1)
+    return _pack(np.broadcast_to(bx[None, :], (ah, aw)), np.broadcast_to(by[:, None], (ah, aw)))
 
 
 # ---------------------------------------------------------------- N2
@@ -347,6 +418,13 @@ def resize_linear_f64(img, dh, dw, float_coeffs=True):
     y0, y1, b0, b1 = _resize_coeffs(sh, dh, float_coeffs)
     hz = img[:, x0] * a0[None, :, None] + img[:, x1] * a1[None, :, None]
     return hz[y0] * b0[:, None, None] + hz[y1] * b1[:, None, None]
+
+
+def resize_linear_u8_exact(img, dh, dw):
+    """The float64 value cv::resize(..., INTER_LINEAR) approximates on a u8 image (main.cu:104-108 builds both pyramids with it), before OpenCV rounds to u8:
+    the centre mapping (x + 0.5) * s - 0.5 clamped at the borders, in float64 throughout. OpenCV's u8 path computes in fixed point and does not document its
+    rounding, so a comparison takes a bound below 1 LSB. img: [sh][sw][3] u8; returns [dh][dw][3] float64."""
+    return resize_linear_f64(np.asarray(img, np.uint8).astype(np.float64), dh, dw, float_coeffs=False)
 
 
 def roughness(ab_up, lab_full):

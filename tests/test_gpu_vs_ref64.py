@@ -28,23 +28,32 @@ def _chan(ab, c):
     return np.r_[ab[0][:, c], ab[1][:, c]]
 
 
-def _check_after_s1(oracle, gs, go, H, W, h, w, flab):
-    """U1, roughness, S2 and A1, each against ref64 applied to the GPU's previous stage. Returns the number of pixels where channel 0 or 1 leaves [0, 1] and
-    channel 2 does not (only the last channel decides the roughness)."""
+def _check_after_s1(oracle, gs, go, H, W, h, w, flab, form=None, step_bound=False):
+    """U1, roughness, S2 and A1, each against ref64 applied to the GPU's previous stage; form: the Lab -> BGR form of the run (oracle.lab2bgr). The upsampled
+    coefficients lie within 1e-7 relative of the pure float64 mapping, or — step_bound, for the large ratios of a whole pyramid (2x2 -> 17x17), where an
+    interpolant near zero between large coefficients breaks a relative bound — within what OpenCV's float table allows in each of the two passes: the float
+    source coordinate (half an ulp of the largest coordinate) times the largest step between neighbours, plus the float weights 1 - fx, fx (half an ulp of 1
+    each) times the largest coefficient; plus the 4 ulp above. Returns
+    the number of pixels where channel 0 or 1 leaves [0, 1] and channel 2 does not (only the last channel decides the roughness)."""
     if (h, w) != (H, W):
         for p in range(2):
             src = gs["ab_nonlocal"][p].reshape(h, w, 3)
             up = ref64.resize_linear_f64(src, H, W).reshape(-1, 3)
             assert _ulp_close(gs["ab_up"][p], up, 4), p
             up64 = ref64.resize_linear_f64(src, H, W, float_coeffs=False).reshape(-1, 3)
-            assert np.all(np.abs(gs["ab_up"][p] - up64) <= 1e-7 * np.abs(up64) + 1e-15), p
+            if step_bound:
+                step = max(np.abs(np.diff(src, axis=0)).max(initial=0), np.abs(np.diff(src, axis=1)).max(initial=0))
+                bound = 2 * (np.spacing(np.float32(max(h, w))) * step + np.spacing(np.float32(1)) * np.abs(src).max()) + 4 * np.spacing(np.abs(up64)) + 1e-15
+                assert np.all(np.abs(gs["ab_up"][p] - up64) <= bound), p
+            else:
+                assert np.all(np.abs(gs["ab_up"][p] - up64) <= 1e-7 * np.abs(up64) + 1e-15), p
     else:
         assert np.array_equal(gs["ab_up"], gs["ab_nonlocal"])
     assert np.array_equal(gs["roughness"], ref64.roughness(gs["ab_up"], flab))
     lam = 0.024 * (H * W) / (h * w) * (4 if (h, w) == (H, W) else 1)
     exact = ref64.wls_solve_exact(gs["ab_up"], flab, H, W, lam, 1.2, gs["roughness"])
     assert np.allclose(gs["ab_wls"], exact, rtol=2e-5, atol=2e-6)
-    assert np.array_equal(go, oracle.lab2bgr(ref64.apply_coeffs(gs["ab_wls"], flab).reshape(H, W, 3)))
+    assert np.array_equal(go, oracle.lab2bgr(ref64.apply_coeffs(gs["ab_wls"], flab).reshape(H, W, 3), form=form))
     nc = flab * gs["ab_up"][0] + gs["ab_up"][1]
     out = (nc < 0) | (nc > 1)
     return int((out[:, :2].any(1) & ~out[:, 2]).sum())
@@ -163,3 +172,109 @@ def test_votes_vs_ref64(ctx, C, dims, weights):
         gi = ctx.bds_vote_image(ia, ib, ann, bnn, wc, wp)
         ei, v = ref64.vote_image(ia, ib, ann, bnn, wc, wp, want_float=True)
         assert _vote_image_agrees(gi, ei, v), kind
+
+
+# ---------------------------------------------------------------- the chained loop (main.cu:47-454)
+# NCT_FLAG_FEAT16 bounds at the fp16-candidate levels (tests/levels_ref64.py): (vs the distance with the candidate map rounded to fp16, vs the exact distance).
+# Measured on both FEAT16 pairs below: at most 5.2e-6 (distances and seed bound in the fp16 metric) and 8.9e-5 (vs exact); the bounds leave about four and
+# five times that.
+FEAT16_TOL = (2e-5, 5e-4)
+
+
+@pytest.fixture(scope="module")
+def vgg():
+    from caffemodel_io import synthetic_vgg19
+    return synthetic_vgg19(19)
+
+
+def _pair_run(c, vgg, src, ref, bds=2.0, levels=5, flags=0):
+    import nct
+    c.vgg19_load_raw(*vgg)
+    prm = nct.Params.default(); prm.bds_weight = bds; prm.levels = levels; prm.flags = flags
+    c.pair_upload(src, ref)
+    lv = c.pair_run_levels(src.shape, ref.shape, prm, want_color=True)
+    assert np.array_equal(c.pair_download(), lv["result"][levels - 1]), "the final image is not the last level's result"
+    return lv
+
+
+def _check_pair(c, oracle, vgg, src, ref, bds, tag, levels=5, **kw):
+    import levels_ref64
+    lv = _pair_run(c, vgg, src, ref, bds, levels, kw.pop("flags", 0))
+    stats = levels_ref64.check_levels(lv, src, ref, *vgg, bds, c.resize_u8c3, levels=levels, oracle=oracle, **kw)
+    print("ref64-levels", tag, {k: float("%.3g" % v) for k, v in stats.items()})
+    return lv, stats
+
+
+def _standin_crop():
+    """160x200 crops of the in4 / tar4 stand-ins: regions of one colour, i.e. kNN hubs, at full resolution"""
+    import os
+    import natural_inputs
+    from PIL import Image
+    d = natural_inputs.require()
+    im = [np.asarray(Image.open(os.path.join(d, n + ".png")).convert("RGB"))[..., ::-1] for n in ("in4", "tar4")]
+    return np.ascontiguousarray(im[0][4:164, 16:216]), np.ascontiguousarray(im[1][10:170, 30:230])
+
+
+@pytest.mark.parametrize("case", __import__("test_ref64_oracle").PAIR_CASES)
+def test_pair_levels_vs_ref64_gpu(ctx, oracle, vgg, case):
+    """Every level of the GPU pair against ref64 recomputed from the two input images (tests/levels_ref64.py), colour stages included: T1, S1 at the cap on the
+    kNN graph rebuilt from the dumped labels with samples = 2^l, resize, roughness, S2, the result."""
+    from test_ref64_oracle import pair_images
+    src, ref = pair_images(case)
+    _check_pair(ctx, oracle, vgg, src, ref, case[2], case[:3])
+
+
+def test_pair_levels_vs_ref64_standin_crop(ctx, oracle, vgg):
+    import nct
+    src, ref = _standin_crop()
+    _check_pair(ctx, oracle, vgg, src, ref, 2.0, "standin")
+    hub = ctx.counter(nct.CTR_S1_HUB_BLOCKS_L0 + 4)
+    assert hub > 0 or hub == -1, f"the crop is meant to have kNN hubs at the finest level ({hub})"
+
+
+def test_pair_levels_vs_ref64_dead_feature_pixels(ctx, oracle, vgg):
+    """test_gpu_pipeline.py::test_pair_with_dead_feature_pixels_matches_oracle's pair: conv1_1 answers 0 in every channel inside a black rectangle of R, so the
+    normalised map holds NaN there and the distances of patches touching it are NaN — at the same pixels as ref64's."""
+    ws, bs = [w.copy() for w in vgg[0]], [b.copy() for b in vgg[1]]
+    mean = np.asarray(ref64.VGG_MEAN_BGR, np.float32)
+    bs[0] = (-(ws[0].sum(axis=(2, 3)) * (-mean)[None, :]).sum(1) - 1.0).astype(np.float32)
+    src, ref = synth.image(1000, 96, 80), synth.image(1001, 72, 104)
+    ref[20:30, 30:44] = 0
+    lv, _ = _check_pair(ctx, oracle, (ws, bs), src, ref, 2.0, "dead")
+    assert np.isnan(lv["bnnd"][4]).any(), "R -> S queries inside the dead region keep a NaN distance"
+
+
+def test_pair_levels_vs_ref64_bds8_and_partial(ctx, oracle, vgg):
+    """bds_weight 8 (completeness ahead of coherence), and a run of three levels (nct_params.levels) whose last result is the final image"""
+    _check_pair(ctx, oracle, vgg, synth.image_flat(1000, 112, 96), synth.image_flat(1001, 80, 128), 8.0, "bds8")
+    _check_pair(ctx, oracle, vgg, synth.image(11, 88, 72), synth.image(12, 64, 96), 2.0, "levels3", levels=3)
+
+
+def test_pair_levels_vs_ref64_s1_short(oracle, vgg, monkeypatch):
+    """NCT_S1_MAXIT=2: at every level S1's iterate equals ref64's literal CGNR over two iterations from the dumped T1 guess (1e-10, as in
+    test_s1_short_runs_vs_literal_cg) — a tight check of the graph, weights and sizes the pipeline hands to S1."""
+    import nct
+    from test_ref64_oracle import PAIR_CASES, pair_images
+    monkeypatch.setenv("NCT_S1_MAXIT", "2")
+    src, ref = pair_images(PAIR_CASES[0])
+    with nct.Context(0) as c:
+        _check_pair(c, oracle, vgg, src, ref, PAIR_CASES[0][2], "s1_maxit2", s1_maxit=2)
+
+
+def test_pair_levels_vs_ref64_feat16(ctx, oracle, vgg):
+    """NCT_FLAG_FEAT16, which the oracle does not model: at the C >= 256 levels the distances are those of fp16 candidate tiles (FEAT16_TOL), elsewhere and in
+    every other check the fp32 bounds hold"""
+    import nct
+    from test_ref64_oracle import PAIR_CASES, pair_images
+    for tag, (src, ref) in (("feat16", pair_images(PAIR_CASES[0])), ("feat16_standin", _standin_crop())):
+        _check_pair(ctx, oracle, vgg, src, ref, 2.0, tag, flags=nct.FLAG_FEAT16, feat16=FEAT16_TOL)
+
+
+def test_pair_levels_vs_ref64_lab2bgr_cube(ctx, oracle, vgg):
+    """NCT_FLAG_LAB2BGR_CUBE: every level's result is the plain-cube Lab -> BGR form of ref64's coefficients applied to the source"""
+    import nct
+    from test_ref64_oracle import PAIR_CASES, pair_images
+    src, ref = pair_images(PAIR_CASES[0])
+    lv, _ = _check_pair(ctx, oracle, vgg, src, ref, 2.0, "cube", flags=nct.FLAG_LAB2BGR_CUBE, lab2bgr_form=1)
+    base = _pair_run(ctx, vgg, src, ref)
+    assert not np.array_equal(lv["result"][4], base["result"][4]), "the cube form is meant to change some pixel of this pair"

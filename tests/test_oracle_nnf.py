@@ -4,6 +4,7 @@ oracle/README.md ("parity unpinned"); these tests pin the restatement against th
 GeneralizedPatchMatch.cu as read by hand."""
 import numpy as np
 import pytest
+import ref64
 import synth
 
 
@@ -38,6 +39,7 @@ def test_nnf_init_matches_numpy_restatement(oracle):
         by = np.minimum((ay / np.float32(ah - 1) * np.float32(bh - 1)).astype(np.int32), bh - 1)
         assert np.array_equal(X(nnf), np.broadcast_to(bx, (ah, aw)))
         assert np.array_equal(Y(nnf), np.broadcast_to(by[:, None], (ah, aw)))
+        assert np.array_equal(nnf, ref64.nnf_init(ah, aw, bh, bw))
 
 
 @pytest.mark.parametrize("dims", [(44, 44, 88, 88), (88, 88, 175, 175), (29, 43, 57, 85), (57, 85, 113, 170), (16, 16, 32, 32)])

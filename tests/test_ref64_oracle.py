@@ -253,3 +253,41 @@ def test_wls_zero_rhs_is_skipped(oracle):
     oracle.l.orc_wls_solve(a.reshape(-1), b.reshape(-1), np.ascontiguousarray(lab).reshape(-1), H, W, 0.37, 1.2, rough, 0)
     assert np.all(exp[0][:, 1] == 0) and np.all(exp[1][:, 2] == 0) and np.all(a[:, 1] == 0) and np.all(b[:, 2] == 0)
     assert np.allclose(np.stack([a, b]), exp, rtol=1e-8, atol=1e-10)
+
+
+# ---------------------------------------------------------------- the chained loop (main.cu:47-454)
+# (source size, reference size, bds_weight, image kind): the pyramid ratios of the second and third pairs are odd at every level (17 -> 9 -> 5 -> 3 -> 2,
+# 400 -> 200 -> 100 -> 50 -> 25, 23 -> 12 -> 6 -> 3 -> 2); the second's coarsest level is 2x2 against 2x2 (the smallest the pipeline accepts)
+PAIR_CASES = [((96, 80), (72, 104), 2.0, "flat"), ((17, 17), (23, 31), 2.0, "cos"), ((17, 400), (40, 23), 0.0, "cos")]
+
+
+def pair_images(case):
+    (sh, sw), (rh, rw), _, kind = case
+    mk = synth.image_flat if kind == "flat" else synth.image
+    return mk(1000, sh, sw), mk(1001, rh, rw)
+
+
+@pytest.mark.parametrize("case", PAIR_CASES)
+def test_pair_levels_vs_ref64(oracle, case):
+    """Every level of the oracle's whole pair against ref64 recomputed from the two input images: pyramid, features (R from the reference image, S from the
+    source and then from the previous level's result), distances at the dumped matches, seed bound, guidance image and matching error (tests/levels_ref64.py)."""
+    import levels_ref64
+    from caffemodel_io import synthetic_vgg19
+    ws, bs = synthetic_vgg19(19)
+    src, ref = pair_images(case)
+    bds = case[2]
+    _, lv = oracle.process_pair(src, ref, ws, bs, dict(bds_weight=bds), want_nnf=True)
+    geo = ref64.level_geometry(*src.shape[:2], *ref.shape[:2])
+    assert geo[0]["ah"] >= 2 and geo[0]["aw"] >= 2
+    # the colour stage's inputs: each level's result must be the oracle's composed colour level run on that level's S image, guidance image and matching
+    # error, with the kNN graph of samples = 2^l (main.cu:351-359) over the k-means labels and layer l; then its stages against ref64 as for the GPU
+    labels, _ = oracle.cluster_features(oracle.vgg19_features(src, ws, bs, 5)[4], 10, 11, 1)
+    spyr, _ = levels_ref64.chain_pyramid(src, [(g["ah"], g["aw"]) for g in geo], oracle.resize_u8c3)
+    lv["labels"], lv["color"] = labels, []
+    for l in range(5):
+        ids, kw = oracle.knn_graph(oracle.bgr2lab(spyr[l]), labels, int(labels.max()) + 1, geo[l]["knn_samples"])
+        out, st = oracle.local_color_transfer(lv["err"][l], spyr[l], lv["guide"][l], src, ids, kw, l, want_stages=True)
+        assert np.array_equal(out, lv["result"][l]), f"level {l}: the result is not the colour stage of the level's inputs"
+        lv["color"].append(st)
+    stats = levels_ref64.check_levels(lv, src, ref, ws, bs, bds, oracle.resize_u8c3, oracle=oracle)
+    print("pair", case, {k: float("%.3g" % v) for k, v in stats.items()})
