@@ -25,6 +25,9 @@ import ref64
 from test_ref64_oracle import _ulp_close, _vote_image_agrees
 
 TOL = 2e-6
+# the float VGG's conv5_1 moved a float L2 distance between normalised features by at most 3.5e-6 relative from ref64's float64 taps (measured with
+# synthetic_vgg19(19) on the sources of PAIR_CASES, the stand-in crop, and the bds8 / levels3 pairs, whose margins were 1.7e-3 .. 3.4e-2); the bar leaves 14x
+KM_VGG_MARGIN = 5e-5
 FP16_MIN_C = 256          # nct_pipeline.cpp: pm_mode = NCT_PM_FP16 for C >= 256 under NCT_FLAG_FEAT16
 
 
@@ -65,11 +68,13 @@ def chain_pyramid(img, sizes, resize):
     return pyr, worst
 
 
-def check_levels(dumps, src, ref, ws, bs, bds_weight, resize, levels=5, feat16=None, oracle=None, s1_maxit=None, lab2bgr_form=None):
-    """Runs checks 1-5 at every level that ran (and 6 when `dumps` holds "color"; `oracle` supplies bgr2lab / knn_graph / lab2bgr). resize: the library's
-    resize_u8c3 (oracle's or GPU's, whichever made the dumps). s1_maxit: NCT_S1_MAXIT of the run — S1's iterate must then equal ref64's literal CGNR from the
+def check_levels(dumps, src, ref, ws, bs, bds_weight, lib, levels=5, feat16=None, s1_maxit=None, lab2bgr_form=None):
+    """Runs checks 1-5 at every level that ran (and 6 when `dumps` holds "color"). lib: the library that made the dumps (the oracle or an nct.Context); its
+    resize_u8c3 builds the pyramids (each step checked against the exact bilinear value), its bgr2lab the Lab bytes and its lab2bgr the expected result image —
+    both conversions are pinned to ref64 over all 2^24 inputs (tests/test_ref64_oracle.py::check_bgr2lab_all, check_lab2bgr_all). The kNN graph is ref64's,
+    over the dumped labels, which must be ref64.kmeans_labels of the source's float64 conv5_1 (with a margin of KM_VGG_MARGIN). s1_maxit: NCT_S1_MAXIT of the run — S1's iterate must then equal ref64's literal CGNR from the
     dumped T1 guess to 1e-10. lab2bgr_form: the Lab -> BGR form the run used (1 under NCT_FLAG_LAB2BGR_CUBE). Returns {check: largest deviation}."""
-    from test_gpu_vs_ref64 import _chan, _check_after_s1
+    from test_gpu_vs_ref64 import _chan, _check_after_s1, _lab2bgr_of
     from test_ref64_oracle import S1_CAP_RATIO
     src, ref = np.asarray(src, np.uint8), np.asarray(ref, np.uint8)
     H, W = src.shape[:2]
@@ -80,12 +85,20 @@ def check_levels(dumps, src, ref, ws, bs, bds_weight, resize, levels=5, feat16=N
     def note(k, v):
         stats[k] = max(stats.get(k, -np.inf), v)
 
+    resize = lib.resize_u8c3
     spyr, ds = chain_pyramid(src, [(g["ah"], g["aw"]) for g in geo], resize)
     rpyr, dr = chain_pyramid(ref, [(g["bh"], g["bw"]) for g in geo], resize)
     note("pyramid", max(ds, dr))
     rtaps = ref64.vgg19_taps(ref, ws, bs, 5)
     s_raw = ref64.vgg19_taps(src, ws, bs, 5)[4]
-    flab = oracle.bgr2lab(src).reshape(-1, 3) / 255.0 if "color" in dumps else None
+    flab = None
+    if "color" in dumps:
+        flab = lib.bgr2lab(src).reshape(-1, 3) / 255.0
+        # C1: the labels the colour stages used are the k-means of the source's conv5_1, here computed in float64 from the image alone
+        el, en, margin = ref64.kmeans_labels(s_raw, 10, 11, 1)
+        assert margin >= KM_VGG_MARGIN, f"k-means margin {margin:.3g}: the pair cannot tell a label error from the float VGG's rounding"
+        assert int(dumps["labels"].max()) + 1 == en and np.array_equal(dumps["labels"], el), "labels differ from ref64.kmeans_labels"
+        note("km_margin_min", -margin)
     for l in range(levels):
         g = geo[l]
         ah, aw, bh, bw, C = g["ah"], g["aw"], g["bh"], g["bw"], g["C"]
@@ -136,9 +149,9 @@ def check_levels(dumps, src, ref, ws, bs, bds_weight, resize, levels=5, feat16=N
         # 6. colour stage
         if "color" in dumps:
             gs = dumps["color"][l]
-            slab_u8, glab_u8 = oracle.bgr2lab(spyr[l]), oracle.bgr2lab(dumps["guide"][l])
+            slab_u8, glab_u8 = lib.bgr2lab(spyr[l]), lib.bgr2lab(dumps["guide"][l])
             labels = dumps["labels"]
-            ids, kw = oracle.knn_graph(slab_u8, labels, int(labels.max()) + 1, g["knn_samples"])
+            ids, kw = ref64.knn_graph(slab_u8, labels, int(labels.max()) + 1, g["knn_samples"])
             ea, eb = ref64.local_stats(slab_u8, glab_u8, 0.60)
             assert _ulp_close(gs["ab_local"][0], ea, 2) and _ulp_close(gs["ab_local"][1], eb, 2), f"level {l}: T1"
             slab, glab = slab_u8.reshape(-1, 3) / 255.0, glab_u8.reshape(-1, 3) / 255.0
@@ -161,5 +174,5 @@ def check_levels(dumps, src, ref, ws, bs, bds_weight, resize, levels=5, feat16=N
                     assert S1_CAP_RATIO[0] <= fg / fr <= S1_CAP_RATIO[1] or abs(fg - fr) <= 1e-4 * (f0 - fr), (l, c, f0, fg, fr)
                     note("s1_ratio_dev", abs(fg / fr - 1.0))
                     note("s1_rel_descent_dev", abs(fg - fr) / (f0 - fr))
-            _check_after_s1(oracle, gs, dumps["result"][l], H, W, ah, aw, flab, form=lab2bgr_form, step_bound=True)
+            _check_after_s1(_lab2bgr_of(lib), gs, dumps["result"][l], H, W, ah, aw, flab, form=lab2bgr_form, step_bound=True)
     return stats

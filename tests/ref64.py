@@ -487,3 +487,307 @@ def apply_coeffs(ab, lab_full):
     lab = np.asarray(lab_full, np.float64).reshape(-1, 3)
     v = np.minimum(np.maximum(lab * ab[0] + ab[1], 0.0), 1.0)
     return np.rint(v * 255.0).astype(np.uint8)
+
+
+def bgr2lab(bgr_u8):
+    """CV_BGR2Lab on 8-bit input (main.cu:352,371; ColorTransfer.h:58) by OpenCV's documented mapping, in float64 without its tables: sRGB gamma
+    (v <= 0.04045: v / 12.92, else ((v + 0.055) / 1.055)^2.4), the D65 matrix, X / Xn and Z / Zn, f(t) = t^(1/3) above 0.008856 and 7.787 t + 16/116 below,
+    L = 116 Y^(1/3) - 16 (903.3 Y below 0.008856), a = 500 (f(X) - f(Y)), b = 200 (f(Y) - f(Z)); then the 8-bit scaling L * 255/100, a + 128, b + 128.
+    OpenCV's 8-bit path quantises linear light to 1/2040 (sRGBGammaTab_b) and the cube root to a table (LabCbrtTab_b), so it differs from this, most in dark
+    colours. Returns (Lab u8 [..., 3] rounded half to even and saturated, the unrounded float64 values)."""
+    v = np.asarray(bgr_u8, np.uint8).astype(np.float64) / 255.0
+    lin = np.where(v <= 0.04045, v / 12.92, ((v + 0.055) / 1.055) ** 2.4)
+    B, G, R = lin[..., 0], lin[..., 1], lin[..., 2]
+    X = (0.412453 * R + 0.357580 * G + 0.180423 * B) / 0.950456
+    Y = 0.212671 * R + 0.715160 * G + 0.072169 * B
+    Z = (0.019334 * R + 0.119193 * G + 0.950227 * B) / 1.088754
+
+    def f(t):
+        return np.where(t > 0.008856, np.cbrt(t), 7.787 * t + 16.0 / 116.0)
+
+    L = np.where(Y > 0.008856, 116.0 * np.cbrt(Y) - 16.0, 903.3 * Y)
+    val = np.stack([L * 255.0 / 100.0, 500.0 * (f(X) - f(Y)) + 128.0, 200.0 * (f(Y) - f(Z)) + 128.0], -1)
+    return np.clip(np.rint(val), 0, 255).astype(np.uint8), val
+
+
+def lab2bgr(lab_u8, form):
+    """CV_Lab2BGR on 8-bit input (ColorTransfer.cpp:1469): L_u8 * 100/255, a - 128, b - 128, the float Lab2RGB_f in float64 without tables (exact sRGB gamma),
+    saturate_cast<uchar>(v * 255). The two forms of Lab2RGB_f in OpenCV's history:
+      form 0 (piecewise): CIE's linear branch below L* = 8 (Y = L / 903.3) and below f = 6/29 ((f - 16/116) / 7.787); linear RGB clipped to [0, 1];
+      form 1 (plain cubes): fY = (L + 16) / 116, fX = fY + a / 500, fZ = fY - b / 200, each cubed; linear RGB not clipped before the gamma table.
+    Returns (BGR u8-valued float64 [n][3], far_out [n][3]): far_out marks, in the cube form only, channels far below the gamut (linear value < -0.02), where
+    OpenCV's spline table is extrapolated hundreds of steps and its cubic term takes over — a saturated byte (0 or 255) this function does not model."""
+    lab = np.asarray(lab_u8).reshape(-1, 3)
+    L = lab[:, 0].astype(np.float64) * 100 / 255; a = lab[:, 1].astype(np.float64) - 128; b = lab[:, 2].astype(np.float64) - 128
+    if form == 1:
+        fy = (L + 16) / 116
+        y, X, Z = fy ** 3, (fy + a / 500) ** 3 * 0.950456, (fy - b / 200) ** 3 * 1.088754
+    else:
+        fy = np.where(L <= 0.008856 * 903.3, 7.787 * (L / 903.3) + 16 / 116, (L + 16) / 116)
+        y = np.where(L <= 0.008856 * 903.3, L / 903.3, fy ** 3)
+        finv = lambda f: np.where(f <= 7.787 * 0.008856 + 16 / 116, (f - 16 / 116) / 7.787, f ** 3)
+        X, Z = finv(a / 500 + fy) * 0.950456, finv(fy - b / 200) * 1.088754
+    M = np.array([[3.240479, -1.53715, -0.498535], [-0.969256, 1.875991, 0.041556], [0.055648, -0.204043, 1.057311]])
+    rgb = np.stack([X, y, Z], 1) @ M.T
+    far_out = rgb[:, ::-1] < -0.02
+    if form == 0:
+        rgb = np.clip(rgb, 0, 1)
+    srgb = np.where(rgb <= 0.0031308, 12.92 * rgb, 1.055 * np.maximum(rgb, 0) ** (1 / 2.4) - 0.055)
+    return np.clip(np.rint(srgb[:, ::-1] * 255), 0, 255), (far_out if form == 1 else np.zeros_like(far_out))
+
+
+# ---------------------------------------------------------------- C1
+def _perm_splitmix(n, seed):
+    """SPEC.md §4's stand-in for MSVC rand() in UniqueRandom: the Fisher-Yates permutation of 0 .. n-1 driven by SplitMix64 from `seed` — for i = n-1 down to 1,
+    j = next() mod (i + 1), swap(perm[i], perm[j])."""
+    M = (1 << 64) - 1
+    perm = list(range(n))
+    x = seed & M
+    for i in range(n - 1, 0, -1):
+        x = (x + 0x9E3779B97F4A7C15) & M
+        z = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M
+        j = (z ^ (z >> 31)) % (i + 1)
+        perm[i], perm[j] = perm[j], perm[i]
+    return perm
+
+
+def _l2_float(pts, centres, chunk=256):
+    """cvflann::L2<float>::operator() (Flann/dist.h:153-181) of float points [n][C] against centres [K][C] (float or double): each difference is taken in the
+    wider type and converted to float, the four squares of a group summed left to right in float and added to a float accumulator group by group; a tail of
+    C mod 4 terms one at a time. Returns float32 [n][K], emulated exactly with np.float32 (np.add.accumulate adds sequentially)."""
+    p = np.asarray(pts, np.float32)
+    c = np.asarray(centres)
+    wide = np.float64 if c.dtype == np.float64 else np.float32
+    n, C = p.shape
+    g = C - C % 4
+    out = np.empty((n, c.shape[0]), np.float32)
+    cw = c.astype(wide)
+    for s0 in range(0, n, chunk):
+        d = (p[s0:s0 + chunk, None, :].astype(wide) - cw[None]).astype(np.float32)
+        q = d * d
+        if g:
+            q4 = q[..., :g].reshape(q.shape[0], q.shape[1], g // 4, 4)
+            grp = ((q4[..., 0] + q4[..., 1]) + q4[..., 2]) + q4[..., 3]
+            acc = np.add.accumulate(grp, axis=-1, dtype=np.float32)[..., -1]
+        else:
+            acc = np.zeros(q.shape[:2], np.float32)
+        for i in range(g, C):
+            acc = acc + q[..., i]
+        out[s0:s0 + chunk] = acc
+    return out
+
+
+def kmeans_labels(feat_chw, K=10, iters=11, seed=1, exact=False, normalized=False, want_info=False):
+    """clusterFeastures (ColorTransfer.cpp:355-395): cvflann::hierarchicalClustering<L2<float>> with KMeansIndexParams(K, 11, FLANN_CENTERS_RANDOM) on the
+    normalised conv5_1 features (normalize, rounded to the float buffer the reference clusters); the labels are the root's split, computeClustering
+    (Flann/kmeans_index.h:700-880):
+      - n < K, or fewer than K distinct centres found, leaves the root a leaf: one label (:705-710, :716-722);
+      - chooseCentersRandom (:108-135): candidates in the order of _perm_splitmix (SPEC.md §4), skipping one whose float distance to an earlier centre is
+        below 1e-16;
+      - assignment: the first centre, then each later one if strictly nearer (sq_dist > new_sq_dist: ties go to the lower id), distances _l2_float against
+        the double centres; the radius of a cluster is its largest such distance;
+      - up to `iters` Lloyd steps while any label changes: centres are double sums in ascending point order divided by the count; a cluster left empty takes
+        the first point (ascending) of the next cluster with more than one member whose distance equals that cluster's radius, and the step is not converged.
+    exact: distances in float64 instead (to confirm the float emulation where the margin is large). normalized: feat_chw is already the normalised float map
+    (taken as is). want_info: also return {"steps": Lloyd steps run, "converged": bool, "donors": empty-cluster moves}. Returns (labels [h][w] int32, number of labels, margin):
+    margin is the smallest relative gap (second - best) / second between the nearest and second-nearest centre over all points and assignment passes, and,
+    where a donor moved, between the radius and the next distance in the donor cluster — how far a perturbation of the inputs can go before a label flips."""
+    f = np.asarray(feat_chw, np.float32) if normalized else normalize(feat_chw).astype(np.float32)
+    C, h, w = f.shape
+    info = {"steps": 0, "converged": False, "donors": 0}
+    done = (lambda *r: r + (info,)) if want_info else (lambda *r: r)
+    n = h * w
+    pts = np.ascontiguousarray(f.reshape(C, n).T)
+    labels = np.zeros(n, np.int32)
+    if n < K:
+        return done(labels.reshape(h, w), 1, np.inf)
+    dist = (lambda p, c: ((p.astype(np.float64)[:, None, :] - np.asarray(c, np.float64)[None]) ** 2).sum(-1)) if exact else _l2_float
+    perm = _perm_splitmix(n, seed)
+    cidx, pos = [], 0
+    while len(cidx) < K:
+        if pos >= n:
+            return done(labels.reshape(h, w), 1, np.inf)
+        cand = perm[pos]; pos += 1
+        if cidx and (_l2_float(pts[cand:cand + 1], pts[cidx]) < 1e-16).any():
+            continue
+        cidx.append(cand)
+    centres = pts[cidx].astype(np.float64)
+    margin = np.inf
+
+    def assign(centres):
+        d = dist(pts, centres)
+        lab = np.argmin(d, 1).astype(np.int32)               # first minimum = the lower id on ties, as the strict > does
+        best = d[np.arange(n), lab]
+        two = np.partition(d, 1, axis=1)[:, :2].astype(np.float64)
+        gap = (two[:, 1] - two[:, 0]) / np.where(two[:, 1] > 0, two[:, 1], 1.0)
+        return lab, best, float(gap.min())
+
+    bel, best, m = assign(centres)
+    margin = min(margin, m)
+    count = np.bincount(bel, minlength=K)
+    for _ in range(iters):
+        info["steps"] += 1
+        centres = np.zeros((K, C))
+        for i in range(K):                                   # double sums in ascending point order (np.cumsum adds sequentially)
+            if count[i]:
+                centres[i] = np.cumsum(pts[bel == i].astype(np.float64), 0)[-1]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            centres /= count[:, None]
+        new, best, m = assign(centres)
+        margin = min(margin, m)
+        radius = np.zeros(K, best.dtype)
+        np.maximum.at(radius, new, best)
+        converged = np.array_equal(new, bel)
+        bel = new
+        count = np.bincount(bel, minlength=K)
+        for i in range(K):
+            if count[i] == 0:
+                j, tries = (i + 1) % K, 0
+                while count[j] <= 1 and tries < K:           # the reference spins forever when no cluster can give
+                    j, tries = (j + 1) % K, tries + 1
+                if count[j] <= 1:
+                    continue
+                dj = dist(pts, centres[j:j + 1])[:, 0]
+                mem = np.flatnonzero(bel == j)
+                far = np.flatnonzero(dj[mem] == radius[j])     # none when an earlier move this step took cluster j's farthest point
+                if far.size:
+                    rest = np.sort(dj[mem])[::-1]
+                    if rest.size > 1 and rest[0] > 0:
+                        margin = min(margin, float((rest[0] - rest[1]) / rest[0]))
+                    kk = mem[far[0]]
+                    bel[kk] = i; count[j] -= 1; count[i] += 1
+                    info["donors"] += 1
+                converged = False
+        if converged:
+            info["converged"] = True
+            break
+    return done(bel.reshape(h, w), K, margin)
+
+
+# ---------------------------------------------------------------- K1
+def cluster_members(labels, nlabels):
+    """getClusters (ColorTransfer.cpp:273-330) on the label grid: cell (x, y) joins its own label's cluster and the cluster of every 4-neighbour whose label
+    differs (the neighbour's cell is marked in the cell's cluster). Returns member [nlabels][lh][lw] bool."""
+    lab = np.asarray(labels, np.int64)
+    lh, lw = lab.shape
+    mem = np.zeros((nlabels, lh, lw), bool)
+    yy, xx = np.mgrid[0:lh, 0:lw]
+    mem[lab, yy, xx] = True
+    for dy, dx in ((0, 1), (0, -1), (1, 0), (-1, 0)):
+        ys, xs = yy + dy, xx + dx
+        ok = (ys >= 0) & (ys < lh) & (xs >= 0) & (xs < lw)
+        ok[ok] &= lab[ys[ok], xs[ok]] != lab[ok]
+        mem[lab[ok], ys[ok], xs[ok]] = True
+    return mem
+
+
+def _cluster_top(key, ids, col, k):
+    """The first k + 1 (distance, id) pairs of every distinct colour of one cluster over all its members, self included (the query's own colour at distance
+    0). key: packed 24-bit colours of the members, ids: their pixel ids, col: their Lab bytes. Returns (colour index per member, top ids [m][k+1] padded -1,
+    top distances [m][k+1] padded inf)."""
+    from scipy.spatial import cKDTree
+    order = np.lexsort((ids, key))
+    key, ids, col = key[order], ids[order], col[order]
+    uk, first, inv, cnt = np.unique(key, return_index=True, return_inverse=True, return_counts=True)
+    uc = col[first].astype(np.int64)
+    m = uk.size
+    kk = min(k + 1, m)
+    # each colour's first k + 1 pixel ids (ascending): no colour contributes more
+    take = np.minimum(cnt, k + 1)
+    rank = np.arange(key.size) - first[inv]
+    sel = rank < k + 1
+    cid = np.full((m, k + 1), -1, np.int64)
+    cid[inv[sel], rank[sel]] = ids[sel]
+    # D: the largest integer squared distance among the k + 1 nearest distinct colours; every colour with integer squared distance <= D is a candidate
+    tree = cKDTree(uc.astype(np.float64))
+    _, nn = tree.query(uc.astype(np.float64), k=kk)
+    nn = nn.reshape(m, kk)
+    D = ((uc[nn] - uc[:, None, :]) ** 2).sum(-1).max(1)
+    balls = tree.query_ball_point(uc.astype(np.float64), np.sqrt(D) + 1e-6, return_sorted=False)
+    ln = np.fromiter((len(b) for b in balls), np.int64, m)
+    q = np.repeat(np.arange(m), ln)
+    c = np.concatenate([np.asarray(b, np.int64) for b in balls])
+    keep = ((uc[c] - uc[q]) ** 2).sum(-1) <= D[q]
+    q, c = q[keep], c[keep]
+    # PointColor::kdtree_distance (ColorTransfer.cpp:20-27) on convertTo(CV_64F, 1/255) values (main.cu:355-356)
+    lab = uc.astype(np.float64) * (1.0 / 255.0)
+    dv = lab[c] - lab[q]
+    d = np.maximum(np.sqrt(dv[:, 0] * dv[:, 0] + dv[:, 1] * dv[:, 1] + dv[:, 2] * dv[:, 2]), 0.0)
+    # expand every candidate colour to its first take[c] ids, then the k + 1 smallest (d, id) per query colour
+    t = take[c]
+    qe = np.repeat(q, t)
+    de = np.repeat(d, t)
+    off = np.arange(t.sum()) - np.repeat(np.cumsum(t) - t, t)
+    ie = cid[np.repeat(c, t), off]
+    o = np.lexsort((ie, de, qe))
+    qe, de, ie = qe[o], de[o], ie[o]
+    start = np.searchsorted(qe, np.arange(m))
+    r = np.arange(qe.size) - start[qe]
+    s = r < k + 1
+    top_id = np.full((m, k + 1), -1, np.int64)
+    top_d = np.full((m, k + 1), np.inf)
+    top_id[qe[s], r[s]] = ie[s]
+    top_d[qe[s], r[s]] = de[s]
+    inv_orig = np.empty_like(inv)
+    inv_orig[order] = inv
+    return inv_orig, top_id, top_d
+
+
+def knn_graph(lab_u8, labels, nlabels, samples, k=8):
+    """findKnns (ColorTransfer.cpp:397-423) with the (distance, id) order of cmpDist for the KD-tree's ties (SPEC.md §4): lab_u8 is the level's Lab u8 map
+    [h][w][3], labels the k-means grid [lh][lw].
+      getClusters (:273-330): cluster_members; insertClusterPixel (:255-271): every member cell (x, y) contributes the samples x samples block at
+        (x * samples, y * samples), clipped at the level's edge;
+      findSubKNNs (:136-190): per cluster and member, the k + 1 smallest (distance, id) over the cluster, self included; self dropped if among them; the
+        first k kept;
+      sortMergeComputeWeight (:60-110): a pixel's lists of all its clusters sorted by cmpDist (:44), repeated ids dropped, the first k kept, w = exp(1 - d/3)
+        (not normalised: convertDist2Weight is never called on this path); fewer than k distinct neighbours are padded with self at weight 0 (quirk 10, where
+        the reference asserts).
+    Distinct colours are searched with a KD-tree over integer Lab, every colour up to the (k + 1)-th nearest colour's integer squared distance gathered (equal
+    integer distances need not stay equal after the double rounding; distinct ones stay ordered). Returns (ids [h*w][k] int32, weights [h*w][k] float64)."""
+    lab = np.asarray(lab_u8, np.uint8)
+    h, w = lab.shape[:2]
+    n = h * w
+    col = lab.reshape(n, 3)
+    key = (col[:, 0].astype(np.int64) << 16) | (col[:, 1].astype(np.int64) << 8) | col[:, 2]
+    mem = cluster_members(labels, nlabels)
+    lh, lw = mem.shape[1:]
+    py, px = np.divmod(np.arange(n), w)
+    cy, cx = py // samples, px // samples
+    inside = (cy < lh) & (cx < lw)
+    cand_d = np.full((n, 5 * k), np.inf)
+    cand_i = np.full((n, 5 * k), -1, np.int64)
+    nc = np.zeros(n, np.int64)
+    for l in range(nlabels):
+        m_ok = np.zeros(n, bool)
+        m_ok[inside] = mem[l, cy[inside], cx[inside]]
+        ids = np.flatnonzero(m_ok)
+        if ids.size == 0:
+            continue
+        ci, top_id, top_d = _cluster_top(key[ids], ids, col[ids], k)
+        ti, td = top_id[ci], top_d[ci]
+        is_self = ti == ids[:, None]
+        drop = np.where(is_self.any(1), np.argmax(is_self, 1), k)
+        keep = np.arange(k + 1)[None, :] != drop[:, None]
+        ti = ti[keep].reshape(-1, k)
+        td = td[keep].reshape(-1, k)
+        slot = nc[ids][:, None] * k + np.arange(k)[None, :]
+        cand_i[ids[:, None], slot] = ti
+        cand_d[ids[:, None], slot] = td
+        nc[ids] += 1
+    o = np.lexsort((cand_i, cand_d), axis=1)
+    cd = np.take_along_axis(cand_d, o, 1)
+    cdi = np.take_along_axis(cand_i, o, 1)
+    valid = cdi >= 0
+    first = np.ones_like(valid)
+    first[:, 1:] = cdi[:, 1:] != cdi[:, :-1]
+    use = valid & first
+    rank = np.cumsum(use, 1) - 1
+    use &= rank < k
+    out_i = np.repeat(np.arange(n, dtype=np.int64)[:, None], k, 1)
+    out_w = np.zeros((n, k))
+    rr, cc = np.nonzero(use)
+    out_i[rr, rank[rr, cc]] = cdi[rr, cc]
+    out_w[rr, rank[rr, cc]] = np.exp(1.0 - cd[rr, cc] / 3.0)
+    return out_i.astype(np.int32), out_w

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
+import ref64
 import synth
 
 
@@ -29,34 +30,13 @@ LAB_PIN = np.array([[0, 128, 128], [5, 128, 128], [12, 130, 120], [20, 128, 128]
                     [200, 250, 250], [40, 10, 240], [128, 128, 250], [128, 20, 128]], np.uint8)
 
 
-def _lab2bgr_numpy(lab, form):
-    """float64 evaluation of the two Lab2RGB_f forms, no tables (exact sRGB gamma): the independent pin of both restatements."""
-    L = lab[:, 0].astype(np.float64) * 100 / 255; a = lab[:, 1].astype(np.float64) - 128; b = lab[:, 2].astype(np.float64) - 128
-    if form == 1:        # plain cubes, no clipping before the gamma table
-        fy = (L + 16) / 116
-        y, X, Z = fy ** 3, (fy + a / 500) ** 3 * 0.950456, (fy - b / 200) ** 3 * 1.088754
-    else:                # piecewise: CIE's linear branch below L* = 8 / f = 6/29, clip to [0, 1]
-        fy = np.where(L <= 0.008856 * 903.3, 7.787 * (L / 903.3) + 16 / 116, (L + 16) / 116)
-        y = np.where(L <= 0.008856 * 903.3, L / 903.3, fy ** 3)
-        finv = lambda f: np.where(f <= 7.787 * 0.008856 + 16 / 116, (f - 16 / 116) / 7.787, f ** 3)
-        X, Z = finv(a / 500 + fy) * 0.950456, finv(fy - b / 200) * 1.088754
-    M = np.array([[3.240479, -1.53715, -0.498535], [-0.969256, 1.875991, 0.041556], [0.055648, -0.204043, 1.057311]])
-    rgb = np.stack([X, y, Z], 1) @ M.T
-    far_out = rgb[:, ::-1] < -0.02      # cube form only: far below the gamut the table's first cubic is extrapolated hundreds of steps and its tiny cubic
-    #                                     term takes over (-> a saturated byte, 0 or 255, decided by the spline coefficients): not modelled here
-    if form == 0:
-        rgb = np.clip(rgb, 0, 1)
-    srgb = np.where(rgb <= 0.0031308, 12.92 * rgb, 1.055 * np.maximum(rgb, 0) ** (1 / 2.4) - 0.055)
-    return np.clip(np.rint(srgb[:, ::-1] * 255), 0, 255), (far_out if form == 1 else np.zeros_like(far_out))
-
-
 def test_lab2bgr_both_forms_pinned(oracle):
     """CV_Lab2BGR on 8-bit input (ColorTransfer.cpp:1469), both forms of OpenCV's Lab2RGB_f: the 2.4.x cube form (default: the reference
     links OpenCV 2.4.10) and the 3.x piecewise form. Independent float64 evaluation for dark (L_u8 <= 20), grey, saturated and out-of-gamut triples, +-1 LSB for
     the spline-interpolated gamma table, plus hand-computed values where the two forms must differ."""
     for form in (0, 1):
         got = oracle.lab2bgr(LAB_PIN, form=form).astype(int)
-        exp, far_out = _lab2bgr_numpy(LAB_PIN, form)
+        exp, far_out = ref64.lab2bgr(LAB_PIN, form)
         assert np.abs(got - exp)[~far_out].max() <= 1, (form, got.tolist(), exp.tolist())
         assert np.isin(got[far_out], (0, 255)).all()
         assert got[7].tolist() == [128, 128, 128]

@@ -289,5 +289,240 @@ def test_pair_levels_vs_ref64(oracle, case):
         out, st = oracle.local_color_transfer(lv["err"][l], spyr[l], lv["guide"][l], src, ids, kw, l, want_stages=True)
         assert np.array_equal(out, lv["result"][l]), f"level {l}: the result is not the colour stage of the level's inputs"
         lv["color"].append(st)
-    stats = levels_ref64.check_levels(lv, src, ref, ws, bs, bds, oracle.resize_u8c3, oracle=oracle)
+    stats = levels_ref64.check_levels(lv, src, ref, ws, bs, bds, oracle)
     print("pair", case, {k: float("%.3g" % v) for k, v in stats.items()})
+
+
+# ---------------------------------------------------------------- A1: BGR <-> Lab over every 8-bit input
+# bgr2lab: OpenCV's 8-bit path against the exact mapping (ref64.bgr2lab's unrounded value), per band of the exact L byte and per channel. The 8-bit path rounds
+# its result (0.5), scales L by 296/2^15 instead of 295.8 (<= 0.2 at L = 255), quantises linear light to 1/2040 (sRGBGammaTab_b) and the cube root to 2^-15
+# (LabCbrtTab_b) before the matrix and after it. The linear-light step moves f = Y^(1/3) by step / (3 Y^(2/3)): in dark colours (L byte < 64, Y < 0.043) up to
+# a few tenths of an L unit, in a and b — differences of two such cube roots scaled by 500 and 200 — over a unit more; above, the step shrinks below half a
+# unit. Measured maxima over all 2^24 inputs, (L, a, b): [0, 64) 1.55 / 2.67 / 1.70, [64, 128) 0.92 / 1.37 / 1.26, [128, 256) 0.75 / 0.84 / 0.94.
+BGR2LAB_BANDS = [(0, 64, (2.0, 3.0, 2.0)), (64, 128, (1.25, 1.75, 1.5)), (128, 256, (1.0, 1.0, 1.0))]
+
+
+def _lattice(b0, b1):
+    g = np.arange(256)
+    return np.stack(np.meshgrid(np.arange(b0, b1), g, g, indexing="ij"), -1).reshape(-1, 3).astype(np.uint8)
+
+
+def check_bgr2lab_all(bgr2lab):
+    """bgr2lab (a library's) over all 2^24 BGR triples, in chunks, within BGR2LAB_BANDS of ref64.bgr2lab; on the grey axis a and b exactly 128 and L within
+    1 LSB of the exact byte. Returns the largest deviation per band."""
+    worst = np.zeros((len(BGR2LAB_BANDS), 3))
+    for b0 in range(0, 256, 32):
+        bgr = _lattice(b0, b0 + 32)
+        got = np.asarray(bgr2lab(bgr)).astype(np.float64)
+        _, val = ref64.bgr2lab(bgr)
+        dev = np.abs(got - val)
+        L = np.rint(val[:, 0])
+        for bi, (lo, hi, bound) in enumerate(BGR2LAB_BANDS):
+            sel = (L >= lo) & (L < hi)
+            if sel.any():
+                worst[bi] = np.maximum(worst[bi], dev[sel].max(0))
+    for bi, (lo, hi, bound) in enumerate(BGR2LAB_BANDS):
+        assert np.all(worst[bi] <= bound), (lo, hi, worst[bi].tolist(), bound)
+    grey = np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, 1)
+    got, (eb, _) = np.asarray(bgr2lab(grey)).astype(int), ref64.bgr2lab(grey)
+    assert np.all(got[:, 1:] == 128) and np.abs(got[:, 0] - eb[:, 0]).max() <= 1
+    return worst
+
+
+def check_lab2bgr_all(lab2bgr):
+    """lab2bgr(lab, form) (a library's) over all 2^24 Lab triples, both forms, within 1 LSB of ref64.lab2bgr outside the cube form's far-out channels.
+    Returns the largest deviation per form."""
+    worst = []
+    for form in (0, 1):
+        dev = 0
+        for b0 in range(0, 256, 32):
+            lab = _lattice(b0, b0 + 32)
+            got = np.asarray(lab2bgr(lab, form)).astype(np.float64)
+            exp, far = ref64.lab2bgr(lab, form)
+            dev = max(dev, float(np.abs(got - exp)[~far].max()))
+        assert dev <= 1, (form, dev)
+        worst.append(dev)
+    return worst
+
+
+def test_bgr2lab_all_inputs_vs_ref64(oracle):
+    print("bgr2lab", check_bgr2lab_all(oracle.bgr2lab).round(3).tolist())
+
+
+def test_lab2bgr_all_inputs_vs_ref64(oracle):
+    print("lab2bgr", check_lab2bgr_all(lambda lab, form: oracle.lab2bgr(lab, form=form)))
+
+
+# ---------------------------------------------------------------- C1: k-means labels
+# A label comparison through two normalisations (the library's float one, ref64's float64 one rounded to float) is meaningful only where no point lies nearer
+# than that to a tie: the two normalised maps differ by <= 1e-7 relative, which moved a float L2 distance by at most 5.1e-7 relative (measured on
+# synth.features 44 x 44 x 512, 64-channel 9 x 11 maps and 63 x 63 blobs). Every case's margin (ref64.kmeans_labels) must exceed four times that.
+KM_MARGIN = 2e-6
+
+
+def _km_blobs(seed, C, h, w, nb, noise):
+    rng = np.random.default_rng(seed)
+    cen = rng.random((nb, C)).astype(np.float32)
+    pts = np.abs(cen[rng.integers(0, nb, h * w)] + np.float32(noise) * rng.standard_normal((h * w, C)).astype(np.float32)) + np.float32(0.01)
+    return np.ascontiguousarray(pts.T.reshape(C, h, w))
+
+
+def _km_few(seed, C, h, w, distinct, skew):
+    """few distinct vectors; skew: the first holds that fraction of the points, so centre selection rejects duplicates deep into the permutation"""
+    rng = np.random.default_rng(seed)
+    protos = (rng.random((distinct, C), dtype=np.float32) + np.float32(0.05)) * np.float32(3.0)
+    which = np.where(rng.random(h * w) < skew, 0, rng.integers(1, distinct, h * w))
+    return np.ascontiguousarray(protos[which].T.reshape(C, h, w))
+
+
+def _km_donor():
+    """33 points near 12 prototypes in 8 channels: seed 1 leaves a cluster empty after the first step (the donor rule moves the farthest point of the next
+    cluster into it)"""
+    rng = np.random.default_rng(67)
+    n, C = int(rng.integers(10, 40)), 8
+    pro = rng.random((12, C)).astype(np.float32) + 0.01
+    return np.ascontiguousarray((pro[rng.integers(0, 12, n)] + 0.05 * rng.random((n, C))).T.reshape(C, 1, n)).astype(np.float32)
+
+
+def _km_tie():
+    """ten distinct unit vectors in 16 channels, 40 copies each, and the midpoints of the pairs (0, 1), (2, 3), (4, 5): after normalisation a midpoint is
+    exactly as far from both ends (the two squares swap places inside one group of four), so its first assignment is an exact tie that the strict > gives to
+    the lower centre id. No margin: the tie is the point."""
+    C = 16
+    v = np.zeros((10, C), np.float32)
+    v[np.arange(10), np.arange(10)] = 1.0
+    v[:, 12] = 0.25
+    mids = np.stack([(v[2 * i] + v[2 * i + 1]) * np.float32(0.5) for i in range(3)])
+    pts = np.concatenate([np.repeat(v, 40, 0), mids])
+    return np.ascontiguousarray(pts.T.reshape(C, 1, -1))
+
+
+# (name, features, seeds, what the case must reach: steps == 11 ("cap"), an early stop ("early"), a donor move, one label, duplicate rejections, an exact tie;
+#  whether the margin above KM_MARGIN is required — where it is not, only the comparison on the library's own normalised map holds, which is exact)
+KM_CASES = [("synth16", lambda: synth.features(3, 512, 16, 16) * np.float32(5.0), (1, 2, 3), "early"),
+            ("synth44_cap", lambda: synth.features(3, 512, 44, 44) * np.float32(5.0), (2,), "cap"),
+            ("c64_9x11", lambda: synth.features(1, 64, 9, 11), (1, 2, 3), "early"),
+            ("blobs63", lambda: _km_blobs(1, 512, 63, 63, 10, 0.05), (2,), "donor"),
+            ("blobs70", lambda: _km_blobs(1, 512, 70, 70, 10, 0.05), (1,), "cap"),
+            ("few70", lambda: _km_few(4, 512, 70, 70, 12, 0.9), (1, 2, 3), "dups"),
+            ("few30_one_label", lambda: _km_few(5, 512, 30, 30, 4, 0.5), (1,), "one"),
+            ("n_below_K", lambda: synth.features(2, 512, 3, 3), (1,), "one"),
+            ("n_equals_K", lambda: synth.features(2, 512, 2, 5), (1, 2), "early"),
+            ("donor8", _km_donor, (1,), "donor"),
+            ("tie16", _km_tie, (1, 2, 3), "tie", False),
+            ("synth44_tight_cap", lambda: synth.features(3, 512, 44, 44) * np.float32(5.0), (1,), "cap", False),      # an exact tie in a Lloyd step
+            ("synth63_tight_cap", lambda: synth.features(3, 512, 63, 63) * np.float32(5.0), (1,), "cap", False)]
+
+
+def check_kmeans(cluster, normalize, f, seed, expect, need_margin=True):
+    """cluster(f, K, iters, seed) -> (labels, n): bit for bit ref64.kmeans_labels of the library's own normalised map (no margin needed: ref64 emulates every
+    float operation), and of ref64's normalisation of f with the margin above KM_MARGIN (need_margin False: only reported). Returns the margin."""
+    gl, gn = cluster(f, 10, 11, seed)
+    el, en, _, info = ref64.kmeans_labels(normalize(f), 10, 11, seed, normalized=True, want_info=True)
+    assert gn == en and np.array_equal(gl, el), "labels differ from ref64 on the library's normalised map"
+    rl, rn, margin = ref64.kmeans_labels(f, 10, 11, seed)
+    if need_margin:
+        assert margin >= KM_MARGIN, f"margin {margin:.3g}: this case cannot tell a label error from the normalisation's rounding"
+        assert gn == rn and np.array_equal(gl, rl)
+    if expect == "cap":
+        assert info["steps"] == 11 and not info["converged"], info
+    elif expect == "early":
+        assert info["converged"] and info["steps"] < 11, info
+    elif expect == "donor":
+        assert info["donors"] > 0, info
+    elif expect == "one":
+        assert gn == 1 and not gl.any()
+    return margin
+
+
+@pytest.mark.parametrize("case", KM_CASES, ids=[c[0] for c in KM_CASES])
+def test_kmeans_labels_vs_ref64(oracle, case):
+    name, mk, seeds, expect = case[:4]
+    f = mk()
+    if expect == "dups":
+        perm = ref64._perm_splitmix(f.shape[1] * f.shape[2], 1)
+        assert np.flatnonzero(f.reshape(f.shape[0], -1)[0][perm] != f.reshape(f.shape[0], -1)[0][perm[0]]).size > 0
+    for seed in seeds:
+        m = check_kmeans(oracle.cluster_features, oracle.feat_normalize, f, seed, expect, *case[4:])
+        print(name, seed, "margin %.3g" % m)
+
+
+@pytest.mark.parametrize("case", PAIR_CASES[:1] + PAIR_CASES[2:])
+def test_kmeans_labels_of_conv5_vs_ref64(oracle, case):
+    """the source's and the reference's float64 conv5_1 (ref64.vgg19_taps) at the pair sizes of test_pair_levels_vs_ref64"""
+    from caffemodel_io import synthetic_vgg19
+    ws, bs = synthetic_vgg19(19)
+    for img in pair_images(case):
+        f = ref64.vgg19_taps(img, ws, bs, 5)[4]
+        for seed in (1, 2, 3):
+            check_kmeans(oracle.cluster_features, oracle.feat_normalize, f, seed, None)
+
+
+# ---------------------------------------------------------------- K1: kNN graph
+def knn_labels(kind, lh, lw, seed=0):
+    """label grids: "checker" (x + 2y) mod 5 — every cell's four neighbours carry four other labels, so with dilation each cell is in 5 clusters; "single" —
+    random labels 0..3 plus label 4 on one cell and label 5 on one corner cell (one-cell clusters); "bands" — vertical bands of 3 labels"""
+    yy, xx = np.mgrid[0:lh, 0:lw]
+    if kind == "checker":
+        return ((xx + 2 * yy) % 5).astype(np.int32), 5
+    if kind == "single":
+        lb = np.random.default_rng(seed).integers(0, 4, (lh, lw)).astype(np.int32)
+        lb[lh // 2, lw // 3] = 4
+        lb[0, lw - 1] = 5
+        return lb, 6
+    return (xx * 3 // lw).astype(np.int32), 3
+
+
+def knn_image(kind, h, w, seed=9):
+    img = synth.image_flat(seed, h, w) if kind == "flat" else synth.image(seed, h, w)
+    if kind == "flat":
+        img[h // 2:h // 2 + 2, : w // 2] = (255, 0, 255)           # isolated far colours
+        img[0, 0] = (0, 255, 0)
+    return img
+
+
+def check_knn(gi, gw, ei, ew, what):
+    """ids exactly, weights within 4e-16 relative (orc_exp / the kernels' exp are within 1 ulp of libm). Returns (padded entries, max relative deviation)."""
+    assert np.array_equal(gi, ei), f"{what}: ids differ from ref64 at {int((gi != ei).any(1).sum())} pixels"
+    assert np.allclose(gw, ew, rtol=4e-16, atol=0), what
+    nz = ew > 0
+    dev = float((np.abs(gw - ew)[nz] / ew[nz]).max(initial=0.0))
+    pad = int(((ew == 0) & (ei == np.arange(ei.shape[0])[:, None])).sum())
+    return pad, dev
+
+
+# (level h, w, label grid lh, lw, label kind, image kind, samples)
+KNN_CASES = [(113, 170, 8, 11, "checker", "flat", 16), (113, 170, 8, 11, "single", "cos", 16), (60, 47, 12, 10, "checker", "flat", 5),
+             (40, 44, 40, 44, "single", "flat", 1), (45, 61, 23, 31, "checker", "cos", 2), (70, 33, 10, 5, "single", "flat", 7),
+             (64, 64, 8, 8, "bands", "flat", 8), (37, 53, 3, 4, "checker", "cos", 13), (30, 30, 30, 30, "checker", "flat", 1)]
+
+
+@pytest.mark.parametrize("case", KNN_CASES)
+def test_knn_graph_vs_ref64(oracle, case):
+    h, w, lh, lw, lkind, ikind, samples = case
+    labels, nl = knn_labels(lkind, lh, lw)
+    lab = oracle.bgr2lab(knn_image(ikind, h, w))
+    gi, gw = oracle.knn_graph(lab, labels, nl, samples)
+    ei, ew = ref64.knn_graph(lab, labels, nl, samples)
+    pad, dev = check_knn(gi, gw, ei, ew, str(case))
+    print(case, "padded", pad, "max rel dev %.3g" % dev)
+
+
+def test_knn_graph_flat_ties_and_padding(oracle):
+    """a map of few colours (every distance tied many times) and a grid that leaves pixels uncovered (3 x 4 cells of 5 on a 17 x 23 level): the (distance, id)
+    order and the zero-weight self padding"""
+    rng = np.random.default_rng(2)
+    pal = rng.integers(0, 256, (4, 3)).astype(np.uint8)
+    lab = oracle.bgr2lab(pal[rng.integers(0, 4, (17, 23))])
+    labels, nl = knn_labels("single", 3, 4, 1)
+    gi, gw = oracle.knn_graph(lab, labels, nl, 5)
+    ei, ew = ref64.knn_graph(lab, labels, nl, 5)
+    pad, _ = check_knn(gi, gw, ei, ew, "flat")
+    assert pad > 0 and np.all(ew.reshape(17, 23, 8)[15:, :, :] == 0)
+    # one cluster of 2 x 4 covered pixels: each has 7 others, so the eighth entry is the zero-weight self edge
+    labels = np.zeros((2, 4), np.int32)
+    gi, gw = oracle.knn_graph(lab, labels, 1, 1)
+    ei, ew = ref64.knn_graph(lab, labels, 1, 1)
+    check_knn(gi, gw, ei, ew, "2x4")
+    cov = (np.arange(17)[:, None] < 2) & (np.arange(23)[None, :] < 4)
+    assert np.all(ew.reshape(17, 23, 8)[cov][:, 7] == 0) and np.all(ew.reshape(17, 23, 8)[cov][:, :7] > 0)
