@@ -1126,10 +1126,10 @@ struct PartBufs {
     double *x6, *r, *p, *sv, *w, *partial, *sums; PState* st;      // Krylov vectors [NQ][N], reduction scratch, double-buffered state
     vf* rf;                                                         // the residual rounded to fp32: what the V-cycle's finest level reads (written next to r by k_pcg_start / k_cg_update)
     std::vector<Lvl> lv;                                            // the shared operator hierarchy with THIS part's V-cycle vectors (b, x, x2)
-    PState* hst; hipEvent_t ev[2];                                  // two page-locked read-back slots and their events
+    PState* hst;                                                    // two page-locked slots the solver state is published to
     const double* rough;                                            // the data term (right-hand side = rough * x0)
     nct_ctx* kt;                                                    // kernel clock (NCT_FLAG_TIME_KERNELS, unsplit solves only), else null
-    int maxit, graph;
+    int maxit;
     bool trace;
     bool forecast;                                                  // size the batches by the convergence forecast (pcg_part)
     bool lines;                                                     // block step on the finest level (default; NCT_S2_LINES=0: without)
@@ -1147,10 +1147,9 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
     const PState* cur = st;
     const double rtol2 = rtol * rtol;
     hipLaunchKernelGGL(k_pcg_start<NQ>, dim3(nb), dim3(256), 0, s, F, B.rough, (const double*)X, (double*)x6, (double*)r, rf, (double*)partial); LCHK();
-    const bool zero_copy = !B.graph;                       // the graph hook replays fixed kernel arguments: it keeps the copy + event form
     int seq_of_slot[2] = {0, 0};
-    seq_of_slot[0] = ++g_seq;
-    hipLaunchKernelGGL(k_pcg_start_fin<NQ>, dim3(1), dim3(256), 0, s, (const double*)partial, nb, st, rtol2, zero_copy ? &B.hst[0] : (PState*)nullptr, seq_of_slot[0]); LCHK();
+    seq_of_slot[0] = ++g_seq;                              // the state after the start kernel (x0 may already solve the system) goes to slot 0
+    hipLaunchKernelGGL(k_pcg_start_fin<NQ>, dim3(1), dim3(256), 0, s, (const double*)partial, nb, st, rtol2, &B.hst[0], seq_of_slot[0]); LCHK();
 
     // z = Vcycle(r). Levels 0..nl-2 run the tile-fused down/up legs (2 launches per level), the coarsest grid one wave per right-hand side.
     // lv[l].x2 = where level l's correction ends up (the up leg cannot write in place: neighbouring tiles still read lv[l].x).
@@ -1231,8 +1230,8 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
         return 0;
     };
     const vf* z = B.lines ? lv[0].x : lv[0].x2;
-    // Convergence is polled without draining the stream: after every batch of `batch` iterations the solver state is copied to
-    // page-locked host memory and an event is recorded; the host then enqueues the NEXT batch before it waits for that event, so
+    // Convergence is polled without draining the stream: the update kernel of the last iteration of every batch publishes the solver
+    // state, with a sequence number, into page-locked host memory; the host enqueues the NEXT batch before it spins on that number, so
     // the GPU always has a batch queued. The batch enqueued past convergence costs only empty launches (nactive == 0).
     const int maxit = B.maxit, batch = NCT_WLS_BATCH;
     PState* hst = B.hst;                                  // two slots of page-locked memory
@@ -1253,11 +1252,6 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
         cur = nxt;
         return 0;
     };
-    auto snapshot = [&](int slot) -> int {               // copy + event form (graph hook only)
-        NCT_HIP(hipMemcpyAsync(&hst[slot], cur, sizeof(PState), hipMemcpyDeviceToHost, s));
-        NCT_HIP(hipEventRecord(B.ev[slot], s));
-        return 0;
-    };
     auto wait_published = [&](int slot) -> int {           // spin on the publication number (the kernels of at least one batch are queued behind it)
         const int want_seq = seq_of_slot[slot];
         const auto t0 = std::chrono::steady_clock::now();
@@ -1271,7 +1265,7 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
         }
         return 0;
     };
-    // Snapshot k is taken behind the k-th enqueue (k = 0: behind the start kernel), into slot k & 1; the host reads them in order, one per turn, after it
+    // Snapshot k is published by the last kernel of the k-th enqueue (k = 0: by the start kernel), into slot k & 1; the host reads them in order, one per turn, after it
     // has enqueued the next batch. How MANY iterations that batch gets is a forecast: from the last two snapshots it has read, the host knows r.r of every
     // system still iterating and its decay per iteration, hence the iterations still needed (the one that finds r.r below the threshold included); what is
     // already in flight is subtracted. A forecast of 0 enqueues nothing and just waits for the in-flight snapshot — if the solve is not done then (the decay
@@ -1280,17 +1274,11 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
     int it = 0; bool done = false;
     int issued = 0, seen = -1;                             // snapshot numbers
     int its_at_snapshot[2] = {0, 0};                       // iterations enqueued when snapshot (k & 1) was taken
-    if (!zero_copy) { int rc = snapshot(0); if (rc) return rc; }   // state after the start kernel (x0 may already solve the system); zero-copy: k_pcg_start_fin published it
     PState fin; memset(&fin, 0, sizeof fin);
     double prev_rho[6]; int prev_its = -1;
     int remaining_after_seen = -1;                         // forecast; -1 = none yet
     int its_seen = 0;
-    // Experiment hook (NCT_WLS_GRAPH=1): from the second batch on, the iteration batch (its kernels, arguments and the
-    // state double-buffering repeat exactly) is captured once and replayed as a HIP graph instead of being enqueued kernel by kernel.
-    hipGraph_t graph = nullptr; hipGraphExec_t gexec = nullptr;
-    struct GraphCleanup { hipGraph_t& g; hipGraphExec_t& e; ~GraphCleanup() { if (e) (void)hipGraphExecDestroy(e); if (g) (void)hipGraphDestroy(g); } } gcleanup{graph, gexec};
-    const bool forecast = B.forecast && !B.graph;
-    bool forecast_on = forecast;
+    bool forecast_on = B.forecast;
     while (true) {
         int want = batch;
         if (forecast_on && remaining_after_seen >= 0) {
@@ -1302,36 +1290,21 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
                                                                                        // flattened) — the GPU just idled for a round trip; fixed batches for the rest of this solve
         }
         if (it + want > maxit) want = maxit - it;
-        const bool enqueued = want > 0;
-        if (enqueued && B.graph && it >= batch && want == batch) {
-            if (!gexec) {
-                NCT_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                int rc = 0;
-                for (int k = 0; k < batch && !rc; ++k) rc = iteration(it + k);
-                hipError_t e = hipStreamEndCapture(s, &graph);
-                if (rc) return rc;
-                NCT_HIP(e);
-                NCT_HIP(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
-            }
-            NCT_HIP(hipGraphLaunch(gexec, s));
-            it += batch;
-            cur = st + (it & 1);
-        } else
-        if (enqueued) {
+        if (want > 0) {
             for (int k = 0; k < want; ++k, ++it) {
-                if (zero_copy && k == want - 1) { seq_of_slot[(issued + 1) & 1] = ++g_seq; pub_to = &hst[(issued + 1) & 1]; pub_seq = seq_of_slot[(issued + 1) & 1]; }
+                if (k == want - 1) { seq_of_slot[(issued + 1) & 1] = ++g_seq; pub_to = &hst[(issued + 1) & 1]; pub_seq = seq_of_slot[(issued + 1) & 1]; }
                 int rc = iteration(it); pub_to = nullptr; if (rc) return rc;
             }
+            ++issued; its_at_snapshot[issued & 1] = it;
         }
-        if (enqueued) { ++issued; its_at_snapshot[issued & 1] = it; if (!zero_copy) { int rc = snapshot(issued & 1); if (rc) return rc; } }
         if (seen == issued) break;                         // nothing left to read: the iteration budget is spent
         ++seen;
-        if (zero_copy) { int rc = wait_published(seen & 1); if (rc) return rc; } else NCT_HIP(hipEventSynchronize(B.ev[seen & 1]));
+        { int rc = wait_published(seen & 1); if (rc) return rc; }
         fin = hst[seen & 1];
         its_seen = its_at_snapshot[seen & 1];
         if (fin.nactive == 0) { done = true; break; }
         if (it >= maxit && seen == issued) break;
-        if (forecast) {
+        if (B.forecast) {
             // iterations still needed after this snapshot: the slowest system's m = ceil(log(threshold / rho) / log(decay per iteration)), decay from the
             // previous snapshot read; no forecast (full batches) while there is no history or the residual does not decay
             const int ridx = its_seen > 0 ? its_seen - 1 : 0;   // fin.rho = r_ridx . r_ridx (the start kernel and iteration 0 both see r_0)
@@ -1445,8 +1418,8 @@ int nctk_wls_solve_mg(nct_ctx* ctx, hipStream_t s, double* X, const double* roug
             L.b = l == 0 ? nullptr : newf((size_t)L.n * nq0); L.x = newf((size_t)L.n * nq0); L.x2 = newf((size_t)L.n * nq0);
             if ((l > 0 && !L.b) || !L.x || !L.x2) return NCT_ERR_HIP;
         }
-        B.hst = (PState*)ctx->pinned + 2 * h; B.ev[0] = ctx->ev_poll[2 * h]; B.ev[1] = ctx->ev_poll[2 * h + 1];
-        B.maxit = ctx->wls_maxit; B.graph = ctx->wls_graph; B.forecast = ctx->wls_forecast != 0; B.lines = ctx->wls_lines != 0; B.trace = getenv("NCT_WLS_TRACE") != nullptr; B.rough = rough; B.kt = (ctx->kt_on && !split && !ctx->wls_graph) ? ctx : nullptr;   /* events recorded inside a stream capture cannot be read back: no kernel clock under NCT_WLS_GRAPH */
+        B.hst = (PState*)ctx->pinned + 2 * h;
+        B.maxit = ctx->wls_maxit; B.forecast = ctx->wls_forecast != 0; B.lines = ctx->wls_lines != 0; B.trace = getenv("NCT_WLS_TRACE") != nullptr; B.rough = rough; B.kt = (ctx->kt_on && !split) ? ctx : nullptr;
         memset(B.iters, 0, sizeof B.iters);
     }
     if (!split) {

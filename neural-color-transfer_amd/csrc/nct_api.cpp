@@ -96,10 +96,7 @@ int nct_create(int device, nct_ctx** out) {
     }
     for (int l = 0; l < 5; ++l)
         if ((e = hipEventCreateWithFlags(&c->ev_level[l], hipEventDisableTiming)) != hipSuccess) { g_create_err = std::string("event creation: ") + hipGetErrorString(e); delete c; return NCT_ERR_HIP; }
-    for (int l = 0; l < 4; ++l)
-        if ((e = hipEventCreateWithFlags(&c->ev_poll[l], hipEventDisableTiming)) != hipSuccess) { g_create_err = std::string("event creation: ") + hipGetErrorString(e); delete c; return NCT_ERR_HIP; }
     if ((e = hipHostMalloc(&c->pinned, 4096 + 64, hipHostMallocDefault)) != hipSuccess) { g_create_err = std::string("hipHostMalloc: ") + hipGetErrorString(e); delete c; return NCT_ERR_HIP; }
-    if (const char* g = getenv("NCT_WLS_GRAPH")) c->wls_graph = atoi(g);
     if (const char* g = getenv("NCT_S2_LINES")) c->wls_lines = atoi(g) != 0;
     if (const char* f = getenv("NCT_WLS_FORECAST")) { const int v = atoi(f); if (v == 0 || v == 1) c->wls_forecast = v; }
     if (const char* r = getenv("NCT_WLS_RTOL")) { const double v = atof(r); if (v > 0 && v < 1) c->wls_rtol = v; }
@@ -107,10 +104,7 @@ int nct_create(int device, nct_ctx** out) {
     { static std::atomic<int> next_home{0}; c->home_xcd = next_home.fetch_add(1) & 7; }
     if (const char* q = getenv("NCT_CONV_PAIR")) { const int v = atoi(q); if (v == 0 || v == 1) c->conv_pair = v; }
     if (const char* q = getenv("NCT_KNN_RUNS")) { const int v = atoi(q); if (v == 0 || v == 1) c->knn_runs = v; }
-    if (const char* q = getenv("NCT_PM_PERSIST")) { const int v = atoi(q); if (v == 0 || v == 1) c->pm_persist = v; }
-    if (const char* q = getenv("NCT_PM_PERSIST_WGS")) { const int v = atoi(q); if (v > 0) c->pm_persist_wgs = v; }
     if (const char* q = getenv("NCT_S1_HUB_HINT")) { const int v = atoi(q); if (v == 0 || v == 1) c->s1_hub_hint = v; }
-    if (const char* q = getenv("NCT_S1_HUB_WAIT")) { const int v = atoi(q); if (v == 0 || v == 1) c->s1_hub_wait = v; }
     if (const char* m = getenv("NCT_WLS_MAXIT")) { const int v = atoi(m); if (v > 0) c->wls_maxit = v; }
     if (const char* m = getenv("NCT_S1_MAXIT")) { const int v = atoi(m); if (v > 0) c->s1_maxit = v; }
     *out = c;
@@ -157,7 +151,6 @@ void nct_destroy(nct_ctx* ctx) {
     for (hipEvent_t e : ctx->tm_events) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->kt_events) (void)hipEventDestroy(e);
     if (ctx->d_counter) (void)hipFree(ctx->d_counter);
-    if (ctx->d_pm_err) (void)hipFree(ctx->d_pm_err);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -165,7 +158,6 @@ void nct_destroy(nct_ctx* ctx) {
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
     for (int l = 0; l < 5; ++l) if (ctx->ev_level[l]) (void)hipEventDestroy(ctx->ev_level[l]);
-    for (int l = 0; l < 4; ++l) if (ctx->ev_poll[l]) (void)hipEventDestroy(ctx->ev_poll[l]);
     if (ctx->stream_wls) (void)hipStreamDestroy(ctx->stream_wls);
     if (ctx->ev_wls_fork) (void)hipEventDestroy(ctx->ev_wls_fork);
     if (ctx->ev_wls_join) (void)hipEventDestroy(ctx->ev_wls_join);
@@ -187,7 +179,7 @@ int nct_synchronize(nct_ctx* ctx) {
     if (!ctx) return NCT_ERR_INVALID;
     NCT_HIP(hipSetDevice(ctx->device));
     NCT_HIP(hipDeviceSynchronize());
-    return nctk_pm_check(ctx);
+    return NCT_OK;
 }
 
 #define CTX_ENTER() do { if (!ctx) return NCT_ERR_INVALID; NCT_HIP(hipSetDevice(ctx->device)); } while (0)
@@ -258,7 +250,6 @@ int nct_patchmatch(nct_ctx* ctx, const float* a_chw, const float* b_chw, int C, 
     RC(nctk_patchmatch(ctx, ctx->stream, A, B, C, ah, aw, bh, bw, iters, rs_max, seed, n, d, nullptr));
     D2H(nnf, n, sizeof(uint32_t) * na);
     D2H(dist, d, sizeof(float) * na);
-    RC(nctk_pm_check(ctx));
     SYNC();
     return NCT_OK;
 }
@@ -360,7 +351,6 @@ int nct_pm_bench_run(nct_ctx* ctx, int iters, int rs_max, uint32_t seed, float* 
     RC(nctk_patchmatch(ctx, ctx->stream, ctx->bench_a, ctx->bench_b, C, ah, aw, bh, bw, iters, rs_max, seed, n, d, counter));
     NCT_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     NCT_HIP(hipEventSynchronize(ctx->ev1));
-    RC(nctk_pm_check(ctx));
     float ms = 0.f;
     NCT_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     if (kernel_ms) *kernel_ms = ms;
@@ -389,7 +379,6 @@ int nct_pm_bench_run_bidir(nct_ctx* ctx, int iters, int rs_max, uint32_t seed, i
                              an, ad, bn, bd, pm_mode, counter));
     NCT_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     NCT_HIP(hipEventSynchronize(ctx->ev1));
-    RC(nctk_pm_check(ctx));
     float ms = 0.f;
     NCT_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     if (kernel_ms) *kernel_ms = ms;

@@ -16,10 +16,9 @@ struct nct_ctx {
     hipStream_t stream2 = nullptr;    // second stream (R->S direction runs concurrently)
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t ev_level[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // side-stream completion of level l's kNN graph
-    hipEvent_t ev_poll[4] = {nullptr, nullptr, nullptr, nullptr};   // completion of the in-flight solver-state read-backs (k_wls_mg.hip: two per half-solve)
     hipStream_t stream_wls = nullptr;  // helper stream of the split WLS solve (NCT_FLAG_LATENCY)
     hipEvent_t ev_wls_fork = nullptr, ev_wls_join = nullptr;
-    void* pinned = nullptr;                        // 4 KB of page-locked host memory for those read-backs (+ 64 B: s1_hub_blocks)
+    void* pinned = nullptr;                        // 4 KB of page-locked host memory the WLS solver publishes its state to (k_wls_mg.hip: two slots per half-solve; + 64 B: s1_hub_blocks)
     std::string err;
     std::vector<nct_block> blocks;    // cached device allocations, reused across calls and pairs
     size_t bytes_allocated = 0;
@@ -32,16 +31,12 @@ struct nct_ctx {
     unsigned long long* d_counter = nullptr;   // device counters of the pm kernels (NCT_FLAG_COUNT_EVALS): [0] distance evaluations performed, [1] accepted candidates;
                                                 // 4 slots per pyramid level in pair runs (nct_pipeline.cpp reads [4 l] and [4 l + 1])
     int home_xcd = 0;                           // the XCD this context's single-XCD launches aim at (k_s1.hip: small S1 levels); contexts of a process count round-robin (nct_create)
-    int pm_persist = 0;                         // PatchMatch: one persistent launch per pyramid level (k_pm_level) instead of 1 + 4 iters launches (env NCT_PM_PERSIST)
-    int pm_persist_wgs = 0;                     // workgroups of that launch (0: CUs x occupancy; env NCT_PM_PERSIST_WGS, experiments)
-    uint32_t* d_pm_err = nullptr;               // device word the persistent kernel's watchdog sets; read by nctk_pm_check at the synchronisation points
     unsigned pm_attr_mask = 0;                 // k_pm_step instantiations whose dynamic-LDS opt-in has been set on this context's device
     // stage clock: events recorded on the main stream at stage boundaries, read once after the pair's final synchronise
     // (no host syncs in between: see nct_pair_timing in nct.h)
     int wls_split = 0;                          // NCT_FLAG_LATENCY of the running pair: a- and b-half of the WLS solve on two streams
     int wls_forecast = 1;                       // size the PCG iteration batches by the host's convergence forecast (k_wls_mg.hip: pcg_part); NCT_WLS_FORECAST=0: fixed batches
     int wls_lines = 1;                          // block step of alternating line solves on the finest S2 level (k_wls_mg.hip: k_mg_block; oracle: mg_block_step). NCT_S2_LINES=0: the cycle without it (other arithmetic; comparison only)
-    int wls_graph = 0;                          // experiment hook (env NCT_WLS_GRAPH=1): replay the PCG iteration batch as a HIP graph
     int conv_pool_fuse = -1;                    // VGG: 2x2 max-pool inside the conv epilogue: -1 = where the tile shape fits the map (nctk_conv3x3_pool_fits), 0 never, 1 always (NCT_CONV_POOL_FUSE; tests)
     double wls_rtol = 3e-8;                     // relative residual at which the WLS solve stops. The loosest tolerance at which the 8-bit result of every level equals the EXACT solve's on the
                                                 // 700x700, mixed and 1000x1000 fixtures: 1e-7 with the point smoother of rounds 3-5a (1e-6: 55.4 / 50.1 dB), 3e-8 with the block step (the same residual norm
@@ -59,8 +54,6 @@ struct nct_ctx {
     long long s1_hub_blocks_last[5] = {0, 0, 0, 0, 0};            // the counts the last pair's solves were launched with (-1: not known when the solve was enqueued); nct_ctx_counter
     int knn_runs = -1;                          // kNN search form: -1 = one search per (cluster, colour) run where runs average > 2.5 entries, decided on the device; 0 / 1 = NCT_KNN_RUNS (tests)
     int s1_hub_hint = 1;                        // use the host-side hub block counts (NCT_S1_HUB_HINT=0: always launch the hub pass — the conservative path, for tests)
-    int s1_hub_wait = 1;                        // level 0 only: the host waits for the coarsest graph's event instead of launching 101 + 101 hub passes blind (NCT_S1_HUB_WAIT=0: no host wait inside a pair;
-                                                // measured in round 6, profiles/round6_ab.md: waiting is 0.8 ms faster per single pair and +0.5-1 % with four in flight)
     bool kt_on = false;
     std::vector<hipEvent_t> kt_events; std::vector<int> kt_ids;
     int kt_begin(hipStream_t s, int id);        // nct_api.cpp; no-ops unless kt_on
@@ -104,8 +97,6 @@ int nctk_hwc_to_chw(nct_ctx* ctx, hipStream_t s, const float* src, float* dst, i
 int nctk_normalize(nct_ctx* ctx, hipStream_t s, const float* src_hwc, float* dst_hwc, float* resp /*nullable*/, int C, int HW,
                    void* dst_h16 = nullptr /* nullable: fp16 (round-to-nearest) shadow copy of dst, same HWC layout */);
 int nctk_feature_distance(nct_ctx* ctx, hipStream_t s, const float* a_hwc, const float* b_hwc, float* err, int C, int HW);
-// k_patchmatch.hip: after a stream synchronise — has a persistent PatchMatch level's watchdog fired since the last check? (NCT_ERR_HIP then; no-op without pm_persist)
-int nctk_pm_check(nct_ctx* ctx);
 // k_nnf.hip
 int nctk_nnf_init(nct_ctx* ctx, hipStream_t s, uint32_t* nnf, int ah, int aw, int bh, int bw);
 int nctk_nnf_upsample(nct_ctx* ctx, hipStream_t s, const uint32_t* nnf_half, uint32_t* nnf, int ah, int aw, int bh, int bw, int ah_half, int aw_half);

@@ -224,7 +224,7 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
         rc = nctk_patchmatch_bidir(ctx, s, na, nb, (const uint16_t*)na_h, (const uint16_t*)nb_h, C, ah[l], aw[l], bh[l], bw[l], prm->pm_iters, rs_range[l], seed_ab, seed_ba,
                                    ann, annd, bnn, bnnd, pm_mode, count ? ctx->d_counter + 4 * l : nullptr); if (rc) return rc;
         MARK(ST_PM, l);
-        if (timing) timing->pm_level_launches[l] = (ctx->pm_persist && 4 * prm->pm_iters <= 250) ? 1 : 1 + 4 * prm->pm_iters;
+        if (timing) timing->pm_level_launches[l] = 1 + 4 * prm->pm_iters;
         if (lv) {
             rc = d2h(lv->ann[l], ann, sizeof(uint32_t) * na_px); if (rc) return rc;
             rc = d2h(lv->bnn[l], bnn, sizeof(uint32_t) * nb_px); if (rc) return rc;
@@ -258,10 +258,9 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
         // has just waited for the previous level's WLS solve); else -1 and the hub pass is launched on the device-side count. The result does not depend on it.
         int hub_hint = -1, sup_hint = -1;
         // the coarsest level's graph is built while the host is still far ahead of the GPU (the VGG forwards are running), so its count has not arrived when the host gets
-        // here. Default: wait for that one event — the GPU has the level's correspondence work queued meanwhile and the solve's 200 launches are enqueued faster than they
-        // execute. NCT_S1_HUB_WAIT=0 (no host wait inside a pair): the level's 101 hub passes (+ 101 second-level passes) are launched blind on grids sized by
-        // the level and exit on the device-side count. Measured (profiles/round6_ab.md): 77.9 vs 78.7 ms per single pair, 15.44-15.49 vs 15.31-15.38 pairs/s with four in flight.
-        if (ctx->s1_hub_hint && ctx->s1_hub_wait && l == 0) (void)hipEventSynchronize(ctx->ev_level[0]);
+        // here: wait for that one event. The GPU has the level's correspondence work queued meanwhile and the solve's 200 launches are enqueued faster than they execute;
+        // without the count the level's 101 hub passes (+ 101 second-level passes) would be launched blind (measured slower: DESIGN.md §9).
+        if (ctx->s1_hub_hint && l == 0) (void)hipEventSynchronize(ctx->ev_level[0]);
         if (ctx->s1_hub_hint && hipEventQuery(ctx->ev_level[l]) == hipSuccess) { hub_hint = *(volatile int*)(ctx->s1_hub_blocks() + 2 * l); sup_hint = *(volatile int*)(ctx->s1_hub_blocks() + 2 * l + 1); }
         (void)hipGetLastError();                                     // hipEventQuery's hipErrorNotReady is not an error
         ctx->s1_hub_blocks_last[l] = hub_hint;
@@ -283,7 +282,6 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
     }
     // the side stream's kNN graphs (one per level that ran) finish before their buffers go back (Cleanup3 synchronises stream2)
     NCT_HIP(hipStreamSynchronize(s));
-    rc = nctk_pm_check(ctx); if (rc) return rc;
     if (timing) {
         timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
         rc = read_marks(ctx, timing); if (rc) return rc;
