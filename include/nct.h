@@ -241,6 +241,21 @@ int nct_pair_run(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing);
 int nct_pair_run_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* levels);   /* + host copies of the intermediates */
 int nct_pair_download(nct_ctx* ctx, uint8_t* out_bgr);
 
+/* ---- full-resolution output (SPEC §6.1; an extension: the reference returns every image shrunk to MAX_SIZE, main.cu:500-522).
+ * nct_working_size (no context; the message of a refusal is nct_last_error(NULL)): the size the pyramid runs at — unchanged if both sides are <= max_side,
+ * else the longer side becomes max_side and the other (int)(max_side / (float)long * short). Refused with NCT_ERR_INVALID: max_side outside [17, 4000],
+ * a side above 16384, more than 2^26 pixels, a working side below 17.
+ * nct_process_pair_fullres: both images are shrunk by that rule on the device, every level runs as nct_process_pair runs it on the shrunk pair, except
+ * that the last level's U1 / S2 / A1 target the ORIGINAL source: out has sh x sw pixels. A source that is not shrunk gives nct_process_pair's result.
+ * nct_pair_timing: the finish's WLS counts in wls_ms / wls_level_ms[levels-1] and wls_iters[levels-1], the rest of it in color_ms.
+ * nct_color_finish: that finish alone, on host buffers: ab = nct_color_stages.ab_nonlocal of a level of h x w in a pyramid of working size
+ * work_h x work_w, s_bgr_full the source at H x W (>= h x w). stages (nullable) receives ab_up, roughness, ab_wls and wls_iters. */
+int nct_working_size(int h, int w, int max_side, int* work_h, int* work_w);
+int nct_process_pair_fullres(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw, int max_side,
+                             const nct_params* prm, uint8_t* out_bgr /* sh x sw x 3 */, nct_pair_timing* timing);
+int nct_color_finish(nct_ctx* ctx, const double* ab, int h, int w, int work_h, int work_w, const uint8_t* s_bgr_full, int H, int W, const nct_params* prm,
+                     uint8_t* out_bgr_full, nct_color_stages* stages);
+
 /* ---- device-pointer seams: the same operations on buffers that stay in HBM between calls (main.cu:204-316 keeps Ndata_C1, ann_device, ... on the device
  * across these kernels; an integrator replacing single seams should not pay H2D + D2H + a synchronise per call). Buffers come from the context's arena
  * (nct_dev_alloc / nct_dev_free; any device pointer of the context's GPU works as an operand). Calls are enqueued on the context's stream in call order and return

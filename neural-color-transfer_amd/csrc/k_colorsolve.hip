@@ -1,5 +1,6 @@
 // k_colorsolve.hip — local colour transfer on the GPU: T1 local statistics, T2 confidence weights, S1 nonlocal
-// least squares (truncated CG), U1 upsample + roughness, S2 edge-aware WLS smoothing (PCG), A1 apply.
+// least squares (truncated CG), U1 upsample + roughness, S2 edge-aware WLS smoothing (PCG), A1 apply. U1..A1 are "the finish"
+// (nctk_color_finish): on the pipeline's levels it targets the working grid, in the full-resolution entry the original source (SPEC §6.1).
 // Reference: ColorTransfer::transfer_color_downsample ColorTransfer.cpp:1180-1478 and what it calls:
 //   stats loop :1194-1265 (+ build_accumTable_downsample :425-455), weights :1302-1357,
 //   solve_nonlocal_downsample_gpu_gradient :548-949 -> solve_ls_cg_gpu SparseSolver_GPU.cu:3-198,
@@ -128,11 +129,56 @@ static int dbg_copy(nct_ctx* ctx, hipStream_t s, double* host, const double* dev
     return 0;
 }
 
+// ================================================================= the finish: U1, roughness, S2, A1 on a target grid H x W >= h x w
+// x: [2][h*w][3] coefficients after S1 on the level grid; Hw x Ww: the working size the pyramid runs at (the pipeline's "full" grid of every
+// level). The pipeline's own levels pass H x W = Hw x Ww; the full-resolution entry passes the original source (SPEC §6.1). Index arithmetic is
+// int for pixels (N <= 2^26) and size_t for every element offset past 3 N.
+int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int Hw, int Ww, const uint8_t* s_lab_full, int H, int W,
+                      const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg) {
+    NCT_REQUIRE(h > 0 && w > 0 && H >= h && W >= w && H <= NCT_FINISH_MAX_SIDE && W <= NCT_FINISH_MAX_SIDE && (long long)H * W <= NCT_FINISH_MAX_PIXELS,
+                "color finish: target %dx%d outside [%dx%d, %d per side, %lld px]", W, H, w, h, NCT_FINISH_MAX_SIDE, (long long)NCT_FINISH_MAX_PIXELS);
+    // ---------------- U1: bilinear upsample to full resolution + roughness
+    const int n = h * w, N = H * W, nbL = cdiv(N, 256);
+    const double* xa = x; const double* xb = x + (size_t)3 * n;
+    DevBuf<double> X(ctx, (size_t)6 * N), rough(ctx, N);
+    if (!X.ok() || !rough.ok()) return NCT_ERR_HIP;
+    double* Xa = X; double* Xb = (double*)X + (size_t)3 * N;
+    if (W > w || H > h) {
+        int rc = nctk_resize_f64c3(ctx, s, xa, h, w, Xa, H, W); if (rc) return rc;
+        rc = nctk_resize_f64c3(ctx, s, xb, h, w, Xb, H, W); if (rc) return rc;
+    } else {
+        NCT_HIP(hipMemcpyAsync(X, x, sizeof(double) * (size_t)6 * N, hipMemcpyDeviceToDevice, s));
+    }
+    hipLaunchKernelGGL(k_roughness, dim3(nbL), dim3(256), 0, s, (const double*)Xa, (const double*)Xb, s_lab_full, N, (double*)rough); LCHK();
+    if (dbg) { int rc = dbg_copy(ctx, s, dbg->ab_up, X, (size_t)6 * N); if (rc) return rc; rc = dbg_copy(ctx, s, dbg->rough, rough, N); if (rc) return rc; }
+    // ---------------- S2: WLS (k_wls_mg.hip)
+    {
+        // ColorTransfer.cpp:1418-1424 with the target's own ratio; the x4 of a level that already has the working size stays tied to the working size (SPEC §6.1)
+        const double r = (double)((long long)H * W) / (double)((long long)h * w);
+        double lamda = prm.wls_lambda_init * r;
+        if (h == Hw && w == Ww) lamda *= 4;
+        DevBuf<double> gx(ctx, N), gy(ctx, N), diag(ctx, N), wx(ctx, N), wy(ctx, N);
+        if (!gx.ok() || !gy.ok() || !diag.ok() || !wx.ok() || !wy.ok()) return NCT_ERR_HIP;
+        hipLaunchKernelGGL(k_gradient_weights, dim3(nbL), dim3(256), 0, s, s_lab_full, H, W, lamda, prm.wls_alpha, (double*)gx, (double*)gy); LCHK();
+        hipLaunchKernelGGL(k_wls_system, dim3(nbL), dim3(256), 0, s, (const double*)gx, (const double*)gy, (const double*)rough, H, W, (double*)diag, (double*)wx, (double*)wy); LCHK();
+        int wit[6] = {0, 0, 0, 0, 0, 0};
+        { int rcm = ctx->mark(s, nct_stage_tag_color()); if (rcm) return rcm; }
+        int rc = nctk_wls_solve_mg(ctx, s, X, rough, wx, wy, H, W, ctx->wls_rtol, wit); if (rc) return rc;
+        { int rcm = ctx->mark(s, nct_stage_tag_wls()); if (rcm) return rcm; }
+        if (dbg && dbg->wls_iters) for (int q = 0; q < 6; ++q) dbg->wls_iters[q] = wit[q];
+    }
+    if (dbg) { int rc = dbg_copy(ctx, s, dbg->ab_wls, X, (size_t)6 * N); if (rc) return rc; }
+    // ---------------- A1
+    hipLaunchKernelGGL(k_apply, dim3(cdiv(3 * N, 256)), dim3(256), 0, s, (const double*)Xa, (const double*)Xb, s_lab_full, N, out_lab_full); LCHK();
+    return 0;
+}
+
 int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, const uint8_t* s_lab_level, const uint8_t* g_lab_level,
                               const uint8_t* s_lab_full, const int* knn_id, const double* knn_w, int layer, int h, int w, int H, int W,
-                              const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg, const nct_s1_graph* graph) {
-    const int n = h * w, N = H * W;
-    const int nbl = cdiv(n, 256), nbL = cdiv(N, 256);
+                              const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg, const nct_s1_graph* graph,
+                              const nct_finish_target* fin) {
+    const int n = h * w;
+    const int nbl = cdiv(n, 256);
     // ---------------- T1 + T2
     DevBuf<double> x(ctx, (size_t)6 * n), weight(ctx, n);
     DevBuf<unsigned> mm(ctx, 2);
@@ -168,34 +214,6 @@ int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, con
     }
     { int rcm = ctx->mark(s, nct_stage_tag_nonlocal()); if (rcm) return rcm; }
     if (dbg) { int rc = dbg_copy(ctx, s, dbg->ab_nonlocal, x, (size_t)6 * n); if (rc) return rc; }
-    // ---------------- U1: bilinear upsample to full resolution + roughness
-    DevBuf<double> X(ctx, (size_t)6 * N), rough(ctx, N);
-    if (!X.ok() || !rough.ok()) return NCT_ERR_HIP;
-    double* Xa = X; double* Xb = (double*)X + (size_t)3 * N;
-    if (W > w || H > h) {
-        int rc = nctk_resize_f64c3(ctx, s, xa, h, w, Xa, H, W); if (rc) return rc;
-        rc = nctk_resize_f64c3(ctx, s, xb, h, w, Xb, H, W); if (rc) return rc;
-    } else {
-        NCT_HIP(hipMemcpyAsync(X, x, sizeof(double) * (size_t)6 * N, hipMemcpyDeviceToDevice, s));
-    }
-    hipLaunchKernelGGL(k_roughness, dim3(nbL), dim3(256), 0, s, (const double*)Xa, (const double*)Xb, s_lab_full, N, (double*)rough); LCHK();
-    if (dbg) { int rc = dbg_copy(ctx, s, dbg->ab_up, X, (size_t)6 * N); if (rc) return rc; rc = dbg_copy(ctx, s, dbg->rough, rough, N); if (rc) return rc; }
-    // ---------------- S2: WLS (k_wls_mg.hip)
-    {
-        double lamda = prm.wls_lambda_init * normFactor;
-        if (h == H && w == W) lamda *= 4;                               // ColorTransfer.cpp:1418-1424
-        DevBuf<double> gx(ctx, N), gy(ctx, N), diag(ctx, N), wx(ctx, N), wy(ctx, N);
-        if (!gx.ok() || !gy.ok() || !diag.ok() || !wx.ok() || !wy.ok()) return NCT_ERR_HIP;
-        hipLaunchKernelGGL(k_gradient_weights, dim3(nbL), dim3(256), 0, s, s_lab_full, H, W, lamda, prm.wls_alpha, (double*)gx, (double*)gy); LCHK();
-        hipLaunchKernelGGL(k_wls_system, dim3(nbL), dim3(256), 0, s, (const double*)gx, (const double*)gy, (const double*)rough, H, W, (double*)diag, (double*)wx, (double*)wy); LCHK();
-        int wit[6] = {0, 0, 0, 0, 0, 0};
-        { int rcm = ctx->mark(s, nct_stage_tag_color()); if (rcm) return rcm; }
-        int rc = nctk_wls_solve_mg(ctx, s, X, rough, wx, wy, H, W, ctx->wls_rtol, wit); if (rc) return rc;
-        { int rcm = ctx->mark(s, nct_stage_tag_wls()); if (rcm) return rcm; }
-        if (dbg && dbg->wls_iters) for (int q = 0; q < 6; ++q) dbg->wls_iters[q] = wit[q];
-    }
-    if (dbg) { int rc = dbg_copy(ctx, s, dbg->ab_wls, X, (size_t)6 * N); if (rc) return rc; }
-    // ---------------- A1
-    hipLaunchKernelGGL(k_apply, dim3(cdiv(3 * N, 256)), dim3(256), 0, s, (const double*)Xa, (const double*)Xb, s_lab_full, N, out_lab_full); LCHK();
-    return 0;
+    if (fin) return nctk_color_finish(ctx, s, x, h, w, H, W, fin->s_lab, fin->H, fin->W, prm, fin->out_lab, dbg);
+    return nctk_color_finish(ctx, s, x, h, w, H, W, s_lab_full, H, W, prm, out_lab_full, dbg);
 }

@@ -8,6 +8,7 @@
 #include <mutex>
 
 static std::string g_create_err;
+void nct_set_ctxless_error(const char* msg) { g_create_err = msg; }   // the message of a failed entry point that takes no context (nct_last_error(NULL))
 void nct_vgg_free(nct_ctx* ctx);   // nct_vgg.cpp
 
 void* nct_ctx::alloc(size_t bytes) {

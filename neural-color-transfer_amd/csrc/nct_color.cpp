@@ -121,4 +121,27 @@ int nct_local_color_transfer(nct_ctx* ctx, const float* err, const uint8_t* s_bg
     return NCT_OK;
 }
 
+// the finish alone (SPEC §6.1): U1 / roughness / S2 / A1 of S1's coefficients onto s_bgr_full, which may be larger than the working size
+int nct_color_finish(nct_ctx* ctx, const double* ab, int h, int w, int work_h, int work_w, const uint8_t* s_bgr_full, int H, int W, const nct_params* prm,
+                     uint8_t* out_bgr_full, nct_color_stages* stages) {
+    CTX_ENTER();
+    NCT_REQUIRE(ab && s_bgr_full && prm && out_bgr_full, "color_finish: null pointer");
+    NCT_REQUIRE(h > 0 && w > 0 && work_h >= h && work_w >= w && H >= h && W >= w, "color_finish: bad geometry (level %dx%d, working %dx%d, target %dx%d)", w, h, work_w, work_h, W, H);
+    NCT_REQUIRE(H <= NCT_FINISH_MAX_SIDE && W <= NCT_FINISH_MAX_SIDE && (long long)H * W <= NCT_FINISH_MAX_PIXELS, "color_finish: target %dx%d above 16384 per side or 2^26 pixels", W, H);
+    const size_t n = (size_t)h * w, N = (size_t)H * W;
+    DevBuf<double> x(ctx, 6 * n);
+    DevBuf<uint8_t> sf(ctx, N * 3), sflab(ctx, N * 3), olab(ctx, N * 3), obgr(ctx, N * 3);
+    if (!x.ok() || !sf.ok() || !sflab.ok() || !olab.ok() || !obgr.ok()) return NCT_ERR_HIP;
+    H2D(x, ab, sizeof(double) * 6 * n); H2D(sf, s_bgr_full, N * 3);
+    RC(nctk_bgr2lab(ctx, ctx->stream, sf, sflab, N));
+    nct_color_params cp{prm->eps, prm->nonlocal_weight, prm->local_weight, prm->wls_lambda_init, prm->wls_alpha, (double)prm->k_num};
+    nct_color_debug dbg{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (stages) { dbg.ab_up = stages->ab_up; dbg.rough = stages->roughness; dbg.ab_wls = stages->ab_wls; dbg.wls_iters = stages->wls_iters; }
+    ctx->wls_split = (prm->flags & NCT_FLAG_LATENCY) ? 1 : 0;
+    RC(nctk_color_finish(ctx, ctx->stream, x, h, w, work_h, work_w, sflab, H, W, cp, olab, stages ? &dbg : nullptr));
+    RC(nctk_lab2bgr(ctx, ctx->stream, olab, obgr, N, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0));
+    D2H(out_bgr_full, obgr, N * 3); SYNC();
+    return NCT_OK;
+}
+
 }  // extern "C"

@@ -156,10 +156,23 @@ int nctk_s1_solve(nct_ctx* ctx, hipStream_t s, const nct_s1_graph& g, const int*
 // k_colorsolve.hip
 struct nct_color_params { double eps, nonlocal_weight, local_weight, wls_lambda_init, wls_alpha, k_num; };
 struct nct_color_debug { double *ab_local, *ab_nonlocal, *ab_up, *rough, *ab_wls; int* cg_iters; int* wls_iters; };   // host pointers, all nullable
+// a finish target other than the working grid (SPEC §6.1): the source at its original size H x W in 8-bit Lab, and where its recoloured Lab goes
+struct nct_finish_target { const uint8_t* s_lab; int H, W; uint8_t* out_lab; };
+// the largest finish target: S2's hierarchy stays within MG_MAXL levels (k_wls_mg.hip) and each of its arrays below 4 GB (6 fp64 right-hand sides: 3.2 GB)
+#define NCT_FINISH_MAX_SIDE 16384
+#define NCT_FINISH_MAX_PIXELS (1LL << 26)
+// H x W: the working size (S1's dWeight); fin (nullable) retargets U1 / S2 / A1 — null: they target H x W, s_lab_full, out_lab_full
 int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, const uint8_t* s_lab_level, const uint8_t* g_lab_level,
                               const uint8_t* s_lab_full, const int* knn_id, const double* knn_w, int layer, int h, int w, int H, int W,
                               const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg,
-                              const nct_s1_graph* graph = nullptr /* the level's prebuilt graph part of S1; null: built inside, on s */);
+                              const nct_s1_graph* graph = nullptr /* the level's prebuilt graph part of S1; null: built inside, on s */,
+                              const nct_finish_target* fin = nullptr);
+// U1 + roughness + S2 + A1 of coefficients x ([2][h*w][3], device) onto the grid H x W of s_lab_full; Hw x Ww = the working size (the x4 of S2's lambda)
+int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int Hw, int Ww, const uint8_t* s_lab_full, int H, int W,
+                      const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg);
+// SPEC §6.1 rule 1 + the limits of rule 5: nullptr and the working size, or the reason the image is refused (a static string)
+const char* nct_working_size_rule(int h, int w, int max_side, int* work_h, int* work_w);
+void nct_set_ctxless_error(const char* msg);   // nct_api.cpp
 // k_wls_mg.hip
 int nctk_wls_solve_mg(nct_ctx* ctx, hipStream_t s, double* X, const double* rough, const double* wx, const double* wy, int H, int W,
                       double rtol, int* iters_out);

@@ -65,8 +65,11 @@ static int read_marks(nct_ctx* ctx, nct_pair_timing* t) {
     return 0;
 }
 
-// run the whole L=5->1 loop on device-resident images
-static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* lv) {
+// the full-resolution finish of the last level (nct_process_pair_fullres, SPEC §6.1): the original source on the device and where its result goes
+struct fullres_target { const uint8_t* src; int H, W; uint8_t* out; };
+
+// run the whole L=5->1 loop on device-resident images; fin (nullable) moves the last level's U1 / S2 / A1 onto the original source
+static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* lv, const fullres_target* fin = nullptr) {
     pair_state* P = (pair_state*)ctx->pair;
     if (!P || !P->src || !P->ref) return ctx->fail(NCT_ERR_STATE, "process: no pair uploaded");
     hipStream_t s = ctx->stream;
@@ -74,6 +77,7 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
     NCT_REQUIRE(prm->patch_size == 3 && prm->k_num == 8, "process: patch_size must be 3 and k_num 8 (Config.h:68-70)");
     NCT_REQUIRE(prm->cluster_num >= 1 && prm->cluster_num <= 16, "process: cluster_num out of range");
     NCT_REQUIRE(prm->levels >= 1 && prm->levels <= 5, "process: levels must be in [1, 5] (got %d)", prm->levels);
+    NCT_REQUIRE(!fin || !lv, "process: no level intermediates with a full-resolution finish");
     if (timing) memset(timing, 0, sizeof *timing);
     auto wall0 = std::chrono::steady_clock::now();
     ctx->tm_on = timing != nullptr; ctx->tm_tags.clear(); ctx->tm_host.clear();
@@ -265,9 +269,20 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
         (void)hipGetLastError();                                     // hipEventQuery's hipErrorNotReady is not an error
         ctx->s1_hub_blocks_last[l] = hub_hint;
         const nct_s1_graph s1graph = s1g[l]->view(hub_hint, sup_hint);
-        rc = nctk_local_color_transfer(ctx, s, err, s_lab_l, g_lab_l, s_lab_full, knn_id, knn_w, l, ah[l], aw[l], H, W, cp, out_lab, (timing || cs) ? &dbg : nullptr, &s1graph); if (rc) return rc;
-        if (cs && cs->wls_iters) for (int q = 0; q < 6; ++q) cs->wls_iters[q] = wls_it[q];
-        rc = nctk_lab2bgr(ctx, s, out_lab, P->out, N, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0); if (rc) return rc;
+        if (fin && l == nlevels - 1) {
+            // the last level finishes on the original source: S0 in Lab once, here (its time counts as colour stage), U1 / S2 / A1 at H0 x W0
+            const size_t N0 = (size_t)fin->H * fin->W;
+            DevBuf<uint8_t> s0_lab(ctx, N0 * 3), out0_lab(ctx, N0 * 3);
+            if (!s0_lab.ok() || !out0_lab.ok()) return NCT_ERR_HIP;
+            rc = nctk_bgr2lab(ctx, s, fin->src, s0_lab, N0); if (rc) return rc;
+            const nct_finish_target ft{s0_lab, fin->H, fin->W, out0_lab};
+            rc = nctk_local_color_transfer(ctx, s, err, s_lab_l, g_lab_l, s_lab_full, knn_id, knn_w, l, ah[l], aw[l], H, W, cp, out_lab, timing ? &dbg : nullptr, &s1graph, &ft); if (rc) return rc;
+            rc = nctk_lab2bgr(ctx, s, out0_lab, fin->out, N0, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0); if (rc) return rc;
+        } else {
+            rc = nctk_local_color_transfer(ctx, s, err, s_lab_l, g_lab_l, s_lab_full, knn_id, knn_w, l, ah[l], aw[l], H, W, cp, out_lab, (timing || cs) ? &dbg : nullptr, &s1graph); if (rc) return rc;
+            if (cs && cs->wls_iters) for (int q = 0; q < 6; ++q) cs->wls_iters[q] = wls_it[q];
+            rc = nctk_lab2bgr(ctx, s, out_lab, P->out, N, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0); if (rc) return rc;
+        }
         if (timing) { timing->wls_iters[l] = *std::max_element(wls_it, wls_it + 6); }
         MARK(ST_COLOR, l);
         if (lv) { rc = d2h(lv->result[l], P->out, N * 3); if (rc) return rc; }
@@ -299,6 +314,23 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
         }
     }
     return NCT_OK;
+}
+
+// SPEC §6.1 rule 1 (host/main.cpp's shrink: the longer side becomes max_side, the other (int)(max_side / (float)long * short)) and the limits of rule 5
+const char* nct_working_size_rule(int h, int w, int max_side, int* work_h, int* work_w) {
+    if (!work_h || !work_w) return "null output pointer";
+    if (max_side < 17 || max_side > 4000) return "max_side must be in [17, 4000]";
+    if (h < 1 || w < 1) return "image sides must be positive";
+    if (h > NCT_FINISH_MAX_SIDE || w > NCT_FINISH_MAX_SIDE) return "image sides must be at most 16384";
+    if ((long long)h * w > NCT_FINISH_MAX_PIXELS) return "images must have at most 2^26 pixels";
+    int ch = h, cw = w;
+    if (w > max_side || h > max_side) {
+        cw = max_side; ch = (int)(cw / (float)w * h);
+        if (w < h) { ch = max_side; cw = (int)(ch / (float)h * w); }
+    }
+    if (ch < 17 || cw < 17) return "the working size has a side below 17";
+    *work_h = ch; *work_w = cw;
+    return nullptr;
 }
 
 extern "C" {
@@ -354,6 +386,61 @@ int nct_process_pair(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const
     int rc = nct_pair_upload(ctx, src_bgr, sh, sw, ref_bgr, rh, rw); if (rc) return rc;
     rc = nct_pair_run(ctx, prm, timing); if (rc) return rc;
     return nct_pair_download(ctx, out_bgr);
+}
+
+int nct_working_size(int h, int w, int max_side, int* work_h, int* work_w) {
+    const char* why = nct_working_size_rule(h, w, max_side, work_h, work_w);
+    if (why) { nct_set_ctxless_error(why); return NCT_ERR_INVALID; }
+    return NCT_OK;
+}
+
+int nct_process_pair_fullres(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw, int max_side,
+                             const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
+    if (!ctx) return NCT_ERR_INVALID;
+    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_REQUIRE(src_bgr && ref_bgr && prm && out_bgr, "process_pair_fullres: null pointer");
+    int wh = 0, ww = 0, rwh = 0, rww = 0;
+    const char* why = nct_working_size_rule(sh, sw, max_side, &wh, &ww);
+    if (why) return ctx->fail(NCT_ERR_INVALID, "process_pair_fullres: source %dx%d: %s", sw, sh, why);
+    why = nct_working_size_rule(rh, rw, max_side, &rwh, &rww);
+    if (why) return ctx->fail(NCT_ERR_INVALID, "process_pair_fullres: reference %dx%d: %s", rw, rh, why);
+    const bool shrunk = wh != sh || ww != sw;
+    // the originals go to the arena and are shrunk there (rule 1: nct_resize_u8c3's arithmetic); the pair state holds the working-size pair
+    pair_state* P = pair_of(ctx);
+    if (P->src) { ctx->release(P->src); P->src = nullptr; }
+    if (P->ref) { ctx->release(P->ref); P->ref = nullptr; }
+    if (P->out) { ctx->release(P->out); P->out = nullptr; }
+    DevBuf<uint8_t> s0(ctx, (size_t)sh * sw * 3);
+    if (!s0.ok()) return NCT_ERR_HIP;
+    P->src = (uint8_t*)ctx->alloc((size_t)wh * ww * 3);
+    P->ref = (uint8_t*)ctx->alloc((size_t)rwh * rww * 3);
+    if (!P->src || !P->ref) return NCT_ERR_HIP;
+    P->sh = P->sw = P->rh = P->rw = 0;
+    NCT_HIP(hipMemcpyAsync(s0, src_bgr, (size_t)sh * sw * 3, hipMemcpyHostToDevice, ctx->stream));
+    int rc = nctk_resize_u8c3(ctx, ctx->stream, s0, sh, sw, P->src, wh, ww); if (rc) return rc;
+    {
+        DevBuf<uint8_t> r0(ctx, (size_t)rh * rw * 3);
+        if (!r0.ok()) return NCT_ERR_HIP;
+        NCT_HIP(hipMemcpyAsync(r0, ref_bgr, (size_t)rh * rw * 3, hipMemcpyHostToDevice, ctx->stream));
+        rc = nctk_resize_u8c3(ctx, ctx->stream, r0, rh, rw, P->ref, rwh, rww); if (rc) return rc;
+    }
+    NCT_HIP(hipStreamSynchronize(ctx->stream));
+    P->sh = wh; P->sw = ww; P->rh = rwh; P->rw = rww;
+    if (!shrunk) {
+        // rule 4: a source that is not shrunk has nothing to finish at another size — this is nct_process_pair on (S0, shrunk R)
+        rc = process_resident(ctx, prm, timing, nullptr); if (rc) return rc;
+        return nct_pair_download(ctx, out_bgr);
+    }
+    DevBuf<uint8_t> o0(ctx, (size_t)sh * sw * 3);
+    if (!o0.ok()) return NCT_ERR_HIP;
+    const fullres_target fin{s0, sh, sw, o0};
+    rc = process_resident(ctx, prm, timing, nullptr, &fin);
+    // the working-size result buffer holds the second-to-last level's image: no nct_pair_download of it
+    if (P->out) { ctx->release(P->out); P->out = nullptr; }
+    if (rc) return rc;
+    NCT_HIP(hipMemcpyAsync(out_bgr, o0, (size_t)sh * sw * 3, hipMemcpyDeviceToHost, ctx->stream));
+    NCT_HIP(hipStreamSynchronize(ctx->stream));
+    return NCT_OK;
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 // extensions `-gpus N` (pairs sharded over N GPUs, one context per worker thread), `-inflight K`, `-io T` (shared decode/encode pool: the GPU workers never
 // touch zlib), `-pin` (threads on the GPU's NUMA node), weights parsed once per process and held once per GPU, `-seed`, `-levels L` (BASELINE
 // config 1: "L=5 only" = -levels 1), `-resume 1` (skip pairs whose output exists; <out>/status.jsonl gets one JSON line per pair)
-// and `-feat16 1` (reduced-precision PatchMatch features; not bit-identical).
+// and `-feat16 1` (reduced-precision PatchMatch features; not bit-identical), `-fullres 1` (the result at the content image's own size, SPEC §6.1).
 #include <sys/stat.h>
 #include <sys/wait.h>
 #include <fcntl.h>
@@ -107,7 +107,7 @@ std::string stem(const std::string& path) {          // main.cu:524-531 (find_la
 struct Pair { std::string cnt, stl; float bds; };
 std::mutex g_print;
 
-struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false; int rank = 0, world = 1; };
+struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false, fullres = false; int rank = 0, world = 1; };
 
 // ---- ENABLE_VIS debug outputs (Config.h:8) behind the runtime flag -vis 1: per pyramid level the flow maps of both NNFs (reconstruct_flow,
 // GeneralizedPatchMatch.cu:337-353), the level images tCnt / tStl (main.cu:343-347), the matching-error heat map (getHeat,
@@ -314,7 +314,30 @@ void load_pair(const Config& cfg, Job& j) {
     j.say("Read style file: %s, w = %d, h = %d\n", stlStr.c_str(), j.stl.w, j.stl.h);
 }
 
+// the reference's per-level lines (main.cu:331; ColorTransfer.cpp:1373,1434), then its total (main.cu:453); the decoded inputs are dropped
+void log_times(Job& j, const nct_params& prm, const nct_pair_timing& tm) {
+    for (int l = 0; l < prm.levels; ++l) {
+        j.say("Patch Match Time: %lf sec.\n", (tm.pm_level_ms[l] + tm.vote_level_ms[l]) * 1e-3);
+        j.say("Nonlocal Solve Time: %lf\n", tm.nonlocal_level_ms[l] * 1e-3);
+        j.say("WLS Solve Time: %lf\n", tm.wls_level_ms[l] * 1e-3);
+    }
+    j.say("VGG19 Time: %lf sec.\n", tm.vgg_ms * 1e-3);
+    j.say("**Finished Time: %lf sec.\n", tm.total_ms * 1e-3);
+    j.stl.px.clear(); j.stl.px.shrink_to_fit();
+    j.cnt.px.clear(); j.cnt.px.shrink_to_fit();                 // the store stage needs only cnt.h / cnt.w
+}
+
 void run_pair(nct_ctx* ctx, const Config& cfg, Job& j) {
+    if (cfg.fullres) {                                          // -fullres 1: the library shrinks both images itself and returns the content image at its own size
+        nct_params prm = cfg.prm;
+        prm.bds_weight = j.p.bds;
+        j.out.resize((size_t)j.cnt.h * j.cnt.w * 3);
+        nct_pair_timing tm;
+        const int rc = nct_process_pair_fullres(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, j.stl.px.data(), j.stl.h, j.stl.w, MAX_SIZE, &prm, j.out.data(), &tm);
+        if (rc != NCT_OK) { j.say("Error: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
+        log_times(j, prm, tm);
+        return;
+    }
     if (!shrink(ctx, j.cnt) || !shrink(ctx, j.stl)) { j.say("Error: resize failed: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
     nct_params prm = cfg.prm;
     prm.bds_weight = j.p.bds;                                   // the per-line weight overrides -bds (main.cu:475)
@@ -328,16 +351,7 @@ void run_pair(nct_ctx* ctx, const Config& cfg, Job& j) {
         const int rc = nct_process_pair(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, j.stl.px.data(), j.stl.h, j.stl.w, &prm, j.out.data(), &tm);
         if (rc != NCT_OK) { j.say("Error: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
     }
-    // the reference's per-level lines (main.cu:331; ColorTransfer.cpp:1373,1434), then its total (main.cu:453)
-    for (int l = 0; l < prm.levels; ++l) {
-        j.say("Patch Match Time: %lf sec.\n", (tm.pm_level_ms[l] + tm.vote_level_ms[l]) * 1e-3);
-        j.say("Nonlocal Solve Time: %lf\n", tm.nonlocal_level_ms[l] * 1e-3);
-        j.say("WLS Solve Time: %lf\n", tm.wls_level_ms[l] * 1e-3);
-    }
-    j.say("VGG19 Time: %lf sec.\n", tm.vgg_ms * 1e-3);
-    j.say("**Finished Time: %lf sec.\n", tm.total_ms * 1e-3);
-    j.stl.px.clear(); j.stl.px.shrink_to_fit();
-    j.cnt.px.clear(); j.cnt.px.shrink_to_fit();                 // the store stage needs only cnt.h / cnt.w
+    log_times(j, prm, tm);
 }
 
 void store_pair(Job& j) {
@@ -383,8 +397,9 @@ struct Pipeline {
     // bounded by bytes as well as by count — a new load starts only while the decoded backlog is below byte_cap (or nothing at all is queued or loading)
     // Loads in flight are charged too: a load reserves `load_estimate` bytes when it starts — the largest decoded pair seen so far, at least two 1000 x 1000
     // images — and is corrected to its real size when it lands in `ready`, so several I/O threads cannot all pass the test while the backlog is still being decoded.
-    size_t ready_bytes = 0, byte_cap = (size_t)1 << 30, loading_bytes = 0, load_estimate = (size_t)6 << 20;
-    bool may_load() const { return !exhausted && ready.size() + loading < cap && (ready_bytes + loading_bytes < byte_cap || ready.size() + loading == 0); }
+    // Results waiting for the encoder are charged as well (`results_bytes`): with -fullres 1 an output has the content image's own size, up to 192 MB.
+    size_t ready_bytes = 0, byte_cap = (size_t)1 << 30, loading_bytes = 0, load_estimate = (size_t)6 << 20, results_bytes = 0;
+    bool may_load() const { return !exhausted && ready.size() + loading < cap && (ready_bytes + loading_bytes + results_bytes < byte_cap || ready.size() + loading == 0); }
     bool loads_done() const { return exhausted && loading == 0; }
     bool all_done() const { return exhausted && finished == taken; }
 };
@@ -395,7 +410,7 @@ void io_thread(Pipeline& P, const Config& cfg, const std::vector<Pair>& pairs) {
         {
             std::unique_lock<std::mutex> lk(P.m);
             P.cv.wait(lk, [&] { return !P.results.empty() || P.may_load() || P.all_done(); });
-            if (!P.results.empty()) { j = std::move(P.results.front()); P.results.pop_front(); store = true; }       // encoding first: it frees memory and unblocks workers
+            if (!P.results.empty()) { j = std::move(P.results.front()); P.results.pop_front(); P.results_bytes -= j->out.size(); store = true; }       // encoding first: it frees memory and unblocks workers
             else if (P.may_load()) {
                 const long t = P.tickets.draw();
                 if (t < 0) { P.exhausted = true; lk.unlock(); P.cv.notify_all(); continue; }
@@ -442,6 +457,7 @@ void gpu_worker(Pipeline& P, nct_ctx* ctx, const Config& cfg) {
         } else {
             std::unique_lock<std::mutex> lk(P.m);
             P.cv.wait(lk, [&] { return P.results.size() < P.cap; });
+            P.results_bytes += j->out.size();
             P.results.push_back(std::move(j));
         }
         P.cv.notify_all();
@@ -471,7 +487,7 @@ int main(int argc, char** argv) {
     CmdLine cl;
     Config cfg;
     nct_params_default(&cfg.prm);
-    int gpu = 0, ngpus = 1, seed = 1, inflight = 1, levels = 5, resume = 0, feat16 = 0, vis = 0, io = -1, pin = 1, world = 1, rank = 0, steal = 0, procs = 0, rccl = 0;
+    int gpu = 0, ngpus = 1, seed = 1, inflight = 1, levels = 5, resume = 0, feat16 = 0, vis = 0, fullres = 0, io = -1, pin = 1, world = 1, rank = 0, steal = 0, procs = 0, rccl = 0;
     cl.add("m", cfg.model_dir, "Directory of network models.");
     cl.add("i", cfg.input_dir, "Input directory of content and style images and pairs.txt.");
     cl.add("o", cfg.output_dir, "Output directory of result images.");
@@ -491,6 +507,7 @@ int main(int argc, char** argv) {
     cl.add("levels", levels, "[extension] pyramid levels to run, coarse to fine: 5 = the full L=5..1 loop, 1 = L=5 only.");
     cl.add("resume", resume, "[extension] 1 = skip pairs whose output file exists and is a complete PNG; every pair appends a JSON line to <output>/status.jsonl.");
     cl.add("vis", vis, "[extension] 1 = the reference's ENABLE_VIS dumps per level (flow maps, level images, error heat map, coefficient and cluster images) next to the output.");
+    cl.add("fullres", fullres, "[extension] 1 = return the content image at its own size: the pyramid runs at most 1000 px on a side, its last level's WLS finish at the original size (SPEC 6.1); not with -vis 1.");
     cl.add("procs", procs, "[extension] N > 0: fork N processes, one per GPU (-g, -g + 1, ...): process r runs with -rank r -world N on its own device, HIP runtime and status.<r>.jsonl (the process-per-GPU shape; -gpus N keeps all GPUs in one process).");
     cl.add("world", world, "[extension] number of cooperating processes that share this pairs.txt and output directory (default 1); set by -procs, or by hand with -rank.");
     cl.add("rank", rank, "[extension] this process's rank in [0, world): it runs the pairs.txt lines i with i mod world = rank (or the ones it draws, -steal 1).");
@@ -511,6 +528,7 @@ int main(int argc, char** argv) {
     }
     if (!parsed) return -1;
     if (world < 1 || rank < 0 || rank >= world) { printf("Error: -rank %d is not in [0, -world %d).\n", rank, world); return -1; }
+    if (fullres && vis) { printf("Error: -fullres 1 cannot be combined with -vis 1 (the -vis dumps are working-size images).\n"); return -1; }
     mkdir(cfg.output_dir.c_str(), 0777);                                    // main.cu:458
     uint64_t run_token = getenv("NCT_RUN_TOKEN") ? strtoull(getenv("NCT_RUN_TOKEN"), nullptr, 0) : 0;      // hand-started ranks of one run share it (and remove <output>/.rccl_id between runs)
     const std::string tickets_path = cfg.output_dir + "/.tickets";
@@ -544,6 +562,7 @@ int main(int argc, char** argv) {
     if (inflight <= 1) cfg.prm.flags |= NCT_FLAG_LATENCY;          // one pair at a time per GPU: split WLS solves (same result, -3 ms per 700x700 pair)
     cfg.resume = resume != 0;
     cfg.vis = vis != 0;
+    cfg.fullres = fullres != 0;
     if (ngpus < 1) ngpus = 1;
     if (inflight < 1) inflight = 1;
     if (inflight > 8) inflight = 8;

@@ -86,6 +86,9 @@ SIGNATURES = {
     "nct_knn_graph": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _f64p]),
     "nct_local_color_transfer": (C.c_int, [C.c_void_p, _f32p, _u8p, _u8p, _u8p, _i32p, _f64p] + [C.c_int] * 5 + [C.c_void_p, _u8p, C.c_void_p]),
     "nct_process_pair": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p]),
+    "nct_working_size": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nct_process_pair_fullres": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p]),
+    "nct_color_finish": (C.c_int, [C.c_void_p, _f64p] + [C.c_int] * 4 + [_u8p, C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p]),
     "nct_pair_upload": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int]),
     "nct_pair_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_pair_run_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -162,6 +165,15 @@ FLAG_LAB2BGR_CUBE = 8
 FLAG_TIME_KERNELS = 16
 KT_NAMES = ("s1_apply", "s1_scalars", "s1_update", "wls_down", "wls_up", "wls_apply", "wls_update", "wls_coarse", "wls_block_pre", "wls_block_post")      # nct.h NCT_KT_*
 LAB2BGR_PIECEWISE, LAB2BGR_CUBE = 0, 1
+
+
+def working_size(h, w, max_side=1000):
+    """nct_working_size (SPEC §6.1 rule 1 + the limits of rule 5; no GPU needed): the (h, w) the pyramid runs at; NctError when refused"""
+    wh, ww = C.c_int(), C.c_int()
+    rc = lib().nct_working_size(h, w, max_side, C.byref(wh), C.byref(ww))
+    if rc != 0:
+        raise NctError(rc, (lib().nct_last_error(None) or b"").decode())
+    return wh.value, ww.value
 
 
 class Model:
@@ -481,6 +493,33 @@ class Context:
         self._chk(self._l.nct_process_pair(self._h, s.reshape(-1, 3), s.shape[0], s.shape[1], r.reshape(-1, 3), r.shape[0], r.shape[1],
                                            C.addressof(prm), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
         return (out, tm.as_dict()) if want_timing else out
+
+    def process_pair_fullres(self, src_bgr, ref_bgr, max_side=1000, params=None, want_timing=False):
+        """nct_process_pair_fullres: the pair runs at working_size(..., max_side), the last level finishes on the original source (result: src's size)"""
+        s = np.ascontiguousarray(src_bgr, np.uint8)
+        r = np.ascontiguousarray(ref_bgr, np.uint8)
+        prm = params or Params.default()
+        out = np.empty_like(s)
+        tm = PairTiming() if want_timing else None
+        self._chk(self._l.nct_process_pair_fullres(self._h, s.reshape(-1, 3), s.shape[0], s.shape[1], r.reshape(-1, 3), r.shape[0], r.shape[1], max_side,
+                                                   C.addressof(prm), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
+        return (out, tm.as_dict()) if want_timing else out
+
+    def color_finish(self, ab, h, w, work_h, work_w, s_full, params=None, want_stages=False):
+        """nct_color_finish: U1 / roughness / S2 / A1 of ab ([2][h*w][3], S1's ab_nonlocal) onto s_full (H x W x 3 BGR) in a pyramid of working size work_h x work_w"""
+        a = np.ascontiguousarray(ab, np.float64).reshape(-1)
+        assert a.size == 6 * h * w
+        s_full = np.ascontiguousarray(s_full, np.uint8)
+        H, W = s_full.shape[:2]
+        prm = params or Params.default()
+        out = np.empty((H, W, 3), np.uint8)
+        st, keep = None, {}
+        if want_stages:
+            keep = {"ab_up": np.empty((2, H * W, 3)), "roughness": np.empty(H * W), "ab_wls": np.empty((2, H * W, 3)), "wls_iters": np.zeros(6, np.int32)}
+            st = ColorStages(None, None, keep["ab_up"].ctypes.data, keep["roughness"].ctypes.data, keep["ab_wls"].ctypes.data, None, keep["wls_iters"].ctypes.data)
+        self._chk(self._l.nct_color_finish(self._h, a, h, w, work_h, work_w, s_full.reshape(-1, 3), H, W, C.addressof(prm), out.reshape(-1, 3),
+                                           C.addressof(st) if st else None))
+        return (out, keep) if want_stages else out
 
     def pair_upload(self, src_bgr, ref_bgr):
         s = np.ascontiguousarray(src_bgr, np.uint8)
