@@ -26,8 +26,9 @@ extern "C" {
 #endif
 
 /* bumped whenever a struct of this header changes layout or an entry point changes meaning (round 6: 110 — nct_model_layer; nct_pair_timing grew in round 5 without a
- * bump). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI and the python binding do. */
-#define NCT_VERSION 110
+ * bump; 111 — nct_multi_levels and the entry points for several references). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
+ * and the python binding do. */
+#define NCT_VERSION 111
 
 typedef enum {
     NCT_OK = 0,
@@ -255,6 +256,40 @@ int nct_process_pair_fullres(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int s
                              const nct_params* prm, uint8_t* out_bgr /* sh x sw x 3 */, nct_pair_timing* timing);
 int nct_color_finish(nct_ctx* ctx, const double* ab, int h, int w, int work_h, int work_w, const uint8_t* s_bgr_full, int H, int W, const nct_params* prm,
                      uint8_t* out_bgr_full, nct_color_stages* stages);
+
+/* ---- several references (SPEC §6.2; an extension: the paper describes it, the reference ships the single-reference form only).
+ * Every level runs nct_pair_run's correspondence once per reference R_k (its own NNFs, its own random-search radius max(H, W, RH_k, RW_k), the single-pair seeds),
+ * which gives K guidance images G_k and matching errors E_k on the source's level grid. The selection then labels every pixel with the reference whose error,
+ * summed over the 3 x 3 window in double (NaN = 0.0, taps outside the grid skipped, dy outer / dx inner), is smallest — the lowest index on a tie — and merges
+ * G and E by that label; the rest of the level (Lab, kNN graph, T1 … A1, re-predict) runs once, unchanged. K = 1 is nct_process_pair byte for byte and
+ * enqueues the same launches; a list that repeats one image gives the K = 1 result and the label 0 everywhere.
+ * nct_select_reference: the selection alone. err[k]: h*w fp32, guide_bgr[k]: h*w*3; label (h*w), guide_out (h*w*3), err_out (h*w; the selected fp32 WORD, a NaN
+ * stays that NaN) are all nullable. Host pointers, synchronous; the _dev form takes device pointers (the two arrays OF pointers are host memory: they travel
+ * in the kernel's argument block) and is enqueued on the context's stream like the other device-pointer seams.
+ * nct_multi_upload / _run / _run_levels / nct_process_multi mirror the nct_pair_* calls; every image obeys nct_pair_upload's limits, 1 <= K <= NCT_MAX_REFS,
+ * anything else is NCT_ERR_INVALID with a message. nct_pair_download fetches the result of either form. nct_pair_timing: patchmatch_ms, vote_ms,
+ * pm_level_ms[l] and pm_level_launches[l] are sums over the references; the selection counts as vote time. */
+#define NCT_MAX_REFS 8
+/* per-level intermediates of a run with several references (all pointers nullable; sizes as in nct_pair_levels, per reference k < K its own bh*bw) */
+typedef struct nct_multi_levels {
+    uint32_t* ann[NCT_MAX_REFS][5]; uint32_t* bnn[NCT_MAX_REFS][5];
+    float* annd[NCT_MAX_REFS][5]; float* bnnd[NCT_MAX_REFS][5];
+    uint8_t* ref_guide[NCT_MAX_REFS][5];   /* G_k */
+    float* ref_err[NCT_MAX_REFS][5];       /* E_k */
+    uint8_t* label[5];                     /* [ah*aw] the selected reference per pixel */
+    uint8_t* guide[5];                     /* merged G */
+    float* err[5];                         /* merged E */
+    uint8_t* result[5];
+    int* labels;                           /* k-means labels, as in nct_pair_levels */
+} nct_multi_levels;
+int nct_select_reference(nct_ctx* ctx, const float* const* err, const uint8_t* const* guide_bgr, int K, int h, int w, uint8_t* label, uint8_t* guide_out, float* err_out);
+int nct_select_reference_dev(nct_ctx* ctx, const float* const* d_err, const uint8_t* const* d_guide_bgr, int K, int h, int w, uint8_t* d_label, uint8_t* d_guide_out,
+                             float* d_err_out);
+int nct_multi_upload(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw);
+int nct_multi_run(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing);
+int nct_multi_run_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_multi_levels* levels);
+int nct_process_multi(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw, const nct_params* prm,
+                      uint8_t* out_bgr, nct_pair_timing* timing);
 
 /* ---- device-pointer seams: the same operations on buffers that stay in HBM between calls (main.cu:204-316 keeps Ndata_C1, ann_device, ... on the device
  * across these kernels; an integrator replacing single seams should not pay H2D + D2H + a synchronise per call). Buffers come from the context's arena

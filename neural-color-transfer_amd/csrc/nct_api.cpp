@@ -290,6 +290,31 @@ int nct_feature_distance(nct_ctx* ctx, const float* a_chw, const float* b_chw, f
     return NCT_OK;
 }
 
+// SPEC §6.2 rules 2-3 on host maps: K error maps and guidance images up, one k_select_reference launch, label / merged guidance / merged error down
+int nct_select_reference(nct_ctx* ctx, const float* const* err, const uint8_t* const* guide_bgr, int K, int h, int w, uint8_t* label, uint8_t* guide_out, float* err_out) {
+    CTX_ENTER();
+    NCT_REQUIRE(K >= 1 && K <= NCT_MAX_REFS, "select_reference: K must be in [1, %d] (got %d)", NCT_MAX_REFS, K);
+    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "select_reference: grid %dx%d out of range", w, h);
+    NCT_REQUIRE(err && (guide_bgr || !guide_out), "select_reference: null map list");
+    for (int k = 0; k < K; ++k) NCT_REQUIRE(err[k] && (!guide_out || guide_bgr[k]), "select_reference: null map of reference %d", k);
+    const size_t n = (size_t)h * w;
+    DevBuf<float> e(ctx, n * K), eo(ctx, n);
+    DevBuf<uint8_t> g(ctx, guide_out ? n * 3 * K : 16), go(ctx, n * 3), lab(ctx, n);
+    if (!e.ok() || !eo.ok() || !g.ok() || !go.ok() || !lab.ok()) return NCT_ERR_HIP;
+    const float* de[NCT_MAX_REFS]; const uint8_t* dg[NCT_MAX_REFS];
+    for (int k = 0; k < K; ++k) {
+        de[k] = e + n * k; dg[k] = guide_out ? g + n * 3 * k : nullptr;
+        H2D(e + n * k, err[k], sizeof(float) * n);
+        if (guide_out) H2D(g + n * 3 * k, guide_bgr[k], n * 3);
+    }
+    RC(nctk_select_reference(ctx, ctx->stream, de, guide_out ? dg : nullptr, K, h, w, lab, guide_out ? (uint8_t*)go : nullptr, eo));
+    if (label) D2H(label, lab, n);
+    if (guide_out) D2H(guide_out, go, n * 3);
+    if (err_out) D2H(err_out, eo, sizeof(float) * n);
+    SYNC();
+    return NCT_OK;
+}
+
 int nct_bds_vote_image(nct_ctx* ctx, const uint8_t* a_bgr, int ah, int aw, const uint8_t* b_bgr, int bh, int bw,
                        const uint32_t* ann, const uint32_t* bnn, int patch, double w_coherence, double w_complete, uint8_t* out_bgr) {
     CTX_ENTER();

@@ -121,4 +121,10 @@ int nct_feature_distance_dev(nct_ctx* ctx, const float* a_hwc, const float* b_hw
     return nctk_feature_distance(ctx, ctx->stream, a_hwc, b_hwc, err, C, H * W);
 }
 
+int nct_select_reference_dev(nct_ctx* ctx, const float* const* d_err, const uint8_t* const* d_guide_bgr, int K, int h, int w, uint8_t* d_label, uint8_t* d_guide_out,
+                             float* d_err_out) {                                                                                                       /* SPEC §6.2 */
+    CTX_ENTER();
+    return nctk_select_reference(ctx, ctx->stream, d_err, d_guide_bgr, K, h, w, d_label, d_guide_out, d_err_out);
+}
+
 }  // extern "C"

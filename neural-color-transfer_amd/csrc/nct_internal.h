@@ -173,6 +173,10 @@ int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w
 // SPEC §6.1 rule 1 + the limits of rule 5: nullptr and the working size, or the reason the image is refused (a static string)
 const char* nct_working_size_rule(int h, int w, int max_side, int* work_h, int* work_w);
 void nct_set_ctxless_error(const char* msg);   // nct_api.cpp
+// k_select.hip — SPEC §6.2 rules 2-3: per pixel the reference with the smallest 3 x 3 error sum, and G / E merged by that label. err / guide: host arrays of K device
+// pointers (they go into the kernel's argument block); label, guide_out (then guide may be null too) and err_out are nullable
+int nctk_select_reference(nct_ctx* ctx, hipStream_t s, const float* const* err, const uint8_t* const* guide, int K, int h, int w,
+                          uint8_t* label, uint8_t* guide_out, float* err_out);
 // k_wls_mg.hip
 int nctk_wls_solve_mg(nct_ctx* ctx, hipStream_t s, double* X, const double* rough, const double* wx, const double* wy, int H, int W,
                       double rtol, int* iters_out);

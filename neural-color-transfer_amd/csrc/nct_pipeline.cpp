@@ -10,10 +10,13 @@
 #include <cstring>
 #include <algorithm>
 #include <cmath>
+#include <memory>
 
 struct pair_state {
-    uint8_t *src = nullptr, *ref = nullptr, *out = nullptr;    // device BGR images
-    int sh = 0, sw = 0, rh = 0, rw = 0;
+    uint8_t *src = nullptr, *out = nullptr;                    // device BGR images
+    uint8_t* ref[NCT_MAX_REFS] = {};                           // the K references (SPEC §6.2; a pair: K = 1)
+    int K = 0;
+    int sh = 0, sw = 0, rh[NCT_MAX_REFS] = {}, rw[NCT_MAX_REFS] = {};
 };
 static pair_state* pair_of(nct_ctx* ctx) {
     if (!ctx->pair) ctx->pair = new pair_state();
@@ -25,7 +28,7 @@ void nct_pair_free(nct_ctx* ctx) {
     if (!ctx->pair) return;
     pair_state* p = (pair_state*)ctx->pair;
     if (p->src) ctx->release(p->src);
-    if (p->ref) ctx->release(p->ref);
+    for (uint8_t* r : p->ref) if (r) ctx->release(r);
     if (p->out) ctx->release(p->out);
     delete p; ctx->pair = nullptr;
 }
@@ -68,16 +71,33 @@ static int read_marks(nct_ctx* ctx, nct_pair_timing* t) {
 // the full-resolution finish of the last level (nct_process_pair_fullres, SPEC §6.1): the original source on the device and where its result goes
 struct fullres_target { const uint8_t* src; int H, W; uint8_t* out; };
 
-// run the whole L=5->1 loop on device-resident images; fin (nullable) moves the last level's U1 / S2 / A1 onto the original source
-static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* lv, const fullres_target* fin = nullptr) {
+// what one reference owns during a run (SPEC §6.2): its image pyramid, its five un-normalised taps, its NNFs; with several references also its G_k and E_k
+struct ref_bufs {
+    int bh[5], bw[5], rs_range[5];
+    DevBuf<uint8_t>* pyr[5] = {};
+    DevBuf<float>* feat[5] = {};
+    DevBuf<uint32_t> *ann = nullptr, *bnn = nullptr, *ann_prev = nullptr, *bnn_prev = nullptr;
+    DevBuf<float> *bnnd = nullptr, *err = nullptr;
+    DevBuf<uint8_t>* guide = nullptr;
+    const uint8_t* img[5];
+    ~ref_bufs() { for (auto* p : pyr) delete p; for (auto* p : feat) delete p; delete ann; delete bnn; delete ann_prev; delete bnn_prev; delete bnnd; delete err; delete guide; }
+};
+
+// run the whole L=5->1 loop on the device-resident source and its K references; fin (nullable) moves the last level's U1 / S2 / A1 onto the original source.
+// With K = 1 this enqueues a pair's launches and nothing else; lv and mlv (at most one of them) receive the level intermediates of a pair / of a multi run
+static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* lv, const fullres_target* fin = nullptr,
+                            const nct_multi_levels* mlv = nullptr) {
     pair_state* P = (pair_state*)ctx->pair;
-    if (!P || !P->src || !P->ref) return ctx->fail(NCT_ERR_STATE, "process: no pair uploaded");
+    if (!P || !P->src || P->K < 1 || !P->ref[0]) return ctx->fail(NCT_ERR_STATE, "process: no pair uploaded");
     hipStream_t s = ctx->stream;
-    const int H = P->sh, W = P->sw, RH = P->rh, RW = P->rw;
+    const int H = P->sh, W = P->sw, K = P->K;
+    NCT_REQUIRE(!fin || K == 1, "process: no full-resolution finish with several references");
     NCT_REQUIRE(prm->patch_size == 3 && prm->k_num == 8, "process: patch_size must be 3 and k_num 8 (Config.h:68-70)");
     NCT_REQUIRE(prm->cluster_num >= 1 && prm->cluster_num <= 16, "process: cluster_num out of range");
     NCT_REQUIRE(prm->levels >= 1 && prm->levels <= 5, "process: levels must be in [1, 5] (got %d)", prm->levels);
     NCT_REQUIRE(!fin || !lv, "process: no level intermediates with a full-resolution finish");
+    NCT_REQUIRE(!lv || !mlv, "process: one kind of level intermediates at a time");
+    NCT_REQUIRE(!lv || K == 1, "process: nct_pair_levels describes a pair; several references report through nct_multi_levels");
     if (timing) memset(timing, 0, sizeof *timing);
     auto wall0 = std::chrono::steady_clock::now();
     ctx->tm_on = timing != nullptr; ctx->tm_tags.clear(); ctx->tm_host.clear();
@@ -94,54 +114,72 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
     MARK(ST_OTHER, 0);
 
     // level geometry, coarse -> fine (level 0 = conv5_1)
-    int ah[5], aw[5], bh[5], bw[5];
-    { int h = H, w = W, h2 = RH, w2 = RW;
-      for (int t = 0; t < 5; ++t) { ah[4 - t] = h; aw[4 - t] = w; bh[4 - t] = h2; bw[4 - t] = w2; h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; h2 = (h2 - 1) / 2 + 1; w2 = (w2 - 1) / 2 + 1; } }
-    const int maxLen = std::max(std::max(W, H), std::max(RW, RH));
-    const int rs_range[5] = {maxLen / 16, maxLen / 32, maxLen / 64, 32, 32};                   // main.cu:77-83
+    int ah[5], aw[5];
+    { int h = H, w = W;
+      for (int t = 0; t < 5; ++t) { ah[4 - t] = h; aw[4 - t] = w; h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; } }
+    std::vector<ref_bufs> R(K);
+    size_t NR = 0;                                                                             // pixels of the largest reference: the shared scratch of R's normalised features
+    for (int k = 0; k < K; ++k) {
+        int h2 = P->rh[k], w2 = P->rw[k];
+        for (int t = 0; t < 5; ++t) { R[k].bh[4 - t] = h2; R[k].bw[4 - t] = w2; h2 = (h2 - 1) / 2 + 1; w2 = (w2 - 1) / 2 + 1; }
+        // the random-search radius of reference k is the pair (S, R_k)'s own (SPEC §6.2 rule 1), not the largest reference's
+        const int maxLen = std::max(std::max(W, H), std::max(P->rw[k], P->rh[k]));
+        const int rs[5] = {maxLen / 16, maxLen / 32, maxLen / 64, 32, 32};                     // main.cu:77-83
+        for (int l = 0; l < 5; ++l) R[k].rs_range[l] = rs[l];
+        NR = std::max(NR, (size_t)P->rh[k] * P->rw[k]);
+    }
     const size_t N = (size_t)H * W;
 
     // ---- S in Lab (ColorTransfer ctor, ColorTransfer.h:54-75) and image pyramids (main.cu:104-108)
     DevBuf<uint8_t> s_lab_full(ctx, N * 3);
     if (!s_lab_full.ok()) return NCT_ERR_HIP;
     int rc = nctk_bgr2lab(ctx, s, P->src, s_lab_full, N); if (rc) return rc;
-    std::vector<DevBuf<uint8_t>*> spyr(5, nullptr), rpyr(5, nullptr);
-    struct Cleanup { std::vector<DevBuf<uint8_t>*>&a, &b; ~Cleanup() { for (auto* p : a) delete p; for (auto* p : b) delete p; } } cleanup{spyr, rpyr};
-    const uint8_t* simg[5]; const uint8_t* rimg[5];
-    simg[4] = P->src; rimg[4] = P->ref;
+    std::vector<DevBuf<uint8_t>*> spyr(5, nullptr);
+    struct Cleanup { std::vector<DevBuf<uint8_t>*>&a; ~Cleanup() { for (auto* p : a) delete p; } } cleanup{spyr};
+    const uint8_t* simg[5];
+    simg[4] = P->src;
+    for (int k = 0; k < K; ++k) R[k].img[4] = P->ref[k];
     for (int l = 3; l >= 0; --l) {
-        spyr[l] = new DevBuf<uint8_t>(ctx, (size_t)ah[l] * aw[l] * 3); rpyr[l] = new DevBuf<uint8_t>(ctx, (size_t)bh[l] * bw[l] * 3);
-        if (!spyr[l]->ok() || !rpyr[l]->ok()) return NCT_ERR_HIP;
+        spyr[l] = new DevBuf<uint8_t>(ctx, (size_t)ah[l] * aw[l] * 3);
+        if (!spyr[l]->ok()) return NCT_ERR_HIP;
+        for (int k = 0; k < K; ++k) { R[k].pyr[l] = new DevBuf<uint8_t>(ctx, (size_t)R[k].bh[l] * R[k].bw[l] * 3); if (!R[k].pyr[l]->ok()) return NCT_ERR_HIP; }
         rc = nctk_resize_u8c3(ctx, s, simg[l + 1], ah[l + 1], aw[l + 1], *spyr[l], ah[l], aw[l]); if (rc) return rc;
-        rc = nctk_resize_u8c3(ctx, s, rimg[l + 1], bh[l + 1], bw[l + 1], *rpyr[l], bh[l], bw[l]); if (rc) return rc;
-        simg[l] = *spyr[l]; rimg[l] = *rpyr[l];
+        simg[l] = *spyr[l];
+        for (int k = 0; k < K; ++k) {
+            rc = nctk_resize_u8c3(ctx, s, R[k].img[l + 1], R[k].bh[l + 1], R[k].bw[l + 1], *R[k].pyr[l], R[k].bh[l], R[k].bw[l]); if (rc) return rc;
+            R[k].img[l] = *R[k].pyr[l];
+        }
     }
     MARK(ST_OTHER, 0);
 
     // ---- VGG19: R once (all five taps kept, HWC), S to conv5_1 (main.cu:94,102)
     DevBuf<float> sfeat(ctx, (size_t)64 * N);   // S features of the current level, channel-last (largest: H x W x 64)
     if (!sfeat.ok()) return NCT_ERR_HIP;
-    std::vector<DevBuf<float>*> rfeat(5, nullptr);     // R features, un-normalised, HWC, indexed by level
-    struct Cleanup2 { std::vector<DevBuf<float>*>& a; ~Cleanup2() { for (auto* p : a) delete p; } } cleanup2{rfeat};
-    {
+    // R features (ref_bufs::feat): un-normalised, HWC, indexed by level
+    for (int k = 0; k < K; ++k) {
         // the five taps of R arrive channel-last straight from their conv layers' epilogues (round 4: no CHW -> HWC transpose pass)
         float* taps_hwc[5];
         for (int t = 0; t < 5; ++t) {
             const int l = 4 - t;
-            rfeat[l] = new DevBuf<float>(ctx, (size_t)kTapC[t] * bh[l] * bw[l]); if (!rfeat[l]->ok()) return NCT_ERR_HIP;
-            taps_hwc[t] = *rfeat[l];
+            R[k].feat[l] = new DevBuf<float>(ctx, (size_t)kTapC[t] * R[k].bh[l] * R[k].bw[l]); if (!R[k].feat[l]->ok()) return NCT_ERR_HIP;
+            taps_hwc[t] = *R[k].feat[l];
         }
-        // R and S together: conv5_1 of both images is one launch (two grids of 124 workgroups at 700 x 700 would each leave half the chip idle)
-        float* staps_hwc[5] = {nullptr, nullptr, nullptr, nullptr, sfeat};
-        rc = nctk_vgg19_forward_pair(ctx, s, P->ref, RH, RW, RW * 3, taps_hwc, P->src, H, W, W * 3, staps_hwc); if (rc) return rc;
+        if (k == 0) {
+            // R and S together: conv5_1 of both images is one launch (two grids of 124 workgroups at 700 x 700 would each leave half the chip idle)
+            float* staps_hwc[5] = {nullptr, nullptr, nullptr, nullptr, sfeat};
+            rc = nctk_vgg19_forward_pair(ctx, s, P->ref[0], P->rh[0], P->rw[0], P->rw[0] * 3, taps_hwc, P->src, H, W, W * 3, staps_hwc); if (rc) return rc;
+        } else {
+            // the further references (SPEC §6.2) have no partner for their last layer: a forward of their own
+            rc = nctk_vgg19_forward(ctx, s, P->ref[k], P->rh[k], P->rw[k], P->rw[k] * 3, 5, nullptr, nullptr, taps_hwc); if (rc) return rc;
+        }
     }
     MARK(ST_VGG, 0);
 
     // ---- C1: cluster the coarsest S features (main.cu:139-168)
     DevBuf<int> labels(ctx, (size_t)ah[0] * aw[0]), nlab_dev(ctx, 1);
-    DevBuf<float> na(ctx, (size_t)64 * N), nb(ctx, (size_t)64 * (size_t)RH * RW), voted(ctx, (size_t)64 * N), nvoted(ctx, (size_t)64 * N);
+    DevBuf<float> na(ctx, (size_t)64 * N), nb(ctx, (size_t)64 * NR), voted(ctx, (size_t)64 * N), nvoted(ctx, (size_t)64 * N);
     // fp16 shadow maps of the normalised features: the candidate tiles of the opt-in reduced-precision mode (NCT_FLAG_FEAT16)
-    DevBuf<uint16_t> na_h(ctx, feat16 ? (size_t)64 * N : 8), nb_h(ctx, feat16 ? (size_t)64 * (size_t)RH * RW : 8);
+    DevBuf<uint16_t> na_h(ctx, feat16 ? (size_t)64 * N : 8), nb_h(ctx, feat16 ? (size_t)64 * NR : 8);
     if (!labels.ok() || !nlab_dev.ok() || !na.ok() || !nb.ok() || !voted.ok() || !nvoted.ok() || !na_h.ok() || !nb_h.ok()) return NCT_ERR_HIP;
     rc = nctk_normalize(ctx, s, sfeat, na, nullptr, 512, ah[0] * aw[0], feat16 ? (uint16_t*)na_h : nullptr); if (rc) return rc;
     rc = nctk_kmeans_labels(ctx, s, na, ah[0] * aw[0], 512, prm->cluster_num, 11, (uint64_t)prm->seed, labels, nlab_dev); if (rc) return rc;
@@ -188,22 +226,48 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
     };
 
     // ---- level loop (main.cu:179-428)
-    DevBuf<uint32_t> ann(ctx, N), bnn(ctx, (size_t)RH * RW), ann_prev(ctx, N), bnn_prev(ctx, (size_t)RH * RW);
-    DevBuf<float> annd(ctx, N), bnnd(ctx, (size_t)RH * RW), err(ctx, N);
+    // per reference: the NNFs of both directions (kept from level to level) and the R -> S distances; annd is scratch shared by the references.
+    // err / guide: what the colour stage reads — reference 0's own maps with K = 1, the merged maps (rule 3) with several, whose E_k / G_k are allocated below
+    for (int k = 0; k < K; ++k) {
+        const size_t nr = (size_t)P->rh[k] * P->rw[k];
+        R[k].ann = new DevBuf<uint32_t>(ctx, N); R[k].bnn = new DevBuf<uint32_t>(ctx, nr); R[k].ann_prev = new DevBuf<uint32_t>(ctx, N); R[k].bnn_prev = new DevBuf<uint32_t>(ctx, nr);
+        if (!R[k].ann->ok() || !R[k].bnn->ok() || !R[k].ann_prev->ok() || !R[k].bnn_prev->ok()) return NCT_ERR_HIP;
+    }
+    DevBuf<float> annd(ctx, N);
+    for (int k = 0; k < K; ++k) { R[k].bnnd = new DevBuf<float>(ctx, (size_t)P->rh[k] * P->rw[k]); if (!R[k].bnnd->ok()) return NCT_ERR_HIP; }
+    DevBuf<float> err(ctx, N);
     DevBuf<uint8_t> guide(ctx, N * 3), g_lab_l(ctx, N * 3), out_lab(ctx, N * 3);
-    if (!ann.ok() || !bnn.ok() || !ann_prev.ok() || !bnn_prev.ok() || !annd.ok() || !bnnd.ok() || !err.ok() || !guide.ok() ||
-        !g_lab_l.ok() || !out_lab.ok()) return NCT_ERR_HIP;
+    if (!annd.ok() || !err.ok() || !guide.ok() || !g_lab_l.ok() || !out_lab.ok()) return NCT_ERR_HIP;
+    std::unique_ptr<DevBuf<uint8_t>> sel_label;                // the selection's label map (rule 2); a pair allocates none of this
+    if (K > 1) {
+        sel_label.reset(new DevBuf<uint8_t>(ctx, N));
+        if (!sel_label->ok()) return NCT_ERR_HIP;
+        for (int k = 0; k < K; ++k) {
+            R[k].err = new DevBuf<float>(ctx, N); R[k].guide = new DevBuf<uint8_t>(ctx, N * 3);
+            if (!R[k].err->ok() || !R[k].guide->ok()) return NCT_ERR_HIP;
+        }
+    }
     if (!P->out) { P->out = (uint8_t*)ctx->alloc(N * 3); if (!P->out) return NCT_ERR_HIP; }
     auto d2h = [&](void* dst, const void* src, size_t bytes) -> int {
         if (dst) NCT_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
         return 0;
     };
     if (lv) { rc = d2h(lv->labels, labels, sizeof(int) * (size_t)ah[0] * aw[0]); if (rc) return rc; }
+    if (mlv) { rc = d2h(mlv->labels, labels, sizeof(int) * (size_t)ah[0] * aw[0]); if (rc) return rc; }
     nct_color_params cp{prm->eps, prm->nonlocal_weight, prm->local_weight, prm->wls_lambda_init, prm->wls_alpha, (double)prm->k_num};
 
     for (int l = 0; l < nlevels; ++l) {
         const int C = kTapC[4 - l];
-        const int na_px = ah[l] * aw[l], nb_px = bh[l] * bw[l];
+        const int na_px = ah[l] * aw[l];
+      // the correspondence of the level, once per reference in index order on the main stream (SPEC §6.2 rule 1); a pair runs the body once
+      for (int k = 0; k < K; ++k) {
+        const int* bh = R[k].bh; const int* bw = R[k].bw;
+        const int nb_px = bh[l] * bw[l];
+        uint32_t *ann = *R[k].ann, *bnn = *R[k].bnn, *ann_prev = *R[k].ann_prev, *bnn_prev = *R[k].bnn_prev;
+        float* bnnd = *R[k].bnnd;
+        // where this reference's guidance image and matching error go: with several references into its own maps, which the selection merges below
+        uint8_t* guide_k = K > 1 ? (uint8_t*)*R[k].guide : (uint8_t*)guide;
+        float* err_k = K > 1 ? (float*)*R[k].err : (float*)err;
         // NNF init / upsample (main.cu:230-251)
         if (l == 0) {
             rc = nctk_nnf_init(ctx, s, ann, ah[0], aw[0], bh[0], bw[0]); if (rc) return rc;
@@ -214,9 +278,9 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
             rc = nctk_nnf_upsample(ctx, s, ann_prev, ann, ah[l], aw[l], bh[l], bw[l], ah[l - 1], aw[l - 1]); if (rc) return rc;
             rc = nctk_nnf_upsample(ctx, s, bnn_prev, bnn, bh[l], bw[l], ah[l], aw[l], bh[l - 1], bw[l - 1]); if (rc) return rc;
         }
-        // normalise (main.cu:259-275), PatchMatch both directions (main.cu:283-284)
-        if (l > 0) { rc = nctk_normalize(ctx, s, sfeat, na, nullptr, C, na_px, feat16 ? (uint16_t*)na_h : nullptr); if (rc) return rc; }
-        rc = nctk_normalize(ctx, s, *rfeat[l], nb, nullptr, C, nb_px, feat16 ? (uint16_t*)nb_h : nullptr); if (rc) return rc;
+        // normalise (main.cu:259-275), PatchMatch both directions (main.cu:283-284); S's normalised features serve every reference
+        if (l > 0 && k == 0) { rc = nctk_normalize(ctx, s, sfeat, na, nullptr, C, na_px, feat16 ? (uint16_t*)na_h : nullptr); if (rc) return rc; }
+        rc = nctk_normalize(ctx, s, *R[k].feat[l], nb, nullptr, C, nb_px, feat16 ? (uint16_t*)nb_h : nullptr); if (rc) return rc;
         MARK(ST_OTHER, l);
         const uint32_t seed_ab = prm->seed ^ (0x9E3779B9u * (uint32_t)(2 * l + 1)), seed_ba = prm->seed ^ (0x9E3779B9u * (uint32_t)(2 * l + 2));
         // na, nb are unit vectors: the row-wise rejection is exact (and worth a third of the finest level: 15.7 vs 24.1 ms with NCT_PM_PLAIN). The fp16 tiles pay from C = 128 on (11-37 % per level); the C = 64 level is
@@ -225,24 +289,48 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
 #define NCT_PIPE_PM_EXACT_MODE NCT_PM_ROWREJECT
 #endif
         const int pm_mode = (feat16 && C >= 256) ? NCT_PM_FP16 : NCT_PIPE_PM_EXACT_MODE;
-        rc = nctk_patchmatch_bidir(ctx, s, na, nb, (const uint16_t*)na_h, (const uint16_t*)nb_h, C, ah[l], aw[l], bh[l], bw[l], prm->pm_iters, rs_range[l], seed_ab, seed_ba,
+        rc = nctk_patchmatch_bidir(ctx, s, na, nb, (const uint16_t*)na_h, (const uint16_t*)nb_h, C, ah[l], aw[l], bh[l], bw[l], prm->pm_iters, R[k].rs_range[l], seed_ab, seed_ba,
                                    ann, annd, bnn, bnnd, pm_mode, count ? ctx->d_counter + 4 * l : nullptr); if (rc) return rc;
         MARK(ST_PM, l);
-        if (timing) timing->pm_level_launches[l] = 1 + 4 * prm->pm_iters;
+        if (timing) timing->pm_level_launches[l] += 1 + 4 * prm->pm_iters;
         if (lv) {
             rc = d2h(lv->ann[l], ann, sizeof(uint32_t) * na_px); if (rc) return rc;
             rc = d2h(lv->bnn[l], bnn, sizeof(uint32_t) * nb_px); if (rc) return rc;
             rc = d2h(lv->annd[l], annd, sizeof(float) * na_px); if (rc) return rc;
             rc = d2h(lv->bnnd[l], bnnd, sizeof(float) * nb_px); if (rc) return rc;
         }
+        if (mlv) {
+            rc = d2h(mlv->ann[k][l], ann, sizeof(uint32_t) * na_px); if (rc) return rc;
+            rc = d2h(mlv->bnn[k][l], bnn, sizeof(uint32_t) * nb_px); if (rc) return rc;
+            rc = d2h(mlv->annd[k][l], annd, sizeof(float) * na_px); if (rc) return rc;
+            rc = d2h(mlv->bnnd[k][l], bnnd, sizeof(float) * nb_px); if (rc) return rc;
+        }
         // BDS votes: guidance image (main.cu:291) and features + matching error (main.cu:303-318)
-        rc = nctk_bds_vote_both(ctx, s, rimg[l], *rfeat[l], ann, bnn, C, ah[l], aw[l], bh[l], bw[l], 1.0, prm->bds_weight, guide, voted); if (rc) return rc;
+        rc = nctk_bds_vote_both(ctx, s, R[k].img[l], *R[k].feat[l], ann, bnn, C, ah[l], aw[l], bh[l], bw[l], 1.0, prm->bds_weight, guide_k, voted); if (rc) return rc;
         rc = nctk_normalize(ctx, s, voted, nvoted, nullptr, C, na_px); if (rc) return rc;
-        rc = nctk_feature_distance(ctx, s, na, nvoted, err, C, na_px); if (rc) return rc;
+        rc = nctk_feature_distance(ctx, s, na, nvoted, err_k, C, na_px); if (rc) return rc;
+        if (K > 1 && k == K - 1) {
+            // selection and merge (SPEC §6.2 rules 2-3): the one launch a level with several references adds; it counts as vote time
+            const float* errs[NCT_MAX_REFS]; const uint8_t* guides[NCT_MAX_REFS];
+            for (int q = 0; q < K; ++q) { errs[q] = *R[q].err; guides[q] = *R[q].guide; }
+            rc = nctk_select_reference(ctx, s, errs, guides, K, ah[l], aw[l], *sel_label, guide, err); if (rc) return rc;
+        }
         MARK(ST_VOTE, l);
         if (lv) {
             rc = d2h(lv->guide[l], guide, (size_t)na_px * 3); if (rc) return rc;
             rc = d2h(lv->err[l], err, sizeof(float) * na_px); if (rc) return rc;
+        }
+        if (mlv) {
+            rc = d2h(mlv->ref_guide[k][l], guide_k, (size_t)na_px * 3); if (rc) return rc;
+            rc = d2h(mlv->ref_err[k][l], err_k, sizeof(float) * na_px); if (rc) return rc;
+        }
+      }
+        if (mlv) {
+            // K = 1 has no selection: its label map is all zero and the merged maps are reference 0's
+            if (K > 1) { rc = d2h(mlv->label[l], *sel_label, (size_t)na_px); if (rc) return rc; }
+            else if (mlv->label[l]) memset(mlv->label[l], 0, (size_t)na_px);
+            rc = d2h(mlv->guide[l], guide, (size_t)na_px * 3); if (rc) return rc;
+            rc = d2h(mlv->err[l], err, sizeof(float) * na_px); if (rc) return rc;
         }
         // kNN graph in Lab (main.cu:351-359): computed on the side stream; join once before its first use
         rc = nctk_bgr2lab(ctx, s, guide, g_lab_l, na_px); if (rc) return rc;
@@ -286,6 +374,7 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
         if (timing) { timing->wls_iters[l] = *std::max_element(wls_it, wls_it + 6); }
         MARK(ST_COLOR, l);
         if (lv) { rc = d2h(lv->result[l], P->out, N * 3); if (rc) return rc; }
+        if (mlv) { rc = d2h(mlv->result[l], P->out, N * 3); if (rc) return rc; }
         // re-predict: S features of the next level from the intermediate result (main.cu:424-427)
         if (l < nlevels - 1) {
             const int tap = 4 - l;                         // next level uses tap (5 - (l+1))
@@ -333,6 +422,29 @@ const char* nct_working_size_rule(int h, int w, int max_side, int* work_h, int* 
     return nullptr;
 }
 
+// drop what the context holds of the last pair / reference list
+static void drop_images(nct_ctx* ctx, pair_state* P) {
+    if (P->src) { ctx->release(P->src); P->src = nullptr; }
+    for (uint8_t*& r : P->ref) if (r) { ctx->release(r); r = nullptr; }
+    if (P->out) { ctx->release(P->out); P->out = nullptr; }
+    P->K = 0;
+}
+
+// the source and its K references (checked by the caller) into the arena
+static int upload_images(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw) {
+    pair_state* P = pair_of(ctx);
+    drop_images(ctx, P);
+    P->src = (uint8_t*)ctx->alloc((size_t)sh * sw * 3);
+    if (!P->src) return NCT_ERR_HIP;
+    for (int k = 0; k < K; ++k) { P->ref[k] = (uint8_t*)ctx->alloc((size_t)rh[k] * rw[k] * 3); if (!P->ref[k]) return NCT_ERR_HIP; }
+    NCT_HIP(hipMemcpyAsync(P->src, src_bgr, (size_t)sh * sw * 3, hipMemcpyHostToDevice, ctx->stream));
+    for (int k = 0; k < K; ++k) NCT_HIP(hipMemcpyAsync(P->ref[k], refs_bgr[k], (size_t)rh[k] * rw[k] * 3, hipMemcpyHostToDevice, ctx->stream));
+    NCT_HIP(hipStreamSynchronize(ctx->stream));
+    P->sh = sh; P->sw = sw; P->K = K;
+    for (int k = 0; k < K; ++k) { P->rh[k] = rh[k]; P->rw[k] = rw[k]; }
+    return NCT_OK;
+}
+
 extern "C" {
 
 int nct_pair_upload(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw) {
@@ -342,18 +454,41 @@ int nct_pair_upload(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const 
     // the coarsest pyramid level (four ceil-halvings) must be at least 2x2 (init_Ann_kernel scales by (bw-1)/(aw-1)): side >= 17
     NCT_REQUIRE(sh >= 17 && sw >= 17 && rh >= 17 && rw >= 17 && sh <= 4000 && sw <= 4000 && rh <= 4000 && rw <= 4000,
                 "pair_upload: image sides must be in [17, 4000] (got %dx%d and %dx%d)", sw, sh, rw, rh);
-    pair_state* P = pair_of(ctx);
-    if (P->src) { ctx->release(P->src); P->src = nullptr; }
-    if (P->ref) { ctx->release(P->ref); P->ref = nullptr; }
-    if (P->out) { ctx->release(P->out); P->out = nullptr; }
-    P->src = (uint8_t*)ctx->alloc((size_t)sh * sw * 3);
-    P->ref = (uint8_t*)ctx->alloc((size_t)rh * rw * 3);
-    if (!P->src || !P->ref) return NCT_ERR_HIP;
-    NCT_HIP(hipMemcpyAsync(P->src, src_bgr, (size_t)sh * sw * 3, hipMemcpyHostToDevice, ctx->stream));
-    NCT_HIP(hipMemcpyAsync(P->ref, ref_bgr, (size_t)rh * rw * 3, hipMemcpyHostToDevice, ctx->stream));
-    NCT_HIP(hipStreamSynchronize(ctx->stream));
-    P->sh = sh; P->sw = sw; P->rh = rh; P->rw = rw;
-    return NCT_OK;
+    return upload_images(ctx, src_bgr, sh, sw, 1, &ref_bgr, &rh, &rw);
+}
+
+int nct_multi_upload(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw) {
+    if (!ctx) return NCT_ERR_INVALID;
+    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_REQUIRE(K >= 1 && K <= NCT_MAX_REFS, "multi_upload: the number of references must be in [1, %d] (got %d)", NCT_MAX_REFS, K);
+    NCT_REQUIRE(src_bgr && refs_bgr && rh && rw, "multi_upload: null pointer");
+    NCT_REQUIRE(sh >= 17 && sw >= 17 && sh <= 4000 && sw <= 4000, "multi_upload: image sides must be in [17, 4000] (source: %dx%d)", sw, sh);
+    for (int k = 0; k < K; ++k) {
+        NCT_REQUIRE(refs_bgr[k], "multi_upload: reference %d is a null image", k);
+        NCT_REQUIRE(rh[k] >= 17 && rw[k] >= 17 && rh[k] <= 4000 && rw[k] <= 4000, "multi_upload: image sides must be in [17, 4000] (reference %d: %dx%d)", k, rw[k], rh[k]);
+    }
+    return upload_images(ctx, src_bgr, sh, sw, K, refs_bgr, rh, rw);
+}
+
+int nct_multi_run(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing) {
+    if (!ctx) return NCT_ERR_INVALID;
+    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_REQUIRE(prm, "multi_run: null params");
+    return process_resident(ctx, prm, timing, nullptr);
+}
+
+int nct_multi_run_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_multi_levels* levels) {
+    if (!ctx) return NCT_ERR_INVALID;
+    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_REQUIRE(prm, "multi_run_levels: null params");
+    return process_resident(ctx, prm, timing, nullptr, nullptr, levels);
+}
+
+int nct_process_multi(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw, const nct_params* prm,
+                      uint8_t* out_bgr, nct_pair_timing* timing) {
+    int rc = nct_multi_upload(ctx, src_bgr, sh, sw, K, refs_bgr, rh, rw); if (rc) return rc;
+    rc = nct_multi_run(ctx, prm, timing); if (rc) return rc;
+    return nct_pair_download(ctx, out_bgr);
 }
 
 int nct_pair_run(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing) {
@@ -407,25 +542,23 @@ int nct_process_pair_fullres(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int s
     const bool shrunk = wh != sh || ww != sw;
     // the originals go to the arena and are shrunk there (rule 1: nct_resize_u8c3's arithmetic); the pair state holds the working-size pair
     pair_state* P = pair_of(ctx);
-    if (P->src) { ctx->release(P->src); P->src = nullptr; }
-    if (P->ref) { ctx->release(P->ref); P->ref = nullptr; }
-    if (P->out) { ctx->release(P->out); P->out = nullptr; }
+    drop_images(ctx, P);
     DevBuf<uint8_t> s0(ctx, (size_t)sh * sw * 3);
     if (!s0.ok()) return NCT_ERR_HIP;
     P->src = (uint8_t*)ctx->alloc((size_t)wh * ww * 3);
-    P->ref = (uint8_t*)ctx->alloc((size_t)rwh * rww * 3);
-    if (!P->src || !P->ref) return NCT_ERR_HIP;
-    P->sh = P->sw = P->rh = P->rw = 0;
+    P->ref[0] = (uint8_t*)ctx->alloc((size_t)rwh * rww * 3);
+    if (!P->src || !P->ref[0]) return NCT_ERR_HIP;
+    P->sh = P->sw = P->rh[0] = P->rw[0] = 0;
     NCT_HIP(hipMemcpyAsync(s0, src_bgr, (size_t)sh * sw * 3, hipMemcpyHostToDevice, ctx->stream));
     int rc = nctk_resize_u8c3(ctx, ctx->stream, s0, sh, sw, P->src, wh, ww); if (rc) return rc;
     {
         DevBuf<uint8_t> r0(ctx, (size_t)rh * rw * 3);
         if (!r0.ok()) return NCT_ERR_HIP;
         NCT_HIP(hipMemcpyAsync(r0, ref_bgr, (size_t)rh * rw * 3, hipMemcpyHostToDevice, ctx->stream));
-        rc = nctk_resize_u8c3(ctx, ctx->stream, r0, rh, rw, P->ref, rwh, rww); if (rc) return rc;
+        rc = nctk_resize_u8c3(ctx, ctx->stream, r0, rh, rw, P->ref[0], rwh, rww); if (rc) return rc;
     }
     NCT_HIP(hipStreamSynchronize(ctx->stream));
-    P->sh = wh; P->sw = ww; P->rh = rwh; P->rw = rww;
+    P->sh = wh; P->sw = ww; P->rh[0] = rwh; P->rw[0] = rww; P->K = 1;
     if (!shrunk) {
         // rule 4: a source that is not shrunk has nothing to finish at another size — this is nct_process_pair on (S0, shrunk R)
         rc = process_resident(ctx, prm, timing, nullptr); if (rc) return rc;

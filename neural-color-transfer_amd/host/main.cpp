@@ -6,7 +6,8 @@
 // extensions `-gpus N` (pairs sharded over N GPUs, one context per worker thread), `-inflight K`, `-io T` (shared decode/encode pool: the GPU workers never
 // touch zlib), `-pin` (threads on the GPU's NUMA node), weights parsed once per process and held once per GPU, `-seed`, `-levels L` (BASELINE
 // config 1: "L=5 only" = -levels 1), `-resume 1` (skip pairs whose output exists; <out>/status.jsonl gets one JSON line per pair)
-// and `-feat16 1` (reduced-precision PatchMatch features; not bit-identical), `-fullres 1` (the result at the content image's own size, SPEC §6.1).
+// and `-feat16 1` (reduced-precision PatchMatch features; not bit-identical), `-fullres 1` (the result at the content image's own size, SPEC §6.1),
+// and pairs.txt lines whose second token lists several references separated by commas (SPEC §6.2: every pixel takes its colours from the reference that matches it best).
 #include <sys/stat.h>
 #include <sys/wait.h>
 #include <fcntl.h>
@@ -104,7 +105,9 @@ std::string stem(const std::string& path) {          // main.cu:524-531 (find_la
     return path.substr(pos, dot == std::string::npos || dot < pos ? std::string::npos : dot - pos);
 }
 
-struct Pair { std::string cnt, stl; float bds; };
+// one pairs.txt line. stl is the line's second token as written; refs its names: one, or several where the token holds commas (SPEC §6.2).
+// err: why the line is refused (too many or empty names) — reported when its turn comes, the run goes on
+struct Pair { std::string cnt, stl; float bds; std::vector<std::string> refs; std::string err; };
 std::mutex g_print;
 
 struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false, fullres = false; int rank = 0, world = 1; };
@@ -245,6 +248,36 @@ bool run_with_vis(nct_ctx* ctx, const ImageBGR& cnt, const ImageBGR& stl, const 
     }
     return true;
 }
+// the level intermediates a line with several references shows under -vis 1: per level the label map as an 8-bit grey image (label * (255 / max(K - 1, 1))), the merged
+// guidance image and the intermediate result, named like run_with_vis's dumps (<pre>_label_<l>.png, <pre>_guide_<l>.png, <pre>_result_<l>.png)
+bool run_multi_with_vis(nct_ctx* ctx, const ImageBGR& cnt, const std::vector<const ImageBGR*>& refs, const nct_params& prm, const std::string& pre, uint8_t* out,
+                        nct_pair_timing* tm, std::string& err) {
+    const int K = (int)refs.size();
+    int ah[5], aw[5];
+    { int h = cnt.h, w = cnt.w; for (int t = 0; t < 5; ++t) { ah[4 - t] = h; aw[4 - t] = w; h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; } }
+    std::vector<std::vector<uint8_t>> label(5), guide(5), result(5);
+    nct_multi_levels lv; memset(&lv, 0, sizeof lv);
+    for (int l = 0; l < prm.levels; ++l) {
+        label[l].resize((size_t)ah[l] * aw[l]); guide[l].resize((size_t)ah[l] * aw[l] * 3); result[l].resize((size_t)cnt.h * cnt.w * 3);
+        lv.label[l] = label[l].data(); lv.guide[l] = guide[l].data(); lv.result[l] = result[l].data();
+    }
+    std::vector<const uint8_t*> px(K); std::vector<int> rh(K), rw(K);
+    for (int k = 0; k < K; ++k) { px[k] = refs[k]->px.data(); rh[k] = refs[k]->h; rw[k] = refs[k]->w; }
+    if (nct_multi_upload(ctx, cnt.px.data(), cnt.h, cnt.w, K, px.data(), rh.data(), rw.data()) != NCT_OK || nct_multi_run_levels(ctx, &prm, tm, &lv) != NCT_OK ||
+        nct_pair_download(ctx, out) != NCT_OK) { err = nct_last_error(ctx); return false; }
+    const int step = 255 / std::max(K - 1, 1);
+    for (int l = 0; l < prm.levels; ++l) {
+        for (uint8_t& v : label[l]) v = (uint8_t)(v * step);
+        char name[1200]; std::string e;
+        snprintf(name, sizeof name, "%s_label_%d.png", pre.c_str(), l);
+        if (!pngio::write(name, label[l].data(), ah[l], aw[l], e, 1)) { err = "cannot write the -vis images"; return false; }
+        snprintf(name, sizeof name, "%s_guide_%d.png", pre.c_str(), l);
+        if (!pngio::write(name, guide[l].data(), ah[l], aw[l], e)) { err = "cannot write the -vis images"; return false; }
+        snprintf(name, sizeof name, "%s_result_%d.png", pre.c_str(), l);
+        if (!pngio::write(name, result[l].data(), cnt.h, cnt.w, e)) { err = "cannot write the -vis images"; return false; }
+    }
+    return true;
+}
 std::mutex g_status;
 
 std::string json_escape(const std::string& s) {
@@ -283,6 +316,8 @@ bool shrink(nct_ctx* ctx, ImageBGR& img) {
 struct Job {
     size_t index = 0; Pair p; std::string name, log, err;
     ImageBGR cnt, stl; std::vector<uint8_t> out;
+    std::vector<ImageBGR> more;                                  // the second and further references of a line with several (SPEC §6.2)
+    size_t input_bytes() const { size_t b = cnt.px.size() + stl.px.size(); for (const auto& m : more) b += m.px.size(); return b; }
     std::chrono::steady_clock::time_point t0;
     enum { LOADED, SKIPPED, FAILED, DONE } state = LOADED;
     template <typename... A> void say(const char* fmt, A... a) { char line[1200]; snprintf(line, sizeof line, fmt, a...); log += line; }
@@ -295,14 +330,46 @@ void finish(const Config& cfg, Job& j) {           // status line + the pair's l
     std::lock_guard<std::mutex> g(g_print); fputs(j.log.c_str(), stdout); fflush(stdout);
 }
 
+// the second token of a pairs.txt line: one name, or several separated by commas (SPEC §6.2). More than NCT_MAX_REFS names or an empty one refuse the line
+void split_refs(Pair& p) {
+    p.refs.clear(); p.err.clear();
+    if (p.stl.find(',') == std::string::npos) { p.refs.push_back(p.stl); return; }
+    size_t pos = 0;
+    for (;;) {
+        const size_t c = p.stl.find(',', pos);
+        p.refs.push_back(p.stl.substr(pos, c == std::string::npos ? std::string::npos : c - pos));
+        if (c == std::string::npos) break;
+        pos = c + 1;
+    }
+    for (const auto& r : p.refs) if (r.empty()) { p.err = "empty reference name in \"" + p.stl + "\""; return; }
+    if (p.refs.size() > (size_t)NCT_MAX_REFS) p.err = std::to_string(p.refs.size()) + " references in one line, at most " + std::to_string(NCT_MAX_REFS) + " are supported";
+}
+
+// why this run does not take the line (its own fault, or an option it cannot be combined with); empty: it runs
+std::string refusal(const Config& cfg, const Pair& p) {
+    if (!p.err.empty()) return p.err;
+    if (cfg.fullres && p.refs.size() > 1) return "-fullres 1 cannot be combined with several references";
+    return "";
+}
+
+// <out>/<src stem>_<ref stem>_<bds %2.2f>.png (main.cu:524-537); with several references their stems joined by '+'
+std::string output_name(const Config& cfg, const Pair& p) {
+    std::string refs;
+    for (size_t k = 0; k < p.refs.size(); ++k) refs += (k ? "+" : "") + stem(cfg.input_dir + "/" + p.refs[k]);
+    char name[2048];
+    snprintf(name, sizeof name, "%s/%s_%s_%2.2f.png", cfg.output_dir.c_str(), stem(cfg.input_dir + "/" + p.cnt).c_str(), refs.c_str(), (double)p.bds);
+    return name;
+}
+
 void load_pair(const Config& cfg, Job& j) {
     j.t0 = std::chrono::steady_clock::now();
     j.log += "-----------------***********************----------------------\n";
     j.say("Content: %s, style: %s, BDS weight: %f.\n", j.p.cnt.c_str(), j.p.stl.c_str(), (double)j.p.bds);
-    const std::string cntStr = cfg.input_dir + "/" + j.p.cnt, stlStr = cfg.input_dir + "/" + j.p.stl;
-    char name[1024];
-    snprintf(name, sizeof name, "%s/%s_%s_%2.2f.png", cfg.output_dir.c_str(), stem(cntStr).c_str(), stem(stlStr).c_str(), (double)j.p.bds);   // main.cu:524-537
-    j.name = name;
+    const std::string why = refusal(cfg, j.p);
+    if (!why.empty()) { j.say("Error: %s\n", why.c_str()); j.err = why; j.state = Job::FAILED; return; }
+    const std::string cntStr = cfg.input_dir + "/" + j.p.cnt, stlStr = cfg.input_dir + "/" + j.p.refs[0];
+    j.name = output_name(cfg, j.p);
+    const char* name = j.name.c_str();
     if (cfg.resume && pngio::looks_complete(j.name)) {           // a truncated file (killed run, full disk) is redone, not skipped
         j.say("Skipping (-resume): %s exists.\n\n", name);
         j.state = Job::SKIPPED; return;
@@ -312,6 +379,12 @@ void load_pair(const Config& cfg, Job& j) {
     j.say("\n**Read content file: %s, w = %d, h = %d\n", cntStr.c_str(), j.cnt.w, j.cnt.h);
     if (!imgio::read(stlStr, j.stl, err)) { j.say("Error: Fail reading style image: %s\n", stlStr.c_str()); j.err = "cannot read style image: " + err; j.state = Job::FAILED; return; }
     j.say("Read style file: %s, w = %d, h = %d\n", stlStr.c_str(), j.stl.w, j.stl.h);
+    j.more.resize(j.p.refs.size() - 1);
+    for (size_t k = 1; k < j.p.refs.size(); ++k) {
+        const std::string refStr = cfg.input_dir + "/" + j.p.refs[k];
+        if (!imgio::read(refStr, j.more[k - 1], err)) { j.say("Error: Fail reading style image: %s\n", refStr.c_str()); j.err = "cannot read style image: " + err; j.state = Job::FAILED; return; }
+        j.say("Read style file: %s, w = %d, h = %d\n", refStr.c_str(), j.more[k - 1].w, j.more[k - 1].h);
+    }
 }
 
 // the reference's per-level lines (main.cu:331; ColorTransfer.cpp:1373,1434), then its total (main.cu:453); the decoded inputs are dropped
@@ -324,6 +397,7 @@ void log_times(Job& j, const nct_params& prm, const nct_pair_timing& tm) {
     j.say("VGG19 Time: %lf sec.\n", tm.vgg_ms * 1e-3);
     j.say("**Finished Time: %lf sec.\n", tm.total_ms * 1e-3);
     j.stl.px.clear(); j.stl.px.shrink_to_fit();
+    j.more.clear(); j.more.shrink_to_fit();
     j.cnt.px.clear(); j.cnt.px.shrink_to_fit();                 // the store stage needs only cnt.h / cnt.w
 }
 
@@ -338,12 +412,27 @@ void run_pair(nct_ctx* ctx, const Config& cfg, Job& j) {
         log_times(j, prm, tm);
         return;
     }
-    if (!shrink(ctx, j.cnt) || !shrink(ctx, j.stl)) { j.say("Error: resize failed: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
+    bool shrunk = shrink(ctx, j.cnt) && shrink(ctx, j.stl);
+    for (auto& m : j.more) shrunk = shrunk && shrink(ctx, m);
+    if (!shrunk) { j.say("Error: resize failed: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
     nct_params prm = cfg.prm;
     prm.bds_weight = j.p.bds;                                   // the per-line weight overrides -bds (main.cu:475)
     j.out.resize((size_t)j.cnt.h * j.cnt.w * 3);
     nct_pair_timing tm;                                         // stage times come from stream events: asking for them adds no host synchronisation
-    if (cfg.vis) {
+    if (!j.more.empty()) {                                      // several references (SPEC §6.2)
+        std::vector<const ImageBGR*> refs{&j.stl};
+        for (const auto& m : j.more) refs.push_back(&m);
+        if (cfg.vis) {
+            std::string pre(j.name); pre.resize(pre.size() - 4);
+            std::string err;
+            if (!run_multi_with_vis(ctx, j.cnt, refs, prm, pre, j.out.data(), &tm, err)) { j.say("Error: %s\n", err.c_str()); j.err = err; j.state = Job::FAILED; return; }
+        } else {
+            std::vector<const uint8_t*> px; std::vector<int> rh, rw;
+            for (const ImageBGR* r : refs) { px.push_back(r->px.data()); rh.push_back(r->h); rw.push_back(r->w); }
+            const int rc = nct_process_multi(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, (int)refs.size(), px.data(), rh.data(), rw.data(), &prm, j.out.data(), &tm);
+            if (rc != NCT_OK) { j.say("Error: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
+        }
+    } else if (cfg.vis) {
         std::string pre(j.name); pre.resize(pre.size() - 4);    // the output file's stem
         std::string err;
         if (!run_with_vis(ctx, j.cnt, j.stl, prm, pre, j.out.data(), &tm, err)) { j.say("Error: %s\n", err.c_str()); j.err = err; j.state = Job::FAILED; return; }
@@ -430,7 +519,7 @@ void io_thread(Pipeline& P, const Config& cfg, const std::vector<Pair>& pairs) {
             std::lock_guard<std::mutex> lk(P.m);
             --P.loading; P.loading_bytes -= reserved;
             if (go) {
-                const size_t b = j->cnt.px.size() + j->stl.px.size();
+                const size_t b = j->input_bytes();
                 P.ready_bytes += b; P.load_estimate = std::max(P.load_estimate, b);
                 P.ready.push_back(std::move(j));
             } else ++P.finished;
@@ -447,7 +536,7 @@ void gpu_worker(Pipeline& P, nct_ctx* ctx, const Config& cfg) {
             P.cv.wait(lk, [&] { return !P.ready.empty() || P.loads_done(); });
             if (P.ready.empty()) return;
             j = std::move(P.ready.front()); P.ready.pop_front();
-            P.ready_bytes -= j->cnt.px.size() + j->stl.px.size();
+            P.ready_bytes -= j->input_bytes();
         }
         P.cv.notify_all();
         run_pair(ctx, cfg, *j);
@@ -516,8 +605,10 @@ int main(int argc, char** argv) {
     cl.add("feat16", feat16, "[extension] 1 = fp16 PatchMatch feature tiles (fp32 accumulate); not bit-identical to the default (about 45 dB against it).");
     // parser self-test hook (no GPU): `--parse-only <args…>` parses the rest like a normal run and prints what main would go on with, in the format of
     // oracle/ref_cmdline.cpp (the reference's own parser): tests/test_cli.py compares the two on the vectors of tests/golden/cmdline_ref.json
+    // job-planning hook (no GPU): `--plan-only <args…>` goes as far as a normal run goes before it creates a context and prints, per pairs.txt line, what it would run
     const bool parse_only = argc >= 2 && !strcmp(argv[1], "--parse-only");
-    const bool parsed = cl.parse(argc, argv, parse_only ? 2 : 1);
+    const bool plan_only = argc >= 2 && !strcmp(argv[1], "--plan-only");
+    const bool parsed = cl.parse(argc, argv, parse_only || plan_only ? 2 : 1);
     if (parse_only) {
         std::cout << std::flush;
         printf("@@RESULT rc=%d\n", parsed ? 1 : 0);
@@ -529,10 +620,10 @@ int main(int argc, char** argv) {
     if (!parsed) return -1;
     if (world < 1 || rank < 0 || rank >= world) { printf("Error: -rank %d is not in [0, -world %d).\n", rank, world); return -1; }
     if (fullres && vis) { printf("Error: -fullres 1 cannot be combined with -vis 1 (the -vis dumps are working-size images).\n"); return -1; }
-    mkdir(cfg.output_dir.c_str(), 0777);                                    // main.cu:458
+    if (!plan_only) mkdir(cfg.output_dir.c_str(), 0777);                    // main.cu:458
     uint64_t run_token = getenv("NCT_RUN_TOKEN") ? strtoull(getenv("NCT_RUN_TOKEN"), nullptr, 0) : 0;      // hand-started ranks of one run share it (and remove <output>/.rccl_id between runs)
     const std::string tickets_path = cfg.output_dir + "/.tickets";
-    if (procs > 0) {
+    if (procs > 0 && !plan_only) {
         // one process per GPU: fork BEFORE anything touches the HIP runtime (a forked HIP context is unusable), every child goes on as rank r of `procs` on device -g + r
         if (world != 1) { printf("Error: -procs and -world are exclusive (-procs sets -world for its children).\n"); return -1; }
         if (steal) { unlink(tickets_path.c_str()); }                         // a fresh counter for this run
@@ -576,8 +667,18 @@ int main(int argc, char** argv) {
     if (!fp) { printf("Error: File %s does not exist in the input directory.\n", pairsFile.c_str()); return -1; }
     std::vector<Pair> pairs;
     char a[260], b[260]; float w = 0.f;
-    while (fscanf(fp, "%259s %259s %f\n", a, b, &w) == 3) pairs.push_back({a, b, w});
+    while (fscanf(fp, "%259s %259s %f\n", a, b, &w) == 3) { pairs.push_back({a, b, w, {}, ""}); split_refs(pairs.back()); }
     fclose(fp);
+    if (plan_only) {
+        for (const Pair& p : pairs) {
+            const std::string why = refusal(cfg, p);
+            if (!why.empty()) { printf("@@JOB error=%s\n", why.c_str()); continue; }
+            std::string refs;
+            for (size_t k = 0; k < p.refs.size(); ++k) refs += (k ? "|" : "") + p.refs[k];
+            printf("@@JOB src=%s refs=%s bds=%.6g out=%s\n", p.cnt.c_str(), refs.c_str(), (double)p.bds, output_name(cfg, p).c_str());
+        }
+        return 0;
+    }
 
     // model: <model_dir>/vgg19/VGG_ILSVRC_19_layers_deploy.prototxt + VGG_ILSVRC_19_layers.caffemodel (main.cu:575-580; '\\' or '/' accepted in model_dir).
     // The topology is built into the library, so the prototxt is only checked: a directory that describes another network is refused, a missing file is noted.

@@ -93,16 +93,19 @@ inline bool read(const std::string& path, ImageBGR& img, std::string& err) {
     return true;
 }
 
-inline bool write(const std::string& path, const uint8_t* bgr, int h, int w, std::string& err) {
-    std::vector<uint8_t> raw(((size_t)w * 3 + 1) * h);
+// ch = 3: BGR pixels -> an 8-bit RGB file; ch = 1: one byte per pixel -> an 8-bit greyscale file (the -vis label maps)
+inline bool write(const std::string& path, const uint8_t* bgr, int h, int w, std::string& err, int ch = 3) {
+    const size_t nc = ch == 1 ? 1 : 3;
+    std::vector<uint8_t> raw(((size_t)w * nc + 1) * h);
     for (int y = 0; y < h; ++y) {
-        uint8_t* line = &raw[((size_t)w * 3 + 1) * y];
+        uint8_t* line = &raw[((size_t)w * nc + 1) * y];
         line[0] = y == 0 ? 1 : 2;            // Sub on the first row, Up elsewhere
         for (int x = 0; x < w; ++x)
-            for (int c = 0; c < 3; ++c) {
-                const int v = bgr[((size_t)y * w + x) * 3 + (2 - c)];
-                const int pred = y == 0 ? (x > 0 ? bgr[((size_t)y * w + x - 1) * 3 + (2 - c)] : 0) : bgr[((size_t)(y - 1) * w + x) * 3 + (2 - c)];
-                line[1 + (size_t)x * 3 + c] = (uint8_t)(v - pred);
+            for (size_t c = 0; c < nc; ++c) {
+                const size_t sc = nc == 3 ? 2 - c : 0;
+                const int v = bgr[((size_t)y * w + x) * nc + sc];
+                const int pred = y == 0 ? (x > 0 ? bgr[((size_t)y * w + x - 1) * nc + sc] : 0) : bgr[((size_t)(y - 1) * w + x) * nc + sc];
+                line[1 + (size_t)x * nc + c] = (uint8_t)(v - pred);
             }
     }
     uLongf clen = compressBound((uLong)raw.size());
@@ -118,7 +121,7 @@ inline bool write(const std::string& path, const uint8_t* bgr, int h, int w, std
     };
     uint8_t ihdr[13]; uint32_t ww = (uint32_t)w, hh = (uint32_t)h;
     ihdr[0] = ww >> 24; ihdr[1] = ww >> 16; ihdr[2] = ww >> 8; ihdr[3] = ww; ihdr[4] = hh >> 24; ihdr[5] = hh >> 16; ihdr[6] = hh >> 8; ihdr[7] = hh;
-    ihdr[8] = 8; ihdr[9] = 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
+    ihdr[8] = 8; ihdr[9] = nc == 3 ? 2 : 0; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
     chunk("IHDR", ihdr, 13); chunk("IDAT", comp.data(), (uint32_t)clen); chunk("IEND", nullptr, 0);
     // written under a temporary name and renamed: a run killed mid-write (or a full disk) never leaves a truncated file under the final name,
     // which -resume would take for a finished pair

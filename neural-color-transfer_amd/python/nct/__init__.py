@@ -38,7 +38,8 @@ def lib():
     return _lib
 
 
-NCT_VERSION = 110        # include/nct.h
+NCT_VERSION = 111        # include/nct.h
+MAX_REFS = 8             # NCT_MAX_REFS
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
@@ -93,6 +94,12 @@ SIGNATURES = {
     "nct_pair_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_pair_run_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_pair_download": (C.c_int, [C.c_void_p, _u8p]),
+    "nct_select_reference": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_select_reference_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_multi_upload": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nct_multi_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_multi_run_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_process_multi": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, _u8p, C.c_void_p]),
     "nct_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "nct_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nct_dev_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -213,6 +220,12 @@ def check_prototxt(path):
 class PairLevels(C.Structure):
     """struct nct_pair_levels (include/nct.h)."""
     _fields_ = [(k, C.c_void_p * 5) for k in ("ann", "bnn", "annd", "bnnd", "guide", "err", "result", "color")] + [("labels", C.c_void_p)]
+
+
+class MultiLevels(C.Structure):
+    """struct nct_multi_levels (include/nct.h)."""
+    _fields_ = [(k, (C.c_void_p * 5) * MAX_REFS) for k in ("ann", "bnn", "annd", "bnnd", "ref_guide", "ref_err")] + \
+               [(k, C.c_void_p * 5) for k in ("label", "guide", "err", "result")] + [("labels", C.c_void_p)]
 
 
 class ColorStages(C.Structure):
@@ -520,6 +533,112 @@ class Context:
         self._chk(self._l.nct_color_finish(self._h, a, h, w, work_h, work_w, s_full.reshape(-1, 3), H, W, C.addressof(prm), out.reshape(-1, 3),
                                            C.addressof(st) if st else None))
         return (out, keep) if want_stages else out
+
+    # ---- several references (SPEC §6.2)
+    @staticmethod
+    def _ref_list(refs):
+        """-> (K, contiguous arrays, void*[K], int[K] heights, int[K] widths); K and null entries are checked by the library, not here"""
+        arrs = [None if r is None else np.ascontiguousarray(r, np.uint8) for r in refs]
+        K = len(arrs)
+        ptrs = (C.c_void_p * max(K, 1))(*[None if a is None else a.ctypes.data for a in arrs])
+        hs = (C.c_int * max(K, 1))(*[0 if a is None else a.shape[0] for a in arrs])
+        ws = (C.c_int * max(K, 1))(*[0 if a is None else a.shape[1] for a in arrs])
+        return K, arrs, ptrs, hs, ws
+
+    def select_reference(self, errs, guides=None):
+        """nct_select_reference: K error maps (h x w fp32) and, optionally, K guidance images (h x w x 3) -> (label, merged guide or None, merged err)"""
+        es = [np.ascontiguousarray(e, np.float32) for e in errs]
+        gs = None if guides is None else [np.ascontiguousarray(g, np.uint8) for g in guides]
+        K = len(es)
+        h, w = es[0].shape if K else (1, 1)
+        ep = (C.c_void_p * max(K, 1))(*[e.ctypes.data for e in es])
+        gp = None if gs is None else (C.c_void_p * max(K, 1))(*[g.ctypes.data for g in gs])
+        label = np.empty((h, w), np.uint8)
+        gout = None if gs is None else np.empty((h, w, 3), np.uint8)
+        eout = np.empty((h, w), np.float32)
+        self._chk(self._l.nct_select_reference(self._h, ep, gp, K, h, w, _ptr(label), _ptr(gout), _ptr(eout)))
+        return label, gout, eout
+
+    def select_reference_dev(self, errs, guides):
+        """the same through nct_select_reference_dev: maps uploaded to arena blocks, the launch enqueued on the context's stream, results downloaded"""
+        es = [np.ascontiguousarray(e, np.float32) for e in errs]
+        gs = [np.ascontiguousarray(g, np.uint8) for g in guides]
+        K = len(es)
+        h, w = es[0].shape
+        de = [self.dev_upload(e) for e in es]
+        dg = [self.dev_upload(g) for g in gs]
+        dl, dgo, deo = self.dev_alloc(h * w), self.dev_alloc(h * w * 3), self.dev_alloc(h * w * 4)
+        try:
+            self._chk(self._l.nct_select_reference_dev(self._h, (C.c_void_p * K)(*de), (C.c_void_p * K)(*dg), K, h, w, dl, dgo, deo))
+            return self.dev_download(dl, (h, w), np.uint8), self.dev_download(dgo, (h, w, 3), np.uint8), self.dev_download(deo, (h, w), np.float32)
+        finally:
+            self.synchronize()
+            for p in de + dg + [dl, dgo, deo]:
+                self.dev_free(p)
+
+    def process_multi(self, src_bgr, refs_bgr, params=None, want_timing=False):
+        """nct_process_multi: one source, a list of references -> the result at the source's size"""
+        s = np.ascontiguousarray(src_bgr, np.uint8)
+        K, keep, ptrs, hs, ws = self._ref_list(refs_bgr)
+        prm = params or Params.default()
+        out = np.empty_like(s)
+        tm = PairTiming() if want_timing else None
+        self._chk(self._l.nct_process_multi(self._h, s.reshape(-1, 3), s.shape[0], s.shape[1], K, ptrs, hs, ws, C.addressof(prm), out.reshape(-1, 3),
+                                            C.addressof(tm) if tm is not None else None))
+        return (out, tm.as_dict()) if want_timing else out
+
+    def multi_upload(self, src_bgr, refs_bgr):
+        s = np.ascontiguousarray(src_bgr, np.uint8)
+        K, keep, ptrs, hs, ws = self._ref_list(refs_bgr)
+        self._pair_shape = s.shape
+        self._chk(self._l.nct_multi_upload(self._h, s.reshape(-1, 3), s.shape[0], s.shape[1], K, ptrs, hs, ws))
+        self._multi_shapes = [a.shape for a in keep]
+
+    def multi_run(self, params=None, want_timing=False):
+        prm = params or Params.default()
+        tm = PairTiming() if want_timing else None
+        self._chk(self._l.nct_multi_run(self._h, C.addressof(prm), C.addressof(tm) if tm is not None else None))
+        return tm.as_dict() if want_timing else None
+
+    def multi_run_levels(self, params=None):
+        """nct_multi_run_levels on the uploaded list -> dict: per reference and level "ann", "bnn", "annd", "bnnd", "ref_guide", "ref_err" ([k][l]); per level the merged
+        "label", "guide", "err", "result" ([l]); "labels" (k-means), "timing". Level 0 = coarsest."""
+        prm = params or Params.default()
+        H, W = self._pair_shape[:2]
+        K = len(self._multi_shapes)
+
+        def pyramid(h, w):
+            d = []
+            for _ in range(5):
+                d.insert(0, (h, w)); h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+            return d
+        adims = pyramid(H, W)
+        bdims = [pyramid(*sh[:2]) for sh in self._multi_shapes]
+        per_ref = {"ann": (np.uint32, "a"), "bnn": (np.uint32, "b"), "annd": (np.float32, "a"), "bnnd": (np.float32, "b"), "ref_guide": (np.uint8, "a3"), "ref_err": (np.float32, "a")}
+        keep = {}
+        lv = MultiLevels()
+        for name, (dt, side) in per_ref.items():
+            keep[name] = []
+            for k in range(K):
+                row = []
+                for l in range(5):
+                    shape = bdims[k][l] if side == "b" else adims[l] + ((3,) if side == "a3" else ())
+                    row.append(np.zeros(shape, dt))
+                    getattr(lv, name)[k][l] = row[-1].ctypes.data
+                keep[name].append(row)
+        for name, dt in (("label", np.uint8), ("guide", np.uint8), ("err", np.float32), ("result", np.uint8)):
+            keep[name] = []
+            for l in range(5):
+                shape = {"label": adims[l], "guide": adims[l] + (3,), "err": adims[l], "result": (H, W, 3)}[name]
+                keep[name].append(np.zeros(shape, dt))
+                getattr(lv, name)[l] = keep[name][-1].ctypes.data
+        labels = np.zeros(adims[0], np.int32)
+        lv.labels = labels.ctypes.data
+        tm = PairTiming()
+        self._chk(self._l.nct_multi_run_levels(self._h, C.addressof(prm), C.addressof(tm), C.addressof(lv)))
+        keep["labels"] = labels
+        keep["timing"] = tm.as_dict()
+        return keep
 
     def pair_upload(self, src_bgr, ref_bgr):
         s = np.ascontiguousarray(src_bgr, np.uint8)
