@@ -144,13 +144,13 @@ int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w
     if (!X.ok() || !rough.ok()) return NCT_ERR_HIP;
     double* Xa = X; double* Xb = (double*)X + (size_t)3 * N;
     if (W > w || H > h) {
-        int rc = nctk_resize_f64c3(ctx, s, xa, h, w, Xa, H, W); if (rc) return rc;
-        rc = nctk_resize_f64c3(ctx, s, xb, h, w, Xb, H, W); if (rc) return rc;
+        NCT_TRY(nctk_resize_f64c3(ctx, s, xa, h, w, Xa, H, W));
+        NCT_TRY(nctk_resize_f64c3(ctx, s, xb, h, w, Xb, H, W));
     } else {
         NCT_HIP(hipMemcpyAsync(X, x, sizeof(double) * (size_t)6 * N, hipMemcpyDeviceToDevice, s));
     }
     hipLaunchKernelGGL(k_roughness, dim3(nbL), dim3(256), 0, s, (const double*)Xa, (const double*)Xb, s_lab_full, N, (double*)rough); LCHK();
-    if (dbg) { int rc = dbg_copy(ctx, s, dbg->ab_up, X, (size_t)6 * N); if (rc) return rc; rc = dbg_copy(ctx, s, dbg->rough, rough, N); if (rc) return rc; }
+    if (dbg) { NCT_TRY(dbg_copy(ctx, s, dbg->ab_up, X, (size_t)6 * N)); NCT_TRY(dbg_copy(ctx, s, dbg->rough, rough, N)); }
     // ---------------- S2: WLS (k_wls_mg.hip)
     {
         // ColorTransfer.cpp:1418-1424 with the target's own ratio; the x4 of a level that already has the working size stays tied to the working size (SPEC §6.1)
@@ -162,12 +162,12 @@ int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w
         hipLaunchKernelGGL(k_gradient_weights, dim3(nbL), dim3(256), 0, s, s_lab_full, H, W, lamda, prm.wls_alpha, (double*)gx, (double*)gy); LCHK();
         hipLaunchKernelGGL(k_wls_system, dim3(nbL), dim3(256), 0, s, (const double*)gx, (const double*)gy, (const double*)rough, H, W, (double*)diag, (double*)wx, (double*)wy); LCHK();
         int wit[6] = {0, 0, 0, 0, 0, 0};
-        { int rcm = ctx->mark(s, nct_stage_tag_color()); if (rcm) return rcm; }
-        int rc = nctk_wls_solve_mg(ctx, s, X, rough, wx, wy, H, W, ctx->wls_rtol, wit); if (rc) return rc;
-        { int rcm = ctx->mark(s, nct_stage_tag_wls()); if (rcm) return rcm; }
+        NCT_TRY(ctx->mark(s, nct_stage_tag(NCT_ST_COLOR, ctx->tm_level)));
+        NCT_TRY(nctk_wls_solve_mg(ctx, s, X, rough, wx, wy, H, W, ctx->wls_rtol, wit));
+        NCT_TRY(ctx->mark(s, nct_stage_tag(NCT_ST_WLS, ctx->tm_level)));
         if (dbg && dbg->wls_iters) for (int q = 0; q < 6; ++q) dbg->wls_iters[q] = wit[q];
     }
-    if (dbg) { int rc = dbg_copy(ctx, s, dbg->ab_wls, X, (size_t)6 * N); if (rc) return rc; }
+    if (dbg) NCT_TRY(dbg_copy(ctx, s, dbg->ab_wls, X, (size_t)6 * N));
     // ---------------- A1
     hipLaunchKernelGGL(k_apply, dim3(cdiv(3 * N, 256)), dim3(256), 0, s, (const double*)Xa, (const double*)Xb, s_lab_full, N, out_lab_full); LCHK();
     return 0;
@@ -185,12 +185,12 @@ int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, con
     if (!x.ok() || !weight.ok() || !mm.ok()) return NCT_ERR_HIP;
     double* xa = x; double* xb = (double*)x + (size_t)3 * n;
     hipLaunchKernelGGL(k_local_stats, dim3(nbl), dim3(256), 0, s, s_lab_level, g_lab_level, h, w, prm.eps, xa, xb); LCHK();
-    if (dbg) { int rc = dbg_copy(ctx, s, dbg->ab_local, x, (size_t)6 * n); if (rc) return rc; }
+    if (dbg) NCT_TRY(dbg_copy(ctx, s, dbg->ab_local, x, (size_t)6 * n));
     NCT_HIP(hipMemsetD32Async((hipDeviceptr_t)(unsigned*)mm, (int)0xFFFFFFFFu, 1, s));
     NCT_HIP(hipMemsetD32Async((hipDeviceptr_t)((unsigned*)mm + 1), 0, 1, s));
     hipLaunchKernelGGL(k_minmax_f, dim3(128), dim3(256), 0, s, err, n, (unsigned*)mm); LCHK();
     hipLaunchKernelGGL(k_err_weight, dim3(nbl), dim3(256), 0, s, err, n, (const unsigned*)mm, (double*)weight); LCHK();
-    { int rcm = ctx->mark(s, nct_stage_tag_color()); if (rcm) return rcm; }
+    NCT_TRY(ctx->mark(s, nct_stage_tag(NCT_ST_COLOR, ctx->tm_level)));
     // ---------------- S1 (k_s1.hip)
     const double normFactor = (double)(W * H) / (double)(w * h);
     {
@@ -204,16 +204,16 @@ int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, con
             rc1 = nctk_s1_solve(ctx, s, *graph, knn_id, weight, dWeight_f, s_lab_level, g_lab_level, gx, gy, layer, h, w, x, dbg ? dbg->cg_iters : nullptr);
         } else {
             // no prebuilt graph part (the host entry point nct_local_color_transfer): build it here, on this stream; the host does not know the hub block count
-            nct_s1_graph_bufs gb(ctx, n);
-            if (!gb.ok()) return NCT_ERR_HIP;
+            nct_s1_graph_bufs gb;
+            if (!gb.alloc(ctx, n)) return NCT_ERR_HIP;
             const nct_s1_graph g = gb.view(-1, -1);
             rc1 = nctk_s1_graph_build(ctx, s, knn_id, knn_w, sqrt(prm.nonlocal_weight / prm.k_num), g, nullptr);
             if (rc1 == 0) rc1 = nctk_s1_solve(ctx, s, g, knn_id, weight, dWeight_f, s_lab_level, g_lab_level, gx, gy, layer, h, w, x, dbg ? dbg->cg_iters : nullptr);
         }
         if (rc1) return rc1;
     }
-    { int rcm = ctx->mark(s, nct_stage_tag_nonlocal()); if (rcm) return rcm; }
-    if (dbg) { int rc = dbg_copy(ctx, s, dbg->ab_nonlocal, x, (size_t)6 * n); if (rc) return rc; }
+    NCT_TRY(ctx->mark(s, nct_stage_tag(NCT_ST_NONLOCAL, ctx->tm_level)));
+    if (dbg) NCT_TRY(dbg_copy(ctx, s, dbg->ab_nonlocal, x, (size_t)6 * n));
     if (fin) return nctk_color_finish(ctx, s, x, h, w, H, W, fin->s_lab, fin->H, fin->W, prm, fin->out_lab, dbg);
     return nctk_color_finish(ctx, s, x, h, w, H, W, s_lab_full, H, W, prm, out_lab_full, dbg);
 }

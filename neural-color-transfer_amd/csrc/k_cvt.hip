@@ -145,13 +145,13 @@ __global__ void k_lab2bgr(const uint8_t* __restrict__ src, uint8_t* __restrict__
 }
 
 int nctk_bgr2lab(nct_ctx* ctx, hipStream_t s, const uint8_t* src, uint8_t* dst, size_t npix) {
-    const CvtTables* t; int rc = get_tables(ctx, &t); if (rc) return rc;
+    const CvtTables* t; NCT_TRY(get_tables(ctx, &t));
     hipLaunchKernelGGL(k_bgr2lab, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, src, dst, npix, t);
     NCT_LAUNCH_CHECK();
     return 0;
 }
 int nctk_lab2bgr(nct_ctx* ctx, hipStream_t s, const uint8_t* src, uint8_t* dst, size_t npix, int form) {
-    const CvtTables* t; int rc = get_tables(ctx, &t); if (rc) return rc;
+    const CvtTables* t; NCT_TRY(get_tables(ctx, &t));
     if (form == 1) hipLaunchKernelGGL(k_lab2bgr<1>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, src, dst, npix, t);
     else hipLaunchKernelGGL(k_lab2bgr<0>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, src, dst, npix, t);
     NCT_LAUNCH_CHECK();

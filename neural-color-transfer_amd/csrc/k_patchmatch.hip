@@ -808,14 +808,12 @@ static int pm_run(nct_ctx* ctx, hipStream_t s, const float* a_hwc, const float* 
         }
     };
     // the total number of Jacobi steps is even (iters*4), so ping-ponging (nnf,dist) <-> (tmp) ends in (nnf,dist)
-    int rc = step(0, 0, 0, 0, 0, 0, 0);            // init: dist(current NNF), NNF untouched
-    if (rc) return rc;
+    NCT_TRY(step(0, 0, 0, 0, 0, 0, 0));       // init: dist(current NNF), NNF untouched
     int cur = 0, t = 0;
     for (int iter = 0; iter < iters; ++iter)
         for (int jump = 8; jump > 0; jump >>= 1) {
             ++t;
-            rc = step(cur, cur ^ 1, 1, jump, iter, stamps ? t : 0, (!stamps || t == 4 * iters) ? 1 : 0);
-            if (rc) return rc;
+            NCT_TRY(step(cur, cur ^ 1, 1, jump, iter, stamps ? t : 0, (!stamps || t == 4 * iters) ? 1 : 0));
             cur ^= 1;
         }
     // cur == 0 here. The tmp buffers return to the arena now; that is safe because arena blocks are recycled in

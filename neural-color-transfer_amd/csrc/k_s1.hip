@@ -517,19 +517,19 @@ int nctk_s1_solve(nct_ctx* ctx, hipStream_t s, const nct_s1_graph& g, const int*
         return 0;
     };
     auto apply = [&](bool kt) -> int {
-        if (kt) { int rk = ctx->kt_begin(s, NCT_KT_S1_APPLY); if (rk) return rk; }
+        if (kt) NCT_TRY(ctx->kt_begin(s, NCT_KT_S1_APPLY));
         if (coop) hipLaunchKernelGGL(k_s1_apply<true>, dim3(nbl), dim3(256), 0, s, S, (const double*)r6, (double*)w6, (double*)partial);
         else      hipLaunchKernelGGL(k_s1_apply<false>, dim3(ogrid), dim3(256), 0, s, S, (const double*)r6, (double*)w6, (double*)partial);
         LCHK();
-        if (kt) { int rk = ctx->kt_end(s); if (rk) return rk; }
+        if (kt) NCT_TRY(ctx->kt_end(s));
         return 0;
     };
     hipLaunchKernelGGL(k_pack6, dim3(cdiv(6 * n, 256)), dim3(256), 0, s, n, (const double*)x, (double*)x6); LCHK();
-    { int rc = hub(x6); if (rc) return rc; }
+    NCT_TRY(hub(x6));
     if (coop) hipLaunchKernelGGL(k_s1_residual<true>, dim3(nbl), dim3(256), 0, s, S, (const double*)x6, (const double*)rhs, (double*)r6);
     else      hipLaunchKernelGGL(k_s1_residual<false>, dim3(nbl), dim3(256), 0, s, S, (const double*)x6, (const double*)rhs, (double*)r6);
     LCHK();
-    { int rc = hub(r6); if (rc) return rc; rc = apply(false); if (rc) return rc; }
+    NCT_TRY(hub(r6)); NCT_TRY(apply(false));
     // ST_j = state after operator pass j lives in slot j & 1; vector pass k uses ST_{k-1}
     S1State* slot[2] = {(S1State*)st, (S1State*)st + 1};
     for (int k = 1; k <= maxit; ++k) {
@@ -538,14 +538,14 @@ int nctk_s1_solve(nct_ctx* ctx, hipStream_t s, const nct_s1_graph& g, const int*
             hipLaunchKernelGGL(k_s1_update<true>, dim3(ogrid), dim3(256), 0, s, n, nbl, (const double*)partial, (const S1State*)slot[k & 1], slot[(k - 1) & 1], k == 1 ? 1 : 0, tol2,
                                k == 1 ? 1 : 0, (double*)r6, (const double*)w6, (double*)p6, (double*)s6, (double*)x6, one_xcd); LCHK();
         } else {
-            if (kt) { int rk = ctx->kt_begin(s, NCT_KT_S1_SCALARS); if (rk) return rk; }
+            if (kt) NCT_TRY(ctx->kt_begin(s, NCT_KT_S1_SCALARS));
             hipLaunchKernelGGL(k_s1_scal, dim3(1), dim3(256), 0, s, (const double*)partial, nbl, (const S1State*)slot[k & 1], slot[(k - 1) & 1], k == 1 ? 1 : 0, tol2); LCHK();
-            if (kt) { int rk = ctx->kt_end(s); if (rk) return rk; rk = ctx->kt_begin(s, NCT_KT_S1_UPDATE); if (rk) return rk; }
+            if (kt) { NCT_TRY(ctx->kt_end(s)); NCT_TRY(ctx->kt_begin(s, NCT_KT_S1_UPDATE)); }
             hipLaunchKernelGGL(k_s1_update<false>, dim3(nbl), dim3(256), 0, s, n, nbl, (const double*)partial, (const S1State*)slot[(k - 1) & 1], slot[(k - 1) & 1], 0, tol2,
                                k == 1 ? 1 : 0, (double*)r6, (const double*)w6, (double*)p6, (double*)s6, (double*)x6, 0); LCHK();
-            if (kt) { int rk = ctx->kt_end(s); if (rk) return rk; }
+            if (kt) NCT_TRY(ctx->kt_end(s));
         }
-        if (k < maxit) { int rc = hub(r6); if (rc) return rc; rc = apply(kt); if (rc) return rc; }
+        if (k < maxit) { NCT_TRY(hub(r6)); NCT_TRY(apply(kt)); }
     }
     hipLaunchKernelGGL(k_unpack6, dim3(cdiv(6 * n, 256)), dim3(256), 0, s, n, (const double*)x6, x); LCHK();
     if (cg_iters_host) {

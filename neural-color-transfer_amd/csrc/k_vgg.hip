@@ -342,7 +342,7 @@ int nctk_conv3x3_pair(nct_ctx* ctx, hipStream_t s, const float* in1, int H1, int
     const bool ok = (Cin & 1) == 0 && (Cout & 63) == 0 && small(H1, W1) && small(H2, W2) && (size_t)Cin * H1 * W1 * 4 < ((size_t)1 << 32) && (size_t)Cin * H2 * W2 * 4 < ((size_t)1 << 32) &&
                     (out1 || hwc1) && (out2 || hwc2) && ctx->conv_pair != 0;
     if (!ok) {
-        int rc = nctk_conv3x3(ctx, s, in1, wp, bias, out1, Cin, Cout, H1, W1, relu, 0, hwc1); if (rc) return rc;
+        NCT_TRY(nctk_conv3x3(ctx, s, in1, wp, bias, out1, Cin, Cout, H1, W1, relu, 0, hwc1));
         return nctk_conv3x3(ctx, s, in2, wp, bias, out2, Cin, Cout, H2, W2, relu, 0, hwc2);
     }
     const int nt1 = cdiv(H1 * W1, 64), nt2 = cdiv(H2 * W2, 64);

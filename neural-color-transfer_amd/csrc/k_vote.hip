@@ -383,8 +383,7 @@ int nctk_bds_vote_features(nct_ctx* ctx, hipStream_t s, const uint32_t* ann, con
     NCT_REQUIRE(C > 0 && (C & 3) == 0 && C <= 512, "bds_vote_features: C=%d must be a multiple of 4 and <= 512", C);
     InvMap inv(ctx, bh * bw, ah * aw);
     if (!inv.ok()) return NCT_ERR_HIP;
-    int rc = build_inverse(ctx, s, bnn, bh, bw, ah, aw, inv);
-    if (rc) return rc;
+    NCT_TRY(build_inverse(ctx, s, bnn, bh, bw, ah, aw, inv));
     return launch_vote_features(ctx, s, inv, ann, pin_hwc, pout_hwc, pw, C, ah, aw, bh, bw, w_coh, w_comp);
 }
 
@@ -432,8 +431,7 @@ int nctk_bds_vote_image(nct_ctx* ctx, hipStream_t s, const uint8_t* b_bgr, const
                         int ah, int aw, int bh, int bw, double w_coh, double w_comp, uint8_t* out_bgr) {
     InvMap inv(ctx, bh * bw, ah * aw);
     if (!inv.ok()) return NCT_ERR_HIP;
-    int rc = build_inverse(ctx, s, bnn, bh, bw, ah, aw, inv);
-    if (rc) return rc;
+    NCT_TRY(build_inverse(ctx, s, bnn, bh, bw, ah, aw, inv));
     return launch_vote_image(ctx, s, inv, b_bgr, ann, ah, aw, bh, bw, w_coh, w_comp, out_bgr);
 }
 // both votes of a level (main.cu:291 and :303-318) from ONE inversion of the R->S field
@@ -442,14 +440,12 @@ int nctk_bds_vote_both(nct_ctx* ctx, hipStream_t s, const uint8_t* b_bgr, const 
     NCT_REQUIRE(C > 0 && (C & 3) == 0 && C <= 512, "bds_vote: C=%d must be a multiple of 4 and <= 512", C);
     InvMap inv(ctx, bh * bw, ah * aw);
     if (!inv.ok()) return NCT_ERR_HIP;
-    int rc = build_inverse(ctx, s, bnn, bh, bw, ah, aw, inv);
-    if (rc) return rc;
+    NCT_TRY(build_inverse(ctx, s, bnn, bh, bw, ah, aw, inv));
     // the image vote rides in the feature kernel (same taps, same source lists). Its weights are the doubles w / (w h) of launch_vote_image; the feature kernel derives
     // them from the float casts of the same values — identical as long as the cast is exact, which it is checked to be (bds weights are small decimals like 2.0: if a caller
     // ever passes a weight that is not a float, the two votes run as two kernels)
     if ((double)(float)w_coh == w_coh && (double)(float)w_comp == w_comp)
         return launch_vote_features(ctx, s, inv, ann, pin_hwc, pout_hwc, nullptr, C, ah, aw, bh, bw, (float)w_coh, (float)w_comp, b_bgr, out_bgr);
-    rc = launch_vote_image(ctx, s, inv, b_bgr, ann, ah, aw, bh, bw, w_coh, w_comp, out_bgr);
-    if (rc) return rc;
+    NCT_TRY(launch_vote_image(ctx, s, inv, b_bgr, ann, ah, aw, bh, bw, w_coh, w_comp, out_bgr));
     return launch_vote_features(ctx, s, inv, ann, pin_hwc, pout_hwc, nullptr, C, ah, aw, bh, bw, (float)w_coh, (float)w_comp);
 }

@@ -1206,18 +1206,17 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
     auto kt_e = [&]() -> int { if (ktime && B.kt->kt_end(s)) return ctx->fail(NCT_ERR_HIP, "%s", B.kt->err.c_str()); return 0; };
     auto vcycle = [&]() -> int {
         if (ktime) {
-            int rc = 0;
-            if (B.lines) { rc = kt_b(NCT_KT_WLS_BLOCK_PRE); if (rc) return rc; block_step(false); LCHK(); rc = kt_e(); if (rc) return rc; }
-            rc = kt_b(NCT_KT_WLS_DOWN); if (rc) return rc; down(0); LCHK(); rc = kt_e(); if (rc) return rc;
-            rc = kt_b(NCT_KT_WLS_COARSE); if (rc) return rc;
+            if (B.lines) { NCT_TRY(kt_b(NCT_KT_WLS_BLOCK_PRE)); block_step(false); LCHK(); NCT_TRY(kt_e()); }
+            NCT_TRY(kt_b(NCT_KT_WLS_DOWN)); down(0); LCHK(); NCT_TRY(kt_e());
+            NCT_TRY(kt_b(NCT_KT_WLS_COARSE));
             for (int l = 1; l < tail0; ++l) { down(l); LCHK(); }
             if (lv[tail0].n <= MID_T) hipLaunchKernelGGL(k_mg_mid<1>, dim3(NQ), dim3(MID_T), 0, s, cur, pack, 60);
             else                      hipLaunchKernelGGL(k_mg_mid<2>, dim3(NQ), dim3(MID_T), 0, s, cur, pack, 60);
             LCHK();
             for (int l = tail0 - 1; l >= 1; --l) { up(l, lv[l + 1].x2); LCHK(); }
-            rc = kt_e(); if (rc) return rc;
-            rc = kt_b(NCT_KT_WLS_UP); if (rc) return rc; up(0, lv[1].x2); LCHK(); rc = kt_e(); if (rc) return rc;
-            if (B.lines) { rc = kt_b(NCT_KT_WLS_BLOCK_POST); if (rc) return rc; block_step(true); LCHK(); rc = kt_e(); if (rc) return rc; }
+            NCT_TRY(kt_e());
+            NCT_TRY(kt_b(NCT_KT_WLS_UP)); up(0, lv[1].x2); LCHK(); NCT_TRY(kt_e());
+            if (B.lines) { NCT_TRY(kt_b(NCT_KT_WLS_BLOCK_POST)); block_step(true); LCHK(); NCT_TRY(kt_e()); }
             return 0;
         }
         block_step(false); LCHK();
@@ -1240,15 +1239,15 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
         cur = st + (it & 1);
         PState* nxt = st + ((it + 1) & 1);
         ktime = B.kt != nullptr && it >= 2 && it < 6 && tail0 >= 1;
-        int rc = vcycle(); if (rc) return rc;
-        rc = kt_b(NCT_KT_WLS_APPLY); if (rc) return rc;
+        NCT_TRY(vcycle());
+        NCT_TRY(kt_b(NCT_KT_WLS_APPLY));
         hipLaunchKernelGGL(k_cg_apply<NQ>, dim3(nb), dim3(256), 0, s, cur, F, z, (const double*)r, (double*)w, (double*)partial); LCHK();
-        rc = kt_e(); if (rc) return rc;
+        NCT_TRY(kt_e());
         hipLaunchKernelGGL(k_cg_fin<NQ>, dim3(3), dim3(256), 0, s, cur, (const double*)partial, nb, (double*)sums); LCHK();
-        rc = kt_b(NCT_KT_WLS_UPDATE); if (rc) return rc;
+        NCT_TRY(kt_b(NCT_KT_WLS_UPDATE));
         hipLaunchKernelGGL(k_cg_update<NQ>, dim3(nb), dim3(256), 0, s, N, cur, nxt, (const double*)sums, rtol2, it == 0 ? 1 : 0, z, (const double*)w,
                            (double*)p, (double*)sv, (double*)x6, (double*)r, rf, pub_to, pub_seq); LCHK();
-        rc = kt_e(); if (rc) return rc;
+        NCT_TRY(kt_e());
         cur = nxt;
         return 0;
     };
@@ -1299,7 +1298,7 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
         }
         if (seen == issued) break;                         // nothing left to read: the iteration budget is spent
         ++seen;
-        { int rc = wait_published(seen & 1); if (rc) return rc; }
+        NCT_TRY(wait_published(seen & 1));
         fin = hst[seen & 1];
         its_seen = its_at_snapshot[seen & 1];
         if (fin.nactive == 0) { done = true; break; }
@@ -1341,7 +1340,7 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
 
 // X: [2][N][3] in (x0) / out. rough, wx, wy: fine-level data term and edge weights (wx[i] = edge (i,i+1), wy[i] = edge (i,i+W)).
 // ctx->wls_split (NCT_FLAG_LATENCY): the a-half and the b-half (3 right-hand sides each, same operator, no shared value) are solved
-// concurrently — the second on ctx->stream2 from a helper thread — so that one half's latency-bound coarse legs hide behind the other's
+// concurrently — the second enqueued on ctx->stream_wls by a helper thread, forked from and joined into s by events — so that one half's latency-bound coarse legs hide behind the other's
 // bandwidth-bound 700x700 kernels. Every right-hand side sees exactly the same arithmetic as in the 6-wide solve (per-system reductions,
 // scalars and convergence tests): the result is bit-identical. It doubles the launches, so it is for ONE pair in flight.
 int nctk_wls_solve_mg(nct_ctx* ctx, hipStream_t s, double* X, const double* rough, const double* wx, const double* wy, int H, int W,

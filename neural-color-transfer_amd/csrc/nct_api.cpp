@@ -90,8 +90,7 @@ int nct_create(int device, nct_ctx** out) {
         (e = hipEventCreateWithFlags(&c->ev_wls_fork, hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&c->ev_wls_join, hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming)) != hipSuccess) {
+        (e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)) != hipSuccess) {
         g_create_err = std::string("stream/event creation: ") + hipGetErrorString(e);
         delete c; return NCT_ERR_HIP;
     }
@@ -157,7 +156,6 @@ void nct_destroy(nct_ctx* ctx) {
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
     for (int l = 0; l < 5; ++l) if (ctx->ev_level[l]) (void)hipEventDestroy(ctx->ev_level[l]);
     if (ctx->stream_wls) (void)hipStreamDestroy(ctx->stream_wls);
     if (ctx->ev_wls_fork) (void)hipEventDestroy(ctx->ev_wls_fork);
@@ -177,67 +175,61 @@ int nct_device_name(nct_ctx* ctx, char* buf, int buflen) {
 }
 
 int nct_synchronize(nct_ctx* ctx) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     NCT_HIP(hipDeviceSynchronize());
     return NCT_OK;
 }
 
-#define CTX_ENTER() do { if (!ctx) return NCT_ERR_INVALID; NCT_HIP(hipSetDevice(ctx->device)); } while (0)
-#define H2D(dst, src, bytes) NCT_HIP(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, ctx->stream))
-#define D2H(dst, src, bytes) NCT_HIP(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, ctx->stream))
-#define SYNC() NCT_HIP(hipStreamSynchronize(ctx->stream))
-#define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 // upload a CHW host tensor and return it in HWC device layout
 static int upload_hwc(nct_ctx* ctx, const float* chw, float* d_tmp, float* d_hwc, int C, int HW) {
-    H2D(d_tmp, chw, sizeof(float) * (size_t)C * HW);
+    NCT_H2D(d_tmp, chw, sizeof(float) * (size_t)C * HW);
     return nctk_chw_to_hwc(ctx, ctx->stream, d_tmp, d_hwc, C, HW);
 }
 
 int nct_feat_normalize(nct_ctx* ctx, const float* src_chw, float* dst_chw, float* resp, int C, int H, int W) {
-    CTX_ENTER();
+    NCT_CTX_ENTER();
     NCT_REQUIRE(src_chw && dst_chw && H > 0 && W > 0, "feat_normalize: null pointer or empty image");
     const int HW = H * W; const size_t n = (size_t)C * HW;
     DevBuf<float> t(ctx, n), x(ctx, n), y(ctx, n), r(ctx, HW);
     if (!t.ok() || !x.ok() || !y.ok() || !r.ok()) return NCT_ERR_HIP;
-    RC(upload_hwc(ctx, src_chw, t, x, C, HW));
-    RC(nctk_normalize(ctx, ctx->stream, x, y, resp ? (float*)r : nullptr, C, HW));
-    RC(nctk_hwc_to_chw(ctx, ctx->stream, y, t, C, HW));
-    D2H(dst_chw, t, sizeof(float) * n);
-    if (resp) D2H(resp, r, sizeof(float) * HW);
-    SYNC();
+    NCT_TRY(upload_hwc(ctx, src_chw, t, x, C, HW));
+    NCT_TRY(nctk_normalize(ctx, ctx->stream, x, y, resp ? (float*)r : nullptr, C, HW));
+    NCT_TRY(nctk_hwc_to_chw(ctx, ctx->stream, y, t, C, HW));
+    NCT_D2H(dst_chw, t, sizeof(float) * n);
+    if (resp) NCT_D2H(resp, r, sizeof(float) * HW);
+    NCT_SYNC();
     return NCT_OK;
 }
 
 int nct_nnf_init(nct_ctx* ctx, uint32_t* nnf, int ah, int aw, int bh, int bw) {
-    CTX_ENTER();
+    NCT_CTX_ENTER();
     NCT_REQUIRE(nnf, "nnf_init: null pointer");
     NCT_REQUIRE(ah > 0 && aw > 0, "nnf_init: empty query image");
     DevBuf<uint32_t> d(ctx, (size_t)ah * aw);
     if (!d.ok()) return NCT_ERR_HIP;
-    RC(nctk_nnf_init(ctx, ctx->stream, d, ah, aw, bh, bw));
-    D2H(nnf, d, sizeof(uint32_t) * (size_t)ah * aw);
-    SYNC();
+    NCT_TRY(nctk_nnf_init(ctx, ctx->stream, d, ah, aw, bh, bw));
+    NCT_D2H(nnf, d, sizeof(uint32_t) * (size_t)ah * aw);
+    NCT_SYNC();
     return NCT_OK;
 }
 
 int nct_nnf_upsample(nct_ctx* ctx, const uint32_t* nnf_half, uint32_t* nnf, int ah, int aw, int bh, int bw, int ah_half, int aw_half) {
-    CTX_ENTER();
+    NCT_CTX_ENTER();
     NCT_REQUIRE(nnf_half && nnf, "nnf_upsample: null pointer");
     NCT_REQUIRE(ah > 0 && aw > 0 && ah_half > 0 && aw_half > 0, "nnf_upsample: empty image");
     DevBuf<uint32_t> h(ctx, (size_t)ah_half * aw_half), d(ctx, (size_t)ah * aw);
     if (!h.ok() || !d.ok()) return NCT_ERR_HIP;
-    H2D(h, nnf_half, sizeof(uint32_t) * (size_t)ah_half * aw_half);
-    RC(nctk_nnf_upsample(ctx, ctx->stream, h, d, ah, aw, bh, bw, ah_half, aw_half));
-    D2H(nnf, d, sizeof(uint32_t) * (size_t)ah * aw);
-    SYNC();
+    NCT_H2D(h, nnf_half, sizeof(uint32_t) * (size_t)ah_half * aw_half);
+    NCT_TRY(nctk_nnf_upsample(ctx, ctx->stream, h, d, ah, aw, bh, bw, ah_half, aw_half));
+    NCT_D2H(nnf, d, sizeof(uint32_t) * (size_t)ah * aw);
+    NCT_SYNC();
     return NCT_OK;
 }
 
 int nct_patchmatch(nct_ctx* ctx, const float* a_chw, const float* b_chw, int C, int ah, int aw, int bh, int bw,
                    int patch, int iters, int rs_max, uint32_t seed, uint32_t* nnf, float* dist) {
-    CTX_ENTER();
+    NCT_CTX_ENTER();
     NCT_REQUIRE(a_chw && b_chw && nnf && dist, "patchmatch: null pointer");
     NCT_REQUIRE(patch == 3, "patchmatch: only patch=3 is supported (Config.h:70), got %d", patch);
     NCT_REQUIRE(ah > 0 && aw > 0 && bh > 0 && bw > 0, "patchmatch: empty image");
@@ -245,19 +237,19 @@ int nct_patchmatch(nct_ctx* ctx, const float* a_chw, const float* b_chw, int C, 
     DevBuf<float> t(ctx, (size_t)C * (na > nb ? na : nb)), A(ctx, C * na), B(ctx, C * nb), d(ctx, na);
     DevBuf<uint32_t> n(ctx, na);
     if (!t.ok() || !A.ok() || !B.ok() || !d.ok() || !n.ok()) return NCT_ERR_HIP;
-    RC(upload_hwc(ctx, a_chw, t, A, C, (int)na));
-    RC(upload_hwc(ctx, b_chw, t, B, C, (int)nb));
-    H2D(n, nnf, sizeof(uint32_t) * na);
-    RC(nctk_patchmatch(ctx, ctx->stream, A, B, C, ah, aw, bh, bw, iters, rs_max, seed, n, d, nullptr));
-    D2H(nnf, n, sizeof(uint32_t) * na);
-    D2H(dist, d, sizeof(float) * na);
-    SYNC();
+    NCT_TRY(upload_hwc(ctx, a_chw, t, A, C, (int)na));
+    NCT_TRY(upload_hwc(ctx, b_chw, t, B, C, (int)nb));
+    NCT_H2D(n, nnf, sizeof(uint32_t) * na);
+    NCT_TRY(nctk_patchmatch(ctx, ctx->stream, A, B, C, ah, aw, bh, bw, iters, rs_max, seed, n, d, nullptr));
+    NCT_D2H(nnf, n, sizeof(uint32_t) * na);
+    NCT_D2H(dist, d, sizeof(float) * na);
+    NCT_SYNC();
     return NCT_OK;
 }
 
 int nct_bds_vote_features(nct_ctx* ctx, const uint32_t* ann, const uint32_t* bnn, const float* pin_chw, float* pout_chw, float* pw,
                           int C, int ah, int aw, int bh, int bw, int patch, float w_coherence, float w_complete) {
-    CTX_ENTER();
+    NCT_CTX_ENTER();
     NCT_REQUIRE(ann && bnn && pin_chw && pout_chw, "bds_vote_features: null pointer");
     NCT_REQUIRE(patch == 3, "bds_vote_features: only patch=3 is supported, got %d", patch);
     NCT_REQUIRE(ah > 0 && aw > 0 && bh > 0 && bw > 0, "bds_vote_features: empty image");
@@ -265,34 +257,34 @@ int nct_bds_vote_features(nct_ctx* ctx, const uint32_t* ann, const uint32_t* bnn
     DevBuf<float> t(ctx, (size_t)C * (na > nb ? na : nb)), P(ctx, C * nb), O(ctx, C * na), w(ctx, na);
     DevBuf<uint32_t> da(ctx, na), db(ctx, nb);
     if (!t.ok() || !P.ok() || !O.ok() || !w.ok() || !da.ok() || !db.ok()) return NCT_ERR_HIP;
-    RC(upload_hwc(ctx, pin_chw, t, P, C, (int)nb));
-    H2D(da, ann, sizeof(uint32_t) * na);
-    H2D(db, bnn, sizeof(uint32_t) * nb);
-    RC(nctk_bds_vote_features(ctx, ctx->stream, da, db, P, O, w, C, ah, aw, bh, bw, w_coherence, w_complete));
-    RC(nctk_hwc_to_chw(ctx, ctx->stream, O, t, C, (int)na));
-    D2H(pout_chw, t, sizeof(float) * C * na);
-    if (pw) D2H(pw, w, sizeof(float) * na);
-    SYNC();
+    NCT_TRY(upload_hwc(ctx, pin_chw, t, P, C, (int)nb));
+    NCT_H2D(da, ann, sizeof(uint32_t) * na);
+    NCT_H2D(db, bnn, sizeof(uint32_t) * nb);
+    NCT_TRY(nctk_bds_vote_features(ctx, ctx->stream, da, db, P, O, w, C, ah, aw, bh, bw, w_coherence, w_complete));
+    NCT_TRY(nctk_hwc_to_chw(ctx, ctx->stream, O, t, C, (int)na));
+    NCT_D2H(pout_chw, t, sizeof(float) * C * na);
+    if (pw) NCT_D2H(pw, w, sizeof(float) * na);
+    NCT_SYNC();
     return NCT_OK;
 }
 
 int nct_feature_distance(nct_ctx* ctx, const float* a_chw, const float* b_chw, float* err, int C, int H, int W) {
-    CTX_ENTER();
+    NCT_CTX_ENTER();
     NCT_REQUIRE(a_chw && b_chw && err && H > 0 && W > 0, "feature_distance: null pointer or empty image");
     const size_t n = (size_t)H * W;
     DevBuf<float> t(ctx, C * n), A(ctx, C * n), B(ctx, C * n), e(ctx, n);
     if (!t.ok() || !A.ok() || !B.ok() || !e.ok()) return NCT_ERR_HIP;
-    RC(upload_hwc(ctx, a_chw, t, A, C, (int)n));
-    RC(upload_hwc(ctx, b_chw, t, B, C, (int)n));
-    RC(nctk_feature_distance(ctx, ctx->stream, A, B, e, C, (int)n));
-    D2H(err, e, sizeof(float) * n);
-    SYNC();
+    NCT_TRY(upload_hwc(ctx, a_chw, t, A, C, (int)n));
+    NCT_TRY(upload_hwc(ctx, b_chw, t, B, C, (int)n));
+    NCT_TRY(nctk_feature_distance(ctx, ctx->stream, A, B, e, C, (int)n));
+    NCT_D2H(err, e, sizeof(float) * n);
+    NCT_SYNC();
     return NCT_OK;
 }
 
 // SPEC §6.2 rules 2-3 on host maps: K error maps and guidance images up, one k_select_reference launch, label / merged guidance / merged error down
 int nct_select_reference(nct_ctx* ctx, const float* const* err, const uint8_t* const* guide_bgr, int K, int h, int w, uint8_t* label, uint8_t* guide_out, float* err_out) {
-    CTX_ENTER();
+    NCT_CTX_ENTER();
     NCT_REQUIRE(K >= 1 && K <= NCT_MAX_REFS, "select_reference: K must be in [1, %d] (got %d)", NCT_MAX_REFS, K);
     NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "select_reference: grid %dx%d out of range", w, h);
     NCT_REQUIRE(err && (guide_bgr || !guide_out), "select_reference: null map list");
@@ -304,20 +296,20 @@ int nct_select_reference(nct_ctx* ctx, const float* const* err, const uint8_t* c
     const float* de[NCT_MAX_REFS]; const uint8_t* dg[NCT_MAX_REFS];
     for (int k = 0; k < K; ++k) {
         de[k] = e + n * k; dg[k] = guide_out ? g + n * 3 * k : nullptr;
-        H2D(e + n * k, err[k], sizeof(float) * n);
-        if (guide_out) H2D(g + n * 3 * k, guide_bgr[k], n * 3);
+        NCT_H2D(e + n * k, err[k], sizeof(float) * n);
+        if (guide_out) NCT_H2D(g + n * 3 * k, guide_bgr[k], n * 3);
     }
-    RC(nctk_select_reference(ctx, ctx->stream, de, guide_out ? dg : nullptr, K, h, w, lab, guide_out ? (uint8_t*)go : nullptr, eo));
-    if (label) D2H(label, lab, n);
-    if (guide_out) D2H(guide_out, go, n * 3);
-    if (err_out) D2H(err_out, eo, sizeof(float) * n);
-    SYNC();
+    NCT_TRY(nctk_select_reference(ctx, ctx->stream, de, guide_out ? dg : nullptr, K, h, w, lab, guide_out ? (uint8_t*)go : nullptr, eo));
+    if (label) NCT_D2H(label, lab, n);
+    if (guide_out) NCT_D2H(guide_out, go, n * 3);
+    if (err_out) NCT_D2H(err_out, eo, sizeof(float) * n);
+    NCT_SYNC();
     return NCT_OK;
 }
 
 int nct_bds_vote_image(nct_ctx* ctx, const uint8_t* a_bgr, int ah, int aw, const uint8_t* b_bgr, int bh, int bw,
                        const uint32_t* ann, const uint32_t* bnn, int patch, double w_coherence, double w_complete, uint8_t* out_bgr) {
-    CTX_ENTER();
+    NCT_CTX_ENTER();
     (void)a_bgr;   // reconstruct_bds only uses a's size (GeneralizedPatchMatch.cu:124-131)
     NCT_REQUIRE(b_bgr && ann && bnn && out_bgr, "bds_vote_image: null pointer");
     NCT_REQUIRE(patch == 3, "bds_vote_image: only patch=3 is supported, got %d", patch);
@@ -326,18 +318,18 @@ int nct_bds_vote_image(nct_ctx* ctx, const uint8_t* a_bgr, int ah, int aw, const
     DevBuf<uint8_t> b(ctx, nb * 3), o(ctx, na * 3);
     DevBuf<uint32_t> da(ctx, na), db(ctx, nb);
     if (!b.ok() || !o.ok() || !da.ok() || !db.ok()) return NCT_ERR_HIP;
-    H2D(b, b_bgr, nb * 3);
-    H2D(da, ann, sizeof(uint32_t) * na);
-    H2D(db, bnn, sizeof(uint32_t) * nb);
-    RC(nctk_bds_vote_image(ctx, ctx->stream, b, da, db, ah, aw, bh, bw, w_coherence, w_complete, o));
-    D2H(out_bgr, o, na * 3);
-    SYNC();
+    NCT_H2D(b, b_bgr, nb * 3);
+    NCT_H2D(da, ann, sizeof(uint32_t) * na);
+    NCT_H2D(db, bnn, sizeof(uint32_t) * nb);
+    NCT_TRY(nctk_bds_vote_image(ctx, ctx->stream, b, da, db, ah, aw, bh, bw, w_coherence, w_complete, o));
+    NCT_D2H(out_bgr, o, na * 3);
+    NCT_SYNC();
     return NCT_OK;
 }
 
 // ---------------------------------------------------------------- measurement hooks
 int nct_pm_bench_setup(nct_ctx* ctx, const float* a_chw, const float* b_chw, int C, int ah, int aw, int bh, int bw) {
-    CTX_ENTER();
+    NCT_CTX_ENTER();
     NCT_REQUIRE(a_chw && b_chw, "pm_bench_setup: null pointer");
     const size_t na = (size_t)ah * aw, nb = (size_t)bh * bw;
     if (ctx->bench_a) { (void)hipFree(ctx->bench_a); ctx->bench_a = nullptr; }
@@ -352,29 +344,29 @@ int nct_pm_bench_setup(nct_ctx* ctx, const float* a_chw, const float* b_chw, int
     {
         DevBuf<float> t(ctx, (size_t)C * (na > nb ? na : nb)), x(ctx, (size_t)C * (na > nb ? na : nb));
         if (!t.ok() || !x.ok()) return NCT_ERR_HIP;
-        RC(upload_hwc(ctx, a_chw, t, x, C, (int)na));
-        RC(nctk_normalize(ctx, ctx->stream, x, ctx->bench_a, nullptr, C, (int)na, ctx->bench_ah16));
-        RC(upload_hwc(ctx, b_chw, t, x, C, (int)nb));
-        RC(nctk_normalize(ctx, ctx->stream, x, ctx->bench_b, nullptr, C, (int)nb, ctx->bench_bh16));
-        SYNC();
+        NCT_TRY(upload_hwc(ctx, a_chw, t, x, C, (int)na));
+        NCT_TRY(nctk_normalize(ctx, ctx->stream, x, ctx->bench_a, nullptr, C, (int)na, ctx->bench_ah16));
+        NCT_TRY(upload_hwc(ctx, b_chw, t, x, C, (int)nb));
+        NCT_TRY(nctk_normalize(ctx, ctx->stream, x, ctx->bench_b, nullptr, C, (int)nb, ctx->bench_bh16));
+        NCT_SYNC();
     }
     ctx->bench_C = C; ctx->bench_ah = ah; ctx->bench_aw = aw; ctx->bench_bh = bh; ctx->bench_bw = bw;
     return NCT_OK;
 }
 
 int nct_pm_bench_run(nct_ctx* ctx, int iters, int rs_max, uint32_t seed, float* kernel_ms, uint64_t* evals, uint32_t* nnf_out, float* dist_out) {
-    CTX_ENTER();
+    NCT_CTX_ENTER();
     if (!ctx->bench_a) return ctx->fail(NCT_ERR_STATE, "pm_bench_run: call nct_pm_bench_setup first");
     const int C = ctx->bench_C, ah = ctx->bench_ah, aw = ctx->bench_aw, bh = ctx->bench_bh, bw = ctx->bench_bw;
     const size_t na = (size_t)ah * aw;
     DevBuf<uint32_t> n(ctx, na);
     DevBuf<float> d(ctx, na);
     if (!n.ok() || !d.ok()) return NCT_ERR_HIP;
-    RC(nctk_nnf_init(ctx, ctx->stream, n, ah, aw, bh, bw));
+    NCT_TRY(nctk_nnf_init(ctx, ctx->stream, n, ah, aw, bh, bw));
     unsigned long long* counter = evals ? ctx->d_counter : nullptr;
     if (counter) NCT_HIP(hipMemsetAsync(counter, 0, 4 * sizeof(unsigned long long), ctx->stream));
     NCT_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-    RC(nctk_patchmatch(ctx, ctx->stream, ctx->bench_a, ctx->bench_b, C, ah, aw, bh, bw, iters, rs_max, seed, n, d, counter));
+    NCT_TRY(nctk_patchmatch(ctx, ctx->stream, ctx->bench_a, ctx->bench_b, C, ah, aw, bh, bw, iters, rs_max, seed, n, d, counter));
     NCT_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     NCT_HIP(hipEventSynchronize(ctx->ev1));
     float ms = 0.f;
@@ -388,7 +380,7 @@ int nct_pm_bench_run(nct_ctx* ctx, int iters, int rs_max, uint32_t seed, float* 
 
 int nct_pm_bench_run_bidir(nct_ctx* ctx, int iters, int rs_max, uint32_t seed, int pm_mode, float* kernel_ms, uint64_t* counters, uint32_t* ann_out, float* annd_out,
                            uint32_t* bnn_out, float* bnnd_out) {
-    CTX_ENTER();
+    NCT_CTX_ENTER();
     if (!ctx->bench_a) return ctx->fail(NCT_ERR_STATE, "pm_bench_run_bidir: call nct_pm_bench_setup first");
     NCT_REQUIRE(pm_mode >= NCT_PM_PLAIN && pm_mode <= NCT_PM_FP16, "pm_bench_run_bidir: pm_mode must be 0 (fp32), 1 (fp32 + row rejection) or 2 (fp16)");
     const int C = ctx->bench_C, ah = ctx->bench_ah, aw = ctx->bench_aw, bh = ctx->bench_bh, bw = ctx->bench_bw;
@@ -396,12 +388,12 @@ int nct_pm_bench_run_bidir(nct_ctx* ctx, int iters, int rs_max, uint32_t seed, i
     DevBuf<uint32_t> an(ctx, na), bn(ctx, nb);
     DevBuf<float> ad(ctx, na), bd(ctx, nb);
     if (!an.ok() || !bn.ok() || !ad.ok() || !bd.ok()) return NCT_ERR_HIP;
-    RC(nctk_nnf_init(ctx, ctx->stream, an, ah, aw, bh, bw));
-    RC(nctk_nnf_init(ctx, ctx->stream, bn, bh, bw, ah, aw));
+    NCT_TRY(nctk_nnf_init(ctx, ctx->stream, an, ah, aw, bh, bw));
+    NCT_TRY(nctk_nnf_init(ctx, ctx->stream, bn, bh, bw, ah, aw));
     unsigned long long* counter = counters ? ctx->d_counter : nullptr;
     if (counter) NCT_HIP(hipMemsetAsync(counter, 0, 4 * sizeof(unsigned long long), ctx->stream));
     NCT_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-    RC(nctk_patchmatch_bidir(ctx, ctx->stream, ctx->bench_a, ctx->bench_b, ctx->bench_ah16, ctx->bench_bh16, C, ah, aw, bh, bw, iters, rs_max, seed, seed ^ 0x5bd1e995u,
+    NCT_TRY(nctk_patchmatch_bidir(ctx, ctx->stream, ctx->bench_a, ctx->bench_b, ctx->bench_ah16, ctx->bench_bh16, C, ah, aw, bh, bw, iters, rs_max, seed, seed ^ 0x5bd1e995u,
                              an, ad, bn, bd, pm_mode, counter));
     NCT_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     NCT_HIP(hipEventSynchronize(ctx->ev1));

@@ -13,8 +13,8 @@ struct nct_block { void* p; size_t bytes; bool used; };
 struct nct_ctx {
     int device = 0;
     hipStream_t stream = nullptr;     // main stream (S->R direction, VGG, colour stage)
-    hipStream_t stream2 = nullptr;    // second stream (R->S direction runs concurrently)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr, ev_join = nullptr;
+    hipStream_t stream2 = nullptr;    // side stream: the kNN graphs and S1 graph parts of a pair's levels, built beside the main stream's correspondence work (nct_pipeline.cpp)
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr;
     hipEvent_t ev_level[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // side-stream completion of level l's kNN graph
     hipStream_t stream_wls = nullptr;  // helper stream of the split WLS solve (NCT_FLAG_LATENCY)
     hipEvent_t ev_wls_fork = nullptr, ev_wls_join = nullptr;
@@ -44,6 +44,7 @@ struct nct_ctx {
     int wls_maxit = 5000;                       // iteration budget of the WLS solve (test hook: env NCT_WLS_MAXIT)
     int s1_maxit = 0;                           // S1 iteration cap; 0 = the reference's (50 at layer 4, else 100). Test hook: env NCT_S1_MAXIT
     bool tm_on = false;
+    int tm_level = 0;                           // pyramid level whose colour stage is being enqueued: the level of the marks k_colorsolve.hip sets
     std::vector<hipEvent_t> tm_events;          // pool, reused across pairs
     std::vector<double> tm_host;                // host clock (us) at mark i: NCT_HOST_TRACE=1 prints it beside the GPU clock (how far the host runs ahead)
     std::vector<int> tm_tags;                   // tag of mark i = the stage that ENDS at event i
@@ -73,12 +74,18 @@ struct nct_ctx {
     void flush_deferred() { for (void* p : deferred) for (auto& b : blocks) if (b.p == p) { b.used = false; break; } deferred.clear(); }
 };
 
-// RAII scratch buffer from the context arena
+// stage tags of the event marks (nct_ctx::mark): tag = stage * 8 + level; a mark closes the stage it names
+enum { NCT_ST_OTHER = 0, NCT_ST_VGG, NCT_ST_CLUSTER, NCT_ST_PM, NCT_ST_VOTE, NCT_ST_KNN, NCT_ST_COLOR, NCT_ST_NONLOCAL, NCT_ST_WLS };
+static inline int nct_stage_tag(int stage, int level) { return stage * 8 + level; }
+
+// RAII scratch buffer from the context arena: allocated by its constructor, or empty (a member, an array element) until alloc()
 template <typename T> struct DevBuf {
-    nct_ctx* c; T* p;
-    DevBuf(nct_ctx* ctx, size_t n) : c(ctx), p((T*)ctx->alloc(n * sizeof(T))) {}
+    nct_ctx* c = nullptr; T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(nct_ctx* ctx, size_t n) { alloc(ctx, n); }
     ~DevBuf() { if (p) c->release(p); }
     DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+    bool alloc(nct_ctx* ctx, size_t n) { if (p) c->release(p); c = ctx; p = (T*)ctx->alloc(n * sizeof(T)); return p != nullptr; }
     operator T*() const { return p; }
     bool ok() const { return p != nullptr; }
 };
@@ -87,6 +94,13 @@ template <typename T> struct DevBuf {
     return ctx->fail(NCT_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 #define NCT_LAUNCH_CHECK() NCT_HIP(hipGetLastError())
 #define NCT_REQUIRE(cond, ...) do { if (!(cond)) return ctx->fail(NCT_ERR_INVALID, __VA_ARGS__); } while (0)
+// an int-returning call (nctk_*, nct_ctx::mark, …) whose failure ends the calling function with the same code
+#define NCT_TRY(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
+// what the C-ABI entry points open and move data with: a null context is refused, the context's device is made current; copies and the wait are on the main stream
+#define NCT_CTX_ENTER() do { if (!ctx) return NCT_ERR_INVALID; NCT_HIP(hipSetDevice(ctx->device)); } while (0)
+#define NCT_H2D(dst, src, bytes) NCT_HIP(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, ctx->stream))
+#define NCT_D2H(dst, src, bytes) NCT_HIP(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, ctx->stream))
+#define NCT_SYNC() NCT_HIP(hipStreamSynchronize(ctx->stream))
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
@@ -119,7 +133,6 @@ int nctk_resize_u8c3(nct_ctx* ctx, hipStream_t s, const uint8_t* src, int sh, in
 int nctk_resize_f64c3(nct_ctx* ctx, hipStream_t s, const double* src, int sh, int sw, double* dst, int dh, int dw);
 void nct_cvt_free(nct_ctx* ctx);
 void nct_pair_free(nct_ctx* ctx);   // nct_pipeline.cpp
-int nct_stage_tag_nonlocal(); int nct_stage_tag_wls(); int nct_stage_tag_color();   // event-mark tags of the colour stage (nct_pipeline.cpp)
 // k_cluster.hip
 int nctk_kmeans_labels(nct_ctx* ctx, hipStream_t s, const float* feat_hwc_norm, int n, int C, int K, int iters, uint64_t seed, int* labels, int* nlabels_dev);
 int nctk_knn_graph(nct_ctx* ctx, hipStream_t s, const uint8_t* lab_u8, int h, int w, const int* labels, int lh, int lw, int nlabels, const int* nlabels_dev /*nullable: overrides nlabels*/, int samples,
@@ -142,12 +155,14 @@ struct nct_s1_graph {
     int nseg_hint, nsup_hint;                // what the host knows about the two counts (-1: nothing yet)
 };
 struct nct_s1_graph_bufs {
-    int n;
+    int n = 0;
     DevBuf<double> iw2, c_w, rev_w, hub_part, sup_part; DevBuf<unsigned long long> starts; DevBuf<int> c_src, rev_start, rev_src, seg_tgt, seg_e0, sup_start, sup_b0;
-    nct_s1_graph_bufs(nct_ctx* c, int n_) : n(n_), iw2(c, (size_t)8 * n_), c_w(c, (size_t)8 * n_), rev_w(c, (size_t)8 * n_), hub_part(c, ((size_t)n_ / 8 + 1) * 6), sup_part(c, ((size_t)n_ / 256 + 2) * 6),
-                                            starts(c, (size_t)n_ + 1), c_src(c, (size_t)8 * n_), rev_start(c, (size_t)n_ + 1), rev_src(c, (size_t)8 * n_), seg_tgt(c, (size_t)n_ / 8 + 1),
-                                            seg_e0(c, (size_t)n_ / 8 + 1), sup_start(c, (size_t)n_ + 1), sup_b0(c, (size_t)n_ / 256 + 2) {}
-    bool ok() const { return iw2.ok() && c_w.ok() && rev_w.ok() && hub_part.ok() && sup_part.ok() && starts.ok() && c_src.ok() && rev_start.ok() && rev_src.ok() && seg_tgt.ok() && seg_e0.ok() && sup_start.ok() && sup_b0.ok(); }
+    bool alloc(nct_ctx* c, int n_) {
+        n = n_;
+        return iw2.alloc(c, (size_t)8 * n_) && c_w.alloc(c, (size_t)8 * n_) && rev_w.alloc(c, (size_t)8 * n_) && hub_part.alloc(c, ((size_t)n_ / 8 + 1) * 6) && sup_part.alloc(c, ((size_t)n_ / 256 + 2) * 6) &&
+               starts.alloc(c, (size_t)n_ + 1) && c_src.alloc(c, (size_t)8 * n_) && rev_start.alloc(c, (size_t)n_ + 1) && rev_src.alloc(c, (size_t)8 * n_) && seg_tgt.alloc(c, (size_t)n_ / 8 + 1) &&
+               seg_e0.alloc(c, (size_t)n_ / 8 + 1) && sup_start.alloc(c, (size_t)n_ + 1) && sup_b0.alloc(c, (size_t)n_ / 256 + 2);
+    }
     nct_s1_graph view(int hint, int hint2) const { return nct_s1_graph{n, iw2, starts, c_src, c_w, rev_start, rev_src, rev_w, seg_tgt, seg_e0, hub_part, sup_start, sup_b0, sup_part, hint, hint2}; }
 };
 int nctk_s1_graph_build(nct_ctx* ctx, hipStream_t s, const int* knn_id, const double* knn_w, double nonlocalWeight, const nct_s1_graph& g, int* nseg_pinned /*nullable: [2] hub blocks, super-blocks*/);

@@ -10,7 +10,6 @@
 #include <cstring>
 #include <algorithm>
 #include <cmath>
-#include <memory>
 
 struct pair_state {
     uint8_t *src = nullptr, *out = nullptr;                    // device BGR images
@@ -22,26 +21,24 @@ static pair_state* pair_of(nct_ctx* ctx) {
     if (!ctx->pair) ctx->pair = new pair_state();
     return (pair_state*)ctx->pair;
 }
+// drop what the context holds of the last pair / reference list
+static void drop_images(nct_ctx* ctx, pair_state* P) {
+    if (P->src) { ctx->release(P->src); P->src = nullptr; }
+    for (uint8_t*& r : P->ref) if (r) { ctx->release(r); r = nullptr; }
+    if (P->out) { ctx->release(P->out); P->out = nullptr; }
+    P->K = 0;
+}
 // the images live in the context arena like every other device buffer (no hipMalloc/hipFree — device-wide synchronisation points —
 // between the pairs of other contexts in flight on the same GPU)
 void nct_pair_free(nct_ctx* ctx) {
     if (!ctx->pair) return;
-    pair_state* p = (pair_state*)ctx->pair;
-    if (p->src) ctx->release(p->src);
-    for (uint8_t* r : p->ref) if (r) ctx->release(r);
-    if (p->out) ctx->release(p->out);
-    delete p; ctx->pair = nullptr;
+    drop_images(ctx, (pair_state*)ctx->pair);
+    delete (pair_state*)ctx->pair; ctx->pair = nullptr;
 }
 
 static const int kTapC[5] = {64, 128, 256, 512, 512};       // tap 1 (conv1_1) … tap 5 (conv5_1)
 
-// stage tags of the event marks (nct_ctx::mark): tag = stage * 8 + level; a mark closes the stage it names
-enum { ST_OTHER = 0, ST_VGG, ST_CLUSTER, ST_PM, ST_VOTE, ST_KNN, ST_COLOR, ST_NONLOCAL, ST_WLS };
-static thread_local int g_tm_level = 0;          // pyramid level whose colour stage is being enqueued (per host thread = per context)
-int nct_stage_tag_nonlocal() { return ST_NONLOCAL * 8 + g_tm_level; }
-int nct_stage_tag_wls() { return ST_WLS * 8 + g_tm_level; }
-int nct_stage_tag_color() { return ST_COLOR * 8 + g_tm_level; }
-#define MARK(stage, level) do { int rcm_ = ctx->mark(s, (stage) * 8 + (level)); if (rcm_) return rcm_; } while (0)
+#define MARK(stage, level) NCT_TRY(ctx->mark(s, nct_stage_tag(stage, level)))
 
 static int read_marks(nct_ctx* ctx, nct_pair_timing* t) {
     double* acc[9] = {&t->other_ms, &t->vgg_ms, &t->cluster_ms, &t->patchmatch_ms, &t->vote_ms, &t->knn_ms, &t->color_ms, &t->nonlocal_ms, &t->wls_ms};
@@ -51,10 +48,10 @@ static int read_marks(nct_ctx* ctx, nct_pair_timing* t) {
         const int stage = ctx->tm_tags[i] >> 3, level = ctx->tm_tags[i] & 7;
         if (stage >= 0 && stage < 9) *acc[stage] += ms;
         if (level < 5) {
-            if (stage == ST_PM) t->pm_level_ms[level] += ms;
-            else if (stage == ST_VOTE) t->vote_level_ms[level] += ms;
-            else if (stage == ST_NONLOCAL) t->nonlocal_level_ms[level] += ms;
-            else if (stage == ST_WLS) t->wls_level_ms[level] += ms;
+            if (stage == NCT_ST_PM) t->pm_level_ms[level] += ms;
+            else if (stage == NCT_ST_VOTE) t->vote_level_ms[level] += ms;
+            else if (stage == NCT_ST_NONLOCAL) t->nonlocal_level_ms[level] += ms;
+            else if (stage == NCT_ST_WLS) t->wls_level_ms[level] += ms;
         }
     }
     if (getenv("NCT_HOST_TRACE") && ctx->tm_host.size() == ctx->tm_tags.size()) {
@@ -68,138 +65,188 @@ static int read_marks(nct_ctx* ctx, nct_pair_timing* t) {
     return 0;
 }
 
+// what a finished run (the main stream has been synchronised) leaves for nct_pair_timing beside total_ms: the stage marks, the kernel clock, the evaluation counters
+static int read_timing(nct_ctx* ctx, nct_pair_timing* timing, bool count) {
+    NCT_TRY(read_marks(ctx, timing));
+    for (size_t i = 0; i < ctx->kt_ids.size(); ++i) {               // NCT_FLAG_TIME_KERNELS: average the samples per kernel
+        float ms = 0.f;
+        NCT_HIP(hipEventElapsedTime(&ms, ctx->kt_events[2 * i], ctx->kt_events[2 * i + 1]));
+        const int id = ctx->kt_ids[i];
+        if (id >= 0 && id < 10) { timing->kernel_us[id] += 1e3 * ms; timing->kernel_samples[id] += 1; }
+    }
+    for (int id = 0; id < 10; ++id) if (timing->kernel_samples[id]) timing->kernel_us[id] /= timing->kernel_samples[id];
+    if (count) {
+        unsigned long long h[32];
+        NCT_HIP(hipMemcpy(h, ctx->d_counter, sizeof h, hipMemcpyDeviceToHost));
+        for (int l = 0; l < 5; ++l) { timing->pm_level_evals[l] = h[4 * l]; timing->pm_level_accepted[l] = h[4 * l + 1]; }
+    }
+    return 0;
+}
+
 // the full-resolution finish of the last level (nct_process_pair_fullres, SPEC §6.1): the original source on the device and where its result goes
 struct fullres_target { const uint8_t* src; int H, W; uint8_t* out; };
 
-// what one reference owns during a run (SPEC §6.2): its image pyramid, its five un-normalised taps, its NNFs; with several references also its G_k and E_k
+// what one reference owns during a run (SPEC §6.2): its image pyramid, its five un-normalised taps (HWC, indexed by level), its NNFs of both directions (kept from
+// level to level) and its R -> S distances; with several references also its G_k and E_k
 struct ref_bufs {
     int bh[5], bw[5], rs_range[5];
-    DevBuf<uint8_t>* pyr[5] = {};
-    DevBuf<float>* feat[5] = {};
-    DevBuf<uint32_t> *ann = nullptr, *bnn = nullptr, *ann_prev = nullptr, *bnn_prev = nullptr;
-    DevBuf<float> *bnnd = nullptr, *err = nullptr;
-    DevBuf<uint8_t>* guide = nullptr;
+    DevBuf<uint8_t> pyr[5];
+    DevBuf<float> feat[5];
+    DevBuf<uint32_t> ann, bnn, ann_prev, bnn_prev;
+    DevBuf<float> bnnd, err;
+    DevBuf<uint8_t> guide;
     const uint8_t* img[5];
-    ~ref_bufs() { for (auto* p : pyr) delete p; for (auto* p : feat) delete p; delete ann; delete bnn; delete ann_prev; delete bnn_prev; delete bnnd; delete err; delete guide; }
 };
 
-// run the whole L=5->1 loop on the device-resident source and its K references; fin (nullable) moves the last level's U1 / S2 / A1 onto the original source.
-// With K = 1 this enqueues a pair's launches and nothing else; lv and mlv (at most one of them) receive the level intermediates of a pair / of a multi run
-static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* lv, const fullres_target* fin = nullptr,
-                            const nct_multi_levels* mlv = nullptr) {
-    pair_state* P = (pair_state*)ctx->pair;
-    if (!P || !P->src || P->K < 1 || !P->ref[0]) return ctx->fail(NCT_ERR_STATE, "process: no pair uploaded");
-    hipStream_t s = ctx->stream;
-    const int H = P->sh, W = P->sw, K = P->K;
-    NCT_REQUIRE(!fin || K == 1, "process: no full-resolution finish with several references");
-    NCT_REQUIRE(prm->patch_size == 3 && prm->k_num == 8, "process: patch_size must be 3 and k_num 8 (Config.h:68-70)");
-    NCT_REQUIRE(prm->cluster_num >= 1 && prm->cluster_num <= 16, "process: cluster_num out of range");
-    NCT_REQUIRE(prm->levels >= 1 && prm->levels <= 5, "process: levels must be in [1, 5] (got %d)", prm->levels);
-    NCT_REQUIRE(!fin || !lv, "process: no level intermediates with a full-resolution finish");
-    NCT_REQUIRE(!lv || !mlv, "process: one kind of level intermediates at a time");
-    NCT_REQUIRE(!lv || K == 1, "process: nct_pair_levels describes a pair; several references report through nct_multi_levels");
-    if (timing) memset(timing, 0, sizeof *timing);
-    auto wall0 = std::chrono::steady_clock::now();
-    ctx->tm_on = timing != nullptr; ctx->tm_tags.clear(); ctx->tm_host.clear();
-    ctx->kt_on = timing != nullptr && (prm->flags & NCT_FLAG_TIME_KERNELS) != 0; ctx->kt_ids.clear();
-    struct TmOff { nct_ctx* c; ~TmOff() { c->tm_on = false; c->kt_on = false; } } tm_off{ctx};
-    const int nlevels = prm->levels;
-    const bool feat16 = (prm->flags & NCT_FLAG_FEAT16) != 0;
-    ctx->wls_split = (prm->flags & NCT_FLAG_LATENCY) ? 1 : 0;
-    const bool count = timing && (prm->flags & NCT_FLAG_COUNT_EVALS);
-    if (count) {
-        if (!ctx->d_counter) NCT_HIP(hipMalloc(&ctx->d_counter, 32 * sizeof(unsigned long long)));
-        NCT_HIP(hipMemsetAsync(ctx->d_counter, 0, 32 * sizeof(unsigned long long), s));
+// What the side stream writes: per level that runs, S's level image in Lab, its kNN graph and the graph-only part of S1's system (reverse adjacency, hub block
+// table: k_s1.hip), built behind each graph. THE RULE: no arena block that the side stream may still read or write is marked free before stream2 has been
+// synchronised. So the destructor first waits for the side stream, ends the deferral and frees what was released meanwhile, and only then do the members go back —
+// on every way out of a run, the error returns included. What the side stream only reads (S's pyramid, the labels) belongs to members of pair_run declared
+// in front of this one, which are therefore released after it.
+struct side_bufs {
+    nct_ctx* ctx;
+    DevBuf<uint8_t> slab[5];
+    DevBuf<int> knn_ids[5];
+    DevBuf<double> knn_ws[5];
+    nct_s1_graph_bufs s1g[5];
+    explicit side_bufs(nct_ctx* c) : ctx(c) {}
+    ~side_bufs() { (void)hipStreamSynchronize(ctx->stream2); ctx->defer_release = false; ctx->flush_deferred(); }
+};
+
+static const nct_multi_levels kNoLevels = {};
+
+// One run of the L=5->1 loop on the device-resident source and its K references: the state its stages share and, as members in the order the stages allocate them,
+// every buffer of the run (the arena is best-fit over cached blocks: order and sizes decide what a context holds afterwards). With K = 1 this enqueues a pair's
+// launches and nothing else.
+struct pair_run {
+    nct_ctx* const ctx; const nct_params* const prm; nct_pair_timing* const timing;
+    const nct_multi_levels* const lv;              // where the level intermediates go (every pointer nullable): a pair reports as the list of one reference
+    const nct_color_stages* const* const color;    // nullable: [5] the colour stage's coefficient maps a pair may ask for
+    const fullres_target* const fin;               // nullable: moves the last level's U1 / S2 / A1 onto the original source
+    pair_state* const P; const hipStream_t s;
+    const int H, W, K, nlevels; const size_t N;
+    const bool feat16, count;
+    size_t NR = 0;                                 // pixels of the largest reference: the shared scratch of R's normalised features
+    int ah[5], aw[5];
+    const uint8_t* simg[5];
+    ref_bufs R[NCT_MAX_REFS];
+    DevBuf<uint8_t> s_lab_full, spyr[5];
+    DevBuf<float> sfeat;                           // S features of the current level, channel-last (largest: H x W x 64)
+    DevBuf<int> labels, nlab_dev;
+    DevBuf<float> na, nb, voted, nvoted;
+    DevBuf<uint16_t> na_h, nb_h;                   // fp16 shadow maps of the normalised features: the candidate tiles of the opt-in reduced-precision mode (NCT_FLAG_FEAT16)
+    side_bufs side;
+    // annd is scratch shared by the references. err / guide: what the colour stage reads — reference 0's own maps with K = 1, the merged maps (rule 3) with several
+    DevBuf<float> annd, err;
+    DevBuf<uint8_t> guide, g_lab_l, out_lab;
+    DevBuf<uint8_t> sel_label;                     // the selection's label map (rule 2); a pair allocates none of this
+    const nct_color_params cp;
+
+    pair_run(nct_ctx* c, const nct_params* p, nct_pair_timing* t, const nct_multi_levels* levels, const nct_color_stages* const* col, const fullres_target* f)
+        : ctx(c), prm(p), timing(t), lv(levels ? levels : &kNoLevels), color(col), fin(f), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
+          nlevels(p->levels), N((size_t)H * W), feat16((p->flags & NCT_FLAG_FEAT16) != 0), count(t && (p->flags & NCT_FLAG_COUNT_EVALS)), side(c),
+          cp{p->eps, p->nonlocal_weight, p->local_weight, p->wls_lambda_init, p->wls_alpha, (double)p->k_num} {}
+
+    int d2h(void* dst, const void* src, size_t bytes) {
+        if (dst) NCT_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+        return 0;
     }
-    MARK(ST_OTHER, 0);
 
     // level geometry, coarse -> fine (level 0 = conv5_1)
-    int ah[5], aw[5];
-    { int h = H, w = W;
-      for (int t = 0; t < 5; ++t) { ah[4 - t] = h; aw[4 - t] = w; h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; } }
-    std::vector<ref_bufs> R(K);
-    size_t NR = 0;                                                                             // pixels of the largest reference: the shared scratch of R's normalised features
-    for (int k = 0; k < K; ++k) {
-        int h2 = P->rh[k], w2 = P->rw[k];
-        for (int t = 0; t < 5; ++t) { R[k].bh[4 - t] = h2; R[k].bw[4 - t] = w2; h2 = (h2 - 1) / 2 + 1; w2 = (w2 - 1) / 2 + 1; }
-        // the random-search radius of reference k is the pair (S, R_k)'s own (SPEC §6.2 rule 1), not the largest reference's
-        const int maxLen = std::max(std::max(W, H), std::max(P->rw[k], P->rh[k]));
-        const int rs[5] = {maxLen / 16, maxLen / 32, maxLen / 64, 32, 32};                     // main.cu:77-83
-        for (int l = 0; l < 5; ++l) R[k].rs_range[l] = rs[l];
-        NR = std::max(NR, (size_t)P->rh[k] * P->rw[k]);
-    }
-    const size_t N = (size_t)H * W;
-
-    // ---- S in Lab (ColorTransfer ctor, ColorTransfer.h:54-75) and image pyramids (main.cu:104-108)
-    DevBuf<uint8_t> s_lab_full(ctx, N * 3);
-    if (!s_lab_full.ok()) return NCT_ERR_HIP;
-    int rc = nctk_bgr2lab(ctx, s, P->src, s_lab_full, N); if (rc) return rc;
-    std::vector<DevBuf<uint8_t>*> spyr(5, nullptr);
-    struct Cleanup { std::vector<DevBuf<uint8_t>*>&a; ~Cleanup() { for (auto* p : a) delete p; } } cleanup{spyr};
-    const uint8_t* simg[5];
-    simg[4] = P->src;
-    for (int k = 0; k < K; ++k) R[k].img[4] = P->ref[k];
-    for (int l = 3; l >= 0; --l) {
-        spyr[l] = new DevBuf<uint8_t>(ctx, (size_t)ah[l] * aw[l] * 3);
-        if (!spyr[l]->ok()) return NCT_ERR_HIP;
-        for (int k = 0; k < K; ++k) { R[k].pyr[l] = new DevBuf<uint8_t>(ctx, (size_t)R[k].bh[l] * R[k].bw[l] * 3); if (!R[k].pyr[l]->ok()) return NCT_ERR_HIP; }
-        rc = nctk_resize_u8c3(ctx, s, simg[l + 1], ah[l + 1], aw[l + 1], *spyr[l], ah[l], aw[l]); if (rc) return rc;
-        simg[l] = *spyr[l];
+    void geometry() {
+        { int h = H, w = W;
+          for (int t = 0; t < 5; ++t) { ah[4 - t] = h; aw[4 - t] = w; h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; } }
         for (int k = 0; k < K; ++k) {
-            rc = nctk_resize_u8c3(ctx, s, R[k].img[l + 1], R[k].bh[l + 1], R[k].bw[l + 1], *R[k].pyr[l], R[k].bh[l], R[k].bw[l]); if (rc) return rc;
-            R[k].img[l] = *R[k].pyr[l];
+            int h2 = P->rh[k], w2 = P->rw[k];
+            for (int t = 0; t < 5; ++t) { R[k].bh[4 - t] = h2; R[k].bw[4 - t] = w2; h2 = (h2 - 1) / 2 + 1; w2 = (w2 - 1) / 2 + 1; }
+            // the random-search radius of reference k is the pair (S, R_k)'s own (SPEC §6.2 rule 1), not the largest reference's
+            const int maxLen = std::max(std::max(W, H), std::max(P->rw[k], P->rh[k]));
+            const int rs[5] = {maxLen / 16, maxLen / 32, maxLen / 64, 32, 32};                     // main.cu:77-83
+            for (int l = 0; l < 5; ++l) R[k].rs_range[l] = rs[l];
+            NR = std::max(NR, (size_t)P->rh[k] * P->rw[k]);
         }
     }
-    MARK(ST_OTHER, 0);
 
-    // ---- VGG19: R once (all five taps kept, HWC), S to conv5_1 (main.cu:94,102)
-    DevBuf<float> sfeat(ctx, (size_t)64 * N);   // S features of the current level, channel-last (largest: H x W x 64)
-    if (!sfeat.ok()) return NCT_ERR_HIP;
-    // R features (ref_bufs::feat): un-normalised, HWC, indexed by level
-    for (int k = 0; k < K; ++k) {
-        // the five taps of R arrive channel-last straight from their conv layers' epilogues (round 4: no CHW -> HWC transpose pass)
-        float* taps_hwc[5];
-        for (int t = 0; t < 5; ++t) {
-            const int l = 4 - t;
-            R[k].feat[l] = new DevBuf<float>(ctx, (size_t)kTapC[t] * R[k].bh[l] * R[k].bw[l]); if (!R[k].feat[l]->ok()) return NCT_ERR_HIP;
-            taps_hwc[t] = *R[k].feat[l];
+    // S in Lab (ColorTransfer ctor, ColorTransfer.h:54-75) and image pyramids (main.cu:104-108)
+    int lab_and_pyramids() {
+        if (!s_lab_full.alloc(ctx, N * 3)) return NCT_ERR_HIP;
+        NCT_TRY(nctk_bgr2lab(ctx, s, P->src, s_lab_full, N));
+        simg[4] = P->src;
+        for (int k = 0; k < K; ++k) R[k].img[4] = P->ref[k];
+        for (int l = 3; l >= 0; --l) {
+            if (!spyr[l].alloc(ctx, (size_t)ah[l] * aw[l] * 3)) return NCT_ERR_HIP;
+            for (int k = 0; k < K; ++k) if (!R[k].pyr[l].alloc(ctx, (size_t)R[k].bh[l] * R[k].bw[l] * 3)) return NCT_ERR_HIP;
+            NCT_TRY(nctk_resize_u8c3(ctx, s, simg[l + 1], ah[l + 1], aw[l + 1], spyr[l], ah[l], aw[l]));
+            simg[l] = spyr[l];
+            for (int k = 0; k < K; ++k) {
+                NCT_TRY(nctk_resize_u8c3(ctx, s, R[k].img[l + 1], R[k].bh[l + 1], R[k].bw[l + 1], R[k].pyr[l], R[k].bh[l], R[k].bw[l]));
+                R[k].img[l] = R[k].pyr[l];
+            }
         }
-        if (k == 0) {
-            // R and S together: conv5_1 of both images is one launch (two grids of 124 workgroups at 700 x 700 would each leave half the chip idle)
-            float* staps_hwc[5] = {nullptr, nullptr, nullptr, nullptr, sfeat};
-            rc = nctk_vgg19_forward_pair(ctx, s, P->ref[0], P->rh[0], P->rw[0], P->rw[0] * 3, taps_hwc, P->src, H, W, W * 3, staps_hwc); if (rc) return rc;
-        } else {
-            // the further references (SPEC §6.2) have no partner for their last layer: a forward of their own
-            rc = nctk_vgg19_forward(ctx, s, P->ref[k], P->rh[k], P->rw[k], P->rw[k] * 3, 5, nullptr, nullptr, taps_hwc); if (rc) return rc;
-        }
+        MARK(NCT_ST_OTHER, 0);
+        return NCT_OK;
     }
-    MARK(ST_VGG, 0);
 
-    // ---- C1: cluster the coarsest S features (main.cu:139-168)
-    DevBuf<int> labels(ctx, (size_t)ah[0] * aw[0]), nlab_dev(ctx, 1);
-    DevBuf<float> na(ctx, (size_t)64 * N), nb(ctx, (size_t)64 * NR), voted(ctx, (size_t)64 * N), nvoted(ctx, (size_t)64 * N);
-    // fp16 shadow maps of the normalised features: the candidate tiles of the opt-in reduced-precision mode (NCT_FLAG_FEAT16)
-    DevBuf<uint16_t> na_h(ctx, feat16 ? (size_t)64 * N : 8), nb_h(ctx, feat16 ? (size_t)64 * NR : 8);
-    if (!labels.ok() || !nlab_dev.ok() || !na.ok() || !nb.ok() || !voted.ok() || !nvoted.ok() || !na_h.ok() || !nb_h.ok()) return NCT_ERR_HIP;
-    rc = nctk_normalize(ctx, s, sfeat, na, nullptr, 512, ah[0] * aw[0], feat16 ? (uint16_t*)na_h : nullptr); if (rc) return rc;
-    rc = nctk_kmeans_labels(ctx, s, na, ah[0] * aw[0], 512, prm->cluster_num, 11, (uint64_t)prm->seed, labels, nlab_dev); if (rc) return rc;
-    // the number of labels (1 if k-means degenerated, else K) stays on the device: reading it back would stall the host — and with it
-    // the enqueueing of everything below — until the VGG forwards and k-means have finished
-    MARK(ST_CLUSTER, 0);
+    // VGG19: R once (all five taps kept, HWC), S to conv5_1 (main.cu:94,102)
+    int forwards() {
+        if (!sfeat.alloc(ctx, (size_t)64 * N)) return NCT_ERR_HIP;
+        for (int k = 0; k < K; ++k) {
+            // the five taps of R arrive channel-last straight from their conv layers' epilogues (round 4: no CHW -> HWC transpose pass)
+            float* taps_hwc[5];
+            for (int t = 0; t < 5; ++t) {
+                const int l = 4 - t;
+                if (!R[k].feat[l].alloc(ctx, (size_t)kTapC[t] * R[k].bh[l] * R[k].bw[l])) return NCT_ERR_HIP;
+                taps_hwc[t] = R[k].feat[l];
+            }
+            if (k == 0) {
+                // R and S together: conv5_1 of both images is one launch (two grids of 124 workgroups at 700 x 700 would each leave half the chip idle)
+                float* staps_hwc[5] = {nullptr, nullptr, nullptr, nullptr, sfeat};
+                NCT_TRY(nctk_vgg19_forward_pair(ctx, s, P->ref[0], P->rh[0], P->rw[0], P->rw[0] * 3, taps_hwc, P->src, H, W, W * 3, staps_hwc));
+            } else {
+                // the further references (SPEC §6.2) have no partner for their last layer: a forward of their own
+                NCT_TRY(nctk_vgg19_forward(ctx, s, P->ref[k], P->rh[k], P->rw[k], P->rw[k] * 3, 5, nullptr, nullptr, taps_hwc));
+            }
+        }
+        MARK(NCT_ST_VGG, 0);
+        return NCT_OK;
+    }
 
-    // ---- K1 for the levels that run (nct_params.levels) on the side stream: the kNN graph of a level depends only on the level image of S and on the
+    // C1: cluster the coarsest S features (main.cu:139-168)
+    int cluster() {
+        if (!labels.alloc(ctx, (size_t)ah[0] * aw[0]) || !nlab_dev.alloc(ctx, 1)) return NCT_ERR_HIP;
+        if (!na.alloc(ctx, (size_t)64 * N) || !nb.alloc(ctx, (size_t)64 * NR) || !voted.alloc(ctx, (size_t)64 * N) || !nvoted.alloc(ctx, (size_t)64 * N)) return NCT_ERR_HIP;
+        if (!na_h.alloc(ctx, feat16 ? (size_t)64 * N : 8) || !nb_h.alloc(ctx, feat16 ? (size_t)64 * NR : 8)) return NCT_ERR_HIP;
+        NCT_TRY(nctk_normalize(ctx, s, sfeat, na, nullptr, 512, ah[0] * aw[0], feat16 ? (uint16_t*)na_h : nullptr));
+        NCT_TRY(nctk_kmeans_labels(ctx, s, na, ah[0] * aw[0], 512, prm->cluster_num, 11, (uint64_t)prm->seed, labels, nlab_dev));
+        // the number of labels (1 if k-means degenerated, else K) stays on the device: reading it back would stall the host — and with it
+        // the enqueueing of everything below — until the VGG forwards and k-means have finished
+        MARK(NCT_ST_CLUSTER, 0);
+        return NCT_OK;
+    }
+
+    // what the level loop (main.cu:179-428) works in, and the result image
+    int level_buffers() {
+        for (int k = 0; k < K; ++k) {
+            const size_t nr = (size_t)P->rh[k] * P->rw[k];
+            if (!R[k].ann.alloc(ctx, N) || !R[k].bnn.alloc(ctx, nr) || !R[k].ann_prev.alloc(ctx, N) || !R[k].bnn_prev.alloc(ctx, nr)) return NCT_ERR_HIP;
+        }
+        if (!annd.alloc(ctx, N)) return NCT_ERR_HIP;
+        for (int k = 0; k < K; ++k) if (!R[k].bnnd.alloc(ctx, (size_t)P->rh[k] * P->rw[k])) return NCT_ERR_HIP;
+        if (!err.alloc(ctx, N) || !guide.alloc(ctx, N * 3) || !g_lab_l.alloc(ctx, N * 3) || !out_lab.alloc(ctx, N * 3)) return NCT_ERR_HIP;
+        if (K > 1) {
+            if (!sel_label.alloc(ctx, N)) return NCT_ERR_HIP;
+            for (int k = 0; k < K; ++k) if (!R[k].err.alloc(ctx, N) || !R[k].guide.alloc(ctx, N * 3)) return NCT_ERR_HIP;
+        }
+        if (!P->out) { P->out = (uint8_t*)ctx->alloc(N * 3); if (!P->out) return NCT_ERR_HIP; }
+        return d2h(lv->labels, labels, sizeof(int) * (size_t)ah[0] * aw[0]);
+    }
+
+    // K1 for the levels that run (nct_params.levels) on the side stream: the kNN graph of a level depends only on the level image of S and on the
     // labels (main.cu:351-359), not on the correspondence, so it overlaps with PatchMatch / votes / solvers of the main stream
     // (whose many small launches leave most CUs idle). Scratch released meanwhile stays reserved until the join (nct_internal.h).
-    std::vector<DevBuf<uint8_t>*> slab(5, nullptr);
-    std::vector<DevBuf<int>*> knn_ids(5, nullptr);
-    std::vector<DevBuf<double>*> knn_ws(5, nullptr);
-    std::vector<nct_s1_graph_bufs*> s1g(5, nullptr);       // the graph-only part of S1's system (reverse adjacency, hub block table: k_s1.hip), built behind each graph
-    struct Cleanup3 { std::vector<DevBuf<uint8_t>*>& a; std::vector<DevBuf<int>*>& b; std::vector<DevBuf<double>*>& c; std::vector<nct_s1_graph_bufs*>& d; nct_ctx* ctx;
-                      ~Cleanup3() { (void)hipStreamSynchronize(ctx->stream2); ctx->defer_release = false; ctx->flush_deferred();
-                                    for (auto* p : a) delete p; for (auto* p : b) delete p; for (auto* p : c) delete p; for (auto* p : d) delete p; } } cleanup3{slab, knn_ids, knn_ws, s1g, ctx};
-    // enqueued from inside the level loop, AFTER the coarsest level's correspondence work has been submitted: the side stream's ~200
+    // Enqueued from inside the level loop, AFTER the coarsest level's correspondence work has been submitted: the side stream's ~200
     // small packets would otherwise sit in front of the main stream's and the main stream starts the level loop ~2.6 ms late
-    auto enqueue_knn = [&]() -> int {
+    int enqueue_side_graphs() {
         // arena blocks are recycled in stream order: the side stream may reuse blocks the main stream released up to this point, so it
         // starts behind everything enqueued on the main stream so far
         hipStream_t s2 = ctx->stream2;
@@ -207,147 +254,89 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
         NCT_HIP(hipStreamWaitEvent(s2, ctx->ev_fork, 0));
         for (int l = 0; l < nlevels; ++l) {
             const size_t npx = (size_t)ah[l] * aw[l];
-            slab[l] = new DevBuf<uint8_t>(ctx, npx * 3); knn_ids[l] = new DevBuf<int>(ctx, npx * 8); knn_ws[l] = new DevBuf<double>(ctx, npx * 8);
-            s1g[l] = new nct_s1_graph_bufs(ctx, (int)npx);
-            if (!slab[l]->ok() || !knn_ids[l]->ok() || !knn_ws[l]->ok() || !s1g[l]->ok()) return NCT_ERR_HIP;
+            if (!side.slab[l].alloc(ctx, npx * 3) || !side.knn_ids[l].alloc(ctx, npx * 8) || !side.knn_ws[l].alloc(ctx, npx * 8) || !side.s1g[l].alloc(ctx, (int)npx)) return NCT_ERR_HIP;
         }
-        int rc2 = 0;
+        int rc = 0;
         ctx->defer_release = true;
-        for (int l = 0; l < nlevels && rc2 == 0; ++l) {      // only the levels that run (nct_params.levels)
-            rc2 = nctk_bgr2lab(ctx, s2, simg[l], *slab[l], (size_t)ah[l] * aw[l]);
-            if (rc2 == 0) rc2 = nctk_knn_graph(ctx, s2, *slab[l], ah[l], aw[l], labels, ah[0], aw[0], 0, nlab_dev, 1 << l, *knn_ids[l], *knn_ws[l]);
+        for (int l = 0; l < nlevels && rc == 0; ++l) {      // only the levels that run (nct_params.levels)
+            rc = nctk_bgr2lab(ctx, s2, simg[l], side.slab[l], (size_t)ah[l] * aw[l]);
+            if (rc == 0) rc = nctk_knn_graph(ctx, s2, side.slab[l], ah[l], aw[l], labels, ah[0], aw[0], 0, nlab_dev, 1 << l, side.knn_ids[l], side.knn_ws[l]);
             // S1's reverse adjacency and hub block table depend on the graph alone: built here, off the main stream; the block count lands in page-locked memory
             // before ev_level[l] completes, so the host can size (or skip) the level's hub passes without a synchronisation
-            if (rc2 == 0) rc2 = nctk_s1_graph_build(ctx, s2, *knn_ids[l], *knn_ws[l], sqrt(prm->nonlocal_weight / (double)prm->k_num), s1g[l]->view(-1, -1), ctx->s1_hub_blocks() + 2 * l);
-            if (rc2 == 0 && hipEventRecord(ctx->ev_level[l], s2) != hipSuccess) rc2 = ctx->fail(NCT_ERR_HIP, "hipEventRecord failed");
+            if (rc == 0) rc = nctk_s1_graph_build(ctx, s2, side.knn_ids[l], side.knn_ws[l], sqrt(prm->nonlocal_weight / (double)prm->k_num), side.s1g[l].view(-1, -1), ctx->s1_hub_blocks() + 2 * l);
+            if (rc == 0 && hipEventRecord(ctx->ev_level[l], s2) != hipSuccess) rc = ctx->fail(NCT_ERR_HIP, "hipEventRecord failed");
         }
         ctx->defer_release = false;
-        return rc2;
-    };
-
-    // ---- level loop (main.cu:179-428)
-    // per reference: the NNFs of both directions (kept from level to level) and the R -> S distances; annd is scratch shared by the references.
-    // err / guide: what the colour stage reads — reference 0's own maps with K = 1, the merged maps (rule 3) with several, whose E_k / G_k are allocated below
-    for (int k = 0; k < K; ++k) {
-        const size_t nr = (size_t)P->rh[k] * P->rw[k];
-        R[k].ann = new DevBuf<uint32_t>(ctx, N); R[k].bnn = new DevBuf<uint32_t>(ctx, nr); R[k].ann_prev = new DevBuf<uint32_t>(ctx, N); R[k].bnn_prev = new DevBuf<uint32_t>(ctx, nr);
-        if (!R[k].ann->ok() || !R[k].bnn->ok() || !R[k].ann_prev->ok() || !R[k].bnn_prev->ok()) return NCT_ERR_HIP;
+        return rc;
     }
-    DevBuf<float> annd(ctx, N);
-    for (int k = 0; k < K; ++k) { R[k].bnnd = new DevBuf<float>(ctx, (size_t)P->rh[k] * P->rw[k]); if (!R[k].bnnd->ok()) return NCT_ERR_HIP; }
-    DevBuf<float> err(ctx, N);
-    DevBuf<uint8_t> guide(ctx, N * 3), g_lab_l(ctx, N * 3), out_lab(ctx, N * 3);
-    if (!annd.ok() || !err.ok() || !guide.ok() || !g_lab_l.ok() || !out_lab.ok()) return NCT_ERR_HIP;
-    std::unique_ptr<DevBuf<uint8_t>> sel_label;                // the selection's label map (rule 2); a pair allocates none of this
-    if (K > 1) {
-        sel_label.reset(new DevBuf<uint8_t>(ctx, N));
-        if (!sel_label->ok()) return NCT_ERR_HIP;
-        for (int k = 0; k < K; ++k) {
-            R[k].err = new DevBuf<float>(ctx, N); R[k].guide = new DevBuf<uint8_t>(ctx, N * 3);
-            if (!R[k].err->ok() || !R[k].guide->ok()) return NCT_ERR_HIP;
-        }
-    }
-    if (!P->out) { P->out = (uint8_t*)ctx->alloc(N * 3); if (!P->out) return NCT_ERR_HIP; }
-    auto d2h = [&](void* dst, const void* src, size_t bytes) -> int {
-        if (dst) NCT_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
-        return 0;
-    };
-    if (lv) { rc = d2h(lv->labels, labels, sizeof(int) * (size_t)ah[0] * aw[0]); if (rc) return rc; }
-    if (mlv) { rc = d2h(mlv->labels, labels, sizeof(int) * (size_t)ah[0] * aw[0]); if (rc) return rc; }
-    nct_color_params cp{prm->eps, prm->nonlocal_weight, prm->local_weight, prm->wls_lambda_init, prm->wls_alpha, (double)prm->k_num};
 
-    for (int l = 0; l < nlevels; ++l) {
+    // the correspondence of level l with reference k (SPEC §6.2 rule 1): NNFs, PatchMatch both directions, BDS votes, matching error
+    int correspondence(int l, int k) {
         const int C = kTapC[4 - l];
-        const int na_px = ah[l] * aw[l];
-      // the correspondence of the level, once per reference in index order on the main stream (SPEC §6.2 rule 1); a pair runs the body once
-      for (int k = 0; k < K; ++k) {
         const int* bh = R[k].bh; const int* bw = R[k].bw;
-        const int nb_px = bh[l] * bw[l];
-        uint32_t *ann = *R[k].ann, *bnn = *R[k].bnn, *ann_prev = *R[k].ann_prev, *bnn_prev = *R[k].bnn_prev;
-        float* bnnd = *R[k].bnnd;
-        // where this reference's guidance image and matching error go: with several references into its own maps, which the selection merges below
-        uint8_t* guide_k = K > 1 ? (uint8_t*)*R[k].guide : (uint8_t*)guide;
-        float* err_k = K > 1 ? (float*)*R[k].err : (float*)err;
+        const int na_px = ah[l] * aw[l], nb_px = bh[l] * bw[l];
+        uint32_t *ann = R[k].ann, *bnn = R[k].bnn, *ann_prev = R[k].ann_prev, *bnn_prev = R[k].bnn_prev;
+        float* bnnd = R[k].bnnd;
         // NNF init / upsample (main.cu:230-251)
         if (l == 0) {
-            rc = nctk_nnf_init(ctx, s, ann, ah[0], aw[0], bh[0], bw[0]); if (rc) return rc;
-            rc = nctk_nnf_init(ctx, s, bnn, bh[0], bw[0], ah[0], aw[0]); if (rc) return rc;
+            NCT_TRY(nctk_nnf_init(ctx, s, ann, ah[0], aw[0], bh[0], bw[0]));
+            NCT_TRY(nctk_nnf_init(ctx, s, bnn, bh[0], bw[0], ah[0], aw[0]));
         } else {
             NCT_HIP(hipMemcpyAsync(ann_prev, ann, sizeof(uint32_t) * ah[l - 1] * aw[l - 1], hipMemcpyDeviceToDevice, s));
             NCT_HIP(hipMemcpyAsync(bnn_prev, bnn, sizeof(uint32_t) * bh[l - 1] * bw[l - 1], hipMemcpyDeviceToDevice, s));
-            rc = nctk_nnf_upsample(ctx, s, ann_prev, ann, ah[l], aw[l], bh[l], bw[l], ah[l - 1], aw[l - 1]); if (rc) return rc;
-            rc = nctk_nnf_upsample(ctx, s, bnn_prev, bnn, bh[l], bw[l], ah[l], aw[l], bh[l - 1], bw[l - 1]); if (rc) return rc;
+            NCT_TRY(nctk_nnf_upsample(ctx, s, ann_prev, ann, ah[l], aw[l], bh[l], bw[l], ah[l - 1], aw[l - 1]));
+            NCT_TRY(nctk_nnf_upsample(ctx, s, bnn_prev, bnn, bh[l], bw[l], ah[l], aw[l], bh[l - 1], bw[l - 1]));
         }
         // normalise (main.cu:259-275), PatchMatch both directions (main.cu:283-284); S's normalised features serve every reference
-        if (l > 0 && k == 0) { rc = nctk_normalize(ctx, s, sfeat, na, nullptr, C, na_px, feat16 ? (uint16_t*)na_h : nullptr); if (rc) return rc; }
-        rc = nctk_normalize(ctx, s, *R[k].feat[l], nb, nullptr, C, nb_px, feat16 ? (uint16_t*)nb_h : nullptr); if (rc) return rc;
-        MARK(ST_OTHER, l);
+        if (l > 0 && k == 0) NCT_TRY(nctk_normalize(ctx, s, sfeat, na, nullptr, C, na_px, feat16 ? (uint16_t*)na_h : nullptr));
+        NCT_TRY(nctk_normalize(ctx, s, R[k].feat[l], nb, nullptr, C, nb_px, feat16 ? (uint16_t*)nb_h : nullptr));
+        MARK(NCT_ST_OTHER, l);
         const uint32_t seed_ab = prm->seed ^ (0x9E3779B9u * (uint32_t)(2 * l + 1)), seed_ba = prm->seed ^ (0x9E3779B9u * (uint32_t)(2 * l + 2));
         // na, nb are unit vectors: the row-wise rejection is exact (and worth a third of the finest level: 15.7 vs 24.1 ms with NCT_PM_PLAIN). The fp16 tiles pay from C = 128 on (11-37 % per level); the C = 64 level is
         // latency bound, not byte bound (fp16 tiles: 15.8 vs 16.0 ms), and stays fp32
-#ifndef NCT_PIPE_PM_EXACT_MODE
-#define NCT_PIPE_PM_EXACT_MODE NCT_PM_ROWREJECT
-#endif
-        const int pm_mode = (feat16 && C >= 256) ? NCT_PM_FP16 : NCT_PIPE_PM_EXACT_MODE;
-        rc = nctk_patchmatch_bidir(ctx, s, na, nb, (const uint16_t*)na_h, (const uint16_t*)nb_h, C, ah[l], aw[l], bh[l], bw[l], prm->pm_iters, R[k].rs_range[l], seed_ab, seed_ba,
-                                   ann, annd, bnn, bnnd, pm_mode, count ? ctx->d_counter + 4 * l : nullptr); if (rc) return rc;
-        MARK(ST_PM, l);
+        const int pm_mode = (feat16 && C >= 256) ? NCT_PM_FP16 : NCT_PM_ROWREJECT;
+        NCT_TRY(nctk_patchmatch_bidir(ctx, s, na, nb, (const uint16_t*)na_h, (const uint16_t*)nb_h, C, ah[l], aw[l], bh[l], bw[l], prm->pm_iters, R[k].rs_range[l], seed_ab, seed_ba,
+                                      ann, annd, bnn, bnnd, pm_mode, count ? ctx->d_counter + 4 * l : nullptr));
+        MARK(NCT_ST_PM, l);
         if (timing) timing->pm_level_launches[l] += 1 + 4 * prm->pm_iters;
-        if (lv) {
-            rc = d2h(lv->ann[l], ann, sizeof(uint32_t) * na_px); if (rc) return rc;
-            rc = d2h(lv->bnn[l], bnn, sizeof(uint32_t) * nb_px); if (rc) return rc;
-            rc = d2h(lv->annd[l], annd, sizeof(float) * na_px); if (rc) return rc;
-            rc = d2h(lv->bnnd[l], bnnd, sizeof(float) * nb_px); if (rc) return rc;
-        }
-        if (mlv) {
-            rc = d2h(mlv->ann[k][l], ann, sizeof(uint32_t) * na_px); if (rc) return rc;
-            rc = d2h(mlv->bnn[k][l], bnn, sizeof(uint32_t) * nb_px); if (rc) return rc;
-            rc = d2h(mlv->annd[k][l], annd, sizeof(float) * na_px); if (rc) return rc;
-            rc = d2h(mlv->bnnd[k][l], bnnd, sizeof(float) * nb_px); if (rc) return rc;
-        }
+        NCT_TRY(d2h(lv->ann[k][l], ann, sizeof(uint32_t) * na_px));
+        NCT_TRY(d2h(lv->bnn[k][l], bnn, sizeof(uint32_t) * nb_px));
+        NCT_TRY(d2h(lv->annd[k][l], annd, sizeof(float) * na_px));
+        NCT_TRY(d2h(lv->bnnd[k][l], bnnd, sizeof(float) * nb_px));
         // BDS votes: guidance image (main.cu:291) and features + matching error (main.cu:303-318)
-        rc = nctk_bds_vote_both(ctx, s, R[k].img[l], *R[k].feat[l], ann, bnn, C, ah[l], aw[l], bh[l], bw[l], 1.0, prm->bds_weight, guide_k, voted); if (rc) return rc;
-        rc = nctk_normalize(ctx, s, voted, nvoted, nullptr, C, na_px); if (rc) return rc;
-        rc = nctk_feature_distance(ctx, s, na, nvoted, err_k, C, na_px); if (rc) return rc;
-        if (K > 1 && k == K - 1) {
-            // selection and merge (SPEC §6.2 rules 2-3): the one launch a level with several references adds; it counts as vote time
-            const float* errs[NCT_MAX_REFS]; const uint8_t* guides[NCT_MAX_REFS];
-            for (int q = 0; q < K; ++q) { errs[q] = *R[q].err; guides[q] = *R[q].guide; }
-            rc = nctk_select_reference(ctx, s, errs, guides, K, ah[l], aw[l], *sel_label, guide, err); if (rc) return rc;
+        NCT_TRY(nctk_bds_vote_both(ctx, s, R[k].img[l], R[k].feat[l], ann, bnn, C, ah[l], aw[l], bh[l], bw[l], 1.0, prm->bds_weight, guide_of(k), voted));
+        NCT_TRY(nctk_normalize(ctx, s, voted, nvoted, nullptr, C, na_px));
+        return nctk_feature_distance(ctx, s, na, nvoted, err_of(k), C, na_px);
+    }
+    // where reference k's guidance image and matching error go: with several references into its own maps, which the selection merges
+    uint8_t* guide_of(int k) { return K > 1 ? R[k].guide : guide; }
+    float* err_of(int k) { return K > 1 ? R[k].err : err; }
+
+    // the correspondence of the level, once per reference in index order on the main stream (SPEC §6.2 rule 1; a pair runs the body once), then what the colour stage reads: G and E
+    int correspondences(int l) {
+        const int na_px = ah[l] * aw[l];
+        for (int k = 0; k < K; ++k) {
+            NCT_TRY(correspondence(l, k));
+            if (K > 1 && k == K - 1) {
+                // selection and merge (SPEC §6.2 rules 2-3): the one launch a level with several references adds; it counts as vote time
+                const float* errs[NCT_MAX_REFS]; const uint8_t* guides[NCT_MAX_REFS];
+                for (int q = 0; q < K; ++q) { errs[q] = R[q].err; guides[q] = R[q].guide; }
+                NCT_TRY(nctk_select_reference(ctx, s, errs, guides, K, ah[l], aw[l], sel_label, guide, err));
+            }
+            MARK(NCT_ST_VOTE, l);
+            NCT_TRY(d2h(lv->ref_guide[k][l], guide_of(k), (size_t)na_px * 3));
+            NCT_TRY(d2h(lv->ref_err[k][l], err_of(k), sizeof(float) * na_px));
         }
-        MARK(ST_VOTE, l);
-        if (lv) {
-            rc = d2h(lv->guide[l], guide, (size_t)na_px * 3); if (rc) return rc;
-            rc = d2h(lv->err[l], err, sizeof(float) * na_px); if (rc) return rc;
-        }
-        if (mlv) {
-            rc = d2h(mlv->ref_guide[k][l], guide_k, (size_t)na_px * 3); if (rc) return rc;
-            rc = d2h(mlv->ref_err[k][l], err_k, sizeof(float) * na_px); if (rc) return rc;
-        }
-      }
-        if (mlv) {
-            // K = 1 has no selection: its label map is all zero and the merged maps are reference 0's
-            if (K > 1) { rc = d2h(mlv->label[l], *sel_label, (size_t)na_px); if (rc) return rc; }
-            else if (mlv->label[l]) memset(mlv->label[l], 0, (size_t)na_px);
-            rc = d2h(mlv->guide[l], guide, (size_t)na_px * 3); if (rc) return rc;
-            rc = d2h(mlv->err[l], err, sizeof(float) * na_px); if (rc) return rc;
-        }
-        // kNN graph in Lab (main.cu:351-359): computed on the side stream; join once before its first use
-        rc = nctk_bgr2lab(ctx, s, guide, g_lab_l, na_px); if (rc) return rc;
-        if (l == 0) { rc = enqueue_knn(); if (rc) return rc; }
-        NCT_HIP(hipStreamWaitEvent(s, ctx->ev_level[l], 0));          // level l's graph only: the fine levels keep overlapping
-        if (l == nlevels - 1) ctx->flush_deferred();
-        const uint8_t* s_lab_l = *slab[l]; const int* knn_id = *knn_ids[l]; const double* knn_w = *knn_ws[l];
-        MARK(ST_KNN, l);
-        // local colour transfer (main.cu:368-380)
-        g_tm_level = l;
-        nct_color_debug dbg{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        int wls_it[6] = {0, 0, 0, 0, 0, 0};
-        dbg.wls_iters = wls_it;
-        const nct_color_stages* cs = lv ? lv->color[l] : nullptr;
-        if (cs) { dbg.ab_local = cs->ab_local; dbg.ab_nonlocal = cs->ab_nonlocal; dbg.ab_up = cs->ab_up; dbg.rough = cs->roughness; dbg.ab_wls = cs->ab_wls; dbg.cg_iters = cs->cg_iters; }
-        // what the host knows about level l's hub blocks right now: the count, if the side stream has passed ev_level[l] (always, from the second level on: the host
-        // has just waited for the previous level's WLS solve); else -1 and the hub pass is launched on the device-side count. The result does not depend on it.
+        // K = 1 has no selection: its label map is all zero and the merged maps are reference 0's
+        if (K > 1) NCT_TRY(d2h(lv->label[l], sel_label, (size_t)na_px));
+        else if (lv->label[l]) memset(lv->label[l], 0, (size_t)na_px);
+        NCT_TRY(d2h(lv->guide[l], guide, (size_t)na_px * 3));
+        return d2h(lv->err[l], err, sizeof(float) * na_px);
+    }
+
+    // level l's prebuilt part of S1's system with what the host knows about its hub blocks right now: the count, if the side stream has passed ev_level[l] (always, from
+    // the second level on: the host has just waited for the previous level's WLS solve); else -1 and the hub pass is launched on the device-side count. The result does not depend on it.
+    nct_s1_graph s1_graph_of(int l) {
         int hub_hint = -1, sup_hint = -1;
         // the coarsest level's graph is built while the host is still far ahead of the GPU (the VGG forwards are running), so its count has not arrived when the host gets
         // here: wait for that one event. The GPU has the level's correspondence work queued meanwhile and the solve's 200 launches are enqueued faster than they execute;
@@ -356,53 +345,100 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
         if (ctx->s1_hub_hint && hipEventQuery(ctx->ev_level[l]) == hipSuccess) { hub_hint = *(volatile int*)(ctx->s1_hub_blocks() + 2 * l); sup_hint = *(volatile int*)(ctx->s1_hub_blocks() + 2 * l + 1); }
         (void)hipGetLastError();                                     // hipEventQuery's hipErrorNotReady is not an error
         ctx->s1_hub_blocks_last[l] = hub_hint;
-        const nct_s1_graph s1graph = s1g[l]->view(hub_hint, sup_hint);
+        return side.s1g[l].view(hub_hint, sup_hint);
+    }
+
+    // the colour stage of level l: the level's kNN graph joins from the side stream, local colour transfer (main.cu:368-380), the intermediate result in BGR
+    int color_stage(int l) {
+        const int na_px = ah[l] * aw[l];
+        // kNN graph in Lab (main.cu:351-359): computed on the side stream; join once before its first use
+        NCT_TRY(nctk_bgr2lab(ctx, s, guide, g_lab_l, na_px));
+        if (l == 0) NCT_TRY(enqueue_side_graphs());
+        NCT_HIP(hipStreamWaitEvent(s, ctx->ev_level[l], 0));          // level l's graph only: the fine levels keep overlapping
+        if (l == nlevels - 1) ctx->flush_deferred();
+        MARK(NCT_ST_KNN, l);
+        ctx->tm_level = l;
+        nct_color_debug dbg{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        int wls_it[6] = {0, 0, 0, 0, 0, 0};
+        dbg.wls_iters = wls_it;
+        const nct_color_stages* cs = color ? color[l] : nullptr;
+        if (cs) { dbg.ab_local = cs->ab_local; dbg.ab_nonlocal = cs->ab_nonlocal; dbg.ab_up = cs->ab_up; dbg.rough = cs->roughness; dbg.ab_wls = cs->ab_wls; dbg.cg_iters = cs->cg_iters; }
+        const nct_s1_graph s1graph = s1_graph_of(l);
+        const int cube = (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0;
         if (fin && l == nlevels - 1) {
             // the last level finishes on the original source: S0 in Lab once, here (its time counts as colour stage), U1 / S2 / A1 at H0 x W0
             const size_t N0 = (size_t)fin->H * fin->W;
             DevBuf<uint8_t> s0_lab(ctx, N0 * 3), out0_lab(ctx, N0 * 3);
             if (!s0_lab.ok() || !out0_lab.ok()) return NCT_ERR_HIP;
-            rc = nctk_bgr2lab(ctx, s, fin->src, s0_lab, N0); if (rc) return rc;
+            NCT_TRY(nctk_bgr2lab(ctx, s, fin->src, s0_lab, N0));
             const nct_finish_target ft{s0_lab, fin->H, fin->W, out0_lab};
-            rc = nctk_local_color_transfer(ctx, s, err, s_lab_l, g_lab_l, s_lab_full, knn_id, knn_w, l, ah[l], aw[l], H, W, cp, out_lab, timing ? &dbg : nullptr, &s1graph, &ft); if (rc) return rc;
-            rc = nctk_lab2bgr(ctx, s, out0_lab, fin->out, N0, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0); if (rc) return rc;
+            NCT_TRY(nctk_local_color_transfer(ctx, s, err, side.slab[l], g_lab_l, s_lab_full, side.knn_ids[l], side.knn_ws[l], l, ah[l], aw[l], H, W, cp, out_lab, timing ? &dbg : nullptr, &s1graph, &ft));
+            NCT_TRY(nctk_lab2bgr(ctx, s, out0_lab, fin->out, N0, cube));
         } else {
-            rc = nctk_local_color_transfer(ctx, s, err, s_lab_l, g_lab_l, s_lab_full, knn_id, knn_w, l, ah[l], aw[l], H, W, cp, out_lab, (timing || cs) ? &dbg : nullptr, &s1graph); if (rc) return rc;
+            NCT_TRY(nctk_local_color_transfer(ctx, s, err, side.slab[l], g_lab_l, s_lab_full, side.knn_ids[l], side.knn_ws[l], l, ah[l], aw[l], H, W, cp, out_lab, (timing || cs) ? &dbg : nullptr, &s1graph));
             if (cs && cs->wls_iters) for (int q = 0; q < 6; ++q) cs->wls_iters[q] = wls_it[q];
-            rc = nctk_lab2bgr(ctx, s, out_lab, P->out, N, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0); if (rc) return rc;
+            NCT_TRY(nctk_lab2bgr(ctx, s, out_lab, P->out, N, cube));
         }
-        if (timing) { timing->wls_iters[l] = *std::max_element(wls_it, wls_it + 6); }
-        MARK(ST_COLOR, l);
-        if (lv) { rc = d2h(lv->result[l], P->out, N * 3); if (rc) return rc; }
-        if (mlv) { rc = d2h(mlv->result[l], P->out, N * 3); if (rc) return rc; }
-        // re-predict: S features of the next level from the intermediate result (main.cu:424-427)
-        if (l < nlevels - 1) {
-            const int tap = 4 - l;                         // next level uses tap (5 - (l+1))
-            float* taps_hwc[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-            taps_hwc[tap - 1] = sfeat;
-            rc = nctk_vgg19_forward(ctx, s, P->out, H, W, W * 3, tap, nullptr, nullptr, taps_hwc); if (rc) return rc;
-            MARK(ST_VGG, l);
-        }
+        if (timing) timing->wls_iters[l] = *std::max_element(wls_it, wls_it + 6);
+        MARK(NCT_ST_COLOR, l);
+        return d2h(lv->result[l], P->out, N * 3);
     }
-    // the side stream's kNN graphs (one per level that ran) finish before their buffers go back (Cleanup3 synchronises stream2)
-    NCT_HIP(hipStreamSynchronize(s));
-    if (timing) {
-        timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-        rc = read_marks(ctx, timing); if (rc) return rc;
-        for (size_t i = 0; i < ctx->kt_ids.size(); ++i) {               // NCT_FLAG_TIME_KERNELS: average the samples per kernel
-            float ms = 0.f;
-            NCT_HIP(hipEventElapsedTime(&ms, ctx->kt_events[2 * i], ctx->kt_events[2 * i + 1]));
-            const int id = ctx->kt_ids[i];
-            if (id >= 0 && id < 10) { timing->kernel_us[id] += 1e3 * ms; timing->kernel_samples[id] += 1; }
-        }
-        for (int id = 0; id < 10; ++id) if (timing->kernel_samples[id]) timing->kernel_us[id] /= timing->kernel_samples[id];
+
+    // re-predict: S features of the next level from the intermediate result (main.cu:424-427)
+    int repredict(int l) {
+        const int tap = 4 - l;                         // next level uses tap (5 - (l+1))
+        float* taps_hwc[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        taps_hwc[tap - 1] = sfeat;
+        NCT_TRY(nctk_vgg19_forward(ctx, s, P->out, H, W, W * 3, tap, nullptr, nullptr, taps_hwc));
+        MARK(NCT_ST_VGG, l);
+        return NCT_OK;
+    }
+
+    // everything the run enqueues, and the wait for the main stream. The side stream's kNN graphs (one per level that ran) finish before their buffers go back (~side_bufs)
+    int run() {
         if (count) {
-            unsigned long long h[32];
-            NCT_HIP(hipMemcpy(h, ctx->d_counter, sizeof h, hipMemcpyDeviceToHost));
-            for (int l = 0; l < 5; ++l) { timing->pm_level_evals[l] = h[4 * l]; timing->pm_level_accepted[l] = h[4 * l + 1]; }
+            if (!ctx->d_counter) NCT_HIP(hipMalloc(&ctx->d_counter, 32 * sizeof(unsigned long long)));
+            NCT_HIP(hipMemsetAsync(ctx->d_counter, 0, 32 * sizeof(unsigned long long), s));
         }
+        MARK(NCT_ST_OTHER, 0);
+        geometry();
+        NCT_TRY(lab_and_pyramids());
+        NCT_TRY(forwards());
+        NCT_TRY(cluster());
+        NCT_TRY(level_buffers());
+        for (int l = 0; l < nlevels; ++l) {
+            NCT_TRY(correspondences(l));
+            NCT_TRY(color_stage(l));
+            if (l < nlevels - 1) NCT_TRY(repredict(l));
+        }
+        NCT_HIP(hipStreamSynchronize(s));
+        return NCT_OK;
     }
-    return NCT_OK;
+};
+
+// run the whole L=5->1 loop on the uploaded source and its K references. lv (nullable): host copies of the level intermediates; color (nullable, a pair only): [5] the
+// colour stage's coefficient maps per level; fin (nullable, a pair only): the full-resolution finish
+static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_multi_levels* lv = nullptr, const nct_color_stages* const* color = nullptr,
+                            const fullres_target* fin = nullptr) {
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->src || P->K < 1 || !P->ref[0]) return ctx->fail(NCT_ERR_STATE, "process: no pair uploaded");
+    NCT_REQUIRE(!fin || P->K == 1, "process: no full-resolution finish with several references");
+    NCT_REQUIRE(prm->patch_size == 3 && prm->k_num == 8, "process: patch_size must be 3 and k_num 8 (Config.h:68-70)");
+    NCT_REQUIRE(prm->cluster_num >= 1 && prm->cluster_num <= 16, "process: cluster_num out of range");
+    NCT_REQUIRE(prm->levels >= 1 && prm->levels <= 5, "process: levels must be in [1, 5] (got %d)", prm->levels);
+    NCT_REQUIRE(!fin || (!lv && !color), "process: no level intermediates with a full-resolution finish");
+    NCT_REQUIRE(!color || P->K == 1, "process: nct_pair_levels describes a pair; several references report through nct_multi_levels");
+    if (timing) memset(timing, 0, sizeof *timing);
+    auto wall0 = std::chrono::steady_clock::now();
+    ctx->tm_on = timing != nullptr; ctx->tm_tags.clear(); ctx->tm_host.clear();
+    ctx->kt_on = timing != nullptr && (prm->flags & NCT_FLAG_TIME_KERNELS) != 0; ctx->kt_ids.clear();
+    ctx->wls_split = (prm->flags & NCT_FLAG_LATENCY) ? 1 : 0;
+    pair_run run(ctx, prm, timing, lv, color, fin);
+    const int rc = run.run();
+    ctx->tm_on = false; ctx->kt_on = false;
+    if (rc || !timing) return rc;
+    timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    return read_timing(ctx, timing, run.count);
 }
 
 // SPEC §6.1 rule 1 (host/main.cpp's shrink: the longer side becomes max_side, the other (int)(max_side / (float)long * short)) and the limits of rule 5
@@ -422,14 +458,6 @@ const char* nct_working_size_rule(int h, int w, int max_side, int* work_h, int* 
     return nullptr;
 }
 
-// drop what the context holds of the last pair / reference list
-static void drop_images(nct_ctx* ctx, pair_state* P) {
-    if (P->src) { ctx->release(P->src); P->src = nullptr; }
-    for (uint8_t*& r : P->ref) if (r) { ctx->release(r); r = nullptr; }
-    if (P->out) { ctx->release(P->out); P->out = nullptr; }
-    P->K = 0;
-}
-
 // the source and its K references (checked by the caller) into the arena
 static int upload_images(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw) {
     pair_state* P = pair_of(ctx);
@@ -437,9 +465,9 @@ static int upload_images(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, i
     P->src = (uint8_t*)ctx->alloc((size_t)sh * sw * 3);
     if (!P->src) return NCT_ERR_HIP;
     for (int k = 0; k < K; ++k) { P->ref[k] = (uint8_t*)ctx->alloc((size_t)rh[k] * rw[k] * 3); if (!P->ref[k]) return NCT_ERR_HIP; }
-    NCT_HIP(hipMemcpyAsync(P->src, src_bgr, (size_t)sh * sw * 3, hipMemcpyHostToDevice, ctx->stream));
-    for (int k = 0; k < K; ++k) NCT_HIP(hipMemcpyAsync(P->ref[k], refs_bgr[k], (size_t)rh[k] * rw[k] * 3, hipMemcpyHostToDevice, ctx->stream));
-    NCT_HIP(hipStreamSynchronize(ctx->stream));
+    NCT_H2D(P->src, src_bgr, (size_t)sh * sw * 3);
+    for (int k = 0; k < K; ++k) NCT_H2D(P->ref[k], refs_bgr[k], (size_t)rh[k] * rw[k] * 3);
+    NCT_SYNC();
     P->sh = sh; P->sw = sw; P->K = K;
     for (int k = 0; k < K; ++k) { P->rh[k] = rh[k]; P->rw[k] = rw[k]; }
     return NCT_OK;
@@ -448,8 +476,7 @@ static int upload_images(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, i
 extern "C" {
 
 int nct_pair_upload(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     NCT_REQUIRE(src_bgr && ref_bgr, "pair_upload: null image");
     // the coarsest pyramid level (four ceil-halvings) must be at least 2x2 (init_Ann_kernel scales by (bw-1)/(aw-1)): side >= 17
     NCT_REQUIRE(sh >= 17 && sw >= 17 && rh >= 17 && rw >= 17 && sh <= 4000 && sw <= 4000 && rh <= 4000 && rw <= 4000,
@@ -458,8 +485,7 @@ int nct_pair_upload(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const 
 }
 
 int nct_multi_upload(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     NCT_REQUIRE(K >= 1 && K <= NCT_MAX_REFS, "multi_upload: the number of references must be in [1, %d] (got %d)", NCT_MAX_REFS, K);
     NCT_REQUIRE(src_bgr && refs_bgr && rh && rw, "multi_upload: null pointer");
     NCT_REQUIRE(sh >= 17 && sw >= 17 && sh <= 4000 && sw <= 4000, "multi_upload: image sides must be in [17, 4000] (source: %dx%d)", sw, sh);
@@ -471,55 +497,58 @@ int nct_multi_upload(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K
 }
 
 int nct_multi_run(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     NCT_REQUIRE(prm, "multi_run: null params");
-    return process_resident(ctx, prm, timing, nullptr);
+    return process_resident(ctx, prm, timing);
 }
 
 int nct_multi_run_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_multi_levels* levels) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     NCT_REQUIRE(prm, "multi_run_levels: null params");
-    return process_resident(ctx, prm, timing, nullptr, nullptr, levels);
+    return process_resident(ctx, prm, timing, levels);
 }
 
 int nct_process_multi(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw, const nct_params* prm,
                       uint8_t* out_bgr, nct_pair_timing* timing) {
-    int rc = nct_multi_upload(ctx, src_bgr, sh, sw, K, refs_bgr, rh, rw); if (rc) return rc;
-    rc = nct_multi_run(ctx, prm, timing); if (rc) return rc;
+    NCT_TRY(nct_multi_upload(ctx, src_bgr, sh, sw, K, refs_bgr, rh, rw));
+    NCT_TRY(nct_multi_run(ctx, prm, timing));
     return nct_pair_download(ctx, out_bgr);
 }
 
 int nct_pair_run(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     NCT_REQUIRE(prm, "pair_run: null params");
-    return process_resident(ctx, prm, timing, nullptr);
+    return process_resident(ctx, prm, timing);
 }
 
 int nct_pair_run_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* levels) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     NCT_REQUIRE(prm, "pair_run_levels: null params");
-    return process_resident(ctx, prm, timing, levels);
+    if (!levels) return process_resident(ctx, prm, timing);
+    // a pair is the list of one reference (SPEC §6.2): its maps are reference 0's NNFs and the merged guide / err; it has no label map and no G_k / E_k of their own
+    nct_multi_levels m; memset(&m, 0, sizeof m);
+    for (int l = 0; l < 5; ++l) {
+        m.ann[0][l] = levels->ann[l]; m.bnn[0][l] = levels->bnn[l]; m.annd[0][l] = levels->annd[l]; m.bnnd[0][l] = levels->bnnd[l];
+        m.guide[l] = levels->guide[l]; m.err[l] = levels->err[l]; m.result[l] = levels->result[l];
+    }
+    m.labels = levels->labels;
+    return process_resident(ctx, prm, timing, &m, levels->color);
 }
 
 int nct_pair_download(nct_ctx* ctx, uint8_t* out_bgr) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     pair_state* P = (pair_state*)ctx->pair;
     if (!P || !P->out) return ctx->fail(NCT_ERR_STATE, "pair_download: no result (call nct_pair_run first)");
     NCT_REQUIRE(out_bgr, "pair_download: null pointer");
-    NCT_HIP(hipMemcpyAsync(out_bgr, P->out, (size_t)P->sh * P->sw * 3, hipMemcpyDeviceToHost, ctx->stream));
-    NCT_HIP(hipStreamSynchronize(ctx->stream));
+    NCT_D2H(out_bgr, P->out, (size_t)P->sh * P->sw * 3);
+    NCT_SYNC();
     return NCT_OK;
 }
 
 int nct_process_pair(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw, const nct_params* prm,
                      uint8_t* out_bgr, nct_pair_timing* timing) {
-    int rc = nct_pair_upload(ctx, src_bgr, sh, sw, ref_bgr, rh, rw); if (rc) return rc;
-    rc = nct_pair_run(ctx, prm, timing); if (rc) return rc;
+    NCT_TRY(nct_pair_upload(ctx, src_bgr, sh, sw, ref_bgr, rh, rw));
+    NCT_TRY(nct_pair_run(ctx, prm, timing));
     return nct_pair_download(ctx, out_bgr);
 }
 
@@ -531,8 +560,7 @@ int nct_working_size(int h, int w, int max_side, int* work_h, int* work_w) {
 
 int nct_process_pair_fullres(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw, int max_side,
                              const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     NCT_REQUIRE(src_bgr && ref_bgr && prm && out_bgr, "process_pair_fullres: null pointer");
     int wh = 0, ww = 0, rwh = 0, rww = 0;
     const char* why = nct_working_size_rule(sh, sw, max_side, &wh, &ww);
@@ -549,30 +577,30 @@ int nct_process_pair_fullres(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int s
     P->ref[0] = (uint8_t*)ctx->alloc((size_t)rwh * rww * 3);
     if (!P->src || !P->ref[0]) return NCT_ERR_HIP;
     P->sh = P->sw = P->rh[0] = P->rw[0] = 0;
-    NCT_HIP(hipMemcpyAsync(s0, src_bgr, (size_t)sh * sw * 3, hipMemcpyHostToDevice, ctx->stream));
-    int rc = nctk_resize_u8c3(ctx, ctx->stream, s0, sh, sw, P->src, wh, ww); if (rc) return rc;
+    NCT_H2D(s0, src_bgr, (size_t)sh * sw * 3);
+    NCT_TRY(nctk_resize_u8c3(ctx, ctx->stream, s0, sh, sw, P->src, wh, ww));
     {
         DevBuf<uint8_t> r0(ctx, (size_t)rh * rw * 3);
         if (!r0.ok()) return NCT_ERR_HIP;
-        NCT_HIP(hipMemcpyAsync(r0, ref_bgr, (size_t)rh * rw * 3, hipMemcpyHostToDevice, ctx->stream));
-        rc = nctk_resize_u8c3(ctx, ctx->stream, r0, rh, rw, P->ref[0], rwh, rww); if (rc) return rc;
+        NCT_H2D(r0, ref_bgr, (size_t)rh * rw * 3);
+        NCT_TRY(nctk_resize_u8c3(ctx, ctx->stream, r0, rh, rw, P->ref[0], rwh, rww));
     }
-    NCT_HIP(hipStreamSynchronize(ctx->stream));
+    NCT_SYNC();
     P->sh = wh; P->sw = ww; P->rh[0] = rwh; P->rw[0] = rww; P->K = 1;
     if (!shrunk) {
         // rule 4: a source that is not shrunk has nothing to finish at another size — this is nct_process_pair on (S0, shrunk R)
-        rc = process_resident(ctx, prm, timing, nullptr); if (rc) return rc;
+        NCT_TRY(process_resident(ctx, prm, timing));
         return nct_pair_download(ctx, out_bgr);
     }
     DevBuf<uint8_t> o0(ctx, (size_t)sh * sw * 3);
     if (!o0.ok()) return NCT_ERR_HIP;
     const fullres_target fin{s0, sh, sw, o0};
-    rc = process_resident(ctx, prm, timing, nullptr, &fin);
+    const int rc = process_resident(ctx, prm, timing, nullptr, nullptr, &fin);
     // the working-size result buffer holds the second-to-last level's image: no nct_pair_download of it
     if (P->out) { ctx->release(P->out); P->out = nullptr; }
     if (rc) return rc;
-    NCT_HIP(hipMemcpyAsync(out_bgr, o0, (size_t)sh * sw * 3, hipMemcpyDeviceToHost, ctx->stream));
-    NCT_HIP(hipStreamSynchronize(ctx->stream));
+    NCT_D2H(out_bgr, o0, (size_t)sh * sw * 3);
+    NCT_SYNC();
     return NCT_OK;
 }
 

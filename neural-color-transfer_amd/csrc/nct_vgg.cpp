@@ -66,8 +66,7 @@ static int upload_layer(nct_ctx* ctx, int i, const float* w, const float* b) {
     DevBuf<float> tmp(ctx, nw);
     if (!tmp.ok()) return NCT_ERR_HIP;
     NCT_HIP(hipMemcpyAsync(tmp, w, sizeof(float) * nw, hipMemcpyHostToDevice, ctx->stream));
-    int rc = nctk_pack_weights(ctx, ctx->stream, tmp, v->wp[i], kCout[i], kCin[i], cin_pad);
-    if (rc) return rc;
+    NCT_TRY(nctk_pack_weights(ctx, ctx->stream, tmp, v->wp[i], kCout[i], kCin[i], cin_pad));
     NCT_HIP(hipMemcpyAsync(v->bias[i], b, sizeof(float) * kCout[i], hipMemcpyHostToDevice, ctx->stream));
     NCT_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -285,14 +284,12 @@ static int check_prototxt(const char* path, std::string& err) {
 extern "C" {
 
 int nct_vgg19_load_raw(nct_ctx* ctx, const float* const* weights, const float* const* biases, int nlayers) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     NCT_REQUIRE(weights && biases && nlayers >= kNeeded && nlayers <= NCONV, "vgg19_load_raw: need >= %d conv layers (conv1_1..conv5_1)", kNeeded);
     vgg_own(ctx)->loaded = false;
     for (int i = 0; i < kNeeded; ++i) {
         NCT_REQUIRE(weights[i] && biases[i], "vgg19_load_raw: layer %s missing", kConvName[i]);
-        int rc = upload_layer(ctx, i, weights[i], biases[i]);
-        if (rc) return rc;
+        NCT_TRY(upload_layer(ctx, i, weights[i], biases[i]));
     }
     vgg_of(ctx)->loaded = true;
     return NCT_OK;
@@ -318,18 +315,16 @@ int nct_model_layer(const nct_model* m, int layer, const float** weights, const 
 const char* nct_model_last_error(void) { return g_model_err.c_str(); }
 
 int nct_vgg19_load_model(nct_ctx* ctx, const nct_model* m) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     NCT_REQUIRE(m, "vgg19_load_model: null model");
     vgg_own(ctx)->loaded = false;
-    for (int i = 0; i < kNeeded; ++i) { int rc = upload_layer(ctx, i, m->w[i].data(), m->b[i].data()); if (rc) return rc; }
+    for (int i = 0; i < kNeeded; ++i) NCT_TRY(upload_layer(ctx, i, m->w[i].data(), m->b[i].data()));
     vgg_of(ctx)->loaded = true;
     return NCT_OK;
 }
 
 int nct_vgg19_load_caffemodel(nct_ctx* ctx, const char* path) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     NCT_REQUIRE(path, "vgg19_load_caffemodel: null path");
     nct_model m; std::string err;
     const int rc = parse_caffemodel(path, m, err);
@@ -391,8 +386,7 @@ static int vgg19_forward_impl(nct_ctx* ctx, hipStream_t s, const uint8_t* d_bgr,
     if (!pp0.ok() || !pp1.ok()) return NCT_ERR_HIP;
     float* pp[2] = {pp0, pp1};
     int h = H, w = W;
-    int rc = nctk_vgg_preprocess(ctx, s, d_bgr, stride, pp[0], H, W);
-    if (rc) return rc;
+    NCT_TRY(nctk_vgg_preprocess(ctx, s, d_bgr, stride, pp[0], H, W));
     const float* cur = pp[0];
     const int last = kTapConv[deepest_tap - 1];
     for (int i = 0; i <= last; ++i) {
@@ -409,15 +403,13 @@ static int vgg19_forward_impl(nct_ctx* ctx, hipStream_t s, const uint8_t* d_bgr,
         const bool pooled = kPoolAfter[i] && i < last;
         const bool fuse = pooled && tap < 0 && (ctx->conv_pool_fuse == 1 || (ctx->conv_pool_fuse < 0 && nctk_conv3x3_pool_fits(h, w)));
         if (into_stop && (fuse || !pooled)) dst = stop_into;
-        rc = nctk_conv3x3(ctx, s, cur, v->wp[i], v->bias[i], dst, (kCin[i] + 1) & ~1, kCout[i], h, w, 1, fuse ? 1 : 0, dst_hwc);
-        if (rc) return rc;
+        NCT_TRY(nctk_conv3x3(ctx, s, cur, v->wp[i], v->bias[i], dst, (kCin[i] + 1) & ~1, kCout[i], h, w, 1, fuse ? 1 : 0, dst_hwc));
         cur = dst;
         if (tap >= 0 && dims) { dims[tap * 3 + 0] = kCout[i]; dims[tap * 3 + 1] = h; dims[tap * 3 + 2] = w; }
         if (fuse) { h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
         else if (pooled) {
             float* pd = into_stop ? stop_into : ((cur == pp[0]) ? pp[1] : pp[0]);
-            rc = nctk_maxpool2x2(ctx, s, cur, pd, kCout[i], h, w);
-            if (rc) return rc;
+            NCT_TRY(nctk_maxpool2x2(ctx, s, cur, pd, kCout[i], h, w));
             cur = pd; h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1;
         }
     }
@@ -433,8 +425,8 @@ int nctk_vgg19_forward_pair(nct_ctx* ctx, hipStream_t s, const uint8_t* d_bgr1, 
     DevBuf<float> p1(ctx, (size_t)512 * pooled4(H1) * pooled4(W1)), p2(ctx, (size_t)512 * pooled4(H2) * pooled4(W2));
     if (!p1.ok() || !p2.ok()) return NCT_ERR_HIP;
     int h1 = 0, w1 = 0, h2 = 0, w2 = 0;
-    int rc = vgg19_forward_impl(ctx, s, d_bgr1, H1, W1, stride1, 5, nullptr, nullptr, taps_hwc1, p1, &h1, &w1); if (rc) return rc;
-    rc = vgg19_forward_impl(ctx, s, d_bgr2, H2, W2, stride2, 5, nullptr, nullptr, taps_hwc2, p2, &h2, &w2); if (rc) return rc;
+    NCT_TRY(vgg19_forward_impl(ctx, s, d_bgr1, H1, W1, stride1, 5, nullptr, nullptr, taps_hwc1, p1, &h1, &w1));
+    NCT_TRY(vgg19_forward_impl(ctx, s, d_bgr2, H2, W2, stride2, 5, nullptr, nullptr, taps_hwc2, p2, &h2, &w2));
     vgg_weights* v = ((vgg_holder*)ctx->vgg)->w.get();
     const int i = kTapConv[4];
     return nctk_conv3x3_pair(ctx, s, p1, h1, w1, p2, h2, w2, v->wp[i], v->bias[i], nullptr, nullptr, (kCin[i] + 1) & ~1, kCout[i], 1, taps_hwc1[4], taps_hwc2[4]);
@@ -443,8 +435,7 @@ int nctk_vgg19_forward_pair(nct_ctx* ctx, hipStream_t s, const uint8_t* d_bgr1, 
 extern "C" {
 
 int nct_vgg19_features(nct_ctx* ctx, const uint8_t* bgr, int h, int w, int stride, int deepest_tap, float* const* taps_chw, int* dims) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     NCT_REQUIRE(bgr && h > 0 && w > 0 && stride >= 3 * w, "vgg19_features: bad image arguments");
     NCT_REQUIRE(deepest_tap >= 1 && deepest_tap <= 5, "vgg19_features: deepest_tap must be 1..5");
     DevBuf<uint8_t> img(ctx, (size_t)stride * h);
@@ -454,10 +445,10 @@ int nct_vgg19_features(nct_ctx* ctx, const uint8_t* bgr, int h, int w, int strid
     int hh = h, ww = w; size_t sizes[5]; int td[5][3];
     for (int t = 0; t < 5; ++t) { const int C = kCout[kTapConv[t]]; td[t][0] = C; td[t][1] = hh; td[t][2] = ww; sizes[t] = (size_t)C * hh * ww; hh = (hh - 1) / 2 + 1; ww = (ww - 1) / 2 + 1; }
     float* d_taps[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    std::vector<DevBuf<float>*> bufs;
+    DevBuf<float> bufs[5];
     int rc = 0;
     for (int t = 0; t < deepest_tap && rc == 0; ++t)
-        if (taps_chw && taps_chw[t]) { auto* b = new DevBuf<float>(ctx, sizes[t]); bufs.push_back(b); if (!b->ok()) rc = NCT_ERR_HIP; d_taps[t] = *b; }
+        if (taps_chw && taps_chw[t]) { if (!bufs[t].alloc(ctx, sizes[t])) rc = NCT_ERR_HIP; d_taps[t] = bufs[t]; }
     int ldims[15] = {0};
     if (rc == 0) rc = nctk_vgg19_forward(ctx, ctx->stream, img, h, w, stride, deepest_tap, d_taps, ldims);
     if (rc == 0)
@@ -466,7 +457,6 @@ int nct_vgg19_features(nct_ctx* ctx, const uint8_t* bgr, int h, int w, int strid
                              if (e != hipSuccess) { rc = ctx->fail(NCT_ERR_HIP, "D2H of tap %d failed: %s", t + 1, hipGetErrorString(e)); break; } }
     hipError_t e = hipStreamSynchronize(ctx->stream);
     if (rc == 0 && e != hipSuccess) rc = ctx->fail(NCT_ERR_HIP, "vgg19_features: %s", hipGetErrorString(e));
-    for (auto* b : bufs) delete b;
     if (dims) for (int t = 0; t < 5; ++t) for (int k = 0; k < 3; ++k) dims[t * 3 + k] = t < deepest_tap ? td[t][k] : 0;
     return rc;
 }
@@ -474,8 +464,7 @@ int nct_vgg19_features(nct_ctx* ctx, const uint8_t* bgr, int h, int w, int strid
 // single-layer entry points (unit parity tests against Caffe's known answers / the oracle)
 int nct_conv3x3_relu(nct_ctx* ctx, const float* in_chw, int Cin, int H, int W, const float* weights /*[Cout][Cin][3][3]*/, const float* bias,
                      int Cout, float* out_chw, int relu) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     NCT_REQUIRE(in_chw && weights && bias && out_chw, "conv3x3_relu: null pointer");
     NCT_REQUIRE(Cin >= 1 && (Cout & 63) == 0 && H >= 2 && W >= 2, "conv3x3_relu: need Cout %% 64 == 0, H,W >= 2");
     const int cin_pad = (Cin + 1) & ~1;
@@ -486,25 +475,21 @@ int nct_conv3x3_relu(nct_ctx* ctx, const float* in_chw, int Cin, int H, int W, c
     NCT_HIP(hipMemcpyAsync(din, in_chw, sizeof(float) * Cin * hw, hipMemcpyHostToDevice, ctx->stream));
     NCT_HIP(hipMemcpyAsync(dw, weights, sizeof(float) * (size_t)Cout * Cin * 9, hipMemcpyHostToDevice, ctx->stream));
     NCT_HIP(hipMemcpyAsync(db, bias, sizeof(float) * Cout, hipMemcpyHostToDevice, ctx->stream));
-    int rc = nctk_pack_weights(ctx, ctx->stream, dw, dwp, Cout, Cin, cin_pad);
-    if (rc) return rc;
-    rc = nctk_conv3x3(ctx, ctx->stream, din, dwp, db, dout, cin_pad, Cout, H, W, relu, 0);
-    if (rc) return rc;
+    NCT_TRY(nctk_pack_weights(ctx, ctx->stream, dw, dwp, Cout, Cin, cin_pad));
+    NCT_TRY(nctk_conv3x3(ctx, ctx->stream, din, dwp, db, dout, cin_pad, Cout, H, W, relu, 0));
     NCT_HIP(hipMemcpyAsync(out_chw, dout, sizeof(float) * Cout * hw, hipMemcpyDeviceToHost, ctx->stream));
     NCT_HIP(hipStreamSynchronize(ctx->stream));
     return NCT_OK;
 }
 
 int nct_maxpool2x2(nct_ctx* ctx, const float* in_chw, int C, int H, int W, float* out_chw) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_HIP(hipSetDevice(ctx->device));
+    NCT_CTX_ENTER();
     NCT_REQUIRE(in_chw && out_chw && C >= 1 && H >= 2 && W >= 2, "maxpool2x2: bad arguments");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     DevBuf<float> din(ctx, (size_t)C * H * W), dout(ctx, (size_t)C * Ho * Wo);
     if (!din.ok() || !dout.ok()) return NCT_ERR_HIP;
     NCT_HIP(hipMemcpyAsync(din, in_chw, sizeof(float) * C * H * W, hipMemcpyHostToDevice, ctx->stream));
-    int rc = nctk_maxpool2x2(ctx, ctx->stream, din, dout, C, H, W);
-    if (rc) return rc;
+    NCT_TRY(nctk_maxpool2x2(ctx, ctx->stream, din, dout, C, H, W));
     NCT_HIP(hipMemcpyAsync(out_chw, dout, sizeof(float) * C * Ho * Wo, hipMemcpyDeviceToHost, ctx->stream));
     NCT_HIP(hipStreamSynchronize(ctx->stream));
     return NCT_OK;

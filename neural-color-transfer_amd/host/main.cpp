@@ -250,9 +250,8 @@ bool run_with_vis(nct_ctx* ctx, const ImageBGR& cnt, const ImageBGR& stl, const 
 }
 // the level intermediates a line with several references shows under -vis 1: per level the label map as an 8-bit grey image (label * (255 / max(K - 1, 1))), the merged
 // guidance image and the intermediate result, named like run_with_vis's dumps (<pre>_label_<l>.png, <pre>_guide_<l>.png, <pre>_result_<l>.png)
-bool run_multi_with_vis(nct_ctx* ctx, const ImageBGR& cnt, const std::vector<const ImageBGR*>& refs, const nct_params& prm, const std::string& pre, uint8_t* out,
+bool run_multi_with_vis(nct_ctx* ctx, const ImageBGR& cnt, int K, const uint8_t* const* px, const int* rh, const int* rw, const nct_params& prm, const std::string& pre, uint8_t* out,
                         nct_pair_timing* tm, std::string& err) {
-    const int K = (int)refs.size();
     int ah[5], aw[5];
     { int h = cnt.h, w = cnt.w; for (int t = 0; t < 5; ++t) { ah[4 - t] = h; aw[4 - t] = w; h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; } }
     std::vector<std::vector<uint8_t>> label(5), guide(5), result(5);
@@ -261,9 +260,7 @@ bool run_multi_with_vis(nct_ctx* ctx, const ImageBGR& cnt, const std::vector<con
         label[l].resize((size_t)ah[l] * aw[l]); guide[l].resize((size_t)ah[l] * aw[l] * 3); result[l].resize((size_t)cnt.h * cnt.w * 3);
         lv.label[l] = label[l].data(); lv.guide[l] = guide[l].data(); lv.result[l] = result[l].data();
     }
-    std::vector<const uint8_t*> px(K); std::vector<int> rh(K), rw(K);
-    for (int k = 0; k < K; ++k) { px[k] = refs[k]->px.data(); rh[k] = refs[k]->h; rw[k] = refs[k]->w; }
-    if (nct_multi_upload(ctx, cnt.px.data(), cnt.h, cnt.w, K, px.data(), rh.data(), rw.data()) != NCT_OK || nct_multi_run_levels(ctx, &prm, tm, &lv) != NCT_OK ||
+    if (nct_multi_upload(ctx, cnt.px.data(), cnt.h, cnt.w, K, px, rh, rw) != NCT_OK || nct_multi_run_levels(ctx, &prm, tm, &lv) != NCT_OK ||
         nct_pair_download(ctx, out) != NCT_OK) { err = nct_last_error(ctx); return false; }
     const int step = 255 / std::max(K - 1, 1);
     for (int l = 0; l < prm.levels; ++l) {
@@ -315,9 +312,9 @@ bool shrink(nct_ctx* ctx, ImageBGR& img) {
 // With `-io 0` a GPU worker runs all three itself (the round-2 behaviour).
 struct Job {
     size_t index = 0; Pair p; std::string name, log, err;
-    ImageBGR cnt, stl; std::vector<uint8_t> out;
-    std::vector<ImageBGR> more;                                  // the second and further references of a line with several (SPEC §6.2)
-    size_t input_bytes() const { size_t b = cnt.px.size() + stl.px.size(); for (const auto& m : more) b += m.px.size(); return b; }
+    ImageBGR cnt; std::vector<uint8_t> out;
+    std::vector<ImageBGR> refs;                                  // the line's references: one, or several (SPEC §6.2)
+    size_t input_bytes() const { size_t b = cnt.px.size(); for (const auto& r : refs) b += r.px.size(); return b; }
     std::chrono::steady_clock::time_point t0;
     enum { LOADED, SKIPPED, FAILED, DONE } state = LOADED;
     template <typename... A> void say(const char* fmt, A... a) { char line[1200]; snprintf(line, sizeof line, fmt, a...); log += line; }
@@ -367,7 +364,7 @@ void load_pair(const Config& cfg, Job& j) {
     j.say("Content: %s, style: %s, BDS weight: %f.\n", j.p.cnt.c_str(), j.p.stl.c_str(), (double)j.p.bds);
     const std::string why = refusal(cfg, j.p);
     if (!why.empty()) { j.say("Error: %s\n", why.c_str()); j.err = why; j.state = Job::FAILED; return; }
-    const std::string cntStr = cfg.input_dir + "/" + j.p.cnt, stlStr = cfg.input_dir + "/" + j.p.refs[0];
+    const std::string cntStr = cfg.input_dir + "/" + j.p.cnt;
     j.name = output_name(cfg, j.p);
     const char* name = j.name.c_str();
     if (cfg.resume && pngio::looks_complete(j.name)) {           // a truncated file (killed run, full disk) is redone, not skipped
@@ -377,13 +374,11 @@ void load_pair(const Config& cfg, Job& j) {
     std::string err;
     if (!imgio::read(cntStr, j.cnt, err)) { j.say("Error: Fail reading content image: %s\n", cntStr.c_str()); j.err = "cannot read content image: " + err; j.state = Job::FAILED; return; }
     j.say("\n**Read content file: %s, w = %d, h = %d\n", cntStr.c_str(), j.cnt.w, j.cnt.h);
-    if (!imgio::read(stlStr, j.stl, err)) { j.say("Error: Fail reading style image: %s\n", stlStr.c_str()); j.err = "cannot read style image: " + err; j.state = Job::FAILED; return; }
-    j.say("Read style file: %s, w = %d, h = %d\n", stlStr.c_str(), j.stl.w, j.stl.h);
-    j.more.resize(j.p.refs.size() - 1);
-    for (size_t k = 1; k < j.p.refs.size(); ++k) {
+    j.refs.resize(j.p.refs.size());
+    for (size_t k = 0; k < j.refs.size(); ++k) {
         const std::string refStr = cfg.input_dir + "/" + j.p.refs[k];
-        if (!imgio::read(refStr, j.more[k - 1], err)) { j.say("Error: Fail reading style image: %s\n", refStr.c_str()); j.err = "cannot read style image: " + err; j.state = Job::FAILED; return; }
-        j.say("Read style file: %s, w = %d, h = %d\n", refStr.c_str(), j.more[k - 1].w, j.more[k - 1].h);
+        if (!imgio::read(refStr, j.refs[k], err)) { j.say("Error: Fail reading style image: %s\n", refStr.c_str()); j.err = "cannot read style image: " + err; j.state = Job::FAILED; return; }
+        j.say("Read style file: %s, w = %d, h = %d\n", refStr.c_str(), j.refs[k].w, j.refs[k].h);
     }
 }
 
@@ -396,50 +391,42 @@ void log_times(Job& j, const nct_params& prm, const nct_pair_timing& tm) {
     }
     j.say("VGG19 Time: %lf sec.\n", tm.vgg_ms * 1e-3);
     j.say("**Finished Time: %lf sec.\n", tm.total_ms * 1e-3);
-    j.stl.px.clear(); j.stl.px.shrink_to_fit();
-    j.more.clear(); j.more.shrink_to_fit();
+    j.refs.clear(); j.refs.shrink_to_fit();
     j.cnt.px.clear(); j.cnt.px.shrink_to_fit();                 // the store stage needs only cnt.h / cnt.w
 }
 
 void run_pair(nct_ctx* ctx, const Config& cfg, Job& j) {
+    nct_params prm = cfg.prm;
+    prm.bds_weight = j.p.bds;                                   // the per-line weight overrides -bds (main.cu:475)
+    nct_pair_timing tm;                                         // stage times come from stream events: asking for them adds no host synchronisation
     if (cfg.fullres) {                                          // -fullres 1: the library shrinks both images itself and returns the content image at its own size
-        nct_params prm = cfg.prm;
-        prm.bds_weight = j.p.bds;
+        const ImageBGR& stl = j.refs[0];
         j.out.resize((size_t)j.cnt.h * j.cnt.w * 3);
-        nct_pair_timing tm;
-        const int rc = nct_process_pair_fullres(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, j.stl.px.data(), j.stl.h, j.stl.w, MAX_SIZE, &prm, j.out.data(), &tm);
+        const int rc = nct_process_pair_fullres(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, stl.px.data(), stl.h, stl.w, MAX_SIZE, &prm, j.out.data(), &tm);
         if (rc != NCT_OK) { j.say("Error: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
         log_times(j, prm, tm);
         return;
     }
-    bool shrunk = shrink(ctx, j.cnt) && shrink(ctx, j.stl);
-    for (auto& m : j.more) shrunk = shrunk && shrink(ctx, m);
+    bool shrunk = shrink(ctx, j.cnt);
+    for (auto& r : j.refs) shrunk = shrunk && shrink(ctx, r);
     if (!shrunk) { j.say("Error: resize failed: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
-    nct_params prm = cfg.prm;
-    prm.bds_weight = j.p.bds;                                   // the per-line weight overrides -bds (main.cu:475)
     j.out.resize((size_t)j.cnt.h * j.cnt.w * 3);
-    nct_pair_timing tm;                                         // stage times come from stream events: asking for them adds no host synchronisation
-    if (!j.more.empty()) {                                      // several references (SPEC §6.2)
-        std::vector<const ImageBGR*> refs{&j.stl};
-        for (const auto& m : j.more) refs.push_back(&m);
-        if (cfg.vis) {
-            std::string pre(j.name); pre.resize(pre.size() - 4);
-            std::string err;
-            if (!run_multi_with_vis(ctx, j.cnt, refs, prm, pre, j.out.data(), &tm, err)) { j.say("Error: %s\n", err.c_str()); j.err = err; j.state = Job::FAILED; return; }
-        } else {
-            std::vector<const uint8_t*> px; std::vector<int> rh, rw;
-            for (const ImageBGR* r : refs) { px.push_back(r->px.data()); rh.push_back(r->h); rw.push_back(r->w); }
-            const int rc = nct_process_multi(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, (int)refs.size(), px.data(), rh.data(), rw.data(), &prm, j.out.data(), &tm);
-            if (rc != NCT_OK) { j.say("Error: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
-        }
-    } else if (cfg.vis) {
+    // what the library takes of the references; one of them runs as a pair, several as SPEC §6.2's list — under the entry points whose names the error texts carry
+    const int K = (int)j.refs.size();
+    std::vector<const uint8_t*> px(K); std::vector<int> rh(K), rw(K);
+    for (int k = 0; k < K; ++k) { px[k] = j.refs[k].px.data(); rh[k] = j.refs[k].h; rw[k] = j.refs[k].w; }
+    std::string err;
+    bool ok;
+    if (cfg.vis) {
         std::string pre(j.name); pre.resize(pre.size() - 4);    // the output file's stem
-        std::string err;
-        if (!run_with_vis(ctx, j.cnt, j.stl, prm, pre, j.out.data(), &tm, err)) { j.say("Error: %s\n", err.c_str()); j.err = err; j.state = Job::FAILED; return; }
+        ok = K > 1 ? run_multi_with_vis(ctx, j.cnt, K, px.data(), rh.data(), rw.data(), prm, pre, j.out.data(), &tm, err)
+                   : run_with_vis(ctx, j.cnt, j.refs[0], prm, pre, j.out.data(), &tm, err);
     } else {
-        const int rc = nct_process_pair(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, j.stl.px.data(), j.stl.h, j.stl.w, &prm, j.out.data(), &tm);
-        if (rc != NCT_OK) { j.say("Error: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
+        ok = (K > 1 ? nct_process_multi(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, K, px.data(), rh.data(), rw.data(), &prm, j.out.data(), &tm)
+                    : nct_process_pair(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, px[0], rh[0], rw[0], &prm, j.out.data(), &tm)) == NCT_OK;
+        if (!ok) err = nct_last_error(ctx);
     }
+    if (!ok) { j.say("Error: %s\n", err.c_str()); j.err = err; j.state = Job::FAILED; return; }
     log_times(j, prm, tm);
 }
 
@@ -450,8 +437,6 @@ void store_pair(Job& j) {
     j.state = Job::DONE;
 }
 
-// Bounded hand-over between the I/O pool and the GPU workers. `ready` holds decoded pairs (at most `cap`: the decoders stay a little ahead of the GPUs, not a
-// whole batch), `results` finished ones waiting for the PNG encoder (the same bound: a worker blocks rather than pile up results if zlib falls behind).
 // Which pairs.txt lines this process runs. One process (-world 1): all of them, in order. One process per GPU (-world N -rank r; what `-procs N` forks): line i belongs to
 // rank i mod N — or, with -steal 1, to whichever rank draws it: a counter in <output>/.tickets, advanced under an fcntl lock, hands the lines out in order to whoever is
 // free (BASELINE config 5, mixed sizes; north_star's "work-stealing" — a file lock rather than RCCL: the ranks exchange one integer per pair, and a lock file also works
