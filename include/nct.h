@@ -26,9 +26,9 @@ extern "C" {
 #endif
 
 /* bumped whenever a struct of this header changes layout or an entry point changes meaning (round 6: 110 — nct_model_layer; nct_pair_timing grew in round 5 without a
- * bump; 111 — nct_multi_levels and the entry points for several references). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
+ * bump; 111 — nct_multi_levels and the entry points for several references; 112 — frame sequences, nct_seq_*). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
-#define NCT_VERSION 111
+#define NCT_VERSION 112
 
 typedef enum {
     NCT_OK = 0,
@@ -290,6 +290,34 @@ int nct_multi_run(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing);
 int nct_multi_run_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_multi_levels* levels);
 int nct_process_multi(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw, const nct_params* prm,
                       uint8_t* out_bgr, nct_pair_timing* timing);
+
+/* ---- frame sequences (SPEC §6.3; an extension: the reference treats every pair on its own, so the frames of a clip graded to one reference flicker).
+ * A sequence is one reference, one nct_params (copied at begin), a temporal weight tau in [0, 1), a sensitivity sigma > 0 (8-bit Lab units) and frames of one size
+ * sh x sw. Every frame runs nct_pair_run's level loop on (S_t, R) unchanged, with one insertion per level between S1 and U1: S1's coefficients X_t are blended with
+ * the coefficients X'_(t-1) that went into the previous frame's finish, X'_t = X_t + tau_p (X'_(t-1) - X_t), tau_p = tau / (1 + qbar / sigma^2), qbar = the mean squared
+ * difference of the two frames' 8-bit Lab level images over the pixel's 3 x 3 window (integer sum, dy outer / dx inner, taps outside the grid skipped, divided by
+ * 3 * taps); a NaN in X'_(t-1) leaves X_t. X'_t replaces S1's output in U1 / roughness / S2 / A1 and so in the next level's re-predict. Frame 0, the first frame
+ * after nct_seq_reset and every frame with tau == 0 enqueue no blend and equal nct_process_pair(S_t, R) byte for byte.
+ * nct_seq_begin prepares the reference once (upload, pyramid, one VGG19 forward: its five taps stay on the device) and reserves the per-level state (X': 48 B,
+ * L: 3 B per level pixel); all of it lives in the context's arena until nct_seq_end / nct_destroy. While a sequence is open nct_pair_upload, nct_multi_upload,
+ * nct_process_pair_fullres and what is built on them return NCT_ERR_STATE. tau outside [0, 1), a sigma that is not finite and positive or an image outside
+ * nct_pair_upload's limits is NCT_ERR_INVALID; nct_seq_frame without an open sequence NCT_ERR_STATE. A frame that fails leaves the sequence reset.
+ * nct_seq_frame_levels: nct_pair_levels as in nct_pair_run_levels — color[l]->ab_nonlocal is S1's output BEFORE the blend, ab_up / roughness / ab_wls come after
+ * it; nct_seq_levels adds X'_t and the tau_p map per level (a frame without a blend reports X_t and 0.0). The blend's time counts in nct_pair_timing.color_ms.
+ * nct_seq_blend: the blend alone on host maps (synchronous), x / x_prev / x_out [2][h*w][3], lab / lab_prev h*w*3 (8-bit Lab), tau_map (nullable) h*w;
+ * nct_seq_blend_dev: the same on device pointers, enqueued on the context's stream (x_out may be x or x_prev: every thread reads its pixel before it writes it). */
+typedef struct nct_seq_params { double tau, sigma; } nct_seq_params;
+void nct_seq_params_default(nct_seq_params* p);     /* tau 0.7, sigma 10.0 */
+typedef struct nct_seq_levels { double* ab_blend[5]; double* tau_map[5]; } nct_seq_levels;   /* X'_t [2][h*w][3]; tau_p [h*w]; all nullable */
+int nct_seq_begin(nct_ctx* ctx, const uint8_t* ref_bgr, int rh, int rw, int sh, int sw, const nct_params* prm, const nct_seq_params* seq);
+int nct_seq_frame(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing);
+int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels);
+int nct_seq_reset(nct_ctx* ctx);   /* scene cut: the next frame is a first frame; the reference stays prepared */
+int nct_seq_end(nct_ctx* ctx);     /* frees the state; nct_destroy does it too */
+int nct_seq_blend(nct_ctx* ctx, const double* x, const double* x_prev, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, double tau, double sigma,
+                  double* x_out, double* tau_map);
+int nct_seq_blend_dev(nct_ctx* ctx, const double* d_x, const double* d_x_prev, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, double tau, double sigma,
+                      double* d_x_out, double* d_tau_map);
 
 /* ---- device-pointer seams: the same operations on buffers that stay in HBM between calls (main.cu:204-316 keeps Ndata_C1, ann_device, ... on the device
  * across these kernels; an integrator replacing single seams should not pay H2D + D2H + a synchronise per call). Buffers come from the context's arena

@@ -176,7 +176,7 @@ int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w
 int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, const uint8_t* s_lab_level, const uint8_t* g_lab_level,
                               const uint8_t* s_lab_full, const int* knn_id, const double* knn_w, int layer, int h, int w, int H, int W,
                               const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg, const nct_s1_graph* graph,
-                              const nct_finish_target* fin) {
+                              const nct_finish_target* fin, const nct_seq_link* seq) {
     const int n = h * w;
     const int nbl = cdiv(n, 256);
     // ---------------- T1 + T2
@@ -214,6 +214,20 @@ int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, con
     }
     NCT_TRY(ctx->mark(s, nct_stage_tag(NCT_ST_NONLOCAL, ctx->tm_level)));
     if (dbg) NCT_TRY(dbg_copy(ctx, s, dbg->ab_nonlocal, x, (size_t)6 * n));
+    if (seq) {
+        // a frame of a sequence (SPEC §6.3): X'_t = the blend of S1's output with X'_(t-1), in place in the kept state, which the finish reads; L_t replaces L_(t-1)
+        DevBuf<double> tmap;
+        if (seq->tau_map_host && !tmap.alloc(ctx, n)) return NCT_ERR_HIP;
+        if (seq->blend) NCT_TRY(nctk_seq_blend(ctx, s, x, seq->keep_x, s_lab_level, seq->keep_lab, h, w, seq->tau, seq->sigma, seq->keep_x, tmap));
+        else {
+            NCT_HIP(hipMemcpyAsync(seq->keep_x, x, sizeof(double) * (size_t)6 * n, hipMemcpyDeviceToDevice, s));
+            if (tmap.ok()) NCT_HIP(hipMemsetAsync(tmap, 0, sizeof(double) * (size_t)n, s));
+        }
+        NCT_HIP(hipMemcpyAsync(seq->keep_lab, s_lab_level, (size_t)3 * n, hipMemcpyDeviceToDevice, s));
+        NCT_TRY(dbg_copy(ctx, s, seq->ab_blend_host, seq->keep_x, (size_t)6 * n));
+        if (tmap.ok()) NCT_TRY(dbg_copy(ctx, s, seq->tau_map_host, tmap, n));
+        return nctk_color_finish(ctx, s, seq->keep_x, h, w, H, W, s_lab_full, H, W, prm, out_lab_full, dbg);
+    }
     if (fin) return nctk_color_finish(ctx, s, x, h, w, H, W, fin->s_lab, fin->H, fin->W, prm, fin->out_lab, dbg);
     return nctk_color_finish(ctx, s, x, h, w, H, W, s_lab_full, H, W, prm, out_lab_full, dbg);
 }

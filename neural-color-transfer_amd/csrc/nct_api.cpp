@@ -307,6 +307,25 @@ int nct_select_reference(nct_ctx* ctx, const float* const* err, const uint8_t* c
     return NCT_OK;
 }
 
+// SPEC §6.3 rule 3 on host maps: the two coefficient maps and the two Lab level images up, one k_seq_blend launch, X' (and the tau_p map) down
+int nct_seq_blend(nct_ctx* ctx, const double* x, const double* x_prev, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, double tau, double sigma,
+                  double* x_out, double* tau_map) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(x && x_prev && lab && lab_prev && x_out, "seq_blend: null pointer");
+    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_blend: grid %dx%d out of range", w, h);
+    const size_t n = (size_t)h * w;
+    DevBuf<double> dx(ctx, 6 * n), dp(ctx, 6 * n), dt(ctx, n);
+    DevBuf<uint8_t> dl(ctx, 3 * n), dlp(ctx, 3 * n);
+    if (!dx.ok() || !dp.ok() || !dt.ok() || !dl.ok() || !dlp.ok()) return NCT_ERR_HIP;
+    NCT_H2D(dx, x, sizeof(double) * 6 * n); NCT_H2D(dp, x_prev, sizeof(double) * 6 * n);
+    NCT_H2D(dl, lab, 3 * n); NCT_H2D(dlp, lab_prev, 3 * n);
+    NCT_TRY(nctk_seq_blend(ctx, ctx->stream, dx, dp, dl, dlp, h, w, tau, sigma, dp, tau_map ? (double*)dt : nullptr));      // in place into the previous state, as a frame does it
+    NCT_D2H(x_out, dp, sizeof(double) * 6 * n);
+    if (tau_map) NCT_D2H(tau_map, dt, sizeof(double) * n);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
 int nct_bds_vote_image(nct_ctx* ctx, const uint8_t* a_bgr, int ah, int aw, const uint8_t* b_bgr, int bh, int bw,
                        const uint32_t* ann, const uint32_t* bnn, int patch, double w_coherence, double w_complete, uint8_t* out_bgr) {
     NCT_CTX_ENTER();

@@ -126,4 +126,10 @@ int nct_select_reference_dev(nct_ctx* ctx, const float* const* d_err, const uint
     return nctk_select_reference(ctx, ctx->stream, d_err, d_guide_bgr, K, h, w, d_label, d_guide_out, d_err_out);
 }
 
+int nct_seq_blend_dev(nct_ctx* ctx, const double* d_x, const double* d_x_prev, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, double tau, double sigma,
+                      double* d_x_out, double* d_tau_map) {                                                                                          /* SPEC §6.3 */
+    NCT_CTX_ENTER();
+    return nctk_seq_blend(ctx, ctx->stream, d_x, d_x_prev, d_lab, d_lab_prev, h, w, tau, sigma, d_x_out, d_tau_map);
+}
+
 }  // extern "C"

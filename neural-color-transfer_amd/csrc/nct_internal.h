@@ -176,12 +176,16 @@ struct nct_finish_target { const uint8_t* s_lab; int H, W; uint8_t* out_lab; };
 // the largest finish target: S2's hierarchy stays within MG_MAXL levels (k_wls_mg.hip) and each of its arrays below 4 GB (6 fp64 right-hand sides: 3.2 GB)
 #define NCT_FINISH_MAX_SIDE 16384
 #define NCT_FINISH_MAX_PIXELS (1LL << 26)
+// A level of a sequence frame (SPEC §6.3), between S1 and the finish. keep_x ([2][n][3]) / keep_lab ([n][3]): the level's state, X'_(t-1) and L_(t-1) on entry where blend is set,
+// X'_t and L_t on return: with blend one k_seq_blend launch in place into keep_x, which the finish then reads; without (first frame) S1's output is copied there.
+// tau_map_host / ab_blend_host (nullable): host copies for level-wise validation
+struct nct_seq_link { double* keep_x; uint8_t* keep_lab; bool blend; double tau, sigma; double* ab_blend_host; double* tau_map_host; };
 // H x W: the working size (S1's dWeight); fin (nullable) retargets U1 / S2 / A1 — null: they target H x W, s_lab_full, out_lab_full
 int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, const uint8_t* s_lab_level, const uint8_t* g_lab_level,
                               const uint8_t* s_lab_full, const int* knn_id, const double* knn_w, int layer, int h, int w, int H, int W,
                               const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg,
                               const nct_s1_graph* graph = nullptr /* the level's prebuilt graph part of S1; null: built inside, on s */,
-                              const nct_finish_target* fin = nullptr);
+                              const nct_finish_target* fin = nullptr, const nct_seq_link* seq = nullptr /* a frame of a sequence (SPEC §6.3): blend S1's output with the kept state */);
 // U1 + roughness + S2 + A1 of coefficients x ([2][h*w][3], device) onto the grid H x W of s_lab_full; Hw x Ww = the working size (the x4 of S2's lambda)
 int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int Hw, int Ww, const uint8_t* s_lab_full, int H, int W,
                       const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg);
@@ -192,6 +196,9 @@ void nct_set_ctxless_error(const char* msg);   // nct_api.cpp
 // pointers (they go into the kernel's argument block); label, guide_out (then guide may be null too) and err_out are nullable
 int nctk_select_reference(nct_ctx* ctx, hipStream_t s, const float* const* err, const uint8_t* const* guide, int K, int h, int w,
                           uint8_t* label, uint8_t* guide_out, float* err_out);
+// k_temporal.hip — SPEC §6.3 rule 3: x_out = x + tau_p (x_prev - x) per level pixel, tau_p from the 3 x 3 mean squared Lab difference; x_out may alias x or x_prev; tau_map nullable
+int nctk_seq_blend(nct_ctx* ctx, hipStream_t s, const double* x, const double* x_prev, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, double tau, double sigma,
+                   double* x_out, double* tau_map);
 // k_wls_mg.hip
 int nctk_wls_solve_mg(nct_ctx* ctx, hipStream_t s, double* X, const double* rough, const double* wx, const double* wy, int H, int W,
                       double rtol, int* iters_out);

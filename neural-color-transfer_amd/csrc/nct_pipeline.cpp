@@ -11,8 +11,19 @@
 #include <algorithm>
 #include <cmath>
 
+// An open frame sequence (SPEC §6.3): what nct_seq_begin prepares once and every frame borrows — the reference's pyramid and its five un-normalised taps (HWC, by
+// level) — and the state the blend carries from frame to frame, per level X' ([2][h*w][3] doubles) and L (the frame's level image in 8-bit Lab). All of it comes from
+// the context's arena and outlives the runs; the frame and the reference at working size are pair_state's src / ref[0] as for a pair.
+struct seq_state {
+    nct_params prm; double tau = 0, sigma = 0;
+    long frames = 0;                                           // frames since nct_seq_begin / nct_seq_reset: 0 = the next one is a first frame
+    int ah[5], aw[5], bh[5], bw[5];
+    uint8_t* rpyr[4] = {}; float* rfeat[5] = {};
+    double* keep_x[5] = {}; uint8_t* keep_lab[5] = {};
+};
 struct pair_state {
     uint8_t *src = nullptr, *out = nullptr;                    // device BGR images
+    seq_state* seq = nullptr;
     uint8_t* ref[NCT_MAX_REFS] = {};                           // the K references (SPEC §6.2; a pair: K = 1)
     int K = 0;
     int sh = 0, sw = 0, rh[NCT_MAX_REFS] = {}, rw[NCT_MAX_REFS] = {};
@@ -28,10 +39,23 @@ static void drop_images(nct_ctx* ctx, pair_state* P) {
     if (P->out) { ctx->release(P->out); P->out = nullptr; }
     P->K = 0;
 }
+// what an open sequence holds goes back to the arena
+static void seq_free(nct_ctx* ctx, pair_state* P) {
+    seq_state* q = P->seq;
+    if (!q) return;
+    for (int l = 0; l < 5; ++l) {
+        if (l < 4 && q->rpyr[l]) ctx->release(q->rpyr[l]);
+        if (q->rfeat[l]) ctx->release(q->rfeat[l]);
+        if (q->keep_x[l]) ctx->release(q->keep_x[l]);
+        if (q->keep_lab[l]) ctx->release(q->keep_lab[l]);
+    }
+    delete q; P->seq = nullptr;
+}
 // the images live in the context arena like every other device buffer (no hipMalloc/hipFree — device-wide synchronisation points —
 // between the pairs of other contexts in flight on the same GPU)
 void nct_pair_free(nct_ctx* ctx) {
     if (!ctx->pair) return;
+    seq_free(ctx, (pair_state*)ctx->pair);
     drop_images(ctx, (pair_state*)ctx->pair);
     delete (pair_state*)ctx->pair; ctx->pair = nullptr;
 }
@@ -96,6 +120,7 @@ struct ref_bufs {
     DevBuf<float> bnnd, err;
     DevBuf<uint8_t> guide;
     const uint8_t* img[5];
+    const float* featp[5];                          // the taps the correspondence reads: feat[l], or the ones an open sequence prepared (SPEC §6.3)
 };
 
 // What the side stream writes: per level that runs, S's level image in Lab, its kNN graph and the graph-only part of S1's system (reverse adjacency, hub block
@@ -123,6 +148,8 @@ struct pair_run {
     const nct_multi_levels* const lv;              // where the level intermediates go (every pointer nullable): a pair reports as the list of one reference
     const nct_color_stages* const* const color;    // nullable: [5] the colour stage's coefficient maps a pair may ask for
     const fullres_target* const fin;               // nullable: moves the last level's U1 / S2 / A1 onto the original source
+    seq_state* const seq;                          // nullable: this run is a frame of the open sequence (SPEC §6.3) — the reference's pyramid and taps are borrowed, S1's output is blended
+    const nct_seq_levels* const slv;               // nullable: where a frame's X'_t and tau_p maps go
     pair_state* const P; const hipStream_t s;
     const int H, W, K, nlevels; const size_t N;
     const bool feat16, count;
@@ -142,8 +169,9 @@ struct pair_run {
     DevBuf<uint8_t> sel_label;                     // the selection's label map (rule 2); a pair allocates none of this
     const nct_color_params cp;
 
-    pair_run(nct_ctx* c, const nct_params* p, nct_pair_timing* t, const nct_multi_levels* levels, const nct_color_stages* const* col, const fullres_target* f)
-        : ctx(c), prm(p), timing(t), lv(levels ? levels : &kNoLevels), color(col), fin(f), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
+    pair_run(nct_ctx* c, const nct_params* p, nct_pair_timing* t, const nct_multi_levels* levels, const nct_color_stages* const* col, const fullres_target* f,
+             seq_state* q = nullptr, const nct_seq_levels* sl = nullptr)
+        : ctx(c), prm(p), timing(t), lv(levels ? levels : &kNoLevels), color(col), fin(f), seq(q), slv(sl), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
           nlevels(p->levels), N((size_t)H * W), feat16((p->flags & NCT_FLAG_FEAT16) != 0), count(t && (p->flags & NCT_FLAG_COUNT_EVALS)), side(c),
           cp{p->eps, p->nonlocal_weight, p->local_weight, p->wls_lambda_init, p->wls_alpha, (double)p->k_num} {}
 
@@ -175,9 +203,10 @@ struct pair_run {
         for (int k = 0; k < K; ++k) R[k].img[4] = P->ref[k];
         for (int l = 3; l >= 0; --l) {
             if (!spyr[l].alloc(ctx, (size_t)ah[l] * aw[l] * 3)) return NCT_ERR_HIP;
-            for (int k = 0; k < K; ++k) if (!R[k].pyr[l].alloc(ctx, (size_t)R[k].bh[l] * R[k].bw[l] * 3)) return NCT_ERR_HIP;
+            for (int k = 0; k < K && !seq; ++k) if (!R[k].pyr[l].alloc(ctx, (size_t)R[k].bh[l] * R[k].bw[l] * 3)) return NCT_ERR_HIP;
             NCT_TRY(nctk_resize_u8c3(ctx, s, simg[l + 1], ah[l + 1], aw[l + 1], spyr[l], ah[l], aw[l]));
             simg[l] = spyr[l];
+            if (seq) { R[0].img[l] = seq->rpyr[l]; continue; }          // the sequence's reference pyramid was built at nct_seq_begin
             for (int k = 0; k < K; ++k) {
                 NCT_TRY(nctk_resize_u8c3(ctx, s, R[k].img[l + 1], R[k].bh[l + 1], R[k].bw[l + 1], R[k].pyr[l], R[k].bh[l], R[k].bw[l]));
                 R[k].img[l] = R[k].pyr[l];
@@ -190,13 +219,22 @@ struct pair_run {
     // VGG19: R once (all five taps kept, HWC), S to conv5_1 (main.cu:94,102)
     int forwards() {
         if (!sfeat.alloc(ctx, (size_t)64 * N)) return NCT_ERR_HIP;
+        if (seq) {
+            // the reference's taps are the sequence's (one forward at nct_seq_begin): S runs to conv5_1 on its own. Every conv output is its own fmaf chain, so the
+            // bytes are those of the paired launch
+            for (int l = 0; l < 5; ++l) R[0].featp[l] = seq->rfeat[l];
+            float* staps_hwc[5] = {nullptr, nullptr, nullptr, nullptr, sfeat};
+            NCT_TRY(nctk_vgg19_forward(ctx, s, P->src, H, W, W * 3, 5, nullptr, nullptr, staps_hwc));
+            MARK(NCT_ST_VGG, 0);
+            return NCT_OK;
+        }
         for (int k = 0; k < K; ++k) {
             // the five taps of R arrive channel-last straight from their conv layers' epilogues (round 4: no CHW -> HWC transpose pass)
             float* taps_hwc[5];
             for (int t = 0; t < 5; ++t) {
                 const int l = 4 - t;
                 if (!R[k].feat[l].alloc(ctx, (size_t)kTapC[t] * R[k].bh[l] * R[k].bw[l])) return NCT_ERR_HIP;
-                taps_hwc[t] = R[k].feat[l];
+                taps_hwc[t] = R[k].feat[l]; R[k].featp[l] = R[k].feat[l];
             }
             if (k == 0) {
                 // R and S together: conv5_1 of both images is one launch (two grids of 124 workgroups at 700 x 700 would each leave half the chip idle)
@@ -289,7 +327,7 @@ struct pair_run {
         }
         // normalise (main.cu:259-275), PatchMatch both directions (main.cu:283-284); S's normalised features serve every reference
         if (l > 0 && k == 0) NCT_TRY(nctk_normalize(ctx, s, sfeat, na, nullptr, C, na_px, feat16 ? (uint16_t*)na_h : nullptr));
-        NCT_TRY(nctk_normalize(ctx, s, R[k].feat[l], nb, nullptr, C, nb_px, feat16 ? (uint16_t*)nb_h : nullptr));
+        NCT_TRY(nctk_normalize(ctx, s, R[k].featp[l], nb, nullptr, C, nb_px, feat16 ? (uint16_t*)nb_h : nullptr));
         MARK(NCT_ST_OTHER, l);
         const uint32_t seed_ab = prm->seed ^ (0x9E3779B9u * (uint32_t)(2 * l + 1)), seed_ba = prm->seed ^ (0x9E3779B9u * (uint32_t)(2 * l + 2));
         // na, nb are unit vectors: the row-wise rejection is exact (and worth a third of the finest level: 15.7 vs 24.1 ms with NCT_PM_PLAIN). The fp16 tiles pay from C = 128 on (11-37 % per level); the C = 64 level is
@@ -304,7 +342,7 @@ struct pair_run {
         NCT_TRY(d2h(lv->annd[k][l], annd, sizeof(float) * na_px));
         NCT_TRY(d2h(lv->bnnd[k][l], bnnd, sizeof(float) * nb_px));
         // BDS votes: guidance image (main.cu:291) and features + matching error (main.cu:303-318)
-        NCT_TRY(nctk_bds_vote_both(ctx, s, R[k].img[l], R[k].feat[l], ann, bnn, C, ah[l], aw[l], bh[l], bw[l], 1.0, prm->bds_weight, guide_of(k), voted));
+        NCT_TRY(nctk_bds_vote_both(ctx, s, R[k].img[l], R[k].featp[l], ann, bnn, C, ah[l], aw[l], bh[l], bw[l], 1.0, prm->bds_weight, guide_of(k), voted));
         NCT_TRY(nctk_normalize(ctx, s, voted, nvoted, nullptr, C, na_px));
         return nctk_feature_distance(ctx, s, na, nvoted, err_of(k), C, na_px);
     }
@@ -375,7 +413,11 @@ struct pair_run {
             NCT_TRY(nctk_local_color_transfer(ctx, s, err, side.slab[l], g_lab_l, s_lab_full, side.knn_ids[l], side.knn_ws[l], l, ah[l], aw[l], H, W, cp, out_lab, timing ? &dbg : nullptr, &s1graph, &ft));
             NCT_TRY(nctk_lab2bgr(ctx, s, out0_lab, fin->out, N0, cube));
         } else {
-            NCT_TRY(nctk_local_color_transfer(ctx, s, err, side.slab[l], g_lab_l, s_lab_full, side.knn_ids[l], side.knn_ws[l], l, ah[l], aw[l], H, W, cp, out_lab, (timing || cs) ? &dbg : nullptr, &s1graph));
+            // a frame of a sequence: the blend between S1 and the finish (SPEC §6.3 rule 3); the first frame and tau == 0 only keep the state, with no blend launch
+            nct_seq_link link{};
+            if (seq) link = nct_seq_link{seq->keep_x[l], seq->keep_lab[l], seq->frames > 0 && seq->tau > 0.0, seq->tau, seq->sigma, slv ? slv->ab_blend[l] : nullptr, slv ? slv->tau_map[l] : nullptr};
+            NCT_TRY(nctk_local_color_transfer(ctx, s, err, side.slab[l], g_lab_l, s_lab_full, side.knn_ids[l], side.knn_ws[l], l, ah[l], aw[l], H, W, cp, out_lab, (timing || cs) ? &dbg : nullptr, &s1graph,
+                                              nullptr, seq ? &link : nullptr));
             if (cs && cs->wls_iters) for (int q = 0; q < 6; ++q) cs->wls_iters[q] = wls_it[q];
             NCT_TRY(nctk_lab2bgr(ctx, s, out_lab, P->out, N, cube));
         }
@@ -419,8 +461,9 @@ struct pair_run {
 // run the whole L=5->1 loop on the uploaded source and its K references. lv (nullable): host copies of the level intermediates; color (nullable, a pair only): [5] the
 // colour stage's coefficient maps per level; fin (nullable, a pair only): the full-resolution finish
 static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_multi_levels* lv = nullptr, const nct_color_stages* const* color = nullptr,
-                            const fullres_target* fin = nullptr) {
+                            const fullres_target* fin = nullptr, seq_state* seq = nullptr, const nct_seq_levels* slv = nullptr) {
     pair_state* P = (pair_state*)ctx->pair;
+    if (P && P->seq && !seq) return ctx->fail(NCT_ERR_STATE, "process: a sequence is open on this context (nct_seq_frame runs its frames; nct_seq_end closes it)");
     if (!P || !P->src || P->K < 1 || !P->ref[0]) return ctx->fail(NCT_ERR_STATE, "process: no pair uploaded");
     NCT_REQUIRE(!fin || P->K == 1, "process: no full-resolution finish with several references");
     NCT_REQUIRE(prm->patch_size == 3 && prm->k_num == 8, "process: patch_size must be 3 and k_num 8 (Config.h:68-70)");
@@ -433,7 +476,7 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
     ctx->tm_on = timing != nullptr; ctx->tm_tags.clear(); ctx->tm_host.clear();
     ctx->kt_on = timing != nullptr && (prm->flags & NCT_FLAG_TIME_KERNELS) != 0; ctx->kt_ids.clear();
     ctx->wls_split = (prm->flags & NCT_FLAG_LATENCY) ? 1 : 0;
-    pair_run run(ctx, prm, timing, lv, color, fin);
+    pair_run run(ctx, prm, timing, lv, color, fin, seq, slv);
     const int rc = run.run();
     ctx->tm_on = false; ctx->kt_on = false;
     if (rc || !timing) return rc;
@@ -458,6 +501,10 @@ const char* nct_working_size_rule(int h, int w, int max_side, int* work_h, int* 
     return nullptr;
 }
 
+// what replaces the context's images is refused while a sequence holds them (SPEC §6.3)
+#define NCT_NO_OPEN_SEQ(what) do { if (ctx->pair && ((pair_state*)ctx->pair)->seq) \
+    return ctx->fail(NCT_ERR_STATE, what ": a sequence is open on this context (nct_seq_end closes it)"); } while (0)
+
 // the source and its K references (checked by the caller) into the arena
 static int upload_images(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw) {
     pair_state* P = pair_of(ctx);
@@ -477,6 +524,7 @@ extern "C" {
 
 int nct_pair_upload(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw) {
     NCT_CTX_ENTER();
+    NCT_NO_OPEN_SEQ("pair_upload");
     NCT_REQUIRE(src_bgr && ref_bgr, "pair_upload: null image");
     // the coarsest pyramid level (four ceil-halvings) must be at least 2x2 (init_Ann_kernel scales by (bw-1)/(aw-1)): side >= 17
     NCT_REQUIRE(sh >= 17 && sw >= 17 && rh >= 17 && rw >= 17 && sh <= 4000 && sw <= 4000 && rh <= 4000 && rw <= 4000,
@@ -486,6 +534,7 @@ int nct_pair_upload(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const 
 
 int nct_multi_upload(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw) {
     NCT_CTX_ENTER();
+    NCT_NO_OPEN_SEQ("multi_upload");
     NCT_REQUIRE(K >= 1 && K <= NCT_MAX_REFS, "multi_upload: the number of references must be in [1, %d] (got %d)", NCT_MAX_REFS, K);
     NCT_REQUIRE(src_bgr && refs_bgr && rh && rw, "multi_upload: null pointer");
     NCT_REQUIRE(sh >= 17 && sw >= 17 && sh <= 4000 && sw <= 4000, "multi_upload: image sides must be in [17, 4000] (source: %dx%d)", sw, sh);
@@ -552,6 +601,105 @@ int nct_process_pair(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const
     return nct_pair_download(ctx, out_bgr);
 }
 
+// ---- frame sequences (SPEC §6.3)
+void nct_seq_params_default(nct_seq_params* p) {
+    if (!p) return;
+    p->tau = 0.7; p->sigma = 10.0;
+}
+
+int nct_seq_end(nct_ctx* ctx) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return NCT_OK;
+    NCT_SYNC();
+    seq_free(ctx, P);
+    drop_images(ctx, P);
+    return NCT_OK;
+}
+
+int nct_seq_reset(nct_ctx* ctx) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_reset: no sequence is open (nct_seq_begin first)");
+    P->seq->frames = 0;
+    return NCT_OK;
+}
+
+// the reference once: upload, pyramid (main.cu:104-108), one VGG19 forward with all five taps kept channel-last; and the per-level state
+static int seq_prepare(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* ref_bgr, int rh, int rw, int sh, int sw) {
+    hipStream_t s = ctx->stream;
+    { int h = sh, w = sw, h2 = rh, w2 = rw;
+      for (int t = 0; t < 5; ++t) { q->ah[4 - t] = h; q->aw[4 - t] = w; q->bh[4 - t] = h2; q->bw[4 - t] = w2; h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; h2 = (h2 - 1) / 2 + 1; w2 = (w2 - 1) / 2 + 1; } }
+    P->src = (uint8_t*)ctx->alloc((size_t)sh * sw * 3);
+    P->ref[0] = (uint8_t*)ctx->alloc((size_t)rh * rw * 3);
+    if (!P->src || !P->ref[0]) return NCT_ERR_HIP;
+    P->sh = sh; P->sw = sw; P->K = 1; P->rh[0] = rh; P->rw[0] = rw;
+    for (int l = 0; l < 5; ++l) {
+        const size_t n = (size_t)q->ah[l] * q->aw[l], nr = (size_t)q->bh[l] * q->bw[l];
+        if (l < 4 && !(q->rpyr[l] = (uint8_t*)ctx->alloc(nr * 3))) return NCT_ERR_HIP;
+        if (!(q->rfeat[l] = (float*)ctx->alloc(sizeof(float) * kTapC[4 - l] * nr))) return NCT_ERR_HIP;
+        if (l < q->prm.levels) {
+            if (!(q->keep_x[l] = (double*)ctx->alloc(sizeof(double) * 6 * n)) || !(q->keep_lab[l] = (uint8_t*)ctx->alloc(n * 3))) return NCT_ERR_HIP;
+        }
+    }
+    NCT_H2D(P->ref[0], ref_bgr, (size_t)rh * rw * 3);
+    const uint8_t* img = P->ref[0];
+    for (int l = 3; l >= 0; --l) {
+        NCT_TRY(nctk_resize_u8c3(ctx, s, img, q->bh[l + 1], q->bw[l + 1], q->rpyr[l], q->bh[l], q->bw[l]));
+        img = q->rpyr[l];
+    }
+    float* taps_hwc[5];
+    for (int t = 0; t < 5; ++t) taps_hwc[t] = q->rfeat[4 - t];
+    NCT_TRY(nctk_vgg19_forward(ctx, s, P->ref[0], rh, rw, rw * 3, 5, nullptr, nullptr, taps_hwc));
+    NCT_SYNC();
+    return NCT_OK;
+}
+
+int nct_seq_begin(nct_ctx* ctx, const uint8_t* ref_bgr, int rh, int rw, int sh, int sw, const nct_params* prm, const nct_seq_params* sp) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(ref_bgr && prm && sp, "seq_begin: null pointer");
+    NCT_REQUIRE(sh >= 17 && sw >= 17 && rh >= 17 && rw >= 17 && sh <= 4000 && sw <= 4000 && rh <= 4000 && rw <= 4000,
+                "seq_begin: image sides must be in [17, 4000] (got frames of %dx%d and a reference of %dx%d)", sw, sh, rw, rh);
+    NCT_REQUIRE(sp->tau >= 0.0 && sp->tau < 1.0, "seq_begin: tau must be in [0, 1) (got %g)", sp->tau);
+    NCT_REQUIRE(sp->sigma > 0.0 && sp->sigma <= 1.7976931348623157e308, "seq_begin: sigma must be finite and positive (got %g)", sp->sigma);
+    NCT_REQUIRE(prm->levels >= 1 && prm->levels <= 5, "seq_begin: levels must be in [1, 5] (got %d)", prm->levels);
+    NCT_TRY(nct_seq_end(ctx));                                   // a sequence that is still open is closed first
+    pair_state* P = pair_of(ctx);
+    drop_images(ctx, P);
+    seq_state* q = new seq_state();
+    q->prm = *prm; q->tau = sp->tau; q->sigma = sp->sigma;
+    P->seq = q;
+    const int rc = seq_prepare(ctx, P, q, ref_bgr, rh, rw, sh, sw);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); seq_free(ctx, P); drop_images(ctx, P); }
+    return rc;
+}
+
+int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_frame: no sequence is open (nct_seq_begin first)");
+    NCT_REQUIRE(src_bgr && out_bgr, "seq_frame: null image");
+    seq_state* q = P->seq;
+    NCT_H2D(P->src, src_bgr, (size_t)P->sh * P->sw * 3);
+    nct_multi_levels m; memset(&m, 0, sizeof m);
+    if (levels) {
+        for (int l = 0; l < 5; ++l) {
+            m.ann[0][l] = levels->ann[l]; m.bnn[0][l] = levels->bnn[l]; m.annd[0][l] = levels->annd[l]; m.bnnd[0][l] = levels->bnnd[l];
+            m.guide[l] = levels->guide[l]; m.err[l] = levels->err[l]; m.result[l] = levels->result[l];
+        }
+        m.labels = levels->labels;
+    }
+    const int rc = process_resident(ctx, &q->prm, timing, levels ? &m : nullptr, levels ? levels->color : nullptr, nullptr, q, seq_levels);
+    // a frame that failed may have replaced the state of some levels only: the next frame starts over
+    if (rc) { q->frames = 0; return rc; }
+    q->frames += 1;
+    return nct_pair_download(ctx, out_bgr);
+}
+
+int nct_seq_frame(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing) {
+    return nct_seq_frame_levels(ctx, src_bgr, out_bgr, timing, nullptr, nullptr);
+}
+
 int nct_working_size(int h, int w, int max_side, int* work_h, int* work_w) {
     const char* why = nct_working_size_rule(h, w, max_side, work_h, work_w);
     if (why) { nct_set_ctxless_error(why); return NCT_ERR_INVALID; }
@@ -561,6 +709,7 @@ int nct_working_size(int h, int w, int max_side, int* work_h, int* work_w) {
 int nct_process_pair_fullres(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw, int max_side,
                              const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
     NCT_CTX_ENTER();
+    NCT_NO_OPEN_SEQ("process_pair_fullres");
     NCT_REQUIRE(src_bgr && ref_bgr && prm && out_bgr, "process_pair_fullres: null pointer");
     int wh = 0, ww = 0, rwh = 0, rww = 0;
     const char* why = nct_working_size_rule(sh, sw, max_side, &wh, &ww);

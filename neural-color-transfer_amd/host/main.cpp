@@ -7,7 +7,8 @@
 // touch zlib), `-pin` (threads on the GPU's NUMA node), weights parsed once per process and held once per GPU, `-seed`, `-levels L` (BASELINE
 // config 1: "L=5 only" = -levels 1), `-resume 1` (skip pairs whose output exists; <out>/status.jsonl gets one JSON line per pair)
 // and `-feat16 1` (reduced-precision PatchMatch features; not bit-identical), `-fullres 1` (the result at the content image's own size, SPEC §6.1),
-// and pairs.txt lines whose second token lists several references separated by commas (SPEC §6.2: every pixel takes its colours from the reference that matches it best).
+// and pairs.txt lines whose second token lists several references separated by commas (SPEC §6.2: every pixel takes its colours from the reference that matches it best),
+// `-seq 1` (+ `-tau`, `-sigma`): consecutive lines with one and the same reference are the frames of a sequence, graded with temporally blended coefficients (SPEC §6.3).
 #include <sys/stat.h>
 #include <sys/wait.h>
 #include <fcntl.h>
@@ -110,7 +111,7 @@ std::string stem(const std::string& path) {          // main.cu:524-531 (find_la
 struct Pair { std::string cnt, stl; float bds; std::vector<std::string> refs; std::string err; };
 std::mutex g_print;
 
-struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false, fullres = false; int rank = 0, world = 1; };
+struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false, fullres = false, seq = false; nct_seq_params sp; int rank = 0, world = 1; };
 
 // ---- ENABLE_VIS debug outputs (Config.h:8) behind the runtime flag -vis 1: per pyramid level the flow maps of both NNFs (reconstruct_flow,
 // GeneralizedPatchMatch.cu:337-353), the level images tCnt / tStl (main.cu:343-347), the matching-error heat map (getHeat,
@@ -358,7 +359,8 @@ std::string output_name(const Config& cfg, const Pair& p) {
     return name;
 }
 
-void load_pair(const Config& cfg, Job& j) {
+// in_seq: the line is a frame of a sequence (-seq 1) — its resume check and its reference belong to the sequence, not to the line
+void load_pair(const Config& cfg, Job& j, bool in_seq = false) {
     j.t0 = std::chrono::steady_clock::now();
     j.log += "-----------------***********************----------------------\n";
     j.say("Content: %s, style: %s, BDS weight: %f.\n", j.p.cnt.c_str(), j.p.stl.c_str(), (double)j.p.bds);
@@ -367,13 +369,14 @@ void load_pair(const Config& cfg, Job& j) {
     const std::string cntStr = cfg.input_dir + "/" + j.p.cnt;
     j.name = output_name(cfg, j.p);
     const char* name = j.name.c_str();
-    if (cfg.resume && pngio::looks_complete(j.name)) {           // a truncated file (killed run, full disk) is redone, not skipped
+    if (!in_seq && cfg.resume && pngio::looks_complete(j.name)) {           // a truncated file (killed run, full disk) is redone, not skipped
         j.say("Skipping (-resume): %s exists.\n\n", name);
         j.state = Job::SKIPPED; return;
     }
     std::string err;
     if (!imgio::read(cntStr, j.cnt, err)) { j.say("Error: Fail reading content image: %s\n", cntStr.c_str()); j.err = "cannot read content image: " + err; j.state = Job::FAILED; return; }
     j.say("\n**Read content file: %s, w = %d, h = %d\n", cntStr.c_str(), j.cnt.w, j.cnt.h);
+    if (in_seq) return;
     j.refs.resize(j.p.refs.size());
     for (size_t k = 0; k < j.refs.size(); ++k) {
         const std::string refStr = cfg.input_dir + "/" + j.p.refs[k];
@@ -435,6 +438,74 @@ void store_pair(Job& j) {
     if (!pngio::write(j.name, j.out.data(), j.cnt.h, j.cnt.w, err)) { j.say("Error: cannot write %s: %s\n", j.name.c_str(), err.c_str()); j.err = "cannot write output: " + err; j.state = Job::FAILED; return; }
     j.say("Final output file: %s.\n\n", j.name.c_str());
     j.state = Job::DONE;
+}
+
+// ---- -seq 1 (SPEC §6.3). A group is what one worker context takes in one piece: a sequence — a maximal run of consecutive lines with a single reference, the same
+// reference token and the same bds weight — or a single line of any other kind (several references, a refused line), which runs as without -seq and ends a run.
+struct Group { size_t first = 0, count = 0; long seq = -1; };   // lines [first, first + count); seq: the sequence's number in file order, -1 = not a sequence
+std::vector<Group> plan_groups(const std::vector<Pair>& pairs) {
+    std::vector<Group> g;
+    long nseq = 0;
+    for (size_t i = 0; i < pairs.size(); ++i) {
+        const Pair& p = pairs[i];
+        const bool frame = p.err.empty() && p.refs.size() == 1;
+        if (frame && !g.empty() && g.back().seq >= 0 && pairs[g.back().first].stl == p.stl && pairs[g.back().first].bds == p.bds) { ++g.back().count; continue; }
+        g.push_back({i, 1, frame ? nseq++ : -1});
+    }
+    return g;
+}
+
+// one sequence on one context, its frames in file order. The reference is decoded and shrunk once; a frame whose (shrunk) size differs from the open sequence's begins
+// a new one at that frame; a line that cannot be decoded is skipped and the state continues from the last good frame; with -resume 1 the sequence is skipped only if
+// every output is complete, else it is redone from its first frame. Returns the number of lines it finished
+size_t run_sequence(nct_ctx* ctx, const Config& cfg, const std::vector<Pair>& pairs, const Group& g) {
+    nct_params prm = cfg.prm;
+    prm.bds_weight = pairs[g.first].bds;
+    if (cfg.resume) {
+        bool all = true;
+        for (size_t i = g.first; i < g.first + g.count && all; ++i) all = pngio::looks_complete(output_name(cfg, pairs[i]));
+        if (all) {
+            for (size_t i = g.first; i < g.first + g.count; ++i) {
+                Job j; j.index = i; j.p = pairs[i]; j.t0 = std::chrono::steady_clock::now(); j.name = output_name(cfg, j.p);
+                j.say("Skipping (-resume): %s exists.\n\n", j.name.c_str());
+                j.state = Job::SKIPPED; finish(cfg, j);
+            }
+            return g.count;
+        }
+    }
+    ImageBGR ref; std::string ref_err; bool ref_tried = false, open = false;
+    int fh = 0, fw = 0;
+    for (size_t i = g.first; i < g.first + g.count; ++i) {
+        Job j; j.index = i; j.p = pairs[i];
+        load_pair(cfg, j, true);
+        if (j.state == Job::LOADED && !ref_tried) {
+            ref_tried = true;
+            const std::string refStr = cfg.input_dir + "/" + j.p.refs[0];
+            if (!imgio::read(refStr, ref, ref_err)) { ref.px.clear(); j.say("Error: Fail reading style image: %s\n", refStr.c_str()); }
+            else {
+                j.say("Read style file: %s, w = %d, h = %d\n", refStr.c_str(), ref.w, ref.h);
+                if (!shrink(ctx, ref)) { ref_err = nct_last_error(ctx); ref.px.clear(); }
+            }
+        }
+        if (j.state == Job::LOADED && ref.px.empty()) { j.err = "cannot read style image: " + ref_err; j.state = Job::FAILED; }
+        if (j.state == Job::LOADED && !shrink(ctx, j.cnt)) { j.say("Error: resize failed: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; }
+        if (j.state == Job::LOADED) {
+            int rc = NCT_OK;
+            if (!open || j.cnt.h != fh || j.cnt.w != fw) {
+                rc = nct_seq_begin(ctx, ref.px.data(), ref.h, ref.w, j.cnt.h, j.cnt.w, &prm, &cfg.sp);
+                open = rc == NCT_OK; fh = j.cnt.h; fw = j.cnt.w;
+                if (open) j.say("Sequence %ld: begins at this frame (%d x %d, tau = %g, sigma = %g).\n", g.seq, fw, fh, cfg.sp.tau, cfg.sp.sigma);
+            }
+            nct_pair_timing tm;
+            j.out.resize((size_t)j.cnt.h * j.cnt.w * 3);
+            if (rc == NCT_OK) rc = nct_seq_frame(ctx, j.cnt.px.data(), j.out.data(), &tm);
+            if (rc != NCT_OK) { j.say("Error: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; }
+            else { log_times(j, prm, tm); store_pair(j); }
+        }
+        finish(cfg, j);
+    }
+    if (open) nct_seq_end(ctx);
+    return g.count;
 }
 
 // Which pairs.txt lines this process runs. One process (-world 1): all of them, in order. One process per GPU (-world N -rank r; what `-procs N` forks): line i belongs to
@@ -561,7 +632,8 @@ int main(int argc, char** argv) {
     CmdLine cl;
     Config cfg;
     nct_params_default(&cfg.prm);
-    int gpu = 0, ngpus = 1, seed = 1, inflight = 1, levels = 5, resume = 0, feat16 = 0, vis = 0, fullres = 0, io = -1, pin = 1, world = 1, rank = 0, steal = 0, procs = 0, rccl = 0;
+    nct_seq_params_default(&cfg.sp);
+    int gpu = 0, ngpus = 1, seed = 1, inflight = 1, levels = 5, resume = 0, feat16 = 0, vis = 0, fullres = 0, seq = 0, io = -1, pin = 1, world = 1, rank = 0, steal = 0, procs = 0, rccl = 0;
     cl.add("m", cfg.model_dir, "Directory of network models.");
     cl.add("i", cfg.input_dir, "Input directory of content and style images and pairs.txt.");
     cl.add("o", cfg.output_dir, "Output directory of result images.");
@@ -588,6 +660,9 @@ int main(int argc, char** argv) {
     cl.add("rccl", rccl, "[extension] 1 = the ranks of -procs / -world form an RCCL communicator (one rank per GPU, over xGMI on a node): a start barrier, and the job's time = MAX over ranks and its pair count = SUM over ranks by all-reduce, printed by rank 0. Nothing of a pair's data crosses GPUs; without RCCL (or with 0, the default) the ranks simply run.");
     cl.add("steal", steal, "[extension] 1 = with -world > 1, lines are drawn from a shared counter (<output>/.tickets under a file lock) by whichever rank is free, instead of i mod world: mixed-size batches.");
     cl.add("feat16", feat16, "[extension] 1 = fp16 PatchMatch feature tiles (fp32 accumulate); not bit-identical to the default (about 45 dB against it).");
+    cl.add("seq", seq, "[extension] 1 = consecutive pairs.txt lines with one and the same reference and weight are the frames of a sequence (SPEC 6.3): one worker runs them in file order and blends each frame's colour coefficients with the previous frame's; every worker does its own file I/O (-io is not used); not with -fullres 1 or -vis 1.");
+    cl.add("tau", cfg.sp.tau, "[extension] -seq 1: temporal weight in [0, 1); 0 = every frame on its own.");
+    cl.add("sigma", cfg.sp.sigma, "[extension] -seq 1: sensitivity of the blend to changes between frames, in 8-bit Lab units (> 0).");
     // parser self-test hook (no GPU): `--parse-only <args…>` parses the rest like a normal run and prints what main would go on with, in the format of
     // oracle/ref_cmdline.cpp (the reference's own parser): tests/test_cli.py compares the two on the vectors of tests/golden/cmdline_ref.json
     // job-planning hook (no GPU): `--plan-only <args…>` goes as far as a normal run goes before it creates a context and prints, per pairs.txt line, what it would run
@@ -605,6 +680,10 @@ int main(int argc, char** argv) {
     if (!parsed) return -1;
     if (world < 1 || rank < 0 || rank >= world) { printf("Error: -rank %d is not in [0, -world %d).\n", rank, world); return -1; }
     if (fullres && vis) { printf("Error: -fullres 1 cannot be combined with -vis 1 (the -vis dumps are working-size images).\n"); return -1; }
+    if (seq && fullres) { printf("Error: -seq 1 cannot be combined with -fullres 1 (a sequence runs at the working size only).\n"); return -1; }
+    if (seq && vis) { printf("Error: -seq 1 cannot be combined with -vis 1 (the -vis dumps describe single pairs).\n"); return -1; }
+    if (seq && !(cfg.sp.tau >= 0.0 && cfg.sp.tau < 1.0)) { printf("Error: -tau %g is not in [0, 1).\n", cfg.sp.tau); return -1; }
+    if (seq && !(cfg.sp.sigma > 0.0 && cfg.sp.sigma <= 1.7976931348623157e308)) { printf("Error: -sigma %g is not finite and positive.\n", cfg.sp.sigma); return -1; }
     if (!plan_only) mkdir(cfg.output_dir.c_str(), 0777);                    // main.cu:458
     uint64_t run_token = getenv("NCT_RUN_TOKEN") ? strtoull(getenv("NCT_RUN_TOKEN"), nullptr, 0) : 0;      // hand-started ranks of one run share it (and remove <output>/.rccl_id between runs)
     const std::string tickets_path = cfg.output_dir + "/.tickets";
@@ -639,6 +718,7 @@ int main(int argc, char** argv) {
     cfg.resume = resume != 0;
     cfg.vis = vis != 0;
     cfg.fullres = fullres != 0;
+    cfg.seq = seq != 0;
     if (ngpus < 1) ngpus = 1;
     if (inflight < 1) inflight = 1;
     if (inflight > 8) inflight = 8;
@@ -654,13 +734,18 @@ int main(int argc, char** argv) {
     char a[260], b[260]; float w = 0.f;
     while (fscanf(fp, "%259s %259s %f\n", a, b, &w) == 3) { pairs.push_back({a, b, w, {}, ""}); split_refs(pairs.back()); }
     fclose(fp);
+    const std::vector<Group> groups = cfg.seq ? plan_groups(pairs) : std::vector<Group>();
     if (plan_only) {
-        for (const Pair& p : pairs) {
+        std::vector<std::string> seq_of(pairs.size());               // -seq 1: " seq=<sequence>:<index>" behind the lines that are frames
+        for (const Group& g : groups)
+            if (g.seq >= 0) for (size_t i = 0; i < g.count; ++i) seq_of[g.first + i] = " seq=" + std::to_string(g.seq) + ":" + std::to_string(i);
+        for (size_t i = 0; i < pairs.size(); ++i) {
+            const Pair& p = pairs[i];
             const std::string why = refusal(cfg, p);
             if (!why.empty()) { printf("@@JOB error=%s\n", why.c_str()); continue; }
             std::string refs;
             for (size_t k = 0; k < p.refs.size(); ++k) refs += (k ? "|" : "") + p.refs[k];
-            printf("@@JOB src=%s refs=%s bds=%.6g out=%s\n", p.cnt.c_str(), refs.c_str(), (double)p.bds, output_name(cfg, p).c_str());
+            printf("@@JOB src=%s refs=%s bds=%.6g out=%s%s\n", p.cnt.c_str(), refs.c_str(), (double)p.bds, output_name(cfg, p).c_str(), seq_of[i].c_str());
         }
         return 0;
     }
@@ -721,7 +806,7 @@ int main(int argc, char** argv) {
     // which worker runs a pair has no influence on its result
     std::vector<std::thread> threads;
     Pipeline P; P.cap = (size_t)std::max(2, 2 * nworkers);
-    P.tickets.total = pairs.size(); P.tickets.rank = rank; P.tickets.world = world;
+    P.tickets.total = cfg.seq ? groups.size() : pairs.size(); P.tickets.rank = rank; P.tickets.world = world;
     if (world > 1 && steal) {
         P.tickets.fd = open(tickets_path.c_str(), O_RDWR | O_CREAT, 0644);     // 8 bytes: the next line to hand out (absent or short = 0). A hand-started set of ranks removes it between runs.
         if (P.tickets.fd < 0) { printf("Error: cannot open %s for -steal.\n", tickets_path.c_str()); return -1; }
@@ -729,7 +814,30 @@ int main(int argc, char** argv) {
     if (const char* e = getenv("NCT_IO_READY_MB")) P.byte_cap = (size_t)std::max(0L, atol(e)) << 20;      // test hook: decoded backlog allowed in front of the GPU workers (default 1 GiB)
     std::mutex next_m;
     size_t mine = 0;
-    if (io > 0) {
+    if (cfg.seq) {
+        // -seq 1: the ticket is a group (a whole sequence, or one line of another kind), for -gpus, -inflight, -world, -steal and -procs alike; the worker that draws it
+        // decodes, runs and encodes its lines in file order
+        io = 0;
+        for (int j = 0; j < nworkers; ++j)
+            threads.emplace_back([&, j] {
+                if (pin) affinity::pin_current_thread(loc[j % ngpus].cpus);
+                for (;;) {
+                    long t; { std::lock_guard<std::mutex> lk(next_m); t = P.tickets.draw(); }
+                    if (t < 0) break;
+                    const Group& g = groups[(size_t)t];
+                    size_t n = 1;
+                    if (g.seq >= 0) n = run_sequence(ctxs[j], cfg, pairs, g);
+                    else {
+                        Job job; job.index = g.first; job.p = pairs[g.first];
+                        load_pair(cfg, job);
+                        if (job.state == Job::LOADED) run_pair(ctxs[j], cfg, job);
+                        if (job.state == Job::LOADED) store_pair(job);
+                        finish(cfg, job);
+                    }
+                    std::lock_guard<std::mutex> lk(next_m); mine += n;
+                }
+            });
+    } else if (io > 0) {
         for (int t = 0; t < io; ++t) threads.emplace_back([&, t] { if (pin) affinity::pin_current_thread(loc[t % ngpus].cpus); io_thread(P, cfg, pairs); });
         for (int j = 0; j < nworkers; ++j) threads.emplace_back([&, j] { if (pin) affinity::pin_current_thread(loc[j % ngpus].cpus); gpu_worker(P, ctxs[j], cfg); });
     } else {

@@ -38,7 +38,7 @@ def lib():
     return _lib
 
 
-NCT_VERSION = 111        # include/nct.h
+NCT_VERSION = 112        # include/nct.h
 MAX_REFS = 8             # NCT_MAX_REFS
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -100,6 +100,14 @@ SIGNATURES = {
     "nct_multi_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_multi_run_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_process_multi": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, _u8p, C.c_void_p]),
+    "nct_seq_params_default": (None, [C.c_void_p]),
+    "nct_seq_begin": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nct_seq_frame": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p]),
+    "nct_seq_frame_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_reset": (C.c_int, [C.c_void_p]),
+    "nct_seq_end": (C.c_int, [C.c_void_p]),
+    "nct_seq_blend": (C.c_int, [C.c_void_p, _f64p, _f64p, _u8p, _u8p, C.c_int, C.c_int, C.c_double, C.c_double, _f64p, C.c_void_p]),
+    "nct_seq_blend_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "nct_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "nct_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nct_dev_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -226,6 +234,22 @@ class MultiLevels(C.Structure):
     """struct nct_multi_levels (include/nct.h)."""
     _fields_ = [(k, (C.c_void_p * 5) * MAX_REFS) for k in ("ann", "bnn", "annd", "bnnd", "ref_guide", "ref_err")] + \
                [(k, C.c_void_p * 5) for k in ("label", "guide", "err", "result")] + [("labels", C.c_void_p)]
+
+
+class SeqParams(C.Structure):
+    """struct nct_seq_params (include/nct.h)."""
+    _fields_ = [("tau", C.c_double), ("sigma", C.c_double)]
+
+    @staticmethod
+    def default():
+        p = SeqParams()
+        lib().nct_seq_params_default(C.byref(p))
+        return p
+
+
+class SeqLevels(C.Structure):
+    """struct nct_seq_levels (include/nct.h)."""
+    _fields_ = [("ab_blend", C.c_void_p * 5), ("tau_map", C.c_void_p * 5)]
 
 
 class ColorStages(C.Structure):
@@ -639,6 +663,109 @@ class Context:
         keep["labels"] = labels
         keep["timing"] = tm.as_dict()
         return keep
+
+    # ---- frame sequences (SPEC §6.3)
+    def seq_begin(self, ref_bgr, src_shape, params=None, tau=None, sigma=None):
+        """nct_seq_begin: prepare the reference once for frames of src_shape[:2]; tau / sigma default to nct_seq_params_default (0.7, 10.0)"""
+        r = np.ascontiguousarray(ref_bgr, np.uint8)
+        prm = params or Params.default()
+        sp = SeqParams.default()
+        if tau is not None:
+            sp.tau = tau
+        if sigma is not None:
+            sp.sigma = sigma
+        self._chk(self._l.nct_seq_begin(self._h, r.reshape(-1, 3), r.shape[0], r.shape[1], int(src_shape[0]), int(src_shape[1]), C.addressof(prm), C.addressof(sp)))
+        self._seq_shapes = (tuple(src_shape[:2]), r.shape[:2], prm.levels)
+
+    def seq_frame(self, src_bgr, want_timing=False):
+        s = np.ascontiguousarray(src_bgr, np.uint8)
+        shp = getattr(self, "_seq_shapes", None)
+        if shp is not None and tuple(s.shape[:2]) != shp[0]:
+            raise NctError(-2, "seq_frame: the frame is %dx%d, the sequence was begun for %dx%d" % (s.shape[1], s.shape[0], shp[0][1], shp[0][0]))
+        out = np.empty_like(s)
+        tm = PairTiming() if want_timing else None
+        self._chk(self._l.nct_seq_frame(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
+        return (out, tm.as_dict()) if want_timing else out
+
+    def seq_frame_levels(self, src_bgr, want_color=True):
+        """nct_seq_frame_levels -> (result, dict): pair_run_levels' per-level lists ("ann" … "result", with want_color "color" and "labels"), plus "ab_blend" and "tau_map"
+        per level that ran (X'_t [2, h*w, 3] and tau_p [h, w]; a frame without a blend reports X_t and zeros) and "timing"."""
+        s = np.ascontiguousarray(src_bgr, np.uint8)
+        (H, W), (RH, RW), levels = self._seq_shapes
+        if tuple(s.shape[:2]) != (H, W):
+            raise NctError(-2, "seq_frame_levels: the frame is %dx%d, the sequence was begun for %dx%d" % (s.shape[1], s.shape[0], W, H))
+        dims = []
+        h, w, h2, w2 = H, W, RH, RW
+        for _ in range(5):
+            dims.insert(0, (h, w, h2, w2))
+            h, w, h2, w2 = (h - 1) // 2 + 1, (w - 1) // 2 + 1, (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
+        keep = {"ann": [], "bnn": [], "annd": [], "bnnd": [], "guide": [], "err": [], "result": []}
+        for (ah, aw, bh, bw) in dims:
+            keep["ann"].append(np.zeros((ah, aw), np.uint32)); keep["bnn"].append(np.zeros((bh, bw), np.uint32))
+            keep["annd"].append(np.zeros((ah, aw), np.float32)); keep["bnnd"].append(np.zeros((bh, bw), np.float32))
+            keep["guide"].append(np.zeros((ah, aw, 3), np.uint8)); keep["err"].append(np.zeros((ah, aw), np.float32))
+            keep["result"].append(np.zeros((H, W, 3), np.uint8))
+        lv = PairLevels()
+        for k in keep:
+            setattr(lv, k, (C.c_void_p * 5)(*[a.ctypes.data for a in keep[k]]))
+        if want_color:
+            color, structs = [], []
+            for (ah, aw, _, _) in dims:
+                d = {"ab_local": np.empty((2, ah * aw, 3)), "ab_nonlocal": np.empty((2, ah * aw, 3)), "ab_up": np.empty((2, H * W, 3)),
+                     "roughness": np.empty(H * W), "ab_wls": np.empty((2, H * W, 3)), "cg_iters": np.zeros(3, np.int32), "wls_iters": np.zeros(6, np.int32)}
+                color.append(d)
+                structs.append(ColorStages(*[d[k].ctypes.data for k in ("ab_local", "ab_nonlocal", "ab_up", "roughness", "ab_wls", "cg_iters", "wls_iters")]))
+            lv.color = (C.c_void_p * 5)(*[C.addressof(st) if i < levels else None for i, st in enumerate(structs)])
+            labels = np.zeros(dims[0][:2], np.int32)
+            lv.labels = labels.ctypes.data
+        ab_blend = [np.zeros((2, ah * aw, 3)) for (ah, aw, _, _) in dims[:levels]]
+        tau_map = [np.zeros((ah, aw)) for (ah, aw, _, _) in dims[:levels]]
+        sl = SeqLevels()
+        for l in range(levels):
+            sl.ab_blend[l] = ab_blend[l].ctypes.data; sl.tau_map[l] = tau_map[l].ctypes.data
+        out = np.empty_like(s)
+        tm = PairTiming()
+        self._chk(self._l.nct_seq_frame_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv), C.addressof(sl)))
+        if want_color:
+            keep["color"] = color; keep["labels"] = labels
+        keep["ab_blend"] = ab_blend; keep["tau_map"] = tau_map
+        keep["timing"] = tm.as_dict(); keep["dims"] = dims
+        return out, keep
+
+    def seq_reset(self):
+        self._chk(self._l.nct_seq_reset(self._h))
+
+    def seq_end(self):
+        self._chk(self._l.nct_seq_end(self._h))
+        self._seq_shapes = None
+
+    def seq_blend(self, x, x_prev, lab, lab_prev, tau, sigma, want_tau_map=True):
+        """nct_seq_blend (SPEC §6.3 rule 3): x, x_prev [2, h*w, 3] doubles, lab / lab_prev h x w x 3 8-bit Lab -> (X', tau_p map [h, w] or None)"""
+        lab = np.ascontiguousarray(lab, np.uint8)
+        h, w = lab.shape[:2]
+        a = np.ascontiguousarray(x, np.float64).reshape(-1)
+        b = np.ascontiguousarray(x_prev, np.float64).reshape(-1)
+        assert a.size == 6 * h * w and b.size == 6 * h * w
+        out = np.empty((2, h * w, 3))
+        tm = np.empty((h, w)) if want_tau_map else None
+        self._chk(self._l.nct_seq_blend(self._h, a, b, lab.reshape(-1, 3), np.ascontiguousarray(lab_prev, np.uint8).reshape(-1, 3), h, w, tau, sigma, out.reshape(-1), _ptr(tm)))
+        return out, tm
+
+    def seq_blend_dev(self, x, x_prev, lab, lab_prev, tau, sigma):
+        """the same through nct_seq_blend_dev: maps uploaded to arena blocks, the launch enqueued on the context's stream (into a block of its own), results downloaded"""
+        lab = np.ascontiguousarray(lab, np.uint8)
+        h, w = lab.shape[:2]
+        n = h * w
+        ins = [self.dev_upload(np.ascontiguousarray(x, np.float64).reshape(-1)), self.dev_upload(np.ascontiguousarray(x_prev, np.float64).reshape(-1)),
+               self.dev_upload(lab), self.dev_upload(np.ascontiguousarray(lab_prev, np.uint8))]
+        do, dt = self.dev_alloc(48 * n), self.dev_alloc(8 * n)
+        try:
+            self._chk(self._l.nct_seq_blend_dev(self._h, ins[0], ins[1], ins[2], ins[3], h, w, tau, sigma, do, dt))
+            return self.dev_download(do, (2, n, 3), np.float64), self.dev_download(dt, (h, w), np.float64)
+        finally:
+            self.synchronize()
+            for p in ins + [do, dt]:
+                self.dev_free(p)
 
     def pair_upload(self, src_bgr, ref_bgr):
         s = np.ascontiguousarray(src_bgr, np.uint8)
