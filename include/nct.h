@@ -26,9 +26,10 @@ extern "C" {
 #endif
 
 /* bumped whenever a struct of this header changes layout or an entry point changes meaning (round 6: 110 — nct_model_layer; nct_pair_timing grew in round 5 without a
- * bump; 111 — nct_multi_levels and the entry points for several references; 112 — frame sequences, nct_seq_*). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
+ * bump; 111 — nct_multi_levels and the entry points for several references; 112 — frame sequences, nct_seq_*; 113 — nct_seq_levels.motion and motion-compensated
+ * sequences, nct_seq_set_motion). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
-#define NCT_VERSION 112
+#define NCT_VERSION 113
 
 typedef enum {
     NCT_OK = 0,
@@ -305,10 +306,23 @@ int nct_process_multi(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int 
  * nct_seq_frame_levels: nct_pair_levels as in nct_pair_run_levels — color[l]->ab_nonlocal is S1's output BEFORE the blend, ab_up / roughness / ab_wls come after
  * it; nct_seq_levels adds X'_t and the tau_p map per level (a frame without a blend reports X_t and 0.0). The blend's time counts in nct_pair_timing.color_ms.
  * nct_seq_blend: the blend alone on host maps (synchronous), x / x_prev / x_out [2][h*w][3], lab / lab_prev h*w*3 (8-bit Lab), tau_map (nullable) h*w;
- * nct_seq_blend_dev: the same on device pointers, enqueued on the context's stream (x_out may be x or x_prev: every thread reads its pixel before it writes it). */
+ * nct_seq_blend_dev: the same on device pointers, enqueued on the context's stream (x_out may be x or x_prev: every thread reads its pixel before it writes it).
+ * Motion compensation (SPEC §6.4): nct_seq_begin opens a sequence without it. nct_seq_set_motion, on an open sequence between frames, turns it on from the next frame
+ * (radius0 in [0, 8], radius in [0, 3], penalty in [0, 255]; out of range NCT_ERR_INVALID, no open sequence NCT_ERR_STATE) and reserves 8 B per level pixel more;
+ * NULL or both radii 0 turns it off and gives that back: every byte and every launch is then the plain sequence's. On a frame that blends, every level first finds
+ * per pixel the displacement m(p) = (my, mx) into the previous frame's Lab level image — a 5 x 5 block match, integer SAD over the three Lab bytes, searched
+ * radius0 around (0, 0) at the first level run and radius around twice the coarser level's vector elsewhere, key = cost + penalty * taps * (|dy| + |dx|), compared
+ * as cost per tap — and the blend reads L_(t-1) (for qbar: 3 x 3 taps inside the grid in both frames) and X'_(t-1) at p + m(p). Identical frames give m = 0.
+ * nct_seq_levels.motion: the field per level, int16 [h*w][2]; a level without one (motion off, no blend) reports zeros.
+ * nct_seq_motion_field / _dev: the search alone. lab / lab_prev h*w*3, parent (nullable: the centre is (0, 0)) the coarser field int16 [ph*pw][2], R in [0, 8],
+ * m_out int16 [h*w][2]. nct_seq_blend_mc / _dev: nct_seq_blend with a nullable field; with one, x_out must not be x_prev (the blend gathers from other pixels), and a
+ * vector that leaves the grid is clamped to it. */
 typedef struct nct_seq_params { double tau, sigma; } nct_seq_params;
 void nct_seq_params_default(nct_seq_params* p);     /* tau 0.7, sigma 10.0 */
-typedef struct nct_seq_levels { double* ab_blend[5]; double* tau_map[5]; } nct_seq_levels;   /* X'_t [2][h*w][3]; tau_p [h*w]; all nullable */
+typedef struct nct_seq_levels { double* ab_blend[5]; double* tau_map[5]; int16_t* motion[5]; } nct_seq_levels;   /* X'_t [2][h*w][3]; tau_p [h*w]; m [h*w][2]; all nullable */
+typedef struct nct_seq_motion { int radius0, radius, penalty; } nct_seq_motion;
+void nct_seq_motion_default(nct_seq_motion* p);     /* 3, 1, 1 */
+int nct_seq_set_motion(nct_ctx* ctx, const nct_seq_motion* motion);
 int nct_seq_begin(nct_ctx* ctx, const uint8_t* ref_bgr, int rh, int rw, int sh, int sw, const nct_params* prm, const nct_seq_params* seq);
 int nct_seq_frame(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing);
 int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels);
@@ -318,6 +332,13 @@ int nct_seq_blend(nct_ctx* ctx, const double* x, const double* x_prev, const uin
                   double* x_out, double* tau_map);
 int nct_seq_blend_dev(nct_ctx* ctx, const double* d_x, const double* d_x_prev, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, double tau, double sigma,
                       double* d_x_out, double* d_tau_map);
+int nct_seq_motion_field(nct_ctx* ctx, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, const int16_t* parent, int ph, int pw, int R, int penalty, int16_t* m_out);
+int nct_seq_motion_field_dev(nct_ctx* ctx, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, const int16_t* d_parent, int ph, int pw, int R, int penalty,
+                             int16_t* d_m_out);
+int nct_seq_blend_mc(nct_ctx* ctx, const double* x, const double* x_prev, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, double tau, double sigma,
+                     double* x_out, double* tau_map, const int16_t* field);
+int nct_seq_blend_mc_dev(nct_ctx* ctx, const double* d_x, const double* d_x_prev, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, double tau, double sigma,
+                         double* d_x_out, double* d_tau_map, const int16_t* d_field);
 
 /* ---- device-pointer seams: the same operations on buffers that stay in HBM between calls (main.cu:204-316 keeps Ndata_C1, ann_device, ... on the device
  * across these kernels; an integrator replacing single seams should not pay H2D + D2H + a synchronise per call). Buffers come from the context's arena

@@ -122,12 +122,14 @@ __global__ void k_wls_system(const double* __restrict__ gx, const double* __rest
 }
 // ================================================================= orchestration
 #define LCHK() NCT_LAUNCH_CHECK()
-static int dbg_copy(nct_ctx* ctx, hipStream_t s, double* host, const double* dev, size_t n) {
+static int dbg_copy_bytes(nct_ctx* ctx, hipStream_t s, void* host, const void* dev, size_t bytes) {
     if (!host) return 0;
-    NCT_HIP(hipMemcpyAsync(host, dev, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    NCT_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s));
     NCT_HIP(hipStreamSynchronize(s));
     return 0;
 }
+static int dbg_copy(nct_ctx* ctx, hipStream_t s, double* host, const double* dev, size_t n) { return dbg_copy_bytes(ctx, s, host, dev, sizeof(double) * n); }
+static int dbg_copy(nct_ctx* ctx, hipStream_t s, int16_t* host, const int16_t* dev, size_t n) { return dbg_copy_bytes(ctx, s, host, dev, sizeof(int16_t) * n); }
 
 // ================================================================= the finish: U1, roughness, S2, A1 on a target grid H x W >= h x w
 // x: [2][h*w][3] coefficients after S1 on the level grid; Hw x Ww: the working size the pyramid runs at (the pipeline's "full" grid of every
@@ -218,12 +220,19 @@ int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, con
         // a frame of a sequence (SPEC §6.3): X'_t = the blend of S1's output with X'_(t-1), in place in the kept state, which the finish reads; L_t replaces L_(t-1)
         DevBuf<double> tmap;
         if (seq->tau_map_host && !tmap.alloc(ctx, n)) return NCT_ERR_HIP;
-        if (seq->blend) NCT_TRY(nctk_seq_blend(ctx, s, x, seq->keep_x, s_lab_level, seq->keep_lab, h, w, seq->tau, seq->sigma, seq->keep_x, tmap));
+        if (seq->blend && seq->field) {
+            // with motion (SPEC §6.4): the level's field, then the blend gathers X'_(t-1) and L_(t-1) through it — not in place: into S1's own buffer, then into the state
+            NCT_TRY(nctk_seq_motion(ctx, s, s_lab_level, seq->keep_pk, h, w, seq->parent, seq->ph, seq->pw, seq->R, seq->penalty, seq->field));
+            NCT_TRY(nctk_seq_blend(ctx, s, x, seq->keep_x, s_lab_level, seq->keep_lab, h, w, seq->tau, seq->sigma, x, tmap, seq->field));
+            NCT_HIP(hipMemcpyAsync(seq->keep_x, x, sizeof(double) * (size_t)6 * n, hipMemcpyDeviceToDevice, s));
+            NCT_TRY(dbg_copy(ctx, s, seq->motion_host, seq->field, (size_t)2 * n));
+        } else if (seq->blend) NCT_TRY(nctk_seq_blend(ctx, s, x, seq->keep_x, s_lab_level, seq->keep_lab, h, w, seq->tau, seq->sigma, seq->keep_x, tmap));
         else {
             NCT_HIP(hipMemcpyAsync(seq->keep_x, x, sizeof(double) * (size_t)6 * n, hipMemcpyDeviceToDevice, s));
             if (tmap.ok()) NCT_HIP(hipMemsetAsync(tmap, 0, sizeof(double) * (size_t)n, s));
         }
         NCT_HIP(hipMemcpyAsync(seq->keep_lab, s_lab_level, (size_t)3 * n, hipMemcpyDeviceToDevice, s));
+        if (seq->field) NCT_TRY(nctk_seq_pack(ctx, s, s_lab_level, n, seq->keep_pk));
         NCT_TRY(dbg_copy(ctx, s, seq->ab_blend_host, seq->keep_x, (size_t)6 * n));
         if (tmap.ok()) NCT_TRY(dbg_copy(ctx, s, seq->tau_map_host, tmap, n));
         return nctk_color_finish(ctx, s, seq->keep_x, h, w, H, W, s_lab_full, H, W, prm, out_lab_full, dbg);

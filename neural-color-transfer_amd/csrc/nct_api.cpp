@@ -326,6 +326,48 @@ int nct_seq_blend(nct_ctx* ctx, const double* x, const double* x_prev, const uin
     return NCT_OK;
 }
 
+// SPEC §6.4 rule 4 on host maps; without a field it is nct_seq_blend
+int nct_seq_blend_mc(nct_ctx* ctx, const double* x, const double* x_prev, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, double tau, double sigma,
+                     double* x_out, double* tau_map, const int16_t* field) {
+    if (!field) return nct_seq_blend(ctx, x, x_prev, lab, lab_prev, h, w, tau, sigma, x_out, tau_map);
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(x && x_prev && lab && lab_prev && x_out, "seq_blend: null pointer");
+    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_blend: grid %dx%d out of range", w, h);
+    NCT_REQUIRE(x_out != x_prev, "seq_blend: with a motion field x_out must not alias x_prev");
+    const size_t n = (size_t)h * w;
+    DevBuf<double> dx(ctx, 6 * n), dp(ctx, 6 * n), dt(ctx, n);
+    DevBuf<uint8_t> dl(ctx, 3 * n), dlp(ctx, 3 * n);
+    DevBuf<int16_t> df(ctx, 2 * n);
+    if (!dx.ok() || !dp.ok() || !dt.ok() || !dl.ok() || !dlp.ok() || !df.ok()) return NCT_ERR_HIP;
+    NCT_H2D(dx, x, sizeof(double) * 6 * n); NCT_H2D(dp, x_prev, sizeof(double) * 6 * n);
+    NCT_H2D(dl, lab, 3 * n); NCT_H2D(dlp, lab_prev, 3 * n); NCT_H2D(df, field, sizeof(int16_t) * 2 * n);
+    NCT_TRY(nctk_seq_blend(ctx, ctx->stream, dx, dp, dl, dlp, h, w, tau, sigma, dx, tau_map ? (double*)dt : nullptr, df));   // into S1's own map, as a frame does it
+    NCT_D2H(x_out, dx, sizeof(double) * 6 * n);
+    if (tau_map) NCT_D2H(tau_map, dt, sizeof(double) * n);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
+// SPEC §6.4 rules 1-3 on host maps: the two Lab level images (and the coarser level's field) up, L_(t-1) packed, one k_seq_motion launch, the field down
+int nct_seq_motion_field(nct_ctx* ctx, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, const int16_t* parent, int ph, int pw, int R, int penalty, int16_t* m_out) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(lab && lab_prev && m_out, "seq_motion_field: null pointer");
+    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_motion_field: grid %dx%d out of range", w, h);
+    NCT_REQUIRE(!parent || (ph >= 1 && pw >= 1 && ph <= 4096 && pw <= 4096), "seq_motion_field: parent grid %dx%d out of range", pw, ph);
+    const size_t n = (size_t)h * w, np = parent ? (size_t)ph * pw : 1;
+    DevBuf<uint8_t> dl(ctx, 3 * n), dlp(ctx, 3 * n);
+    DevBuf<uint32_t> pk(ctx, n);
+    DevBuf<int16_t> dpar(ctx, 2 * np), dm(ctx, 2 * n);
+    if (!dl.ok() || !dlp.ok() || !pk.ok() || !dpar.ok() || !dm.ok()) return NCT_ERR_HIP;
+    NCT_H2D(dl, lab, 3 * n); NCT_H2D(dlp, lab_prev, 3 * n);
+    if (parent) NCT_H2D(dpar, parent, sizeof(int16_t) * 2 * np);
+    NCT_TRY(nctk_seq_pack(ctx, ctx->stream, dlp, (int)n, pk));
+    NCT_TRY(nctk_seq_motion(ctx, ctx->stream, dl, pk, h, w, parent ? (const int16_t*)dpar : nullptr, ph, pw, R, penalty, dm));
+    NCT_D2H(m_out, dm, sizeof(int16_t) * 2 * n);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
 int nct_bds_vote_image(nct_ctx* ctx, const uint8_t* a_bgr, int ah, int aw, const uint8_t* b_bgr, int bh, int bw,
                        const uint32_t* ann, const uint32_t* bnn, int patch, double w_coherence, double w_complete, uint8_t* out_bgr) {
     NCT_CTX_ENTER();

@@ -132,4 +132,21 @@ int nct_seq_blend_dev(nct_ctx* ctx, const double* d_x, const double* d_x_prev, c
     return nctk_seq_blend(ctx, ctx->stream, d_x, d_x_prev, d_lab, d_lab_prev, h, w, tau, sigma, d_x_out, d_tau_map);
 }
 
+int nct_seq_blend_mc_dev(nct_ctx* ctx, const double* d_x, const double* d_x_prev, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, double tau, double sigma,
+                         double* d_x_out, double* d_tau_map, const int16_t* d_field) {                                                                /* SPEC §6.4 rule 4 */
+    NCT_CTX_ENTER();
+    return nctk_seq_blend(ctx, ctx->stream, d_x, d_x_prev, d_lab, d_lab_prev, h, w, tau, sigma, d_x_out, d_tau_map, d_field);
+}
+
+int nct_seq_motion_field_dev(nct_ctx* ctx, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, const int16_t* d_parent, int ph, int pw, int R, int penalty,
+                             int16_t* d_m_out) {                                                                                                      /* SPEC §6.4 rules 1-3 */
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(d_lab && d_lab_prev && d_m_out, "seq_motion_field_dev: null pointer");
+    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_motion_field_dev: grid %dx%d out of range", w, h);
+    DevBuf<uint32_t> pk(ctx, (size_t)h * w);                     // L_(t-1) one word per pixel; the block goes back in stream order
+    if (!pk.ok()) return NCT_ERR_HIP;
+    NCT_TRY(nctk_seq_pack(ctx, ctx->stream, d_lab_prev, h * w, pk));
+    return nctk_seq_motion(ctx, ctx->stream, d_lab, pk, h, w, d_parent, ph, pw, R, penalty, d_m_out);
+}
+
 }  // extern "C"

@@ -179,7 +179,11 @@ struct nct_finish_target { const uint8_t* s_lab; int H, W; uint8_t* out_lab; };
 // A level of a sequence frame (SPEC §6.3), between S1 and the finish. keep_x ([2][n][3]) / keep_lab ([n][3]): the level's state, X'_(t-1) and L_(t-1) on entry where blend is set,
 // X'_t and L_t on return: with blend one k_seq_blend launch in place into keep_x, which the finish then reads; without (first frame) S1's output is copied there.
 // tau_map_host / ab_blend_host (nullable): host copies for level-wise validation
-struct nct_seq_link { double* keep_x; uint8_t* keep_lab; bool blend; double tau, sigma; double* ab_blend_host; double* tau_map_host; };
+// Motion compensation (SPEC §6.4) where field is set: keep_pk ([n] words) is L_(t-1) packed for k_seq_motion and becomes L_t packed; with blend the level's field goes to
+// field ([n][2] int16; parent / ph / pw: the previous level's, null at the first level run; R: that level's radius), the blend gathers through it into S1's own buffer
+// and the result is copied to keep_x. motion_host (nullable): the field's host copy
+struct nct_seq_link { double* keep_x = nullptr; uint8_t* keep_lab = nullptr; bool blend = false; double tau = 0, sigma = 0; double* ab_blend_host = nullptr; double* tau_map_host = nullptr;
+                      uint32_t* keep_pk = nullptr; int16_t* field = nullptr; const int16_t* parent = nullptr; int ph = 0, pw = 0, R = 0, penalty = 0; int16_t* motion_host = nullptr; };
 // H x W: the working size (S1's dWeight); fin (nullable) retargets U1 / S2 / A1 — null: they target H x W, s_lab_full, out_lab_full
 int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, const uint8_t* s_lab_level, const uint8_t* g_lab_level,
                               const uint8_t* s_lab_full, const int* knn_id, const double* knn_w, int layer, int h, int w, int H, int W,
@@ -196,9 +200,14 @@ void nct_set_ctxless_error(const char* msg);   // nct_api.cpp
 // pointers (they go into the kernel's argument block); label, guide_out (then guide may be null too) and err_out are nullable
 int nctk_select_reference(nct_ctx* ctx, hipStream_t s, const float* const* err, const uint8_t* const* guide, int K, int h, int w,
                           uint8_t* label, uint8_t* guide_out, float* err_out);
-// k_temporal.hip — SPEC §6.3 rule 3: x_out = x + tau_p (x_prev - x) per level pixel, tau_p from the 3 x 3 mean squared Lab difference; x_out may alias x or x_prev; tau_map nullable
+// k_temporal.hip — SPEC §6.3 rule 3: x_out = x + tau_p (x_prev - x) per level pixel, tau_p from the 3 x 3 mean squared Lab difference; x_out may alias x or x_prev; tau_map nullable.
+// field (nullable, [h*w][2] int16 (my, mx)): SPEC §6.4 rule 4 — L_(t-1) and x_prev are read at p + m(p); x_out may then alias x only
 int nctk_seq_blend(nct_ctx* ctx, hipStream_t s, const double* x, const double* x_prev, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, double tau, double sigma,
-                   double* x_out, double* tau_map);
+                   double* x_out, double* tau_map, const int16_t* field = nullptr);
+// SPEC §6.4 rules 1-3: the level's motion field from L_t ([n][3] bytes) and L_(t-1) packed by nctk_seq_pack ([n] words L | a << 8 | b << 16); parent nullable
+int nctk_seq_pack(nct_ctx* ctx, hipStream_t s, const uint8_t* lab, int n, uint32_t* out);
+int nctk_seq_motion(nct_ctx* ctx, hipStream_t s, const uint8_t* lab, const uint32_t* prev_packed, int h, int w, const int16_t* parent, int ph, int pw, int R, int penalty,
+                    int16_t* m_out);
 // k_wls_mg.hip
 int nctk_wls_solve_mg(nct_ctx* ctx, hipStream_t s, double* X, const double* rough, const double* wx, const double* wy, int H, int W,
                       double rtol, int* iters_out);

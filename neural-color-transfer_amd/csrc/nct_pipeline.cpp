@@ -14,12 +14,15 @@
 // An open frame sequence (SPEC §6.3): what nct_seq_begin prepares once and every frame borrows — the reference's pyramid and its five un-normalised taps (HWC, by
 // level) — and the state the blend carries from frame to frame, per level X' ([2][h*w][3] doubles) and L (the frame's level image in 8-bit Lab). All of it comes from
 // the context's arena and outlives the runs; the frame and the reference at working size are pair_state's src / ref[0] as for a pair.
+// While motion compensation is on (SPEC §6.4, nct_seq_set_motion) it also holds, per level, L packed one word per pixel and the level's field (4 B per level pixel each).
 struct seq_state {
     nct_params prm; double tau = 0, sigma = 0;
     long frames = 0;                                           // frames since nct_seq_begin / nct_seq_reset: 0 = the next one is a first frame
     int ah[5], aw[5], bh[5], bw[5];
     uint8_t* rpyr[4] = {}; float* rfeat[5] = {};
     double* keep_x[5] = {}; uint8_t* keep_lab[5] = {};
+    bool motion = false; nct_seq_motion mp = {0, 0, 0};
+    uint32_t* keep_pk[5] = {}; int16_t* field[5] = {};
 };
 struct pair_state {
     uint8_t *src = nullptr, *out = nullptr;                    // device BGR images
@@ -39,10 +42,19 @@ static void drop_images(nct_ctx* ctx, pair_state* P) {
     if (P->out) { ctx->release(P->out); P->out = nullptr; }
     P->K = 0;
 }
+// what motion compensation holds goes back to the arena
+static void seq_motion_free(nct_ctx* ctx, seq_state* q) {
+    for (int l = 0; l < 5; ++l) {
+        if (q->keep_pk[l]) { ctx->release(q->keep_pk[l]); q->keep_pk[l] = nullptr; }
+        if (q->field[l]) { ctx->release(q->field[l]); q->field[l] = nullptr; }
+    }
+    q->motion = false;
+}
 // what an open sequence holds goes back to the arena
 static void seq_free(nct_ctx* ctx, pair_state* P) {
     seq_state* q = P->seq;
     if (!q) return;
+    seq_motion_free(ctx, q);
     for (int l = 0; l < 5; ++l) {
         if (l < 4 && q->rpyr[l]) ctx->release(q->rpyr[l]);
         if (q->rfeat[l]) ctx->release(q->rfeat[l]);
@@ -414,8 +426,17 @@ struct pair_run {
             NCT_TRY(nctk_lab2bgr(ctx, s, out0_lab, fin->out, N0, cube));
         } else {
             // a frame of a sequence: the blend between S1 and the finish (SPEC §6.3 rule 3); the first frame and tau == 0 only keep the state, with no blend launch
-            nct_seq_link link{};
-            if (seq) link = nct_seq_link{seq->keep_x[l], seq->keep_lab[l], seq->frames > 0 && seq->tau > 0.0, seq->tau, seq->sigma, slv ? slv->ab_blend[l] : nullptr, slv ? slv->tau_map[l] : nullptr};
+            nct_seq_link link;
+            if (seq) {
+                link.keep_x = seq->keep_x[l]; link.keep_lab = seq->keep_lab[l]; link.blend = seq->frames > 0 && seq->tau > 0.0; link.tau = seq->tau; link.sigma = seq->sigma;
+                link.ab_blend_host = slv ? slv->ab_blend[l] : nullptr; link.tau_map_host = slv ? slv->tau_map[l] : nullptr;
+            }
+            if (seq && seq->motion) {
+                // SPEC §6.4: the first level run searches radius0 around (0, 0), every other level radius around twice the previous level's vector
+                link.keep_pk = seq->keep_pk[l]; link.field = seq->field[l]; link.R = l == 0 ? seq->mp.radius0 : seq->mp.radius; link.penalty = seq->mp.penalty;
+                if (l > 0) { link.parent = seq->field[l - 1]; link.ph = ah[l - 1]; link.pw = aw[l - 1]; }
+                link.motion_host = slv ? slv->motion[l] : nullptr;
+            }
             NCT_TRY(nctk_local_color_transfer(ctx, s, err, side.slab[l], g_lab_l, s_lab_full, side.knn_ids[l], side.knn_ws[l], l, ah[l], aw[l], H, W, cp, out_lab, (timing || cs) ? &dbg : nullptr, &s1graph,
                                               nullptr, seq ? &link : nullptr));
             if (cs && cs->wls_iters) for (int q = 0; q < 6; ++q) cs->wls_iters[q] = wls_it[q];
@@ -617,6 +638,45 @@ int nct_seq_end(nct_ctx* ctx) {
     return NCT_OK;
 }
 
+void nct_seq_motion_default(nct_seq_motion* p) {
+    if (!p) return;
+    p->radius0 = 3; p->radius = 1; p->penalty = 1;
+}
+
+// SPEC §6.4: motion compensation of the open sequence on (from the next frame) or off. Turning it on reserves the packed maps and the fields and packs the kept L of
+// a sequence that already has frames; turning it off gives them back
+int nct_seq_set_motion(nct_ctx* ctx, const nct_seq_motion* mp) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_set_motion: no sequence is open (nct_seq_begin first)");
+    seq_state* q = P->seq;
+    if (mp) {
+        NCT_REQUIRE(mp->radius0 >= 0 && mp->radius0 <= 8, "seq_set_motion: radius0 must be in [0, 8] (got %d)", mp->radius0);
+        NCT_REQUIRE(mp->radius >= 0 && mp->radius <= 3, "seq_set_motion: radius must be in [0, 3] (got %d)", mp->radius);
+        NCT_REQUIRE(mp->penalty >= 0 && mp->penalty <= 255, "seq_set_motion: penalty must be in [0, 255] (got %d)", mp->penalty);
+    }
+    const bool on = mp && (mp->radius0 > 0 || mp->radius > 0);
+    if (!on) {
+        if (q->motion) { NCT_SYNC(); seq_motion_free(ctx, q); }
+        return NCT_OK;
+    }
+    q->mp = *mp;
+    if (q->motion) return NCT_OK;
+    for (int l = 0; l < q->prm.levels; ++l) {
+        const size_t n = (size_t)q->ah[l] * q->aw[l];
+        q->keep_pk[l] = (uint32_t*)ctx->alloc(sizeof(uint32_t) * n); q->field[l] = (int16_t*)ctx->alloc(sizeof(int16_t) * 2 * n);
+        if (!q->keep_pk[l] || !q->field[l]) { seq_motion_free(ctx, q); return NCT_ERR_HIP; }
+    }
+    q->motion = true;
+    if (q->frames > 0) {
+        for (int l = 0; l < q->prm.levels; ++l) {
+            const int rc = nctk_seq_pack(ctx, ctx->stream, q->keep_lab[l], q->ah[l] * q->aw[l], q->keep_pk[l]);
+            if (rc) { seq_motion_free(ctx, q); return rc; }
+        }
+    }
+    return NCT_OK;
+}
+
 int nct_seq_reset(nct_ctx* ctx) {
     NCT_CTX_ENTER();
     pair_state* P = (pair_state*)ctx->pair;
@@ -680,6 +740,8 @@ int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr,
     if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_frame: no sequence is open (nct_seq_begin first)");
     NCT_REQUIRE(src_bgr && out_bgr, "seq_frame: null image");
     seq_state* q = P->seq;
+    // a level without a field (motion off, a first frame, tau == 0) reports zeros
+    if (seq_levels) for (int l = 0; l < q->prm.levels; ++l) if (seq_levels->motion[l]) memset(seq_levels->motion[l], 0, sizeof(int16_t) * 2 * (size_t)q->ah[l] * q->aw[l]);
     NCT_H2D(P->src, src_bgr, (size_t)P->sh * P->sw * 3);
     nct_multi_levels m; memset(&m, 0, sizeof m);
     if (levels) {

@@ -9,6 +9,7 @@
 // and `-feat16 1` (reduced-precision PatchMatch features; not bit-identical), `-fullres 1` (the result at the content image's own size, SPEC §6.1),
 // and pairs.txt lines whose second token lists several references separated by commas (SPEC §6.2: every pixel takes its colours from the reference that matches it best),
 // `-seq 1` (+ `-tau`, `-sigma`): consecutive lines with one and the same reference are the frames of a sequence, graded with temporally blended coefficients (SPEC §6.3).
+// `-motion 1` (+ `-mr0`, `-mr`, `-mpen`): the blend of a sequence follows the motion between the frames (SPEC §6.4).
 #include <sys/stat.h>
 #include <sys/wait.h>
 #include <fcntl.h>
@@ -111,7 +112,7 @@ std::string stem(const std::string& path) {          // main.cu:524-531 (find_la
 struct Pair { std::string cnt, stl; float bds; std::vector<std::string> refs; std::string err; };
 std::mutex g_print;
 
-struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false, fullres = false, seq = false; nct_seq_params sp; int rank = 0, world = 1; };
+struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false, fullres = false, seq = false, motion = false; nct_seq_params sp; nct_seq_motion mp; int rank = 0, world = 1; };
 
 // ---- ENABLE_VIS debug outputs (Config.h:8) behind the runtime flag -vis 1: per pyramid level the flow maps of both NNFs (reconstruct_flow,
 // GeneralizedPatchMatch.cu:337-353), the level images tCnt / tStl (main.cu:343-347), the matching-error heat map (getHeat,
@@ -495,6 +496,11 @@ size_t run_sequence(nct_ctx* ctx, const Config& cfg, const std::vector<Pair>& pa
                 rc = nct_seq_begin(ctx, ref.px.data(), ref.h, ref.w, j.cnt.h, j.cnt.w, &prm, &cfg.sp);
                 open = rc == NCT_OK; fh = j.cnt.h; fw = j.cnt.w;
                 if (open) j.say("Sequence %ld: begins at this frame (%d x %d, tau = %g, sigma = %g).\n", g.seq, fw, fh, cfg.sp.tau, cfg.sp.sigma);
+                if (open && cfg.motion) {
+                    rc = nct_seq_set_motion(ctx, &cfg.mp);
+                    if (rc == NCT_OK) j.say("Sequence %ld: motion compensation (radius0 = %d, radius = %d, penalty = %d).\n", g.seq, cfg.mp.radius0, cfg.mp.radius, cfg.mp.penalty);
+                    else { nct_seq_end(ctx); open = false; }               // no plain sequence where -motion 1 was asked: the next frame begins again
+                }
             }
             nct_pair_timing tm;
             j.out.resize((size_t)j.cnt.h * j.cnt.w * 3);
@@ -633,6 +639,8 @@ int main(int argc, char** argv) {
     Config cfg;
     nct_params_default(&cfg.prm);
     nct_seq_params_default(&cfg.sp);
+    nct_seq_motion_default(&cfg.mp);
+    int motion = 0;
     int gpu = 0, ngpus = 1, seed = 1, inflight = 1, levels = 5, resume = 0, feat16 = 0, vis = 0, fullres = 0, seq = 0, io = -1, pin = 1, world = 1, rank = 0, steal = 0, procs = 0, rccl = 0;
     cl.add("m", cfg.model_dir, "Directory of network models.");
     cl.add("i", cfg.input_dir, "Input directory of content and style images and pairs.txt.");
@@ -663,6 +671,10 @@ int main(int argc, char** argv) {
     cl.add("seq", seq, "[extension] 1 = consecutive pairs.txt lines with one and the same reference and weight are the frames of a sequence (SPEC 6.3): one worker runs them in file order and blends each frame's colour coefficients with the previous frame's; every worker does its own file I/O (-io is not used); not with -fullres 1 or -vis 1.");
     cl.add("tau", cfg.sp.tau, "[extension] -seq 1: temporal weight in [0, 1); 0 = every frame on its own.");
     cl.add("sigma", cfg.sp.sigma, "[extension] -seq 1: sensitivity of the blend to changes between frames, in 8-bit Lab units (> 0).");
+    cl.add("motion", motion, "[extension] -seq 1: 1 = motion-compensated blend (SPEC 6.4): every level finds per pixel where it was in the previous frame (5 x 5 block match on the Lab level images, coarse to fine) and blends with the coefficients there.");
+    cl.add("mr0", cfg.mp.radius0, "[extension] -motion 1: search radius at the coarsest level, in [0, 8].");
+    cl.add("mr", cfg.mp.radius, "[extension] -motion 1: search radius of the refinement at every finer level, in [0, 3].");
+    cl.add("mpen", cfg.mp.penalty, "[extension] -motion 1: cost per tap and pixel of displacement from the search centre, in [0, 255].");
     // parser self-test hook (no GPU): `--parse-only <args…>` parses the rest like a normal run and prints what main would go on with, in the format of
     // oracle/ref_cmdline.cpp (the reference's own parser): tests/test_cli.py compares the two on the vectors of tests/golden/cmdline_ref.json
     // job-planning hook (no GPU): `--plan-only <args…>` goes as far as a normal run goes before it creates a context and prints, per pairs.txt line, what it would run
@@ -684,6 +696,10 @@ int main(int argc, char** argv) {
     if (seq && vis) { printf("Error: -seq 1 cannot be combined with -vis 1 (the -vis dumps describe single pairs).\n"); return -1; }
     if (seq && !(cfg.sp.tau >= 0.0 && cfg.sp.tau < 1.0)) { printf("Error: -tau %g is not in [0, 1).\n", cfg.sp.tau); return -1; }
     if (seq && !(cfg.sp.sigma > 0.0 && cfg.sp.sigma <= 1.7976931348623157e308)) { printf("Error: -sigma %g is not finite and positive.\n", cfg.sp.sigma); return -1; }
+    if (motion && !seq) { printf("Error: -motion 1 needs -seq 1 (motion compensation belongs to a sequence's blend).\n"); return -1; }
+    if (motion && (cfg.mp.radius0 < 0 || cfg.mp.radius0 > 8)) { printf("Error: -mr0 %d is not in [0, 8].\n", cfg.mp.radius0); return -1; }
+    if (motion && (cfg.mp.radius < 0 || cfg.mp.radius > 3)) { printf("Error: -mr %d is not in [0, 3].\n", cfg.mp.radius); return -1; }
+    if (motion && (cfg.mp.penalty < 0 || cfg.mp.penalty > 255)) { printf("Error: -mpen %d is not in [0, 255].\n", cfg.mp.penalty); return -1; }
     if (!plan_only) mkdir(cfg.output_dir.c_str(), 0777);                    // main.cu:458
     uint64_t run_token = getenv("NCT_RUN_TOKEN") ? strtoull(getenv("NCT_RUN_TOKEN"), nullptr, 0) : 0;      // hand-started ranks of one run share it (and remove <output>/.rccl_id between runs)
     const std::string tickets_path = cfg.output_dir + "/.tickets";
@@ -719,6 +735,7 @@ int main(int argc, char** argv) {
     cfg.vis = vis != 0;
     cfg.fullres = fullres != 0;
     cfg.seq = seq != 0;
+    cfg.motion = motion != 0;
     if (ngpus < 1) ngpus = 1;
     if (inflight < 1) inflight = 1;
     if (inflight > 8) inflight = 8;

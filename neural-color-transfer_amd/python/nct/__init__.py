@@ -38,7 +38,7 @@ def lib():
     return _lib
 
 
-NCT_VERSION = 112        # include/nct.h
+NCT_VERSION = 113        # include/nct.h
 MAX_REFS = 8             # NCT_MAX_REFS
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -108,6 +108,12 @@ SIGNATURES = {
     "nct_seq_end": (C.c_int, [C.c_void_p]),
     "nct_seq_blend": (C.c_int, [C.c_void_p, _f64p, _f64p, _u8p, _u8p, C.c_int, C.c_int, C.c_double, C.c_double, _f64p, C.c_void_p]),
     "nct_seq_blend_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "nct_seq_motion_default": (None, [C.c_void_p]),
+    "nct_seq_set_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "nct_seq_motion_field": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "nct_seq_motion_field_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "nct_seq_blend_mc": (C.c_int, [C.c_void_p, _f64p, _f64p, _u8p, _u8p, C.c_int, C.c_int, C.c_double, C.c_double, _f64p, C.c_void_p, C.c_void_p]),
+    "nct_seq_blend_mc_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "nct_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nct_dev_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -249,7 +255,18 @@ class SeqParams(C.Structure):
 
 class SeqLevels(C.Structure):
     """struct nct_seq_levels (include/nct.h)."""
-    _fields_ = [("ab_blend", C.c_void_p * 5), ("tau_map", C.c_void_p * 5)]
+    _fields_ = [("ab_blend", C.c_void_p * 5), ("tau_map", C.c_void_p * 5), ("motion", C.c_void_p * 5)]
+
+
+class SeqMotion(C.Structure):
+    """struct nct_seq_motion (include/nct.h)."""
+    _fields_ = [("radius0", C.c_int), ("radius", C.c_int), ("penalty", C.c_int)]
+
+    @staticmethod
+    def default():
+        p = SeqMotion()
+        lib().nct_seq_motion_default(C.byref(p))
+        return p
 
 
 class ColorStages(C.Structure):
@@ -689,7 +706,8 @@ class Context:
 
     def seq_frame_levels(self, src_bgr, want_color=True):
         """nct_seq_frame_levels -> (result, dict): pair_run_levels' per-level lists ("ann" … "result", with want_color "color" and "labels"), plus "ab_blend" and "tau_map"
-        per level that ran (X'_t [2, h*w, 3] and tau_p [h, w]; a frame without a blend reports X_t and zeros) and "timing"."""
+        per level that ran (X'_t [2, h*w, 3] and tau_p [h, w]; a frame without a blend reports X_t and zeros), "motion" (SPEC §6.4: the level's field, int16 [h, w, 2] of
+        (my, mx); zeros without motion or without a blend) and "timing"."""
         s = np.ascontiguousarray(src_bgr, np.uint8)
         (H, W), (RH, RW), levels = self._seq_shapes
         if tuple(s.shape[:2]) != (H, W):
@@ -720,15 +738,16 @@ class Context:
             lv.labels = labels.ctypes.data
         ab_blend = [np.zeros((2, ah * aw, 3)) for (ah, aw, _, _) in dims[:levels]]
         tau_map = [np.zeros((ah, aw)) for (ah, aw, _, _) in dims[:levels]]
+        motion = [np.zeros((ah, aw, 2), np.int16) for (ah, aw, _, _) in dims[:levels]]
         sl = SeqLevels()
         for l in range(levels):
-            sl.ab_blend[l] = ab_blend[l].ctypes.data; sl.tau_map[l] = tau_map[l].ctypes.data
+            sl.ab_blend[l] = ab_blend[l].ctypes.data; sl.tau_map[l] = tau_map[l].ctypes.data; sl.motion[l] = motion[l].ctypes.data
         out = np.empty_like(s)
         tm = PairTiming()
         self._chk(self._l.nct_seq_frame_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv), C.addressof(sl)))
         if want_color:
             keep["color"] = color; keep["labels"] = labels
-        keep["ab_blend"] = ab_blend; keep["tau_map"] = tau_map
+        keep["ab_blend"] = ab_blend; keep["tau_map"] = tau_map; keep["motion"] = motion
         keep["timing"] = tm.as_dict(); keep["dims"] = dims
         return out, keep
 
@@ -738,6 +757,76 @@ class Context:
     def seq_end(self):
         self._chk(self._l.nct_seq_end(self._h))
         self._seq_shapes = None
+
+    def seq_set_motion(self, radius0=None, radius=None, penalty=None, off=False):
+        """nct_seq_set_motion (SPEC §6.4): motion compensation of the open sequence from the next frame on; values left out are nct_seq_motion_default's (3, 1, 1).
+        off=True passes NULL; both radii 0 turn it off as well"""
+        if off:
+            self._chk(self._l.nct_seq_set_motion(self._h, None))
+            return
+        mp = SeqMotion.default()
+        for k, v in (("radius0", radius0), ("radius", radius), ("penalty", penalty)):
+            if v is not None:
+                setattr(mp, k, int(v))
+        self._chk(self._l.nct_seq_set_motion(self._h, C.addressof(mp)))
+
+    def seq_motion_field(self, lab, lab_prev, parent, R, penalty):
+        """nct_seq_motion_field (SPEC §6.4 rules 1-3): lab / lab_prev h x w x 3 8-bit Lab, parent None or the coarser level's field int16 [ph, pw, 2] -> int16 [h, w, 2] of (my, mx)"""
+        lab = np.ascontiguousarray(lab, np.uint8)
+        h, w = lab.shape[:2]
+        par = None if parent is None else np.ascontiguousarray(parent, np.int16)
+        ph, pw = (0, 0) if par is None else par.shape[:2]
+        out = np.empty((h, w, 2), np.int16)
+        self._chk(self._l.nct_seq_motion_field(self._h, lab.reshape(-1, 3), np.ascontiguousarray(lab_prev, np.uint8).reshape(-1, 3), h, w, _ptr(par), ph, pw, int(R), int(penalty), out.ctypes.data))
+        return out
+
+    def seq_motion_field_dev(self, lab, lab_prev, parent, R, penalty):
+        """the same through nct_seq_motion_field_dev on arena blocks"""
+        lab = np.ascontiguousarray(lab, np.uint8)
+        h, w = lab.shape[:2]
+        par = None if parent is None else np.ascontiguousarray(parent, np.int16)
+        ph, pw = (0, 0) if par is None else par.shape[:2]
+        ins = [self.dev_upload(lab), self.dev_upload(np.ascontiguousarray(lab_prev, np.uint8))] + ([] if par is None else [self.dev_upload(par)])
+        do = self.dev_alloc(4 * h * w)
+        try:
+            self._chk(self._l.nct_seq_motion_field_dev(self._h, ins[0], ins[1], h, w, None if par is None else ins[2], ph, pw, int(R), int(penalty), do))
+            return self.dev_download(do, (h, w, 2), np.int16)
+        finally:
+            self.synchronize()
+            for p in ins + [do]:
+                self.dev_free(p)
+
+    def seq_blend_mc(self, x, x_prev, lab, lab_prev, tau, sigma, field, want_tau_map=True):
+        """nct_seq_blend_mc (SPEC §6.4 rule 4): seq_blend with L_(t-1) and x_prev read through field (int16 [h, w, 2], or None: seq_blend)"""
+        lab = np.ascontiguousarray(lab, np.uint8)
+        h, w = lab.shape[:2]
+        a = np.ascontiguousarray(x, np.float64).reshape(-1)
+        b = np.ascontiguousarray(x_prev, np.float64).reshape(-1)
+        assert a.size == 6 * h * w and b.size == 6 * h * w
+        f = None if field is None else np.ascontiguousarray(field, np.int16)
+        assert f is None or f.size == 2 * h * w
+        out = np.empty((2, h * w, 3))
+        tm = np.empty((h, w)) if want_tau_map else None
+        self._chk(self._l.nct_seq_blend_mc(self._h, a, b, lab.reshape(-1, 3), np.ascontiguousarray(lab_prev, np.uint8).reshape(-1, 3), h, w, tau, sigma, out.reshape(-1), _ptr(tm), _ptr(f)))
+        return out, tm
+
+    def seq_blend_mc_dev(self, x, x_prev, lab, lab_prev, tau, sigma, field, alias_prev=False):
+        """the same through nct_seq_blend_mc_dev on arena blocks, into a block of its own (alias_prev: into x_prev's block, which a field makes an error)"""
+        lab = np.ascontiguousarray(lab, np.uint8)
+        h, w = lab.shape[:2]
+        n = h * w
+        ins = [self.dev_upload(np.ascontiguousarray(x, np.float64).reshape(-1)), self.dev_upload(np.ascontiguousarray(x_prev, np.float64).reshape(-1)),
+               self.dev_upload(lab), self.dev_upload(np.ascontiguousarray(lab_prev, np.uint8))]
+        if field is not None:
+            ins.append(self.dev_upload(np.ascontiguousarray(field, np.int16)))
+        do, dt = self.dev_alloc(48 * n), self.dev_alloc(8 * n)
+        try:
+            self._chk(self._l.nct_seq_blend_mc_dev(self._h, ins[0], ins[1], ins[2], ins[3], h, w, tau, sigma, ins[1] if alias_prev else do, dt, ins[4] if field is not None else None))
+            return self.dev_download(ins[1] if alias_prev else do, (2, n, 3), np.float64), self.dev_download(dt, (h, w), np.float64)
+        finally:
+            self.synchronize()
+            for p in ins + [do, dt]:
+                self.dev_free(p)
 
     def seq_blend(self, x, x_prev, lab, lab_prev, tau, sigma, want_tau_map=True):
         """nct_seq_blend (SPEC §6.3 rule 3): x, x_prev [2, h*w, 3] doubles, lab / lab_prev h x w x 3 8-bit Lab -> (X', tau_p map [h, w] or None)"""
