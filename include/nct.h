@@ -27,9 +27,9 @@ extern "C" {
 
 /* bumped whenever a struct of this header changes layout or an entry point changes meaning (round 6: 110 — nct_model_layer; nct_pair_timing grew in round 5 without a
  * bump; 111 — nct_multi_levels and the entry points for several references; 112 — frame sequences, nct_seq_*; 113 — nct_seq_levels.motion and motion-compensated
- * sequences, nct_seq_set_motion). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
+ * sequences, nct_seq_set_motion; 114 — propagated frames, nct_seq_frame_propagate and nct_seq_warp). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
-#define NCT_VERSION 113
+#define NCT_VERSION 114
 
 typedef enum {
     NCT_OK = 0,
@@ -316,7 +316,21 @@ int nct_process_multi(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int 
  * nct_seq_levels.motion: the field per level, int16 [h*w][2]; a level without one (motion off, no blend) reports zeros.
  * nct_seq_motion_field / _dev: the search alone. lab / lab_prev h*w*3, parent (nullable: the centre is (0, 0)) the coarser field int16 [ph*pw][2], R in [0, 8],
  * m_out int16 [h*w][2]. nct_seq_blend_mc / _dev: nct_seq_blend with a nullable field; with one, x_out must not be x_prev (the blend gathers from other pixels), and a
- * vector that leaves the grid is clamped to it. */
+ * vector that leaves the grid is clamped to it.
+ * Propagated frames (SPEC §6.5): nct_seq_frame_propagate runs a frame of the open sequence without the pair's level loop. Per level run it takes the frame's 8-bit Lab
+ * level image L_t (the pyramid and cvtColor of a full frame), finds the field m of §6.4 on (L_t, L_(t-1)) while motion is on (m = 0 while it is off) and moves the kept
+ * coefficients along it, X'_t(p) = X'_(t-1)(p + m(p)): the 64-bit words are copied, a NaN stays that NaN. X'_t, L_t and the packed map replace the previous frame's, so a
+ * later nct_seq_frame blends against a propagated frame as against any other. The result is the finish of the last level run alone — nct_color_finish(X'_t[levels-1],
+ * h, w, sh, sw, S_t) — on the frame's own pixels. No VGG forward, normalise, NNF, PatchMatch, vote, k-means, kNN graph, T1, T2, S1 or re-predict is enqueued; tau and
+ * sigma play no part. A frame identical to the previous one returns the previous frame's bytes. Which frames are full ("key frames") is the caller's choice; a sequence
+ * that never propagates is unchanged in bytes, launches and arena size: the one scratch map the warp needs (48 B per pixel of the last level run, only with motion on) is
+ * reserved by the first propagated frame. No open sequence, or one without state (the first frame after nct_seq_begin / nct_seq_reset): NCT_ERR_STATE; a null image:
+ * NCT_ERR_INVALID; a refused call changes nothing, a frame that fails later leaves the sequence reset.
+ * nct_pair_timing of a propagated frame: vgg_ms, patchmatch_ms, vote_ms, knn_ms and pm_level_launches[] are 0; the finish counts in color_ms / wls_ms /
+ * wls_level_ms[levels-1] / wls_iters[levels-1]. nct_seq_frame_propagate_levels reports through nct_seq_levels: ab_blend[l] = X'_t[l], motion[l] = the field (zeros with
+ * motion off), tau_map[l] = 1.0 everywhere (the previous frame's weight).
+ * nct_seq_warp: the warp alone on host maps (synchronous): x_prev / x_out [2][h*w][3], field int16 [h*w][2] of (my, mx); a vector that leaves the grid is first clamped
+ * component-wise so that p + m is inside. nct_seq_warp_dev: the same on device pointers, enqueued; x_out must not overlap x_prev (the warp gathers): NCT_ERR_INVALID. */
 typedef struct nct_seq_params { double tau, sigma; } nct_seq_params;
 void nct_seq_params_default(nct_seq_params* p);     /* tau 0.7, sigma 10.0 */
 typedef struct nct_seq_levels { double* ab_blend[5]; double* tau_map[5]; int16_t* motion[5]; } nct_seq_levels;   /* X'_t [2][h*w][3]; tau_p [h*w]; m [h*w][2]; all nullable */
@@ -326,6 +340,8 @@ int nct_seq_set_motion(nct_ctx* ctx, const nct_seq_motion* motion);
 int nct_seq_begin(nct_ctx* ctx, const uint8_t* ref_bgr, int rh, int rw, int sh, int sw, const nct_params* prm, const nct_seq_params* seq);
 int nct_seq_frame(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing);
 int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels);
+int nct_seq_frame_propagate(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing);
+int nct_seq_frame_propagate_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* seq_levels);
 int nct_seq_reset(nct_ctx* ctx);   /* scene cut: the next frame is a first frame; the reference stays prepared */
 int nct_seq_end(nct_ctx* ctx);     /* frees the state; nct_destroy does it too */
 int nct_seq_blend(nct_ctx* ctx, const double* x, const double* x_prev, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, double tau, double sigma,
@@ -339,6 +355,8 @@ int nct_seq_blend_mc(nct_ctx* ctx, const double* x, const double* x_prev, const 
                      double* x_out, double* tau_map, const int16_t* field);
 int nct_seq_blend_mc_dev(nct_ctx* ctx, const double* d_x, const double* d_x_prev, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, double tau, double sigma,
                          double* d_x_out, double* d_tau_map, const int16_t* d_field);
+int nct_seq_warp(nct_ctx* ctx, const double* x_prev, int h, int w, const int16_t* field, double* x_out);
+int nct_seq_warp_dev(nct_ctx* ctx, const double* d_x_prev, int h, int w, const int16_t* d_field, double* d_x_out);
 
 /* ---- device-pointer seams: the same operations on buffers that stay in HBM between calls (main.cu:204-316 keeps Ndata_C1, ann_device, ... on the device
  * across these kernels; an integrator replacing single seams should not pay H2D + D2H + a synchronise per call). Buffers come from the context's arena

@@ -13,6 +13,10 @@
 // registers across the candidates; the previous frame's packed map (k_seq_pack, kept in the sequence state) is read through global memory at clamped addresses, the
 // out-of-grid taps masked out of cost and count. The candidate loops are uniform over the block (only the centre differs per pixel), the tap loops fully unrolled.
 // k_seq_blend<true> then reads L_(t-1) and X'_(t-1) at p + m(p): it gathers from other pixels, so x_out may be x but not x_prev.
+//
+// Propagated frames (SPEC §6.5). k_seq_warp moves the kept coefficients along a field: x_out(p) = x_prev(p + m(p)), the six 64-bit words of the pixel copied as integers
+// (a NaN keeps its payload). One thread per pixel: one short2, six gathered words in flight together, six plain stores; no LDS, no atomics. It gathers, so it runs out of
+// place. At 700 x 700 the finest level moves 47 MB + 2 MB of field: stream-bound there, launch-bound on the coarse levels.
 #include "nct_internal.h"
 #include "nct_device.h"
 
@@ -81,6 +85,21 @@ __global__ void __launch_bounds__(256) k_seq_pack(const uint8_t* __restrict__ la
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     out[i] = (uint32_t)lab[3 * i] | ((uint32_t)lab[3 * i + 1] << 8) | ((uint32_t)lab[3 * i + 2] << 16);
+}
+
+// SPEC §6.5 rule 3. The words stay in the colour stage's [2][n][3] layout; the vector is clamped component-wise as in k_seq_blend<true>
+__global__ void __launch_bounds__(256) k_seq_warp(const unsigned long long* __restrict__ x_prev, int h, int w, const short2* __restrict__ field, unsigned long long* __restrict__ x_out) {
+    const int n = h * w;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int y = i / w, px = i - y * w;
+    const short2 m = field[i];
+    const int ip = clampi(y + m.x, 0, h - 1) * w + clampi(px + m.y, 0, w - 1);
+    unsigned long long v[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) v[q] = x_prev[(size_t)(q / 3) * 3 * n + (size_t)3 * ip + q % 3];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) x_out[(size_t)(q / 3) * 3 * n + (size_t)3 * i + q % 3] = v[q];
 }
 
 #define MC_BW 32
@@ -191,6 +210,17 @@ int nctk_seq_motion(nct_ctx* ctx, hipStream_t s, const uint8_t* lab, const uint3
     NCT_REQUIRE(R >= 0 && R <= 8, "seq_motion: the search radius must be in [0, 8] (got %d)", R);
     NCT_REQUIRE(penalty >= 0 && penalty <= 255, "seq_motion: the penalty must be in [0, 255] (got %d)", penalty);
     hipLaunchKernelGGL(k_seq_motion, dim3(cdiv(w, MC_BW), cdiv(h, MC_BH)), dim3(MC_BW, MC_BH), 0, s, lab, prev_packed, h, w, (const short2*)parent, ph, pw, R, penalty, (short2*)m_out);
+    NCT_LAUNCH_CHECK();
+    return 0;
+}
+
+int nctk_seq_warp(nct_ctx* ctx, hipStream_t s, const double* x_prev, int h, int w, const int16_t* field, double* x_out) {
+    NCT_REQUIRE(x_prev && field && x_out, "seq_warp: null pointer");
+    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_warp: grid %dx%d out of range", w, h);
+    // the kernel reads x_prev at other pixels than the one it writes: any overlap of the two maps is refused
+    const size_t bytes = sizeof(double) * 6 * (size_t)h * w;
+    NCT_REQUIRE((const char*)x_out + bytes <= (const char*)x_prev || (const char*)x_prev + bytes <= (const char*)x_out, "seq_warp: x_out must not alias x_prev");
+    hipLaunchKernelGGL(k_seq_warp, dim3(cdiv(h * w, 256)), dim3(256), 0, s, (const unsigned long long*)x_prev, h, w, (const short2*)field, (unsigned long long*)x_out);
     NCT_LAUNCH_CHECK();
     return 0;
 }

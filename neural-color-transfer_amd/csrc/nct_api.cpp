@@ -368,6 +368,22 @@ int nct_seq_motion_field(nct_ctx* ctx, const uint8_t* lab, const uint8_t* lab_pr
     return NCT_OK;
 }
 
+// SPEC §6.5 rule 3 on host maps: the kept coefficients and the field up, one k_seq_warp launch out of place, the warped map down
+int nct_seq_warp(nct_ctx* ctx, const double* x_prev, int h, int w, const int16_t* field, double* x_out) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(x_prev && field && x_out, "seq_warp: null pointer");
+    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_warp: grid %dx%d out of range", w, h);
+    const size_t n = (size_t)h * w;
+    DevBuf<double> dp(ctx, 6 * n), dx(ctx, 6 * n);
+    DevBuf<int16_t> df(ctx, 2 * n);
+    if (!dp.ok() || !dx.ok() || !df.ok()) return NCT_ERR_HIP;
+    NCT_H2D(dp, x_prev, sizeof(double) * 6 * n); NCT_H2D(df, field, sizeof(int16_t) * 2 * n);
+    NCT_TRY(nctk_seq_warp(ctx, ctx->stream, dp, h, w, df, dx));
+    NCT_D2H(x_out, dx, sizeof(double) * 6 * n);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
 int nct_bds_vote_image(nct_ctx* ctx, const uint8_t* a_bgr, int ah, int aw, const uint8_t* b_bgr, int bh, int bw,
                        const uint32_t* ann, const uint32_t* bnn, int patch, double w_coherence, double w_complete, uint8_t* out_bgr) {
     NCT_CTX_ENTER();

@@ -208,6 +208,8 @@ int nctk_seq_blend(nct_ctx* ctx, hipStream_t s, const double* x, const double* x
 int nctk_seq_pack(nct_ctx* ctx, hipStream_t s, const uint8_t* lab, int n, uint32_t* out);
 int nctk_seq_motion(nct_ctx* ctx, hipStream_t s, const uint8_t* lab, const uint32_t* prev_packed, int h, int w, const int16_t* parent, int ph, int pw, int R, int penalty,
                     int16_t* m_out);
+// SPEC §6.5 rule 3: x_out(p) = x_prev(p + m(p)), the 64-bit words copied, a vector that leaves the grid clamped to it; x_out must not overlap x_prev
+int nctk_seq_warp(nct_ctx* ctx, hipStream_t s, const double* x_prev, int h, int w, const int16_t* field, double* x_out);
 // k_wls_mg.hip
 int nctk_wls_solve_mg(nct_ctx* ctx, hipStream_t s, double* X, const double* rough, const double* wx, const double* wy, int H, int W,
                       double rtol, int* iters_out);

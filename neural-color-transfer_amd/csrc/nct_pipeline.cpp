@@ -15,6 +15,7 @@
 // level) — and the state the blend carries from frame to frame, per level X' ([2][h*w][3] doubles) and L (the frame's level image in 8-bit Lab). All of it comes from
 // the context's arena and outlives the runs; the frame and the reference at working size are pair_state's src / ref[0] as for a pair.
 // While motion compensation is on (SPEC §6.4, nct_seq_set_motion) it also holds, per level, L packed one word per pixel and the level's field (4 B per level pixel each).
+// A propagated frame (SPEC §6.5) with motion on warps X' out of place: warp_x, one map of the largest level run, reserved by the first such frame.
 struct seq_state {
     nct_params prm; double tau = 0, sigma = 0;
     long frames = 0;                                           // frames since nct_seq_begin / nct_seq_reset: 0 = the next one is a first frame
@@ -23,6 +24,7 @@ struct seq_state {
     double* keep_x[5] = {}; uint8_t* keep_lab[5] = {};
     bool motion = false; nct_seq_motion mp = {0, 0, 0};
     uint32_t* keep_pk[5] = {}; int16_t* field[5] = {};
+    double* warp_x = nullptr;
 };
 struct pair_state {
     uint8_t *src = nullptr, *out = nullptr;                    // device BGR images
@@ -48,6 +50,7 @@ static void seq_motion_free(nct_ctx* ctx, seq_state* q) {
         if (q->keep_pk[l]) { ctx->release(q->keep_pk[l]); q->keep_pk[l] = nullptr; }
         if (q->field[l]) { ctx->release(q->field[l]); q->field[l] = nullptr; }
     }
+    if (q->warp_x) { ctx->release(q->warp_x); q->warp_x = nullptr; }
     q->motion = false;
 }
 // what an open sequence holds goes back to the arena
@@ -760,6 +763,89 @@ int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr,
 
 int nct_seq_frame(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing) {
     return nct_seq_frame_levels(ctx, src_bgr, out_bgr, timing, nullptr, nullptr);
+}
+
+// SPEC §6.5: what a propagated frame enqueues — the frame's pyramid, per level L_t and (motion on) the field, the warp of the kept X' and the packed map, then the
+// finish of the last level run on the kept X' and the frame's own pixels, and the download. Nothing upstream of the finish runs. L_t goes straight into the state:
+// on this path nothing reads L_(t-1) but the search, which reads its packed form
+static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* slv) {
+    const hipStream_t s = ctx->stream;
+    const nct_params& prm = q->prm;
+    const int H = P->sh, W = P->sw, top = prm.levels - 1;
+    const size_t N = (size_t)H * W;
+    MARK(NCT_ST_OTHER, 0);
+    DevBuf<uint8_t> s_lab_full(ctx, N * 3), out_lab(ctx, N * 3), spyr[4];
+    if (!s_lab_full.ok() || !out_lab.ok()) return NCT_ERR_HIP;
+    NCT_TRY(nctk_bgr2lab(ctx, s, P->src, s_lab_full, N));
+    const uint8_t* simg[5]; simg[4] = P->src;
+    for (int l = 3; l >= 0; --l) {
+        if (!spyr[l].alloc(ctx, (size_t)q->ah[l] * q->aw[l] * 3)) return NCT_ERR_HIP;
+        NCT_TRY(nctk_resize_u8c3(ctx, s, simg[l + 1], q->ah[l + 1], q->aw[l + 1], spyr[l], q->ah[l], q->aw[l]));
+        simg[l] = spyr[l];
+    }
+    MARK(NCT_ST_OTHER, 0);
+    if (q->motion && !q->warp_x && !(q->warp_x = (double*)ctx->alloc(sizeof(double) * 6 * (size_t)q->ah[top] * q->aw[top]))) return NCT_ERR_HIP;
+    if (!P->out) { P->out = (uint8_t*)ctx->alloc(N * 3); if (!P->out) return NCT_ERR_HIP; }
+    for (int l = 0; l <= top; ++l) {
+        const int h = q->ah[l], w = q->aw[l];
+        const size_t n = (size_t)h * w;
+        NCT_TRY(nctk_bgr2lab(ctx, s, simg[l], q->keep_lab[l], n));
+        if (q->motion) {
+            NCT_TRY(nctk_seq_motion(ctx, s, q->keep_lab[l], q->keep_pk[l], h, w, l > 0 ? q->field[l - 1] : nullptr, l > 0 ? q->ah[l - 1] : 0, l > 0 ? q->aw[l - 1] : 0,
+                                    l == 0 ? q->mp.radius0 : q->mp.radius, q->mp.penalty, q->field[l]));
+            NCT_TRY(nctk_seq_warp(ctx, s, q->keep_x[l], h, w, q->field[l], q->warp_x));
+            // the scratch has the last level's size: there the two maps change places, elsewhere the warped map is copied back
+            if (l == top) std::swap(q->keep_x[l], q->warp_x);
+            else NCT_HIP(hipMemcpyAsync(q->keep_x[l], q->warp_x, sizeof(double) * 6 * n, hipMemcpyDeviceToDevice, s));
+            NCT_TRY(nctk_seq_pack(ctx, s, q->keep_lab[l], (int)n, q->keep_pk[l]));
+        }
+        if (slv) {
+            if (slv->ab_blend[l]) NCT_HIP(hipMemcpyAsync(slv->ab_blend[l], q->keep_x[l], sizeof(double) * 6 * n, hipMemcpyDeviceToHost, s));
+            if (slv->motion[l]) {
+                if (q->motion) NCT_HIP(hipMemcpyAsync(slv->motion[l], q->field[l], sizeof(int16_t) * 2 * n, hipMemcpyDeviceToHost, s));
+                else memset(slv->motion[l], 0, sizeof(int16_t) * 2 * n);
+            }
+            if (slv->tau_map[l]) std::fill(slv->tau_map[l], slv->tau_map[l] + n, 1.0);          // the previous frame's weight
+        }
+    }
+    ctx->tm_level = top;
+    int wls_it[6] = {0, 0, 0, 0, 0, 0};
+    const nct_color_debug dbg{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, wls_it};
+    const nct_color_params cp{prm.eps, prm.nonlocal_weight, prm.local_weight, prm.wls_lambda_init, prm.wls_alpha, (double)prm.k_num};
+    NCT_TRY(nctk_color_finish(ctx, s, q->keep_x[top], q->ah[top], q->aw[top], H, W, s_lab_full, H, W, cp, out_lab, timing ? &dbg : nullptr));
+    NCT_TRY(nctk_lab2bgr(ctx, s, out_lab, P->out, N, (prm.flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0));
+    if (timing) timing->wls_iters[top] = *std::max_element(wls_it, wls_it + 6);
+    MARK(NCT_ST_COLOR, top);
+    NCT_D2H(out_bgr, P->out, N * 3);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
+int nct_seq_frame_propagate_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* seq_levels) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_frame_propagate: no sequence is open (nct_seq_begin first)");
+    seq_state* q = P->seq;
+    if (q->frames == 0) return ctx->fail(NCT_ERR_STATE, "seq_frame_propagate: the sequence has no state to propagate (the first frame after nct_seq_begin / nct_seq_reset is nct_seq_frame's)");
+    NCT_REQUIRE(src_bgr && out_bgr, "seq_frame_propagate: null image");
+    if (timing) memset(timing, 0, sizeof *timing);
+    const auto wall0 = std::chrono::steady_clock::now();
+    ctx->tm_on = timing != nullptr; ctx->tm_tags.clear(); ctx->tm_host.clear();
+    ctx->kt_on = timing != nullptr && (q->prm.flags & NCT_FLAG_TIME_KERNELS) != 0; ctx->kt_ids.clear();
+    ctx->wls_split = (q->prm.flags & NCT_FLAG_LATENCY) ? 1 : 0;
+    int rc = hipMemcpyAsync(P->src, src_bgr, (size_t)P->sh * P->sw * 3, hipMemcpyHostToDevice, ctx->stream) == hipSuccess ? NCT_OK : ctx->fail(NCT_ERR_HIP, "seq_frame_propagate: upload failed");
+    if (rc == NCT_OK) rc = propagate_run(ctx, P, q, out_bgr, timing, seq_levels);
+    ctx->tm_on = false; ctx->kt_on = false;
+    // a frame that failed may have replaced the state of some levels only: the next frame starts over
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); q->frames = 0; return rc; }
+    q->frames += 1;
+    if (!timing) return NCT_OK;
+    timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    return read_timing(ctx, timing, false);
+}
+
+int nct_seq_frame_propagate(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing) {
+    return nct_seq_frame_propagate_levels(ctx, src_bgr, out_bgr, timing, nullptr);
 }
 
 int nct_working_size(int h, int w, int max_side, int* work_h, int* work_w) {

@@ -10,6 +10,7 @@
 // and pairs.txt lines whose second token lists several references separated by commas (SPEC §6.2: every pixel takes its colours from the reference that matches it best),
 // `-seq 1` (+ `-tau`, `-sigma`): consecutive lines with one and the same reference are the frames of a sequence, graded with temporally blended coefficients (SPEC §6.3).
 // `-motion 1` (+ `-mr0`, `-mr`, `-mpen`): the blend of a sequence follows the motion between the frames (SPEC §6.4).
+// `-key N`: only every N-th frame of a sequence runs the whole pair; the others are propagated from the frame before them (SPEC §6.5).
 #include <sys/stat.h>
 #include <sys/wait.h>
 #include <fcntl.h>
@@ -112,7 +113,7 @@ std::string stem(const std::string& path) {          // main.cu:524-531 (find_la
 struct Pair { std::string cnt, stl; float bds; std::vector<std::string> refs; std::string err; };
 std::mutex g_print;
 
-struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false, fullres = false, seq = false, motion = false; nct_seq_params sp; nct_seq_motion mp; int rank = 0, world = 1; };
+struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false, fullres = false, seq = false, motion = false; nct_seq_params sp; nct_seq_motion mp; int key = 1; int rank = 0, world = 1; };
 
 // ---- ENABLE_VIS debug outputs (Config.h:8) behind the runtime flag -vis 1: per pyramid level the flow maps of both NNFs (reconstruct_flow,
 // GeneralizedPatchMatch.cu:337-353), the level images tCnt / tStl (main.cu:343-347), the matching-error heat map (getHeat,
@@ -458,7 +459,8 @@ std::vector<Group> plan_groups(const std::vector<Pair>& pairs) {
 
 // one sequence on one context, its frames in file order. The reference is decoded and shrunk once; a frame whose (shrunk) size differs from the open sequence's begins
 // a new one at that frame; a line that cannot be decoded is skipped and the state continues from the last good frame; with -resume 1 the sequence is skipped only if
-// every output is complete, else it is redone from its first frame. Returns the number of lines it finished
+// every output is complete, else it is redone from its first frame. With -key N the k-th frame run since the last nct_seq_begin is a full frame iff k % N == 0 and a
+// propagated one (SPEC §6.5) otherwise; a frame that failed left the sequence reset, so the next one is full. Returns the number of lines it finished
 size_t run_sequence(nct_ctx* ctx, const Config& cfg, const std::vector<Pair>& pairs, const Group& g) {
     nct_params prm = cfg.prm;
     prm.bds_weight = pairs[g.first].bds;
@@ -476,6 +478,7 @@ size_t run_sequence(nct_ctx* ctx, const Config& cfg, const std::vector<Pair>& pa
     }
     ImageBGR ref; std::string ref_err; bool ref_tried = false, open = false;
     int fh = 0, fw = 0;
+    long k = 0;                                                            // frames run since the last nct_seq_begin
     for (size_t i = g.first; i < g.first + g.count; ++i) {
         Job j; j.index = i; j.p = pairs[i];
         load_pair(cfg, j, true);
@@ -494,7 +497,7 @@ size_t run_sequence(nct_ctx* ctx, const Config& cfg, const std::vector<Pair>& pa
             int rc = NCT_OK;
             if (!open || j.cnt.h != fh || j.cnt.w != fw) {
                 rc = nct_seq_begin(ctx, ref.px.data(), ref.h, ref.w, j.cnt.h, j.cnt.w, &prm, &cfg.sp);
-                open = rc == NCT_OK; fh = j.cnt.h; fw = j.cnt.w;
+                open = rc == NCT_OK; fh = j.cnt.h; fw = j.cnt.w; k = 0;
                 if (open) j.say("Sequence %ld: begins at this frame (%d x %d, tau = %g, sigma = %g).\n", g.seq, fw, fh, cfg.sp.tau, cfg.sp.sigma);
                 if (open && cfg.motion) {
                     rc = nct_seq_set_motion(ctx, &cfg.mp);
@@ -504,7 +507,10 @@ size_t run_sequence(nct_ctx* ctx, const Config& cfg, const std::vector<Pair>& pa
             }
             nct_pair_timing tm;
             j.out.resize((size_t)j.cnt.h * j.cnt.w * 3);
-            if (rc == NCT_OK) rc = nct_seq_frame(ctx, j.cnt.px.data(), j.out.data(), &tm);
+            const bool prop = k % cfg.key != 0;
+            if (rc == NCT_OK && prop) j.say("Sequence %ld: frame %ld is propagated from the frame before it (-key %d).\n", g.seq, k, cfg.key);
+            if (rc == NCT_OK) rc = prop ? nct_seq_frame_propagate(ctx, j.cnt.px.data(), j.out.data(), &tm) : nct_seq_frame(ctx, j.cnt.px.data(), j.out.data(), &tm);
+            k = rc == NCT_OK ? k + 1 : 0;
             if (rc != NCT_OK) { j.say("Error: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; }
             else { log_times(j, prm, tm); store_pair(j); }
         }
@@ -640,7 +646,7 @@ int main(int argc, char** argv) {
     nct_params_default(&cfg.prm);
     nct_seq_params_default(&cfg.sp);
     nct_seq_motion_default(&cfg.mp);
-    int motion = 0;
+    int motion = 0, key = 1;
     int gpu = 0, ngpus = 1, seed = 1, inflight = 1, levels = 5, resume = 0, feat16 = 0, vis = 0, fullres = 0, seq = 0, io = -1, pin = 1, world = 1, rank = 0, steal = 0, procs = 0, rccl = 0;
     cl.add("m", cfg.model_dir, "Directory of network models.");
     cl.add("i", cfg.input_dir, "Input directory of content and style images and pairs.txt.");
@@ -675,6 +681,7 @@ int main(int argc, char** argv) {
     cl.add("mr0", cfg.mp.radius0, "[extension] -motion 1: search radius at the coarsest level, in [0, 8].");
     cl.add("mr", cfg.mp.radius, "[extension] -motion 1: search radius of the refinement at every finer level, in [0, 3].");
     cl.add("mpen", cfg.mp.penalty, "[extension] -motion 1: cost per tap and pixel of displacement from the search centre, in [0, 255].");
+    cl.add("key", key, "[extension] -seq 1: N in [1, 1000]: within a sequence only every N-th frame runs the whole pair; the frames between take their colour coefficients from the frame before them through the motion field and run the last level's finish only (SPEC 6.5). 1 = every frame is a full frame.");
     // parser self-test hook (no GPU): `--parse-only <args…>` parses the rest like a normal run and prints what main would go on with, in the format of
     // oracle/ref_cmdline.cpp (the reference's own parser): tests/test_cli.py compares the two on the vectors of tests/golden/cmdline_ref.json
     // job-planning hook (no GPU): `--plan-only <args…>` goes as far as a normal run goes before it creates a context and prints, per pairs.txt line, what it would run
@@ -700,6 +707,8 @@ int main(int argc, char** argv) {
     if (motion && (cfg.mp.radius0 < 0 || cfg.mp.radius0 > 8)) { printf("Error: -mr0 %d is not in [0, 8].\n", cfg.mp.radius0); return -1; }
     if (motion && (cfg.mp.radius < 0 || cfg.mp.radius > 3)) { printf("Error: -mr %d is not in [0, 3].\n", cfg.mp.radius); return -1; }
     if (motion && (cfg.mp.penalty < 0 || cfg.mp.penalty > 255)) { printf("Error: -mpen %d is not in [0, 255].\n", cfg.mp.penalty); return -1; }
+    if (key < 1 || key > 1000) { printf("Error: -key %d is not in [1, 1000].\n", key); return -1; }
+    if (key > 1 && !seq) { printf("Error: -key %d needs -seq 1 (propagated frames belong to a sequence).\n", key); return -1; }
     if (!plan_only) mkdir(cfg.output_dir.c_str(), 0777);                    // main.cu:458
     uint64_t run_token = getenv("NCT_RUN_TOKEN") ? strtoull(getenv("NCT_RUN_TOKEN"), nullptr, 0) : 0;      // hand-started ranks of one run share it (and remove <output>/.rccl_id between runs)
     const std::string tickets_path = cfg.output_dir + "/.tickets";
@@ -736,6 +745,7 @@ int main(int argc, char** argv) {
     cfg.fullres = fullres != 0;
     cfg.seq = seq != 0;
     cfg.motion = motion != 0;
+    cfg.key = key;
     if (ngpus < 1) ngpus = 1;
     if (inflight < 1) inflight = 1;
     if (inflight > 8) inflight = 8;
@@ -753,9 +763,9 @@ int main(int argc, char** argv) {
     fclose(fp);
     const std::vector<Group> groups = cfg.seq ? plan_groups(pairs) : std::vector<Group>();
     if (plan_only) {
-        std::vector<std::string> seq_of(pairs.size());               // -seq 1: " seq=<sequence>:<index>" behind the lines that are frames
+        std::vector<std::string> seq_of(pairs.size());               // -seq 1: " seq=<sequence>:<index>" behind the lines that are frames, -key N: " prop" behind the propagated ones
         for (const Group& g : groups)
-            if (g.seq >= 0) for (size_t i = 0; i < g.count; ++i) seq_of[g.first + i] = " seq=" + std::to_string(g.seq) + ":" + std::to_string(i);
+            if (g.seq >= 0) for (size_t i = 0; i < g.count; ++i) seq_of[g.first + i] = " seq=" + std::to_string(g.seq) + ":" + std::to_string(i) + (i % (size_t)cfg.key ? " prop" : "");
         for (size_t i = 0; i < pairs.size(); ++i) {
             const Pair& p = pairs[i];
             const std::string why = refusal(cfg, p);

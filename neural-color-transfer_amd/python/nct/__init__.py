@@ -38,7 +38,7 @@ def lib():
     return _lib
 
 
-NCT_VERSION = 113        # include/nct.h
+NCT_VERSION = 114        # include/nct.h
 MAX_REFS = 8             # NCT_MAX_REFS
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -104,6 +104,10 @@ SIGNATURES = {
     "nct_seq_begin": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nct_seq_frame": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p]),
     "nct_seq_frame_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_frame_propagate": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p]),
+    "nct_seq_frame_propagate_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p]),
+    "nct_seq_warp": (C.c_int, [C.c_void_p, _f64p, C.c_int, C.c_int, C.c_void_p, _f64p]),
+    "nct_seq_warp_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nct_seq_reset": (C.c_int, [C.c_void_p]),
     "nct_seq_end": (C.c_int, [C.c_void_p]),
     "nct_seq_blend": (C.c_int, [C.c_void_p, _f64p, _f64p, _u8p, _u8p, C.c_int, C.c_int, C.c_double, C.c_double, _f64p, C.c_void_p]),
@@ -750,6 +754,70 @@ class Context:
         keep["ab_blend"] = ab_blend; keep["tau_map"] = tau_map; keep["motion"] = motion
         keep["timing"] = tm.as_dict(); keep["dims"] = dims
         return out, keep
+
+    def _seq_frame_arg(self, src_bgr, what):
+        s = np.ascontiguousarray(src_bgr, np.uint8)
+        shp = getattr(self, "_seq_shapes", None)
+        if shp is not None and tuple(s.shape[:2]) != tuple(shp[0]):
+            raise NctError(-2, "%s: the frame is %dx%d, the sequence was begun for %dx%d" % (what, s.shape[1], s.shape[0], shp[0][1], shp[0][0]))
+        return s
+
+    def seq_frame_propagate(self, src_bgr, want_timing=False):
+        """nct_seq_frame_propagate (SPEC §6.5): the frame takes the previous frame's coefficients through the motion field and runs the last level's finish only"""
+        s = self._seq_frame_arg(src_bgr, "seq_frame_propagate")
+        out = np.empty_like(s)
+        tm = PairTiming() if want_timing else None
+        self._chk(self._l.nct_seq_frame_propagate(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
+        return (out, tm.as_dict()) if want_timing else out
+
+    def seq_frame_propagate_levels(self, src_bgr):
+        """nct_seq_frame_propagate_levels -> (result, dict): per level that ran "ab_blend" (X'_t [2, h*w, 3]), "motion" (int16 [h, w, 2]; zeros with motion off) and
+        "tau_map" (1.0 everywhere), plus "timing" and "dims" (the source's level grids)"""
+        s = self._seq_frame_arg(src_bgr, "seq_frame_propagate_levels")
+        shp = getattr(self, "_seq_shapes", None)
+        if shp is None:                                        # no open sequence: the library refuses; the maps are never written
+            shp = (s.shape[:2], None, 0)
+        levels = shp[2]
+        dims = []
+        h, w = s.shape[:2]
+        for _ in range(5):
+            dims.insert(0, (h, w))
+            h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        ab_blend = [np.zeros((2, ah * aw, 3)) for (ah, aw) in dims[:levels]]
+        tau_map = [np.zeros((ah, aw)) for (ah, aw) in dims[:levels]]
+        motion = [np.zeros((ah, aw, 2), np.int16) for (ah, aw) in dims[:levels]]
+        sl = SeqLevels()
+        for l in range(levels):
+            sl.ab_blend[l] = ab_blend[l].ctypes.data; sl.tau_map[l] = tau_map[l].ctypes.data; sl.motion[l] = motion[l].ctypes.data
+        out = np.empty_like(s)
+        tm = PairTiming()
+        self._chk(self._l.nct_seq_frame_propagate_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(sl)))
+        return out, {"ab_blend": ab_blend, "tau_map": tau_map, "motion": motion, "timing": tm.as_dict(), "dims": dims}
+
+    def seq_warp(self, x_prev, field):
+        """nct_seq_warp (SPEC §6.5 rule 3): x_prev [2, h*w, 3] doubles, field int16 [h, w, 2] of (my, mx) -> x_prev read at p + m(p), the 64-bit words copied"""
+        f = np.ascontiguousarray(field, np.int16)
+        h, w = f.shape[:2]
+        a = np.ascontiguousarray(x_prev, np.float64).reshape(-1)
+        assert a.size == 6 * h * w and f.size == 2 * h * w
+        out = np.empty((2, h * w, 3))
+        self._chk(self._l.nct_seq_warp(self._h, a, h, w, f.ctypes.data, out.reshape(-1)))
+        return out
+
+    def seq_warp_dev(self, x_prev, field, alias=False):
+        """the same through nct_seq_warp_dev on arena blocks, into a block of its own (alias: into x_prev's block, which is an error)"""
+        f = np.ascontiguousarray(field, np.int16)
+        h, w = f.shape[:2]
+        n = h * w
+        ins = [self.dev_upload(np.ascontiguousarray(x_prev, np.float64).reshape(-1)), self.dev_upload(f)]
+        do = self.dev_alloc(48 * n)
+        try:
+            self._chk(self._l.nct_seq_warp_dev(self._h, ins[0], h, w, ins[1], ins[0] if alias else do))
+            return self.dev_download(do, (2, n, 3), np.float64)
+        finally:
+            self.synchronize()
+            for p in ins + [do]:
+                self.dev_free(p)
 
     def seq_reset(self):
         self._chk(self._l.nct_seq_reset(self._h))
