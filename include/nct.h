@@ -27,9 +27,10 @@ extern "C" {
 
 /* bumped whenever a struct of this header changes layout or an entry point changes meaning (round 6: 110 — nct_model_layer; nct_pair_timing grew in round 5 without a
  * bump; 111 — nct_multi_levels and the entry points for several references; 112 — frame sequences, nct_seq_*; 113 — nct_seq_levels.motion and motion-compensated
- * sequences, nct_seq_set_motion; 114 — propagated frames, nct_seq_frame_propagate and nct_seq_warp). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
+ * sequences, nct_seq_set_motion; 114 — propagated frames, nct_seq_frame_propagate and nct_seq_warp; 115 — the single-layer conv seams nct_conv3x3_dev and
+ * nct_conv3x3_pair_dev). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
-#define NCT_VERSION 114
+#define NCT_VERSION 115
 
 typedef enum {
     NCT_OK = 0,
@@ -387,6 +388,16 @@ int nct_bds_vote_features_dev(nct_ctx* ctx, const uint32_t* ann, const uint32_t*
 int nct_bds_vote_image_dev(nct_ctx* ctx, const uint8_t* b_bgr, const uint32_t* ann, const uint32_t* bnn, int ah, int aw, int bh, int bw, int patch,
                            double w_coherence, double w_complete, uint8_t* out_bgr);                                                                   /* main.cu:291 */
 int nct_feature_distance_dev(nct_ctx* ctx, const float* a_hwc, const float* b_hwc, float* err, int C, int H, int W);                                  /* main.cu:316 */
+/* One 3x3 / pad 1 / stride 1 conv layer (+ bias, ReLU if `relu`) through the launcher the VGG forward uses, with every store form of its kernel: d_out_chw planar [Cout][H][W],
+ * d_out_hwc channel-last [H*W][Cout], either or both (one may be null); pool = 1: d_out_chw receives only the 2x2/2 ceil-mode max-pooled map [Cout][(H-1)/2+1][(W-1)/2+1]
+ * and d_out_hwc must be null. d_weights: Caffe layout [Cout][Cin][3][3] on the device (packed by the call into an arena block of its own), d_bias [Cout]. Cout % 64 == 0,
+ * 1 <= H, W < 4096. The kernel consumes input channels in pairs: for an odd Cin, d_in must hold Cin + 1 planes and the CALLER zeroes the last one (the call neither copies nor writes
+ * the input). nct_conv3x3_pair_dev: the same layer for two maps of different size; one launch where both grids are too small to fill the GPU (and NCT_CONV_PAIR is not 0),
+ * two launches otherwise; the bits are the same either way. Per map one of the two outputs may be null. No pooling. */
+int nct_conv3x3_dev(nct_ctx* ctx, const float* d_in, const float* d_weights, const float* d_bias, int Cin, int Cout, int H, int W, int relu, int pool,
+                    float* d_out_chw, float* d_out_hwc);
+int nct_conv3x3_pair_dev(nct_ctx* ctx, const float* d_in1, int H1, int W1, const float* d_in2, int H2, int W2, const float* d_weights, const float* d_bias, int Cin, int Cout,
+                         int relu, float* d_out1, float* d_out2, float* d_hwc1, float* d_hwc2);
 
 /* ---- measurement hooks (bench.py / rocprof): device-resident PatchMatch on synthetic features ----
  * nct_pm_bench_setup uploads + normalises two CHW feature maps once; nct_pm_bench_run re-initialises the NNF

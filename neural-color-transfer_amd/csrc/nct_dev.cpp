@@ -62,6 +62,42 @@ int nct_vgg19_features_hwc_dev(nct_ctx* ctx, const uint8_t* d_bgr, int h, int w,
     return nctk_vgg19_forward(ctx, ctx->stream, d_bgr, h, w, stride, deepest_tap, d_taps_chw, dims, d_taps_hwc);
 }
 
+// One 3x3 / pad 1 / stride 1 conv layer of the VGG stage through the launcher the forward uses (nctk_conv3x3: same dispatch over the four tile forms), every epilogue
+// reachable: planar (d_out_chw), channel-last (d_out_hwc), both, or pool = 1 (d_out_chw receives only the 2x2/2 ceil-mode pooled map). d_weights in Caffe layout
+// [Cout][Cin][3][3]; packed here into an arena block that goes back in stream order. The kernel consumes channels in pairs: for odd Cin the CALLER's d_in holds Cin + 1
+// planes, the last one zero (the packed weights of that channel are zero, but 0 * inf is not) — the forward's preprocess writes conv1_1's fourth plane the same way.
+static int conv_pack(nct_ctx* ctx, const float* d_weights, int Cin, int Cout, DevBuf<float>& wp) {
+    const int cin_pad = (Cin + 1) & ~1;
+    if (!wp.alloc(ctx, (size_t)cin_pad * 9 * Cout)) return NCT_ERR_HIP;
+    return nctk_pack_weights(ctx, ctx->stream, d_weights, wp, Cout, Cin, cin_pad);
+}
+int nct_conv3x3_dev(nct_ctx* ctx, const float* d_in, const float* d_weights, const float* d_bias, int Cin, int Cout, int H, int W, int relu, int pool,
+                    float* d_out_chw, float* d_out_hwc) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(d_in && d_weights && d_bias, "conv3x3_dev: null pointer");
+    NCT_REQUIRE(Cin >= 1 && Cout >= 64 && H >= 1 && W >= 1 && H < 4096 && W < 4096, "conv3x3_dev: Cin=%d Cout=%d map %dx%d out of range", Cin, Cout, W, H);
+    NCT_REQUIRE(d_out_chw || d_out_hwc, "conv3x3: no output");                        // nctk_conv3x3's own refusals, repeated in front of the packing launch
+    NCT_REQUIRE(!(pool && d_out_hwc), "conv3x3: the channel-last output exists for un-pooled layers only");
+    NCT_REQUIRE((Cout & 63) == 0, "conv3x3: Cout=%d must be a multiple of 64", Cout);
+    DevBuf<float> wp;
+    NCT_TRY(conv_pack(ctx, d_weights, Cin, Cout, wp));
+    return nctk_conv3x3(ctx, ctx->stream, d_in, wp, d_bias, d_out_chw, (Cin + 1) & ~1, Cout, H, W, relu, pool ? 1 : 0, d_out_hwc);
+}
+// The same layer for two images of different geometry (conv5_1 of the source and the reference in the pipeline): one launch where both grids are small and the context's
+// conv_pair switch (NCT_CONV_PAIR) allows it, two launches otherwise — nctk_conv3x3_pair decides, as for the pipeline. Per image one of the two outputs may be null.
+int nct_conv3x3_pair_dev(nct_ctx* ctx, const float* d_in1, int H1, int W1, const float* d_in2, int H2, int W2, const float* d_weights, const float* d_bias, int Cin, int Cout,
+                         int relu, float* d_out1, float* d_out2, float* d_hwc1, float* d_hwc2) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(d_in1 && d_in2 && d_weights && d_bias, "conv3x3_pair_dev: null pointer");
+    NCT_REQUIRE(Cin >= 1 && Cout >= 64 && H1 >= 1 && W1 >= 1 && H2 >= 1 && W2 >= 1 && H1 < 4096 && W1 < 4096 && H2 < 4096 && W2 < 4096,
+                "conv3x3_pair_dev: Cin=%d Cout=%d maps %dx%d, %dx%d out of range", Cin, Cout, W1, H1, W2, H2);
+    NCT_REQUIRE((d_out1 || d_hwc1) && (d_out2 || d_hwc2), "conv3x3: no output");
+    NCT_REQUIRE((Cout & 63) == 0, "conv3x3: Cout=%d must be a multiple of 64", Cout);
+    DevBuf<float> wp;
+    NCT_TRY(conv_pack(ctx, d_weights, Cin, Cout, wp));
+    return nctk_conv3x3_pair(ctx, ctx->stream, d_in1, H1, W1, d_in2, H2, W2, wp, d_bias, d_out1, d_out2, (Cin + 1) & ~1, Cout, relu, d_hwc1, d_hwc2);
+}
+
 // N1: norm (main.cu:265,274,313)
 int nct_feat_normalize_dev(nct_ctx* ctx, const float* src_hwc, float* dst_hwc, float* resp, int C, int H, int W) {
     NCT_CTX_ENTER();

@@ -118,6 +118,10 @@ int nctk_nnf_upsample(nct_ctx* ctx, hipStream_t s, const uint32_t* nnf_half, uin
 int nctk_patchmatch(nct_ctx* ctx, hipStream_t s, const float* a_hwc, const float* b_hwc, int C, int ah, int aw, int bh, int bw,
                     int iters, int rs_max, uint32_t seed, uint32_t* nnf, float* dist, unsigned long long* eval_counter /*nullable*/);
 // k_vgg.hip / nct_vgg.cpp
+// one conv layer: in = Cin (even: a zero pad plane for an odd layer) planar maps, wp = weights packed by nctk_pack_weights; out (planar; pool = 1: only the 2x2/2 pooled map) and
+// out_hwc (channel-last, pool == 0 only) are each nullable, not both
+int nctk_conv3x3(nct_ctx* ctx, hipStream_t s, const float* in, const float* wp, const float* bias, float* out, int Cin, int Cout, int H, int W, int relu, int pool, float* out_hwc = nullptr);
+int nctk_pack_weights(nct_ctx* ctx, hipStream_t s, const float* w /*[Cout][Cin][3][3]*/, float* wp /*[Cin_pad*9][Cout]*/, int Cout, int Cin, int Cin_pad);
 int nctk_conv3x3_pair(nct_ctx* ctx, hipStream_t s, const float* in1, int H1, int W1, const float* in2, int H2, int W2, const float* wp, const float* bias,
                       float* out1, float* out2, int Cin, int Cout, int relu, float* hwc1, float* hwc2);
 // both images to conv5_1 (channel-last taps only), the last layer for both in one launch

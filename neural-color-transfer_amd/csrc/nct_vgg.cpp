@@ -16,11 +16,9 @@
 #include <fcntl.h>
 #include <unistd.h>
 
-int nctk_conv3x3(nct_ctx*, hipStream_t, const float* in, const float* wp, const float* bias, float* out, int Cin, int Cout, int H, int W, int relu, int pool, float* out_hwc = nullptr);
 bool nctk_conv3x3_pool_fits(int H, int W);
 int nctk_maxpool2x2(nct_ctx*, hipStream_t, const float* in, float* out, int C, int H, int W);
 int nctk_vgg_preprocess(nct_ctx*, hipStream_t, const uint8_t* bgr, int stride, float* out, int H, int W);
-int nctk_pack_weights(nct_ctx*, hipStream_t, const float* w, float* wp, int Cout, int Cin, int Cin_pad);
 
 static const int NCONV = 16;
 static const char* const kConvName[NCONV] = {"conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv3_4",

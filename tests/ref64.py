@@ -48,6 +48,29 @@ def vgg19_taps(bgr, ws, bs, deepest=5):
     return taps
 
 
+def conv3x3(x, w, b, relu=True):
+    """One Caffe convolution layer, 3x3, pad 1, stride 1 (conv_layer.cpp: out = sum_ci sum_taps w * in + bias), optionally followed by ReLU, in float64 with
+    torch.nn.functional on the CPU. x: [Cin][H][W], w: [Cout][Cin][3][3], b: [Cout]. Returns (y, M): the map and the magnitude map M = conv(|x|, |w|) + |b|, the sum of
+    the absolute values of everything that is added up for an output element — what a rounding-error bound of that sum is proportional to (ReLU moves no bound:
+    |max(a, 0) - max(b, 0)| <= |a - b|)."""
+    import torch
+    import torch.nn.functional as F
+    xt, wt, bt = (torch.from_numpy(np.array(a, np.float64)) for a in (x, w, b))          # copies: the caller's arrays may be read-only
+    xt = xt[None]
+    y = F.conv2d(xt, wt, bt, padding=1)
+    if relu:
+        y = F.relu(y)
+    m = F.conv2d(xt.abs(), wt.abs(), bt.abs(), padding=1)
+    return y[0].numpy().copy(), m[0].numpy().copy()
+
+
+def maxpool2x2_ceil(x):
+    """Caffe's MAX pooling, kernel 2, stride 2, pad 0 (pooling_layer.cpp:90-93 ceil mode, :153-170 windows clipped to the map), float64. x: [C][H][W]."""
+    import torch
+    import torch.nn.functional as F
+    return F.max_pool2d(torch.from_numpy(np.array(x, np.float64))[None], 2, 2, ceil_mode=True)[0].numpy().copy()
+
+
 def pool_out(n):
     """pooling_layer.cpp:90-93 for kernel 2, stride 2, pad 0: ceil((n - 2) / 2) + 1"""
     return int(np.ceil((n - 2) / 2.0)) + 1

@@ -1,5 +1,9 @@
 """GPU parity for VGG19 (V1 caffemodel ingest, V2 features): f32-MFMA conv is a k-ordered fmaf chain, so the bar is
-BIT-EXACT vs oracle/orc_vgg.c (which itself is pinned to Caffe's known answers and torch in tests/test_oracle_vgg.py)."""
+BIT-EXACT vs oracle/orc_vgg.c (which itself is pinned to Caffe's known answers and torch in tests/test_oracle_vgg.py).
+
+test_conv3x3_bit_exact goes through nct_conv3x3_relu and so reaches the PLANAR store of the conv kernel only (in all four tile forms); the whole forwards here are small enough
+that every pooled or channel-last layer runs in a CT = 1 form. The other epilogues — channel-last, fused pool, both in the CT = 2 forms that production sizes take — and the paired
+launch are pinned form by form in tests/test_gpu_conv_forms.py, against the oracle and a float64 reference."""
 import os
 import numpy as np
 import pytest
