@@ -11,13 +11,24 @@ static std::string g_create_err;
 void nct_set_ctxless_error(const char* msg) { g_create_err = msg; }   // the message of a failed entry point that takes no context (nct_last_error(NULL))
 void nct_vgg_free(nct_ctx* ctx);   // nct_vgg.cpp
 
+// NCT_ARENA_FILL: the whole block (its cached size, not the request) is set to the fill byte. Blocks are recycled in stream order over three streams, so the
+// fill waits for every queued kernel that may still use the block and is complete before any stream touches it
+static void* arena_filled(nct_ctx* c, void* p, size_t block_bytes) {
+    if (c->arena_fill < 0) return p;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemset(p, c->arena_fill, block_bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { c->release(p); c->fail(NCT_ERR_HIP, "NCT_ARENA_FILL: filling a block of %zu bytes failed: %s", block_bytes, hipGetErrorString(e)); return nullptr; }
+    return p;
+}
+
 void* nct_ctx::alloc(size_t bytes) {
     if (bytes == 0) bytes = 16;
     bytes = (bytes + 255) & ~(size_t)255;
     int best = -1;
     for (size_t i = 0; i < blocks.size(); ++i)
         if (!blocks[i].used && blocks[i].bytes >= bytes && (best < 0 || blocks[i].bytes < blocks[best].bytes)) best = (int)i;
-    if (best >= 0 && blocks[best].bytes <= bytes * 2 + (1u << 20)) { blocks[best].used = true; return blocks[best].p; }
+    if (best >= 0 && blocks[best].bytes <= bytes * 2 + (1u << 20)) { blocks[best].used = true; return arena_filled(this, blocks[best].p, blocks[best].bytes); }
     void* p = nullptr;
     hipError_t e = hipMalloc(&p, bytes);
     if (e != hipSuccess) {
@@ -27,9 +38,9 @@ void* nct_ctx::alloc(size_t bytes) {
         if (e != hipSuccess) { fail(NCT_ERR_HIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); return nullptr; }
     }
     bytes_allocated += bytes;
-    for (auto& b : blocks) if (!b.p) { b = {p, bytes, true}; return p; }
+    for (auto& b : blocks) if (!b.p) { b = {p, bytes, true}; return arena_filled(this, p, bytes); }
     blocks.push_back({p, bytes, true});
-    return p;
+    return arena_filled(this, p, bytes);
 }
 int nct_ctx::mark(hipStream_t s, int tag) {
     if (!tm_on) return 0;
@@ -107,6 +118,7 @@ int nct_create(int device, nct_ctx** out) {
     if (const char* q = getenv("NCT_S1_HUB_HINT")) { const int v = atoi(q); if (v == 0 || v == 1) c->s1_hub_hint = v; }
     if (const char* m = getenv("NCT_WLS_MAXIT")) { const int v = atoi(m); if (v > 0) c->wls_maxit = v; }
     if (const char* m = getenv("NCT_S1_MAXIT")) { const int v = atoi(m); if (v > 0) c->s1_maxit = v; }
+    if (const char* m = getenv("NCT_ARENA_FILL")) { char* end = nullptr; const long v = strtol(m, &end, 0); if (end != m && *end == 0 && v >= 0 && v <= 255) c->arena_fill = (int)v; }
     *out = c;
     return NCT_OK;
 }

@@ -22,6 +22,7 @@ struct nct_ctx {
     std::string err;
     std::vector<nct_block> blocks;    // cached device allocations, reused across calls and pairs
     size_t bytes_allocated = 0;
+    int arena_fill = -1;              // test hook (env NCT_ARENA_FILL=0..255): alloc() fills the whole block it hands out with this byte; -1 = off
     // measurement fixture (nct_pm_bench_*)
     float *bench_a = nullptr, *bench_b = nullptr; void *bench_ah16 = nullptr, *bench_bh16 = nullptr; int bench_C = 0, bench_ah = 0, bench_aw = 0, bench_bh = 0, bench_bw = 0;
     // opaque sub-states owned by other translation units
