@@ -28,9 +28,9 @@ extern "C" {
 /* bumped whenever a struct of this header changes layout or an entry point changes meaning (round 6: 110 — nct_model_layer; nct_pair_timing grew in round 5 without a
  * bump; 111 — nct_multi_levels and the entry points for several references; 112 — frame sequences, nct_seq_*; 113 — nct_seq_levels.motion and motion-compensated
  * sequences, nct_seq_set_motion; 114 — propagated frames, nct_seq_frame_propagate and nct_seq_warp; 115 — the single-layer conv seams nct_conv3x3_dev and
- * nct_conv3x3_pair_dev). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
+ * nct_conv3x3_pair_dev; 116 — 3D colour look-up tables, nct_lut_*). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
-#define NCT_VERSION 115
+#define NCT_VERSION 116
 
 typedef enum {
     NCT_OK = 0,
@@ -358,6 +358,29 @@ int nct_seq_blend_mc_dev(nct_ctx* ctx, const double* d_x, const double* d_x_prev
                          double* d_x_out, double* d_tau_map, const int16_t* d_field);
 int nct_seq_warp(nct_ctx* ctx, const double* x_prev, int h, int w, const int16_t* field, double* x_out);
 int nct_seq_warp_dev(nct_ctx* ctx, const double* d_x_prev, int h, int w, const int16_t* d_field, double* d_x_out);
+
+/* ---- 3D colour look-up tables (SPEC §6.6; an extension: the reference leaves every result as pixels). A table hands a computed look to other tools (.cube) and puts it on
+ * pixels the pyramid never saw: a photograph above the working size, the frames of a clip. Lattice size N in {3, 5, 9, 17, 33, 65}; a table is float [N][N][N][3] indexed
+ * [ib][ig][ir], channels BGR, values in grey levels, not clamped.
+ * nct_lut_fit: from two images of npix pixels each, a source S and a result O (8-bit BGR, tightly packed). (1) splat: per lattice node the integer sums W = sum w and
+ * R[c] = sum w (O_c - S_c) over all pixels, w the pixel's trilinear integer weight (eight per pixel, summing to 255^3); (2) solve: the displacement field D (double) that
+ * minimises sum_n W_n / 255^3 (D_n - R_n / W_n)^2 + lambda sum_edges (D_u - D_v)^2 over the lattice's 6-neighbour edges, by a fixed number of multigrid cycles: empty
+ * cells are filled by the smoothness term; (3) LUT_n[c] = (float)(node colour_c + D_n[c]). stages (nullable, its arrays nullable) receives W [N^3], R [N^3][3], D [N^3][3].
+ * nct_lut_apply: out_c = saturate_cast<uchar>(sum over the eight corners of w LUT[c] / 255^3), the sum in double; the table whose nodes are the node colours returns the
+ * input. out_bgr may be bgr. The host form refuses a table with a non-finite entry; the _dev form does not look.
+ * The _dev forms take device pointers (stages: a host struct of device pointers) and are enqueued on the context's stream like the other device-pointer seams.
+ * nct_pair_fit_lut: the fit from the source and the result the context's last finished run holds on the device (nct_pair_run, nct_multi_run, nct_seq_frame and what is built
+ * on them: at the result's size; nct_process_pair_fullres: the original source and the full-resolution result), no PCIe round trip but the table's; synchronous. Without a
+ * finished run: NCT_ERR_STATE.
+ * NCT_ERR_INVALID with a message: a size outside the set, a lambda that is not finite and greater than 0, a null pointer, npix < 1 or npix > 2^26. */
+typedef struct nct_lut_params { int size; double lambda; } nct_lut_params;
+void nct_lut_params_default(nct_lut_params* p);     /* size 33, lambda 0.1 (the sweep) */
+typedef struct nct_lut_stages { uint64_t* weight; int64_t* resid; double* disp; } nct_lut_stages;
+int nct_lut_fit(nct_ctx* ctx, const uint8_t* src_bgr, const uint8_t* res_bgr, size_t npix, const nct_lut_params* prm, float* lut_out, nct_lut_stages* stages);
+int nct_lut_fit_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, const uint8_t* d_res_bgr, size_t npix, const nct_lut_params* prm, float* d_lut_out, nct_lut_stages* d_stages);
+int nct_lut_apply(nct_ctx* ctx, const float* lut, int size, const uint8_t* bgr, size_t npix, uint8_t* out_bgr);
+int nct_lut_apply_dev(nct_ctx* ctx, const float* d_lut, int size, const uint8_t* d_bgr, size_t npix, uint8_t* d_out_bgr);
+int nct_pair_fit_lut(nct_ctx* ctx, const nct_lut_params* prm, float* lut_out);
 
 /* ---- device-pointer seams: the same operations on buffers that stay in HBM between calls (main.cu:204-316 keeps Ndata_C1, ann_device, ... on the device
  * across these kernels; an integrator replacing single seams should not pay H2D + D2H + a synchronise per call). Buffers come from the context's arena

@@ -88,6 +88,7 @@ template <typename T> struct DevBuf {
     DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
     bool alloc(nct_ctx* ctx, size_t n) { if (p) c->release(p); c = ctx; p = (T*)ctx->alloc(n * sizeof(T)); return p != nullptr; }
     operator T*() const { return p; }
+    T* detach() { T* q = p; p = nullptr; return q; }           // the block stays reserved: the caller releases it
     bool ok() const { return p != nullptr; }
 };
 
@@ -215,6 +216,19 @@ int nctk_seq_motion(nct_ctx* ctx, hipStream_t s, const uint8_t* lab, const uint3
                     int16_t* m_out);
 // SPEC §6.5 rule 3: x_out(p) = x_prev(p + m(p)), the 64-bit words copied, a vector that leaves the grid clamped to it; x_out must not overlap x_prev
 int nctk_seq_warp(nct_ctx* ctx, hipStream_t s, const double* x_prev, int h, int w, const int16_t* field, double* x_out);
+// k_lut.hip — 3D colour look-up tables (SPEC §6.6). W [N^3] / R [N^3][3]: the splat's integer sums (zeroed on s by the splat itself); D [N^3][3]: the displacement
+// field after NCT_LUT_CYCLES V(2,2) cycles; lut [N^3][3] fp32. in / out of the apply may be the same buffer
+#define NCT_LUT_CYCLES 17
+#define NCT_LUT_MAX_PIXELS (1L << 26)
+bool nct_lut_size_ok(int N);
+int nctk_lut_splat(nct_ctx* ctx, hipStream_t s, const uint8_t* src, const uint8_t* res, long npix, int N, uint64_t* W, int64_t* R);
+int nctk_lut_solve(nct_ctx* ctx, hipStream_t s, const uint64_t* W, const int64_t* R, int N, double lambda, double* D);
+int nctk_lut_table(nct_ctx* ctx, hipStream_t s, const double* D, int N, float* lut);
+int nctk_lut_apply(nct_ctx* ctx, hipStream_t s, const float* lut, int N, const uint8_t* in, long npix, uint8_t* out);
+// nct_lut.cpp: the checks of nct_lut_fit's arguments (`what` names the entry point in the message), and splat + solve + table on device pointers, enqueued on the
+// main stream; stages (nullable, its arrays nullable): DEVICE pointers
+int nct_lut_fit_check(nct_ctx* ctx, const char* what, const void* src, const void* res, size_t npix, const nct_lut_params* prm, const void* lut_out);
+int nct_lut_fit_enqueue(nct_ctx* ctx, const uint8_t* d_src, const uint8_t* d_res, size_t npix, const nct_lut_params* prm, float* d_lut, const nct_lut_stages* d_stages);
 // k_wls_mg.hip
 int nctk_wls_solve_mg(nct_ctx* ctx, hipStream_t s, double* X, const double* rough, const double* wx, const double* wy, int H, int W,
                       double rtol, int* iters_out);

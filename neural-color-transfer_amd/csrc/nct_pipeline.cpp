@@ -32,6 +32,9 @@ struct pair_state {
     uint8_t* ref[NCT_MAX_REFS] = {};                           // the K references (SPEC §6.2; a pair: K = 1)
     int K = 0;
     int sh = 0, sw = 0, rh[NCT_MAX_REFS] = {}, rw[NCT_MAX_REFS] = {};
+    uint8_t *full_src = nullptr, *full_out = nullptr;          // a finished full-resolution run (SPEC §6.1): the original source and its result, full_h x full_w, kept for nct_pair_fit_lut
+    int full_h = 0, full_w = 0;
+    bool finished = false;                                     // the last run on these images ran to its end: `out` (or full_out) holds its result
 };
 static pair_state* pair_of(nct_ctx* ctx) {
     if (!ctx->pair) ctx->pair = new pair_state();
@@ -42,7 +45,9 @@ static void drop_images(nct_ctx* ctx, pair_state* P) {
     if (P->src) { ctx->release(P->src); P->src = nullptr; }
     for (uint8_t*& r : P->ref) if (r) { ctx->release(r); r = nullptr; }
     if (P->out) { ctx->release(P->out); P->out = nullptr; }
-    P->K = 0;
+    if (P->full_src) { ctx->release(P->full_src); P->full_src = nullptr; }
+    if (P->full_out) { ctx->release(P->full_out); P->full_out = nullptr; }
+    P->K = 0; P->finished = false;
 }
 // what motion compensation holds goes back to the arena
 static void seq_motion_free(nct_ctx* ctx, seq_state* q) {
@@ -495,6 +500,10 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
     NCT_REQUIRE(prm->levels >= 1 && prm->levels <= 5, "process: levels must be in [1, 5] (got %d)", prm->levels);
     NCT_REQUIRE(!fin || (!lv && !color), "process: no level intermediates with a full-resolution finish");
     NCT_REQUIRE(!color || P->K == 1, "process: nct_pair_levels describes a pair; several references report through nct_multi_levels");
+    // a new run on the resident images: an earlier full-resolution run is no longer the last one, and its two original-size images go back to the arena
+    if (P->full_src) { ctx->release(P->full_src); P->full_src = nullptr; }
+    if (P->full_out) { ctx->release(P->full_out); P->full_out = nullptr; }
+    P->finished = false;
     if (timing) memset(timing, 0, sizeof *timing);
     auto wall0 = std::chrono::steady_clock::now();
     ctx->tm_on = timing != nullptr; ctx->tm_tags.clear(); ctx->tm_host.clear();
@@ -503,6 +512,7 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
     pair_run run(ctx, prm, timing, lv, color, fin, seq, slv);
     const int rc = run.run();
     ctx->tm_on = false; ctx->kt_on = false;
+    P->finished = rc == NCT_OK;
     if (rc || !timing) return rc;
     timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     return read_timing(ctx, timing, run.count);
@@ -897,6 +907,26 @@ int nct_process_pair_fullres(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int s
     if (P->out) { ctx->release(P->out); P->out = nullptr; }
     if (rc) return rc;
     NCT_D2H(out_bgr, o0, (size_t)sh * sw * 3);
+    NCT_SYNC();
+    P->full_src = s0.detach(); P->full_out = o0.detach(); P->full_h = sh; P->full_w = sw;
+    return NCT_OK;
+}
+
+// SPEC §6.6 rule 10: the table of the last finished run, from the images the context still holds on the device
+int nct_pair_fit_lut(nct_ctx* ctx, const nct_lut_params* prm, float* lut_out) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    const uint8_t *src = nullptr, *res = nullptr; size_t npix = 0;
+    if (P && !P->finished) P = nullptr;
+    if (P && P->full_src && P->full_out) { src = P->full_src; res = P->full_out; npix = (size_t)P->full_h * P->full_w; }
+    else if (P && P->src && P->out && P->sh > 0) { src = P->src; res = P->out; npix = (size_t)P->sh * P->sw; }
+    if (!src) return ctx->fail(NCT_ERR_STATE, "pair_fit_lut: no finished run on this context (nct_pair_run first)");
+    NCT_TRY(nct_lut_fit_check(ctx, "pair_fit_lut", src, res, npix, prm, lut_out));
+    const size_t n = (size_t)prm->size * prm->size * prm->size * 3;
+    DevBuf<float> dl(ctx, n);
+    if (!dl.ok()) return NCT_ERR_HIP;
+    NCT_TRY(nct_lut_fit_enqueue(ctx, src, res, npix, prm, dl, nullptr));
+    NCT_D2H(lut_out, dl, sizeof(float) * n);
     NCT_SYNC();
     return NCT_OK;
 }

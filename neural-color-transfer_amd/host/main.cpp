@@ -33,6 +33,7 @@
 #include <vector>
 #include "nct.h"
 #include "png_io.h"
+#include "cube_io.h"
 #include "jpeg_io.h"
 #include "affinity.h"
 #include "rccl_sync.h"
@@ -113,7 +114,8 @@ std::string stem(const std::string& path) {          // main.cu:524-531 (find_la
 struct Pair { std::string cnt, stl; float bds; std::vector<std::string> refs; std::string err; };
 std::mutex g_print;
 
-struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false, fullres = false, seq = false, motion = false; nct_seq_params sp; nct_seq_motion mp; int key = 1; int rank = 0, world = 1; };
+struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false, fullres = false, seq = false, motion = false; nct_seq_params sp; nct_seq_motion mp; int key = 1; int rank = 0, world = 1;
+                int lut = 0; double lut_lambda = 0.0; bool lutfull = false; };   // -lut N (0 = off), -lutlambda (0 = the library's default), -lutfull 1
 
 // ---- ENABLE_VIS debug outputs (Config.h:8) behind the runtime flag -vis 1: per pyramid level the flow maps of both NNFs (reconstruct_flow,
 // GeneralizedPatchMatch.cu:337-353), the level images tCnt / tStl (main.cu:343-347), the matching-error heat map (getHeat,
@@ -316,6 +318,9 @@ bool shrink(nct_ctx* ctx, ImageBGR& img) {
 struct Job {
     size_t index = 0; Pair p; std::string name, log, err;
     ImageBGR cnt; std::vector<uint8_t> out;
+    ImageBGR orig;                                               // -lutfull 1: the content image as decoded, before the shrink to MAX_SIZE
+    std::vector<float> lut; std::vector<uint8_t> lut_out;       // -lut N: the job's table; -lutfull 1: the table on `orig`
+    int lut_n = 0; std::string lut_err;                          // the table's size; why the job has no table (its result image is written all the same)
     std::vector<ImageBGR> refs;                                  // the line's references: one, or several (SPEC §6.2)
     size_t input_bytes() const { size_t b = cnt.px.size(); for (const auto& r : refs) b += r.px.size(); return b; }
     std::chrono::steady_clock::time_point t0;
@@ -361,6 +366,36 @@ std::string output_name(const Config& cfg, const Pair& p) {
     return name;
 }
 
+// what a job writes beside <name>.png: <name>.cube with -lut N, <name>_lut.png with -lutfull 1
+std::string cube_name(const std::string& png) { return png.substr(0, png.size() - 4) + ".cube"; }
+std::string lutfull_name(const std::string& png) { return png.substr(0, png.size() - 4) + "_lut.png"; }
+// -resume: every file of the job's output is there and complete
+bool outputs_complete(const Config& cfg, const std::string& png) {
+    return pngio::looks_complete(png) && (!cfg.lut || cubeio::looks_complete(cube_name(png), cfg.lut)) && (!cfg.lutfull || pngio::looks_complete(lutfull_name(png)));
+}
+
+// -lut N: the table of a finished job (SPEC §6.6), fitted through the host-pointer call from the equal-sized source and result the job holds; -lutfull 1: that table
+// on the content image at its original size. Before log_times, which drops the inputs
+bool job_lut(nct_ctx* ctx, const Config& cfg, Job& j) {
+    if (!cfg.lut) return true;
+    nct_lut_params lp; nct_lut_params_default(&lp);
+    lp.size = cfg.lut;
+    if (cfg.lut_lambda > 0.0) lp.lambda = cfg.lut_lambda;
+    j.lut.resize((size_t)lp.size * lp.size * lp.size * 3);
+    int rc = nct_lut_fit(ctx, j.cnt.px.data(), j.out.data(), (size_t)j.cnt.h * j.cnt.w, &lp, j.lut.data(), nullptr);
+    if (rc == NCT_OK && cfg.lutfull) {
+        j.lut_out.resize(j.orig.px.size());
+        rc = nct_lut_apply(ctx, j.lut.data(), lp.size, j.orig.px.data(), (size_t)j.orig.h * j.orig.w, j.lut_out.data());
+        j.orig.px.clear(); j.orig.px.shrink_to_fit();
+    }
+    // a table that cannot be made (a full-resolution source above the fit's 2^26 pixels, for one) does not take the computed result with it: store_pair writes the
+    // image, then reports the job as failed for its table
+    if (rc != NCT_OK) { j.lut_err = nct_last_error(ctx); j.lut.clear(); j.lut_out.clear(); return true; }
+    j.lut_n = lp.size;
+    j.say("Look-up table: %d x %d x %d, lambda = %g.\n", lp.size, lp.size, lp.size, lp.lambda);
+    return true;
+}
+
 // in_seq: the line is a frame of a sequence (-seq 1) — its resume check and its reference belong to the sequence, not to the line
 void load_pair(const Config& cfg, Job& j, bool in_seq = false) {
     j.t0 = std::chrono::steady_clock::now();
@@ -371,7 +406,7 @@ void load_pair(const Config& cfg, Job& j, bool in_seq = false) {
     const std::string cntStr = cfg.input_dir + "/" + j.p.cnt;
     j.name = output_name(cfg, j.p);
     const char* name = j.name.c_str();
-    if (!in_seq && cfg.resume && pngio::looks_complete(j.name)) {           // a truncated file (killed run, full disk) is redone, not skipped
+    if (!in_seq && cfg.resume && outputs_complete(cfg, j.name)) {           // a truncated file (killed run, full disk) is redone, not skipped
         j.say("Skipping (-resume): %s exists.\n\n", name);
         j.state = Job::SKIPPED; return;
     }
@@ -409,9 +444,11 @@ void run_pair(nct_ctx* ctx, const Config& cfg, Job& j) {
         j.out.resize((size_t)j.cnt.h * j.cnt.w * 3);
         const int rc = nct_process_pair_fullres(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, stl.px.data(), stl.h, stl.w, MAX_SIZE, &prm, j.out.data(), &tm);
         if (rc != NCT_OK) { j.say("Error: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
+        if (!job_lut(ctx, cfg, j)) return;
         log_times(j, prm, tm);
         return;
     }
+    if (cfg.lutfull) j.orig = j.cnt;
     bool shrunk = shrink(ctx, j.cnt);
     for (auto& r : j.refs) shrunk = shrunk && shrink(ctx, r);
     if (!shrunk) { j.say("Error: resize failed: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
@@ -432,13 +469,23 @@ void run_pair(nct_ctx* ctx, const Config& cfg, Job& j) {
         if (!ok) err = nct_last_error(ctx);
     }
     if (!ok) { j.say("Error: %s\n", err.c_str()); j.err = err; j.state = Job::FAILED; return; }
+    if (!job_lut(ctx, cfg, j)) return;
     log_times(j, prm, tm);
 }
 
 void store_pair(Job& j) {
     std::string err;
     if (!pngio::write(j.name, j.out.data(), j.cnt.h, j.cnt.w, err)) { j.say("Error: cannot write %s: %s\n", j.name.c_str(), err.c_str()); j.err = "cannot write output: " + err; j.state = Job::FAILED; return; }
+    if (!j.lut.empty()) {
+        if (!cubeio::write(cube_name(j.name), j.lut.data(), j.lut_n, err)) { j.say("Error: %s\n", err.c_str()); j.err = "cannot write table: " + err; j.state = Job::FAILED; return; }
+        j.say("Look-up table file: %s.\n", cube_name(j.name).c_str());
+    }
+    if (!j.lut_out.empty()) {
+        if (!pngio::write(lutfull_name(j.name), j.lut_out.data(), j.orig.h, j.orig.w, err)) { j.say("Error: cannot write %s: %s\n", lutfull_name(j.name).c_str(), err.c_str()); j.err = "cannot write output: " + err; j.state = Job::FAILED; return; }
+        j.say("Look-up table on the original: %s.\n", lutfull_name(j.name).c_str());
+    }
     j.say("Final output file: %s.\n\n", j.name.c_str());
+    if (!j.lut_err.empty()) { j.say("Error: no look-up table: %s\n", j.lut_err.c_str()); j.err = "no look-up table: " + j.lut_err; j.state = Job::FAILED; return; }
     j.state = Job::DONE;
 }
 
@@ -466,7 +513,7 @@ size_t run_sequence(nct_ctx* ctx, const Config& cfg, const std::vector<Pair>& pa
     prm.bds_weight = pairs[g.first].bds;
     if (cfg.resume) {
         bool all = true;
-        for (size_t i = g.first; i < g.first + g.count && all; ++i) all = pngio::looks_complete(output_name(cfg, pairs[i]));
+        for (size_t i = g.first; i < g.first + g.count && all; ++i) all = outputs_complete(cfg, output_name(cfg, pairs[i]));
         if (all) {
             for (size_t i = g.first; i < g.first + g.count; ++i) {
                 Job j; j.index = i; j.p = pairs[i]; j.t0 = std::chrono::steady_clock::now(); j.name = output_name(cfg, j.p);
@@ -492,6 +539,7 @@ size_t run_sequence(nct_ctx* ctx, const Config& cfg, const std::vector<Pair>& pa
             }
         }
         if (j.state == Job::LOADED && ref.px.empty()) { j.err = "cannot read style image: " + ref_err; j.state = Job::FAILED; }
+        if (j.state == Job::LOADED && cfg.lutfull) j.orig = j.cnt;
         if (j.state == Job::LOADED && !shrink(ctx, j.cnt)) { j.say("Error: resize failed: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; }
         if (j.state == Job::LOADED) {
             int rc = NCT_OK;
@@ -512,7 +560,7 @@ size_t run_sequence(nct_ctx* ctx, const Config& cfg, const std::vector<Pair>& pa
             if (rc == NCT_OK) rc = prop ? nct_seq_frame_propagate(ctx, j.cnt.px.data(), j.out.data(), &tm) : nct_seq_frame(ctx, j.cnt.px.data(), j.out.data(), &tm);
             k = rc == NCT_OK ? k + 1 : 0;
             if (rc != NCT_OK) { j.say("Error: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; }
-            else { log_times(j, prm, tm); store_pair(j); }
+            else if (job_lut(ctx, cfg, j)) { log_times(j, prm, tm); store_pair(j); }
         }
         finish(cfg, j);
     }
@@ -646,7 +694,8 @@ int main(int argc, char** argv) {
     nct_params_default(&cfg.prm);
     nct_seq_params_default(&cfg.sp);
     nct_seq_motion_default(&cfg.mp);
-    int motion = 0, key = 1;
+    int motion = 0, key = 1, lut = 0, lutfull = 0;
+    double lutlambda = 0.0; bool lutlambda_set = false;
     int gpu = 0, ngpus = 1, seed = 1, inflight = 1, levels = 5, resume = 0, feat16 = 0, vis = 0, fullres = 0, seq = 0, io = -1, pin = 1, world = 1, rank = 0, steal = 0, procs = 0, rccl = 0;
     cl.add("m", cfg.model_dir, "Directory of network models.");
     cl.add("i", cfg.input_dir, "Input directory of content and style images and pairs.txt.");
@@ -682,6 +731,9 @@ int main(int argc, char** argv) {
     cl.add("mr", cfg.mp.radius, "[extension] -motion 1: search radius of the refinement at every finer level, in [0, 3].");
     cl.add("mpen", cfg.mp.penalty, "[extension] -motion 1: cost per tap and pixel of displacement from the search centre, in [0, 255].");
     cl.add("key", key, "[extension] -seq 1: N in [1, 1000]: within a sequence only every N-th frame runs the whole pair; the frames between take their colour coefficients from the frame before them through the motion field and run the last level's finish only (SPEC 6.5). 1 = every frame is a full frame.");
+    cl.add("lut", lut, "[extension] N in {3, 5, 9, 17, 33, 65}: beside each result image write <same name>.cube, a 3D look-up table of N^3 nodes fitted from the source and the result (SPEC 6.6); works in every mode.");
+    cl.add("lutlambda", lutlambda, "[extension] -lut N: smoothness weight of the table's fit (> 0; default: the library's, 0.1).");
+    cl.add("lutfull", lutfull, "[extension] -lut N: 1 = also write <name>_lut.png, the table applied to the content image at its original size; not with -fullres 1.");
     // parser self-test hook (no GPU): `--parse-only <args…>` parses the rest like a normal run and prints what main would go on with, in the format of
     // oracle/ref_cmdline.cpp (the reference's own parser): tests/test_cli.py compares the two on the vectors of tests/golden/cmdline_ref.json
     // job-planning hook (no GPU): `--plan-only <args…>` goes as far as a normal run goes before it creates a context and prints, per pairs.txt line, what it would run
@@ -709,6 +761,13 @@ int main(int argc, char** argv) {
     if (motion && (cfg.mp.penalty < 0 || cfg.mp.penalty > 255)) { printf("Error: -mpen %d is not in [0, 255].\n", cfg.mp.penalty); return -1; }
     if (key < 1 || key > 1000) { printf("Error: -key %d is not in [1, 1000].\n", key); return -1; }
     if (key > 1 && !seq) { printf("Error: -key %d needs -seq 1 (propagated frames belong to a sequence).\n", key); return -1; }
+    for (int a = 1; a < argc; ++a) lutlambda_set = lutlambda_set || !strcmp(argv[a], "-lutlambda");
+    if (lut != 0 && lut != 3 && lut != 5 && lut != 9 && lut != 17 && lut != 33 && lut != 65) { printf("Error: -lut %d is not one of 3, 5, 9, 17, 33, 65.\n", lut); return -1; }
+    if (lutlambda_set && !lut) { printf("Error: -lutlambda needs -lut N.\n"); return -1; }
+    if (lutlambda_set && !(lutlambda > 0.0 && lutlambda <= 1.7976931348623157e308)) { printf("Error: -lutlambda %g is not finite and greater than 0.\n", lutlambda); return -1; }
+    if (lutfull && !lut) { printf("Error: -lutfull 1 needs -lut N.\n"); return -1; }
+    if (lutfull && fullres) { printf("Error: -lutfull 1 cannot be combined with -fullres 1 (the result already has the original size).\n"); return -1; }
+    cfg.lut = lut; cfg.lut_lambda = lutlambda_set ? lutlambda : 0.0; cfg.lutfull = lutfull != 0;
     if (!plan_only) mkdir(cfg.output_dir.c_str(), 0777);                    // main.cu:458
     uint64_t run_token = getenv("NCT_RUN_TOKEN") ? strtoull(getenv("NCT_RUN_TOKEN"), nullptr, 0) : 0;      // hand-started ranks of one run share it (and remove <output>/.rccl_id between runs)
     const std::string tickets_path = cfg.output_dir + "/.tickets";

@@ -38,7 +38,7 @@ def lib():
     return _lib
 
 
-NCT_VERSION = 115        # include/nct.h
+NCT_VERSION = 116        # include/nct.h
 MAX_REFS = 8             # NCT_MAX_REFS
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -118,6 +118,12 @@ SIGNATURES = {
     "nct_seq_motion_field_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "nct_seq_blend_mc": (C.c_int, [C.c_void_p, _f64p, _f64p, _u8p, _u8p, C.c_int, C.c_int, C.c_double, C.c_double, _f64p, C.c_void_p, C.c_void_p]),
     "nct_seq_blend_mc_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_lut_params_default": (None, [C.c_void_p]),
+    "nct_lut_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_lut_fit_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_lut_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nct_lut_apply_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nct_pair_fit_lut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "nct_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nct_dev_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -246,6 +252,31 @@ class MultiLevels(C.Structure):
     """struct nct_multi_levels (include/nct.h)."""
     _fields_ = [(k, (C.c_void_p * 5) * MAX_REFS) for k in ("ann", "bnn", "annd", "bnnd", "ref_guide", "ref_err")] + \
                [(k, C.c_void_p * 5) for k in ("label", "guide", "err", "result")] + [("labels", C.c_void_p)]
+
+
+class LutParams(C.Structure):
+    """struct nct_lut_params (include/nct.h)."""
+    _fields_ = [("size", C.c_int), ("lambda_", C.c_double)]
+
+    @staticmethod
+    def default():
+        p = LutParams()
+        lib().nct_lut_params_default(C.byref(p))
+        return p
+
+
+class LutStages(C.Structure):
+    """struct nct_lut_stages (include/nct.h)."""
+    _fields_ = [("weight", C.c_void_p), ("resid", C.c_void_p), ("disp", C.c_void_p)]
+
+
+def _lut_params(size, lam):
+    p = LutParams.default()
+    if size is not None:
+        p.size = int(size)
+    if lam is not None:
+        p.lambda_ = float(lam)
+    return p
 
 
 class SeqParams(C.Structure):
@@ -820,6 +851,69 @@ class Context:
             self.synchronize()
             for p in ins + [do]:
                 self.dev_free(p)
+
+    # ---- 3D colour look-up tables (SPEC §6.6)
+    def lut_fit(self, src, res, size=None, lam=None, want_stages=False):
+        """nct_lut_fit: source and result images (any shape [..., 3], uint8 BGR) -> table float32 [N, N, N, 3] (+ {"weight", "resid", "disp"}); size / lam left
+        out are nct_lut_params_default's"""
+        s, r = np.ascontiguousarray(src, np.uint8).reshape(-1, 3), np.ascontiguousarray(res, np.uint8).reshape(-1, 3)
+        assert s.shape == r.shape
+        prm = _lut_params(size, lam)
+        N = prm.size if 0 < prm.size <= 65 else 1                      # a refused size never reaches the arrays
+        lut = np.empty((N, N, N, 3), np.float32)
+        st = {"weight": np.empty(N ** 3, np.uint64), "resid": np.empty((N ** 3, 3), np.int64), "disp": np.empty((N ** 3, 3), np.float64)}
+        cs = LutStages(*(st[k].ctypes.data for k in ("weight", "resid", "disp")))
+        self._chk(self._l.nct_lut_fit(self._h, s.ctypes.data, r.ctypes.data, len(s), C.addressof(prm), lut.ctypes.data, C.addressof(cs) if want_stages else None))
+        return (lut, st) if want_stages else lut
+
+    def lut_fit_dev(self, src, res, size=None, lam=None, want_stages=False):
+        """the same through nct_lut_fit_dev on arena blocks"""
+        s, r = np.ascontiguousarray(src, np.uint8).reshape(-1, 3), np.ascontiguousarray(res, np.uint8).reshape(-1, 3)
+        prm = _lut_params(size, lam)
+        n3 = prm.size ** 3
+        blocks = [self.dev_upload(s), self.dev_upload(r), self.dev_alloc(12 * n3), self.dev_alloc(8 * n3), self.dev_alloc(24 * n3), self.dev_alloc(24 * n3)]
+        try:
+            cs = LutStages(blocks[3], blocks[4], blocks[5])
+            self._chk(self._l.nct_lut_fit_dev(self._h, blocks[0], blocks[1], len(s), C.addressof(prm), blocks[2], C.addressof(cs) if want_stages else None))
+            lut = self.dev_download(blocks[2], (prm.size,) * 3 + (3,), np.float32)
+            if not want_stages:
+                return lut
+            return lut, {"weight": self.dev_download(blocks[3], (n3,), np.uint64), "resid": self.dev_download(blocks[4], (n3, 3), np.int64),
+                         "disp": self.dev_download(blocks[5], (n3, 3), np.float64)}
+        finally:
+            self.synchronize()
+            for p in blocks:
+                self.dev_free(p)
+
+    def lut_apply(self, lut, img):
+        """nct_lut_apply: table [N, N, N, 3] float32 on an image [..., 3] uint8 BGR -> the image of the same shape"""
+        t = np.ascontiguousarray(lut, np.float32)
+        a = np.ascontiguousarray(img, np.uint8)
+        out = np.empty_like(a)
+        self._chk(self._l.nct_lut_apply(self._h, t.ctypes.data, t.shape[0], a.ctypes.data, a.size // 3, out.ctypes.data))
+        return out
+
+    def lut_apply_dev(self, lut, img, in_place=False):
+        """the same through nct_lut_apply_dev on arena blocks (in_place: the output over the input)"""
+        t = np.ascontiguousarray(lut, np.float32)
+        a = np.ascontiguousarray(img, np.uint8)
+        blocks = [self.dev_upload(t), self.dev_upload(a), self.dev_alloc(a.size)]
+        try:
+            dst = blocks[1] if in_place else blocks[2]
+            self._chk(self._l.nct_lut_apply_dev(self._h, blocks[0], t.shape[0], blocks[1], a.size // 3, dst))
+            return self.dev_download(dst, a.shape, np.uint8)
+        finally:
+            self.synchronize()
+            for p in blocks:
+                self.dev_free(p)
+
+    def pair_fit_lut(self, size=None, lam=None):
+        """nct_pair_fit_lut: the table of the context's last finished run, from the images it holds on the device"""
+        prm = _lut_params(size, lam)
+        N = prm.size if 0 < prm.size <= 65 else 1
+        lut = np.empty((N, N, N, 3), np.float32)
+        self._chk(self._l.nct_pair_fit_lut(self._h, C.addressof(prm), lut.ctypes.data))
+        return lut
 
     def seq_reset(self):
         self._chk(self._l.nct_seq_reset(self._h))
