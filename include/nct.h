@@ -28,9 +28,9 @@ extern "C" {
 /* bumped whenever a struct of this header changes layout or an entry point changes meaning (round 6: 110 — nct_model_layer; nct_pair_timing grew in round 5 without a
  * bump; 111 — nct_multi_levels and the entry points for several references; 112 — frame sequences, nct_seq_*; 113 — nct_seq_levels.motion and motion-compensated
  * sequences, nct_seq_set_motion; 114 — propagated frames, nct_seq_frame_propagate and nct_seq_warp; 115 — the single-layer conv seams nct_conv3x3_dev and
- * nct_conv3x3_pair_dev; 116 — 3D colour look-up tables, nct_lut_*). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
+ * nct_conv3x3_pair_dev; 116 — 3D colour look-up tables, nct_lut_*; 117 — adaptive key frames, nct_seq_change, nct_seq_probe and nct_seq_frame_auto). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
-#define NCT_VERSION 116
+#define NCT_VERSION 117
 
 typedef enum {
     NCT_OK = 0,
@@ -358,6 +358,42 @@ int nct_seq_blend_mc_dev(nct_ctx* ctx, const double* d_x, const double* d_x_prev
                          double* d_x_out, double* d_tau_map, const int16_t* d_field);
 int nct_seq_warp(nct_ctx* ctx, const double* x_prev, int h, int w, const int16_t* field, double* x_out);
 int nct_seq_warp_dev(nct_ctx* ctx, const double* d_x_prev, int h, int w, const int16_t* d_field, double* d_x_out);
+
+/* ---- adaptive key frames (SPEC §6.7; an extension). Which frames of a sequence run the whole pair is decided per frame from how much of the frame the motion field
+ * fails to explain, measured on the 8-bit Lab level images before any expensive stage runs.
+ * nct_seq_change: the measure alone (rule 1), integers only. lab / lab_prev h*w*3 (8-bit Lab, the frame's and the previous frame's), field (nullable: m = 0) int16
+ * [h*w][2] of (my, mx), a vector that leaves the grid first clamped component-wise so that p + m is inside. r(p) = sum over the three bytes of
+ * |lab(p) - lab_prev(p + m(p))| (0 … 765); out->sad = sum_p r(p), out->changed = the number of pixels with r(p) > threshold, out->pixels = h * w. Host pointers,
+ * synchronous; the _dev form takes device pointers (d_out: 16 bytes on the device) and is enqueued on the context's stream. NCT_ERR_INVALID with a message naming the
+ * argument: a null image or a null out, a grid outside 1 … 4096 per side, a threshold outside [0, 765]. (The record's type is nct_seq_change_rec: C has one name space for
+ * functions and typedef names.)
+ * nct_seq_probe (rule 2): on an open sequence with state, the measure of the frame src_bgr against the previous frame at level lambda = min(levels - 1, 2) in run order
+ * (0 = coarsest): the frame goes into scratch, its pyramid is built as a full frame builds it, L_t[l] is taken for l = 0 … lambda, with motion on the fields of §6.4 rules
+ * 1-3 are found level by level against the kept packed maps (with motion off there is no field), then rule 1 with a->threshold. The probe reads the kept L and packed maps
+ * and writes neither; X', the frame count and the counters below stay as they are; the per-level field buffers serve as scratch (every frame path rewrites them before it
+ * reads them); everything else comes from the arena for the call and goes back. Synchronous. out: the decision this frame would get (rule 3), its counters not updated.
+ * No open sequence, or one without state (the first frame after nct_seq_begin / nct_seq_reset): NCT_ERR_STATE; a null image or out, parameters out of range: NCT_ERR_INVALID.
+ * The decision (rule 3), exact 64-bit integer comparisons in this order — NCT_SEQ_FIRST: the sequence has no state (no probe runs; change is zero, level -1);
+ * NCT_SEQ_CUT: changed * 1000 >= cut_permille * pixels; NCT_SEQ_KEY: gap >= max_gap - 1, or key_permille != 1001 and (acc + changed) * 1000 >= key_permille * pixels; NCT_SEQ_PROPAGATED otherwise.
+ * gap = the propagated frames since the last full frame, whichever call ran them; acc = the sum of `changed` over the frames nct_seq_frame_auto propagated since the last
+ * full frame. nct_seq_begin, nct_seq_reset and every full frame (a manual nct_seq_frame too) zero both; a manual nct_seq_frame_propagate adds 1 to gap only.
+ * threshold in [0, 765], cut_permille and key_permille in [0, 1001] (1001 = never), max_gap in [1, 1000]; anything else NCT_ERR_INVALID. a == NULL: the defaults.
+ * nct_seq_decision: acc_changed and gap are the counters the rules compared against, before this frame's update; probe_ms the host wall time of the probe, its
+ * synchronise included (0 for NCT_SEQ_FIRST). nct_pair_timing keeps its layout.
+ * nct_seq_frame_auto (rule 4): probe, decide, then exactly one of the existing calls, unchanged — FIRST / KEY: nct_seq_frame; CUT: nct_seq_reset, then nct_seq_frame;
+ * PROPAGATED: nct_seq_frame_propagate — and the update of acc and gap. timing (nullable) is the chosen call's, out (nullable) the decision. Every frame's bytes and the
+ * state after it are those of the manual call the decision names; a CUT frame is nct_process_pair(S_t, R). key_permille = 0 with cut_permille = 1001 gives the all-full
+ * sequence; cut_permille = key_permille = 1001 with max_gap = N gives the key-frame grid N. A refused call changes nothing; a frame that fails after the probe leaves the
+ * sequence reset. A sequence that never calls these entry points keeps its bytes, its launches and its arena size. */
+typedef struct nct_seq_change_rec { uint64_t sad; uint32_t changed, pixels; } nct_seq_change_rec;
+typedef struct nct_seq_auto { int threshold, cut_permille, key_permille, max_gap; } nct_seq_auto;
+void nct_seq_auto_default(nct_seq_auto* p);     /* 24, 500, 100, 8 */
+enum { NCT_SEQ_FIRST = 0, NCT_SEQ_PROPAGATED = 1, NCT_SEQ_KEY = 2, NCT_SEQ_CUT = 3 };
+typedef struct nct_seq_decision { int kind, level; nct_seq_change_rec change; uint32_t acc_changed; int gap; double probe_ms; } nct_seq_decision;
+int nct_seq_change(nct_ctx* ctx, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, const int16_t* field, int threshold, nct_seq_change_rec* out);
+int nct_seq_change_dev(nct_ctx* ctx, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, const int16_t* d_field, int threshold, nct_seq_change_rec* d_out);
+int nct_seq_probe(nct_ctx* ctx, const uint8_t* src_bgr, const nct_seq_auto* a, nct_seq_decision* out);
+int nct_seq_frame_auto(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_auto* a, nct_seq_decision* out);
 
 /* ---- 3D colour look-up tables (SPEC §6.6; an extension: the reference leaves every result as pixels). A table hands a computed look to other tools (.cube) and puts it on
  * pixels the pyramid never saw: a photograph above the working size, the frames of a clip. Lattice size N in {3, 5, 9, 17, 33, 65}; a table is float [N][N][N][3] indexed

@@ -17,6 +17,11 @@
 // Propagated frames (SPEC §6.5). k_seq_warp moves the kept coefficients along a field: x_out(p) = x_prev(p + m(p)), the six 64-bit words of the pixel copied as integers
 // (a NaN keeps its payload). One thread per pixel: one short2, six gathered words in flight together, six plain stores; no LDS, no atomics. It gathers, so it runs out of
 // place. At 700 x 700 the finest level moves 47 MB + 2 MB of field: stream-bound there, launch-bound on the coarse levels.
+//
+// The change measure (SPEC §6.7 rule 1). k_seq_change sums, over a level, r(p) = the three-byte SAD of L_t(p) and L_(t-1)(p + m(p)), and counts the pixels with r(p) > T.
+// One thread per pixel: the two triples packed into words, one v_sad_u8. A wave's two sums fit one 32-bit word (64 * 765 < 2^16 below, a count <= 64 above), so the wave
+// reduces with six lane shifts of one register; the four words of a workgroup meet in LDS, and thread 0 adds the workgroup's sums to the record's two integer fields
+// with vector atomics. Integer sums do not depend on the order the workgroups arrive in: the record is exact and the same on every run. No float, no second pass.
 #include "nct_internal.h"
 #include "nct_device.h"
 
@@ -100,6 +105,39 @@ __global__ void __launch_bounds__(256) k_seq_warp(const unsigned long long* __re
     for (int q = 0; q < 6; ++q) v[q] = x_prev[(size_t)(q / 3) * 3 * n + (size_t)3 * ip + q % 3];
 #pragma unroll
     for (int q = 0; q < 6; ++q) x_out[(size_t)(q / 3) * 3 * n + (size_t)3 * i + q % 3] = v[q];
+}
+
+// SPEC §6.7 rule 1; the vector is clamped component-wise as in k_seq_warp. rec is zeroed on the stream before the launch. A thread past the grid loads nothing and adds 0
+__global__ void __launch_bounds__(256) k_seq_change(const uint8_t* __restrict__ lab, const uint8_t* __restrict__ lab_prev, int h, int w, const short2* __restrict__ field, int T,
+                                                    nct_seq_change_rec* __restrict__ rec) {
+    __shared__ uint32_t s_wave[4];
+    const int n = h * w;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t v = 0;                                            // r(p) | (r(p) > T) << 16
+    if (i < n) {
+        int ip = i;
+        if (field) {
+            const int y = i / w, px = i - y * w;
+            const short2 m = field[i];
+            ip = clampi(y + m.x, 0, h - 1) * w + clampi(px + m.y, 0, w - 1);
+        }
+        const uint32_t a = (uint32_t)lab[3 * i] | ((uint32_t)lab[3 * i + 1] << 8) | ((uint32_t)lab[3 * i + 2] << 16);
+        const uint32_t b = (uint32_t)lab_prev[3 * ip] | ((uint32_t)lab_prev[3 * ip + 1] << 8) | ((uint32_t)lab_prev[3 * ip + 2] << 16);
+        const uint32_t r = __builtin_amdgcn_sad_u8(a, b, 0u);
+        v = r | ((int)r > T ? 1u << 16 : 0u);
+    }
+    v += __shfl_down(v, 32); v += __shfl_down(v, 16); v += __shfl_down(v, 8);
+    v += __shfl_down(v, 4); v += __shfl_down(v, 2); v += __shfl_down(v, 1);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long sad = 0; uint32_t changed = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { sad += s_wave[k] & 0xffffu; changed += s_wave[k] >> 16; }
+        if (sad) atomicAdd((unsigned long long*)&rec->sad, sad);
+        if (changed) atomicAdd(&rec->changed, changed);
+        if (blockIdx.x == 0) rec->pixels = (uint32_t)n;
+    }
 }
 
 #define MC_BW 32
@@ -221,6 +259,17 @@ int nctk_seq_warp(nct_ctx* ctx, hipStream_t s, const double* x_prev, int h, int 
     const size_t bytes = sizeof(double) * 6 * (size_t)h * w;
     NCT_REQUIRE((const char*)x_out + bytes <= (const char*)x_prev || (const char*)x_prev + bytes <= (const char*)x_out, "seq_warp: x_out must not alias x_prev");
     hipLaunchKernelGGL(k_seq_warp, dim3(cdiv(h * w, 256)), dim3(256), 0, s, (const unsigned long long*)x_prev, h, w, (const short2*)field, (unsigned long long*)x_out);
+    NCT_LAUNCH_CHECK();
+    return 0;
+}
+
+int nctk_seq_change(nct_ctx* ctx, hipStream_t s, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, const int16_t* field, int threshold, nct_seq_change_rec* rec) {
+    NCT_REQUIRE(lab && lab_prev, "seq_change: null image");
+    NCT_REQUIRE(rec, "seq_change: null out");
+    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_change: grid %dx%d out of range", w, h);
+    NCT_REQUIRE(threshold >= 0 && threshold <= 765, "seq_change: the threshold must be in [0, 765] (got %d)", threshold);
+    NCT_HIP(hipMemsetAsync(rec, 0, sizeof *rec, s));
+    hipLaunchKernelGGL(k_seq_change, dim3(cdiv(h * w, 256)), dim3(256), 0, s, lab, lab_prev, h, w, (const short2*)field, threshold, rec);
     NCT_LAUNCH_CHECK();
     return 0;
 }

@@ -396,6 +396,26 @@ int nct_seq_warp(nct_ctx* ctx, const double* x_prev, int h, int w, const int16_t
     return NCT_OK;
 }
 
+// SPEC §6.7 rule 1 on host maps: the two Lab level images (and the field) up, one k_seq_change launch, the 16-byte record down
+int nct_seq_change(nct_ctx* ctx, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, const int16_t* field, int threshold, nct_seq_change_rec* out) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(lab && lab_prev, "seq_change: null image");
+    NCT_REQUIRE(out, "seq_change: null out");
+    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_change: grid %dx%d out of range", w, h);
+    NCT_REQUIRE(threshold >= 0 && threshold <= 765, "seq_change: the threshold must be in [0, 765] (got %d)", threshold);
+    const size_t n = (size_t)h * w;
+    DevBuf<uint8_t> dl(ctx, 3 * n), dlp(ctx, 3 * n);
+    DevBuf<int16_t> df(ctx, field ? 2 * n : 8);
+    DevBuf<nct_seq_change_rec> dr(ctx, 1);
+    if (!dl.ok() || !dlp.ok() || !df.ok() || !dr.ok()) return NCT_ERR_HIP;
+    NCT_H2D(dl, lab, 3 * n); NCT_H2D(dlp, lab_prev, 3 * n);
+    if (field) NCT_H2D(df, field, sizeof(int16_t) * 2 * n);
+    NCT_TRY(nctk_seq_change(ctx, ctx->stream, dl, dlp, h, w, field ? (const int16_t*)df : nullptr, threshold, dr));
+    NCT_D2H(out, dr, sizeof *out);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
 int nct_bds_vote_image(nct_ctx* ctx, const uint8_t* a_bgr, int ah, int aw, const uint8_t* b_bgr, int bh, int bw,
                        const uint32_t* ann, const uint32_t* bnn, int patch, double w_coherence, double w_complete, uint8_t* out_bgr) {
     NCT_CTX_ENTER();

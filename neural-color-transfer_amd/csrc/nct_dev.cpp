@@ -179,6 +179,11 @@ int nct_seq_warp_dev(nct_ctx* ctx, const double* d_x_prev, int h, int w, const i
     return nctk_seq_warp(ctx, ctx->stream, d_x_prev, h, w, d_field, d_x_out);
 }
 
+int nct_seq_change_dev(nct_ctx* ctx, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, const int16_t* d_field, int threshold, nct_seq_change_rec* d_out) {   /* SPEC §6.7 rule 1 */
+    NCT_CTX_ENTER();
+    return nctk_seq_change(ctx, ctx->stream, d_lab, d_lab_prev, h, w, d_field, threshold, d_out);
+}
+
 int nct_seq_motion_field_dev(nct_ctx* ctx, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, const int16_t* d_parent, int ph, int pw, int R, int penalty,
                              int16_t* d_m_out) {                                                                                                      /* SPEC §6.4 rules 1-3 */
     NCT_CTX_ENTER();

@@ -216,6 +216,9 @@ int nctk_seq_motion(nct_ctx* ctx, hipStream_t s, const uint8_t* lab, const uint3
                     int16_t* m_out);
 // SPEC §6.5 rule 3: x_out(p) = x_prev(p + m(p)), the 64-bit words copied, a vector that leaves the grid clamped to it; x_out must not overlap x_prev
 int nctk_seq_warp(nct_ctx* ctx, hipStream_t s, const double* x_prev, int h, int w, const int16_t* field, double* x_out);
+// SPEC §6.7 rule 1: sad = sum_p r(p), changed = #{p : r(p) > threshold}, pixels = h * w, r(p) the three-byte SAD of lab(p) and lab_prev(p + m(p)); field nullable (m = 0).
+// rec: 16 bytes on the device, zeroed and filled on s
+int nctk_seq_change(nct_ctx* ctx, hipStream_t s, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, const int16_t* field, int threshold, nct_seq_change_rec* rec);
 // k_lut.hip — 3D colour look-up tables (SPEC §6.6). W [N^3] / R [N^3][3]: the splat's integer sums (zeroed on s by the splat itself); D [N^3][3]: the displacement
 // field after NCT_LUT_CYCLES V(2,2) cycles; lut [N^3][3] fp32. in / out of the apply may be the same buffer
 #define NCT_LUT_CYCLES 17

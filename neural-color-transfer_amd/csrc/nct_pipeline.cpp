@@ -16,9 +16,12 @@
 // the context's arena and outlives the runs; the frame and the reference at working size are pair_state's src / ref[0] as for a pair.
 // While motion compensation is on (SPEC §6.4, nct_seq_set_motion) it also holds, per level, L packed one word per pixel and the level's field (4 B per level pixel each).
 // A propagated frame (SPEC §6.5) with motion on warps X' out of place: warp_x, one map of the largest level run, reserved by the first such frame.
+// The two counters of the key-frame decision (SPEC §6.7 rule 3) are host integers: they cost no device memory.
 struct seq_state {
     nct_params prm; double tau = 0, sigma = 0;
     long frames = 0;                                           // frames since nct_seq_begin / nct_seq_reset: 0 = the next one is a first frame
+    long gap = 0;                                              // propagated frames since the last full frame, whichever call ran them
+    unsigned long long acc = 0;                                // sum of `changed` over the frames nct_seq_frame_auto propagated since the last full frame
     int ah[5], aw[5], bh[5], bw[5];
     uint8_t* rpyr[4] = {}; float* rfeat[5] = {};
     double* keep_x[5] = {}; uint8_t* keep_lab[5] = {};
@@ -694,7 +697,7 @@ int nct_seq_reset(nct_ctx* ctx) {
     NCT_CTX_ENTER();
     pair_state* P = (pair_state*)ctx->pair;
     if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_reset: no sequence is open (nct_seq_begin first)");
-    P->seq->frames = 0;
+    P->seq->frames = 0; P->seq->gap = 0; P->seq->acc = 0;
     return NCT_OK;
 }
 
@@ -766,6 +769,7 @@ int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr,
     }
     const int rc = process_resident(ctx, &q->prm, timing, levels ? &m : nullptr, levels ? levels->color : nullptr, nullptr, q, seq_levels);
     // a frame that failed may have replaced the state of some levels only: the next frame starts over
+    q->gap = 0; q->acc = 0;                                      // a full frame (and a failed one: the next is a first frame) starts the count over
     if (rc) { q->frames = 0; return rc; }
     q->frames += 1;
     return nct_pair_download(ctx, out_bgr);
@@ -847,8 +851,8 @@ int nct_seq_frame_propagate_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t
     if (rc == NCT_OK) rc = propagate_run(ctx, P, q, out_bgr, timing, seq_levels);
     ctx->tm_on = false; ctx->kt_on = false;
     // a frame that failed may have replaced the state of some levels only: the next frame starts over
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); q->frames = 0; return rc; }
-    q->frames += 1;
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); q->frames = 0; q->gap = 0; q->acc = 0; return rc; }
+    q->frames += 1; q->gap += 1;
     if (!timing) return NCT_OK;
     timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     return read_timing(ctx, timing, false);
@@ -856,6 +860,109 @@ int nct_seq_frame_propagate_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t
 
 int nct_seq_frame_propagate(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing) {
     return nct_seq_frame_propagate_levels(ctx, src_bgr, out_bgr, timing, nullptr);
+}
+
+// ---- adaptive key frames (SPEC §6.7)
+void nct_seq_auto_default(nct_seq_auto* p) {
+    if (!p) return;
+    p->threshold = 24; p->cut_permille = 500; p->key_permille = 100; p->max_gap = 8;
+}
+
+static const char* seq_auto_check(const nct_seq_auto& a) {
+    if (a.threshold < 0 || a.threshold > 765) return "threshold must be in [0, 765]";
+    if (a.cut_permille < 0 || a.cut_permille > 1001) return "cut_permille must be in [0, 1001]";
+    if (a.key_permille < 0 || a.key_permille > 1001) return "key_permille must be in [0, 1001]";
+    if (a.max_gap < 1 || a.max_gap > 1000) return "max_gap must be in [1, 1000]";
+    return nullptr;
+}
+
+// SPEC §6.7 rule 3 on a measured frame: 64-bit integers, in this order. 1001 is "never": changed <= pixels makes the cut's comparison say so by itself; the accumulated
+// count may exceed the pixels, so the key's 1001 is tested apart
+static int seq_decide(const nct_seq_auto& a, const nct_seq_change_rec& c, unsigned long long acc, long gap) {
+    const unsigned long long px = c.pixels;
+    if ((unsigned long long)c.changed * 1000ull >= (unsigned long long)a.cut_permille * px) return NCT_SEQ_CUT;
+    if (gap >= a.max_gap - 1 || (a.key_permille != 1001 && (acc + c.changed) * 1000ull >= (unsigned long long)a.key_permille * px)) return NCT_SEQ_KEY;
+    return NCT_SEQ_PROPAGATED;
+}
+
+// SPEC §6.7 rule 2: what the probe enqueues — the frame into scratch (P->src may still be read by nct_pair_fit_lut), its pyramid, L_t[l] for l = 0 … lambda, with motion on
+// the level's field against the kept packed map into the level's field buffer (scratch between frames), the measure at lambda, 16 bytes back. The kept L, the packed
+// maps, X' and the counters are only read
+static int probe_run(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* src_bgr, int threshold, int lambda, nct_seq_change_rec* rec) {
+    const hipStream_t s = ctx->stream;
+    const size_t N = (size_t)P->sh * P->sw;
+    DevBuf<uint8_t> frame(ctx, N * 3), spyr[4], lab[3];
+    DevBuf<nct_seq_change_rec> d_rec(ctx, 1);
+    if (!frame.ok() || !d_rec.ok()) return NCT_ERR_HIP;
+    NCT_H2D(frame, src_bgr, N * 3);
+    const uint8_t* simg[5]; simg[4] = frame;
+    for (int l = 3; l >= 0; --l) {
+        if (!spyr[l].alloc(ctx, (size_t)q->ah[l] * q->aw[l] * 3)) return NCT_ERR_HIP;
+        NCT_TRY(nctk_resize_u8c3(ctx, s, simg[l + 1], q->ah[l + 1], q->aw[l + 1], spyr[l], q->ah[l], q->aw[l]));
+        simg[l] = spyr[l];
+    }
+    for (int l = 0; l <= lambda; ++l) {
+        const int h = q->ah[l], w = q->aw[l];
+        if (!lab[l].alloc(ctx, (size_t)h * w * 3)) return NCT_ERR_HIP;
+        NCT_TRY(nctk_bgr2lab(ctx, s, simg[l], lab[l], (size_t)h * w));
+        if (q->motion)
+            NCT_TRY(nctk_seq_motion(ctx, s, lab[l], q->keep_pk[l], h, w, l > 0 ? q->field[l - 1] : nullptr, l > 0 ? q->ah[l - 1] : 0, l > 0 ? q->aw[l - 1] : 0,
+                                    l == 0 ? q->mp.radius0 : q->mp.radius, q->mp.penalty, q->field[l]));
+    }
+    NCT_TRY(nctk_seq_change(ctx, s, lab[lambda], q->keep_lab[lambda], q->ah[lambda], q->aw[lambda], q->motion ? q->field[lambda] : nullptr, threshold, d_rec));
+    NCT_D2H(rec, d_rec, sizeof *rec);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
+// the checks of nct_seq_probe / nct_seq_frame_auto, then the probe and the decision; first_ok: a sequence without state is NCT_SEQ_FIRST, not an error
+static int seq_probe_decide(nct_ctx* ctx, const char* who, const uint8_t* src_bgr, const nct_seq_auto* a, bool first_ok, nct_seq_auto* used, nct_seq_decision* d) {
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "%s: no sequence is open (nct_seq_begin first)", who);
+    seq_state* q = P->seq;
+    if (q->frames == 0 && !first_ok)
+        return ctx->fail(NCT_ERR_STATE, "%s: the sequence has no state to compare with (the first frame after nct_seq_begin / nct_seq_reset is nct_seq_frame's)", who);
+    NCT_REQUIRE(src_bgr, "%s: null image", who);
+    if (a) *used = *a; else nct_seq_auto_default(used);
+    if (const char* why = seq_auto_check(*used)) return ctx->fail(NCT_ERR_INVALID, "%s: %s", who, why);
+    memset(d, 0, sizeof *d);
+    d->acc_changed = (uint32_t)std::min<unsigned long long>(q->acc, 0xffffffffull); d->gap = (int)q->gap;
+    if (q->frames == 0) { d->kind = NCT_SEQ_FIRST; d->level = -1; return NCT_OK; }
+    const auto wall0 = std::chrono::steady_clock::now();
+    d->level = std::min(q->prm.levels - 1, 2);
+    const int rc = probe_run(ctx, P, q, src_bgr, used->threshold, d->level, &d->change);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }     // the probe wrote no state: the sequence stays as it was
+    d->probe_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    d->kind = seq_decide(*used, d->change, q->acc, q->gap);
+    return NCT_OK;
+}
+
+int nct_seq_probe(nct_ctx* ctx, const uint8_t* src_bgr, const nct_seq_auto* a, nct_seq_decision* out) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(out, "seq_probe: null out");
+    nct_seq_auto used; nct_seq_decision d;
+    NCT_TRY(seq_probe_decide(ctx, "seq_probe", src_bgr, a, false, &used, &d));
+    *out = d;
+    return NCT_OK;
+}
+
+// SPEC §6.7 rule 4: probe, decide, one of the existing calls, the counters
+int nct_seq_frame_auto(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_auto* a, nct_seq_decision* out) {
+    NCT_CTX_ENTER();
+    // refused before the probe runs; without an open sequence the state error below comes first, as in the other frame calls
+    NCT_REQUIRE(!ctx->pair || !((pair_state*)ctx->pair)->seq || out_bgr, "seq_frame_auto: null image");
+    nct_seq_auto used; nct_seq_decision d;
+    NCT_TRY(seq_probe_decide(ctx, "seq_frame_auto", src_bgr, a, true, &used, &d));
+    seq_state* q = ((pair_state*)ctx->pair)->seq;
+    if (out) *out = d;
+    if (d.kind == NCT_SEQ_PROPAGATED) {
+        const unsigned long long acc = q->acc + d.change.changed;
+        NCT_TRY(nct_seq_frame_propagate(ctx, src_bgr, out_bgr, timing));      // counts the frame in gap
+        q->acc = acc;
+        return NCT_OK;
+    }
+    if (d.kind == NCT_SEQ_CUT) NCT_TRY(nct_seq_reset(ctx));
+    return nct_seq_frame(ctx, src_bgr, out_bgr, timing);                      // zeroes both counters
 }
 
 int nct_working_size(int h, int w, int max_side, int* work_h, int* work_w) {

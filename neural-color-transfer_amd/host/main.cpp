@@ -11,6 +11,7 @@
 // `-seq 1` (+ `-tau`, `-sigma`): consecutive lines with one and the same reference are the frames of a sequence, graded with temporally blended coefficients (SPEC §6.3).
 // `-motion 1` (+ `-mr0`, `-mr`, `-mpen`): the blend of a sequence follows the motion between the frames (SPEC §6.4).
 // `-key N`: only every N-th frame of a sequence runs the whole pair; the others are propagated from the frame before them (SPEC §6.5).
+// `-autokey 1` (+ `-keythr`, `-keycut`, `-keychange`, `-keygap`): the library decides per frame whether it is propagated, a key frame or a scene cut (SPEC §6.7).
 #include <sys/stat.h>
 #include <sys/wait.h>
 #include <fcntl.h>
@@ -114,7 +115,7 @@ std::string stem(const std::string& path) {          // main.cu:524-531 (find_la
 struct Pair { std::string cnt, stl; float bds; std::vector<std::string> refs; std::string err; };
 std::mutex g_print;
 
-struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false, fullres = false, seq = false, motion = false; nct_seq_params sp; nct_seq_motion mp; int key = 1; int rank = 0, world = 1;
+struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false, fullres = false, seq = false, motion = false; nct_seq_params sp; nct_seq_motion mp; int key = 1; bool autokey = false; nct_seq_auto ap; int rank = 0, world = 1;
                 int lut = 0; double lut_lambda = 0.0; bool lutfull = false; };   // -lut N (0 = off), -lutlambda (0 = the library's default), -lutfull 1
 
 // ---- ENABLE_VIS debug outputs (Config.h:8) behind the runtime flag -vis 1: per pyramid level the flow maps of both NNFs (reconstruct_flow,
@@ -507,7 +508,8 @@ std::vector<Group> plan_groups(const std::vector<Pair>& pairs) {
 // one sequence on one context, its frames in file order. The reference is decoded and shrunk once; a frame whose (shrunk) size differs from the open sequence's begins
 // a new one at that frame; a line that cannot be decoded is skipped and the state continues from the last good frame; with -resume 1 the sequence is skipped only if
 // every output is complete, else it is redone from its first frame. With -key N the k-th frame run since the last nct_seq_begin is a full frame iff k % N == 0 and a
-// propagated one (SPEC §6.5) otherwise; a frame that failed left the sequence reset, so the next one is full. Returns the number of lines it finished
+// propagated one (SPEC §6.5) otherwise; a frame that failed left the sequence reset, so the next one is full. With -autokey 1 every frame goes through
+// nct_seq_frame_auto (SPEC §6.7) and the log says what each frame after a sequence's first turned out to be. Returns the number of lines it finished
 size_t run_sequence(nct_ctx* ctx, const Config& cfg, const std::vector<Pair>& pairs, const Group& g) {
     nct_params prm = cfg.prm;
     prm.bds_weight = pairs[g.first].bds;
@@ -555,9 +557,15 @@ size_t run_sequence(nct_ctx* ctx, const Config& cfg, const std::vector<Pair>& pa
             }
             nct_pair_timing tm;
             j.out.resize((size_t)j.cnt.h * j.cnt.w * 3);
-            const bool prop = k % cfg.key != 0;
+            const bool prop = !cfg.autokey && k % cfg.key != 0;
             if (rc == NCT_OK && prop) j.say("Sequence %ld: frame %ld is propagated from the frame before it (-key %d).\n", g.seq, k, cfg.key);
-            if (rc == NCT_OK) rc = prop ? nct_seq_frame_propagate(ctx, j.cnt.px.data(), j.out.data(), &tm) : nct_seq_frame(ctx, j.cnt.px.data(), j.out.data(), &tm);
+            if (rc == NCT_OK && cfg.autokey) {
+                nct_seq_decision d;
+                rc = nct_seq_frame_auto(ctx, j.cnt.px.data(), j.out.data(), &tm, &cfg.ap, &d);
+                if (rc == NCT_OK && d.kind != NCT_SEQ_FIRST)
+                    j.say("Sequence %ld: frame %ld is %s (changed %u of %u at level %d).\n", g.seq, k,
+                          d.kind == NCT_SEQ_PROPAGATED ? "propagated" : d.kind == NCT_SEQ_CUT ? "a scene cut" : "a key frame", d.change.changed, d.change.pixels, d.level);
+            } else if (rc == NCT_OK) rc = prop ? nct_seq_frame_propagate(ctx, j.cnt.px.data(), j.out.data(), &tm) : nct_seq_frame(ctx, j.cnt.px.data(), j.out.data(), &tm);
             k = rc == NCT_OK ? k + 1 : 0;
             if (rc != NCT_OK) { j.say("Error: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; }
             else if (job_lut(ctx, cfg, j)) { log_times(j, prm, tm); store_pair(j); }
@@ -694,6 +702,8 @@ int main(int argc, char** argv) {
     nct_params_default(&cfg.prm);
     nct_seq_params_default(&cfg.sp);
     nct_seq_motion_default(&cfg.mp);
+    nct_seq_auto_default(&cfg.ap);
+    int autokey = 0;
     int motion = 0, key = 1, lut = 0, lutfull = 0;
     double lutlambda = 0.0; bool lutlambda_set = false;
     int gpu = 0, ngpus = 1, seed = 1, inflight = 1, levels = 5, resume = 0, feat16 = 0, vis = 0, fullres = 0, seq = 0, io = -1, pin = 1, world = 1, rank = 0, steal = 0, procs = 0, rccl = 0;
@@ -731,6 +741,11 @@ int main(int argc, char** argv) {
     cl.add("mr", cfg.mp.radius, "[extension] -motion 1: search radius of the refinement at every finer level, in [0, 3].");
     cl.add("mpen", cfg.mp.penalty, "[extension] -motion 1: cost per tap and pixel of displacement from the search centre, in [0, 255].");
     cl.add("key", key, "[extension] -seq 1: N in [1, 1000]: within a sequence only every N-th frame runs the whole pair; the frames between take their colour coefficients from the frame before them through the motion field and run the last level's finish only (SPEC 6.5). 1 = every frame is a full frame.");
+    cl.add("autokey", autokey, "[extension] -seq 1: 1 = the key frames are chosen per frame (SPEC 6.7): a cheap probe measures how much of the frame the motion field does not explain, and the frame is propagated, runs as a key frame, or restarts the sequence at a scene cut; not with -key N > 1.");
+    cl.add("keythr", cfg.ap.threshold, "[extension] -autokey 1: a pixel counts as changed when its three Lab bytes differ from the previous frame's by more than this in sum, in [0, 765].");
+    cl.add("keycut", cfg.ap.cut_permille, "[extension] -autokey 1: a frame with at least this many changed pixels per thousand is a scene cut, in [0, 1001]; 1001 = never.");
+    cl.add("keychange", cfg.ap.key_permille, "[extension] -autokey 1: a frame is a key frame once the changed pixels since the last full frame reach this many per thousand, in [0, 1001]; 1001 = never.");
+    cl.add("keygap", cfg.ap.max_gap, "[extension] -autokey 1: at most this many frames from one full frame to the next, in [1, 1000].");
     cl.add("lut", lut, "[extension] N in {3, 5, 9, 17, 33, 65}: beside each result image write <same name>.cube, a 3D look-up table of N^3 nodes fitted from the source and the result (SPEC 6.6); works in every mode.");
     cl.add("lutlambda", lutlambda, "[extension] -lut N: smoothness weight of the table's fit (> 0; default: the library's, 0.1).");
     cl.add("lutfull", lutfull, "[extension] -lut N: 1 = also write <name>_lut.png, the table applied to the content image at its original size; not with -fullres 1.");
@@ -761,6 +776,12 @@ int main(int argc, char** argv) {
     if (motion && (cfg.mp.penalty < 0 || cfg.mp.penalty > 255)) { printf("Error: -mpen %d is not in [0, 255].\n", cfg.mp.penalty); return -1; }
     if (key < 1 || key > 1000) { printf("Error: -key %d is not in [1, 1000].\n", key); return -1; }
     if (key > 1 && !seq) { printf("Error: -key %d needs -seq 1 (propagated frames belong to a sequence).\n", key); return -1; }
+    if (autokey && !seq) { printf("Error: -autokey 1 needs -seq 1 (key frames belong to a sequence).\n"); return -1; }
+    if (autokey && key > 1) { printf("Error: -autokey 1 cannot be combined with -key %d (the key frames are either chosen or on a grid).\n", key); return -1; }
+    if (autokey && (cfg.ap.threshold < 0 || cfg.ap.threshold > 765)) { printf("Error: -keythr %d is not in [0, 765].\n", cfg.ap.threshold); return -1; }
+    if (autokey && (cfg.ap.cut_permille < 0 || cfg.ap.cut_permille > 1001)) { printf("Error: -keycut %d is not in [0, 1001].\n", cfg.ap.cut_permille); return -1; }
+    if (autokey && (cfg.ap.key_permille < 0 || cfg.ap.key_permille > 1001)) { printf("Error: -keychange %d is not in [0, 1001].\n", cfg.ap.key_permille); return -1; }
+    if (autokey && (cfg.ap.max_gap < 1 || cfg.ap.max_gap > 1000)) { printf("Error: -keygap %d is not in [1, 1000].\n", cfg.ap.max_gap); return -1; }
     for (int a = 1; a < argc; ++a) lutlambda_set = lutlambda_set || !strcmp(argv[a], "-lutlambda");
     if (lut != 0 && lut != 3 && lut != 5 && lut != 9 && lut != 17 && lut != 33 && lut != 65) { printf("Error: -lut %d is not one of 3, 5, 9, 17, 33, 65.\n", lut); return -1; }
     if (lutlambda_set && !lut) { printf("Error: -lutlambda needs -lut N.\n"); return -1; }
@@ -805,6 +826,7 @@ int main(int argc, char** argv) {
     cfg.seq = seq != 0;
     cfg.motion = motion != 0;
     cfg.key = key;
+    cfg.autokey = autokey != 0;
     if (ngpus < 1) ngpus = 1;
     if (inflight < 1) inflight = 1;
     if (inflight > 8) inflight = 8;
@@ -822,9 +844,10 @@ int main(int argc, char** argv) {
     fclose(fp);
     const std::vector<Group> groups = cfg.seq ? plan_groups(pairs) : std::vector<Group>();
     if (plan_only) {
-        std::vector<std::string> seq_of(pairs.size());               // -seq 1: " seq=<sequence>:<index>" behind the lines that are frames, -key N: " prop" behind the propagated ones
+        std::vector<std::string> seq_of(pairs.size());               // -seq 1: " seq=<sequence>:<index>" behind the lines that are frames, -key N: " prop" behind the propagated ones; -autokey 1: " auto" behind every frame but a sequence's first (what it becomes is known only when it runs)
         for (const Group& g : groups)
-            if (g.seq >= 0) for (size_t i = 0; i < g.count; ++i) seq_of[g.first + i] = " seq=" + std::to_string(g.seq) + ":" + std::to_string(i) + (i % (size_t)cfg.key ? " prop" : "");
+            if (g.seq >= 0) for (size_t i = 0; i < g.count; ++i)
+                seq_of[g.first + i] = " seq=" + std::to_string(g.seq) + ":" + std::to_string(i) + (cfg.autokey ? (i ? " auto" : "") : (i % (size_t)cfg.key ? " prop" : ""));
         for (size_t i = 0; i < pairs.size(); ++i) {
             const Pair& p = pairs[i];
             const std::string why = refusal(cfg, p);

@@ -38,7 +38,7 @@ def lib():
     return _lib
 
 
-NCT_VERSION = 116        # include/nct.h
+NCT_VERSION = 117        # include/nct.h
 MAX_REFS = 8             # NCT_MAX_REFS
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -118,6 +118,11 @@ SIGNATURES = {
     "nct_seq_motion_field_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "nct_seq_blend_mc": (C.c_int, [C.c_void_p, _f64p, _f64p, _u8p, _u8p, C.c_int, C.c_int, C.c_double, C.c_double, _f64p, C.c_void_p, C.c_void_p]),
     "nct_seq_blend_mc_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_auto_default": (None, [C.c_void_p]),
+    "nct_seq_change": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "nct_seq_change_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "nct_seq_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_frame_auto": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_lut_params_default": (None, [C.c_void_p]),
     "nct_lut_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_lut_fit_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -304,6 +309,47 @@ class SeqMotion(C.Structure):
         p = SeqMotion()
         lib().nct_seq_motion_default(C.byref(p))
         return p
+
+
+class SeqChange(C.Structure):
+    """struct nct_seq_change_rec (include/nct.h)."""
+    _fields_ = [("sad", C.c_uint64), ("changed", C.c_uint32), ("pixels", C.c_uint32)]
+
+    def as_dict(self):
+        return {"sad": int(self.sad), "changed": int(self.changed), "pixels": int(self.pixels)}
+
+
+class SeqAuto(C.Structure):
+    """struct nct_seq_auto (include/nct.h)."""
+    _fields_ = [("threshold", C.c_int), ("cut_permille", C.c_int), ("key_permille", C.c_int), ("max_gap", C.c_int)]
+
+    @staticmethod
+    def default():
+        p = SeqAuto()
+        lib().nct_seq_auto_default(C.byref(p))
+        return p
+
+
+SEQ_FIRST, SEQ_PROPAGATED, SEQ_KEY, SEQ_CUT = 0, 1, 2, 3        # nct.h NCT_SEQ_*
+
+
+class SeqDecision(C.Structure):
+    """struct nct_seq_decision (include/nct.h)."""
+    _fields_ = [("kind", C.c_int), ("level", C.c_int), ("change", SeqChange), ("acc_changed", C.c_uint32), ("gap", C.c_int), ("probe_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {"kind": self.kind, "level": self.level, "acc_changed": int(self.acc_changed), "gap": self.gap, "probe_ms": self.probe_ms}
+        d.update(self.change.as_dict())
+        return d
+
+
+def seq_auto(threshold=None, cut_permille=None, key_permille=None, max_gap=None):
+    """struct nct_seq_auto with nct_seq_auto_default's values (24, 500, 100, 8) where an argument is left out"""
+    p = SeqAuto.default()
+    for k, v in (("threshold", threshold), ("cut_permille", cut_permille), ("key_permille", key_permille), ("max_gap", max_gap)):
+        if v is not None:
+            setattr(p, k, int(v))
+    return p
 
 
 class ColorStages(C.Structure):
@@ -851,6 +897,51 @@ class Context:
             self.synchronize()
             for p in ins + [do]:
                 self.dev_free(p)
+
+    # ---- adaptive key frames (SPEC §6.7)
+    def seq_change(self, lab, lab_prev, field=None, threshold=24):
+        """nct_seq_change (SPEC §6.7 rule 1): lab / lab_prev h x w x 3 8-bit Lab, field None or int16 [h, w, 2] of (my, mx) -> {"sad", "changed", "pixels"}"""
+        a = np.ascontiguousarray(lab, np.uint8)
+        b = np.ascontiguousarray(lab_prev, np.uint8)
+        h, w = a.shape[:2]
+        f = None if field is None else np.ascontiguousarray(field, np.int16)
+        assert b.shape == a.shape and (f is None or f.size == 2 * h * w)
+        rec = SeqChange()
+        self._chk(self._l.nct_seq_change(self._h, a.ctypes.data, b.ctypes.data, h, w, _ptr(f), int(threshold), C.addressof(rec)))
+        return rec.as_dict()
+
+    def seq_change_dev(self, lab, lab_prev, field=None, threshold=24):
+        """the same through nct_seq_change_dev on arena blocks; the record's block holds 0xff bytes before the call"""
+        a = np.ascontiguousarray(lab, np.uint8)
+        h, w = a.shape[:2]
+        ins = [self.dev_upload(a), self.dev_upload(np.ascontiguousarray(lab_prev, np.uint8))] + ([] if field is None else [self.dev_upload(np.ascontiguousarray(field, np.int16))])
+        do = self.dev_upload(np.full(16, 0xff, np.uint8))
+        try:
+            self._chk(self._l.nct_seq_change_dev(self._h, ins[0], ins[1], h, w, None if field is None else ins[2], int(threshold), do))
+            raw = self.dev_download(do, (16,), np.uint8)
+            return SeqChange.from_buffer_copy(raw.tobytes()).as_dict()
+        finally:
+            self.synchronize()
+            for p in ins + [do]:
+                self.dev_free(p)
+
+    def seq_probe(self, src_bgr, auto=None):
+        """nct_seq_probe (SPEC §6.7 rule 2): the decision the frame would get on the open sequence, nothing changed -> dict (SeqDecision.as_dict); auto: a SeqAuto or
+        None = the defaults"""
+        s = self._seq_frame_arg(src_bgr, "seq_probe")
+        d = SeqDecision()
+        self._chk(self._l.nct_seq_probe(self._h, s.ctypes.data, C.addressof(auto) if auto is not None else None, C.addressof(d)))
+        return d.as_dict()
+
+    def seq_frame_auto(self, src_bgr, auto=None, want_timing=False):
+        """nct_seq_frame_auto (SPEC §6.7 rule 4): probe, decide, run the frame -> (result, decision dict[, timing dict])"""
+        s = self._seq_frame_arg(src_bgr, "seq_frame_auto")
+        out = np.empty_like(s)
+        d = SeqDecision()
+        tm = PairTiming() if want_timing else None
+        self._chk(self._l.nct_seq_frame_auto(self._h, s.ctypes.data, out.ctypes.data, C.addressof(tm) if tm is not None else None,
+                                             C.addressof(auto) if auto is not None else None, C.addressof(d)))
+        return (out, d.as_dict(), tm.as_dict()) if want_timing else (out, d.as_dict())
 
     # ---- 3D colour look-up tables (SPEC §6.6)
     def lut_fit(self, src, res, size=None, lam=None, want_stages=False):
