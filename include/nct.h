@@ -28,9 +28,10 @@ extern "C" {
 /* bumped whenever a struct of this header changes layout or an entry point changes meaning (round 6: 110 — nct_model_layer; nct_pair_timing grew in round 5 without a
  * bump; 111 — nct_multi_levels and the entry points for several references; 112 — frame sequences, nct_seq_*; 113 — nct_seq_levels.motion and motion-compensated
  * sequences, nct_seq_set_motion; 114 — propagated frames, nct_seq_frame_propagate and nct_seq_warp; 115 — the single-layer conv seams nct_conv3x3_dev and
- * nct_conv3x3_pair_dev; 116 — 3D colour look-up tables, nct_lut_*; 117 — adaptive key frames, nct_seq_change, nct_seq_probe and nct_seq_frame_auto). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
+ * nct_conv3x3_pair_dev; 116 — 3D colour look-up tables, nct_lut_*; 117 — adaptive key frames, nct_seq_change, nct_seq_probe and nct_seq_frame_auto; 118 — the upsampling finish and
+ * full-resolution sequences, nct_color_finish_upsample, nct_process_pair_fullres_finish and nct_seq_begin_fullres). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
-#define NCT_VERSION 117
+#define NCT_VERSION 118
 
 typedef enum {
     NCT_OK = 0,
@@ -259,6 +260,24 @@ int nct_process_pair_fullres(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int s
 int nct_color_finish(nct_ctx* ctx, const double* ab, int h, int w, int work_h, int work_w, const uint8_t* s_bgr_full, int H, int W, const nct_params* prm,
                      uint8_t* out_bgr_full, nct_color_stages* stages);
 
+/* ---- the upsampling finish (SPEC §6.8; an extension). The exact finish above costs one WLS solve at the original size. The upsampling finish runs the last level's
+ * finish at the working size as nct_process_pair does, then takes that finish's smoothed coefficient maps (nct_color_stages.ab_wls, [2][h*w][3]), upsamples them to
+ * the original size with U1's arithmetic (nct_resize_f64c3; equal sizes: a copy) and applies them to the original pixels with A1's: per original pixel
+ * Lab = nct_bgr2lab_u8(S0), v = Lab / 255 * a + b clamped to [0, 1], rint(v * 255), then Lab -> BGR in the form NCT_FLAG_LAB2BGR_CUBE selects. One kernel, 3 B read
+ * and 3 B written per original pixel, no original-size intermediate; byte for byte the chain nct_bgr2lab_u8 -> nct_resize_f64c3 x2 -> A1 -> nct_lab2bgr_u8.
+ * nct_color_finish_upsample: host pointers, synchronous; 1 <= h <= H <= 16384, 1 <= w <= W <= 16384, at most 2^26 pixels each. nct_color_finish_upsample_dev: the same on
+ * device pointers, enqueued on the context's stream. A null pointer, a grid out of range or a target smaller than the grid: NCT_ERR_INVALID with a message.
+ * nct_process_pair_fullres_finish: nct_process_pair_fullres with the finish chosen. NCT_FINISH_EXACT is nct_process_pair_fullres (which calls this). With
+ * NCT_FINISH_UPSAMPLE every level, the last level's working-size S2 included, runs as nct_process_pair runs it on the shrunk pair; the rule above then gives the
+ * sh x sw result. A source that is not shrunk gives nct_process_pair's bytes for either finish; any other `finish` is NCT_ERR_INVALID. nct_pair_timing: wls_* then
+ * count the working-size solve, the upsampling pass counts in color_ms. nct_pair_fit_lut afterwards reads the original source and the full result. */
+enum { NCT_FINISH_EXACT = 0, NCT_FINISH_UPSAMPLE = 1 };
+int nct_color_finish_upsample(nct_ctx* ctx, const double* ab_wls, int h, int w, const uint8_t* s_bgr_full, int H, int W, const nct_params* prm, uint8_t* out_bgr_full);
+int nct_color_finish_upsample_dev(nct_ctx* ctx, const double* d_ab_wls, int h, int w, const uint8_t* d_s_bgr_full, int H, int W, const nct_params* prm,
+                                  uint8_t* d_out_bgr_full);
+int nct_process_pair_fullres_finish(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw, int max_side, int finish,
+                                    const nct_params* prm, uint8_t* out_bgr /* sh x sw x 3 */, nct_pair_timing* timing);
+
 /* ---- several references (SPEC §6.2; an extension: the paper describes it, the reference ships the single-reference form only).
  * Every level runs nct_pair_run's correspondence once per reference R_k (its own NNFs, its own random-search radius max(H, W, RH_k, RW_k), the single-pair seeds),
  * which gives K guidance images G_k and matching errors E_k on the source's level grid. The selection then labels every pixel with the reference whose error,
@@ -339,6 +358,17 @@ typedef struct nct_seq_motion { int radius0, radius, penalty; } nct_seq_motion;
 void nct_seq_motion_default(nct_seq_motion* p);     /* 3, 1, 1 */
 int nct_seq_set_motion(nct_ctx* ctx, const nct_seq_motion* motion);
 int nct_seq_begin(nct_ctx* ctx, const uint8_t* ref_bgr, int rh, int rw, int sh, int sw, const nct_params* prm, const nct_seq_params* seq);
+/* Full-resolution sequences (SPEC §6.9): nct_seq_begin_fullres opens a sequence whose reference and frames arrive at their ORIGINAL size (limits: nct_working_size's).
+ * Both are shrunk on the device by nct_working_size's rule with nct_resize_u8c3's arithmetic — the reference once, every frame when it arrives. Until nct_seq_end every
+ * frame call above and below (nct_seq_frame, _levels, _propagate, _propagate_levels, nct_seq_probe, nct_seq_frame_auto) takes sh x sw originals and returns sh x sw
+ * bytes. Everything the sequence keeps — X', L, packed maps, fields, the counters — lives on the working-size level grids and equals, word for word, the state of
+ * nct_seq_begin(shrunk reference, working size) fed the shrunk frames, for either finish: probe records and nct_seq_frame_auto's decisions are that sequence's. Only
+ * the finish of the last level run differs: NCT_FINISH_EXACT — nct_color_finish(X'_t[top], h, w, work_h, work_w, S0_t); NCT_FINISH_UPSAMPLE — the working-size finish,
+ * then nct_color_finish_upsample of its ab_wls onto S0_t. With NCT_FINISH_EXACT a first frame (and a frame after nct_seq_reset) equals nct_process_pair_fullres byte for
+ * byte; with frames that need no shrinking every call returns the nct_seq_begin sequence's bytes. nct_seq_frame_levels: `levels` must be NULL (its result[] arrays have
+ * no single size: NCT_ERR_INVALID), seq_levels reports the working-size maps. The original frame and its result stay in the arena for the life of the sequence
+ * (nct_pair_fit_lut reads them); the exact finish's transients go back after every frame. A bad finish or max_side or a size outside the limits: NCT_ERR_INVALID. */
+int nct_seq_begin_fullres(nct_ctx* ctx, const uint8_t* ref_bgr, int rh, int rw, int sh, int sw, int max_side, int finish, const nct_params* prm, const nct_seq_params* seq);
 int nct_seq_frame(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing);
 int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels);
 int nct_seq_frame_propagate(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing);

@@ -22,11 +22,11 @@
 #include "nct_device.h"
 #include "nct_detmath.h"
 #include "nct_reduce.h"
+#include "nct_pixel.h"                               // LAB_D, apply_px
 #include <cstring>
 #include <cstdio>
 #include <rocprim/device/device_radix_sort.hpp>   // rocPRIM directly (no CUB-compatibility layer)
 
-#define LAB_D(u) ((double)(u) * (1.0 / 255.0))      // Mat::convertTo(CV_64F, 1/255)
 
 // ================================================================= T1 local statistics
 __global__ void k_local_stats(const uint8_t* __restrict__ cnt, const uint8_t* __restrict__ stl, int h, int w, double eps,
@@ -99,10 +99,7 @@ __global__ void k_roughness(const double* __restrict__ a, const double* __restri
 __global__ void k_apply(const double* __restrict__ a, const double* __restrict__ b, const uint8_t* __restrict__ lab, int n, uint8_t* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * 3) return;
-    double v = LAB_D(lab[i]) * a[i] + b[i];
-    v = v > 0.0 ? v : 0.0; v = v < 1.0 ? v : 1.0;
-    const int q = (int)rint(v * 255.0);
-    out[i] = (uint8_t)(q < 0 ? 0 : (q > 255 ? 255 : q));
+    out[i] = apply_px(a[i], b[i], lab[i]);
 }
 
 // ================================================================= S2 WLS: (diag(r) + L) x = r x0, 6 right-hand sides
@@ -136,7 +133,7 @@ static int dbg_copy(nct_ctx* ctx, hipStream_t s, int16_t* host, const int16_t* d
 // level). The pipeline's own levels pass H x W = Hw x Ww; the full-resolution entry passes the original source (SPEC §6.1). Index arithmetic is
 // int for pixels (N <= 2^26) and size_t for every element offset past 3 N.
 int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int Hw, int Ww, const uint8_t* s_lab_full, int H, int W,
-                      const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg) {
+                      const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg, const nct_finish_up* up) {
     NCT_REQUIRE(h > 0 && w > 0 && H >= h && W >= w && H <= NCT_FINISH_MAX_SIDE && W <= NCT_FINISH_MAX_SIDE && (long long)H * W <= NCT_FINISH_MAX_PIXELS,
                 "color finish: target %dx%d outside [%dx%d, %d per side, %lld px]", W, H, w, h, NCT_FINISH_MAX_SIDE, (long long)NCT_FINISH_MAX_PIXELS);
     // ---------------- U1: bilinear upsample to full resolution + roughness
@@ -172,13 +169,15 @@ int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w
     if (dbg) NCT_TRY(dbg_copy(ctx, s, dbg->ab_wls, X, (size_t)6 * N));
     // ---------------- A1
     hipLaunchKernelGGL(k_apply, dim3(cdiv(3 * N, 256)), dim3(256), 0, s, (const double*)Xa, (const double*)Xb, s_lab_full, N, out_lab_full); LCHK();
+    // ---------------- SPEC §6.8: the same smoothed maps onto the original source
+    if (up) NCT_TRY(nctk_finish_upsample(ctx, s, X, H, W, up->s_bgr, up->H, up->W, up->form, up->out_bgr));
     return 0;
 }
 
 int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, const uint8_t* s_lab_level, const uint8_t* g_lab_level,
                               const uint8_t* s_lab_full, const int* knn_id, const double* knn_w, int layer, int h, int w, int H, int W,
                               const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg, const nct_s1_graph* graph,
-                              const nct_finish_target* fin, const nct_seq_link* seq) {
+                              const nct_finish_target* fin, const nct_seq_link* seq, const nct_finish_up* up) {
     const int n = h * w;
     const int nbl = cdiv(n, 256);
     // ---------------- T1 + T2
@@ -235,8 +234,10 @@ int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, con
         if (seq->field) NCT_TRY(nctk_seq_pack(ctx, s, s_lab_level, n, seq->keep_pk));
         NCT_TRY(dbg_copy(ctx, s, seq->ab_blend_host, seq->keep_x, (size_t)6 * n));
         if (tmap.ok()) NCT_TRY(dbg_copy(ctx, s, seq->tau_map_host, tmap, n));
-        return nctk_color_finish(ctx, s, seq->keep_x, h, w, H, W, s_lab_full, H, W, prm, out_lab_full, dbg);
+        // a full-resolution sequence (SPEC §6.9 rule 2) finishes X'_t on the original frame like a pair finishes S1's output
+        if (fin) return nctk_color_finish(ctx, s, seq->keep_x, h, w, H, W, fin->s_lab, fin->H, fin->W, prm, fin->out_lab, dbg);
+        return nctk_color_finish(ctx, s, seq->keep_x, h, w, H, W, s_lab_full, H, W, prm, out_lab_full, dbg, up);
     }
     if (fin) return nctk_color_finish(ctx, s, x, h, w, H, W, fin->s_lab, fin->H, fin->W, prm, fin->out_lab, dbg);
-    return nctk_color_finish(ctx, s, x, h, w, H, W, s_lab_full, H, W, prm, out_lab_full, dbg);
+    return nctk_color_finish(ctx, s, x, h, w, H, W, s_lab_full, H, W, prm, out_lab_full, dbg, up);
 }

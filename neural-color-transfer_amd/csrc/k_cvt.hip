@@ -7,14 +7,11 @@
 // All kernels are trivially bandwidth bound (3-24 B per pixel).
 #include "nct_internal.h"
 #include "nct_device.h"
+#include "nct_pixel.h"
 #include <cmath>
 #include <mutex>
 
 namespace {
-enum { LAB_SHIFT = 12, LAB_SHIFT2 = 15, GAMMA_SHIFT = 3, CBRT_TAB = 256 * 3 / 2 * (1 << GAMMA_SHIFT), GAMMA_TAB = 1024 };
-
-struct CvtTables { unsigned short gamma[256]; unsigned short cbrt[CBRT_TAB]; float inv_gamma[GAMMA_TAB * 4]; int coeffs[9]; float l2r[9]; };
-
 inline int cv_round_h(double v) { return (int)lrint(v); }
 inline unsigned short sat_u16(float v) { int i = cv_round_h(v); return (unsigned short)(i < 0 ? 0 : (i > 65535 ? 65535 : i)); }
 
@@ -76,32 +73,14 @@ static int get_tables(nct_ctx* ctx, const CvtTables** out) {
     *out = ((cvt_dev*)ctx->cvt)->d;
     return 0;
 }
+int nctk_cvt_tables(nct_ctx* ctx, const void** out) { const CvtTables* t; NCT_TRY(get_tables(ctx, &t)); *out = t; return 0; }
 void nct_cvt_free(nct_ctx* ctx) { if (ctx->cvt) { cvt_dev* cd = (cvt_dev*)ctx->cvt; if (cd->d) (void)hipFree(cd->d); delete cd; ctx->cvt = nullptr; } }
 
-#define DESCALE(x, n) (((x) + (1 << ((n) - 1))) >> (n))
-__device__ __forceinline__ unsigned char sat8(int v) { return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
-
+// the per-pixel bodies live in nct_pixel.h (the upsampling finish shares them)
 __global__ void k_bgr2lab(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, size_t n, const CvtTables* __restrict__ t) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int Lscale = (116 * 255 + 50) / 100;
-    const int Lshift = -((16 * 255 * (1 << LAB_SHIFT2) + 50) / 100);
-    const int R = t->gamma[src[i * 3]], G = t->gamma[src[i * 3 + 1]], B = t->gamma[src[i * 3 + 2]];
-    const int* C = t->coeffs;
-    const int fX = t->cbrt[DESCALE(R * C[0] + G * C[1] + B * C[2], LAB_SHIFT)];
-    const int fY = t->cbrt[DESCALE(R * C[3] + G * C[4] + B * C[5], LAB_SHIFT)];
-    const int fZ = t->cbrt[DESCALE(R * C[6] + G * C[7] + B * C[8], LAB_SHIFT)];
-    dst[i * 3] = sat8(DESCALE(Lscale * fY + Lshift, LAB_SHIFT2));
-    dst[i * 3 + 1] = sat8(DESCALE(500 * (fX - fY) + 128 * (1 << LAB_SHIFT2), LAB_SHIFT2));
-    dst[i * 3 + 2] = sat8(DESCALE(200 * (fY - fZ) + 128 * (1 << LAB_SHIFT2), LAB_SHIFT2));
-}
-
-__device__ __forceinline__ float spline_eval(float x, const float* __restrict__ tab) {
-    int ix = (int)floorf(x);
-    ix = ix < 0 ? 0 : (ix > GAMMA_TAB - 1 ? GAMMA_TAB - 1 : ix);
-    x -= (float)ix;
-    tab += ix * 4;
-    return ((tab[3] * x + tab[2]) * x + tab[1]) * x + tab[0];
+    bgr2lab_px(src[i * 3], src[i * 3 + 1], src[i * 3 + 2], t, dst[i * 3], dst[i * 3 + 1], dst[i * 3 + 2]);
 }
 
 // CV_Lab2BGR on 8U = Lab2RGB_b: L * 100/255, a - 128, b - 128 -> float Lab2RGB_f -> * 255 -> saturate_cast<uchar> (cvRound). Two forms of Lab2RGB_f exist in
@@ -116,32 +95,7 @@ template <int FORM>
 __global__ void k_lab2bgr(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, size_t n, const CvtTables* __restrict__ t) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float li = (float)src[i * 3] * (100.f / 255.f), ai = (float)((int)src[i * 3 + 1] - 128), bi = (float)((int)src[i * 3 + 2] - 128);
-    float fx, y, fz;
-    if constexpr (FORM == 1) {
-        const float fy = (li + 16.f) * (1.f / 116.f);
-        fx = fy + ai * 0.002f; fz = fy - bi * 0.005f;
-        y = fy * fy * fy; fx = fx * fx * fx; fz = fz * fz * fz;
-    } else {
-        const float lThresh = 0.008856f * 903.3f;
-        const float fThresh = 7.787f * 0.008856f + 16.0f / 116.0f;
-        float fy;
-        if (li <= lThresh) { y = li / 903.3f; fy = 7.787f * y + 16.0f / 116.0f; }
-        else { fy = (li + 16.0f) / 116.0f; y = fy * fy * fy; }
-        fx = ai / 500.0f + fy; fz = fy - bi / 200.0f;
-        fx = fx <= fThresh ? (fx - 16.0f / 116.0f) / 7.787f : fx * fx * fx;
-        fz = fz <= fThresh ? (fz - 16.0f / 116.0f) / 7.787f : fz * fz * fz;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        float v = t->l2r[k * 3] * fx + t->l2r[k * 3 + 1] * y + t->l2r[k * 3 + 2] * fz;
-        if constexpr (FORM == 0) v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
-        v = spline_eval(v * (float)GAMMA_TAB, t->inv_gamma);
-        v = v * 255.f;
-        // saturate_cast<uchar>(float) = saturate(cvRound(v)); the clamp in float first keeps the conversion defined for extrapolated values
-        v = v < -1.f ? -1.f : (v > 256.f ? 256.f : v);
-        dst[i * 3 + k] = sat8((int)rintf(v));
-    }
+    lab2bgr_px<FORM>(src[i * 3], src[i * 3 + 1], src[i * 3 + 2], t, dst + i * 3);
 }
 
 int nctk_bgr2lab(nct_ctx* ctx, hipStream_t s, const uint8_t* src, uint8_t* dst, size_t npix) {
@@ -159,18 +113,6 @@ int nctk_lab2bgr(nct_ctx* ctx, hipStream_t s, const uint8_t* src, uint8_t* dst, 
 }
 
 // ---------------------------------------------------------------- resize
-struct LinCoef { int s; float a0, a1; bool tail; };     // tail: dx >= xmax => D = S[s] * ONE
-__device__ __forceinline__ LinCoef lin_coef(int d, int ssize, int dsize) {
-    const double scale = (double)ssize / (double)dsize;
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { f = 0.f; s = 0; }
-    bool tail = false;
-    if (s + 1 >= ssize) { tail = true; if (s >= ssize - 1) { f = 0.f; s = ssize - 1; } }
-    return LinCoef{s, 1.f - f, f, tail};
-}
-
 __global__ void k_resize_u8c3(const uint8_t* __restrict__ src, int sh, int sw, uint8_t* __restrict__ dst, int dh, int dw, int area2) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= dh * dw) return;
@@ -213,15 +155,10 @@ __global__ void k_resize_f64c3(const double* __restrict__ src, int sh, int sw, d
     const int dy = i / dw, dx = i - dy * dw;
     const LinCoef cx = lin_coef(dx, sw, dw), cy = lin_coef(dy, sh, dh);
     const int sy0 = cy.s, sy1 = min(cy.s + 1, sh - 1), sx1 = min(cx.s + 1, sw - 1);
-    const double a0 = (double)cx.a0, a1 = (double)cx.a1, b0 = (double)cy.a0, b1 = (double)cy.a1;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double p00 = src[((size_t)sy0 * sw + cx.s) * 3 + c], p01 = src[((size_t)sy0 * sw + sx1) * 3 + c];
-        const double p10 = src[((size_t)sy1 * sw + cx.s) * 3 + c], p11 = src[((size_t)sy1 * sw + sx1) * 3 + c];
-        const double r0 = cx.tail ? p00 * 1.0 : p00 * a0 + p01 * a1;
-        const double r1 = cx.tail ? p10 * 1.0 : p10 * a0 + p11 * a1;
-        dst[(size_t)i * 3 + c] = r0 * b0 + r1 * b1;
-    }
+    for (int c = 0; c < 3; ++c)
+        dst[(size_t)i * 3 + c] = resize_f64_px(src[((size_t)sy0 * sw + cx.s) * 3 + c], src[((size_t)sy0 * sw + sx1) * 3 + c],
+                                               src[((size_t)sy1 * sw + cx.s) * 3 + c], src[((size_t)sy1 * sw + sx1) * 3 + c], cx, cy);
 }
 
 int nctk_resize_f64c3(nct_ctx* ctx, hipStream_t s, const double* src, int sh, int sw, double* dst, int dh, int dw) {

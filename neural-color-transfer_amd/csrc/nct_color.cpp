@@ -139,4 +139,22 @@ int nct_color_finish(nct_ctx* ctx, const double* ab, int h, int w, int work_h, i
     return NCT_OK;
 }
 
+// the upsampling finish alone (SPEC §6.8): the working-size S2 output upsampled and applied to the original source in one kernel (k_finish_up.hip)
+int nct_color_finish_upsample(nct_ctx* ctx, const double* ab_wls, int h, int w, const uint8_t* s_bgr_full, int H, int W, const nct_params* prm, uint8_t* out_bgr_full) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(ab_wls && s_bgr_full && prm && out_bgr_full, "color_finish_upsample: null pointer");
+    NCT_REQUIRE(h >= 1 && w >= 1 && h <= NCT_FINISH_MAX_SIDE && w <= NCT_FINISH_MAX_SIDE && (long long)h * w <= NCT_FINISH_MAX_PIXELS,
+                "color_finish_upsample: grid %dx%d outside [1x1, 16384 per side, 2^26 px]", w, h);
+    NCT_REQUIRE(H >= h && W >= w, "color_finish_upsample: target %dx%d smaller than the grid %dx%d", W, H, w, h);
+    NCT_REQUIRE(H <= NCT_FINISH_MAX_SIDE && W <= NCT_FINISH_MAX_SIDE && (long long)H * W <= NCT_FINISH_MAX_PIXELS, "color_finish_upsample: target %dx%d above 16384 per side or 2^26 pixels", W, H);
+    const size_t n = (size_t)h * w, N = (size_t)H * W;
+    DevBuf<double> x(ctx, 6 * n);
+    DevBuf<uint8_t> sf(ctx, N * 3), obgr(ctx, N * 3);
+    if (!x.ok() || !sf.ok() || !obgr.ok()) return NCT_ERR_HIP;
+    NCT_H2D(x, ab_wls, sizeof(double) * 6 * n); NCT_H2D(sf, s_bgr_full, N * 3);
+    NCT_TRY(nctk_finish_upsample(ctx, ctx->stream, x, h, w, sf, H, W, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0, obgr));
+    NCT_D2H(out_bgr_full, obgr, N * 3); NCT_SYNC();
+    return NCT_OK;
+}
+
 }  // extern "C"

@@ -195,4 +195,11 @@ int nct_seq_motion_field_dev(nct_ctx* ctx, const uint8_t* d_lab, const uint8_t* 
     return nctk_seq_motion(ctx, ctx->stream, d_lab, pk, h, w, d_parent, ph, pw, R, penalty, d_m_out);
 }
 
+int nct_color_finish_upsample_dev(nct_ctx* ctx, const double* d_ab_wls, int h, int w, const uint8_t* d_s_bgr_full, int H, int W, const nct_params* prm,
+                                  uint8_t* d_out_bgr_full) {                                                                                          /* SPEC §6.8 */
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(prm, "color_finish_upsample_dev: null pointer");
+    return nctk_finish_upsample(ctx, ctx->stream, d_ab_wls, h, w, d_s_bgr_full, H, W, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0, d_out_bgr_full);
+}
+
 }  // extern "C"

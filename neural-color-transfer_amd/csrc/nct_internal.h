@@ -137,6 +137,7 @@ int nctk_bgr2lab(nct_ctx* ctx, hipStream_t s, const uint8_t* src, uint8_t* dst, 
 int nctk_lab2bgr(nct_ctx* ctx, hipStream_t s, const uint8_t* src, uint8_t* dst, size_t npix, int form = 0 /* 0 = piecewise form (default), 1 = plain-cube form: k_cvt.hip */);
 int nctk_resize_u8c3(nct_ctx* ctx, hipStream_t s, const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw);
 int nctk_resize_f64c3(nct_ctx* ctx, hipStream_t s, const double* src, int sh, int sw, double* dst, int dh, int dw);
+int nctk_cvt_tables(nct_ctx* ctx, const void** tables);   // the context's conversion tables on the device (struct CvtTables, nct_pixel.h), built at first use
 void nct_cvt_free(nct_ctx* ctx);
 void nct_pair_free(nct_ctx* ctx);   // nct_pipeline.cpp
 // k_cluster.hip
@@ -190,15 +191,21 @@ struct nct_finish_target { const uint8_t* s_lab; int H, W; uint8_t* out_lab; };
 // and the result is copied to keep_x. motion_host (nullable): the field's host copy
 struct nct_seq_link { double* keep_x = nullptr; uint8_t* keep_lab = nullptr; bool blend = false; double tau = 0, sigma = 0; double* ab_blend_host = nullptr; double* tau_map_host = nullptr;
                       uint32_t* keep_pk = nullptr; int16_t* field = nullptr; const int16_t* parent = nullptr; int ph = 0, pw = 0, R = 0, penalty = 0; int16_t* motion_host = nullptr; };
+// the upsampling finish behind a working-size finish (SPEC §6.8): the original source in BGR at H x W, where its result goes, the Lab -> BGR form
+struct nct_finish_up { const uint8_t* s_bgr; int H, W; uint8_t* out_bgr; int form; };
 // H x W: the working size (S1's dWeight); fin (nullable) retargets U1 / S2 / A1 — null: they target H x W, s_lab_full, out_lab_full
 int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, const uint8_t* s_lab_level, const uint8_t* g_lab_level,
                               const uint8_t* s_lab_full, const int* knn_id, const double* knn_w, int layer, int h, int w, int H, int W,
                               const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg,
                               const nct_s1_graph* graph = nullptr /* the level's prebuilt graph part of S1; null: built inside, on s */,
-                              const nct_finish_target* fin = nullptr, const nct_seq_link* seq = nullptr /* a frame of a sequence (SPEC §6.3): blend S1's output with the kept state */);
-// U1 + roughness + S2 + A1 of coefficients x ([2][h*w][3], device) onto the grid H x W of s_lab_full; Hw x Ww = the working size (the x4 of S2's lambda)
+                              const nct_finish_target* fin = nullptr, const nct_seq_link* seq = nullptr /* a frame of a sequence (SPEC §6.3): blend S1's output with the kept state */,
+                              const nct_finish_up* up = nullptr /* after the finish: its S2 output upsampled onto the original source (SPEC §6.8) */);
+// U1 + roughness + S2 + A1 of coefficients x ([2][h*w][3], device) onto the grid H x W of s_lab_full; Hw x Ww = the working size (the x4 of S2's lambda).
+// up (nullable): S2's output, still on the device, then also goes through the upsampling finish onto up's source
 int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int Hw, int Ww, const uint8_t* s_lab_full, int H, int W,
-                      const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg);
+                      const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg, const nct_finish_up* up = nullptr);
+// k_finish_up.hip — SPEC §6.8: ab_wls ([2][h*w][3], device) upsampled (U1's arithmetic) and applied (A1's) to s_bgr_full (H x W >= h x w), BGR in, BGR out, one kernel
+int nctk_finish_upsample(nct_ctx* ctx, hipStream_t s, const double* ab_wls, int h, int w, const uint8_t* s_bgr_full, int H, int W, int form, uint8_t* out_bgr_full);
 // SPEC §6.1 rule 1 + the limits of rule 5: nullptr and the working size, or the reason the image is refused (a static string)
 const char* nct_working_size_rule(int h, int w, int max_side, int* work_h, int* work_w);
 void nct_set_ctxless_error(const char* msg);   // nct_api.cpp

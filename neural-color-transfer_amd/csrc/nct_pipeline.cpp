@@ -17,6 +17,8 @@
 // While motion compensation is on (SPEC §6.4, nct_seq_set_motion) it also holds, per level, L packed one word per pixel and the level's field (4 B per level pixel each).
 // A propagated frame (SPEC §6.5) with motion on warps X' out of place: warp_x, one map of the largest level run, reserved by the first such frame.
 // The two counters of the key-frame decision (SPEC §6.7 rule 3) are host integers: they cost no device memory.
+// A full-resolution sequence (SPEC §6.9, nct_seq_begin_fullres) keeps all of that on the working-size grids and adds the frame at its original size H0 x W0 and
+// its result: pair_state's full_src / full_out, which live as long as the sequence and are what nct_pair_fit_lut reads.
 struct seq_state {
     nct_params prm; double tau = 0, sigma = 0;
     long frames = 0;                                           // frames since nct_seq_begin / nct_seq_reset: 0 = the next one is a first frame
@@ -28,6 +30,7 @@ struct seq_state {
     bool motion = false; nct_seq_motion mp = {0, 0, 0};
     uint32_t* keep_pk[5] = {}; int16_t* field[5] = {};
     double* warp_x = nullptr;
+    bool fullres = false; int H0 = 0, W0 = 0, finish = NCT_FINISH_EXACT;
 };
 struct pair_state {
     uint8_t *src = nullptr, *out = nullptr;                    // device BGR images
@@ -131,7 +134,8 @@ static int read_timing(nct_ctx* ctx, nct_pair_timing* timing, bool count) {
 }
 
 // the full-resolution finish of the last level (nct_process_pair_fullres, SPEC §6.1): the original source on the device and where its result goes
-struct fullres_target { const uint8_t* src; int H, W; uint8_t* out; };
+// finish: NCT_FINISH_EXACT moves U1 / S2 / A1 there, NCT_FINISH_UPSAMPLE leaves them at the working size and upsamples S2's output (SPEC §6.8)
+struct fullres_target { const uint8_t* src; int H, W; uint8_t* out; int finish; };
 
 // what one reference owns during a run (SPEC §6.2): its image pyramid, its five un-normalised taps (HWC, indexed by level), its NNFs of both directions (kept from
 // level to level) and its R -> S distances; with several references also its G_k and E_k
@@ -426,30 +430,34 @@ struct pair_run {
         if (cs) { dbg.ab_local = cs->ab_local; dbg.ab_nonlocal = cs->ab_nonlocal; dbg.ab_up = cs->ab_up; dbg.rough = cs->roughness; dbg.ab_wls = cs->ab_wls; dbg.cg_iters = cs->cg_iters; }
         const nct_s1_graph s1graph = s1_graph_of(l);
         const int cube = (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0;
-        if (fin && l == nlevels - 1) {
+        // a frame of a sequence: the blend between S1 and the finish (SPEC §6.3 rule 3); the first frame and tau == 0 only keep the state, with no blend launch
+        nct_seq_link link;
+        if (seq) {
+            link.keep_x = seq->keep_x[l]; link.keep_lab = seq->keep_lab[l]; link.blend = seq->frames > 0 && seq->tau > 0.0; link.tau = seq->tau; link.sigma = seq->sigma;
+            link.ab_blend_host = slv ? slv->ab_blend[l] : nullptr; link.tau_map_host = slv ? slv->tau_map[l] : nullptr;
+        }
+        if (seq && seq->motion) {
+            // SPEC §6.4: the first level run searches radius0 around (0, 0), every other level radius around twice the previous level's vector
+            link.keep_pk = seq->keep_pk[l]; link.field = seq->field[l]; link.R = l == 0 ? seq->mp.radius0 : seq->mp.radius; link.penalty = seq->mp.penalty;
+            if (l > 0) { link.parent = seq->field[l - 1]; link.ph = ah[l - 1]; link.pw = aw[l - 1]; }
+            link.motion_host = slv ? slv->motion[l] : nullptr;
+        }
+        const bool last = l == nlevels - 1;
+        if (fin && last && fin->finish == NCT_FINISH_EXACT) {
             // the last level finishes on the original source: S0 in Lab once, here (its time counts as colour stage), U1 / S2 / A1 at H0 x W0
             const size_t N0 = (size_t)fin->H * fin->W;
             DevBuf<uint8_t> s0_lab(ctx, N0 * 3), out0_lab(ctx, N0 * 3);
             if (!s0_lab.ok() || !out0_lab.ok()) return NCT_ERR_HIP;
             NCT_TRY(nctk_bgr2lab(ctx, s, fin->src, s0_lab, N0));
             const nct_finish_target ft{s0_lab, fin->H, fin->W, out0_lab};
-            NCT_TRY(nctk_local_color_transfer(ctx, s, err, side.slab[l], g_lab_l, s_lab_full, side.knn_ids[l], side.knn_ws[l], l, ah[l], aw[l], H, W, cp, out_lab, timing ? &dbg : nullptr, &s1graph, &ft));
+            NCT_TRY(nctk_local_color_transfer(ctx, s, err, side.slab[l], g_lab_l, s_lab_full, side.knn_ids[l], side.knn_ws[l], l, ah[l], aw[l], H, W, cp, out_lab, timing ? &dbg : nullptr, &s1graph, &ft,
+                                              seq ? &link : nullptr));
             NCT_TRY(nctk_lab2bgr(ctx, s, out0_lab, fin->out, N0, cube));
         } else {
-            // a frame of a sequence: the blend between S1 and the finish (SPEC §6.3 rule 3); the first frame and tau == 0 only keep the state, with no blend launch
-            nct_seq_link link;
-            if (seq) {
-                link.keep_x = seq->keep_x[l]; link.keep_lab = seq->keep_lab[l]; link.blend = seq->frames > 0 && seq->tau > 0.0; link.tau = seq->tau; link.sigma = seq->sigma;
-                link.ab_blend_host = slv ? slv->ab_blend[l] : nullptr; link.tau_map_host = slv ? slv->tau_map[l] : nullptr;
-            }
-            if (seq && seq->motion) {
-                // SPEC §6.4: the first level run searches radius0 around (0, 0), every other level radius around twice the previous level's vector
-                link.keep_pk = seq->keep_pk[l]; link.field = seq->field[l]; link.R = l == 0 ? seq->mp.radius0 : seq->mp.radius; link.penalty = seq->mp.penalty;
-                if (l > 0) { link.parent = seq->field[l - 1]; link.ph = ah[l - 1]; link.pw = aw[l - 1]; }
-                link.motion_host = slv ? slv->motion[l] : nullptr;
-            }
+            // the upsampling finish (SPEC §6.8): the last level finishes at the working size as ever, its S2 output then goes onto the original source
+            const nct_finish_up up{fin ? fin->src : nullptr, fin ? fin->H : 0, fin ? fin->W : 0, fin ? fin->out : nullptr, cube};
             NCT_TRY(nctk_local_color_transfer(ctx, s, err, side.slab[l], g_lab_l, s_lab_full, side.knn_ids[l], side.knn_ws[l], l, ah[l], aw[l], H, W, cp, out_lab, (timing || cs) ? &dbg : nullptr, &s1graph,
-                                              nullptr, seq ? &link : nullptr));
+                                              nullptr, seq ? &link : nullptr, (fin && last) ? &up : nullptr));
             if (cs && cs->wls_iters) for (int q = 0; q < 6; ++q) cs->wls_iters[q] = wls_it[q];
             NCT_TRY(nctk_lab2bgr(ctx, s, out_lab, P->out, N, cube));
         }
@@ -504,8 +512,11 @@ static int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing
     NCT_REQUIRE(!fin || (!lv && !color), "process: no level intermediates with a full-resolution finish");
     NCT_REQUIRE(!color || P->K == 1, "process: nct_pair_levels describes a pair; several references report through nct_multi_levels");
     // a new run on the resident images: an earlier full-resolution run is no longer the last one, and its two original-size images go back to the arena
-    if (P->full_src) { ctx->release(P->full_src); P->full_src = nullptr; }
-    if (P->full_out) { ctx->release(P->full_out); P->full_out = nullptr; }
+    // (a full-resolution sequence keeps its two for its whole life: SPEC §6.9 rule 6)
+    if (!(seq && seq->fullres)) {
+        if (P->full_src) { ctx->release(P->full_src); P->full_src = nullptr; }
+        if (P->full_out) { ctx->release(P->full_out); P->full_out = nullptr; }
+    }
     P->finished = false;
     if (timing) memset(timing, 0, sizeof *timing);
     auto wall0 = std::chrono::steady_clock::now();
@@ -702,7 +713,8 @@ int nct_seq_reset(nct_ctx* ctx) {
 }
 
 // the reference once: upload, pyramid (main.cu:104-108), one VGG19 forward with all five taps kept channel-last; and the per-level state
-static int seq_prepare(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* ref_bgr, int rh, int rw, int sh, int sw) {
+// rh0 x rw0: the reference as the caller holds it — larger than rh x rw only in a full-resolution sequence, which shrinks it on the device (SPEC §6.9)
+static int seq_prepare(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* ref_bgr, int rh0, int rw0, int rh, int rw, int sh, int sw) {
     hipStream_t s = ctx->stream;
     { int h = sh, w = sw, h2 = rh, w2 = rw;
       for (int t = 0; t < 5; ++t) { q->ah[4 - t] = h; q->aw[4 - t] = w; q->bh[4 - t] = h2; q->bw[4 - t] = w2; h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; h2 = (h2 - 1) / 2 + 1; w2 = (w2 - 1) / 2 + 1; } }
@@ -718,7 +730,18 @@ static int seq_prepare(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t*
             if (!(q->keep_x[l] = (double*)ctx->alloc(sizeof(double) * 6 * n)) || !(q->keep_lab[l] = (uint8_t*)ctx->alloc(n * 3))) return NCT_ERR_HIP;
         }
     }
-    NCT_H2D(P->ref[0], ref_bgr, (size_t)rh * rw * 3);
+    if (rh0 == rh && rw0 == rw) NCT_H2D(P->ref[0], ref_bgr, (size_t)rh * rw * 3);
+    else {
+        DevBuf<uint8_t> r0(ctx, (size_t)rh0 * rw0 * 3);
+        if (!r0.ok()) return NCT_ERR_HIP;
+        NCT_H2D(r0, ref_bgr, (size_t)rh0 * rw0 * 3);
+        NCT_TRY(nctk_resize_u8c3(ctx, s, r0, rh0, rw0, P->ref[0], rh, rw));
+    }
+    if (q->fullres) {
+        P->full_src = (uint8_t*)ctx->alloc((size_t)q->H0 * q->W0 * 3); P->full_out = (uint8_t*)ctx->alloc((size_t)q->H0 * q->W0 * 3);
+        if (!P->full_src || !P->full_out) return NCT_ERR_HIP;
+        P->full_h = q->H0; P->full_w = q->W0;
+    }
     const uint8_t* img = P->ref[0];
     for (int l = 3; l >= 0; --l) {
         NCT_TRY(nctk_resize_u8c3(ctx, s, img, q->bh[l + 1], q->bw[l + 1], q->rpyr[l], q->bh[l], q->bw[l]));
@@ -745,9 +768,42 @@ int nct_seq_begin(nct_ctx* ctx, const uint8_t* ref_bgr, int rh, int rw, int sh, 
     seq_state* q = new seq_state();
     q->prm = *prm; q->tau = sp->tau; q->sigma = sp->sigma;
     P->seq = q;
-    const int rc = seq_prepare(ctx, P, q, ref_bgr, rh, rw, sh, sw);
+    const int rc = seq_prepare(ctx, P, q, ref_bgr, rh, rw, rh, rw, sh, sw);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); seq_free(ctx, P); drop_images(ctx, P); }
     return rc;
+}
+
+// SPEC §6.9: a sequence whose frames and reference arrive at their original size. Everything the sequence keeps lives on the working-size grids, as after
+// nct_seq_begin on the shrunk images; only the last level's finish reaches the original frame
+int nct_seq_begin_fullres(nct_ctx* ctx, const uint8_t* ref_bgr, int rh, int rw, int sh, int sw, int max_side, int finish, const nct_params* prm, const nct_seq_params* sp) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(ref_bgr && prm && sp, "seq_begin_fullres: null pointer");
+    NCT_REQUIRE(finish == NCT_FINISH_EXACT || finish == NCT_FINISH_UPSAMPLE, "seq_begin_fullres: finish must be NCT_FINISH_EXACT (0) or NCT_FINISH_UPSAMPLE (1) (got %d)", finish);
+    int wh = 0, ww = 0, rwh = 0, rww = 0;
+    const char* why = nct_working_size_rule(sh, sw, max_side, &wh, &ww);
+    if (why) return ctx->fail(NCT_ERR_INVALID, "seq_begin_fullres: frames of %dx%d, max_side %d: %s", sw, sh, max_side, why);
+    why = nct_working_size_rule(rh, rw, max_side, &rwh, &rww);
+    if (why) return ctx->fail(NCT_ERR_INVALID, "seq_begin_fullres: reference %dx%d, max_side %d: %s", rw, rh, max_side, why);
+    NCT_REQUIRE(sp->tau >= 0.0 && sp->tau < 1.0, "seq_begin_fullres: tau must be in [0, 1) (got %g)", sp->tau);
+    NCT_REQUIRE(sp->sigma > 0.0 && sp->sigma <= 1.7976931348623157e308, "seq_begin_fullres: sigma must be finite and positive (got %g)", sp->sigma);
+    NCT_REQUIRE(prm->levels >= 1 && prm->levels <= 5, "seq_begin_fullres: levels must be in [1, 5] (got %d)", prm->levels);
+    NCT_TRY(nct_seq_end(ctx));                                   // a sequence that is still open is closed first
+    pair_state* P = pair_of(ctx);
+    drop_images(ctx, P);
+    seq_state* q = new seq_state();
+    q->prm = *prm; q->tau = sp->tau; q->sigma = sp->sigma;
+    q->fullres = true; q->H0 = sh; q->W0 = sw; q->finish = finish;
+    P->seq = q;
+    const int rc = seq_prepare(ctx, P, q, ref_bgr, rh, rw, rwh, rww, wh, ww);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); seq_free(ctx, P); drop_images(ctx, P); }
+    return rc;
+}
+
+// a frame of the open sequence onto the device: into P->src, or (SPEC §6.9) at its original size into full_src and from there shrunk into P->src
+static int seq_upload_frame(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* src_bgr) {
+    if (!q->fullres) { NCT_H2D(P->src, src_bgr, (size_t)P->sh * P->sw * 3); return NCT_OK; }
+    NCT_H2D(P->full_src, src_bgr, (size_t)q->H0 * q->W0 * 3);
+    return nctk_resize_u8c3(ctx, ctx->stream, P->full_src, q->H0, q->W0, P->src, P->sh, P->sw);
 }
 
 int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels) {
@@ -756,9 +812,10 @@ int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr,
     if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_frame: no sequence is open (nct_seq_begin first)");
     NCT_REQUIRE(src_bgr && out_bgr, "seq_frame: null image");
     seq_state* q = P->seq;
+    NCT_REQUIRE(!(q->fullres && levels), "seq_frame_levels: levels must be NULL in a full-resolution sequence (its result[] arrays have no single size); seq_levels reports the working-size maps");
     // a level without a field (motion off, a first frame, tau == 0) reports zeros
     if (seq_levels) for (int l = 0; l < q->prm.levels; ++l) if (seq_levels->motion[l]) memset(seq_levels->motion[l], 0, sizeof(int16_t) * 2 * (size_t)q->ah[l] * q->aw[l]);
-    NCT_H2D(P->src, src_bgr, (size_t)P->sh * P->sw * 3);
+    int rc = seq_upload_frame(ctx, P, q, src_bgr);
     nct_multi_levels m; memset(&m, 0, sizeof m);
     if (levels) {
         for (int l = 0; l < 5; ++l) {
@@ -767,12 +824,16 @@ int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr,
         }
         m.labels = levels->labels;
     }
-    const int rc = process_resident(ctx, &q->prm, timing, levels ? &m : nullptr, levels ? levels->color : nullptr, nullptr, q, seq_levels);
+    const fullres_target fin{P->full_src, q->H0, q->W0, P->full_out, q->finish};
+    if (rc == NCT_OK) rc = process_resident(ctx, &q->prm, timing, levels ? &m : nullptr, levels ? levels->color : nullptr, q->fullres ? &fin : nullptr, q, seq_levels);
     // a frame that failed may have replaced the state of some levels only: the next frame starts over
     q->gap = 0; q->acc = 0;                                      // a full frame (and a failed one: the next is a first frame) starts the count over
     if (rc) { q->frames = 0; return rc; }
     q->frames += 1;
-    return nct_pair_download(ctx, out_bgr);
+    if (!q->fullres) return nct_pair_download(ctx, out_bgr);
+    NCT_D2H(out_bgr, P->full_out, (size_t)q->H0 * q->W0 * 3);
+    NCT_SYNC();
+    return NCT_OK;
 }
 
 int nct_seq_frame(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing) {
@@ -826,11 +887,24 @@ static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out
     int wls_it[6] = {0, 0, 0, 0, 0, 0};
     const nct_color_debug dbg{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, wls_it};
     const nct_color_params cp{prm.eps, prm.nonlocal_weight, prm.local_weight, prm.wls_lambda_init, prm.wls_alpha, (double)prm.k_num};
-    NCT_TRY(nctk_color_finish(ctx, s, q->keep_x[top], q->ah[top], q->aw[top], H, W, s_lab_full, H, W, cp, out_lab, timing ? &dbg : nullptr));
-    NCT_TRY(nctk_lab2bgr(ctx, s, out_lab, P->out, N, (prm.flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0));
+    const int cube = (prm.flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0;
+    const size_t N0 = (size_t)q->H0 * q->W0;
+    if (q->fullres && q->finish == NCT_FINISH_EXACT) {
+        // SPEC §6.9 rule 3: the warped X' finishes on the original frame
+        DevBuf<uint8_t> s0_lab(ctx, N0 * 3), out0_lab(ctx, N0 * 3);
+        if (!s0_lab.ok() || !out0_lab.ok()) return NCT_ERR_HIP;
+        NCT_TRY(nctk_bgr2lab(ctx, s, P->full_src, s0_lab, N0));
+        NCT_TRY(nctk_color_finish(ctx, s, q->keep_x[top], q->ah[top], q->aw[top], H, W, s0_lab, q->H0, q->W0, cp, out0_lab, timing ? &dbg : nullptr));
+        NCT_TRY(nctk_lab2bgr(ctx, s, out0_lab, P->full_out, N0, cube));
+    } else {
+        const nct_finish_up up{P->full_src, q->H0, q->W0, P->full_out, cube};
+        NCT_TRY(nctk_color_finish(ctx, s, q->keep_x[top], q->ah[top], q->aw[top], H, W, s_lab_full, H, W, cp, out_lab, timing ? &dbg : nullptr, q->fullres ? &up : nullptr));
+        NCT_TRY(nctk_lab2bgr(ctx, s, out_lab, P->out, N, cube));
+    }
     if (timing) timing->wls_iters[top] = *std::max_element(wls_it, wls_it + 6);
     MARK(NCT_ST_COLOR, top);
-    NCT_D2H(out_bgr, P->out, N * 3);
+    if (q->fullres) NCT_D2H(out_bgr, P->full_out, N0 * 3);
+    else NCT_D2H(out_bgr, P->out, N * 3);
     NCT_SYNC();
     return NCT_OK;
 }
@@ -847,7 +921,7 @@ int nct_seq_frame_propagate_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t
     ctx->tm_on = timing != nullptr; ctx->tm_tags.clear(); ctx->tm_host.clear();
     ctx->kt_on = timing != nullptr && (q->prm.flags & NCT_FLAG_TIME_KERNELS) != 0; ctx->kt_ids.clear();
     ctx->wls_split = (q->prm.flags & NCT_FLAG_LATENCY) ? 1 : 0;
-    int rc = hipMemcpyAsync(P->src, src_bgr, (size_t)P->sh * P->sw * 3, hipMemcpyHostToDevice, ctx->stream) == hipSuccess ? NCT_OK : ctx->fail(NCT_ERR_HIP, "seq_frame_propagate: upload failed");
+    int rc = seq_upload_frame(ctx, P, q, src_bgr);
     if (rc == NCT_OK) rc = propagate_run(ctx, P, q, out_bgr, timing, seq_levels);
     ctx->tm_on = false; ctx->kt_on = false;
     // a frame that failed may have replaced the state of some levels only: the next frame starts over
@@ -894,7 +968,13 @@ static int probe_run(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* s
     DevBuf<uint8_t> frame(ctx, N * 3), spyr[4], lab[3];
     DevBuf<nct_seq_change_rec> d_rec(ctx, 1);
     if (!frame.ok() || !d_rec.ok()) return NCT_ERR_HIP;
-    NCT_H2D(frame, src_bgr, N * 3);
+    if (q->fullres) {
+        // SPEC §6.9: the original frame into scratch of its own size, shrunk from there
+        DevBuf<uint8_t> frame0(ctx, (size_t)q->H0 * q->W0 * 3);
+        if (!frame0.ok()) return NCT_ERR_HIP;
+        NCT_H2D(frame0, src_bgr, (size_t)q->H0 * q->W0 * 3);
+        NCT_TRY(nctk_resize_u8c3(ctx, s, frame0, q->H0, q->W0, frame, P->sh, P->sw));
+    } else NCT_H2D(frame, src_bgr, N * 3);
     const uint8_t* simg[5]; simg[4] = frame;
     for (int l = 3; l >= 0; --l) {
         if (!spyr[l].alloc(ctx, (size_t)q->ah[l] * q->aw[l] * 3)) return NCT_ERR_HIP;
@@ -973,9 +1053,17 @@ int nct_working_size(int h, int w, int max_side, int* work_h, int* work_w) {
 
 int nct_process_pair_fullres(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw, int max_side,
                              const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
+    return nct_process_pair_fullres_finish(ctx, src_bgr, sh, sw, ref_bgr, rh, rw, max_side, NCT_FINISH_EXACT, prm, out_bgr, timing);
+}
+
+// finish: NCT_FINISH_EXACT — the last level's U1 / S2 / A1 on the original source (SPEC §6.1); NCT_FINISH_UPSAMPLE — they stay at the working size and S2's output
+// is upsampled onto the original source (SPEC §6.8)
+int nct_process_pair_fullres_finish(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw, int max_side, int finish,
+                                    const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
     NCT_CTX_ENTER();
     NCT_NO_OPEN_SEQ("process_pair_fullres");
     NCT_REQUIRE(src_bgr && ref_bgr && prm && out_bgr, "process_pair_fullres: null pointer");
+    NCT_REQUIRE(finish == NCT_FINISH_EXACT || finish == NCT_FINISH_UPSAMPLE, "process_pair_fullres: finish must be NCT_FINISH_EXACT (0) or NCT_FINISH_UPSAMPLE (1) (got %d)", finish);
     int wh = 0, ww = 0, rwh = 0, rww = 0;
     const char* why = nct_working_size_rule(sh, sw, max_side, &wh, &ww);
     if (why) return ctx->fail(NCT_ERR_INVALID, "process_pair_fullres: source %dx%d: %s", sw, sh, why);
@@ -1008,9 +1096,9 @@ int nct_process_pair_fullres(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int s
     }
     DevBuf<uint8_t> o0(ctx, (size_t)sh * sw * 3);
     if (!o0.ok()) return NCT_ERR_HIP;
-    const fullres_target fin{s0, sh, sw, o0};
+    const fullres_target fin{s0, sh, sw, o0, finish};
     const int rc = process_resident(ctx, prm, timing, nullptr, nullptr, &fin);
-    // the working-size result buffer holds the second-to-last level's image: no nct_pair_download of it
+    // the working-size result buffer holds the second-to-last level's image (the upsampling finish: the working-size result, which nobody asked for): no nct_pair_download of it
     if (P->out) { ctx->release(P->out); P->out = nullptr; }
     if (rc) return rc;
     NCT_D2H(out_bgr, o0, (size_t)sh * sw * 3);

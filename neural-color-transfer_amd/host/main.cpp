@@ -6,10 +6,11 @@
 // extensions `-gpus N` (pairs sharded over N GPUs, one context per worker thread), `-inflight K`, `-io T` (shared decode/encode pool: the GPU workers never
 // touch zlib), `-pin` (threads on the GPU's NUMA node), weights parsed once per process and held once per GPU, `-seed`, `-levels L` (BASELINE
 // config 1: "L=5 only" = -levels 1), `-resume 1` (skip pairs whose output exists; <out>/status.jsonl gets one JSON line per pair)
-// and `-feat16 1` (reduced-precision PatchMatch features; not bit-identical), `-fullres 1` (the result at the content image's own size, SPEC §6.1),
+// and `-feat16 1` (reduced-precision PatchMatch features; not bit-identical), `-fullres 1` (the result at the content image's own size, SPEC §6.1; `-fullres 2`: with the upsampling finish, SPEC §6.8),
 // and pairs.txt lines whose second token lists several references separated by commas (SPEC §6.2: every pixel takes its colours from the reference that matches it best),
 // `-seq 1` (+ `-tau`, `-sigma`): consecutive lines with one and the same reference are the frames of a sequence, graded with temporally blended coefficients (SPEC §6.3).
 // `-motion 1` (+ `-mr0`, `-mr`, `-mpen`): the blend of a sequence follows the motion between the frames (SPEC §6.4).
+// `-seqfull 1|2`: a sequence takes and returns frames at their own size, with the exact or the upsampling finish (SPEC §6.9).
 // `-key N`: only every N-th frame of a sequence runs the whole pair; the others are propagated from the frame before them (SPEC §6.5).
 // `-autokey 1` (+ `-keythr`, `-keycut`, `-keychange`, `-keygap`): the library decides per frame whether it is propagated, a key frame or a scene cut (SPEC §6.7).
 #include <sys/stat.h>
@@ -116,7 +117,9 @@ struct Pair { std::string cnt, stl; float bds; std::vector<std::string> refs; st
 std::mutex g_print;
 
 struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false, fullres = false, seq = false, motion = false; nct_seq_params sp; nct_seq_motion mp; int key = 1; bool autokey = false; nct_seq_auto ap; int rank = 0, world = 1;
-                int lut = 0; double lut_lambda = 0.0; bool lutfull = false; };   // -lut N (0 = off), -lutlambda (0 = the library's default), -lutfull 1
+                int lut = 0; double lut_lambda = 0.0; bool lutfull = false;
+                int finish = NCT_FINISH_EXACT;          // -fullres 1 / 2: the exact or the upsampling finish (SPEC §6.1 / §6.8)
+                int seqfull = 0; };                      // -seqfull 1 / 2: full-resolution sequences (SPEC §6.9) with the exact or the upsampling finish   // -lut N (0 = off), -lutlambda (0 = the library's default), -lutfull 1
 
 // ---- ENABLE_VIS debug outputs (Config.h:8) behind the runtime flag -vis 1: per pyramid level the flow maps of both NNFs (reconstruct_flow,
 // GeneralizedPatchMatch.cu:337-353), the level images tCnt / tStl (main.cu:343-347), the matching-error heat map (getHeat,
@@ -354,7 +357,7 @@ void split_refs(Pair& p) {
 // why this run does not take the line (its own fault, or an option it cannot be combined with); empty: it runs
 std::string refusal(const Config& cfg, const Pair& p) {
     if (!p.err.empty()) return p.err;
-    if (cfg.fullres && p.refs.size() > 1) return "-fullres 1 cannot be combined with several references";
+    if (cfg.fullres && p.refs.size() > 1) return cfg.finish == NCT_FINISH_UPSAMPLE ? "-fullres 2 cannot be combined with several references" : "-fullres 1 cannot be combined with several references";
     return "";
 }
 
@@ -440,10 +443,10 @@ void run_pair(nct_ctx* ctx, const Config& cfg, Job& j) {
     nct_params prm = cfg.prm;
     prm.bds_weight = j.p.bds;                                   // the per-line weight overrides -bds (main.cu:475)
     nct_pair_timing tm;                                         // stage times come from stream events: asking for them adds no host synchronisation
-    if (cfg.fullres) {                                          // -fullres 1: the library shrinks both images itself and returns the content image at its own size
+    if (cfg.fullres) {                                          // -fullres 1 / 2: the library shrinks both images itself and returns the content image at its own size
         const ImageBGR& stl = j.refs[0];
         j.out.resize((size_t)j.cnt.h * j.cnt.w * 3);
-        const int rc = nct_process_pair_fullres(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, stl.px.data(), stl.h, stl.w, MAX_SIZE, &prm, j.out.data(), &tm);
+        const int rc = nct_process_pair_fullres_finish(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, stl.px.data(), stl.h, stl.w, MAX_SIZE, cfg.finish, &prm, j.out.data(), &tm);
         if (rc != NCT_OK) { j.say("Error: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
         if (!job_lut(ctx, cfg, j)) return;
         log_times(j, prm, tm);
@@ -506,7 +509,7 @@ std::vector<Group> plan_groups(const std::vector<Pair>& pairs) {
 }
 
 // one sequence on one context, its frames in file order. The reference is decoded and shrunk once; a frame whose (shrunk) size differs from the open sequence's begins
-// a new one at that frame; a line that cannot be decoded is skipped and the state continues from the last good frame; with -resume 1 the sequence is skipped only if
+// a new one at that frame (-seqfull: nothing is shrunk here, the library takes and returns originals, and it is the frame's ORIGINAL size that counts); a line that cannot be decoded is skipped and the state continues from the last good frame; with -resume 1 the sequence is skipped only if
 // every output is complete, else it is redone from its first frame. With -key N the k-th frame run since the last nct_seq_begin is a full frame iff k % N == 0 and a
 // propagated one (SPEC §6.5) otherwise; a frame that failed left the sequence reset, so the next one is full. With -autokey 1 every frame goes through
 // nct_seq_frame_auto (SPEC §6.7) and the log says what each frame after a sequence's first turned out to be. Returns the number of lines it finished
@@ -537,18 +540,20 @@ size_t run_sequence(nct_ctx* ctx, const Config& cfg, const std::vector<Pair>& pa
             if (!imgio::read(refStr, ref, ref_err)) { ref.px.clear(); j.say("Error: Fail reading style image: %s\n", refStr.c_str()); }
             else {
                 j.say("Read style file: %s, w = %d, h = %d\n", refStr.c_str(), ref.w, ref.h);
-                if (!shrink(ctx, ref)) { ref_err = nct_last_error(ctx); ref.px.clear(); }
+                if (!cfg.seqfull && !shrink(ctx, ref)) { ref_err = nct_last_error(ctx); ref.px.clear(); }
             }
         }
         if (j.state == Job::LOADED && ref.px.empty()) { j.err = "cannot read style image: " + ref_err; j.state = Job::FAILED; }
         if (j.state == Job::LOADED && cfg.lutfull) j.orig = j.cnt;
-        if (j.state == Job::LOADED && !shrink(ctx, j.cnt)) { j.say("Error: resize failed: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; }
+        if (j.state == Job::LOADED && !cfg.seqfull && !shrink(ctx, j.cnt)) { j.say("Error: resize failed: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; }
         if (j.state == Job::LOADED) {
             int rc = NCT_OK;
             if (!open || j.cnt.h != fh || j.cnt.w != fw) {
-                rc = nct_seq_begin(ctx, ref.px.data(), ref.h, ref.w, j.cnt.h, j.cnt.w, &prm, &cfg.sp);
+                rc = cfg.seqfull ? nct_seq_begin_fullres(ctx, ref.px.data(), ref.h, ref.w, j.cnt.h, j.cnt.w, MAX_SIZE, cfg.seqfull == 2 ? NCT_FINISH_UPSAMPLE : NCT_FINISH_EXACT, &prm, &cfg.sp)
+                                 : nct_seq_begin(ctx, ref.px.data(), ref.h, ref.w, j.cnt.h, j.cnt.w, &prm, &cfg.sp);
                 open = rc == NCT_OK; fh = j.cnt.h; fw = j.cnt.w; k = 0;
                 if (open) j.say("Sequence %ld: begins at this frame (%d x %d, tau = %g, sigma = %g).\n", g.seq, fw, fh, cfg.sp.tau, cfg.sp.sigma);
+                if (open && cfg.seqfull) j.say("Sequence %ld: full resolution, %s finish (-seqfull %d).\n", g.seq, cfg.seqfull == 2 ? "upsampling" : "exact", cfg.seqfull);
                 if (open && cfg.motion) {
                     rc = nct_seq_set_motion(ctx, &cfg.mp);
                     if (rc == NCT_OK) j.say("Sequence %ld: motion compensation (radius0 = %d, radius = %d, penalty = %d).\n", g.seq, cfg.mp.radius0, cfg.mp.radius, cfg.mp.penalty);
@@ -704,7 +709,7 @@ int main(int argc, char** argv) {
     nct_seq_motion_default(&cfg.mp);
     nct_seq_auto_default(&cfg.ap);
     int autokey = 0;
-    int motion = 0, key = 1, lut = 0, lutfull = 0;
+    int motion = 0, key = 1, lut = 0, lutfull = 0, seqfull = 0;
     double lutlambda = 0.0; bool lutlambda_set = false;
     int gpu = 0, ngpus = 1, seed = 1, inflight = 1, levels = 5, resume = 0, feat16 = 0, vis = 0, fullres = 0, seq = 0, io = -1, pin = 1, world = 1, rank = 0, steal = 0, procs = 0, rccl = 0;
     cl.add("m", cfg.model_dir, "Directory of network models.");
@@ -726,7 +731,7 @@ int main(int argc, char** argv) {
     cl.add("levels", levels, "[extension] pyramid levels to run, coarse to fine: 5 = the full L=5..1 loop, 1 = L=5 only.");
     cl.add("resume", resume, "[extension] 1 = skip pairs whose output file exists and is a complete PNG; every pair appends a JSON line to <output>/status.jsonl.");
     cl.add("vis", vis, "[extension] 1 = the reference's ENABLE_VIS dumps per level (flow maps, level images, error heat map, coefficient and cluster images) next to the output.");
-    cl.add("fullres", fullres, "[extension] 1 = return the content image at its own size: the pyramid runs at most 1000 px on a side, its last level's WLS finish at the original size (SPEC 6.1); not with -vis 1.");
+    cl.add("fullres", fullres, "[extension] 1 = return the content image at its own size: the pyramid runs at most 1000 px on a side, its last level's WLS finish at the original size (SPEC 6.1); 2 = the same with the upsampling finish: that finish stays at the working size and its smoothed coefficient maps are upsampled onto the original pixels (SPEC 6.8); not with -vis 1.");
     cl.add("procs", procs, "[extension] N > 0: fork N processes, one per GPU (-g, -g + 1, ...): process r runs with -rank r -world N on its own device, HIP runtime and status.<r>.jsonl (the process-per-GPU shape; -gpus N keeps all GPUs in one process).");
     cl.add("world", world, "[extension] number of cooperating processes that share this pairs.txt and output directory (default 1); set by -procs, or by hand with -rank.");
     cl.add("rank", rank, "[extension] this process's rank in [0, world): it runs the pairs.txt lines i with i mod world = rank (or the ones it draws, -steal 1).");
@@ -734,6 +739,7 @@ int main(int argc, char** argv) {
     cl.add("steal", steal, "[extension] 1 = with -world > 1, lines are drawn from a shared counter (<output>/.tickets under a file lock) by whichever rank is free, instead of i mod world: mixed-size batches.");
     cl.add("feat16", feat16, "[extension] 1 = fp16 PatchMatch feature tiles (fp32 accumulate); not bit-identical to the default (about 45 dB against it).");
     cl.add("seq", seq, "[extension] 1 = consecutive pairs.txt lines with one and the same reference and weight are the frames of a sequence (SPEC 6.3): one worker runs them in file order and blends each frame's colour coefficients with the previous frame's; every worker does its own file I/O (-io is not used); not with -fullres 1 or -vis 1.");
+    cl.add("seqfull", seqfull, "[extension] -seq 1: 1 = full-resolution sequences (SPEC 6.9): frames are passed and returned at their own size, the sequence's state stays at the working size and the last level's finish runs at the original size; 2 = the same with the upsampling finish (SPEC 6.8); not with -lutfull 1.");
     cl.add("tau", cfg.sp.tau, "[extension] -seq 1: temporal weight in [0, 1); 0 = every frame on its own.");
     cl.add("sigma", cfg.sp.sigma, "[extension] -seq 1: sensitivity of the blend to changes between frames, in 8-bit Lab units (> 0).");
     cl.add("motion", motion, "[extension] -seq 1: 1 = motion-compensated blend (SPEC 6.4): every level finds per pixel where it was in the previous frame (5 x 5 block match on the Lab level images, coarse to fine) and blends with the coefficients there.");
@@ -765,8 +771,11 @@ int main(int argc, char** argv) {
     }
     if (!parsed) return -1;
     if (world < 1 || rank < 0 || rank >= world) { printf("Error: -rank %d is not in [0, -world %d).\n", rank, world); return -1; }
-    if (fullres && vis) { printf("Error: -fullres 1 cannot be combined with -vis 1 (the -vis dumps are working-size images).\n"); return -1; }
-    if (seq && fullres) { printf("Error: -seq 1 cannot be combined with -fullres 1 (a sequence runs at the working size only).\n"); return -1; }
+    if (fullres < 0 || fullres > 2) { printf("Error: -fullres %d is not one of 0, 1, 2.\n", fullres); return -1; }
+    if (seqfull < 0 || seqfull > 2) { printf("Error: -seqfull %d is not one of 0, 1, 2.\n", seqfull); return -1; }
+    if (seqfull && !seq) { printf("Error: -seqfull %d needs -seq 1 (it chooses how a sequence reaches the frames' own size).\n", seqfull); return -1; }
+    if (fullres && vis) { printf("Error: -fullres %d cannot be combined with -vis 1 (the -vis dumps are working-size images).\n", fullres); return -1; }
+    if (seq && fullres) { printf("Error: -seq 1 cannot be combined with -fullres 1 (a sequence runs at the working size only). Full-resolution sequences are -seqfull 1 or 2.\n"); return -1; }
     if (seq && vis) { printf("Error: -seq 1 cannot be combined with -vis 1 (the -vis dumps describe single pairs).\n"); return -1; }
     if (seq && !(cfg.sp.tau >= 0.0 && cfg.sp.tau < 1.0)) { printf("Error: -tau %g is not in [0, 1).\n", cfg.sp.tau); return -1; }
     if (seq && !(cfg.sp.sigma > 0.0 && cfg.sp.sigma <= 1.7976931348623157e308)) { printf("Error: -sigma %g is not finite and positive.\n", cfg.sp.sigma); return -1; }
@@ -787,7 +796,8 @@ int main(int argc, char** argv) {
     if (lutlambda_set && !lut) { printf("Error: -lutlambda needs -lut N.\n"); return -1; }
     if (lutlambda_set && !(lutlambda > 0.0 && lutlambda <= 1.7976931348623157e308)) { printf("Error: -lutlambda %g is not finite and greater than 0.\n", lutlambda); return -1; }
     if (lutfull && !lut) { printf("Error: -lutfull 1 needs -lut N.\n"); return -1; }
-    if (lutfull && fullres) { printf("Error: -lutfull 1 cannot be combined with -fullres 1 (the result already has the original size).\n"); return -1; }
+    if (lutfull && fullres) { printf("Error: -lutfull 1 cannot be combined with -fullres %d (the result already has the original size).\n", fullres); return -1; }
+    if (lutfull && seqfull) { printf("Error: -lutfull 1 cannot be combined with -seqfull %d (the results already have the original size).\n", seqfull); return -1; }
     cfg.lut = lut; cfg.lut_lambda = lutlambda_set ? lutlambda : 0.0; cfg.lutfull = lutfull != 0;
     if (!plan_only) mkdir(cfg.output_dir.c_str(), 0777);                    // main.cu:458
     uint64_t run_token = getenv("NCT_RUN_TOKEN") ? strtoull(getenv("NCT_RUN_TOKEN"), nullptr, 0) : 0;      // hand-started ranks of one run share it (and remove <output>/.rccl_id between runs)
@@ -822,7 +832,8 @@ int main(int argc, char** argv) {
     if (inflight <= 1) cfg.prm.flags |= NCT_FLAG_LATENCY;          // one pair at a time per GPU: split WLS solves (same result, -3 ms per 700x700 pair)
     cfg.resume = resume != 0;
     cfg.vis = vis != 0;
-    cfg.fullres = fullres != 0;
+    cfg.fullres = fullres != 0; cfg.finish = fullres == 2 ? NCT_FINISH_UPSAMPLE : NCT_FINISH_EXACT;
+    cfg.seqfull = seqfull;
     cfg.seq = seq != 0;
     cfg.motion = motion != 0;
     cfg.key = key;

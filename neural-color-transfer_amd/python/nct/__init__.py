@@ -38,7 +38,8 @@ def lib():
     return _lib
 
 
-NCT_VERSION = 117        # include/nct.h
+NCT_VERSION = 118        # include/nct.h
+FINISH_EXACT, FINISH_UPSAMPLE = 0, 1      # NCT_FINISH_*: how a full-resolution run reaches the original size (SPEC §6.1 / §6.8)
 MAX_REFS = 8             # NCT_MAX_REFS
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -90,6 +91,9 @@ SIGNATURES = {
     "nct_working_size": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nct_process_pair_fullres": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p]),
     "nct_color_finish": (C.c_int, [C.c_void_p, _f64p] + [C.c_int] * 4 + [_u8p, C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p]),
+    "nct_process_pair_fullres_finish": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p]),
+    "nct_color_finish_upsample": (C.c_int, [C.c_void_p, _f64p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_void_p, _u8p]),
+    "nct_color_finish_upsample_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nct_pair_upload": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int]),
     "nct_pair_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_pair_run_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -102,6 +106,7 @@ SIGNATURES = {
     "nct_process_multi": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, _u8p, C.c_void_p]),
     "nct_seq_params_default": (None, [C.c_void_p]),
     "nct_seq_begin": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nct_seq_begin_fullres": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nct_seq_frame": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p]),
     "nct_seq_frame_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_propagate": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p]),
@@ -631,16 +636,48 @@ class Context:
                                            C.addressof(prm), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
         return (out, tm.as_dict()) if want_timing else out
 
-    def process_pair_fullres(self, src_bgr, ref_bgr, max_side=1000, params=None, want_timing=False):
-        """nct_process_pair_fullres: the pair runs at working_size(..., max_side), the last level finishes on the original source (result: src's size)"""
+    def process_pair_fullres(self, src_bgr, ref_bgr, max_side=1000, params=None, want_timing=False, finish=0):
+        """nct_process_pair_fullres: the pair runs at working_size(..., max_side), the last level finishes on the original source (result: src's size).
+        finish: FINISH_EXACT (0) that entry point; anything else goes through nct_process_pair_fullres_finish (FINISH_UPSAMPLE: SPEC §6.8)"""
         s = np.ascontiguousarray(src_bgr, np.uint8)
         r = np.ascontiguousarray(ref_bgr, np.uint8)
         prm = params or Params.default()
         out = np.empty_like(s)
         tm = PairTiming() if want_timing else None
-        self._chk(self._l.nct_process_pair_fullres(self._h, s.reshape(-1, 3), s.shape[0], s.shape[1], r.reshape(-1, 3), r.shape[0], r.shape[1], max_side,
-                                                   C.addressof(prm), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
+        if finish == FINISH_EXACT:
+            self._chk(self._l.nct_process_pair_fullres(self._h, s.reshape(-1, 3), s.shape[0], s.shape[1], r.reshape(-1, 3), r.shape[0], r.shape[1], max_side,
+                                                       C.addressof(prm), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
+        else:
+            self._chk(self._l.nct_process_pair_fullres_finish(self._h, s.reshape(-1, 3), s.shape[0], s.shape[1], r.reshape(-1, 3), r.shape[0], r.shape[1], max_side,
+                                                              int(finish), C.addressof(prm), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
         return (out, tm.as_dict()) if want_timing else out
+
+    def color_finish_upsample(self, ab_wls, h, w, s_full, params=None):
+        """nct_color_finish_upsample (SPEC §6.8): ab_wls ([2][h*w][3], the working-size finish's S2 output) upsampled and applied to s_full (H x W x 3 BGR)"""
+        a = np.ascontiguousarray(ab_wls, np.float64).reshape(-1)
+        assert a.size == 6 * h * w
+        s_full = np.ascontiguousarray(s_full, np.uint8)
+        H, W = s_full.shape[:2]
+        prm = params or Params.default()
+        out = np.empty((H, W, 3), np.uint8)
+        self._chk(self._l.nct_color_finish_upsample(self._h, a, h, w, s_full.reshape(-1, 3), H, W, C.addressof(prm), out.reshape(-1, 3)))
+        return out
+
+    def color_finish_upsample_dev(self, ab_wls, h, w, s_full, params=None):
+        """the same through nct_color_finish_upsample_dev on arena blocks"""
+        a = np.ascontiguousarray(ab_wls, np.float64).reshape(-1)
+        assert a.size == 6 * h * w
+        s_full = np.ascontiguousarray(s_full, np.uint8)
+        H, W = s_full.shape[:2]
+        prm = params or Params.default()
+        blocks = [self.dev_upload(a), self.dev_upload(s_full), self.dev_alloc(s_full.size)]
+        try:
+            self._chk(self._l.nct_color_finish_upsample_dev(self._h, blocks[0], h, w, blocks[1], H, W, C.addressof(prm), blocks[2]))
+            return self.dev_download(blocks[2], (H, W, 3), np.uint8)
+        finally:
+            self.synchronize()
+            for p in blocks:
+                self.dev_free(p)
 
     def color_finish(self, ab, h, w, work_h, work_w, s_full, params=None, want_stages=False):
         """nct_color_finish: U1 / roughness / S2 / A1 of ab ([2][h*w][3], S1's ab_nonlocal) onto s_full (H x W x 3 BGR) in a pyramid of working size work_h x work_w"""
@@ -776,6 +813,22 @@ class Context:
             sp.sigma = sigma
         self._chk(self._l.nct_seq_begin(self._h, r.reshape(-1, 3), r.shape[0], r.shape[1], int(src_shape[0]), int(src_shape[1]), C.addressof(prm), C.addressof(sp)))
         self._seq_shapes = (tuple(src_shape[:2]), r.shape[:2], prm.levels)
+        self._seq_work = None
+
+    def seq_begin_fullres(self, ref_bgr, src_shape, max_side=1000, finish=0, params=None, tau=None, sigma=None):
+        """nct_seq_begin_fullres (SPEC §6.9): frames of src_shape[:2] and the reference arrive at their original size and are shrunk to working_size(..., max_side) on
+        the device; every frame call then takes and returns originals. finish: FINISH_EXACT or FINISH_UPSAMPLE"""
+        r = np.ascontiguousarray(ref_bgr, np.uint8)
+        prm = params or Params.default()
+        sp = SeqParams.default()
+        if tau is not None:
+            sp.tau = tau
+        if sigma is not None:
+            sp.sigma = sigma
+        self._chk(self._l.nct_seq_begin_fullres(self._h, r.reshape(-1, 3), r.shape[0], r.shape[1], int(src_shape[0]), int(src_shape[1]), int(max_side), int(finish),
+                                                C.addressof(prm), C.addressof(sp)))
+        self._seq_shapes = (tuple(src_shape[:2]), r.shape[:2], prm.levels)
+        self._seq_work = (working_size(int(src_shape[0]), int(src_shape[1]), max_side), working_size(r.shape[0], r.shape[1], max_side))
 
     def seq_frame(self, src_bgr, want_timing=False):
         s = np.ascontiguousarray(src_bgr, np.uint8)
@@ -787,7 +840,7 @@ class Context:
         self._chk(self._l.nct_seq_frame(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
         return (out, tm.as_dict()) if want_timing else out
 
-    def seq_frame_levels(self, src_bgr, want_color=True):
+    def seq_frame_levels(self, src_bgr, want_color=True, want_levels=None):
         """nct_seq_frame_levels -> (result, dict): pair_run_levels' per-level lists ("ann" … "result", with want_color "color" and "labels"), plus "ab_blend" and "tau_map"
         per level that ran (X'_t [2, h*w, 3] and tau_p [h, w]; a frame without a blend reports X_t and zeros), "motion" (SPEC §6.4: the level's field, int16 [h, w, 2] of
         (my, mx); zeros without motion or without a blend) and "timing"."""
@@ -795,6 +848,14 @@ class Context:
         (H, W), (RH, RW), levels = self._seq_shapes
         if tuple(s.shape[:2]) != (H, W):
             raise NctError(-2, "seq_frame_levels: the frame is %dx%d, the sequence was begun for %dx%d" % (s.shape[1], s.shape[0], W, H))
+        # a full-resolution sequence (SPEC §6.9 rule 5) reports the working-size maps through "ab_blend" / "tau_map" / "motion" only: nct_pair_levels stays NULL
+        # unless want_levels forces it (which the library refuses)
+        work = getattr(self, "_seq_work", None)
+        if work is not None:
+            (H, W), (RH, RW) = work
+        if want_levels is None:
+            want_levels = work is None
+        want_color = want_color and want_levels
         dims = []
         h, w, h2, w2 = H, W, RH, RW
         for _ in range(5):
@@ -827,7 +888,9 @@ class Context:
             sl.ab_blend[l] = ab_blend[l].ctypes.data; sl.tau_map[l] = tau_map[l].ctypes.data; sl.motion[l] = motion[l].ctypes.data
         out = np.empty_like(s)
         tm = PairTiming()
-        self._chk(self._l.nct_seq_frame_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv), C.addressof(sl)))
+        self._chk(self._l.nct_seq_frame_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv) if want_levels else None, C.addressof(sl)))
+        if not want_levels:
+            keep = {}
         if want_color:
             keep["color"] = color; keep["labels"] = labels
         keep["ab_blend"] = ab_blend; keep["tau_map"] = tau_map; keep["motion"] = motion
@@ -859,6 +922,8 @@ class Context:
         levels = shp[2]
         dims = []
         h, w = s.shape[:2]
+        if getattr(self, "_seq_work", None) is not None:       # a full-resolution sequence keeps its state on the working-size grids
+            h, w = self._seq_work[0]
         for _ in range(5):
             dims.insert(0, (h, w))
             h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
@@ -1012,6 +1077,7 @@ class Context:
     def seq_end(self):
         self._chk(self._l.nct_seq_end(self._h))
         self._seq_shapes = None
+        self._seq_work = None
 
     def seq_set_motion(self, radius0=None, radius=None, penalty=None, off=False):
         """nct_seq_set_motion (SPEC §6.4): motion compensation of the open sequence from the next frame on; values left out are nct_seq_motion_default's (3, 1, 1).
