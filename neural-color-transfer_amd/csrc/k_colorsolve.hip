@@ -1,6 +1,6 @@
 // k_colorsolve.hip — local colour transfer on the GPU: T1 local statistics, T2 confidence weights, S1 nonlocal
-// least squares (truncated CG), U1 upsample + roughness, S2 edge-aware WLS smoothing (PCG), A1 apply. U1..A1 are "the finish"
-// (nctk_color_finish): on the pipeline's levels it targets the working grid, in the full-resolution entry the original source (SPEC §6.1).
+// least squares (truncated CG), U1 upsample + roughness, S2 edge-aware WLS smoothing (PCG), A1 apply. T1..S1 are nctk_color_nonlocal, U1..A1 "the finish"
+// (nctk_color_finish): on the pipeline's levels it targets the working grid, in the full-resolution entry the original source (SPEC §6.1); between the two: nct_seq.cpp.
 // Reference: ColorTransfer::transfer_color_downsample ColorTransfer.cpp:1180-1478 and what it calls:
 //   stats loop :1194-1265 (+ build_accumTable_downsample :425-455), weights :1302-1357,
 //   solve_nonlocal_downsample_gpu_gradient :548-949 -> solve_ls_cg_gpu SparseSolver_GPU.cu:3-198,
@@ -119,14 +119,6 @@ __global__ void k_wls_system(const double* __restrict__ gx, const double* __rest
 }
 // ================================================================= orchestration
 #define LCHK() NCT_LAUNCH_CHECK()
-static int dbg_copy_bytes(nct_ctx* ctx, hipStream_t s, void* host, const void* dev, size_t bytes) {
-    if (!host) return 0;
-    NCT_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s));
-    NCT_HIP(hipStreamSynchronize(s));
-    return 0;
-}
-static int dbg_copy(nct_ctx* ctx, hipStream_t s, double* host, const double* dev, size_t n) { return dbg_copy_bytes(ctx, s, host, dev, sizeof(double) * n); }
-static int dbg_copy(nct_ctx* ctx, hipStream_t s, int16_t* host, const int16_t* dev, size_t n) { return dbg_copy_bytes(ctx, s, host, dev, sizeof(int16_t) * n); }
 
 // ================================================================= the finish: U1, roughness, S2, A1 on a target grid H x W >= h x w
 // x: [2][h*w][3] coefficients after S1 on the level grid; Hw x Ww: the working size the pyramid runs at (the pipeline's "full" grid of every
@@ -174,23 +166,22 @@ int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w
     return 0;
 }
 
-int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, const uint8_t* s_lab_level, const uint8_t* g_lab_level,
-                              const uint8_t* s_lab_full, const int* knn_id, const double* knn_w, int layer, int h, int w, int H, int W,
-                              const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg, const nct_s1_graph* graph,
-                              const nct_finish_target* fin, const nct_seq_link* seq, const nct_finish_up* up) {
+// ================================================================= T1, T2, S1 on the level grid h x w: the level's coefficients into b.x
+// H x W: the working size (S1's dWeight). b stays the caller's until the finish that reads b.x has been enqueued
+int nctk_color_nonlocal(nct_ctx* ctx, hipStream_t s, const float* err, const uint8_t* s_lab_level, const uint8_t* g_lab_level, const int* knn_id, const double* knn_w,
+                        int layer, int h, int w, int H, int W, const nct_color_params& prm, nct_color_bufs& b, const nct_color_debug* dbg, const nct_s1_graph* graph) {
     const int n = h * w;
     const int nbl = cdiv(n, 256);
     // ---------------- T1 + T2
-    DevBuf<double> x(ctx, (size_t)6 * n), weight(ctx, n);
-    DevBuf<unsigned> mm(ctx, 2);
-    if (!x.ok() || !weight.ok() || !mm.ok()) return NCT_ERR_HIP;
-    double* xa = x; double* xb = (double*)x + (size_t)3 * n;
+    if (!b.x.alloc(ctx, (size_t)6 * n) || !b.weight.alloc(ctx, n) || !b.mm.alloc(ctx, 2)) return NCT_ERR_HIP;
+    double* const x = b.x; double* const weight = b.weight; unsigned* const mm = b.mm;
+    double* xa = x; double* xb = x + (size_t)3 * n;
     hipLaunchKernelGGL(k_local_stats, dim3(nbl), dim3(256), 0, s, s_lab_level, g_lab_level, h, w, prm.eps, xa, xb); LCHK();
     if (dbg) NCT_TRY(dbg_copy(ctx, s, dbg->ab_local, x, (size_t)6 * n));
-    NCT_HIP(hipMemsetD32Async((hipDeviceptr_t)(unsigned*)mm, (int)0xFFFFFFFFu, 1, s));
-    NCT_HIP(hipMemsetD32Async((hipDeviceptr_t)((unsigned*)mm + 1), 0, 1, s));
-    hipLaunchKernelGGL(k_minmax_f, dim3(128), dim3(256), 0, s, err, n, (unsigned*)mm); LCHK();
-    hipLaunchKernelGGL(k_err_weight, dim3(nbl), dim3(256), 0, s, err, n, (const unsigned*)mm, (double*)weight); LCHK();
+    NCT_HIP(hipMemsetD32Async((hipDeviceptr_t)mm, (int)0xFFFFFFFFu, 1, s));
+    NCT_HIP(hipMemsetD32Async((hipDeviceptr_t)(mm + 1), 0, 1, s));
+    hipLaunchKernelGGL(k_minmax_f, dim3(128), dim3(256), 0, s, err, n, mm); LCHK();
+    hipLaunchKernelGGL(k_err_weight, dim3(nbl), dim3(256), 0, s, err, n, (const unsigned*)mm, weight); LCHK();
     NCT_TRY(ctx->mark(s, nct_stage_tag(NCT_ST_COLOR, ctx->tm_level)));
     // ---------------- S1 (k_s1.hip)
     const double normFactor = (double)(W * H) / (double)(w * h);
@@ -200,44 +191,14 @@ int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, con
         // lambda / alpha / dWeight arrive as float in the reference signature (ColorTransfer.cpp:548-550)
         const float lambda_f = (float)prm.local_weight, alpha_f = (float)prm.wls_alpha, dWeight_f = (float)normFactor;
         hipLaunchKernelGGL(k_gradient_weights, dim3(nbl), dim3(256), 0, s, s_lab_level, h, w, (double)lambda_f, (double)alpha_f, (double*)gx, (double*)gy); LCHK();
-        int rc1;
-        if (graph) {
-            rc1 = nctk_s1_solve(ctx, s, *graph, knn_id, weight, dWeight_f, s_lab_level, g_lab_level, gx, gy, layer, h, w, x, dbg ? dbg->cg_iters : nullptr);
-        } else {
+        nct_s1_graph_bufs gb;
+        if (!graph) {
             // no prebuilt graph part (the host entry point nct_local_color_transfer): build it here, on this stream; the host does not know the hub block count
-            nct_s1_graph_bufs gb;
             if (!gb.alloc(ctx, n)) return NCT_ERR_HIP;
-            const nct_s1_graph g = gb.view(-1, -1);
-            rc1 = nctk_s1_graph_build(ctx, s, knn_id, knn_w, sqrt(prm.nonlocal_weight / prm.k_num), g, nullptr);
-            if (rc1 == 0) rc1 = nctk_s1_solve(ctx, s, g, knn_id, weight, dWeight_f, s_lab_level, g_lab_level, gx, gy, layer, h, w, x, dbg ? dbg->cg_iters : nullptr);
+            NCT_TRY(nctk_s1_graph_build(ctx, s, knn_id, knn_w, sqrt(prm.nonlocal_weight / prm.k_num), gb.view(-1, -1), nullptr));
         }
-        if (rc1) return rc1;
+        NCT_TRY(nctk_s1_solve(ctx, s, graph ? *graph : gb.view(-1, -1), knn_id, weight, dWeight_f, s_lab_level, g_lab_level, gx, gy, layer, h, w, x, dbg ? dbg->cg_iters : nullptr));
     }
     NCT_TRY(ctx->mark(s, nct_stage_tag(NCT_ST_NONLOCAL, ctx->tm_level)));
-    if (dbg) NCT_TRY(dbg_copy(ctx, s, dbg->ab_nonlocal, x, (size_t)6 * n));
-    if (seq) {
-        // a frame of a sequence (SPEC §6.3): X'_t = the blend of S1's output with X'_(t-1), in place in the kept state, which the finish reads; L_t replaces L_(t-1)
-        DevBuf<double> tmap;
-        if (seq->tau_map_host && !tmap.alloc(ctx, n)) return NCT_ERR_HIP;
-        if (seq->blend && seq->field) {
-            // with motion (SPEC §6.4): the level's field, then the blend gathers X'_(t-1) and L_(t-1) through it — not in place: into S1's own buffer, then into the state
-            NCT_TRY(nctk_seq_motion(ctx, s, s_lab_level, seq->keep_pk, h, w, seq->parent, seq->ph, seq->pw, seq->R, seq->penalty, seq->field));
-            NCT_TRY(nctk_seq_blend(ctx, s, x, seq->keep_x, s_lab_level, seq->keep_lab, h, w, seq->tau, seq->sigma, x, tmap, seq->field));
-            NCT_HIP(hipMemcpyAsync(seq->keep_x, x, sizeof(double) * (size_t)6 * n, hipMemcpyDeviceToDevice, s));
-            NCT_TRY(dbg_copy(ctx, s, seq->motion_host, seq->field, (size_t)2 * n));
-        } else if (seq->blend) NCT_TRY(nctk_seq_blend(ctx, s, x, seq->keep_x, s_lab_level, seq->keep_lab, h, w, seq->tau, seq->sigma, seq->keep_x, tmap));
-        else {
-            NCT_HIP(hipMemcpyAsync(seq->keep_x, x, sizeof(double) * (size_t)6 * n, hipMemcpyDeviceToDevice, s));
-            if (tmap.ok()) NCT_HIP(hipMemsetAsync(tmap, 0, sizeof(double) * (size_t)n, s));
-        }
-        NCT_HIP(hipMemcpyAsync(seq->keep_lab, s_lab_level, (size_t)3 * n, hipMemcpyDeviceToDevice, s));
-        if (seq->field) NCT_TRY(nctk_seq_pack(ctx, s, s_lab_level, n, seq->keep_pk));
-        NCT_TRY(dbg_copy(ctx, s, seq->ab_blend_host, seq->keep_x, (size_t)6 * n));
-        if (tmap.ok()) NCT_TRY(dbg_copy(ctx, s, seq->tau_map_host, tmap, n));
-        // a full-resolution sequence (SPEC §6.9 rule 2) finishes X'_t on the original frame like a pair finishes S1's output
-        if (fin) return nctk_color_finish(ctx, s, seq->keep_x, h, w, H, W, fin->s_lab, fin->H, fin->W, prm, fin->out_lab, dbg);
-        return nctk_color_finish(ctx, s, seq->keep_x, h, w, H, W, s_lab_full, H, W, prm, out_lab_full, dbg, up);
-    }
-    if (fin) return nctk_color_finish(ctx, s, x, h, w, H, W, fin->s_lab, fin->H, fin->W, prm, fin->out_lab, dbg);
-    return nctk_color_finish(ctx, s, x, h, w, H, W, s_lab_full, H, W, prm, out_lab_full, dbg, up);
+    return dbg ? dbg_copy(ctx, s, dbg->ab_nonlocal, x, (size_t)6 * n) : 0;
 }

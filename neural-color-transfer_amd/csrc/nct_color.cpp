@@ -106,12 +106,16 @@ int nct_local_color_transfer(nct_ctx* ctx, const float* err, const uint8_t* s_bg
     NCT_TRY(nctk_bgr2lab(ctx, ctx->stream, sl, slab, n));          // main.cu:351-352
     NCT_TRY(nctk_bgr2lab(ctx, ctx->stream, gl, glab, n));          // main.cu:370-371
     NCT_TRY(nctk_bgr2lab(ctx, ctx->stream, sf, sflab, N));         // ColorTransfer.h:58
-    nct_color_params cp{prm->eps, prm->nonlocal_weight, prm->local_weight, prm->wls_lambda_init, prm->wls_alpha, (double)prm->k_num};
+    const nct_color_params cp = nct_color_params_of(*prm);
     nct_color_debug dbg{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (stages) { dbg.ab_local = stages->ab_local; dbg.ab_nonlocal = stages->ab_nonlocal; dbg.ab_up = stages->ab_up; dbg.rough = stages->roughness;
                   dbg.ab_wls = stages->ab_wls; dbg.cg_iters = stages->cg_iters; dbg.wls_iters = stages->wls_iters; }
-    NCT_TRY(nctk_local_color_transfer(ctx, ctx->stream, derr, slab, glab, sflab, id, kw, layer, h, w, H, W, cp, olab, stages ? &dbg : nullptr));
-    NCT_TRY(nctk_lab2bgr(ctx, ctx->stream, olab, obgr, N, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0));        // ColorTransfer.cpp:1469
+    {
+        nct_color_bufs cb;                                         // T1 .. S1 (its graph part built inside), then the finish on the working grid
+        NCT_TRY(nctk_color_nonlocal(ctx, ctx->stream, derr, slab, glab, id, kw, layer, h, w, H, W, cp, cb, stages ? &dbg : nullptr));
+        NCT_TRY(nctk_color_finish(ctx, ctx->stream, cb.x, h, w, H, W, sflab, H, W, cp, olab, stages ? &dbg : nullptr));
+    }
+    NCT_TRY(nctk_lab2bgr(ctx, ctx->stream, olab, obgr, N, nct_cube_form(*prm)));        // ColorTransfer.cpp:1469
     NCT_D2H(out_bgr_full, obgr, N * 3); NCT_SYNC();
     return NCT_OK;
 }
@@ -129,12 +133,12 @@ int nct_color_finish(nct_ctx* ctx, const double* ab, int h, int w, int work_h, i
     if (!x.ok() || !sf.ok() || !sflab.ok() || !olab.ok() || !obgr.ok()) return NCT_ERR_HIP;
     NCT_H2D(x, ab, sizeof(double) * 6 * n); NCT_H2D(sf, s_bgr_full, N * 3);
     NCT_TRY(nctk_bgr2lab(ctx, ctx->stream, sf, sflab, N));
-    nct_color_params cp{prm->eps, prm->nonlocal_weight, prm->local_weight, prm->wls_lambda_init, prm->wls_alpha, (double)prm->k_num};
+    const nct_color_params cp = nct_color_params_of(*prm);
     nct_color_debug dbg{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (stages) { dbg.ab_up = stages->ab_up; dbg.rough = stages->roughness; dbg.ab_wls = stages->ab_wls; dbg.wls_iters = stages->wls_iters; }
     ctx->wls_split = (prm->flags & NCT_FLAG_LATENCY) ? 1 : 0;
     NCT_TRY(nctk_color_finish(ctx, ctx->stream, x, h, w, work_h, work_w, sflab, H, W, cp, olab, stages ? &dbg : nullptr));
-    NCT_TRY(nctk_lab2bgr(ctx, ctx->stream, olab, obgr, N, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0));
+    NCT_TRY(nctk_lab2bgr(ctx, ctx->stream, olab, obgr, N, nct_cube_form(*prm)));
     NCT_D2H(out_bgr_full, obgr, N * 3); NCT_SYNC();
     return NCT_OK;
 }
@@ -152,7 +156,7 @@ int nct_color_finish_upsample(nct_ctx* ctx, const double* ab_wls, int h, int w, 
     DevBuf<uint8_t> sf(ctx, N * 3), obgr(ctx, N * 3);
     if (!x.ok() || !sf.ok() || !obgr.ok()) return NCT_ERR_HIP;
     NCT_H2D(x, ab_wls, sizeof(double) * 6 * n); NCT_H2D(sf, s_bgr_full, N * 3);
-    NCT_TRY(nctk_finish_upsample(ctx, ctx->stream, x, h, w, sf, H, W, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0, obgr));
+    NCT_TRY(nctk_finish_upsample(ctx, ctx->stream, x, h, w, sf, H, W, nct_cube_form(*prm), obgr));
     NCT_D2H(out_bgr_full, obgr, N * 3); NCT_SYNC();
     return NCT_OK;
 }

@@ -28,7 +28,7 @@ struct nct_ctx {
     // opaque sub-states owned by other translation units
     void* vgg = nullptr;              // struct vgg_weights* (nct_vgg.cpp)
     void* cvt = nullptr;              // struct cvt_dev* (k_cvt.hip): colour-conversion LUTs on the device
-    void* pair = nullptr;             // struct pair_state* (nct_pipeline.cpp): device-resident source/reference/result images
+    void* pair = nullptr;             // struct pair_state* (nct_pipeline.h): device-resident source/reference/result images
     unsigned long long* d_counter = nullptr;   // device counters of the pm kernels (NCT_FLAG_COUNT_EVALS): [0] distance evaluations performed, [1] accepted candidates;
                                                 // 4 slots per pyramid level in pair runs (nct_pipeline.cpp reads [4 l] and [4 l + 1])
     int home_xcd = 0;                           // the XCD this context's single-XCD launches aim at (k_s1.hip: small S1 levels); contexts of a process count round-robin (nct_create)
@@ -105,6 +105,15 @@ template <typename T> struct DevBuf {
 #define NCT_SYNC() NCT_HIP(hipStreamSynchronize(ctx->stream))
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// host-side functions and types shared between translation units that stay out of the library's dynamic symbol table
+#define NCT_LOCAL __attribute__((visibility("hidden")))
+// a host copy for level-wise validation (host nullable): enqueued and waited for
+template <typename T> static inline int dbg_copy(nct_ctx* ctx, hipStream_t s, T* host, const void* dev /* n elements of T */, size_t n) {
+    if (!host) return 0;
+    NCT_HIP(hipMemcpyAsync(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost, s));
+    NCT_HIP(hipStreamSynchronize(s));
+    return 0;
+}
 
 // ---- device-side launchers (all on device pointers, features channel-last HWC fp32) ----
 // k_feat.hip
@@ -177,29 +186,21 @@ int nctk_s1_solve(nct_ctx* ctx, hipStream_t s, const nct_s1_graph& g, const int*
                   const uint8_t* g_lab_level, const double* gx, const double* gy, int layer, int h, int w, double* x, int* cg_iters_host);
 // k_colorsolve.hip
 struct nct_color_params { double eps, nonlocal_weight, local_weight, wls_lambda_init, wls_alpha, k_num; };
+static inline nct_color_params nct_color_params_of(const nct_params& p) { return {p.eps, p.nonlocal_weight, p.local_weight, p.wls_lambda_init, p.wls_alpha, (double)p.k_num}; }
+static inline int nct_cube_form(const nct_params& p) { return (p.flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0; }   // the Lab -> BGR form of nctk_lab2bgr
 struct nct_color_debug { double *ab_local, *ab_nonlocal, *ab_up, *rough, *ab_wls; int* cg_iters; int* wls_iters; };   // host pointers, all nullable
-// a finish target other than the working grid (SPEC §6.1): the source at its original size H x W in 8-bit Lab, and where its recoloured Lab goes
-struct nct_finish_target { const uint8_t* s_lab; int H, W; uint8_t* out_lab; };
 // the largest finish target: S2's hierarchy stays within MG_MAXL levels (k_wls_mg.hip) and each of its arrays below 4 GB (6 fp64 right-hand sides: 3.2 GB)
 #define NCT_FINISH_MAX_SIDE 16384
 #define NCT_FINISH_MAX_PIXELS (1LL << 26)
-// A level of a sequence frame (SPEC §6.3), between S1 and the finish. keep_x ([2][n][3]) / keep_lab ([n][3]): the level's state, X'_(t-1) and L_(t-1) on entry where blend is set,
-// X'_t and L_t on return: with blend one k_seq_blend launch in place into keep_x, which the finish then reads; without (first frame) S1's output is copied there.
-// tau_map_host / ab_blend_host (nullable): host copies for level-wise validation
-// Motion compensation (SPEC §6.4) where field is set: keep_pk ([n] words) is L_(t-1) packed for k_seq_motion and becomes L_t packed; with blend the level's field goes to
-// field ([n][2] int16; parent / ph / pw: the previous level's, null at the first level run; R: that level's radius), the blend gathers through it into S1's own buffer
-// and the result is copied to keep_x. motion_host (nullable): the field's host copy
-struct nct_seq_link { double* keep_x = nullptr; uint8_t* keep_lab = nullptr; bool blend = false; double tau = 0, sigma = 0; double* ab_blend_host = nullptr; double* tau_map_host = nullptr;
-                      uint32_t* keep_pk = nullptr; int16_t* field = nullptr; const int16_t* parent = nullptr; int ph = 0, pw = 0, R = 0, penalty = 0; int16_t* motion_host = nullptr; };
 // the upsampling finish behind a working-size finish (SPEC §6.8): the original source in BGR at H x W, where its result goes, the Lab -> BGR form
 struct nct_finish_up { const uint8_t* s_bgr; int H, W; uint8_t* out_bgr; int form; };
-// H x W: the working size (S1's dWeight); fin (nullable) retargets U1 / S2 / A1 — null: they target H x W, s_lab_full, out_lab_full
-int nctk_local_color_transfer(nct_ctx* ctx, hipStream_t s, const float* err, const uint8_t* s_lab_level, const uint8_t* g_lab_level,
-                              const uint8_t* s_lab_full, const int* knn_id, const double* knn_w, int layer, int h, int w, int H, int W,
-                              const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg,
-                              const nct_s1_graph* graph = nullptr /* the level's prebuilt graph part of S1; null: built inside, on s */,
-                              const nct_finish_target* fin = nullptr, const nct_seq_link* seq = nullptr /* a frame of a sequence (SPEC §6.3): blend S1's output with the kept state */,
-                              const nct_finish_up* up = nullptr /* after the finish: its S2 output upsampled onto the original source (SPEC §6.8) */);
+// what a level's colour stage keeps reserved from T1 until its finish has been enqueued, declared by the caller: the coefficients x ([2][h*w][3]: T1's guess, then S1's
+// output), T2's weights and extremes and — requested between S1 and the finish by a frame of a sequence that reports it (SPEC §6.3) — the tau_p map
+struct NCT_LOCAL nct_color_bufs { DevBuf<double> x, weight; DevBuf<unsigned> mm; DevBuf<double> tmap; };
+// T1, T2 and S1 of a level: its coefficients into b.x. H x W: the working size (S1's dWeight); the finish (nctk_color_finish) reads b.x afterwards
+NCT_LOCAL int nctk_color_nonlocal(nct_ctx* ctx, hipStream_t s, const float* err, const uint8_t* s_lab_level, const uint8_t* g_lab_level, const int* knn_id, const double* knn_w,
+                                  int layer, int h, int w, int H, int W, const nct_color_params& prm, nct_color_bufs& b, const nct_color_debug* dbg,
+                                  const nct_s1_graph* graph = nullptr /* the level's prebuilt graph part of S1; null: built inside, on s */);
 // U1 + roughness + S2 + A1 of coefficients x ([2][h*w][3], device) onto the grid H x W of s_lab_full; Hw x Ww = the working size (the x4 of S2's lambda).
 // up (nullable): S2's output, still on the device, then also goes through the upsampling finish onto up's source
 int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int Hw, int Ww, const uint8_t* s_lab_full, int H, int W,

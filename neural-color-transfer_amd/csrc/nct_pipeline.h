@@ -1,0 +1,101 @@
+// nct_pipeline.h — what the pair / multi-reference run (nct_pipeline.cpp) and the frame sequences (nct_seq.cpp) share: the state, the frame setup, the finish of a level.
+#pragma once
+#include "nct_internal.h"
+#include <chrono>
+// the last level's finish on a source larger than the working size (SPEC §6.1, §6.9): the original source on the device, H x W, where its result goes, and the finish —
+// NCT_FINISH_EXACT moves U1 / S2 / A1 there, NCT_FINISH_UPSAMPLE leaves them at the working size and upsamples S2's output (SPEC §6.8)
+struct full_target { const uint8_t* src = nullptr; int H = 0, W = 0; uint8_t* out = nullptr; int finish = NCT_FINISH_EXACT; };
+
+// An open frame sequence (SPEC §6.3): what nct_seq_begin prepares once and every frame borrows — the reference's pyramid and its five un-normalised taps (HWC, by
+// level) — and the state the blend carries from frame to frame, per level X' ([2][h*w][3] doubles) and L (the frame's level image in 8-bit Lab). All of it comes from
+// the context's arena and outlives the runs; the frame and the reference at working size are pair_state's src / ref[0] as for a pair.
+// While motion compensation is on (SPEC §6.4, nct_seq_set_motion) it also holds, per level, L packed one word per pixel and the level's field (4 B per level pixel each).
+// A propagated frame (SPEC §6.5) with motion on warps X' out of place: warp_x, one map of the largest level run, reserved by the first such frame.
+// The two counters of the key-frame decision (SPEC §6.7 rule 3) are host integers: they cost no device memory.
+// A full-resolution sequence (SPEC §6.9, nct_seq_begin_fullres) keeps all of that on the working-size grids and adds the frame at its original size H0 x W0 and
+// its result: pair_state's full_src / full_out, which live as long as the sequence and are what nct_pair_fit_lut reads; `full` describes them, H = 0 in any other sequence.
+struct seq_state {
+    nct_params prm; double tau = 0, sigma = 0;
+    long frames = 0;                                           // frames since nct_seq_begin / nct_seq_reset: 0 = the next one is a first frame
+    long gap = 0;                                              // propagated frames since the last full frame, whichever call ran them
+    unsigned long long acc = 0;                                // sum of `changed` over the frames nct_seq_frame_auto propagated since the last full frame
+    int ah[5], aw[5], bh[5], bw[5];
+    uint8_t* rpyr[4] = {}; float* rfeat[5] = {};
+    double* keep_x[5] = {}; uint8_t* keep_lab[5] = {};
+    bool motion = false; nct_seq_motion mp = {0, 0, 0};
+    uint32_t* keep_pk[5] = {}; int16_t* field[5] = {};
+    double* warp_x = nullptr;
+    full_target full;
+    const full_target* target() const { return full.H ? &full : nullptr; }
+};
+struct pair_state {
+    uint8_t *src = nullptr, *out = nullptr;                    // device BGR images
+    seq_state* seq = nullptr;
+    uint8_t* ref[NCT_MAX_REFS] = {};                           // the K references (SPEC §6.2; a pair: K = 1)
+    int K = 0;
+    int sh = 0, sw = 0, rh[NCT_MAX_REFS] = {}, rw[NCT_MAX_REFS] = {};
+    uint8_t *full_src = nullptr, *full_out = nullptr;          // a finished full-resolution run (SPEC §6.1): the original source and its result, full_h x full_w, kept for nct_pair_fit_lut
+    int full_h = 0, full_w = 0;
+    bool finished = false;                                     // the last run on these images ran to its end: `out` (or full_out) holds its result
+};
+
+static const int kTapC[5] = {64, 128, 256, 512, 512};       // tap 1 (conv1_1) … tap 5 (conv5_1)
+#define MARK(stage, level) NCT_TRY(ctx->mark(s, nct_stage_tag(stage, level)))
+
+// ---- nct_pipeline.cpp
+NCT_LOCAL pair_state* pair_of(nct_ctx* ctx);
+NCT_LOCAL void drop_images(nct_ctx* ctx, pair_state* P);    // drop what the context holds of the last pair / reference list
+// what a run is asked for beside its result, every member nullable. lv: host copies of the level intermediates; color (a pair only): [5] the colour stage's coefficient
+// maps per level; fin (K = 1 only): the full-resolution finish; seq: the run is a frame of this open sequence, slv: where that frame's X'_t, tau_p and fields go
+struct run_extras { const nct_multi_levels* lv; const nct_color_stages* const* color; const full_target* fin; seq_state* seq; const nct_seq_levels* slv; };
+// run the whole L=5->1 loop on the uploaded source and its K references
+NCT_LOCAL int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const run_extras& x = {});
+// a pair is the list of one reference (SPEC §6.2): its maps are reference 0's NNFs and the merged guide / err; it has no label map and no G_k / E_k of their own
+NCT_LOCAL nct_multi_levels multi_levels_of(const nct_pair_levels& levels);
+// the bracket around a timed run: the constructor clears `timing` (nullable) and switches the stage marks and the kernel clock on as the flags ask; stop() switches them
+// off, whatever became of the run; read(), after a run that succeeded and was synchronised, fills `timing`
+struct run_clock {
+    nct_ctx* const ctx; nct_pair_timing* const timing; const std::chrono::steady_clock::time_point wall0;
+    NCT_LOCAL run_clock(nct_ctx* c, nct_pair_timing* t, int flags);
+    void stop() { ctx->tm_on = false; ctx->kt_on = false; }
+    NCT_LOCAL int read(bool count);
+};
+// level geometry, coarse -> fine (level 0 = conv5_1): four ceil-halvings of h x w
+static inline void level_sizes(int h, int w, int* lh, int* lw) {
+    for (int t = 0; t < 5; ++t) { lh[4 - t] = h; lw[4 - t] = w; h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
+}
+// level l of one image's pyramid (main.cu:104-108): a block of its own, resized from level l + 1; img[l] then names it
+static inline int pyramid_level(nct_ctx* ctx, hipStream_t s, DevBuf<uint8_t>& buf, const uint8_t** img, const int* lh, const int* lw, int l) {
+    if (!buf.alloc(ctx, (size_t)lh[l] * lw[l] * 3)) return NCT_ERR_HIP;
+    NCT_TRY(nctk_resize_u8c3(ctx, s, img[l + 1], lh[l + 1], lw[l + 1], buf, lh[l], lw[l]));
+    img[l] = buf;
+    return NCT_OK;
+}
+// an image the caller holds at h0 x w0 onto the device as dst (h x w): uploaded at its own size and shrunk there (SPEC §6.1 rule 1: nct_resize_u8c3's arithmetic).
+// at0 (nullable): where the original goes and stays; null: scratch, back in the arena once the resize is enqueued
+static inline int upload_shrunk(nct_ctx* ctx, const uint8_t* host, int h0, int w0, uint8_t* dst, int h, int w, uint8_t* at0 = nullptr) {
+    DevBuf<uint8_t> scratch;
+    if (!at0) { if (!scratch.alloc(ctx, (size_t)h0 * w0 * 3)) return NCT_ERR_HIP; at0 = scratch; }
+    NCT_H2D(at0, host, (size_t)h0 * w0 * 3);
+    return nctk_resize_u8c3(ctx, ctx->stream, at0, h0, w0, dst, h, w);
+}
+// The exact finish's two Lab images at full->H x full->W, scratch of the run: open() reserves them and converts the source, and is a no-op for any other finish. A step
+// of its own: a level that runs its colour solve enqueues it BEFORE T1, a propagated frame right before the finish (the order of launches and arena requests)
+struct NCT_LOCAL full_lab {
+    DevBuf<uint8_t> s0, out0;
+    NCT_LOCAL int open(nct_ctx* ctx, hipStream_t s, const full_target* full);
+};
+// The finish of a level: U1 / S2 / A1 of x ([2][h*w][3], the level grid) and the result in BGR. full == null (every level but a full-resolution run's last): onto the
+// working grid H x W, s_lab_full -> out_lab -> out_bgr. The exact finish: onto the original source through fl's images into full->out; out_lab and out_bgr stay as they
+// are. The upsampling finish (SPEC §6.8): the working-size finish, and behind it S2's output upsampled onto the original source into full->out
+NCT_LOCAL int finish_level(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int H, int W, const uint8_t* s_lab_full, uint8_t* out_lab, uint8_t* out_bgr,
+                           const full_target* full, const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube);
+// ---- nct_seq.cpp
+NCT_LOCAL void seq_free(nct_ctx* ctx, pair_state* P);       // what an open sequence holds goes back to the arena
+// SPEC §6.4: level l's field from L_t (`lab`) and the kept packed map: the first level run searches radius0 around (0, 0), every other level radius around twice the
+// previous level's vector
+NCT_LOCAL int seq_motion_level(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, const uint8_t* lab);
+// A level of a sequence frame (SPEC §6.3), between S1 and the finish: X'_t = the blend of S1's output x with X'_(t-1), into the kept state q->keep_x[l], which the finish
+// then reads; L_t (`lab`) replaces L_(t-1). The first frame and tau == 0 only keep the state, with no blend launch. tmap: the caller's, requested here where slv asks
+// for the tau_p map and reserved until the finish has been enqueued. slv (nullable): host copies of X'_t, tau_p and the field
+NCT_LOCAL int seq_level_step(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, const uint8_t* lab, double* x, DevBuf<double>& tmap, const nct_seq_levels* slv);

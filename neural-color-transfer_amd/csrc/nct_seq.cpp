@@ -1,0 +1,404 @@
+// nct_seq.cpp — frame sequences (SPEC §6.3-§6.9): the state an open sequence keeps in the context's arena, what a level of a frame does between S1 and the finish,
+// the frame entry points — a full frame is a run of nct_pipeline.cpp's level loop — the propagated frame, the probe and the key-frame decision.
+#include "nct_pipeline.h"
+#include <cstring>
+#include <algorithm>
+
+// what motion compensation holds goes back to the arena
+static void seq_motion_free(nct_ctx* ctx, seq_state* q) {
+    for (int l = 0; l < 5; ++l) {
+        if (q->keep_pk[l]) { ctx->release(q->keep_pk[l]); q->keep_pk[l] = nullptr; }
+        if (q->field[l]) { ctx->release(q->field[l]); q->field[l] = nullptr; }
+    }
+    if (q->warp_x) { ctx->release(q->warp_x); q->warp_x = nullptr; }
+    q->motion = false;
+}
+// what an open sequence holds goes back to the arena
+void seq_free(nct_ctx* ctx, pair_state* P) {
+    seq_state* q = P->seq;
+    if (!q) return;
+    seq_motion_free(ctx, q);
+    for (int l = 0; l < 5; ++l) {
+        if (l < 4 && q->rpyr[l]) ctx->release(q->rpyr[l]);
+        if (q->rfeat[l]) ctx->release(q->rfeat[l]);
+        if (q->keep_x[l]) ctx->release(q->keep_x[l]);
+        if (q->keep_lab[l]) ctx->release(q->keep_lab[l]);
+    }
+    delete q; P->seq = nullptr;
+}
+
+int seq_motion_level(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, const uint8_t* lab) {
+    return nctk_seq_motion(ctx, s, lab, q->keep_pk[l], q->ah[l], q->aw[l], l > 0 ? q->field[l - 1] : nullptr, l > 0 ? q->ah[l - 1] : 0, l > 0 ? q->aw[l - 1] : 0,
+                           l == 0 ? q->mp.radius0 : q->mp.radius, q->mp.penalty, q->field[l]);
+}
+
+int seq_level_step(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, const uint8_t* lab, double* x, DevBuf<double>& tmap, const nct_seq_levels* slv) {
+    const int h = q->ah[l], w = q->aw[l], n = h * w;
+    const bool blend = q->frames > 0 && q->tau > 0.0;
+    double* const keep_x = q->keep_x[l];
+    if (slv && slv->tau_map[l] && !tmap.alloc(ctx, n)) return NCT_ERR_HIP;
+    if (blend && q->motion) {
+        // with motion (SPEC §6.4): the level's field, then the blend gathers X'_(t-1) and L_(t-1) through it — not in place: into S1's own buffer, then into the state
+        NCT_TRY(seq_motion_level(ctx, s, q, l, lab));
+        NCT_TRY(nctk_seq_blend(ctx, s, x, keep_x, lab, q->keep_lab[l], h, w, q->tau, q->sigma, x, tmap, q->field[l]));
+        NCT_HIP(hipMemcpyAsync(keep_x, x, sizeof(double) * (size_t)6 * n, hipMemcpyDeviceToDevice, s));
+        if (slv) NCT_TRY(dbg_copy(ctx, s, slv->motion[l], q->field[l], (size_t)2 * n));
+    } else if (blend) NCT_TRY(nctk_seq_blend(ctx, s, x, keep_x, lab, q->keep_lab[l], h, w, q->tau, q->sigma, keep_x, tmap));
+    else {
+        NCT_HIP(hipMemcpyAsync(keep_x, x, sizeof(double) * (size_t)6 * n, hipMemcpyDeviceToDevice, s));
+        if (tmap.ok()) NCT_HIP(hipMemsetAsync(tmap, 0, sizeof(double) * (size_t)n, s));
+    }
+    NCT_HIP(hipMemcpyAsync(q->keep_lab[l], lab, (size_t)3 * n, hipMemcpyDeviceToDevice, s));
+    if (q->motion) NCT_TRY(nctk_seq_pack(ctx, s, lab, n, q->keep_pk[l]));
+    if (slv) NCT_TRY(dbg_copy(ctx, s, slv->ab_blend[l], keep_x, (size_t)6 * n));
+    if (tmap.ok()) NCT_TRY(dbg_copy(ctx, s, slv->tau_map[l], (double*)tmap, n));
+    return NCT_OK;
+}
+
+extern "C" {
+
+// ---- frame sequences (SPEC §6.3)
+void nct_seq_params_default(nct_seq_params* p) {
+    if (!p) return;
+    p->tau = 0.7; p->sigma = 10.0;
+}
+
+int nct_seq_end(nct_ctx* ctx) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return NCT_OK;
+    NCT_SYNC();
+    seq_free(ctx, P);
+    drop_images(ctx, P);
+    return NCT_OK;
+}
+
+void nct_seq_motion_default(nct_seq_motion* p) {
+    if (!p) return;
+    p->radius0 = 3; p->radius = 1; p->penalty = 1;
+}
+
+// SPEC §6.4: motion compensation of the open sequence on (from the next frame) or off. Turning it on reserves the packed maps and the fields and packs the kept L of
+// a sequence that already has frames; turning it off gives them back
+int nct_seq_set_motion(nct_ctx* ctx, const nct_seq_motion* mp) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_set_motion: no sequence is open (nct_seq_begin first)");
+    seq_state* q = P->seq;
+    if (mp) {
+        NCT_REQUIRE(mp->radius0 >= 0 && mp->radius0 <= 8, "seq_set_motion: radius0 must be in [0, 8] (got %d)", mp->radius0);
+        NCT_REQUIRE(mp->radius >= 0 && mp->radius <= 3, "seq_set_motion: radius must be in [0, 3] (got %d)", mp->radius);
+        NCT_REQUIRE(mp->penalty >= 0 && mp->penalty <= 255, "seq_set_motion: penalty must be in [0, 255] (got %d)", mp->penalty);
+    }
+    const bool on = mp && (mp->radius0 > 0 || mp->radius > 0);
+    if (!on) {
+        if (q->motion) { NCT_SYNC(); seq_motion_free(ctx, q); }
+        return NCT_OK;
+    }
+    q->mp = *mp;
+    if (q->motion) return NCT_OK;
+    for (int l = 0; l < q->prm.levels; ++l) {
+        const size_t n = (size_t)q->ah[l] * q->aw[l];
+        q->keep_pk[l] = (uint32_t*)ctx->alloc(sizeof(uint32_t) * n); q->field[l] = (int16_t*)ctx->alloc(sizeof(int16_t) * 2 * n);
+        if (!q->keep_pk[l] || !q->field[l]) { seq_motion_free(ctx, q); return NCT_ERR_HIP; }
+    }
+    q->motion = true;
+    if (q->frames > 0) {
+        for (int l = 0; l < q->prm.levels; ++l) {
+            const int rc = nctk_seq_pack(ctx, ctx->stream, q->keep_lab[l], q->ah[l] * q->aw[l], q->keep_pk[l]);
+            if (rc) { seq_motion_free(ctx, q); return rc; }
+        }
+    }
+    return NCT_OK;
+}
+
+int nct_seq_reset(nct_ctx* ctx) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_reset: no sequence is open (nct_seq_begin first)");
+    P->seq->frames = 0; P->seq->gap = 0; P->seq->acc = 0;
+    return NCT_OK;
+}
+
+// the reference once: upload, pyramid (main.cu:104-108), one VGG19 forward with all five taps kept channel-last; and the per-level state
+// rh0 x rw0: the reference as the caller holds it — larger than rh x rw only in a full-resolution sequence, which shrinks it on the device (SPEC §6.9)
+static int seq_prepare(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* ref_bgr, int rh0, int rw0, int rh, int rw, int sh, int sw) {
+    hipStream_t s = ctx->stream;
+    level_sizes(sh, sw, q->ah, q->aw); level_sizes(rh, rw, q->bh, q->bw);
+    P->src = (uint8_t*)ctx->alloc((size_t)sh * sw * 3);
+    P->ref[0] = (uint8_t*)ctx->alloc((size_t)rh * rw * 3);
+    if (!P->src || !P->ref[0]) return NCT_ERR_HIP;
+    P->sh = sh; P->sw = sw; P->K = 1; P->rh[0] = rh; P->rw[0] = rw;
+    for (int l = 0; l < 5; ++l) {
+        const size_t n = (size_t)q->ah[l] * q->aw[l], nr = (size_t)q->bh[l] * q->bw[l];
+        if (l < 4 && !(q->rpyr[l] = (uint8_t*)ctx->alloc(nr * 3))) return NCT_ERR_HIP;
+        if (!(q->rfeat[l] = (float*)ctx->alloc(sizeof(float) * kTapC[4 - l] * nr))) return NCT_ERR_HIP;
+        if (l < q->prm.levels) {
+            if (!(q->keep_x[l] = (double*)ctx->alloc(sizeof(double) * 6 * n)) || !(q->keep_lab[l] = (uint8_t*)ctx->alloc(n * 3))) return NCT_ERR_HIP;
+        }
+    }
+    if (rh0 == rh && rw0 == rw) NCT_H2D(P->ref[0], ref_bgr, (size_t)rh * rw * 3);
+    else NCT_TRY(upload_shrunk(ctx, ref_bgr, rh0, rw0, P->ref[0], rh, rw));
+    if (q->target()) {
+        q->full.src = P->full_src = (uint8_t*)ctx->alloc((size_t)q->full.H * q->full.W * 3); q->full.out = P->full_out = (uint8_t*)ctx->alloc((size_t)q->full.H * q->full.W * 3);
+        if (!P->full_src || !P->full_out) return NCT_ERR_HIP;
+        P->full_h = q->full.H; P->full_w = q->full.W;
+    }
+    const uint8_t* img = P->ref[0];
+    for (int l = 3; l >= 0; --l) {
+        NCT_TRY(nctk_resize_u8c3(ctx, s, img, q->bh[l + 1], q->bw[l + 1], q->rpyr[l], q->bh[l], q->bw[l]));
+        img = q->rpyr[l];
+    }
+    float* taps_hwc[5];
+    for (int t = 0; t < 5; ++t) taps_hwc[t] = q->rfeat[4 - t];
+    NCT_TRY(nctk_vgg19_forward(ctx, s, P->ref[0], rh, rw, rw * 3, 5, nullptr, nullptr, taps_hwc));
+    NCT_SYNC();
+    return NCT_OK;
+}
+
+// what both nct_seq_begin* entry points (`who`) do once the image sizes are settled; full (nullable): the original frame size and the finish of a full-resolution sequence
+static int seq_open(nct_ctx* ctx, const char* who, const uint8_t* ref_bgr, int rh0, int rw0, int rh, int rw, int sh, int sw, const full_target* full, const nct_params* prm,
+                    const nct_seq_params* sp) {
+    NCT_REQUIRE(sp->tau >= 0.0 && sp->tau < 1.0, "%s: tau must be in [0, 1) (got %g)", who, sp->tau);
+    NCT_REQUIRE(sp->sigma > 0.0 && sp->sigma <= 1.7976931348623157e308, "%s: sigma must be finite and positive (got %g)", who, sp->sigma);
+    NCT_REQUIRE(prm->levels >= 1 && prm->levels <= 5, "%s: levels must be in [1, 5] (got %d)", who, prm->levels);
+    NCT_TRY(nct_seq_end(ctx));                                   // a sequence that is still open is closed first
+    pair_state* P = pair_of(ctx);
+    drop_images(ctx, P);
+    seq_state* q = new seq_state();
+    q->prm = *prm; q->tau = sp->tau; q->sigma = sp->sigma;
+    if (full) q->full = *full;
+    P->seq = q;
+    const int rc = seq_prepare(ctx, P, q, ref_bgr, rh0, rw0, rh, rw, sh, sw);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); seq_free(ctx, P); drop_images(ctx, P); }
+    return rc;
+}
+
+int nct_seq_begin(nct_ctx* ctx, const uint8_t* ref_bgr, int rh, int rw, int sh, int sw, const nct_params* prm, const nct_seq_params* sp) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(ref_bgr && prm && sp, "seq_begin: null pointer");
+    NCT_REQUIRE(sh >= 17 && sw >= 17 && rh >= 17 && rw >= 17 && sh <= 4000 && sw <= 4000 && rh <= 4000 && rw <= 4000,
+                "seq_begin: image sides must be in [17, 4000] (got frames of %dx%d and a reference of %dx%d)", sw, sh, rw, rh);
+    return seq_open(ctx, "seq_begin", ref_bgr, rh, rw, rh, rw, sh, sw, nullptr, prm, sp);
+}
+
+// SPEC §6.9: a sequence whose frames and reference arrive at their original size. Everything the sequence keeps lives on the working-size grids, as after
+// nct_seq_begin on the shrunk images; only the last level's finish reaches the original frame
+int nct_seq_begin_fullres(nct_ctx* ctx, const uint8_t* ref_bgr, int rh, int rw, int sh, int sw, int max_side, int finish, const nct_params* prm, const nct_seq_params* sp) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(ref_bgr && prm && sp, "seq_begin_fullres: null pointer");
+    NCT_REQUIRE(finish == NCT_FINISH_EXACT || finish == NCT_FINISH_UPSAMPLE, "seq_begin_fullres: finish must be NCT_FINISH_EXACT (0) or NCT_FINISH_UPSAMPLE (1) (got %d)", finish);
+    int wh = 0, ww = 0, rwh = 0, rww = 0;
+    const char* why = nct_working_size_rule(sh, sw, max_side, &wh, &ww);
+    if (why) return ctx->fail(NCT_ERR_INVALID, "seq_begin_fullres: frames of %dx%d, max_side %d: %s", sw, sh, max_side, why);
+    why = nct_working_size_rule(rh, rw, max_side, &rwh, &rww);
+    if (why) return ctx->fail(NCT_ERR_INVALID, "seq_begin_fullres: reference %dx%d, max_side %d: %s", rw, rh, max_side, why);
+    const full_target full{nullptr, sh, sw, nullptr, finish};    // the two images: seq_prepare
+    return seq_open(ctx, "seq_begin_fullres", ref_bgr, rh, rw, rwh, rww, wh, ww, &full, prm, sp);
+}
+
+// a frame of the open sequence onto the device: into P->src, or (SPEC §6.9) at its original size into full_src and from there shrunk into P->src
+static int seq_upload_frame(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* src_bgr) {
+    if (!q->target()) { NCT_H2D(P->src, src_bgr, (size_t)P->sh * P->sw * 3); return NCT_OK; }
+    return upload_shrunk(ctx, src_bgr, q->full.H, q->full.W, P->src, P->sh, P->sw, P->full_src);
+}
+
+int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_frame: no sequence is open (nct_seq_begin first)");
+    NCT_REQUIRE(src_bgr && out_bgr, "seq_frame: null image");
+    seq_state* q = P->seq;
+    NCT_REQUIRE(!(q->target() && levels), "seq_frame_levels: levels must be NULL in a full-resolution sequence (its result[] arrays have no single size); seq_levels reports the working-size maps");
+    // a level without a field (motion off, a first frame, tau == 0) reports zeros
+    if (seq_levels) for (int l = 0; l < q->prm.levels; ++l) if (seq_levels->motion[l]) memset(seq_levels->motion[l], 0, sizeof(int16_t) * 2 * (size_t)q->ah[l] * q->aw[l]);
+    int rc = seq_upload_frame(ctx, P, q, src_bgr);
+    const nct_multi_levels m = levels ? multi_levels_of(*levels) : nct_multi_levels{};
+    if (rc == NCT_OK) rc = process_resident(ctx, &q->prm, timing, {levels ? &m : nullptr, levels ? levels->color : nullptr, q->target(), q, seq_levels});
+    // a frame that failed may have replaced the state of some levels only: the next frame starts over
+    q->gap = 0; q->acc = 0;                                      // a full frame (and a failed one: the next is a first frame) starts the count over
+    if (rc) { q->frames = 0; return rc; }
+    q->frames += 1;
+    if (!q->target()) return nct_pair_download(ctx, out_bgr);
+    NCT_D2H(out_bgr, P->full_out, (size_t)q->full.H * q->full.W * 3);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
+int nct_seq_frame(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing) {
+    return nct_seq_frame_levels(ctx, src_bgr, out_bgr, timing, nullptr, nullptr);
+}
+
+// SPEC §6.5: what a propagated frame enqueues — the frame's pyramid, per level L_t and (motion on) the field, the warp of the kept X' and the packed map, then the
+// finish of the last level run on the kept X' and the frame's own pixels, and the download. Nothing upstream of the finish runs. L_t goes straight into the state:
+// on this path nothing reads L_(t-1) but the search, which reads its packed form
+static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* slv) {
+    const hipStream_t s = ctx->stream;
+    const nct_params& prm = q->prm;
+    const int H = P->sh, W = P->sw, top = prm.levels - 1;
+    const size_t N = (size_t)H * W;
+    MARK(NCT_ST_OTHER, 0);
+    DevBuf<uint8_t> s_lab_full(ctx, N * 3), out_lab(ctx, N * 3), spyr[4];
+    if (!s_lab_full.ok() || !out_lab.ok()) return NCT_ERR_HIP;
+    NCT_TRY(nctk_bgr2lab(ctx, s, P->src, s_lab_full, N));
+    const uint8_t* simg[5]; simg[4] = P->src;
+    for (int l = 3; l >= 0; --l) NCT_TRY(pyramid_level(ctx, s, spyr[l], simg, q->ah, q->aw, l));
+    MARK(NCT_ST_OTHER, 0);
+    if (q->motion && !q->warp_x && !(q->warp_x = (double*)ctx->alloc(sizeof(double) * 6 * (size_t)q->ah[top] * q->aw[top]))) return NCT_ERR_HIP;
+    if (!P->out) { P->out = (uint8_t*)ctx->alloc(N * 3); if (!P->out) return NCT_ERR_HIP; }
+    for (int l = 0; l <= top; ++l) {
+        const int h = q->ah[l], w = q->aw[l];
+        const size_t n = (size_t)h * w;
+        NCT_TRY(nctk_bgr2lab(ctx, s, simg[l], q->keep_lab[l], n));
+        if (q->motion) {
+            NCT_TRY(seq_motion_level(ctx, s, q, l, q->keep_lab[l]));
+            NCT_TRY(nctk_seq_warp(ctx, s, q->keep_x[l], h, w, q->field[l], q->warp_x));
+            // the scratch has the last level's size: there the two maps change places, elsewhere the warped map is copied back
+            if (l == top) std::swap(q->keep_x[l], q->warp_x);
+            else NCT_HIP(hipMemcpyAsync(q->keep_x[l], q->warp_x, sizeof(double) * 6 * n, hipMemcpyDeviceToDevice, s));
+            NCT_TRY(nctk_seq_pack(ctx, s, q->keep_lab[l], (int)n, q->keep_pk[l]));
+        }
+        if (slv) {
+            if (slv->ab_blend[l]) NCT_HIP(hipMemcpyAsync(slv->ab_blend[l], q->keep_x[l], sizeof(double) * 6 * n, hipMemcpyDeviceToHost, s));
+            if (slv->motion[l]) {
+                if (q->motion) NCT_HIP(hipMemcpyAsync(slv->motion[l], q->field[l], sizeof(int16_t) * 2 * n, hipMemcpyDeviceToHost, s));
+                else memset(slv->motion[l], 0, sizeof(int16_t) * 2 * n);
+            }
+            if (slv->tau_map[l]) std::fill(slv->tau_map[l], slv->tau_map[l] + n, 1.0);          // the previous frame's weight
+        }
+    }
+    // the kept (warped) X' of the last level run finishes on the frame's own pixels: at the working size, or (SPEC §6.9 rule 3) on the original frame
+    ctx->tm_level = top;
+    int wls_it[6] = {0, 0, 0, 0, 0, 0};
+    const nct_color_debug dbg{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, wls_it};
+    full_lab fl;
+    NCT_TRY(fl.open(ctx, s, q->target()));
+    NCT_TRY(finish_level(ctx, s, q->keep_x[top], q->ah[top], q->aw[top], H, W, s_lab_full, out_lab, P->out, q->target(), fl, nct_color_params_of(prm), timing ? &dbg : nullptr, nct_cube_form(prm)));
+    if (timing) timing->wls_iters[top] = *std::max_element(wls_it, wls_it + 6);
+    MARK(NCT_ST_COLOR, top);
+    if (q->target()) NCT_D2H(out_bgr, P->full_out, (size_t)q->full.H * q->full.W * 3);
+    else NCT_D2H(out_bgr, P->out, N * 3);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
+int nct_seq_frame_propagate_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* seq_levels) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_frame_propagate: no sequence is open (nct_seq_begin first)");
+    seq_state* q = P->seq;
+    if (q->frames == 0) return ctx->fail(NCT_ERR_STATE, "seq_frame_propagate: the sequence has no state to propagate (the first frame after nct_seq_begin / nct_seq_reset is nct_seq_frame's)");
+    NCT_REQUIRE(src_bgr && out_bgr, "seq_frame_propagate: null image");
+    run_clock clock(ctx, timing, q->prm.flags);
+    int rc = seq_upload_frame(ctx, P, q, src_bgr);
+    if (rc == NCT_OK) rc = propagate_run(ctx, P, q, out_bgr, timing, seq_levels);
+    clock.stop();
+    // a frame that failed may have replaced the state of some levels only: the next frame starts over
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); q->frames = 0; q->gap = 0; q->acc = 0; return rc; }
+    q->frames += 1; q->gap += 1;
+    return clock.read(false);
+}
+
+int nct_seq_frame_propagate(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing) {
+    return nct_seq_frame_propagate_levels(ctx, src_bgr, out_bgr, timing, nullptr);
+}
+
+// ---- adaptive key frames (SPEC §6.7)
+void nct_seq_auto_default(nct_seq_auto* p) {
+    if (!p) return;
+    p->threshold = 24; p->cut_permille = 500; p->key_permille = 100; p->max_gap = 8;
+}
+
+static const char* seq_auto_check(const nct_seq_auto& a) {
+    if (a.threshold < 0 || a.threshold > 765) return "threshold must be in [0, 765]";
+    if (a.cut_permille < 0 || a.cut_permille > 1001) return "cut_permille must be in [0, 1001]";
+    if (a.key_permille < 0 || a.key_permille > 1001) return "key_permille must be in [0, 1001]";
+    if (a.max_gap < 1 || a.max_gap > 1000) return "max_gap must be in [1, 1000]";
+    return nullptr;
+}
+
+// SPEC §6.7 rule 3 on a measured frame: 64-bit integers, in this order. 1001 is "never": changed <= pixels makes the cut's comparison say so by itself; the accumulated
+// count may exceed the pixels, so the key's 1001 is tested apart
+static int seq_decide(const nct_seq_auto& a, const nct_seq_change_rec& c, unsigned long long acc, long gap) {
+    const unsigned long long px = c.pixels;
+    if ((unsigned long long)c.changed * 1000ull >= (unsigned long long)a.cut_permille * px) return NCT_SEQ_CUT;
+    if (gap >= a.max_gap - 1 || (a.key_permille != 1001 && (acc + c.changed) * 1000ull >= (unsigned long long)a.key_permille * px)) return NCT_SEQ_KEY;
+    return NCT_SEQ_PROPAGATED;
+}
+
+// SPEC §6.7 rule 2: what the probe enqueues — the frame into scratch (P->src may still be read by nct_pair_fit_lut), its pyramid, L_t[l] for l = 0 … lambda, with motion on
+// the level's field against the kept packed map into the level's field buffer (scratch between frames), the measure at lambda, 16 bytes back. The kept L, the packed
+// maps, X' and the counters are only read
+static int probe_run(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* src_bgr, int threshold, int lambda, nct_seq_change_rec* rec) {
+    const hipStream_t s = ctx->stream;
+    const size_t N = (size_t)P->sh * P->sw;
+    DevBuf<uint8_t> frame(ctx, N * 3), spyr[4], lab[3];
+    DevBuf<nct_seq_change_rec> d_rec(ctx, 1);
+    if (!frame.ok() || !d_rec.ok()) return NCT_ERR_HIP;
+    if (q->target()) NCT_TRY(upload_shrunk(ctx, src_bgr, q->full.H, q->full.W, frame, P->sh, P->sw));     // SPEC §6.9: the original frame into scratch of its own size
+    else NCT_H2D(frame, src_bgr, N * 3);
+    const uint8_t* simg[5]; simg[4] = frame;
+    for (int l = 3; l >= 0; --l) NCT_TRY(pyramid_level(ctx, s, spyr[l], simg, q->ah, q->aw, l));
+    for (int l = 0; l <= lambda; ++l) {
+        const int h = q->ah[l], w = q->aw[l];
+        if (!lab[l].alloc(ctx, (size_t)h * w * 3)) return NCT_ERR_HIP;
+        NCT_TRY(nctk_bgr2lab(ctx, s, simg[l], lab[l], (size_t)h * w));
+        if (q->motion) NCT_TRY(seq_motion_level(ctx, s, q, l, lab[l]));
+    }
+    NCT_TRY(nctk_seq_change(ctx, s, lab[lambda], q->keep_lab[lambda], q->ah[lambda], q->aw[lambda], q->motion ? q->field[lambda] : nullptr, threshold, d_rec));
+    NCT_D2H(rec, d_rec, sizeof *rec);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
+// the checks of nct_seq_probe / nct_seq_frame_auto, then the probe and the decision; first_ok: a sequence without state is NCT_SEQ_FIRST, not an error
+static int seq_probe_decide(nct_ctx* ctx, const char* who, const uint8_t* src_bgr, const nct_seq_auto* a, bool first_ok, nct_seq_auto* used, nct_seq_decision* d) {
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "%s: no sequence is open (nct_seq_begin first)", who);
+    seq_state* q = P->seq;
+    if (q->frames == 0 && !first_ok)
+        return ctx->fail(NCT_ERR_STATE, "%s: the sequence has no state to compare with (the first frame after nct_seq_begin / nct_seq_reset is nct_seq_frame's)", who);
+    NCT_REQUIRE(src_bgr, "%s: null image", who);
+    if (a) *used = *a; else nct_seq_auto_default(used);
+    if (const char* why = seq_auto_check(*used)) return ctx->fail(NCT_ERR_INVALID, "%s: %s", who, why);
+    memset(d, 0, sizeof *d);
+    d->acc_changed = (uint32_t)std::min<unsigned long long>(q->acc, 0xffffffffull); d->gap = (int)q->gap;
+    if (q->frames == 0) { d->kind = NCT_SEQ_FIRST; d->level = -1; return NCT_OK; }
+    const auto wall0 = std::chrono::steady_clock::now();
+    d->level = std::min(q->prm.levels - 1, 2);
+    const int rc = probe_run(ctx, P, q, src_bgr, used->threshold, d->level, &d->change);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }     // the probe wrote no state: the sequence stays as it was
+    d->probe_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    d->kind = seq_decide(*used, d->change, q->acc, q->gap);
+    return NCT_OK;
+}
+
+int nct_seq_probe(nct_ctx* ctx, const uint8_t* src_bgr, const nct_seq_auto* a, nct_seq_decision* out) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(out, "seq_probe: null out");
+    nct_seq_auto used; nct_seq_decision d;
+    NCT_TRY(seq_probe_decide(ctx, "seq_probe", src_bgr, a, false, &used, &d));
+    *out = d;
+    return NCT_OK;
+}
+
+// SPEC §6.7 rule 4: probe, decide, one of the existing calls, the counters
+int nct_seq_frame_auto(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_auto* a, nct_seq_decision* out) {
+    NCT_CTX_ENTER();
+    // refused before the probe runs; without an open sequence the state error below comes first, as in the other frame calls
+    NCT_REQUIRE(!ctx->pair || !((pair_state*)ctx->pair)->seq || out_bgr, "seq_frame_auto: null image");
+    nct_seq_auto used; nct_seq_decision d;
+    NCT_TRY(seq_probe_decide(ctx, "seq_frame_auto", src_bgr, a, true, &used, &d));
+    seq_state* q = ((pair_state*)ctx->pair)->seq;
+    if (out) *out = d;
+    if (d.kind == NCT_SEQ_PROPAGATED) {
+        const unsigned long long acc = q->acc + d.change.changed;
+        NCT_TRY(nct_seq_frame_propagate(ctx, src_bgr, out_bgr, timing));      // counts the frame in gap
+        q->acc = acc;
+        return NCT_OK;
+    }
+    if (d.kind == NCT_SEQ_CUT) NCT_TRY(nct_seq_reset(ctx));
+    return nct_seq_frame(ctx, src_bgr, out_bgr, timing);                      // zeroes both counters
+}
+
+}  // extern "C"
