@@ -29,7 +29,8 @@ extern "C" {
  * bump; 111 — nct_multi_levels and the entry points for several references; 112 — frame sequences, nct_seq_*; 113 — nct_seq_levels.motion and motion-compensated
  * sequences, nct_seq_set_motion; 114 — propagated frames, nct_seq_frame_propagate and nct_seq_warp; 115 — the single-layer conv seams nct_conv3x3_dev and
  * nct_conv3x3_pair_dev; 116 — 3D colour look-up tables, nct_lut_*; 117 — adaptive key frames, nct_seq_change, nct_seq_probe and nct_seq_frame_auto; 118 — the upsampling finish and
- * full-resolution sequences, nct_color_finish_upsample, nct_process_pair_fullres_finish and nct_seq_begin_fullres). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
+ * full-resolution sequences, nct_color_finish_upsample, nct_process_pair_fullres_finish and nct_seq_begin_fullres; still 118 with the guided finish, nct_color_finish_guided[_dev], nct_set_finish_guided and nct_guided_params: no struct
+ * changed layout and no existing entry point changed meaning, entry points were only added). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
 #define NCT_VERSION 118
 
@@ -277,6 +278,29 @@ int nct_color_finish_upsample_dev(nct_ctx* ctx, const double* d_ab_wls, int h, i
                                   uint8_t* d_out_bgr_full);
 int nct_process_pair_fullres_finish(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw, int max_side, int finish,
                                     const nct_params* prm, uint8_t* out_bgr /* sh x sw x 3 */, nct_pair_timing* timing);
+
+/* ---- the guided finish (SPEC §6.10; an extension): the upsampling finish made edge-aware, a MODIFIER of NCT_FINISH_UPSAMPLE and not a third finish. S2 is edge-aware,
+ * so ab_wls jumps at object boundaries and the bilinear stretch above smears every jump over the original-to-working ratio in original pixels. The guided finish is the
+ * joint-bilateral upsampling: per original pixel, with L = nct_bgr2lab_u8(S0) and (s, f) the source index and fraction of nct_resize's bilinear rule per axis, the
+ * 4 x 4 working-size taps (s_y + j, s_x + k), j, k = -1 .. 2 (j outer), that lie inside the grid get the weight
+ *     g = (1 - |f_y - j| / 2) (1 - |f_x - k| / 2) / (1 + d2 / sigma^2),    d2 = the integer squared distance of L and lab_work(tap) over the three bytes,
+ * a tap whose spatial weight is exactly 0 is skipped (a NaN coefficient there stays out), a = sum g a(tap) / sum g, b likewise, in tap order in double, then A1 and
+ * Lab -> BGR as above. lab_work: the 8-bit Lab image of the WORKING-size source (h*w*3, nct_bgr2lab_u8 of the shrunk source). sigma: finite and > 0, in 8-bit Lab
+ * units, its square finite and > 0 as well; default 10. Equal sizes give nct_color_finish_upsample's bytes. One kernel, 3 B read and 3 B written per original
+ * pixel, no original-size intermediate. nct_color_finish_guided: host pointers, synchronous; nct_color_finish_guided_dev: device pointers, enqueued on the context's
+ * stream. Limits and refusals as nct_color_finish_upsample; a bad sigma is NCT_ERR_INVALID.
+ * nct_set_finish_guided: non-null turns the modifier on for this context, NULL turns it off (the default); a bad sigma is NCT_ERR_INVALID and leaves the setting as
+ * it was. It may be called at any time, also while a sequence is open, and takes effect with the next finish that is enqueued. While it is on, every upsampling
+ * finish behind a working-size finish runs guided, with that finish's own Lab image as the guide and no further device memory: nct_process_pair_fullres_finish(...,
+ * NCT_FINISH_UPSAMPLE, ...) and the full, propagated and auto frames of nct_seq_begin_fullres(..., NCT_FINISH_UPSAMPLE, ...). Unaffected: NCT_FINISH_EXACT,
+ * nct_color_finish_upsample[_dev] themselves, sources that need no shrinking and everything at the working size (a sequence's state, probes, decisions). */
+typedef struct nct_guided_params { double sigma; } nct_guided_params;
+void nct_guided_params_default(nct_guided_params* p);
+int nct_color_finish_guided(nct_ctx* ctx, const double* ab_wls, const uint8_t* lab_work, int h, int w, const uint8_t* s_bgr_full, int H, int W, const nct_guided_params* guided,
+                            const nct_params* prm, uint8_t* out_bgr_full);
+int nct_color_finish_guided_dev(nct_ctx* ctx, const double* d_ab_wls, const uint8_t* d_lab_work, int h, int w, const uint8_t* d_s_bgr_full, int H, int W,
+                                const nct_guided_params* guided, const nct_params* prm, uint8_t* d_out_bgr_full);
+int nct_set_finish_guided(nct_ctx* ctx, const nct_guided_params* guided);
 
 /* ---- several references (SPEC §6.2; an extension: the paper describes it, the reference ships the single-reference form only).
  * Every level runs nct_pair_run's correspondence once per reference R_k (its own NNFs, its own random-search radius max(H, W, RH_k, RW_k), the single-pair seeds),

@@ -161,4 +161,37 @@ int nct_color_finish_upsample(nct_ctx* ctx, const double* ab_wls, int h, int w, 
     return NCT_OK;
 }
 
+// ---- the guided finish (SPEC §6.10): the upsampling finish with joint-bilateral weights (k_finish_up.hip: k_finish_guided)
+void nct_guided_params_default(nct_guided_params* p) {
+    if (!p) return;
+    p->sigma = 10.0;
+}
+
+// the modifier of a context: non-null = every upsampling finish behind a working-size finish (finish_level, nct_pipeline.cpp) runs guided from the next one enqueued on
+int nct_set_finish_guided(nct_ctx* ctx, const nct_guided_params* guided) {
+    if (!ctx) return NCT_ERR_INVALID;
+    NCT_REQUIRE(!guided || nct_guided_sigma_ok(guided->sigma), "set_finish_guided: sigma must be finite and > 0, and so must its square (got %g)", guided->sigma);
+    ctx->guided_sigma = guided ? guided->sigma : 0.0;
+    return NCT_OK;
+}
+
+int nct_color_finish_guided(nct_ctx* ctx, const double* ab_wls, const uint8_t* lab_work, int h, int w, const uint8_t* s_bgr_full, int H, int W, const nct_guided_params* guided,
+                            const nct_params* prm, uint8_t* out_bgr_full) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(ab_wls && lab_work && s_bgr_full && guided && prm && out_bgr_full, "color_finish_guided: null pointer");
+    NCT_REQUIRE(h >= 1 && w >= 1 && h <= NCT_FINISH_MAX_SIDE && w <= NCT_FINISH_MAX_SIDE && (long long)h * w <= NCT_FINISH_MAX_PIXELS,
+                "color_finish_guided: grid %dx%d outside [1x1, 16384 per side, 2^26 px]", w, h);
+    NCT_REQUIRE(H >= h && W >= w, "color_finish_guided: target %dx%d smaller than the grid %dx%d", W, H, w, h);
+    NCT_REQUIRE(H <= NCT_FINISH_MAX_SIDE && W <= NCT_FINISH_MAX_SIDE && (long long)H * W <= NCT_FINISH_MAX_PIXELS, "color_finish_guided: target %dx%d above 16384 per side or 2^26 pixels", W, H);
+    NCT_REQUIRE(nct_guided_sigma_ok(guided->sigma), "color_finish_guided: sigma must be finite and > 0, and so must its square (got %g)", guided->sigma);
+    const size_t n = (size_t)h * w, N = (size_t)H * W;
+    DevBuf<double> x(ctx, 6 * n);
+    DevBuf<uint8_t> lw(ctx, n * 3), sf(ctx, N * 3), obgr(ctx, N * 3);
+    if (!x.ok() || !lw.ok() || !sf.ok() || !obgr.ok()) return NCT_ERR_HIP;
+    NCT_H2D(x, ab_wls, sizeof(double) * 6 * n); NCT_H2D(lw, lab_work, n * 3); NCT_H2D(sf, s_bgr_full, N * 3);
+    NCT_TRY(nctk_finish_guided(ctx, ctx->stream, x, lw, h, w, sf, H, W, guided->sigma, nct_cube_form(*prm), obgr));
+    NCT_D2H(out_bgr_full, obgr, N * 3); NCT_SYNC();
+    return NCT_OK;
+}
+
 }  // extern "C"

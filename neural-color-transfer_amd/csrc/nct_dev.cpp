@@ -202,4 +202,11 @@ int nct_color_finish_upsample_dev(nct_ctx* ctx, const double* d_ab_wls, int h, i
     return nctk_finish_upsample(ctx, ctx->stream, d_ab_wls, h, w, d_s_bgr_full, H, W, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0, d_out_bgr_full);
 }
 
+int nct_color_finish_guided_dev(nct_ctx* ctx, const double* d_ab_wls, const uint8_t* d_lab_work, int h, int w, const uint8_t* d_s_bgr_full, int H, int W,
+                                const nct_guided_params* guided, const nct_params* prm, uint8_t* d_out_bgr_full) {                                     /* SPEC §6.10 */
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(guided && prm, "color_finish_guided_dev: null pointer");
+    return nctk_finish_guided(ctx, ctx->stream, d_ab_wls, d_lab_work, h, w, d_s_bgr_full, H, W, guided->sigma, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0, d_out_bgr_full);
+}
+
 }  // extern "C"

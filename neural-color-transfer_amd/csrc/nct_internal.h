@@ -61,6 +61,8 @@ struct nct_ctx {
     int kt_begin(hipStream_t s, int id);        // nct_api.cpp; no-ops unless kt_on
     int kt_end(hipStream_t s);
 
+    double guided_sigma = 0.0;                  // nct_set_finish_guided (SPEC §6.10): > 0 = every upsampling finish behind a working-size finish runs guided with this sigma; 0 = off (the default)
+
     int fail(int code, const char* fmt, ...) {
         char buf[512]; va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
         err = buf; return code;
@@ -193,7 +195,8 @@ struct nct_color_debug { double *ab_local, *ab_nonlocal, *ab_up, *rough, *ab_wls
 #define NCT_FINISH_MAX_SIDE 16384
 #define NCT_FINISH_MAX_PIXELS (1LL << 26)
 // the upsampling finish behind a working-size finish (SPEC §6.8): the original source in BGR at H x W, where its result goes, the Lab -> BGR form
-struct nct_finish_up { const uint8_t* s_bgr; int H, W; uint8_t* out_bgr; int form; };
+// sigma > 0: the guided finish (SPEC §6.10) with the working-size Lab image of that finish as its guide; 0: the plain bilinear one
+struct nct_finish_up { const uint8_t* s_bgr; int H, W; uint8_t* out_bgr; int form; double sigma; };
 // what a level's colour stage keeps reserved from T1 until its finish has been enqueued, declared by the caller: the coefficients x ([2][h*w][3]: T1's guess, then S1's
 // output), T2's weights and extremes and — requested between S1 and the finish by a frame of a sequence that reports it (SPEC §6.3) — the tau_p map
 struct NCT_LOCAL nct_color_bufs { DevBuf<double> x, weight; DevBuf<unsigned> mm; DevBuf<double> tmap; };
@@ -207,6 +210,11 @@ int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w
                       const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg, const nct_finish_up* up = nullptr);
 // k_finish_up.hip — SPEC §6.8: ab_wls ([2][h*w][3], device) upsampled (U1's arithmetic) and applied (A1's) to s_bgr_full (H x W >= h x w), BGR in, BGR out, one kernel
 int nctk_finish_upsample(nct_ctx* ctx, hipStream_t s, const double* ab_wls, int h, int w, const uint8_t* s_bgr_full, int H, int W, int form, uint8_t* out_bgr_full);
+// k_finish_up.hip — SPEC §6.10: the same pass with joint-bilateral weights; lab_work ([h*w][3], device): the 8-bit Lab image of the working-size source. Equal sizes: nctk_finish_upsample
+int nctk_finish_guided(nct_ctx* ctx, hipStream_t s, const double* ab_wls, const uint8_t* lab_work, int h, int w, const uint8_t* s_bgr_full, int H, int W, double sigma, int form,
+                       uint8_t* out_bgr_full);
+// sigma and sigma^2 (what the kernel divides by) are finite and > 0
+static inline bool nct_guided_sigma_ok(double sigma) { const double s2 = sigma * sigma; return sigma > 0.0 && s2 > 0.0 && s2 <= 1.7976931348623157e308; }
 // SPEC §6.1 rule 1 + the limits of rule 5: nullptr and the working size, or the reason the image is refused (a static string)
 const char* nct_working_size_rule(int h, int w, int max_side, int* work_h, int* work_w);
 void nct_set_ctxless_error(const char* msg);   // nct_api.cpp

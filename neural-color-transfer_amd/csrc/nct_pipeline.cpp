@@ -96,7 +96,7 @@ int finish_level(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int
         NCT_TRY(nctk_color_finish(ctx, s, x, h, w, H, W, fl.s0, full->H, full->W, cp, fl.out0, dbg));
         return nctk_lab2bgr(ctx, s, fl.out0, full->out, (size_t)full->H * full->W, cube);
     }
-    const nct_finish_up up{full ? full->src : nullptr, full ? full->H : 0, full ? full->W : 0, full ? full->out : nullptr, cube};
+    const nct_finish_up up{full ? full->src : nullptr, full ? full->H : 0, full ? full->W : 0, full ? full->out : nullptr, cube, ctx->guided_sigma /* nct_set_finish_guided */};
     NCT_TRY(nctk_color_finish(ctx, s, x, h, w, H, W, s_lab_full, H, W, cp, out_lab, dbg, full ? &up : nullptr));
     return nctk_lab2bgr(ctx, s, out_lab, out_bgr, (size_t)H * W, cube);
 }

@@ -1,6 +1,6 @@
 // nct_pixel.h — the per-pixel bodies of the 8-bit BGR<->Lab conversions (k_cvt.hip), of the 64FC3 bilinear resize (k_cvt.hip) and of A1 (k_colorsolve.hip), as
 // __device__ functions: the kernels that run one of them per launch and the upsampling finish (k_finish_up.hip, SPEC §6.8), which runs all four per pixel,
-// share ONE copy of each expression. The build has -ffp-contract=off: an expression written once rounds the same way wherever it is inlined.
+// share ONE copy of each expression; the guided finish (SPEC §6.10) adds its tap weights below. The build has -ffp-contract=off: an expression written once rounds the same way wherever it is inlined.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -88,6 +88,17 @@ __device__ __forceinline__ double resize_f64_px(double p00, double p01, double p
     const double r1 = cx.tail ? p10 * 1.0 : p10 * a0 + p11 * a1;
     return r0 * b0 + r1 * b1;
 }
+
+// SPEC §6.10, the guided upsampling finish (k_finish_up.hip: k_finish_guided). The spatial weight of the tap at offset j (-1 .. 2) from lin_coef's source index, f its
+// fraction as a double: a tent of half-width 2 working pixels; 0 only at j = 2 with f = 0
+__device__ __forceinline__ double tent2_px(double f, int j) { return 1.0 - fabs(f - (double)j) * 0.5; }
+// the squared distance of two Lab triples, lw packed L | a << 8 | b << 16: 0 .. 195075
+__device__ __forceinline__ int lab_d2_px(const unsigned char* lab, unsigned lw) {
+    const int d0 = (int)lab[0] - (int)(lw & 255u), d1 = (int)lab[1] - (int)((lw >> 8) & 255u), d2 = (int)lab[2] - (int)((lw >> 16) & 255u);
+    return d0 * d0 + d1 * d1 + d2 * d2;
+}
+// a tap's weight: its spatial weight vu over 1 + d2 / sigma^2 (IEEE division twice, no transcendental)
+__device__ __forceinline__ double guided_weight_px(double vu, int d2, double s2) { return vu / (1.0 + (double)d2 / s2); }
 
 // A1: one Lab byte recoloured by its coefficients (ColorTransfer.cpp:1452-1466)
 __device__ __forceinline__ unsigned char apply_px(double a, double b, unsigned char lab) {

@@ -11,6 +11,7 @@
 // `-seq 1` (+ `-tau`, `-sigma`): consecutive lines with one and the same reference are the frames of a sequence, graded with temporally blended coefficients (SPEC §6.3).
 // `-motion 1` (+ `-mr0`, `-mr`, `-mpen`): the blend of a sequence follows the motion between the frames (SPEC §6.4).
 // `-seqfull 1|2`: a sequence takes and returns frames at their own size, with the exact or the upsampling finish (SPEC §6.9).
+// `-upguide 1` (+ `-upsigma`): the upsampling finish of `-fullres 2` / `-seqfull 2` runs guided by the working-size image, which keeps coefficient edges sharp (SPEC §6.10).
 // `-key N`: only every N-th frame of a sequence runs the whole pair; the others are propagated from the frame before them (SPEC §6.5).
 // `-autokey 1` (+ `-keythr`, `-keycut`, `-keychange`, `-keygap`): the library decides per frame whether it is propagated, a key frame or a scene cut (SPEC §6.7).
 #include <sys/stat.h>
@@ -119,6 +120,7 @@ std::mutex g_print;
 struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bool resume = false, vis = false, fullres = false, seq = false, motion = false; nct_seq_params sp; nct_seq_motion mp; int key = 1; bool autokey = false; nct_seq_auto ap; int rank = 0, world = 1;
                 int lut = 0; double lut_lambda = 0.0; bool lutfull = false;
                 int finish = NCT_FINISH_EXACT;          // -fullres 1 / 2: the exact or the upsampling finish (SPEC §6.1 / §6.8)
+                bool upguide = false; nct_guided_params gp;   // -upguide 1, -upsigma: the guided modifier of the upsampling finish (SPEC §6.10), set on every context
                 int seqfull = 0; };                      // -seqfull 1 / 2: full-resolution sequences (SPEC §6.9) with the exact or the upsampling finish   // -lut N (0 = off), -lutlambda (0 = the library's default), -lutfull 1
 
 // ---- ENABLE_VIS debug outputs (Config.h:8) behind the runtime flag -vis 1: per pyramid level the flow maps of both NNFs (reconstruct_flow,
@@ -709,7 +711,8 @@ int main(int argc, char** argv) {
     nct_seq_motion_default(&cfg.mp);
     nct_seq_auto_default(&cfg.ap);
     int autokey = 0;
-    int motion = 0, key = 1, lut = 0, lutfull = 0, seqfull = 0;
+    int motion = 0, key = 1, lut = 0, lutfull = 0, seqfull = 0, upguide = 0;
+    nct_guided_params_default(&cfg.gp);
     double lutlambda = 0.0; bool lutlambda_set = false;
     int gpu = 0, ngpus = 1, seed = 1, inflight = 1, levels = 5, resume = 0, feat16 = 0, vis = 0, fullres = 0, seq = 0, io = -1, pin = 1, world = 1, rank = 0, steal = 0, procs = 0, rccl = 0;
     cl.add("m", cfg.model_dir, "Directory of network models.");
@@ -740,6 +743,8 @@ int main(int argc, char** argv) {
     cl.add("feat16", feat16, "[extension] 1 = fp16 PatchMatch feature tiles (fp32 accumulate); not bit-identical to the default (about 45 dB against it).");
     cl.add("seq", seq, "[extension] 1 = consecutive pairs.txt lines with one and the same reference and weight are the frames of a sequence (SPEC 6.3): one worker runs them in file order and blends each frame's colour coefficients with the previous frame's; every worker does its own file I/O (-io is not used); not with -fullres 1 or -vis 1.");
     cl.add("seqfull", seqfull, "[extension] -seq 1: 1 = full-resolution sequences (SPEC 6.9): frames are passed and returned at their own size, the sequence's state stays at the working size and the last level's finish runs at the original size; 2 = the same with the upsampling finish (SPEC 6.8); not with -lutfull 1.");
+    cl.add("upguide", upguide, "[extension] -fullres 2 or -seqfull 2: 1 = the upsampling finish is guided by the working-size image (SPEC 6.10): each original pixel weights its 4 x 4 working-size coefficient taps by how well their colour matches its own, which keeps the coefficients' edges sharp.");
+    cl.add("upsigma", cfg.gp.sigma, "[extension] -upguide 1: how far a tap's colour may be from the pixel's before its weight halves, in 8-bit Lab units (finite, > 0).");
     cl.add("tau", cfg.sp.tau, "[extension] -seq 1: temporal weight in [0, 1); 0 = every frame on its own.");
     cl.add("sigma", cfg.sp.sigma, "[extension] -seq 1: sensitivity of the blend to changes between frames, in 8-bit Lab units (> 0).");
     cl.add("motion", motion, "[extension] -seq 1: 1 = motion-compensated blend (SPEC 6.4): every level finds per pixel where it was in the previous frame (5 x 5 block match on the Lab level images, coarse to fine) and blends with the coefficients there.");
@@ -774,6 +779,9 @@ int main(int argc, char** argv) {
     if (fullres < 0 || fullres > 2) { printf("Error: -fullres %d is not one of 0, 1, 2.\n", fullres); return -1; }
     if (seqfull < 0 || seqfull > 2) { printf("Error: -seqfull %d is not one of 0, 1, 2.\n", seqfull); return -1; }
     if (seqfull && !seq) { printf("Error: -seqfull %d needs -seq 1 (it chooses how a sequence reaches the frames' own size).\n", seqfull); return -1; }
+    if (upguide < 0 || upguide > 1) { printf("Error: -upguide %d is not one of 0, 1.\n", upguide); return -1; }
+    if (upguide && fullres != 2 && seqfull != 2) { printf("Error: -upguide 1 needs -fullres 2 or -seq 1 -seqfull 2 (it modifies the upsampling finish).\n"); return -1; }
+    if (!(cfg.gp.sigma > 0.0 && cfg.gp.sigma * cfg.gp.sigma > 0.0 && cfg.gp.sigma * cfg.gp.sigma <= 1.7976931348623157e308)) { printf("Error: -upsigma %g is not finite and greater than 0 (and its square as well).\n", cfg.gp.sigma); return -1; }
     if (fullres && vis) { printf("Error: -fullres %d cannot be combined with -vis 1 (the -vis dumps are working-size images).\n", fullres); return -1; }
     if (seq && fullres) { printf("Error: -seq 1 cannot be combined with -fullres 1 (a sequence runs at the working size only). Full-resolution sequences are -seqfull 1 or 2.\n"); return -1; }
     if (seq && vis) { printf("Error: -seq 1 cannot be combined with -vis 1 (the -vis dumps describe single pairs).\n"); return -1; }
@@ -834,6 +842,7 @@ int main(int argc, char** argv) {
     cfg.vis = vis != 0;
     cfg.fullres = fullres != 0; cfg.finish = fullres == 2 ? NCT_FINISH_UPSAMPLE : NCT_FINISH_EXACT;
     cfg.seqfull = seqfull;
+    cfg.upguide = upguide != 0;
     cfg.seq = seq != 0;
     cfg.motion = motion != 0;
     cfg.key = key;
@@ -893,6 +902,7 @@ int main(int argc, char** argv) {
         const int g = j % ngpus, dev = device_of(g);
         if (nct_create(dev, &ctxs[j]) != NCT_OK) { printf("Error: %s\n", nct_last_error(nullptr)); return -1; }
         if (j < ngpus) { char name[256]; nct_device_name(ctxs[j], name, sizeof name); printf("Set device %d: %s.\n", dev, name); }
+        if (cfg.upguide && nct_set_finish_guided(ctxs[j], &cfg.gp) != NCT_OK) { printf("Error: %s\n", nct_last_error(ctxs[j])); return -1; }
         int owner = -1;
         for (int k = 0; k < j; ++k) if (device_of(k % ngpus) == dev) { owner = k; break; }
         const int rc = owner < 0 ? (++uploads, nct_vgg19_load_model(ctxs[j], host_model)) : nct_vgg19_share_weights(ctxs[j], ctxs[owner]);

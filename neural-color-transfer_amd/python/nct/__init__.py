@@ -94,6 +94,10 @@ SIGNATURES = {
     "nct_process_pair_fullres_finish": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p]),
     "nct_color_finish_upsample": (C.c_int, [C.c_void_p, _f64p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_void_p, _u8p]),
     "nct_color_finish_upsample_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nct_guided_params_default": (None, [C.c_void_p]),
+    "nct_color_finish_guided": (C.c_int, [C.c_void_p, _f64p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _u8p]),
+    "nct_color_finish_guided_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_set_finish_guided": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nct_pair_upload": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int]),
     "nct_pair_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_pair_run_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -286,6 +290,24 @@ def _lut_params(size, lam):
         p.size = int(size)
     if lam is not None:
         p.lambda_ = float(lam)
+    return p
+
+
+class GuidedParams(C.Structure):
+    """struct nct_guided_params (include/nct.h)."""
+    _fields_ = [("sigma", C.c_double)]
+
+    @staticmethod
+    def default():
+        p = GuidedParams()
+        lib().nct_guided_params_default(C.byref(p))
+        return p
+
+
+def _guided_params(sigma):
+    p = GuidedParams.default()
+    if sigma is not None:
+        p.sigma = float(sigma)
     return p
 
 
@@ -678,6 +700,44 @@ class Context:
             self.synchronize()
             for p in blocks:
                 self.dev_free(p)
+
+    def color_finish_guided(self, ab_wls, lab_work, h, w, s_full, sigma=None, params=None):
+        """nct_color_finish_guided (SPEC §6.10): the upsampling finish with joint-bilateral weights; lab_work (h x w x 3): the 8-bit Lab image of the working-size source;
+        sigma None = the library's default"""
+        a = np.ascontiguousarray(ab_wls, np.float64).reshape(-1)
+        lw = np.ascontiguousarray(lab_work, np.uint8)
+        assert a.size == 6 * h * w and lw.size == 3 * h * w
+        s_full = np.ascontiguousarray(s_full, np.uint8)
+        H, W = s_full.shape[:2]
+        prm, gp = params or Params.default(), _guided_params(sigma)
+        out = np.empty((H, W, 3), np.uint8)
+        self._chk(self._l.nct_color_finish_guided(self._h, a, lw.reshape(-1, 3), h, w, s_full.reshape(-1, 3), H, W, C.addressof(gp), C.addressof(prm), out.reshape(-1, 3)))
+        return out
+
+    def color_finish_guided_dev(self, ab_wls, lab_work, h, w, s_full, sigma=None, params=None):
+        """the same through nct_color_finish_guided_dev on arena blocks"""
+        a = np.ascontiguousarray(ab_wls, np.float64).reshape(-1)
+        lw = np.ascontiguousarray(lab_work, np.uint8)
+        assert a.size == 6 * h * w and lw.size == 3 * h * w
+        s_full = np.ascontiguousarray(s_full, np.uint8)
+        H, W = s_full.shape[:2]
+        prm, gp = params or Params.default(), _guided_params(sigma)
+        blocks = [self.dev_upload(a), self.dev_upload(lw), self.dev_upload(s_full), self.dev_alloc(s_full.size)]
+        try:
+            self._chk(self._l.nct_color_finish_guided_dev(self._h, blocks[0], blocks[1], h, w, blocks[2], H, W, C.addressof(gp), C.addressof(prm), blocks[3]))
+            return self.dev_download(blocks[3], (H, W, 3), np.uint8)
+        finally:
+            self.synchronize()
+            for p in blocks:
+                self.dev_free(p)
+
+    def set_finish_guided(self, sigma):
+        """nct_set_finish_guided: a sigma turns the guided modifier of the upsampling finish on for this context, None turns it off (the default)"""
+        if sigma is None:
+            self._chk(self._l.nct_set_finish_guided(self._h, None))
+        else:
+            gp = _guided_params(sigma)
+            self._chk(self._l.nct_set_finish_guided(self._h, C.addressof(gp)))
 
     def color_finish(self, ab, h, w, work_h, work_w, s_full, params=None, want_stages=False):
         """nct_color_finish: U1 / roughness / S2 / A1 of ab ([2][h*w][3], S1's ab_nonlocal) onto s_full (H x W x 3 BGR) in a pyramid of working size work_h x work_w"""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The numbers of DESIGN.md §3.14 (the upsampling finish and full-resolution sequences). One JSON line per measurement. Needs a GPU.
+"""The numbers of DESIGN.md §3.14 (the upsampling finish and full-resolution sequences) and §3.15 (the guided finish). One JSON line per measurement. Needs a GPU.
 
     python scripts/finish_up_times.py kernels --mp 24      one source size (2, 8 or 24 MP, working size 666 x 1000): nct_color_finish_upsample_dev, wall time of
                                                            `reps` enqueued calls between two synchronisations, and the exact finish twice (its bgr2lab, resize_f64c3 x2,
@@ -12,6 +12,16 @@
                                                            sequence on the shrunk frames; WLS iterations of the last level and the arena
     python scripts/finish_up_times.py quality              the nine stand-in pairs, content image upscaled to a longer side of 2000: PSNR of the upsampling finish and of the
                                                            table of the working-size pair (-lut 33 -lutfull 1) against the exact finish; one five-frame pan: transform flicker
+    python scripts/finish_up_times.py guided-kernels --mp 24
+                                                           nct_color_finish_upsample_dev and nct_color_finish_guided_dev (sigma 10) on the same maps and source, wall time of
+                                                           `reps` enqueued calls each; under rocprofv3 as above the stats hold k_finish_up and k_finish_guided side by side
+    python scripts/finish_up_times.py guided-report DIR/k_kernel_stats.csv --mp 24
+                                                           the two kernels' average times, their ratio, Gpx/s
+    python scripts/finish_up_times.py guided-quality       the nine stand-in pairs as in `quality`: PSNR against the exact finish of the bilinear upsampling finish and of the
+                                                           guided one at sigma 5, 10 and 20
+    python scripts/finish_up_times.py guided-frames --mp 24
+                                                           one pair at that source size (max_side 1000): host wall time and color_ms (the colour stage, WLS included) of the upsampling finish, the guided one
+                                                           and the exact finish (median of three after a warm-up)
 """
 import argparse
 import csv
@@ -81,6 +91,95 @@ def report(args):
     total = sum(chain.values())
     print(json.dumps({"mp": args.mp, "chain_us": chain, "chain_total_us": round(total, 1), "k_finish_up_us": round(fu, 1), "speedup": round(total / fu, 2) if fu else None,
                       "k_finish_up_GBps_on_6B_per_px": round(6 * H * W / fu / 1e3, 1) if fu else None}))
+
+
+def guided_kernels(args):
+    import ctypes as C
+    import nct
+    import synth
+    from fullres_ref import smooth_ab
+    H, W = SIZES[args.mp]
+    h, w = nct.working_size(H, W, 1000)
+    ab = smooth_ab(7, h, w)
+    with nct.Context(0) as c:
+        src = c.resize_u8c3(synth.image(61, 600, 400), H, W)
+        lab_w = c.bgr2lab(c.resize_u8c3(src, h, w))
+        prm, gp = nct.Params.default(), nct.GuidedParams.default()
+        d_ab, d_lw, d_s, d_o = c.dev_upload(ab.reshape(-1)), c.dev_upload(lab_w), c.dev_upload(src), c.dev_alloc(3 * H * W)
+        calls = {"color_finish_upsample_dev": lambda: c._chk(c._l.nct_color_finish_upsample_dev(c._h, d_ab, h, w, d_s, H, W, C.addressof(prm), d_o)),
+                 "color_finish_guided_dev": lambda: c._chk(c._l.nct_color_finish_guided_dev(c._h, d_ab, d_lw, h, w, d_s, H, W, C.addressof(gp), C.addressof(prm), d_o))}
+        for name, call in calls.items():
+            call(); c.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.reps):
+                call()
+            c.synchronize()
+            us = (time.perf_counter() - t0) / args.reps * 1e6
+            print(json.dumps({"call": name, "mp": args.mp, "H": H, "W": W, "h": h, "w": w, "us_per_call": round(us, 1), "reps": args.reps,
+                              "Gpx_per_s": round(H * W / us / 1e3, 2)}), flush=True)
+        for p in (d_ab, d_lw, d_s, d_o):
+            c.dev_free(p)
+
+
+def guided_report(args):
+    H, W = SIZES[args.mp]
+    rows = {r["Name"]: r for r in csv.DictReader(open(args.csv))}
+    avg = lambda pat: [float(r["AverageNs"]) / 1e3 for n, r in rows.items() if re.search(r"\b" + pat + r"\b", n)]
+    fu, fg = avg("k_finish_up"), avg("k_finish_guided")
+    fu, fg = sum(fu) / max(len(fu), 1), sum(fg) / max(len(fg), 1)
+    print(json.dumps({"mp": args.mp, "k_finish_up_us": round(fu, 1), "k_finish_guided_us": round(fg, 1), "guided_over_bilinear": round(fg / fu, 2) if fu else None,
+                      "k_finish_guided_Gpx_per_s": round(H * W / fg / 1e3, 2) if fg else None}))
+
+
+def guided_quality(args):
+    import nct
+    import natural_inputs
+    from PIL import Image
+    from caffemodel_io import synthetic_vgg19
+    ws, bs = synthetic_vgg19(19)
+    d = natural_inputs.require()
+    ld = lambda n: np.ascontiguousarray(np.asarray(Image.open(os.path.join(d, n + ".png")).convert("RGB"))[..., ::-1])
+    cases = [("in0", "tar0", 2.0), ("in1", "tar1", 2.0), ("in2", "tar2", 2.0), ("in3", "tar3", 2.0)] + [("in4", "tar4", b) for b in (0.0, 1.0, 2.0, 4.0, 8.0)]
+    with nct.Context(0) as c:
+        c.vgg19_load_raw(ws, bs)
+        for s, r, bds in cases:
+            src, ref = ld(s), ld(r)
+            k = 2000.0 / max(src.shape[:2])
+            src0 = c.resize_u8c3(src, int(round(src.shape[0] * k)), int(round(src.shape[1] * k)))
+            prm = nct.Params.default(); prm.bds_weight = bds
+            exact = c.process_pair_fullres(src0, ref, 1000, prm)
+            row = {"pair": "%s/%s bds %g" % (s, r, bds), "source": "%dx%d" % src0.shape[1::-1],
+                   "psnr_bilinear_vs_exact": round(psnr(c.process_pair_fullres(src0, ref, 1000, prm, finish=nct.FINISH_UPSAMPLE), exact), 2)}
+            for sigma in (5.0, 10.0, 20.0):
+                c.set_finish_guided(sigma)
+                row["psnr_guided_sigma_%g_vs_exact" % sigma] = round(psnr(c.process_pair_fullres(src0, ref, 1000, prm, finish=nct.FINISH_UPSAMPLE), exact), 2)
+                c.set_finish_guided(None)
+            print(json.dumps(row), flush=True)
+
+
+def guided_frames(args):
+    import nct
+    import synth
+    from caffemodel_io import synthetic_vgg19
+    ws, bs = synthetic_vgg19(19)
+    H, W = SIZES[args.mp]
+    ref = synth.image(62, 800, 640)
+    prm = nct.Params.default()
+    prm.flags = nct.FLAG_LATENCY
+    with nct.Context(0) as c:
+        c.vgg19_load_raw(ws, bs)
+        src0 = c.resize_u8c3(synth.image(61, 600, 400), H, W)
+        for mode, finish, sigma in (("upsample", nct.FINISH_UPSAMPLE, None), ("guided", nct.FINISH_UPSAMPLE, 10.0), ("exact", nct.FINISH_EXACT, None)):
+            c.set_finish_guided(sigma)
+            ms, color = [], []
+            for t in range(4):
+                t0 = time.perf_counter()
+                _, tm = c.process_pair_fullres(src0, ref, 1000, prm, want_timing=True, finish=finish)
+                if t:
+                    ms.append((time.perf_counter() - t0) * 1e3); color.append(tm["color_ms"])
+            c.set_finish_guided(None)
+            print(json.dumps({"pair": "%dx%d" % (W, H), "mode": mode, "host_ms_median": round(float(np.median(ms)), 1), "host_ms_range": [round(min(ms), 1), round(max(ms), 1)],
+                              "color_ms_median": round(float(np.median(color)), 1), "wls_ms_last": round(tm["wls_ms"], 1)}), flush=True)
 
 
 def clip(c, H, W, n, step):
@@ -185,12 +284,13 @@ def quality(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=("kernels", "report", "frames", "quality"))
+    ap.add_argument("what", choices=("kernels", "report", "frames", "quality", "guided-kernels", "guided-report", "guided-quality", "guided-frames"))
     ap.add_argument("csv", nargs="?")
     ap.add_argument("--mp", type=int, default=24, choices=sorted(SIZES))
     ap.add_argument("--reps", type=int, default=20)
     args = ap.parse_args()
-    {"kernels": kernels, "report": report, "frames": frames, "quality": quality}[args.what](args)
+    {"kernels": kernels, "report": report, "frames": frames, "quality": quality, "guided-kernels": guided_kernels, "guided-report": guided_report,
+     "guided-quality": guided_quality, "guided-frames": guided_frames}[args.what](args)
 
 
 if __name__ == "__main__":
