@@ -362,16 +362,9 @@ int nctk_kmeans_labels(nct_ctx* ctx, hipStream_t s, const float* feat, int n, in
 }
 
 // ================================================================= K1: kNN graph
-#ifndef NCT_KNN_MAX_BLOCKS
-#define NCT_KNN_MAX_BLOCKS 1024
-#endif
-#ifndef NCT_KNN_LANES16_BELOW
-#define NCT_KNN_LANES16_BELOW 31000     // pixels: 44^2 .. 175^2 of a 700^2 pair search with sixteen lanes per entry (k_knn_grid16)
-#endif
-#ifndef NCT_KNN_RING_UNITS
-#define NCT_KNN_RING_UNITS 16
-#endif
-constexpr int KNN_RING_UNITS = NCT_KNN_RING_UNITS;   // Lab units of Chebyshev rings after which a search scans the rest of its cluster in one pass
+constexpr int KNN_MAX_BLOCKS = 1024;
+constexpr int KNN_LANES16_BELOW = 31000;   // pixels: 44^2 .. 175^2 of a 700^2 pair search with sixteen lanes per entry (k_knn_grid16)
+constexpr int KNN_RING_UNITS = 16;         // Lab units of Chebyshev rings after which a search scans the rest of its cluster in one pass
 constexpr int KNN_K = 8;          // Config.h:68 m_kNum
 constexpr int KNN_SLOTS = 5;      // a pixel belongs to its own cluster + at most 4 neighbouring ones
 
@@ -847,11 +840,11 @@ int nctk_knn_graph(nct_ctx* ctx, hipStream_t s, const uint8_t* lab_u8, int h, in
     const KnnOut ko{run_id, run_col, nslot, cand_d, cand_id};
     const int force = ctx->knn_runs;                        // -1: by the entries-per-run ratio, on the device; 0 / 1: NCT_KNN_RUNS (tests)
 #define NCT_KNN_LAUNCH(RUNS) do { \
-    if (n <= NCT_KNN_LANES16_BELOW) \
-        hipLaunchKernelGGL(k_knn_grid16<RUNS>, dim3(std::min(cdiv(cap, 16), 4 * NCT_KNN_MAX_BLOCKS)), dim3(256), 0, s, (const unsigned*)cols, count, (const int*)incl, (const int*)lead, \
+    if (n <= KNN_LANES16_BELOW) \
+        hipLaunchKernelGGL(k_knn_grid16<RUNS>, dim3(std::min(cdiv(cap, 16), 4 * KNN_MAX_BLOCKS)), dim3(256), 0, s, (const unsigned*)cols, count, (const int*)incl, (const int*)lead, \
                            (const unsigned*)keys_s, (const unsigned*)vals_s, (const int*)start, cs, force, ko); \
     else \
-        hipLaunchKernelGGL(k_knn_grid<RUNS>, dim3(std::min(cdiv(cap, 256), NCT_KNN_MAX_BLOCKS)), dim3(256), 0, s, (const unsigned*)cols, count, (const int*)incl, (const int*)lead, \
+        hipLaunchKernelGGL(k_knn_grid<RUNS>, dim3(std::min(cdiv(cap, 256), KNN_MAX_BLOCKS)), dim3(256), 0, s, (const unsigned*)cols, count, (const int*)incl, (const int*)lead, \
                            (const unsigned*)keys_s, (const unsigned*)vals_s, (const int*)start, cs, force, ko); \
     NCT_LAUNCH_CHECK(); } while (0)
     NCT_KNN_LAUNCH(false);

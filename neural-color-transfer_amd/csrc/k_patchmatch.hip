@@ -34,21 +34,9 @@
 
 // workgroups per CU (= waves per SIMD) the C = 64 kernels are compiled for. Round 2: five (92 registers) beat four, 16.0 vs 17.4 ms per pair, six (80, spills) 19.1 ms.
 // Round 3: with two patch rows per round trip (pm_dist8 STAGE 1: 109 registers) four waves beat five-with-one-row: 13.0 vs 14.6 ms (five with spills: 15.3); C = 128 at five: 10.4 vs 8.5 ms
-#ifndef NCT_PM_OCC8
-#define NCT_PM_OCC8 4
-#endif
-#ifndef NCT_PM_FAR_MAG
-#define NCT_PM_FAR_MAG 16       // random samples drawn with this radius or more are "far" (mostly rejected after their first row)
-#endif
-#ifndef NCT_PM_FAR_STAGE
-#define NCT_PM_FAR_STAGE 1
-#endif
-#ifndef NCT_PM_NEAR_STAGE
-#define NCT_PM_NEAR_STAGE 1
-#endif
-#ifndef NCT_PM_FAST_MAX
-#define NCT_PM_FAST_MAX 2
-#endif
+constexpr int PM_OCC8 = 4;
+// largest C / 64 with an fp32 interior fast path (pm_dist: for C >= 256 it measured slower)
+constexpr int PM_FAST_MAX = 2;
 struct PMGeom { int C, ah, aw, bh, bw, tiles_x, tiles_y; };
 
 __device__ __forceinline__ float dot4h_acc(const float4 a, const uint2 bh, float acc) {
@@ -88,13 +76,13 @@ __global__ void k_pm_interleave64(const float4* __restrict__ src, float4* __rest
 }
 // B, a_lds: interleaved layout; l = lane of the query's 8-lane group. Same contract as pm_dist below.
 // STAGE: how the three patch rows of an interior candidate are fetched. The level is bound by the latency of DEPENDENT fetches (row -> partial sum -> test -> next row), so:
-//   0  one row at a time, rejection test after each of the first two (three round trips for a survivor);
-//   1  the first row alone (most far random samples stop here), then the other two TOGETHER (two round trips);
-//   2  the whole tile at once (one round trip): for candidates that are rarely rejected early — propagated matches and near random samples (radius < NCT_PM_FAR_MAG).
-// The fmaf chains run in the same order in every form, and an early return only ever replaces a value that could not win: same bits.
+//   0  one row at a time, rejection test after each of the first two (three round trips for a survivor): the init step and k_pm_prop;
+//   1  the first row alone (most far random samples stop here), then the other two TOGETHER (two round trips): k_pm_step.
+// The fmaf chains run in the same order in both forms, and an early return only ever replaces a value that could not win: same bits.
 template <int MODE, int RW, int STAGE = 0>
 __device__ __forceinline__ float pm_dist8(const float* __restrict__ B, const PMGeom& g, int ax, int ay, unsigned amask, int bx, int by, int l,
                                           const float4* __restrict__ a_lds, int lx, int ly, float need) {
+    static_assert(STAGE == 0 || STAGE == 1, "pm_dist8 fetches a row at a time (0) or the first row, then the other two (1)");
     constexpr bool EX = MODE == NCT_PM_ROWREJECT;
     constexpr int C4 = 16;
     const bool inside = amask == 0x1FFu && bx >= 1 && bx < g.bw - 1 && by >= 1 && by < g.bh - 1;
@@ -116,24 +104,15 @@ __device__ __forceinline__ float pm_dist8(const float* __restrict__ B, const PMG
             }
         } else {
             float4 t[3][3][2];                                 // [row][dx][half of the pixel record]
-            if constexpr (STAGE == 2) {
 #pragma unroll
-                for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-                    for (int dx = -1; dx <= 1; ++dx) { t[dy + 1][dx + 1][0] = pbc[(dy * g.bw + dx) * C4]; t[dy + 1][dx + 1][1] = pbc[(dy * g.bw + dx) * C4 + 8]; }
-            } else {
-#pragma unroll
-                for (int dx = -1; dx <= 1; ++dx) { t[0][dx + 1][0] = pbc[(-g.bw + dx) * C4]; t[0][dx + 1][1] = pbc[(-g.bw + dx) * C4 + 8]; }
-            }
+            for (int dx = -1; dx <= 1; ++dx) { t[0][dx + 1][0] = pbc[(-g.bw + dx) * C4]; t[0][dx + 1][1] = pbc[(-g.bw + dx) * C4 + 8]; }
 #pragma unroll
             for (int dx = -1; dx <= 1; ++dx) acc = pk_dot4_acc(pac[(-RW + dx) * C4], pac[(-RW + dx) * C4 + 8], t[0][dx + 1][0], t[0][dx + 1][1], acc);
-            if constexpr (STAGE == 1) {
-                if (need > -FLT_MAX && half8_sum(acc.x, acc.y) + 6.0007f < need) return FLT_MAX;
+            if (need > -FLT_MAX && half8_sum(acc.x, acc.y) + 6.0007f < need) return FLT_MAX;
 #pragma unroll
-                for (int dy = 0; dy <= 1; ++dy)
+            for (int dy = 0; dy <= 1; ++dy)
 #pragma unroll
-                    for (int dx = -1; dx <= 1; ++dx) { t[dy + 1][dx + 1][0] = pbc[(dy * g.bw + dx) * C4]; t[dy + 1][dx + 1][1] = pbc[(dy * g.bw + dx) * C4 + 8]; }
-            }
+                for (int dx = -1; dx <= 1; ++dx) { t[dy + 1][dx + 1][0] = pbc[(dy * g.bw + dx) * C4]; t[dy + 1][dx + 1][1] = pbc[(dy * g.bw + dx) * C4 + 8]; }
 #pragma unroll
             for (int dy = 0; dy <= 1; ++dy)
 #pragma unroll
@@ -190,7 +169,7 @@ __device__ __forceinline__ float pm_dist(const float* __restrict__ A, const floa
     // issue slots; for C >= 256 the fast path measured slower (the LDS-staged 36-73 KB query regions already limit occupancy), so
     // those instantiations keep the general loop.
     static_assert(NCH != 1, "C = 64 has its own 8-lane forms (pm_dist8, pm_dist8h)");
-    if constexpr (NCH >= 1 && (HALF || NCH <= NCT_PM_FAST_MAX)) {
+    if constexpr (NCH >= 1 && (HALF || NCH <= PM_FAST_MAX)) {
         const bool inside = amask == 0x1FFu && bx >= 1 && bx < g.bw - 1 && by >= 1 && by < g.bh - 1;
         if (__builtin_amdgcn_ballot_w64(inside) == __builtin_amdgcn_ballot_w64(true)) {
             constexpr int C4 = 16 * NCH;
@@ -362,6 +341,10 @@ __device__ __forceinline__ void pm_stage_region(const float* __restrict__ A, con
     }
 }
 
+// propagation candidate k comes from the neighbour at this offset: 0 left, 1 right, 2 up, 3 down, `jump` pixels away
+__device__ __forceinline__ int pm_nb_dx(int k, int jump) { return (k == 0) ? -jump : (k == 1 ? jump : 0); }
+__device__ __forceinline__ int pm_nb_dy(int k, int jump) { return (k == 2) ? -jump : (k == 3 ? jump : 0); }
+
 template <int NCH, int MODE, int TQX, int TQY, int LPQ>
 __device__ __forceinline__ void pm_step_tile(const PMJob& J, int tx, int ty, int mode, int jump, int iter, int tstep, int strip, float4* __restrict__ s_a, unsigned& nevals, unsigned& naccept) {
     constexpr int RW = 4 * TQX + 2, RH = 4 * TQY + 2;
@@ -390,7 +373,7 @@ __device__ __forceinline__ void pm_step_tile(const PMJob& J, int tx, int ty, int
             q.d = d_in[qi];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const int nx = ax + ((k == 0) ? -jump : (k == 1 ? jump : 0)), ny = ay + ((k == 2) ? -jump : (k == 3 ? jump : 0));
+                const int nx = ax + pm_nb_dx(k, jump), ny = ay + pm_nb_dy(k, jump);
                 q.vnb[k] = *(nnf_in + clampi(ny, 0, g.ah - 1) * g.aw + clampi(nx, 0, g.aw - 1));
             }
         }
@@ -460,20 +443,17 @@ __device__ __forceinline__ void pm_step_tile(const PMJob& J, int tx, int ty, int
             uint32_t cl0 = 0, cl1 = 0, cl2 = 0, cl3 = 0; int ncl = 0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const int sxx = (k == 0) ? -jump : (k == 1 ? jump : 0);
-                const int syy = (k == 2) ? -jump : (k == 3 ? jump : 0);
+                const int sxx = pm_nb_dx(k, jump), syy = pm_nb_dy(k, jump);
                 const int nx = ax + sxx, ny = ay + syy;
                 const uint32_t vp = vnb[k];
                 const int xp = nnf_x(vp) - sxx, yp = nnf_y(vp) - syy;
                 bool valid = nx >= 0 && nx < g.aw && ny >= 0 && ny < g.ah && yp >= 0 && yp < g.bh && xp >= 0 && xp < g.bw;
-#ifndef NCT_PM_EVAL_STALE
                 // A neighbour whose match has not changed since the step of the PREVIOUS iteration with this jump (four steps ago) proposes the candidate that
                 // was evaluated then and lost (or won and has been the best, or been beaten, since): the query's best only ever decreases, so d >= dbest
                 // again — it cannot win and is not fetched. Exact: same NNF, same distances (the oracle evaluates everything). The step a match last
                 // changed in travels in the top byte of its (double-buffered) NNF word, so the test costs no load. As the field converges — 70-95 % of the
                 // matches are unchanged from iteration 3 on — most propagation candidates drop out; the random search is always fresh.
                 valid = valid && !(tstep > 4 && (int)(vp >> 24) < tstep - 4);
-#endif
                 if (valid) {
                     const uint32_t c = xy_pack(xp, yp);
                     cl0 = ncl == 0 ? c : cl0; cl1 = ncl == 1 ? c : cl1; cl2 = ncl == 2 ? c : cl2; cl3 = ncl == 3 ? c : cl3;
@@ -486,16 +466,14 @@ __device__ __forceinline__ void pm_step_tile(const PMJob& J, int tx, int ty, int
             int mag = rs_start;
             const int ncand = nprop + nrand;
             for (int k = 0; k < ncand; ++k) {
-                int xp, yp; bool valid; float rr; bool far = false;
+                int xp, yp; bool valid; float rr;
                 if (k < nprop) {
                     const uint32_t c = k == 0 ? cl0 : (k == 1 ? cl1 : (k == 2 ? cl2 : cl3));
                     xp = nnf_x(c); yp = nnf_y(c);
                     valid = k < ncl;
-#ifndef NCT_PM_EVAL_SAME
                     // a neighbour that proposes the current match cannot improve it (d == dbest is not < dbest): its lanes sit the evaluation out
                     // (with the wave near the L1 bandwidth limit the unissued tile requests are what is saved, not instructions)
                     valid = valid && !(xp == xbest && yp == ybest);
-#endif
                     rr = 0.f;
                 } else {
                     const int step = k - nprop;
@@ -507,19 +485,13 @@ __device__ __forceinline__ void pm_step_tile(const PMJob& J, int tx, int ty, int
                     const int rx = (int)(rand_u01(seed, ax, ay, iter, step, 0) * (float)wx), ry = (int)(rand_u01(seed, ax, ay, iter, step, 1) * (float)wy);
                     xp = xmin + (rx == wx ? 0 : rx);
                     yp = ymin + (ry == wy ? 0 : ry);
-                    far = mag >= NCT_PM_FAR_MAG;
                     mag >>= 1;
                     valid = true; rr = FLT_MIN;
                 }
                 if (valid) {
                     // to win, -sum/9 (+rr) < dbest, i.e. sum > -9 dbest: unreachable sums are cut off (unit-norm features only)
                     float d;
-                    if constexpr (LPQ == 8) {
-                        // (wave-uniform branch: the search radius is the same for every query of a step)
-                        if constexpr (NCT_PM_FAR_STAGE == NCT_PM_NEAR_STAGE) d = pm_dist8<MODE, RW, NCT_PM_FAR_STAGE>(B, g, ax, ay, amask, xp, yp, v, s_a, lx, ly, EX ? -9.0f * dbest : -FLT_MAX);   // one inlined copy, not two
-                        else if (far) d = pm_dist8<MODE, RW, NCT_PM_FAR_STAGE>(B, g, ax, ay, amask, xp, yp, v, s_a, lx, ly, EX ? -9.0f * dbest : -FLT_MAX);
-                        else d = pm_dist8<MODE, RW, NCT_PM_NEAR_STAGE>(B, g, ax, ay, amask, xp, yp, v, s_a, lx, ly, EX ? -9.0f * dbest : -FLT_MAX);
-                    }
+                    if constexpr (LPQ == 8) d = pm_dist8<MODE, RW, 1>(B, g, ax, ay, amask, xp, yp, v, s_a, lx, ly, EX ? -9.0f * dbest : -FLT_MAX);
                     else d = pm_dist<NCH, MODE, RW>(A, B, Bh, g, ax, ay, amask, xp, yp, v, s_a, lx, ly, EX ? -9.0f * dbest : -FLT_MAX);
                     if (d >= dbest) d = dbest;                       // cutoff clamp of dist_compute_single
                     if (d + rr < dbest) { xbest = xp; ybest = yp; dbest = d; if (live && v == 0) ++naccept; }
@@ -557,7 +529,7 @@ __device__ __forceinline__ void pm_count(unsigned long long* __restrict__ counte
 }
 
 template <int NCH, int MODE, int TQX, int TQY, int LPQ>
-__global__ __launch_bounds__(256, NCH == 8 ? 2 : (LPQ == 8 ? NCT_PM_OCC8 : 1)) void k_pm_step(PMJob j0, PMJob j1, int nblk0, int mode, int jump, int iter,
+__global__ __launch_bounds__(256, NCH == 8 ? 2 : (LPQ == 8 ? PM_OCC8 : 1)) void k_pm_step(PMJob j0, PMJob j1, int nblk0, int mode, int jump, int iter,
                                                  int tstep, int strip, unsigned long long* __restrict__ counter) {
     const bool second = (int)blockIdx.x >= nblk0;
     const PMJob& J = second ? j1 : j0;
@@ -576,13 +548,9 @@ __global__ __launch_bounds__(256, NCH == 8 ? 2 : (LPQ == 8 ? NCT_PM_OCC8 : 1)) v
 // to, and finally each query scans ITS results in candidate order with the reference's accept rule (d < dbest, first wins). A propagation candidate's distance does not depend
 // on the other candidates of its query — only the early-rejection threshold did, and the initial dbest is a valid (weaker) threshold — so NNF and distances are the same bits.
 // Rounds per wave: ceil(live candidates / 8) instead of sum over the passes of the longest list.
-#ifndef NCT_PM_PACK
-#define NCT_PM_PACK 3        // 0: off, 1: C = 64 only, 2: C = 64 and 128, 3: every level (C >= 256: one pass, the four queries of a wave share its lane groups)
-#endif
-#ifndef NCT_PM_PROP_OCC
-#define NCT_PM_PROP_OCC NCT_PM_OCC8        // workgroups per CU the packed kernel is compiled for, and how it fetches a candidate's rows (pm_dist8 STAGE): one row at a time
-#define NCT_PM_PROP_STAGE 0                // measured 11.41 ms for the finest level of a 700x700 pair vs 12.17 (first row, then two together) / 12.18 (whole tile); five workgroups per CU 11.53, six 13.5
-#endif
+// It serves every level with fp32 tiles (C >= 256: one pass, the four queries of a wave share its lane groups).
+constexpr int PM_PROP_OCC = PM_OCC8;       // workgroups per CU the packed kernel is compiled for, and how it fetches a candidate's rows (pm_dist8 STAGE): one row at a time
+constexpr int PM_PROP_STAGE = 0;           // measured 11.41 ms for the finest level of a 700x700 pair vs 12.17 (first row, then two together) / 12.18 (whole tile); five workgroups per CU 11.53, six 13.5
 template <int NCH, int MODE, int TQX, int TQY, int LPQ>
 __device__ __forceinline__ void pm_prop_tile(const PMJob& J, int tx, int ty, int jump, int tstep, int strip, float4* __restrict__ s_a, unsigned& nevals, unsigned& naccept) {
     constexpr int RW = 4 * TQX + 2, RH = 4 * TQY + 2, QW = LPQ == 16 ? 4 : 8, QH = 256 / LPQ / QW, NSX = 4 * TQX / QW, NSUB = NSX * (4 * TQY / QH);
@@ -610,7 +578,7 @@ __device__ __forceinline__ void pm_prop_tile(const PMJob& J, int tx, int ty, int
         vbest[sub] = nnf_in[qi[sub]]; dq[sub] = d_in[qi[sub]];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int nx = ax + ((k == 0) ? -jump : (k == 1 ? jump : 0)), ny = ay + ((k == 2) ? -jump : (k == 3 ? jump : 0));
+            const int nx = ax + pm_nb_dx(k, jump), ny = ay + pm_nb_dy(k, jump);
             vnb[sub][k] = *(nnf_in + clampi(ny, 0, g.ah - 1) * g.aw + clampi(nx, 0, g.aw - 1));
         }
     }
@@ -626,7 +594,7 @@ __device__ __forceinline__ void pm_prop_tile(const PMJob& J, int tx, int ty, int
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             cl[sub][k] = 0;
-            const int sxx = (k == 0) ? -jump : (k == 1 ? jump : 0), syy = (k == 2) ? -jump : (k == 3 ? jump : 0);
+            const int sxx = pm_nb_dx(k, jump), syy = pm_nb_dy(k, jump);
             const int nx = ax + sxx, ny = ay + syy;
             const uint32_t vp = vnb[sub][k];
             const int xp = nnf_x(vp) - sxx, yp = nnf_y(vp) - syy;
@@ -670,7 +638,7 @@ __device__ __forceinline__ void pm_prop_tile(const PMJob& J, int tx, int ty, int
             const unsigned amask = q.y >> 16;
             const float dbest = __uint_as_float(q.z);
             float d;
-            if constexpr (LPQ == 8) d = pm_dist8<MODE, RW, NCT_PM_PROP_STAGE>(B, g, ax, ay, amask, nnf_x(ent & 0xFFFFFFu), nnf_y(ent & 0xFFFFFFu), v, s_a, lx, ly, EX ? -9.0f * dbest : -FLT_MAX);
+            if constexpr (LPQ == 8) d = pm_dist8<MODE, RW, PM_PROP_STAGE>(B, g, ax, ay, amask, nnf_x(ent & 0xFFFFFFu), nnf_y(ent & 0xFFFFFFu), v, s_a, lx, ly, EX ? -9.0f * dbest : -FLT_MAX);
             else d = pm_dist<NCH, MODE, RW>(A, B, Bh, g, ax, ay, amask, nnf_x(ent & 0xFFFFFFu), nnf_y(ent & 0xFFFFFFu), v, s_a, lx, ly, EX ? -9.0f * dbest : -FLT_MAX);
             if (v == 0) s_res[wv][slot * 4 + k] = d;
         }
@@ -698,7 +666,7 @@ __device__ __forceinline__ void pm_prop_tile(const PMJob& J, int tx, int ty, int
 }
 
 template <int NCH, int MODE, int TQX, int TQY, int LPQ>
-__global__ __launch_bounds__(256, LPQ == 8 ? NCT_PM_PROP_OCC : (NCH == 8 ? 2 : 1)) void k_pm_prop(PMJob j0, PMJob j1, int nblk0, int jump, int tstep, int strip, unsigned long long* __restrict__ counter) {
+__global__ __launch_bounds__(256, LPQ == 8 ? PM_PROP_OCC : (NCH == 8 ? 2 : 1)) void k_pm_prop(PMJob j0, PMJob j1, int nblk0, int jump, int tstep, int strip, unsigned long long* __restrict__ counter) {
     const bool second = (int)blockIdx.x >= nblk0;
     const PMJob& J = second ? j1 : j0;
     const int bid = pm_xcd_tile((int)blockIdx.x - (second ? nblk0 : 0), J.g.tiles_x * J.g.tiles_y);
@@ -709,38 +677,34 @@ __global__ __launch_bounds__(256, LPQ == 8 ? NCT_PM_PROP_OCC : (NCH == 8 ? 2 : 1
     pm_count(counter, (int)(threadIdx.x % LPQ), nevals, naccept);
 }
 
-// query tile of a workgroup per channel count: 8x8 at C = 64 (25 KB of LDS), 8x4 at C = 128 (31 KB), 4x4 above (37 / 74 KB)
-template <int NCH> struct PMTile { static constexpr int TQX = NCH == 1 ? 2 : (NCH == 2 ? 2 : 1), TQY = NCH == 1 ? 2 : 1; };
+// query tile of a workgroup (in 4x4 sub-tiles) per nch = C / 64, 0 = any other C: 8x8 at C = 64 (25 KB of LDS), 8x4 at C = 128 (31 KB), 4x4 above (37 / 74 KB)
+struct PMTile { int tqx, tqy; };
+constexpr PMTile pm_tile(int nch) { return {nch == 1 || nch == 2 ? 2 : 1, nch == 1 ? 2 : 1}; }
 // lanes per query: 8 at C = 64 (pm_dist8), else 16. Measured alternatives (two unpacked chains per lane): C = 128 with 8 lanes
 // 10.7 vs 8.6 ms, C = 64 with 4 lanes 22.0 vs 17.6 ms per pair and level.
 template <int NCH> struct PMLanes { static constexpr int LPQ = NCH == 1 ? 8 : 16; };
+// More than 32 KB of dynamic LDS (the staged query region: 36 KB at C = 256, 72 KB at C = 512) needs the opt-in attribute on this device: set once per context
+// (= per device) and kernel instantiation, remembered in the instantiation's bit of ctx->pm_attr_mask.
+static int pm_lds_opt_in(nct_ctx* ctx, const void* kernel, unsigned bit, size_t lds) {
+    if (lds > 32768 && !(ctx->pm_attr_mask & bit)) {
+        NCT_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ctx->pm_attr_mask |= bit;
+    }
+    return 0;
+}
+
 template <int NCH, int MODE>
 static int launch_mode(nct_ctx* ctx, hipStream_t s, const PMJob& j0, const PMJob& j1, int nblk0, int nblk1, int mode, int jump, int iter, int tstep, int strip, unsigned long long* counter) {
-    constexpr int TQX = PMTile<NCH>::TQX, TQY = PMTile<NCH>::TQY, LPQ = PMLanes<NCH>::LPQ;
+    constexpr int TQX = pm_tile(NCH).tqx, TQY = pm_tile(NCH).tqy, LPQ = PMLanes<NCH>::LPQ;
     const size_t lds = NCH >= 1 ? (size_t)(4 * TQX + 2) * (4 * TQY + 2) * NCH * 16 * sizeof(float4) : 0;      // region pixels x C/4 float4
-    // > 64 KB of dynamic LDS (C=512: 72 KB for the staged query region) needs the opt-in attribute on this device: set once per context (= per device) and instantiation
-    constexpr unsigned abit = 1u << ((NCH > 8 ? 9 : NCH) * 3 + MODE);
-    if (lds > 32768 && !(ctx->pm_attr_mask & abit)) {
-        NCT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pm_step<NCH, MODE, TQX, TQY, LPQ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ctx->pm_attr_mask |= abit;
-    }
-    // k_pm_prop hard-codes the two exact skip rules (stale candidates, candidates equal to the current match); the checking builds that evaluate them anyway
-    // (-DNCT_PM_EVAL_STALE / -DNCT_PM_EVAL_SAME) therefore take k_pm_step for every step, which honours the macros. Its eval counters also differ in meaning:
-    // k_pm_prop filters against the query's INITIAL match of the step, so a candidate proposed by two neighbours is evaluated and counted twice (+0.08 % evaluations).
-#if defined(NCT_PM_EVAL_STALE) || defined(NCT_PM_EVAL_SAME)
-    constexpr bool packed_ok = false;
-#else
-    constexpr bool packed_ok = true;
-#endif
-    if constexpr (packed_ok && (NCH == 1 || (NCH == 2 && NCT_PM_PACK >= 2) || (NCH >= 4 && NCT_PM_PACK >= 3)) && MODE != NCT_PM_FP16 && NCT_PM_PACK != 0) {
-        if (mode == 1 && jump != 1) {              // propagation-only step: the packed form (its dynamic LDS is the same staged region)
-            if constexpr (NCH >= 4) {                  // > 32 KB of dynamic LDS: the same opt-in as k_pm_step, once per context and instantiation (bits 27..30 of the mask)
-                constexpr unsigned pbit = 1u << (27 + (NCH == 8 ? 2 : 0) + (MODE == NCT_PM_ROWREJECT ? 1 : 0));
-                if (!(ctx->pm_attr_mask & pbit)) {
-                    NCT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pm_prop<NCH, MODE, TQX, TQY, LPQ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    ctx->pm_attr_mask |= pbit;
-                }
-            }
+    // mask bits: k_pm_step 0..26 by (C / 64, MODE), k_pm_prop 27..30
+    NCT_TRY(pm_lds_opt_in(ctx, reinterpret_cast<const void*>(&k_pm_step<NCH, MODE, TQX, TQY, LPQ>), 1u << ((NCH > 8 ? 9 : NCH) * 3 + MODE), lds));
+    // The packed form serves the propagation-only steps of every staged level with fp32 tiles (its dynamic LDS is the same staged region). It applies the same two exact
+    // skip rules as k_pm_step, but its eval counter differs in meaning: k_pm_prop filters against the query's INITIAL match of the step, so a candidate proposed by two
+    // neighbours is evaluated and counted twice (+0.08 % evaluations).
+    if constexpr (NCH >= 1 && MODE != NCT_PM_FP16) {
+        if (mode == 1 && jump != 1) {
+            NCT_TRY(pm_lds_opt_in(ctx, reinterpret_cast<const void*>(&k_pm_prop<NCH, MODE, TQX, TQY, LPQ>), 1u << (27 + (NCH == 8 ? 2 : 0) + (MODE == NCT_PM_ROWREJECT ? 1 : 0)), lds));
             hipLaunchKernelGGL((k_pm_prop<NCH, MODE, TQX, TQY, LPQ>), dim3(nblk0 + nblk1), dim3(256), lds, s, j0, j1, nblk0, jump, tstep, strip, counter);
             NCT_LAUNCH_CHECK();
             return 0;
@@ -758,7 +722,7 @@ static int launch_step(nct_ctx* ctx, hipStream_t s, const PMJob& j0, const PMJob
     if constexpr (NCH >= 2) { if (pm_mode == NCT_PM_FP16) return launch_mode<NCH, NCT_PM_FP16>(ctx, s, j0, j1, nblk0, nblk1, mode, jump, iter, tstep, strip, counter); }
     if (NCH == 1 && pm_mode == NCT_PM_FP16) pm_mode = NCT_PM_PLAIN;
     // unit-norm features (the pipeline): the instantiation with the exact early rejection; it exists for the C with an fp32 interior fast path
-    if (NCH >= 1 && NCH <= NCT_PM_FAST_MAX && pm_mode == NCT_PM_ROWREJECT) return launch_mode<NCH, NCT_PM_ROWREJECT>(ctx, s, j0, j1, nblk0, nblk1, mode, jump, iter, tstep, strip, counter);
+    if (NCH >= 1 && NCH <= PM_FAST_MAX && pm_mode == NCT_PM_ROWREJECT) return launch_mode<NCH, NCT_PM_ROWREJECT>(ctx, s, j0, j1, nblk0, nblk1, mode, jump, iter, tstep, strip, counter);
     return launch_mode<NCH, NCT_PM_PLAIN>(ctx, s, j0, j1, nblk0, nblk1, mode, jump, iter, tstep, strip, counter);
 }
 
@@ -788,7 +752,8 @@ static int pm_run(nct_ctx* ctx, hipStream_t s, const float* a_hwc, const float* 
     DevBuf<uint32_t> a_tmp(ctx, na), b_tmp(ctx, two ? nb : 1);
     DevBuf<float> ad_tmp(ctx, na), bd_tmp(ctx, two ? nb : 1);
     if (!a_tmp.ok() || !b_tmp.ok() || !ad_tmp.ok() || !bd_tmp.ok()) return NCT_ERR_HIP;
-    const int tqx = C == 64 ? PMTile<1>::TQX : (C == 128 ? PMTile<2>::TQX : 1), tqy = C == 64 ? PMTile<1>::TQY : (C == 128 ? PMTile<2>::TQY : 1);
+    const int nch = (C == 64 || C == 128 || C == 256 || C == 512) ? C / 64 : 0;        // the instantiation `step` launches
+    const int tqx = pm_tile(nch).tqx, tqy = pm_tile(nch).tqy;
     const PMGeom ga{C, ah, aw, bh, bw, cdiv(aw, 4 * tqx), cdiv(ah, 4 * tqy)}, gb{C, bh, bw, ah, aw, cdiv(bw, 4 * tqx), cdiv(bh, 4 * tqy)};
     const int nblk0 = ga.tiles_x * ga.tiles_y, nblk1 = two ? gb.tiles_x * gb.tiles_y : 0;
     uint32_t* na_buf[2] = {ann, a_tmp}; float* da_buf[2] = {annd, ad_tmp};
@@ -799,11 +764,11 @@ static int pm_run(nct_ctx* ctx, hipStream_t s, const float* a_hwc, const float* 
     auto step = [&](int in, int out, int mode, int jump, int iter, int tstep, int strip) -> int {
         PMJob j0{a_hwc, b_hwc, (const uint2*)b_h16, na_buf[in], da_buf[in], mode ? na_buf[out] : nullptr, da_buf[out], ga, rs_max, seed_ab};
         PMJob j1{b_hwc, a_hwc, (const uint2*)a_h16, nb_buf[in], db_buf[in], mode ? nb_buf[out] : nullptr, db_buf[out], gb, rs_max, seed_ba};
-        switch (C) {
-            case 64:  return launch_step<1>(ctx, s, j0, j1, nblk0, nblk1, mode, jump, iter, tstep, strip, eval_counter, pm_mode);
-            case 128: return launch_step<2>(ctx, s, j0, j1, nblk0, nblk1, mode, jump, iter, tstep, strip, eval_counter, pm_mode);
-            case 256: return launch_step<4>(ctx, s, j0, j1, nblk0, nblk1, mode, jump, iter, tstep, strip, eval_counter, pm_mode);
-            case 512: return launch_step<8>(ctx, s, j0, j1, nblk0, nblk1, mode, jump, iter, tstep, strip, eval_counter, pm_mode);
+        switch (nch) {
+            case 1:  return launch_step<1>(ctx, s, j0, j1, nblk0, nblk1, mode, jump, iter, tstep, strip, eval_counter, pm_mode);
+            case 2:  return launch_step<2>(ctx, s, j0, j1, nblk0, nblk1, mode, jump, iter, tstep, strip, eval_counter, pm_mode);
+            case 4:  return launch_step<4>(ctx, s, j0, j1, nblk0, nblk1, mode, jump, iter, tstep, strip, eval_counter, pm_mode);
+            case 8:  return launch_step<8>(ctx, s, j0, j1, nblk0, nblk1, mode, jump, iter, tstep, strip, eval_counter, pm_mode);
             default:  return launch_step<0>(ctx, s, j0, j1, nblk0, nblk1, mode, jump, iter, tstep, strip, eval_counter, pm_mode == NCT_PM_FP16 ? NCT_PM_PLAIN : pm_mode);
         }
     };

@@ -25,7 +25,6 @@
 #include "nct_internal.h"
 #include "nct_device.h"
 #include "nct_reduce.h"
-#include <cstdlib>
 #include <rocprim/device/device_radix_sort.hpp>   // rocPRIM directly (no CUB-compatibility layer)
 #include <rocprim/device/device_scan.hpp>
 
@@ -40,7 +39,7 @@ struct S1Sys {
     const double *gx, *gy;                  // [n]
     const int* knn_id;                      // [n][8]
     nct_s1_graph g;                         // iw2, compact in-edge arrays, hub block table
-    int xcd;                                // workgroups of one XCD take a contiguous range of pixel blocks (the shared-gather levels; NCT_S1_XCD=0: plain order)
+    int xcd;                                // workgroups of one XCD take a contiguous range of pixel blocks (the shared-gather levels; 0: plain order)
     int one_xcd;                            // small levels: 1 + h = the launch is 8 x the grid and only the workgroups that land on XCD h work (s1_one_xcd below); 0: off
 };
 // Small levels (<= 32 workgroups: 44 x 44 and 88 x 88 of a 700 x 700 pair) are pure latency chains — own record -> neighbour ids -> gathers -> in-edge ids -> gathers —
@@ -244,10 +243,7 @@ __global__ __launch_bounds__(256) void k_s1_hub2(nct_s1_graph G) {
 // The in-degree is mild on the synthetic pairs (mean 8, p99 19, max 37) but an in-edge is a dependent random 48-byte gather, so at the bandwidth-bound levels
 // (COOP) the gathers are shared: the first-block in-edges of a workgroup's 256 consecutive pixels are ONE contiguous range of the compact arrays; the threads
 // fetch it edge-parallel into LDS in chunks of S1_CHUNK edges, then every thread adds ITS edges from LDS in edge order — same per-pixel order, same bits.
-#ifndef NCT_S1_CHUNK
-#define NCT_S1_CHUNK 1024
-#endif
-constexpr int S1_CHUNK = NCT_S1_CHUNK;
+constexpr int S1_CHUNK = 1024;
 template <bool COOP>
 __device__ __forceinline__ void s1_op(const S1Sys& S, const double* __restrict__ p, int i, bool live, double (&a)[3], double (&b)[3], double (&ya)[3], double (&yb)[3], int lb = -1) {
     const int w = S.w, h = S.h;
@@ -496,11 +492,10 @@ int nctk_s1_solve(nct_ctx* ctx, hipStream_t s, const nct_s1_graph& g, const int*
     // block's pixels and the block's own records are in ITS L2 (round 4 measured no gain on the two-pass recurrence's operator; on this one: 9.8 -> 9.3-9.5 ms for the
     // finest level of the bench pair, same bits — the partial sums keep their logical block slot). A cluster-major pixel order on top of it (scripts/s1_cluster_probe.py)
     // LOSES: only 41 % of the bench pair's kNN edges stay inside the pixel's own k-means cluster.
-    static const int s1_xcd = [] { const char* e = getenv("NCT_S1_XCD"); return e ? atoi(e) : 1; }();
-    static const int s1_one_max = [] { const char* e = getenv("NCT_S1_ONE_XCD_MAX"); return e ? atoi(e) : 32; }();    // largest grid (workgroups) that runs on one XCD; 0: off
-    const int one_xcd = (nbl <= s1_one_max && nbl <= S1_FUSE_NB) ? 1 + (ctx->home_xcd & 7) : 0;
+    constexpr int one_xcd_max = 32;                                 // largest grid (workgroups) that runs on one XCD
+    const int one_xcd = (nbl <= one_xcd_max && nbl <= S1_FUSE_NB) ? 1 + (ctx->home_xcd & 7) : 0;
     const int ogrid = one_xcd ? nbl * 8 : nbl;
-    S1Sys S{n, h, w, daa, dab, dbb, gx, gy, knn_id, g, (s1_xcd && n >= 100000) ? 1 : 0, one_xcd};
+    S1Sys S{n, h, w, daa, dab, dbb, gx, gy, knn_id, g, n >= 100000 ? 1 : 0, one_xcd};
     const double tol2 = 1e-6 * 1e-6;
     const int maxit = ctx->s1_maxit > 0 ? ctx->s1_maxit : (layer == 4 ? 50 : 100);    // ColorTransfer.cpp:916-921 (NCT_S1_MAXIT: test hook)
     const bool coop = n >= 100000;                                  // shared in-edge gathers pay off on the bandwidth-bound levels only

@@ -37,9 +37,7 @@ __global__ void k_vgg_preprocess(const uint8_t* __restrict__ bgr, int stride, fl
 // and 64 couts, a workgroup = 4 waves = WCO along cout x (4/WCO) along pixels. 1-D tiling wastes no lanes on ragged 2-D tile edges: conv4_x at 88x88 needs
 // 61 x 4 = 244 workgroups (one per CU, one round) where 16x8 tiles needed 264 — 8 CUs with two workgroups doubled the layer time.
 struct ConvGeom { int Cin, Cout, H, W, npx_blocks, nblk_n, tiles_x, Ho, Wo; };   // tiles_x, Ho, Wo: fused 2x2 pooling only
-#ifndef NCT_CONV_PT1_BELOW
-#define NCT_CONV_PT1_BELOW 128
-#endif
+constexpr int CONV_PT1_BELOW = 128;     // grids of fewer workgroups than this take 32 couts per wave (launch_conv)
 
 // The kernel. Rounds 1-2 used v_mfma_f32_32x32x2_f32 (lane halves = two k values): every tap of every pixel tile was its own 4-byte load, 24 vector-memory
 // instructions per 36 MFMAs, MFMA busy 0.61-0.68 (git history: k_conv3x3_mfma). Round 3: v_mfma_f32_32x32x1_2b_f32 multiplies two independent 32x32 blocks
@@ -115,19 +113,11 @@ __device__ __forceinline__ void conv3x3_mfma2b_body(const float* __restrict__ in
     ASet a0x, a1x, a0y, a1y; BSet bx, by;
     // weights first, then the activation rows (requesting them in the order the MFMAs consume them, or activations first, measured 3-5 % slower: DESIGN.md 9)
     auto bload = [&](unsigned so, int r) { return __builtin_amdgcn_raw_buffer_load_b96(rs, voff[r], so, 0); };
-#ifndef NCT_CONV_TIMING_SKIP
-#define NCT_CONV_TIMING_SKIP 0                                   // timing experiments only (results wrong): 1 = K loop without the A stream, 2 = without the B stream, 3 = neither
-#endif
     auto load_pair = [&](ASet& a0, ASet& a1, BSet& b) {          // channels (soff - plane + bias) / plane and the next one
-        constexpr bool LA = !(NCT_CONV_TIMING_SKIP & 1), LB = !(NCT_CONV_TIMING_SKIP & 2);
-        if constexpr (LA) {
-            a0.q0 = ap4[0]; a0.q1 = ap4[(size_t)2 * g.Cout]; a0.s8 = ap1[0];
-            if constexpr (CT == 2) { a1.q0 = ap4[32]; a1.q1 = ap4[(size_t)2 * g.Cout + 32]; a1.s8 = ap1[32]; }
-        }
-        if constexpr (LB) {
+        a0.q0 = ap4[0]; a0.q1 = ap4[(size_t)2 * g.Cout]; a0.s8 = ap1[0];
+        if constexpr (CT == 2) { a1.q0 = ap4[32]; a1.q1 = ap4[(size_t)2 * g.Cout + 32]; a1.s8 = ap1[32]; }
 #pragma unroll
-            for (int r = 0; r < 3; ++r) { b.r[0][r] = bload(soff - plane_bytes, r); b.r[1][r] = bload(soff, r); }
-        }
+        for (int r = 0; r < 3; ++r) { b.r[0][r] = bload(soff - plane_bytes, r); b.r[1][r] = bload(soff, r); }
         ap4 += (size_t)18 * g.Cout / 4;
         ap1 += (size_t)18 * g.Cout;
         soff += 2u * plane_bytes;
@@ -150,17 +140,13 @@ __device__ __forceinline__ void conv3x3_mfma2b_body(const float* __restrict__ in
             }
         }
     };
-#ifndef NCT_CONV_SCHED
-#define NCT_CONV_SCHED 0
-#endif
     auto interleave = [] {
-        if constexpr (NCT_CONV_SCHED == 2) return;
         if constexpr (CT == 2) {                                       // 36 MFMAs, 12 loads (6 A + 6 B)
 #pragma unroll
             for (int i = 0; i < 12; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, NCT_CONV_SCHED == 1 ? 1 : 2, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
                 __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, NCT_CONV_SCHED == 1 ? 2 : 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             }
         } else {                                                       // 18 MFMAs, 9 loads (3 A + 6 B)
 #pragma unroll
@@ -312,7 +298,7 @@ int nctk_conv3x3(nct_ctx* ctx, hipStream_t s, const float* in, const float* wp, 
     NCT_REQUIRE((size_t)Cin * H * W * 4 < ((size_t)1 << 32), "conv3x3: input of %d x %d x %d floats exceeds the 4 GB a buffer descriptor addresses", Cin, H, W);
     const int WCO = (Cout % 128 == 0) ? 2 : 1;
     const int tiles_x = cdiv(W, 32), ntiles = pool ? tiles_x * cdiv(H, 2) : cdiv(H * W, 64);         // 64-pixel wave tiles
-    // 64 couts x 64 px per wave unless that grid has fewer than NCT_CONV_PT1_BELOW workgroups: then 32 couts per wave, four waves along cout
+    // 64 couts x 64 px per wave unless that grid has fewer than CONV_PT1_BELOW workgroups: then 32 couts per wave, four waves along cout
     const int full_blocks = cdiv(ntiles, 4 / WCO) * (Cout / (64 * WCO));
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
 #define NCT_CONV_LAUNCH(wco, ct, wpx, nblk_n_)                                                                                                    \
@@ -322,7 +308,7 @@ int nctk_conv3x3(nct_ctx* ctx, hipStream_t s, const float* in, const float* wp, 
         if (pool) hipLaunchKernelGGL((k_conv3x3_mfma2b<wco, ct, true>), dim3(nblocks), dim3(256), 0, s, in, wp, bias, out, g, relu, (float*)nullptr);             \
         else      hipLaunchKernelGGL((k_conv3x3_mfma2b<wco, ct, false>), dim3(nblocks), dim3(256), 0, s, in, wp, bias, out, g, relu, out_hwc);            \
     } while (0)
-    if (full_blocks >= NCT_CONV_PT1_BELOW) {
+    if (full_blocks >= CONV_PT1_BELOW) {
         if (WCO == 2) NCT_CONV_LAUNCH(2, 2, 2, Cout / 128);
         else          NCT_CONV_LAUNCH(1, 2, 4, Cout / 64);
     } else if (Cout % 128 == 0) NCT_CONV_LAUNCH(4, 1, 1, Cout / 128);
@@ -337,7 +323,7 @@ int nctk_conv3x3_pair(nct_ctx* ctx, hipStream_t s, const float* in1, int H1, int
                       float* out1, float* out2, int Cin, int Cout, int relu, float* hwc1, float* hwc2) {
     auto small = [&](int H, int W) {
         const int WCO = (Cout % 128 == 0) ? 2 : 1;
-        return cdiv(cdiv(H * W, 64), 4 / WCO) * (Cout / (64 * WCO)) < NCT_CONV_PT1_BELOW;
+        return cdiv(cdiv(H * W, 64), 4 / WCO) * (Cout / (64 * WCO)) < CONV_PT1_BELOW;
     };
     const bool ok = (Cin & 1) == 0 && (Cout & 63) == 0 && small(H1, W1) && small(H2, W2) && (size_t)Cin * H1 * W1 * 4 < ((size_t)1 << 32) && (size_t)Cin * H2 * W2 * 4 < ((size_t)1 << 32) &&
                     (out1 || hwc1) && (out2 || hwc2) && ctx->conv_pair != 0;

@@ -40,11 +40,8 @@ namespace {
 // than /20 nothing more (scripts: NCT_MG_W1 / NCT_MG_W2 builds). The coarsest grid keeps 60 sweeps at 0.8.
 // Round 3: MG_NS = 3 sweeps per leg with the degree-3 weights on [lambda_max / 30, lambda_max] (0.5346, 0.9677, 5.0974): 60/41/29/22/22 instead of 71/53/39/31/31 iterations
 // (-24 %) for legs that cost ~1.3x (halo 3 instead of 2) — and, at rtol 1e-7, the same 8-bit result. Degree 4 (0.5193, 0.7153, 1.5340, 8.0502 on [lambda_max / 40, lambda_max]):
-// -35 % iterations, legs ~1.7x. NCT_MG_NS selects 2 / 3 / 4 at build time (the oracle mirrors it: orc_set_mg_smoother).
-#ifndef NCT_MG_NS
-#define NCT_MG_NS 3
-#endif
-constexpr int MG_NS = NCT_MG_NS;
+// -35 % iterations, legs ~1.7x.
+constexpr int MG_NS = 3;
 static_assert(MG_NS >= 2 && MG_NS <= 4, "2, 3 or 4 smoothing sweeps per leg");
 constexpr double MG_W[4] = {MG_NS == 2 ? 0.5808 : (MG_NS == 3 ? 0.5346 : 0.5193), MG_NS == 2 ? 2.6437 : (MG_NS == 3 ? 0.9677 : 0.7153), MG_NS == 3 ? 5.0974 : 1.5340, 8.0502};
 constexpr double OMEGA = MG_W[0];
@@ -52,10 +49,6 @@ constexpr double OMEGA = MG_W[0];
 __host__ __device__ constexpr float mg_rk(int k) { return (float)(MG_W[k] / MG_W[0]); }
 constexpr float MG_R0 = (float)(0.8 / MG_W[0]);
 constexpr int NQMAX = 6;      // right-hand sides of a solve: 6 (a and b of the 3 Lab channels) or 3 + 3 on two streams (template parameter NQ)
-#ifndef NCT_MG_TXB
-#define NCT_MG_TXB 32
-#define NCT_MG_TYB 16
-#endif
 
 // The PCG itself (and the hierarchy construction) is fp64; the V-cycle — a fixed linear preconditioner, whose accuracy does not
 // limit the accuracy of the solution — runs in fp32 on rounded copies of the level operators: half the bytes on the two
@@ -360,10 +353,7 @@ __global__ void k_mg_finish(Lvl L) {
 // The small levels of the hierarchy in ONE launch: one 1024-thread workgroup walks levels l0 .. nl-1 (coarse level of at most MG_TAIL_N points each) through
 // the same five stages with the same per-point functions; a stage boundary is a workgroup barrier instead of a kernel boundary (5 launches of ~5 us of dependent
 // latency each per level before: 24 launches and ~0.12 ms per solve at 700x700). Needs pa / pb of level l0 - 1 (k_mg_weights) done.
-#ifndef NCT_MG_TAIL_N
-#define NCT_MG_TAIL_N 512
-#endif
-constexpr int MG_TAIL_N = NCT_MG_TAIL_N;
+constexpr int MG_TAIL_N = 512;
 constexpr int MG_MAXL = 12;
 struct LvlPack { Lvl lv[MG_MAXL]; };
 __global__ __launch_bounds__(1024) void k_mg_setup_tail(LvlPack P, int l0, int nl, double* pst) {
@@ -755,10 +745,8 @@ __global__ __launch_bounds__(LBX * LBY, 8) void k_mg_block(const PState* __restr
 // level: its rhs lv[0].b was written by the restriction above it, its correction goes to lv[0].x2. The coarsest grid (n <= 64) is solved by
 // `sweeps` damped-Jacobi sweeps from zero by one wave (one lane per unknown, the iterate in a register, neighbours through ds_bpermute).
 // P0 = pixels per thread of the first fused level: 1 or 2 (<= 2048 pixels: 44x44 at 700x700; 63x63 at 1000x1000 stays on tile launches — four pixels per thread measured slower)
-#ifndef NCT_MID_MAXP0
-#define NCT_MID_MAXP0 2      // largest first fused level, in units of 1024 pixels (1 or 2): 2 = the 44x44 level of a 700x700 pair rides in k_mg_mid (same time as its two tile launches, 186 launches fewer per pair)
-#endif
-static_assert(NCT_MID_MAXP0 == 1 || NCT_MID_MAXP0 == 2, "k_mg_mid is instantiated for one or two pixels per thread at its first level (four measured slower: DESIGN.md 9)");
+constexpr int MID_MAXP0 = 2;      // largest first fused level, in units of 1024 pixels (1 or 2): 2 = the 44x44 level of a 700x700 pair rides in k_mg_mid (same time as its two tile launches, 186 launches fewer per pair)
+static_assert(MID_MAXP0 == 1 || MID_MAXP0 == 2, "k_mg_mid is instantiated for one or two pixels per thread at its first level (four measured slower: DESIGN.md 9)");
 constexpr int MID_T = 1024, MID_P1 = 1, MID_N1 = MID_T * MID_P1, MID_LV = 5;
 // largest level at depth d >= 1 (the first fused level: P0 * 1024); levels shrink ~4x per depth. The levels below the first park their 10 coefficients and 4 prolongation
 // weights per pixel in LDS for the way back up (a workgroup has the CU to itself: 79 KB of the 160 KB), so only right-hand side and iterate stay in registers across the recursion
@@ -1110,9 +1098,7 @@ __global__ void k_pcg_finish(int n, const double* __restrict__ x6, double* __res
 }  // namespace
 
 #define LCHK() NCT_LAUNCH_CHECK()
-#ifndef NCT_WLS_BATCH
-#define NCT_WLS_BATCH 2      // iterations enqueued between two convergence polls (even: the state double buffer); 4: +1.0 ms of empty launches past convergence per pair, 6: +1.3
-#endif
+constexpr int WLS_BATCH = 2;      // iterations enqueued between two convergence polls (even: the state double buffer); 4: +1.0 ms of empty launches past convergence per pair, 6: +1.3
 
 namespace {
 // One PCG solve over NQ right-hand sides on its own stream. Everything it needs was allocated by the caller (the arena is not thread safe);
@@ -1155,7 +1141,7 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
     // lv[l].x2 = where level l's correction ends up (the up leg cannot write in place: neighbouring tiles still read lv[l].x).
     // Tile shapes: bandwidth-bound levels use TXB x TYB tiles; below 100k pixels the legs are latency bound, so a 16x8 tile keeps the
     // dependent load chains short and spreads over more CUs.
-    constexpr int TXB = NCT_MG_TXB, TYB = NCT_MG_TYB;
+    constexpr int TXB = 32, TYB = 16;
     auto down = [&](int l) {
         const dim3 gb(cdiv(lv[l].W, TXB) * cdiv(lv[l].H, TYB)), gs(cdiv(lv[l].W, 16) * cdiv(lv[l].H, 8));      // 1-D: mg_tile_of_block maps block -> tile
         if (l == 0 && B.lines) {
@@ -1195,7 +1181,7 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
     int tail0 = nl - 1;
     auto mid_fits = [&](int first) {                     // levels first .. nl-1 as depths 0 .. of k_mg_mid
         if (nl - first > MID_LV) return false;
-        for (int l = first; l < nl; ++l) { const int d = l - first; if (lv[l].n > (d == 0 ? NCT_MID_MAXP0 * MID_T : mid_cap(d))) return false; }
+        for (int l = first; l < nl; ++l) { const int d = l - first; if (lv[l].n > (d == 0 ? MID_MAXP0 * MID_T : mid_cap(d))) return false; }
         return true;
     };
     while (tail0 > 1 && mid_fits(tail0 - 1)) --tail0;
@@ -1232,7 +1218,7 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
     // Convergence is polled without draining the stream: the update kernel of the last iteration of every batch publishes the solver
     // state, with a sequence number, into page-locked host memory; the host enqueues the NEXT batch before it spins on that number, so
     // the GPU always has a batch queued. The batch enqueued past convergence costs only empty launches (nactive == 0).
-    const int maxit = B.maxit, batch = NCT_WLS_BATCH;
+    const int maxit = B.maxit, batch = WLS_BATCH;
     PState* hst = B.hst;                                  // two slots of page-locked memory
     PState* pub_to = nullptr; int pub_seq = 0;           // set for the LAST iteration of a batch: its update kernel publishes the state
     auto iteration = [&](int it) -> int {

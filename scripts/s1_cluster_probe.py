@@ -1,9 +1,9 @@
 """Does a CLUSTER-MAJOR pixel order confine the S1 operator's gathers to an XCD's L2? The kNN edges of a pixel stay inside the (dilated) k-means clusters it belongs to, and the
-clusters are spatial blobs: if threads and vectors are ordered (cluster, raster) and every XCD takes a contiguous range of that order (NCT_S1_XCD=1), an XCD gathers from ~1/8 of the
+clusters are spatial blobs: if threads and vectors are ordered (cluster, raster) and every XCD takes a contiguous range of that order (what the library does for the bandwidth-bound levels), an XCD gathers from ~1/8 of the
 23.5 MB vector. Probe (like s1_sorted_probe.py): the finest-level solve of the bench pair's real graph, and of the same graph with image, graph and weights renumbered cluster-major
 (a different system — the raster terms then couple neighbours of the new order — with the permuted solver's gather pattern, minus its scattered raster gathers: an optimistic bound).
-usage: [NCT_S1_XCD=1] python scripts/s1_cluster_probe.py"""
-import sys, time, os
+usage: python scripts/s1_cluster_probe.py"""
+import sys, time
 sys.path.insert(0, "tests"); sys.path.insert(0, "neural-color-transfer_amd/python")
 import numpy as np, nct, synth
 from caffemodel_io import synthetic_vgg19
@@ -26,7 +26,7 @@ def run(name, src_, guide_, g, w_, e_):
     ctx.local_color_transfer(e_, src_, guide_, src_, g, w_, 4)
     t = time.perf_counter()
     for _ in range(5): ctx.local_color_transfer(e_, src_, guide_, src_, g, w_, 4)
-    print("%-70s %.2f ms per call (NCT_S1_XCD=%s)" % (name, (time.perf_counter() - t) / 5 * 1e3, os.environ.get("NCT_S1_XCD", "0")), flush=True)
+    print("%-70s %.2f ms per call" % (name, (time.perf_counter() - t) / 5 * 1e3), flush=True)
 
 
 run("real kNN graph, raster order", src, guide, ids, ws, err)

@@ -21,7 +21,7 @@ from caffemodel_io import synthetic_vgg19
 
 pytestmark = pytest.mark.gpu
 
-PT1_BELOW = 128          # NCT_CONV_PT1_BELOW (k_vgg.hip)
+PT1_BELOW = 128          # CONV_PT1_BELOW (k_vgg.hip)
 U = 2.0 ** -24           # unit roundoff of float32
 
 
