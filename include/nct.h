@@ -30,7 +30,8 @@ extern "C" {
  * sequences, nct_seq_set_motion; 114 — propagated frames, nct_seq_frame_propagate and nct_seq_warp; 115 — the single-layer conv seams nct_conv3x3_dev and
  * nct_conv3x3_pair_dev; 116 — 3D colour look-up tables, nct_lut_*; 117 — adaptive key frames, nct_seq_change, nct_seq_probe and nct_seq_frame_auto; 118 — the upsampling finish and
  * full-resolution sequences, nct_color_finish_upsample, nct_process_pair_fullres_finish and nct_seq_begin_fullres; still 118 with the guided finish, nct_color_finish_guided[_dev], nct_set_finish_guided and nct_guided_params: no struct
- * changed layout and no existing entry point changed meaning, entry points were only added). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
+ * changed layout and no existing entry point changed meaning, entry points were only added; likewise still 118 with source region masks, nct_region_*, nct_pair_set_region,
+ * nct_process_pair_region and nct_lut_fit_masked). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
 #define NCT_VERSION 118
 
@@ -471,6 +472,56 @@ int nct_lut_fit_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, const uint8_t* d_res
 int nct_lut_apply(nct_ctx* ctx, const float* lut, int size, const uint8_t* bgr, size_t npix, uint8_t* out_bgr);
 int nct_lut_apply_dev(nct_ctx* ctx, const float* d_lut, int size, const uint8_t* d_bgr, size_t npix, uint8_t* d_out_bgr);
 int nct_pair_fit_lut(nct_ctx* ctx, const nct_lut_params* prm, float* lut_out);
+
+/* ---- source region masks (SPEC §6.11; an extension): recolour only part of the source. A mask M has one byte per SOURCE pixel: 0 keeps the source, 255 is the full
+ * transfer, values between are partial. The level masks are the single-channel form of the image pyramid: M_top = M at the working size, M_l = nct_resize_u8c1 of
+ * M_(l+1) to level l's grid; nct_resize_u8c1 is channel 0 of nct_resize_u8c3 on (M, M, M), the INTER_AREA switch included. Every level of a masked run has two steps
+ * more than nct_pair_run's: between S1 and U1 the mix moves S1's coefficients toward the identity transform, with m = M_l(p) / 255 in double a' = 1 + m (a - 1),
+ * b' = m b (M_l = 255: the six 64-bit words are copied, a NaN stays that NaN; M_l = 0: a = 1, b = 0, which heals a NaN), and X' replaces S1's output in U1, roughness,
+ * S2 and A1 — S2's edge-aware smoothing then carries the transition along the source's own edges; behind A1 the compose, at the size the finish targets with the mask at
+ * that size, writes out(p) = keep ? S(p) : Lab2BGR(Lab_o(p)), keep = (protect and M(p) == 0) or (M(p) != 255 and Lab_o(p) == nct_bgr2lab_u8(S)(p) on all three bytes):
+ * a pixel whose Lab value did not move keeps its source bytes instead of the Lab round trip's. The composed image is the level's result and what the next level's
+ * re-predict reads. protect (default 0) trades a possible step at a binary mask drawn through a smooth region for the guarantee that an M == 0 pixel never changes.
+ * No mask: today's bytes, launches and arena. M == 255 everywhere: nct_process_pair's bytes. M == 0 everywhere: the source, byte for byte.
+ * nct_resize_u8c1, nct_region_mix (x, x_out [2][h*w][3], mask h*w; grid sides 1 … 4096), nct_region_compose (s_bgr, lab_out, out_bgr npix*3, mask npix; 1 <= npix <= 2^26;
+ * Lab -> BGR in the form prm->flags selects): the three steps alone on host pointers, synchronous; the _dev forms take device pointers and are enqueued on the context's
+ * stream (nct_region_mix_dev: x_out may be x; nct_region_compose_dev converts S to Lab in an arena block that goes back in stream order).
+ * nct_pair_set_region: after nct_pair_upload / nct_multi_upload, copies the mask (sh x sw of the uploaded source) to the device; nct_pair_run, nct_multi_run and their
+ * _levels forms then run masked, nct_pair_fit_lut fits over the pixels with M >= 128 (the mask at the size it reads). NULL removes the mask; the next upload drops it.
+ * No uploaded source, or an open sequence: NCT_ERR_STATE (sequences with a mask are not defined). region NULL: the defaults; protect outside {0, 1}: NCT_ERR_INVALID.
+ * nct_pair_run_region_levels: nct_pair_run_levels (levels nullable) plus, per level, the level mask and X' — color[l]->ab_nonlocal stays S1's output BEFORE the mix,
+ * ab_up / roughness / ab_wls come after it. With region levels asked for and no mask set: NCT_ERR_STATE. The mix's time counts in nct_pair_timing.color_ms.
+ * nct_process_pair_region = nct_pair_upload + nct_pair_set_region + nct_pair_run + nct_pair_download; mask NULL: nct_process_pair.
+ * nct_process_pair_fullres_region: nct_process_pair_fullres with a mask at the ORIGINAL size: the working mask is nct_resize_u8c1 of mask0 to nct_working_size's size, the
+ * last level mixes on its grid with the working-size level mask and composes at sh x sw with mask0; a source that is not shrunk gives nct_process_pair_region's bytes;
+ * nct_pair_fit_lut afterwards uses mask0. nct_process_pair_fullres_finish_region: the same with the finish chosen; NCT_FINISH_UPSAMPLE (plain or guided) with a mask is
+ * not defined and refused with NCT_ERR_INVALID. mask0 NULL: nct_process_pair_fullres_finish.
+ * nct_lut_fit_masked[_dev]: nct_lut_fit whose splat skips the pixels with mask < 128 — the fit of the subsequence of kept pixels; mask NULL: nct_lut_fit. A mask that
+ * keeps no pixel: NCT_ERR_INVALID. The masked _dev form waits for its splat (it has to learn whether a pixel was kept) before it enqueues the solve.
+ * A mask on the REFERENCE ("take colours only from the sky") is not part of this: it needs masked BDS votes, a new canonical vote order. */
+typedef struct nct_region_params { int protect; } nct_region_params;
+void nct_region_params_default(nct_region_params* p);     /* protect 0 */
+typedef struct nct_region_levels { double* ab_mix[5]; uint8_t* mask[5]; } nct_region_levels;   /* X' [2][h*w][3]; M_l [h*w]; all nullable */
+int nct_resize_u8c1(nct_ctx* ctx, const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw);
+int nct_resize_u8c1_dev(nct_ctx* ctx, const uint8_t* d_src, int sh, int sw, uint8_t* d_dst, int dh, int dw);
+int nct_region_mix(nct_ctx* ctx, const double* x, const uint8_t* mask, int h, int w, double* x_out);
+int nct_region_mix_dev(nct_ctx* ctx, const double* d_x, const uint8_t* d_mask, int h, int w, double* d_x_out);
+int nct_region_compose(nct_ctx* ctx, const uint8_t* s_bgr, const uint8_t* lab_out, const uint8_t* mask, size_t npix, const nct_region_params* region, const nct_params* prm,
+                       uint8_t* out_bgr);
+int nct_region_compose_dev(nct_ctx* ctx, const uint8_t* d_s_bgr, const uint8_t* d_lab_out, const uint8_t* d_mask, size_t npix, const nct_region_params* region,
+                           const nct_params* prm, uint8_t* d_out_bgr);
+int nct_pair_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_params* region);
+int nct_pair_run_region_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_region_levels* region_levels);
+int nct_process_pair_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* mask, const uint8_t* ref_bgr, int rh, int rw, const nct_region_params* region,
+                            const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing);
+int nct_process_pair_fullres_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* mask0, const uint8_t* ref_bgr, int rh, int rw, int max_side,
+                                    const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr /* sh x sw x 3 */, nct_pair_timing* timing);
+int nct_process_pair_fullres_finish_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* mask0, const uint8_t* ref_bgr, int rh, int rw, int max_side,
+                                           int finish, const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr /* sh x sw x 3 */, nct_pair_timing* timing);
+int nct_lut_fit_masked(nct_ctx* ctx, const uint8_t* src_bgr, const uint8_t* res_bgr, const uint8_t* mask, size_t npix, const nct_lut_params* prm, float* lut_out,
+                       nct_lut_stages* stages);
+int nct_lut_fit_masked_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, const uint8_t* d_res_bgr, const uint8_t* d_mask, size_t npix, const nct_lut_params* prm, float* d_lut_out,
+                           nct_lut_stages* d_stages);
 
 /* ---- device-pointer seams: the same operations on buffers that stay in HBM between calls (main.cu:204-316 keeps Ndata_C1, ann_device, ... on the device
  * across these kernels; an integrator replacing single seams should not pay H2D + D2H + a synchronise per call). Buffers come from the context's arena

@@ -85,6 +85,57 @@ __global__ __launch_bounds__(256) void k_lut_splat(const uint8_t* __restrict__ S
     }
 }
 
+// The masked splat (SPEC §6.11 rule 7): k_lut_splat over the pixels with M >= 128 only, a kernel of its own so that the unmasked one stays as it is. The integer sums
+// are order-free, so it equals the splat of the subsequence of kept pixels. kept: the number of kept pixels, one atomic per workgroup (zeroed by the launcher).
+__global__ __launch_bounds__(256) void k_lut_splat_masked(const uint8_t* __restrict__ S, const uint8_t* __restrict__ O, const uint8_t* __restrict__ M, long npix, long chunk, int N,
+                                                          int packed, u64* __restrict__ W, u64* __restrict__ R, u64* __restrict__ kept) {
+    __shared__ int keys[LUT_HASH];
+    __shared__ u64 acc[LUT_HASH * 4];
+    __shared__ unsigned nkept;
+    for (int i = threadIdx.x; i < LUT_HASH; i += 256) keys[i] = -1;
+    for (int i = threadIdx.x; i < LUT_HASH * 4; i += 256) acc[i] = 0ull;
+    if (threadIdx.x == 0) nkept = 0u;
+    __syncthreads();
+    const long first = (long)blockIdx.x * chunk, last = min(first + chunk, npix);          // chunk is a multiple of 4
+    unsigned mine = 0u;
+    for (long p0 = first + (long)threadIdx.x * 4; p0 < last; p0 += 256 * 4) {
+        const int cnt = (int)min(4L, last - p0);
+        uint32_t sw[3], ow[3];
+        lut_load4(S, p0, cnt, packed != 0, sw);
+        lut_load4(O, p0, cnt, packed != 0, ow);
+        for (int j = 0; j < cnt; ++j) {
+            if (M[p0 + j] < 128) continue;
+            ++mine;
+            int ib, fb, ig, fg, ir, fr;
+            lut_axis(lut_byte(sw, 3 * j), N, ib, fb); lut_axis(lut_byte(sw, 3 * j + 1), N, ig, fg); lut_axis(lut_byte(sw, 3 * j + 2), N, ir, fr);
+            long long d[3];
+            for (int c = 0; c < 3; ++c) d[c] = (long long)(lut_byte(ow, 3 * j + c) - lut_byte(sw, 3 * j + c));
+            for (int corner = 0; corner < 8; ++corner) {
+                const int db = corner >> 2, dg = (corner >> 1) & 1, dr = corner & 1;
+                const long long w = (long long)((db ? fb : 255 - fb) * (dg ? fg : 255 - fg)) * (long long)(dr ? fr : 255 - fr);
+                if (w == 0) continue;
+                const int node = ((ib + db) * N + ig + dg) * N + ir + dr;
+                const int slot = lut_slot(keys, node);
+                u64* dst = slot >= 0 ? &acc[slot * 4] : nullptr;
+                if (dst) atomicAdd(dst, (u64)w); else atomicAdd(&W[node], (u64)w);
+                for (int c = 0; c < 3; ++c) {
+                    if (d[c] == 0) continue;
+                    if (dst) atomicAdd(dst + 1 + c, (u64)(w * d[c])); else atomicAdd(&R[(size_t)node * 3 + c], (u64)(w * d[c]));
+                }
+            }
+        }
+    }
+    if (mine) atomicAdd(&nkept, mine);
+    __syncthreads();
+    for (int i = threadIdx.x; i < LUT_HASH * 4; i += 256) {
+        const int key = keys[i >> 2], comp = i & 3;
+        const u64 v = acc[i];
+        if (key < 0 || v == 0ull) continue;
+        if (comp == 0) atomicAdd(&W[key], v); else atomicAdd(&R[(size_t)key * 3 + comp - 1], v);
+    }
+    if (threadIdx.x == 0 && nkept) atomicAdd(kept, (u64)nkept);
+}
+
 // ================================================================= solve (rules 4-7): element-wise operations, each over `count` elements from `tid` in steps of `nth`
 // A level's operator is a 27-point stencil A [n^3][27], entry e = (db + 1) * 9 + (dg + 1) * 3 + dr + 1; an entry whose neighbour lies outside the lattice is 0.0.
 struct lut_level { int n; double* A; double* q; double* x; double* t; double* b; double* r; };
@@ -327,6 +378,20 @@ int nctk_lut_splat(nct_ctx* ctx, hipStream_t s, const uint8_t* src, const uint8_
     const int grid = (int)((npix + chunk - 1) / chunk);
     const int packed = (((uintptr_t)src | (uintptr_t)res) & 3) == 0;
     k_lut_splat<<<grid, 256, 0, s>>>(src, res, npix, chunk, N, packed, (u64*)W, (u64*)R);
+    NCT_LAUNCH_CHECK();
+    return NCT_OK;
+}
+
+int nctk_lut_splat_masked(nct_ctx* ctx, hipStream_t s, const uint8_t* src, const uint8_t* res, const uint8_t* mask, long npix, int N, uint64_t* W, int64_t* R, uint64_t* kept) {
+    const size_t n3 = (size_t)N * N * N;
+    NCT_HIP(hipMemsetAsync(W, 0, n3 * sizeof(uint64_t), s));
+    NCT_HIP(hipMemsetAsync(R, 0, n3 * 3 * sizeof(int64_t), s));
+    NCT_HIP(hipMemsetAsync(kept, 0, sizeof(uint64_t), s));
+    long chunk = (npix + 1023) / 1024;                       // the grid of nctk_lut_splat
+    chunk = chunk < 1024 ? 1024 : (chunk + 3) / 4 * 4;
+    const int grid = (int)((npix + chunk - 1) / chunk);
+    const int packed = (((uintptr_t)src | (uintptr_t)res) & 3) == 0;
+    k_lut_splat_masked<<<grid, 256, 0, s>>>(src, res, mask, npix, chunk, N, packed, (u64*)W, (u64*)R, (u64*)kept);
     NCT_LAUNCH_CHECK();
     return NCT_OK;
 }

@@ -47,6 +47,44 @@ int nct_resize_u8c3(nct_ctx* ctx, const uint8_t* src, int sh, int sw, uint8_t* d
     NCT_D2H(dst, b, (size_t)dh * dw * 3); NCT_SYNC();
     return NCT_OK;
 }
+// ---- source region masks (SPEC §6.11): the three steps alone, on host maps
+int nct_resize_u8c1(nct_ctx* ctx, const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(src && dst, "resize_u8c1: null pointer");
+    NCT_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0 && sh <= 16384 && sw <= 16384 && dh <= 16384 && dw <= 16384 && (long long)sh * sw <= (1LL << 26) && (long long)dh * dw <= (1LL << 26),
+                "resize_u8c1: size %dx%d -> %dx%d out of range", sw, sh, dw, dh);
+    DevBuf<uint8_t> a(ctx, (size_t)sh * sw), b(ctx, (size_t)dh * dw);
+    if (!a.ok() || !b.ok()) return NCT_ERR_HIP;
+    NCT_H2D(a, src, (size_t)sh * sw);
+    NCT_TRY(nctk_resize_u8c1(ctx, ctx->stream, a, sh, sw, b, dh, dw));
+    NCT_D2H(dst, b, (size_t)dh * dw); NCT_SYNC();
+    return NCT_OK;
+}
+int nct_region_mix(nct_ctx* ctx, const double* x, const uint8_t* mask, int h, int w, double* x_out) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(x && mask && x_out, "region_mix: null pointer");
+    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "region_mix: grid %dx%d out of range", w, h);
+    const size_t n = (size_t)h * w;
+    DevBuf<double> dx(ctx, 6 * n); DevBuf<uint8_t> dm(ctx, n);
+    if (!dx.ok() || !dm.ok()) return NCT_ERR_HIP;
+    NCT_H2D(dx, x, sizeof(double) * 6 * n); NCT_H2D(dm, mask, n);
+    NCT_TRY(nctk_region_mix(ctx, ctx->stream, dx, dm, h, w, dx));          // in place, as a level does it
+    NCT_D2H(x_out, dx, sizeof(double) * 6 * n); NCT_SYNC();
+    return NCT_OK;
+}
+int nct_region_compose(nct_ctx* ctx, const uint8_t* s_bgr, const uint8_t* lab_out, const uint8_t* mask, size_t npix, const nct_region_params* region, const nct_params* prm,
+                       uint8_t* out_bgr) {
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_region_compose_check(ctx, "region_compose", s_bgr, lab_out, mask, npix, region, prm, out_bgr));
+    DevBuf<uint8_t> ds(ctx, npix * 3), dls(ctx, npix * 3), dlo(ctx, npix * 3), dm(ctx, npix), dout(ctx, npix * 3);
+    if (!ds.ok() || !dls.ok() || !dlo.ok() || !dm.ok() || !dout.ok()) return NCT_ERR_HIP;
+    NCT_H2D(ds, s_bgr, npix * 3); NCT_H2D(dlo, lab_out, npix * 3); NCT_H2D(dm, mask, npix);
+    NCT_TRY(nctk_bgr2lab(ctx, ctx->stream, ds, dls, npix));
+    NCT_TRY(nctk_region_compose(ctx, ctx->stream, ds, dls, dlo, dm, npix, region ? region->protect : 0, nct_cube_form(*prm), dout));
+    NCT_D2H(out_bgr, dout, npix * 3); NCT_SYNC();
+    return NCT_OK;
+}
+
 int nct_resize_f64c3(nct_ctx* ctx, const double* src, int sh, int sw, double* dst, int dh, int dw) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(src && dst && sh > 0 && sw > 0 && dh > 0 && dw > 0, "resize_f64c3: bad arguments");

@@ -195,6 +195,30 @@ int nct_seq_motion_field_dev(nct_ctx* ctx, const uint8_t* d_lab, const uint8_t* 
     return nctk_seq_motion(ctx, ctx->stream, d_lab, pk, h, w, d_parent, ph, pw, R, penalty, d_m_out);
 }
 
+// ---- SPEC §6.11 on device pointers
+int nct_resize_u8c1_dev(nct_ctx* ctx, const uint8_t* d_src, int sh, int sw, uint8_t* d_dst, int dh, int dw) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(d_src && d_dst, "resize_u8c1_dev: null pointer");
+    NCT_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0 && sh <= 16384 && sw <= 16384 && dh <= 16384 && dw <= 16384 && (long long)sh * sw <= (1LL << 26) && (long long)dh * dw <= (1LL << 26),
+                "resize_u8c1_dev: size %dx%d -> %dx%d out of range", sw, sh, dw, dh);
+    return nctk_resize_u8c1(ctx, ctx->stream, d_src, sh, sw, d_dst, dh, dw);
+}
+
+int nct_region_mix_dev(nct_ctx* ctx, const double* d_x, const uint8_t* d_mask, int h, int w, double* d_x_out) {
+    NCT_CTX_ENTER();
+    return nctk_region_mix(ctx, ctx->stream, d_x, d_mask, h, w, d_x_out);
+}
+
+int nct_region_compose_dev(nct_ctx* ctx, const uint8_t* d_s_bgr, const uint8_t* d_lab_out, const uint8_t* d_mask, size_t npix, const nct_region_params* region,
+                           const nct_params* prm, uint8_t* d_out_bgr) {
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_region_compose_check(ctx, "region_compose_dev", d_s_bgr, d_lab_out, d_mask, npix, region, prm, d_out_bgr));
+    DevBuf<uint8_t> ls(ctx, npix * 3);                           // Lab_S; the block goes back in stream order
+    if (!ls.ok()) return NCT_ERR_HIP;
+    NCT_TRY(nctk_bgr2lab(ctx, ctx->stream, d_s_bgr, ls, npix));
+    return nctk_region_compose(ctx, ctx->stream, d_s_bgr, ls, d_lab_out, d_mask, npix, region ? region->protect : 0, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0, d_out_bgr);
+}
+
 int nct_color_finish_upsample_dev(nct_ctx* ctx, const double* d_ab_wls, int h, int w, const uint8_t* d_s_bgr_full, int H, int W, const nct_params* prm,
                                   uint8_t* d_out_bgr_full) {                                                                                          /* SPEC §6.8 */
     NCT_CTX_ENTER();

@@ -248,6 +248,25 @@ int nctk_lut_apply(nct_ctx* ctx, hipStream_t s, const float* lut, int N, const u
 // main stream; stages (nullable, its arrays nullable): DEVICE pointers
 int nct_lut_fit_check(nct_ctx* ctx, const char* what, const void* src, const void* res, size_t npix, const nct_lut_params* prm, const void* lut_out);
 int nct_lut_fit_enqueue(nct_ctx* ctx, const uint8_t* d_src, const uint8_t* d_res, size_t npix, const nct_lut_params* prm, float* d_lut, const nct_lut_stages* d_stages);
+// SPEC §6.11 rule 7: the splat over the pixels with mask >= 128; kept (8 bytes on the device, zeroed on s): how many there were. nct_lut_fit_enqueue_masked: the fit with
+// that splat (d_mask non-null); it waits for the splat to learn whether any pixel was kept and refuses an empty fit with NCT_ERR_INVALID (`what` names the entry point)
+int nctk_lut_splat_masked(nct_ctx* ctx, hipStream_t s, const uint8_t* src, const uint8_t* res, const uint8_t* mask, long npix, int N, uint64_t* W, int64_t* R, uint64_t* kept);
+int nct_lut_fit_enqueue_masked(nct_ctx* ctx, const char* what, const uint8_t* d_src, const uint8_t* d_res, const uint8_t* d_mask, size_t npix, const nct_lut_params* prm, float* d_lut,
+                               const nct_lut_stages* d_stages);
+// k_region.hip — source region masks (SPEC §6.11). The single-channel form of nctk_resize_u8c3; the mix of coefficients x ([2][h*w][3]) toward the identity by the level
+// mask (x_out may be x); the compose of a finish's Lab result o_lab with the source (BGR and Lab) by the mask at that size, Lab -> BGR in `form` included
+int nctk_resize_u8c1(nct_ctx* ctx, hipStream_t s, const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw);
+int nctk_region_mix(nct_ctx* ctx, hipStream_t s, const double* x, const uint8_t* mask, int h, int w, double* x_out);
+// the argument checks of nct_region_compose[_dev] (`what` names the entry point in the message)
+static inline int nct_region_compose_check(nct_ctx* ctx, const char* what, const void* s_bgr, const void* lab_out, const void* mask, size_t npix, const nct_region_params* region, const nct_params* prm,
+                             const void* out_bgr) {
+    NCT_REQUIRE(s_bgr && lab_out && mask && prm && out_bgr, "%s: null pointer", what);
+    NCT_REQUIRE(npix >= 1 && npix <= (size_t)NCT_FINISH_MAX_PIXELS, "%s: the number of pixels must be in [1, 2^26] (got %zu)", what, npix);
+    NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "%s: region protect must be 0 or 1 (got %d)", what, region ? region->protect : 0);
+    return NCT_OK;
+}
+int nctk_region_compose(nct_ctx* ctx, hipStream_t s, const uint8_t* s_bgr, const uint8_t* s_lab, const uint8_t* o_lab, const uint8_t* mask, size_t npix, int protect, int form,
+                        uint8_t* out_bgr);
 // k_wls_mg.hip
 int nctk_wls_solve_mg(nct_ctx* ctx, hipStream_t s, double* X, const double* rough, const double* wx, const double* wy, int H, int W,
                       double rtol, int* iters_out);

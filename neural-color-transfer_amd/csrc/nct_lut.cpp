@@ -10,7 +10,9 @@ int nct_lut_fit_check(nct_ctx* ctx, const char* what, const void* src, const voi
     return NCT_OK;
 }
 
-int nct_lut_fit_enqueue(nct_ctx* ctx, const uint8_t* d_src, const uint8_t* d_res, size_t npix, const nct_lut_params* prm, float* d_lut, const nct_lut_stages* st) {
+// d_mask null: the fit of every pixel. Non-null (SPEC §6.11 rule 7): the masked splat, and a wait for it — a fit that kept no pixel is refused before the solve
+static int lut_fit_run(nct_ctx* ctx, const char* what, const uint8_t* d_src, const uint8_t* d_res, const uint8_t* d_mask, size_t npix, const nct_lut_params* prm, float* d_lut,
+                       const nct_lut_stages* st) {
     const int N = prm->size;
     const size_t n3 = (size_t)N * N * N;
     const hipStream_t s = ctx->stream;
@@ -22,9 +24,24 @@ int nct_lut_fit_enqueue(nct_ctx* ctx, const uint8_t* d_src, const uint8_t* d_res
     if (!W) { if (!w.alloc(ctx, n3)) return NCT_ERR_HIP; W = w; }
     if (!R) { if (!r.alloc(ctx, n3 * 3)) return NCT_ERR_HIP; R = r; }
     if (!D) { if (!d.alloc(ctx, n3 * 3)) return NCT_ERR_HIP; D = d; }
-    NCT_TRY(nctk_lut_splat(ctx, s, d_src, d_res, (long)npix, N, W, R));
+    if (d_mask) {
+        DevBuf<uint64_t> kept(ctx, 1);
+        if (!kept.ok()) return NCT_ERR_HIP;
+        NCT_TRY(nctk_lut_splat_masked(ctx, s, d_src, d_res, d_mask, (long)npix, N, W, R, kept));
+        uint64_t nkept = 0;
+        NCT_D2H(&nkept, kept, sizeof nkept);
+        NCT_SYNC();
+        NCT_REQUIRE(nkept > 0, "%s: the mask keeps no pixel (none of the %zu has mask >= 128)", what, npix);
+    } else NCT_TRY(nctk_lut_splat(ctx, s, d_src, d_res, (long)npix, N, W, R));
     NCT_TRY(nctk_lut_solve(ctx, s, W, R, N, prm->lambda, D));
     return nctk_lut_table(ctx, s, D, N, d_lut);
+}
+int nct_lut_fit_enqueue(nct_ctx* ctx, const uint8_t* d_src, const uint8_t* d_res, size_t npix, const nct_lut_params* prm, float* d_lut, const nct_lut_stages* st) {
+    return lut_fit_run(ctx, "lut_fit", d_src, d_res, nullptr, npix, prm, d_lut, st);
+}
+int nct_lut_fit_enqueue_masked(nct_ctx* ctx, const char* what, const uint8_t* d_src, const uint8_t* d_res, const uint8_t* d_mask, size_t npix, const nct_lut_params* prm, float* d_lut,
+                               const nct_lut_stages* st) {
+    return lut_fit_run(ctx, what, d_src, d_res, d_mask, npix, prm, d_lut, st);
 }
 
 static int lut_apply_check(nct_ctx* ctx, const char* what, const void* lut, int size, const void* bgr, size_t npix, const void* out) {
@@ -64,6 +81,35 @@ int nct_lut_fit_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, const uint8_t* d_res
     NCT_CTX_ENTER();
     NCT_TRY(nct_lut_fit_check(ctx, "lut_fit_dev", d_src_bgr, d_res_bgr, npix, prm, d_lut_out));
     return nct_lut_fit_enqueue(ctx, d_src_bgr, d_res_bgr, npix, prm, d_lut_out, d_stages);
+}
+
+// SPEC §6.11 rule 7: the fit over the pixels with mask >= 128; mask NULL: nct_lut_fit
+int nct_lut_fit_masked(nct_ctx* ctx, const uint8_t* src_bgr, const uint8_t* res_bgr, const uint8_t* mask, size_t npix, const nct_lut_params* prm, float* lut_out, nct_lut_stages* stages) {
+    if (!mask) return nct_lut_fit(ctx, src_bgr, res_bgr, npix, prm, lut_out, stages);
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_lut_fit_check(ctx, "lut_fit_masked", src_bgr, res_bgr, npix, prm, lut_out));
+    const size_t n3 = (size_t)prm->size * prm->size * prm->size;
+    DevBuf<uint8_t> ds(ctx, npix * 3), dr(ctx, npix * 3), dm(ctx, npix);
+    DevBuf<float> dl(ctx, n3 * 3);
+    DevBuf<uint64_t> w(ctx, n3); DevBuf<int64_t> r(ctx, n3 * 3); DevBuf<double> d(ctx, n3 * 3);
+    if (!ds.ok() || !dr.ok() || !dm.ok() || !dl.ok() || !w.ok() || !r.ok() || !d.ok()) return NCT_ERR_HIP;
+    NCT_H2D(ds, src_bgr, npix * 3); NCT_H2D(dr, res_bgr, npix * 3); NCT_H2D(dm, mask, npix);
+    const nct_lut_stages dst{w, r, d};
+    NCT_TRY(nct_lut_fit_enqueue_masked(ctx, "lut_fit_masked", ds, dr, dm, npix, prm, dl, &dst));
+    NCT_D2H(lut_out, dl, sizeof(float) * n3 * 3);
+    if (stages && stages->weight) NCT_D2H(stages->weight, w, sizeof(uint64_t) * n3);
+    if (stages && stages->resid) NCT_D2H(stages->resid, r, sizeof(int64_t) * n3 * 3);
+    if (stages && stages->disp) NCT_D2H(stages->disp, d, sizeof(double) * n3 * 3);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
+int nct_lut_fit_masked_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, const uint8_t* d_res_bgr, const uint8_t* d_mask, size_t npix, const nct_lut_params* prm, float* d_lut_out,
+                           nct_lut_stages* d_stages) {
+    if (!d_mask) return nct_lut_fit_dev(ctx, d_src_bgr, d_res_bgr, npix, prm, d_lut_out, d_stages);
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_lut_fit_check(ctx, "lut_fit_masked_dev", d_src_bgr, d_res_bgr, npix, prm, d_lut_out));
+    return nct_lut_fit_enqueue_masked(ctx, "lut_fit_masked_dev", d_src_bgr, d_res_bgr, d_mask, npix, prm, d_lut_out, d_stages);
 }
 
 int nct_lut_apply(nct_ctx* ctx, const float* lut, int size, const uint8_t* bgr, size_t npix, uint8_t* out_bgr) {

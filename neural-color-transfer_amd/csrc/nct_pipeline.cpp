@@ -21,7 +21,9 @@ void drop_images(nct_ctx* ctx, pair_state* P) {
     if (P->out) { ctx->release(P->out); P->out = nullptr; }
     if (P->full_src) { ctx->release(P->full_src); P->full_src = nullptr; }
     if (P->full_out) { ctx->release(P->full_out); P->full_out = nullptr; }
-    P->K = 0; P->finished = false;
+    if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
+    if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
+    P->K = 0; P->finished = false; P->protect = 0;
 }
 // the images live in the context arena like every other device buffer (no hipMalloc/hipFree — device-wide synchronisation points —
 // between the pairs of other contexts in flight on the same GPU)
@@ -91,13 +93,15 @@ int full_lab::open(nct_ctx* ctx, hipStream_t s, const full_target* full) {
     return nctk_bgr2lab(ctx, s, full->src, s0, N0);
 }
 int finish_level(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int H, int W, const uint8_t* s_lab_full, uint8_t* out_lab, uint8_t* out_bgr,
-                 const full_target* full, const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube) {
+                 const full_target* full, const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube, const region_fin* region) {
     if (full && full->finish == NCT_FINISH_EXACT) {
         NCT_TRY(nctk_color_finish(ctx, s, x, h, w, H, W, fl.s0, full->H, full->W, cp, fl.out0, dbg));
+        if (region) return nctk_region_compose(ctx, s, full->src, fl.s0, fl.out0, full->mask, (size_t)full->H * full->W, region->protect, cube, full->out);
         return nctk_lab2bgr(ctx, s, fl.out0, full->out, (size_t)full->H * full->W, cube);
     }
     const nct_finish_up up{full ? full->src : nullptr, full ? full->H : 0, full ? full->W : 0, full ? full->out : nullptr, cube, ctx->guided_sigma /* nct_set_finish_guided */};
     NCT_TRY(nctk_color_finish(ctx, s, x, h, w, H, W, s_lab_full, H, W, cp, out_lab, dbg, full ? &up : nullptr));
+    if (region) return nctk_region_compose(ctx, s, region->s_bgr, s_lab_full, out_lab, region->mask, (size_t)H * W, region->protect, cube, out_bgr);
     return nctk_lab2bgr(ctx, s, out_lab, out_bgr, (size_t)H * W, cube);
 }
 
@@ -141,6 +145,7 @@ struct pair_run {
     const full_target* const fin;                  // nullable: the last level finishes on the original source (finish_level)
     seq_state* const seq;                          // nullable: this run is a frame of the open sequence (SPEC §6.3) — the reference's pyramid and taps are borrowed, S1's output is blended
     const nct_seq_levels* const slv;               // nullable: where a frame's X'_t and tau_p maps go
+    const nct_region_levels* const rlv;            // nullable: where a masked run's level masks and mixed coefficients go (SPEC §6.11)
     pair_state* const P; const hipStream_t s;
     const int H, W, K, nlevels; const size_t N;
     const bool feat16, count;
@@ -158,11 +163,14 @@ struct pair_run {
     DevBuf<float> annd, err;
     DevBuf<uint8_t> guide, g_lab_l, out_lab;
     DevBuf<uint8_t> sel_label;                     // the selection's label map (rule 2); a pair allocates none of this
+    // the source's region mask (SPEC §6.11; null: none, and the run enqueues and reserves what it always did) and its level masks — the pyramid's single-channel form
+    const uint8_t* const mask;
+    DevBuf<uint8_t> mpyr[4]; const uint8_t* mimg[5] = {};
     const nct_color_params cp;
 
     pair_run(nct_ctx* c, const nct_params* p, nct_pair_timing* t, const run_extras& x)
-        : ctx(c), prm(p), timing(t), lv(x.lv ? x.lv : &kNoLevels), color(x.color), fin(x.fin), seq(x.seq), slv(x.slv), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
-          nlevels(p->levels), N((size_t)H * W), feat16((p->flags & NCT_FLAG_FEAT16) != 0), count(t && (p->flags & NCT_FLAG_COUNT_EVALS)), side(c),
+        : ctx(c), prm(p), timing(t), lv(x.lv ? x.lv : &kNoLevels), color(x.color), fin(x.fin), seq(x.seq), slv(x.slv), rlv(x.rlv), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
+          nlevels(p->levels), N((size_t)H * W), feat16((p->flags & NCT_FLAG_FEAT16) != 0), count(t && (p->flags & NCT_FLAG_COUNT_EVALS)), side(c), mask(x.seq ? nullptr : P->mask),
           cp(nct_color_params_of(*p)) {}
 
     int d2h(void* dst, const void* src, size_t bytes) {
@@ -193,6 +201,15 @@ struct pair_run {
             NCT_TRY(pyramid_level(ctx, s, spyr[l], simg, ah, aw, l));
             if (seq) { R[0].img[l] = seq->rpyr[l]; continue; }          // the sequence's reference pyramid was built at nct_seq_begin
             for (int k = 0; k < K; ++k) NCT_TRY(pyramid_level(ctx, s, R[k].pyr[l], R[k].img, R[k].bh, R[k].bw, l));
+        }
+        if (mask) {
+            // SPEC §6.11 rule 1: the level masks, each resized from the level above like the image pyramid
+            mimg[4] = mask;
+            for (int l = 3; l >= 0; --l) {
+                if (!mpyr[l].alloc(ctx, (size_t)ah[l] * aw[l])) return NCT_ERR_HIP;
+                NCT_TRY(nctk_resize_u8c1(ctx, s, mimg[l + 1], ah[l + 1], aw[l + 1], mpyr[l], ah[l], aw[l]));
+                mimg[l] = mpyr[l];
+            }
         }
         MARK(NCT_ST_OTHER, 0);
         return NCT_OK;
@@ -391,7 +408,13 @@ struct pair_run {
         NCT_TRY(nctk_color_nonlocal(ctx, s, err, side.slab[l], g_lab_l, side.knn_ids[l], side.knn_ws[l], l, ah[l], aw[l], H, W, cp, cb, d, &s1graph));
         // a frame of a sequence: the blend between S1 and the finish, which then reads the kept X'_t (SPEC §6.3 rule 3)
         if (seq) NCT_TRY(seq_level_step(ctx, s, seq, l, side.slab[l], cb.x, cb.tmap, slv));
-        NCT_TRY(finish_level(ctx, s, seq ? seq->keep_x[l] : (double*)cb.x, ah[l], aw[l], H, W, s_lab_full, out_lab, P->out, full, fl, cp, d, nct_cube_form(*prm)));
+        // a masked run (SPEC §6.11 rule 2): S1's coefficients move toward the identity by the level mask, in place; the finish reads X' and composes with the source (rule 3)
+        const region_fin rg{mask, P->src, P->protect};
+        if (mask) {
+            NCT_TRY(nctk_region_mix(ctx, s, cb.x, mimg[l], ah[l], aw[l], cb.x));
+            if (rlv) { NCT_TRY(dbg_copy(ctx, s, rlv->ab_mix[l], (double*)cb.x, (size_t)6 * na_px)); NCT_TRY(dbg_copy(ctx, s, rlv->mask[l], mimg[l], (size_t)na_px)); }
+        }
+        NCT_TRY(finish_level(ctx, s, seq ? seq->keep_x[l] : (double*)cb.x, ah[l], aw[l], H, W, s_lab_full, out_lab, P->out, full, fl, cp, d, nct_cube_form(*prm), mask ? &rg : nullptr));
         if (cs && cs->wls_iters) for (int q = 0; q < 6; ++q) cs->wls_iters[q] = wls_it[q];
         if (timing) timing->wls_iters[l] = *std::max_element(wls_it, wls_it + 6);
         MARK(NCT_ST_COLOR, l);
@@ -440,11 +463,14 @@ int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timin
     NCT_REQUIRE(prm->levels >= 1 && prm->levels <= 5, "process: levels must be in [1, 5] (got %d)", prm->levels);
     NCT_REQUIRE(!x.fin || (!x.lv && !x.color), "process: no level intermediates with a full-resolution finish");
     NCT_REQUIRE(!x.color || P->K == 1, "process: nct_pair_levels describes a pair; several references report through nct_multi_levels");
+    if (x.rlv && !P->mask) return ctx->fail(NCT_ERR_STATE, "process: region levels asked for, but no region mask is set (nct_pair_set_region first)");
+    NCT_REQUIRE(!(P->mask && x.fin) || (x.fin->finish == NCT_FINISH_EXACT && x.fin->mask), "process: a region mask is defined for the exact full-resolution finish only");
     // a new run on the resident images: an earlier full-resolution run is no longer the last one, and its two original-size images go back to the arena
     // (a full-resolution sequence keeps its two for its whole life: SPEC §6.9 rule 6)
     if (!(x.seq && x.seq->target())) {
         if (P->full_src) { ctx->release(P->full_src); P->full_src = nullptr; }
         if (P->full_out) { ctx->release(P->full_out); P->full_out = nullptr; }
+        if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
     }
     P->finished = false;
     run_clock clock(ctx, timing, prm->flags);
@@ -559,6 +585,50 @@ int nct_pair_run_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* ti
     return process_resident(ctx, prm, timing, {&m, levels->color});
 }
 
+// ---- source region masks (SPEC §6.11)
+void nct_region_params_default(nct_region_params* p) {
+    if (!p) return;
+    p->protect = 0;
+}
+
+int nct_pair_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_params* region) {
+    NCT_CTX_ENTER();
+    NCT_NO_OPEN_SEQ("pair_set_region");
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->src || P->sh < 1) return ctx->fail(NCT_ERR_STATE, "pair_set_region: no source uploaded (nct_pair_upload or nct_multi_upload first)");
+    NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "pair_set_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
+    // the images stay; what an earlier run left is no longer the result of these settings
+    P->finished = false;
+    if (!mask) {
+        if (P->mask) { NCT_SYNC(); ctx->release(P->mask); P->mask = nullptr; }
+        P->protect = 0;
+        return NCT_OK;
+    }
+    if (!P->mask && !(P->mask = (uint8_t*)ctx->alloc((size_t)P->sh * P->sw))) return NCT_ERR_HIP;
+    NCT_H2D(P->mask, mask, (size_t)P->sh * P->sw);
+    NCT_SYNC();
+    P->protect = region ? region->protect : 0;
+    return NCT_OK;
+}
+
+int nct_pair_run_region_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_region_levels* region_levels) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(prm, "pair_run_region_levels: null params");
+    if (!levels) return process_resident(ctx, prm, timing, {nullptr, nullptr, nullptr, nullptr, nullptr, region_levels});
+    const nct_multi_levels m = multi_levels_of(*levels);
+    return process_resident(ctx, prm, timing, {&m, levels->color, nullptr, nullptr, nullptr, region_levels});
+}
+
+int nct_process_pair_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* mask, const uint8_t* ref_bgr, int rh, int rw, const nct_region_params* region,
+                            const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
+    if (!ctx) return NCT_ERR_INVALID;
+    NCT_REQUIRE(!mask || !region || region->protect == 0 || region->protect == 1, "process_pair_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
+    NCT_TRY(nct_pair_upload(ctx, src_bgr, sh, sw, ref_bgr, rh, rw));
+    if (mask) NCT_TRY(nct_pair_set_region(ctx, mask, region));
+    NCT_TRY(nct_pair_run(ctx, prm, timing));
+    return nct_pair_download(ctx, out_bgr);
+}
+
 int nct_pair_download(nct_ctx* ctx, uint8_t* out_bgr) {
     NCT_CTX_ENTER();
     pair_state* P = (pair_state*)ctx->pair;
@@ -591,10 +661,23 @@ int nct_process_pair_fullres(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int s
 // is upsampled onto the original source (SPEC §6.8)
 int nct_process_pair_fullres_finish(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw, int max_side, int finish,
                                     const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
+    return nct_process_pair_fullres_finish_region(ctx, src_bgr, sh, sw, nullptr, ref_bgr, rh, rw, max_side, finish, nullptr, prm, out_bgr, timing);
+}
+
+int nct_process_pair_fullres_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* mask0, const uint8_t* ref_bgr, int rh, int rw, int max_side,
+                                    const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
+    return nct_process_pair_fullres_finish_region(ctx, src_bgr, sh, sw, mask0, ref_bgr, rh, rw, max_side, NCT_FINISH_EXACT, region, prm, out_bgr, timing);
+}
+
+// mask0 (nullable: the unmasked run, with its launches and arena requests): the source's region mask at sh x sw (SPEC §6.11 rule 5)
+int nct_process_pair_fullres_finish_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* mask0, const uint8_t* ref_bgr, int rh, int rw, int max_side,
+                                           int finish, const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
     NCT_CTX_ENTER();
     NCT_NO_OPEN_SEQ("process_pair_fullres");
     NCT_REQUIRE(src_bgr && ref_bgr && prm && out_bgr, "process_pair_fullres: null pointer");
     NCT_REQUIRE(finish == NCT_FINISH_EXACT || finish == NCT_FINISH_UPSAMPLE, "process_pair_fullres: finish must be NCT_FINISH_EXACT (0) or NCT_FINISH_UPSAMPLE (1) (got %d)", finish);
+    NCT_REQUIRE(!mask0 || finish == NCT_FINISH_EXACT, "process_pair_fullres: a region mask with NCT_FINISH_UPSAMPLE is not defined (SPEC 6.11 rule 8): use NCT_FINISH_EXACT");
+    NCT_REQUIRE(!mask0 || !region || region->protect == 0 || region->protect == 1, "process_pair_fullres: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
     int wh = 0, ww = 0, rwh = 0, rww = 0;
     const char* why = nct_working_size_rule(sh, sw, max_side, &wh, &ww);
     if (why) return ctx->fail(NCT_ERR_INVALID, "process_pair_fullres: source %dx%d: %s", sw, sh, why);
@@ -612,6 +695,14 @@ int nct_process_pair_fullres_finish(nct_ctx* ctx, const uint8_t* src_bgr, int sh
     P->sh = P->sw = P->rh[0] = P->rw[0] = 0;
     NCT_TRY(upload_shrunk(ctx, src_bgr, sh, sw, P->src, wh, ww, s0));
     NCT_TRY(upload_shrunk(ctx, ref_bgr, rh, rw, P->ref[0], rwh, rww));
+    DevBuf<uint8_t> m0;
+    if (mask0) {
+        // rule 5: the mask arrives at the original size; the working mask is its single-channel resize (equal sizes: a copy)
+        if (!m0.alloc(ctx, (size_t)sh * sw) || !(P->mask = (uint8_t*)ctx->alloc((size_t)wh * ww))) return NCT_ERR_HIP;
+        NCT_H2D(m0, mask0, (size_t)sh * sw);
+        NCT_TRY(nctk_resize_u8c1(ctx, ctx->stream, m0, sh, sw, P->mask, wh, ww));
+        P->protect = region ? region->protect : 0;
+    }
     NCT_SYNC();
     P->sh = wh; P->sw = ww; P->rh[0] = rwh; P->rw[0] = rww; P->K = 1;
     if (!shrunk) {
@@ -621,7 +712,7 @@ int nct_process_pair_fullres_finish(nct_ctx* ctx, const uint8_t* src_bgr, int sh
     }
     DevBuf<uint8_t> o0(ctx, (size_t)sh * sw * 3);
     if (!o0.ok()) return NCT_ERR_HIP;
-    const full_target fin{s0, sh, sw, o0, finish};
+    const full_target fin{s0, sh, sw, o0, finish, m0};
     const int rc = process_resident(ctx, prm, timing, {nullptr, nullptr, &fin});
     // the working-size result buffer holds the second-to-last level's image (the upsampling finish: the working-size result, which nobody asked for): no nct_pair_download of it
     if (P->out) { ctx->release(P->out); P->out = nullptr; }
@@ -629,6 +720,7 @@ int nct_process_pair_fullres_finish(nct_ctx* ctx, const uint8_t* src_bgr, int sh
     NCT_D2H(out_bgr, o0, (size_t)sh * sw * 3);
     NCT_SYNC();
     P->full_src = s0.detach(); P->full_out = o0.detach(); P->full_h = sh; P->full_w = sw;
+    if (mask0) P->full_mask = m0.detach();
     return NCT_OK;
 }
 
@@ -636,16 +728,18 @@ int nct_process_pair_fullres_finish(nct_ctx* ctx, const uint8_t* src_bgr, int sh
 int nct_pair_fit_lut(nct_ctx* ctx, const nct_lut_params* prm, float* lut_out) {
     NCT_CTX_ENTER();
     pair_state* P = (pair_state*)ctx->pair;
-    const uint8_t *src = nullptr, *res = nullptr; size_t npix = 0;
+    const uint8_t *src = nullptr, *res = nullptr, *mask = nullptr; size_t npix = 0;
     if (P && !P->finished) P = nullptr;
-    if (P && P->full_src && P->full_out) { src = P->full_src; res = P->full_out; npix = (size_t)P->full_h * P->full_w; }
-    else if (P && P->src && P->out && P->sh > 0) { src = P->src; res = P->out; npix = (size_t)P->sh * P->sw; }
+    // a masked run's table is fitted over its region (SPEC §6.11 rule 7), with the mask at the size of the images it reads
+    if (P && P->full_src && P->full_out) { src = P->full_src; res = P->full_out; mask = P->full_mask; npix = (size_t)P->full_h * P->full_w; }
+    else if (P && P->src && P->out && P->sh > 0) { src = P->src; res = P->out; mask = P->seq ? nullptr : P->mask; npix = (size_t)P->sh * P->sw; }
     if (!src) return ctx->fail(NCT_ERR_STATE, "pair_fit_lut: no finished run on this context (nct_pair_run first)");
     NCT_TRY(nct_lut_fit_check(ctx, "pair_fit_lut", src, res, npix, prm, lut_out));
     const size_t n = (size_t)prm->size * prm->size * prm->size * 3;
     DevBuf<float> dl(ctx, n);
     if (!dl.ok()) return NCT_ERR_HIP;
-    NCT_TRY(nct_lut_fit_enqueue(ctx, src, res, npix, prm, dl, nullptr));
+    if (mask) NCT_TRY(nct_lut_fit_enqueue_masked(ctx, "pair_fit_lut", src, res, mask, npix, prm, dl, nullptr));
+    else NCT_TRY(nct_lut_fit_enqueue(ctx, src, res, npix, prm, dl, nullptr));
     NCT_D2H(lut_out, dl, sizeof(float) * n);
     NCT_SYNC();
     return NCT_OK;

@@ -4,7 +4,8 @@
 #include <chrono>
 // the last level's finish on a source larger than the working size (SPEC §6.1, §6.9): the original source on the device, H x W, where its result goes, and the finish —
 // NCT_FINISH_EXACT moves U1 / S2 / A1 there, NCT_FINISH_UPSAMPLE leaves them at the working size and upsamples S2's output (SPEC §6.8)
-struct full_target { const uint8_t* src = nullptr; int H = 0, W = 0; uint8_t* out = nullptr; int finish = NCT_FINISH_EXACT; };
+// mask (nullable; the exact finish only): the source's region mask at H x W (SPEC §6.11 rule 5), on the device
+struct full_target { const uint8_t* src = nullptr; int H = 0, W = 0; uint8_t* out = nullptr; int finish = NCT_FINISH_EXACT; const uint8_t* mask = nullptr; };
 
 // An open frame sequence (SPEC §6.3): what nct_seq_begin prepares once and every frame borrows — the reference's pyramid and its five un-normalised taps (HWC, by
 // level) — and the state the blend carries from frame to frame, per level X' ([2][h*w][3] doubles) and L (the frame's level image in 8-bit Lab). All of it comes from
@@ -36,6 +37,8 @@ struct pair_state {
     int sh = 0, sw = 0, rh[NCT_MAX_REFS] = {}, rw[NCT_MAX_REFS] = {};
     uint8_t *full_src = nullptr, *full_out = nullptr;          // a finished full-resolution run (SPEC §6.1): the original source and its result, full_h x full_w, kept for nct_pair_fit_lut
     int full_h = 0, full_w = 0;
+    uint8_t *mask = nullptr, *full_mask = nullptr;             // the source's region mask (SPEC §6.11): sh x sw bytes, set by nct_pair_set_region, dropped with the images; after a masked
+    int protect = 0;                                           // full-resolution run also the mask at full_h x full_w, beside full_src / full_out. protect: nct_region_params
     bool finished = false;                                     // the last run on these images ran to its end: `out` (or full_out) holds its result
 };
 
@@ -47,7 +50,8 @@ NCT_LOCAL pair_state* pair_of(nct_ctx* ctx);
 NCT_LOCAL void drop_images(nct_ctx* ctx, pair_state* P);    // drop what the context holds of the last pair / reference list
 // what a run is asked for beside its result, every member nullable. lv: host copies of the level intermediates; color (a pair only): [5] the colour stage's coefficient
 // maps per level; fin (K = 1 only): the full-resolution finish; seq: the run is a frame of this open sequence, slv: where that frame's X'_t, tau_p and fields go
-struct run_extras { const nct_multi_levels* lv; const nct_color_stages* const* color; const full_target* fin; seq_state* seq; const nct_seq_levels* slv; };
+// rlv: where a masked run's level masks and mixed coefficients go (SPEC §6.11)
+struct run_extras { const nct_multi_levels* lv; const nct_color_stages* const* color; const full_target* fin; seq_state* seq; const nct_seq_levels* slv; const nct_region_levels* rlv; };
 // run the whole L=5->1 loop on the uploaded source and its K references
 NCT_LOCAL int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const run_extras& x = {});
 // a pair is the list of one reference (SPEC §6.2): its maps are reference 0's NNFs and the merged guide / err; it has no label map and no G_k / E_k of their own
@@ -88,8 +92,11 @@ struct NCT_LOCAL full_lab {
 // The finish of a level: U1 / S2 / A1 of x ([2][h*w][3], the level grid) and the result in BGR. full == null (every level but a full-resolution run's last): onto the
 // working grid H x W, s_lab_full -> out_lab -> out_bgr. The exact finish: onto the original source through fl's images into full->out; out_lab and out_bgr stay as they
 // are. The upsampling finish (SPEC §6.8): the working-size finish, and behind it S2's output upsampled onto the original source into full->out
+// region (nullable; SPEC §6.11 rule 3): the run is masked — the compose with the source takes the place of Lab -> BGR, at the working size with region's mask and source, in
+// the exact finish with full's
+struct region_fin { const uint8_t* mask; const uint8_t* s_bgr; int protect; };
 NCT_LOCAL int finish_level(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int H, int W, const uint8_t* s_lab_full, uint8_t* out_lab, uint8_t* out_bgr,
-                           const full_target* full, const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube);
+                           const full_target* full, const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube, const region_fin* region = nullptr);
 // ---- nct_seq.cpp
 NCT_LOCAL void seq_free(nct_ctx* ctx, pair_state* P);       // what an open sequence holds goes back to the arena
 // SPEC §6.4: level l's field from L_t (`lab`) and the kept packed map: the first level run searches radius0 around (0, 0), every other level radius around twice the

@@ -138,6 +138,21 @@ SIGNATURES = {
     "nct_lut_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "nct_lut_apply_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "nct_pair_fit_lut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_region_params_default": (None, [C.c_void_p]),
+    "nct_resize_u8c1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "nct_resize_u8c1_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "nct_region_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "nct_region_mix_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "nct_region_compose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_region_compose_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_pair_set_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_pair_run_region_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_process_pair_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_process_pair_fullres_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_process_pair_fullres_finish_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p]),
+    "nct_lut_fit_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_lut_fit_masked_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "nct_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nct_dev_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -309,6 +324,37 @@ def _guided_params(sigma):
     if sigma is not None:
         p.sigma = float(sigma)
     return p
+
+
+class RegionParams(C.Structure):
+    """struct nct_region_params (include/nct.h)."""
+    _fields_ = [("protect", C.c_int)]
+
+    @staticmethod
+    def default():
+        p = RegionParams()
+        lib().nct_region_params_default(C.byref(p))
+        return p
+
+
+class RegionLevels(C.Structure):
+    """struct nct_region_levels (include/nct.h)."""
+    _fields_ = [("ab_mix", C.c_void_p * 5), ("mask", C.c_void_p * 5)]
+
+
+def _region_params(protect):
+    p = RegionParams.default()
+    if protect is not None:
+        p.protect = int(protect)
+    return p
+
+
+def _mask_arg(mask, shape, what):
+    """a region mask as contiguous bytes of the source's h x w; a mask of another size is refused here: the C entry points take the source's size for it"""
+    m = np.ascontiguousarray(mask, np.uint8)
+    if m.shape != tuple(shape[:2]):
+        raise NctError(-2, f"{what}: mask is {m.shape[1] if m.ndim == 2 else '?'}x{m.shape[0] if m.ndim else '?'}, the source {shape[1]}x{shape[0]}")
+    return m
 
 
 class SeqParams(C.Structure):
@@ -1249,10 +1295,8 @@ class Context:
         self._chk(self._l.nct_pair_run(self._h, C.addressof(prm), C.addressof(tm) if tm is not None else None))
         return tm.as_dict() if want_timing else None
 
-    def pair_run_levels(self, src_shape, ref_shape, params=None, want_color=False):
-        """nct_pair_run_levels on the uploaded pair -> dict of per-level intermediates (lists indexed by level, 0 = coarsest).
-        want_color adds "color" (per level the dict of coefficient maps local_color_transfer(want_stages=True) returns) and "labels"."""
-        prm = params or Params.default()
+    def _pair_levels_arrays(self, src_shape, ref_shape, prm, want_color):
+        """the host arrays nct_pair_levels points into -> (dict of them + "dims", the PairLevels, what must stay alive until the call returns)"""
         H, W = src_shape[:2]; RH, RW = ref_shape[:2]
         dims = []
         h, w, h2, w2 = H, W, RH, RW
@@ -1268,8 +1312,9 @@ class Context:
         lv = PairLevels()
         for k in keep:
             setattr(lv, k, (C.c_void_p * 5)(*[a.ctypes.data for a in keep[k]]))
+        structs = []
         if want_color:
-            color, structs = [], []
+            color = []
             for (ah, aw, _, _) in dims:
                 d = {"ab_local": np.empty((2, ah * aw, 3)), "ab_nonlocal": np.empty((2, ah * aw, 3)), "ab_up": np.empty((2, H * W, 3)),
                      "roughness": np.empty(H * W), "ab_wls": np.empty((2, H * W, 3)), "cg_iters": np.zeros(3, np.int32), "wls_iters": np.zeros(6, np.int32)}
@@ -1278,13 +1323,175 @@ class Context:
             lv.color = (C.c_void_p * 5)(*[C.addressof(st) if i < prm.levels else None for i, st in enumerate(structs)])
             labels = np.zeros(dims[0][:2], np.int32)
             lv.labels = labels.ctypes.data
+            keep["color"] = color; keep["labels"] = labels
+        keep["dims"] = dims
+        return keep, lv, structs
+
+    def pair_run_levels(self, src_shape, ref_shape, params=None, want_color=False):
+        """nct_pair_run_levels on the uploaded pair -> dict of per-level intermediates (lists indexed by level, 0 = coarsest).
+        want_color adds "color" (per level the dict of coefficient maps local_color_transfer(want_stages=True) returns) and "labels"."""
+        prm = params or Params.default()
+        keep, lv, hold = self._pair_levels_arrays(src_shape, ref_shape, prm, want_color)
         tm = PairTiming()
         self._chk(self._l.nct_pair_run_levels(self._h, C.addressof(prm), C.addressof(tm), C.addressof(lv)))
-        if want_color:
-            keep["color"] = color; keep["labels"] = labels
         keep["timing"] = tm.as_dict()
-        keep["dims"] = dims
         return keep
+
+    # ---- source region masks (SPEC §6.11)
+    def resize_u8c1(self, img, dh, dw):
+        """nct_resize_u8c1: one-channel uint8 image [h, w] -> [dh, dw]"""
+        a = np.ascontiguousarray(img, np.uint8)
+        out = np.empty((dh, dw), np.uint8)
+        self._chk(self._l.nct_resize_u8c1(self._h, a.ctypes.data, a.shape[0], a.shape[1], out.ctypes.data, dh, dw))
+        return out
+
+    def resize_u8c1_dev(self, img, dh, dw):
+        """the same through nct_resize_u8c1_dev on arena blocks"""
+        a = np.ascontiguousarray(img, np.uint8)
+        blocks = [self.dev_upload(a), self.dev_alloc(dh * dw)]
+        try:
+            self._chk(self._l.nct_resize_u8c1_dev(self._h, blocks[0], a.shape[0], a.shape[1], blocks[1], dh, dw))
+            return self.dev_download(blocks[1], (dh, dw), np.uint8)
+        finally:
+            self.synchronize()
+            for p in blocks:
+                self.dev_free(p)
+
+    def region_mix(self, x, mask):
+        """nct_region_mix (SPEC §6.11 rule 2): x [2, h*w, 3] doubles, mask [h, w] bytes -> X'"""
+        m = np.ascontiguousarray(mask, np.uint8)
+        h, w = m.shape
+        a = np.ascontiguousarray(x, np.float64).reshape(-1)
+        assert a.size == 6 * h * w
+        out = np.empty((2, h * w, 3))
+        self._chk(self._l.nct_region_mix(self._h, a.ctypes.data, m.ctypes.data, h, w, out.ctypes.data))
+        return out
+
+    def region_mix_dev(self, x, mask, in_place=False):
+        """the same through nct_region_mix_dev on arena blocks, into a block of its own (in_place: over x)"""
+        m = np.ascontiguousarray(mask, np.uint8)
+        h, w = m.shape
+        a = np.ascontiguousarray(x, np.float64).reshape(-1)
+        assert a.size == 6 * h * w
+        blocks = [self.dev_upload(a), self.dev_upload(m), self.dev_alloc(48 * h * w)]
+        try:
+            dst = blocks[0] if in_place else blocks[2]
+            self._chk(self._l.nct_region_mix_dev(self._h, blocks[0], blocks[1], h, w, dst))
+            return self.dev_download(dst, (2, h * w, 3), np.float64)
+        finally:
+            self.synchronize()
+            for p in blocks:
+                self.dev_free(p)
+
+    def region_compose(self, s_bgr, lab_out, mask, protect=None, params=None):
+        """nct_region_compose (SPEC §6.11 rule 3): the source, a finish's 8-bit Lab result and the mask at that size -> the composed BGR image"""
+        s = np.ascontiguousarray(s_bgr, np.uint8)
+        lo, m = np.ascontiguousarray(lab_out, np.uint8), np.ascontiguousarray(mask, np.uint8)
+        assert lo.size == s.size and m.size * 3 == s.size
+        prm, rg = params or Params.default(), _region_params(protect)
+        out = np.empty_like(s)
+        self._chk(self._l.nct_region_compose(self._h, s.ctypes.data, lo.ctypes.data, m.ctypes.data, m.size, C.addressof(rg), C.addressof(prm), out.ctypes.data))
+        return out
+
+    def region_compose_dev(self, s_bgr, lab_out, mask, protect=None, params=None):
+        """the same through nct_region_compose_dev on arena blocks"""
+        s = np.ascontiguousarray(s_bgr, np.uint8)
+        lo, m = np.ascontiguousarray(lab_out, np.uint8), np.ascontiguousarray(mask, np.uint8)
+        assert lo.size == s.size and m.size * 3 == s.size
+        prm, rg = params or Params.default(), _region_params(protect)
+        blocks = [self.dev_upload(s), self.dev_upload(lo), self.dev_upload(m), self.dev_alloc(s.size)]
+        try:
+            self._chk(self._l.nct_region_compose_dev(self._h, blocks[0], blocks[1], blocks[2], m.size, C.addressof(rg), C.addressof(prm), blocks[3]))
+            return self.dev_download(blocks[3], s.shape, np.uint8)
+        finally:
+            self.synchronize()
+            for p in blocks:
+                self.dev_free(p)
+
+    def pair_set_region(self, mask, protect=None):
+        """nct_pair_set_region on the uploaded source: mask [h, w] bytes, or None to remove it"""
+        if mask is None:
+            self._chk(self._l.nct_pair_set_region(self._h, None, None))
+            return
+        m = _mask_arg(mask, self._pair_shape, "pair_set_region")
+        rg = _region_params(protect)
+        self._chk(self._l.nct_pair_set_region(self._h, m.ctypes.data, C.addressof(rg)))
+
+    def pair_run_region_levels(self, src_shape, ref_shape, params=None, want_color=True):
+        """nct_pair_run_region_levels on the uploaded, masked pair -> pair_run_levels' dict plus per level "mask" [h, w] and "ab_mix" [2, h*w, 3]"""
+        prm = params or Params.default()
+        keep, lv, hold = self._pair_levels_arrays(src_shape, ref_shape, prm, want_color)
+        rl = RegionLevels()
+        keep["mask"], keep["ab_mix"] = [], []
+        for l, (ah, aw, _, _) in enumerate(keep["dims"]):
+            keep["mask"].append(np.zeros((ah, aw), np.uint8)); keep["ab_mix"].append(np.zeros((2, ah * aw, 3)))
+            rl.mask[l] = keep["mask"][-1].ctypes.data; rl.ab_mix[l] = keep["ab_mix"][-1].ctypes.data
+        tm = PairTiming()
+        self._chk(self._l.nct_pair_run_region_levels(self._h, C.addressof(prm), C.addressof(tm), C.addressof(lv), C.addressof(rl)))
+        keep["timing"] = tm.as_dict()
+        return keep
+
+    def process_pair_region(self, src_bgr, mask, ref_bgr, protect=None, params=None, want_timing=False):
+        """nct_process_pair_region: process_pair recolouring only where mask ([h, w] bytes of the source; None: process_pair) says so"""
+        s = np.ascontiguousarray(src_bgr, np.uint8)
+        r = np.ascontiguousarray(ref_bgr, np.uint8)
+        m = None if mask is None else _mask_arg(mask, s.shape, "process_pair_region")
+        prm, rg = params or Params.default(), _region_params(protect)
+        out = np.empty_like(s)
+        tm = PairTiming() if want_timing else None
+        self._chk(self._l.nct_process_pair_region(self._h, s.ctypes.data if s.size else None, s.shape[0], s.shape[1], _ptr(m), r.ctypes.data, r.shape[0], r.shape[1], C.addressof(rg),
+                                                  C.addressof(prm), out.ctypes.data, C.addressof(tm) if tm is not None else None))
+        return (out, tm.as_dict()) if want_timing else out
+
+    def process_pair_fullres_region(self, src_bgr, mask0, ref_bgr, max_side=1000, protect=None, params=None, want_timing=False, finish=0):
+        """nct_process_pair_fullres_region (SPEC §6.11 rule 5): mask0 at the source's original size; finish other than FINISH_EXACT goes through
+        nct_process_pair_fullres_finish_region (which refuses FINISH_UPSAMPLE with a mask)"""
+        s = np.ascontiguousarray(src_bgr, np.uint8)
+        r = np.ascontiguousarray(ref_bgr, np.uint8)
+        m = None if mask0 is None else _mask_arg(mask0, s.shape, "process_pair_fullres_region")
+        prm, rg = params or Params.default(), _region_params(protect)
+        out = np.empty_like(s)
+        tm = PairTiming() if want_timing else None
+        if finish == FINISH_EXACT:
+            self._chk(self._l.nct_process_pair_fullres_region(self._h, s.ctypes.data, s.shape[0], s.shape[1], _ptr(m), r.ctypes.data, r.shape[0], r.shape[1], max_side, C.addressof(rg),
+                                                              C.addressof(prm), out.ctypes.data, C.addressof(tm) if tm is not None else None))
+        else:
+            self._chk(self._l.nct_process_pair_fullres_finish_region(self._h, s.ctypes.data, s.shape[0], s.shape[1], _ptr(m), r.ctypes.data, r.shape[0], r.shape[1], max_side, int(finish),
+                                                                     C.addressof(rg), C.addressof(prm), out.ctypes.data, C.addressof(tm) if tm is not None else None))
+        return (out, tm.as_dict()) if want_timing else out
+
+    def lut_fit_masked(self, src, res, mask, size=None, lam=None, want_stages=False):
+        """nct_lut_fit_masked (SPEC §6.11 rule 7): lut_fit over the pixels with mask >= 128 (mask None: lut_fit)"""
+        s, r = np.ascontiguousarray(src, np.uint8).reshape(-1, 3), np.ascontiguousarray(res, np.uint8).reshape(-1, 3)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        assert s.shape == r.shape and (m is None or len(m) == len(s))
+        prm = _lut_params(size, lam)
+        N = prm.size if 0 < prm.size <= 65 else 1
+        lut = np.empty((N, N, N, 3), np.float32)
+        st = {"weight": np.empty(N ** 3, np.uint64), "resid": np.empty((N ** 3, 3), np.int64), "disp": np.empty((N ** 3, 3), np.float64)}
+        cs = LutStages(*(st[k].ctypes.data for k in ("weight", "resid", "disp")))
+        self._chk(self._l.nct_lut_fit_masked(self._h, s.ctypes.data, r.ctypes.data, _ptr(m), len(s), C.addressof(prm), lut.ctypes.data, C.addressof(cs) if want_stages else None))
+        return (lut, st) if want_stages else lut
+
+    def lut_fit_masked_dev(self, src, res, mask, size=None, lam=None, want_stages=False):
+        """the same through nct_lut_fit_masked_dev on arena blocks"""
+        s, r = np.ascontiguousarray(src, np.uint8).reshape(-1, 3), np.ascontiguousarray(res, np.uint8).reshape(-1, 3)
+        m = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        prm = _lut_params(size, lam)
+        n3 = prm.size ** 3
+        blocks = [self.dev_upload(s), self.dev_upload(r), self.dev_alloc(12 * n3), self.dev_alloc(8 * n3), self.dev_alloc(24 * n3), self.dev_alloc(24 * n3), self.dev_upload(m)]
+        try:
+            cs = LutStages(blocks[3], blocks[4], blocks[5])
+            self._chk(self._l.nct_lut_fit_masked_dev(self._h, blocks[0], blocks[1], blocks[6], len(s), C.addressof(prm), blocks[2], C.addressof(cs) if want_stages else None))
+            lut = self.dev_download(blocks[2], (prm.size,) * 3 + (3,), np.float32)
+            if not want_stages:
+                return lut
+            return lut, {"weight": self.dev_download(blocks[3], (n3,), np.uint64), "resid": self.dev_download(blocks[4], (n3, 3), np.int64),
+                         "disp": self.dev_download(blocks[5], (n3, 3), np.float64)}
+        finally:
+            self.synchronize()
+            for p in blocks:
+                self.dev_free(p)
 
     def pair_download(self):
         out = np.empty(self._pair_shape, np.uint8)
