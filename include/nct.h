@@ -31,7 +31,8 @@ extern "C" {
  * nct_conv3x3_pair_dev; 116 — 3D colour look-up tables, nct_lut_*; 117 — adaptive key frames, nct_seq_change, nct_seq_probe and nct_seq_frame_auto; 118 — the upsampling finish and
  * full-resolution sequences, nct_color_finish_upsample, nct_process_pair_fullres_finish and nct_seq_begin_fullres; still 118 with the guided finish, nct_color_finish_guided[_dev], nct_set_finish_guided and nct_guided_params: no struct
  * changed layout and no existing entry point changed meaning, entry points were only added; likewise still 118 with source region masks, nct_region_*, nct_pair_set_region,
- * nct_process_pair_region and nct_lut_fit_masked). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
+ * nct_process_pair_region and nct_lut_fit_masked, and with reference region masks, nct_region_pull[_dev], nct_pair_set_ref_region, nct_multi_run_ref_region_levels and
+ * nct_process_*_ref_region). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
 #define NCT_VERSION 118
 
@@ -498,7 +499,7 @@ int nct_pair_fit_lut(nct_ctx* ctx, const nct_lut_params* prm, float* lut_out);
  * not defined and refused with NCT_ERR_INVALID. mask0 NULL: nct_process_pair_fullres_finish.
  * nct_lut_fit_masked[_dev]: nct_lut_fit whose splat skips the pixels with mask < 128 — the fit of the subsequence of kept pixels; mask NULL: nct_lut_fit. A mask that
  * keeps no pixel: NCT_ERR_INVALID. The masked _dev form waits for its splat (it has to learn whether a pixel was kept) before it enqueues the solve.
- * A mask on the REFERENCE ("take colours only from the sky") is not part of this: it needs masked BDS votes, a new canonical vote order. */
+ * A mask on the REFERENCE ("take colours only from the sky"): the next block (SPEC §6.12). */
 typedef struct nct_region_params { int protect; } nct_region_params;
 void nct_region_params_default(nct_region_params* p);     /* protect 0 */
 typedef struct nct_region_levels { double* ab_mix[5]; uint8_t* mask[5]; } nct_region_levels;   /* X' [2][h*w][3]; M_l [h*w]; all nullable */
@@ -522,6 +523,52 @@ int nct_lut_fit_masked(nct_ctx* ctx, const uint8_t* src_bgr, const uint8_t* res_
                        nct_lut_stages* stages);
 int nct_lut_fit_masked_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, const uint8_t* d_res_bgr, const uint8_t* d_mask, size_t npix, const nct_lut_params* prm, float* d_lut_out,
                            nct_lut_stages* d_stages);
+
+/* ---- reference region masks (SPEC §6.12; an extension): take colours from part of the reference. A mask Q_k has one byte per pixel of REFERENCE k: 0 = excluded,
+ * 255 = allowed, between = partial. The votes are not masked — the mask is voted: Q_k's pyramid (Q_k,top = Q_k, Q_k,l = nct_resize_u8c1 of Q_k,(l+1) onto the
+ * reference's level grid) is carried to the source through the level's NNFs by B1's taps, bounds tests and source lists, P_k,l(p) = (uint8) rint((A wa + B wb) /
+ * (ca wa + cb wb)) in double (A, ca: coherence sum and count over the nine taps of ann; B, cb: completeness sum and count over bnn's sources; wa = w_coherence / (ah aw),
+ * wb = w_complete / (bh bw)): nct_bds_vote_image on one channel, rounded to nearest where that truncates, so that Q == 255 gives exactly 255 and Q == 0 exactly 0. With
+ * several references P_l(p) = P_label(p),l(p) (a reference without a mask: 255). The level mask M_l = min(P_l, the source's level mask of §6.11 or 255) drives §6.11's
+ * mix; the target mask F_l = nct_resize_u8c1(P_l -> the size the level's finish targets), then the minimum with the source mask at that size, drives §6.11's compose with
+ * the run's protect. A source pixel whose correspondences land in the excluded part keeps its colours; it is not forced onto the allowed part, and where P is partial the
+ * guidance colour is still B1's vote over allowed and excluded pixels alike: only the strength of the transfer follows the mask. No reference mask: today's bytes, launches
+ * and arena. Every Q_k == 255: nct_process_pair's / nct_process_multi's bytes (with a source mask: nct_process_pair_region's). K = 1 and Q == 0: the source, byte for byte.
+ * nct_region_pull: the pull alone on host pointers, synchronous (q_mask bh x bw, ann ah x aw words, bnn bh x bw words, out ah x aw bytes; grid sides 1 … 4096; a null
+ * pointer or a side out of range: NCT_ERR_INVALID, the message names the argument); nct_region_pull_dev: device pointers, enqueued on the context's stream.
+ * nct_pair_set_ref_region: after nct_pair_upload / nct_multi_upload, copies reference k's mask (rh[k] x rw[k] of the uploaded reference); nct_pair_run, nct_multi_run and
+ * their _levels forms then run masked, nct_pair_fit_lut fits over the pixels whose last level's F is >= 128. mask NULL removes reference k's; the next upload drops all.
+ * k outside [0, K) or protect outside {0, 1}: NCT_ERR_INVALID; no upload, or an open sequence: NCT_ERR_STATE (sequences with a mask are not defined). region non-NULL
+ * sets the run's protect — the last setter called decides it, nct_pair_set_region or this one; region NULL leaves it.
+ * nct_multi_run_ref_region_levels: nct_multi_run_levels (levels nullable) plus per level Q_k,l [bh*bw], P_k,l [h*w] (masked references only), M_l [h*w], F_l [H*W] and X'
+ * [2][h*w][3]; with no reference mask set: NCT_ERR_STATE. nct_pair_run_ref_region_levels: the same for a pair, beside nct_pair_run_levels' maps (the colour stages included).
+ * Scratch: while a pull runs it holds 144 bytes per REFERENCE pixel of the level from the context's arena (two arrays of nine 64-bit words, plus the scan's own and the
+ * inverse map's 20): 70 MB at 700 x 700, 2.3 GB at 4000 x 4000, 2.4 GB at nct_region_pull's largest grid; a device that cannot give it answers NCT_ERR_HIP. The pull and the merge count in nct_pair_timing.vote_ms / vote_level_ms, the mix in color_ms.
+ * nct_process_pair_ref_region = upload + nct_pair_set_region (src_mask non-NULL) + nct_pair_set_ref_region (ref_mask non-NULL) + run + download; both NULL:
+ * nct_process_pair. nct_process_multi_ref_region: the same for K references, ref_masks and each of its K entries nullable. nct_process_pair_fullres_ref_region: both masks
+ * at the ORIGINAL sizes, shrunk with their images by nct_resize_u8c1; the exact finish only: the last level resizes its P to sh x sw, takes the minimum with mask0 where
+ * set and composes on the original; a source that is not shrunk gives nct_process_pair_ref_region's bytes. No entry point takes a reference mask and the upsampling finish.
+ * Restricting PatchMatch's candidates to the allowed region is a different feature and not part of this. */
+typedef struct nct_ref_region_levels {
+    uint8_t* ref_mask[NCT_MAX_REFS][5];    /* Q_k,l */
+    uint8_t* pulled[NCT_MAX_REFS][5];      /* P_k,l */
+    uint8_t* mask[5];                      /* M_l */
+    uint8_t* mask_full[5];                 /* F_l */
+    double* ab_mix[5];                     /* X' */
+} nct_ref_region_levels;                   /* all nullable */
+int nct_region_pull(nct_ctx* ctx, const uint8_t* q_mask, int bh, int bw, const uint32_t* ann, const uint32_t* bnn, int ah, int aw, double w_coherence, double w_complete,
+                    uint8_t* out);
+int nct_region_pull_dev(nct_ctx* ctx, const uint8_t* d_q_mask, int bh, int bw, const uint32_t* d_ann, const uint32_t* d_bnn, int ah, int aw, double w_coherence,
+                        double w_complete, uint8_t* d_out);
+int nct_pair_set_ref_region(nct_ctx* ctx, int k, const uint8_t* mask, const nct_region_params* region);
+int nct_multi_run_ref_region_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_multi_levels* levels, const nct_ref_region_levels* region_levels);
+int nct_pair_run_ref_region_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_ref_region_levels* region_levels);
+int nct_process_pair_ref_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* src_mask, const uint8_t* ref_bgr, int rh, int rw, const uint8_t* ref_mask,
+                                const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing);
+int nct_process_multi_ref_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* src_mask, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw,
+                                 const uint8_t* const* ref_masks, const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing);
+int nct_process_pair_fullres_ref_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* mask0, const uint8_t* ref_bgr, int rh, int rw, const uint8_t* ref_mask0,
+                                        int max_side, const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr /* sh x sw x 3 */, nct_pair_timing* timing);
 
 /* ---- device-pointer seams: the same operations on buffers that stay in HBM between calls (main.cu:204-316 keeps Ndata_C1, ann_device, ... on the device
  * across these kernels; an integrator replacing single seams should not pay H2D + D2H + a synchronise per call). Buffers come from the context's arena

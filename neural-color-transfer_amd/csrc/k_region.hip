@@ -99,3 +99,48 @@ int nctk_region_compose(nct_ctx* ctx, hipStream_t s, const uint8_t* s_bgr, const
     NCT_LAUNCH_CHECK();
     return 0;
 }
+
+// ---- reference region masks (SPEC §6.12): what stands between the pulled masks P_k,l (k_vote.hip: k_pull_vote) and the mix and compose above. Streams, one thread per pixel.
+// rules 3 and 4: P_l(p) = P_label(p),l(p) (a reference without a mask counts as 255; label null: reference 0) into p_out, and the level mask M_l = min(P_l, Ms_l)
+// into m_out — one launch for both; either output nullable, ms null = 255
+struct region_pulled { const uint8_t* p[NCT_MAX_REFS]; };
+__global__ void k_region_merge(region_pulled pk, const uint8_t* __restrict__ label, const uint8_t* __restrict__ ms, int n, uint8_t* __restrict__ p_out, uint8_t* __restrict__ m_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int k = label ? min((int)label[i], NCT_MAX_REFS - 1) : 0;
+    const uint8_t* src = pk.p[0];
+#pragma unroll
+    for (int j = 1; j < NCT_MAX_REFS; ++j) src = j == k ? pk.p[j] : src;
+    const int v = src ? src[i] : 255;
+    if (p_out) p_out[i] = (uint8_t)v;
+    if (m_out) m_out[i] = (uint8_t)min(v, ms ? (int)ms[i] : 255);
+}
+
+int nctk_region_merge(nct_ctx* ctx, hipStream_t s, const uint8_t* const* pulled, int K, const uint8_t* label, const uint8_t* ms, int n, uint8_t* p_out, uint8_t* m_out) {
+    region_pulled pk{};
+    for (int k = 0; k < K; ++k) pk.p[k] = pulled[k];
+    hipLaunchKernelGGL(k_region_merge, dim3(cdiv(n, 256)), dim3(256), 0, s, pk, K > 1 ? label : nullptr, ms, n, p_out, m_out);
+    NCT_LAUNCH_CHECK();
+    return 0;
+}
+
+// rule 5: F_l = nct_resize_u8c1(P_l -> dh x dw), then the minimum with the source mask at that size (mn nullable). The target is never smaller than the level
+// grid, so the 2x area case of k_resize_u8c1 cannot occur: the fixed-point bilinear chain, or — equal sizes — the byte itself
+__global__ void k_region_upsize_min(const uint8_t* __restrict__ src, int sh, int sw, const uint8_t* __restrict__ mn, uint8_t* __restrict__ dst, int dh, int dw) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)dh * dw) return;
+    int v;
+    if (sh == dh && sw == dw) v = src[i];
+    else {
+        const int dy = (int)(i / dw), dx = (int)(i - (size_t)dy * dw);
+        v = resize_u8_px(src, sh, sw, dy, dx, dh, dw);
+    }
+    dst[i] = (uint8_t)(mn ? min(v, (int)mn[i]) : v);
+}
+
+int nctk_region_upsize_min(nct_ctx* ctx, hipStream_t s, const uint8_t* src, int sh, int sw, const uint8_t* mn, uint8_t* dst, int dh, int dw) {
+    NCT_REQUIRE(dh >= sh && dw >= sw, "region_upsize_min: the target %dx%d is smaller than the level grid %dx%d", dw, dh, sw, sh);
+    hipLaunchKernelGGL(k_region_upsize_min, dim3((unsigned)(((size_t)dh * dw + 255) / 256)), dim3(256), 0, s, src, sh, sw, mn, dst, dh, dw);
+    NCT_LAUNCH_CHECK();
+    return 0;
+}

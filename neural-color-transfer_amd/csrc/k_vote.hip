@@ -434,9 +434,12 @@ int nctk_bds_vote_image(nct_ctx* ctx, hipStream_t s, const uint8_t* b_bgr, const
     NCT_TRY(build_inverse(ctx, s, bnn, bh, bw, ah, aw, inv));
     return launch_vote_image(ctx, s, inv, b_bgr, ann, ah, aw, bh, bw, w_coh, w_comp, out_bgr);
 }
-// both votes of a level (main.cu:291 and :303-318) from ONE inversion of the R->S field
+static int launch_region_pull(nct_ctx* ctx, hipStream_t s, const InvMap& inv, const uint8_t* q_mask, const uint32_t* ann, int ah, int aw, int bh, int bw,
+                              double w_coh, double w_comp, uint8_t* out);
+// both votes of a level (main.cu:291 and :303-318) from ONE inversion of the R->S field. q_mask (nullable; SPEC §6.12 rule 2): behind the votes the reference's level
+// mask is pulled to S's grid (pulled: ah x aw bytes) through the same inversion — no second sort
 int nctk_bds_vote_both(nct_ctx* ctx, hipStream_t s, const uint8_t* b_bgr, const float* pin_hwc, const uint32_t* ann, const uint32_t* bnn, int C,
-                       int ah, int aw, int bh, int bw, double w_coh, double w_comp, uint8_t* out_bgr, float* pout_hwc) {
+                       int ah, int aw, int bh, int bw, double w_coh, double w_comp, uint8_t* out_bgr, float* pout_hwc, const uint8_t* q_mask, uint8_t* pulled) {
     NCT_REQUIRE(C > 0 && (C & 3) == 0 && C <= 512, "bds_vote: C=%d must be a multiple of 4 and <= 512", C);
     InvMap inv(ctx, bh * bw, ah * aw);
     if (!inv.ok()) return NCT_ERR_HIP;
@@ -445,7 +448,121 @@ int nctk_bds_vote_both(nct_ctx* ctx, hipStream_t s, const uint8_t* b_bgr, const 
     // them from the float casts of the same values — identical as long as the cast is exact, which it is checked to be (bds weights are small decimals like 2.0: if a caller
     // ever passes a weight that is not a float, the two votes run as two kernels)
     if ((double)(float)w_coh == w_coh && (double)(float)w_comp == w_comp)
-        return launch_vote_features(ctx, s, inv, ann, pin_hwc, pout_hwc, nullptr, C, ah, aw, bh, bw, (float)w_coh, (float)w_comp, b_bgr, out_bgr);
-    NCT_TRY(launch_vote_image(ctx, s, inv, b_bgr, ann, ah, aw, bh, bw, w_coh, w_comp, out_bgr));
-    return launch_vote_features(ctx, s, inv, ann, pin_hwc, pout_hwc, nullptr, C, ah, aw, bh, bw, (float)w_coh, (float)w_comp);
+        NCT_TRY(launch_vote_features(ctx, s, inv, ann, pin_hwc, pout_hwc, nullptr, C, ah, aw, bh, bw, (float)w_coh, (float)w_comp, b_bgr, out_bgr));
+    else {
+        NCT_TRY(launch_vote_image(ctx, s, inv, b_bgr, ann, ah, aw, bh, bw, w_coh, w_comp, out_bgr));
+        NCT_TRY(launch_vote_features(ctx, s, inv, ann, pin_hwc, pout_hwc, nullptr, C, ah, aw, bh, bw, (float)w_coh, (float)w_comp));
+    }
+    return q_mask ? launch_region_pull(ctx, s, inv, q_mask, ann, ah, aw, bh, bw, w_coh, w_comp, pulled) : 0;
+}
+
+// ---------------------------------------------------------------- reference region masks: the pull (SPEC §6.12 rule 2)
+// B1 on the one-byte image Q — the same nine taps, bounds tests and source lists — rounded to nearest. The sums are integers and carry no order, so the
+// completeness part does not walk the lists (k_vote_image's walk is one thread per list: 47 535 dependent byte gathers on the target named above): the sources of
+// tap t of target p are the contiguous range start[s] .. start[s + 1] of the sorted inverse map, s = p - t, and a range sum is the difference of two prefix sums.
+//   k_pull_gather  per tap t and sorted position i one 64-bit word: Q(vals_s[i] + t) and the in-bounds flag (0 where the tapped pixel leaves R)
+//   rocPRIM        one exclusive scan over the nine concatenated tap arrays (+ 1 word, so that the last range has its end)
+//   k_pull_vote    one thread per S pixel: nine ann gathers and byte reads (coherence), 18 start and 18 prefix reads (completeness), rule 2's arithmetic
+// No step walks a list: grid sizes, scan length and loads per thread are the same however the sources are spread over the targets (what was measured: DESIGN.md §3.17).
+// Bytes per R pixel: 4 + 9 in and 72 out (gather), 72 in and 72 out (scan); per S pixel 36 + 9 + 72 + 144 in, 1 out.
+// Packing: bits 0 .. 35 the sum of Q, bits 36 .. 63 the count. Over all nine taps of a 4096 x 4096 grid (the largest side any entry point takes) the sum is
+// at most 9 * 255 * 2^24 = 3.86e10 < 2^36 = 6.87e10 and the count at most 9 * 2^24 = 1.51e8 < 2^28, so no prefix carries from one field into the other and a
+// difference of two prefixes borrows from none (both fields are monotone).
+typedef unsigned long long pull_word;
+constexpr int PULL_CNT_SHIFT = 36;
+constexpr pull_word PULL_SUM_MASK = (1ull << PULL_CNT_SHIFT) - 1ull;
+
+__global__ __launch_bounds__(256) void k_pull_gather(const uint8_t* __restrict__ q, const uint32_t* __restrict__ inv_vals, int nb, int bh, int bw, pull_word* __restrict__ g) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) g[(size_t)9 * nb] = 0ull;                  // the scan's last input: its output is the total
+    if (i >= nb) return;
+    const int r = (int)inv_vals[i];
+    const int ry = r / bw, rx = r - ry * bw;
+    uint8_t v[9]; bool ok[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const int dx = t / 3 - 1, dy = t % 3 - 1;
+        const int xb = rx + dx, yb = ry + dy;
+        ok[t] = xb < bw && xb >= 0 && yb < bh && yb >= 0;
+        v[t] = q[ok[t] ? yb * bw + xb : r];
+    }
+#pragma unroll
+    for (int t = 0; t < 9; ++t) g[(size_t)t * nb + i] = ok[t] ? ((1ull << PULL_CNT_SHIFT) | (pull_word)v[t]) : 0ull;
+}
+
+__global__ __launch_bounds__(256) void k_pull_vote(const uint8_t* __restrict__ q, const uint32_t* __restrict__ ann, const int* __restrict__ inv_start,
+                                                   const pull_word* __restrict__ pre, int ah, int aw, int bh, int bw, double wa, double wb, uint8_t* __restrict__ out) {
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= ah * aw) return;
+    const int ay = pix / aw, ax = pix - ay * aw;
+    const size_t nb = (size_t)bh * bw;
+    // coherence: the nine NNF words together, then the nine mask bytes (an absent tap reads its own pixel / byte 0 and is not added)
+    uint32_t vps[9]; bool ok[9]; int src_px[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const int dx = t / 3 - 1, dy = t % 3 - 1;
+        const int nx = ax + dx, ny = ay + dy;
+        ok[t] = nx < aw && nx >= 0 && ny < ah && ny >= 0;
+        vps[t] = ann[ok[t] ? ny * aw + nx : pix];
+    }
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const int dx = t / 3 - 1, dy = t % 3 - 1;
+        const int xp = nnf_x(vps[t]) - dx, yp = nnf_y(vps[t]) - dy;
+        ok[t] = ok[t] && xp < bw && xp >= 0 && yp < bh && yp >= 0;
+        src_px[t] = ok[t] ? yp * bw + xp : 0;
+    }
+    int qa[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) qa[t] = q[src_px[t]];
+    // completeness: per tap the range of the matched neighbour s = p - t, as two prefix words
+    int lo[9], hi[9]; bool in[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const int dx = t / 3 - 1, dy = t % 3 - 1;
+        const int sx = ax - dx, sy = ay - dy;
+        in[t] = sx >= 0 && sx < aw && sy >= 0 && sy < ah;
+        const int s = in[t] ? sy * aw + sx : pix;
+        lo[t] = inv_start[s]; hi[t] = inv_start[s + 1];
+    }
+    pull_word acc = 0ull;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const pull_word d = pre[(size_t)t * nb + hi[t]] - pre[(size_t)t * nb + lo[t]];
+        acc += in[t] ? d : 0ull;
+    }
+    int A = 0, ca = 0;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) if (ok[t]) { A += qa[t]; ++ca; }
+    const long long B = (long long)(acc & PULL_SUM_MASK), cb = (long long)(acc >> PULL_CNT_SHIFT);
+    // rule 2: the products first, then the sums, then the quotient (no contraction: -ffp-contract=off); ca >= 1, the centre tap is inside
+    const double num = (double)A * wa + (double)B * wb;
+    const double den = (double)ca * wa + (double)cb * wb;
+    out[pix] = (uint8_t)rint(num / den);
+}
+
+static int launch_region_pull(nct_ctx* ctx, hipStream_t s, const InvMap& inv, const uint8_t* q_mask, const uint32_t* ann, int ah, int aw, int bh, int bw,
+                              double w_coh, double w_comp, uint8_t* out) {
+    const double wa = w_coh / (double)(aw * ah);
+    const double wb = w_comp / (double)(bw * bh);
+    const int na = ah * aw, nb = bh * bw;
+    const size_t nw = (size_t)9 * nb + 1;
+    DevBuf<pull_word> g(ctx, nw), pre(ctx, nw);
+    if (!g.ok() || !pre.ok()) return NCT_ERR_HIP;
+    hipLaunchKernelGGL(k_pull_gather, dim3(cdiv(nb, 256)), dim3(256), 0, s, q_mask, (const uint32_t*)inv.vals_s, nb, bh, bw, (pull_word*)g); NCT_LAUNCH_CHECK();
+    size_t scan_bytes = 0;
+    NCT_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (const pull_word*)g, (pull_word*)pre, (pull_word)0, nw, rocprim::plus<pull_word>(), s));
+    DevBuf<char> tmp(ctx, scan_bytes + 16);
+    if (!tmp.ok()) return NCT_ERR_HIP;
+    NCT_HIP(rocprim::exclusive_scan((void*)(char*)tmp, scan_bytes, (const pull_word*)g, (pull_word*)pre, (pull_word)0, nw, rocprim::plus<pull_word>(), s));
+    hipLaunchKernelGGL(k_pull_vote, dim3(cdiv(na, 256)), dim3(256), 0, s, q_mask, ann, (const int*)inv.start, (const pull_word*)pre, ah, aw, bh, bw, wa, wb, out);
+    NCT_LAUNCH_CHECK();
+    return 0;                              // g, pre and tmp return to the arena (recycled in stream order)
+}
+int nctk_region_pull(nct_ctx* ctx, hipStream_t s, const uint8_t* q_mask, int bh, int bw, const uint32_t* ann, const uint32_t* bnn, int ah, int aw,
+                     double w_coh, double w_comp, uint8_t* out) {
+    InvMap inv(ctx, bh * bw, ah * aw);
+    if (!inv.ok()) return NCT_ERR_HIP;
+    NCT_TRY(build_inverse(ctx, s, bnn, bh, bw, ah, aw, inv));
+    return launch_region_pull(ctx, s, inv, q_mask, ann, ah, aw, bh, bw, w_coh, w_comp, out);
 }

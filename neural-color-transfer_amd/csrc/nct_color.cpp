@@ -85,6 +85,20 @@ int nct_region_compose(nct_ctx* ctx, const uint8_t* s_bgr, const uint8_t* lab_ou
     return NCT_OK;
 }
 
+// ---- reference region masks (SPEC §6.12 rule 2): the pull alone, on host maps
+int nct_region_pull(nct_ctx* ctx, const uint8_t* q_mask, int bh, int bw, const uint32_t* ann, const uint32_t* bnn, int ah, int aw, double w_coherence, double w_complete,
+                    uint8_t* out) {
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_region_pull_check(ctx, "region_pull", q_mask, bh, bw, ann, bnn, ah, aw, out));
+    const size_t na = (size_t)ah * aw, nb = (size_t)bh * bw;
+    DevBuf<uint8_t> dq(ctx, nb), dout(ctx, na); DevBuf<uint32_t> da(ctx, na), db(ctx, nb);
+    if (!dq.ok() || !dout.ok() || !da.ok() || !db.ok()) return NCT_ERR_HIP;
+    NCT_H2D(dq, q_mask, nb); NCT_H2D(da, ann, sizeof(uint32_t) * na); NCT_H2D(db, bnn, sizeof(uint32_t) * nb);
+    NCT_TRY(nctk_region_pull(ctx, ctx->stream, dq, bh, bw, da, db, ah, aw, w_coherence, w_complete, dout));
+    NCT_D2H(out, dout, na); NCT_SYNC();
+    return NCT_OK;
+}
+
 int nct_resize_f64c3(nct_ctx* ctx, const double* src, int sh, int sw, double* dst, int dh, int dw) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(src && dst && sh > 0 && sw > 0 && dh > 0 && dw > 0, "resize_f64c3: bad arguments");

@@ -219,6 +219,14 @@ int nct_region_compose_dev(nct_ctx* ctx, const uint8_t* d_s_bgr, const uint8_t* 
     return nctk_region_compose(ctx, ctx->stream, d_s_bgr, ls, d_lab_out, d_mask, npix, region ? region->protect : 0, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0, d_out_bgr);
 }
 
+// ---- SPEC §6.12 rule 2 on device pointers
+int nct_region_pull_dev(nct_ctx* ctx, const uint8_t* d_q_mask, int bh, int bw, const uint32_t* d_ann, const uint32_t* d_bnn, int ah, int aw, double w_coherence,
+                        double w_complete, uint8_t* d_out) {
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_region_pull_check(ctx, "region_pull_dev", d_q_mask, bh, bw, d_ann, d_bnn, ah, aw, d_out));
+    return nctk_region_pull(ctx, ctx->stream, d_q_mask, bh, bw, d_ann, d_bnn, ah, aw, w_coherence, w_complete, d_out);
+}
+
 int nct_color_finish_upsample_dev(nct_ctx* ctx, const double* d_ab_wls, int h, int w, const uint8_t* d_s_bgr_full, int H, int W, const nct_params* prm,
                                   uint8_t* d_out_bgr_full) {                                                                                          /* SPEC §6.8 */
     NCT_CTX_ENTER();

@@ -267,6 +267,11 @@ static inline int nct_region_compose_check(nct_ctx* ctx, const char* what, const
 }
 int nctk_region_compose(nct_ctx* ctx, hipStream_t s, const uint8_t* s_bgr, const uint8_t* s_lab, const uint8_t* o_lab, const uint8_t* mask, size_t npix, int protect, int form,
                         uint8_t* out_bgr);
+// SPEC §6.12 rules 3-5. nctk_region_merge: P_l = the pulled mask of the pixel's label (pulled: K device pointers, null = a reference without a mask = 255; label is read
+// with K > 1 only) into p_out and M_l = min(P_l, ms) into m_out (ms null = 255; either output nullable). nctk_region_upsize_min: dst = min(resize_u8c1(src -> dh x dw), mn)
+// for a target not smaller than the source grid (mn nullable; equal sizes: the copy / the minimum)
+int nctk_region_merge(nct_ctx* ctx, hipStream_t s, const uint8_t* const* pulled, int K, const uint8_t* label, const uint8_t* ms, int n, uint8_t* p_out, uint8_t* m_out);
+int nctk_region_upsize_min(nct_ctx* ctx, hipStream_t s, const uint8_t* src, int sh, int sw, const uint8_t* mn, uint8_t* dst, int dh, int dw);
 // k_wls_mg.hip
 int nctk_wls_solve_mg(nct_ctx* ctx, hipStream_t s, double* X, const double* rough, const double* wx, const double* wy, int H, int W,
                       double rtol, int* iters_out);
@@ -283,4 +288,22 @@ int nctk_bds_vote_features(nct_ctx* ctx, hipStream_t s, const uint32_t* ann, con
 int nctk_bds_vote_image(nct_ctx* ctx, hipStream_t s, const uint8_t* b_bgr, const uint32_t* ann, const uint32_t* bnn,
                         int ah, int aw, int bh, int bw, double w_coh, double w_comp, uint8_t* out_bgr);
 int nctk_bds_vote_both(nct_ctx* ctx, hipStream_t s, const uint8_t* b_bgr, const float* pin_hwc, const uint32_t* ann, const uint32_t* bnn, int C,
-                       int ah, int aw, int bh, int bw, double w_coh, double w_comp, uint8_t* out_bgr, float* pout_hwc);
+                       int ah, int aw, int bh, int bw, double w_coh, double w_comp, uint8_t* out_bgr, float* pout_hwc,
+                       const uint8_t* q_mask = nullptr /* SPEC §6.12: the reference's level mask (bh x bw), pulled behind the votes through their inversion of bnn … */,
+                       uint8_t* pulled = nullptr /* … into this (ah x aw) */);
+// reference region masks (SPEC §6.12 rule 2): the pull of the one-byte image q_mask (bh x bw) to the source's grid (out: ah x aw) — B1 on one channel, rounded to
+// nearest — through the sorted inverse map and one prefix scan; a level's pull rides behind nctk_bds_vote_both's votes
+int nctk_region_pull(nct_ctx* ctx, hipStream_t s, const uint8_t* q_mask, int bh, int bw, const uint32_t* ann, const uint32_t* bnn, int ah, int aw,
+                     double w_coh, double w_comp, uint8_t* out);
+// the argument checks of nct_region_pull[_dev] (`what` names the entry point in the message)
+static inline int nct_region_pull_check(nct_ctx* ctx, const char* what, const void* q_mask, int bh, int bw, const void* ann, const void* bnn, int ah, int aw, const void* out) {
+    NCT_REQUIRE(q_mask, "%s: q_mask is null", what);
+    NCT_REQUIRE(ann, "%s: ann is null", what);
+    NCT_REQUIRE(bnn, "%s: bnn is null", what);
+    NCT_REQUIRE(out, "%s: out is null", what);
+    NCT_REQUIRE(bh >= 1 && bh <= 4096, "%s: bh = %d is not in [1, 4096]", what, bh);
+    NCT_REQUIRE(bw >= 1 && bw <= 4096, "%s: bw = %d is not in [1, 4096]", what, bw);
+    NCT_REQUIRE(ah >= 1 && ah <= 4096, "%s: ah = %d is not in [1, 4096]", what, ah);
+    NCT_REQUIRE(aw >= 1 && aw <= 4096, "%s: aw = %d is not in [1, 4096]", what, aw);
+    return NCT_OK;
+}

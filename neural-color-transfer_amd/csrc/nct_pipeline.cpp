@@ -23,6 +23,8 @@ void drop_images(nct_ctx* ctx, pair_state* P) {
     if (P->full_out) { ctx->release(P->full_out); P->full_out = nullptr; }
     if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
     if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
+    for (uint8_t*& m : P->rmask) if (m) { ctx->release(m); m = nullptr; }
+    if (P->fin_mask) { ctx->release(P->fin_mask); P->fin_mask = nullptr; }
     P->K = 0; P->finished = false; P->protect = 0;
 }
 // the images live in the context arena like every other device buffer (no hipMalloc/hipFree — device-wide synchronisation points —
@@ -96,7 +98,7 @@ int finish_level(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int
                  const full_target* full, const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube, const region_fin* region) {
     if (full && full->finish == NCT_FINISH_EXACT) {
         NCT_TRY(nctk_color_finish(ctx, s, x, h, w, H, W, fl.s0, full->H, full->W, cp, fl.out0, dbg));
-        if (region) return nctk_region_compose(ctx, s, full->src, fl.s0, fl.out0, full->mask, (size_t)full->H * full->W, region->protect, cube, full->out);
+        if (region) return nctk_region_compose(ctx, s, full->src, fl.s0, fl.out0, region->mask0 ? region->mask0 : full->mask, (size_t)full->H * full->W, region->protect, cube, full->out);
         return nctk_lab2bgr(ctx, s, fl.out0, full->out, (size_t)full->H * full->W, cube);
     }
     const nct_finish_up up{full ? full->src : nullptr, full ? full->H : 0, full ? full->W : 0, full ? full->out : nullptr, cube, ctx->guided_sigma /* nct_set_finish_guided */};
@@ -115,6 +117,8 @@ struct ref_bufs {
     DevBuf<float> bnnd, err;
     DevBuf<uint8_t> guide;
     const uint8_t* img[5];
+    // the reference's region mask (SPEC §6.12; qimg[4] null: none): its level masks Q_k,l beside the image pyramid, and P_k,l, the current level's mask pulled to S's grid
+    DevBuf<uint8_t> qpyr[4], pulled; const uint8_t* qimg[5] = {};
     const float* featp[5];                          // the taps the correspondence reads: feat[l], or the ones an open sequence prepared (SPEC §6.3)
 };
 
@@ -146,6 +150,7 @@ struct pair_run {
     seq_state* const seq;                          // nullable: this run is a frame of the open sequence (SPEC §6.3) — the reference's pyramid and taps are borrowed, S1's output is blended
     const nct_seq_levels* const slv;               // nullable: where a frame's X'_t and tau_p maps go
     const nct_region_levels* const rlv;            // nullable: where a masked run's level masks and mixed coefficients go (SPEC §6.11)
+    const nct_ref_region_levels* const qlv;        // nullable: the same for a run with a reference mask (SPEC §6.12)
     pair_state* const P; const hipStream_t s;
     const int H, W, K, nlevels; const size_t N;
     const bool feat16, count;
@@ -166,12 +171,18 @@ struct pair_run {
     // the source's region mask (SPEC §6.11; null: none, and the run enqueues and reserves what it always did) and its level masks — the pyramid's single-channel form
     const uint8_t* const mask;
     DevBuf<uint8_t> mpyr[4]; const uint8_t* mimg[5] = {};
+    // reference region masks (SPEC §6.12; ref_masked false: the run enqueues and reserves what it always did). p_merged: P_l of several references (rule 3); m_level: M_l where
+    // it is not P_l itself (rule 4: a source mask as well); f_level: F_l of a level that is not the last (the last level's is pair_state's fin_mask). p_l / m_l / f_l: the
+    // current level's three masks, wherever they live
+    const bool ref_masked;
+    DevBuf<uint8_t> p_merged, m_level, f_level;
+    const uint8_t *p_l = nullptr, *m_l = nullptr, *f_l = nullptr;
     const nct_color_params cp;
 
     pair_run(nct_ctx* c, const nct_params* p, nct_pair_timing* t, const run_extras& x)
-        : ctx(c), prm(p), timing(t), lv(x.lv ? x.lv : &kNoLevels), color(x.color), fin(x.fin), seq(x.seq), slv(x.slv), rlv(x.rlv), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
+        : ctx(c), prm(p), timing(t), lv(x.lv ? x.lv : &kNoLevels), color(x.color), fin(x.fin), seq(x.seq), slv(x.slv), rlv(x.rlv), qlv(x.qlv), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
           nlevels(p->levels), N((size_t)H * W), feat16((p->flags & NCT_FLAG_FEAT16) != 0), count(t && (p->flags & NCT_FLAG_COUNT_EVALS)), side(c), mask(x.seq ? nullptr : P->mask),
-          cp(nct_color_params_of(*p)) {}
+          ref_masked(!x.seq && P->ref_masked()), cp(nct_color_params_of(*p)) {}
 
     int d2h(void* dst, const void* src, size_t bytes) {
         if (dst) NCT_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
@@ -209,6 +220,16 @@ struct pair_run {
                 if (!mpyr[l].alloc(ctx, (size_t)ah[l] * aw[l])) return NCT_ERR_HIP;
                 NCT_TRY(nctk_resize_u8c1(ctx, s, mimg[l + 1], ah[l + 1], aw[l + 1], mpyr[l], ah[l], aw[l]));
                 mimg[l] = mpyr[l];
+            }
+        }
+        for (int k = 0; k < K && ref_masked; ++k) {
+            // SPEC §6.12 rule 1: the masked references' level masks, on the reference's level grids
+            if (!P->rmask[k]) continue;
+            R[k].qimg[4] = P->rmask[k];
+            for (int l = 3; l >= 0; --l) {
+                if (!R[k].qpyr[l].alloc(ctx, (size_t)R[k].bh[l] * R[k].bw[l])) return NCT_ERR_HIP;
+                NCT_TRY(nctk_resize_u8c1(ctx, s, R[k].qimg[l + 1], R[k].bh[l + 1], R[k].bw[l + 1], R[k].qpyr[l], R[k].bh[l], R[k].bw[l]));
+                R[k].qimg[l] = R[k].qpyr[l];
             }
         }
         MARK(NCT_ST_OTHER, 0);
@@ -273,6 +294,12 @@ struct pair_run {
         if (K > 1) {
             if (!sel_label.alloc(ctx, N)) return NCT_ERR_HIP;
             for (int k = 0; k < K; ++k) if (!R[k].err.alloc(ctx, N) || !R[k].guide.alloc(ctx, N * 3)) return NCT_ERR_HIP;
+        }
+        if (ref_masked) {
+            for (int k = 0; k < K; ++k) if (R[k].qimg[4] && !R[k].pulled.alloc(ctx, N)) return NCT_ERR_HIP;
+            if (K > 1 && !p_merged.alloc(ctx, N)) return NCT_ERR_HIP;
+            if (mask && !m_level.alloc(ctx, N)) return NCT_ERR_HIP;
+            if (nlevels > 1 && !f_level.alloc(ctx, N)) return NCT_ERR_HIP;          // one level: its F is the last level's, pair_state's fin_mask
         }
         if (!P->out) { P->out = (uint8_t*)ctx->alloc(N * 3); if (!P->out) return NCT_ERR_HIP; }
         return d2h(lv->labels, labels, sizeof(int) * (size_t)ah[0] * aw[0]);
@@ -341,7 +368,8 @@ struct pair_run {
         NCT_TRY(d2h(lv->annd[k][l], annd, sizeof(float) * na_px));
         NCT_TRY(d2h(lv->bnnd[k][l], bnnd, sizeof(float) * nb_px));
         // BDS votes: guidance image (main.cu:291) and features + matching error (main.cu:303-318)
-        NCT_TRY(nctk_bds_vote_both(ctx, s, R[k].img[l], R[k].featp[l], ann, bnn, C, ah[l], aw[l], bh[l], bw[l], 1.0, prm->bds_weight, guide_of(k), voted));
+        // a masked reference (SPEC §6.12 rule 2; else qimg[l] is null): its level mask is pulled to S's grid behind the votes, through the same inversion of bnn
+        NCT_TRY(nctk_bds_vote_both(ctx, s, R[k].img[l], R[k].featp[l], ann, bnn, C, ah[l], aw[l], bh[l], bw[l], 1.0, prm->bds_weight, guide_of(k), voted, R[k].qimg[l], R[k].pulled));
         NCT_TRY(nctk_normalize(ctx, s, voted, nvoted, nullptr, C, na_px));
         return nctk_feature_distance(ctx, s, na, nvoted, err_of(k), C, na_px);
     }
@@ -360,6 +388,7 @@ struct pair_run {
                 for (int q = 0; q < K; ++q) { errs[q] = R[q].err; guides[q] = R[q].guide; }
                 NCT_TRY(nctk_select_reference(ctx, s, errs, guides, K, ah[l], aw[l], sel_label, guide, err));
             }
+            if (ref_masked && k == K - 1) NCT_TRY(level_masks(l));
             MARK(NCT_ST_VOTE, l);
             NCT_TRY(d2h(lv->ref_guide[k][l], guide_of(k), (size_t)na_px * 3));
             NCT_TRY(d2h(lv->ref_err[k][l], err_of(k), sizeof(float) * na_px));
@@ -369,6 +398,24 @@ struct pair_run {
         else if (lv->label[l]) memset(lv->label[l], 0, (size_t)na_px);
         NCT_TRY(d2h(lv->guide[l], guide, (size_t)na_px * 3));
         return d2h(lv->err[l], err, sizeof(float) * na_px);
+    }
+
+    // SPEC §6.12 rules 3-4, behind the last reference's votes (and the selection): P_l = the pulled mask of the pixel's label, M_l = min(P_l, the source's level mask).
+    // One reference and no source mask: P_l and M_l are reference 0's pulled mask, no launch
+    int level_masks(int l) {
+        const int na_px = ah[l] * aw[l];
+        const uint8_t* pulled[NCT_MAX_REFS];
+        for (int k = 0; k < K; ++k) pulled[k] = R[k].qimg[4] ? (const uint8_t*)R[k].pulled : nullptr;
+        p_l = K > 1 ? (const uint8_t*)p_merged : pulled[0];
+        m_l = mask ? (const uint8_t*)m_level : p_l;
+        if (K > 1 || mask) NCT_TRY(nctk_region_merge(ctx, s, pulled, K, sel_label, mimg[l], na_px, K > 1 ? (uint8_t*)p_merged : nullptr, mask ? (uint8_t*)m_level : nullptr));
+        if (!qlv) return NCT_OK;
+        for (int k = 0; k < K; ++k) {
+            if (!R[k].qimg[4]) continue;
+            NCT_TRY(d2h(qlv->ref_mask[k][l], R[k].qimg[l], (size_t)R[k].bh[l] * R[k].bw[l]));
+            NCT_TRY(d2h(qlv->pulled[k][l], R[k].pulled, (size_t)na_px));
+        }
+        return d2h(qlv->mask[l], m_l, (size_t)na_px);
     }
 
     // level l's prebuilt part of S1's system with what the host knows about its hub blocks right now: the count, if the side stream has passed ev_level[l] (always, from
@@ -409,12 +456,24 @@ struct pair_run {
         // a frame of a sequence: the blend between S1 and the finish, which then reads the kept X'_t (SPEC §6.3 rule 3)
         if (seq) NCT_TRY(seq_level_step(ctx, s, seq, l, side.slab[l], cb.x, cb.tmap, slv));
         // a masked run (SPEC §6.11 rule 2): S1's coefficients move toward the identity by the level mask, in place; the finish reads X' and composes with the source (rule 3)
-        const region_fin rg{mask, P->src, P->protect};
+        region_fin rg{mask, P->src, P->protect};
+        if (ref_masked) {
+            // SPEC §6.12 rules 4-5: the mix by M_l; F_l at the size the finish targets — the last level's is kept for nct_pair_fit_lut (rule 7) — for the compose
+            const bool last = l == nlevels - 1;
+            const int fh = full ? full->H : H, fw = full ? full->W : W;
+            uint8_t* f = f_level;
+            if (last) { if (!(P->fin_mask = (uint8_t*)ctx->alloc((size_t)fh * fw))) return NCT_ERR_HIP; f = P->fin_mask; }
+            NCT_TRY(nctk_region_upsize_min(ctx, s, p_l, ah[l], aw[l], full ? full->mask : mask, f, fh, fw));
+            NCT_TRY(nctk_region_mix(ctx, s, cb.x, m_l, ah[l], aw[l], cb.x));
+            if (qlv) { NCT_TRY(dbg_copy(ctx, s, qlv->ab_mix[l], (double*)cb.x, (size_t)6 * na_px)); NCT_TRY(dbg_copy(ctx, s, qlv->mask_full[l], f, (size_t)fh * fw)); }
+            if (rlv) { NCT_TRY(dbg_copy(ctx, s, rlv->ab_mix[l], (double*)cb.x, (size_t)6 * na_px)); NCT_TRY(dbg_copy(ctx, s, rlv->mask[l], m_l, (size_t)na_px)); }
+            rg.mask = f; rg.mask0 = f;
+        } else
         if (mask) {
             NCT_TRY(nctk_region_mix(ctx, s, cb.x, mimg[l], ah[l], aw[l], cb.x));
             if (rlv) { NCT_TRY(dbg_copy(ctx, s, rlv->ab_mix[l], (double*)cb.x, (size_t)6 * na_px)); NCT_TRY(dbg_copy(ctx, s, rlv->mask[l], mimg[l], (size_t)na_px)); }
         }
-        NCT_TRY(finish_level(ctx, s, seq ? seq->keep_x[l] : (double*)cb.x, ah[l], aw[l], H, W, s_lab_full, out_lab, P->out, full, fl, cp, d, nct_cube_form(*prm), mask ? &rg : nullptr));
+        NCT_TRY(finish_level(ctx, s, seq ? seq->keep_x[l] : (double*)cb.x, ah[l], aw[l], H, W, s_lab_full, out_lab, P->out, full, fl, cp, d, nct_cube_form(*prm), (mask || ref_masked) ? &rg : nullptr));
         if (cs && cs->wls_iters) for (int q = 0; q < 6; ++q) cs->wls_iters[q] = wls_it[q];
         if (timing) timing->wls_iters[l] = *std::max_element(wls_it, wls_it + 6);
         MARK(NCT_ST_COLOR, l);
@@ -465,6 +524,8 @@ int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timin
     NCT_REQUIRE(!x.color || P->K == 1, "process: nct_pair_levels describes a pair; several references report through nct_multi_levels");
     if (x.rlv && !P->mask) return ctx->fail(NCT_ERR_STATE, "process: region levels asked for, but no region mask is set (nct_pair_set_region first)");
     NCT_REQUIRE(!(P->mask && x.fin) || (x.fin->finish == NCT_FINISH_EXACT && x.fin->mask), "process: a region mask is defined for the exact full-resolution finish only");
+    if (x.qlv && !P->ref_masked()) return ctx->fail(NCT_ERR_STATE, "process: reference region levels asked for, but no reference mask is set (nct_pair_set_ref_region first)");
+    NCT_REQUIRE(!(P->ref_masked() && x.fin) || x.fin->finish == NCT_FINISH_EXACT, "process: a reference region mask is defined for the exact full-resolution finish only");
     // a new run on the resident images: an earlier full-resolution run is no longer the last one, and its two original-size images go back to the arena
     // (a full-resolution sequence keeps its two for its whole life: SPEC §6.9 rule 6)
     if (!(x.seq && x.seq->target())) {
@@ -472,6 +533,7 @@ int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timin
         if (P->full_out) { ctx->release(P->full_out); P->full_out = nullptr; }
         if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
     }
+    if (P->fin_mask) { ctx->release(P->fin_mask); P->fin_mask = nullptr; }
     P->finished = false;
     run_clock clock(ctx, timing, prm->flags);
     pair_run run(ctx, prm, timing, x);
@@ -629,6 +691,65 @@ int nct_process_pair_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw
     return nct_pair_download(ctx, out_bgr);
 }
 
+// ---- reference region masks (SPEC §6.12)
+int nct_pair_set_ref_region(nct_ctx* ctx, int k, const uint8_t* mask, const nct_region_params* region) {
+    NCT_CTX_ENTER();
+    NCT_NO_OPEN_SEQ("pair_set_ref_region");
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->src || P->sh < 1 || P->K < 1) return ctx->fail(NCT_ERR_STATE, "pair_set_ref_region: no references uploaded (nct_pair_upload or nct_multi_upload first)");
+    NCT_REQUIRE(k >= 0 && k < P->K, "pair_set_ref_region: k = %d is not one of the %d uploaded references", k, P->K);
+    NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "pair_set_ref_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
+    P->finished = false;
+    const size_t n = (size_t)P->rh[k] * P->rw[k];
+    if (!mask) {
+        if (P->rmask[k]) { NCT_SYNC(); ctx->release(P->rmask[k]); P->rmask[k] = nullptr; }
+    } else {
+        if (!P->rmask[k] && !(P->rmask[k] = (uint8_t*)ctx->alloc(n))) return NCT_ERR_HIP;
+        NCT_H2D(P->rmask[k], mask, n);
+        NCT_SYNC();
+    }
+    if (region) P->protect = region->protect;
+    return NCT_OK;
+}
+
+int nct_multi_run_ref_region_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_multi_levels* levels, const nct_ref_region_levels* region_levels) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(prm, "multi_run_ref_region_levels: null params");
+    return process_resident(ctx, prm, timing, {levels, nullptr, nullptr, nullptr, nullptr, nullptr, region_levels});
+}
+
+int nct_pair_run_ref_region_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_ref_region_levels* region_levels) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(prm, "pair_run_ref_region_levels: null params");
+    if (!levels) return process_resident(ctx, prm, timing, {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, region_levels});
+    const nct_multi_levels m = multi_levels_of(*levels);
+    return process_resident(ctx, prm, timing, {&m, levels->color, nullptr, nullptr, nullptr, nullptr, region_levels});
+}
+
+int nct_process_multi_ref_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* src_mask, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw,
+                                 const uint8_t* const* ref_masks, const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
+    if (!ctx) return NCT_ERR_INVALID;
+    bool any = src_mask != nullptr;                              // as in the pair form: protect is read only where a mask is given
+    for (int k = 0; k < K && k < NCT_MAX_REFS && ref_masks; ++k) any = any || ref_masks[k];
+    NCT_REQUIRE(!any || !region || region->protect == 0 || region->protect == 1, "process_multi_ref_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
+    NCT_TRY(nct_multi_upload(ctx, src_bgr, sh, sw, K, refs_bgr, rh, rw));
+    if (src_mask) NCT_TRY(nct_pair_set_region(ctx, src_mask, region));
+    for (int k = 0; k < K && ref_masks; ++k) if (ref_masks[k]) NCT_TRY(nct_pair_set_ref_region(ctx, k, ref_masks[k], region));
+    NCT_TRY(nct_multi_run(ctx, prm, timing));
+    return nct_pair_download(ctx, out_bgr);
+}
+
+int nct_process_pair_ref_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* src_mask, const uint8_t* ref_bgr, int rh, int rw, const uint8_t* ref_mask,
+                                const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
+    if (!ctx) return NCT_ERR_INVALID;
+    NCT_REQUIRE((!src_mask && !ref_mask) || !region || region->protect == 0 || region->protect == 1, "process_pair_ref_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
+    NCT_TRY(nct_pair_upload(ctx, src_bgr, sh, sw, ref_bgr, rh, rw));
+    if (src_mask) NCT_TRY(nct_pair_set_region(ctx, src_mask, region));
+    if (ref_mask) NCT_TRY(nct_pair_set_ref_region(ctx, 0, ref_mask, region));
+    NCT_TRY(nct_pair_run(ctx, prm, timing));
+    return nct_pair_download(ctx, out_bgr);
+}
+
 int nct_pair_download(nct_ctx* ctx, uint8_t* out_bgr) {
     NCT_CTX_ENTER();
     pair_state* P = (pair_state*)ctx->pair;
@@ -669,15 +790,27 @@ int nct_process_pair_fullres_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh
     return nct_process_pair_fullres_finish_region(ctx, src_bgr, sh, sw, mask0, ref_bgr, rh, rw, max_side, NCT_FINISH_EXACT, region, prm, out_bgr, timing);
 }
 
+static int fullres_run(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* mask0, const uint8_t* ref_bgr, int rh, int rw, const uint8_t* ref_mask0, int max_side,
+                       int finish, const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing);
 // mask0 (nullable: the unmasked run, with its launches and arena requests): the source's region mask at sh x sw (SPEC §6.11 rule 5)
 int nct_process_pair_fullres_finish_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* mask0, const uint8_t* ref_bgr, int rh, int rw, int max_side,
                                            int finish, const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
+    return fullres_run(ctx, src_bgr, sh, sw, mask0, ref_bgr, rh, rw, nullptr, max_side, finish, region, prm, out_bgr, timing);
+}
+// SPEC §6.12 rule 5: both masks at the original sizes, the exact finish
+int nct_process_pair_fullres_ref_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* mask0, const uint8_t* ref_bgr, int rh, int rw, const uint8_t* ref_mask0,
+                                        int max_side, const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
+    return fullres_run(ctx, src_bgr, sh, sw, mask0, ref_bgr, rh, rw, ref_mask0, max_side, NCT_FINISH_EXACT, region, prm, out_bgr, timing);
+}
+// ref_mask0 (nullable): the reference's region mask at rh x rw (SPEC §6.12), shrunk with its image
+static int fullres_run(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* mask0, const uint8_t* ref_bgr, int rh, int rw, const uint8_t* ref_mask0, int max_side,
+                       int finish, const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
     NCT_CTX_ENTER();
     NCT_NO_OPEN_SEQ("process_pair_fullres");
     NCT_REQUIRE(src_bgr && ref_bgr && prm && out_bgr, "process_pair_fullres: null pointer");
     NCT_REQUIRE(finish == NCT_FINISH_EXACT || finish == NCT_FINISH_UPSAMPLE, "process_pair_fullres: finish must be NCT_FINISH_EXACT (0) or NCT_FINISH_UPSAMPLE (1) (got %d)", finish);
     NCT_REQUIRE(!mask0 || finish == NCT_FINISH_EXACT, "process_pair_fullres: a region mask with NCT_FINISH_UPSAMPLE is not defined (SPEC 6.11 rule 8): use NCT_FINISH_EXACT");
-    NCT_REQUIRE(!mask0 || !region || region->protect == 0 || region->protect == 1, "process_pair_fullres: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
+    NCT_REQUIRE((!mask0 && !ref_mask0) || !region || region->protect == 0 || region->protect == 1, "process_pair_fullres: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
     int wh = 0, ww = 0, rwh = 0, rww = 0;
     const char* why = nct_working_size_rule(sh, sw, max_side, &wh, &ww);
     if (why) return ctx->fail(NCT_ERR_INVALID, "process_pair_fullres: source %dx%d: %s", sw, sh, why);
@@ -701,6 +834,13 @@ int nct_process_pair_fullres_finish_region(nct_ctx* ctx, const uint8_t* src_bgr,
         if (!m0.alloc(ctx, (size_t)sh * sw) || !(P->mask = (uint8_t*)ctx->alloc((size_t)wh * ww))) return NCT_ERR_HIP;
         NCT_H2D(m0, mask0, (size_t)sh * sw);
         NCT_TRY(nctk_resize_u8c1(ctx, ctx->stream, m0, sh, sw, P->mask, wh, ww));
+        P->protect = region ? region->protect : 0;
+    }
+    DevBuf<uint8_t> q0;
+    if (ref_mask0) {
+        if (!q0.alloc(ctx, (size_t)rh * rw) || !(P->rmask[0] = (uint8_t*)ctx->alloc((size_t)rwh * rww))) return NCT_ERR_HIP;
+        NCT_H2D(q0, ref_mask0, (size_t)rh * rw);
+        NCT_TRY(nctk_resize_u8c1(ctx, ctx->stream, q0, rh, rw, P->rmask[0], rwh, rww));
         P->protect = region ? region->protect : 0;
     }
     NCT_SYNC();
@@ -733,6 +873,8 @@ int nct_pair_fit_lut(nct_ctx* ctx, const nct_lut_params* prm, float* lut_out) {
     // a masked run's table is fitted over its region (SPEC §6.11 rule 7), with the mask at the size of the images it reads
     if (P && P->full_src && P->full_out) { src = P->full_src; res = P->full_out; mask = P->full_mask; npix = (size_t)P->full_h * P->full_w; }
     else if (P && P->src && P->out && P->sh > 0) { src = P->src; res = P->out; mask = P->seq ? nullptr : P->mask; npix = (size_t)P->sh * P->sw; }
+    // a run with a reference mask: its last level's target mask, which has the size of the result (SPEC §6.12 rule 7)
+    if (src && P->fin_mask && !P->seq) mask = P->fin_mask;
     if (!src) return ctx->fail(NCT_ERR_STATE, "pair_fit_lut: no finished run on this context (nct_pair_run first)");
     NCT_TRY(nct_lut_fit_check(ctx, "pair_fit_lut", src, res, npix, prm, lut_out));
     const size_t n = (size_t)prm->size * prm->size * prm->size * 3;

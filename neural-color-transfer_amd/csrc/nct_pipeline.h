@@ -39,6 +39,9 @@ struct pair_state {
     int full_h = 0, full_w = 0;
     uint8_t *mask = nullptr, *full_mask = nullptr;             // the source's region mask (SPEC §6.11): sh x sw bytes, set by nct_pair_set_region, dropped with the images; after a masked
     int protect = 0;                                           // full-resolution run also the mask at full_h x full_w, beside full_src / full_out. protect: nct_region_params
+    uint8_t* rmask[NCT_MAX_REFS] = {};                         // the references' region masks (SPEC §6.12): rh[k] x rw[k] bytes, set by nct_pair_set_ref_region, dropped with the images
+    uint8_t* fin_mask = nullptr;                               // the last level's target mask F of a run with a reference mask, at the size of its result (rule 7: nct_pair_fit_lut); gone with the next run
+    bool ref_masked() const { for (const uint8_t* m : rmask) if (m) return true; return false; }
     bool finished = false;                                     // the last run on these images ran to its end: `out` (or full_out) holds its result
 };
 
@@ -51,7 +54,8 @@ NCT_LOCAL void drop_images(nct_ctx* ctx, pair_state* P);    // drop what the con
 // what a run is asked for beside its result, every member nullable. lv: host copies of the level intermediates; color (a pair only): [5] the colour stage's coefficient
 // maps per level; fin (K = 1 only): the full-resolution finish; seq: the run is a frame of this open sequence, slv: where that frame's X'_t, tau_p and fields go
 // rlv: where a masked run's level masks and mixed coefficients go (SPEC §6.11)
-struct run_extras { const nct_multi_levels* lv; const nct_color_stages* const* color; const full_target* fin; seq_state* seq; const nct_seq_levels* slv; const nct_region_levels* rlv; };
+struct run_extras { const nct_multi_levels* lv; const nct_color_stages* const* color; const full_target* fin; seq_state* seq; const nct_seq_levels* slv; const nct_region_levels* rlv;
+                    const nct_ref_region_levels* qlv; };      // qlv: where a run with a reference mask reports Q_k,l, P_k,l, M_l, F_l and X' (SPEC §6.12)
 // run the whole L=5->1 loop on the uploaded source and its K references
 NCT_LOCAL int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const run_extras& x = {});
 // a pair is the list of one reference (SPEC §6.2): its maps are reference 0's NNFs and the merged guide / err; it has no label map and no G_k / E_k of their own
@@ -94,7 +98,8 @@ struct NCT_LOCAL full_lab {
 // are. The upsampling finish (SPEC §6.8): the working-size finish, and behind it S2's output upsampled onto the original source into full->out
 // region (nullable; SPEC §6.11 rule 3): the run is masked — the compose with the source takes the place of Lab -> BGR, at the working size with region's mask and source, in
 // the exact finish with full's
-struct region_fin { const uint8_t* mask; const uint8_t* s_bgr; int protect; };
+// mask0 (null: full's own): with a reference mask (SPEC §6.12 rule 5) the target mask F at full's size
+struct region_fin { const uint8_t* mask; const uint8_t* s_bgr; int protect; const uint8_t* mask0 = nullptr; };
 NCT_LOCAL int finish_level(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int H, int W, const uint8_t* s_lab_full, uint8_t* out_lab, uint8_t* out_bgr,
                            const full_target* full, const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube, const region_fin* region = nullptr);
 // ---- nct_seq.cpp

@@ -81,6 +81,21 @@ __device__ __forceinline__ LinCoef lin_coef(int d, int ssize, int dsize) {
     return LinCoef{s, 1.f - f, f, tail};
 }
 
+// 8UC1 bilinear, one destination pixel of a sh x sw image: cv::resize's 11-bit fixed-point chain (weights rounded to 1/2048, >> 4, * b, >> 16, + 2, >> 2) — the arithmetic
+// of k_resize_u8c3 / k_resize_u8c1 on one byte, for kernels that resize inside another step
+__device__ __forceinline__ int resize_u8_px(const unsigned char* __restrict__ src, int sh, int sw, int dy, int dx, int dh, int dw) {
+    const LinCoef cx = lin_coef(dx, sw, dw), cy = lin_coef(dy, sh, dh);
+    const int a0 = (short)(int)rintf(cx.a0 * 2048.f), a1 = (short)(int)rintf(cx.a1 * 2048.f);
+    const int b0 = (short)(int)rintf(cy.a0 * 2048.f), b1 = (short)(int)rintf(cy.a1 * 2048.f);
+    const int sy0 = cy.s, sy1 = min(cy.s + 1, sh - 1);
+    const int sx1 = min(cx.s + 1, sw - 1);
+    const int p00 = src[(size_t)sy0 * sw + cx.s], p01 = src[(size_t)sy0 * sw + sx1];
+    const int p10 = src[(size_t)sy1 * sw + cx.s], p11 = src[(size_t)sy1 * sw + sx1];
+    const int r0 = cx.tail ? p00 * 2048 : p00 * a0 + p01 * a1;
+    const int r1 = cx.tail ? p10 * 2048 : p10 * a0 + p11 * a1;
+    return (uint8_t)((((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2);
+}
+
 // 64FC3 bilinear, one channel of one destination pixel from its four taps: float weights, double accumulation, horizontal then vertical
 __device__ __forceinline__ double resize_f64_px(double p00, double p01, double p10, double p11, const LinCoef& cx, const LinCoef& cy) {
     const double a0 = (double)cx.a0, a1 = (double)cx.a1, b0 = (double)cy.a0, b1 = (double)cy.a1;

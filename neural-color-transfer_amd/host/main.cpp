@@ -122,6 +122,7 @@ struct Config { std::string input_dir, output_dir, model_dir; nct_params prm; bo
                 int finish = NCT_FINISH_EXACT;          // -fullres 1 / 2: the exact or the upsampling finish (SPEC §6.1 / §6.8)
                 bool upguide = false; nct_guided_params gp;   // -upguide 1, -upsigma: the guided modifier of the upsampling finish (SPEC §6.10), set on every context
                 int seqfull = 0;
+                std::string refmask_dir;                  // -refmask <dir>: reference region masks by reference file name (SPEC §6.12)
                 std::string mask_dir; int maskprotect = 0; };   // -mask <dir>: region masks by content file name (SPEC §6.11), -maskprotect 0 / 1                      // -seqfull 1 / 2: full-resolution sequences (SPEC §6.9) with the exact or the upsampling finish   // -lut N (0 = off), -lutlambda (0 = the library's default), -lutfull 1
 
 // ---- ENABLE_VIS debug outputs (Config.h:8) behind the runtime flag -vis 1: per pyramid level the flow maps of both NNFs (reconstruct_flow,
@@ -163,9 +164,18 @@ bool save_level_masks(nct_ctx* ctx, const uint8_t* mask, int h, int w, int level
     }
     return true;
 }
-// mask (nullable): the content image's region mask, cnt.h x cnt.w; the line then runs masked (SPEC §6.11)
+// -refmask with -vis 1: the pulled masks P_l of a line (SPEC §6.12 rules 2-3) as 8-bit grey images <pre>_refmask_<l>.png
+bool save_level_pulls(const std::vector<std::vector<uint8_t>>& P, const int* ah, const int* aw, int levels, const std::string& pre, std::string& err) {
+    for (int l = 0; l < levels; ++l) {
+        char name[1200]; std::string e;
+        snprintf(name, sizeof name, "%s_refmask_%d.png", pre.c_str(), l);
+        if (!pngio::write(name, P[l].data(), ah[l], aw[l], e, 1)) { err = "cannot write the -vis images"; return false; }
+    }
+    return true;
+}
+// mask (nullable): the content image's region mask, cnt.h x cnt.w; the line then runs masked (SPEC §6.11). refmask (nullable): the reference's, stl.h x stl.w (SPEC §6.12)
 bool run_with_vis(nct_ctx* ctx, const ImageBGR& cnt, const ImageBGR& stl, const nct_params& prm, const std::string& pre, uint8_t* out, nct_pair_timing* tm, std::string& err,
-                  const uint8_t* mask = nullptr, const nct_region_params* region = nullptr) {
+                  const uint8_t* mask = nullptr, const nct_region_params* region = nullptr, const uint8_t* refmask = nullptr) {
     int ah[5], aw[5], bh[5], bw[5];
     { int h = cnt.h, w = cnt.w, h2 = stl.h, w2 = stl.w;
       for (int t = 0; t < 5; ++t) { ah[4 - t] = h; aw[4 - t] = w; bh[4 - t] = h2; bw[4 - t] = w2; h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; h2 = (h2 - 1) / 2 + 1; w2 = (w2 - 1) / 2 + 1; } }
@@ -186,9 +196,16 @@ bool run_with_vis(nct_ctx* ctx, const ImageBGR& cnt, const ImageBGR& stl, const 
         errm[l].resize((size_t)ah[l] * aw[l]); result[l].resize((size_t)cnt.h * cnt.w * 3);
         lv.ann[l] = ann[l].data(); lv.bnn[l] = bnn[l].data(); lv.guide[l] = guide[l].data(); lv.err[l] = errm[l].data(); lv.result[l] = result[l].data();
     }
+    // a masked reference (SPEC §6.12): the run's own pulled masks P_l come back per level
+    std::vector<std::vector<uint8_t>> P(5);
+    nct_ref_region_levels rl; memset(&rl, 0, sizeof rl);
+    for (int l = 0; l < prm.levels && refmask; ++l) { P[l].resize((size_t)ah[l] * aw[l]); rl.pulled[0][l] = P[l].data(); }
     if (nct_pair_upload(ctx, cnt.px.data(), cnt.h, cnt.w, stl.px.data(), stl.h, stl.w) != NCT_OK || (mask && nct_pair_set_region(ctx, mask, region) != NCT_OK) ||
-        nct_pair_run_levels(ctx, &prm, tm, &lv) != NCT_OK || nct_pair_download(ctx, out) != NCT_OK) { err = nct_last_error(ctx); return false; }
+        (refmask && nct_pair_set_ref_region(ctx, 0, refmask, region) != NCT_OK) ||
+        (refmask ? nct_pair_run_ref_region_levels(ctx, &prm, tm, &lv, &rl) : nct_pair_run_levels(ctx, &prm, tm, &lv)) != NCT_OK ||
+        nct_pair_download(ctx, out) != NCT_OK) { err = nct_last_error(ctx); return false; }
     if (mask && !save_level_masks(ctx, mask, cnt.h, cnt.w, prm.levels, pre, err)) return false;
+    if (refmask && !save_level_pulls(P, ah, aw, prm.levels, pre, err)) return false;
     // level images: the progressive bilinear pyramid of main.cu:104-108
     simg[4] = cnt.px; rimg[4] = stl.px;
     for (int l = 3; l >= 0; --l) {
@@ -283,7 +300,7 @@ bool run_with_vis(nct_ctx* ctx, const ImageBGR& cnt, const ImageBGR& stl, const 
 // the level intermediates a line with several references shows under -vis 1: per level the label map as an 8-bit grey image (label * (255 / max(K - 1, 1))), the merged
 // guidance image and the intermediate result, named like run_with_vis's dumps (<pre>_label_<l>.png, <pre>_guide_<l>.png, <pre>_result_<l>.png)
 bool run_multi_with_vis(nct_ctx* ctx, const ImageBGR& cnt, int K, const uint8_t* const* px, const int* rh, const int* rw, const nct_params& prm, const std::string& pre, uint8_t* out,
-                        nct_pair_timing* tm, std::string& err, const uint8_t* mask = nullptr, const nct_region_params* region = nullptr) {
+                        nct_pair_timing* tm, std::string& err, const uint8_t* mask = nullptr, const nct_region_params* region = nullptr, const uint8_t* const* refmasks = nullptr) {
     int ah[5], aw[5];
     { int h = cnt.h, w = cnt.w; for (int t = 0; t < 5; ++t) { ah[4 - t] = h; aw[4 - t] = w; h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; } }
     std::vector<std::vector<uint8_t>> label(5), guide(5), result(5);
@@ -292,9 +309,27 @@ bool run_multi_with_vis(nct_ctx* ctx, const ImageBGR& cnt, int K, const uint8_t*
         label[l].resize((size_t)ah[l] * aw[l]); guide[l].resize((size_t)ah[l] * aw[l] * 3); result[l].resize((size_t)cnt.h * cnt.w * 3);
         lv.label[l] = label[l].data(); lv.guide[l] = guide[l].data(); lv.result[l] = result[l].data();
     }
-    if (nct_multi_upload(ctx, cnt.px.data(), cnt.h, cnt.w, K, px, rh, rw) != NCT_OK || (mask && nct_pair_set_region(ctx, mask, region) != NCT_OK) ||
-        nct_multi_run_levels(ctx, &prm, tm, &lv) != NCT_OK || nct_pair_download(ctx, out) != NCT_OK) { err = nct_last_error(ctx); return false; }
+    if (nct_multi_upload(ctx, cnt.px.data(), cnt.h, cnt.w, K, px, rh, rw) != NCT_OK || (mask && nct_pair_set_region(ctx, mask, region) != NCT_OK)) { err = nct_last_error(ctx); return false; }
+    // masked references (SPEC §6.12): their pulled masks come back per level and are merged by the label map below
+    std::vector<std::vector<uint8_t>> pulled[NCT_MAX_REFS];
+    nct_ref_region_levels rl; memset(&rl, 0, sizeof rl);
+    for (int k = 0; k < K && refmasks; ++k) {
+        if (!refmasks[k]) continue;
+        if (nct_pair_set_ref_region(ctx, k, refmasks[k], region) != NCT_OK) { err = nct_last_error(ctx); return false; }
+        pulled[k].resize(5);
+        for (int l = 0; l < prm.levels; ++l) { pulled[k][l].resize((size_t)ah[l] * aw[l]); rl.pulled[k][l] = pulled[k][l].data(); }
+    }
+    if ((refmasks ? nct_multi_run_ref_region_levels(ctx, &prm, tm, &lv, &rl) : nct_multi_run_levels(ctx, &prm, tm, &lv)) != NCT_OK ||
+        nct_pair_download(ctx, out) != NCT_OK) { err = nct_last_error(ctx); return false; }
     if (mask && !save_level_masks(ctx, mask, cnt.h, cnt.w, prm.levels, pre, err)) return false;
+    if (refmasks) {
+        std::vector<std::vector<uint8_t>> P(5);
+        for (int l = 0; l < prm.levels; ++l) {
+            P[l].resize((size_t)ah[l] * aw[l]);
+            for (size_t i = 0; i < P[l].size(); ++i) { const auto& pk = pulled[K > 1 ? label[l][i] : 0]; P[l][i] = pk.empty() ? 255 : pk[l][i]; }
+        }
+        if (!save_level_pulls(P, ah, aw, prm.levels, pre, err)) return false;
+    }
     const int step = 255 / std::max(K - 1, 1);
     for (int l = 0; l < prm.levels; ++l) {
         for (uint8_t& v : label[l]) v = (uint8_t)(v * step);
@@ -348,6 +383,8 @@ struct Job {
     ImageBGR cnt; std::vector<uint8_t> out;
     ImageBGR orig;                                               // -lutfull 1: the content image as decoded, before the shrink to MAX_SIZE
     std::vector<float> lut; std::vector<uint8_t> lut_out;       // -lut N: the job's table; -lutfull 1: the table on `orig`
+    std::vector<std::vector<uint8_t>> refmask;                   // -refmask: per reference its region mask, one byte per pixel of refs[k] (empty: that reference has none)
+    bool ref_masked() const { for (const auto& q : refmask) if (!q.empty()) return true; return false; }
     std::vector<uint8_t> mask;                                   // -mask: the content image's region mask, one byte per pixel of cnt (empty: the line has none)
     int orig_h = 0, orig_w = 0;                                  // cnt's size as decoded, before run_pair's shrink (the mask's size until it is shrunk too)
     int lut_n = 0; std::string lut_err;                          // the table's size; why the job has no table (its result image is written all the same)
@@ -413,7 +450,9 @@ bool job_lut(nct_ctx* ctx, const Config& cfg, Job& j) {
     if (cfg.lut_lambda > 0.0) lp.lambda = cfg.lut_lambda;
     j.lut.resize((size_t)lp.size * lp.size * lp.size * 3);
     // a masked line's table is fitted over its region (SPEC §6.11 rule 7); without a mask this is nct_lut_fit
-    int rc = nct_lut_fit_masked(ctx, j.cnt.px.data(), j.out.data(), j.mask.empty() ? nullptr : j.mask.data(), (size_t)j.cnt.h * j.cnt.w, &lp, j.lut.data(), nullptr);
+    // a line with a reference mask: over the last level's target mask, which the context that has just run the line still holds (SPEC §6.12 rule 7)
+    int rc = j.ref_masked() ? nct_pair_fit_lut(ctx, &lp, j.lut.data())
+                            : nct_lut_fit_masked(ctx, j.cnt.px.data(), j.out.data(), j.mask.empty() ? nullptr : j.mask.data(), (size_t)j.cnt.h * j.cnt.w, &lp, j.lut.data(), nullptr);
     if (rc == NCT_OK && cfg.lutfull) {
         j.lut_out.resize(j.orig.px.size());
         rc = nct_lut_apply(ctx, j.lut.data(), lp.size, j.orig.px.data(), (size_t)j.orig.h * j.orig.w, j.lut_out.data());
@@ -471,6 +510,29 @@ void load_pair(const Config& cfg, Job& j, bool in_seq = false) {
         if (!imgio::read(refStr, j.refs[k], err)) { j.say("Error: Fail reading style image: %s\n", refStr.c_str()); j.err = "cannot read style image: " + err; j.state = Job::FAILED; return; }
         j.say("Read style file: %s, w = %d, h = %d\n", refStr.c_str(), j.refs[k].w, j.refs[k].h);
     }
+    if (!cfg.refmask_dir.empty()) {
+        // -refmask <dir>: a reference in/y.png uses <dir>/y.png (or .jpg) where it exists; the mask has the reference's size as decoded and is its file's first channel
+        j.refmask.resize(j.refs.size());
+        for (size_t k = 0; k < j.refs.size(); ++k) {
+            const std::string st = stem(cfg.input_dir + "/" + j.p.refs[k]);
+            for (const char* ext : {".png", ".jpg"}) {
+                const std::string mpath = cfg.refmask_dir + "/" + st + ext;
+                FILE* f = fopen(mpath.c_str(), "rb");
+                if (!f) continue;
+                fclose(f);
+                ImageBGR m;
+                if (!imgio::read(mpath, m, err)) { j.say("Error: Fail reading mask image: %s\n", mpath.c_str()); j.err = "cannot read mask image: " + err; j.state = Job::FAILED; return; }
+                if (m.h != j.refs[k].h || m.w != j.refs[k].w) {
+                    char why[400]; snprintf(why, sizeof why, "-refmask: %s is %d x %d, the style image %d x %d", mpath.c_str(), m.w, m.h, j.refs[k].w, j.refs[k].h);
+                    j.say("Error: %s\n", why); j.err = why; j.state = Job::FAILED; return;
+                }
+                j.refmask[k].resize((size_t)m.h * m.w);
+                for (size_t i = 0; i < j.refmask[k].size(); ++i) j.refmask[k][i] = m.px[3 * i + 2];
+                j.say("Read reference mask file: %s\n", mpath.c_str());
+                break;
+            }
+        }
+    }
 }
 
 // the reference's per-level lines (main.cu:331; ColorTransfer.cpp:1373,1434), then its total (main.cu:453); the decoded inputs are dropped
@@ -496,7 +558,10 @@ void run_pair(nct_ctx* ctx, const Config& cfg, Job& j) {
     if (cfg.fullres) {                                          // -fullres 1 / 2: the library shrinks both images itself and returns the content image at its own size
         const ImageBGR& stl = j.refs[0];
         j.out.resize((size_t)j.cnt.h * j.cnt.w * 3);
-        const int rc = nct_process_pair_fullres_finish_region(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, mask, stl.px.data(), stl.h, stl.w, MAX_SIZE, cfg.finish, &region, &prm,
+        // a reference mask (SPEC §6.12) goes in at the reference's original size and takes the exact finish: -fullres 2 with -refmask was refused at the start
+        const int rc = (!j.refmask.empty() && !j.refmask[0].empty()) ? nct_process_pair_fullres_ref_region(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, mask, stl.px.data(), stl.h, stl.w, j.refmask[0].data(), MAX_SIZE,
+                                                                            &region, &prm, j.out.data(), &tm)
+                                      : nct_process_pair_fullres_finish_region(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, mask, stl.px.data(), stl.h, stl.w, MAX_SIZE, cfg.finish, &region, &prm,
                                                               j.out.data(), &tm);
         if (rc != NCT_OK) { j.say("Error: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
         if (!job_lut(ctx, cfg, j)) return;
@@ -506,13 +571,23 @@ void run_pair(nct_ctx* ctx, const Config& cfg, Job& j) {
     if (cfg.lutfull) j.orig = j.cnt;
     j.orig_h = j.cnt.h; j.orig_w = j.cnt.w;
     bool shrunk = shrink(ctx, j.cnt);
-    for (auto& r : j.refs) shrunk = shrunk && shrink(ctx, r);
+    // a mask shrinks with its image, by the same routine on the replicated three-channel image (= the single-channel resize, SPEC §6.11 rule 1)
+    auto shrink_mask = [&](std::vector<uint8_t>& mk, int oh, int ow) {
+        ImageBGR m; m.h = oh; m.w = ow; m.px.resize(mk.size() * 3);
+        for (size_t i = 0; i < mk.size(); ++i) m.px[3 * i] = m.px[3 * i + 1] = m.px[3 * i + 2] = mk[i];
+        if (!shrink(ctx, m)) return false;
+        mk.resize((size_t)m.h * m.w);
+        for (size_t i = 0; i < mk.size(); ++i) mk[i] = m.px[3 * i];
+        return true;
+    };
+    for (size_t k = 0; k < j.refs.size(); ++k) {
+        const int oh = j.refs[k].h, ow = j.refs[k].w;
+        shrunk = shrunk && shrink(ctx, j.refs[k]);
+        if (shrunk && k < j.refmask.size() && !j.refmask[k].empty() && (oh != j.refs[k].h || ow != j.refs[k].w)) shrunk = shrink_mask(j.refmask[k], oh, ow);
+    }
     if (mask && j.mask.size() != (size_t)j.cnt.h * j.cnt.w) {
-        // the mask shrinks with its image, by the same routine on the replicated three-channel image (= the single-channel resize, SPEC §6.11 rule 1)
-        ImageBGR m; m.h = j.orig_h; m.w = j.orig_w; m.px.resize(j.mask.size() * 3);
-        for (size_t i = 0; i < j.mask.size(); ++i) m.px[3 * i] = m.px[3 * i + 1] = m.px[3 * i + 2] = j.mask[i];
-        shrunk = shrunk && shrink(ctx, m);
-        if (shrunk) { j.mask.resize((size_t)m.h * m.w); for (size_t i = 0; i < j.mask.size(); ++i) j.mask[i] = m.px[3 * i]; mask = j.mask.data(); }
+        shrunk = shrunk && shrink_mask(j.mask, j.orig_h, j.orig_w);
+        if (shrunk) mask = j.mask.data();
     }
     if (!shrunk) { j.say("Error: resize failed: %s\n", nct_last_error(ctx)); j.err = nct_last_error(ctx); j.state = Job::FAILED; return; }
     j.out.resize((size_t)j.cnt.h * j.cnt.w * 3);
@@ -522,12 +597,18 @@ void run_pair(nct_ctx* ctx, const Config& cfg, Job& j) {
     for (int k = 0; k < K; ++k) { px[k] = j.refs[k].px.data(); rh[k] = j.refs[k].h; rw[k] = j.refs[k].w; }
     std::string err;
     bool ok;
+    std::vector<const uint8_t*> qs(K, nullptr);                 // -refmask: the references' masks (SPEC §6.12); null: that reference has none
+    for (int k = 0; k < K && k < (int)j.refmask.size(); ++k) if (!j.refmask[k].empty()) qs[k] = j.refmask[k].data();
+    const uint8_t* const* refmasks = j.ref_masked() ? qs.data() : nullptr;
     if (cfg.vis) {
         std::string pre(j.name); pre.resize(pre.size() - 4);    // the output file's stem
-        ok = K > 1 ? run_multi_with_vis(ctx, j.cnt, K, px.data(), rh.data(), rw.data(), prm, pre, j.out.data(), &tm, err, mask, &region)
-                   : run_with_vis(ctx, j.cnt, j.refs[0], prm, pre, j.out.data(), &tm, err, mask, &region);
+        ok = K > 1 ? run_multi_with_vis(ctx, j.cnt, K, px.data(), rh.data(), rw.data(), prm, pre, j.out.data(), &tm, err, mask, &region, refmasks)
+                   : run_with_vis(ctx, j.cnt, j.refs[0], prm, pre, j.out.data(), &tm, err, mask, &region, qs[0]);
     } else {
-        if (mask && K > 1)
+        if (refmasks)
+            ok = (K > 1 ? nct_process_multi_ref_region(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, mask, K, px.data(), rh.data(), rw.data(), refmasks, &region, &prm, j.out.data(), &tm)
+                        : nct_process_pair_ref_region(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, mask, px[0], rh[0], rw[0], qs[0], &region, &prm, j.out.data(), &tm)) == NCT_OK;
+        else if (mask && K > 1)
             ok = nct_multi_upload(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, K, px.data(), rh.data(), rw.data()) == NCT_OK && nct_pair_set_region(ctx, mask, &region) == NCT_OK &&
                  nct_multi_run(ctx, &prm, &tm) == NCT_OK && nct_pair_download(ctx, j.out.data()) == NCT_OK;
         else if (mask) ok = nct_process_pair_region(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, mask, px[0], rh[0], rw[0], &region, &prm, j.out.data(), &tm) == NCT_OK;
@@ -822,7 +903,8 @@ int main(int argc, char** argv) {
     cl.add("lut", lut, "[extension] N in {3, 5, 9, 17, 33, 65}: beside each result image write <same name>.cube, a 3D look-up table of N^3 nodes fitted from the source and the result (SPEC 6.6); works in every mode.");
     cl.add("lutlambda", lutlambda, "[extension] -lut N: smoothness weight of the table's fit (> 0; default: the library's, 0.1).");
     cl.add("mask", cfg.mask_dir, "[extension] directory of region masks (SPEC 6.11): a content image in/x.png is recoloured only where <dir>/x.png (or .jpg; its first channel, the content image's size) is not 0 — 255 = the full transfer, between = partial; a line without a mask file runs as without -mask; works with -fullres 1, several references, -lut, -lutfull and -vis 1; not with -fullres 2 or -seq 1.");
-    cl.add("maskprotect", cfg.maskprotect, "[extension] -mask: 1 = a pixel whose mask is 0 never changes (default 0: the transition follows the image's own edges and may reach such pixels).");
+    cl.add("refmask", cfg.refmask_dir, "[extension] directory of reference region masks (SPEC 6.12): colours are taken only from where <dir>/y.png (or .jpg; its first channel, the style image's size) of a style image in/y.png is not 0 — 255 = allowed, between = partial; a style image without a mask file counts as allowed everywhere; combines with -mask, -maskprotect, -fullres 1, several references, -lut, -lutfull and -vis 1; not with -fullres 2 or -seq 1.");
+    cl.add("maskprotect", cfg.maskprotect, "[extension] -mask / -refmask: 1 = a pixel whose mask is 0 never changes (default 0: the transition follows the image's own edges and may reach such pixels).");
     cl.add("lutfull", lutfull, "[extension] -lut N: 1 = also write <name>_lut.png, the table applied to the content image at its original size; not with -fullres 1.");
     // parser self-test hook (no GPU): `--parse-only <args…>` parses the rest like a normal run and prints what main would go on with, in the format of
     // oracle/ref_cmdline.cpp (the reference's own parser): tests/test_cli.py compares the two on the vectors of tests/golden/cmdline_ref.json
@@ -865,7 +947,9 @@ int main(int argc, char** argv) {
     if (autokey && (cfg.ap.max_gap < 1 || cfg.ap.max_gap > 1000)) { printf("Error: -keygap %d is not in [1, 1000].\n", cfg.ap.max_gap); return -1; }
     for (int a = 1; a < argc; ++a) lutlambda_set = lutlambda_set || !strcmp(argv[a], "-lutlambda");
     if (cfg.maskprotect != 0 && cfg.maskprotect != 1) { printf("Error: -maskprotect %d is not one of 0, 1.\n", cfg.maskprotect); return -1; }
-    if (cfg.maskprotect && cfg.mask_dir.empty()) { printf("Error: -maskprotect 1 needs -mask <dir>.\n"); return -1; }
+    if (cfg.maskprotect && cfg.mask_dir.empty() && cfg.refmask_dir.empty()) { printf("Error: -maskprotect 1 needs -mask <dir> or -refmask <dir>.\n"); return -1; }
+    if (!cfg.refmask_dir.empty() && fullres == 2) { printf("Error: -refmask cannot be combined with -fullres 2 (a reference mask with the upsampling finish is not defined, SPEC 6.12); use -fullres 1.\n"); return -1; }
+    if (!cfg.refmask_dir.empty() && seq) { printf("Error: -refmask cannot be combined with -seq 1 (sequences with a reference mask are not defined, SPEC 6.12).\n"); return -1; }
     if (!cfg.mask_dir.empty() && fullres == 2) { printf("Error: -mask cannot be combined with -fullres 2 (a mask with the upsampling finish is not defined, SPEC 6.11); use -fullres 1.\n"); return -1; }
     if (!cfg.mask_dir.empty() && seq) { printf("Error: -mask cannot be combined with -seq 1 (sequences with a region mask are not defined, SPEC 6.11).\n"); return -1; }
     if (lut != 0 && lut != 3 && lut != 5 && lut != 9 && lut != 17 && lut != 33 && lut != 65) { printf("Error: -lut %d is not one of 3, 5, 9, 17, 33, 65.\n", lut); return -1; }

@@ -153,6 +153,16 @@ SIGNATURES = {
                                                          C.c_void_p]),
     "nct_lut_fit_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_lut_fit_masked_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_region_pull": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
+    "nct_region_pull_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
+    "nct_pair_set_ref_region": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "nct_multi_run_ref_region_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_pair_run_ref_region_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_process_pair_ref_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_process_multi_ref_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p),
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_process_pair_fullres_ref_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p]),
     "nct_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "nct_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nct_dev_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -342,6 +352,11 @@ class RegionLevels(C.Structure):
     _fields_ = [("ab_mix", C.c_void_p * 5), ("mask", C.c_void_p * 5)]
 
 
+class RefRegionLevels(C.Structure):
+    """struct nct_ref_region_levels (include/nct.h)."""
+    _fields_ = [("ref_mask", (C.c_void_p * 5) * MAX_REFS), ("pulled", (C.c_void_p * 5) * MAX_REFS), ("mask", C.c_void_p * 5), ("mask_full", C.c_void_p * 5), ("ab_mix", C.c_void_p * 5)]
+
+
 def _region_params(protect):
     p = RegionParams.default()
     if protect is not None:
@@ -350,10 +365,10 @@ def _region_params(protect):
 
 
 def _mask_arg(mask, shape, what):
-    """a region mask as contiguous bytes of the source's h x w; a mask of another size is refused here: the C entry points take the source's size for it"""
+    """a region mask as contiguous bytes of its image's h x w (shape: that image's); a mask of another size is refused here: the C entry points take the image's size for it"""
     m = np.ascontiguousarray(mask, np.uint8)
     if m.shape != tuple(shape[:2]):
-        raise NctError(-2, f"{what}: mask is {m.shape[1] if m.ndim == 2 else '?'}x{m.shape[0] if m.ndim else '?'}, the source {shape[1]}x{shape[0]}")
+        raise NctError(-2, f"{what}: mask is {m.shape[1] if m.ndim == 2 else '?'}x{m.shape[0] if m.ndim else '?'}, its image {shape[1]}x{shape[0]}")
     return m
 
 
@@ -871,6 +886,14 @@ class Context:
         """nct_multi_run_levels on the uploaded list -> dict: per reference and level "ann", "bnn", "annd", "bnnd", "ref_guide", "ref_err" ([k][l]); per level the merged
         "label", "guide", "err", "result" ([l]); "labels" (k-means), "timing". Level 0 = coarsest."""
         prm = params or Params.default()
+        keep, lv = self._multi_levels_arrays()
+        tm = PairTiming()
+        self._chk(self._l.nct_multi_run_levels(self._h, C.addressof(prm), C.addressof(tm), C.addressof(lv)))
+        keep["timing"] = tm.as_dict()
+        return keep
+
+    def _multi_levels_arrays(self):
+        """the host arrays nct_multi_levels points into -> (dict of them + "labels", "adims", "bdims", the MultiLevels)"""
         H, W = self._pair_shape[:2]
         K = len(self._multi_shapes)
 
@@ -901,11 +924,112 @@ class Context:
                 getattr(lv, name)[l] = keep[name][-1].ctypes.data
         labels = np.zeros(adims[0], np.int32)
         lv.labels = labels.ctypes.data
-        tm = PairTiming()
-        self._chk(self._l.nct_multi_run_levels(self._h, C.addressof(prm), C.addressof(tm), C.addressof(lv)))
         keep["labels"] = labels
+        keep["adims"], keep["bdims"] = adims, bdims
+        return keep, lv
+
+    # ---- reference region masks (SPEC §6.12)
+    def region_pull(self, q_mask, ann, bnn, w_coh=1.0, w_comp=2.0):
+        """nct_region_pull (SPEC §6.12 rule 2): q_mask [bh, bw] bytes, ann [ah, aw] and bnn [bh, bw] NNF words -> the pulled mask [ah, aw]"""
+        q, a, b = np.ascontiguousarray(q_mask, np.uint8), np.ascontiguousarray(ann, np.uint32), np.ascontiguousarray(bnn, np.uint32)
+        if q.shape != b.shape:
+            raise NctError(-2, f"region_pull: mask is {q.shape}, bnn {b.shape}")
+        out = np.empty(a.shape, np.uint8)
+        self._chk(self._l.nct_region_pull(self._h, q.ctypes.data, q.shape[0], q.shape[1], a.ctypes.data, b.ctypes.data, a.shape[0], a.shape[1], w_coh, w_comp, out.ctypes.data))
+        return out
+
+    def region_pull_dev(self, q_mask, ann, bnn, w_coh=1.0, w_comp=2.0):
+        """the same through nct_region_pull_dev on arena blocks"""
+        q, a, b = np.ascontiguousarray(q_mask, np.uint8), np.ascontiguousarray(ann, np.uint32), np.ascontiguousarray(bnn, np.uint32)
+        if q.shape != b.shape:
+            raise NctError(-2, f"region_pull_dev: mask is {q.shape}, bnn {b.shape}")
+        blocks = [self.dev_upload(q), self.dev_upload(a), self.dev_upload(b), self.dev_alloc(a.size)]
+        try:
+            self._chk(self._l.nct_region_pull_dev(self._h, blocks[0], q.shape[0], q.shape[1], blocks[1], blocks[2], a.shape[0], a.shape[1], w_coh, w_comp, blocks[3]))
+            return self.dev_download(blocks[3], a.shape, np.uint8)
+        finally:
+            self.synchronize()
+            for p in blocks:
+                self.dev_free(p)
+
+    def pair_set_ref_region(self, k, mask, protect=None):
+        """nct_pair_set_ref_region on the uploaded references: reference k's mask [rh, rw] bytes, or None to remove it; protect None leaves the run's protect as it is"""
+        rg = None if protect is None else _region_params(protect)
+        if mask is None:
+            self._chk(self._l.nct_pair_set_ref_region(self._h, int(k), None, None if rg is None else C.addressof(rg)))
+            return
+        shapes = getattr(self, "_multi_shapes", [])
+        m = np.ascontiguousarray(mask, np.uint8)
+        if 0 <= k < len(shapes):                        # the library refuses a k out of range
+            m = _mask_arg(mask, shapes[k], "pair_set_ref_region")
+        self._chk(self._l.nct_pair_set_ref_region(self._h, int(k), m.ctypes.data, None if rg is None else C.addressof(rg)))
+
+    def multi_run_ref_region_levels(self, params=None):
+        """nct_multi_run_ref_region_levels on the uploaded, masked list -> multi_run_levels' dict plus "ref_mask" and "pulled" ([k][l]; unmasked references stay zero),
+        "mask" [h, w], "mask_full" [H, W] and "ab_mix" [2, h*w, 3] per level"""
+        prm = params or Params.default()
+        keep, lv = self._multi_levels_arrays()
+        H, W = self._pair_shape[:2]
+        rl = RefRegionLevels()
+        keep["ref_mask"] = [[np.zeros(d, np.uint8) for d in bd] for bd in keep["bdims"]]
+        keep["pulled"] = [[np.zeros(d, np.uint8) for d in keep["adims"]] for _ in keep["bdims"]]
+        keep["mask"] = [np.zeros(d, np.uint8) for d in keep["adims"]]
+        keep["mask_full"] = [np.zeros((H, W), np.uint8) for _ in range(5)]
+        keep["ab_mix"] = [np.zeros((2, d[0] * d[1], 3)) for d in keep["adims"]]
+        for l in range(5):
+            for k in range(len(keep["bdims"])):
+                rl.ref_mask[k][l] = keep["ref_mask"][k][l].ctypes.data; rl.pulled[k][l] = keep["pulled"][k][l].ctypes.data
+            rl.mask[l] = keep["mask"][l].ctypes.data; rl.mask_full[l] = keep["mask_full"][l].ctypes.data; rl.ab_mix[l] = keep["ab_mix"][l].ctypes.data
+        tm = PairTiming()
+        self._chk(self._l.nct_multi_run_ref_region_levels(self._h, C.addressof(prm), C.addressof(tm), C.addressof(lv), C.addressof(rl)))
         keep["timing"] = tm.as_dict()
         return keep
+
+    def process_pair_ref_region(self, src_bgr, src_mask, ref_bgr, ref_mask, protect=None, params=None, want_timing=False):
+        """nct_process_pair_ref_region: process_pair with a mask on the source ([h, w] of the source) and / or on the reference ([rh, rw]); both None: process_pair"""
+        s = np.ascontiguousarray(src_bgr, np.uint8)
+        r = np.ascontiguousarray(ref_bgr, np.uint8)
+        m = None if src_mask is None else _mask_arg(src_mask, s.shape, "process_pair_ref_region")
+        q = None if ref_mask is None else _mask_arg(ref_mask, r.shape, "process_pair_ref_region (reference)")
+        prm, rg = params or Params.default(), _region_params(protect)
+        out = np.empty_like(s)
+        tm = PairTiming() if want_timing else None
+        self._pair_shape = s.shape; self._multi_shapes = [r.shape]
+        self._chk(self._l.nct_process_pair_ref_region(self._h, s.ctypes.data, s.shape[0], s.shape[1], _ptr(m), r.ctypes.data, r.shape[0], r.shape[1], _ptr(q), C.addressof(rg),
+                                                      C.addressof(prm), out.ctypes.data, C.addressof(tm) if tm is not None else None))
+        return (out, tm.as_dict()) if want_timing else out
+
+    def process_multi_ref_region(self, src_bgr, src_mask, refs_bgr, ref_masks, protect=None, params=None, want_timing=False):
+        """nct_process_multi_ref_region: process_multi with a mask on the source and / or on some references (ref_masks: None, or a list with None entries)"""
+        s = np.ascontiguousarray(src_bgr, np.uint8)
+        K, keep, ptrs, hs, ws = self._ref_list(refs_bgr)
+        m = None if src_mask is None else _mask_arg(src_mask, s.shape, "process_multi_ref_region")
+        qs, qp = None, None
+        if ref_masks is not None:
+            if len(ref_masks) != K:
+                raise NctError(-2, f"process_multi_ref_region: {len(ref_masks)} masks for {K} references")
+            qs = [None if q is None else _mask_arg(q, keep[k].shape, "process_multi_ref_region (reference %d)" % k) for k, q in enumerate(ref_masks)]
+            qp = (C.c_void_p * max(K, 1))(*[None if q is None else q.ctypes.data for q in qs])
+        prm, rg = params or Params.default(), _region_params(protect)
+        out = np.empty_like(s)
+        tm = PairTiming() if want_timing else None
+        self._pair_shape = s.shape; self._multi_shapes = [a.shape for a in keep]
+        self._chk(self._l.nct_process_multi_ref_region(self._h, s.ctypes.data, s.shape[0], s.shape[1], _ptr(m), K, ptrs, hs, ws, qp, C.addressof(rg), C.addressof(prm), out.ctypes.data,
+                                                       C.addressof(tm) if tm is not None else None))
+        return (out, tm.as_dict()) if want_timing else out
+
+    def process_pair_fullres_ref_region(self, src_bgr, mask0, ref_bgr, ref_mask0, max_side=1000, protect=None, params=None, want_timing=False):
+        """nct_process_pair_fullres_ref_region (SPEC §6.12 rule 5): both masks at their images' original sizes; the exact finish"""
+        s = np.ascontiguousarray(src_bgr, np.uint8)
+        r = np.ascontiguousarray(ref_bgr, np.uint8)
+        m = None if mask0 is None else _mask_arg(mask0, s.shape, "process_pair_fullres_ref_region")
+        q = None if ref_mask0 is None else _mask_arg(ref_mask0, r.shape, "process_pair_fullres_ref_region (reference)")
+        prm, rg = params or Params.default(), _region_params(protect)
+        out = np.empty_like(s)
+        tm = PairTiming() if want_timing else None
+        self._chk(self._l.nct_process_pair_fullres_ref_region(self._h, s.ctypes.data, s.shape[0], s.shape[1], _ptr(m), r.ctypes.data, r.shape[0], r.shape[1], _ptr(q), max_side,
+                                                              C.addressof(rg), C.addressof(prm), out.ctypes.data, C.addressof(tm) if tm is not None else None))
+        return (out, tm.as_dict()) if want_timing else out
 
     # ---- frame sequences (SPEC §6.3)
     def seq_begin(self, ref_bgr, src_shape, params=None, tau=None, sigma=None):
@@ -1287,6 +1411,7 @@ class Context:
         s = np.ascontiguousarray(src_bgr, np.uint8)
         r = np.ascontiguousarray(ref_bgr, np.uint8)
         self._pair_shape = s.shape
+        self._multi_shapes = [r.shape]
         self._chk(self._l.nct_pair_upload(self._h, s.reshape(-1, 3), s.shape[0], s.shape[1], r.reshape(-1, 3), r.shape[0], r.shape[1]))
 
     def pair_run(self, params=None, want_timing=False):
