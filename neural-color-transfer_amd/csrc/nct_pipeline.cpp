@@ -98,7 +98,7 @@ int finish_level(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int
                  const full_target* full, const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube, const region_fin* region) {
     if (full && full->finish == NCT_FINISH_EXACT) {
         NCT_TRY(nctk_color_finish(ctx, s, x, h, w, H, W, fl.s0, full->H, full->W, cp, fl.out0, dbg));
-        if (region) return nctk_region_compose(ctx, s, full->src, fl.s0, fl.out0, region->mask0 ? region->mask0 : full->mask, (size_t)full->H * full->W, region->protect, cube, full->out);
+        if (region) return nctk_region_compose(ctx, s, full->src, fl.s0, fl.out0, region->mask, (size_t)full->H * full->W, region->protect, cube, full->out);
         return nctk_lab2bgr(ctx, s, fl.out0, full->out, (size_t)full->H * full->W, cube);
     }
     const nct_finish_up up{full ? full->src : nullptr, full ? full->H : 0, full ? full->W : 0, full ? full->out : nullptr, cube, ctx->guided_sigma /* nct_set_finish_guided */};
@@ -149,8 +149,7 @@ struct pair_run {
     const full_target* const fin;                  // nullable: the last level finishes on the original source (finish_level)
     seq_state* const seq;                          // nullable: this run is a frame of the open sequence (SPEC §6.3) — the reference's pyramid and taps are borrowed, S1's output is blended
     const nct_seq_levels* const slv;               // nullable: where a frame's X'_t and tau_p maps go
-    const nct_region_levels* const rlv;            // nullable: where a masked run's level masks and mixed coefficients go (SPEC §6.11)
-    const nct_ref_region_levels* const qlv;        // nullable: the same for a run with a reference mask (SPEC §6.12)
+    const nct_ref_region_levels* const qlv;        // nullable: where a masked run's level masks and mixed coefficients go (SPEC §6.11, §6.12)
     pair_state* const P; const hipStream_t s;
     const int H, W, K, nlevels; const size_t N;
     const bool feat16, count;
@@ -168,19 +167,19 @@ struct pair_run {
     DevBuf<float> annd, err;
     DevBuf<uint8_t> guide, g_lab_l, out_lab;
     DevBuf<uint8_t> sel_label;                     // the selection's label map (rule 2); a pair allocates none of this
-    // the source's region mask (SPEC §6.11; null: none, and the run enqueues and reserves what it always did) and its level masks — the pyramid's single-channel form
+    // The run's masks (neither: the run enqueues and reserves what it always did). mask: the source's region mask (SPEC §6.11; null: none), mpyr / mimg: its level masks —
+    // the pyramid's single-channel form. ref_masked: a reference has a region mask (SPEC §6.12); p_merged: P_l of several references (rule 3), m_level: M_l where it is not
+    // P_l itself (rule 4: a source mask as well), f_level: F_l of a level that is not the last (the last level's is pair_state's fin_mask).
+    // What a level's colour stage reads of all that (level_masks, color_stage): m_l, the mix mask on the level grid, and f_l, the compose mask at the size its finish targets
     const uint8_t* const mask;
     DevBuf<uint8_t> mpyr[4]; const uint8_t* mimg[5] = {};
-    // reference region masks (SPEC §6.12; ref_masked false: the run enqueues and reserves what it always did). p_merged: P_l of several references (rule 3); m_level: M_l where
-    // it is not P_l itself (rule 4: a source mask as well); f_level: F_l of a level that is not the last (the last level's is pair_state's fin_mask). p_l / m_l / f_l: the
-    // current level's three masks, wherever they live
     const bool ref_masked;
     DevBuf<uint8_t> p_merged, m_level, f_level;
     const uint8_t *p_l = nullptr, *m_l = nullptr, *f_l = nullptr;
     const nct_color_params cp;
 
     pair_run(nct_ctx* c, const nct_params* p, nct_pair_timing* t, const run_extras& x)
-        : ctx(c), prm(p), timing(t), lv(x.lv ? x.lv : &kNoLevels), color(x.color), fin(x.fin), seq(x.seq), slv(x.slv), rlv(x.rlv), qlv(x.qlv), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
+        : ctx(c), prm(p), timing(t), lv(x.lv ? x.lv : &kNoLevels), color(x.color), fin(x.fin), seq(x.seq), slv(x.slv), qlv(x.qlv), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
           nlevels(p->levels), N((size_t)H * W), feat16((p->flags & NCT_FLAG_FEAT16) != 0), count(t && (p->flags & NCT_FLAG_COUNT_EVALS)), side(c), mask(x.seq ? nullptr : P->mask),
           ref_masked(!x.seq && P->ref_masked()), cp(nct_color_params_of(*p)) {}
 
@@ -388,7 +387,7 @@ struct pair_run {
                 for (int q = 0; q < K; ++q) { errs[q] = R[q].err; guides[q] = R[q].guide; }
                 NCT_TRY(nctk_select_reference(ctx, s, errs, guides, K, ah[l], aw[l], sel_label, guide, err));
             }
-            if (ref_masked && k == K - 1) NCT_TRY(level_masks(l));
+            if ((mask || ref_masked) && k == K - 1) NCT_TRY(level_masks(l));
             MARK(NCT_ST_VOTE, l);
             NCT_TRY(d2h(lv->ref_guide[k][l], guide_of(k), (size_t)na_px * 3));
             NCT_TRY(d2h(lv->ref_err[k][l], err_of(k), sizeof(float) * na_px));
@@ -400,22 +399,23 @@ struct pair_run {
         return d2h(lv->err[l], err, sizeof(float) * na_px);
     }
 
-    // SPEC §6.12 rules 3-4, behind the last reference's votes (and the selection): P_l = the pulled mask of the pixel's label, M_l = min(P_l, the source's level mask).
-    // One reference and no source mask: P_l and M_l are reference 0's pulled mask, no launch
+    // The level's mix mask m_l, behind the last reference's votes (and the selection). A source mask only (SPEC §6.11 rule 1): its level mask, no launch. With a reference mask
+    // (SPEC §6.12 rules 3-4): P_l = the pulled mask of the pixel's label, M_l = min(P_l, the source's level mask) — one reference and no source mask: both are reference 0's
+    // pulled mask, no launch
     int level_masks(int l) {
+        if (!ref_masked) { m_l = mimg[l]; return NCT_OK; }
         const int na_px = ah[l] * aw[l];
         const uint8_t* pulled[NCT_MAX_REFS];
         for (int k = 0; k < K; ++k) pulled[k] = R[k].qimg[4] ? (const uint8_t*)R[k].pulled : nullptr;
         p_l = K > 1 ? (const uint8_t*)p_merged : pulled[0];
         m_l = mask ? (const uint8_t*)m_level : p_l;
         if (K > 1 || mask) NCT_TRY(nctk_region_merge(ctx, s, pulled, K, sel_label, mimg[l], na_px, K > 1 ? (uint8_t*)p_merged : nullptr, mask ? (uint8_t*)m_level : nullptr));
-        if (!qlv) return NCT_OK;
-        for (int k = 0; k < K; ++k) {
+        for (int k = 0; k < K && qlv; ++k) {
             if (!R[k].qimg[4]) continue;
             NCT_TRY(d2h(qlv->ref_mask[k][l], R[k].qimg[l], (size_t)R[k].bh[l] * R[k].bw[l]));
             NCT_TRY(d2h(qlv->pulled[k][l], R[k].pulled, (size_t)na_px));
         }
-        return d2h(qlv->mask[l], m_l, (size_t)na_px);
+        return NCT_OK;
     }
 
     // level l's prebuilt part of S1's system with what the host knows about its hub blocks right now: the count, if the side stream has passed ev_level[l] (always, from
@@ -455,25 +455,27 @@ struct pair_run {
         NCT_TRY(nctk_color_nonlocal(ctx, s, err, side.slab[l], g_lab_l, side.knn_ids[l], side.knn_ws[l], l, ah[l], aw[l], H, W, cp, cb, d, &s1graph));
         // a frame of a sequence: the blend between S1 and the finish, which then reads the kept X'_t (SPEC §6.3 rule 3)
         if (seq) NCT_TRY(seq_level_step(ctx, s, seq, l, side.slab[l], cb.x, cb.tmap, slv));
-        // a masked run (SPEC §6.11 rule 2): S1's coefficients move toward the identity by the level mask, in place; the finish reads X' and composes with the source (rule 3)
-        region_fin rg{mask, P->src, P->protect};
-        if (ref_masked) {
-            // SPEC §6.12 rules 4-5: the mix by M_l; F_l at the size the finish targets — the last level's is kept for nct_pair_fit_lut (rule 7) — for the compose
-            const bool last = l == nlevels - 1;
+        // a masked run: S1's coefficients move toward the identity by the mix mask m_l, in place (SPEC §6.11 rule 2); the finish reads X' and composes with the source by f_l
+        // (rule 3), the mask at the size the finish targets. A source mask only: f_l is that mask as it came. With a reference mask (SPEC §6.12 rules 4-5): F_l = P_l at that
+        // size, then the minimum with the source's — the last level's is kept for nct_pair_fit_lut (rule 7)
+        const bool masked = mask || ref_masked;
+        if (masked) {
             const int fh = full ? full->H : H, fw = full ? full->W : W;
-            uint8_t* f = f_level;
-            if (last) { if (!(P->fin_mask = (uint8_t*)ctx->alloc((size_t)fh * fw))) return NCT_ERR_HIP; f = P->fin_mask; }
-            NCT_TRY(nctk_region_upsize_min(ctx, s, p_l, ah[l], aw[l], full ? full->mask : mask, f, fh, fw));
+            f_l = full ? full->mask : mask;
+            if (ref_masked) {
+                uint8_t* f = f_level;
+                if (l == nlevels - 1) { if (!(P->fin_mask = (uint8_t*)ctx->alloc((size_t)fh * fw))) return NCT_ERR_HIP; f = P->fin_mask; }
+                NCT_TRY(nctk_region_upsize_min(ctx, s, p_l, ah[l], aw[l], f_l, f, fh, fw));
+                f_l = f;
+            }
             NCT_TRY(nctk_region_mix(ctx, s, cb.x, m_l, ah[l], aw[l], cb.x));
-            if (qlv) { NCT_TRY(dbg_copy(ctx, s, qlv->ab_mix[l], (double*)cb.x, (size_t)6 * na_px)); NCT_TRY(dbg_copy(ctx, s, qlv->mask_full[l], f, (size_t)fh * fw)); }
-            if (rlv) { NCT_TRY(dbg_copy(ctx, s, rlv->ab_mix[l], (double*)cb.x, (size_t)6 * na_px)); NCT_TRY(dbg_copy(ctx, s, rlv->mask[l], m_l, (size_t)na_px)); }
-            rg.mask = f; rg.mask0 = f;
-        } else
-        if (mask) {
-            NCT_TRY(nctk_region_mix(ctx, s, cb.x, mimg[l], ah[l], aw[l], cb.x));
-            if (rlv) { NCT_TRY(dbg_copy(ctx, s, rlv->ab_mix[l], (double*)cb.x, (size_t)6 * na_px)); NCT_TRY(dbg_copy(ctx, s, rlv->mask[l], mimg[l], (size_t)na_px)); }
+            if (qlv) {
+                NCT_TRY(dbg_copy(ctx, s, qlv->ab_mix[l], (double*)cb.x, (size_t)6 * na_px)); NCT_TRY(dbg_copy(ctx, s, qlv->mask[l], m_l, (size_t)na_px));
+                NCT_TRY(dbg_copy(ctx, s, qlv->mask_full[l], f_l, (size_t)fh * fw));
+            }
         }
-        NCT_TRY(finish_level(ctx, s, seq ? seq->keep_x[l] : (double*)cb.x, ah[l], aw[l], H, W, s_lab_full, out_lab, P->out, full, fl, cp, d, nct_cube_form(*prm), (mask || ref_masked) ? &rg : nullptr));
+        const region_fin rg{f_l, P->src, P->protect};
+        NCT_TRY(finish_level(ctx, s, seq ? seq->keep_x[l] : (double*)cb.x, ah[l], aw[l], H, W, s_lab_full, out_lab, P->out, full, fl, cp, d, nct_cube_form(*prm), masked ? &rg : nullptr));
         if (cs && cs->wls_iters) for (int q = 0; q < 6; ++q) cs->wls_iters[q] = wls_it[q];
         if (timing) timing->wls_iters[l] = *std::max_element(wls_it, wls_it + 6);
         MARK(NCT_ST_COLOR, l);
@@ -522,9 +524,8 @@ int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timin
     NCT_REQUIRE(prm->levels >= 1 && prm->levels <= 5, "process: levels must be in [1, 5] (got %d)", prm->levels);
     NCT_REQUIRE(!x.fin || (!x.lv && !x.color), "process: no level intermediates with a full-resolution finish");
     NCT_REQUIRE(!x.color || P->K == 1, "process: nct_pair_levels describes a pair; several references report through nct_multi_levels");
-    if (x.rlv && !P->mask) return ctx->fail(NCT_ERR_STATE, "process: region levels asked for, but no region mask is set (nct_pair_set_region first)");
+    if (x.refusal) return ctx->fail(NCT_ERR_STATE, "%s", x.refusal);
     NCT_REQUIRE(!(P->mask && x.fin) || (x.fin->finish == NCT_FINISH_EXACT && x.fin->mask), "process: a region mask is defined for the exact full-resolution finish only");
-    if (x.qlv && !P->ref_masked()) return ctx->fail(NCT_ERR_STATE, "process: reference region levels asked for, but no reference mask is set (nct_pair_set_ref_region first)");
     NCT_REQUIRE(!(P->ref_masked() && x.fin) || x.fin->finish == NCT_FINISH_EXACT, "process: a reference region mask is defined for the exact full-resolution finish only");
     // a new run on the resident images: an earlier full-resolution run is no longer the last one, and its two original-size images go back to the arena
     // (a full-resolution sequence keeps its two for its whole life: SPEC §6.9 rule 6)
@@ -551,6 +552,12 @@ nct_multi_levels multi_levels_of(const nct_pair_levels& levels) {
     }
     m.labels = levels.labels;
     return m;
+}
+// a source-masked run's report (SPEC §6.11) is the part of the reference-masked one's that it has: M_l and X'
+static nct_ref_region_levels ref_region_levels_of(const nct_region_levels& levels) {
+    nct_ref_region_levels q = {};
+    for (int l = 0; l < 5; ++l) { q.ab_mix[l] = levels.ab_mix[l]; q.mask[l] = levels.mask[l]; }
+    return q;
 }
 
 // SPEC §6.1 rule 1 (host/main.cpp's shrink: the longer side becomes max_side, the other (int)(max_side / (float)long * short)) and the limits of rule 5
@@ -589,6 +596,39 @@ static int upload_images(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, i
     return NCT_OK;
 }
 
+// The run forms of the C ABI on the uploaded images, `who` for the refusal texts. Each form names the reports it was given: multi, or pair — a pair reports as the list of
+// one reference, its colour stages beside it — and region or ref_region, which describe the same masked run (SPEC §6.11, §6.12) and are refused without their mask
+struct run_form { const nct_multi_levels* multi = nullptr; const nct_pair_levels* pair = nullptr; const nct_region_levels* region = nullptr; const nct_ref_region_levels* ref_region = nullptr; };
+static int run_resident(nct_ctx* ctx, const char* who, const nct_params* prm, nct_pair_timing* timing, const run_form& f = {}) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(prm, "%s: null params", who);
+    const pair_state* P = (pair_state*)ctx->pair;
+    run_extras x; nct_multi_levels m; nct_ref_region_levels q;
+    x.lv = f.multi;
+    if (f.pair) { m = multi_levels_of(*f.pair); x.lv = &m; x.color = f.pair->color; }
+    x.qlv = f.ref_region;
+    if (f.ref_region && !(P && P->ref_masked())) x.refusal = "process: reference region levels asked for, but no reference mask is set (nct_pair_set_ref_region first)";
+    if (f.region) { q = ref_region_levels_of(*f.region); x.qlv = &q; }
+    if (f.region && !(P && P->mask)) x.refusal = "process: region levels asked for, but no region mask is set (nct_pair_set_region first)";
+    return process_resident(ctx, prm, timing, x);
+}
+
+// The working-size nct_process_* forms, `who` for the refusal text: `upload` (the caller's, which words the refusals of the images), the masks that are given (ref_masks and
+// each of its K entries nullable), `run` and the download. protect is read only where a mask is given, and refused before anything is uploaded
+template <typename Upload>
+static int process_form(nct_ctx* ctx, const char* who, Upload upload, const uint8_t* src_mask, int K, const uint8_t* const* ref_masks, const nct_region_params* region,
+                        int (*run)(nct_ctx*, const nct_params*, nct_pair_timing*), const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
+    if (!ctx) return NCT_ERR_INVALID;
+    bool any = src_mask != nullptr;
+    for (int k = 0; k < K && k < NCT_MAX_REFS && ref_masks; ++k) any = any || ref_masks[k];
+    NCT_REQUIRE(!any || !region || region->protect == 0 || region->protect == 1, "%s: region protect must be 0 or 1 (got %d)", who, region ? region->protect : 0);
+    NCT_TRY(upload());
+    if (src_mask) NCT_TRY(nct_pair_set_region(ctx, src_mask, region));
+    for (int k = 0; k < K && ref_masks; ++k) if (ref_masks[k]) NCT_TRY(nct_pair_set_ref_region(ctx, k, ref_masks[k], region));
+    NCT_TRY(run(ctx, prm, timing));
+    return nct_pair_download(ctx, out_bgr);
+}
+
 extern "C" {
 
 int nct_pair_upload(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw) {
@@ -614,37 +654,24 @@ int nct_multi_upload(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K
     return upload_images(ctx, src_bgr, sh, sw, K, refs_bgr, rh, rw);
 }
 
-int nct_multi_run(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing) {
-    NCT_CTX_ENTER();
-    NCT_REQUIRE(prm, "multi_run: null params");
-    return process_resident(ctx, prm, timing);
-}
-
+int nct_multi_run(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing) { return run_resident(ctx, "multi_run", prm, timing); }
 int nct_multi_run_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_multi_levels* levels) {
-    NCT_CTX_ENTER();
-    NCT_REQUIRE(prm, "multi_run_levels: null params");
-    return process_resident(ctx, prm, timing, {levels});
+    run_form f; f.multi = levels;
+    return run_resident(ctx, "multi_run_levels", prm, timing, f);
+}
+int nct_pair_run(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing) { return run_resident(ctx, "pair_run", prm, timing); }
+int nct_pair_run_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* levels) {
+    run_form f; f.pair = levels;
+    return run_resident(ctx, "pair_run_levels", prm, timing, f);
 }
 
+int nct_process_pair(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw, const nct_params* prm,
+                     uint8_t* out_bgr, nct_pair_timing* timing) {
+    return process_form(ctx, "process_pair", [&] { return nct_pair_upload(ctx, src_bgr, sh, sw, ref_bgr, rh, rw); }, nullptr, 1, nullptr, nullptr, nct_pair_run, prm, out_bgr, timing);
+}
 int nct_process_multi(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw, const nct_params* prm,
                       uint8_t* out_bgr, nct_pair_timing* timing) {
-    NCT_TRY(nct_multi_upload(ctx, src_bgr, sh, sw, K, refs_bgr, rh, rw));
-    NCT_TRY(nct_multi_run(ctx, prm, timing));
-    return nct_pair_download(ctx, out_bgr);
-}
-
-int nct_pair_run(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing) {
-    NCT_CTX_ENTER();
-    NCT_REQUIRE(prm, "pair_run: null params");
-    return process_resident(ctx, prm, timing);
-}
-
-int nct_pair_run_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* levels) {
-    NCT_CTX_ENTER();
-    NCT_REQUIRE(prm, "pair_run_levels: null params");
-    if (!levels) return process_resident(ctx, prm, timing);
-    const nct_multi_levels m = multi_levels_of(*levels);
-    return process_resident(ctx, prm, timing, {&m, levels->color});
+    return process_form(ctx, "process_multi", [&] { return nct_multi_upload(ctx, src_bgr, sh, sw, K, refs_bgr, rh, rw); }, nullptr, K, nullptr, nullptr, nct_multi_run, prm, out_bgr, timing);
 }
 
 // ---- source region masks (SPEC §6.11)
@@ -674,21 +701,13 @@ int nct_pair_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_para
 }
 
 int nct_pair_run_region_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_region_levels* region_levels) {
-    NCT_CTX_ENTER();
-    NCT_REQUIRE(prm, "pair_run_region_levels: null params");
-    if (!levels) return process_resident(ctx, prm, timing, {nullptr, nullptr, nullptr, nullptr, nullptr, region_levels});
-    const nct_multi_levels m = multi_levels_of(*levels);
-    return process_resident(ctx, prm, timing, {&m, levels->color, nullptr, nullptr, nullptr, region_levels});
+    run_form f; f.pair = levels; f.region = region_levels;
+    return run_resident(ctx, "pair_run_region_levels", prm, timing, f);
 }
 
 int nct_process_pair_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* mask, const uint8_t* ref_bgr, int rh, int rw, const nct_region_params* region,
                             const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_REQUIRE(!mask || !region || region->protect == 0 || region->protect == 1, "process_pair_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
-    NCT_TRY(nct_pair_upload(ctx, src_bgr, sh, sw, ref_bgr, rh, rw));
-    if (mask) NCT_TRY(nct_pair_set_region(ctx, mask, region));
-    NCT_TRY(nct_pair_run(ctx, prm, timing));
-    return nct_pair_download(ctx, out_bgr);
+    return process_form(ctx, "process_pair_region", [&] { return nct_pair_upload(ctx, src_bgr, sh, sw, ref_bgr, rh, rw); }, mask, 1, nullptr, region, nct_pair_run, prm, out_bgr, timing);
 }
 
 // ---- reference region masks (SPEC §6.12)
@@ -713,41 +732,23 @@ int nct_pair_set_ref_region(nct_ctx* ctx, int k, const uint8_t* mask, const nct_
 }
 
 int nct_multi_run_ref_region_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_multi_levels* levels, const nct_ref_region_levels* region_levels) {
-    NCT_CTX_ENTER();
-    NCT_REQUIRE(prm, "multi_run_ref_region_levels: null params");
-    return process_resident(ctx, prm, timing, {levels, nullptr, nullptr, nullptr, nullptr, nullptr, region_levels});
+    run_form f; f.multi = levels; f.ref_region = region_levels;
+    return run_resident(ctx, "multi_run_ref_region_levels", prm, timing, f);
 }
-
 int nct_pair_run_ref_region_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_ref_region_levels* region_levels) {
-    NCT_CTX_ENTER();
-    NCT_REQUIRE(prm, "pair_run_ref_region_levels: null params");
-    if (!levels) return process_resident(ctx, prm, timing, {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, region_levels});
-    const nct_multi_levels m = multi_levels_of(*levels);
-    return process_resident(ctx, prm, timing, {&m, levels->color, nullptr, nullptr, nullptr, nullptr, region_levels});
+    run_form f; f.pair = levels; f.ref_region = region_levels;
+    return run_resident(ctx, "pair_run_ref_region_levels", prm, timing, f);
 }
 
 int nct_process_multi_ref_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* src_mask, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw,
                                  const uint8_t* const* ref_masks, const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
-    if (!ctx) return NCT_ERR_INVALID;
-    bool any = src_mask != nullptr;                              // as in the pair form: protect is read only where a mask is given
-    for (int k = 0; k < K && k < NCT_MAX_REFS && ref_masks; ++k) any = any || ref_masks[k];
-    NCT_REQUIRE(!any || !region || region->protect == 0 || region->protect == 1, "process_multi_ref_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
-    NCT_TRY(nct_multi_upload(ctx, src_bgr, sh, sw, K, refs_bgr, rh, rw));
-    if (src_mask) NCT_TRY(nct_pair_set_region(ctx, src_mask, region));
-    for (int k = 0; k < K && ref_masks; ++k) if (ref_masks[k]) NCT_TRY(nct_pair_set_ref_region(ctx, k, ref_masks[k], region));
-    NCT_TRY(nct_multi_run(ctx, prm, timing));
-    return nct_pair_download(ctx, out_bgr);
+    return process_form(ctx, "process_multi_ref_region", [&] { return nct_multi_upload(ctx, src_bgr, sh, sw, K, refs_bgr, rh, rw); }, src_mask, K, ref_masks, region, nct_multi_run, prm,
+                        out_bgr, timing);
 }
-
 int nct_process_pair_ref_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* src_mask, const uint8_t* ref_bgr, int rh, int rw, const uint8_t* ref_mask,
                                 const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing) {
-    if (!ctx) return NCT_ERR_INVALID;
-    NCT_REQUIRE((!src_mask && !ref_mask) || !region || region->protect == 0 || region->protect == 1, "process_pair_ref_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
-    NCT_TRY(nct_pair_upload(ctx, src_bgr, sh, sw, ref_bgr, rh, rw));
-    if (src_mask) NCT_TRY(nct_pair_set_region(ctx, src_mask, region));
-    if (ref_mask) NCT_TRY(nct_pair_set_ref_region(ctx, 0, ref_mask, region));
-    NCT_TRY(nct_pair_run(ctx, prm, timing));
-    return nct_pair_download(ctx, out_bgr);
+    return process_form(ctx, "process_pair_ref_region", [&] { return nct_pair_upload(ctx, src_bgr, sh, sw, ref_bgr, rh, rw); }, src_mask, 1, &ref_mask, region, nct_pair_run, prm,
+                        out_bgr, timing);
 }
 
 int nct_pair_download(nct_ctx* ctx, uint8_t* out_bgr) {
@@ -758,13 +759,6 @@ int nct_pair_download(nct_ctx* ctx, uint8_t* out_bgr) {
     NCT_D2H(out_bgr, P->out, (size_t)P->sh * P->sw * 3);
     NCT_SYNC();
     return NCT_OK;
-}
-
-int nct_process_pair(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* ref_bgr, int rh, int rw, const nct_params* prm,
-                     uint8_t* out_bgr, nct_pair_timing* timing) {
-    NCT_TRY(nct_pair_upload(ctx, src_bgr, sh, sw, ref_bgr, rh, rw));
-    NCT_TRY(nct_pair_run(ctx, prm, timing));
-    return nct_pair_download(ctx, out_bgr);
 }
 
 int nct_working_size(int h, int w, int max_side, int* work_h, int* work_w) {
@@ -853,7 +847,8 @@ static int fullres_run(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, con
     DevBuf<uint8_t> o0(ctx, (size_t)sh * sw * 3);
     if (!o0.ok()) return NCT_ERR_HIP;
     const full_target fin{s0, sh, sw, o0, finish, m0};
-    const int rc = process_resident(ctx, prm, timing, {nullptr, nullptr, &fin});
+    run_extras x; x.fin = &fin;
+    const int rc = process_resident(ctx, prm, timing, x);
     // the working-size result buffer holds the second-to-last level's image (the upsampling finish: the working-size result, which nobody asked for): no nct_pair_download of it
     if (P->out) { ctx->release(P->out); P->out = nullptr; }
     if (rc) return rc;

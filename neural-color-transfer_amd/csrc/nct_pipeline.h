@@ -51,11 +51,12 @@ static const int kTapC[5] = {64, 128, 256, 512, 512};       // tap 1 (conv1_1) โ
 // ---- nct_pipeline.cpp
 NCT_LOCAL pair_state* pair_of(nct_ctx* ctx);
 NCT_LOCAL void drop_images(nct_ctx* ctx, pair_state* P);    // drop what the context holds of the last pair / reference list
-// what a run is asked for beside its result, every member nullable. lv: host copies of the level intermediates; color (a pair only): [5] the colour stage's coefficient
-// maps per level; fin (K = 1 only): the full-resolution finish; seq: the run is a frame of this open sequence, slv: where that frame's X'_t, tau_p and fields go
-// rlv: where a masked run's level masks and mixed coefficients go (SPEC ยง6.11)
-struct run_extras { const nct_multi_levels* lv; const nct_color_stages* const* color; const full_target* fin; seq_state* seq; const nct_seq_levels* slv; const nct_region_levels* rlv;
-                    const nct_ref_region_levels* qlv; };      // qlv: where a run with a reference mask reports Q_k,l, P_k,l, M_l, F_l and X' (SPEC ยง6.12)
+// what a run is asked for beside its result, every member nullable and filled by name (run_extras x; x.fin = โฆ;). lv: host copies of the level intermediates; color (a pair
+// only): [5] the colour stage's coefficient maps per level; fin (K = 1 only): the full-resolution finish; seq: the run is a frame of this open sequence, slv: where that
+// frame's X'_t, tau_p and fields go; qlv: where a masked run reports Q_k,l, P_k,l, M_l, F_l and X' (SPEC ยง6.11, ยง6.12: the one report target of both kinds of mask);
+// refusal: the entry point asked for the report of a mask that is not set โ the run is refused with NCT_ERR_STATE and this text, behind the checks of state and parameters
+struct run_extras { const nct_multi_levels* lv = nullptr; const nct_color_stages* const* color = nullptr; const full_target* fin = nullptr; seq_state* seq = nullptr;
+                    const nct_seq_levels* slv = nullptr; const nct_ref_region_levels* qlv = nullptr; const char* refusal = nullptr; };
 // run the whole L=5->1 loop on the uploaded source and its K references
 NCT_LOCAL int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const run_extras& x = {});
 // a pair is the list of one reference (SPEC ยง6.2): its maps are reference 0's NNFs and the merged guide / err; it has no label map and no G_k / E_k of their own
@@ -96,10 +97,9 @@ struct NCT_LOCAL full_lab {
 // The finish of a level: U1 / S2 / A1 of x ([2][h*w][3], the level grid) and the result in BGR. full == null (every level but a full-resolution run's last): onto the
 // working grid H x W, s_lab_full -> out_lab -> out_bgr. The exact finish: onto the original source through fl's images into full->out; out_lab and out_bgr stay as they
 // are. The upsampling finish (SPEC ยง6.8): the working-size finish, and behind it S2's output upsampled onto the original source into full->out
-// region (nullable; SPEC ยง6.11 rule 3): the run is masked โ the compose with the source takes the place of Lab -> BGR, at the working size with region's mask and source, in
-// the exact finish with full's
-// mask0 (null: full's own): with a reference mask (SPEC ยง6.12 rule 5) the target mask F at full's size
-struct region_fin { const uint8_t* mask; const uint8_t* s_bgr; int protect; const uint8_t* mask0 = nullptr; };
+// region (nullable; SPEC ยง6.11 rule 3, ยง6.12 rule 5): the run is masked โ the compose with the source takes the place of Lab -> BGR. mask: the compose mask at the size this
+// finish targets (the exact finish: full's size, and the source is full's; else H x W and s_bgr)
+struct region_fin { const uint8_t* mask; const uint8_t* s_bgr; int protect; };
 NCT_LOCAL int finish_level(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int H, int W, const uint8_t* s_lab_full, uint8_t* out_lab, uint8_t* out_bgr,
                            const full_target* full, const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube, const region_fin* region = nullptr);
 // ---- nct_seq.cpp

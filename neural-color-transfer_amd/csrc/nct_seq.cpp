@@ -214,7 +214,9 @@ int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr,
     if (seq_levels) for (int l = 0; l < q->prm.levels; ++l) if (seq_levels->motion[l]) memset(seq_levels->motion[l], 0, sizeof(int16_t) * 2 * (size_t)q->ah[l] * q->aw[l]);
     int rc = seq_upload_frame(ctx, P, q, src_bgr);
     const nct_multi_levels m = levels ? multi_levels_of(*levels) : nct_multi_levels{};
-    if (rc == NCT_OK) rc = process_resident(ctx, &q->prm, timing, {levels ? &m : nullptr, levels ? levels->color : nullptr, q->target(), q, seq_levels});
+    run_extras x; x.fin = q->target(); x.seq = q; x.slv = seq_levels;
+    if (levels) { x.lv = &m; x.color = levels->color; }
+    if (rc == NCT_OK) rc = process_resident(ctx, &q->prm, timing, x);
     // a frame that failed may have replaced the state of some levels only: the next frame starts over
     q->gap = 0; q->acc = 0;                                      // a full frame (and a failed one: the next is a first frame) starts the count over
     if (rc) { q->frames = 0; return rc; }

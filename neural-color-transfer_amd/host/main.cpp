@@ -605,16 +605,9 @@ void run_pair(nct_ctx* ctx, const Config& cfg, Job& j) {
         ok = K > 1 ? run_multi_with_vis(ctx, j.cnt, K, px.data(), rh.data(), rw.data(), prm, pre, j.out.data(), &tm, err, mask, &region, refmasks)
                    : run_with_vis(ctx, j.cnt, j.refs[0], prm, pre, j.out.data(), &tm, err, mask, &region, qs[0]);
     } else {
-        if (refmasks)
-            ok = (K > 1 ? nct_process_multi_ref_region(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, mask, K, px.data(), rh.data(), rw.data(), refmasks, &region, &prm, j.out.data(), &tm)
-                        : nct_process_pair_ref_region(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, mask, px[0], rh[0], rw[0], qs[0], &region, &prm, j.out.data(), &tm)) == NCT_OK;
-        else if (mask && K > 1)
-            ok = nct_multi_upload(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, K, px.data(), rh.data(), rw.data()) == NCT_OK && nct_pair_set_region(ctx, mask, &region) == NCT_OK &&
-                 nct_multi_run(ctx, &prm, &tm) == NCT_OK && nct_pair_download(ctx, j.out.data()) == NCT_OK;
-        else if (mask) ok = nct_process_pair_region(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, mask, px[0], rh[0], rw[0], &region, &prm, j.out.data(), &tm) == NCT_OK;
-        else
-        ok = (K > 1 ? nct_process_multi(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, K, px.data(), rh.data(), rw.data(), &prm, j.out.data(), &tm)
-                    : nct_process_pair(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, px[0], rh[0], rw[0], &prm, j.out.data(), &tm)) == NCT_OK;
+        // NULL masks are the plain forms (nct.h): one call per kind of upload, whatever -mask and -refmask gave
+        ok = (K > 1 ? nct_process_multi_ref_region(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, mask, K, px.data(), rh.data(), rw.data(), refmasks, &region, &prm, j.out.data(), &tm)
+                    : nct_process_pair_ref_region(ctx, j.cnt.px.data(), j.cnt.h, j.cnt.w, mask, px[0], rh[0], rw[0], qs[0], &region, &prm, j.out.data(), &tm)) == NCT_OK;
         if (!ok) err = nct_last_error(ctx);
     }
     if (!ok) { j.say("Error: %s\n", err.c_str()); j.err = err; j.state = Job::FAILED; return; }

@@ -5,6 +5,7 @@ fallback anywhere in this package: if the library is missing or no HIP device is
 Function names and argument meaning mirror include/nct.h, which cites the reference seam each one replaces
 (code/windows/neural_color_transfer/source/main.cu).
 """
+import contextlib
 import ctypes as C
 import os
 import numpy as np
@@ -574,6 +575,16 @@ class Context:
     def dev_free(self, p):
         self._chk(self._l.nct_dev_free(self._h, p))
 
+    @contextlib.contextmanager
+    def _blocks(self, ptrs):
+        """around the calls of a *_dev wrapper on the arena blocks it took (dev_upload, dev_alloc): on every way out the stream is synchronised, then they go back"""
+        try:
+            yield
+        finally:
+            self.synchronize()
+            for p in ptrs:
+                self.dev_free(p)
+
     def dev_upload(self, arr):
         a = np.ascontiguousarray(arr)
         p = self.dev_alloc(a.nbytes)
@@ -709,31 +720,33 @@ class Context:
         return (out, keep) if want_stages else out
 
     # ---- per-pair hot loop
-    def process_pair(self, src_bgr, ref_bgr, params=None, want_timing=False):
+    def _process(self, name, src_bgr, args, params, want_timing):
+        """what every process_* method does around its own C entry point `name`(ctx, source, h, w, *args, params, result, timing): the source and the result, the
+        defaults, the timing. An array among args is an image or a mask (None: none) and goes over as the declared argument type takes it"""
         s = np.ascontiguousarray(src_bgr, np.uint8)
-        r = np.ascontiguousarray(ref_bgr, np.uint8)
         prm = params or Params.default()
         out = np.empty_like(s)
         tm = PairTiming() if want_timing else None
-        self._chk(self._l.nct_process_pair(self._h, s.reshape(-1, 3), s.shape[0], s.shape[1], r.reshape(-1, 3), r.shape[0], r.shape[1],
-                                           C.addressof(prm), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
+        fn = getattr(self._l, name)
+        call = [self._h, s, s.shape[0], s.shape[1], *args, C.addressof(prm), out, C.addressof(tm) if tm is not None else None]
+        self._chk(fn(*[(a if t is _u8p else a.ctypes.data) if isinstance(a, np.ndarray) else a for a, t in zip(call, fn.argtypes)]))
         return (out, tm.as_dict()) if want_timing else out
+
+    @staticmethod
+    def _image(bgr):
+        """-> the image as contiguous bytes, its height, its width: the three arguments an image takes"""
+        a = np.ascontiguousarray(bgr, np.uint8)
+        return a, a.shape[0], a.shape[1]
+
+    def process_pair(self, src_bgr, ref_bgr, params=None, want_timing=False):
+        return self._process("nct_process_pair", src_bgr, self._image(ref_bgr), params, want_timing)
 
     def process_pair_fullres(self, src_bgr, ref_bgr, max_side=1000, params=None, want_timing=False, finish=0):
         """nct_process_pair_fullres: the pair runs at working_size(..., max_side), the last level finishes on the original source (result: src's size).
         finish: FINISH_EXACT (0) that entry point; anything else goes through nct_process_pair_fullres_finish (FINISH_UPSAMPLE: SPEC §6.8)"""
-        s = np.ascontiguousarray(src_bgr, np.uint8)
-        r = np.ascontiguousarray(ref_bgr, np.uint8)
-        prm = params or Params.default()
-        out = np.empty_like(s)
-        tm = PairTiming() if want_timing else None
         if finish == FINISH_EXACT:
-            self._chk(self._l.nct_process_pair_fullres(self._h, s.reshape(-1, 3), s.shape[0], s.shape[1], r.reshape(-1, 3), r.shape[0], r.shape[1], max_side,
-                                                       C.addressof(prm), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
-        else:
-            self._chk(self._l.nct_process_pair_fullres_finish(self._h, s.reshape(-1, 3), s.shape[0], s.shape[1], r.reshape(-1, 3), r.shape[0], r.shape[1], max_side,
-                                                              int(finish), C.addressof(prm), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
-        return (out, tm.as_dict()) if want_timing else out
+            return self._process("nct_process_pair_fullres", src_bgr, [*self._image(ref_bgr), max_side], params, want_timing)
+        return self._process("nct_process_pair_fullres_finish", src_bgr, [*self._image(ref_bgr), max_side, int(finish)], params, want_timing)
 
     def color_finish_upsample(self, ab_wls, h, w, s_full, params=None):
         """nct_color_finish_upsample (SPEC §6.8): ab_wls ([2][h*w][3], the working-size finish's S2 output) upsampled and applied to s_full (H x W x 3 BGR)"""
@@ -754,13 +767,9 @@ class Context:
         H, W = s_full.shape[:2]
         prm = params or Params.default()
         blocks = [self.dev_upload(a), self.dev_upload(s_full), self.dev_alloc(s_full.size)]
-        try:
+        with self._blocks(blocks):
             self._chk(self._l.nct_color_finish_upsample_dev(self._h, blocks[0], h, w, blocks[1], H, W, C.addressof(prm), blocks[2]))
             return self.dev_download(blocks[2], (H, W, 3), np.uint8)
-        finally:
-            self.synchronize()
-            for p in blocks:
-                self.dev_free(p)
 
     def color_finish_guided(self, ab_wls, lab_work, h, w, s_full, sigma=None, params=None):
         """nct_color_finish_guided (SPEC §6.10): the upsampling finish with joint-bilateral weights; lab_work (h x w x 3): the 8-bit Lab image of the working-size source;
@@ -784,13 +793,9 @@ class Context:
         H, W = s_full.shape[:2]
         prm, gp = params or Params.default(), _guided_params(sigma)
         blocks = [self.dev_upload(a), self.dev_upload(lw), self.dev_upload(s_full), self.dev_alloc(s_full.size)]
-        try:
+        with self._blocks(blocks):
             self._chk(self._l.nct_color_finish_guided_dev(self._h, blocks[0], blocks[1], h, w, blocks[2], H, W, C.addressof(gp), C.addressof(prm), blocks[3]))
             return self.dev_download(blocks[3], (H, W, 3), np.uint8)
-        finally:
-            self.synchronize()
-            for p in blocks:
-                self.dev_free(p)
 
     def set_finish_guided(self, sigma):
         """nct_set_finish_guided: a sigma turns the guided modifier of the upsampling finish on for this context, None turns it off (the default)"""
@@ -850,24 +855,14 @@ class Context:
         de = [self.dev_upload(e) for e in es]
         dg = [self.dev_upload(g) for g in gs]
         dl, dgo, deo = self.dev_alloc(h * w), self.dev_alloc(h * w * 3), self.dev_alloc(h * w * 4)
-        try:
+        with self._blocks(de + dg + [dl, dgo, deo]):
             self._chk(self._l.nct_select_reference_dev(self._h, (C.c_void_p * K)(*de), (C.c_void_p * K)(*dg), K, h, w, dl, dgo, deo))
             return self.dev_download(dl, (h, w), np.uint8), self.dev_download(dgo, (h, w, 3), np.uint8), self.dev_download(deo, (h, w), np.float32)
-        finally:
-            self.synchronize()
-            for p in de + dg + [dl, dgo, deo]:
-                self.dev_free(p)
 
     def process_multi(self, src_bgr, refs_bgr, params=None, want_timing=False):
         """nct_process_multi: one source, a list of references -> the result at the source's size"""
-        s = np.ascontiguousarray(src_bgr, np.uint8)
         K, keep, ptrs, hs, ws = self._ref_list(refs_bgr)
-        prm = params or Params.default()
-        out = np.empty_like(s)
-        tm = PairTiming() if want_timing else None
-        self._chk(self._l.nct_process_multi(self._h, s.reshape(-1, 3), s.shape[0], s.shape[1], K, ptrs, hs, ws, C.addressof(prm), out.reshape(-1, 3),
-                                            C.addressof(tm) if tm is not None else None))
-        return (out, tm.as_dict()) if want_timing else out
+        return self._process("nct_process_multi", src_bgr, [K, ptrs, hs, ws], params, want_timing)
 
     def multi_upload(self, src_bgr, refs_bgr):
         s = np.ascontiguousarray(src_bgr, np.uint8)
@@ -944,13 +939,9 @@ class Context:
         if q.shape != b.shape:
             raise NctError(-2, f"region_pull_dev: mask is {q.shape}, bnn {b.shape}")
         blocks = [self.dev_upload(q), self.dev_upload(a), self.dev_upload(b), self.dev_alloc(a.size)]
-        try:
+        with self._blocks(blocks):
             self._chk(self._l.nct_region_pull_dev(self._h, blocks[0], q.shape[0], q.shape[1], blocks[1], blocks[2], a.shape[0], a.shape[1], w_coh, w_comp, blocks[3]))
             return self.dev_download(blocks[3], a.shape, np.uint8)
-        finally:
-            self.synchronize()
-            for p in blocks:
-                self.dev_free(p)
 
     def pair_set_ref_region(self, k, mask, protect=None):
         """nct_pair_set_ref_region on the uploaded references: reference k's mask [rh, rw] bytes, or None to remove it; protect None leaves the run's protect as it is"""
@@ -987,49 +978,34 @@ class Context:
 
     def process_pair_ref_region(self, src_bgr, src_mask, ref_bgr, ref_mask, protect=None, params=None, want_timing=False):
         """nct_process_pair_ref_region: process_pair with a mask on the source ([h, w] of the source) and / or on the reference ([rh, rw]); both None: process_pair"""
-        s = np.ascontiguousarray(src_bgr, np.uint8)
-        r = np.ascontiguousarray(ref_bgr, np.uint8)
-        m = None if src_mask is None else _mask_arg(src_mask, s.shape, "process_pair_ref_region")
+        r, rh, rw = self._image(ref_bgr)
+        m = None if src_mask is None else _mask_arg(src_mask, np.shape(src_bgr), "process_pair_ref_region")
         q = None if ref_mask is None else _mask_arg(ref_mask, r.shape, "process_pair_ref_region (reference)")
-        prm, rg = params or Params.default(), _region_params(protect)
-        out = np.empty_like(s)
-        tm = PairTiming() if want_timing else None
-        self._pair_shape = s.shape; self._multi_shapes = [r.shape]
-        self._chk(self._l.nct_process_pair_ref_region(self._h, s.ctypes.data, s.shape[0], s.shape[1], _ptr(m), r.ctypes.data, r.shape[0], r.shape[1], _ptr(q), C.addressof(rg),
-                                                      C.addressof(prm), out.ctypes.data, C.addressof(tm) if tm is not None else None))
-        return (out, tm.as_dict()) if want_timing else out
+        rg = _region_params(protect)
+        self._pair_shape = np.shape(src_bgr); self._multi_shapes = [r.shape]
+        return self._process("nct_process_pair_ref_region", src_bgr, [m, r, rh, rw, q, C.addressof(rg)], params, want_timing)
 
     def process_multi_ref_region(self, src_bgr, src_mask, refs_bgr, ref_masks, protect=None, params=None, want_timing=False):
         """nct_process_multi_ref_region: process_multi with a mask on the source and / or on some references (ref_masks: None, or a list with None entries)"""
-        s = np.ascontiguousarray(src_bgr, np.uint8)
         K, keep, ptrs, hs, ws = self._ref_list(refs_bgr)
-        m = None if src_mask is None else _mask_arg(src_mask, s.shape, "process_multi_ref_region")
+        m = None if src_mask is None else _mask_arg(src_mask, np.shape(src_bgr), "process_multi_ref_region")
         qs, qp = None, None
         if ref_masks is not None:
             if len(ref_masks) != K:
                 raise NctError(-2, f"process_multi_ref_region: {len(ref_masks)} masks for {K} references")
             qs = [None if q is None else _mask_arg(q, keep[k].shape, "process_multi_ref_region (reference %d)" % k) for k, q in enumerate(ref_masks)]
             qp = (C.c_void_p * max(K, 1))(*[None if q is None else q.ctypes.data for q in qs])
-        prm, rg = params or Params.default(), _region_params(protect)
-        out = np.empty_like(s)
-        tm = PairTiming() if want_timing else None
-        self._pair_shape = s.shape; self._multi_shapes = [a.shape for a in keep]
-        self._chk(self._l.nct_process_multi_ref_region(self._h, s.ctypes.data, s.shape[0], s.shape[1], _ptr(m), K, ptrs, hs, ws, qp, C.addressof(rg), C.addressof(prm), out.ctypes.data,
-                                                       C.addressof(tm) if tm is not None else None))
-        return (out, tm.as_dict()) if want_timing else out
+        rg = _region_params(protect)
+        self._pair_shape = np.shape(src_bgr); self._multi_shapes = [a.shape for a in keep]
+        return self._process("nct_process_multi_ref_region", src_bgr, [m, K, ptrs, hs, ws, qp, C.addressof(rg)], params, want_timing)
 
     def process_pair_fullres_ref_region(self, src_bgr, mask0, ref_bgr, ref_mask0, max_side=1000, protect=None, params=None, want_timing=False):
         """nct_process_pair_fullres_ref_region (SPEC §6.12 rule 5): both masks at their images' original sizes; the exact finish"""
-        s = np.ascontiguousarray(src_bgr, np.uint8)
-        r = np.ascontiguousarray(ref_bgr, np.uint8)
-        m = None if mask0 is None else _mask_arg(mask0, s.shape, "process_pair_fullres_ref_region")
+        r, rh, rw = self._image(ref_bgr)
+        m = None if mask0 is None else _mask_arg(mask0, np.shape(src_bgr), "process_pair_fullres_ref_region")
         q = None if ref_mask0 is None else _mask_arg(ref_mask0, r.shape, "process_pair_fullres_ref_region (reference)")
-        prm, rg = params or Params.default(), _region_params(protect)
-        out = np.empty_like(s)
-        tm = PairTiming() if want_timing else None
-        self._chk(self._l.nct_process_pair_fullres_ref_region(self._h, s.ctypes.data, s.shape[0], s.shape[1], _ptr(m), r.ctypes.data, r.shape[0], r.shape[1], _ptr(q), max_side,
-                                                              C.addressof(rg), C.addressof(prm), out.ctypes.data, C.addressof(tm) if tm is not None else None))
-        return (out, tm.as_dict()) if want_timing else out
+        rg = _region_params(protect)
+        return self._process("nct_process_pair_fullres_ref_region", src_bgr, [m, r, rh, rw, q, max_side, C.addressof(rg)], params, want_timing)
 
     # ---- frame sequences (SPEC §6.3)
     def seq_begin(self, ref_bgr, src_shape, params=None, tau=None, sigma=None):
@@ -1185,13 +1161,9 @@ class Context:
         n = h * w
         ins = [self.dev_upload(np.ascontiguousarray(x_prev, np.float64).reshape(-1)), self.dev_upload(f)]
         do = self.dev_alloc(48 * n)
-        try:
+        with self._blocks(ins + [do]):
             self._chk(self._l.nct_seq_warp_dev(self._h, ins[0], h, w, ins[1], ins[0] if alias else do))
             return self.dev_download(do, (2, n, 3), np.float64)
-        finally:
-            self.synchronize()
-            for p in ins + [do]:
-                self.dev_free(p)
 
     # ---- adaptive key frames (SPEC §6.7)
     def seq_change(self, lab, lab_prev, field=None, threshold=24):
@@ -1211,14 +1183,10 @@ class Context:
         h, w = a.shape[:2]
         ins = [self.dev_upload(a), self.dev_upload(np.ascontiguousarray(lab_prev, np.uint8))] + ([] if field is None else [self.dev_upload(np.ascontiguousarray(field, np.int16))])
         do = self.dev_upload(np.full(16, 0xff, np.uint8))
-        try:
+        with self._blocks(ins + [do]):
             self._chk(self._l.nct_seq_change_dev(self._h, ins[0], ins[1], h, w, None if field is None else ins[2], int(threshold), do))
             raw = self.dev_download(do, (16,), np.uint8)
             return SeqChange.from_buffer_copy(raw.tobytes()).as_dict()
-        finally:
-            self.synchronize()
-            for p in ins + [do]:
-                self.dev_free(p)
 
     def seq_probe(self, src_bgr, auto=None):
         """nct_seq_probe (SPEC §6.7 rule 2): the decision the frame would get on the open sequence, nothing changed -> dict (SeqDecision.as_dict); auto: a SeqAuto or
@@ -1258,7 +1226,7 @@ class Context:
         prm = _lut_params(size, lam)
         n3 = prm.size ** 3
         blocks = [self.dev_upload(s), self.dev_upload(r), self.dev_alloc(12 * n3), self.dev_alloc(8 * n3), self.dev_alloc(24 * n3), self.dev_alloc(24 * n3)]
-        try:
+        with self._blocks(blocks):
             cs = LutStages(blocks[3], blocks[4], blocks[5])
             self._chk(self._l.nct_lut_fit_dev(self._h, blocks[0], blocks[1], len(s), C.addressof(prm), blocks[2], C.addressof(cs) if want_stages else None))
             lut = self.dev_download(blocks[2], (prm.size,) * 3 + (3,), np.float32)
@@ -1266,10 +1234,6 @@ class Context:
                 return lut
             return lut, {"weight": self.dev_download(blocks[3], (n3,), np.uint64), "resid": self.dev_download(blocks[4], (n3, 3), np.int64),
                          "disp": self.dev_download(blocks[5], (n3, 3), np.float64)}
-        finally:
-            self.synchronize()
-            for p in blocks:
-                self.dev_free(p)
 
     def lut_apply(self, lut, img):
         """nct_lut_apply: table [N, N, N, 3] float32 on an image [..., 3] uint8 BGR -> the image of the same shape"""
@@ -1284,14 +1248,10 @@ class Context:
         t = np.ascontiguousarray(lut, np.float32)
         a = np.ascontiguousarray(img, np.uint8)
         blocks = [self.dev_upload(t), self.dev_upload(a), self.dev_alloc(a.size)]
-        try:
+        with self._blocks(blocks):
             dst = blocks[1] if in_place else blocks[2]
             self._chk(self._l.nct_lut_apply_dev(self._h, blocks[0], t.shape[0], blocks[1], a.size // 3, dst))
             return self.dev_download(dst, a.shape, np.uint8)
-        finally:
-            self.synchronize()
-            for p in blocks:
-                self.dev_free(p)
 
     def pair_fit_lut(self, size=None, lam=None):
         """nct_pair_fit_lut: the table of the context's last finished run, from the images it holds on the device"""
@@ -1339,13 +1299,9 @@ class Context:
         ph, pw = (0, 0) if par is None else par.shape[:2]
         ins = [self.dev_upload(lab), self.dev_upload(np.ascontiguousarray(lab_prev, np.uint8))] + ([] if par is None else [self.dev_upload(par)])
         do = self.dev_alloc(4 * h * w)
-        try:
+        with self._blocks(ins + [do]):
             self._chk(self._l.nct_seq_motion_field_dev(self._h, ins[0], ins[1], h, w, None if par is None else ins[2], ph, pw, int(R), int(penalty), do))
             return self.dev_download(do, (h, w, 2), np.int16)
-        finally:
-            self.synchronize()
-            for p in ins + [do]:
-                self.dev_free(p)
 
     def seq_blend_mc(self, x, x_prev, lab, lab_prev, tau, sigma, field, want_tau_map=True):
         """nct_seq_blend_mc (SPEC §6.4 rule 4): seq_blend with L_(t-1) and x_prev read through field (int16 [h, w, 2], or None: seq_blend)"""
@@ -1371,13 +1327,9 @@ class Context:
         if field is not None:
             ins.append(self.dev_upload(np.ascontiguousarray(field, np.int16)))
         do, dt = self.dev_alloc(48 * n), self.dev_alloc(8 * n)
-        try:
+        with self._blocks(ins + [do, dt]):
             self._chk(self._l.nct_seq_blend_mc_dev(self._h, ins[0], ins[1], ins[2], ins[3], h, w, tau, sigma, ins[1] if alias_prev else do, dt, ins[4] if field is not None else None))
             return self.dev_download(ins[1] if alias_prev else do, (2, n, 3), np.float64), self.dev_download(dt, (h, w), np.float64)
-        finally:
-            self.synchronize()
-            for p in ins + [do, dt]:
-                self.dev_free(p)
 
     def seq_blend(self, x, x_prev, lab, lab_prev, tau, sigma, want_tau_map=True):
         """nct_seq_blend (SPEC §6.3 rule 3): x, x_prev [2, h*w, 3] doubles, lab / lab_prev h x w x 3 8-bit Lab -> (X', tau_p map [h, w] or None)"""
@@ -1399,13 +1351,9 @@ class Context:
         ins = [self.dev_upload(np.ascontiguousarray(x, np.float64).reshape(-1)), self.dev_upload(np.ascontiguousarray(x_prev, np.float64).reshape(-1)),
                self.dev_upload(lab), self.dev_upload(np.ascontiguousarray(lab_prev, np.uint8))]
         do, dt = self.dev_alloc(48 * n), self.dev_alloc(8 * n)
-        try:
+        with self._blocks(ins + [do, dt]):
             self._chk(self._l.nct_seq_blend_dev(self._h, ins[0], ins[1], ins[2], ins[3], h, w, tau, sigma, do, dt))
             return self.dev_download(do, (2, n, 3), np.float64), self.dev_download(dt, (h, w), np.float64)
-        finally:
-            self.synchronize()
-            for p in ins + [do, dt]:
-                self.dev_free(p)
 
     def pair_upload(self, src_bgr, ref_bgr):
         s = np.ascontiguousarray(src_bgr, np.uint8)
@@ -1474,13 +1422,9 @@ class Context:
         """the same through nct_resize_u8c1_dev on arena blocks"""
         a = np.ascontiguousarray(img, np.uint8)
         blocks = [self.dev_upload(a), self.dev_alloc(dh * dw)]
-        try:
+        with self._blocks(blocks):
             self._chk(self._l.nct_resize_u8c1_dev(self._h, blocks[0], a.shape[0], a.shape[1], blocks[1], dh, dw))
             return self.dev_download(blocks[1], (dh, dw), np.uint8)
-        finally:
-            self.synchronize()
-            for p in blocks:
-                self.dev_free(p)
 
     def region_mix(self, x, mask):
         """nct_region_mix (SPEC §6.11 rule 2): x [2, h*w, 3] doubles, mask [h, w] bytes -> X'"""
@@ -1499,14 +1443,10 @@ class Context:
         a = np.ascontiguousarray(x, np.float64).reshape(-1)
         assert a.size == 6 * h * w
         blocks = [self.dev_upload(a), self.dev_upload(m), self.dev_alloc(48 * h * w)]
-        try:
+        with self._blocks(blocks):
             dst = blocks[0] if in_place else blocks[2]
             self._chk(self._l.nct_region_mix_dev(self._h, blocks[0], blocks[1], h, w, dst))
             return self.dev_download(dst, (2, h * w, 3), np.float64)
-        finally:
-            self.synchronize()
-            for p in blocks:
-                self.dev_free(p)
 
     def region_compose(self, s_bgr, lab_out, mask, protect=None, params=None):
         """nct_region_compose (SPEC §6.11 rule 3): the source, a finish's 8-bit Lab result and the mask at that size -> the composed BGR image"""
@@ -1525,13 +1465,9 @@ class Context:
         assert lo.size == s.size and m.size * 3 == s.size
         prm, rg = params or Params.default(), _region_params(protect)
         blocks = [self.dev_upload(s), self.dev_upload(lo), self.dev_upload(m), self.dev_alloc(s.size)]
-        try:
+        with self._blocks(blocks):
             self._chk(self._l.nct_region_compose_dev(self._h, blocks[0], blocks[1], blocks[2], m.size, C.addressof(rg), C.addressof(prm), blocks[3]))
             return self.dev_download(blocks[3], s.shape, np.uint8)
-        finally:
-            self.synchronize()
-            for p in blocks:
-                self.dev_free(p)
 
     def pair_set_region(self, mask, protect=None):
         """nct_pair_set_region on the uploaded source: mask [h, w] bytes, or None to remove it"""
@@ -1558,32 +1494,18 @@ class Context:
 
     def process_pair_region(self, src_bgr, mask, ref_bgr, protect=None, params=None, want_timing=False):
         """nct_process_pair_region: process_pair recolouring only where mask ([h, w] bytes of the source; None: process_pair) says so"""
-        s = np.ascontiguousarray(src_bgr, np.uint8)
-        r = np.ascontiguousarray(ref_bgr, np.uint8)
-        m = None if mask is None else _mask_arg(mask, s.shape, "process_pair_region")
-        prm, rg = params or Params.default(), _region_params(protect)
-        out = np.empty_like(s)
-        tm = PairTiming() if want_timing else None
-        self._chk(self._l.nct_process_pair_region(self._h, s.ctypes.data if s.size else None, s.shape[0], s.shape[1], _ptr(m), r.ctypes.data, r.shape[0], r.shape[1], C.addressof(rg),
-                                                  C.addressof(prm), out.ctypes.data, C.addressof(tm) if tm is not None else None))
-        return (out, tm.as_dict()) if want_timing else out
+        m = None if mask is None else _mask_arg(mask, np.shape(src_bgr), "process_pair_region")
+        rg = _region_params(protect)
+        return self._process("nct_process_pair_region", src_bgr, [m, *self._image(ref_bgr), C.addressof(rg)], params, want_timing)
 
     def process_pair_fullres_region(self, src_bgr, mask0, ref_bgr, max_side=1000, protect=None, params=None, want_timing=False, finish=0):
         """nct_process_pair_fullres_region (SPEC §6.11 rule 5): mask0 at the source's original size; finish other than FINISH_EXACT goes through
         nct_process_pair_fullres_finish_region (which refuses FINISH_UPSAMPLE with a mask)"""
-        s = np.ascontiguousarray(src_bgr, np.uint8)
-        r = np.ascontiguousarray(ref_bgr, np.uint8)
-        m = None if mask0 is None else _mask_arg(mask0, s.shape, "process_pair_fullres_region")
-        prm, rg = params or Params.default(), _region_params(protect)
-        out = np.empty_like(s)
-        tm = PairTiming() if want_timing else None
+        m = None if mask0 is None else _mask_arg(mask0, np.shape(src_bgr), "process_pair_fullres_region")
+        rg = _region_params(protect)
         if finish == FINISH_EXACT:
-            self._chk(self._l.nct_process_pair_fullres_region(self._h, s.ctypes.data, s.shape[0], s.shape[1], _ptr(m), r.ctypes.data, r.shape[0], r.shape[1], max_side, C.addressof(rg),
-                                                              C.addressof(prm), out.ctypes.data, C.addressof(tm) if tm is not None else None))
-        else:
-            self._chk(self._l.nct_process_pair_fullres_finish_region(self._h, s.ctypes.data, s.shape[0], s.shape[1], _ptr(m), r.ctypes.data, r.shape[0], r.shape[1], max_side, int(finish),
-                                                                     C.addressof(rg), C.addressof(prm), out.ctypes.data, C.addressof(tm) if tm is not None else None))
-        return (out, tm.as_dict()) if want_timing else out
+            return self._process("nct_process_pair_fullres_region", src_bgr, [m, *self._image(ref_bgr), max_side, C.addressof(rg)], params, want_timing)
+        return self._process("nct_process_pair_fullres_finish_region", src_bgr, [m, *self._image(ref_bgr), max_side, int(finish), C.addressof(rg)], params, want_timing)
 
     def lut_fit_masked(self, src, res, mask, size=None, lam=None, want_stages=False):
         """nct_lut_fit_masked (SPEC §6.11 rule 7): lut_fit over the pixels with mask >= 128 (mask None: lut_fit)"""
@@ -1605,7 +1527,7 @@ class Context:
         prm = _lut_params(size, lam)
         n3 = prm.size ** 3
         blocks = [self.dev_upload(s), self.dev_upload(r), self.dev_alloc(12 * n3), self.dev_alloc(8 * n3), self.dev_alloc(24 * n3), self.dev_alloc(24 * n3), self.dev_upload(m)]
-        try:
+        with self._blocks(blocks):
             cs = LutStages(blocks[3], blocks[4], blocks[5])
             self._chk(self._l.nct_lut_fit_masked_dev(self._h, blocks[0], blocks[1], blocks[6], len(s), C.addressof(prm), blocks[2], C.addressof(cs) if want_stages else None))
             lut = self.dev_download(blocks[2], (prm.size,) * 3 + (3,), np.float32)
@@ -1613,10 +1535,6 @@ class Context:
                 return lut
             return lut, {"weight": self.dev_download(blocks[3], (n3,), np.uint64), "resid": self.dev_download(blocks[4], (n3, 3), np.int64),
                          "disp": self.dev_download(blocks[5], (n3, 3), np.float64)}
-        finally:
-            self.synchronize()
-            for p in blocks:
-                self.dev_free(p)
 
     def pair_download(self):
         out = np.empty(self._pair_shape, np.uint8)

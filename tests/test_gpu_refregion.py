@@ -1,5 +1,5 @@
 """Reference region masks (SPEC §6.12) on the GPU: the pull alone (host and device-pointer forms) against the numpy pull, the masked pair level by level against
-tests/refregion_ref.py, the identities of rule 6, both masks together, two references, full resolution, the table, refusals and the CLI's -refmask. Every comparison is
+tests/refregion_ref.py, the identities of rule 6, both masks together, two references, full resolution, the table, refusals, the CLI's -refmask and its -mask on a line of two references. Every comparison is
 equality of bytes or bit patterns."""
 import os
 import subprocess
@@ -163,6 +163,39 @@ def test_source_and_reference_mask(gpu, oracle, weights, images):
             F = got["mask_full"][4]
             out = gpu.pair_download()
             assert (F == 0).any() and np.array_equal(out[F == 0], src[F == 0])
+
+
+def test_both_report_forms_describe_one_masked_run(gpu, images):
+    """with both masks set, nct_pair_run_region_levels reports the M_l and X' that nct_multi_run_ref_region_levels reports (whose values the test above pins to the oracle)"""
+    src, ref = images
+    gpu.pair_upload(src, ref)
+    gpu.pair_set_region(region_ref.mask("ramp", SH, SW))
+    gpu.pair_set_ref_region(0, region_ref.mask("half", RH, RW))
+    a = gpu.pair_run_region_levels(src.shape, ref.shape, _params(5))
+    out_a = gpu.pair_download()
+    b = gpu.multi_run_ref_region_levels(_params(5))
+    for l in range(5):
+        assert np.array_equal(a["mask"][l], b["mask"][l]), l
+        assert np.array_equal(_bits(a["ab_mix"][l]), _bits(b["ab_mix"][l])), l
+    assert np.array_equal(out_a, gpu.pair_download())
+
+
+def test_a_report_form_is_refused_without_its_own_mask(gpu, images):
+    src, ref = images
+    gpu.pair_upload(src, ref)
+    gpu.pair_set_region(region_ref.mask("ramp", SH, SW))
+    before = gpu.counter(nct.CTR_ARENA_BYTES)
+    with pytest.raises(nct.NctError) as e:                          # a source mask only
+        gpu.multi_run_ref_region_levels(_params(1))
+    assert e.value.code == -5 and "reference mask" in str(e.value)
+    assert gpu.counter(nct.CTR_ARENA_BYTES) == before
+    gpu.pair_upload(src, ref)                                       # drops the source mask
+    gpu.pair_set_ref_region(0, region_ref.mask("half", RH, RW))
+    before = gpu.counter(nct.CTR_ARENA_BYTES)
+    with pytest.raises(nct.NctError) as e:                          # a reference mask only
+        gpu.pair_run_region_levels(src.shape, ref.shape, _params(1))
+    assert e.value.code == -5 and "region mask" in str(e.value)
+    assert gpu.counter(nct.CTR_ARENA_BYTES) == before
 
 
 # ---- 5. two references, the first masked
@@ -348,3 +381,32 @@ def test_cli_refmask_fullres_shrinks_the_mask_with_its_image(tmp_path, gpu, weig
         assert r.returncode == 0, r.stdout + r.stderr
         out = np.asarray(Image.open(tmp_path / tag / "a_r_2.00.png").convert("RGB"))[..., ::-1]
         assert np.array_equal(out, gpu.process_pair_fullres_ref_region(a, None, big, q, 1000, None, prm)), tag
+
+
+def test_cli_mask_with_two_references(tmp_path, gpu, weights):
+    """-mask on a comma line: the bytes of nct_multi_upload + nct_pair_set_region + nct_multi_run + nct_pair_download"""
+    from caffemodel_io import write_caffemodel
+    (tmp_path / "model" / "vgg19").mkdir(parents=True)
+    write_caffemodel(str(tmp_path / "model" / "vgg19" / "VGG_ILSVRC_19_layers.caffemodel"), *weights)
+    inp, masks = tmp_path / "in", tmp_path / "masks"
+    inp.mkdir(); masks.mkdir()
+    imgs = {n: synth.image(2000 + i, 40, 56) for i, n in enumerate(("a", "r", "s"))}
+    for n, im in imgs.items():
+        Image.fromarray(im[..., ::-1].copy()).save(inp / (n + ".png"))
+    ms = region_ref.mask("ramp", 40, 56)
+    Image.fromarray(ms, "L").save(masks / "a.png")
+    (inp / "pairs.txt").write_text("a.png r.png,s.png 2.0\n")
+    prm = _params(1)
+    prm.bds_weight = 2.0
+    outs = {}
+    for tag, extra in (("masked", ["-mask", str(masks), "-maskprotect", "1"]), ("plain", [])):
+        r = subprocess.run([BIN, "-m", str(tmp_path / "model"), "-i", str(inp), "-levels", "1", "-o", str(tmp_path / tag), *extra], capture_output=True, text=True)
+        pngs = [n for n in os.listdir(tmp_path / tag) if n.endswith(".png")]
+        assert r.returncode == 0 and len(pngs) == 1, r.stdout + r.stderr
+        outs[tag] = np.asarray(Image.open(tmp_path / tag / pngs[0]).convert("RGB"))[..., ::-1]
+    gpu.multi_upload(imgs["a"], [imgs["r"], imgs["s"]])
+    gpu.pair_set_region(ms, 1)
+    gpu.multi_run(prm)
+    assert np.array_equal(outs["masked"], gpu.pair_download())
+    assert np.array_equal(outs["plain"], gpu.process_multi(imgs["a"], [imgs["r"], imgs["s"]], prm))
+    assert not np.array_equal(outs["masked"], outs["plain"])
