@@ -10,7 +10,7 @@ MAX_SIDE, MAX_PIXELS = 16384, 1 << 26
 
 
 def working_size(h, w, max_side):
-    """rule 1 (host/main.cpp's shrink) in float32 exactly as C evaluates `(int)(max_side / (float)long * short)`, plus the limits of rule 5; None = refused"""
+    """rule 1 (host/cli_job.cpp's shrink) in float32 exactly as C evaluates `(int)(max_side / (float)long * short)`, plus the limits of rule 5; None = refused"""
     if not 17 <= max_side <= 4000 or h < 1 or w < 1 or h > MAX_SIDE or w > MAX_SIDE or h * w > MAX_PIXELS:
         return None
     ch, cw = h, w
