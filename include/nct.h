@@ -32,7 +32,8 @@ extern "C" {
  * full-resolution sequences, nct_color_finish_upsample, nct_process_pair_fullres_finish and nct_seq_begin_fullres; still 118 with the guided finish, nct_color_finish_guided[_dev], nct_set_finish_guided and nct_guided_params: no struct
  * changed layout and no existing entry point changed meaning, entry points were only added; likewise still 118 with source region masks, nct_region_*, nct_pair_set_region,
  * nct_process_pair_region and nct_lut_fit_masked, and with reference region masks, nct_region_pull[_dev], nct_pair_set_ref_region, nct_multi_run_ref_region_levels and
- * nct_process_*_ref_region). A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
+ * nct_process_*_ref_region, and with region masks in sequences, nct_seq_set_region, nct_seq_frame[_propagate]_region_levels and nct_color_finish_{upsample,guided}_region[_dev]).
+ * A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
 #define NCT_VERSION 118
 
@@ -569,6 +570,43 @@ int nct_process_multi_ref_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, i
                                  const uint8_t* const* ref_masks, const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr, nct_pair_timing* timing);
 int nct_process_pair_fullres_ref_region(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, const uint8_t* mask0, const uint8_t* ref_bgr, int rh, int rw, const uint8_t* ref_mask0,
                                         int max_side, const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr /* sh x sw x 3 */, nct_pair_timing* timing);
+
+/* ---- region masks in sequences (SPEC §6.13; an extension): §6.11's source mask on the frames of an open sequence, and the masked upsampling finish.
+ * nct_seq_set_region: on an open sequence, between frames. mask has one byte per pixel at the size frames arrive — sh x sw after nct_seq_begin, the original size after
+ * nct_seq_begin_fullres, where it is also shrunk on the device to the working size by nct_resize_u8c1 — and is copied to the device in the call. It is sticky: every later
+ * nct_seq_frame, _levels, _propagate, _propagate_levels and nct_seq_frame_auto runs masked until the mask is replaced or removed with mask == NULL; nct_seq_reset keeps
+ * it, nct_seq_end and nct_destroy drop it. region NULL: the defaults. No open sequence: NCT_ERR_STATE; protect outside {0, 1}: NCT_ERR_INVALID, and the setting stays as
+ * it was. A caller with a matte per frame calls it before every frame.
+ * A full frame runs per level S1, §6.3's blend (into the kept state, unchanged), §6.11's mix OUT OF PLACE from the kept X'_t into the level's own map, U1 / roughness /
+ * S2 / A1 on the mixed map, §6.11's compose. The kept X' is never mixed: a matte that moves or changes needs no reset, and the next frame's blend never sees this frame's
+ * matte. A propagated frame runs §6.5 unchanged on the unmixed state, then mixes the top level run's X'_t with that level's mask into 48 B per level pixel of scratch and
+ * finishes on that; only the level masks down to the top level run are built. Finishes: the working size and NCT_FINISH_EXACT compose as §6.11 rules 3 and 5; with
+ * NCT_FINISH_UPSAMPLE (plain or guided) the working-size finish runs as in a working-size masked sequence and the masked upsampling finish follows: per original pixel
+ * Lab_S and Lab_o as nct_color_finish_upsample / nct_color_finish_guided compute them up to A1, keep = (protect and M0 == 0) or (M0 != 255 and Lab_o == Lab_S on all
+ * three bytes), out = keep ? S0 : Lab2BGR(Lab_o). One kernel, 3 + 1 B read and 3 B written per original pixel, no original-size intermediate.
+ * No nct_seq_set_region call: the sequence's bytes, launches and arena of before. M == 255: the unmasked sequence's bytes and state; M == 0: every frame is its source.
+ * A first frame, a frame after nct_seq_reset, a CUT frame and every frame with tau == 0 equal nct_process_pair_region (NCT_FINISH_EXACT: nct_process_pair_fullres_region).
+ * nct_seq_probe's record and nct_seq_frame_auto's decisions do not depend on the mask. nct_pair_fit_lut after a masked frame fits over M >= 128 at the size it reads.
+ * nct_seq_frame_region_levels / nct_seq_frame_propagate_region_levels: the _levels forms plus nct_region_levels — ab_mix[l] = the mixed map the finish read (a propagated
+ * frame: the top level run only), mask[l] = M_l; seq_levels->ab_blend[l] stays the unmixed kept state. Region levels asked for and no mask set: NCT_ERR_STATE.
+ * nct_color_finish_upsample_region[_dev], nct_color_finish_guided_region[_dev]: the masked upsampling finish alone; the arguments, limits and refusals of the unmasked
+ * calls plus mask (H*W bytes; NULL: the unmasked call) and region (NULL: the defaults; a bad protect: NCT_ERR_INVALID). Equal sizes keep the copy path.
+ * Not defined: reference masks in sequences (nct_pair_set_ref_region keeps its refusal), carrying a matte along the motion field, and a masked upsampling finish for
+ * pairs through nct_process_pair_fullres_finish_region (its refusal stays; a one-frame full-resolution sequence gives those bytes). */
+int nct_seq_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_params* region);
+int nct_seq_frame_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels,
+                                const nct_region_levels* region_levels);
+int nct_seq_frame_propagate_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* seq_levels,
+                                          const nct_region_levels* region_levels);
+int nct_color_finish_upsample_region(nct_ctx* ctx, const double* ab_wls, int h, int w, const uint8_t* s_bgr_full, int H, int W, const uint8_t* mask /* H*W */,
+                                     const nct_region_params* region, const nct_params* prm, uint8_t* out_bgr_full);
+int nct_color_finish_upsample_region_dev(nct_ctx* ctx, const double* d_ab_wls, int h, int w, const uint8_t* d_s_bgr_full, int H, int W, const uint8_t* d_mask /* H*W */,
+                                         const nct_region_params* region, const nct_params* prm, uint8_t* d_out_bgr_full);
+int nct_color_finish_guided_region(nct_ctx* ctx, const double* ab_wls, const uint8_t* lab_work, int h, int w, const uint8_t* s_bgr_full, int H, int W, const uint8_t* mask /* H*W */,
+                                   const nct_region_params* region, const nct_guided_params* guided, const nct_params* prm, uint8_t* out_bgr_full);
+int nct_color_finish_guided_region_dev(nct_ctx* ctx, const double* d_ab_wls, const uint8_t* d_lab_work, int h, int w, const uint8_t* d_s_bgr_full, int H, int W,
+                                       const uint8_t* d_mask /* H*W */, const nct_region_params* region, const nct_guided_params* guided, const nct_params* prm,
+                                       uint8_t* d_out_bgr_full);
 
 /* ---- device-pointer seams: the same operations on buffers that stay in HBM between calls (main.cu:204-316 keeps Ndata_C1, ann_device, ... on the device
  * across these kernels; an integrator replacing single seams should not pay H2D + D2H + a synchronise per call). Buffers come from the context's arena

@@ -241,4 +241,22 @@ int nct_color_finish_guided_dev(nct_ctx* ctx, const double* d_ab_wls, const uint
     return nctk_finish_guided(ctx, ctx->stream, d_ab_wls, d_lab_work, h, w, d_s_bgr_full, H, W, guided->sigma, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0, d_out_bgr_full);
 }
 
+// ---- SPEC §6.13 rule 4 on device pointers: the masked upsampling finish; mask NULL is the unmasked call
+int nct_color_finish_upsample_region_dev(nct_ctx* ctx, const double* d_ab_wls, int h, int w, const uint8_t* d_s_bgr_full, int H, int W, const uint8_t* d_mask,
+                                         const nct_region_params* region, const nct_params* prm, uint8_t* d_out_bgr_full) {
+    if (!d_mask) return nct_color_finish_upsample_dev(ctx, d_ab_wls, h, w, d_s_bgr_full, H, W, prm, d_out_bgr_full);
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(prm, "color_finish_upsample_region_dev: null pointer");
+    return nctk_finish_upsample_region(ctx, ctx->stream, d_ab_wls, h, w, d_s_bgr_full, d_mask, H, W, region ? region->protect : 0, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0, d_out_bgr_full);
+}
+
+int nct_color_finish_guided_region_dev(nct_ctx* ctx, const double* d_ab_wls, const uint8_t* d_lab_work, int h, int w, const uint8_t* d_s_bgr_full, int H, int W,
+                                       const uint8_t* d_mask, const nct_region_params* region, const nct_guided_params* guided, const nct_params* prm, uint8_t* d_out_bgr_full) {
+    if (!d_mask) return nct_color_finish_guided_dev(ctx, d_ab_wls, d_lab_work, h, w, d_s_bgr_full, H, W, guided, prm, d_out_bgr_full);
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(guided && prm, "color_finish_guided_region_dev: null pointer");
+    return nctk_finish_guided_region(ctx, ctx->stream, d_ab_wls, d_lab_work, h, w, d_s_bgr_full, d_mask, H, W, guided->sigma, region ? region->protect : 0,
+                                     (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0, d_out_bgr_full);
+}
+
 }  // extern "C"

@@ -196,7 +196,8 @@ struct nct_color_debug { double *ab_local, *ab_nonlocal, *ab_up, *rough, *ab_wls
 #define NCT_FINISH_MAX_PIXELS (1LL << 26)
 // the upsampling finish behind a working-size finish (SPEC §6.8): the original source in BGR at H x W, where its result goes, the Lab -> BGR form
 // sigma > 0: the guided finish (SPEC §6.10) with the working-size Lab image of that finish as its guide; 0: the plain bilinear one
-struct nct_finish_up { const uint8_t* s_bgr; int H, W; uint8_t* out_bgr; int form; double sigma; };
+// mask (nullable): the masked upsampling finish (SPEC §6.13 rule 4) — the source's region mask at H x W and nct_region_params.protect
+struct nct_finish_up { const uint8_t* s_bgr; int H, W; uint8_t* out_bgr; int form; double sigma; const uint8_t* mask; int protect; };
 // what a level's colour stage keeps reserved from T1 until its finish has been enqueued, declared by the caller: the coefficients x ([2][h*w][3]: T1's guess, then S1's
 // output), T2's weights and extremes and — requested between S1 and the finish by a frame of a sequence that reports it (SPEC §6.3) — the tau_p map
 struct NCT_LOCAL nct_color_bufs { DevBuf<double> x, weight; DevBuf<unsigned> mm; DevBuf<double> tmap; };
@@ -213,6 +214,12 @@ int nctk_finish_upsample(nct_ctx* ctx, hipStream_t s, const double* ab_wls, int 
 // k_finish_up.hip — SPEC §6.10: the same pass with joint-bilateral weights; lab_work ([h*w][3], device): the 8-bit Lab image of the working-size source. Equal sizes: nctk_finish_upsample
 int nctk_finish_guided(nct_ctx* ctx, hipStream_t s, const double* ab_wls, const uint8_t* lab_work, int h, int w, const uint8_t* s_bgr_full, int H, int W, double sigma, int form,
                        uint8_t* out_bgr_full);
+// k_finish_up_region.hip — SPEC §6.13 rule 4: the two passes above with the compose of SPEC §6.11 rule 3 in the place of their Lab -> BGR; mask ([H*W], device) must
+// not be null, protect is nct_region_params'. Equal sizes keep the copy path
+int nctk_finish_upsample_region(nct_ctx* ctx, hipStream_t s, const double* ab_wls, int h, int w, const uint8_t* s_bgr_full, const uint8_t* mask, int H, int W, int protect, int form,
+                                uint8_t* out_bgr_full);
+int nctk_finish_guided_region(nct_ctx* ctx, hipStream_t s, const double* ab_wls, const uint8_t* lab_work, int h, int w, const uint8_t* s_bgr_full, const uint8_t* mask, int H, int W,
+                              double sigma, int protect, int form, uint8_t* out_bgr_full);
 // sigma and sigma^2 (what the kernel divides by) are finite and > 0
 static inline bool nct_guided_sigma_ok(double sigma) { const double s2 = sigma * sigma; return sigma > 0.0 && s2 > 0.0 && s2 <= 1.7976931348623157e308; }
 // SPEC §6.1 rule 1 + the limits of rule 5: nullptr and the working size, or the reason the image is refused (a static string)

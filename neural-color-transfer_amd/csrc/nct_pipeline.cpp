@@ -101,7 +101,8 @@ int finish_level(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int
         if (region) return nctk_region_compose(ctx, s, full->src, fl.s0, fl.out0, region->mask, (size_t)full->H * full->W, region->protect, cube, full->out);
         return nctk_lab2bgr(ctx, s, fl.out0, full->out, (size_t)full->H * full->W, cube);
     }
-    const nct_finish_up up{full ? full->src : nullptr, full ? full->H : 0, full ? full->W : 0, full ? full->out : nullptr, cube, ctx->guided_sigma /* nct_set_finish_guided */};
+    const nct_finish_up up{full ? full->src : nullptr, full ? full->H : 0, full ? full->W : 0, full ? full->out : nullptr, cube, ctx->guided_sigma /* nct_set_finish_guided */,
+                           full && region ? full->mask : nullptr, region ? region->protect : 0};
     NCT_TRY(nctk_color_finish(ctx, s, x, h, w, H, W, s_lab_full, H, W, cp, out_lab, dbg, full ? &up : nullptr));
     if (region) return nctk_region_compose(ctx, s, region->s_bgr, s_lab_full, out_lab, region->mask, (size_t)H * W, region->protect, cube, out_bgr);
     return nctk_lab2bgr(ctx, s, out_lab, out_bgr, (size_t)H * W, cube);
@@ -180,7 +181,7 @@ struct pair_run {
 
     pair_run(nct_ctx* c, const nct_params* p, nct_pair_timing* t, const run_extras& x)
         : ctx(c), prm(p), timing(t), lv(x.lv ? x.lv : &kNoLevels), color(x.color), fin(x.fin), seq(x.seq), slv(x.slv), qlv(x.qlv), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
-          nlevels(p->levels), N((size_t)H * W), feat16((p->flags & NCT_FLAG_FEAT16) != 0), count(t && (p->flags & NCT_FLAG_COUNT_EVALS)), side(c), mask(x.seq ? nullptr : P->mask),
+          nlevels(p->levels), N((size_t)H * W), feat16((p->flags & NCT_FLAG_FEAT16) != 0), count(t && (p->flags & NCT_FLAG_COUNT_EVALS)), side(c), mask(P->mask),
           ref_masked(!x.seq && P->ref_masked()), cp(nct_color_params_of(*p)) {}
 
     int d2h(void* dst, const void* src, size_t bytes) {
@@ -456,26 +457,28 @@ struct pair_run {
         // a frame of a sequence: the blend between S1 and the finish, which then reads the kept X'_t (SPEC §6.3 rule 3)
         if (seq) NCT_TRY(seq_level_step(ctx, s, seq, l, side.slab[l], cb.x, cb.tmap, slv));
         // a masked run: S1's coefficients move toward the identity by the mix mask m_l, in place (SPEC §6.11 rule 2); the finish reads X' and composes with the source by f_l
-        // (rule 3), the mask at the size the finish targets. A source mask only: f_l is that mask as it came. With a reference mask (SPEC §6.12 rules 4-5): F_l = P_l at that
+        // (rule 3), the mask at the size the finish targets. A source mask only: f_l is that mask as it came. A masked frame of a sequence (SPEC §6.13 rule 2) mixes out of
+        // place, from the kept X'_t into the level's own map, which the finish then reads: the state is never mixed. With a reference mask (SPEC §6.12 rules 4-5): F_l = P_l at that
         // size, then the minimum with the source's — the last level's is kept for nct_pair_fit_lut (rule 7)
         const bool masked = mask || ref_masked;
         if (masked) {
-            const int fh = full ? full->H : H, fw = full ? full->W : W;
-            f_l = full ? full->mask : mask;
+            const bool exact = full && full->finish == NCT_FINISH_EXACT;      // the upsampling finish composes at the working size (and, in its own pass, on the original)
+            const int fh = exact ? full->H : H, fw = exact ? full->W : W;
+            f_l = exact ? full->mask : mask;
             if (ref_masked) {
                 uint8_t* f = f_level;
                 if (l == nlevels - 1) { if (!(P->fin_mask = (uint8_t*)ctx->alloc((size_t)fh * fw))) return NCT_ERR_HIP; f = P->fin_mask; }
                 NCT_TRY(nctk_region_upsize_min(ctx, s, p_l, ah[l], aw[l], f_l, f, fh, fw));
                 f_l = f;
             }
-            NCT_TRY(nctk_region_mix(ctx, s, cb.x, m_l, ah[l], aw[l], cb.x));
+            NCT_TRY(nctk_region_mix(ctx, s, seq ? seq->keep_x[l] : (double*)cb.x, m_l, ah[l], aw[l], cb.x));
             if (qlv) {
                 NCT_TRY(dbg_copy(ctx, s, qlv->ab_mix[l], (double*)cb.x, (size_t)6 * na_px)); NCT_TRY(dbg_copy(ctx, s, qlv->mask[l], m_l, (size_t)na_px));
                 NCT_TRY(dbg_copy(ctx, s, qlv->mask_full[l], f_l, (size_t)fh * fw));
             }
         }
         const region_fin rg{f_l, P->src, P->protect};
-        NCT_TRY(finish_level(ctx, s, seq ? seq->keep_x[l] : (double*)cb.x, ah[l], aw[l], H, W, s_lab_full, out_lab, P->out, full, fl, cp, d, nct_cube_form(*prm), masked ? &rg : nullptr));
+        NCT_TRY(finish_level(ctx, s, seq && !masked ? seq->keep_x[l] : (double*)cb.x, ah[l], aw[l], H, W, s_lab_full, out_lab, P->out, full, fl, cp, d, nct_cube_form(*prm), masked ? &rg : nullptr));
         if (cs && cs->wls_iters) for (int q = 0; q < 6; ++q) cs->wls_iters[q] = wls_it[q];
         if (timing) timing->wls_iters[l] = *std::max_element(wls_it, wls_it + 6);
         MARK(NCT_ST_COLOR, l);
@@ -525,7 +528,7 @@ int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timin
     NCT_REQUIRE(!x.fin || (!x.lv && !x.color), "process: no level intermediates with a full-resolution finish");
     NCT_REQUIRE(!x.color || P->K == 1, "process: nct_pair_levels describes a pair; several references report through nct_multi_levels");
     if (x.refusal) return ctx->fail(NCT_ERR_STATE, "%s", x.refusal);
-    NCT_REQUIRE(!(P->mask && x.fin) || (x.fin->finish == NCT_FINISH_EXACT && x.fin->mask), "process: a region mask is defined for the exact full-resolution finish only");
+    NCT_REQUIRE(!(P->mask && x.fin) || (x.fin->mask && (x.fin->finish == NCT_FINISH_EXACT || x.seq)), "process: a region mask is defined for the exact full-resolution finish only");
     NCT_REQUIRE(!(P->ref_masked() && x.fin) || x.fin->finish == NCT_FINISH_EXACT, "process: a reference region mask is defined for the exact full-resolution finish only");
     // a new run on the resident images: an earlier full-resolution run is no longer the last one, and its two original-size images go back to the arena
     // (a full-resolution sequence keeps its two for its whole life: SPEC §6.9 rule 6)
@@ -553,8 +556,7 @@ nct_multi_levels multi_levels_of(const nct_pair_levels& levels) {
     m.labels = levels.labels;
     return m;
 }
-// a source-masked run's report (SPEC §6.11) is the part of the reference-masked one's that it has: M_l and X'
-static nct_ref_region_levels ref_region_levels_of(const nct_region_levels& levels) {
+nct_ref_region_levels ref_region_levels_of(const nct_region_levels& levels) {
     nct_ref_region_levels q = {};
     for (int l = 0; l < 5; ++l) { q.ab_mix[l] = levels.ab_mix[l]; q.mask[l] = levels.mask[l]; }
     return q;
@@ -867,7 +869,7 @@ int nct_pair_fit_lut(nct_ctx* ctx, const nct_lut_params* prm, float* lut_out) {
     if (P && !P->finished) P = nullptr;
     // a masked run's table is fitted over its region (SPEC §6.11 rule 7), with the mask at the size of the images it reads
     if (P && P->full_src && P->full_out) { src = P->full_src; res = P->full_out; mask = P->full_mask; npix = (size_t)P->full_h * P->full_w; }
-    else if (P && P->src && P->out && P->sh > 0) { src = P->src; res = P->out; mask = P->seq ? nullptr : P->mask; npix = (size_t)P->sh * P->sw; }
+    else if (P && P->src && P->out && P->sh > 0) { src = P->src; res = P->out; mask = P->mask; npix = (size_t)P->sh * P->sw; }
     // a run with a reference mask: its last level's target mask, which has the size of the result (SPEC §6.12 rule 7)
     if (src && P->fin_mask && !P->seq) mask = P->fin_mask;
     if (!src) return ctx->fail(NCT_ERR_STATE, "pair_fit_lut: no finished run on this context (nct_pair_run first)");

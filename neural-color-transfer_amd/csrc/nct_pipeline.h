@@ -4,7 +4,8 @@
 #include <chrono>
 // the last level's finish on a source larger than the working size (SPEC §6.1, §6.9): the original source on the device, H x W, where its result goes, and the finish —
 // NCT_FINISH_EXACT moves U1 / S2 / A1 there, NCT_FINISH_UPSAMPLE leaves them at the working size and upsamples S2's output (SPEC §6.8)
-// mask (nullable; the exact finish only): the source's region mask at H x W (SPEC §6.11 rule 5), on the device
+// mask (nullable): the source's region mask at H x W, on the device — the exact finish composes with it (SPEC §6.11 rule 5), the upsampling finish of a masked
+// sequence frame runs its masked form with it (SPEC §6.13 rule 4)
 struct full_target { const uint8_t* src = nullptr; int H = 0, W = 0; uint8_t* out = nullptr; int finish = NCT_FINISH_EXACT; const uint8_t* mask = nullptr; };
 
 // An open frame sequence (SPEC §6.3): what nct_seq_begin prepares once and every frame borrows — the reference's pyramid and its five un-normalised taps (HWC, by
@@ -39,12 +40,15 @@ struct pair_state {
     int full_h = 0, full_w = 0;
     uint8_t *mask = nullptr, *full_mask = nullptr;             // the source's region mask (SPEC §6.11): sh x sw bytes, set by nct_pair_set_region, dropped with the images; after a masked
     int protect = 0;                                           // full-resolution run also the mask at full_h x full_w, beside full_src / full_out. protect: nct_region_params
+                                                               // An open sequence (SPEC §6.13): both are nct_seq_set_region's and go back with the sequence (seq_free)
     uint8_t* rmask[NCT_MAX_REFS] = {};                         // the references' region masks (SPEC §6.12): rh[k] x rw[k] bytes, set by nct_pair_set_ref_region, dropped with the images
     uint8_t* fin_mask = nullptr;                               // the last level's target mask F of a run with a reference mask, at the size of its result (rule 7: nct_pair_fit_lut); gone with the next run
     bool ref_masked() const { for (const uint8_t* m : rmask) if (m) return true; return false; }
     bool finished = false;                                     // the last run on these images ran to its end: `out` (or full_out) holds its result
 };
 
+// a source-masked run's report (SPEC §6.11, §6.13) is the part of the reference-masked one's that it has: M_l and X'
+NCT_LOCAL nct_ref_region_levels ref_region_levels_of(const nct_region_levels& levels);
 static const int kTapC[5] = {64, 128, 256, 512, 512};       // tap 1 (conv1_1) … tap 5 (conv5_1)
 #define MARK(stage, level) NCT_TRY(ctx->mark(s, nct_stage_tag(stage, level)))
 
@@ -98,7 +102,8 @@ struct NCT_LOCAL full_lab {
 // working grid H x W, s_lab_full -> out_lab -> out_bgr. The exact finish: onto the original source through fl's images into full->out; out_lab and out_bgr stay as they
 // are. The upsampling finish (SPEC §6.8): the working-size finish, and behind it S2's output upsampled onto the original source into full->out
 // region (nullable; SPEC §6.11 rule 3, §6.12 rule 5): the run is masked — the compose with the source takes the place of Lab -> BGR. mask: the compose mask at the size this
-// finish targets (the exact finish: full's size, and the source is full's; else H x W and s_bgr)
+// finish targets (the exact finish: full's size, and the source is full's; else H x W and s_bgr). The upsampling finish of a masked run (SPEC §6.13 rule 4) composes at
+// H x W with `mask` and on the original source with full->mask, in the upsampling pass itself
 struct region_fin { const uint8_t* mask; const uint8_t* s_bgr; int protect; };
 NCT_LOCAL int finish_level(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int H, int W, const uint8_t* s_lab_full, uint8_t* out_lab, uint8_t* out_bgr,
                            const full_target* full, const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube, const region_fin* region = nullptr);

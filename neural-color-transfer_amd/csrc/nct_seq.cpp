@@ -1,4 +1,4 @@
-// nct_seq.cpp — frame sequences (SPEC §6.3-§6.9): the state an open sequence keeps in the context's arena, what a level of a frame does between S1 and the finish,
+// nct_seq.cpp — frame sequences (SPEC §6.3-§6.9, their region mask §6.13): the state an open sequence keeps in the context's arena, what a level of a frame does between S1 and the finish,
 // the frame entry points — a full frame is a run of nct_pipeline.cpp's level loop — the propagated frame, the probe and the key-frame decision.
 #include "nct_pipeline.h"
 #include <cstring>
@@ -24,6 +24,10 @@ void seq_free(nct_ctx* ctx, pair_state* P) {
         if (q->keep_x[l]) ctx->release(q->keep_x[l]);
         if (q->keep_lab[l]) ctx->release(q->keep_lab[l]);
     }
+    // the sequence's region mask (SPEC §6.13 rule 1) ends with it
+    if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
+    if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
+    P->protect = 0;
     delete q; P->seq = nullptr;
 }
 
@@ -120,6 +124,51 @@ int nct_seq_reset(nct_ctx* ctx) {
     return NCT_OK;
 }
 
+// the mask of nct_seq_set_region onto the device, into blocks the sequence keeps until the mask is removed: at the size it came, and (a full-resolution sequence) shrunk
+static int seq_mask_upload(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* mask) {
+    const size_t n = (size_t)P->sh * P->sw;
+    if (!P->mask && !(P->mask = (uint8_t*)ctx->alloc(n))) return NCT_ERR_HIP;
+    if (q->target()) {
+        const size_t n0 = (size_t)q->full.H * q->full.W;
+        if (!P->full_mask && !(P->full_mask = (uint8_t*)ctx->alloc(n0))) return NCT_ERR_HIP;
+        NCT_H2D(P->full_mask, mask, n0);
+        NCT_TRY(nctk_resize_u8c1(ctx, ctx->stream, P->full_mask, q->full.H, q->full.W, P->mask, P->sh, P->sw));
+        q->full.mask = P->full_mask;
+    } else NCT_H2D(P->mask, mask, n);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
+// SPEC §6.13 rule 1: the open sequence's region mask, sticky from the next frame on. It arrives at the size frames arrive; a full-resolution sequence keeps it at that
+// size (the exact and the upsampling finish compose with it, nct_pair_fit_lut reads it) and shrinks it on the device to the working size. NULL removes it
+int nct_seq_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_params* region) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_set_region: no sequence is open (nct_seq_begin first)");
+    NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "seq_set_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
+    seq_state* q = P->seq;
+    // the state stays; what the last frame left is no longer the result of these settings
+    P->finished = false;
+    if (!mask) {
+        if (P->mask || P->full_mask) NCT_SYNC();
+        if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
+        if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
+        q->full.mask = nullptr; P->protect = 0;
+        return NCT_OK;
+    }
+    const int rc = seq_mask_upload(ctx, P, q, mask);
+    if (rc) {
+        // a device error half way: no mask is better than a block of unknown bytes
+        (void)hipStreamSynchronize(ctx->stream);
+        if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
+        if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
+        q->full.mask = nullptr; P->protect = 0;
+        return rc;
+    }
+    P->protect = region ? region->protect : 0;
+    return NCT_OK;
+}
+
 // the reference once: upload, pyramid (main.cu:104-108), one VGG19 forward with all five taps kept channel-last; and the per-level state
 // rh0 x rw0: the reference as the caller holds it — larger than rh x rw only in a full-resolution sequence, which shrinks it on the device (SPEC §6.9)
 static int seq_prepare(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* ref_bgr, int rh0, int rw0, int rh, int rw, int sh, int sw) {
@@ -204,6 +253,12 @@ static int seq_upload_frame(nct_ctx* ctx, pair_state* P, seq_state* q, const uin
 }
 
 int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels) {
+    return nct_seq_frame_region_levels(ctx, src_bgr, out_bgr, timing, levels, seq_levels, nullptr);
+}
+
+// region_levels (nullable; SPEC §6.13): where a masked frame's mixed maps and level masks go
+int nct_seq_frame_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels,
+                                const nct_region_levels* region_levels) {
     NCT_CTX_ENTER();
     pair_state* P = (pair_state*)ctx->pair;
     if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_frame: no sequence is open (nct_seq_begin first)");
@@ -216,6 +271,9 @@ int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr,
     const nct_multi_levels m = levels ? multi_levels_of(*levels) : nct_multi_levels{};
     run_extras x; x.fin = q->target(); x.seq = q; x.slv = seq_levels;
     if (levels) { x.lv = &m; x.color = levels->color; }
+    nct_ref_region_levels qlv;
+    if (region_levels) { qlv = ref_region_levels_of(*region_levels); x.qlv = &qlv; }
+    if (region_levels && !P->mask) x.refusal = "seq_frame: region levels asked for, but no region mask is set (nct_seq_set_region first)";
     if (rc == NCT_OK) rc = process_resident(ctx, &q->prm, timing, x);
     // a frame that failed may have replaced the state of some levels only: the next frame starts over
     q->gap = 0; q->acc = 0;                                      // a full frame (and a failed one: the next is a first frame) starts the count over
@@ -234,7 +292,9 @@ int nct_seq_frame(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pa
 // SPEC §6.5: what a propagated frame enqueues — the frame's pyramid, per level L_t and (motion on) the field, the warp of the kept X' and the packed map, then the
 // finish of the last level run on the kept X' and the frame's own pixels, and the download. Nothing upstream of the finish runs. L_t goes straight into the state:
 // on this path nothing reads L_(t-1) but the search, which reads its packed form
-static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* slv) {
+// With a region mask (SPEC §6.13 rule 3) all of that runs unchanged on the unmixed state; then the last level run's X'_t is mixed with that level's mask into scratch of
+// the call, the finish reads the mixed map and composes. Only the level masks down to that level are built. rlv (nullable): where the mixed map and those masks go
+static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* slv, const nct_region_levels* rlv) {
     const hipStream_t s = ctx->stream;
     const nct_params& prm = q->prm;
     const int H = P->sh, W = P->sw, top = prm.levels - 1;
@@ -275,7 +335,28 @@ static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out
     const nct_color_debug dbg{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, wls_it};
     full_lab fl;
     NCT_TRY(fl.open(ctx, s, q->target()));
-    NCT_TRY(finish_level(ctx, s, q->keep_x[top], q->ah[top], q->aw[top], H, W, s_lab_full, out_lab, P->out, q->target(), fl, nct_color_params_of(prm), timing ? &dbg : nullptr, nct_cube_form(prm)));
+    const double* x_fin = q->keep_x[top];
+    DevBuf<uint8_t> mpyr[4]; DevBuf<double> x_mix;
+    const bool exact = q->target() && q->full.finish == NCT_FINISH_EXACT;
+    const region_fin rg{exact ? q->full.mask : P->mask, P->src, P->protect};
+    if (P->mask) {
+        const uint8_t* mimg[5]; mimg[4] = P->mask;
+        for (int l = 3; l >= top; --l) {
+            if (!mpyr[l].alloc(ctx, (size_t)q->ah[l] * q->aw[l])) return NCT_ERR_HIP;
+            NCT_TRY(nctk_resize_u8c1(ctx, s, mimg[l + 1], q->ah[l + 1], q->aw[l + 1], mpyr[l], q->ah[l], q->aw[l]));
+            mimg[l] = mpyr[l];
+        }
+        const size_t n = (size_t)q->ah[top] * q->aw[top];
+        if (!x_mix.alloc(ctx, 6 * n)) return NCT_ERR_HIP;
+        NCT_TRY(nctk_region_mix(ctx, s, q->keep_x[top], mimg[top], q->ah[top], q->aw[top], x_mix));
+        x_fin = x_mix;
+        if (rlv) {
+            NCT_TRY(dbg_copy(ctx, s, rlv->ab_mix[top], (double*)x_mix, 6 * n));
+            for (int l = top; l < 5; ++l) NCT_TRY(dbg_copy(ctx, s, rlv->mask[l], mimg[l], (size_t)q->ah[l] * q->aw[l]));
+        }
+    }
+    NCT_TRY(finish_level(ctx, s, x_fin, q->ah[top], q->aw[top], H, W, s_lab_full, out_lab, P->out, q->target(), fl, nct_color_params_of(prm), timing ? &dbg : nullptr, nct_cube_form(prm),
+                         P->mask ? &rg : nullptr));
     if (timing) timing->wls_iters[top] = *std::max_element(wls_it, wls_it + 6);
     MARK(NCT_ST_COLOR, top);
     if (q->target()) NCT_D2H(out_bgr, P->full_out, (size_t)q->full.H * q->full.W * 3);
@@ -285,15 +366,22 @@ static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out
 }
 
 int nct_seq_frame_propagate_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* seq_levels) {
+    return nct_seq_frame_propagate_region_levels(ctx, src_bgr, out_bgr, timing, seq_levels, nullptr);
+}
+
+int nct_seq_frame_propagate_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* seq_levels,
+                                          const nct_region_levels* region_levels) {
     NCT_CTX_ENTER();
     pair_state* P = (pair_state*)ctx->pair;
     if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_frame_propagate: no sequence is open (nct_seq_begin first)");
     seq_state* q = P->seq;
     if (q->frames == 0) return ctx->fail(NCT_ERR_STATE, "seq_frame_propagate: the sequence has no state to propagate (the first frame after nct_seq_begin / nct_seq_reset is nct_seq_frame's)");
     NCT_REQUIRE(src_bgr && out_bgr, "seq_frame_propagate: null image");
+    if (region_levels && !P->mask) return ctx->fail(NCT_ERR_STATE, "seq_frame_propagate: region levels asked for, but no region mask is set (nct_seq_set_region first)");
     run_clock clock(ctx, timing, q->prm.flags);
     int rc = seq_upload_frame(ctx, P, q, src_bgr);
-    if (rc == NCT_OK) rc = propagate_run(ctx, P, q, out_bgr, timing, seq_levels);
+    if (rc == NCT_OK) rc = propagate_run(ctx, P, q, out_bgr, timing, seq_levels, region_levels);
+    if (rc == NCT_OK) P->finished = true;                        // nct_seq_set_region cleared it: this frame is the result of the new settings
     clock.stop();
     // a frame that failed may have replaced the state of some levels only: the next frame starts over
     if (rc) { (void)hipStreamSynchronize(ctx->stream); q->frames = 0; q->gap = 0; q->acc = 0; return rc; }

@@ -154,6 +154,14 @@ SIGNATURES = {
                                                          C.c_void_p]),
     "nct_lut_fit_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_lut_fit_masked_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_set_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_frame_region_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_frame_propagate_region_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_color_finish_upsample_region": (C.c_int, [C.c_void_p, _f64p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _u8p]),
+    "nct_color_finish_upsample_region_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_color_finish_guided_region": (C.c_int, [C.c_void_p, _f64p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u8p]),
+    "nct_color_finish_guided_region_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]),
     "nct_region_pull": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "nct_region_pull_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "nct_pair_set_ref_region": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -797,6 +805,44 @@ class Context:
             self._chk(self._l.nct_color_finish_guided_dev(self._h, blocks[0], blocks[1], h, w, blocks[2], H, W, C.addressof(gp), C.addressof(prm), blocks[3]))
             return self.dev_download(blocks[3], (H, W, 3), np.uint8)
 
+    def color_finish_upsample_region(self, ab_wls, h, w, s_full, mask, protect=None, params=None, dev=False):
+        """nct_color_finish_upsample_region[_dev] (SPEC §6.13 rule 4): color_finish_upsample with §6.11's compose in its pass; mask [H, W] bytes of s_full, None: the
+        unmasked call"""
+        return self._finish_region(ab_wls, None, h, w, s_full, mask, protect, None, params, dev)
+
+    def color_finish_upsample_region_dev(self, ab_wls, h, w, s_full, mask, protect=None, params=None):
+        return self._finish_region(ab_wls, None, h, w, s_full, mask, protect, None, params, True)
+
+    def color_finish_guided_region(self, ab_wls, lab_work, h, w, s_full, mask, protect=None, sigma=None, params=None, dev=False):
+        """nct_color_finish_guided_region[_dev] (SPEC §6.13 rule 4): color_finish_guided with §6.11's compose in its pass"""
+        return self._finish_region(ab_wls, np.ascontiguousarray(lab_work, np.uint8), h, w, s_full, mask, protect, _guided_params(sigma), params, dev)
+
+    def color_finish_guided_region_dev(self, ab_wls, lab_work, h, w, s_full, mask, protect=None, sigma=None, params=None):
+        return self._finish_region(ab_wls, np.ascontiguousarray(lab_work, np.uint8), h, w, s_full, mask, protect, _guided_params(sigma), params, True)
+
+    def _finish_region(self, ab_wls, lw, h, w, s_full, mask, protect, gp, params, dev):
+        """the four masked finish seams: lw / gp None = the plain upsampling finish, else the guided one"""
+        a = np.ascontiguousarray(ab_wls, np.float64).reshape(-1)
+        assert a.size == 6 * h * w and (lw is None or lw.size == 3 * h * w)
+        s_full = np.ascontiguousarray(s_full, np.uint8)
+        H, W = s_full.shape[:2]
+        name = "nct_color_finish_upsample_region" if lw is None else "nct_color_finish_guided_region"
+        m = None if mask is None else _mask_arg(mask, s_full.shape, name[4:])
+        prm, rg = params or Params.default(), _region_params(protect)
+        tail = [C.addressof(rg)] + ([C.addressof(gp)] if lw is not None else []) + [C.addressof(prm)]
+        if not dev:
+            out = np.empty((H, W, 3), np.uint8)
+            mid = [a] + ([lw.reshape(-1, 3)] if lw is not None else [])
+            self._chk(getattr(self._l, name)(self._h, *mid, h, w, s_full.reshape(-1, 3), H, W, m.ctypes.data if m is not None else None, *tail, out.reshape(-1, 3)))
+            return out
+        blocks = [self.dev_upload(a)] + ([self.dev_upload(lw)] if lw is not None else []) + [self.dev_upload(s_full), self.dev_alloc(s_full.size)]
+        if m is not None:
+            blocks.append(self.dev_upload(m))
+        with self._blocks(blocks):
+            nin = 1 if lw is None else 2
+            self._chk(getattr(self._l, name + "_dev")(self._h, *blocks[:nin], h, w, blocks[nin], H, W, blocks[nin + 2] if m is not None else None, *tail, blocks[nin + 1]))
+            return self.dev_download(blocks[nin + 1], (H, W, 3), np.uint8)
+
     def set_finish_guided(self, sigma):
         """nct_set_finish_guided: a sigma turns the guided modifier of the upsampling finish on for this context, None turns it off (the default)"""
         if sigma is None:
@@ -1046,7 +1092,39 @@ class Context:
         self._chk(self._l.nct_seq_frame(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
         return (out, tm.as_dict()) if want_timing else out
 
-    def seq_frame_levels(self, src_bgr, want_color=True, want_levels=None):
+    def seq_set_region(self, mask, protect=None):
+        """nct_seq_set_region (SPEC §6.13) on the open sequence: mask [h, w] bytes at the size frames arrive, or None to remove it. Sticky until replaced or removed"""
+        if mask is None:
+            self._chk(self._l.nct_seq_set_region(self._h, None, None))
+            return
+        rg = _region_params(protect)
+        shp = getattr(self, "_seq_shapes", None)
+        if shp is None:                                        # no open sequence: the library refuses; the mask is never read
+            m = np.ascontiguousarray(mask, np.uint8)
+        else:
+            m = _mask_arg(mask, shp[0], "seq_set_region")
+        self._chk(self._l.nct_seq_set_region(self._h, m.ctypes.data, C.addressof(rg)))
+
+    def seq_frame_region_levels(self, src_bgr, want_color=True, want_levels=None):
+        """nct_seq_frame_region_levels -> seq_frame_levels' (result, dict) plus per level that ran "ab_mix" (the mixed map the finish read, [2, h*w, 3]) and "mask" (M_l [h, w])"""
+        return self.seq_frame_levels(src_bgr, want_color, want_levels, _region=True)
+
+    def seq_frame_propagate_region_levels(self, src_bgr):
+        """nct_seq_frame_propagate_region_levels -> seq_frame_propagate_levels' (result, dict) plus "ab_mix" and "mask" per level that ran: the last level run's mixed map
+        (zeros elsewhere) and the level masks that were built (that level and finer; zeros elsewhere)"""
+        return self.seq_frame_propagate_levels(src_bgr, _region=True)
+
+    def _region_levels_arrays(self, dims, levels):
+        rl = RegionLevels()
+        ab_mix = [np.zeros((2, d[0] * d[1], 3)) for d in dims[:levels]]
+        mask = [np.zeros((d[0], d[1]), np.uint8) for d in dims]
+        for l in range(levels):
+            rl.ab_mix[l] = ab_mix[l].ctypes.data
+        for l in range(5):
+            rl.mask[l] = mask[l].ctypes.data
+        return rl, ab_mix, mask
+
+    def seq_frame_levels(self, src_bgr, want_color=True, want_levels=None, _region=False):
         """nct_seq_frame_levels -> (result, dict): pair_run_levels' per-level lists ("ann" … "result", with want_color "color" and "labels"), plus "ab_blend" and "tau_map"
         per level that ran (X'_t [2, h*w, 3] and tau_p [h, w]; a frame without a blend reports X_t and zeros), "motion" (SPEC §6.4: the level's field, int16 [h, w, 2] of
         (my, mx); zeros without motion or without a blend) and "timing"."""
@@ -1094,9 +1172,16 @@ class Context:
             sl.ab_blend[l] = ab_blend[l].ctypes.data; sl.tau_map[l] = tau_map[l].ctypes.data; sl.motion[l] = motion[l].ctypes.data
         out = np.empty_like(s)
         tm = PairTiming()
-        self._chk(self._l.nct_seq_frame_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv) if want_levels else None, C.addressof(sl)))
+        if _region:
+            rl, ab_mix, mask = self._region_levels_arrays(dims, levels)
+            self._chk(self._l.nct_seq_frame_region_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv) if want_levels else None, C.addressof(sl),
+                                                          C.addressof(rl)))
+        else:
+            self._chk(self._l.nct_seq_frame_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv) if want_levels else None, C.addressof(sl)))
         if not want_levels:
             keep = {}
+        if _region:
+            keep["ab_mix"] = ab_mix; keep["mask"] = mask[:levels]
         if want_color:
             keep["color"] = color; keep["labels"] = labels
         keep["ab_blend"] = ab_blend; keep["tau_map"] = tau_map; keep["motion"] = motion
@@ -1118,7 +1203,7 @@ class Context:
         self._chk(self._l.nct_seq_frame_propagate(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
         return (out, tm.as_dict()) if want_timing else out
 
-    def seq_frame_propagate_levels(self, src_bgr):
+    def seq_frame_propagate_levels(self, src_bgr, _region=False):
         """nct_seq_frame_propagate_levels -> (result, dict): per level that ran "ab_blend" (X'_t [2, h*w, 3]), "motion" (int16 [h, w, 2]; zeros with motion off) and
         "tau_map" (1.0 everywhere), plus "timing" and "dims" (the source's level grids)"""
         s = self._seq_frame_arg(src_bgr, "seq_frame_propagate_levels")
@@ -1141,6 +1226,10 @@ class Context:
             sl.ab_blend[l] = ab_blend[l].ctypes.data; sl.tau_map[l] = tau_map[l].ctypes.data; sl.motion[l] = motion[l].ctypes.data
         out = np.empty_like(s)
         tm = PairTiming()
+        if _region:
+            rl, ab_mix, mask = self._region_levels_arrays(dims, levels)
+            self._chk(self._l.nct_seq_frame_propagate_region_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(sl), C.addressof(rl)))
+            return out, {"ab_blend": ab_blend, "tau_map": tau_map, "motion": motion, "timing": tm.as_dict(), "dims": dims, "ab_mix": ab_mix, "mask": mask[:levels]}
         self._chk(self._l.nct_seq_frame_propagate_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(sl)))
         return out, {"ab_blend": ab_blend, "tau_map": tau_map, "motion": motion, "timing": tm.as_dict(), "dims": dims}
 
