@@ -32,7 +32,8 @@ extern "C" {
  * full-resolution sequences, nct_color_finish_upsample, nct_process_pair_fullres_finish and nct_seq_begin_fullres; still 118 with the guided finish, nct_color_finish_guided[_dev], nct_set_finish_guided and nct_guided_params: no struct
  * changed layout and no existing entry point changed meaning, entry points were only added; likewise still 118 with source region masks, nct_region_*, nct_pair_set_region,
  * nct_process_pair_region and nct_lut_fit_masked, and with reference region masks, nct_region_pull[_dev], nct_pair_set_ref_region, nct_multi_run_ref_region_levels and
- * nct_process_*_ref_region, and with region masks in sequences, nct_seq_set_region, nct_seq_frame[_propagate]_region_levels and nct_color_finish_{upsample,guided}_region[_dev]).
+ * nct_process_*_ref_region, and with region masks in sequences, nct_seq_set_region, nct_seq_frame[_propagate]_region_levels and nct_color_finish_{upsample,guided}_region[_dev], and with region tracking,
+ * nct_seq_matte_warp[_dev], nct_seq_set_region_tracking and nct_seq_get_region).
  * A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
 #define NCT_VERSION 118
@@ -591,7 +592,7 @@ int nct_process_pair_fullres_ref_region(nct_ctx* ctx, const uint8_t* src_bgr, in
  * frame: the top level run only), mask[l] = M_l; seq_levels->ab_blend[l] stays the unmixed kept state. Region levels asked for and no mask set: NCT_ERR_STATE.
  * nct_color_finish_upsample_region[_dev], nct_color_finish_guided_region[_dev]: the masked upsampling finish alone; the arguments, limits and refusals of the unmasked
  * calls plus mask (H*W bytes; NULL: the unmasked call) and region (NULL: the defaults; a bad protect: NCT_ERR_INVALID). Equal sizes keep the copy path.
- * Not defined: reference masks in sequences (nct_pair_set_ref_region keeps its refusal), carrying a matte along the motion field, and a masked upsampling finish for
+ * Not defined: reference masks in sequences (nct_pair_set_ref_region keeps its refusal) and a masked upsampling finish for
  * pairs through nct_process_pair_fullres_finish_region (its refusal stays; a one-frame full-resolution sequence gives those bytes). */
 int nct_seq_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_params* region);
 int nct_seq_frame_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels,
@@ -607,6 +608,35 @@ int nct_color_finish_guided_region(nct_ctx* ctx, const double* ab_wls, const uin
 int nct_color_finish_guided_region_dev(nct_ctx* ctx, const double* d_ab_wls, const uint8_t* d_lab_work, int h, int w, const uint8_t* d_s_bgr_full, int H, int W,
                                        const uint8_t* d_mask /* H*W */, const nct_region_params* region, const nct_guided_params* guided, const nct_params* prm,
                                        uint8_t* d_out_bgr_full);
+
+/* ---- region tracking (SPEC §6.14; an extension): the matte of §6.13 follows the motion field of §6.4, so that it is drawn on one frame and carried through the shot.
+ * nct_seq_matte_warp[_dev]: the carry alone. mask_prev: H x W bytes; field: h x w int16 pairs (my, mx), a backward field on a level grid (it points from the frame
+ * into the previous one), 1 <= h <= H <= 16384, 1 <= w <= W <= 16384, h, w <= 4096, H * W <= 2^26. Per target pixel and axis (y shown): num = (2y + 1) h - H,
+ * s = floor(num / 2H), t = num - 2H s, clamped to the grid with t = 0 at its ends, s1 = min(s + 1, h - 1) — nct_resize's centre-aligned index rule as an exact
+ * fraction; the four vectors around (sy, sx) are weighted with (2H - ty, ty) x (2W - tx, tx) into the sum S, and d_y = floor((2 S_y H + den) / (2 den)),
+ * den = h * 2H * 2W (d_x: W and w): the vector in target pixels, rounded half up. mask_out(y, x) = mask_prev(clamp(y + d_y, 0, H - 1), clamp(x + d_x, 0, W - 1)).
+ * 64-bit integers only; a byte is copied, never interpolated: a binary matte stays binary, all-255 stays all-255, a zero field returns the input, and with H == h,
+ * W == w this is nct_seq_warp's gather on bytes. The host form is synchronous; the _dev form is enqueued on the context's stream and refuses a mask_out that overlaps
+ * mask_prev. A null pointer, a side out of range and a target smaller than the field grid are NCT_ERR_INVALID, the message names the argument.
+ * nct_seq_set_region_tracking: on an open sequence, between frames; off (0) is the default, no open sequence is NCT_ERR_STATE, `on` outside {0, 1} NCT_ERR_INVALID.
+ * A matte given to nct_seq_set_region belongs to the next frame that runs: that frame uses it as it came (age 0); a refused call and nct_seq_probe do not use it up.
+ * While tracking is on, every later nct_seq_frame, _levels, _region_levels, _propagate* and nct_seq_frame_auto first carries the matte: M_t = matte_warp(M_(t-1), the
+ * field of the frame's top level run against the previous frame), at the size frames arrive — a full-resolution sequence carries M0 at the original size with the
+ * working-size level's field and shrinks the result with nct_resize_u8c1, as nct_seq_set_region does; with levels < 5 the field's grid is coarser than the working
+ * size, which the same rule covers. From there on the frame is §6.13's: its bytes and kept state are those of the same sequence with nct_seq_set_region(M_t) called
+ * before it. The field is zero — the matte stays, the age still counts — with motion off, in a sequence without state (a first frame, after nct_seq_reset) and on a
+ * CUT frame of nct_seq_frame_auto: AFTER A CUT THE CALLER SHOULD SET A NEW MATTE, the old one marks a place in a shot that is over. A full frame finds its fields ahead
+ * of its level masks whether or not it blends (tau == 0 too); the carry's time counts in other_ms. A coarse field holds whole vectors of its own grid: a pan of a
+ * fraction of a cell per frame does not move the matte (SPEC §6.14 rule 5). Turning tracking off leaves the matte in force as a sticky §6.13 matte. The first carry
+ * reserves one second matte block at the size frames arrive; the two change places. Never turned on, or no matte set: every sequence path is what it was.
+ * nct_seq_get_region: the matte in force at the size frames arrive (a full-resolution sequence: the original size) and, through `age` (nullable), the frames run since
+ * the matte's own frame while tracking was on. No open sequence or no matte: NCT_ERR_STATE. Synchronous.
+ * Not defined: occlusion handling or a confidence for the carried matte, sub-pixel motion, and which of the two mattes stays after a frame that fails (such a frame
+ * leaves the sequence reset). */
+int nct_seq_matte_warp(nct_ctx* ctx, const uint8_t* mask_prev /* H*W */, int H, int W, const int16_t* field /* h*w*2 */, int h, int w, uint8_t* mask_out /* H*W */);
+int nct_seq_matte_warp_dev(nct_ctx* ctx, const uint8_t* d_mask_prev, int H, int W, const int16_t* d_field, int h, int w, uint8_t* d_mask_out);
+int nct_seq_set_region_tracking(nct_ctx* ctx, int on);
+int nct_seq_get_region(nct_ctx* ctx, uint8_t* mask_out, int* age);
 
 /* ---- device-pointer seams: the same operations on buffers that stay in HBM between calls (main.cu:204-316 keeps Ndata_C1, ann_device, ... on the device
  * across these kernels; an integrator replacing single seams should not pay H2D + D2H + a synchronise per call). Buffers come from the context's arena

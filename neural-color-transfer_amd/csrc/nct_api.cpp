@@ -396,6 +396,21 @@ int nct_seq_warp(nct_ctx* ctx, const double* x_prev, int h, int w, const int16_t
     return NCT_OK;
 }
 
+// SPEC §6.14 rule 1 on host arrays: the matte and the field up, one k_seq_matte_warp launch out of place, the carried matte down
+int nct_seq_matte_warp(nct_ctx* ctx, const uint8_t* mask_prev, int H, int W, const int16_t* field, int h, int w, uint8_t* mask_out) {
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_seq_matte_warp_check(ctx, "seq_matte_warp", mask_prev, H, W, field, h, w, mask_out));
+    const size_t N = (size_t)H * W, n = (size_t)h * w;
+    DevBuf<uint8_t> dp(ctx, N), dm(ctx, N);
+    DevBuf<int16_t> df(ctx, 2 * n);
+    if (!dp.ok() || !dm.ok() || !df.ok()) return NCT_ERR_HIP;
+    NCT_H2D(dp, mask_prev, N); NCT_H2D(df, field, sizeof(int16_t) * 2 * n);
+    NCT_TRY(nctk_seq_matte_warp(ctx, ctx->stream, dp, H, W, df, h, w, dm));
+    NCT_D2H(mask_out, dm, N);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
 // SPEC §6.7 rule 1 on host maps: the two Lab level images (and the field) up, one k_seq_change launch, the 16-byte record down
 int nct_seq_change(nct_ctx* ctx, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, const int16_t* field, int threshold, nct_seq_change_rec* out) {
     NCT_CTX_ENTER();

@@ -179,6 +179,11 @@ int nct_seq_warp_dev(nct_ctx* ctx, const double* d_x_prev, int h, int w, const i
     return nctk_seq_warp(ctx, ctx->stream, d_x_prev, h, w, d_field, d_x_out);
 }
 
+int nct_seq_matte_warp_dev(nct_ctx* ctx, const uint8_t* d_mask_prev, int H, int W, const int16_t* d_field, int h, int w, uint8_t* d_mask_out) {       /* SPEC §6.14 rule 1 */
+    NCT_CTX_ENTER();
+    return nctk_seq_matte_warp(ctx, ctx->stream, d_mask_prev, H, W, d_field, h, w, d_mask_out);
+}
+
 int nct_seq_change_dev(nct_ctx* ctx, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, const int16_t* d_field, int threshold, nct_seq_change_rec* d_out) {   /* SPEC §6.7 rule 1 */
     NCT_CTX_ENTER();
     return nctk_seq_change(ctx, ctx->stream, d_lab, d_lab_prev, h, w, d_field, threshold, d_out);

@@ -242,6 +242,11 @@ int nctk_seq_warp(nct_ctx* ctx, hipStream_t s, const double* x_prev, int h, int 
 // SPEC §6.7 rule 1: sad = sum_p r(p), changed = #{p : r(p) > threshold}, pixels = h * w, r(p) the three-byte SAD of lab(p) and lab_prev(p + m(p)); field nullable (m = 0).
 // rec: 16 bytes on the device, zeroed and filled on s
 int nctk_seq_change(nct_ctx* ctx, hipStream_t s, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, const int16_t* field, int threshold, nct_seq_change_rec* rec);
+// k_seq_track.hip — SPEC §6.14 rule 1: mask_out(p) = mask_prev(p + d(p)), d the field ([h*w][2] int16 (my, mx) on a level grid h x w <= H x W) interpolated at p, scaled to
+// target pixels and rounded half up in integers, a position that leaves the matte clamped to it; mask_out must not overlap mask_prev
+int nctk_seq_matte_warp(nct_ctx* ctx, hipStream_t s, const uint8_t* mask_prev, int H, int W, const int16_t* field, int h, int w, uint8_t* mask_out);
+// its argument checks (`who` names the entry point in the message), for the host form to run before it moves anything
+int nct_seq_matte_warp_check(nct_ctx* ctx, const char* who, const void* mask_prev, int H, int W, const void* field, int h, int w, const void* mask_out);
 // k_lut.hip — 3D colour look-up tables (SPEC §6.6). W [N^3] / R [N^3][3]: the splat's integer sums (zeroed on s by the splat itself); D [N^3][3]: the displacement
 // field after NCT_LUT_CYCLES V(2,2) cycles; lut [N^3][3] fp32. in / out of the apply may be the same buffer
 #define NCT_LUT_CYCLES 17

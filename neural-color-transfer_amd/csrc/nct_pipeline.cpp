@@ -172,7 +172,7 @@ struct pair_run {
     // the pyramid's single-channel form. ref_masked: a reference has a region mask (SPEC §6.12); p_merged: P_l of several references (rule 3), m_level: M_l where it is not
     // P_l itself (rule 4: a source mask as well), f_level: F_l of a level that is not the last (the last level's is pair_state's fin_mask).
     // What a level's colour stage reads of all that (level_masks, color_stage): m_l, the mix mask on the level grid, and f_l, the compose mask at the size its finish targets
-    const uint8_t* const mask;
+    const uint8_t* mask;                           // a tracked frame of a sequence (SPEC §6.14) carries the matte first: lab_and_pyramids reads the pointer again
     DevBuf<uint8_t> mpyr[4]; const uint8_t* mimg[5] = {};
     const bool ref_masked;
     DevBuf<uint8_t> p_merged, m_level, f_level;
@@ -213,6 +213,8 @@ struct pair_run {
             if (seq) { R[0].img[l] = seq->rpyr[l]; continue; }          // the sequence's reference pyramid was built at nct_seq_begin
             for (int k = 0; k < K; ++k) NCT_TRY(pyramid_level(ctx, s, R[k].pyr[l], R[k].img, R[k].bh, R[k].bw, l));
         }
+        // SPEC §6.14: a tracked sequence's matte follows the frame's field before its level masks are built; the two matte blocks may have changed places
+        if (seq && mask) { NCT_TRY(seq_track_step(ctx, s, P, seq, simg)); mask = P->mask; }
         if (mask) {
             // SPEC §6.11 rule 1: the level masks, each resized from the level above like the image pyramid
             mimg[4] = mask;

@@ -16,6 +16,8 @@ struct full_target { const uint8_t* src = nullptr; int H = 0, W = 0; uint8_t* ou
 // The two counters of the key-frame decision (SPEC §6.7 rule 3) are host integers: they cost no device memory.
 // A full-resolution sequence (SPEC §6.9, nct_seq_begin_fullres) keeps all of that on the working-size grids and adds the frame at its original size H0 x W0 and
 // its result: pair_state's full_src / full_out, which live as long as the sequence and are what nct_pair_fit_lut reads; `full` describes them, H = 0 in any other sequence.
+// Region tracking (SPEC §6.14, nct_seq_set_region_tracking): the matte in force (pair_state's mask, or full_mask in a full-resolution sequence) is carried out of
+// place into matte_alt, a second block of the size frames arrive, reserved by the first carry; then the two change places. The flags and the age are host values.
 struct seq_state {
     nct_params prm; double tau = 0, sigma = 0;
     long frames = 0;                                           // frames since nct_seq_begin / nct_seq_reset: 0 = the next one is a first frame
@@ -27,6 +29,10 @@ struct seq_state {
     bool motion = false; nct_seq_motion mp = {0, 0, 0};
     uint32_t* keep_pk[5] = {}; int16_t* field[5] = {};
     double* warp_x = nullptr;
+    bool tracking = false;                                     // SPEC §6.14: carry the matte along the field in front of every frame but the matte's own
+    bool matte_fresh = false;                                  // nct_seq_set_region gave a matte that no frame has used yet: the next frame that runs is its own
+    long matte_age = 0;                                        // frames run since the matte's own frame while tracking was on
+    uint8_t* matte_alt = nullptr;
     full_target full;
     const full_target* target() const { return full.H ? &full : nullptr; }
 };
@@ -112,6 +118,14 @@ NCT_LOCAL void seq_free(nct_ctx* ctx, pair_state* P);       // what an open sequ
 // SPEC §6.4: level l's field from L_t (`lab`) and the kept packed map: the first level run searches radius0 around (0, 0), every other level radius around twice the
 // previous level's vector
 NCT_LOCAL int seq_motion_level(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, const uint8_t* lab);
+// The chain ahead of the expensive stages, shared by the probe (SPEC §6.7 rule 2) and the carry of a full frame (SPEC §6.14): for l = 0 … top the frame's level image
+// simg[l] in Lab into lab[l] (requested here, the caller's to give back) and, with motion on, level l's field against the kept packed map into the level's field buffer
+NCT_LOCAL int seq_field_chain(nct_ctx* ctx, hipStream_t s, seq_state* q, const uint8_t* const* simg, int top, DevBuf<uint8_t>* lab);
+// SPEC §6.14 rule 2, in front of a frame's level masks: nothing without a matte; the matte's own frame only marks it used; else, with tracking on, the age counts and —
+// where the frame has a field (motion on, a sequence with state) — the matte is carried through the field of the top level run, the two blocks change places, and a
+// full-resolution sequence shrinks the carried matte to the working size. simg: the frame's pyramid, from which a full frame finds the fields first; null: a
+// propagated frame, whose level loop has just left them in the field buffers
+NCT_LOCAL int seq_track_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, const uint8_t* const* simg);
 // A level of a sequence frame (SPEC §6.3), between S1 and the finish: X'_t = the blend of S1's output x with X'_(t-1), into the kept state q->keep_x[l], which the finish
 // then reads; L_t (`lab`) replaces L_(t-1). The first frame and tau == 0 only keep the state, with no blend launch. tmap: the caller's, requested here where slv asks
 // for the tau_p map and reserved until the finish has been enqueued. slv (nullable): host copies of X'_t, tau_p and the field

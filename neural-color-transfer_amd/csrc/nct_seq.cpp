@@ -1,4 +1,4 @@
-// nct_seq.cpp — frame sequences (SPEC §6.3-§6.9, their region mask §6.13): the state an open sequence keeps in the context's arena, what a level of a frame does between S1 and the finish,
+// nct_seq.cpp — frame sequences (SPEC §6.3-§6.9, their region mask §6.13 and its tracking §6.14): the state an open sequence keeps in the context's arena, what a level of a frame does between S1 and the finish,
 // the frame entry points — a full frame is a run of nct_pipeline.cpp's level loop — the propagated frame, the probe and the key-frame decision.
 #include "nct_pipeline.h"
 #include <cstring>
@@ -27,6 +27,7 @@ void seq_free(nct_ctx* ctx, pair_state* P) {
     // the sequence's region mask (SPEC §6.13 rule 1) ends with it
     if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
     if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
+    if (q->matte_alt) { ctx->release(q->matte_alt); q->matte_alt = nullptr; }
     P->protect = 0;
     delete q; P->seq = nullptr;
 }
@@ -56,6 +57,42 @@ int seq_level_step(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, const uint8
     if (q->motion) NCT_TRY(nctk_seq_pack(ctx, s, lab, n, q->keep_pk[l]));
     if (slv) NCT_TRY(dbg_copy(ctx, s, slv->ab_blend[l], keep_x, (size_t)6 * n));
     if (tmap.ok()) NCT_TRY(dbg_copy(ctx, s, slv->tau_map[l], (double*)tmap, n));
+    return NCT_OK;
+}
+
+int seq_field_chain(nct_ctx* ctx, hipStream_t s, seq_state* q, const uint8_t* const* simg, int top, DevBuf<uint8_t>* lab) {
+    for (int l = 0; l <= top; ++l) {
+        const int h = q->ah[l], w = q->aw[l];
+        if (!lab[l].alloc(ctx, (size_t)h * w * 3)) return NCT_ERR_HIP;
+        NCT_TRY(nctk_bgr2lab(ctx, s, simg[l], lab[l], (size_t)h * w));
+        if (q->motion) NCT_TRY(seq_motion_level(ctx, s, q, l, lab[l]));
+    }
+    return NCT_OK;
+}
+
+int seq_track_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, const uint8_t* const* simg) {
+    if (!P->mask) return NCT_OK;
+    if (q->matte_fresh) { q->matte_fresh = false; return NCT_OK; }          // the matte's own frame uses it as it came: age 0
+    if (!q->tracking) return NCT_OK;
+    q->matte_age += 1;
+    // a zero field (motion off; a first frame, a frame after nct_seq_reset, a CUT frame: no state) leaves the matte where it is
+    if (!q->motion || q->frames == 0) return NCT_OK;
+    const int top = q->prm.levels - 1;
+    if (simg) {
+        // a full frame finds its fields here, ahead of its level masks, whether or not it blends; the Lab scratch goes back with this call
+        DevBuf<uint8_t> lab[5];
+        NCT_TRY(seq_field_chain(ctx, s, q, simg, top, lab));
+    }
+    uint8_t*& matte = q->target() ? P->full_mask : P->mask;
+    const int H = q->target() ? q->full.H : P->sh, W = q->target() ? q->full.W : P->sw;
+    if (!q->matte_alt && !(q->matte_alt = (uint8_t*)ctx->alloc((size_t)H * W))) return NCT_ERR_HIP;
+    NCT_TRY(nctk_seq_matte_warp(ctx, s, matte, H, W, q->field[top], q->ah[top], q->aw[top], q->matte_alt));
+    std::swap(matte, q->matte_alt);
+    if (q->target()) {
+        // the carry ran at the original size; the working-size matte is its shrink, as nct_seq_set_region makes it
+        q->full.mask = P->full_mask;
+        NCT_TRY(nctk_resize_u8c1(ctx, s, P->full_mask, H, W, P->mask, P->sh, P->sw));
+    }
     return NCT_OK;
 }
 
@@ -124,6 +161,14 @@ int nct_seq_reset(nct_ctx* ctx) {
     return NCT_OK;
 }
 
+// the sequence's matte blocks go back to the arena (the caller has waited for the stream)
+static void seq_mask_drop(nct_ctx* ctx, pair_state* P, seq_state* q) {
+    if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
+    if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
+    if (q->matte_alt) { ctx->release(q->matte_alt); q->matte_alt = nullptr; }
+    q->full.mask = nullptr; P->protect = 0; q->matte_fresh = false; q->matte_age = 0;
+}
+
 // the mask of nct_seq_set_region onto the device, into blocks the sequence keeps until the mask is removed: at the size it came, and (a full-resolution sequence) shrunk
 static int seq_mask_upload(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* mask) {
     const size_t n = (size_t)P->sh * P->sw;
@@ -151,21 +196,44 @@ int nct_seq_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_param
     P->finished = false;
     if (!mask) {
         if (P->mask || P->full_mask) NCT_SYNC();
-        if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
-        if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
-        q->full.mask = nullptr; P->protect = 0;
+        seq_mask_drop(ctx, P, q);
         return NCT_OK;
     }
     const int rc = seq_mask_upload(ctx, P, q, mask);
     if (rc) {
         // a device error half way: no mask is better than a block of unknown bytes
         (void)hipStreamSynchronize(ctx->stream);
-        if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
-        if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
-        q->full.mask = nullptr; P->protect = 0;
+        seq_mask_drop(ctx, P, q);
         return rc;
     }
     P->protect = region ? region->protect : 0;
+    // SPEC §6.14 rule 2: the matte belongs to the next frame that runs
+    q->matte_fresh = true; q->matte_age = 0;
+    return NCT_OK;
+}
+
+// SPEC §6.14 rule 2: from the next frame on the matte in force follows the motion field (1), or stays where it is as a sticky §6.13 matte (0)
+int nct_seq_set_region_tracking(nct_ctx* ctx, int on) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_set_region_tracking: no sequence is open (nct_seq_begin first)");
+    NCT_REQUIRE(on == 0 || on == 1, "seq_set_region_tracking: on must be 0 or 1 (got %d)", on);
+    P->seq->tracking = on == 1;
+    return NCT_OK;
+}
+
+// the matte in force at the size frames arrive, and how many frames it has been carried or kept since its own
+int nct_seq_get_region(nct_ctx* ctx, uint8_t* mask_out, int* age) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_get_region: no sequence is open (nct_seq_begin first)");
+    if (!P->mask) return ctx->fail(NCT_ERR_STATE, "seq_get_region: no region mask is set (nct_seq_set_region first)");
+    NCT_REQUIRE(mask_out, "seq_get_region: null mask_out");
+    const seq_state* q = P->seq;
+    if (q->target()) NCT_D2H(mask_out, P->full_mask, (size_t)q->full.H * q->full.W);
+    else NCT_D2H(mask_out, P->mask, (size_t)P->sh * P->sw);
+    NCT_SYNC();
+    if (age) *age = (int)std::min<long>(q->matte_age, 0x7fffffffL);
     return NCT_OK;
 }
 
@@ -329,6 +397,12 @@ static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out
             if (slv->tau_map[l]) std::fill(slv->tau_map[l], slv->tau_map[l] + n, 1.0);          // the previous frame's weight
         }
     }
+    if (P->mask && q->tracking) {
+        // SPEC §6.14: the level loop has left the frame's fields in place; the matte follows the last level run's before the level masks are built. Its time is other_ms
+        MARK(NCT_ST_COLOR, top);
+        NCT_TRY(seq_track_step(ctx, s, P, q, nullptr));
+        MARK(NCT_ST_OTHER, 0);
+    } else NCT_TRY(seq_track_step(ctx, s, P, q, nullptr));      // only marks a new matte used
     // the kept (warped) X' of the last level run finishes on the frame's own pixels: at the working size, or (SPEC §6.9 rule 3) on the original frame
     ctx->tm_level = top;
     int wls_it[6] = {0, 0, 0, 0, 0, 0};
@@ -429,12 +503,7 @@ static int probe_run(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* s
     else NCT_H2D(frame, src_bgr, N * 3);
     const uint8_t* simg[5]; simg[4] = frame;
     for (int l = 3; l >= 0; --l) NCT_TRY(pyramid_level(ctx, s, spyr[l], simg, q->ah, q->aw, l));
-    for (int l = 0; l <= lambda; ++l) {
-        const int h = q->ah[l], w = q->aw[l];
-        if (!lab[l].alloc(ctx, (size_t)h * w * 3)) return NCT_ERR_HIP;
-        NCT_TRY(nctk_bgr2lab(ctx, s, simg[l], lab[l], (size_t)h * w));
-        if (q->motion) NCT_TRY(seq_motion_level(ctx, s, q, l, lab[l]));
-    }
+    NCT_TRY(seq_field_chain(ctx, s, q, simg, lambda, lab));
     NCT_TRY(nctk_seq_change(ctx, s, lab[lambda], q->keep_lab[lambda], q->ah[lambda], q->aw[lambda], q->motion ? q->field[lambda] : nullptr, threshold, d_rec));
     NCT_D2H(rec, d_rec, sizeof *rec);
     NCT_SYNC();

@@ -156,6 +156,10 @@ SIGNATURES = {
     "nct_lut_fit_masked_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_set_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_region_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_matte_warp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "nct_seq_matte_warp_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "nct_seq_set_region_tracking": (C.c_int, [C.c_void_p, C.c_int]),
+    "nct_seq_get_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_propagate_region_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_color_finish_upsample_region": (C.c_int, [C.c_void_p, _f64p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _u8p]),
     "nct_color_finish_upsample_region_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1104,6 +1108,37 @@ class Context:
         else:
             m = _mask_arg(mask, shp[0], "seq_set_region")
         self._chk(self._l.nct_seq_set_region(self._h, m.ctypes.data, C.addressof(rg)))
+
+    # ---- region tracking (SPEC §6.14)
+    def seq_matte_warp(self, mask, field, dev=False, alias=False):
+        """nct_seq_matte_warp[_dev] (SPEC §6.14 rule 1): mask [H, W] bytes, field int16 [h, w, 2] of (my, mx) on a level grid -> the matte read at p + d(p), d the field
+        interpolated at p in target pixels. dev: on arena blocks, into a block of its own (alias: into the matte's block, which is an error)"""
+        m = np.ascontiguousarray(mask, np.uint8)
+        f = np.ascontiguousarray(field, np.int16)
+        if m.ndim != 2 or f.ndim != 3 or f.shape[2] != 2:
+            raise NctError(-2, "seq_matte_warp: mask must be [H, W] bytes and field [h, w, 2] int16")
+        (H, W), (h, w) = m.shape, f.shape[:2]
+        if not dev:
+            out = np.empty_like(m)
+            self._chk(self._l.nct_seq_matte_warp(self._h, m.ctypes.data, H, W, f.ctypes.data, h, w, out.ctypes.data))
+            return out
+        ins = [self.dev_upload(m), self.dev_upload(f)]
+        do = self.dev_alloc(m.size)
+        with self._blocks(ins + [do]):
+            self._chk(self._l.nct_seq_matte_warp_dev(self._h, ins[0], H, W, ins[1], h, w, ins[0] if alias else do))
+            return self.dev_download(do, (H, W), np.uint8)
+
+    def seq_set_region_tracking(self, on):
+        """nct_seq_set_region_tracking: from the next frame on the open sequence's matte follows the motion field (True) or stays sticky (False)"""
+        self._chk(self._l.nct_seq_set_region_tracking(self._h, int(on)))
+
+    def seq_get_region(self):
+        """nct_seq_get_region -> (the matte in force at the size frames arrive, its age in frames)"""
+        shp = getattr(self, "_seq_shapes", None)
+        out = np.zeros(tuple(shp[0]) if shp is not None else (1, 1), np.uint8)      # no open sequence: the library refuses; nothing is written
+        age = C.c_int(-1)
+        self._chk(self._l.nct_seq_get_region(self._h, out.ctypes.data, C.addressof(age)))
+        return out, age.value
 
     def seq_frame_region_levels(self, src_bgr, want_color=True, want_levels=None):
         """nct_seq_frame_region_levels -> seq_frame_levels' (result, dict) plus per level that ran "ab_mix" (the mixed map the finish read, [2, h*w, 3]) and "mask" (M_l [h, w])"""
