@@ -33,7 +33,8 @@ extern "C" {
  * changed layout and no existing entry point changed meaning, entry points were only added; likewise still 118 with source region masks, nct_region_*, nct_pair_set_region,
  * nct_process_pair_region and nct_lut_fit_masked, and with reference region masks, nct_region_pull[_dev], nct_pair_set_ref_region, nct_multi_run_ref_region_levels and
  * nct_process_*_ref_region, and with region masks in sequences, nct_seq_set_region, nct_seq_frame[_propagate]_region_levels and nct_color_finish_{upsample,guided}_region[_dev], and with region tracking,
- * nct_seq_matte_warp[_dev], nct_seq_set_region_tracking and nct_seq_get_region).
+ * nct_seq_matte_warp[_dev], nct_seq_set_region_tracking and nct_seq_get_region, and with matte snapping, nct_region_snap[_dev], nct_region_snap_params and
+ * nct_seq_set_region_snap).
  * A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
 #define NCT_VERSION 118
@@ -637,6 +638,30 @@ int nct_seq_matte_warp(nct_ctx* ctx, const uint8_t* mask_prev /* H*W */, int H, 
 int nct_seq_matte_warp_dev(nct_ctx* ctx, const uint8_t* d_mask_prev, int H, int W, const int16_t* d_field, int h, int w, uint8_t* d_mask_out);
 int nct_seq_set_region_tracking(nct_ctx* ctx, int on);
 int nct_seq_get_region(nct_ctx* ctx, uint8_t* mask_out, int* age);
+
+/* ---- matte snapping (SPEC §6.15; an extension): a carried matte is re-fitted to the colours of the frame it now belongs to — a joint filter over the matte with the
+ * frame's 8-bit Lab image as the guide, in integers only.
+ * nct_region_snap[_dev]: mask: H x W bytes; lab: the 8-bit Lab image (nct_bgr2lab_u8) of the same frame at the same size, H x W x 3; 1 <= H, W <= 16384, H * W <= 2^26
+ * (nct_seq_matte_warp's target limits); params NULL: the defaults (radius 3, sigma 10, binary 1); radius in [1, 8], sigma in [1, 255] (8-bit Lab units), binary in {0, 1}.
+ * Per pixel p and tap q = p + (dy, dx), dy, dx = -radius … radius, taps outside the image skipped: d2 = the squared distance of lab(p) and lab(q) over the three bytes,
+ * w(q) = max(0, 3 sigma^2 - d2), A = sum w(q) mask(q), B = sum w(q) (the centre tap weighs 3 sigma^2: B > 0); v = floor((2A + B) / (2B)), the mean rounded half up;
+ * mask_out(p) = v, or with binary set v >= 128 ? 255 : 0. A constant matte comes back as it is; with binary 0 every byte lies between the least and the largest
+ * byte of its window; a guide whose every pixel is at least 3 sigma^2 away from all its neighbours returns the matte; a flat guide makes the pass a box mean (binary: a
+ * majority filter). The host form is synchronous; the _dev form is enqueued on the context's stream and refuses a mask_out that overlaps mask or lab (the pass
+ * gathers). A null pointer, a side or a parameter out of range are NCT_ERR_INVALID, the message names the argument.
+ * nct_seq_set_region_snap: on an open sequence, between frames; non-NULL turns snapping on with these parameters, NULL turns it off (the default). Bad parameters are
+ * NCT_ERR_INVALID and leave the setting as it was; no open sequence is NCT_ERR_STATE. Snapping acts only while tracking is on and a matte is set: on every frame on
+ * which the matte's age counts (not the matte's own frame) in a sequence with state — not on a first frame, a frame after nct_seq_reset or a CUT frame — the matte is
+ * snapped behind the carry, M_t = snap(matte_warp(M_(t-1), field), Lab(S_t)), with motion on or off (off: the field is zero, the snap alone re-fits the matte). The
+ * guide is nct_bgr2lab_u8 of the frame at the size frames arrive: a full-resolution sequence snaps at the original size, before the shrink to the working-size matte.
+ * From there on the frame is §6.13's, its bytes and kept state those of the same sequence with nct_seq_set_region(M_t) called before it; nct_seq_get_region returns
+ * the snapped matte; the snap's time counts in other_ms. It reserves nothing for the life of the sequence beside tracking's second matte block. A MATTE DRAWN ON NOTHING
+ * HAS NOTHING TO SNAP TO: a region that is texture, not an object of its own colour, erodes. Never turned on: every sequence path is what it was. */
+typedef struct nct_region_snap_params { int radius, sigma, binary; } nct_region_snap_params;
+void nct_region_snap_params_default(nct_region_snap_params* p);     /* radius 3, sigma 10, binary 1 */
+int nct_region_snap(nct_ctx* ctx, const uint8_t* mask /* H*W */, const uint8_t* lab /* H*W*3 */, int H, int W, const nct_region_snap_params* params, uint8_t* mask_out /* H*W */);
+int nct_region_snap_dev(nct_ctx* ctx, const uint8_t* d_mask, const uint8_t* d_lab, int H, int W, const nct_region_snap_params* params, uint8_t* d_mask_out);
+int nct_seq_set_region_snap(nct_ctx* ctx, const nct_region_snap_params* params);
 
 /* ---- device-pointer seams: the same operations on buffers that stay in HBM between calls (main.cu:204-316 keeps Ndata_C1, ann_device, ... on the device
  * across these kernels; an integrator replacing single seams should not pay H2D + D2H + a synchronise per call). Buffers come from the context's arena

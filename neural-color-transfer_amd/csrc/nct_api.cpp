@@ -411,6 +411,20 @@ int nct_seq_matte_warp(nct_ctx* ctx, const uint8_t* mask_prev, int H, int W, con
     return NCT_OK;
 }
 
+// SPEC §6.15 rule 1 on host arrays: the matte and the guide up, one k_region_snap launch out of place, the snapped matte down
+int nct_region_snap(nct_ctx* ctx, const uint8_t* mask, const uint8_t* lab, int H, int W, const nct_region_snap_params* params, uint8_t* mask_out) {
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_region_snap_check(ctx, "region_snap", mask, lab, H, W, params, mask_out));
+    const size_t N = (size_t)H * W;
+    DevBuf<uint8_t> dm(ctx, N), dl(ctx, N * 3), dout(ctx, N);
+    if (!dm.ok() || !dl.ok() || !dout.ok()) return NCT_ERR_HIP;
+    NCT_H2D(dm, mask, N); NCT_H2D(dl, lab, N * 3);
+    NCT_TRY(nctk_region_snap(ctx, ctx->stream, dm, dl, H, W, params, dout));
+    NCT_D2H(mask_out, dout, N);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
 // SPEC §6.7 rule 1 on host maps: the two Lab level images (and the field) up, one k_seq_change launch, the 16-byte record down
 int nct_seq_change(nct_ctx* ctx, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, const int16_t* field, int threshold, nct_seq_change_rec* out) {
     NCT_CTX_ENTER();

@@ -184,6 +184,11 @@ int nct_seq_matte_warp_dev(nct_ctx* ctx, const uint8_t* d_mask_prev, int H, int 
     return nctk_seq_matte_warp(ctx, ctx->stream, d_mask_prev, H, W, d_field, h, w, d_mask_out);
 }
 
+int nct_region_snap_dev(nct_ctx* ctx, const uint8_t* d_mask, const uint8_t* d_lab, int H, int W, const nct_region_snap_params* params, uint8_t* d_mask_out) {       /* SPEC §6.15 rule 1 */
+    NCT_CTX_ENTER();
+    return nctk_region_snap(ctx, ctx->stream, d_mask, d_lab, H, W, params, d_mask_out);
+}
+
 int nct_seq_change_dev(nct_ctx* ctx, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, const int16_t* d_field, int threshold, nct_seq_change_rec* d_out) {   /* SPEC §6.7 rule 1 */
     NCT_CTX_ENTER();
     return nctk_seq_change(ctx, ctx->stream, d_lab, d_lab_prev, h, w, d_field, threshold, d_out);

@@ -247,6 +247,12 @@ int nctk_seq_change(nct_ctx* ctx, hipStream_t s, const uint8_t* lab, const uint8
 int nctk_seq_matte_warp(nct_ctx* ctx, hipStream_t s, const uint8_t* mask_prev, int H, int W, const int16_t* field, int h, int w, uint8_t* mask_out);
 // its argument checks (`who` names the entry point in the message), for the host form to run before it moves anything
 int nct_seq_matte_warp_check(nct_ctx* ctx, const char* who, const void* mask_prev, int H, int W, const void* field, int h, int w, const void* mask_out);
+// k_region_snap.hip — SPEC §6.15 rule 1: mask_out(p) = the mean of mask over p's (2 radius + 1)^2 window inside the image, weighted with max(0, 3 sigma^2 - |lab(p) - lab(q)|^2)
+// and rounded half up (binary: cut at 128 to 0 / 255); lab: the frame's 8-bit Lab image [H*W][3]; params null: the defaults; mask_out must overlap neither input
+int nctk_region_snap(nct_ctx* ctx, hipStream_t s, const uint8_t* mask, const uint8_t* lab, int H, int W, const nct_region_snap_params* params, uint8_t* mask_out);
+// its argument checks (`who` names the entry point in the message), for the host form to run before it moves anything, and the parameters' alone (null: the defaults)
+int nct_region_snap_check(nct_ctx* ctx, const char* who, const void* mask, const void* lab, int H, int W, const nct_region_snap_params* params, const void* mask_out);
+int nct_region_snap_params_check(nct_ctx* ctx, const char* who, const nct_region_snap_params* params);
 // k_lut.hip — 3D colour look-up tables (SPEC §6.6). W [N^3] / R [N^3][3]: the splat's integer sums (zeroed on s by the splat itself); D [N^3][3]: the displacement
 // field after NCT_LUT_CYCLES V(2,2) cycles; lut [N^3][3] fp32. in / out of the apply may be the same buffer
 #define NCT_LUT_CYCLES 17

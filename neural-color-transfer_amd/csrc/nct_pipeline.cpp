@@ -214,7 +214,7 @@ struct pair_run {
             for (int k = 0; k < K; ++k) NCT_TRY(pyramid_level(ctx, s, R[k].pyr[l], R[k].img, R[k].bh, R[k].bw, l));
         }
         // SPEC §6.14: a tracked sequence's matte follows the frame's field before its level masks are built; the two matte blocks may have changed places
-        if (seq && mask) { NCT_TRY(seq_track_step(ctx, s, P, seq, simg)); mask = P->mask; }
+        if (seq && mask) { NCT_TRY(seq_track_step(ctx, s, P, seq, simg, s_lab_full)); mask = P->mask; }
         if (mask) {
             // SPEC §6.11 rule 1: the level masks, each resized from the level above like the image pyramid
             mimg[4] = mask;

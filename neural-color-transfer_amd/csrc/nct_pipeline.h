@@ -18,6 +18,8 @@ struct full_target { const uint8_t* src = nullptr; int H = 0, W = 0; uint8_t* ou
 // its result: pair_state's full_src / full_out, which live as long as the sequence and are what nct_pair_fit_lut reads; `full` describes them, H = 0 in any other sequence.
 // Region tracking (SPEC §6.14, nct_seq_set_region_tracking): the matte in force (pair_state's mask, or full_mask in a full-resolution sequence) is carried out of
 // place into matte_alt, a second block of the size frames arrive, reserved by the first carry; then the two change places. The flags and the age are host values.
+// Matte snapping (SPEC §6.15, nct_seq_set_region_snap): behind the carry the matte is snapped to the frame's Lab image, again out of place into matte_alt — the block
+// the carry has just left — and the two change places once more; a frame that snaps without a carry (motion off) reserves the block the same way.
 struct seq_state {
     nct_params prm; double tau = 0, sigma = 0;
     long frames = 0;                                           // frames since nct_seq_begin / nct_seq_reset: 0 = the next one is a first frame
@@ -33,6 +35,7 @@ struct seq_state {
     bool matte_fresh = false;                                  // nct_seq_set_region gave a matte that no frame has used yet: the next frame that runs is its own
     long matte_age = 0;                                        // frames run since the matte's own frame while tracking was on
     uint8_t* matte_alt = nullptr;
+    bool snap = false; nct_region_snap_params snap_p = {0, 0, 0};  // SPEC §6.15: snap the carried matte to the frame's edges with these parameters
     full_target full;
     const full_target* target() const { return full.H ? &full : nullptr; }
 };
@@ -124,8 +127,10 @@ NCT_LOCAL int seq_field_chain(nct_ctx* ctx, hipStream_t s, seq_state* q, const u
 // SPEC §6.14 rule 2, in front of a frame's level masks: nothing without a matte; the matte's own frame only marks it used; else, with tracking on, the age counts and —
 // where the frame has a field (motion on, a sequence with state) — the matte is carried through the field of the top level run, the two blocks change places, and a
 // full-resolution sequence shrinks the carried matte to the working size. simg: the frame's pyramid, from which a full frame finds the fields first; null: a
-// propagated frame, whose level loop has just left them in the field buffers
-NCT_LOCAL int seq_track_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, const uint8_t* const* simg);
+// propagated frame, whose level loop has just left them in the field buffers. With snapping on (SPEC §6.15) a sequence with state then snaps the matte, carried or
+// not, to the frame's Lab image at the size frames arrive: lab_work, the working-size frame in Lab that the caller holds, or — a full-resolution sequence whose
+// frames are larger — the original frame converted into scratch of this call
+NCT_LOCAL int seq_track_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, const uint8_t* const* simg, const uint8_t* lab_work);
 // A level of a sequence frame (SPEC §6.3), between S1 and the finish: X'_t = the blend of S1's output x with X'_(t-1), into the kept state q->keep_x[l], which the finish
 // then reads; L_t (`lab`) replaces L_(t-1). The first frame and tau == 0 only keep the state, with no blend launch. tmap: the caller's, requested here where slv asks
 // for the tau_p map and reserved until the finish has been enqueued. slv (nullable): host copies of X'_t, tau_p and the field

@@ -1,4 +1,4 @@
-// nct_seq.cpp — frame sequences (SPEC §6.3-§6.9, their region mask §6.13 and its tracking §6.14): the state an open sequence keeps in the context's arena, what a level of a frame does between S1 and the finish,
+// nct_seq.cpp — frame sequences (SPEC §6.3-§6.9, their region mask §6.13, its tracking §6.14 and the snap §6.15): the state an open sequence keeps in the context's arena, what a level of a frame does between S1 and the finish,
 // the frame entry points — a full frame is a run of nct_pipeline.cpp's level loop — the propagated frame, the probe and the key-frame decision.
 #include "nct_pipeline.h"
 #include <cstring>
@@ -70,15 +70,16 @@ int seq_field_chain(nct_ctx* ctx, hipStream_t s, seq_state* q, const uint8_t* co
     return NCT_OK;
 }
 
-int seq_track_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, const uint8_t* const* simg) {
+int seq_track_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, const uint8_t* const* simg, const uint8_t* lab_work) {
     if (!P->mask) return NCT_OK;
     if (q->matte_fresh) { q->matte_fresh = false; return NCT_OK; }          // the matte's own frame uses it as it came: age 0
     if (!q->tracking) return NCT_OK;
     q->matte_age += 1;
-    // a zero field (motion off; a first frame, a frame after nct_seq_reset, a CUT frame: no state) leaves the matte where it is
-    if (!q->motion || q->frames == 0) return NCT_OK;
+    // a sequence without state (a first frame, a frame after nct_seq_reset, a CUT frame) has a zero field and nothing to snap to: the matte marks a place in a shot
+    // that is over. With motion off the field is zero too: the matte stays where it is, and only the snap (SPEC §6.15) may re-fit it
+    if (q->frames == 0 || (!q->motion && !q->snap)) return NCT_OK;
     const int top = q->prm.levels - 1;
-    if (simg) {
+    if (q->motion && simg) {
         // a full frame finds its fields here, ahead of its level masks, whether or not it blends; the Lab scratch goes back with this call
         DevBuf<uint8_t> lab[5];
         NCT_TRY(seq_field_chain(ctx, s, q, simg, top, lab));
@@ -86,10 +87,24 @@ int seq_track_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, con
     uint8_t*& matte = q->target() ? P->full_mask : P->mask;
     const int H = q->target() ? q->full.H : P->sh, W = q->target() ? q->full.W : P->sw;
     if (!q->matte_alt && !(q->matte_alt = (uint8_t*)ctx->alloc((size_t)H * W))) return NCT_ERR_HIP;
-    NCT_TRY(nctk_seq_matte_warp(ctx, s, matte, H, W, q->field[top], q->ah[top], q->aw[top], q->matte_alt));
-    std::swap(matte, q->matte_alt);
+    if (q->motion) {
+        NCT_TRY(nctk_seq_matte_warp(ctx, s, matte, H, W, q->field[top], q->ah[top], q->aw[top], q->matte_alt));
+        std::swap(matte, q->matte_alt);
+    }
+    if (q->snap) {
+        // SPEC §6.15 rule 3: the guide is the frame in Lab at the size frames arrive; the block the carry has left takes the snapped matte
+        DevBuf<uint8_t> lab0;
+        const uint8_t* guide = lab_work;
+        if (H != P->sh || W != P->sw) {
+            if (!lab0.alloc(ctx, (size_t)H * W * 3)) return NCT_ERR_HIP;
+            NCT_TRY(nctk_bgr2lab(ctx, s, P->full_src, lab0, (size_t)H * W));
+            guide = lab0;
+        }
+        NCT_TRY(nctk_region_snap(ctx, s, matte, guide, H, W, &q->snap_p, q->matte_alt));
+        std::swap(matte, q->matte_alt);
+    }
     if (q->target()) {
-        // the carry ran at the original size; the working-size matte is its shrink, as nct_seq_set_region makes it
+        // the carry and the snap ran at the original size; the working-size matte is the shrink of their result, as nct_seq_set_region makes it
         q->full.mask = P->full_mask;
         NCT_TRY(nctk_resize_u8c1(ctx, s, P->full_mask, H, W, P->mask, P->sh, P->sw));
     }
@@ -219,6 +234,17 @@ int nct_seq_set_region_tracking(nct_ctx* ctx, int on) {
     if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_set_region_tracking: no sequence is open (nct_seq_begin first)");
     NCT_REQUIRE(on == 0 || on == 1, "seq_set_region_tracking: on must be 0 or 1 (got %d)", on);
     P->seq->tracking = on == 1;
+    return NCT_OK;
+}
+
+// SPEC §6.15 rule 3: from the next frame on a tracked matte is snapped to its frame's edges behind the carry (non-null: with these parameters), or not (null)
+int nct_seq_set_region_snap(nct_ctx* ctx, const nct_region_snap_params* params) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_set_region_snap: no sequence is open (nct_seq_begin first)");
+    NCT_TRY(nct_region_snap_params_check(ctx, "seq_set_region_snap", params));
+    P->seq->snap = params != nullptr;
+    if (params) P->seq->snap_p = *params;
     return NCT_OK;
 }
 
@@ -398,11 +424,11 @@ static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out
         }
     }
     if (P->mask && q->tracking) {
-        // SPEC §6.14: the level loop has left the frame's fields in place; the matte follows the last level run's before the level masks are built. Its time is other_ms
+        // SPEC §6.14: the level loop has left the frame's fields in place; the matte follows the last level run's (and, SPEC §6.15, is snapped to the frame) before the level masks are built. Its time is other_ms
         MARK(NCT_ST_COLOR, top);
-        NCT_TRY(seq_track_step(ctx, s, P, q, nullptr));
+        NCT_TRY(seq_track_step(ctx, s, P, q, nullptr, s_lab_full));
         MARK(NCT_ST_OTHER, 0);
-    } else NCT_TRY(seq_track_step(ctx, s, P, q, nullptr));      // only marks a new matte used
+    } else NCT_TRY(seq_track_step(ctx, s, P, q, nullptr, s_lab_full));      // only marks a new matte used
     // the kept (warped) X' of the last level run finishes on the frame's own pixels: at the working size, or (SPEC §6.9 rule 3) on the original frame
     ctx->tm_level = top;
     int wls_it[6] = {0, 0, 0, 0, 0, 0};

@@ -160,6 +160,10 @@ SIGNATURES = {
     "nct_seq_matte_warp_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "nct_seq_set_region_tracking": (C.c_int, [C.c_void_p, C.c_int]),
     "nct_seq_get_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_region_snap_params_default": (None, [C.c_void_p]),
+    "nct_region_snap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nct_region_snap_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nct_seq_set_region_snap": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nct_seq_frame_propagate_region_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_color_finish_upsample_region": (C.c_int, [C.c_void_p, _f64p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _u8p]),
     "nct_color_finish_upsample_region_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -374,6 +378,28 @@ def _region_params(protect):
     p = RegionParams.default()
     if protect is not None:
         p.protect = int(protect)
+    return p
+
+
+class RegionSnapParams(C.Structure):
+    """struct nct_region_snap_params (include/nct.h)."""
+    _fields_ = [("radius", C.c_int), ("sigma", C.c_int), ("binary", C.c_int)]
+
+    @staticmethod
+    def default():
+        p = RegionSnapParams()
+        lib().nct_region_snap_params_default(C.byref(p))
+        return p
+
+
+def _snap_params(radius, sigma, binary):
+    p = RegionSnapParams.default()
+    if radius is not None:
+        p.radius = int(radius)
+    if sigma is not None:
+        p.sigma = int(sigma)
+    if binary is not None:
+        p.binary = int(binary)
     return p
 
 
@@ -1139,6 +1165,35 @@ class Context:
         age = C.c_int(-1)
         self._chk(self._l.nct_seq_get_region(self._h, out.ctypes.data, C.addressof(age)))
         return out, age.value
+
+    # ---- matte snapping (SPEC §6.15)
+    def region_snap(self, mask, lab, radius=None, sigma=None, binary=None, dev=False, alias=None):
+        """nct_region_snap[_dev] (SPEC §6.15 rule 1): mask [H, W] bytes, lab [H, W, 3] the same frame in 8-bit Lab -> the matte re-fitted to the guide's edges; a
+        parameter left None keeps its default (radius 3, sigma 10, binary 1). dev: on arena blocks, into a block of its own (alias "mask" / "lab": into that input's
+        block, which is an error)"""
+        m, g = np.ascontiguousarray(mask, np.uint8), np.ascontiguousarray(lab, np.uint8)
+        if m.ndim != 2 or g.shape != m.shape + (3,):
+            raise NctError(-2, "region_snap: mask must be [H, W] bytes and lab [H, W, 3] bytes")
+        H, W = m.shape
+        sp = _snap_params(radius, sigma, binary)
+        if not dev:
+            out = np.empty_like(m)
+            self._chk(self._l.nct_region_snap(self._h, m.ctypes.data, g.ctypes.data, H, W, C.addressof(sp), out.ctypes.data))
+            return out
+        ins = [self.dev_upload(m), self.dev_upload(g)]
+        do = self.dev_alloc(m.size)
+        with self._blocks(ins + [do]):
+            self._chk(self._l.nct_region_snap_dev(self._h, ins[0], ins[1], H, W, C.addressof(sp), {None: do, "mask": ins[0], "lab": ins[1]}[alias]))
+            return self.dev_download(do, (H, W), np.uint8)
+
+    def seq_set_region_snap(self, on=True, radius=None, sigma=None, binary=None):
+        """nct_seq_set_region_snap: from the next frame on the open sequence's tracked matte is snapped to its frame's edges behind the carry (on; a parameter left
+        None keeps its default), or not (on false: NULL)"""
+        if not on:
+            self._chk(self._l.nct_seq_set_region_snap(self._h, None))
+            return
+        sp = _snap_params(radius, sigma, binary)
+        self._chk(self._l.nct_seq_set_region_snap(self._h, C.addressof(sp)))
 
     def seq_frame_region_levels(self, src_bgr, want_color=True, want_levels=None):
         """nct_seq_frame_region_levels -> seq_frame_levels' (result, dict) plus per level that ran "ab_mix" (the mixed map the finish read, [2, h*w, 3]) and "mask" (M_l [h, w])"""
