@@ -34,7 +34,8 @@ extern "C" {
  * nct_process_pair_region and nct_lut_fit_masked, and with reference region masks, nct_region_pull[_dev], nct_pair_set_ref_region, nct_multi_run_ref_region_levels and
  * nct_process_*_ref_region, and with region masks in sequences, nct_seq_set_region, nct_seq_frame[_propagate]_region_levels and nct_color_finish_{upsample,guided}_region[_dev], and with region tracking,
  * nct_seq_matte_warp[_dev], nct_seq_set_region_tracking and nct_seq_get_region, and with matte snapping, nct_region_snap[_dev], nct_region_snap_params and
- * nct_seq_set_region_snap).
+ * nct_seq_set_region_snap, and with region selection from strokes, nct_region_select[_dev], nct_feat_quantize[_dev], nct_region_score[_dev], nct_pair_select_region and
+ * nct_seq_select_region).
  * A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
 #define NCT_VERSION 118
@@ -663,6 +664,52 @@ int nct_region_snap(nct_ctx* ctx, const uint8_t* mask /* H*W */, const uint8_t* 
 int nct_region_snap_dev(nct_ctx* ctx, const uint8_t* d_mask, const uint8_t* d_lab, int H, int W, const nct_region_snap_params* params, uint8_t* d_mask_out);
 int nct_seq_set_region_snap(nct_ctx* ctx, const nct_region_snap_params* params);
 
+/* ---- region selection from strokes (SPEC §6.16; an extension): the matte the region calls above take, made from a few marked pixels and the VGG19 features the
+ * correspondence is built on. strokes has one byte per source pixel: NCT_STROKE_IN marks "inside the object", NCT_STROKE_OUT "outside", every other value is unmarked.
+ * nct_region_select[_dev]: src_bgr h x w x 3 (sides in nct_pair_upload's range [17, 4000]), strokes and mask_out h x w. params NULL: the defaults (tap 2, sharpness 1024,
+ * floor_permille 700, max_seeds 4096, snap_iters 1, snap = nct_region_snap_params_default); tap in [1, 5], sharpness in [1, 65536], floor_permille in [0, 1000], max_seeds
+ * in [1, 4096], snap_iters in [0, 8], snap as nct_region_snap takes it.
+ * (1) F = tap `tap` of nct_vgg19_features(src) on its grid h_t x w_t, h_t = ((h - 1) >> (tap - 1)) + 1, with C channels; u = nct_feat_normalize(F).
+ * (2) q(p)[c] = (int16) rint(u(p)[c] * 32767), the product in fp32; a non-finite u (the zero-norm pixel) gives 0. |q| < 32780, so every dot product of two rows and every
+ *     partial sum of it stays below 2^31: int32 sums are exact in any order.
+ * (3) Source pixel (y, x) belongs to cell (y >> (tap - 1), x >> (tap - 1)). A cell with an IN pixel and no OUT pixel is an inside seed, the reverse an outside seed, one
+ *     with both is mixed and no seed. A class with n > max_seeds seeds keeps the seed of raster rank i iff floor((i + 1) max_seeds / n) > floor(i max_seeds / n): exactly max_seeds.
+ * (4) Per cell p: s_in = the largest dot product q(p) . q(s) over the kept inside seeds s, s_out the same over the kept outside seeds, or floor(floor_permille 2^30 / 1000)
+ *     without any; d = s_in - s_out; m(p) = clamp(128 + floor((d sharpness + 2^29) / 2^30), 0, 255) in 64 bits. Then every inside seed cell, kept or not, is 255 and every
+ *     outside seed cell 0.
+ * (5) M = nct_resize_u8c1(m -> h x w); at tap 1 a copy.
+ * (6) The stamp sets IN pixels to 255 and OUT pixels to 0; then snap_iters times M = nct_region_snap(M, nct_bgr2lab_u8(src), snap) and the stamp again.
+ * Integers from (2) on: the result does not depend on any summation order. nct_region_select: host pointers, synchronous; stages (nullable, its arrays nullable) receives
+ * q [cells][C], per cell the code 0 none, 1 inside kept, 2 outside kept, 3 inside not kept, 4 outside not kept, 5 mixed, m on the tap grid and M after (5).
+ * nct_region_select_dev: device pointers, no stages; it waits once, for the two seed counts (the refusal and the launch shapes need them), and returns with the rest
+ * enqueued. All transients come from the arena and go back in stream order; nothing is kept. NCT_ERR_STATE: no weights loaded. NCT_ERR_INVALID with a message naming the
+ * argument: a null pointer, a side or a parameter out of range; and "no inside seed cell" where no cell is an inside seed (an IN stroke that lies only in mixed cells too).
+ * nct_feat_quantize: (2) alone behind N1, CHW fp32 in like nct_feat_normalize, [H*W][C] int16 out; nct_feat_quantize_dev: HWC in. C a positive multiple of 4.
+ * nct_region_score[_dev]: (4) without the seed-cell overwrite. q [cells][C], seeds_in [n_in][C], seeds_out [n_out][C] (nullable with n_out = 0) int16, rows with |row| < 32780
+ * (not checked: a longer row may wrap an int32 sum); cells in [1, 2^24], C a multiple of 4 in [4, 4096], n_in in [1, 65536], n_out in [0, 65536]; score_out [cells] bytes.
+ * The _dev form reads rows in 8-byte units: its three arrays must be 8-byte aligned (arena blocks are).
+ * nct_pair_select_region: after nct_pair_upload / nct_multi_upload, nct_region_select on the uploaded source followed by nct_pair_set_region(matte, region), the matte never
+ * leaving the device; its refusals are those two calls'. nct_seq_select_region: on a sequence opened with nct_seq_begin, nct_region_select on frame_bgr (a frame of the
+ * sequence's size; it is not run) followed by nct_seq_set_region: the matte belongs to the next frame that runs, and tracks and snaps from there. In a full-resolution
+ * sequence: NCT_ERR_STATE with a message (selection at an original size above 4000 is not defined).
+ * THE RULE WAS TRIED WITH SYNTHETIC WEIGHTS ONLY; nobody has measured it with the Oxford weights. */
+#define NCT_STROKE_IN 255
+#define NCT_STROKE_OUT 128
+typedef struct nct_region_select_params { int tap, sharpness, floor_permille, max_seeds, snap_iters; nct_region_snap_params snap; } nct_region_select_params;
+void nct_region_select_params_default(nct_region_select_params* p);     /* 2, 1024, 700, 4096, 1, {3, 10, 1} */
+typedef struct nct_region_select_stages { int16_t* q; uint8_t* cell; uint8_t* score; uint8_t* up; } nct_region_select_stages;   /* [cells][C]; [cells]; [cells]; [h*w]; all nullable */
+int nct_region_select(nct_ctx* ctx, const uint8_t* src_bgr, int h, int w, const uint8_t* strokes, const nct_region_select_params* params, uint8_t* mask_out,
+                      const nct_region_select_stages* stages);
+int nct_region_select_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, int h, int w, const uint8_t* d_strokes, const nct_region_select_params* params, uint8_t* d_mask_out);
+int nct_feat_quantize(nct_ctx* ctx, const float* src_chw, int16_t* dst, int C, int H, int W);
+int nct_feat_quantize_dev(nct_ctx* ctx, const float* d_src_hwc, int16_t* d_dst, int C, int H, int W);
+int nct_region_score(nct_ctx* ctx, const int16_t* q, int cells, int C, const int16_t* seeds_in, int n_in, const int16_t* seeds_out, int n_out, int sharpness, int floor_permille,
+                     uint8_t* score_out);
+int nct_region_score_dev(nct_ctx* ctx, const int16_t* d_q, int cells, int C, const int16_t* d_seeds_in, int n_in, const int16_t* d_seeds_out, int n_out, int sharpness,
+                         int floor_permille, uint8_t* d_score_out);
+int nct_pair_select_region(nct_ctx* ctx, const uint8_t* strokes, const nct_region_select_params* params, const nct_region_params* region);
+int nct_seq_select_region(nct_ctx* ctx, const uint8_t* frame_bgr, const uint8_t* strokes, const nct_region_select_params* params, const nct_region_params* region);
+
 /* ---- device-pointer seams: the same operations on buffers that stay in HBM between calls (main.cu:204-316 keeps Ndata_C1, ann_device, ... on the device
  * across these kernels; an integrator replacing single seams should not pay H2D + D2H + a synchronise per call). Buffers come from the context's arena
  * (nct_dev_alloc / nct_dev_free; any device pointer of the context's GPU works as an operand). Calls are enqueued on the context's stream in call order and return
@@ -715,6 +762,10 @@ int nct_pm_bench_run(nct_ctx* ctx, int iters, int rs_max, uint32_t seed, float* 
  * evaluations, accepted candidates. */
 int nct_pm_bench_run_bidir(nct_ctx* ctx, int iters, int rs_max, uint32_t seed, int pm_mode, float* kernel_ms, uint64_t* counters, uint32_t* ann_out, float* annd_out,
                            uint32_t* bnn_out, float* bnnd_out);
+/* the score kernel of region selection alone (SPEC §6.16 rule 4; scripts/region_select_times.py): nct_region_score_dev's arguments; one warm-up launch, then `reps`
+ * launches (1 … 1000) between two HIP events on the library's own stream; kernel_ms receives the mean device time of one launch. Synchronous. */
+int nct_region_score_bench(nct_ctx* ctx, const int16_t* d_q, int cells, int C, const int16_t* d_seeds_in, int n_in, const int16_t* d_seeds_out, int n_out, int sharpness,
+                           int floor_permille, uint8_t* d_score_out, int reps, float* kernel_ms);
 
 #ifdef __cplusplus
 }

@@ -253,6 +253,21 @@ int nctk_region_snap(nct_ctx* ctx, hipStream_t s, const uint8_t* mask, const uin
 // its argument checks (`who` names the entry point in the message), for the host form to run before it moves anything, and the parameters' alone (null: the defaults)
 int nct_region_snap_check(nct_ctx* ctx, const char* who, const void* mask, const void* lab, int H, int W, const nct_region_snap_params* params, const void* mask_out);
 int nct_region_snap_params_check(nct_ctx* ctx, const char* who, const nct_region_snap_params* params);
+// k_region_select.hip — region selection from strokes (SPEC §6.16). nctk_feat_quantize: rule 2 from the raw HWC tap, N1 (nctk_normalize's bits) and the int16 rows [HW][C].
+// nctk_sel_cells: rule 3's cell flags (bit 0: an IN pixel, bit 1: an OUT pixel; [cells] words, zeroed here) and their exclusive scan pre [cells + 1] — low half the inside
+// seed cells in front of the cell, high half the outside ones, the last word both totals. nctk_sel_seeds: with those totals n_* and the kept counts k_* = min(n_*,
+// max_seeds): the cell codes of nct_region_select_stages.cell, the kept seeds' cells idx [k_in + k_out] (inside first) and their rows of q, seeds [k_in + k_out][C].
+// nctk_region_score: rule 4 — code (nullable): the seed-cell overwrite by those codes. nctk_sel_stamp: rule 6's stamp in place
+int nctk_feat_quantize(nct_ctx* ctx, hipStream_t s, const float* src_hwc, int16_t* dst, int C, int HW);
+int nctk_sel_cells(nct_ctx* ctx, hipStream_t s, const uint8_t* strokes, int h, int w, int tap, unsigned* flags, unsigned long long* pre);
+int nctk_sel_seeds(nct_ctx* ctx, hipStream_t s, const int16_t* q, const unsigned* flags, const unsigned long long* pre, int cells, int C, unsigned n_in, unsigned n_out,
+                   unsigned k_in, unsigned k_out, uint8_t* code, int* idx, int16_t* seeds);
+int nctk_region_score(nct_ctx* ctx, hipStream_t s, const int16_t* q, int cells, int C, const int16_t* seeds_in, int n_in, const int16_t* seeds_out, int n_out, int sharpness,
+                      int floor_permille, const uint8_t* code, uint8_t* score_out);
+// its argument checks (`who` names the entry point in the message), for the host form to run before it moves anything
+int nct_region_score_check(nct_ctx* ctx, const char* who, const void* q, int cells, int C, const void* seeds_in, int n_in, const void* seeds_out, int n_out, int sharpness,
+                           int floor_permille, const void* score_out);
+int nctk_sel_stamp(nct_ctx* ctx, hipStream_t s, const uint8_t* strokes, size_t n, uint8_t* m);
 // k_lut.hip — 3D colour look-up tables (SPEC §6.6). W [N^3] / R [N^3][3]: the splat's integer sums (zeroed on s by the splat itself); D [N^3][3]: the displacement
 // field after NCT_LUT_CYCLES V(2,2) cycles; lut [N^3][3] fp32. in / out of the apply may be the same buffer
 #define NCT_LUT_CYCLES 17

@@ -684,7 +684,8 @@ void nct_region_params_default(nct_region_params* p) {
     p->protect = 0;
 }
 
-int nct_pair_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_params* region) {
+// kind: where `mask` lives — the caller's memory (nct_pair_set_region) or the device (pair_set_region_dev)
+static int pair_set_region_from(nct_ctx* ctx, const uint8_t* mask, const nct_region_params* region, hipMemcpyKind kind) {
     NCT_CTX_ENTER();
     NCT_NO_OPEN_SEQ("pair_set_region");
     pair_state* P = (pair_state*)ctx->pair;
@@ -698,11 +699,12 @@ int nct_pair_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_para
         return NCT_OK;
     }
     if (!P->mask && !(P->mask = (uint8_t*)ctx->alloc((size_t)P->sh * P->sw))) return NCT_ERR_HIP;
-    NCT_H2D(P->mask, mask, (size_t)P->sh * P->sw);
+    NCT_HIP(hipMemcpyAsync(P->mask, mask, (size_t)P->sh * P->sw, kind, ctx->stream));
     NCT_SYNC();
     P->protect = region ? region->protect : 0;
     return NCT_OK;
 }
+int nct_pair_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_params* region) { return pair_set_region_from(ctx, mask, region, hipMemcpyHostToDevice); }
 
 int nct_pair_run_region_levels(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_region_levels* region_levels) {
     run_form f; f.pair = levels; f.region = region_levels;
@@ -887,3 +889,5 @@ int nct_pair_fit_lut(nct_ctx* ctx, const nct_lut_params* prm, float* lut_out) {
 }
 
 }  // extern "C"
+
+int pair_set_region_dev(nct_ctx* ctx, const uint8_t* d_mask, const nct_region_params* region) { return pair_set_region_from(ctx, d_mask, region, hipMemcpyDeviceToDevice); }

@@ -116,7 +116,11 @@ struct NCT_LOCAL full_lab {
 struct region_fin { const uint8_t* mask; const uint8_t* s_bgr; int protect; };
 NCT_LOCAL int finish_level(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int H, int W, const uint8_t* s_lab_full, uint8_t* out_lab, uint8_t* out_bgr,
                            const full_target* full, const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube, const region_fin* region = nullptr);
+// nct_pair_set_region with the mask already on the device (nct_pair_select_region, SPEC §6.16): the same checks, block and state, a device-to-device copy
+NCT_LOCAL int pair_set_region_dev(nct_ctx* ctx, const uint8_t* d_mask, const nct_region_params* region);
 // ---- nct_seq.cpp
+// nct_seq_set_region with the mask already on the device, at the size frames arrive (nct_seq_select_region, SPEC §6.16)
+NCT_LOCAL int seq_set_region_dev(nct_ctx* ctx, const uint8_t* d_mask, const nct_region_params* region);
 NCT_LOCAL void seq_free(nct_ctx* ctx, pair_state* P);       // what an open sequence holds goes back to the arena
 // SPEC §6.4: level l's field from L_t (`lab`) and the kept packed map: the first level run searches radius0 around (0, 0), every other level radius around twice the
 // previous level's vector

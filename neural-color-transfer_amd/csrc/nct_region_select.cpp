@@ -1,0 +1,220 @@
+// nct_region_select.cpp — region selection from strokes (SPEC §6.16): the chain VGG19 forward to the tap -> quantise -> seed cells -> score -> nct_resize_u8c1 -> stamp
+// and snap passes on device pointers, its host and device entry points, the two seams (nct_feat_quantize, nct_region_score) and the two compositions with the region
+// setters of a pair and of a sequence. Kernels: k_region_select.hip. Every transient is an arena block that goes back in stream order; nothing outlives a call.
+#include "nct_pipeline.h"
+#include <algorithm>
+
+void nct_region_select_params_default(nct_region_select_params* p) {
+    if (!p) return;
+    p->tap = 2; p->sharpness = 1024; p->floor_permille = 700; p->max_seeds = 4096; p->snap_iters = 1;
+    nct_region_snap_params_default(&p->snap);
+}
+
+// the arguments of nct_region_select[_dev] and of what is built on it (`who` names the entry point in the message); on success *p holds the parameters in force
+static int select_check(nct_ctx* ctx, const char* who, const void* src_bgr, int h, int w, const void* strokes, const nct_region_select_params* params, const void* mask_out,
+                        nct_region_select_params* p) {
+    NCT_REQUIRE(src_bgr, "%s: null src_bgr", who);
+    NCT_REQUIRE(strokes, "%s: null strokes", who);
+    NCT_REQUIRE(mask_out, "%s: null mask_out", who);
+    NCT_REQUIRE(h >= 17 && h <= 4000, "%s: h must be in [17, 4000] (got %d)", who, h);
+    NCT_REQUIRE(w >= 17 && w <= 4000, "%s: w must be in [17, 4000] (got %d)", who, w);
+    if (params) *p = *params; else nct_region_select_params_default(p);
+    NCT_REQUIRE(p->tap >= 1 && p->tap <= 5, "%s: tap must be in [1, 5] (got %d)", who, p->tap);
+    NCT_REQUIRE(p->sharpness >= 1 && p->sharpness <= 65536, "%s: sharpness must be in [1, 65536] (got %d)", who, p->sharpness);
+    NCT_REQUIRE(p->floor_permille >= 0 && p->floor_permille <= 1000, "%s: floor_permille must be in [0, 1000] (got %d)", who, p->floor_permille);
+    NCT_REQUIRE(p->max_seeds >= 1 && p->max_seeds <= 4096, "%s: max_seeds must be in [1, 4096] (got %d)", who, p->max_seeds);
+    NCT_REQUIRE(p->snap_iters >= 0 && p->snap_iters <= 8, "%s: snap_iters must be in [0, 8] (got %d)", who, p->snap_iters);
+    NCT_TRY(nct_region_snap_params_check(ctx, who, &p->snap));
+    if (nct_vgg19_weights_info(ctx, nullptr, nullptr, nullptr) != NCT_OK)
+        return ctx->fail(NCT_ERR_STATE, "%s: VGG19 weights not loaded (nct_vgg19_load_caffemodel / _load_raw)", who);
+    return NCT_OK;
+}
+
+// SPEC §6.16 rules 1-6 on device pointers, checked arguments. st (nullable): HOST arrays for the stages, each copied and waited for as it is made. The one wait of the
+// plain chain is for the seed counts: the refusal and the launch shapes need them
+static int select_enqueue(nct_ctx* ctx, const char* who, const uint8_t* d_src, int h, int w, const uint8_t* d_strokes, const nct_region_select_params& p, uint8_t* d_out,
+                          const nct_region_select_stages* st) {
+    hipStream_t s = ctx->stream;
+    const int tap = p.tap, C = kTapC[tap - 1], ht = ((h - 1) >> (tap - 1)) + 1, wt = ((w - 1) >> (tap - 1)) + 1, cells = ht * wt;
+    const size_t N = (size_t)h * w;
+    DevBuf<int16_t> q(ctx, (size_t)cells * C);
+    if (!q.ok()) return NCT_ERR_HIP;
+    {
+        // rule 1 and 2: the forward stops at the tap, whose own epilogue writes it channel-last; N1 is fused into the quantise pass
+        DevBuf<float> feat(ctx, (size_t)cells * C);
+        if (!feat.ok()) return NCT_ERR_HIP;
+        float* taps[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        taps[tap - 1] = feat;
+        NCT_TRY(nctk_vgg19_forward(ctx, s, d_src, h, w, 3 * w, tap, nullptr, nullptr, taps));
+        NCT_TRY(nctk_feat_quantize(ctx, s, feat, q, C, cells));
+    }
+    if (st) NCT_TRY(dbg_copy(ctx, s, st->q, q, (size_t)cells * C));
+    // rule 3
+    DevBuf<unsigned> flags(ctx, cells);
+    DevBuf<unsigned long long> pre(ctx, (size_t)cells + 1);
+    if (!flags.ok() || !pre.ok()) return NCT_ERR_HIP;
+    NCT_TRY(nctk_sel_cells(ctx, s, d_strokes, h, w, tap, flags, pre));
+    unsigned long long totals = 0;
+    NCT_HIP(hipMemcpyAsync(&totals, (unsigned long long*)pre + cells, sizeof totals, hipMemcpyDeviceToHost, s));
+    NCT_HIP(hipStreamSynchronize(s));
+    const unsigned n_in = (unsigned)(totals & 0xffffffffull), n_out = (unsigned)(totals >> 32);
+    if (n_in == 0)
+        return ctx->fail(NCT_ERR_INVALID, "%s: no inside seed cell (an inside stroke must cover a cell of the tap grid that holds no outside stroke)", who);
+    const unsigned k_in = std::min(n_in, (unsigned)p.max_seeds), k_out = std::min(n_out, (unsigned)p.max_seeds);
+    DevBuf<uint8_t> code(ctx, cells), m(ctx, cells);
+    DevBuf<int> idx(ctx, k_in + k_out);
+    DevBuf<int16_t> seeds(ctx, (size_t)(k_in + k_out) * C);
+    if (!code.ok() || !m.ok() || !idx.ok() || !seeds.ok()) return NCT_ERR_HIP;
+    NCT_TRY(nctk_sel_seeds(ctx, s, q, flags, pre, cells, C, n_in, n_out, k_in, k_out, code, idx, seeds));
+    if (st) NCT_TRY(dbg_copy(ctx, s, st->cell, code, (size_t)cells));
+    // rule 4
+    NCT_TRY(nctk_region_score(ctx, s, q, cells, C, seeds, (int)k_in, (int16_t*)seeds + (size_t)k_in * C, (int)k_out, p.sharpness, p.floor_permille, code, m));
+    if (st) NCT_TRY(dbg_copy(ctx, s, st->score, m, (size_t)cells));
+    // rules 5 and 6: every snap pass runs out of place between d_out and one block of scratch; the first matte goes where the last pass ends in d_out
+    DevBuf<uint8_t> alt, lab;
+    if (p.snap_iters > 0) {
+        if (!alt.alloc(ctx, N) || !lab.alloc(ctx, N * 3)) return NCT_ERR_HIP;
+        NCT_TRY(nctk_bgr2lab(ctx, s, d_src, lab, N));
+    }
+    uint8_t *cur = (p.snap_iters & 1) ? (uint8_t*)alt : d_out, *oth = (p.snap_iters & 1) ? d_out : (uint8_t*)alt;
+    NCT_TRY(nctk_resize_u8c1(ctx, s, m, ht, wt, cur, h, w));
+    if (st) NCT_TRY(dbg_copy(ctx, s, st->up, cur, N));
+    NCT_TRY(nctk_sel_stamp(ctx, s, d_strokes, N, cur));
+    for (int it = 0; it < p.snap_iters; ++it) {
+        NCT_TRY(nctk_region_snap(ctx, s, cur, lab, h, w, &p.snap, oth));
+        std::swap(cur, oth);
+        NCT_TRY(nctk_sel_stamp(ctx, s, d_strokes, N, cur));
+    }
+    return NCT_OK;
+}
+
+extern "C" {
+
+int nct_region_select_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, int h, int w, const uint8_t* d_strokes, const nct_region_select_params* params, uint8_t* d_mask_out) {
+    NCT_CTX_ENTER();
+    nct_region_select_params p;
+    NCT_TRY(select_check(ctx, "region_select_dev", d_src_bgr, h, w, d_strokes, params, d_mask_out, &p));
+    return select_enqueue(ctx, "region_select_dev", d_src_bgr, h, w, d_strokes, p, d_mask_out, nullptr);
+}
+
+int nct_region_select(nct_ctx* ctx, const uint8_t* src_bgr, int h, int w, const uint8_t* strokes, const nct_region_select_params* params, uint8_t* mask_out,
+                      const nct_region_select_stages* stages) {
+    NCT_CTX_ENTER();
+    nct_region_select_params p;
+    NCT_TRY(select_check(ctx, "region_select", src_bgr, h, w, strokes, params, mask_out, &p));
+    const size_t N = (size_t)h * w;
+    DevBuf<uint8_t> ds(ctx, N * 3), dt(ctx, N), dm(ctx, N);
+    if (!ds.ok() || !dt.ok() || !dm.ok()) return NCT_ERR_HIP;
+    NCT_H2D(ds, src_bgr, N * 3); NCT_H2D(dt, strokes, N);
+    NCT_TRY(select_enqueue(ctx, "region_select", ds, h, w, dt, p, dm, stages));
+    NCT_D2H(mask_out, dm, N);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
+// rule 2 alone on a host blob in Caffe's layout: up, to channel-last, one k_feat_quantize launch, the rows down
+int nct_feat_quantize(nct_ctx* ctx, const float* src_chw, int16_t* dst, int C, int H, int W) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(src_chw, "feat_quantize: null src_chw");
+    NCT_REQUIRE(dst, "feat_quantize: null dst");
+    NCT_REQUIRE(C > 0 && (C & 3) == 0 && C <= 4096, "feat_quantize: C must be a positive multiple of 4, at most 4096 (got %d)", C);
+    NCT_REQUIRE(H >= 1 && W >= 1 && H <= 4096 && W <= 4096, "feat_quantize: grid %dx%d out of range", W, H);
+    const int HW = H * W; const size_t n = (size_t)C * HW;
+    DevBuf<float> t(ctx, n), x(ctx, n);
+    DevBuf<int16_t> y(ctx, n);
+    if (!t.ok() || !x.ok() || !y.ok()) return NCT_ERR_HIP;
+    NCT_H2D(t, src_chw, sizeof(float) * n);
+    NCT_TRY(nctk_chw_to_hwc(ctx, ctx->stream, t, x, C, HW));
+    NCT_TRY(nctk_feat_quantize(ctx, ctx->stream, x, y, C, HW));
+    NCT_D2H(dst, y, sizeof(int16_t) * n);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
+int nct_feat_quantize_dev(nct_ctx* ctx, const float* d_src_hwc, int16_t* d_dst, int C, int H, int W) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(d_src_hwc, "feat_quantize_dev: null d_src_hwc");
+    NCT_REQUIRE(d_dst, "feat_quantize_dev: null d_dst");
+    NCT_REQUIRE(C > 0 && (C & 3) == 0 && C <= 4096, "feat_quantize_dev: C must be a positive multiple of 4, at most 4096 (got %d)", C);
+    NCT_REQUIRE(H >= 1 && W >= 1 && H <= 4096 && W <= 4096, "feat_quantize_dev: grid %dx%d out of range", W, H);
+    return nctk_feat_quantize(ctx, ctx->stream, d_src_hwc, d_dst, C, H * W);
+}
+
+// rule 4 alone on host rows: the queries and the two seed lists up, one k_region_score launch, the bytes down
+int nct_region_score(nct_ctx* ctx, const int16_t* q, int cells, int C, const int16_t* seeds_in, int n_in, const int16_t* seeds_out, int n_out, int sharpness, int floor_permille,
+                     uint8_t* score_out) {
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_region_score_check(ctx, "region_score", q, cells, C, seeds_in, n_in, seeds_out, n_out, sharpness, floor_permille, score_out));
+    DevBuf<int16_t> dq(ctx, (size_t)cells * C), di(ctx, (size_t)n_in * C), dn(ctx, (size_t)n_out * C);
+    DevBuf<uint8_t> dm(ctx, cells);
+    if (!dq.ok() || !di.ok() || !dn.ok() || !dm.ok()) return NCT_ERR_HIP;
+    NCT_H2D(dq, q, sizeof(int16_t) * (size_t)cells * C);
+    NCT_H2D(di, seeds_in, sizeof(int16_t) * (size_t)n_in * C);
+    if (n_out > 0) NCT_H2D(dn, seeds_out, sizeof(int16_t) * (size_t)n_out * C);
+    NCT_TRY(nctk_region_score(ctx, ctx->stream, dq, cells, C, di, n_in, dn, n_out, sharpness, floor_permille, nullptr, dm));
+    NCT_D2H(score_out, dm, (size_t)cells);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
+int nct_region_score_dev(nct_ctx* ctx, const int16_t* d_q, int cells, int C, const int16_t* d_seeds_in, int n_in, const int16_t* d_seeds_out, int n_out, int sharpness,
+                         int floor_permille, uint8_t* d_score_out) {
+    NCT_CTX_ENTER();
+    return nctk_region_score(ctx, ctx->stream, d_q, cells, C, d_seeds_in, n_in, d_seeds_out, n_out, sharpness, floor_permille, nullptr, d_score_out);
+}
+
+// measurement hook: the mean device time of one k_region_score launch, between two events on the library's stream
+int nct_region_score_bench(nct_ctx* ctx, const int16_t* d_q, int cells, int C, const int16_t* d_seeds_in, int n_in, const int16_t* d_seeds_out, int n_out, int sharpness,
+                           int floor_permille, uint8_t* d_score_out, int reps, float* kernel_ms) {
+    NCT_CTX_ENTER();
+    NCT_REQUIRE(kernel_ms, "region_score_bench: null kernel_ms");
+    NCT_REQUIRE(reps >= 1 && reps <= 1000, "region_score_bench: reps must be in [1, 1000] (got %d)", reps);
+    NCT_TRY(nctk_region_score(ctx, ctx->stream, d_q, cells, C, d_seeds_in, n_in, d_seeds_out, n_out, sharpness, floor_permille, nullptr, d_score_out));   // warm-up
+    NCT_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    for (int r = 0; r < reps; ++r)
+        NCT_TRY(nctk_region_score(ctx, ctx->stream, d_q, cells, C, d_seeds_in, n_in, d_seeds_out, n_out, sharpness, floor_permille, nullptr, d_score_out));
+    NCT_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    NCT_HIP(hipEventSynchronize(ctx->ev1));
+    float ms = 0.f;
+    NCT_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    *kernel_ms = ms / reps;
+    return NCT_OK;
+}
+
+// nct_region_select on the uploaded source, then nct_pair_set_region with the matte where it is: the strokes go up, nothing comes down
+int nct_pair_select_region(nct_ctx* ctx, const uint8_t* strokes, const nct_region_select_params* params, const nct_region_params* region) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (P && P->seq) return ctx->fail(NCT_ERR_STATE, "pair_select_region: a sequence is open on this context (nct_seq_end closes it)");
+    if (!P || !P->src || P->sh < 1) return ctx->fail(NCT_ERR_STATE, "pair_select_region: no source uploaded (nct_pair_upload or nct_multi_upload first)");
+    NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "pair_select_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
+    const size_t N = (size_t)P->sh * P->sw;
+    DevBuf<uint8_t> dt(ctx, N), dm(ctx, N);
+    if (!dt.ok() || !dm.ok()) return NCT_ERR_HIP;
+    nct_region_select_params p;
+    NCT_TRY(select_check(ctx, "pair_select_region", P->src, P->sh, P->sw, strokes, params, (uint8_t*)dm, &p));
+    NCT_H2D(dt, strokes, N);
+    NCT_TRY(select_enqueue(ctx, "pair_select_region", P->src, P->sh, P->sw, dt, p, dm, nullptr));
+    return pair_set_region_dev(ctx, dm, region);             // waits for the copy: dm may go back
+}
+
+// nct_region_select on a frame of the open sequence's size, then nct_seq_set_region with the matte where it is
+int nct_seq_select_region(nct_ctx* ctx, const uint8_t* frame_bgr, const uint8_t* strokes, const nct_region_select_params* params, const nct_region_params* region) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_select_region: no sequence is open (nct_seq_begin first)");
+    if (P->seq->target())
+        return ctx->fail(NCT_ERR_STATE, "seq_select_region: not defined in a full-resolution sequence (select on the frame with nct_region_select, then nct_seq_set_region)");
+    NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "seq_select_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
+    NCT_REQUIRE(frame_bgr, "seq_select_region: null frame_bgr");
+    const size_t N = (size_t)P->sh * P->sw;
+    DevBuf<uint8_t> ds(ctx, N * 3), dt(ctx, N), dm(ctx, N);
+    if (!ds.ok() || !dt.ok() || !dm.ok()) return NCT_ERR_HIP;
+    nct_region_select_params p;
+    NCT_TRY(select_check(ctx, "seq_select_region", frame_bgr, P->sh, P->sw, strokes, params, (uint8_t*)dm, &p));
+    NCT_H2D(ds, frame_bgr, N * 3); NCT_H2D(dt, strokes, N);
+    NCT_TRY(select_enqueue(ctx, "seq_select_region", ds, P->sh, P->sw, dt, p, dm, nullptr));
+    return seq_set_region_dev(ctx, dm, region);
+}
+
+}  // extern "C"

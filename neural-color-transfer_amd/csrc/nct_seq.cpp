@@ -185,23 +185,24 @@ static void seq_mask_drop(nct_ctx* ctx, pair_state* P, seq_state* q) {
 }
 
 // the mask of nct_seq_set_region onto the device, into blocks the sequence keeps until the mask is removed: at the size it came, and (a full-resolution sequence) shrunk
-static int seq_mask_upload(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* mask) {
+static int seq_mask_upload(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* mask, hipMemcpyKind kind) {
     const size_t n = (size_t)P->sh * P->sw;
     if (!P->mask && !(P->mask = (uint8_t*)ctx->alloc(n))) return NCT_ERR_HIP;
     if (q->target()) {
         const size_t n0 = (size_t)q->full.H * q->full.W;
         if (!P->full_mask && !(P->full_mask = (uint8_t*)ctx->alloc(n0))) return NCT_ERR_HIP;
-        NCT_H2D(P->full_mask, mask, n0);
+        NCT_HIP(hipMemcpyAsync(P->full_mask, mask, n0, kind, ctx->stream));
         NCT_TRY(nctk_resize_u8c1(ctx, ctx->stream, P->full_mask, q->full.H, q->full.W, P->mask, P->sh, P->sw));
         q->full.mask = P->full_mask;
-    } else NCT_H2D(P->mask, mask, n);
+    } else NCT_HIP(hipMemcpyAsync(P->mask, mask, n, kind, ctx->stream));
     NCT_SYNC();
     return NCT_OK;
 }
 
 // SPEC §6.13 rule 1: the open sequence's region mask, sticky from the next frame on. It arrives at the size frames arrive; a full-resolution sequence keeps it at that
 // size (the exact and the upsampling finish compose with it, nct_pair_fit_lut reads it) and shrinks it on the device to the working size. NULL removes it
-int nct_seq_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_params* region) {
+// kind: where `mask` lives — the caller's memory (nct_seq_set_region) or the device (seq_set_region_dev)
+static int seq_set_region_from(nct_ctx* ctx, const uint8_t* mask, const nct_region_params* region, hipMemcpyKind kind) {
     NCT_CTX_ENTER();
     pair_state* P = (pair_state*)ctx->pair;
     if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_set_region: no sequence is open (nct_seq_begin first)");
@@ -214,7 +215,7 @@ int nct_seq_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_param
         seq_mask_drop(ctx, P, q);
         return NCT_OK;
     }
-    const int rc = seq_mask_upload(ctx, P, q, mask);
+    const int rc = seq_mask_upload(ctx, P, q, mask, kind);
     if (rc) {
         // a device error half way: no mask is better than a block of unknown bytes
         (void)hipStreamSynchronize(ctx->stream);
@@ -226,6 +227,7 @@ int nct_seq_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_param
     q->matte_fresh = true; q->matte_age = 0;
     return NCT_OK;
 }
+int nct_seq_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_params* region) { return seq_set_region_from(ctx, mask, region, hipMemcpyHostToDevice); }
 
 // SPEC §6.14 rule 2: from the next frame on the matte in force follows the motion field (1), or stays where it is as a sticky §6.13 matte (0)
 int nct_seq_set_region_tracking(nct_ctx* ctx, int on) {
@@ -587,3 +589,5 @@ int nct_seq_frame_auto(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, n
 }
 
 }  // extern "C"
+
+int seq_set_region_dev(nct_ctx* ctx, const uint8_t* d_mask, const nct_region_params* region) { return seq_set_region_from(ctx, d_mask, region, hipMemcpyDeviceToDevice); }

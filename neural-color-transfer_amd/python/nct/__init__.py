@@ -164,6 +164,17 @@ SIGNATURES = {
     "nct_region_snap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nct_region_snap_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nct_seq_set_region_snap": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "nct_region_select_params_default": (None, [C.c_void_p]),
+    "nct_region_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_region_select_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_feat_quantize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "nct_feat_quantize_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "nct_region_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "nct_region_score_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "nct_region_score_bench": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                         C.POINTER(C.c_float)]),
+    "nct_pair_select_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_select_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_propagate_region_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_color_finish_upsample_region": (C.c_int, [C.c_void_p, _f64p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _u8p]),
     "nct_color_finish_upsample_region_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -400,6 +411,37 @@ def _snap_params(radius, sigma, binary):
         p.sigma = int(sigma)
     if binary is not None:
         p.binary = int(binary)
+    return p
+
+
+STROKE_IN, STROKE_OUT = 255, 128                          # nct.h NCT_STROKE_*
+
+
+class RegionSelectParams(C.Structure):
+    """struct nct_region_select_params (include/nct.h)."""
+    _fields_ = [("tap", C.c_int), ("sharpness", C.c_int), ("floor_permille", C.c_int), ("max_seeds", C.c_int), ("snap_iters", C.c_int), ("snap", RegionSnapParams)]
+
+    @staticmethod
+    def default():
+        p = RegionSelectParams()
+        lib().nct_region_select_params_default(C.byref(p))
+        return p
+
+
+class RegionSelectStages(C.Structure):
+    """struct nct_region_select_stages (include/nct.h)."""
+    _fields_ = [("q", C.c_void_p), ("cell", C.c_void_p), ("score", C.c_void_p), ("up", C.c_void_p)]
+
+
+def region_select_params(tap=None, sharpness=None, floor_permille=None, max_seeds=None, snap_iters=None, radius=None, sigma=None, binary=None):
+    """struct nct_region_select_params with nct_region_select_params_default's values (2, 1024, 700, 4096, 1, snap 3 / 10 / 1) where an argument is left out"""
+    p = RegionSelectParams.default()
+    for k, v in (("tap", tap), ("sharpness", sharpness), ("floor_permille", floor_permille), ("max_seeds", max_seeds), ("snap_iters", snap_iters)):
+        if v is not None:
+            setattr(p, k, int(v))
+    for k, v in (("radius", radius), ("sigma", sigma), ("binary", binary)):
+        if v is not None:
+            setattr(p.snap, k, int(v))
     return p
 
 
@@ -1194,6 +1236,81 @@ class Context:
             return
         sp = _snap_params(radius, sigma, binary)
         self._chk(self._l.nct_seq_set_region_snap(self._h, C.addressof(sp)))
+
+    # ---- region selection from strokes (SPEC §6.16)
+    def region_select(self, src_bgr, strokes, params=None, want_stages=False, dev=False):
+        """nct_region_select[_dev] (SPEC §6.16): src_bgr [h, w, 3], strokes [h, w] bytes (STROKE_IN inside, STROKE_OUT outside, else unmarked) -> the matte [h, w];
+        params: region_select_params(...) or None for the defaults. want_stages (host form only): -> (matte, {"q" [cells, C] int16, "cell", "score" [h_t, w_t], "up" [h, w]})"""
+        s, t = np.ascontiguousarray(src_bgr, np.uint8), np.ascontiguousarray(strokes, np.uint8)
+        if s.ndim != 3 or s.shape[2] != 3 or t.shape != s.shape[:2]:
+            raise NctError(-2, "region_select: src_bgr must be [h, w, 3] bytes and strokes [h, w] bytes")
+        h, w = t.shape
+        pp = C.addressof(params) if params is not None else None
+        if dev:
+            ins = [self.dev_upload(s), self.dev_upload(t)]
+            do = self.dev_alloc(t.size)
+            with self._blocks(ins + [do]):
+                self._chk(self._l.nct_region_select_dev(self._h, ins[0], h, w, ins[1], pp, do))
+                return self.dev_download(do, (h, w), np.uint8)
+        out = np.empty((h, w), np.uint8)
+        if not want_stages:
+            self._chk(self._l.nct_region_select(self._h, s.ctypes.data, h, w, t.ctypes.data, pp, out.ctypes.data, None))
+            return out
+        tap = params.tap if params is not None else RegionSelectParams.default().tap
+        if not 1 <= tap <= 5:                                  # the library refuses; the stage arrays are never written
+            tap = 1
+        ht, wt = ((h - 1) >> (tap - 1)) + 1, ((w - 1) >> (tap - 1)) + 1
+        st = {"q": np.zeros((ht * wt, self.TAP_C[tap - 1]), np.int16), "cell": np.zeros((ht, wt), np.uint8), "score": np.zeros((ht, wt), np.uint8),
+              "up": np.zeros((h, w), np.uint8)}
+        cs = RegionSelectStages(*[st[k].ctypes.data for k in ("q", "cell", "score", "up")])
+        self._chk(self._l.nct_region_select(self._h, s.ctypes.data, h, w, t.ctypes.data, pp, out.ctypes.data, C.addressof(cs)))
+        return out, st
+
+    def feat_quantize(self, src_chw, dev=False):
+        """nct_feat_quantize[_dev] (SPEC §6.16 rule 2): CHW fp32 features -> [H*W, C] int16 rows rint(N1(F) * 32767); dev: through the channel-last device form"""
+        src = np.ascontiguousarray(src_chw, np.float32)
+        Cc, H, W = src.shape
+        if not dev:
+            out = np.empty((H * W, Cc), np.int16)
+            self._chk(self._l.nct_feat_quantize(self._h, src.ctypes.data, out.ctypes.data, Cc, H, W))
+            return out
+        ins = [self.dev_upload(np.ascontiguousarray(src.reshape(Cc, H * W).T))]
+        do = self.dev_alloc(2 * src.size)
+        with self._blocks(ins + [do]):
+            self._chk(self._l.nct_feat_quantize_dev(self._h, ins[0], do, Cc, H, W))
+            return self.dev_download(do, (H * W, Cc), np.int16)
+
+    def region_score(self, q, seeds_in, seeds_out=None, sharpness=1024, floor_permille=700, dev=False):
+        """nct_region_score[_dev] (SPEC §6.16 rule 4 without the seed-cell overwrite): q [cells, C], seeds_in [n_in, C], seeds_out [n_out, C] or None, int16 -> [cells] bytes"""
+        qq, si = np.ascontiguousarray(q, np.int16), np.ascontiguousarray(seeds_in, np.int16)
+        so = None if seeds_out is None or len(seeds_out) == 0 else np.ascontiguousarray(seeds_out, np.int16)
+        cells, Cc = qq.shape
+        n_in, n_out = si.shape[0], 0 if so is None else so.shape[0]
+        if not dev:
+            out = np.empty(cells, np.uint8)
+            self._chk(self._l.nct_region_score(self._h, qq.ctypes.data, cells, Cc, si.ctypes.data, n_in, None if so is None else so.ctypes.data, n_out, int(sharpness),
+                                               int(floor_permille), out.ctypes.data))
+            return out
+        ins = [self.dev_upload(qq), self.dev_upload(si)] + ([] if so is None else [self.dev_upload(so)])
+        do = self.dev_alloc(cells)
+        with self._blocks(ins + [do]):
+            self._chk(self._l.nct_region_score_dev(self._h, ins[0], cells, Cc, ins[1], n_in, None if so is None else ins[2], n_out, int(sharpness), int(floor_permille), do))
+            return self.dev_download(do, (cells,), np.uint8)
+
+    def pair_select_region(self, strokes, params=None, protect=None):
+        """nct_pair_select_region: region_select on the uploaded source, then pair_set_region with the matte, which stays on the device"""
+        t = _mask_arg(strokes, self._pair_shape, "pair_select_region")
+        rg = _region_params(protect)
+        self._chk(self._l.nct_pair_select_region(self._h, t.ctypes.data, C.addressof(params) if params is not None else None, C.addressof(rg)))
+
+    def seq_select_region(self, frame_bgr, strokes, params=None, protect=None):
+        """nct_seq_select_region on the open sequence: region_select on frame_bgr (a frame of the sequence's size), then seq_set_region with the matte"""
+        f, t = np.ascontiguousarray(frame_bgr, np.uint8), np.ascontiguousarray(strokes, np.uint8)
+        shp = getattr(self, "_seq_shapes", None)
+        if shp is not None and (tuple(f.shape[:2]) != tuple(shp[0]) or t.shape != tuple(shp[0])):
+            raise NctError(-2, "seq_select_region: the frame and the strokes must have the size the sequence was begun for")
+        rg = _region_params(protect)
+        self._chk(self._l.nct_seq_select_region(self._h, f.ctypes.data, t.ctypes.data, C.addressof(params) if params is not None else None, C.addressof(rg)))
 
     def seq_frame_region_levels(self, src_bgr, want_color=True, want_levels=None):
         """nct_seq_frame_region_levels -> seq_frame_levels' (result, dict) plus per level that ran "ab_mix" (the mixed map the finish read, [2, h*w, 3]) and "mask" (M_l [h, w])"""
