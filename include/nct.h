@@ -35,7 +35,7 @@ extern "C" {
  * nct_process_*_ref_region, and with region masks in sequences, nct_seq_set_region, nct_seq_frame[_propagate]_region_levels and nct_color_finish_{upsample,guided}_region[_dev], and with region tracking,
  * nct_seq_matte_warp[_dev], nct_seq_set_region_tracking and nct_seq_get_region, and with matte snapping, nct_region_snap[_dev], nct_region_snap_params and
  * nct_seq_set_region_snap, and with region selection from strokes, nct_region_select[_dev], nct_feat_quantize[_dev], nct_region_score[_dev], nct_pair_select_region and
- * nct_seq_select_region).
+ * nct_seq_select_region, and with region models, nct_region_model_*, nct_region_refind[_dev], nct_pair_apply_region_model and nct_seq_set_region_model).
  * A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
 #define NCT_VERSION 118
@@ -710,6 +710,66 @@ int nct_region_score_dev(nct_ctx* ctx, const int16_t* d_q, int cells, int C, con
 int nct_pair_select_region(nct_ctx* ctx, const uint8_t* strokes, const nct_region_select_params* params, const nct_region_params* region);
 int nct_seq_select_region(nct_ctx* ctx, const uint8_t* frame_bgr, const uint8_t* strokes, const nct_region_select_params* params, const nct_region_params* region);
 
+/* ---- region models (SPEC §6.17; an extension): what a selection from strokes learnt — the kept seed rows of §6.16 rule 3 — held so that the object is found again on
+ * another image, or on every full frame of a shot, without new strokes. nct_region_model is a host object without a context, like nct_model: the tap, C, the kept inside
+ * rows [n_in][C] and the kept outside rows [n_out][C] as int16, in the raster order of §6.16 rule 3, image after image.
+ * nct_region_model_fit: §6.16 rules (1) to (3) on src_bgr and strokes; the kept rows become a new model. Of the params only tap and max_seeds act; the limits and
+ * refusals are nct_region_select's, "no inside seed cell" included. nct_region_model_add: the same on another image, its kept rows appended behind the model's; a tap
+ * other than the model's, or a class that would exceed 65536 rows (nct_region_score's limit), is NCT_ERR_INVALID; a refused call leaves the model unchanged.
+ * nct_region_model_info: tap, C, n_in, n_out (each nullable). nct_region_model_rows: host pointers to the rows (rows_out NULL without outside rows), valid until the next
+ * nct_region_model_add or nct_region_model_free. nct_region_model_from_rows: a model from rows the caller holds (a saved model, rows made by another program); needs no
+ * context; tap in [1, 5], C the tap's channel count (64, 128, 256, 512, 512), n_in in [1, 65536], n_out in [0, 65536]; rows are copied. The three calls without a
+ * context report a refusal through nct_last_error(NULL).
+ * nct_region_refind[_dev]: the re-find step alone. score: ht x wt bytes on the tap grid; prior: H x W bytes or NULL; out: H x W bytes.
+ * (R1) r = nct_resize_u8c1(score: ht x wt -> H x W); equal sizes give the byte itself; the target is never smaller than the grid.
+ * (R2) confident(p) = r(p) >= 128 + margin or r(p) < 128 - margin, in integers, margin in [0, 128].
+ * (R3) out(p) = (prior == NULL or confident(p)) ? r(p) : prior(p).
+ * margin 0 or a NULL prior give nct_resize_u8c1's bytes, margin 128 the prior; a byte is r's or the prior's, never a mix. 1 <= ht <= H <= 16384, 1 <= wt <= W <= 16384,
+ * ht, wt <= 4096, H * W <= 2^26; anything else is NCT_ERR_INVALID, the message names the argument. One kernel, no intermediate of the target's size. The _dev form is
+ * enqueued on the context's stream and refuses an out that overlaps score or prior.
+ * nct_region_model_apply[_dev]: src_bgr h x w x 3 (sides in [17, 4000]), prior h x w or NULL, mask_out h x w. params NULL: the defaults (sharpness 1024, floor_permille
+ * 700, margin 32, snap_iters 1, snap = nct_region_snap_params_default); the ranges are §6.16's and (R2)'s.
+ * (A1) q = §6.16 rules (1) and (2) on the image at the model's tap. (A2) m = nct_region_score(q, rows_in, rows_out, sharpness, floor_permille): no cell of this image is
+ * a seed cell, nothing is overwritten. (A3) M = refind(m, prior, margin) at h x w. (A4) snap_iters times M = nct_region_snap(M, nct_bgr2lab_u8(src), snap); no stamp.
+ * stages (nullable, its arrays nullable; host form only) receives q [cells][C], m on the tap grid and M after (A3). NCT_ERR_STATE: no weights loaded. The _dev form
+ * waits once, for the model's rows to be on the device (the model may be changed or freed on return), and returns with the rest enqueued; it refuses a mask_out that
+ * overlaps src_bgr or prior. All transients come from the arena and go back in stream order; nothing is kept.
+ * nct_pair_apply_region_model: after nct_pair_upload / nct_multi_upload, nct_region_model_apply without a prior on the uploaded source followed by
+ * nct_pair_set_region(matte, region), the matte never leaving the device; its refusals are those two calls'.
+ * nct_seq_set_region_model: on an open sequence, between frames, a full-resolution sequence included; the model's rows are copied to the device once and held until
+ * the model is replaced, removed (model NULL), nct_seq_end or nct_destroy — the model itself may be freed on return. params and region as above (region: the protect of
+ * the re-found matte); bad parameters are NCT_ERR_INVALID and leave the setting as it was; no open sequence is NCT_ERR_STATE. While a model is set:
+ * (S1) a frame that is a fresh matte's own frame (§6.14) uses that matte as it came: no re-find. (S2) Every other full frame — nct_seq_frame* and the FIRST, KEY and CUT
+ *      frames of nct_seq_frame_auto — re-finds at the working size: q comes from the model's tap of the frame's own forward, which also stores that tap channel-last;
+ *      there is no second forward. (S3) The prior is the matte that §6.14 and §6.15 leave for this frame, at the size frames arrive; none where the sequence has no state
+ *      (a first frame, a frame after nct_seq_reset, a CUT frame: the old shot's matte is not evidence) or no matte is set. (S4) M_t = refind(m, prior, margin) straight
+ *      from the working-size tap grid to the size frames arrive — the original size in a full-resolution sequence —, then (A4)'s snap passes with the frame's Lab image
+ *      at that size; a full-resolution sequence then shrinks M_t with nct_resize_u8c1, as nct_seq_set_region does. (S5) From there the frame is §6.13's: its bytes and
+ *      kept state are those of the same sequence with nct_seq_set_region(M_t, region) called before it; nct_seq_get_region returns M_t; a matte the re-find made where
+ *      none was set has age 0 on that frame, else the age counts as in §6.14; the re-find's time counts in other_ms. (S6) Propagated frames run no forward and do not
+ *      re-find: they carry and snap as before. nct_seq_probe's record and the decisions of nct_seq_frame_auto do not depend on the model. A frame that fails leaves the
+ *      sequence reset and the model set. Never set: every sequence path is what it was.
+ * WHERE THE SCORE ALONE FAILS (an object whose appearance changed) A CARRIED MATTE AS THE PRIOR IS THE REMEDY, AND A LAGGING PRIOR COSTS ACCURACY AS THE MARGIN GROWS;
+ * margin 32 balanced the two on one synthetic fixture WITH SYNTHETIC WEIGHTS. Nobody has measured the rule with the Oxford weights. */
+typedef struct nct_region_model nct_region_model;
+typedef struct nct_region_refind_params { int sharpness, floor_permille, margin, snap_iters; nct_region_snap_params snap; } nct_region_refind_params;
+void nct_region_refind_params_default(nct_region_refind_params* p);     /* 1024, 700, 32, 1, {3, 10, 1} */
+typedef struct nct_region_apply_stages { int16_t* q; uint8_t* score; uint8_t* refound; } nct_region_apply_stages;   /* [cells][C]; [cells]; [h*w]; all nullable */
+int nct_region_model_fit(nct_ctx* ctx, const uint8_t* src_bgr, int h, int w, const uint8_t* strokes, const nct_region_select_params* params, nct_region_model** model);
+int nct_region_model_add(nct_ctx* ctx, nct_region_model* model, const uint8_t* src_bgr, int h, int w, const uint8_t* strokes, const nct_region_select_params* params);
+int nct_region_model_info(const nct_region_model* model, int* tap, int* C, int* n_in, int* n_out);
+int nct_region_model_rows(const nct_region_model* model, const int16_t** rows_in, const int16_t** rows_out);
+int nct_region_model_from_rows(int tap, int C, const int16_t* rows_in, int n_in, const int16_t* rows_out, int n_out, nct_region_model** model);
+void nct_region_model_free(nct_region_model* model);
+int nct_region_refind(nct_ctx* ctx, const uint8_t* score, int ht, int wt, const uint8_t* prior /* H*W, nullable */, int H, int W, int margin, uint8_t* out /* H*W */);
+int nct_region_refind_dev(nct_ctx* ctx, const uint8_t* d_score, int ht, int wt, const uint8_t* d_prior, int H, int W, int margin, uint8_t* d_out);
+int nct_region_model_apply(nct_ctx* ctx, const nct_region_model* model, const uint8_t* src_bgr, int h, int w, const uint8_t* prior /* h*w, nullable */,
+                           const nct_region_refind_params* params, uint8_t* mask_out, const nct_region_apply_stages* stages);
+int nct_region_model_apply_dev(nct_ctx* ctx, const nct_region_model* model, const uint8_t* d_src_bgr, int h, int w, const uint8_t* d_prior, const nct_region_refind_params* params,
+                               uint8_t* d_mask_out);
+int nct_pair_apply_region_model(nct_ctx* ctx, const nct_region_model* model, const nct_region_refind_params* params, const nct_region_params* region);
+int nct_seq_set_region_model(nct_ctx* ctx, const nct_region_model* model, const nct_region_refind_params* params, const nct_region_params* region);
+
 /* ---- device-pointer seams: the same operations on buffers that stay in HBM between calls (main.cu:204-316 keeps Ndata_C1, ann_device, ... on the device
  * across these kernels; an integrator replacing single seams should not pay H2D + D2H + a synchronise per call). Buffers come from the context's arena
  * (nct_dev_alloc / nct_dev_free; any device pointer of the context's GPU works as an operand). Calls are enqueued on the context's stream in call order and return
@@ -766,6 +826,9 @@ int nct_pm_bench_run_bidir(nct_ctx* ctx, int iters, int rs_max, uint32_t seed, i
  * launches (1 … 1000) between two HIP events on the library's own stream; kernel_ms receives the mean device time of one launch. Synchronous. */
 int nct_region_score_bench(nct_ctx* ctx, const int16_t* d_q, int cells, int C, const int16_t* d_seeds_in, int n_in, const int16_t* d_seeds_out, int n_out, int sharpness,
                            int floor_permille, uint8_t* d_score_out, int reps, float* kernel_ms);
+/* the re-find kernel alone (SPEC §6.17 rules R1-R3; scripts/region_refind_times.py): nct_region_refind_dev's arguments; one warm-up launch, then `reps` launches
+ * (1 … 1000) between two HIP events on the library's own stream; kernel_ms receives the mean device time of one launch. Synchronous. */
+int nct_region_refind_bench(nct_ctx* ctx, const uint8_t* d_score, int ht, int wt, const uint8_t* d_prior, int H, int W, int margin, uint8_t* d_out, int reps, float* kernel_ms);
 
 #ifdef __cplusplus
 }

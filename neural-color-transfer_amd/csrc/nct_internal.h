@@ -268,6 +268,11 @@ int nctk_region_score(nct_ctx* ctx, hipStream_t s, const int16_t* q, int cells, 
 int nct_region_score_check(nct_ctx* ctx, const char* who, const void* q, int cells, int C, const void* seeds_in, int n_in, const void* seeds_out, int n_out, int sharpness,
                            int floor_permille, const void* score_out);
 int nctk_sel_stamp(nct_ctx* ctx, hipStream_t s, const uint8_t* strokes, size_t n, uint8_t* m);
+// k_region_refind.hip — SPEC §6.17 rules R1-R3 in one pass: out(p) = r(p) = nct_resize_u8c1(score: ht x wt -> H x W)(p) where prior is null or r(p) >= 128 + margin or
+// r(p) < 128 - margin, else prior(p) (H x W bytes); H >= ht, W >= wt; out must overlap neither input
+int nctk_region_refind(nct_ctx* ctx, hipStream_t s, const uint8_t* score, int ht, int wt, const uint8_t* prior, int H, int W, int margin, uint8_t* out);
+// its argument checks (`who` names the entry point in the message), for the host form to run before it moves anything
+int nct_region_refind_check(nct_ctx* ctx, const char* who, const void* score, int ht, int wt, int H, int W, int margin, const void* out);
 // k_lut.hip — 3D colour look-up tables (SPEC §6.6). W [N^3] / R [N^3][3]: the splat's integer sums (zeroed on s by the splat itself); D [N^3][3]: the displacement
 // field after NCT_LUT_CYCLES V(2,2) cycles; lut [N^3][3] fp32. in / out of the apply may be the same buffer
 #define NCT_LUT_CYCLES 17

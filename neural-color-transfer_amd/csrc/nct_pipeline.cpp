@@ -175,6 +175,10 @@ struct pair_run {
     const uint8_t* mask;                           // a tracked frame of a sequence (SPEC §6.14) carries the matte first: lab_and_pyramids reads the pointer again
     DevBuf<uint8_t> mpyr[4]; const uint8_t* mimg[5] = {};
     const bool ref_masked;
+    // SPEC §6.17: this full frame of a sequence with a region model re-finds its matte behind the forward (not the own frame of a fresh matte: rule S1). tapfeat: the
+    // model's tap of that forward, channel-last, where it is not conv5_1 itself. The level masks are then built behind the re-find: nothing reads them before level 0's mix
+    const bool refind;
+    DevBuf<float> tapfeat;
     DevBuf<uint8_t> p_merged, m_level, f_level;
     const uint8_t *p_l = nullptr, *m_l = nullptr, *f_l = nullptr;
     const nct_color_params cp;
@@ -182,7 +186,7 @@ struct pair_run {
     pair_run(nct_ctx* c, const nct_params* p, nct_pair_timing* t, const run_extras& x)
         : ctx(c), prm(p), timing(t), lv(x.lv ? x.lv : &kNoLevels), color(x.color), fin(x.fin), seq(x.seq), slv(x.slv), qlv(x.qlv), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
           nlevels(p->levels), N((size_t)H * W), feat16((p->flags & NCT_FLAG_FEAT16) != 0), count(t && (p->flags & NCT_FLAG_COUNT_EVALS)), side(c), mask(P->mask),
-          ref_masked(!x.seq && P->ref_masked()), cp(nct_color_params_of(*p)) {}
+          ref_masked(!x.seq && P->ref_masked()), refind(x.seq && x.seq->model_rows && !(P->mask && x.seq->matte_fresh)), cp(nct_color_params_of(*p)) {}
 
     int d2h(void* dst, const void* src, size_t bytes) {
         if (dst) NCT_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
@@ -202,6 +206,27 @@ struct pair_run {
         }
     }
 
+    // SPEC §6.11 rule 1: the level masks, each resized from the level above like the image pyramid
+    int source_level_masks() {
+        mimg[4] = mask;
+        for (int l = 3; l >= 0; --l) {
+            if (!mpyr[l].alloc(ctx, (size_t)ah[l] * aw[l])) return NCT_ERR_HIP;
+            NCT_TRY(nctk_resize_u8c1(ctx, s, mimg[l + 1], ah[l + 1], aw[l + 1], mpyr[l], ah[l], aw[l]));
+            mimg[l] = mpyr[l];
+        }
+        return NCT_OK;
+    }
+
+    // SPEC §6.17 rules S2-S5: the frame's matte from the tap its own forward has just written, then the level masks of that matte. Its time counts as other_ms
+    int refind_masks() {
+        NCT_TRY(seq_refind_step(ctx, s, P, seq, tapfeat.ok() ? (const float*)tapfeat : (const float*)sfeat, s_lab_full));
+        if (tapfeat.ok()) ctx->release(tapfeat.detach());
+        mask = P->mask;
+        NCT_TRY(source_level_masks());
+        MARK(NCT_ST_OTHER, 0);
+        return NCT_OK;
+    }
+
     // S in Lab (ColorTransfer ctor, ColorTransfer.h:54-75) and image pyramids (main.cu:104-108)
     int lab_and_pyramids() {
         if (!s_lab_full.alloc(ctx, N * 3)) return NCT_ERR_HIP;
@@ -215,15 +240,7 @@ struct pair_run {
         }
         // SPEC §6.14: a tracked sequence's matte follows the frame's field before its level masks are built; the two matte blocks may have changed places
         if (seq && mask) { NCT_TRY(seq_track_step(ctx, s, P, seq, simg, s_lab_full)); mask = P->mask; }
-        if (mask) {
-            // SPEC §6.11 rule 1: the level masks, each resized from the level above like the image pyramid
-            mimg[4] = mask;
-            for (int l = 3; l >= 0; --l) {
-                if (!mpyr[l].alloc(ctx, (size_t)ah[l] * aw[l])) return NCT_ERR_HIP;
-                NCT_TRY(nctk_resize_u8c1(ctx, s, mimg[l + 1], ah[l + 1], aw[l + 1], mpyr[l], ah[l], aw[l]));
-                mimg[l] = mpyr[l];
-            }
-        }
+        if (mask && !refind) NCT_TRY(source_level_masks());
         for (int k = 0; k < K && ref_masked; ++k) {
             // SPEC §6.12 rule 1: the masked references' level masks, on the reference's level grids
             if (!P->rmask[k]) continue;
@@ -246,6 +263,12 @@ struct pair_run {
             // bytes are those of the paired launch
             for (int l = 0; l < 5; ++l) R[0].featp[l] = seq->rfeat[l];
             float* staps_hwc[5] = {nullptr, nullptr, nullptr, nullptr, sfeat};
+            if (refind && seq->model_tap < 5) {
+                // SPEC §6.17 rule S2: the forward also stores the model's tap channel-last; no second forward
+                const int t = seq->model_tap - 1;
+                if (!tapfeat.alloc(ctx, (size_t)kTapC[t] * ah[4 - t] * aw[4 - t])) return NCT_ERR_HIP;
+                staps_hwc[t] = tapfeat;
+            }
             NCT_TRY(nctk_vgg19_forward(ctx, s, P->src, H, W, W * 3, 5, nullptr, nullptr, staps_hwc));
             MARK(NCT_ST_VGG, 0);
             return NCT_OK;
@@ -507,6 +530,7 @@ struct pair_run {
         geometry();
         NCT_TRY(lab_and_pyramids());
         NCT_TRY(forwards());
+        if (refind) NCT_TRY(refind_masks());
         NCT_TRY(cluster());
         NCT_TRY(level_buffers());
         for (int l = 0; l < nlevels; ++l) {

@@ -36,6 +36,10 @@ struct seq_state {
     long matte_age = 0;                                        // frames run since the matte's own frame while tracking was on
     uint8_t* matte_alt = nullptr;
     bool snap = false; nct_region_snap_params snap_p = {0, 0, 0};  // SPEC §6.15: snap the carried matte to the frame's edges with these parameters
+    // SPEC §6.17 (nct_seq_set_region_model): the model's rows on the device, [model_n_in + model_n_out][model_C], inside first, held until the model is replaced or removed
+    // or the sequence ends; null: no model. model_p: the parameters of the re-find, model_protect: nct_region_params.protect of the re-found matte
+    int16_t* model_rows = nullptr; int model_tap = 0, model_C = 0, model_n_in = 0, model_n_out = 0;
+    nct_region_refind_params model_p = {0, 0, 0, 0, {0, 0, 0}}; int model_protect = 0;
     full_target full;
     const full_target* target() const { return full.H ? &full : nullptr; }
 };
@@ -118,6 +122,17 @@ NCT_LOCAL int finish_level(nct_ctx* ctx, hipStream_t s, const double* x, int h, 
                            const full_target* full, const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube, const region_fin* region = nullptr);
 // nct_pair_set_region with the mask already on the device (nct_pair_select_region, SPEC §6.16): the same checks, block and state, a device-to-device copy
 NCT_LOCAL int pair_set_region_dev(nct_ctx* ctx, const uint8_t* d_mask, const nct_region_params* region);
+// ---- nct_region_select.cpp, shared with the region models of nct_region_model.cpp (SPEC §6.17)
+// the argument checks of nct_region_select[_dev] (`who` names the entry point in the message); on success *p holds the parameters in force
+NCT_LOCAL int select_check(nct_ctx* ctx, const char* who, const void* src_bgr, int h, int w, const void* strokes, const nct_region_select_params* params, const void* mask_out,
+                           nct_region_select_params* p);
+// SPEC §6.16 rules 1 and 2 on a device image: the quantised rows of tap `tap`, [cells][C], into the caller's q
+NCT_LOCAL int select_quantised_tap(nct_ctx* ctx, hipStream_t s, const uint8_t* d_src, int h, int w, int tap, int16_t* q);
+// what rules 1-3 leave on the device, in the order the blocks are requested: the rows, rule 3's flags and scan, the cell codes, rule 4's scores (requested only where
+// the caller runs rule 4), the kept seeds' cells and their rows [k_in + k_out][C], inside first
+struct select_rows { DevBuf<int16_t> q; DevBuf<unsigned> flags; DevBuf<unsigned long long> pre; DevBuf<uint8_t> code, m; DevBuf<int> idx; DevBuf<int16_t> seeds; unsigned k_in = 0, k_out = 0; };
+NCT_LOCAL int select_seed_rows(nct_ctx* ctx, const char* who, const uint8_t* d_src, int h, int w, const uint8_t* d_strokes, const nct_region_select_params& p,
+                               const nct_region_select_stages* st, bool with_m, select_rows& r);
 // ---- nct_seq.cpp
 // nct_seq_set_region with the mask already on the device, at the size frames arrive (nct_seq_select_region, SPEC §6.16)
 NCT_LOCAL int seq_set_region_dev(nct_ctx* ctx, const uint8_t* d_mask, const nct_region_params* region);
@@ -135,6 +150,12 @@ NCT_LOCAL int seq_field_chain(nct_ctx* ctx, hipStream_t s, seq_state* q, const u
 // not, to the frame's Lab image at the size frames arrive: lab_work, the working-size frame in Lab that the caller holds, or — a full-resolution sequence whose
 // frames are larger — the original frame converted into scratch of this call
 NCT_LOCAL int seq_track_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, const uint8_t* const* simg, const uint8_t* lab_work);
+// ---- nct_region_model.cpp
+// SPEC §6.17 rules S2-S5, behind a full frame's forward and in front of its level masks: the frame's matte re-found from tap_hwc — the model's tap of that forward,
+// un-normalised and channel-last on the working-size grid — with the matte the track step left as the prior (none without a matte or without state), straight to the size
+// frames arrive, then the model's snap passes with the frame's Lab image at that size (lab_work, or the original frame converted into scratch) and, in a
+// full-resolution sequence, the shrink to the working-size matte. A sequence without a matte gets its matte blocks here
+NCT_LOCAL int seq_refind_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, const float* tap_hwc, const uint8_t* lab_work);
 // A level of a sequence frame (SPEC §6.3), between S1 and the finish: X'_t = the blend of S1's output x with X'_(t-1), into the kept state q->keep_x[l], which the finish
 // then reads; L_t (`lab`) replaces L_(t-1). The first frame and tau == 0 only keep the state, with no blend launch. tmap: the caller's, requested here where slv asks
 // for the tau_p map and reserved until the finish has been enqueued. slv (nullable): host copies of X'_t, tau_p and the field

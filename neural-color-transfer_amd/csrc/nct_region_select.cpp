@@ -11,8 +11,8 @@ void nct_region_select_params_default(nct_region_select_params* p) {
 }
 
 // the arguments of nct_region_select[_dev] and of what is built on it (`who` names the entry point in the message); on success *p holds the parameters in force
-static int select_check(nct_ctx* ctx, const char* who, const void* src_bgr, int h, int w, const void* strokes, const nct_region_select_params* params, const void* mask_out,
-                        nct_region_select_params* p) {
+int select_check(nct_ctx* ctx, const char* who, const void* src_bgr, int h, int w, const void* strokes, const nct_region_select_params* params, const void* mask_out,
+                 nct_region_select_params* p) {
     NCT_REQUIRE(src_bgr, "%s: null src_bgr", who);
     NCT_REQUIRE(strokes, "%s: null strokes", who);
     NCT_REQUIRE(mask_out, "%s: null mask_out", who);
@@ -30,45 +30,56 @@ static int select_check(nct_ctx* ctx, const char* who, const void* src_bgr, int 
     return NCT_OK;
 }
 
-// SPEC §6.16 rules 1-6 on device pointers, checked arguments. st (nullable): HOST arrays for the stages, each copied and waited for as it is made. The one wait of the
-// plain chain is for the seed counts: the refusal and the launch shapes need them
+// SPEC §6.16 rules 1-3 on device pointers, checked arguments: the quantised rows of the tap into r.q, the cell codes into r.code and the kept seeds' rows (inside first)
+// into r.seeds. st (nullable): HOST arrays for the stages, each copied and waited for as it is made. The one wait of the plain chain is for the seed counts: the refusal
+// and the launch shapes need them. with_m: rule 4's block is requested in its place between the codes and the seeds' cells
+int select_seed_rows(nct_ctx* ctx, const char* who, const uint8_t* d_src, int h, int w, const uint8_t* d_strokes, const nct_region_select_params& p,
+                     const nct_region_select_stages* st, bool with_m, select_rows& r) {
+    hipStream_t s = ctx->stream;
+    const int tap = p.tap, C = kTapC[tap - 1], ht = ((h - 1) >> (tap - 1)) + 1, wt = ((w - 1) >> (tap - 1)) + 1, cells = ht * wt;
+    if (!r.q.alloc(ctx, (size_t)cells * C)) return NCT_ERR_HIP;
+    NCT_TRY(select_quantised_tap(ctx, s, d_src, h, w, tap, r.q));
+    if (st) NCT_TRY(dbg_copy(ctx, s, st->q, r.q, (size_t)cells * C));
+    // rule 3
+    if (!r.flags.alloc(ctx, cells) || !r.pre.alloc(ctx, (size_t)cells + 1)) return NCT_ERR_HIP;
+    NCT_TRY(nctk_sel_cells(ctx, s, d_strokes, h, w, tap, r.flags, r.pre));
+    unsigned long long totals = 0;
+    NCT_HIP(hipMemcpyAsync(&totals, (unsigned long long*)r.pre + cells, sizeof totals, hipMemcpyDeviceToHost, s));
+    NCT_HIP(hipStreamSynchronize(s));
+    const unsigned n_in = (unsigned)(totals & 0xffffffffull), n_out = (unsigned)(totals >> 32);
+    if (n_in == 0)
+        return ctx->fail(NCT_ERR_INVALID, "%s: no inside seed cell (an inside stroke must cover a cell of the tap grid that holds no outside stroke)", who);
+    r.k_in = std::min(n_in, (unsigned)p.max_seeds); r.k_out = std::min(n_out, (unsigned)p.max_seeds);
+    if (!r.code.alloc(ctx, cells) || (with_m && !r.m.alloc(ctx, cells)) || !r.idx.alloc(ctx, r.k_in + r.k_out) || !r.seeds.alloc(ctx, (size_t)(r.k_in + r.k_out) * C))
+        return NCT_ERR_HIP;
+    NCT_TRY(nctk_sel_seeds(ctx, s, r.q, r.flags, r.pre, cells, C, n_in, n_out, r.k_in, r.k_out, r.code, r.idx, r.seeds));
+    if (st) NCT_TRY(dbg_copy(ctx, s, st->cell, r.code, (size_t)cells));
+    return NCT_OK;
+}
+
+// rules 1 and 2: the forward stops at the tap, whose own epilogue writes it channel-last; N1 is fused into the quantise pass. q: [cells][C], the caller's
+int select_quantised_tap(nct_ctx* ctx, hipStream_t s, const uint8_t* d_src, int h, int w, int tap, int16_t* q) {
+    const int C = kTapC[tap - 1], cells = (((h - 1) >> (tap - 1)) + 1) * (((w - 1) >> (tap - 1)) + 1);
+    DevBuf<float> feat(ctx, (size_t)cells * C);
+    if (!feat.ok()) return NCT_ERR_HIP;
+    float* taps[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    taps[tap - 1] = feat;
+    NCT_TRY(nctk_vgg19_forward(ctx, s, d_src, h, w, 3 * w, tap, nullptr, nullptr, taps));
+    return nctk_feat_quantize(ctx, s, feat, q, C, cells);
+}
+
+// SPEC §6.16 rules 1-6 on device pointers, checked arguments
 static int select_enqueue(nct_ctx* ctx, const char* who, const uint8_t* d_src, int h, int w, const uint8_t* d_strokes, const nct_region_select_params& p, uint8_t* d_out,
                           const nct_region_select_stages* st) {
     hipStream_t s = ctx->stream;
     const int tap = p.tap, C = kTapC[tap - 1], ht = ((h - 1) >> (tap - 1)) + 1, wt = ((w - 1) >> (tap - 1)) + 1, cells = ht * wt;
     const size_t N = (size_t)h * w;
-    DevBuf<int16_t> q(ctx, (size_t)cells * C);
-    if (!q.ok()) return NCT_ERR_HIP;
-    {
-        // rule 1 and 2: the forward stops at the tap, whose own epilogue writes it channel-last; N1 is fused into the quantise pass
-        DevBuf<float> feat(ctx, (size_t)cells * C);
-        if (!feat.ok()) return NCT_ERR_HIP;
-        float* taps[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        taps[tap - 1] = feat;
-        NCT_TRY(nctk_vgg19_forward(ctx, s, d_src, h, w, 3 * w, tap, nullptr, nullptr, taps));
-        NCT_TRY(nctk_feat_quantize(ctx, s, feat, q, C, cells));
-    }
-    if (st) NCT_TRY(dbg_copy(ctx, s, st->q, q, (size_t)cells * C));
-    // rule 3
-    DevBuf<unsigned> flags(ctx, cells);
-    DevBuf<unsigned long long> pre(ctx, (size_t)cells + 1);
-    if (!flags.ok() || !pre.ok()) return NCT_ERR_HIP;
-    NCT_TRY(nctk_sel_cells(ctx, s, d_strokes, h, w, tap, flags, pre));
-    unsigned long long totals = 0;
-    NCT_HIP(hipMemcpyAsync(&totals, (unsigned long long*)pre + cells, sizeof totals, hipMemcpyDeviceToHost, s));
-    NCT_HIP(hipStreamSynchronize(s));
-    const unsigned n_in = (unsigned)(totals & 0xffffffffull), n_out = (unsigned)(totals >> 32);
-    if (n_in == 0)
-        return ctx->fail(NCT_ERR_INVALID, "%s: no inside seed cell (an inside stroke must cover a cell of the tap grid that holds no outside stroke)", who);
-    const unsigned k_in = std::min(n_in, (unsigned)p.max_seeds), k_out = std::min(n_out, (unsigned)p.max_seeds);
-    DevBuf<uint8_t> code(ctx, cells), m(ctx, cells);
-    DevBuf<int> idx(ctx, k_in + k_out);
-    DevBuf<int16_t> seeds(ctx, (size_t)(k_in + k_out) * C);
-    if (!code.ok() || !m.ok() || !idx.ok() || !seeds.ok()) return NCT_ERR_HIP;
-    NCT_TRY(nctk_sel_seeds(ctx, s, q, flags, pre, cells, C, n_in, n_out, k_in, k_out, code, idx, seeds));
-    if (st) NCT_TRY(dbg_copy(ctx, s, st->cell, code, (size_t)cells));
+    select_rows r;
+    NCT_TRY(select_seed_rows(ctx, who, d_src, h, w, d_strokes, p, st, true, r));
+    const unsigned k_in = r.k_in, k_out = r.k_out;
+    int16_t* const q = r.q; int16_t* const seeds = r.seeds; uint8_t* const code = r.code; uint8_t* const m = r.m;
     // rule 4
-    NCT_TRY(nctk_region_score(ctx, s, q, cells, C, seeds, (int)k_in, (int16_t*)seeds + (size_t)k_in * C, (int)k_out, p.sharpness, p.floor_permille, code, m));
+    NCT_TRY(nctk_region_score(ctx, s, q, cells, C, seeds, (int)k_in, seeds + (size_t)k_in * C, (int)k_out, p.sharpness, p.floor_permille, code, m));
     if (st) NCT_TRY(dbg_copy(ctx, s, st->score, m, (size_t)cells));
     // rules 5 and 6: every snap pass runs out of place between d_out and one block of scratch; the first matte goes where the last pass ends in d_out
     DevBuf<uint8_t> alt, lab;

@@ -28,6 +28,7 @@ void seq_free(nct_ctx* ctx, pair_state* P) {
     if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
     if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
     if (q->matte_alt) { ctx->release(q->matte_alt); q->matte_alt = nullptr; }
+    if (q->model_rows) { ctx->release(q->model_rows); q->model_rows = nullptr; }     // the region model's rows (SPEC §6.17)
     P->protect = 0;
     delete q; P->seq = nullptr;
 }
@@ -369,7 +370,7 @@ int nct_seq_frame_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* o
     if (levels) { x.lv = &m; x.color = levels->color; }
     nct_ref_region_levels qlv;
     if (region_levels) { qlv = ref_region_levels_of(*region_levels); x.qlv = &qlv; }
-    if (region_levels && !P->mask) x.refusal = "seq_frame: region levels asked for, but no region mask is set (nct_seq_set_region first)";
+    if (region_levels && !P->mask && !q->model_rows) x.refusal = "seq_frame: region levels asked for, but no region mask is set (nct_seq_set_region first)";
     if (rc == NCT_OK) rc = process_resident(ctx, &q->prm, timing, x);
     // a frame that failed may have replaced the state of some levels only: the next frame starts over
     q->gap = 0; q->acc = 0;                                      // a full frame (and a failed one: the next is a first frame) starts the count over

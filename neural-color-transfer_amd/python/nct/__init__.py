@@ -175,6 +175,20 @@ SIGNATURES = {
                                          C.POINTER(C.c_float)]),
     "nct_pair_select_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_select_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_region_refind_params_default": (None, [C.c_void_p]),
+    "nct_region_model_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "nct_region_model_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nct_region_model_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nct_region_model_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "nct_region_model_from_rows": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "nct_region_model_free": (None, [C.c_void_p]),
+    "nct_region_refind": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "nct_region_refind_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "nct_region_refind_bench": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "nct_region_model_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_region_model_apply_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_pair_apply_region_model": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_set_region_model": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_propagate_region_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_color_finish_upsample_region": (C.c_int, [C.c_void_p, _f64p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _u8p]),
     "nct_color_finish_upsample_region_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -443,6 +457,82 @@ def region_select_params(tap=None, sharpness=None, floor_permille=None, max_seed
         if v is not None:
             setattr(p.snap, k, int(v))
     return p
+
+
+class RegionRefindParams(C.Structure):
+    """struct nct_region_refind_params (include/nct.h)."""
+    _fields_ = [("sharpness", C.c_int), ("floor_permille", C.c_int), ("margin", C.c_int), ("snap_iters", C.c_int), ("snap", RegionSnapParams)]
+
+    @staticmethod
+    def default():
+        p = RegionRefindParams()
+        lib().nct_region_refind_params_default(C.byref(p))
+        return p
+
+
+class RegionApplyStages(C.Structure):
+    """struct nct_region_apply_stages (include/nct.h)."""
+    _fields_ = [("q", C.c_void_p), ("score", C.c_void_p), ("refound", C.c_void_p)]
+
+
+def region_refind_params(sharpness=None, floor_permille=None, margin=None, snap_iters=None, radius=None, sigma=None, binary=None):
+    """struct nct_region_refind_params with nct_region_refind_params_default's values (1024, 700, 32, 1, snap 3 / 10 / 1) where an argument is left out"""
+    p = RegionRefindParams.default()
+    for k, v in (("sharpness", sharpness), ("floor_permille", floor_permille), ("margin", margin), ("snap_iters", snap_iters)):
+        if v is not None:
+            setattr(p, k, int(v))
+    for k, v in (("radius", radius), ("sigma", sigma), ("binary", binary)):
+        if v is not None:
+            setattr(p.snap, k, int(v))
+    return p
+
+
+class RegionModel:
+    """nct_region_model (SPEC §6.17): the kept seed rows of a selection from strokes, a host object without a context. Made by Context.region_model_fit or from rows
+    the caller holds (rows_in [n_in, C], rows_out [n_out, C] or None, int16: nct_region_model_from_rows)."""
+
+    def __init__(self, tap=None, rows_in=None, rows_out=None, _handle=None):
+        self._m = None
+        if _handle is not None:
+            self._m = _handle
+            return
+        ri = np.ascontiguousarray(rows_in, np.int16)
+        ro = None if rows_out is None or len(rows_out) == 0 else np.ascontiguousarray(rows_out, np.int16)
+        if ri.ndim != 2 or (ro is not None and (ro.ndim != 2 or ro.shape[1] != ri.shape[1])):
+            raise NctError(-2, "RegionModel: rows_in must be [n_in, C] int16 and rows_out [n_out, C] or None")
+        m = C.c_void_p()
+        rc = lib().nct_region_model_from_rows(int(tap), ri.shape[1], ri.ctypes.data, ri.shape[0], None if ro is None else ro.ctypes.data, 0 if ro is None else ro.shape[0], C.byref(m))
+        if rc != 0:
+            raise NctError(rc, (lib().nct_last_error(None) or b"").decode())
+        self._m = m
+
+    def info(self):
+        """nct_region_model_info -> (tap, C, n_in, n_out)"""
+        v = [C.c_int() for _ in range(4)]
+        rc = lib().nct_region_model_info(self._m, *[C.byref(x) for x in v])
+        if rc != 0:
+            raise NctError(rc, (lib().nct_last_error(None) or b"").decode())
+        return tuple(x.value for x in v)
+
+    def rows(self):
+        """nct_region_model_rows -> (rows_in [n_in, C], rows_out [n_out, C]) as numpy copies"""
+        _, Cc, n_in, n_out = self.info()
+        a, b = C.c_void_p(), C.c_void_p()
+        rc = lib().nct_region_model_rows(self._m, C.byref(a), C.byref(b))
+        if rc != 0:
+            raise NctError(rc, (lib().nct_last_error(None) or b"").decode())
+        def arr(ptr, n):
+            if n == 0:
+                return np.zeros((0, Cc), np.int16)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_int16)), (n, Cc)).copy()
+        return arr(a, n_in), arr(b, n_out)
+
+    def close(self):
+        if self._m:
+            lib().nct_region_model_free(self._m); self._m = None
+
+    def __del__(self):
+        self.close()
 
 
 def _mask_arg(mask, shape, what):
@@ -1311,6 +1401,84 @@ class Context:
             raise NctError(-2, "seq_select_region: the frame and the strokes must have the size the sequence was begun for")
         rg = _region_params(protect)
         self._chk(self._l.nct_seq_select_region(self._h, f.ctypes.data, t.ctypes.data, C.addressof(params) if params is not None else None, C.addressof(rg)))
+
+    # ---- region models (SPEC §6.17)
+    def region_model_fit(self, src_bgr, strokes, params=None):
+        """nct_region_model_fit: §6.16 rules 1 to 3 on src_bgr [h, w, 3] and strokes [h, w] -> a RegionModel of the kept seed rows (of params only tap and max_seeds act)"""
+        s, t = np.ascontiguousarray(src_bgr, np.uint8), np.ascontiguousarray(strokes, np.uint8)
+        if s.ndim != 3 or s.shape[2] != 3 or t.shape != s.shape[:2]:
+            raise NctError(-2, "region_model_fit: src_bgr must be [h, w, 3] bytes and strokes [h, w] bytes")
+        m = C.c_void_p()
+        self._chk(self._l.nct_region_model_fit(self._h, s.ctypes.data, t.shape[0], t.shape[1], t.ctypes.data, C.addressof(params) if params is not None else None, C.byref(m)))
+        return RegionModel(_handle=m)
+
+    def region_model_add(self, model, src_bgr, strokes, params=None):
+        """nct_region_model_add: another image's kept seed rows appended to the model"""
+        s, t = np.ascontiguousarray(src_bgr, np.uint8), np.ascontiguousarray(strokes, np.uint8)
+        if s.ndim != 3 or s.shape[2] != 3 or t.shape != s.shape[:2]:
+            raise NctError(-2, "region_model_add: src_bgr must be [h, w, 3] bytes and strokes [h, w] bytes")
+        self._chk(self._l.nct_region_model_add(self._h, model._m, s.ctypes.data, t.shape[0], t.shape[1], t.ctypes.data, C.addressof(params) if params is not None else None))
+
+    def region_refind(self, score, shape, prior=None, margin=32, dev=False, alias=None):
+        """nct_region_refind[_dev] (SPEC §6.17 rules R1 to R3): score [ht, wt] bytes on the tap grid, shape (H, W), prior [H, W] bytes or None -> the matte [H, W].
+        dev: on arena blocks, into a block of its own (alias "score" / "prior": into that input's block, which is an error)"""
+        m = np.ascontiguousarray(score, np.uint8)
+        pr = None if prior is None else np.ascontiguousarray(prior, np.uint8)
+        H, W = int(shape[0]), int(shape[1])
+        if m.ndim != 2 or (pr is not None and pr.shape != (H, W)):
+            raise NctError(-2, "region_refind: score must be [ht, wt] bytes and prior [H, W] bytes or None")
+        ht, wt = m.shape
+        if not dev:
+            out = np.empty((max(H, 1), max(W, 1)), np.uint8)
+            self._chk(self._l.nct_region_refind(self._h, m.ctypes.data, ht, wt, None if pr is None else pr.ctypes.data, H, W, int(margin), out.ctypes.data))
+            return out
+        ins = [self.dev_upload(m)] + ([] if pr is None else [self.dev_upload(pr)])
+        do = self.dev_alloc(max(H * W, max(m.size, 1)))
+        with self._blocks(ins + [do]):
+            dst = {None: do, "score": ins[0], "prior": ins[-1]}[alias]
+            self._chk(self._l.nct_region_refind_dev(self._h, ins[0], ht, wt, None if pr is None else ins[1], H, W, int(margin), dst))
+            return self.dev_download(do, (H, W), np.uint8)
+
+    def region_model_apply(self, model, src_bgr, prior=None, params=None, want_stages=False, dev=False):
+        """nct_region_model_apply[_dev] (SPEC §6.17 rules A1 to A4): the model's object re-found on src_bgr [h, w, 3] -> the matte [h, w]; prior [h, w] bytes or None;
+        params: region_refind_params(...) or None for the defaults. want_stages (host form only): -> (matte, {"q" [cells, C] int16, "score" [h_t, w_t], "refound" [h, w]})"""
+        s = np.ascontiguousarray(src_bgr, np.uint8)
+        pr = None if prior is None else np.ascontiguousarray(prior, np.uint8)
+        if s.ndim != 3 or s.shape[2] != 3 or (pr is not None and pr.shape != s.shape[:2]):
+            raise NctError(-2, "region_model_apply: src_bgr must be [h, w, 3] bytes and prior [h, w] bytes or None")
+        h, w = s.shape[:2]
+        pp = C.addressof(params) if params is not None else None
+        if dev:
+            ins = [self.dev_upload(s)] + ([] if pr is None else [self.dev_upload(pr)])
+            do = self.dev_alloc(h * w)
+            with self._blocks(ins + [do]):
+                self._chk(self._l.nct_region_model_apply_dev(self._h, model._m, ins[0], h, w, None if pr is None else ins[1], pp, do))
+                return self.dev_download(do, (h, w), np.uint8)
+        out = np.empty((h, w), np.uint8)
+        prp = None if pr is None else pr.ctypes.data
+        if not want_stages:
+            self._chk(self._l.nct_region_model_apply(self._h, model._m, s.ctypes.data, h, w, prp, pp, out.ctypes.data, None))
+            return out
+        tap, Cc, _, _ = model.info()
+        ht, wt = ((h - 1) >> (tap - 1)) + 1, ((w - 1) >> (tap - 1)) + 1
+        st = {"q": np.zeros((ht * wt, Cc), np.int16), "score": np.zeros((ht, wt), np.uint8), "refound": np.zeros((h, w), np.uint8)}
+        cs = RegionApplyStages(*[st[k].ctypes.data for k in ("q", "score", "refound")])
+        self._chk(self._l.nct_region_model_apply(self._h, model._m, s.ctypes.data, h, w, prp, pp, out.ctypes.data, C.addressof(cs)))
+        return out, st
+
+    def pair_apply_region_model(self, model, params=None, protect=None):
+        """nct_pair_apply_region_model: region_model_apply without a prior on the uploaded source, then pair_set_region with the matte, which stays on the device"""
+        rg = _region_params(protect)
+        self._chk(self._l.nct_pair_apply_region_model(self._h, model._m, C.addressof(params) if params is not None else None, C.addressof(rg)))
+
+    def seq_set_region_model(self, model, params=None, protect=None):
+        """nct_seq_set_region_model on the open sequence (SPEC §6.17 rules S1 to S6): from the next full frame on the model's object is re-found on every full frame,
+        with the carried matte as the prior; model None removes it"""
+        if model is None:
+            self._chk(self._l.nct_seq_set_region_model(self._h, None, None, None))
+            return
+        rg = _region_params(protect)
+        self._chk(self._l.nct_seq_set_region_model(self._h, model._m, C.addressof(params) if params is not None else None, C.addressof(rg)))
 
     def seq_frame_region_levels(self, src_bgr, want_color=True, want_levels=None):
         """nct_seq_frame_region_levels -> seq_frame_levels' (result, dict) plus per level that ran "ab_mix" (the mixed map the finish read, [2, h*w, 3]) and "mask" (M_l [h, w])"""
