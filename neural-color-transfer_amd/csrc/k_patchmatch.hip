@@ -548,83 +548,53 @@ __global__ __launch_bounds__(256, NCH == 8 ? 2 : (LPQ == 8 ? PM_OCC8 : 1)) void 
 // to, and finally each query scans ITS results in candidate order with the reference's accept rule (d < dbest, first wins). A propagation candidate's distance does not depend
 // on the other candidates of its query — only the early-rejection threshold did, and the initial dbest is a valid (weaker) threshold — so NNF and distances are the same bits.
 // Rounds per wave: ceil(live candidates / 8) instead of sum over the passes of the longest list.
+// The listing and the scan run once per wave with one lane per (query, neighbour) pair: the wave's pairs number 64 (C = 64), 32 (C = 128) or 16, so one ballot lists them
+// all. Run per pass by every lane of a query's group (the first form), that bookkeeping was most of the 730-800 VALU instructions a wave of a late launch issued.
 // It serves every level with fp32 tiles (C >= 256: one pass, the four queries of a wave share its lane groups).
 constexpr int PM_PROP_OCC = PM_OCC8;       // workgroups per CU the packed kernel is compiled for, and how it fetches a candidate's rows (pm_dist8 STAGE): one row at a time
 constexpr int PM_PROP_STAGE = 0;           // measured 11.41 ms for the finest level of a 700x700 pair vs 12.17 (first row, then two together) / 12.18 (whole tile); five workgroups per CU 11.53, six 13.5
 template <int NCH, int MODE, int TQX, int TQY, int LPQ>
 __device__ __forceinline__ void pm_prop_tile(const PMJob& J, int tx, int ty, int jump, int tstep, int strip, float4* __restrict__ s_a, unsigned& nevals, unsigned& naccept) {
     constexpr int RW = 4 * TQX + 2, RH = 4 * TQY + 2, QW = LPQ == 16 ? 4 : 8, QH = 256 / LPQ / QW, NSX = 4 * TQX / QW, NSUB = NSX * (4 * TQY / QH);
-    constexpr int GPW = 64 / LPQ;                          // lane groups (= queries per pass) of a wave
+    constexpr int GPW = 64 / LPQ, NSLOT = NSUB * GPW;      // lane groups (= queries per pass) and query slots of a wave
     static_assert(NSUB == 1 || NSUB == 2, "one or two passes per workgroup: 16 (C = 64), 8 (C = 128) or 4 (C >= 256) queries per wave");
     constexpr bool EX = MODE == NCT_PM_ROWREJECT;
     const float* __restrict__ A = J.A; const float* __restrict__ B = J.B; const uint2* __restrict__ Bh = J.Bh;
     const uint32_t* nnf_in = J.nnf_in; const float* d_in = J.d_in;
     uint32_t* nnf_out = J.nnf_out; float* d_out = J.d_out;
     const PMGeom g = J.g;
-    const int grp = threadIdx.x / LPQ, v = threadIdx.x % LPQ, wv = threadIdx.x >> 6, gw = grp % GPW;
+    const int v = threadIdx.x % LPQ, wv = threadIdx.x >> 6, gw = (threadIdx.x / LPQ) % GPW;
     const int ox = tx * 4 * TQX, oy = ty * 4 * TQY;
-    __shared__ uint32_t s_list[4][4 * NSUB * GPW];     // per wave: live (slot, k, candidate) entries
-    __shared__ uint4 s_q[4][NSUB * GPW];               // per wave and query slot: ax | ay << 16, lx | ly << 8 | amask << 16, dbest, -
-    __shared__ float s_res[4][4 * NSUB * GPW];         // per wave: distance of candidate k of slot s at [s * 4 + k]
+    __shared__ uint32_t s_list[4][4 * NSLOT];          // per wave: live (slot, k, candidate) entries
+    __shared__ uint4 s_q[4][NSLOT];                    // per wave and query slot: ax | ay << 16, lx | ly << 8 | amask << 16, dbest, -
+    __shared__ float s_res[4][4 * NSLOT];              // per wave: distance of candidate k of slot s at [s * 4 + k]
 
-    // ---- the NNF words of both passes first (they fly under the staging loop's barrier)
-    uint32_t vbest[NSUB], vnb[NSUB][4]; float dq[NSUB]; int qi[NSUB]; bool live[NSUB];
-#pragma unroll
-    for (int sub = 0; sub < NSUB; ++sub) {
-        const int qx = ox + (sub % NSX) * QW + (grp % QW), qy = oy + (sub / NSX) * QH + (grp / QW);
-        live[sub] = qx < g.aw && qy < g.ah;
-        const int ax = live[sub] ? qx : 0, ay = live[sub] ? qy : 0;
-        qi[sub] = ay * g.aw + ax;
-        vbest[sub] = nnf_in[qi[sub]]; dq[sub] = d_in[qi[sub]];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int nx = ax + pm_nb_dx(k, jump), ny = ay + pm_nb_dy(k, jump);
-            vnb[sub][k] = *(nnf_in + clampi(ny, 0, g.ah - 1) * g.aw + clampi(nx, 0, g.aw - 1));
-        }
-    }
+    // ---- front end, once per wave: lane l serves (query slot l / 4, neighbour k = l % 4). Slot s is the query of pass s / GPW and lane group s % GPW, the numbering phase B
+    // takes lx, ly from; a wave has 16 (C = 64), 8 (C = 128) or 4 slots, the lanes beyond them idle here and in phase C. Every coordinate comes from the tile origin and constants.
+    const int wl = threadIdx.x & 63, fslot = wl >> 2, fk = wl & 3;
+    const int fsub = fslot / GPW, fgrp = wv * GPW + fslot % GPW;
+    const int qx = ox + (fsub % NSX) * QW + fgrp % QW, qy = oy + (fsub / NSX) * QH + fgrp / QW;
+    const bool live = fslot < NSLOT && qx < g.aw && qy < g.ah;
+    const int ax = live ? qx : 0, ay = live ? qy : 0, qi = ay * g.aw + ax;
+    const int sxx = pm_nb_dx(fk, jump), syy = pm_nb_dy(fk, jump), nx = ax + sxx, ny = ay + syy;
+    // the slot's word and distance (the same address in the four lanes of a quad) and the lane's neighbour word: three loads per wave, flying under the staging loop's barrier
+    const uint32_t vbest = nnf_in[qi]; const float dq = d_in[qi];
+    const uint32_t vp = *(nnf_in + clampi(ny, 0, g.ah - 1) * g.aw + clampi(nx, 0, g.aw - 1));
     pm_stage_region<NCH, RW, RH>(A, g, ox, oy, s_a);
-    // ---- phase A: every query lists its live candidates (the rules of k_pm_step: inside both images, not stale, not the current match)
-    uint32_t cl[NSUB][4]; int ncl[NSUB];
-    int base = 0;
-#pragma unroll
-    for (int sub = 0; sub < NSUB; ++sub) {
-        const int ax = qi[sub] % g.aw, ay = qi[sub] / g.aw;
-        const int xb0 = nnf_x(vbest[sub]), yb0 = nnf_y(vbest[sub]);
-        ncl[sub] = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            cl[sub][k] = 0;
-            const int sxx = pm_nb_dx(k, jump), syy = pm_nb_dy(k, jump);
-            const int nx = ax + sxx, ny = ay + syy;
-            const uint32_t vp = vnb[sub][k];
-            const int xp = nnf_x(vp) - sxx, yp = nnf_y(vp) - syy;
-            bool valid = live[sub] && nx >= 0 && nx < g.aw && ny >= 0 && ny < g.ah && yp >= 0 && yp < g.bh && xp >= 0 && xp < g.bw;
-            valid = valid && !(tstep > 4 && (int)(vp >> 24) < tstep - 4);
-            valid = valid && !(xp == xb0 && yp == yb0);
-            if (valid) {
-                const uint32_t c = xy_pack(xp, yp);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) if (ncl[sub] == i) cl[sub][i] = c;
-                ++ncl[sub];
-            }
-        }
-        const int slot = sub * GPW + gw;
-        if (v == 0) {
-            unsigned amask = 0;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int yy = ay + t / 3 - 1, xx = ax + t % 3 - 1;
-                amask |= ((yy >= 0 && yy < g.ah && xx >= 0 && xx < g.aw) ? 1u : 0u) << t;
-            }
-            s_q[wv][slot] = make_uint4((unsigned)ax | ((unsigned)ay << 16), (unsigned)(ax - ox) | ((unsigned)(ay - oy) << 8) | (amask << 16), __float_as_uint(dq[sub]), 0u);
-        }
-        const unsigned long long below = (1ull << (threadIdx.x & 63)) - 1ull;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(v == 0 && ncl[sub] > i);
-            if (v == 0 && ncl[sub] > i) s_list[wv][base + __builtin_popcountll(m & below)] = ((unsigned)slot << 26) | ((unsigned)i << 24) | cl[sub][i];
-            base += __builtin_popcountll(m);
-        }
+    // ---- phase A: the live (query, neighbour) pairs of the wave in one ballot (the rules of k_pm_step: inside both images, not stale, not the current match)
+    const int xp = nnf_x(vp) - sxx, yp = nnf_y(vp) - syy;
+    bool valid = live && nx >= 0 && nx < g.aw && ny >= 0 && ny < g.ah && yp >= 0 && yp < g.bh && xp >= 0 && xp < g.bw;
+    valid = valid && !(tstep > 4 && (int)(vp >> 24) < tstep - 4);
+    valid = valid && !(xp == nnf_x(vbest) && yp == nnf_y(vbest));
+    const uint32_t cand = xy_pack(xp, yp);               // meaningful where `valid`
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(valid);
+    const int base = __builtin_popcountll(m);
+    if (valid) s_list[wv][__builtin_popcountll(m & ((1ull << wl) - 1ull))] = ((unsigned)fslot << 26) | ((unsigned)fk << 24) | cand;
+    if (live && fk == 0) {
+        // the nine taps of the query's patch that lie inside A, from its four border flags: row dy holds the column mask where the row exists
+        const unsigned cols = (ax > 0 ? 1u : 0u) | 2u | (ax < g.aw - 1 ? 4u : 0u);
+        const unsigned amask = cols * ((ay > 0 ? 1u : 0u) | 8u | (ay < g.ah - 1 ? 64u : 0u));
+        s_q[wv][fslot] = make_uint4((unsigned)ax | ((unsigned)ay << 16), (unsigned)(ax - ox) | ((unsigned)(ay - oy) << 8) | (amask << 16), __float_as_uint(dq), 0u);
     }
     __syncthreads();                                     // the staged region, the lists and the query records are complete
     // ---- phase B: one list entry per lane group and round
@@ -644,24 +614,27 @@ __device__ __forceinline__ void pm_prop_tile(const PMJob& J, int tx, int ty, int
         }
     }
     __syncthreads();
-    // ---- phase C: every query scans its candidates in order (accept d < dbest: the first of equal distances wins, as in the sequential walk)
-#pragma unroll
-    for (int sub = 0; sub < NSUB; ++sub) {
-        if (!(live[sub] && v == 0)) continue;
-        const int slot = sub * GPW + gw;
-        uint32_t best = vbest[sub] & 0xFFFFFFu; float dbest = dq[sub];
+    // ---- phase C: the first lane of every slot scans the slot's evaluated candidates in neighbour order (accept d < dbest: the first of equal distances wins, as in the
+    // sequential walk). The candidates of neighbours 1..3 come from the other lanes of the quad, fetched while all of them are active.
+    const uint32_t c1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cand, 0x55, 0xF, 0xF, false);     // quad_perm:[1,1,1,1]
+    const uint32_t c2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cand, 0xAA, 0xF, 0xF, false);     // quad_perm:[2,2,2,2]
+    const uint32_t c3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cand, 0xFF, 0xF, 0xF, false);     // quad_perm:[3,3,3,3]
+    if (live && fk == 0) {
+        const unsigned bits = (unsigned)(m >> wl) & 0xFu;   // the slot's four ballot bits: wl = 4 * fslot
+        const uint32_t cq[4] = {cand, c1, c2, c3};
+        uint32_t best = vbest & 0xFFFFFFu; float dbest = dq;
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            if (k < ncl[sub]) {
-                float d = s_res[wv][slot * 4 + k];
+            if ((bits >> k) & 1u) {
+                float d = s_res[wv][wl + k];
                 if (d >= dbest) d = dbest;
-                if (d < dbest) { best = cl[sub][k]; dbest = d; ++naccept; }
+                if (d < dbest) { best = cq[k]; dbest = d; ++naccept; }
                 ++nevals;
             }
-        const uint32_t stamp = best != (vbest[sub] & 0xFFFFFFu) ? (uint32_t)tstep : (vbest[sub] >> 24);
-        uint32_t* const o = nnf_out + qi[sub];                  // address before value, as in pm_step_tile
+        const uint32_t stamp = best != (vbest & 0xFFFFFFu) ? (uint32_t)tstep : (vbest >> 24);
+        uint32_t* const o = nnf_out + qi;                   // address before value, as in pm_step_tile
         *o = best | (strip ? 0u : stamp << 24);
-        d_out[qi[sub]] = dbest;
+        d_out[qi] = dbest;
     }
 }
 
@@ -674,7 +647,7 @@ __global__ __launch_bounds__(256, LPQ == 8 ? PM_PROP_OCC : (NCH == 8 ? 2 : 1)) v
     extern __shared__ float4 s_a[];
     unsigned nevals = 0, naccept = 0;
     pm_prop_tile<NCH, MODE, TQX, TQY, LPQ>(J, tx, ty, jump, tstep, strip, s_a, nevals, naccept);
-    pm_count(counter, (int)(threadIdx.x % LPQ), nevals, naccept);
+    pm_count(counter, (int)(threadIdx.x & 3), nevals, naccept);          // the counts sit in the first lane of every slot's quad
 }
 
 // query tile of a workgroup (in 4x4 sub-tiles) per nch = C / 64, 0 = any other C: 8x8 at C = 64 (25 KB of LDS), 8x4 at C = 128 (31 KB), 4x4 above (37 / 74 KB)
