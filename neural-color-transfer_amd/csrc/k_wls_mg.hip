@@ -19,6 +19,7 @@
 // Jacobi-PCG needed 2633/1391/701/359/357 iterations (rtol 1e-10) on the five levels of a 700x700 pair (profiles/r1b); this needs
 // 63/47/34/27/27 (rtol 1e-6) at ~150 us each. Roofline: Infinity-Cache/HBM streaming at 700^2 and 350^2, launch latency below.
 #include "nct_internal.h"
+#include "nct_wls_schedule.h"
 #include <chrono>
 #include <atomic>
 #include <cstdlib>
@@ -1098,8 +1099,6 @@ __global__ void k_pcg_finish(int n, const double* __restrict__ x6, double* __res
 }  // namespace
 
 #define LCHK() NCT_LAUNCH_CHECK()
-constexpr int WLS_BATCH = 2;      // iterations enqueued between two convergence polls (even: the state double buffer); 4: +1.0 ms of empty launches past convergence per pair, 6: +1.3
-
 namespace {
 // One PCG solve over NQ right-hand sides on its own stream. Everything it needs was allocated by the caller (the arena is not thread safe);
 // `ctx` here is only an error sink, so that the second half of a split solve can run on a helper thread.
@@ -1115,212 +1114,218 @@ struct PartBufs {
     PState* hst;                                                    // two page-locked slots the solver state is published to
     const double* rough;                                            // the data term (right-hand side = rough * x0)
     nct_ctx* kt;                                                    // kernel clock (NCT_FLAG_TIME_KERNELS, unsplit solves only), else null
-    int maxit;
-    bool trace;
-    bool forecast;                                                  // size the batches by the convergence forecast (pcg_part)
-    bool lines;                                                     // block step on the finest level (default; NCT_S2_LINES=0: without)
+    const nct_ctx* cfg;                                             // the solve's settings, read only: wls_maxit, wls_forecast, wls_lines, wls_trace
     int iters[NQMAX];
 };
-template <int NQ>
-int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(s) */, PartBufs& B, double rtol) {
-    const std::vector<Lvl>& lv = B.lv;
+// The kernel form of a V-cycle leg. Tile shapes: bandwidth-bound levels use TXB x TYB tiles; below 100k pixels the legs are latency bound, so a 16x8 tile keeps the
+// dependent load chains short and spreads over more CUs. Grid (1-D: mg_tile_of_block maps block -> tile) and block follow from the tile shape.
+constexpr int TXB = 32, TYB = 16;
+dim3 mg_grid(const Lvl& L, int tx, int ty) { return dim3(cdiv(L.W, tx) * cdiv(L.H, ty)); }
+// down leg of level F, right-hand side b. X0: from the block step's iterate x1 instead of zero: one more halo pixel per side, so 32 x 14 tiles (41 x 23 = 943 threads)
+template <int NQ, bool NINE, bool X0>
+void launch_down(hipStream_t s, const PState* st, const Lvl& F, const vf* b, const Lvl& C, const vf* x1) {
+    constexpr int TYL = X0 ? TYB - 2 : TYB;
+    if (F.n >= 100000) hipLaunchKernelGGL((k_mg_down<NQ, TXB, TYL, vf, NINE, X0>), mg_grid(F, TXB, TYL), dim3(mg_threads(TXB, TYL, X0)), 0, s, st, F, b, F.x, C, C.b, x1);
+    else               hipLaunchKernelGGL((k_mg_down<NQ, 16, 8, vf, NINE, X0>), mg_grid(F, 16, 8), dim3(mg_threads(16, 8, X0)), 0, s, st, F, b, F.x, C, C.b, x1);
+}
+// up leg of level L, right-hand side b, coarse correction C.x2; L.x2 = where level L's correction ends up (the leg cannot write in place: neighbouring tiles still read L.x)
+template <int NQ, bool NINE>
+void launch_up(hipStream_t s, const PState* st, const Lvl& L, const vf* b, const Lvl& C) {
+    if (L.n >= 100000) hipLaunchKernelGGL((k_mg_up<NQ, TXB, TYB, vf, NINE>), mg_grid(L, TXB, TYB), dim3(mg_threads(TXB, TYB)), 0, s, st, L, b, (const vf*)L.x, C.W, C.n, (const vf*)C.x2, L.x2);
+    else               hipLaunchKernelGGL((k_mg_up<NQ, 16, 8, vf, NINE>), mg_grid(L, 16, 8), dim3(mg_threads(16, 8)), 0, s, st, L, b, (const vf*)L.x, C.W, C.n, (const vf*)C.x2, L.x2);
+}
+// The levels of the fused middle + tail (k_mg_mid), tail0 = nl - pack.nl to nl - 1: the deepest run of levels whose first has <= 4096 pixels and the others
+// <= MID_N1, at most MID_LV of them; never the fine level (its right-hand side is the fp64 PCG residual and its tiles fill the chip)
+MidPack mid_levels(const std::vector<Lvl>& lv) {
     const int nl = (int)lv.size();
-    const Lvl& F = lv[0];
-    const int N = F.n, nb = cdiv(N, 256);
-    double *x6 = B.x6, *r = B.r, *p = B.p, *sv = B.sv, *w = B.w, *partial = B.partial, *sums = B.sums;
-    vf* rf = B.rf;
-    PState* st = B.st;                                 // st[0] / st[1]; `cur` = the state the iteration being enqueued reads
-    const PState* cur = st;
-    const double rtol2 = rtol * rtol;
-    hipLaunchKernelGGL(k_pcg_start<NQ>, dim3(nb), dim3(256), 0, s, F, B.rough, (const double*)X, (double*)x6, (double*)r, rf, (double*)partial); LCHK();
-    int seq_of_slot[2] = {0, 0};
-    seq_of_slot[0] = ++g_seq;                              // the state after the start kernel (x0 may already solve the system) goes to slot 0
-    hipLaunchKernelGGL(k_pcg_start_fin<NQ>, dim3(1), dim3(256), 0, s, (const double*)partial, nb, st, rtol2, &B.hst[0], seq_of_slot[0]); LCHK();
-
-    // z = Vcycle(r). Levels 0..nl-2 run the tile-fused down/up legs (2 launches per level), the coarsest grid one wave per right-hand side.
-    // lv[l].x2 = where level l's correction ends up (the up leg cannot write in place: neighbouring tiles still read lv[l].x).
-    // Tile shapes: bandwidth-bound levels use TXB x TYB tiles; below 100k pixels the legs are latency bound, so a 16x8 tile keeps the
-    // dependent load chains short and spreads over more CUs.
-    constexpr int TXB = 32, TYB = 16;
-    auto down = [&](int l) {
-        const dim3 gb(cdiv(lv[l].W, TXB) * cdiv(lv[l].H, TYB)), gs(cdiv(lv[l].W, 16) * cdiv(lv[l].H, 8));      // 1-D: mg_tile_of_block maps block -> tile
-        if (l == 0 && B.lines) {
-            // the leg from the block step's iterate (block_pre: x2, free until the up leg): one more halo pixel per side, so 32 x 14 tiles (41 x 23 = 943 threads)
-            constexpr int TYL = TYB - 2;
-            const dim3 gbl(cdiv(lv[0].W, TXB) * cdiv(lv[0].H, TYL));
-            if (lv[l].n >= 100000) hipLaunchKernelGGL((k_mg_down<NQ, TXB, TYL, vf, false, true>), gbl, dim3(mg_threads(TXB, TYL, true)), 0, s, cur, lv[l], (const vf*)rf, lv[l].x, lv[l + 1], lv[l + 1].b, (const vf*)lv[0].x2);
-            else                   hipLaunchKernelGGL((k_mg_down<NQ, 16, 8, vf, false, true>), gs, dim3(mg_threads(16, 8, true)), 0, s, cur, lv[l], (const vf*)rf, lv[l].x, lv[l + 1], lv[l + 1].b, (const vf*)lv[0].x2);
-        } else if (l == 0) {
-            if (lv[l].n >= 100000) hipLaunchKernelGGL((k_mg_down<NQ, TXB, TYB, vf, false>), gb, dim3(mg_threads(TXB, TYB)), 0, s, cur, lv[l], (const vf*)rf, lv[l].x, lv[l + 1], lv[l + 1].b);
-            else                   hipLaunchKernelGGL((k_mg_down<NQ, 16, 8, vf, false>), gs, dim3(mg_threads(16, 8)), 0, s, cur, lv[l], (const vf*)rf, lv[l].x, lv[l + 1], lv[l + 1].b);
-        } else {
-            if (lv[l].n >= 100000) hipLaunchKernelGGL((k_mg_down<NQ, TXB, TYB, vf, true>), gb, dim3(mg_threads(TXB, TYB)), 0, s, cur, lv[l], (const vf*)lv[l].b, lv[l].x, lv[l + 1], lv[l + 1].b);
-            else                   hipLaunchKernelGGL((k_mg_down<NQ, 16, 8, vf, true>), gs, dim3(mg_threads(16, 8)), 0, s, cur, lv[l], (const vf*)lv[l].b, lv[l].x, lv[l + 1], lv[l + 1].b);
-        }
-    };
-    // the block step (finest level): from zero into x2 in front of the down leg; mirrored, x2 -> x (the pre-smoothed iterate there is dead by then), behind the up leg
-    auto block_step = [&](bool post) {
-        if (!B.lines) return;
-        const dim3 gl(cdiv(lv[0].W, LBX) * cdiv(lv[0].H, LBY));
-        if (!post) hipLaunchKernelGGL((k_mg_block<NQ, false>), gl, dim3(LBX * LBY), 0, s, cur, lv[0], (const vf*)rf, (const vf*)nullptr, lv[0].x2);
-        else       hipLaunchKernelGGL((k_mg_block<NQ, true>), gl, dim3(LBX * LBY), 0, s, cur, lv[0], (const vf*)rf, (const vf*)lv[0].x2, lv[0].x);
-    };
-    auto up = [&](int l, const vf* ec) {
-        const dim3 gb(cdiv(lv[l].W, TXB) * cdiv(lv[l].H, TYB)), gs(cdiv(lv[l].W, 16) * cdiv(lv[l].H, 8));
-        const int Wc = lv[l + 1].W, nc = lv[l + 1].n;
-        if (l == 0) {
-            if (lv[l].n >= 100000) hipLaunchKernelGGL((k_mg_up<NQ, TXB, TYB, vf, false>), gb, dim3(mg_threads(TXB, TYB)), 0, s, cur, lv[l], (const vf*)rf, (const vf*)lv[l].x, Wc, nc, ec, lv[l].x2);
-            else                   hipLaunchKernelGGL((k_mg_up<NQ, 16, 8, vf, false>), gs, dim3(mg_threads(16, 8)), 0, s, cur, lv[l], (const vf*)rf, (const vf*)lv[l].x, Wc, nc, ec, lv[l].x2);
-        } else {
-            if (lv[l].n >= 100000) hipLaunchKernelGGL((k_mg_up<NQ, TXB, TYB, vf, true>), gb, dim3(mg_threads(TXB, TYB)), 0, s, cur, lv[l], (const vf*)lv[l].b, (const vf*)lv[l].x, Wc, nc, ec, lv[l].x2);
-            else                   hipLaunchKernelGGL((k_mg_up<NQ, 16, 8, vf, true>), gs, dim3(mg_threads(16, 8)), 0, s, cur, lv[l], (const vf*)lv[l].b, (const vf*)lv[l].x, Wc, nc, ec, lv[l].x2);
-        }
-    };
-    // tail0 = first level of the fused middle + tail (k_mg_mid): the deepest run of levels whose first has <= 4096 pixels and the others
-    // <= MID_N1, at most MID_LV of them; never the fine level (its right-hand side is the fp64 PCG residual and its tiles fill the chip)
-    int tail0 = nl - 1;
     auto mid_fits = [&](int first) {                     // levels first .. nl-1 as depths 0 .. of k_mg_mid
         if (nl - first > MID_LV) return false;
         for (int l = first; l < nl; ++l) { const int d = l - first; if (lv[l].n > (d == 0 ? MID_MAXP0 * MID_T : mid_cap(d))) return false; }
         return true;
     };
+    int tail0 = nl - 1;
     while (tail0 > 1 && mid_fits(tail0 - 1)) --tail0;
     MidPack pack; memset(&pack, 0, sizeof pack); pack.nl = nl - tail0;
     for (int l = tail0; l < nl; ++l) pack.lv[l - tail0] = lv[l];
-    bool ktime = false;                                   // this iteration's launches are timed one by one (NCT_FLAG_TIME_KERNELS)
+    return pack;
+}
+// Convergence is polled without draining the stream: the update kernel of the last iteration of every batch publishes the solver
+// state, with a sequence number, into page-locked host memory; the host enqueues the NEXT batch before it spins on that number, so
+// the GPU always has a batch queued (the kernels of at least one batch are queued behind the state waited for).
+int wait_published(ErrSink* ctx, hipStream_t s, const PState* slot, int want_seq) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 1; __atomic_load_n(&slot->seq, __ATOMIC_ACQUIRE) != want_seq; ++spins) {
+        if (spins > 4096) std::this_thread::yield();
+        if ((spins & 0xFFFFu) == 0) {
+            const hipError_t q = hipStreamQuery(s);
+            if (q != hipSuccess && q != hipErrorNotReady) return ctx->fail(NCT_ERR_HIP, "WLS MG-PCG: stream error while polling the solver state: %s", hipGetErrorString(q));
+            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60)) return ctx->fail(NCT_ERR_HIP, "WLS MG-PCG: the solver state was not published within 60 s");
+        }
+    }
+    return 0;
+}
+template <int NQ>
+int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(s) */, PartBufs& B, double rtol) {
+    const std::vector<Lvl>& lv = B.lv;
+    const Lvl& F = lv[0];
+    const int N = F.n, nb = cdiv(N, 256);
+    const PState* cur = B.st;                             // B.st[0] / B.st[1]; `cur` = the state the iteration being enqueued reads
+    const double rtol2 = rtol * rtol;
+    const bool lines = B.cfg->wls_lines != 0;              // block step on the finest level (default; NCT_S2_LINES=0: without)
+    hipLaunchKernelGGL(k_pcg_start<NQ>, dim3(nb), dim3(256), 0, s, F, B.rough, (const double*)X, B.x6, B.r, B.rf, B.partial); LCHK();
+    int seq_of_slot[2] = {++g_seq, 0};                     // the state after the start kernel (x0 may already solve the system) goes to slot 0
+    hipLaunchKernelGGL(k_pcg_start_fin<NQ>, dim3(1), dim3(256), 0, s, (const double*)B.partial, nb, B.st, rtol2, &B.hst[0], seq_of_slot[0]); LCHK();
+    // z = Vcycle(r). Levels 0..nl-2 run the tile-fused down/up legs (2 launches per level), the coarsest grid one wave per right-hand side.
+    auto down = [&](int l) {
+        if (l == 0 && lines) launch_down<NQ, false, true>(s, cur, lv[0], B.rf, lv[1], lv[0].x2);
+        else if (l == 0)       launch_down<NQ, false, false>(s, cur, lv[0], B.rf, lv[1], nullptr);
+        else                   launch_down<NQ, true, false>(s, cur, lv[l], lv[l].b, lv[l + 1], nullptr);
+    };
+    // the block step (finest level): from zero into x2 in front of the down leg; mirrored, x2 -> x (the pre-smoothed iterate there is dead by then), behind the up leg
+    auto block_step = [&](bool post) {
+        const dim3 gl(cdiv(lv[0].W, LBX) * cdiv(lv[0].H, LBY));
+        if (!post) hipLaunchKernelGGL((k_mg_block<NQ, false>), gl, dim3(LBX * LBY), 0, s, cur, lv[0], (const vf*)B.rf, (const vf*)nullptr, lv[0].x2);
+        else       hipLaunchKernelGGL((k_mg_block<NQ, true>), gl, dim3(LBX * LBY), 0, s, cur, lv[0], (const vf*)B.rf, (const vf*)lv[0].x2, lv[0].x);
+    };
+    auto up = [&](int l) {                                 // (down, block_step, up: the kernels' order of first use, which is their order in the code object)
+        if (l == 0) launch_up<NQ, false>(s, cur, lv[0], B.rf, lv[1]);
+        else        launch_up<NQ, true>(s, cur, lv[l], lv[l].b, lv[l + 1]);
+    };
+    const MidPack pack = mid_levels(lv);
+    const int tail0 = (int)lv.size() - pack.nl;           // levels tail0 .. run in k_mg_mid
+    bool ktime = false;                                   // this iteration's launches are timed one by one (NCT_FLAG_TIME_KERNELS); kt_b / kt_e do nothing otherwise
     auto kt_b = [&](int id) -> int { if (ktime && B.kt->kt_begin(s, id)) return ctx->fail(NCT_ERR_HIP, "%s", B.kt->err.c_str()); return 0; };
     auto kt_e = [&]() -> int { if (ktime && B.kt->kt_end(s)) return ctx->fail(NCT_ERR_HIP, "%s", B.kt->err.c_str()); return 0; };
     auto vcycle = [&]() -> int {
-        if (ktime) {
-            if (B.lines) { NCT_TRY(kt_b(NCT_KT_WLS_BLOCK_PRE)); block_step(false); LCHK(); NCT_TRY(kt_e()); }
-            NCT_TRY(kt_b(NCT_KT_WLS_DOWN)); down(0); LCHK(); NCT_TRY(kt_e());
-            NCT_TRY(kt_b(NCT_KT_WLS_COARSE));
-            for (int l = 1; l < tail0; ++l) { down(l); LCHK(); }
-            if (lv[tail0].n <= MID_T) hipLaunchKernelGGL(k_mg_mid<1>, dim3(NQ), dim3(MID_T), 0, s, cur, pack, 60);
-            else                      hipLaunchKernelGGL(k_mg_mid<2>, dim3(NQ), dim3(MID_T), 0, s, cur, pack, 60);
-            LCHK();
-            for (int l = tail0 - 1; l >= 1; --l) { up(l, lv[l + 1].x2); LCHK(); }
-            NCT_TRY(kt_e());
-            NCT_TRY(kt_b(NCT_KT_WLS_UP)); up(0, lv[1].x2); LCHK(); NCT_TRY(kt_e());
-            if (B.lines) { NCT_TRY(kt_b(NCT_KT_WLS_BLOCK_POST)); block_step(true); LCHK(); NCT_TRY(kt_e()); }
-            return 0;
-        }
-        block_step(false); LCHK();
-        for (int l = 0; l < tail0; ++l) { down(l); LCHK(); }
+        if (lines) { NCT_TRY(kt_b(NCT_KT_WLS_BLOCK_PRE)); block_step(false); LCHK(); NCT_TRY(kt_e()); }
+        NCT_TRY(kt_b(NCT_KT_WLS_DOWN)); down(0); LCHK(); NCT_TRY(kt_e());
+        NCT_TRY(kt_b(NCT_KT_WLS_COARSE));
+        for (int l = 1; l < tail0; ++l) { down(l); LCHK(); }
         if (lv[tail0].n <= MID_T) hipLaunchKernelGGL(k_mg_mid<1>, dim3(NQ), dim3(MID_T), 0, s, cur, pack, 60);
         else                      hipLaunchKernelGGL(k_mg_mid<2>, dim3(NQ), dim3(MID_T), 0, s, cur, pack, 60);
         LCHK();
-        for (int l = tail0 - 1; l >= 0; --l) { up(l, lv[l + 1].x2); LCHK(); }
-        block_step(true); LCHK();
+        for (int l = tail0 - 1; l >= 1; --l) { up(l); LCHK(); }
+        NCT_TRY(kt_e());
+        NCT_TRY(kt_b(NCT_KT_WLS_UP)); up(0); LCHK(); NCT_TRY(kt_e());
+        if (lines) { NCT_TRY(kt_b(NCT_KT_WLS_BLOCK_POST)); block_step(true); LCHK(); NCT_TRY(kt_e()); }
         return 0;
     };
-    const vf* z = B.lines ? lv[0].x : lv[0].x2;
-    // Convergence is polled without draining the stream: the update kernel of the last iteration of every batch publishes the solver
-    // state, with a sequence number, into page-locked host memory; the host enqueues the NEXT batch before it spins on that number, so
-    // the GPU always has a batch queued. The batch enqueued past convergence costs only empty launches (nactive == 0).
-    const int maxit = B.maxit, batch = WLS_BATCH;
-    PState* hst = B.hst;                                  // two slots of page-locked memory
-    PState* pub_to = nullptr; int pub_seq = 0;           // set for the LAST iteration of a batch: its update kernel publishes the state
-    auto iteration = [&](int it) -> int {
-        cur = st + (it & 1);
-        PState* nxt = st + ((it + 1) & 1);
-        ktime = B.kt != nullptr && it >= 2 && it < 6 && tail0 >= 1;
+    const vf* z = lines ? lv[0].x : lv[0].x2;
+    // One PCG iteration; with pub_to, its update kernel also publishes the state it leaves, under the number pub_seq.
+    auto iteration = [&](int it, PState* pub_to, int pub_seq) -> int {
+        cur = B.st + (it & 1);
+        PState* nxt = B.st + ((it + 1) & 1);
+        ktime = B.kt != nullptr && it >= 2 && it < 6;
         NCT_TRY(vcycle());
         NCT_TRY(kt_b(NCT_KT_WLS_APPLY));
-        hipLaunchKernelGGL(k_cg_apply<NQ>, dim3(nb), dim3(256), 0, s, cur, F, z, (const double*)r, (double*)w, (double*)partial); LCHK();
+        hipLaunchKernelGGL(k_cg_apply<NQ>, dim3(nb), dim3(256), 0, s, cur, F, z, (const double*)B.r, B.w, B.partial); LCHK();
         NCT_TRY(kt_e());
-        hipLaunchKernelGGL(k_cg_fin<NQ>, dim3(3), dim3(256), 0, s, cur, (const double*)partial, nb, (double*)sums); LCHK();
+        hipLaunchKernelGGL(k_cg_fin<NQ>, dim3(3), dim3(256), 0, s, cur, (const double*)B.partial, nb, B.sums); LCHK();
         NCT_TRY(kt_b(NCT_KT_WLS_UPDATE));
-        hipLaunchKernelGGL(k_cg_update<NQ>, dim3(nb), dim3(256), 0, s, N, cur, nxt, (const double*)sums, rtol2, it == 0 ? 1 : 0, z, (const double*)w,
-                           (double*)p, (double*)sv, (double*)x6, (double*)r, rf, pub_to, pub_seq); LCHK();
+        hipLaunchKernelGGL(k_cg_update<NQ>, dim3(nb), dim3(256), 0, s, N, cur, nxt, (const double*)B.sums, rtol2, it == 0 ? 1 : 0, z, (const double*)B.w,
+                           B.p, B.sv, B.x6, B.r, B.rf, pub_to, pub_seq); LCHK();
         NCT_TRY(kt_e());
         cur = nxt;
         return 0;
     };
-    auto wait_published = [&](int slot) -> int {           // spin on the publication number (the kernels of at least one batch are queued behind it)
-        const int want_seq = seq_of_slot[slot];
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned spins = 1; __atomic_load_n(&hst[slot].seq, __ATOMIC_ACQUIRE) != want_seq; ++spins) {
-            if (spins > 4096) std::this_thread::yield();
-            if ((spins & 0xFFFFu) == 0) {
-                const hipError_t q = hipStreamQuery(s);
-                if (q != hipSuccess && q != hipErrorNotReady) return ctx->fail(NCT_ERR_HIP, "WLS MG-PCG: stream error while polling the solver state: %s", hipGetErrorString(q));
-                if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60)) return ctx->fail(NCT_ERR_HIP, "WLS MG-PCG: the solver state was not published within 60 s");
-            }
-        }
-        return 0;
-    };
-    // Snapshot k is published by the last kernel of the k-th enqueue (k = 0: by the start kernel), into slot k & 1; the host reads them in order, one per turn, after it
-    // has enqueued the next batch. How MANY iterations that batch gets is a forecast: from the last two snapshots it has read, the host knows r.r of every
-    // system still iterating and its decay per iteration, hence the iterations still needed (the one that finds r.r below the threshold included); what is
-    // already in flight is subtracted. A forecast of 0 enqueues nothing and just waits for the in-flight snapshot — if the solve is not done then (the decay
-    // slowed down), the GPU idles for one host round trip (~20 us), about what ONE needless iteration costs; without the forecast every solve ran 2-4 of
-    // those (22-44 empty launches: 19 iterations of 110 per 700x700 pair). The forecast never changes what an iteration computes.
-    int it = 0; bool done = false;
-    int issued = 0, seen = -1;                             // snapshot numbers
-    int its_at_snapshot[2] = {0, 0};                       // iterations enqueued when snapshot (k & 1) was taken
-    PState fin; memset(&fin, 0, sizeof fin);
-    double prev_rho[6]; int prev_its = -1;
-    int remaining_after_seen = -1;                         // forecast; -1 = none yet
-    int its_seen = 0;
-    bool forecast_on = B.forecast;
+    // Snapshot k travels through slot k & 1 of the page-locked pair. The batch enqueued past convergence costs only empty launches (nactive == 0).
+    WlsSchedule sched{NQ, B.cfg->wls_maxit, B.cfg->wls_forecast != 0, rtol2};
     while (true) {
-        int want = batch;
-        if (forecast_on && remaining_after_seen >= 0) {
-            const int inflight = it - its_seen;
-            want = remaining_after_seen - inflight;
-            if (want > batch) want = batch;
-            if (want < 0) want = 0;
-            if (want == 0 && issued == seen) { want = batch; forecast_on = false; }   // nothing in flight and not converged: the forecast was short (the decay
-                                                                                       // flattened) — the GPU just idled for a round trip; fixed batches for the rest of this solve
+        const int want = sched.next_batch(), pub = (sched.issued + 1) & 1;
+        for (int k = 0; k < want; ++k) {
+            const bool last = k == want - 1;               // the last iteration of a batch publishes
+            if (last) seq_of_slot[pub] = ++g_seq;
+            NCT_TRY(iteration(sched.it + k, last ? &B.hst[pub] : nullptr, last ? seq_of_slot[pub] : 0));
         }
-        if (it + want > maxit) want = maxit - it;
-        if (want > 0) {
-            for (int k = 0; k < want; ++k, ++it) {
-                if (k == want - 1) { seq_of_slot[(issued + 1) & 1] = ++g_seq; pub_to = &hst[(issued + 1) & 1]; pub_seq = seq_of_slot[(issued + 1) & 1]; }
-                int rc = iteration(it); pub_to = nullptr; if (rc) return rc;
-            }
-            ++issued; its_at_snapshot[issued & 1] = it;
-        }
-        if (seen == issued) break;                         // nothing left to read: the iteration budget is spent
-        ++seen;
-        NCT_TRY(wait_published(seen & 1));
-        fin = hst[seen & 1];
-        its_seen = its_at_snapshot[seen & 1];
-        if (fin.nactive == 0) { done = true; break; }
-        if (it >= maxit && seen == issued) break;
-        if (B.forecast) {
-            // iterations still needed after this snapshot: the slowest system's m = ceil(log(threshold / rho) / log(decay per iteration)), decay from the
-            // previous snapshot read; no forecast (full batches) while there is no history or the residual does not decay
-            const int ridx = its_seen > 0 ? its_seen - 1 : 0;   // fin.rho = r_ridx . r_ridx (the start kernel and iteration 0 both see r_0)
-            int need = -1; bool ok = prev_its >= 0 && ridx > prev_its;
-            if (ok) {
-                need = 1;
-                for (int q = 0; q < NQ; ++q) {
-                    if (!fin.active[q]) continue;
-                    const double thr = rtol2 * fin.bb[q], rho = fin.rho[q];
-                    if (!(rho > 0.0) || !(prev_rho[q] > 0.0) || !(thr > 0.0)) { ok = false; break; }
-                    const double decay = pow(rho / prev_rho[q], 1.0 / (double)(ridx - prev_its));
-                    if (!(decay < 0.95)) { ok = false; break; }
-                    // fin.rho = r.r the LAST iteration saw, i.e. one update older than the residual now: the next iteration sees rho * decay
-                    const double m = rho * decay <= thr ? 1.0 : 1.0 + ceil(log(thr / (rho * decay)) / log(decay));
-                    if (m > need) need = (int)(m < 1e6 ? m : 1e6);
-                }
-            }
-            remaining_after_seen = ok ? need : -1;
-            for (int q = 0; q < NQ; ++q) prev_rho[q] = fin.rho[q];
-            prev_its = ridx;
-        }
+        sched.enqueued(want);
+        if (!sched.pending()) break;
+        const int slot = (sched.seen + 1) & 1;
+        NCT_TRY(wait_published(ctx, s, &B.hst[slot], seq_of_slot[slot]));
+        if (sched.read(B.hst[slot])) break;
     }
-    // iterations enqueued after `fin` was taken leave the state untouched (nactive == 0), so fin is final
-    if (!done) return ctx->fail(NCT_ERR_HIP, "WLS MG-PCG did not converge in %d iterations", maxit);
-    hipLaunchKernelGGL(k_pcg_finish<NQ>, dim3(cdiv(N * NQ, 256)), dim3(256), 0, s, N, (const double*)x6, X); LCHK();
-    for (int q = 0; q < NQ; ++q) B.iters[q] = fin.iters[q];
-    if (B.trace) {                                          // NCT_WLS_TRACE=1: iterations enqueued against iterations that did something, snapshots read
-        int mx = 0; for (int q = 0; q < NQ; ++q) mx = fin.iters[q] > mx ? fin.iters[q] : mx;
-        fprintf(stderr, "nct wls: %d x %d, %d iterations enqueued, %d needed (+1 that finds every system converged), %d snapshots read\n", F.W, F.H, it, mx, seen + 1);
+    if (!sched.done) return ctx->fail(NCT_ERR_HIP, "WLS MG-PCG did not converge in %d iterations", B.cfg->wls_maxit);
+    hipLaunchKernelGGL(k_pcg_finish<NQ>, dim3(cdiv(N * NQ, 256)), dim3(256), 0, s, N, (const double*)B.x6, X); LCHK();
+    int mx = 0;
+    for (int q = 0; q < NQ; ++q) { B.iters[q] = sched.iters[q]; mx = B.iters[q] > mx ? B.iters[q] : mx; }
+    if (B.cfg->wls_trace)                                            // iterations enqueued against iterations that did something, snapshots read
+        fprintf(stderr, "nct wls: %d x %d, %d iterations enqueued, %d needed (+1 that finds every system converged), %d snapshots read\n", F.W, F.H, sched.it, mx, sched.seen + 1);
+    return 0;
+}
+// The arena blocks of one solve, returned when it ends. A failed allocation (ctx->alloc has recorded the message) sets `failed`, which every step checks once.
+// The steps keep their order and sizes of allocation: the arena hands the same blocks to the same arrays in every solve of a size.
+struct SolveBlocks {
+    nct_ctx* c; std::vector<void*> owned; bool failed = false;
+    ~SolveBlocks() { for (void* q : owned) c->release(q); }
+    template <typename T> T* get(size_t n) { void* q = c->alloc(n * sizeof(T)); if (q) owned.push_back(q); else failed = true; return (T*)q; }
+    double* newd(size_t n) { return get<double>(n); }
+    vf* newf(size_t n) { return get<vf>(n); }
+};
+// Step 1: the levels — H x W, halved (rounded up) until <= 64 points — with their operator arrays and the first part's V-cycle vectors.
+int mg_alloc_levels(nct_ctx* ctx, SolveBlocks& A, std::vector<Lvl>& lv, int H, int W, int nq0, const double* wx, const double* wy) {
+    int h = H, w = W;
+    for (int l = 0;; ++l) {
+        Lvl L; memset(&L, 0, sizeof L); L.H = h; L.W = w; L.n = h * w; L.nine = l > 0 ? 1 : 0;
+        const bool last = L.n <= 64 || (h <= 8 && w <= 8) || l >= 15;
+        if (l == 0) { L.wE = (double*)wx; L.wS = (double*)wy; }
+        else { L.wE = A.newd(L.n); L.wS = A.newd(L.n); L.wSE = A.newd(L.n); L.wSW = A.newd(L.n); L.fSE = A.newf(L.n); L.fSW = A.newf(L.n); }
+        L.d = A.newd(L.n); L.fd = A.newf(L.n); L.fdinv = A.newf(L.n); L.fE = A.newf(L.n); L.fS = A.newf(L.n);
+        if (!last) { L.pa = A.newd(L.n); L.pb = A.newd(L.n); }
+        if (!last) { L.fpst = A.newf((size_t)((h + 1) / 2) * ((w + 1) / 2) * 9); L.fpw = A.newf((size_t)L.n * 4); }
+        L.b = l == 0 ? nullptr : A.newf((size_t)L.n * nq0); L.x = A.newf((size_t)L.n * nq0); L.x2 = A.newf((size_t)L.n * nq0);
+        if (l == 0 && ctx->wls_lines) { L.lxm = A.newf(L.n); L.lxp = A.newf(L.n); L.lym = A.newf(L.n); L.lyp = A.newf(L.n); }
+        if (A.failed) return NCT_ERR_HIP;
+        lv.push_back(L);
+        if (last) break;
+        h = (h + 1) / 2; w = (w + 1) / 2;
+    }
+    if (lv.back().n > 64 || lv.size() < 2) return ctx->fail(NCT_ERR_INVALID, "wls: unsupported grid %dx%d (coarsest level %d)", W, H, lv.back().n);
+    return 0;
+}
+// Step 2: the operators of all levels, enqueued on s.
+int mg_build_hierarchy(nct_ctx* ctx, hipStream_t s, SolveBlocks& A, const std::vector<Lvl>& lv, const double* rough) {
+    const int nl = (int)lv.size();
+    double* pst = A.get<double>((size_t)lv[1].n * 9);             // columns of P as 3x3 blocks, reused level by level
+    if (A.failed) return NCT_ERR_HIP;
+    hipLaunchKernelGGL(k_mg_diag, dim3(cdiv(lv[0].n, 256)), dim3(256), 0, s, lv[0], rough); LCHK();
+    if (ctx->wls_lines) { hipLaunchKernelGGL(k_mg_lines_setup, dim3(cdiv(lv[0].H * cdiv(lv[0].W, LBX) + lv[0].W * cdiv(lv[0].H, LBY), 128)), dim3(128), 0, s, lv[0]); LCHK(); }
+    int l_tail = nl;                                            // first level built by k_mg_setup_tail
+    for (int l = 1; l < nl; ++l) if (lv[l].n <= MG_TAIL_N) { l_tail = l; break; }
+    if (nl > MG_MAXL) l_tail = nl;
+    for (int l = 0; l < l_tail; ++l) {
+        const dim3 g(cdiv(lv[l].n, 256));
+        if (l > 0) {
+            const dim3 gc(cdiv(lv[l].n, 128));
+            hipLaunchKernelGGL(k_mg_pstencil, gc, dim3(128), 0, s, lv[l - 1], lv[l], pst); LCHK();
+            hipLaunchKernelGGL(k_mg_pweights, dim3(cdiv(lv[l - 1].n, 256)), dim3(256), 0, s, lv[l - 1], lv[l]); LCHK();
+            hipLaunchKernelGGL(k_mg_galerkin, gc, dim3(128), 0, s, lv[l - 1], lv[l], (const double*)pst); LCHK();
+            hipLaunchKernelGGL(k_mg_finish, g, dim3(256), 0, s, lv[l]); LCHK();
+        }
+        if (l + 1 < nl) { hipLaunchKernelGGL(k_mg_weights, g, dim3(256), 0, s, lv[l]); LCHK(); }
+    }
+    if (l_tail < nl) {
+        LvlPack P;
+        for (int l = 0; l < nl; ++l) P.lv[l] = lv[l];
+        hipLaunchKernelGGL(k_mg_setup_tail, dim3(1), dim3(1024), 0, s, P, l_tail, nl, pst); LCHK();
     }
     return 0;
+}
+// Step 3: what part h (of the split solve: 0 = the a-half, 1 = the b-half) owns. The second part gets V-cycle vectors of its own beside the shared operators.
+int mg_alloc_part(nct_ctx* ctx, SolveBlocks& A, PartBufs& B, int h, const std::vector<Lvl>& lv, int nq0, const double* rough) {
+    const size_t v = (size_t)lv[0].n * nq0;
+    B.rf = A.newf(v);
+    B.x6 = A.newd(v); B.r = A.newd(v); B.p = A.newd(v); B.sv = A.newd(v); B.w = A.newd(v); B.partial = A.newd((size_t)cdiv(lv[0].n, 256) * 3 * nq0); B.sums = A.newd(3 * nq0);
+    B.st = A.get<PState>(2);
+    B.lv = lv;
+    if (h == 1) for (size_t l = 0; l < lv.size(); ++l) {
+        Lvl& L = B.lv[l];
+        L.b = l == 0 ? nullptr : A.newf((size_t)L.n * nq0); L.x = A.newf((size_t)L.n * nq0); L.x2 = A.newf((size_t)L.n * nq0);
+    }
+    static_assert(4 * sizeof(PState) <= 4096, "pinned read-back area too small");
+    B.hst = (PState*)ctx->pinned + 2 * h;
+    B.cfg = ctx; B.rough = rough;
+    B.kt = (ctx->kt_on && !ctx->wls_split) ? ctx : nullptr;
+    memset(B.iters, 0, sizeof B.iters);
+    return A.failed ? NCT_ERR_HIP : 0;
 }
 }  // namespace
 
@@ -1333,104 +1338,31 @@ int nctk_wls_solve_mg(nct_ctx* ctx, hipStream_t s, double* X, const double* roug
                       double rtol, int* iters_out /*host[6], nullable*/) {
     const bool split = ctx->wls_split != 0;
     const int nq0 = split ? 3 : 6;
-    // ---- hierarchy
+    SolveBlocks blocks{ctx};
     std::vector<Lvl> lv;
-    std::vector<void*> owned;
-    struct Cleanup { nct_ctx* c; std::vector<void*>& v; ~Cleanup() { for (void* q : v) c->release(q); } } cleanup{ctx, owned};
-    auto newd = [&](size_t n) -> double* { void* q = ctx->alloc(n * sizeof(double)); if (q) owned.push_back(q); return (double*)q; };
-    auto newf = [&](size_t n) -> vf* { void* q = ctx->alloc(n * sizeof(vf)); if (q) owned.push_back(q); return (vf*)q; };
-    {
-        int h = H, w = W;
-        for (int l = 0;; ++l) {
-            Lvl L; memset(&L, 0, sizeof L); L.H = h; L.W = w; L.n = h * w; L.nine = l > 0 ? 1 : 0;
-            const bool last = L.n <= 64 || (h <= 8 && w <= 8) || l >= 15;
-            if (l == 0) { L.wE = (double*)wx; L.wS = (double*)wy; }
-            else { L.wE = newd(L.n); L.wS = newd(L.n); L.wSE = newd(L.n); L.wSW = newd(L.n); L.fSE = newf(L.n); L.fSW = newf(L.n);
-                   if (!L.wE || !L.wS || !L.wSE || !L.wSW || !L.fSE || !L.fSW) return NCT_ERR_HIP; }
-            L.d = newd(L.n); L.fd = newf(L.n); L.fdinv = newf(L.n); L.fE = newf(L.n); L.fS = newf(L.n);
-            if (!last) { L.pa = newd(L.n); L.pb = newd(L.n); }
-            if (!last) { L.fpst = newf((size_t)((h + 1) / 2) * ((w + 1) / 2) * 9); L.fpw = newf((size_t)L.n * 4); }
-            L.b = l == 0 ? nullptr : newf((size_t)L.n * nq0); L.x = newf((size_t)L.n * nq0); L.x2 = newf((size_t)L.n * nq0);
-            if (l == 0 && ctx->wls_lines) { L.lxm = newf(L.n); L.lxp = newf(L.n); L.lym = newf(L.n); L.lyp = newf(L.n); if (!L.lxm || !L.lxp || !L.lym || !L.lyp) return NCT_ERR_HIP; }
-            if (!L.d || !L.fd || !L.fdinv || !L.fE || !L.fS || (!last && (!L.pa || !L.pb || !L.fpst || !L.fpw)) || (l > 0 && !L.b) || !L.x || !L.x2) return NCT_ERR_HIP;
-            lv.push_back(L);
-            if (last) break;
-            h = (h + 1) / 2; w = (w + 1) / 2;
-        }
-        if (lv.back().n > 64 || lv.size() < 2) return ctx->fail(NCT_ERR_INVALID, "wls: unsupported grid %dx%d (coarsest level %d)", W, H, lv.back().n);
+    NCT_TRY(mg_alloc_levels(ctx, blocks, lv, H, W, nq0, wx, wy));
+    NCT_TRY(mg_build_hierarchy(ctx, s, blocks, lv, rough));
+    PartBufs part[2];                                          // both parts' buffers before anything runs: the helper thread must not touch the arena
+    for (int h = 0; h < (split ? 2 : 1); ++h) NCT_TRY(mg_alloc_part(ctx, blocks, part[h], h, lv, nq0, rough));
+    ErrSink sink[2]; int rc[2] = {0, 0};
+    hipError_t e1 = hipSuccess, e2 = hipSuccess;
+    if (!split) rc[0] = pcg_part<6>(&sink[0], s, X, part[0], rtol);
+    else {
+        // fork: the helper stream starts when the hierarchy (and everything before it on s) is complete; join: s waits for the helper's last kernel
+        hipStream_t s2 = ctx->stream_wls;
+        NCT_HIP(hipEventRecord(ctx->ev_wls_fork, s));
+        NCT_HIP(hipStreamWaitEvent(s2, ctx->ev_wls_fork, 0));
+        const int dev = ctx->device;
+        std::thread helper([&] {
+            if (hipSetDevice(dev) != hipSuccess) { rc[1] = sink[1].fail(NCT_ERR_HIP, "hipSetDevice failed on the WLS helper thread"); return; }
+            rc[1] = pcg_part<3>(&sink[1], s2, X + (size_t)3 * lv[0].n, part[1], rtol);
+        });
+        rc[0] = pcg_part<3>(&sink[0], s, X, part[0], rtol);
+        helper.join();
+        e1 = hipEventRecord(ctx->ev_wls_join, s2); e2 = hipStreamWaitEvent(s, ctx->ev_wls_join, 0);     // also on errors: the arena blocks return in s's order
     }
-    const int nl = (int)lv.size();
-    {
-        double* pst = newd((size_t)lv[1].n * 9);                  // columns of P as 3x3 blocks, reused level by level
-        if (!pst) return NCT_ERR_HIP;
-        hipLaunchKernelGGL(k_mg_diag, dim3(cdiv(lv[0].n, 256)), dim3(256), 0, s, lv[0], rough); LCHK();
-        if (ctx->wls_lines) { hipLaunchKernelGGL(k_mg_lines_setup, dim3(cdiv(lv[0].H * cdiv(lv[0].W, LBX) + lv[0].W * cdiv(lv[0].H, LBY), 128)), dim3(128), 0, s, lv[0]); LCHK(); }
-        int l_tail = nl;                                        // first level built by k_mg_setup_tail
-        for (int l = 1; l < nl; ++l) if (lv[l].n <= MG_TAIL_N) { l_tail = l; break; }
-        if (nl > MG_MAXL) l_tail = nl;
-        for (int l = 0; l < l_tail; ++l) {
-            const dim3 g(cdiv(lv[l].n, 256));
-            if (l > 0) {
-                const dim3 gc(cdiv(lv[l].n, 128));
-                hipLaunchKernelGGL(k_mg_pstencil, gc, dim3(128), 0, s, lv[l - 1], lv[l], pst); LCHK();
-                hipLaunchKernelGGL(k_mg_pweights, dim3(cdiv(lv[l - 1].n, 256)), dim3(256), 0, s, lv[l - 1], lv[l]); LCHK();
-                hipLaunchKernelGGL(k_mg_galerkin, gc, dim3(128), 0, s, lv[l - 1], lv[l], (const double*)pst); LCHK();
-                hipLaunchKernelGGL(k_mg_finish, g, dim3(256), 0, s, lv[l]); LCHK();
-            }
-            if (l + 1 < nl) { hipLaunchKernelGGL(k_mg_weights, g, dim3(256), 0, s, lv[l]); LCHK(); }
-        }
-        if (l_tail < nl) {
-            LvlPack P;
-            for (int l = 0; l < nl; ++l) P.lv[l] = lv[l];
-            hipLaunchKernelGGL(k_mg_setup_tail, dim3(1), dim3(1024), 0, s, P, l_tail, nl, pst); LCHK();
-        }
-    }
-    const int N = lv[0].n, nb = cdiv(N, 256);
-    static_assert(4 * sizeof(PState) <= 4096, "pinned read-back area too small");
-    // ---- per-part buffers (both parts' before anything runs: the helper thread must not touch the arena)
-    PartBufs part[2];
-    const int nparts = split ? 2 : 1;
-    for (int h = 0; h < nparts; ++h) {
-        PartBufs& B = part[h];
-        const size_t v = (size_t)N * nq0;
-        B.rf = newf(v); if (!B.rf) return NCT_ERR_HIP;
-        B.x6 = newd(v); B.r = newd(v); B.p = newd(v); B.sv = newd(v); B.w = newd(v); B.partial = newd((size_t)nb * 3 * nq0); B.sums = newd(3 * nq0);
-        B.st = (PState*)ctx->alloc(2 * sizeof(PState)); if (B.st) owned.push_back(B.st);
-        if (!B.x6 || !B.r || !B.p || !B.sv || !B.w || !B.partial || !B.sums || !B.st) return NCT_ERR_HIP;
-        B.lv = lv;
-        if (h == 1) for (int l = 0; l < nl; ++l) {             // the second part's own V-cycle vectors
-            Lvl& L = B.lv[l];
-            L.b = l == 0 ? nullptr : newf((size_t)L.n * nq0); L.x = newf((size_t)L.n * nq0); L.x2 = newf((size_t)L.n * nq0);
-            if ((l > 0 && !L.b) || !L.x || !L.x2) return NCT_ERR_HIP;
-        }
-        B.hst = (PState*)ctx->pinned + 2 * h;
-        B.maxit = ctx->wls_maxit; B.forecast = ctx->wls_forecast != 0; B.lines = ctx->wls_lines != 0; B.trace = getenv("NCT_WLS_TRACE") != nullptr; B.rough = rough; B.kt = (ctx->kt_on && !split) ? ctx : nullptr;
-        memset(B.iters, 0, sizeof B.iters);
-    }
-    if (!split) {
-        ErrSink sink;
-        const int rc = pcg_part<6>(&sink, s, X, part[0], rtol);
-        if (rc) return ctx->fail(rc, "%s", sink.err.c_str());
-        if (iters_out) for (int q = 0; q < 6; ++q) iters_out[q] = part[0].iters[q];
-        return 0;
-    }
-    // fork: the helper stream starts when the hierarchy (and everything before it on s) is complete; join: s waits for the helper's last kernel
-    hipStream_t s2 = ctx->stream_wls;
-    NCT_HIP(hipEventRecord(ctx->ev_wls_fork, s));
-    NCT_HIP(hipStreamWaitEvent(s2, ctx->ev_wls_fork, 0));
-    ErrSink sink_a, sink_b;
-    int rc_b = 0;
-    const int dev = ctx->device;
-    std::thread helper([&] {
-        if (hipSetDevice(dev) != hipSuccess) { rc_b = sink_b.fail(NCT_ERR_HIP, "hipSetDevice failed on the WLS helper thread"); return; }
-        rc_b = pcg_part<3>(&sink_b, s2, X + (size_t)3 * N, part[1], rtol);
-    });
-    const int rc_a = pcg_part<3>(&sink_a, s, X, part[0], rtol);
-    helper.join();
-    hipError_t e1 = hipEventRecord(ctx->ev_wls_join, s2), e2 = hipStreamWaitEvent(s, ctx->ev_wls_join, 0);     // also on errors: the arena blocks return in s's order
-    if (rc_a) return ctx->fail(rc_a, "%s", sink_a.err.c_str());
-    if (rc_b) return ctx->fail(rc_b, "%s", sink_b.err.c_str());
+    for (int h = 0; h < 2; ++h) if (rc[h]) return ctx->fail(rc[h], "%s", sink[h].err.c_str());
     NCT_HIP(e1); NCT_HIP(e2);
-    if (iters_out) for (int q = 0; q < 3; ++q) { iters_out[q] = part[0].iters[q]; iters_out[3 + q] = part[1].iters[q]; }
+    if (iters_out) for (int q = 0; q < 6; ++q) iters_out[q] = part[q / nq0].iters[q % nq0];
     return 0;
 }

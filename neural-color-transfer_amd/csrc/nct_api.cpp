@@ -117,6 +117,7 @@ int nct_create(int device, nct_ctx** out) {
     if (const char* q = getenv("NCT_KNN_RUNS")) { const int v = atoi(q); if (v == 0 || v == 1) c->knn_runs = v; }
     if (const char* q = getenv("NCT_S1_HUB_HINT")) { const int v = atoi(q); if (v == 0 || v == 1) c->s1_hub_hint = v; }
     if (const char* m = getenv("NCT_WLS_MAXIT")) { const int v = atoi(m); if (v > 0) c->wls_maxit = v; }
+    c->wls_trace = getenv("NCT_WLS_TRACE") != nullptr;
     if (const char* m = getenv("NCT_S1_MAXIT")) { const int v = atoi(m); if (v > 0) c->s1_maxit = v; }
     if (const char* m = getenv("NCT_ARENA_FILL")) { char* end = nullptr; const long v = strtol(m, &end, 0); if (end != m && *end == 0 && v >= 0 && v <= 255) c->arena_fill = (int)v; }
     *out = c;

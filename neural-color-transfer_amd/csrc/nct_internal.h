@@ -43,6 +43,7 @@ struct nct_ctx {
                                                 // 700x700, mixed and 1000x1000 fixtures: 1e-7 with the point smoother of rounds 3-5a (1e-6: 55.4 / 50.1 dB), 3e-8 with the block step (the same residual norm
                                                 // leaves more low-frequency error: 5e-8 differs in 53 bytes on the mixed pair; profiles/round5_wls_rtol_sweep.json). Experiment hook: env NCT_WLS_RTOL
     int wls_maxit = 5000;                       // iteration budget of the WLS solve (test hook: env NCT_WLS_MAXIT)
+    bool wls_trace = false;                     // env NCT_WLS_TRACE: every (half-)solve prints the iterations it enqueued and needed and the snapshots it read (k_wls_mg.hip: pcg_part)
     int s1_maxit = 0;                           // S1 iteration cap; 0 = the reference's (50 at layer 4, else 100). Test hook: env NCT_S1_MAXIT
     bool tm_on = false;
     int tm_level = 0;                           // pyramid level whose colour stage is being enqueued: the level of the marks k_colorsolve.hip sets
