@@ -162,11 +162,8 @@ int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w
     // ---------------- A1
     hipLaunchKernelGGL(k_apply, dim3(cdiv(3 * N, 256)), dim3(256), 0, s, (const double*)Xa, (const double*)Xb, s_lab_full, N, out_lab_full); LCHK();
     // ---------------- SPEC §6.8: the same smoothed maps onto the original source
-    // with a mask (SPEC §6.13 rule 4) the compose with the original source rides in the same pass
-    if (up && up->mask && up->sigma > 0.0) NCT_TRY(nctk_finish_guided_region(ctx, s, X, s_lab_full, H, W, up->s_bgr, up->mask, up->H, up->W, up->sigma, up->protect, up->form, up->out_bgr));
-    else if (up && up->mask) NCT_TRY(nctk_finish_upsample_region(ctx, s, X, H, W, up->s_bgr, up->mask, up->H, up->W, up->protect, up->form, up->out_bgr));
-    else if (up && up->sigma > 0.0) NCT_TRY(nctk_finish_guided(ctx, s, X, s_lab_full, H, W, up->s_bgr, up->H, up->W, up->sigma, up->form, up->out_bgr));     // SPEC §6.10: s_lab_full is the guide
-    else if (up) NCT_TRY(nctk_finish_upsample(ctx, s, X, H, W, up->s_bgr, up->H, up->W, up->form, up->out_bgr));
+    // with a mask (SPEC §6.13 rule 4) the compose with the original source rides in the same pass; guided (SPEC §6.10), s_lab_full is the guide
+    if (up) NCT_TRY(nctk_finish_up(ctx, s, X, s_lab_full, H, W, *up));
     return 0;
 }
 

@@ -195,22 +195,30 @@ int nct_color_finish(nct_ctx* ctx, const double* ab, int h, int w, int work_h, i
     return NCT_OK;
 }
 
-// the upsampling finish alone (SPEC §6.8): the working-size S2 output upsampled and applied to the original source in one kernel (k_finish_up.hip)
-int nct_color_finish_upsample(nct_ctx* ctx, const double* ab_wls, int h, int w, const uint8_t* s_bgr_full, int H, int W, const nct_params* prm, uint8_t* out_bgr_full) {
+// ---- the upsampling finish alone, on host pointers, in its four forms (k_finish_up.hip): the working-size S2 output upsampled and applied to the original source in one
+// kernel (SPEC §6.8); is_guided: with joint-bilateral weights (SPEC §6.10); mask non-null: with the compose in the pass (SPEC §6.13 rule 4; mask NULL is the unmasked call)
+static int finish_up_host(nct_ctx* ctx, bool is_guided, const double* ab_wls, const uint8_t* lab_work, int h, int w, const uint8_t* s_bgr_full, int H, int W, const uint8_t* mask,
+                          const nct_region_params* region, const nct_guided_params* guided, const nct_params* prm, uint8_t* out_bgr_full) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(ab_wls && s_bgr_full && prm && out_bgr_full, "color_finish_upsample: null pointer");
-    NCT_REQUIRE(h >= 1 && w >= 1 && h <= NCT_FINISH_MAX_SIDE && w <= NCT_FINISH_MAX_SIDE && (long long)h * w <= NCT_FINISH_MAX_PIXELS,
-                "color_finish_upsample: grid %dx%d outside [1x1, 16384 per side, 2^26 px]", w, h);
-    NCT_REQUIRE(H >= h && W >= w, "color_finish_upsample: target %dx%d smaller than the grid %dx%d", W, H, w, h);
-    NCT_REQUIRE(H <= NCT_FINISH_MAX_SIDE && W <= NCT_FINISH_MAX_SIDE && (long long)H * W <= NCT_FINISH_MAX_PIXELS, "color_finish_upsample: target %dx%d above 16384 per side or 2^26 pixels", W, H);
+    NCT_REQUIRE(prm && (guided || !is_guided), "%s: null pointer", nct_finish_up_name(is_guided, mask != nullptr));
+    const nct_finish_up host{s_bgr_full, H, W, out_bgr_full, nct_cube_form(*prm), is_guided ? guided->sigma : 0.0, mask, region ? region->protect : 0};
+    NCT_TRY(nctk_finish_up_check(ctx, is_guided, ab_wls, lab_work, h, w, host));      // before anything is reserved
     const size_t n = (size_t)h * w, N = (size_t)H * W;
     DevBuf<double> x(ctx, 6 * n);
-    DevBuf<uint8_t> sf(ctx, N * 3), obgr(ctx, N * 3);
-    if (!x.ok() || !sf.ok() || !obgr.ok()) return NCT_ERR_HIP;
-    NCT_H2D(x, ab_wls, sizeof(double) * 6 * n); NCT_H2D(sf, s_bgr_full, N * 3);
-    NCT_TRY(nctk_finish_upsample(ctx, ctx->stream, x, h, w, sf, H, W, nct_cube_form(*prm), obgr));
+    DevBuf<uint8_t> lw, sf, dm, obgr;
+    if (!x.ok() || (is_guided && !lw.alloc(ctx, n * 3)) || !sf.alloc(ctx, N * 3) || (mask && !dm.alloc(ctx, N)) || !obgr.alloc(ctx, N * 3)) return NCT_ERR_HIP;
+    NCT_H2D(x, ab_wls, sizeof(double) * 6 * n);
+    if (is_guided) NCT_H2D(lw, lab_work, n * 3);
+    NCT_H2D(sf, s_bgr_full, N * 3);
+    if (mask) NCT_H2D(dm, mask, N);
+    nct_finish_up up = host; up.s_bgr = sf; up.mask = dm; up.out_bgr = obgr;          // the same call on the device copies
+    NCT_TRY(nctk_finish_up(ctx, ctx->stream, x, lw, h, w, up));
     NCT_D2H(out_bgr_full, obgr, N * 3); NCT_SYNC();
     return NCT_OK;
+}
+
+int nct_color_finish_upsample(nct_ctx* ctx, const double* ab_wls, int h, int w, const uint8_t* s_bgr_full, int H, int W, const nct_params* prm, uint8_t* out_bgr_full) {
+    return finish_up_host(ctx, false, ab_wls, nullptr, h, w, s_bgr_full, H, W, nullptr, nullptr, nullptr, prm, out_bgr_full);
 }
 
 // ---- the guided finish (SPEC §6.10): the upsampling finish with joint-bilateral weights (k_finish_up.hip: k_finish_guided)
@@ -229,63 +237,17 @@ int nct_set_finish_guided(nct_ctx* ctx, const nct_guided_params* guided) {
 
 int nct_color_finish_guided(nct_ctx* ctx, const double* ab_wls, const uint8_t* lab_work, int h, int w, const uint8_t* s_bgr_full, int H, int W, const nct_guided_params* guided,
                             const nct_params* prm, uint8_t* out_bgr_full) {
-    NCT_CTX_ENTER();
-    NCT_REQUIRE(ab_wls && lab_work && s_bgr_full && guided && prm && out_bgr_full, "color_finish_guided: null pointer");
-    NCT_REQUIRE(h >= 1 && w >= 1 && h <= NCT_FINISH_MAX_SIDE && w <= NCT_FINISH_MAX_SIDE && (long long)h * w <= NCT_FINISH_MAX_PIXELS,
-                "color_finish_guided: grid %dx%d outside [1x1, 16384 per side, 2^26 px]", w, h);
-    NCT_REQUIRE(H >= h && W >= w, "color_finish_guided: target %dx%d smaller than the grid %dx%d", W, H, w, h);
-    NCT_REQUIRE(H <= NCT_FINISH_MAX_SIDE && W <= NCT_FINISH_MAX_SIDE && (long long)H * W <= NCT_FINISH_MAX_PIXELS, "color_finish_guided: target %dx%d above 16384 per side or 2^26 pixels", W, H);
-    NCT_REQUIRE(nct_guided_sigma_ok(guided->sigma), "color_finish_guided: sigma must be finite and > 0, and so must its square (got %g)", guided->sigma);
-    const size_t n = (size_t)h * w, N = (size_t)H * W;
-    DevBuf<double> x(ctx, 6 * n);
-    DevBuf<uint8_t> lw(ctx, n * 3), sf(ctx, N * 3), obgr(ctx, N * 3);
-    if (!x.ok() || !lw.ok() || !sf.ok() || !obgr.ok()) return NCT_ERR_HIP;
-    NCT_H2D(x, ab_wls, sizeof(double) * 6 * n); NCT_H2D(lw, lab_work, n * 3); NCT_H2D(sf, s_bgr_full, N * 3);
-    NCT_TRY(nctk_finish_guided(ctx, ctx->stream, x, lw, h, w, sf, H, W, guided->sigma, nct_cube_form(*prm), obgr));
-    NCT_D2H(out_bgr_full, obgr, N * 3); NCT_SYNC();
-    return NCT_OK;
+    return finish_up_host(ctx, true, ab_wls, lab_work, h, w, s_bgr_full, H, W, nullptr, nullptr, guided, prm, out_bgr_full);
 }
 
-// ---- the masked upsampling finish alone (SPEC §6.13 rule 4; k_finish_up_region.hip): the two calls above with the compose in their pass; mask NULL is the unmasked call
 int nct_color_finish_upsample_region(nct_ctx* ctx, const double* ab_wls, int h, int w, const uint8_t* s_bgr_full, int H, int W, const uint8_t* mask, const nct_region_params* region,
                                      const nct_params* prm, uint8_t* out_bgr_full) {
-    if (!mask) return nct_color_finish_upsample(ctx, ab_wls, h, w, s_bgr_full, H, W, prm, out_bgr_full);
-    NCT_CTX_ENTER();
-    NCT_REQUIRE(ab_wls && s_bgr_full && prm && out_bgr_full, "color_finish_upsample_region: null pointer");
-    NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "color_finish_upsample_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
-    NCT_REQUIRE(h >= 1 && w >= 1 && h <= NCT_FINISH_MAX_SIDE && w <= NCT_FINISH_MAX_SIDE && (long long)h * w <= NCT_FINISH_MAX_PIXELS,
-                "color_finish_upsample_region: grid %dx%d outside [1x1, 16384 per side, 2^26 px]", w, h);
-    NCT_REQUIRE(H >= h && W >= w, "color_finish_upsample_region: target %dx%d smaller than the grid %dx%d", W, H, w, h);
-    NCT_REQUIRE(H <= NCT_FINISH_MAX_SIDE && W <= NCT_FINISH_MAX_SIDE && (long long)H * W <= NCT_FINISH_MAX_PIXELS, "color_finish_upsample_region: target %dx%d above 16384 per side or 2^26 pixels", W, H);
-    const size_t n = (size_t)h * w, N = (size_t)H * W;
-    DevBuf<double> x(ctx, 6 * n);
-    DevBuf<uint8_t> sf(ctx, N * 3), dm(ctx, N), obgr(ctx, N * 3);
-    if (!x.ok() || !sf.ok() || !dm.ok() || !obgr.ok()) return NCT_ERR_HIP;
-    NCT_H2D(x, ab_wls, sizeof(double) * 6 * n); NCT_H2D(sf, s_bgr_full, N * 3); NCT_H2D(dm, mask, N);
-    NCT_TRY(nctk_finish_upsample_region(ctx, ctx->stream, x, h, w, sf, dm, H, W, region ? region->protect : 0, nct_cube_form(*prm), obgr));
-    NCT_D2H(out_bgr_full, obgr, N * 3); NCT_SYNC();
-    return NCT_OK;
+    return finish_up_host(ctx, false, ab_wls, nullptr, h, w, s_bgr_full, H, W, mask, region, nullptr, prm, out_bgr_full);
 }
 
 int nct_color_finish_guided_region(nct_ctx* ctx, const double* ab_wls, const uint8_t* lab_work, int h, int w, const uint8_t* s_bgr_full, int H, int W, const uint8_t* mask,
                                    const nct_region_params* region, const nct_guided_params* guided, const nct_params* prm, uint8_t* out_bgr_full) {
-    if (!mask) return nct_color_finish_guided(ctx, ab_wls, lab_work, h, w, s_bgr_full, H, W, guided, prm, out_bgr_full);
-    NCT_CTX_ENTER();
-    NCT_REQUIRE(ab_wls && lab_work && s_bgr_full && guided && prm && out_bgr_full, "color_finish_guided_region: null pointer");
-    NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "color_finish_guided_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
-    NCT_REQUIRE(h >= 1 && w >= 1 && h <= NCT_FINISH_MAX_SIDE && w <= NCT_FINISH_MAX_SIDE && (long long)h * w <= NCT_FINISH_MAX_PIXELS,
-                "color_finish_guided_region: grid %dx%d outside [1x1, 16384 per side, 2^26 px]", w, h);
-    NCT_REQUIRE(H >= h && W >= w, "color_finish_guided_region: target %dx%d smaller than the grid %dx%d", W, H, w, h);
-    NCT_REQUIRE(H <= NCT_FINISH_MAX_SIDE && W <= NCT_FINISH_MAX_SIDE && (long long)H * W <= NCT_FINISH_MAX_PIXELS, "color_finish_guided_region: target %dx%d above 16384 per side or 2^26 pixels", W, H);
-    NCT_REQUIRE(nct_guided_sigma_ok(guided->sigma), "color_finish_guided_region: sigma must be finite and > 0, and so must its square (got %g)", guided->sigma);
-    const size_t n = (size_t)h * w, N = (size_t)H * W;
-    DevBuf<double> x(ctx, 6 * n);
-    DevBuf<uint8_t> lw(ctx, n * 3), sf(ctx, N * 3), dm(ctx, N), obgr(ctx, N * 3);
-    if (!x.ok() || !lw.ok() || !sf.ok() || !dm.ok() || !obgr.ok()) return NCT_ERR_HIP;
-    NCT_H2D(x, ab_wls, sizeof(double) * 6 * n); NCT_H2D(lw, lab_work, n * 3); NCT_H2D(sf, s_bgr_full, N * 3); NCT_H2D(dm, mask, N);
-    NCT_TRY(nctk_finish_guided_region(ctx, ctx->stream, x, lw, h, w, sf, dm, H, W, guided->sigma, region ? region->protect : 0, nct_cube_form(*prm), obgr));
-    NCT_D2H(out_bgr_full, obgr, N * 3); NCT_SYNC();
-    return NCT_OK;
+    return finish_up_host(ctx, true, ab_wls, lab_work, h, w, s_bgr_full, H, W, mask, region, guided, prm, out_bgr_full);
 }
 
 }  // extern "C"

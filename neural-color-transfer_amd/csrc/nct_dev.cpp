@@ -237,36 +237,33 @@ int nct_region_pull_dev(nct_ctx* ctx, const uint8_t* d_q_mask, int bh, int bw, c
     return nctk_region_pull(ctx, ctx->stream, d_q_mask, bh, bw, d_ann, d_bnn, ah, aw, w_coherence, w_complete, d_out);
 }
 
-int nct_color_finish_upsample_dev(nct_ctx* ctx, const double* d_ab_wls, int h, int w, const uint8_t* d_s_bgr_full, int H, int W, const nct_params* prm,
-                                  uint8_t* d_out_bgr_full) {                                                                                          /* SPEC §6.8 */
+// ---- the upsampling finish on device pointers, in its four forms (SPEC §6.8, §6.10, §6.13 rule 4); mask NULL is the unmasked call. The form's name is nctk_finish_up's
+static int finish_up_dev(nct_ctx* ctx, bool is_guided, const double* d_ab_wls, const uint8_t* d_lab_work, int h, int w, const uint8_t* d_s_bgr_full, int H, int W, const uint8_t* d_mask,
+                         const nct_region_params* region, const nct_guided_params* guided, const nct_params* prm, uint8_t* d_out_bgr_full) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(prm, "color_finish_upsample_dev: null pointer");
-    return nctk_finish_upsample(ctx, ctx->stream, d_ab_wls, h, w, d_s_bgr_full, H, W, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0, d_out_bgr_full);
+    NCT_REQUIRE(prm && (guided || !is_guided), "%s_dev: null pointer", nct_finish_up_name(is_guided, d_mask != nullptr));
+    const nct_finish_up up{d_s_bgr_full, H, W, d_out_bgr_full, nct_cube_form(*prm), is_guided ? guided->sigma : 0.0, d_mask, region ? region->protect : 0};
+    NCT_TRY(nctk_finish_up_check(ctx, is_guided, d_ab_wls, d_lab_work, h, w, up));      // a guided call is never read as a plain one, whatever its sigma
+    return nctk_finish_up(ctx, ctx->stream, d_ab_wls, d_lab_work, h, w, up);
+}
+
+int nct_color_finish_upsample_dev(nct_ctx* ctx, const double* d_ab_wls, int h, int w, const uint8_t* d_s_bgr_full, int H, int W, const nct_params* prm, uint8_t* d_out_bgr_full) {
+    return finish_up_dev(ctx, false, d_ab_wls, nullptr, h, w, d_s_bgr_full, H, W, nullptr, nullptr, nullptr, prm, d_out_bgr_full);
 }
 
 int nct_color_finish_guided_dev(nct_ctx* ctx, const double* d_ab_wls, const uint8_t* d_lab_work, int h, int w, const uint8_t* d_s_bgr_full, int H, int W,
-                                const nct_guided_params* guided, const nct_params* prm, uint8_t* d_out_bgr_full) {                                     /* SPEC §6.10 */
-    NCT_CTX_ENTER();
-    NCT_REQUIRE(guided && prm, "color_finish_guided_dev: null pointer");
-    return nctk_finish_guided(ctx, ctx->stream, d_ab_wls, d_lab_work, h, w, d_s_bgr_full, H, W, guided->sigma, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0, d_out_bgr_full);
+                                const nct_guided_params* guided, const nct_params* prm, uint8_t* d_out_bgr_full) {
+    return finish_up_dev(ctx, true, d_ab_wls, d_lab_work, h, w, d_s_bgr_full, H, W, nullptr, nullptr, guided, prm, d_out_bgr_full);
 }
 
-// ---- SPEC §6.13 rule 4 on device pointers: the masked upsampling finish; mask NULL is the unmasked call
 int nct_color_finish_upsample_region_dev(nct_ctx* ctx, const double* d_ab_wls, int h, int w, const uint8_t* d_s_bgr_full, int H, int W, const uint8_t* d_mask,
                                          const nct_region_params* region, const nct_params* prm, uint8_t* d_out_bgr_full) {
-    if (!d_mask) return nct_color_finish_upsample_dev(ctx, d_ab_wls, h, w, d_s_bgr_full, H, W, prm, d_out_bgr_full);
-    NCT_CTX_ENTER();
-    NCT_REQUIRE(prm, "color_finish_upsample_region_dev: null pointer");
-    return nctk_finish_upsample_region(ctx, ctx->stream, d_ab_wls, h, w, d_s_bgr_full, d_mask, H, W, region ? region->protect : 0, (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0, d_out_bgr_full);
+    return finish_up_dev(ctx, false, d_ab_wls, nullptr, h, w, d_s_bgr_full, H, W, d_mask, region, nullptr, prm, d_out_bgr_full);
 }
 
 int nct_color_finish_guided_region_dev(nct_ctx* ctx, const double* d_ab_wls, const uint8_t* d_lab_work, int h, int w, const uint8_t* d_s_bgr_full, int H, int W,
                                        const uint8_t* d_mask, const nct_region_params* region, const nct_guided_params* guided, const nct_params* prm, uint8_t* d_out_bgr_full) {
-    if (!d_mask) return nct_color_finish_guided_dev(ctx, d_ab_wls, d_lab_work, h, w, d_s_bgr_full, H, W, guided, prm, d_out_bgr_full);
-    NCT_CTX_ENTER();
-    NCT_REQUIRE(guided && prm, "color_finish_guided_region_dev: null pointer");
-    return nctk_finish_guided_region(ctx, ctx->stream, d_ab_wls, d_lab_work, h, w, d_s_bgr_full, d_mask, H, W, guided->sigma, region ? region->protect : 0,
-                                     (prm->flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0, d_out_bgr_full);
+    return finish_up_dev(ctx, true, d_ab_wls, d_lab_work, h, w, d_s_bgr_full, H, W, d_mask, region, guided, prm, d_out_bgr_full);
 }
 
 }  // extern "C"

@@ -210,17 +210,16 @@ NCT_LOCAL int nctk_color_nonlocal(nct_ctx* ctx, hipStream_t s, const float* err,
 // up (nullable): S2's output, still on the device, then also goes through the upsampling finish onto up's source
 int nctk_color_finish(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int Hw, int Ww, const uint8_t* s_lab_full, int H, int W,
                       const nct_color_params& prm, uint8_t* out_lab_full, const nct_color_debug* dbg, const nct_finish_up* up = nullptr);
-// k_finish_up.hip — SPEC §6.8: ab_wls ([2][h*w][3], device) upsampled (U1's arithmetic) and applied (A1's) to s_bgr_full (H x W >= h x w), BGR in, BGR out, one kernel
-int nctk_finish_upsample(nct_ctx* ctx, hipStream_t s, const double* ab_wls, int h, int w, const uint8_t* s_bgr_full, int H, int W, int form, uint8_t* out_bgr_full);
-// k_finish_up.hip — SPEC §6.10: the same pass with joint-bilateral weights; lab_work ([h*w][3], device): the 8-bit Lab image of the working-size source. Equal sizes: nctk_finish_upsample
-int nctk_finish_guided(nct_ctx* ctx, hipStream_t s, const double* ab_wls, const uint8_t* lab_work, int h, int w, const uint8_t* s_bgr_full, int H, int W, double sigma, int form,
-                       uint8_t* out_bgr_full);
-// k_finish_up_region.hip — SPEC §6.13 rule 4: the two passes above with the compose of SPEC §6.11 rule 3 in the place of their Lab -> BGR; mask ([H*W], device) must
-// not be null, protect is nct_region_params'. Equal sizes keep the copy path
-int nctk_finish_upsample_region(nct_ctx* ctx, hipStream_t s, const double* ab_wls, int h, int w, const uint8_t* s_bgr_full, const uint8_t* mask, int H, int W, int protect, int form,
-                                uint8_t* out_bgr_full);
-int nctk_finish_guided_region(nct_ctx* ctx, hipStream_t s, const double* ab_wls, const uint8_t* lab_work, int h, int w, const uint8_t* s_bgr_full, const uint8_t* mask, int H, int W,
-                              double sigma, int protect, int form, uint8_t* out_bgr_full);
+// k_finish_up.hip — the upsampling finish onto up's source, one kernel: ab_wls ([2][h*w][3], device) upsampled (U1's arithmetic; up.sigma > 0: SPEC §6.10's joint-bilateral
+// weights, with lab_work ([h*w][3], device, else nullable), the 8-bit Lab image of the working-size source, as the guide) and applied (A1's) to up.s_bgr (up.H x up.W >=
+// h x w), BGR in, BGR out; with up.mask the compose of SPEC §6.11 rule 3 rides in the place of the Lab -> BGR. Equal sizes: the plain pass's copy path in every form
+int nctk_finish_up(nct_ctx* ctx, hipStream_t s, const double* ab_wls, const uint8_t* lab_work, int h, int w, const nct_finish_up& up);
+// its checks, for a caller that has to refuse before it reserves or uploads anything. `guided` is the form the caller asked for: a guided entry point is refused for a
+// sigma that nctk_finish_up would read as "plain". The messages name the form (nct_finish_up_name)
+int nctk_finish_up_check(nct_ctx* ctx, bool guided, const void* ab_wls, const void* lab_work, int h, int w, const nct_finish_up& up);
+static inline const char* nct_finish_up_name(bool guided, bool masked) {
+    return guided ? (masked ? "color_finish_guided_region" : "color_finish_guided") : (masked ? "color_finish_upsample_region" : "color_finish_upsample");
+}
 // sigma and sigma^2 (what the kernel divides by) are finite and > 0
 static inline bool nct_guided_sigma_ok(double sigma) { const double s2 = sigma * sigma; return sigma > 0.0 && s2 > 0.0 && s2 <= 1.7976931348623157e308; }
 // SPEC §6.1 rule 1 + the limits of rule 5: nullptr and the working size, or the reason the image is refused (a static string)
