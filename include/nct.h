@@ -35,7 +35,8 @@ extern "C" {
  * nct_process_*_ref_region, and with region masks in sequences, nct_seq_set_region, nct_seq_frame[_propagate]_region_levels and nct_color_finish_{upsample,guided}_region[_dev], and with region tracking,
  * nct_seq_matte_warp[_dev], nct_seq_set_region_tracking and nct_seq_get_region, and with matte snapping, nct_region_snap[_dev], nct_region_snap_params and
  * nct_seq_set_region_snap, and with region selection from strokes, nct_region_select[_dev], nct_feat_quantize[_dev], nct_region_score[_dev], nct_pair_select_region and
- * nct_seq_select_region, and with region models, nct_region_model_*, nct_region_refind[_dev], nct_pair_apply_region_model and nct_seq_set_region_model).
+ * nct_seq_select_region, and with region models, nct_region_model_*, nct_region_refind[_dev], nct_pair_apply_region_model and nct_seq_set_region_model, and with sequences
+ * over several references, nct_seq_begin_multi[_fullres], nct_seq_frame_multi[_stage]_levels, nct_seq_hold, nct_seq_hold_levels and nct_select_reference_hold[_dev]).
  * A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
 #define NCT_VERSION 118
@@ -418,6 +419,52 @@ int nct_seq_blend_mc_dev(nct_ctx* ctx, const double* d_x, const double* d_x_prev
                          double* d_x_out, double* d_tau_map, const int16_t* d_field);
 int nct_seq_warp(nct_ctx* ctx, const double* x_prev, int h, int w, const int16_t* field, double* x_out);
 int nct_seq_warp_dev(nct_ctx* ctx, const double* d_x_prev, int h, int w, const int16_t* d_field, double* d_x_out);
+
+/* ---- frame sequences over several references, with a held selection (SPEC §6.18; an extension). C ABI and python only: the console driver has no option for it.
+ * nct_seq_begin_multi / nct_seq_begin_multi_fullres open a sequence over K references, 1 <= K <= NCT_MAX_REFS, every image within the limits of nct_seq_begin /
+ * nct_seq_begin_fullres (rh / rw: K heights and widths). Each reference is prepared as nct_seq_begin prepares its one: upload (shrunk on the device in the
+ * full-resolution form), pyramid, one VGG19 forward, five taps kept. nct_seq_begin[_fullres] is the K = 1 case: bytes, launches and arena requests are the same.
+ * Every level of a full frame runs SPEC §6.2 rule 1 per reference, then a selection, then §6.2 rule 3's merge; the rest of the level, the blend of §6.3 / §6.4 and the
+ * finish (either full-resolution finish too) are those of a sequence over one reference. The sequence keeps one more map per level run: the label map l_t, one byte
+ * per level pixel. The selection is §6.2 rule 2 unchanged, with no new launch, on a first frame, on the frame after nct_seq_reset or a cut, on every frame when
+ * tau == 0, hold == 0 or K == 1. On every other full frame, per level pixel p, in IEEE double, uncontracted, in this order:
+ *   1. score_k(p) as in §6.2 rule 2; n(p) = the window taps inside the grid; f = the lowest k of the smallest score;
+ *   2. m(p) = the level's field of §6.4 while motion is on, clamped component-wise so that p + m is inside the grid, else 0; j = l_(t-1)(p + m(p));
+ *   3. g(p) = the g of §6.3 rule 3 (§6.4 rule 4 with a field) on L_t[l] and the kept L_(t-1)[l], operation for operation;
+ *   4. margin = (hold * g) * (double)n;
+ *   5. l_t(p) = f if j >= K or score_f < score_j - margin (strictly), else j;
+ *   6. the merge is §6.2 rule 3 with l_t, and l_t replaces the kept map (out of place: the rule gathers).
+ * hold is in units of matching error per window tap (E = -cos in [-1, 1]), finite and in [0, 2]; a NULL nct_seq_hold gives nct_seq_hold_default's. Where the frame did
+ * not change, a pixel keeps the label it had along the motion until another reference is better by more than hold per tap; where it changed, g -> 0 and the selection is
+ * free. With motion on the level's field is found once, in front of the selection, and the blend reads that field. A propagated frame carries the labels,
+ * l_t(p) = l_(t-1)(p + m(p)) (left as they are with motion off); a later full frame holds against them like against any other.
+ * nct_seq_frame, nct_seq_frame_propagate[_levels], nct_seq_probe, nct_seq_frame_auto, nct_seq_reset, nct_seq_end, nct_seq_set_motion and the region calls of
+ * §6.13-§6.17 work unchanged (a source mask acts behind the merge, §6.2 rule 5). nct_seq_frame_levels with a non-null nct_pair_levels is NCT_ERR_INVALID for K > 1:
+ * nct_seq_frame_multi_levels reports through nct_multi_levels (label[l] = l_t; in a full-resolution sequence its result[] must be NULL), nct_seq_levels and
+ * nct_seq_hold_levels — free_label[l] = f ([h*w] bytes), margin[l] = rule 4's value ([h*w] doubles), on a frame without a hold f = l_t and 0.0; all nullable.
+ * nct_seq_frame_multi_stage_levels also takes color[5] (nullable, each nullable), the colour stage's maps per level as nct_pair_levels.color reports them.
+ * nct_pair_set_ref_region and nct_multi_upload stay NCT_ERR_STATE while a sequence is open; reference masks in sequences are undefined.
+ * nct_select_reference_hold: rules 1-6 alone on host maps (synchronous). err[k] h*w fp32, guide_bgr[k] h*w*3, prev_label h*w, lab / lab_prev h*w*3 (8-bit Lab), field
+ * (nullable: m = 0) int16 [h*w][2]; label, guide_out, err_out (as in nct_select_reference), free_label (h*w) and margin (h*w doubles) are nullable. The _dev form takes
+ * device pointers (the two arrays OF pointers are host memory) and is enqueued on the context's stream; there label must not overlap prev_label. K outside
+ * [1, NCT_MAX_REFS], a grid outside 1 … 4096 per side, a null input, hold outside [0, 2] or not finite, sigma not finite and positive: NCT_ERR_INVALID. */
+typedef struct nct_seq_hold { double hold; } nct_seq_hold;
+void nct_seq_hold_default(nct_seq_hold* p);         /* hold 0.005 */
+typedef struct nct_seq_hold_levels { uint8_t* free_label[5]; double* margin[5]; } nct_seq_hold_levels;
+int nct_seq_begin_multi(nct_ctx* ctx, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw, int sh, int sw, const nct_params* prm, const nct_seq_params* seq,
+                        const nct_seq_hold* hold);
+int nct_seq_begin_multi_fullres(nct_ctx* ctx, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw, int sh, int sw, int max_side, int finish,
+                                const nct_params* prm, const nct_seq_params* seq, const nct_seq_hold* hold);
+int nct_seq_frame_multi_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_multi_levels* levels, const nct_seq_levels* seq_levels,
+                               const nct_seq_hold_levels* hold_levels);
+int nct_seq_frame_multi_stage_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_multi_levels* levels,
+                                     const nct_color_stages* const* color, const nct_seq_levels* seq_levels, const nct_seq_hold_levels* hold_levels);
+int nct_select_reference_hold(nct_ctx* ctx, const float* const* err, const uint8_t* const* guide_bgr, int K, int h, int w, const uint8_t* prev_label, const uint8_t* lab,
+                              const uint8_t* lab_prev, const int16_t* field, double hold, double sigma, uint8_t* label, uint8_t* guide_out, float* err_out,
+                              uint8_t* free_label, double* margin);
+int nct_select_reference_hold_dev(nct_ctx* ctx, const float* const* d_err, const uint8_t* const* d_guide_bgr, int K, int h, int w, const uint8_t* d_prev_label,
+                                  const uint8_t* d_lab, const uint8_t* d_lab_prev, const int16_t* d_field, double hold, double sigma, uint8_t* d_label, uint8_t* d_guide_out,
+                                  float* d_err_out, uint8_t* d_free_label, double* d_margin);
 
 /* ---- adaptive key frames (SPEC §6.7; an extension). Which frames of a sequence run the whole pair is decided per frame from how much of the frame the motion field
  * fails to explain, measured on the 8-bit Lab level images before any expensive stage runs.

@@ -73,8 +73,7 @@ __global__ void __launch_bounds__(256) k_seq_blend(const double* x, const double
         for (int c = 0; c < 3; ++c) { const int v = cur[t][c] - old[t][c]; d += v * v; }
         if (in[t]) { D += d; taps += 1; }
     }
-    const double qbar = (double)D / (double)(3 * taps);
-    const double g = 1.0 / (1.0 + qbar / sigma2);
+    const double g = seq_gain(D, taps, sigma2);             // nct_device.h: shared with k_select_hold (SPEC §6.18 rule 3)
     const double tp = tau * g;
     if (tau_map) tau_map[i] = tp;
 #pragma unroll

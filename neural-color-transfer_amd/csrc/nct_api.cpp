@@ -320,6 +320,38 @@ int nct_select_reference(nct_ctx* ctx, const float* const* err, const uint8_t* c
     return NCT_OK;
 }
 
+// SPEC §6.18 rules 1-6 on host maps: the K error maps and guidance images, the kept labels, the two Lab level images and the field up, one k_select_hold launch, the
+// label, the merged maps, the free label and the margin down
+int nct_select_reference_hold(nct_ctx* ctx, const float* const* err, const uint8_t* const* guide_bgr, int K, int h, int w, const uint8_t* prev_label, const uint8_t* lab,
+                              const uint8_t* lab_prev, const int16_t* field, double hold, double sigma, uint8_t* label, uint8_t* guide_out, float* err_out,
+                              uint8_t* free_label, double* margin) {
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_select_hold_check(ctx, "select_reference_hold", (const void* const*)err, (const void* const*)guide_bgr, K, h, w, prev_label, lab, lab_prev, hold, sigma, guide_out));
+    const size_t n = (size_t)h * w;
+    DevBuf<float> e(ctx, n * K), eo(ctx, n);
+    DevBuf<uint8_t> g(ctx, guide_out ? n * 3 * K : 16), go(ctx, n * 3), lbl(ctx, n), prev(ctx, n), fr(ctx, n), l1(ctx, n * 3), l0(ctx, n * 3);
+    DevBuf<int16_t> fld(ctx, field ? n * 2 : 8);
+    DevBuf<double> mg(ctx, n);
+    if (!e.ok() || !eo.ok() || !g.ok() || !go.ok() || !lbl.ok() || !prev.ok() || !fr.ok() || !l1.ok() || !l0.ok() || !fld.ok() || !mg.ok()) return NCT_ERR_HIP;
+    const float* de[NCT_MAX_REFS]; const uint8_t* dg[NCT_MAX_REFS];
+    for (int k = 0; k < K; ++k) {
+        de[k] = e + n * k; dg[k] = guide_out ? g + n * 3 * k : nullptr;
+        NCT_H2D(e + n * k, err[k], sizeof(float) * n);
+        if (guide_out) NCT_H2D(g + n * 3 * k, guide_bgr[k], n * 3);
+    }
+    NCT_H2D(prev, prev_label, n); NCT_H2D(l1, lab, n * 3); NCT_H2D(l0, lab_prev, n * 3);
+    if (field) NCT_H2D(fld, field, sizeof(int16_t) * 2 * n);
+    NCT_TRY(nctk_select_hold(ctx, ctx->stream, de, guide_out ? dg : nullptr, K, h, w, prev, l1, l0, field ? (const int16_t*)fld : nullptr, hold, sigma, lbl,
+                             guide_out ? (uint8_t*)go : nullptr, eo, free_label ? (uint8_t*)fr : nullptr, margin ? (double*)mg : nullptr));
+    if (label) NCT_D2H(label, lbl, n);
+    if (guide_out) NCT_D2H(guide_out, go, n * 3);
+    if (err_out) NCT_D2H(err_out, eo, sizeof(float) * n);
+    if (free_label) NCT_D2H(free_label, fr, n);
+    if (margin) NCT_D2H(margin, mg, sizeof(double) * n);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
 // SPEC §6.3 rule 3 on host maps: the two coefficient maps and the two Lab level images up, one k_seq_blend launch, X' (and the tau_p map) down
 int nct_seq_blend(nct_ctx* ctx, const double* x, const double* x_prev, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, double tau, double sigma,
                   double* x_out, double* tau_map) {

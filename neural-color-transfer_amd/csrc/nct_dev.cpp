@@ -162,6 +162,14 @@ int nct_select_reference_dev(nct_ctx* ctx, const float* const* d_err, const uint
     return nctk_select_reference(ctx, ctx->stream, d_err, d_guide_bgr, K, h, w, d_label, d_guide_out, d_err_out);
 }
 
+int nct_select_reference_hold_dev(nct_ctx* ctx, const float* const* d_err, const uint8_t* const* d_guide_bgr, int K, int h, int w, const uint8_t* d_prev_label,
+                                  const uint8_t* d_lab, const uint8_t* d_lab_prev, const int16_t* d_field, double hold, double sigma, uint8_t* d_label, uint8_t* d_guide_out,
+                                  float* d_err_out, uint8_t* d_free_label, double* d_margin) {                                                        /* SPEC §6.18 */
+    NCT_CTX_ENTER();
+    return nctk_select_hold(ctx, ctx->stream, d_err, d_guide_bgr, K, h, w, d_prev_label, d_lab, d_lab_prev, d_field, hold, sigma, d_label, d_guide_out, d_err_out, d_free_label,
+                            d_margin);
+}
+
 int nct_seq_blend_dev(nct_ctx* ctx, const double* d_x, const double* d_x_prev, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, double tau, double sigma,
                       double* d_x_out, double* d_tau_map) {                                                                                          /* SPEC §6.3 */
     NCT_CTX_ENTER();

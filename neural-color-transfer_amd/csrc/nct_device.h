@@ -55,3 +55,11 @@ __device__ __forceinline__ float dot4_acc(const float4 a, const float4 b, float 
     acc = __builtin_fmaf(a.w, b.w, acc);
     return acc;
 }
+
+// The gain g of SPEC §6.3 rule 3 (§6.4 rule 4 with a field) from the window's integer sum D of squared 8-bit Lab differences over `taps` taps; sigma2 = sigma * sigma.
+// IEEE double, uncontracted, in this order. The one definition k_seq_blend (k_temporal.hip) and k_select_hold (k_select_hold.hip) share: SPEC §6.18 rule 3 asks for
+// the blend's g operation for operation
+__device__ __forceinline__ double seq_gain(int D, int taps, double sigma2) {
+    const double qbar = (double)D / (double)(3 * taps);
+    return 1.0 / (1.0 + qbar / sigma2);
+}

@@ -229,6 +229,18 @@ void nct_set_ctxless_error(const char* msg);   // nct_api.cpp
 // pointers (they go into the kernel's argument block); label, guide_out (then guide may be null too) and err_out are nullable
 int nctk_select_reference(nct_ctx* ctx, hipStream_t s, const float* const* err, const uint8_t* const* guide, int K, int h, int w,
                           uint8_t* label, uint8_t* guide_out, float* err_out);
+// k_select_hold.hip — SPEC §6.18 rules 1-6: nctk_select_reference with a memory. prev_label ([h*w] bytes): the labels the previous frame kept, read at p + m(p);
+// lab / lab_prev ([h*w][3] 8-bit Lab): the two frames' level images, for the gain g of nctk_seq_blend; field (nullable: m = 0) as there; hold in [0, 2], sigma > 0.
+// label, guide_out (then guide may be null too), err_out, free_label (rule 1's f) and margin (rule 4's value, [h*w] doubles) are nullable; label must not overlap prev_label
+int nctk_select_hold(nct_ctx* ctx, hipStream_t s, const float* const* err, const uint8_t* const* guide, int K, int h, int w, const uint8_t* prev_label, const uint8_t* lab,
+                     const uint8_t* lab_prev, const int16_t* field, double hold, double sigma, uint8_t* label, uint8_t* guide_out, float* err_out, uint8_t* free_label,
+                     double* margin);
+// its argument checks (`who` names the entry point in the message), for the host form to run before it moves anything, and the range of hold alone
+int nct_select_hold_check(nct_ctx* ctx, const char* who, const void* const* err, const void* const* guide, int K, int h, int w, const void* prev_label, const void* lab,
+                          const void* lab_prev, double hold, double sigma, const void* guide_out);
+bool nct_seq_hold_ok(double hold);
+// SPEC §6.18 rule 7: label_out(p) = label_prev(p + m(p)), a vector that leaves the grid clamped to it; label_out must not overlap label_prev
+int nctk_label_carry(nct_ctx* ctx, hipStream_t s, const uint8_t* label_prev, int h, int w, const int16_t* field, uint8_t* label_out);
 // k_temporal.hip — SPEC §6.3 rule 3: x_out = x + tau_p (x_prev - x) per level pixel, tau_p from the 3 x 3 mean squared Lab difference; x_out may alias x or x_prev; tau_map nullable.
 // field (nullable, [h*w][2] int16 (my, mx)): SPEC §6.4 rule 4 — L_(t-1) and x_prev are read at p + m(p); x_out may then alias x only
 int nctk_seq_blend(nct_ctx* ctx, hipStream_t s, const double* x, const double* x_prev, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, double tau, double sigma,

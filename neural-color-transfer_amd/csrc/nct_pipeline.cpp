@@ -151,6 +151,7 @@ struct pair_run {
     seq_state* const seq;                          // nullable: this run is a frame of the open sequence (SPEC §6.3) — the reference's pyramid and taps are borrowed, S1's output is blended
     const nct_seq_levels* const slv;               // nullable: where a frame's X'_t and tau_p maps go
     const nct_ref_region_levels* const qlv;        // nullable: where a masked run's level masks and mixed coefficients go (SPEC §6.11, §6.12)
+    const nct_seq_hold_levels* const hlv;          // nullable: where a frame over several references reports the held selection's free labels and margins (SPEC §6.18)
     pair_state* const P; const hipStream_t s;
     const int H, W, K, nlevels; const size_t N;
     const bool feat16, count;
@@ -168,6 +169,10 @@ struct pair_run {
     DevBuf<float> annd, err;
     DevBuf<uint8_t> guide, g_lab_l, out_lab;
     DevBuf<uint8_t> sel_label;                     // the selection's label map (rule 2); a pair allocates none of this
+    // SPEC §6.18: this frame of a sequence over several references selects with a memory — it has a previous frame to hold against, it blends and hold > 0. Every other
+    // frame runs rule 2 as it stands; both keep their label map in the sequence. field_found: the level's field was found in front of the selection, the blend reads it
+    const bool held;
+    bool field_found = false;
     // The run's masks (neither: the run enqueues and reserves what it always did). mask: the source's region mask (SPEC §6.11; null: none), mpyr / mimg: its level masks —
     // the pyramid's single-channel form. ref_masked: a reference has a region mask (SPEC §6.12); p_merged: P_l of several references (rule 3), m_level: M_l where it is not
     // P_l itself (rule 4: a source mask as well), f_level: F_l of a level that is not the last (the last level's is pair_state's fin_mask).
@@ -184,8 +189,8 @@ struct pair_run {
     const nct_color_params cp;
 
     pair_run(nct_ctx* c, const nct_params* p, nct_pair_timing* t, const run_extras& x)
-        : ctx(c), prm(p), timing(t), lv(x.lv ? x.lv : &kNoLevels), color(x.color), fin(x.fin), seq(x.seq), slv(x.slv), qlv(x.qlv), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
-          nlevels(p->levels), N((size_t)H * W), feat16((p->flags & NCT_FLAG_FEAT16) != 0), count(t && (p->flags & NCT_FLAG_COUNT_EVALS)), side(c), mask(P->mask),
+        : ctx(c), prm(p), timing(t), lv(x.lv ? x.lv : &kNoLevels), color(x.color), fin(x.fin), seq(x.seq), slv(x.slv), qlv(x.qlv), hlv(x.hlv), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
+          nlevels(p->levels), N((size_t)H * W), feat16((p->flags & NCT_FLAG_FEAT16) != 0), count(t && (p->flags & NCT_FLAG_COUNT_EVALS)), side(c), held(x.seq && P->K > 1 && x.seq->frames > 0 && x.seq->tau > 0.0 && x.seq->hold > 0.0), mask(P->mask),
           ref_masked(!x.seq && P->ref_masked()), refind(x.seq && x.seq->model_rows && !(P->mask && x.seq->matte_fresh)), cp(nct_color_params_of(*p)) {}
 
     int d2h(void* dst, const void* src, size_t bytes) {
@@ -235,7 +240,7 @@ struct pair_run {
         for (int k = 0; k < K; ++k) R[k].img[4] = P->ref[k];
         for (int l = 3; l >= 0; --l) {
             NCT_TRY(pyramid_level(ctx, s, spyr[l], simg, ah, aw, l));
-            if (seq) { R[0].img[l] = seq->rpyr[l]; continue; }          // the sequence's reference pyramid was built at nct_seq_begin
+            if (seq) { for (int k = 0; k < K; ++k) R[k].img[l] = seq->rpyr[k][l]; continue; }          // the sequence's reference pyramids were built at nct_seq_begin
             for (int k = 0; k < K; ++k) NCT_TRY(pyramid_level(ctx, s, R[k].pyr[l], R[k].img, R[k].bh, R[k].bw, l));
         }
         // SPEC §6.14: a tracked sequence's matte follows the frame's field before its level masks are built; the two matte blocks may have changed places
@@ -261,7 +266,7 @@ struct pair_run {
         if (seq) {
             // the reference's taps are the sequence's (one forward at nct_seq_begin): S runs to conv5_1 on its own. Every conv output is its own fmaf chain, so the
             // bytes are those of the paired launch
-            for (int l = 0; l < 5; ++l) R[0].featp[l] = seq->rfeat[l];
+            for (int k = 0; k < K; ++k) for (int l = 0; l < 5; ++l) R[k].featp[l] = seq->rfeat[k][l];
             float* staps_hwc[5] = {nullptr, nullptr, nullptr, nullptr, sfeat};
             if (refind && seq->model_tap < 5) {
                 // SPEC §6.17 rule S2: the forward also stores the model's tap channel-last; no second forward
@@ -411,7 +416,10 @@ struct pair_run {
                 // selection and merge (SPEC §6.2 rules 2-3): the one launch a level with several references adds; it counts as vote time
                 const float* errs[NCT_MAX_REFS]; const uint8_t* guides[NCT_MAX_REFS];
                 for (int q = 0; q < K; ++q) { errs[q] = R[q].err; guides[q] = R[q].guide; }
-                NCT_TRY(nctk_select_reference(ctx, s, errs, guides, K, ah[l], aw[l], sel_label, guide, err));
+                if (held) NCT_TRY(held_selection(l, errs, guides));
+                else NCT_TRY(nctk_select_reference(ctx, s, errs, guides, K, ah[l], aw[l], sel_label, guide, err));
+                // a frame of a sequence keeps its label map (SPEC §6.18): the next full frame holds against it, a propagated frame carries it
+                if (seq) NCT_HIP(hipMemcpyAsync(seq->keep_label[l], sel_label, (size_t)na_px, hipMemcpyDeviceToDevice, s));
             }
             if ((mask || ref_masked) && k == K - 1) NCT_TRY(level_masks(l));
             MARK(NCT_ST_VOTE, l);
@@ -421,8 +429,33 @@ struct pair_run {
         // K = 1 has no selection: its label map is all zero and the merged maps are reference 0's
         if (K > 1) NCT_TRY(d2h(lv->label[l], sel_label, (size_t)na_px));
         else if (lv->label[l]) memset(lv->label[l], 0, (size_t)na_px);
+        if (hlv && !held) {
+            // a frame without a hold: the free label is the label, the margin 0.0
+            if (K > 1) NCT_TRY(d2h(hlv->free_label[l], sel_label, (size_t)na_px));
+            else if (hlv->free_label[l]) memset(hlv->free_label[l], 0, (size_t)na_px);
+            if (hlv->margin[l]) std::fill(hlv->margin[l], hlv->margin[l] + na_px, 0.0);
+        }
         NCT_TRY(d2h(lv->guide[l], guide, (size_t)na_px * 3));
         return d2h(lv->err[l], err, sizeof(float) * na_px);
+    }
+
+    // SPEC §6.18 rules 1-6 in the place of rule 2's launch. The rule reads L_t[l] and, with motion on, the level's field, which the level would otherwise find between S1
+    // and the finish (seq_level_step): both are made here, on the main stream — the side stream's copy of L_t[l] has not been joined yet, and holds the same bytes —
+    // and the blend then reads this field. The kept L_(t-1)[l], the packed map and the kept labels are still the previous frame's: the level replaces them behind S1
+    int held_selection(int l, const float* const* errs, const uint8_t* const* guides) {
+        const int h = ah[l], w = aw[l];
+        const size_t n = (size_t)h * w;
+        DevBuf<uint8_t> lab_l(ctx, n * 3), free_l; DevBuf<double> margin_l;
+        if (!lab_l.ok()) return NCT_ERR_HIP;
+        if (hlv && hlv->free_label[l] && !free_l.alloc(ctx, n)) return NCT_ERR_HIP;
+        if (hlv && hlv->margin[l] && !margin_l.alloc(ctx, n)) return NCT_ERR_HIP;
+        NCT_TRY(nctk_bgr2lab(ctx, s, simg[l], lab_l, n));
+        if (seq->motion) { NCT_TRY(seq_motion_level(ctx, s, seq, l, lab_l)); field_found = true; }
+        NCT_TRY(nctk_select_hold(ctx, s, errs, guides, K, h, w, seq->keep_label[l], lab_l, seq->keep_lab[l], seq->motion ? seq->field[l] : nullptr, seq->hold, seq->sigma,
+                                 sel_label, guide, err, free_l, margin_l));
+        if (free_l.ok()) NCT_TRY(dbg_copy(ctx, s, hlv->free_label[l], (uint8_t*)free_l, n));
+        if (margin_l.ok()) NCT_TRY(dbg_copy(ctx, s, hlv->margin[l], (double*)margin_l, n));
+        return NCT_OK;
     }
 
     // The level's mix mask m_l, behind the last reference's votes (and the selection). A source mask only (SPEC §6.11 rule 1): its level mask, no launch. With a reference mask
@@ -480,7 +513,7 @@ struct pair_run {
         NCT_TRY(fl.open(ctx, s, full));
         NCT_TRY(nctk_color_nonlocal(ctx, s, err, side.slab[l], g_lab_l, side.knn_ids[l], side.knn_ws[l], l, ah[l], aw[l], H, W, cp, cb, d, &s1graph));
         // a frame of a sequence: the blend between S1 and the finish, which then reads the kept X'_t (SPEC §6.3 rule 3)
-        if (seq) NCT_TRY(seq_level_step(ctx, s, seq, l, side.slab[l], cb.x, cb.tmap, slv));
+        if (seq) NCT_TRY(seq_level_step(ctx, s, seq, l, side.slab[l], cb.x, cb.tmap, slv, field_found));
         // a masked run: S1's coefficients move toward the identity by the mix mask m_l, in place (SPEC §6.11 rule 2); the finish reads X' and composes with the source by f_l
         // (rule 3), the mask at the size the finish targets. A source mask only: f_l is that mask as it came. A masked frame of a sequence (SPEC §6.13 rule 2) mixes out of
         // place, from the kept X'_t into the level's own map, which the finish then reads: the state is never mixed. With a reference mask (SPEC §6.12 rules 4-5): F_l = P_l at that
@@ -547,12 +580,12 @@ int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timin
     pair_state* P = (pair_state*)ctx->pair;
     if (P && P->seq && !x.seq) return ctx->fail(NCT_ERR_STATE, "process: a sequence is open on this context (nct_seq_frame runs its frames; nct_seq_end closes it)");
     if (!P || !P->src || P->K < 1 || !P->ref[0]) return ctx->fail(NCT_ERR_STATE, "process: no pair uploaded");
-    NCT_REQUIRE(!x.fin || P->K == 1, "process: no full-resolution finish with several references");
+    NCT_REQUIRE(!x.fin || P->K == 1 || x.seq, "process: no full-resolution finish with several references");      // but for a frame of an open sequence (SPEC §6.18)
     NCT_REQUIRE(prm->patch_size == 3 && prm->k_num == 8, "process: patch_size must be 3 and k_num 8 (Config.h:68-70)");
     NCT_REQUIRE(prm->cluster_num >= 1 && prm->cluster_num <= 16, "process: cluster_num out of range");
     NCT_REQUIRE(prm->levels >= 1 && prm->levels <= 5, "process: levels must be in [1, 5] (got %d)", prm->levels);
-    NCT_REQUIRE(!x.fin || (!x.lv && !x.color), "process: no level intermediates with a full-resolution finish");
-    NCT_REQUIRE(!x.color || P->K == 1, "process: nct_pair_levels describes a pair; several references report through nct_multi_levels");
+    NCT_REQUIRE(!x.fin || ((!x.lv || x.seq) && !x.color), "process: no level intermediates with a full-resolution finish");     // a sequence's frame reports working-size maps only (nct_seq.cpp)
+    NCT_REQUIRE(!x.color || P->K == 1 || x.seq, "process: nct_pair_levels describes a pair; several references report through nct_multi_levels");
     if (x.refusal) return ctx->fail(NCT_ERR_STATE, "%s", x.refusal);
     NCT_REQUIRE(!(P->mask && x.fin) || (x.fin->mask && (x.fin->finish == NCT_FINISH_EXACT || x.seq)), "process: a region mask is defined for the exact full-resolution finish only");
     NCT_REQUIRE(!(P->ref_masked() && x.fin) || x.fin->finish == NCT_FINISH_EXACT, "process: a reference region mask is defined for the exact full-resolution finish only");

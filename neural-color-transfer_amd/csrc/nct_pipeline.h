@@ -13,6 +13,8 @@ struct full_target { const uint8_t* src = nullptr; int H = 0, W = 0; uint8_t* ou
 // the context's arena and outlives the runs; the frame and the reference at working size are pair_state's src / ref[0] as for a pair.
 // While motion compensation is on (SPEC ยง6.4, nct_seq_set_motion) it also holds, per level, L packed one word per pixel and the level's field (4 B per level pixel each).
 // A propagated frame (SPEC ยง6.5) with motion on warps X' out of place: warp_x, one map of the largest level run, reserved by the first such frame.
+// A sequence over several references (SPEC ยง6.18, nct_seq_begin_multi) holds the pyramid and the taps once per reference and, per level run, the label map of the last
+// frame (1 B per level pixel); a sequence over one reference holds exactly what it always did.
 // The two counters of the key-frame decision (SPEC ยง6.7 rule 3) are host integers: they cost no device memory.
 // A full-resolution sequence (SPEC ยง6.9, nct_seq_begin_fullres) keeps all of that on the working-size grids and adds the frame at its original size H0 x W0 and
 // its result: pair_state's full_src / full_out, which live as long as the sequence and are what nct_pair_fit_lut reads; `full` describes them, H = 0 in any other sequence.
@@ -25,9 +27,11 @@ struct seq_state {
     long frames = 0;                                           // frames since nct_seq_begin / nct_seq_reset: 0 = the next one is a first frame
     long gap = 0;                                              // propagated frames since the last full frame, whichever call ran them
     unsigned long long acc = 0;                                // sum of `changed` over the frames nct_seq_frame_auto propagated since the last full frame
-    int ah[5], aw[5], bh[5], bw[5];
-    uint8_t* rpyr[4] = {}; float* rfeat[5] = {};
+    int ah[5], aw[5], bh[NCT_MAX_REFS][5], bw[NCT_MAX_REFS][5];
+    uint8_t* rpyr[NCT_MAX_REFS][4] = {}; float* rfeat[NCT_MAX_REFS][5] = {};     // per reference (SPEC ยง6.18): nct_seq_begin is the list of one
     double* keep_x[5] = {}; uint8_t* keep_lab[5] = {};
+    double hold = 0;                                           // SPEC ยง6.18: the held selection's margin per window tap; plays no part with one reference
+    uint8_t* keep_label[5] = {};                               // several references only: the label map l_t of every level run, one byte per level pixel
     bool motion = false; nct_seq_motion mp = {0, 0, 0};
     uint32_t* keep_pk[5] = {}; int16_t* field[5] = {};
     double* warp_x = nullptr;
@@ -69,11 +73,12 @@ static const int kTapC[5] = {64, 128, 256, 512, 512};       // tap 1 (conv1_1) โ
 NCT_LOCAL pair_state* pair_of(nct_ctx* ctx);
 NCT_LOCAL void drop_images(nct_ctx* ctx, pair_state* P);    // drop what the context holds of the last pair / reference list
 // what a run is asked for beside its result, every member nullable and filled by name (run_extras x; x.fin = โฆ;). lv: host copies of the level intermediates; color (a pair
-// only): [5] the colour stage's coefficient maps per level; fin (K = 1 only): the full-resolution finish; seq: the run is a frame of this open sequence, slv: where that
+// only): [5] the colour stage's coefficient maps per level; fin (K = 1, or a frame of a sequence): the full-resolution finish; seq: the run is a frame of this open sequence, slv: where that
 // frame's X'_t, tau_p and fields go; qlv: where a masked run reports Q_k,l, P_k,l, M_l, F_l and X' (SPEC ยง6.11, ยง6.12: the one report target of both kinds of mask);
 // refusal: the entry point asked for the report of a mask that is not set โ the run is refused with NCT_ERR_STATE and this text, behind the checks of state and parameters
+// hlv: where a frame of a sequence over several references reports the held selection's free labels and margins (SPEC ยง6.18)
 struct run_extras { const nct_multi_levels* lv = nullptr; const nct_color_stages* const* color = nullptr; const full_target* fin = nullptr; seq_state* seq = nullptr;
-                    const nct_seq_levels* slv = nullptr; const nct_ref_region_levels* qlv = nullptr; const char* refusal = nullptr; };
+                    const nct_seq_levels* slv = nullptr; const nct_ref_region_levels* qlv = nullptr; const char* refusal = nullptr; const nct_seq_hold_levels* hlv = nullptr; };
 // run the whole L=5->1 loop on the uploaded source and its K references
 NCT_LOCAL int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const run_extras& x = {});
 // a pair is the list of one reference (SPEC ยง6.2): its maps are reference 0's NNFs and the merged guide / err; it has no label map and no G_k / E_k of their own
@@ -159,4 +164,5 @@ NCT_LOCAL int seq_refind_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_st
 // A level of a sequence frame (SPEC ยง6.3), between S1 and the finish: X'_t = the blend of S1's output x with X'_(t-1), into the kept state q->keep_x[l], which the finish
 // then reads; L_t (`lab`) replaces L_(t-1). The first frame and tau == 0 only keep the state, with no blend launch. tmap: the caller's, requested here where slv asks
 // for the tau_p map and reserved until the finish has been enqueued. slv (nullable): host copies of X'_t, tau_p and the field
-NCT_LOCAL int seq_level_step(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, const uint8_t* lab, double* x, DevBuf<double>& tmap, const nct_seq_levels* slv);
+// field_found: the level's field is already in q->field[l] โ the held selection of a frame over several references (SPEC ยง6.18) found it in front of itself โ and is not searched again
+NCT_LOCAL int seq_level_step(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, const uint8_t* lab, double* x, DevBuf<double>& tmap, const nct_seq_levels* slv, bool field_found = false);

@@ -1,4 +1,4 @@
-// nct_seq.cpp — frame sequences (SPEC §6.3-§6.9, their region mask §6.13, its tracking §6.14 and the snap §6.15): the state an open sequence keeps in the context's arena, what a level of a frame does between S1 and the finish,
+// nct_seq.cpp — frame sequences (SPEC §6.3-§6.9, their region mask §6.13, its tracking §6.14, the snap §6.15 and several references §6.18): the state an open sequence keeps in the context's arena, what a level of a frame does between S1 and the finish,
 // the frame entry points — a full frame is a run of nct_pipeline.cpp's level loop — the propagated frame, the probe and the key-frame decision.
 #include "nct_pipeline.h"
 #include <cstring>
@@ -19,10 +19,13 @@ void seq_free(nct_ctx* ctx, pair_state* P) {
     if (!q) return;
     seq_motion_free(ctx, q);
     for (int l = 0; l < 5; ++l) {
-        if (l < 4 && q->rpyr[l]) ctx->release(q->rpyr[l]);
-        if (q->rfeat[l]) ctx->release(q->rfeat[l]);
+        for (int k = 0; k < NCT_MAX_REFS; ++k) {
+            if (l < 4 && q->rpyr[k][l]) ctx->release(q->rpyr[k][l]);
+            if (q->rfeat[k][l]) ctx->release(q->rfeat[k][l]);
+        }
         if (q->keep_x[l]) ctx->release(q->keep_x[l]);
         if (q->keep_lab[l]) ctx->release(q->keep_lab[l]);
+        if (q->keep_label[l]) ctx->release(q->keep_label[l]);
     }
     // the sequence's region mask (SPEC §6.13 rule 1) ends with it
     if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
@@ -38,14 +41,14 @@ int seq_motion_level(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, const uin
                            l == 0 ? q->mp.radius0 : q->mp.radius, q->mp.penalty, q->field[l]);
 }
 
-int seq_level_step(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, const uint8_t* lab, double* x, DevBuf<double>& tmap, const nct_seq_levels* slv) {
+int seq_level_step(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, const uint8_t* lab, double* x, DevBuf<double>& tmap, const nct_seq_levels* slv, bool field_found) {
     const int h = q->ah[l], w = q->aw[l], n = h * w;
     const bool blend = q->frames > 0 && q->tau > 0.0;
     double* const keep_x = q->keep_x[l];
     if (slv && slv->tau_map[l] && !tmap.alloc(ctx, n)) return NCT_ERR_HIP;
     if (blend && q->motion) {
         // with motion (SPEC §6.4): the level's field, then the blend gathers X'_(t-1) and L_(t-1) through it — not in place: into S1's own buffer, then into the state
-        NCT_TRY(seq_motion_level(ctx, s, q, l, lab));
+        if (!field_found) NCT_TRY(seq_motion_level(ctx, s, q, l, lab));
         NCT_TRY(nctk_seq_blend(ctx, s, x, keep_x, lab, q->keep_lab[l], h, w, q->tau, q->sigma, x, tmap, q->field[l]));
         NCT_HIP(hipMemcpyAsync(keep_x, x, sizeof(double) * (size_t)6 * n, hipMemcpyDeviceToDevice, s));
         if (slv) NCT_TRY(dbg_copy(ctx, s, slv->motion[l], q->field[l], (size_t)2 * n));
@@ -266,56 +269,71 @@ int nct_seq_get_region(nct_ctx* ctx, uint8_t* mask_out, int* age) {
     return NCT_OK;
 }
 
-// the reference once: upload, pyramid (main.cu:104-108), one VGG19 forward with all five taps kept channel-last; and the per-level state
-// rh0 x rw0: the reference as the caller holds it — larger than rh x rw only in a full-resolution sequence, which shrinks it on the device (SPEC §6.9)
-static int seq_prepare(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* ref_bgr, int rh0, int rw0, int rh, int rw, int sh, int sw) {
+// the references once, each: upload, pyramid (main.cu:104-108), one VGG19 forward with all five taps kept channel-last; and the per-level state. One reference
+// (nct_seq_begin) requests what it always did, in the same order; several (SPEC §6.18) also the label map of every level run
+// rh0 x rw0: a reference as the caller holds it — larger than rh x rw only in a full-resolution sequence, which shrinks it on the device (SPEC §6.9)
+static int seq_prepare(nct_ctx* ctx, pair_state* P, seq_state* q, int K, const uint8_t* const* refs_bgr, const int* rh0, const int* rw0, const int* rh, const int* rw, int sh, int sw) {
     hipStream_t s = ctx->stream;
-    level_sizes(sh, sw, q->ah, q->aw); level_sizes(rh, rw, q->bh, q->bw);
+    level_sizes(sh, sw, q->ah, q->aw);
+    for (int k = 0; k < K; ++k) level_sizes(rh[k], rw[k], q->bh[k], q->bw[k]);
     P->src = (uint8_t*)ctx->alloc((size_t)sh * sw * 3);
-    P->ref[0] = (uint8_t*)ctx->alloc((size_t)rh * rw * 3);
-    if (!P->src || !P->ref[0]) return NCT_ERR_HIP;
-    P->sh = sh; P->sw = sw; P->K = 1; P->rh[0] = rh; P->rw[0] = rw;
+    if (!P->src) return NCT_ERR_HIP;
+    for (int k = 0; k < K; ++k) if (!(P->ref[k] = (uint8_t*)ctx->alloc((size_t)rh[k] * rw[k] * 3))) return NCT_ERR_HIP;
+    P->sh = sh; P->sw = sw; P->K = K;
+    for (int k = 0; k < K; ++k) { P->rh[k] = rh[k]; P->rw[k] = rw[k]; }
     for (int l = 0; l < 5; ++l) {
-        const size_t n = (size_t)q->ah[l] * q->aw[l], nr = (size_t)q->bh[l] * q->bw[l];
-        if (l < 4 && !(q->rpyr[l] = (uint8_t*)ctx->alloc(nr * 3))) return NCT_ERR_HIP;
-        if (!(q->rfeat[l] = (float*)ctx->alloc(sizeof(float) * kTapC[4 - l] * nr))) return NCT_ERR_HIP;
+        const size_t n = (size_t)q->ah[l] * q->aw[l];
+        for (int k = 0; k < K; ++k) {
+            const size_t nr = (size_t)q->bh[k][l] * q->bw[k][l];
+            if (l < 4 && !(q->rpyr[k][l] = (uint8_t*)ctx->alloc(nr * 3))) return NCT_ERR_HIP;
+            if (!(q->rfeat[k][l] = (float*)ctx->alloc(sizeof(float) * kTapC[4 - l] * nr))) return NCT_ERR_HIP;
+        }
         if (l < q->prm.levels) {
             if (!(q->keep_x[l] = (double*)ctx->alloc(sizeof(double) * 6 * n)) || !(q->keep_lab[l] = (uint8_t*)ctx->alloc(n * 3))) return NCT_ERR_HIP;
+            if (K > 1 && !(q->keep_label[l] = (uint8_t*)ctx->alloc(n))) return NCT_ERR_HIP;
         }
     }
-    if (rh0 == rh && rw0 == rw) NCT_H2D(P->ref[0], ref_bgr, (size_t)rh * rw * 3);
-    else NCT_TRY(upload_shrunk(ctx, ref_bgr, rh0, rw0, P->ref[0], rh, rw));
+    for (int k = 0; k < K; ++k) {
+        if (rh0[k] == rh[k] && rw0[k] == rw[k]) NCT_H2D(P->ref[k], refs_bgr[k], (size_t)rh[k] * rw[k] * 3);
+        else NCT_TRY(upload_shrunk(ctx, refs_bgr[k], rh0[k], rw0[k], P->ref[k], rh[k], rw[k]));
+    }
     if (q->target()) {
         q->full.src = P->full_src = (uint8_t*)ctx->alloc((size_t)q->full.H * q->full.W * 3); q->full.out = P->full_out = (uint8_t*)ctx->alloc((size_t)q->full.H * q->full.W * 3);
         if (!P->full_src || !P->full_out) return NCT_ERR_HIP;
         P->full_h = q->full.H; P->full_w = q->full.W;
     }
-    const uint8_t* img = P->ref[0];
-    for (int l = 3; l >= 0; --l) {
-        NCT_TRY(nctk_resize_u8c3(ctx, s, img, q->bh[l + 1], q->bw[l + 1], q->rpyr[l], q->bh[l], q->bw[l]));
-        img = q->rpyr[l];
+    for (int k = 0; k < K; ++k) {
+        const uint8_t* img = P->ref[k];
+        for (int l = 3; l >= 0; --l) {
+            NCT_TRY(nctk_resize_u8c3(ctx, s, img, q->bh[k][l + 1], q->bw[k][l + 1], q->rpyr[k][l], q->bh[k][l], q->bw[k][l]));
+            img = q->rpyr[k][l];
+        }
+        float* taps_hwc[5];
+        for (int t = 0; t < 5; ++t) taps_hwc[t] = q->rfeat[k][4 - t];
+        NCT_TRY(nctk_vgg19_forward(ctx, s, P->ref[k], rh[k], rw[k], rw[k] * 3, 5, nullptr, nullptr, taps_hwc));
     }
-    float* taps_hwc[5];
-    for (int t = 0; t < 5; ++t) taps_hwc[t] = q->rfeat[4 - t];
-    NCT_TRY(nctk_vgg19_forward(ctx, s, P->ref[0], rh, rw, rw * 3, 5, nullptr, nullptr, taps_hwc));
     NCT_SYNC();
     return NCT_OK;
 }
 
-// what both nct_seq_begin* entry points (`who`) do once the image sizes are settled; full (nullable): the original frame size and the finish of a full-resolution sequence
-static int seq_open(nct_ctx* ctx, const char* who, const uint8_t* ref_bgr, int rh0, int rw0, int rh, int rw, int sh, int sw, const full_target* full, const nct_params* prm,
-                    const nct_seq_params* sp) {
+// what the nct_seq_begin* entry points (`who`) do once the image sizes are settled; full (nullable): the original frame size and the finish of a full-resolution sequence;
+// hold (nullable: the default): SPEC §6.18's parameter, which plays no part with one reference
+static int seq_open(nct_ctx* ctx, const char* who, int K, const uint8_t* const* refs_bgr, const int* rh0, const int* rw0, const int* rh, const int* rw, int sh, int sw,
+                    const full_target* full, const nct_params* prm, const nct_seq_params* sp, const nct_seq_hold* hold) {
     NCT_REQUIRE(sp->tau >= 0.0 && sp->tau < 1.0, "%s: tau must be in [0, 1) (got %g)", who, sp->tau);
     NCT_REQUIRE(sp->sigma > 0.0 && sp->sigma <= 1.7976931348623157e308, "%s: sigma must be finite and positive (got %g)", who, sp->sigma);
     NCT_REQUIRE(prm->levels >= 1 && prm->levels <= 5, "%s: levels must be in [1, 5] (got %d)", who, prm->levels);
+    nct_seq_hold hp;
+    if (hold) hp = *hold; else nct_seq_hold_default(&hp);
+    NCT_REQUIRE(nct_seq_hold_ok(hp.hold), "%s: hold must be finite and in [0, 2] (got %g)", who, hp.hold);
     NCT_TRY(nct_seq_end(ctx));                                   // a sequence that is still open is closed first
     pair_state* P = pair_of(ctx);
     drop_images(ctx, P);
     seq_state* q = new seq_state();
-    q->prm = *prm; q->tau = sp->tau; q->sigma = sp->sigma;
+    q->prm = *prm; q->tau = sp->tau; q->sigma = sp->sigma; q->hold = hp.hold;
     if (full) q->full = *full;
     P->seq = q;
-    const int rc = seq_prepare(ctx, P, q, ref_bgr, rh0, rw0, rh, rw, sh, sw);
+    const int rc = seq_prepare(ctx, P, q, K, refs_bgr, rh0, rw0, rh, rw, sh, sw);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); seq_free(ctx, P); drop_images(ctx, P); }
     return rc;
 }
@@ -325,7 +343,7 @@ int nct_seq_begin(nct_ctx* ctx, const uint8_t* ref_bgr, int rh, int rw, int sh, 
     NCT_REQUIRE(ref_bgr && prm && sp, "seq_begin: null pointer");
     NCT_REQUIRE(sh >= 17 && sw >= 17 && rh >= 17 && rw >= 17 && sh <= 4000 && sw <= 4000 && rh <= 4000 && rw <= 4000,
                 "seq_begin: image sides must be in [17, 4000] (got frames of %dx%d and a reference of %dx%d)", sw, sh, rw, rh);
-    return seq_open(ctx, "seq_begin", ref_bgr, rh, rw, rh, rw, sh, sw, nullptr, prm, sp);
+    return seq_open(ctx, "seq_begin", 1, &ref_bgr, &rh, &rw, &rh, &rw, sh, sw, nullptr, prm, sp, nullptr);
 }
 
 // SPEC §6.9: a sequence whose frames and reference arrive at their original size. Everything the sequence keeps lives on the working-size grids, as after
@@ -340,7 +358,46 @@ int nct_seq_begin_fullres(nct_ctx* ctx, const uint8_t* ref_bgr, int rh, int rw, 
     why = nct_working_size_rule(rh, rw, max_side, &rwh, &rww);
     if (why) return ctx->fail(NCT_ERR_INVALID, "seq_begin_fullres: reference %dx%d, max_side %d: %s", rw, rh, max_side, why);
     const full_target full{nullptr, sh, sw, nullptr, finish};    // the two images: seq_prepare
-    return seq_open(ctx, "seq_begin_fullres", ref_bgr, rh, rw, rwh, rww, wh, ww, &full, prm, sp);
+    return seq_open(ctx, "seq_begin_fullres", 1, &ref_bgr, &rh, &rw, &rwh, &rww, wh, ww, &full, prm, sp, nullptr);
+}
+
+// SPEC §6.18: the same over K references; the list's own checks, then seq_open
+void nct_seq_hold_default(nct_seq_hold* p) {
+    if (!p) return;
+    p->hold = 0.005;
+}
+
+static int seq_multi_list_check(nct_ctx* ctx, const char* who, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw, const nct_params* prm, const nct_seq_params* sp) {
+    NCT_REQUIRE(K >= 1 && K <= NCT_MAX_REFS, "%s: K must be in [1, %d] (got %d)", who, NCT_MAX_REFS, K);
+    NCT_REQUIRE(refs_bgr && rh && rw && prm && sp, "%s: null pointer", who);
+    for (int k = 0; k < K; ++k) NCT_REQUIRE(refs_bgr[k], "%s: reference %d is null", who, k);
+    return NCT_OK;
+}
+
+int nct_seq_begin_multi(nct_ctx* ctx, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw, int sh, int sw, const nct_params* prm, const nct_seq_params* sp,
+                        const nct_seq_hold* hold) {
+    NCT_CTX_ENTER();
+    NCT_TRY(seq_multi_list_check(ctx, "seq_begin_multi", K, refs_bgr, rh, rw, prm, sp));
+    NCT_REQUIRE(sh >= 17 && sw >= 17 && sh <= 4000 && sw <= 4000, "seq_begin_multi: image sides must be in [17, 4000] (got frames of %dx%d)", sw, sh);
+    for (int k = 0; k < K; ++k)
+        NCT_REQUIRE(rh[k] >= 17 && rw[k] >= 17 && rh[k] <= 4000 && rw[k] <= 4000, "seq_begin_multi: image sides must be in [17, 4000] (got reference %d of %dx%d)", k, rw[k], rh[k]);
+    return seq_open(ctx, "seq_begin_multi", K, refs_bgr, rh, rw, rh, rw, sh, sw, nullptr, prm, sp, hold);
+}
+
+int nct_seq_begin_multi_fullres(nct_ctx* ctx, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw, int sh, int sw, int max_side, int finish,
+                                const nct_params* prm, const nct_seq_params* sp, const nct_seq_hold* hold) {
+    NCT_CTX_ENTER();
+    NCT_TRY(seq_multi_list_check(ctx, "seq_begin_multi_fullres", K, refs_bgr, rh, rw, prm, sp));
+    NCT_REQUIRE(finish == NCT_FINISH_EXACT || finish == NCT_FINISH_UPSAMPLE, "seq_begin_multi_fullres: finish must be NCT_FINISH_EXACT (0) or NCT_FINISH_UPSAMPLE (1) (got %d)", finish);
+    int wh = 0, ww = 0, rwh[NCT_MAX_REFS], rww[NCT_MAX_REFS];
+    const char* why = nct_working_size_rule(sh, sw, max_side, &wh, &ww);
+    if (why) return ctx->fail(NCT_ERR_INVALID, "seq_begin_multi_fullres: frames of %dx%d, max_side %d: %s", sw, sh, max_side, why);
+    for (int k = 0; k < K; ++k) {
+        why = nct_working_size_rule(rh[k], rw[k], max_side, &rwh[k], &rww[k]);
+        if (why) return ctx->fail(NCT_ERR_INVALID, "seq_begin_multi_fullres: reference %d of %dx%d, max_side %d: %s", k, rw[k], rh[k], max_side, why);
+    }
+    const full_target full{nullptr, sh, sw, nullptr, finish};    // the two images: seq_prepare
+    return seq_open(ctx, "seq_begin_multi_fullres", K, refs_bgr, rh, rw, rwh, rww, wh, ww, &full, prm, sp, hold);
 }
 
 // a frame of the open sequence onto the device: into P->src, or (SPEC §6.9) at its original size into full_src and from there shrunk into P->src
@@ -349,25 +406,24 @@ static int seq_upload_frame(nct_ctx* ctx, pair_state* P, seq_state* q, const uin
     return upload_shrunk(ctx, src_bgr, q->full.H, q->full.W, P->src, P->sh, P->sw, P->full_src);
 }
 
-int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels) {
-    return nct_seq_frame_region_levels(ctx, src_bgr, out_bgr, timing, levels, seq_levels, nullptr);
-}
-
-// region_levels (nullable; SPEC §6.13): where a masked frame's mixed maps and level masks go
-int nct_seq_frame_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels,
-                                const nct_region_levels* region_levels) {
+// A full frame of the open sequence, the body of every nct_seq_frame*_levels form. mlv (nullable): the level report — a pair's (as_pair: it came as nct_pair_levels, which
+// describes one reference) or the list's; color (nullable): the colour stage's maps; hold_levels (nullable; SPEC §6.18): the held selection's report
+static int seq_frame_run(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_multi_levels* mlv, const nct_color_stages* const* color,
+                         bool as_pair, const nct_seq_levels* seq_levels, const nct_region_levels* region_levels, const nct_seq_hold_levels* hold_levels) {
     NCT_CTX_ENTER();
     pair_state* P = (pair_state*)ctx->pair;
     if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_frame: no sequence is open (nct_seq_begin first)");
     NCT_REQUIRE(src_bgr && out_bgr, "seq_frame: null image");
     seq_state* q = P->seq;
-    NCT_REQUIRE(!(q->target() && levels), "seq_frame_levels: levels must be NULL in a full-resolution sequence (its result[] arrays have no single size); seq_levels reports the working-size maps");
+    NCT_REQUIRE(!(q->target() && as_pair), "seq_frame_levels: levels must be NULL in a full-resolution sequence (its result[] arrays have no single size); seq_levels reports the working-size maps");
+    NCT_REQUIRE(!(as_pair && P->K > 1), "seq_frame_levels: nct_pair_levels describes a pair; a sequence over several references reports through nct_seq_frame_multi_levels");
+    if (q->target() && mlv) for (int l = 0; l < 5; ++l)
+        NCT_REQUIRE(!mlv->result[l], "seq_frame_multi_levels: levels->result[] must be NULL in a full-resolution sequence (the arrays have no single size)");
+    NCT_REQUIRE(!(q->target() && color), "seq_frame_multi_stage_levels: color must be NULL in a full-resolution sequence");
     // a level without a field (motion off, a first frame, tau == 0) reports zeros
     if (seq_levels) for (int l = 0; l < q->prm.levels; ++l) if (seq_levels->motion[l]) memset(seq_levels->motion[l], 0, sizeof(int16_t) * 2 * (size_t)q->ah[l] * q->aw[l]);
     int rc = seq_upload_frame(ctx, P, q, src_bgr);
-    const nct_multi_levels m = levels ? multi_levels_of(*levels) : nct_multi_levels{};
-    run_extras x; x.fin = q->target(); x.seq = q; x.slv = seq_levels;
-    if (levels) { x.lv = &m; x.color = levels->color; }
+    run_extras x; x.fin = q->target(); x.seq = q; x.slv = seq_levels; x.lv = mlv; x.color = color; x.hlv = hold_levels;
     nct_ref_region_levels qlv;
     if (region_levels) { qlv = ref_region_levels_of(*region_levels); x.qlv = &qlv; }
     if (region_levels && !P->mask && !q->model_rows) x.refusal = "seq_frame: region levels asked for, but no region mask is set (nct_seq_set_region first)";
@@ -380,6 +436,28 @@ int nct_seq_frame_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* o
     NCT_D2H(out_bgr, P->full_out, (size_t)q->full.H * q->full.W * 3);
     NCT_SYNC();
     return NCT_OK;
+}
+
+int nct_seq_frame_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels) {
+    return nct_seq_frame_region_levels(ctx, src_bgr, out_bgr, timing, levels, seq_levels, nullptr);
+}
+
+// region_levels (nullable; SPEC §6.13): where a masked frame's mixed maps and level masks go
+int nct_seq_frame_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels,
+                                const nct_region_levels* region_levels) {
+    if (!levels) return seq_frame_run(ctx, src_bgr, out_bgr, timing, nullptr, nullptr, false, seq_levels, region_levels, nullptr);
+    const nct_multi_levels m = multi_levels_of(*levels);
+    return seq_frame_run(ctx, src_bgr, out_bgr, timing, &m, levels->color, true, seq_levels, region_levels, nullptr);
+}
+
+int nct_seq_frame_multi_stage_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_multi_levels* levels,
+                                     const nct_color_stages* const* color, const nct_seq_levels* seq_levels, const nct_seq_hold_levels* hold_levels) {
+    return seq_frame_run(ctx, src_bgr, out_bgr, timing, levels, color, false, seq_levels, nullptr, hold_levels);
+}
+
+int nct_seq_frame_multi_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_multi_levels* levels, const nct_seq_levels* seq_levels,
+                               const nct_seq_hold_levels* hold_levels) {
+    return seq_frame_run(ctx, src_bgr, out_bgr, timing, levels, nullptr, false, seq_levels, nullptr, hold_levels);
 }
 
 int nct_seq_frame(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing) {
@@ -416,6 +494,13 @@ static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out
             if (l == top) std::swap(q->keep_x[l], q->warp_x);
             else NCT_HIP(hipMemcpyAsync(q->keep_x[l], q->warp_x, sizeof(double) * 6 * n, hipMemcpyDeviceToDevice, s));
             NCT_TRY(nctk_seq_pack(ctx, s, q->keep_lab[l], (int)n, q->keep_pk[l]));
+            if (q->keep_label[l]) {
+                // several references (SPEC §6.18 rule 7): the kept labels follow the field too, out of place through scratch of the call
+                DevBuf<uint8_t> carried(ctx, n);
+                if (!carried.ok()) return NCT_ERR_HIP;
+                NCT_TRY(nctk_label_carry(ctx, s, q->keep_label[l], h, w, q->field[l], carried));
+                NCT_HIP(hipMemcpyAsync(q->keep_label[l], carried, n, hipMemcpyDeviceToDevice, s));
+            }
         }
         if (slv) {
             if (slv->ab_blend[l]) NCT_HIP(hipMemcpyAsync(slv->ab_blend[l], q->keep_x[l], sizeof(double) * 6 * n, hipMemcpyDeviceToHost, s));

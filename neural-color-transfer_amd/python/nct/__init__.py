@@ -112,6 +112,16 @@ SIGNATURES = {
     "nct_seq_params_default": (None, [C.c_void_p]),
     "nct_seq_begin": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nct_seq_begin_fullres": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nct_seq_hold_default": (None, [C.c_void_p]),
+    "nct_seq_begin_multi": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_begin_multi_fullres": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "nct_seq_frame_multi_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_frame_multi_stage_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_select_reference_hold": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_select_reference_hold_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p]),
     "nct_seq_frame_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_propagate": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p]),
@@ -552,6 +562,22 @@ class SeqParams(C.Structure):
         p = SeqParams()
         lib().nct_seq_params_default(C.byref(p))
         return p
+
+
+class SeqHold(C.Structure):
+    """struct nct_seq_hold (include/nct.h; SPEC §6.18)."""
+    _fields_ = [("hold", C.c_double)]
+
+    @staticmethod
+    def default():
+        p = SeqHold()
+        lib().nct_seq_hold_default(C.byref(p))
+        return p
+
+
+class SeqHoldLevels(C.Structure):
+    """struct nct_seq_hold_levels (include/nct.h)."""
+    _fields_ = [("free_label", C.c_void_p * 5), ("margin", C.c_void_p * 5)]
 
 
 class SeqLevels(C.Structure):
@@ -1228,6 +1254,7 @@ class Context:
         self._chk(self._l.nct_seq_begin(self._h, r.reshape(-1, 3), r.shape[0], r.shape[1], int(src_shape[0]), int(src_shape[1]), C.addressof(prm), C.addressof(sp)))
         self._seq_shapes = (tuple(src_shape[:2]), r.shape[:2], prm.levels)
         self._seq_work = None
+        self._seq_multi = (tuple(src_shape[:2]), [r.shape[:2]])
 
     def seq_begin_fullres(self, ref_bgr, src_shape, max_side=1000, finish=0, params=None, tau=None, sigma=None):
         """nct_seq_begin_fullres (SPEC §6.9): frames of src_shape[:2] and the reference arrive at their original size and are shrunk to working_size(..., max_side) on
@@ -1243,6 +1270,113 @@ class Context:
                                                 C.addressof(prm), C.addressof(sp)))
         self._seq_shapes = (tuple(src_shape[:2]), r.shape[:2], prm.levels)
         self._seq_work = (working_size(int(src_shape[0]), int(src_shape[1]), max_side), working_size(r.shape[0], r.shape[1], max_side))
+        self._seq_multi = (self._seq_work[0], [self._seq_work[1]])
+
+    # ---- sequences over several references (SPEC §6.18)
+    def _seq_multi_args(self, params, tau, sigma, hold):
+        prm = params or Params.default()
+        sp = SeqParams.default()
+        if tau is not None:
+            sp.tau = tau
+        if sigma is not None:
+            sp.sigma = sigma
+        hp = None
+        if hold is not None:
+            hp = SeqHold(); hp.hold = hold
+        return prm, sp, hp
+
+    def seq_begin_multi(self, refs_bgr, src_shape, params=None, tau=None, sigma=None, hold=None):
+        """nct_seq_begin_multi: prepare a list of references once for frames of src_shape[:2]; hold None passes NULL (nct_seq_hold_default)"""
+        K, keep, ptrs, hs, ws = self._ref_list(refs_bgr)
+        prm, sp, hp = self._seq_multi_args(params, tau, sigma, hold)
+        self._chk(self._l.nct_seq_begin_multi(self._h, K, ptrs, hs, ws, int(src_shape[0]), int(src_shape[1]), C.addressof(prm), C.addressof(sp),
+                                              None if hp is None else C.addressof(hp)))
+        self._seq_shapes = (tuple(src_shape[:2]), keep[0].shape[:2], prm.levels)
+        self._seq_work = None
+        self._seq_multi = (tuple(src_shape[:2]), [a.shape[:2] for a in keep])
+
+    def seq_begin_multi_fullres(self, refs_bgr, src_shape, max_side=1000, finish=0, params=None, tau=None, sigma=None, hold=None):
+        """nct_seq_begin_multi_fullres: seq_begin_fullres over a list of references"""
+        K, keep, ptrs, hs, ws = self._ref_list(refs_bgr)
+        prm, sp, hp = self._seq_multi_args(params, tau, sigma, hold)
+        self._chk(self._l.nct_seq_begin_multi_fullres(self._h, K, ptrs, hs, ws, int(src_shape[0]), int(src_shape[1]), int(max_side), int(finish), C.addressof(prm),
+                                                      C.addressof(sp), None if hp is None else C.addressof(hp)))
+        work = working_size(int(src_shape[0]), int(src_shape[1]), max_side)
+        rwork = [working_size(a.shape[0], a.shape[1], max_side) for a in keep]
+        self._seq_shapes = (tuple(src_shape[:2]), keep[0].shape[:2], prm.levels)
+        self._seq_work = (work, rwork[0])
+        self._seq_multi = (work, rwork)
+
+    def seq_frame_multi_levels(self, src_bgr, want_color=True):
+        """nct_seq_frame_multi[_stage]_levels -> (result, dict): multi_run_levels' lists at the working size ("ann" … "ref_err" as [k][l]; "label", "guide", "err", "result"
+        as [l]; "labels"), seq_frame_levels' "ab_blend", "tau_map" and "motion" per level that ran, the held selection's "free_label" and "margin" per level that ran, with
+        want_color "color" (a dict per level that ran, as seq_frame_levels reports it) and "timing". A full-resolution sequence reports neither "result" nor "color"."""
+        s = self._seq_frame_arg(src_bgr, "seq_frame_multi_levels")
+        if getattr(self, "_seq_multi", None) is None:
+            raise NctError(-5, "seq_frame_multi_levels: no sequence is open (seq_begin_multi first)")
+        (H, W), rshapes = self._seq_multi
+        levels = self._seq_shapes[2]
+        full = self._seq_work is not None
+        self._pair_shape, self._multi_shapes = (H, W, 3), [tuple(r) + (3,) for r in rshapes]
+        keep, lv = self._multi_levels_arrays()
+        adims = keep["adims"]
+        if full:
+            for l in range(5):
+                lv.result[l] = None
+            del keep["result"]
+        keep["ab_blend"] = [np.zeros((2, d[0] * d[1], 3)) for d in adims[:levels]]
+        keep["tau_map"] = [np.zeros(d) for d in adims[:levels]]
+        keep["motion"] = [np.zeros(d + (2,), np.int16) for d in adims[:levels]]
+        keep["free_label"] = [np.zeros(d, np.uint8) for d in adims[:levels]]
+        keep["margin"] = [np.zeros(d) for d in adims[:levels]]
+        sl, hl = SeqLevels(), SeqHoldLevels()
+        for l in range(levels):
+            sl.ab_blend[l] = keep["ab_blend"][l].ctypes.data; sl.tau_map[l] = keep["tau_map"][l].ctypes.data; sl.motion[l] = keep["motion"][l].ctypes.data
+            hl.free_label[l] = keep["free_label"][l].ctypes.data; hl.margin[l] = keep["margin"][l].ctypes.data
+        out = np.empty_like(s)
+        tm = PairTiming()
+        if want_color and not full:
+            color, structs = [], []
+            for (ah, aw) in adims[:levels]:
+                d = {"ab_local": np.empty((2, ah * aw, 3)), "ab_nonlocal": np.empty((2, ah * aw, 3)), "ab_up": np.empty((2, H * W, 3)),
+                     "roughness": np.empty(H * W), "ab_wls": np.empty((2, H * W, 3)), "cg_iters": np.zeros(3, np.int32), "wls_iters": np.zeros(6, np.int32)}
+                color.append(d)
+                structs.append(ColorStages(*[d[k].ctypes.data for k in ("ab_local", "ab_nonlocal", "ab_up", "roughness", "ab_wls", "cg_iters", "wls_iters")]))
+            cptr = (C.c_void_p * 5)(*[C.addressof(structs[i]) if i < levels else None for i in range(5)])
+            self._chk(self._l.nct_seq_frame_multi_stage_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv), cptr, C.addressof(sl), C.addressof(hl)))
+            keep["color"] = color
+        else:
+            self._chk(self._l.nct_seq_frame_multi_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv), C.addressof(sl), C.addressof(hl)))
+        keep["timing"] = tm.as_dict()
+        return out, keep
+
+    def select_reference_hold(self, errs, guides, prev_label, lab, lab_prev, field=None, hold=0.0, sigma=10.0, dev=False, want=("label", "guide", "err", "free_label", "margin")):
+        """nct_select_reference_hold (dev: its _dev form on arena blocks): K error maps [h, w] fp32, K guidance images [h, w, 3] (or None), the kept labels [h, w], the two
+        frames' 8-bit Lab level images, a field int16 [h, w, 2] or None -> dict of the outputs named in `want` (the others are passed as NULL)"""
+        es = [np.ascontiguousarray(e, np.float32) for e in errs]
+        gs = None if guides is None else [np.ascontiguousarray(g, np.uint8) for g in guides]
+        K = len(es)
+        h, w = es[0].shape if K else (1, 1)
+        pl, l1, l0 = np.ascontiguousarray(prev_label, np.uint8), np.ascontiguousarray(lab, np.uint8), np.ascontiguousarray(lab_prev, np.uint8)
+        f = None if field is None else np.ascontiguousarray(field, np.int16)
+        want = [k for k in want if not (k == "guide" and gs is None)]
+        spec = {"label": ((h, w), np.uint8), "guide": ((h, w, 3), np.uint8), "err": ((h, w), np.float32), "free_label": ((h, w), np.uint8), "margin": ((h, w), np.float64)}
+        order = ("label", "guide", "err", "free_label", "margin")
+        if not dev:
+            ep = (C.c_void_p * max(K, 1))(*[e.ctypes.data for e in es])
+            gp = None if gs is None else (C.c_void_p * max(K, 1))(*[g.ctypes.data for g in gs])
+            outs = {k: np.empty(*spec[k]) for k in want}
+            self._chk(self._l.nct_select_reference_hold(self._h, ep, gp, K, h, w, pl.ctypes.data, l1.ctypes.data, l0.ctypes.data, None if f is None else f.ctypes.data,
+                                                        float(hold), float(sigma), *[_ptr(outs.get(k)) for k in order]))
+            return outs
+        de = [self.dev_upload(e) for e in es]
+        dg = [] if gs is None else [self.dev_upload(g) for g in gs]
+        ins = [self.dev_upload(pl), self.dev_upload(l1), self.dev_upload(l0)] + ([] if f is None else [self.dev_upload(f)])
+        dout = {k: self.dev_alloc(int(np.prod(spec[k][0])) * np.dtype(spec[k][1]).itemsize) for k in want}
+        with self._blocks(de + dg + ins + list(dout.values())):
+            self._chk(self._l.nct_select_reference_hold_dev(self._h, (C.c_void_p * max(K, 1))(*de), None if gs is None else (C.c_void_p * max(K, 1))(*dg), K, h, w, ins[0], ins[1],
+                                                            ins[2], None if f is None else ins[3], float(hold), float(sigma), *[dout.get(k) for k in order]))
+            return {k: self.dev_download(dout[k], *spec[k]) for k in want}
 
     def seq_frame(self, src_bgr, want_timing=False):
         s = np.ascontiguousarray(src_bgr, np.uint8)
@@ -1732,6 +1866,7 @@ class Context:
         self._chk(self._l.nct_seq_end(self._h))
         self._seq_shapes = None
         self._seq_work = None
+        self._seq_multi = None
 
     def seq_set_motion(self, radius0=None, radius=None, penalty=None, off=False):
         """nct_seq_set_motion (SPEC §6.4): motion compensation of the open sequence from the next frame on; values left out are nct_seq_motion_default's (3, 1, 1).
