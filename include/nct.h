@@ -140,7 +140,10 @@ int nct_maxpool2x2(nct_ctx* ctx, const float* in_chw, int C, int H, int W, float
 /* ---- parameters: `Config` (ColorTransfer/Config.h:55-98) + the constants hard-coded in transfer_color_single_bds
  * (main.cu:64-68: iter = 10). nct_params_default fills Config::Config()'s values (bds 2.0, eps 0.60, nl 2.0, l 0.125,
  * w 0.024, clusters 10, k 8, patch 3, alpha 1.2) — the help strings at main.cu:40-43 quote different numbers; the
- * constructor is what runs. `seed` keys the counter-based RNG (PatchMatch random search, k-means centres). */
+ * constructor is what runs. `seed` keys the counter-based RNG (PatchMatch random search, k-means centres).
+ * The solvers' domain: eps, nonlocal_weight, local_weight, wls_lambda_init and wls_alpha must each be finite and > 0 (T1 divides by eps, S1 and S2 take roots of the
+ * weights, and |dL|^wls_alpha is evaluated for an exponent > 0 only), bds_weight finite and >= 0; cluster_num lies in [1, 16], k_num is 8 and patch_size 3. Every entry
+ * point that takes the struct returns NCT_ERR_INVALID for anything else, with a message that names the field, before it enqueues anything. */
 typedef struct nct_params {
     double bds_weight, eps, nonlocal_weight, local_weight, wls_lambda_init;
     int cluster_num, k_num, patch_size;
@@ -181,7 +184,8 @@ int nct_resize_f64c3(nct_ctx* ctx, const double* src, int sh, int sw, double* ds
 
 /* ---- C1: k-means labels of the coarsest S features — main.cu:139-168 -> ColorTransfer::clusterFeastures
  * (ColorTransfer.cpp:355-395; cvflann k-means, branching K, `iters` Lloyd steps). feat_chw: UN-normalised conv5_1 of S;
- * labels: h*w ints in [0, *nlabels). */
+ * labels: h*w ints in [0, *nlabels). K lies in [1, 16]. K == 1 is this library's own rule, not the reference's, whose FLANN refuses a branching below 2
+ * (Flann/kmeans_index.h:370-372): one cluster, every label 0, *nlabels = 1. */
 int nct_cluster_features(nct_ctx* ctx, const float* feat_chw, int C, int h, int w, int K, int iters, uint64_t seed, int* labels, int* nlabels);
 
 /* ---- K1: kNN graph in Lab — ColorTransfer::findKnns (ColorTransfer.cpp:397-423), called main.cu:359.

@@ -147,6 +147,7 @@ int nct_local_color_transfer(nct_ctx* ctx, const float* err, const uint8_t* s_bg
     NCT_CTX_ENTER();
     NCT_REQUIRE(err && s_bgr_level && g_bgr_level && s_bgr_full && knn_id && knn_w && prm && out_bgr_full, "local_color_transfer: null pointer");
     NCT_REQUIRE(h > 0 && w > 0 && H >= h && W >= w && layer >= 0 && layer <= 4, "local_color_transfer: bad geometry");
+    NCT_TRY(nct_params_check(ctx, "local_color_transfer", *prm));
     const size_t n = (size_t)h * w, N = (size_t)H * W;
     DevBuf<float> derr(ctx, n);
     DevBuf<uint8_t> sl(ctx, n * 3), gl(ctx, n * 3), sf(ctx, N * 3), slab(ctx, n * 3), glab(ctx, n * 3), sflab(ctx, N * 3), olab(ctx, N * 3), obgr(ctx, N * 3);
@@ -179,6 +180,7 @@ int nct_color_finish(nct_ctx* ctx, const double* ab, int h, int w, int work_h, i
     NCT_REQUIRE(ab && s_bgr_full && prm && out_bgr_full, "color_finish: null pointer");
     NCT_REQUIRE(h > 0 && w > 0 && work_h >= h && work_w >= w && H >= h && W >= w, "color_finish: bad geometry (level %dx%d, working %dx%d, target %dx%d)", w, h, work_w, work_h, W, H);
     NCT_REQUIRE(H <= NCT_FINISH_MAX_SIDE && W <= NCT_FINISH_MAX_SIDE && (long long)H * W <= NCT_FINISH_MAX_PIXELS, "color_finish: target %dx%d above 16384 per side or 2^26 pixels", W, H);
+    NCT_TRY(nct_params_check(ctx, "color_finish", *prm));
     const size_t n = (size_t)h * w, N = (size_t)H * W;
     DevBuf<double> x(ctx, 6 * n);
     DevBuf<uint8_t> sf(ctx, N * 3), sflab(ctx, N * 3), olab(ctx, N * 3), obgr(ctx, N * 3);
@@ -201,6 +203,7 @@ static int finish_up_host(nct_ctx* ctx, bool is_guided, const double* ab_wls, co
                           const nct_region_params* region, const nct_guided_params* guided, const nct_params* prm, uint8_t* out_bgr_full) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(prm && (guided || !is_guided), "%s: null pointer", nct_finish_up_name(is_guided, mask != nullptr));
+    NCT_TRY(nct_params_check(ctx, nct_finish_up_name(is_guided, mask != nullptr), *prm));
     const nct_finish_up host{s_bgr_full, H, W, out_bgr_full, nct_cube_form(*prm), is_guided ? guided->sigma : 0.0, mask, region ? region->protect : 0};
     NCT_TRY(nctk_finish_up_check(ctx, is_guided, ab_wls, lab_work, h, w, host));      // before anything is reserved
     const size_t n = (size_t)h * w, N = (size_t)H * W;

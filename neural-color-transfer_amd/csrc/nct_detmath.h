@@ -74,7 +74,8 @@ NCT_HD double nct_log(double x) {
     return (ed * LN2_HI + lm) + ed * LN2_LO;
 }
 
-// pow(x, y) for x >= 0 (x == 0 -> 0 for y > 0), as used for |dL|^alpha
+// pow(x, y) for x >= 0 and y > 0 (x == 0 -> 0), as used for |dL|^alpha. Its domain is y > 0: at y == 0 it returns 0 for x == 0 where C's pow gives 1, which is
+// why every entry point refuses a wls_alpha that is not finite and > 0 (include/nct.h at nct_params)
 NCT_HD double nct_pow(double x, double y) {
     if (x <= 0.0) return 0.0;
     if (x == 1.0) return 1.0;

@@ -250,6 +250,9 @@ static int finish_up_dev(nct_ctx* ctx, bool is_guided, const double* d_ab_wls, c
                          const nct_region_params* region, const nct_guided_params* guided, const nct_params* prm, uint8_t* d_out_bgr_full) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(prm && (guided || !is_guided), "%s_dev: null pointer", nct_finish_up_name(is_guided, d_mask != nullptr));
+    char who[64];
+    snprintf(who, sizeof who, "%s_dev", nct_finish_up_name(is_guided, d_mask != nullptr));
+    NCT_TRY(nct_params_check(ctx, who, *prm));
     const nct_finish_up up{d_s_bgr_full, H, W, d_out_bgr_full, nct_cube_form(*prm), is_guided ? guided->sigma : 0.0, d_mask, region ? region->protect : 0};
     NCT_TRY(nctk_finish_up_check(ctx, is_guided, d_ab_wls, d_lab_work, h, w, up));      // a guided call is never read as a plain one, whatever its sigma
     return nctk_finish_up(ctx, ctx->stream, d_ab_wls, d_lab_work, h, w, up);

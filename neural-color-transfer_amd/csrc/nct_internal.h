@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdarg>
+#include <cmath>
 #include <string>
 #include <vector>
 #include "../../include/nct.h"
@@ -191,6 +192,16 @@ int nctk_s1_solve(nct_ctx* ctx, hipStream_t s, const nct_s1_graph& g, const int*
 struct nct_color_params { double eps, nonlocal_weight, local_weight, wls_lambda_init, wls_alpha, k_num; };
 static inline nct_color_params nct_color_params_of(const nct_params& p) { return {p.eps, p.nonlocal_weight, p.local_weight, p.wls_lambda_init, p.wls_alpha, (double)p.k_num}; }
 static inline int nct_cube_form(const nct_params& p) { return (p.flags & NCT_FLAG_LAB2BGR_CUBE) ? 1 : 0; }   // the Lab -> BGR form of nctk_lab2bgr
+// the solvers' domain (include/nct.h at nct_params): T1 divides by eps, S1 takes roots of both weights, S2 of lambda, and nct_pow(., wls_alpha) is defined for an exponent
+// > 0; the vote weighs with bds_weight. One rule for every entry point (`who`) that takes the struct: the first field outside it is named, before anything is enqueued
+static inline int nct_params_check(nct_ctx* ctx, const char* who, const nct_params& p) {
+    const struct { const char* name; double v; bool zero_ok; } fields[] = {{"bds_weight", p.bds_weight, true}, {"eps", p.eps, false}, {"nonlocal_weight", p.nonlocal_weight, false},
+        {"local_weight", p.local_weight, false}, {"wls_lambda_init", p.wls_lambda_init, false}, {"wls_alpha", p.wls_alpha, false}};
+    for (const auto& f : fields)
+        if (!std::isfinite(f.v) || !(f.zero_ok ? f.v >= 0.0 : f.v > 0.0))
+            return ctx->fail(NCT_ERR_INVALID, "%s: %s must be finite and %s (got %g)", who, f.name, f.zero_ok ? ">= 0" : "> 0", f.v);
+    return NCT_OK;
+}
 struct nct_color_debug { double *ab_local, *ab_nonlocal, *ab_up, *rough, *ab_wls; int* cg_iters; int* wls_iters; };   // host pointers, all nullable
 // the largest finish target: S2's hierarchy stays within MG_MAXL levels (k_wls_mg.hip) and each of its arrays below 4 GB (6 fp64 right-hand sides: 3.2 GB)
 #define NCT_FINISH_MAX_SIDE 16384

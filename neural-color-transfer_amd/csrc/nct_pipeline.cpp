@@ -583,6 +583,7 @@ int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timin
     NCT_REQUIRE(!x.fin || P->K == 1 || x.seq, "process: no full-resolution finish with several references");      // but for a frame of an open sequence (SPEC §6.18)
     NCT_REQUIRE(prm->patch_size == 3 && prm->k_num == 8, "process: patch_size must be 3 and k_num 8 (Config.h:68-70)");
     NCT_REQUIRE(prm->cluster_num >= 1 && prm->cluster_num <= 16, "process: cluster_num out of range");
+    NCT_TRY(nct_params_check(ctx, "process", *prm));
     NCT_REQUIRE(prm->levels >= 1 && prm->levels <= 5, "process: levels must be in [1, 5] (got %d)", prm->levels);
     NCT_REQUIRE(!x.fin || ((!x.lv || x.seq) && !x.color), "process: no level intermediates with a full-resolution finish");     // a sequence's frame reports working-size maps only (nct_seq.cpp)
     NCT_REQUIRE(!x.color || P->K == 1 || x.seq, "process: nct_pair_levels describes a pair; several references report through nct_multi_levels");

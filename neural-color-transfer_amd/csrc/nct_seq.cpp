@@ -323,6 +323,7 @@ static int seq_open(nct_ctx* ctx, const char* who, int K, const uint8_t* const* 
     NCT_REQUIRE(sp->tau >= 0.0 && sp->tau < 1.0, "%s: tau must be in [0, 1) (got %g)", who, sp->tau);
     NCT_REQUIRE(sp->sigma > 0.0 && sp->sigma <= 1.7976931348623157e308, "%s: sigma must be finite and positive (got %g)", who, sp->sigma);
     NCT_REQUIRE(prm->levels >= 1 && prm->levels <= 5, "%s: levels must be in [1, 5] (got %d)", who, prm->levels);
+    NCT_TRY(nct_params_check(ctx, who, *prm));
     nct_seq_hold hp;
     if (hold) hp = *hold; else nct_seq_hold_default(&hp);
     NCT_REQUIRE(nct_seq_hold_ok(hp.hold), "%s: hold must be finite and in [0, 2] (got %g)", who, hp.hold);

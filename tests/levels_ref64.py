@@ -68,14 +68,16 @@ def chain_pyramid(img, sizes, resize):
     return pyr, worst
 
 
-def check_levels(dumps, src, ref, ws, bs, bds_weight, lib, levels=5, feat16=None, s1_maxit=None, lab2bgr_form=None):
+def check_levels(dumps, src, ref, ws, bs, bds_weight, lib, levels=5, feat16=None, s1_maxit=None, lab2bgr_form=None, prm=None, cluster_num=10):
     """Runs checks 1-5 at every level that ran (and 6 when `dumps` holds "color"). lib: the library that made the dumps (the oracle or an nct.Context); its
     resize_u8c3 builds the pyramids (each step checked against the exact bilinear value), its bgr2lab the Lab bytes and its lab2bgr the expected result image —
     both conversions are pinned to ref64 over all 2^24 inputs (tests/test_ref64_oracle.py::check_bgr2lab_all, check_lab2bgr_all). The kNN graph is ref64's,
     over the dumped labels, which must be ref64.kmeans_labels of the source's float64 conv5_1 (with a margin of KM_VGG_MARGIN). s1_maxit: NCT_S1_MAXIT of the run — S1's iterate must then equal ref64's literal CGNR from the
-    dumped T1 guess to 1e-10. lab2bgr_form: the Lab -> BGR form the run used (1 under NCT_FLAG_LAB2BGR_CUBE). Returns {check: largest deviation}."""
+    dumped T1 guess to 1e-10. lab2bgr_form: the Lab -> BGR form the run used (1 under NCT_FLAG_LAB2BGR_CUBE). prm, cluster_num: the colour parameters and the cluster
+    count of the run (None: test_ref64_oracle.COLOR_DEFAULTS; 10). Returns {check: largest deviation}."""
     from test_gpu_vs_ref64 import _chan, _check_after_s1, _lab2bgr_of
-    from test_ref64_oracle import S1_CAP_RATIO
+    from test_ref64_oracle import COLOR_DEFAULTS, S1_CAP_RATIO
+    prm = COLOR_DEFAULTS if prm is None else prm
     src, ref = np.asarray(src, np.uint8), np.asarray(ref, np.uint8)
     H, W = src.shape[:2]
     RH, RW = ref.shape[:2]
@@ -95,7 +97,7 @@ def check_levels(dumps, src, ref, ws, bs, bds_weight, lib, levels=5, feat16=None
     if "color" in dumps:
         flab = lib.bgr2lab(src).reshape(-1, 3) / 255.0
         # C1: the labels the colour stages used are the k-means of the source's conv5_1, here computed in float64 from the image alone
-        el, en, margin = ref64.kmeans_labels(s_raw, 10, 11, 1)
+        el, en, margin = ref64.kmeans_labels(s_raw, cluster_num, 11, 1)
         assert margin >= KM_VGG_MARGIN, f"k-means margin {margin:.3g}: the pair cannot tell a label error from the float VGG's rounding"
         assert int(dumps["labels"].max()) + 1 == en and np.array_equal(dumps["labels"], el), "labels differ from ref64.kmeans_labels"
         note("km_margin_min", -margin)
@@ -152,10 +154,11 @@ def check_levels(dumps, src, ref, ws, bs, bds_weight, lib, levels=5, feat16=None
             slab_u8, glab_u8 = lib.bgr2lab(spyr[l]), lib.bgr2lab(dumps["guide"][l])
             labels = dumps["labels"]
             ids, kw = ref64.knn_graph(slab_u8, labels, int(labels.max()) + 1, g["knn_samples"])
-            ea, eb = ref64.local_stats(slab_u8, glab_u8, 0.60)
+            ea, eb = ref64.local_stats(slab_u8, glab_u8, prm["eps"])
             assert _ulp_close(gs["ab_local"][0], ea, 2) and _ulp_close(gs["ab_local"][1], eb, 2), f"level {l}: T1"
             slab, glab = slab_u8.reshape(-1, 3) / 255.0, glab_u8.reshape(-1, 3) / 255.0
-            system = ref64.s1_system(slab, glab, ref64.err_weight(dumps["err"][l]), ids, kw, ah, aw, 0.125, 1.2, H * W / (ah * aw))
+            system = ref64.s1_system(slab, glab, ref64.err_weight(dumps["err"][l]), ids, kw, ah, aw, prm["local_weight"], prm["wls_alpha"], H * W / (ah * aw),
+                                     nonlocal_weight=prm["nonlocal_weight"])
             cap = s1_maxit if s1_maxit else (50 if l == 4 else 100)
             for c in range(3):
                 A, rhs = system[c]
@@ -174,5 +177,5 @@ def check_levels(dumps, src, ref, ws, bs, bds_weight, lib, levels=5, feat16=None
                     assert S1_CAP_RATIO[0] <= fg / fr <= S1_CAP_RATIO[1] or abs(fg - fr) <= 1e-4 * (f0 - fr), (l, c, f0, fg, fr)
                     note("s1_ratio_dev", abs(fg / fr - 1.0))
                     note("s1_rel_descent_dev", abs(fg - fr) / (f0 - fr))
-            _check_after_s1(_lab2bgr_of(lib), gs, dumps["result"][l], H, W, ah, aw, flab, form=lab2bgr_form, step_bound=True)
+            _check_after_s1(_lab2bgr_of(lib), gs, dumps["result"][l], H, W, ah, aw, flab, form=lab2bgr_form, step_bound=True, prm=prm)
     return stats

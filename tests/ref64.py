@@ -605,6 +605,8 @@ def kmeans_labels(feat_chw, K=10, iters=11, seed=1, exact=False, normalized=Fals
     """clusterFeastures (ColorTransfer.cpp:355-395): cvflann::hierarchicalClustering<L2<float>> with KMeansIndexParams(K, 11, FLANN_CENTERS_RANDOM) on the
     normalised conv5_1 features (normalize, rounded to the float buffer the reference clusters); the labels are the root's split, computeClustering
     (Flann/kmeans_index.h:700-880):
+      - K == 1 is one cluster: every label 0, one label, margin inf. The reference's FLANN refuses a branching below 2 (Flann/kmeans_index.h:370-372), so
+        this is the library's own rule (nct_cluster_features, include/nct.h), not the reference's;
       - n < K, or fewer than K distinct centres found, leaves the root a leaf: one label (:705-710, :716-722);
       - chooseCentersRandom (:108-135): candidates in the order of _perm_splitmix (SPEC.md §4), skipping one whose float distance to an earlier centre is
         below 1e-16;
@@ -623,7 +625,7 @@ def kmeans_labels(feat_chw, K=10, iters=11, seed=1, exact=False, normalized=Fals
     n = h * w
     pts = np.ascontiguousarray(f.reshape(C, n).T)
     labels = np.zeros(n, np.int32)
-    if n < K:
+    if n < K or K == 1:
         return done(labels.reshape(h, w), 1, np.inf)
     dist = (lambda p, c: ((p.astype(np.float64)[:, None, :] - np.asarray(c, np.float64)[None]) ** 2).sum(-1)) if exact else _l2_float
     perm = _perm_splitmix(n, seed)

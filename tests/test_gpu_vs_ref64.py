@@ -5,7 +5,7 @@ import pytest
 import ref64
 import synth
 from test_gpu_color import _level_case
-from test_ref64_oracle import S1_CAP_RATIO, _ulp_close, _vote_image_agrees, _nnf
+from test_ref64_oracle import COLOR_DEFAULTS, S1_CAP_RATIO, _ulp_close, _vote_image_agrees, _nnf
 
 pytestmark = pytest.mark.gpu
 
@@ -41,14 +41,15 @@ def _chan(ab, c):
     return np.r_[ab[0][:, c], ab[1][:, c]]
 
 
-def _check_after_s1(lab2bgr, gs, go, H, W, h, w, flab, form=None, step_bound=False):
+def _check_after_s1(lab2bgr, gs, go, H, W, h, w, flab, form=None, step_bound=False, prm=COLOR_DEFAULTS, stats=None):
     """U1, roughness, S2 and A1, each against ref64 applied to the GPU's previous stage; form: the Lab -> BGR form of the run (None: the default, piecewise).
     The result image must be exactly lab2bgr(lab, form) — the library's own conversion, pinned over all 2^24 inputs by check_lab2bgr_all — of ref64's Lab
     bytes, and within 1 LSB of ref64.lab2bgr of them outside the cube form's far-out channels. The upsampled
     coefficients lie within 1e-7 relative of the pure float64 mapping, or — step_bound, for the large ratios of a whole pyramid (2x2 -> 17x17), where an
     interpolant near zero between large coefficients breaks a relative bound — within what OpenCV's float table allows in each of the two passes: the float
     source coordinate (half an ulp of the largest coordinate) times the largest step between neighbours, plus the float weights 1 - fx, fx (half an ulp of 1
-    each) times the largest coefficient; plus the 4 ulp above. Returns
+    each) times the largest coefficient; plus the 4 ulp above. prm: the colour parameters of the run (S2 reads wls_lambda_init and wls_alpha); stats
+    (a dict, optional) receives "s2_frac", the largest |S2 - exact| / (atol + rtol |exact|). Returns
     the number of pixels where channel 0 or 1 leaves [0, 1] and channel 2 does not (only the last channel decides the roughness)."""
     if (h, w) != (H, W):
         for p in range(2):
@@ -65,8 +66,10 @@ def _check_after_s1(lab2bgr, gs, go, H, W, h, w, flab, form=None, step_bound=Fal
     else:
         assert np.array_equal(gs["ab_up"], gs["ab_nonlocal"])
     assert np.array_equal(gs["roughness"], ref64.roughness(gs["ab_up"], flab))
-    lam = 0.024 * (H * W) / (h * w) * (4 if (h, w) == (H, W) else 1)
-    exact = ref64.wls_solve_exact(gs["ab_up"], flab, H, W, lam, 1.2, gs["roughness"])
+    lam = prm["wls_lambda_init"] * (H * W) / (h * w) * (4 if (h, w) == (H, W) else 1)
+    exact = ref64.wls_solve_exact(gs["ab_up"], flab, H, W, lam, prm["wls_alpha"], gs["roughness"])
+    if stats is not None:
+        stats["s2_frac"] = max(stats.get("s2_frac", 0.0), float((np.abs(gs["ab_wls"] - exact) / (2e-6 + 2e-5 * np.abs(exact))).max()))
     assert np.allclose(gs["ab_wls"], exact, rtol=2e-5, atol=2e-6)
     lab_out = ref64.apply_coeffs(gs["ab_wls"], flab)
     assert np.array_equal(go, lab2bgr(lab_out.reshape(H, W, 3), form))

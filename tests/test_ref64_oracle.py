@@ -8,6 +8,8 @@ import synth
 from test_gpu_color import _level_case
 
 SIZES = [(17, 17), (17, 400), (31, 23), (113, 170)]
+# the colour stage's parameters as nct_params_default sets them (Config.h:58-72): what every check below assumes unless it is handed another set
+COLOR_DEFAULTS = dict(eps=0.60, nonlocal_weight=2.0, local_weight=0.125, wls_lambda_init=0.024, wls_alpha=1.2)
 # (A size, B size): A != B in both directions, elongated, and the odd ratios of the pyramid
 AB_SIZES = [((17, 17), (31, 23)), ((31, 23), (17, 17)), ((17, 400), (23, 31)), ((113, 170), (57, 85))]
 
@@ -135,26 +137,35 @@ def _s1_case(oracle, case, seed=21):
     return err, s, g, full, ids, ws, slab, glab
 
 
-@pytest.mark.parametrize("case", S1_CASES)
-def test_s1_short_iterations(oracle, case):
+def check_s1_short_iterations(oracle, case, prm=COLOR_DEFAULTS):
     """maxit 1, 2, 5: the oracle's canonical recurrence (what the kernels reproduce) vs the literal CGNR on ref64's assembled A, from the same x0. Before the
-    truncated CG's chaos sets in they agree to rounding (test_canonical_cg_matches_explicit_for_few_iterations shows the same for the oracle's two forms)."""
+    truncated CG's chaos sets in they agree to rounding (test_canonical_cg_matches_explicit_for_few_iterations shows the same for the oracle's two forms).
+    prm: the colour parameters handed to both sides. Returns the largest |oracle - ref64| / bar over the three runs."""
     H, W, h, w, grid, samples, layer, flat = case
     err, s, g, full, ids, ws, slab, glab = _s1_case(oracle, case)
     if flat:
         assert np.bincount(ids.reshape(-1)).max() > 64
     wgt = ref64.err_weight(err)
     nf = H * W / (h * w)
-    x0 = np.stack(oracle.local_stats(oracle.bgr2lab(s), oracle.bgr2lab(g), 0.6))
-    system = ref64.s1_system(slab, glab, wgt, ids, ws, h, w, 0.125, 1.2, nf)
+    x0 = np.stack(oracle.local_stats(oracle.bgr2lab(s), oracle.bgr2lab(g), prm["eps"]))
+    system = ref64.s1_system(slab, glab, wgt, ids, ws, h, w, prm["local_weight"], prm["wls_alpha"], nf, nonlocal_weight=prm["nonlocal_weight"])
+    worst = 0.0
     for maxit, tol in ((1, 1e-12), (2, 1e-10), (5, 1e-7)):
-        ab, it = oracle.nonlocal_solve(x0, slab, glab, wgt, ids, ws, h, w, layer, 0.125, 1.2, nf, maxit=maxit)
+        ab, it = oracle.nonlocal_solve(x0, slab, glab, wgt, ids, ws, h, w, layer, prm["local_weight"], prm["wls_alpha"], nf, nl_weight=prm["nonlocal_weight"], maxit=maxit)
         assert it.tolist() == [maxit] * 3
         for c in range(3):
             A, rhs = system[c]
             x, k = ref64.s1_cg(A, rhs, np.r_[x0[0][:, c], x0[1][:, c]], maxit)
             assert k == maxit
-            assert np.allclose(np.r_[ab[0][:, c], ab[1][:, c]], x, rtol=tol, atol=tol), (maxit, c)
+            got = np.r_[ab[0][:, c], ab[1][:, c]]
+            worst = max(worst, float((np.abs(got - x) / (tol + tol * np.abs(x))).max()))
+            assert np.allclose(got, x, rtol=tol, atol=tol), (maxit, c)
+    return worst
+
+
+@pytest.mark.parametrize("case", S1_CASES)
+def test_s1_short_iterations(oracle, case):
+    check_s1_short_iterations(oracle, case)
 
 
 # f(oracle's iterate at the cap) / f(ref64's literal iterate at the cap), f = |A x - rhs|^2 per channel. Measured with this file's case generator on 8 seeds x
@@ -165,11 +176,17 @@ S1_CAP_RATIO = (0.9, 1.1)
 
 @pytest.mark.parametrize("case", [(48, 48, 24, 24, (3, 3), 4, 2, False), (40, 56, 20, 28, (5, 7), 4, 3, False), (64, 64, 64, 64, (4, 4), 16, 4, True)])
 def test_s1_at_the_cap_descends_like_the_literal_cg(oracle, case):
+    check_s1_at_the_cap(oracle, case)
+
+
+def check_s1_at_the_cap(oracle, case, prm=COLOR_DEFAULTS, seed=5):
+    """-> the (smallest, largest) energy ratio over the three channels, each inside S1_CAP_RATIO"""
     H, W, h, w, grid, samples, layer, flat = case
-    err, s, g, full, ids, ws, slab, glab = _s1_case(oracle, case, seed=5)
-    _, st = oracle.local_color_transfer(err, s, g, full, ids, ws, layer, want_stages=True)
-    system = ref64.s1_system(slab, glab, ref64.err_weight(err), ids, ws, h, w, 0.125, 1.2, H * W / (h * w))
+    err, s, g, full, ids, ws, slab, glab = _s1_case(oracle, case, seed=seed)
+    _, st = oracle.local_color_transfer(err, s, g, full, ids, ws, layer, params=dict(prm, k_num=8.0), want_stages=True)
+    system = ref64.s1_system(slab, glab, ref64.err_weight(err), ids, ws, h, w, prm["local_weight"], prm["wls_alpha"], H * W / (h * w), nonlocal_weight=prm["nonlocal_weight"])
     cap = 50 if layer == 4 else 100
+    ratios = []
     for c in range(3):
         A, rhs = system[c]
         x0 = np.r_[st["ab_local"][0][:, c], st["ab_local"][1][:, c]]
@@ -178,6 +195,8 @@ def test_s1_at_the_cap_descends_like_the_literal_cg(oracle, case):
         f0, fo, fr = (ref64.s1_objective(A, rhs, v) for v in (x0, xo, xr))
         assert fo <= f0
         assert S1_CAP_RATIO[0] <= fo / fr <= S1_CAP_RATIO[1], (c, fo, fr)
+        ratios.append(fo / fr)
+    return min(ratios), max(ratios)
 
 
 # ---------------------------------------------------------------- U1
@@ -213,13 +232,17 @@ LEVEL_CASES = [(48, 48, 12, 12, (3, 3), 4, 2, False), (40, 56, 20, 28, (5, 7), 4
 
 @pytest.mark.parametrize("case", LEVEL_CASES)
 def test_level_stages_vs_ref64(oracle, case):
+    check_level_stages(oracle, case)
+
+
+def check_level_stages(oracle, case, prm=COLOR_DEFAULTS):
     """The oracle's composed level, stage by stage, against ref64 applied to the oracle's own previous stage: T1, U1 (resize + roughness), the S2 system and
-    its exact solve, A1."""
+    its exact solve, A1. Returns (the stages, the largest |S2 - exact| / (atol + rtol |exact|): the fraction of S2's bar in use)."""
     H, W, h, w, grid, samples, layer, flat = case
     err, s, g, full, ids, ws, slab, glab = _s1_case(oracle, case, seed=40 + layer)
-    out, st = oracle.local_color_transfer(err, s, g, full, ids, ws, layer, want_stages=True)
+    out, st = oracle.local_color_transfer(err, s, g, full, ids, ws, layer, params=dict(prm, k_num=8.0), want_stages=True)
     flab = oracle.bgr2lab(full).reshape(-1, 3) / 255.0
-    ea, eb = ref64.local_stats(oracle.bgr2lab(s), oracle.bgr2lab(g), 0.60)
+    ea, eb = ref64.local_stats(oracle.bgr2lab(s), oracle.bgr2lab(g), prm["eps"])
     assert _ulp_close(st["ab_local"][0], ea, 2) and _ulp_close(st["ab_local"][1], eb, 2)
     if (h, w) != (H, W):
         up = np.stack([ref64.resize_linear_f64(st["ab_nonlocal"][p].reshape(h, w, 3), H, W).reshape(-1, 3) for p in range(2)])
@@ -227,14 +250,15 @@ def test_level_stages_vs_ref64(oracle, case):
     else:
         assert np.array_equal(st["ab_up"], st["ab_nonlocal"])
     assert np.array_equal(st["roughness"], ref64.roughness(st["ab_up"], flab))
-    lam = 0.024 * (H * W) / (h * w) * (4 if (h, w) == (H, W) else 1)
-    for o_, r_ in zip(oracle.wls_system(flab, H, W, lam, 1.2, st["roughness"]), ref64.wls_system(flab, H, W, lam, 1.2, st["roughness"])):
+    lam, alpha = prm["wls_lambda_init"] * (H * W) / (h * w) * (4 if (h, w) == (H, W) else 1), prm["wls_alpha"]
+    for o_, r_ in zip(oracle.wls_system(flab, H, W, lam, alpha, st["roughness"]), ref64.wls_system(flab, H, W, lam, alpha, st["roughness"])):
         assert np.allclose(o_, r_, rtol=1e-14, atol=0)
-    exact = ref64.wls_solve_exact(st["ab_up"], flab, H, W, lam, 1.2, st["roughness"])
+    exact = ref64.wls_solve_exact(st["ab_up"], flab, H, W, lam, alpha, st["roughness"])
     assert np.allclose(st["ab_wls"], exact, rtol=2e-5, atol=2e-6)
     lab_out = ref64.apply_coeffs(st["ab_wls"], flab)
     assert np.array_equal(oracle.apply_coeffs(st["ab_wls"], flab), lab_out)
     assert np.array_equal(out, oracle.lab2bgr(lab_out.reshape(H, W, 3)))
+    return st, float((np.abs(st["ab_wls"] - exact) / (2e-6 + 2e-5 * np.abs(exact))).max())
 
 
 def test_wls_zero_rhs_is_skipped(oracle):
@@ -414,13 +438,13 @@ KM_CASES = [("synth16", lambda: synth.features(3, 512, 16, 16) * np.float32(5.0)
             ("synth63_tight_cap", lambda: synth.features(3, 512, 63, 63) * np.float32(5.0), (1,), "cap", False)]
 
 
-def check_kmeans(cluster, normalize, f, seed, expect, need_margin=True):
+def check_kmeans(cluster, normalize, f, seed, expect, need_margin=True, K=10):
     """cluster(f, K, iters, seed) -> (labels, n): bit for bit ref64.kmeans_labels of the library's own normalised map (no margin needed: ref64 emulates every
     float operation), and of ref64's normalisation of f with the margin above KM_MARGIN (need_margin False: only reported). Returns the margin."""
-    gl, gn = cluster(f, 10, 11, seed)
-    el, en, _, info = ref64.kmeans_labels(normalize(f), 10, 11, seed, normalized=True, want_info=True)
+    gl, gn = cluster(f, K, 11, seed)
+    el, en, _, info = ref64.kmeans_labels(normalize(f), K, 11, seed, normalized=True, want_info=True)
     assert gn == en and np.array_equal(gl, el), "labels differ from ref64 on the library's normalised map"
-    rl, rn, margin = ref64.kmeans_labels(f, 10, 11, seed)
+    rl, rn, margin = ref64.kmeans_labels(f, K, 11, seed)
     if need_margin:
         assert margin >= KM_MARGIN, f"margin {margin:.3g}: this case cannot tell a label error from the normalisation's rounding"
         assert gn == rn and np.array_equal(gl, rl)
