@@ -36,7 +36,8 @@ extern "C" {
  * nct_seq_matte_warp[_dev], nct_seq_set_region_tracking and nct_seq_get_region, and with matte snapping, nct_region_snap[_dev], nct_region_snap_params and
  * nct_seq_set_region_snap, and with region selection from strokes, nct_region_select[_dev], nct_feat_quantize[_dev], nct_region_score[_dev], nct_pair_select_region and
  * nct_seq_select_region, and with region models, nct_region_model_*, nct_region_refind[_dev], nct_pair_apply_region_model and nct_seq_set_region_model, and with sequences
- * over several references, nct_seq_begin_multi[_fullres], nct_seq_frame_multi[_stage]_levels, nct_seq_hold, nct_seq_hold_levels and nct_select_reference_hold[_dev]).
+ * over several references, nct_seq_begin_multi[_fullres], nct_seq_frame_multi[_stage]_levels, nct_seq_hold, nct_seq_hold_levels and nct_select_reference_hold[_dev], and with reference
+ * region masks in sequences, nct_seq_set_ref_region, nct_seq_pull_hold[_dev], nct_seq_pull_levels and nct_seq_frame[_propagate]_ref_region_levels).
  * A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
 #define NCT_VERSION 118
@@ -447,7 +448,7 @@ int nct_seq_warp_dev(nct_ctx* ctx, const double* d_x_prev, int h, int w, const i
  * nct_seq_frame_multi_levels reports through nct_multi_levels (label[l] = l_t; in a full-resolution sequence its result[] must be NULL), nct_seq_levels and
  * nct_seq_hold_levels — free_label[l] = f ([h*w] bytes), margin[l] = rule 4's value ([h*w] doubles), on a frame without a hold f = l_t and 0.0; all nullable.
  * nct_seq_frame_multi_stage_levels also takes color[5] (nullable, each nullable), the colour stage's maps per level as nct_pair_levels.color reports them.
- * nct_pair_set_ref_region and nct_multi_upload stay NCT_ERR_STATE while a sequence is open; reference masks in sequences are undefined.
+ * nct_pair_set_ref_region and nct_multi_upload stay NCT_ERR_STATE while a sequence is open; reference masks in sequences: SPEC §6.19, nct_seq_set_ref_region.
  * nct_select_reference_hold: rules 1-6 alone on host maps (synchronous). err[k] h*w fp32, guide_bgr[k] h*w*3, prev_label h*w, lab / lab_prev h*w*3 (8-bit Lab), field
  * (nullable: m = 0) int16 [h*w][2]; label, guide_out, err_out (as in nct_select_reference), free_label (h*w) and margin (h*w doubles) are nullable. The _dev form takes
  * device pointers (the two arrays OF pointers are host memory) and is enqueued on the context's stream; there label must not overlap prev_label. K outside
@@ -593,7 +594,7 @@ int nct_lut_fit_masked_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, const uint8_t
  * pointer or a side out of range: NCT_ERR_INVALID, the message names the argument); nct_region_pull_dev: device pointers, enqueued on the context's stream.
  * nct_pair_set_ref_region: after nct_pair_upload / nct_multi_upload, copies reference k's mask (rh[k] x rw[k] of the uploaded reference); nct_pair_run, nct_multi_run and
  * their _levels forms then run masked, nct_pair_fit_lut fits over the pixels whose last level's F is >= 128. mask NULL removes reference k's; the next upload drops all.
- * k outside [0, K) or protect outside {0, 1}: NCT_ERR_INVALID; no upload, or an open sequence: NCT_ERR_STATE (sequences with a mask are not defined). region non-NULL
+ * k outside [0, K) or protect outside {0, 1}: NCT_ERR_INVALID; no upload, or an open sequence: NCT_ERR_STATE (a sequence takes its reference masks through nct_seq_set_ref_region, SPEC §6.19). region non-NULL
  * sets the run's protect — the last setter called decides it, nct_pair_set_region or this one; region NULL leaves it.
  * nct_multi_run_ref_region_levels: nct_multi_run_levels (levels nullable) plus per level Q_k,l [bh*bw], P_k,l [h*w] (masked references only), M_l [h*w], F_l [H*W] and X'
  * [2][h*w][3]; with no reference mask set: NCT_ERR_STATE. nct_pair_run_ref_region_levels: the same for a pair, beside nct_pair_run_levels' maps (the colour stages included).
@@ -645,7 +646,7 @@ int nct_process_pair_fullres_ref_region(nct_ctx* ctx, const uint8_t* src_bgr, in
  * frame: the top level run only), mask[l] = M_l; seq_levels->ab_blend[l] stays the unmixed kept state. Region levels asked for and no mask set: NCT_ERR_STATE.
  * nct_color_finish_upsample_region[_dev], nct_color_finish_guided_region[_dev]: the masked upsampling finish alone; the arguments, limits and refusals of the unmasked
  * calls plus mask (H*W bytes; NULL: the unmasked call) and region (NULL: the defaults; a bad protect: NCT_ERR_INVALID). Equal sizes keep the copy path.
- * Not defined: reference masks in sequences (nct_pair_set_ref_region keeps its refusal) and a masked upsampling finish for
+ * Reference masks in sequences: SPEC §6.19 below (nct_pair_set_ref_region keeps its refusal). Not defined: a masked upsampling finish for
  * pairs through nct_process_pair_fullres_finish_region (its refusal stays; a one-frame full-resolution sequence gives those bytes). */
 int nct_seq_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_params* region);
 int nct_seq_frame_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_pair_levels* levels, const nct_seq_levels* seq_levels,
@@ -661,6 +662,52 @@ int nct_color_finish_guided_region(nct_ctx* ctx, const double* ab_wls, const uin
 int nct_color_finish_guided_region_dev(nct_ctx* ctx, const double* d_ab_wls, const uint8_t* d_lab_work, int h, int w, const uint8_t* d_s_bgr_full, int H, int W,
                                        const uint8_t* d_mask /* H*W */, const nct_region_params* region, const nct_guided_params* guided, const nct_params* prm,
                                        uint8_t* d_out_bgr_full);
+
+/* ---- reference region masks in sequences (SPEC §6.19; an extension): §6.12's reference mask on the frames of an open sequence — pulled on full frames, held with the
+ * blend's own weight, carried on propagated frames. C ABI and python only: the console driver has no option for it.
+ * nct_seq_set_ref_region: on an open sequence (plain, multi or full-resolution), between frames. mask has one byte per pixel of reference k at the size that reference
+ * arrived — in a full-resolution sequence the original size, shrunk on the device by nct_resize_u8c1 to the reference's working size — and is copied in the call; its
+ * level masks Q_k,l (§6.12 rule 1) are built once, here, and kept. Sticky until replaced or removed (mask NULL); nct_seq_reset keeps it, nct_seq_end and nct_destroy drop
+ * it. region non-NULL sets the run's protect (the last setter called decides it); NULL leaves it. No open sequence: NCT_ERR_STATE; k outside [0, K) or protect outside
+ * {0, 1}: NCT_ERR_INVALID, and the setting stays as it was. nct_pair_set_ref_region keeps its NCT_ERR_STATE while a sequence is open.
+ * A full frame, per level l: §6.12 rule 2's pull per masked reference behind its votes; §6.12 rule 3's merge with the level's label map (§6.18's l_t with K > 1) gives P_l;
+ * then the hold, on a frame that blends (the sequence has state, tau > 0, and a kept P'_(t-1)[l] exists), per level pixel p in IEEE double, uncontracted:
+ *   m(p) = the level's field as in §6.18 rule 2, clamped so that p + m is inside the grid, 0 with motion off; j = P'_(t-1)[l](p + m(p));
+ *   tau_p = the weight §6.3 rule 3 (§6.4 rule 4 with a field) gives the pixel, the value nct_seq_levels.tau_map reports;
+ *   P'_t(p) = (uint8) rint((double)P_l(p) + tau_p * ((double)j - (double)P_l(p))).
+ * On every other full frame — a first frame, a frame after nct_seq_reset or a cut, tau == 0, the first full frame after any set, replace or remove of a reference mask —
+ * P'_t = P_l with no launch. P'_t replaces the kept map out of place. M_l = min(P'_t, the source level mask in force or 255) drives §6.13 rule 2's out-of-place mix (the
+ * kept X' is never mixed), F_l = nct_resize_u8c1(P'_t -> the size the level's finish targets) then the minimum with the source mask at that size drives the compose with
+ * the run's protect. The last level's finish follows the sequence's form: the working size; NCT_FINISH_EXACT with F at the original size; NCT_FINISH_UPSAMPLE (plain or
+ * guided) composes at the working size and runs the masked upsampling finish with F0 = min(resize(P'_top -> H0 x W0), M0), 1 B per original pixel of scratch.
+ * A propagated frame carries the kept map per level run, P'_t[l](p) = P'_(t-1)[l](p + m(p)) (bytes copied, never interpolated; left as they are with motion off), then
+ * mixes, composes and finishes on the top level run only as §6.13 rule 3 does. While a reference mask is set and no kept P' exists — before the first full frame, or right
+ * after a set, replace or remove — a propagated frame is NCT_ERR_STATE (a full frame must come first) and changes nothing, and nct_seq_frame_auto turns a PROPAGATED
+ * decision into KEY and reports KEY; nct_seq_probe is unchanged. No nct_seq_set_ref_region call: the sequence's bytes, kept state, launches and arena of before. Every
+ * Q_k == 255: the unmasked sequence's bytes and state. K = 1, Q == 0: every frame is its source. A first frame, a frame after reset, a CUT frame and every frame with
+ * tau == 0 equal nct_process_pair_ref_region / nct_process_multi_ref_region (NCT_FINISH_EXACT: nct_process_pair_fullres_ref_region). nct_pair_fit_lut after such a frame
+ * fits over the last level's F >= 128 at the size it reads.
+ * Arena while a reference mask is set: 2 x 1 B per level pixel of every level run (P' and the map the gather writes), 1 B per reference level pixel per masked
+ * reference, and §6.12's 144 B per reference pixel of the level during a pull.
+ * nct_seq_pull_hold: the merge, the hold and the minimum alone on host maps (synchronous). pulled: K host pointers to h*w bytes (a null entry: 255); label h*w (nullable
+ * when K == 1); prev h*w; lab / lab_prev h*w*3 (8-bit Lab); field (nullable: m = 0) int16 [h*w][2]; src_mask h*w (nullable: 255); p_out h*w; m_out and p_free (the merged
+ * P_l before the hold) h*w, nullable. The _dev form takes device pointers (the array OF pointers is host memory), is enqueued on the context's stream and refuses a p_out
+ * that overlaps prev. Grid sides outside 1 … 4096, K outside [1, NCT_MAX_REFS], tau outside [0, 1), sigma not finite and positive, a null input: NCT_ERR_INVALID, the
+ * message names the argument.
+ * nct_seq_frame_ref_region_levels: nct_seq_frame_multi_stage_levels plus nct_ref_region_levels (ref_mask = Q_k,l, pulled = P_k,l, mask = M_l, mask_full = F_l, ab_mix) and
+ * nct_seq_pull_levels (p_free[l] = P_l, p_held[l] = P'_t; on a frame without a hold they are equal). nct_seq_frame_propagate_ref_region_levels: the propagated form; p_held
+ * for every level run, the rest for the top level run only (p_free, pulled and ref_mask are not written). Either report asked for with no reference mask set: NCT_ERR_STATE. */
+typedef struct nct_seq_pull_levels { uint8_t* p_free[5]; uint8_t* p_held[5]; } nct_seq_pull_levels;   /* all nullable */
+int nct_seq_set_ref_region(nct_ctx* ctx, int k, const uint8_t* mask, const nct_region_params* region);
+int nct_seq_pull_hold(nct_ctx* ctx, const uint8_t* const* pulled, int K, const uint8_t* label, const uint8_t* prev, const uint8_t* lab, const uint8_t* lab_prev,
+                      const int16_t* field, const uint8_t* src_mask, int h, int w, double tau, double sigma, uint8_t* p_out, uint8_t* m_out, uint8_t* p_free);
+int nct_seq_pull_hold_dev(nct_ctx* ctx, const uint8_t* const* d_pulled, int K, const uint8_t* d_label, const uint8_t* d_prev, const uint8_t* d_lab, const uint8_t* d_lab_prev,
+                          const int16_t* d_field, const uint8_t* d_src_mask, int h, int w, double tau, double sigma, uint8_t* d_p_out, uint8_t* d_m_out, uint8_t* d_p_free);
+int nct_seq_frame_ref_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_multi_levels* levels,
+                                    const nct_color_stages* const* color, const nct_seq_levels* seq_levels, const nct_seq_hold_levels* hold_levels,
+                                    const nct_ref_region_levels* region_levels, const nct_seq_pull_levels* pull_levels);
+int nct_seq_frame_propagate_ref_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* seq_levels,
+                                              const nct_ref_region_levels* region_levels, const nct_seq_pull_levels* pull_levels);
 
 /* ---- region tracking (SPEC §6.14; an extension): the matte of §6.13 follows the motion field of §6.4, so that it is drawn on one frame and carried through the shot.
  * nct_seq_matte_warp[_dev]: the carry alone. mask_prev: H x W bytes; field: h x w int16 pairs (my, mx), a backward field on a level grid (it points from the frame

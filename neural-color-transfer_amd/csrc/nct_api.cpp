@@ -352,6 +352,34 @@ int nct_select_reference_hold(nct_ctx* ctx, const float* const* err, const uint8
     return NCT_OK;
 }
 
+// SPEC §6.19 rules 2-4 on host maps: the pulled masks, the label map, the kept map, the two Lab level images, the field and the source mask up, one k_seq_pull_hold
+// launch, P', M and the free P down
+int nct_seq_pull_hold(nct_ctx* ctx, const uint8_t* const* pulled, int K, const uint8_t* label, const uint8_t* prev, const uint8_t* lab, const uint8_t* lab_prev,
+                      const int16_t* field, const uint8_t* src_mask, int h, int w, double tau, double sigma, uint8_t* p_out, uint8_t* m_out, uint8_t* p_free) {
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_seq_pull_hold_check(ctx, "seq_pull_hold", (const void* const*)pulled, K, label, prev, lab, lab_prev, h, w, tau, sigma, p_out));
+    const size_t n = (size_t)h * w;
+    DevBuf<uint8_t> pk(ctx, n * K), lbl(ctx, n), pv(ctx, n), l1(ctx, n * 3), l0(ctx, n * 3), ms(ctx, n), po(ctx, n), mo(ctx, n), pf(ctx, n);
+    DevBuf<int16_t> fld(ctx, field ? n * 2 : 8);
+    if (!pk.ok() || !lbl.ok() || !pv.ok() || !l1.ok() || !l0.ok() || !ms.ok() || !po.ok() || !mo.ok() || !pf.ok() || !fld.ok()) return NCT_ERR_HIP;
+    const uint8_t* dp[NCT_MAX_REFS];
+    for (int k = 0; k < K; ++k) {
+        dp[k] = pulled[k] ? pk + n * k : nullptr;
+        if (pulled[k]) NCT_H2D(pk + n * k, pulled[k], n);
+    }
+    if (label) NCT_H2D(lbl, label, n);
+    NCT_H2D(pv, prev, n); NCT_H2D(l1, lab, n * 3); NCT_H2D(l0, lab_prev, n * 3);
+    if (field) NCT_H2D(fld, field, sizeof(int16_t) * 2 * n);
+    if (src_mask) NCT_H2D(ms, src_mask, n);
+    NCT_TRY(nctk_seq_pull_hold(ctx, ctx->stream, dp, K, label ? (const uint8_t*)lbl : nullptr, pv, l1, l0, field ? (const int16_t*)fld : nullptr,
+                               src_mask ? (const uint8_t*)ms : nullptr, h, w, tau, sigma, po, m_out ? (uint8_t*)mo : nullptr, p_free ? (uint8_t*)pf : nullptr));
+    NCT_D2H(p_out, po, n);
+    if (m_out) NCT_D2H(m_out, mo, n);
+    if (p_free) NCT_D2H(p_free, pf, n);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
 // SPEC §6.3 rule 3 on host maps: the two coefficient maps and the two Lab level images up, one k_seq_blend launch, X' (and the tau_p map) down
 int nct_seq_blend(nct_ctx* ctx, const double* x, const double* x_prev, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, double tau, double sigma,
                   double* x_out, double* tau_map) {

@@ -170,6 +170,12 @@ int nct_select_reference_hold_dev(nct_ctx* ctx, const float* const* d_err, const
                             d_margin);
 }
 
+int nct_seq_pull_hold_dev(nct_ctx* ctx, const uint8_t* const* d_pulled, int K, const uint8_t* d_label, const uint8_t* d_prev, const uint8_t* d_lab, const uint8_t* d_lab_prev,
+                          const int16_t* d_field, const uint8_t* d_src_mask, int h, int w, double tau, double sigma, uint8_t* d_p_out, uint8_t* d_m_out, uint8_t* d_p_free) {   /* SPEC §6.19 */
+    NCT_CTX_ENTER();
+    return nctk_seq_pull_hold(ctx, ctx->stream, d_pulled, K, d_label, d_prev, d_lab, d_lab_prev, d_field, d_src_mask, h, w, tau, sigma, d_p_out, d_m_out, d_p_free);
+}
+
 int nct_seq_blend_dev(nct_ctx* ctx, const double* d_x, const double* d_x_prev, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, double tau, double sigma,
                       double* d_x_out, double* d_tau_map) {                                                                                          /* SPEC §6.3 */
     NCT_CTX_ENTER();

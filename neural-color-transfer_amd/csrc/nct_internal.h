@@ -252,6 +252,14 @@ int nct_select_hold_check(nct_ctx* ctx, const char* who, const void* const* err,
 bool nct_seq_hold_ok(double hold);
 // SPEC §6.18 rule 7: label_out(p) = label_prev(p + m(p)), a vector that leaves the grid clamped to it; label_out must not overlap label_prev
 int nctk_label_carry(nct_ctx* ctx, hipStream_t s, const uint8_t* label_prev, int h, int w, const int16_t* field, uint8_t* label_out);
+// k_seq_pull.hip — SPEC §6.19 rules 2-4 in one launch: P_l = the pulled mask of the pixel's label (pulled: K device pointers, null = 255; label is read with K > 1
+// only), P' = P_l held against prev ([h*w] bytes, the map the previous frame kept, read at p + m(p)) with nctk_seq_blend's weight tau_p on lab / lab_prev, M = min(P',
+// src_mask) (null = 255). field (nullable: m = 0) as there. m_out and p_free (P_l before the hold) are nullable; p_out must not overlap prev
+int nctk_seq_pull_hold(nct_ctx* ctx, hipStream_t s, const uint8_t* const* pulled, int K, const uint8_t* label, const uint8_t* prev, const uint8_t* lab, const uint8_t* lab_prev,
+                       const int16_t* field, const uint8_t* src_mask, int h, int w, double tau, double sigma, uint8_t* p_out, uint8_t* m_out, uint8_t* p_free);
+// its argument checks (`who` names the entry point in the message), for the host form to run before it moves anything
+int nct_seq_pull_hold_check(nct_ctx* ctx, const char* who, const void* const* pulled, int K, const void* label, const void* prev, const void* lab, const void* lab_prev, int h, int w,
+                            double tau, double sigma, const void* p_out);
 // k_temporal.hip — SPEC §6.3 rule 3: x_out = x + tau_p (x_prev - x) per level pixel, tau_p from the 3 x 3 mean squared Lab difference; x_out may alias x or x_prev; tau_map nullable.
 // field (nullable, [h*w][2] int16 (my, mx)): SPEC §6.4 rule 4 — L_(t-1) and x_prev are read at p + m(p); x_out may then alias x only
 int nctk_seq_blend(nct_ctx* ctx, hipStream_t s, const double* x, const double* x_prev, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, double tau, double sigma,

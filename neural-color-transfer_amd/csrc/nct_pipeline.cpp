@@ -152,6 +152,7 @@ struct pair_run {
     const nct_seq_levels* const slv;               // nullable: where a frame's X'_t and tau_p maps go
     const nct_ref_region_levels* const qlv;        // nullable: where a masked run's level masks and mixed coefficients go (SPEC §6.11, §6.12)
     const nct_seq_hold_levels* const hlv;          // nullable: where a frame over several references reports the held selection's free labels and margins (SPEC §6.18)
+    const nct_seq_pull_levels* const plv;          // nullable: where a frame with a reference mask reports the merged pull before and after its hold (SPEC §6.19)
     pair_state* const P; const hipStream_t s;
     const int H, W, K, nlevels; const size_t N;
     const bool feat16, count;
@@ -180,6 +181,11 @@ struct pair_run {
     const uint8_t* mask;                           // a tracked frame of a sequence (SPEC §6.14) carries the matte first: lab_and_pyramids reads the pointer again
     DevBuf<uint8_t> mpyr[4]; const uint8_t* mimg[5] = {};
     const bool ref_masked;
+    // SPEC §6.19: this frame of a sequence with a reference mask holds its merged pull against the map the previous frame kept — it blends and such a map exists. Every
+    // other masked frame keeps P_l as it is. hold_lab: L_t[l] for the hold (and the held selection, which then makes it), given back behind the hold. up_masked: the
+    // last level finishes through the masked upsampling finish with F0, made from P' at the original size
+    const bool pull_hold, up_masked;
+    DevBuf<uint8_t> hold_lab;
     // SPEC §6.17: this full frame of a sequence with a region model re-finds its matte behind the forward (not the own frame of a fresh matte: rule S1). tapfeat: the
     // model's tap of that forward, channel-last, where it is not conv5_1 itself. The level masks are then built behind the re-find: nothing reads them before level 0's mix
     const bool refind;
@@ -189,9 +195,10 @@ struct pair_run {
     const nct_color_params cp;
 
     pair_run(nct_ctx* c, const nct_params* p, nct_pair_timing* t, const run_extras& x)
-        : ctx(c), prm(p), timing(t), lv(x.lv ? x.lv : &kNoLevels), color(x.color), fin(x.fin), seq(x.seq), slv(x.slv), qlv(x.qlv), hlv(x.hlv), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
+        : ctx(c), prm(p), timing(t), lv(x.lv ? x.lv : &kNoLevels), color(x.color), fin(x.fin), seq(x.seq), slv(x.slv), qlv(x.qlv), hlv(x.hlv), plv(x.plv), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
           nlevels(p->levels), N((size_t)H * W), feat16((p->flags & NCT_FLAG_FEAT16) != 0), count(t && (p->flags & NCT_FLAG_COUNT_EVALS)), side(c), held(x.seq && P->K > 1 && x.seq->frames > 0 && x.seq->tau > 0.0 && x.seq->hold > 0.0), mask(P->mask),
-          ref_masked(!x.seq && P->ref_masked()), refind(x.seq && x.seq->model_rows && !(P->mask && x.seq->matte_fresh)), cp(nct_color_params_of(*p)) {}
+          ref_masked(P->ref_masked()), pull_hold(ref_masked && x.seq && x.seq->frames > 0 && x.seq->tau > 0.0 && x.seq->pull_kept),
+          up_masked(ref_masked && x.fin && x.fin->finish == NCT_FINISH_UPSAMPLE), refind(x.seq && x.seq->model_rows && !(P->mask && x.seq->matte_fresh)), cp(nct_color_params_of(*p)) {}
 
     int d2h(void* dst, const void* src, size_t bytes) {
         if (dst) NCT_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
@@ -250,6 +257,7 @@ struct pair_run {
             // SPEC §6.12 rule 1: the masked references' level masks, on the reference's level grids
             if (!P->rmask[k]) continue;
             R[k].qimg[4] = P->rmask[k];
+            if (seq) { for (int l = 3; l >= 0; --l) R[k].qimg[l] = seq->rq[k][l]; continue; }          // the sequence's level masks were built by nct_seq_set_ref_region (SPEC §6.19)
             for (int l = 3; l >= 0; --l) {
                 if (!R[k].qpyr[l].alloc(ctx, (size_t)R[k].bh[l] * R[k].bw[l])) return NCT_ERR_HIP;
                 NCT_TRY(nctk_resize_u8c1(ctx, s, R[k].qimg[l + 1], R[k].bh[l + 1], R[k].bw[l + 1], R[k].qpyr[l], R[k].bh[l], R[k].bw[l]));
@@ -327,9 +335,9 @@ struct pair_run {
         }
         if (ref_masked) {
             for (int k = 0; k < K; ++k) if (R[k].qimg[4] && !R[k].pulled.alloc(ctx, N)) return NCT_ERR_HIP;
-            if (K > 1 && !p_merged.alloc(ctx, N)) return NCT_ERR_HIP;
+            if (K > 1 && (!pull_hold || plv) && !p_merged.alloc(ctx, N)) return NCT_ERR_HIP;      // a frame that holds merges inside the hold; the free P_l is kept only for the report
             if (mask && !m_level.alloc(ctx, N)) return NCT_ERR_HIP;
-            if (nlevels > 1 && !f_level.alloc(ctx, N)) return NCT_ERR_HIP;          // one level: its F is the last level's, pair_state's fin_mask
+            if ((nlevels > 1 || up_masked) && !f_level.alloc(ctx, N)) return NCT_ERR_HIP;      // one level: its F is the last level's, pair_state's fin_mask (the masked upsampling finish keeps F0 there)
         }
         if (!P->out) { P->out = (uint8_t*)ctx->alloc(N * 3); if (!P->out) return NCT_ERR_HIP; }
         return d2h(lv->labels, labels, sizeof(int) * (size_t)ah[0] * aw[0]);
@@ -445,8 +453,10 @@ struct pair_run {
     int held_selection(int l, const float* const* errs, const uint8_t* const* guides) {
         const int h = ah[l], w = aw[l];
         const size_t n = (size_t)h * w;
-        DevBuf<uint8_t> lab_l(ctx, n * 3), free_l; DevBuf<double> margin_l;
-        if (!lab_l.ok()) return NCT_ERR_HIP;
+        // a frame that also holds its pull (SPEC §6.19) reads the same L_t[l] and field behind this: the image then outlives the call, in hold_lab
+        DevBuf<uint8_t> lab_own, free_l; DevBuf<double> margin_l;
+        DevBuf<uint8_t>& lab_l = pull_hold ? hold_lab : lab_own;
+        if (!lab_l.alloc(ctx, n * 3)) return NCT_ERR_HIP;
         if (hlv && hlv->free_label[l] && !free_l.alloc(ctx, n)) return NCT_ERR_HIP;
         if (hlv && hlv->margin[l] && !margin_l.alloc(ctx, n)) return NCT_ERR_HIP;
         NCT_TRY(nctk_bgr2lab(ctx, s, simg[l], lab_l, n));
@@ -466,9 +476,30 @@ struct pair_run {
         const int na_px = ah[l] * aw[l];
         const uint8_t* pulled[NCT_MAX_REFS];
         for (int k = 0; k < K; ++k) pulled[k] = R[k].qimg[4] ? (const uint8_t*)R[k].pulled : nullptr;
-        p_l = K > 1 ? (const uint8_t*)p_merged : pulled[0];
-        m_l = mask ? (const uint8_t*)m_level : p_l;
-        if (K > 1 || mask) NCT_TRY(nctk_region_merge(ctx, s, pulled, K, sel_label, mimg[l], na_px, K > 1 ? (uint8_t*)p_merged : nullptr, mask ? (uint8_t*)m_level : nullptr));
+        const uint8_t* p_free = K > 1 ? (const uint8_t*)p_merged : pulled[0];
+        if (pull_hold) {
+            // SPEC §6.19 rule 3: merge, hold and minimum in one launch, out of place into the sequence's second map; the two then change places. L_t[l] and (motion on) the
+            // level's field are made here unless the held selection has made them; the blend reads that field. The kept L_(t-1)[l] is still the previous frame's
+            const int h = ah[l], w = aw[l];
+            if (!held) {
+                if (!hold_lab.alloc(ctx, (size_t)na_px * 3)) return NCT_ERR_HIP;
+                NCT_TRY(nctk_bgr2lab(ctx, s, simg[l], hold_lab, (size_t)na_px));
+                if (seq->motion) { NCT_TRY(seq_motion_level(ctx, s, seq, l, hold_lab)); field_found = true; }
+            }
+            NCT_TRY(nctk_seq_pull_hold(ctx, s, pulled, K, sel_label, seq->keep_pull[l], hold_lab, seq->keep_lab[l], seq->motion ? seq->field[l] : nullptr, mask ? mimg[l] : nullptr, h, w,
+                                       seq->tau, seq->sigma, seq->pull_alt[l], mask ? (uint8_t*)m_level : nullptr, p_merged.ok() ? (uint8_t*)p_merged : nullptr));
+            ctx->release(hold_lab.detach());
+            std::swap(seq->keep_pull[l], seq->pull_alt[l]);
+            p_l = seq->keep_pull[l];
+            m_l = mask ? (const uint8_t*)m_level : p_l;
+        } else {
+            p_l = p_free;
+            m_l = mask ? (const uint8_t*)m_level : p_l;
+            if (K > 1 || mask) NCT_TRY(nctk_region_merge(ctx, s, pulled, K, sel_label, mimg[l], na_px, K > 1 ? (uint8_t*)p_merged : nullptr, mask ? (uint8_t*)m_level : nullptr));
+            // a frame of a sequence that does not hold keeps P_l as its P' (SPEC §6.19 rule 3): a copy, no launch
+            if (seq) NCT_HIP(hipMemcpyAsync(seq->keep_pull[l], p_l, (size_t)na_px, hipMemcpyDeviceToDevice, s));
+        }
+        if (plv) { NCT_TRY(d2h(plv->p_free[l], p_free, (size_t)na_px)); NCT_TRY(d2h(plv->p_held[l], p_l, (size_t)na_px)); }
         for (int k = 0; k < K && qlv; ++k) {
             if (!R[k].qimg[4]) continue;
             NCT_TRY(d2h(qlv->ref_mask[k][l], R[k].qimg[l], (size_t)R[k].bh[l] * R[k].bw[l]));
@@ -519,15 +550,22 @@ struct pair_run {
         // place, from the kept X'_t into the level's own map, which the finish then reads: the state is never mixed. With a reference mask (SPEC §6.12 rules 4-5): F_l = P_l at that
         // size, then the minimum with the source's — the last level's is kept for nct_pair_fit_lut (rule 7)
         const bool masked = mask || ref_masked;
+        full_target up_target;
         if (masked) {
             const bool exact = full && full->finish == NCT_FINISH_EXACT;      // the upsampling finish composes at the working size (and, in its own pass, on the original)
             const int fh = exact ? full->H : H, fw = exact ? full->W : W;
             f_l = exact ? full->mask : mask;
             if (ref_masked) {
                 uint8_t* f = f_level;
-                if (l == nlevels - 1) { if (!(P->fin_mask = (uint8_t*)ctx->alloc((size_t)fh * fw))) return NCT_ERR_HIP; f = P->fin_mask; }
+                if (l == nlevels - 1 && !up_masked) { if (!(P->fin_mask = (uint8_t*)ctx->alloc((size_t)fh * fw))) return NCT_ERR_HIP; f = P->fin_mask; }
                 NCT_TRY(nctk_region_upsize_min(ctx, s, p_l, ah[l], aw[l], f_l, f, fh, fw));
                 f_l = f;
+                if (full && up_masked) {
+                    // SPEC §6.19 rule 8: the masked upsampling finish composes on the original with F0 = min(resize(P' -> H0 x W0), M0); it has the result's size and is kept as fin_mask
+                    if (!(P->fin_mask = (uint8_t*)ctx->alloc((size_t)full->H * full->W))) return NCT_ERR_HIP;
+                    NCT_TRY(nctk_region_upsize_min(ctx, s, p_l, ah[l], aw[l], full->mask, P->fin_mask, full->H, full->W));
+                    up_target = *full; up_target.mask = P->fin_mask;
+                }
             }
             NCT_TRY(nctk_region_mix(ctx, s, seq ? seq->keep_x[l] : (double*)cb.x, m_l, ah[l], aw[l], cb.x));
             if (qlv) {
@@ -536,7 +574,7 @@ struct pair_run {
             }
         }
         const region_fin rg{f_l, P->src, P->protect};
-        NCT_TRY(finish_level(ctx, s, seq && !masked ? seq->keep_x[l] : (double*)cb.x, ah[l], aw[l], H, W, s_lab_full, out_lab, P->out, full, fl, cp, d, nct_cube_form(*prm), masked ? &rg : nullptr));
+        NCT_TRY(finish_level(ctx, s, seq && !masked ? seq->keep_x[l] : (double*)cb.x, ah[l], aw[l], H, W, s_lab_full, out_lab, P->out, full && up_masked ? &up_target : full, fl, cp, d, nct_cube_form(*prm), masked ? &rg : nullptr));
         if (cs && cs->wls_iters) for (int q = 0; q < 6; ++q) cs->wls_iters[q] = wls_it[q];
         if (timing) timing->wls_iters[l] = *std::max_element(wls_it, wls_it + 6);
         MARK(NCT_ST_COLOR, l);
@@ -589,7 +627,7 @@ int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timin
     NCT_REQUIRE(!x.color || P->K == 1 || x.seq, "process: nct_pair_levels describes a pair; several references report through nct_multi_levels");
     if (x.refusal) return ctx->fail(NCT_ERR_STATE, "%s", x.refusal);
     NCT_REQUIRE(!(P->mask && x.fin) || (x.fin->mask && (x.fin->finish == NCT_FINISH_EXACT || x.seq)), "process: a region mask is defined for the exact full-resolution finish only");
-    NCT_REQUIRE(!(P->ref_masked() && x.fin) || x.fin->finish == NCT_FINISH_EXACT, "process: a reference region mask is defined for the exact full-resolution finish only");
+    NCT_REQUIRE(!(P->ref_masked() && x.fin) || x.fin->finish == NCT_FINISH_EXACT || x.seq, "process: a reference region mask is defined for the exact full-resolution finish only");
     // a new run on the resident images: an earlier full-resolution run is no longer the last one, and its two original-size images go back to the arena
     // (a full-resolution sequence keeps its two for its whole life: SPEC §6.9 rule 6)
     if (!(x.seq && x.seq->target())) {
@@ -933,7 +971,7 @@ int nct_pair_fit_lut(nct_ctx* ctx, const nct_lut_params* prm, float* lut_out) {
     if (P && P->full_src && P->full_out) { src = P->full_src; res = P->full_out; mask = P->full_mask; npix = (size_t)P->full_h * P->full_w; }
     else if (P && P->src && P->out && P->sh > 0) { src = P->src; res = P->out; mask = P->mask; npix = (size_t)P->sh * P->sw; }
     // a run with a reference mask: its last level's target mask, which has the size of the result (SPEC §6.12 rule 7)
-    if (src && P->fin_mask && !P->seq) mask = P->fin_mask;
+    if (src && P->fin_mask) mask = P->fin_mask;
     if (!src) return ctx->fail(NCT_ERR_STATE, "pair_fit_lut: no finished run on this context (nct_pair_run first)");
     NCT_TRY(nct_lut_fit_check(ctx, "pair_fit_lut", src, res, npix, prm, lut_out));
     const size_t n = (size_t)prm->size * prm->size * prm->size * 3;

@@ -44,6 +44,12 @@ struct seq_state {
     // or the sequence ends; null: no model. model_p: the parameters of the re-find, model_protect: nct_region_params.protect of the re-found matte
     int16_t* model_rows = nullptr; int model_tap = 0, model_C = 0, model_n_in = 0, model_n_out = 0;
     nct_region_refind_params model_p = {0, 0, 0, 0, {0, 0, 0}}; int model_protect = 0;
+    // SPEC §6.19 (nct_seq_set_ref_region): the masked references' level masks Q_k,l below the working size (Q_k at the working size is pair_state's rmask[k]), built once
+    // per set call; per level run the held pull P' of the last frame and the block the next hold or carry writes — the rule gathers, so the two change places; pull_kept:
+    // keep_pull holds a full frame's P' under the masks in force (false after any set, replace or remove). rh0 / rw0: the references' sizes as they arrived
+    uint8_t* rq[NCT_MAX_REFS][4] = {}; uint8_t *keep_pull[5] = {}, *pull_alt[5] = {};
+    bool pull_kept = false;
+    int rh0[NCT_MAX_REFS] = {}, rw0[NCT_MAX_REFS] = {};
     full_target full;
     const full_target* target() const { return full.H ? &full : nullptr; }
 };
@@ -59,6 +65,7 @@ struct pair_state {
     int protect = 0;                                           // full-resolution run also the mask at full_h x full_w, beside full_src / full_out. protect: nct_region_params
                                                                // An open sequence (SPEC §6.13): both are nct_seq_set_region's and go back with the sequence (seq_free)
     uint8_t* rmask[NCT_MAX_REFS] = {};                         // the references' region masks (SPEC §6.12): rh[k] x rw[k] bytes, set by nct_pair_set_ref_region, dropped with the images
+                                                               // An open sequence (SPEC §6.19): nct_seq_set_ref_region's, at the references' working size
     uint8_t* fin_mask = nullptr;                               // the last level's target mask F of a run with a reference mask, at the size of its result (rule 7: nct_pair_fit_lut); gone with the next run
     bool ref_masked() const { for (const uint8_t* m : rmask) if (m) return true; return false; }
     bool finished = false;                                     // the last run on these images ran to its end: `out` (or full_out) holds its result
@@ -77,8 +84,10 @@ NCT_LOCAL void drop_images(nct_ctx* ctx, pair_state* P);    // drop what the con
 // frame's X'_t, tau_p and fields go; qlv: where a masked run reports Q_k,l, P_k,l, M_l, F_l and X' (SPEC §6.11, §6.12: the one report target of both kinds of mask);
 // refusal: the entry point asked for the report of a mask that is not set — the run is refused with NCT_ERR_STATE and this text, behind the checks of state and parameters
 // hlv: where a frame of a sequence over several references reports the held selection's free labels and margins (SPEC §6.18)
+// plv: where a frame of a sequence with a reference mask reports the merged pull before and after its hold (SPEC §6.19)
 struct run_extras { const nct_multi_levels* lv = nullptr; const nct_color_stages* const* color = nullptr; const full_target* fin = nullptr; seq_state* seq = nullptr;
-                    const nct_seq_levels* slv = nullptr; const nct_ref_region_levels* qlv = nullptr; const char* refusal = nullptr; const nct_seq_hold_levels* hlv = nullptr; };
+                    const nct_seq_levels* slv = nullptr; const nct_ref_region_levels* qlv = nullptr; const char* refusal = nullptr; const nct_seq_hold_levels* hlv = nullptr;
+                    const nct_seq_pull_levels* plv = nullptr; };
 // run the whole L=5->1 loop on the uploaded source and its K references
 NCT_LOCAL int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timing, const run_extras& x = {});
 // a pair is the list of one reference (SPEC §6.2): its maps are reference 0's NNFs and the merged guide / err; it has no label map and no G_k / E_k of their own

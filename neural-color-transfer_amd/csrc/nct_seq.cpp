@@ -1,4 +1,4 @@
-// nct_seq.cpp — frame sequences (SPEC §6.3-§6.9, their region mask §6.13, its tracking §6.14, the snap §6.15 and several references §6.18): the state an open sequence keeps in the context's arena, what a level of a frame does between S1 and the finish,
+// nct_seq.cpp — frame sequences (SPEC §6.3-§6.9, their region mask §6.13, its tracking §6.14, the snap §6.15, several references §6.18 and their region masks §6.19): the state an open sequence keeps in the context's arena, what a level of a frame does between S1 and the finish,
 // the frame entry points — a full frame is a run of nct_pipeline.cpp's level loop — the propagated frame, the probe and the key-frame decision.
 #include "nct_pipeline.h"
 #include <cstring>
@@ -26,6 +26,10 @@ void seq_free(nct_ctx* ctx, pair_state* P) {
         if (q->keep_x[l]) ctx->release(q->keep_x[l]);
         if (q->keep_lab[l]) ctx->release(q->keep_lab[l]);
         if (q->keep_label[l]) ctx->release(q->keep_label[l]);
+        // the reference masks' level masks and the kept pull (SPEC §6.19) end with the sequence; the masks at the working size go back with the images (drop_images)
+        for (int k = 0; k < NCT_MAX_REFS; ++k) if (l < 4 && q->rq[k][l]) ctx->release(q->rq[k][l]);
+        if (q->keep_pull[l]) ctx->release(q->keep_pull[l]);
+        if (q->pull_alt[l]) ctx->release(q->pull_alt[l]);
     }
     // the sequence's region mask (SPEC §6.13 rule 1) ends with it
     if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
@@ -269,6 +273,72 @@ int nct_seq_get_region(nct_ctx* ctx, uint8_t* mask_out, int* age) {
     return NCT_OK;
 }
 
+// what the sequence holds of reference k's mask goes back to the arena, and with the last mask the kept pull (the caller has waited for the stream)
+static void seq_ref_mask_drop(nct_ctx* ctx, pair_state* P, seq_state* q, int k) {
+    if (P->rmask[k]) { ctx->release(P->rmask[k]); P->rmask[k] = nullptr; }
+    for (int l = 0; l < 4; ++l) if (q->rq[k][l]) { ctx->release(q->rq[k][l]); q->rq[k][l] = nullptr; }
+    if (P->ref_masked()) return;
+    for (int l = 0; l < 5; ++l) {
+        if (q->keep_pull[l]) { ctx->release(q->keep_pull[l]); q->keep_pull[l] = nullptr; }
+        if (q->pull_alt[l]) { ctx->release(q->pull_alt[l]); q->pull_alt[l] = nullptr; }
+    }
+}
+
+// reference k's mask onto the device at the reference's working size (a full-resolution sequence: uploaded as it came and shrunk there, as its image was), its level
+// masks by SPEC §6.12 rule 1 on the reference's level grids, and — with the first mask — the two maps per level run of the kept pull
+static int seq_ref_mask_upload(nct_ctx* ctx, pair_state* P, seq_state* q, int k, const uint8_t* mask) {
+    const hipStream_t s = ctx->stream;
+    if (!P->rmask[k] && !(P->rmask[k] = (uint8_t*)ctx->alloc((size_t)P->rh[k] * P->rw[k]))) return NCT_ERR_HIP;
+    for (int l = 0; l < 4; ++l) if (!q->rq[k][l] && !(q->rq[k][l] = (uint8_t*)ctx->alloc((size_t)q->bh[k][l] * q->bw[k][l]))) return NCT_ERR_HIP;
+    for (int l = 0; l < q->prm.levels; ++l) {
+        const size_t n = (size_t)q->ah[l] * q->aw[l];
+        if (!q->keep_pull[l] && !(q->keep_pull[l] = (uint8_t*)ctx->alloc(n))) return NCT_ERR_HIP;
+        if (!q->pull_alt[l] && !(q->pull_alt[l] = (uint8_t*)ctx->alloc(n))) return NCT_ERR_HIP;
+    }
+    if (q->rh0[k] == P->rh[k] && q->rw0[k] == P->rw[k]) NCT_H2D(P->rmask[k], mask, (size_t)P->rh[k] * P->rw[k]);
+    else {
+        DevBuf<uint8_t> q0(ctx, (size_t)q->rh0[k] * q->rw0[k]);
+        if (!q0.ok()) return NCT_ERR_HIP;
+        NCT_H2D(q0, mask, (size_t)q->rh0[k] * q->rw0[k]);
+        NCT_TRY(nctk_resize_u8c1(ctx, s, q0, q->rh0[k], q->rw0[k], P->rmask[k], P->rh[k], P->rw[k]));
+    }
+    const uint8_t* img = P->rmask[k];
+    for (int l = 3; l >= 0; --l) {
+        NCT_TRY(nctk_resize_u8c1(ctx, s, img, q->bh[k][l + 1], q->bw[k][l + 1], q->rq[k][l], q->bh[k][l], q->bw[k][l]));
+        img = q->rq[k][l];
+    }
+    NCT_SYNC();
+    return NCT_OK;
+}
+
+// SPEC §6.19: reference k's region mask on the open sequence, sticky from the next frame on; NULL removes it. Any call makes the kept pull stale: the next full frame
+// keeps its merged pull as it is, and a propagated frame before that is refused
+int nct_seq_set_ref_region(nct_ctx* ctx, int k, const uint8_t* mask, const nct_region_params* region) {
+    NCT_CTX_ENTER();
+    pair_state* P = (pair_state*)ctx->pair;
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_set_ref_region: no sequence is open (nct_seq_begin first)");
+    NCT_REQUIRE(k >= 0 && k < P->K, "seq_set_ref_region: k = %d is not one of the sequence's %d references", k, P->K);
+    NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "seq_set_ref_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
+    seq_state* q = P->seq;
+    // the state stays; what the last frame left is no longer the result of these settings
+    P->finished = false;
+    q->pull_kept = false;
+    NCT_SYNC();
+    if (P->fin_mask) { ctx->release(P->fin_mask); P->fin_mask = nullptr; }
+    if (!mask) seq_ref_mask_drop(ctx, P, q, k);
+    else {
+        const int rc = seq_ref_mask_upload(ctx, P, q, k, mask);
+        if (rc) {
+            // a device error half way: no mask is better than a block of unknown bytes
+            (void)hipStreamSynchronize(ctx->stream);
+            seq_ref_mask_drop(ctx, P, q, k);
+            return rc;
+        }
+    }
+    if (region) P->protect = region->protect;
+    return NCT_OK;
+}
+
 // the references once, each: upload, pyramid (main.cu:104-108), one VGG19 forward with all five taps kept channel-last; and the per-level state. One reference
 // (nct_seq_begin) requests what it always did, in the same order; several (SPEC §6.18) also the label map of every level run
 // rh0 x rw0: a reference as the caller holds it — larger than rh x rw only in a full-resolution sequence, which shrinks it on the device (SPEC §6.9)
@@ -280,7 +350,7 @@ static int seq_prepare(nct_ctx* ctx, pair_state* P, seq_state* q, int K, const u
     if (!P->src) return NCT_ERR_HIP;
     for (int k = 0; k < K; ++k) if (!(P->ref[k] = (uint8_t*)ctx->alloc((size_t)rh[k] * rw[k] * 3))) return NCT_ERR_HIP;
     P->sh = sh; P->sw = sw; P->K = K;
-    for (int k = 0; k < K; ++k) { P->rh[k] = rh[k]; P->rw[k] = rw[k]; }
+    for (int k = 0; k < K; ++k) { P->rh[k] = rh[k]; P->rw[k] = rw[k]; q->rh0[k] = rh0[k]; q->rw0[k] = rw0[k]; }
     for (int l = 0; l < 5; ++l) {
         const size_t n = (size_t)q->ah[l] * q->aw[l];
         for (int k = 0; k < K; ++k) {
@@ -408,9 +478,11 @@ static int seq_upload_frame(nct_ctx* ctx, pair_state* P, seq_state* q, const uin
 }
 
 // A full frame of the open sequence, the body of every nct_seq_frame*_levels form. mlv (nullable): the level report — a pair's (as_pair: it came as nct_pair_levels, which
-// describes one reference) or the list's; color (nullable): the colour stage's maps; hold_levels (nullable; SPEC §6.18): the held selection's report
+// describes one reference) or the list's; color (nullable): the colour stage's maps; hold_levels (nullable; SPEC §6.18): the held selection's report;
+// ref_region_levels, pull_levels (nullable; SPEC §6.19): the report of a frame with a reference mask, refused without one
 static int seq_frame_run(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_multi_levels* mlv, const nct_color_stages* const* color,
-                         bool as_pair, const nct_seq_levels* seq_levels, const nct_region_levels* region_levels, const nct_seq_hold_levels* hold_levels) {
+                         bool as_pair, const nct_seq_levels* seq_levels, const nct_region_levels* region_levels, const nct_seq_hold_levels* hold_levels,
+                         const nct_ref_region_levels* ref_region_levels = nullptr, const nct_seq_pull_levels* pull_levels = nullptr) {
     NCT_CTX_ENTER();
     pair_state* P = (pair_state*)ctx->pair;
     if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_frame: no sequence is open (nct_seq_begin first)");
@@ -428,11 +500,15 @@ static int seq_frame_run(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr,
     nct_ref_region_levels qlv;
     if (region_levels) { qlv = ref_region_levels_of(*region_levels); x.qlv = &qlv; }
     if (region_levels && !P->mask && !q->model_rows) x.refusal = "seq_frame: region levels asked for, but no region mask is set (nct_seq_set_region first)";
+    if (ref_region_levels) x.qlv = ref_region_levels;
+    x.plv = pull_levels;
+    if ((ref_region_levels || pull_levels) && !P->ref_masked()) x.refusal = "seq_frame: reference region levels asked for, but no reference mask is set (nct_seq_set_ref_region first)";
     if (rc == NCT_OK) rc = process_resident(ctx, &q->prm, timing, x);
     // a frame that failed may have replaced the state of some levels only: the next frame starts over
     q->gap = 0; q->acc = 0;                                      // a full frame (and a failed one: the next is a first frame) starts the count over
     if (rc) { q->frames = 0; return rc; }
     q->frames += 1;
+    q->pull_kept = P->ref_masked();                              // SPEC §6.19: every level run now keeps this frame's P'
     if (!q->target()) return nct_pair_download(ctx, out_bgr);
     NCT_D2H(out_bgr, P->full_out, (size_t)q->full.H * q->full.W * 3);
     NCT_SYNC();
@@ -461,6 +537,13 @@ int nct_seq_frame_multi_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* ou
     return seq_frame_run(ctx, src_bgr, out_bgr, timing, levels, nullptr, false, seq_levels, nullptr, hold_levels);
 }
 
+// SPEC §6.19: the multi-stage form plus the report of a frame with a reference mask
+int nct_seq_frame_ref_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_multi_levels* levels,
+                                    const nct_color_stages* const* color, const nct_seq_levels* seq_levels, const nct_seq_hold_levels* hold_levels,
+                                    const nct_ref_region_levels* region_levels, const nct_seq_pull_levels* pull_levels) {
+    return seq_frame_run(ctx, src_bgr, out_bgr, timing, levels, color, false, seq_levels, nullptr, hold_levels, region_levels, pull_levels);
+}
+
 int nct_seq_frame(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing) {
     return nct_seq_frame_levels(ctx, src_bgr, out_bgr, timing, nullptr, nullptr);
 }
@@ -470,8 +553,14 @@ int nct_seq_frame(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pa
 // on this path nothing reads L_(t-1) but the search, which reads its packed form
 // With a region mask (SPEC §6.13 rule 3) all of that runs unchanged on the unmixed state; then the last level run's X'_t is mixed with that level's mask into scratch of
 // the call, the finish reads the mixed map and composes. Only the level masks down to that level are built. rlv (nullable): where the mixed map and those masks go
-static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* slv, const nct_region_levels* rlv) {
+// With a reference mask (SPEC §6.19) the kept pull P' of every level run is carried like the labels; the top level run's P' takes P_l's place in SPEC §6.12 rules 4-5: the
+// mix mask is min(P', the source's level mask), the compose mask P' at the size the finish targets, then the minimum with the source mask there — kept as fin_mask for
+// nct_pair_fit_lut. plv (nullable): where the carried maps go
+static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* slv, const nct_ref_region_levels* rlv,
+                         const nct_seq_pull_levels* plv) {
     const hipStream_t s = ctx->stream;
+    const bool ref_masked = P->ref_masked();
+    if (P->fin_mask) { ctx->release(P->fin_mask); P->fin_mask = nullptr; }
     const nct_params& prm = q->prm;
     const int H = P->sh, W = P->sw, top = prm.levels - 1;
     const size_t N = (size_t)H * W;
@@ -502,7 +591,13 @@ static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out
                 NCT_TRY(nctk_label_carry(ctx, s, q->keep_label[l], h, w, q->field[l], carried));
                 NCT_HIP(hipMemcpyAsync(q->keep_label[l], carried, n, hipMemcpyDeviceToDevice, s));
             }
+            if (ref_masked) {
+                // SPEC §6.19: the kept pull follows the field as well — the same byte gather, into the sequence's second map; the two change places
+                NCT_TRY(nctk_label_carry(ctx, s, q->keep_pull[l], h, w, q->field[l], q->pull_alt[l]));
+                std::swap(q->keep_pull[l], q->pull_alt[l]);
+            }
         }
+        if (ref_masked && plv) NCT_TRY(dbg_copy(ctx, s, plv->p_held[l], q->keep_pull[l], n));
         if (slv) {
             if (slv->ab_blend[l]) NCT_HIP(hipMemcpyAsync(slv->ab_blend[l], q->keep_x[l], sizeof(double) * 6 * n, hipMemcpyDeviceToHost, s));
             if (slv->motion[l]) {
@@ -527,25 +622,56 @@ static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out
     const double* x_fin = q->keep_x[top];
     DevBuf<uint8_t> mpyr[4]; DevBuf<double> x_mix;
     const bool exact = q->target() && q->full.finish == NCT_FINISH_EXACT;
-    const region_fin rg{exact ? q->full.mask : P->mask, P->src, P->protect};
+    region_fin rg{exact ? q->full.mask : P->mask, P->src, P->protect};
+    const uint8_t* mimg[5] = {};
     if (P->mask) {
-        const uint8_t* mimg[5]; mimg[4] = P->mask;
+        mimg[4] = P->mask;
         for (int l = 3; l >= top; --l) {
             if (!mpyr[l].alloc(ctx, (size_t)q->ah[l] * q->aw[l])) return NCT_ERR_HIP;
             NCT_TRY(nctk_resize_u8c1(ctx, s, mimg[l + 1], q->ah[l + 1], q->aw[l + 1], mpyr[l], q->ah[l], q->aw[l]));
             mimg[l] = mpyr[l];
         }
-        const size_t n = (size_t)q->ah[top] * q->aw[top];
+    }
+    DevBuf<uint8_t> m_top, f_work;
+    full_target up_target;
+    const full_target* target = q->target();
+    if (P->mask || ref_masked) {
+        const int h = q->ah[top], w = q->aw[top];
+        const size_t n = (size_t)h * w;
+        const uint8_t* m_l = mimg[top];
+        if (ref_masked) {
+            const uint8_t* const p_top = q->keep_pull[top];
+            m_l = p_top;
+            if (P->mask) {
+                if (!m_top.alloc(ctx, n)) return NCT_ERR_HIP;
+                NCT_TRY(nctk_region_merge(ctx, s, &p_top, 1, nullptr, mimg[top], (int)n, nullptr, m_top));
+                m_l = m_top;
+            }
+            const bool up = target && !exact;
+            const int fh = exact ? q->full.H : H, fw = exact ? q->full.W : W;
+            uint8_t* f = nullptr;
+            if (up) { if (!f_work.alloc(ctx, N)) return NCT_ERR_HIP; f = f_work; }
+            else { if (!(P->fin_mask = (uint8_t*)ctx->alloc((size_t)fh * fw))) return NCT_ERR_HIP; f = P->fin_mask; }
+            NCT_TRY(nctk_region_upsize_min(ctx, s, p_top, h, w, rg.mask, f, fh, fw));
+            rg.mask = f;
+            if (up) {
+                if (!(P->fin_mask = (uint8_t*)ctx->alloc((size_t)q->full.H * q->full.W))) return NCT_ERR_HIP;
+                NCT_TRY(nctk_region_upsize_min(ctx, s, p_top, h, w, q->full.mask, P->fin_mask, q->full.H, q->full.W));
+                up_target = q->full; up_target.mask = P->fin_mask; target = &up_target;
+            }
+            if (rlv) NCT_TRY(dbg_copy(ctx, s, rlv->mask_full[top], rg.mask, (size_t)fh * fw));
+        }
         if (!x_mix.alloc(ctx, 6 * n)) return NCT_ERR_HIP;
-        NCT_TRY(nctk_region_mix(ctx, s, q->keep_x[top], mimg[top], q->ah[top], q->aw[top], x_mix));
+        NCT_TRY(nctk_region_mix(ctx, s, q->keep_x[top], m_l, h, w, x_mix));
         x_fin = x_mix;
         if (rlv) {
             NCT_TRY(dbg_copy(ctx, s, rlv->ab_mix[top], (double*)x_mix, 6 * n));
-            for (int l = top; l < 5; ++l) NCT_TRY(dbg_copy(ctx, s, rlv->mask[l], mimg[l], (size_t)q->ah[l] * q->aw[l]));
+            if (ref_masked) NCT_TRY(dbg_copy(ctx, s, rlv->mask[top], m_l, n));
+            else for (int l = top; l < 5; ++l) NCT_TRY(dbg_copy(ctx, s, rlv->mask[l], mimg[l], (size_t)q->ah[l] * q->aw[l]));
         }
     }
-    NCT_TRY(finish_level(ctx, s, x_fin, q->ah[top], q->aw[top], H, W, s_lab_full, out_lab, P->out, q->target(), fl, nct_color_params_of(prm), timing ? &dbg : nullptr, nct_cube_form(prm),
-                         P->mask ? &rg : nullptr));
+    NCT_TRY(finish_level(ctx, s, x_fin, q->ah[top], q->aw[top], H, W, s_lab_full, out_lab, P->out, target, fl, nct_color_params_of(prm), timing ? &dbg : nullptr, nct_cube_form(prm),
+                         P->mask || ref_masked ? &rg : nullptr));
     if (timing) timing->wls_iters[top] = *std::max_element(wls_it, wls_it + 6);
     MARK(NCT_ST_COLOR, top);
     if (q->target()) NCT_D2H(out_bgr, P->full_out, (size_t)q->full.H * q->full.W * 3);
@@ -558,8 +684,9 @@ int nct_seq_frame_propagate_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t
     return nct_seq_frame_propagate_region_levels(ctx, src_bgr, out_bgr, timing, seq_levels, nullptr);
 }
 
-int nct_seq_frame_propagate_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* seq_levels,
-                                          const nct_region_levels* region_levels) {
+// the body of the propagated forms. region_levels: a source mask's report (SPEC §6.13); ref_region_levels, pull_levels: a reference mask's (SPEC §6.19); all nullable
+static int seq_propagate_form(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* seq_levels, const nct_region_levels* region_levels,
+                              const nct_ref_region_levels* ref_region_levels, const nct_seq_pull_levels* pull_levels) {
     NCT_CTX_ENTER();
     pair_state* P = (pair_state*)ctx->pair;
     if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_frame_propagate: no sequence is open (nct_seq_begin first)");
@@ -567,15 +694,32 @@ int nct_seq_frame_propagate_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, 
     if (q->frames == 0) return ctx->fail(NCT_ERR_STATE, "seq_frame_propagate: the sequence has no state to propagate (the first frame after nct_seq_begin / nct_seq_reset is nct_seq_frame's)");
     NCT_REQUIRE(src_bgr && out_bgr, "seq_frame_propagate: null image");
     if (region_levels && !P->mask) return ctx->fail(NCT_ERR_STATE, "seq_frame_propagate: region levels asked for, but no region mask is set (nct_seq_set_region first)");
+    if ((ref_region_levels || pull_levels) && !P->ref_masked())
+        return ctx->fail(NCT_ERR_STATE, "seq_frame_propagate: reference region levels asked for, but no reference mask is set (nct_seq_set_ref_region first)");
+    // SPEC §6.19: a reference mask whose pull no full frame has kept yet (before the first one, or since a set, replace or remove) has nothing to carry
+    if (P->ref_masked() && !q->pull_kept)
+        return ctx->fail(NCT_ERR_STATE, "seq_frame_propagate: a reference mask is set but no full frame has pulled it yet: a full frame (nct_seq_frame) must come first");
+    nct_ref_region_levels qlv;
+    if (region_levels) { qlv = ref_region_levels_of(*region_levels); ref_region_levels = &qlv; }
     run_clock clock(ctx, timing, q->prm.flags);
     int rc = seq_upload_frame(ctx, P, q, src_bgr);
-    if (rc == NCT_OK) rc = propagate_run(ctx, P, q, out_bgr, timing, seq_levels, region_levels);
+    if (rc == NCT_OK) rc = propagate_run(ctx, P, q, out_bgr, timing, seq_levels, ref_region_levels, pull_levels);
     if (rc == NCT_OK) P->finished = true;                        // nct_seq_set_region cleared it: this frame is the result of the new settings
     clock.stop();
     // a frame that failed may have replaced the state of some levels only: the next frame starts over
     if (rc) { (void)hipStreamSynchronize(ctx->stream); q->frames = 0; q->gap = 0; q->acc = 0; return rc; }
     q->frames += 1; q->gap += 1;
     return clock.read(false);
+}
+
+int nct_seq_frame_propagate_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* seq_levels,
+                                          const nct_region_levels* region_levels) {
+    return seq_propagate_form(ctx, src_bgr, out_bgr, timing, seq_levels, region_levels, nullptr, nullptr);
+}
+
+int nct_seq_frame_propagate_ref_region_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* seq_levels,
+                                              const nct_ref_region_levels* region_levels, const nct_seq_pull_levels* pull_levels) {
+    return seq_propagate_form(ctx, src_bgr, out_bgr, timing, seq_levels, nullptr, region_levels, pull_levels);
 }
 
 int nct_seq_frame_propagate(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing) {
@@ -664,6 +808,8 @@ int nct_seq_frame_auto(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, n
     nct_seq_auto used; nct_seq_decision d;
     NCT_TRY(seq_probe_decide(ctx, "seq_frame_auto", src_bgr, a, true, &used, &d));
     seq_state* q = ((pair_state*)ctx->pair)->seq;
+    // SPEC §6.19: a reference mask whose pull no full frame has kept yet has nothing to carry — the one place where a decision depends on a mask
+    if (d.kind == NCT_SEQ_PROPAGATED && ((pair_state*)ctx->pair)->ref_masked() && !q->pull_kept) d.kind = NCT_SEQ_KEY;
     if (out) *out = d;
     if (d.kind == NCT_SEQ_PROPAGATED) {
         const unsigned long long acc = q->acc + d.change.changed;

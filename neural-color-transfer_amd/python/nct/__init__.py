@@ -165,6 +165,13 @@ SIGNATURES = {
     "nct_lut_fit_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_lut_fit_masked_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_set_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_set_ref_region": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "nct_seq_pull_hold": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                    C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_pull_hold_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_frame_ref_region_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_seq_frame_propagate_ref_region_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_region_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_matte_warp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "nct_seq_matte_warp_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -578,6 +585,11 @@ class SeqHold(C.Structure):
 class SeqHoldLevels(C.Structure):
     """struct nct_seq_hold_levels (include/nct.h)."""
     _fields_ = [("free_label", C.c_void_p * 5), ("margin", C.c_void_p * 5)]
+
+
+class SeqPullLevels(C.Structure):
+    """struct nct_seq_pull_levels (include/nct.h; SPEC §6.19)."""
+    _fields_ = [("p_free", C.c_void_p * 5), ("p_held", C.c_void_p * 5)]
 
 
 class SeqLevels(C.Structure):
@@ -1255,6 +1267,7 @@ class Context:
         self._seq_shapes = (tuple(src_shape[:2]), r.shape[:2], prm.levels)
         self._seq_work = None
         self._seq_multi = (tuple(src_shape[:2]), [r.shape[:2]])
+        self._seq_ref_arrive = [r.shape[:2]]; self._seq_finish = None
 
     def seq_begin_fullres(self, ref_bgr, src_shape, max_side=1000, finish=0, params=None, tau=None, sigma=None):
         """nct_seq_begin_fullres (SPEC §6.9): frames of src_shape[:2] and the reference arrive at their original size and are shrunk to working_size(..., max_side) on
@@ -1271,6 +1284,7 @@ class Context:
         self._seq_shapes = (tuple(src_shape[:2]), r.shape[:2], prm.levels)
         self._seq_work = (working_size(int(src_shape[0]), int(src_shape[1]), max_side), working_size(r.shape[0], r.shape[1], max_side))
         self._seq_multi = (self._seq_work[0], [self._seq_work[1]])
+        self._seq_ref_arrive = [r.shape[:2]]; self._seq_finish = int(finish)
 
     # ---- sequences over several references (SPEC §6.18)
     def _seq_multi_args(self, params, tau, sigma, hold):
@@ -1294,6 +1308,7 @@ class Context:
         self._seq_shapes = (tuple(src_shape[:2]), keep[0].shape[:2], prm.levels)
         self._seq_work = None
         self._seq_multi = (tuple(src_shape[:2]), [a.shape[:2] for a in keep])
+        self._seq_ref_arrive = [a.shape[:2] for a in keep]; self._seq_finish = None
 
     def seq_begin_multi_fullres(self, refs_bgr, src_shape, max_side=1000, finish=0, params=None, tau=None, sigma=None, hold=None):
         """nct_seq_begin_multi_fullres: seq_begin_fullres over a list of references"""
@@ -1306,6 +1321,7 @@ class Context:
         self._seq_shapes = (tuple(src_shape[:2]), keep[0].shape[:2], prm.levels)
         self._seq_work = (work, rwork[0])
         self._seq_multi = (work, rwork)
+        self._seq_ref_arrive = [a.shape[:2] for a in keep]; self._seq_finish = int(finish)
 
     def seq_frame_multi_levels(self, src_bgr, want_color=True):
         """nct_seq_frame_multi[_stage]_levels -> (result, dict): multi_run_levels' lists at the working size ("ann" … "ref_err" as [k][l]; "label", "guide", "err", "result"
@@ -1400,6 +1416,131 @@ class Context:
         else:
             m = _mask_arg(mask, shp[0], "seq_set_region")
         self._chk(self._l.nct_seq_set_region(self._h, m.ctypes.data, C.addressof(rg)))
+
+    # ---- reference region masks in sequences (SPEC §6.19)
+    def seq_set_ref_region(self, k, mask, protect=None):
+        """nct_seq_set_ref_region on the open sequence: reference k's mask [rh, rw] bytes at the size that reference arrived, or None to remove it. Sticky until replaced or
+        removed; protect None leaves the run's protect as it is"""
+        rg = None if protect is None else _region_params(protect)
+        if mask is None:
+            self._chk(self._l.nct_seq_set_ref_region(self._h, int(k), None, None if rg is None else C.addressof(rg)))
+            return
+        shapes = getattr(self, "_seq_ref_arrive", None) or []
+        m = np.ascontiguousarray(mask, np.uint8)
+        if 0 <= k < len(shapes):                        # the library refuses a k out of range and a call without a sequence; the mask is then never read
+            m = _mask_arg(mask, shapes[k], "seq_set_ref_region")
+        self._chk(self._l.nct_seq_set_ref_region(self._h, int(k), m.ctypes.data, None if rg is None else C.addressof(rg)))
+
+    def seq_pull_hold(self, pulled, label, prev, lab, lab_prev, field=None, src_mask=None, tau=0.7, sigma=10.0, dev=False, alias=False, want=("p", "m", "p_free"), shape=None):
+        """nct_seq_pull_hold (dev: its _dev form on arena blocks; alias: p_out is prev's block, which is an error): K pulled masks [h, w] bytes (None entries: 255), the label
+        map [h, w] (None with one reference), the kept map, the two frames' 8-bit Lab level images, a field int16 [h, w, 2] or None, the source level mask or None ->
+        dict of the outputs named in `want` ("p" is always written). shape: the grid, where no array gives it"""
+        ps = [None if q is None else np.ascontiguousarray(q, np.uint8) for q in pulled]
+        K = len(ps)
+        pv, l1, l0 = np.ascontiguousarray(prev, np.uint8), np.ascontiguousarray(lab, np.uint8), np.ascontiguousarray(lab_prev, np.uint8)
+        h, w = shape if shape is not None else pv.shape[:2]
+        lb = None if label is None else np.ascontiguousarray(label, np.uint8)
+        f = None if field is None else np.ascontiguousarray(field, np.int16)
+        ms = None if src_mask is None else np.ascontiguousarray(src_mask, np.uint8)
+        order = ("p", "m", "p_free")
+        want = [k for k in order if k in want or k == "p"]
+        if not dev:
+            pp = (C.c_void_p * max(K, 1))(*[_ptr(q) for q in ps])
+            outs = {k: np.empty((h, w), np.uint8) for k in want}
+            self._chk(self._l.nct_seq_pull_hold(self._h, pp, K, _ptr(lb), pv.ctypes.data, l1.ctypes.data, l0.ctypes.data, _ptr(f), _ptr(ms), int(h), int(w), float(tau), float(sigma),
+                                                *[_ptr(outs.get(k)) for k in order]))
+            return outs
+        dp = [None if q is None else self.dev_upload(q) for q in ps]
+        opt = {"label": lb, "field": f, "ms": ms}
+        dopt = {k: (None if a is None else self.dev_upload(a)) for k, a in opt.items()}
+        ins = [self.dev_upload(pv), self.dev_upload(l1), self.dev_upload(l0)]
+        dout = {k: self.dev_alloc(int(h) * int(w)) for k in want}
+        with self._blocks([b for b in dp if b is not None] + [b for b in dopt.values() if b is not None] + ins + list(dout.values())):
+            outp = [dout.get(k) for k in order]
+            if alias:
+                outp[0] = ins[0]
+            self._chk(self._l.nct_seq_pull_hold_dev(self._h, (C.c_void_p * max(K, 1))(*dp), K, dopt["label"], ins[0], ins[1], ins[2], dopt["field"], dopt["ms"], int(h), int(w),
+                                                    float(tau), float(sigma), *outp))
+            return {k: self.dev_download(dout[k], (h, w), np.uint8) for k in want}
+
+    def _ref_region_arrays(self, adims, bdims, levels, H, W):
+        """the report targets of a frame with a reference mask: RefRegionLevels and SeqPullLevels with their arrays, for the level runs"""
+        full = getattr(self, "_seq_work", None) is not None and getattr(self, "_seq_finish", None) == FINISH_EXACT
+        keep = {"ref_mask": [[np.zeros(d, np.uint8) for d in bd[:levels]] for bd in bdims], "pulled": [[np.zeros(d, np.uint8) for d in adims[:levels]] for _ in bdims],
+                "mask": [np.zeros(d, np.uint8) for d in adims[:levels]],
+                "mask_full": [np.zeros(self._seq_shapes[0] if (full and l == levels - 1) else (H, W), np.uint8) for l in range(levels)],
+                "ab_mix": [np.zeros((2, d[0] * d[1], 3)) for d in adims[:levels]],
+                "p_free": [np.zeros(d, np.uint8) for d in adims[:levels]], "p_held": [np.zeros(d, np.uint8) for d in adims[:levels]]}
+        rl, pl = RefRegionLevels(), SeqPullLevels()
+        for l in range(levels):
+            for k in range(len(bdims)):
+                rl.ref_mask[k][l] = keep["ref_mask"][k][l].ctypes.data; rl.pulled[k][l] = keep["pulled"][k][l].ctypes.data
+            rl.mask[l] = keep["mask"][l].ctypes.data; rl.mask_full[l] = keep["mask_full"][l].ctypes.data; rl.ab_mix[l] = keep["ab_mix"][l].ctypes.data
+            pl.p_free[l] = keep["p_free"][l].ctypes.data; pl.p_held[l] = keep["p_held"][l].ctypes.data
+        return keep, rl, pl
+
+    def seq_frame_ref_region_levels(self, src_bgr):
+        """nct_seq_frame_ref_region_levels -> (result, dict): seq_frame_multi_levels' dict without "color", plus per level that ran "ref_mask" and "pulled" ([k][l]; unmasked
+        references stay zero), "mask" (M_l), "mask_full" (F_l at the size the level's finish targets), "ab_mix", "p_free" (P_l) and "p_held" (P'_t)"""
+        s = self._seq_frame_arg(src_bgr, "seq_frame_ref_region_levels")
+        if getattr(self, "_seq_multi", None) is None:
+            raise NctError(-5, "seq_frame_ref_region_levels: no sequence is open (seq_begin first)")
+        (H, W), rshapes = self._seq_multi
+        levels = self._seq_shapes[2]
+        full = self._seq_work is not None
+        self._pair_shape, self._multi_shapes = (H, W, 3), [tuple(r) + (3,) for r in rshapes]
+        keep, lv = self._multi_levels_arrays()
+        adims = keep["adims"]
+        if full:
+            for l in range(5):
+                lv.result[l] = None
+            del keep["result"]
+        keep["ab_blend"] = [np.zeros((2, d[0] * d[1], 3)) for d in adims[:levels]]
+        keep["tau_map"] = [np.zeros(d) for d in adims[:levels]]
+        keep["motion"] = [np.zeros(d + (2,), np.int16) for d in adims[:levels]]
+        keep["free_label"] = [np.zeros(d, np.uint8) for d in adims[:levels]]
+        keep["margin"] = [np.zeros(d) for d in adims[:levels]]
+        sl, hl = SeqLevels(), SeqHoldLevels()
+        for l in range(levels):
+            sl.ab_blend[l] = keep["ab_blend"][l].ctypes.data; sl.tau_map[l] = keep["tau_map"][l].ctypes.data; sl.motion[l] = keep["motion"][l].ctypes.data
+            hl.free_label[l] = keep["free_label"][l].ctypes.data; hl.margin[l] = keep["margin"][l].ctypes.data
+        more, rl, pl = self._ref_region_arrays(adims, keep["bdims"], levels, H, W)
+        keep.update(more)
+        out = np.empty_like(s)
+        tm = PairTiming()
+        self._chk(self._l.nct_seq_frame_ref_region_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv), None, C.addressof(sl), C.addressof(hl),
+                                                          C.addressof(rl), C.addressof(pl)))
+        keep["timing"] = tm.as_dict()
+        return out, keep
+
+    def seq_frame_propagate_ref_region_levels(self, src_bgr):
+        """nct_seq_frame_propagate_ref_region_levels -> (result, dict): seq_frame_propagate_levels' dict plus "p_held" per level that ran and, for the last level run only
+        (zeros elsewhere), "mask", "mask_full" and "ab_mix" maps"""
+        s = self._seq_frame_arg(src_bgr, "seq_frame_propagate_ref_region_levels")
+        if getattr(self, "_seq_multi", None) is None:
+            raise NctError(-5, "seq_frame_propagate_ref_region_levels: no sequence is open (seq_begin first)")
+        (H, W), rshapes = self._seq_multi
+        levels = self._seq_shapes[2]
+        adims, bdims = [], [[] for _ in rshapes]
+        h, w, rs = H, W, [tuple(r) for r in rshapes]
+        for _ in range(5):
+            adims.insert(0, (h, w))
+            for k, r in enumerate(rs):
+                bdims[k].insert(0, r)
+            h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+            rs = [((r[0] - 1) // 2 + 1, (r[1] - 1) // 2 + 1) for r in rs]
+        keep = {"ab_blend": [np.zeros((2, d[0] * d[1], 3)) for d in adims[:levels]], "tau_map": [np.zeros(d) for d in adims[:levels]],
+                "motion": [np.zeros(d + (2,), np.int16) for d in adims[:levels]], "dims": adims}
+        sl = SeqLevels()
+        for l in range(levels):
+            sl.ab_blend[l] = keep["ab_blend"][l].ctypes.data; sl.tau_map[l] = keep["tau_map"][l].ctypes.data; sl.motion[l] = keep["motion"][l].ctypes.data
+        more, rl, pl = self._ref_region_arrays(adims, bdims, levels, H, W)
+        keep.update(more)
+        out = np.empty_like(s)
+        tm = PairTiming()
+        self._chk(self._l.nct_seq_frame_propagate_ref_region_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(sl), C.addressof(rl), C.addressof(pl)))
+        keep["timing"] = tm.as_dict()
+        return out, keep
 
     # ---- region tracking (SPEC §6.14)
     def seq_matte_warp(self, mask, field, dev=False, alias=False):
@@ -1867,6 +2008,7 @@ class Context:
         self._seq_shapes = None
         self._seq_work = None
         self._seq_multi = None
+        self._seq_ref_arrive = None
 
     def seq_set_motion(self, radius0=None, radius=None, penalty=None, off=False):
         """nct_seq_set_motion (SPEC §6.4): motion compensation of the open sequence from the next frame on; values left out are nct_seq_motion_default's (3, 1, 1).
