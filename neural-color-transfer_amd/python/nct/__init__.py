@@ -5,6 +5,7 @@ fallback anywhere in this package: if the library is missing or no HIP device is
 Function names and argument meaning mirror include/nct.h, which cites the reference seam each one replaces
 (code/windows/neural_color_transfer/source/main.cu).
 """
+import collections
 import contextlib
 import ctypes as C
 import os
@@ -655,6 +656,122 @@ class ColorStages(C.Structure):
                 ("ab_wls", C.c_void_p), ("cg_iters", C.c_void_p), ("wls_iters", C.c_void_p)]
 
 
+# ---- the level reports: the host arrays the report structs above point into, described once per field and allocated by one function
+def _level_dims(h, w):
+    """the five level grids (h, w) of an h x w image, coarsest first"""
+    dims = []
+    for _ in range(5):
+        dims.insert(0, (h, w)); h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    return dims
+
+
+# src[l] / ref[k][l]: the level grids of the source and of reference k; work: the size the pyramid runs at; finish[l]: the size level l's finish targets
+_Grids = collections.namedtuple("_Grids", "src ref work finish")
+
+
+def _grids(src_shape, ref_shapes, finish=None):
+    H, W = src_shape[:2]
+    return _Grids(_level_dims(H, W), [_level_dims(*r[:2]) for r in ref_shapes], (H, W), finish or [(H, W)] * 5)
+
+
+_SHAPES = {                                                       # the grid a field lives on -> its shape at level l (of reference k)
+    "src": lambda g, l, k: g.src[l],                              # a map on the source level
+    "src3": lambda g, l, k: g.src[l] + (3,),                      # an image on the source level
+    "ref": lambda g, l, k: g.ref[k][l],                           # a map on the reference level
+    "coef": lambda g, l, k: (2, g.src[l][0] * g.src[l][1], 3),    # a coefficient map [2, h*w, 3] of the source level
+    "field": lambda g, l, k: g.src[l] + (2,),                     # a field of (my, mx) on the source level
+    "work3": lambda g, l, k: g.work + (3,),                       # an image at the working size
+    "work_coef": lambda g, l, k: (2, g.work[0] * g.work[1], 3),   # a coefficient map of the working size
+    "work_flat": lambda g, l, k: (g.work[0] * g.work[1],),        # a value per working-size pixel
+    "finish": lambda g, l, k: g.finish[l],                        # a map at the size the level's finish targets
+}
+ALL, RUN, ONE = "all five levels", "the levels that run", "one array"
+# a report field: its dtype; its grid (a _SHAPES key, or a fixed shape); whether the struct holds it per reference ([k][l]); the levels it spans
+_Field = collections.namedtuple("_Field", "dtype grid per_ref span", defaults=(False, ALL))
+_REPORT = {                                                       # struct -> field -> _Field, in the struct's order. PairLevels.color points at ColorStages: _pair_report
+    PairLevels: {"ann": _Field(np.uint32, "src"), "bnn": _Field(np.uint32, "ref"), "annd": _Field(np.float32, "src"), "bnnd": _Field(np.float32, "ref"),
+                 "guide": _Field(np.uint8, "src3"), "err": _Field(np.float32, "src"), "result": _Field(np.uint8, "work3"), "labels": _Field(np.int32, "src", span=ONE)},
+    MultiLevels: {"ann": _Field(np.uint32, "src", True), "bnn": _Field(np.uint32, "ref", True), "annd": _Field(np.float32, "src", True), "bnnd": _Field(np.float32, "ref", True),
+                  "ref_guide": _Field(np.uint8, "src3", True), "ref_err": _Field(np.float32, "src", True), "label": _Field(np.uint8, "src"), "guide": _Field(np.uint8, "src3"),
+                  "err": _Field(np.float32, "src"), "result": _Field(np.uint8, "work3"), "labels": _Field(np.int32, "src", span=ONE)},
+    ColorStages: {"ab_local": _Field(np.float64, "coef", span=ONE), "ab_nonlocal": _Field(np.float64, "coef", span=ONE), "ab_up": _Field(np.float64, "work_coef", span=ONE),
+                  "roughness": _Field(np.float64, "work_flat", span=ONE), "ab_wls": _Field(np.float64, "work_coef", span=ONE), "cg_iters": _Field(np.int32, (3,), span=ONE),
+                  "wls_iters": _Field(np.int32, (6,), span=ONE)},
+    SeqLevels: {"ab_blend": _Field(np.float64, "coef", span=RUN), "tau_map": _Field(np.float64, "src", span=RUN), "motion": _Field(np.int16, "field", span=RUN)},
+    SeqHoldLevels: {"free_label": _Field(np.uint8, "src", span=RUN), "margin": _Field(np.float64, "src", span=RUN)},
+    RegionLevels: {"ab_mix": _Field(np.float64, "coef", span=RUN), "mask": _Field(np.uint8, "src")},
+    RefRegionLevels: {"ref_mask": _Field(np.uint8, "ref", True, RUN), "pulled": _Field(np.uint8, "src", True, RUN), "mask": _Field(np.uint8, "src", span=RUN),
+                      "mask_full": _Field(np.uint8, "finish", span=RUN), "ab_mix": _Field(np.float64, "coef", span=RUN)},
+    SeqPullLevels: {"p_free": _Field(np.uint8, "src", span=RUN), "p_held": _Field(np.uint8, "src", span=RUN)},
+}
+
+
+def _report(cls, g, levels=5, level=0):
+    """the arrays a report struct points into on the grids g -> (dict of them by field, zero-filled; the struct, its pointers set). levels: how many levels run (a RUN
+    field stops there); level: the level a ONE field describes"""
+    keep, st = {}, cls()
+    for name, f in _REPORT[cls].items():
+        def new(l, k=0):
+            return np.zeros(f.grid if isinstance(f.grid, tuple) else _SHAPES[f.grid](g, l, k), f.dtype)
+        n = levels if f.span == RUN else 5
+        if f.span == ONE:
+            keep[name] = new(level)
+            setattr(st, name, keep[name].ctypes.data)
+        elif f.per_ref:
+            keep[name] = [[new(l, k) for l in range(n)] for k in range(len(g.ref))]
+            for k, row in enumerate(keep[name]):
+                for l, a in enumerate(row):
+                    getattr(st, name)[k][l] = a.ctypes.data
+        else:
+            keep[name] = [new(l) for l in range(n)]
+            for l, a in enumerate(keep[name]):
+                getattr(st, name)[l] = a.ctypes.data
+    return keep, st
+
+
+def _reports(g, levels, *classes):
+    """several report structs on the same grids -> (one dict of all their arrays, the structs in that order)"""
+    keep, structs = {}, []
+    for cls in classes:
+        more, st = _report(cls, g, levels)
+        keep.update(more); structs.append(st)
+    return keep, structs
+
+
+def _multi_reports(g, levels, *more):
+    """MultiLevels and the structs in `more` -> _reports' pair, with the grids as "adims" ([l]) and "bdims" ([k][l])"""
+    keep, structs = _reports(g, levels, MultiLevels, *more)
+    keep["adims"], keep["bdims"] = g.src, g.ref
+    return keep, structs
+
+
+def _color_stages(g, n, levels):
+    """the colour stage's report of the n coarsest levels -> (a dict of arrays per level; the void*[5] of nct_color_stages, set for the levels that run; the structs
+    it points at, which the caller holds until its call has returned)"""
+    made = [_report(ColorStages, g, level=l) for l in range(n)]
+    structs = [st for _, st in made]
+    return [d for d, _ in made], (C.c_void_p * 5)(*[C.addressof(st) if i < levels else None for i, st in enumerate(structs)]), structs
+
+
+def _pair_report(g, levels, want_color):
+    """PairLevels -> (dict of its arrays + "dims", the struct, what must stay alive until the call returns). want_color: "color" for all five levels, wired for the
+    levels that run, and "labels"; without it both pointers stay NULL"""
+    keep, lv = _report(PairLevels, g)
+    hold = None
+    if want_color:
+        keep["color"], lv.color, hold = _color_stages(g, 5, levels)
+    else:
+        del keep["labels"]
+        lv.labels = None
+    keep["dims"] = [a + b for a, b in zip(g.src, g.ref[0])]
+    return keep, lv, hold
+
+
+# the open sequence as the binding knows it: the (h, w) the frames and each reference arrive at, the (h, w) the pyramid runs at (the same unless the sequence is
+# full-resolution), the levels that run, and the finish of a full-resolution sequence (None otherwise)
+_Seq = collections.namedtuple("_Seq", "arrive ref_arrive work ref_work levels finish")
+
+
 class Context:
     """One context per GPU / process (include/nct.h: not thread-safe)."""
 
@@ -836,10 +953,7 @@ class Context:
         """-> list of `deepest_tap` CHW fp32 arrays (tap 1 = conv1_1 … tap 5 = conv5_1)."""
         img = np.ascontiguousarray(bgr, np.uint8)
         h, w = img.shape[:2]
-        outs, hh, ww = [], h, w
-        for t in range(deepest_tap):
-            outs.append(np.empty((self.TAP_C[t], hh, ww), np.float32))
-            hh, ww = (hh - 1) // 2 + 1, (ww - 1) // 2 + 1
+        outs = [np.empty((self.TAP_C[t],) + hw, np.float32) for t, hw in enumerate(_level_dims(h, w)[::-1][:deepest_tap])]
         ptrs = (C.c_void_p * 5)(*([o.ctypes.data for o in outs] + [None] * (5 - deepest_tap)))
         dims = np.zeros(15, np.int32)
         self._chk(self._l.nct_vgg19_features(self._h, img, h, w, w * 3, deepest_tap, ptrs, _ptr(dims)))
@@ -1126,48 +1240,16 @@ class Context:
     def multi_run_levels(self, params=None):
         """nct_multi_run_levels on the uploaded list -> dict: per reference and level "ann", "bnn", "annd", "bnnd", "ref_guide", "ref_err" ([k][l]); per level the merged
         "label", "guide", "err", "result" ([l]); "labels" (k-means), "timing". Level 0 = coarsest."""
+        keep, structs = _multi_reports(_grids(self._pair_shape, self._multi_shapes), 5)
+        return self._run_call("nct_multi_run_levels", params, keep, *structs)
+
+    def _run_call(self, name, params, keep, *structs):
+        """a run of the uploaded images through the library's `name`(ctx, params, timing, *structs) -> keep, "timing" added"""
         prm = params or Params.default()
-        keep, lv = self._multi_levels_arrays()
         tm = PairTiming()
-        self._chk(self._l.nct_multi_run_levels(self._h, C.addressof(prm), C.addressof(tm), C.addressof(lv)))
+        self._chk(getattr(self._l, name)(self._h, C.addressof(prm), C.addressof(tm), *[C.addressof(st) for st in structs]))
         keep["timing"] = tm.as_dict()
         return keep
-
-    def _multi_levels_arrays(self):
-        """the host arrays nct_multi_levels points into -> (dict of them + "labels", "adims", "bdims", the MultiLevels)"""
-        H, W = self._pair_shape[:2]
-        K = len(self._multi_shapes)
-
-        def pyramid(h, w):
-            d = []
-            for _ in range(5):
-                d.insert(0, (h, w)); h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-            return d
-        adims = pyramid(H, W)
-        bdims = [pyramid(*sh[:2]) for sh in self._multi_shapes]
-        per_ref = {"ann": (np.uint32, "a"), "bnn": (np.uint32, "b"), "annd": (np.float32, "a"), "bnnd": (np.float32, "b"), "ref_guide": (np.uint8, "a3"), "ref_err": (np.float32, "a")}
-        keep = {}
-        lv = MultiLevels()
-        for name, (dt, side) in per_ref.items():
-            keep[name] = []
-            for k in range(K):
-                row = []
-                for l in range(5):
-                    shape = bdims[k][l] if side == "b" else adims[l] + ((3,) if side == "a3" else ())
-                    row.append(np.zeros(shape, dt))
-                    getattr(lv, name)[k][l] = row[-1].ctypes.data
-                keep[name].append(row)
-        for name, dt in (("label", np.uint8), ("guide", np.uint8), ("err", np.float32), ("result", np.uint8)):
-            keep[name] = []
-            for l in range(5):
-                shape = {"label": adims[l], "guide": adims[l] + (3,), "err": adims[l], "result": (H, W, 3)}[name]
-                keep[name].append(np.zeros(shape, dt))
-                getattr(lv, name)[l] = keep[name][-1].ctypes.data
-        labels = np.zeros(adims[0], np.int32)
-        lv.labels = labels.ctypes.data
-        keep["labels"] = labels
-        keep["adims"], keep["bdims"] = adims, bdims
-        return keep, lv
 
     # ---- reference region masks (SPEC §6.12)
     def region_pull(self, q_mask, ann, bnn, w_coh=1.0, w_comp=2.0):
@@ -1204,23 +1286,8 @@ class Context:
     def multi_run_ref_region_levels(self, params=None):
         """nct_multi_run_ref_region_levels on the uploaded, masked list -> multi_run_levels' dict plus "ref_mask" and "pulled" ([k][l]; unmasked references stay zero),
         "mask" [h, w], "mask_full" [H, W] and "ab_mix" [2, h*w, 3] per level"""
-        prm = params or Params.default()
-        keep, lv = self._multi_levels_arrays()
-        H, W = self._pair_shape[:2]
-        rl = RefRegionLevels()
-        keep["ref_mask"] = [[np.zeros(d, np.uint8) for d in bd] for bd in keep["bdims"]]
-        keep["pulled"] = [[np.zeros(d, np.uint8) for d in keep["adims"]] for _ in keep["bdims"]]
-        keep["mask"] = [np.zeros(d, np.uint8) for d in keep["adims"]]
-        keep["mask_full"] = [np.zeros((H, W), np.uint8) for _ in range(5)]
-        keep["ab_mix"] = [np.zeros((2, d[0] * d[1], 3)) for d in keep["adims"]]
-        for l in range(5):
-            for k in range(len(keep["bdims"])):
-                rl.ref_mask[k][l] = keep["ref_mask"][k][l].ctypes.data; rl.pulled[k][l] = keep["pulled"][k][l].ctypes.data
-            rl.mask[l] = keep["mask"][l].ctypes.data; rl.mask_full[l] = keep["mask_full"][l].ctypes.data; rl.ab_mix[l] = keep["ab_mix"][l].ctypes.data
-        tm = PairTiming()
-        self._chk(self._l.nct_multi_run_ref_region_levels(self._h, C.addressof(prm), C.addressof(tm), C.addressof(lv), C.addressof(rl)))
-        keep["timing"] = tm.as_dict()
-        return keep
+        keep, structs = _multi_reports(_grids(self._pair_shape, self._multi_shapes), 5, RefRegionLevels)
+        return self._run_call("nct_multi_run_ref_region_levels", params, keep, *structs)
 
     def process_pair_ref_region(self, src_bgr, src_mask, ref_bgr, ref_mask, protect=None, params=None, want_timing=False):
         """nct_process_pair_ref_region: process_pair with a mask on the source ([h, w] of the source) and / or on the reference ([rh, rw]); both None: process_pair"""
@@ -1254,40 +1321,29 @@ class Context:
         return self._process("nct_process_pair_fullres_ref_region", src_bgr, [m, r, rh, rw, q, max_side, C.addressof(rg)], params, want_timing)
 
     # ---- frame sequences (SPEC §6.3)
-    def seq_begin(self, ref_bgr, src_shape, params=None, tau=None, sigma=None):
-        """nct_seq_begin: prepare the reference once for frames of src_shape[:2]; tau / sigma default to nct_seq_params_default (0.7, 10.0)"""
-        r = np.ascontiguousarray(ref_bgr, np.uint8)
-        prm = params or Params.default()
-        sp = SeqParams.default()
-        if tau is not None:
-            sp.tau = tau
-        if sigma is not None:
-            sp.sigma = sigma
-        self._chk(self._l.nct_seq_begin(self._h, r.reshape(-1, 3), r.shape[0], r.shape[1], int(src_shape[0]), int(src_shape[1]), C.addressof(prm), C.addressof(sp)))
-        self._seq_shapes = (tuple(src_shape[:2]), r.shape[:2], prm.levels)
-        self._seq_work = None
-        self._seq_multi = (tuple(src_shape[:2]), [r.shape[:2]])
-        self._seq_ref_arrive = [r.shape[:2]]; self._seq_finish = None
+    _seq = None                                                   # the open sequence (a _Seq), None when there is none
 
-    def seq_begin_fullres(self, ref_bgr, src_shape, max_side=1000, finish=0, params=None, tau=None, sigma=None):
-        """nct_seq_begin_fullres (SPEC §6.9): frames of src_shape[:2] and the reference arrive at their original size and are shrunk to working_size(..., max_side) on
-        the device; every frame call then takes and returns originals. finish: FINISH_EXACT or FINISH_UPSAMPLE"""
-        r = np.ascontiguousarray(ref_bgr, np.uint8)
-        prm = params or Params.default()
-        sp = SeqParams.default()
-        if tau is not None:
-            sp.tau = tau
-        if sigma is not None:
-            sp.sigma = sigma
-        self._chk(self._l.nct_seq_begin_fullres(self._h, r.reshape(-1, 3), r.shape[0], r.shape[1], int(src_shape[0]), int(src_shape[1]), int(max_side), int(finish),
-                                                C.addressof(prm), C.addressof(sp)))
-        self._seq_shapes = (tuple(src_shape[:2]), r.shape[:2], prm.levels)
-        self._seq_work = (working_size(int(src_shape[0]), int(src_shape[1]), max_side), working_size(r.shape[0], r.shape[1], max_side))
-        self._seq_multi = (self._seq_work[0], [self._seq_work[1]])
-        self._seq_ref_arrive = [r.shape[:2]]; self._seq_finish = int(finish)
+    def _seq_begun(self, src_shape, refs, levels, max_side=None, finish=None):
+        """the record of the sequence a seq_begin* call has opened; max_side and finish: of a full-resolution sequence"""
+        arrive, ref_arrive = tuple(src_shape[:2]), [r.shape[:2] for r in refs]
+        if max_side is None:
+            self._seq = _Seq(arrive, ref_arrive, arrive, ref_arrive, levels, None)
+        else:
+            self._seq = _Seq(arrive, ref_arrive, working_size(int(arrive[0]), int(arrive[1]), max_side), [working_size(h, w, max_side) for h, w in ref_arrive], levels, int(finish))
 
-    # ---- sequences over several references (SPEC §6.18)
-    def _seq_multi_args(self, params, tau, sigma, hold):
+    def _seq_record(self, what, begin):
+        """-> the open sequence's record; `what` needs one"""
+        if self._seq is None:
+            raise NctError(-5, "%s: no sequence is open (%s first)" % (what, begin))
+        return self._seq
+
+    def _seq_grids(self):
+        """the grids of the open sequence's reports: they live at the working size, but the last level run of an exact full-resolution finish targets the arriving size"""
+        q = self._seq
+        return _grids(q.work, q.ref_work, [q.arrive if (q.finish == FINISH_EXACT and l == q.levels - 1) else q.work for l in range(5)])
+
+    def _seq_params(self, params, tau, sigma, hold=None):
+        """-> Params, SeqParams and SeqHold (None: NULL) of a seq_begin* call, the library's defaults where an argument is left out"""
         prm = params or Params.default()
         sp = SeqParams.default()
         if tau is not None:
@@ -1299,72 +1355,69 @@ class Context:
             hp = SeqHold(); hp.hold = hold
         return prm, sp, hp
 
+    def seq_begin(self, ref_bgr, src_shape, params=None, tau=None, sigma=None):
+        """nct_seq_begin: prepare the reference once for frames of src_shape[:2]; tau / sigma default to nct_seq_params_default (0.7, 10.0)"""
+        r = np.ascontiguousarray(ref_bgr, np.uint8)
+        prm, sp, _ = self._seq_params(params, tau, sigma)
+        self._chk(self._l.nct_seq_begin(self._h, r.reshape(-1, 3), r.shape[0], r.shape[1], int(src_shape[0]), int(src_shape[1]), C.addressof(prm), C.addressof(sp)))
+        self._seq_begun(src_shape, [r], prm.levels)
+
+    def seq_begin_fullres(self, ref_bgr, src_shape, max_side=1000, finish=0, params=None, tau=None, sigma=None):
+        """nct_seq_begin_fullres (SPEC §6.9): frames of src_shape[:2] and the reference arrive at their original size and are shrunk to working_size(..., max_side) on
+        the device; every frame call then takes and returns originals. finish: FINISH_EXACT or FINISH_UPSAMPLE"""
+        r = np.ascontiguousarray(ref_bgr, np.uint8)
+        prm, sp, _ = self._seq_params(params, tau, sigma)
+        self._chk(self._l.nct_seq_begin_fullres(self._h, r.reshape(-1, 3), r.shape[0], r.shape[1], int(src_shape[0]), int(src_shape[1]), int(max_side), int(finish),
+                                                C.addressof(prm), C.addressof(sp)))
+        self._seq_begun(src_shape, [r], prm.levels, max_side, finish)
+
+    # ---- sequences over several references (SPEC §6.18)
     def seq_begin_multi(self, refs_bgr, src_shape, params=None, tau=None, sigma=None, hold=None):
         """nct_seq_begin_multi: prepare a list of references once for frames of src_shape[:2]; hold None passes NULL (nct_seq_hold_default)"""
         K, keep, ptrs, hs, ws = self._ref_list(refs_bgr)
-        prm, sp, hp = self._seq_multi_args(params, tau, sigma, hold)
+        prm, sp, hp = self._seq_params(params, tau, sigma, hold)
         self._chk(self._l.nct_seq_begin_multi(self._h, K, ptrs, hs, ws, int(src_shape[0]), int(src_shape[1]), C.addressof(prm), C.addressof(sp),
                                               None if hp is None else C.addressof(hp)))
-        self._seq_shapes = (tuple(src_shape[:2]), keep[0].shape[:2], prm.levels)
-        self._seq_work = None
-        self._seq_multi = (tuple(src_shape[:2]), [a.shape[:2] for a in keep])
-        self._seq_ref_arrive = [a.shape[:2] for a in keep]; self._seq_finish = None
+        self._seq_begun(src_shape, keep, prm.levels)
 
     def seq_begin_multi_fullres(self, refs_bgr, src_shape, max_side=1000, finish=0, params=None, tau=None, sigma=None, hold=None):
         """nct_seq_begin_multi_fullres: seq_begin_fullres over a list of references"""
         K, keep, ptrs, hs, ws = self._ref_list(refs_bgr)
-        prm, sp, hp = self._seq_multi_args(params, tau, sigma, hold)
+        prm, sp, hp = self._seq_params(params, tau, sigma, hold)
         self._chk(self._l.nct_seq_begin_multi_fullres(self._h, K, ptrs, hs, ws, int(src_shape[0]), int(src_shape[1]), int(max_side), int(finish), C.addressof(prm),
                                                       C.addressof(sp), None if hp is None else C.addressof(hp)))
-        work = working_size(int(src_shape[0]), int(src_shape[1]), max_side)
-        rwork = [working_size(a.shape[0], a.shape[1], max_side) for a in keep]
-        self._seq_shapes = (tuple(src_shape[:2]), keep[0].shape[:2], prm.levels)
-        self._seq_work = (work, rwork[0])
-        self._seq_multi = (work, rwork)
-        self._seq_ref_arrive = [a.shape[:2] for a in keep]; self._seq_finish = int(finish)
+        self._seq_begun(src_shape, keep, prm.levels, max_side, finish)
+
+    def _seq_frame_call(self, name, s, keep, *structs):
+        """the frame s (_seq_frame_arg has checked it) through the library's `name`(ctx, frame, result, timing, *structs), a struct None as NULL -> (result, keep with
+        "timing" added). What the structs point at stays with the caller until this returns"""
+        out = np.empty_like(s)
+        tm = PairTiming()
+        self._chk(getattr(self._l, name)(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), *[None if st is None else C.addressof(st) for st in structs]))
+        keep["timing"] = tm.as_dict()
+        return out, keep
+
+    def _seq_multi_reports(self, *more):
+        """what the full frames over several references report: MultiLevels at the working size (a full-resolution sequence reports no "result"), SeqLevels and
+        SeqHoldLevels for the levels that run, then the structs in `more` -> _reports' pair"""
+        q = self._seq
+        keep, structs = _multi_reports(self._seq_grids(), q.levels, SeqLevels, SeqHoldLevels, *more)
+        if q.finish is not None:
+            del keep["result"]
+            structs[0].result = (C.c_void_p * 5)()
+        return keep, structs
 
     def seq_frame_multi_levels(self, src_bgr, want_color=True):
         """nct_seq_frame_multi[_stage]_levels -> (result, dict): multi_run_levels' lists at the working size ("ann" … "ref_err" as [k][l]; "label", "guide", "err", "result"
         as [l]; "labels"), seq_frame_levels' "ab_blend", "tau_map" and "motion" per level that ran, the held selection's "free_label" and "margin" per level that ran, with
         want_color "color" (a dict per level that ran, as seq_frame_levels reports it) and "timing". A full-resolution sequence reports neither "result" nor "color"."""
-        s = self._seq_frame_arg(src_bgr, "seq_frame_multi_levels")
-        if getattr(self, "_seq_multi", None) is None:
-            raise NctError(-5, "seq_frame_multi_levels: no sequence is open (seq_begin_multi first)")
-        (H, W), rshapes = self._seq_multi
-        levels = self._seq_shapes[2]
-        full = self._seq_work is not None
-        self._pair_shape, self._multi_shapes = (H, W, 3), [tuple(r) + (3,) for r in rshapes]
-        keep, lv = self._multi_levels_arrays()
-        adims = keep["adims"]
-        if full:
-            for l in range(5):
-                lv.result[l] = None
-            del keep["result"]
-        keep["ab_blend"] = [np.zeros((2, d[0] * d[1], 3)) for d in adims[:levels]]
-        keep["tau_map"] = [np.zeros(d) for d in adims[:levels]]
-        keep["motion"] = [np.zeros(d + (2,), np.int16) for d in adims[:levels]]
-        keep["free_label"] = [np.zeros(d, np.uint8) for d in adims[:levels]]
-        keep["margin"] = [np.zeros(d) for d in adims[:levels]]
-        sl, hl = SeqLevels(), SeqHoldLevels()
-        for l in range(levels):
-            sl.ab_blend[l] = keep["ab_blend"][l].ctypes.data; sl.tau_map[l] = keep["tau_map"][l].ctypes.data; sl.motion[l] = keep["motion"][l].ctypes.data
-            hl.free_label[l] = keep["free_label"][l].ctypes.data; hl.margin[l] = keep["margin"][l].ctypes.data
-        out = np.empty_like(s)
-        tm = PairTiming()
-        if want_color and not full:
-            color, structs = [], []
-            for (ah, aw) in adims[:levels]:
-                d = {"ab_local": np.empty((2, ah * aw, 3)), "ab_nonlocal": np.empty((2, ah * aw, 3)), "ab_up": np.empty((2, H * W, 3)),
-                     "roughness": np.empty(H * W), "ab_wls": np.empty((2, H * W, 3)), "cg_iters": np.zeros(3, np.int32), "wls_iters": np.zeros(6, np.int32)}
-                color.append(d)
-                structs.append(ColorStages(*[d[k].ctypes.data for k in ("ab_local", "ab_nonlocal", "ab_up", "roughness", "ab_wls", "cg_iters", "wls_iters")]))
-            cptr = (C.c_void_p * 5)(*[C.addressof(structs[i]) if i < levels else None for i in range(5)])
-            self._chk(self._l.nct_seq_frame_multi_stage_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv), cptr, C.addressof(sl), C.addressof(hl)))
-            keep["color"] = color
-        else:
-            self._chk(self._l.nct_seq_frame_multi_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv), C.addressof(sl), C.addressof(hl)))
-        keep["timing"] = tm.as_dict()
-        return out, keep
+        s, q = self._seq_frame_arg(src_bgr, "seq_frame_multi_levels"), self._seq_record("seq_frame_multi_levels", "seq_begin_multi")
+        self._pair_shape, self._multi_shapes = q.work + (3,), [r + (3,) for r in q.ref_work]
+        keep, (lv, sl, hl) = self._seq_multi_reports()
+        if not want_color or q.finish is not None:
+            return self._seq_frame_call("nct_seq_frame_multi_levels", s, keep, lv, sl, hl)
+        keep["color"], cptr, stages = _color_stages(self._seq_grids(), q.levels, q.levels)
+        return self._seq_frame_call("nct_seq_frame_multi_stage_levels", s, keep, lv, cptr, sl, hl)
 
     def select_reference_hold(self, errs, guides, prev_label, lab, lab_prev, field=None, hold=0.0, sigma=10.0, dev=False, want=("label", "guide", "err", "free_label", "margin")):
         """nct_select_reference_hold (dev: its _dev form on arena blocks): K error maps [h, w] fp32, K guidance images [h, w, 3] (or None), the kept labels [h, w], the two
@@ -1395,10 +1448,7 @@ class Context:
             return {k: self.dev_download(dout[k], *spec[k]) for k in want}
 
     def seq_frame(self, src_bgr, want_timing=False):
-        s = np.ascontiguousarray(src_bgr, np.uint8)
-        shp = getattr(self, "_seq_shapes", None)
-        if shp is not None and tuple(s.shape[:2]) != shp[0]:
-            raise NctError(-2, "seq_frame: the frame is %dx%d, the sequence was begun for %dx%d" % (s.shape[1], s.shape[0], shp[0][1], shp[0][0]))
+        s = self._seq_frame_arg(src_bgr, "seq_frame")
         out = np.empty_like(s)
         tm = PairTiming() if want_timing else None
         self._chk(self._l.nct_seq_frame(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm) if tm is not None else None))
@@ -1410,11 +1460,10 @@ class Context:
             self._chk(self._l.nct_seq_set_region(self._h, None, None))
             return
         rg = _region_params(protect)
-        shp = getattr(self, "_seq_shapes", None)
-        if shp is None:                                        # no open sequence: the library refuses; the mask is never read
+        if self._seq is None:                                  # no open sequence: the library refuses; the mask is never read
             m = np.ascontiguousarray(mask, np.uint8)
         else:
-            m = _mask_arg(mask, shp[0], "seq_set_region")
+            m = _mask_arg(mask, self._seq.arrive, "seq_set_region")
         self._chk(self._l.nct_seq_set_region(self._h, m.ctypes.data, C.addressof(rg)))
 
     # ---- reference region masks in sequences (SPEC §6.19)
@@ -1425,7 +1474,7 @@ class Context:
         if mask is None:
             self._chk(self._l.nct_seq_set_ref_region(self._h, int(k), None, None if rg is None else C.addressof(rg)))
             return
-        shapes = getattr(self, "_seq_ref_arrive", None) or []
+        shapes = [] if self._seq is None else self._seq.ref_arrive
         m = np.ascontiguousarray(mask, np.uint8)
         if 0 <= k < len(shapes):                        # the library refuses a k out of range and a call without a sequence; the mask is then never read
             m = _mask_arg(mask, shapes[k], "seq_set_ref_region")
@@ -1463,84 +1512,22 @@ class Context:
                                                     float(tau), float(sigma), *outp))
             return {k: self.dev_download(dout[k], (h, w), np.uint8) for k in want}
 
-    def _ref_region_arrays(self, adims, bdims, levels, H, W):
-        """the report targets of a frame with a reference mask: RefRegionLevels and SeqPullLevels with their arrays, for the level runs"""
-        full = getattr(self, "_seq_work", None) is not None and getattr(self, "_seq_finish", None) == FINISH_EXACT
-        keep = {"ref_mask": [[np.zeros(d, np.uint8) for d in bd[:levels]] for bd in bdims], "pulled": [[np.zeros(d, np.uint8) for d in adims[:levels]] for _ in bdims],
-                "mask": [np.zeros(d, np.uint8) for d in adims[:levels]],
-                "mask_full": [np.zeros(self._seq_shapes[0] if (full and l == levels - 1) else (H, W), np.uint8) for l in range(levels)],
-                "ab_mix": [np.zeros((2, d[0] * d[1], 3)) for d in adims[:levels]],
-                "p_free": [np.zeros(d, np.uint8) for d in adims[:levels]], "p_held": [np.zeros(d, np.uint8) for d in adims[:levels]]}
-        rl, pl = RefRegionLevels(), SeqPullLevels()
-        for l in range(levels):
-            for k in range(len(bdims)):
-                rl.ref_mask[k][l] = keep["ref_mask"][k][l].ctypes.data; rl.pulled[k][l] = keep["pulled"][k][l].ctypes.data
-            rl.mask[l] = keep["mask"][l].ctypes.data; rl.mask_full[l] = keep["mask_full"][l].ctypes.data; rl.ab_mix[l] = keep["ab_mix"][l].ctypes.data
-            pl.p_free[l] = keep["p_free"][l].ctypes.data; pl.p_held[l] = keep["p_held"][l].ctypes.data
-        return keep, rl, pl
-
     def seq_frame_ref_region_levels(self, src_bgr):
         """nct_seq_frame_ref_region_levels -> (result, dict): seq_frame_multi_levels' dict without "color", plus per level that ran "ref_mask" and "pulled" ([k][l]; unmasked
         references stay zero), "mask" (M_l), "mask_full" (F_l at the size the level's finish targets), "ab_mix", "p_free" (P_l) and "p_held" (P'_t)"""
-        s = self._seq_frame_arg(src_bgr, "seq_frame_ref_region_levels")
-        if getattr(self, "_seq_multi", None) is None:
-            raise NctError(-5, "seq_frame_ref_region_levels: no sequence is open (seq_begin first)")
-        (H, W), rshapes = self._seq_multi
-        levels = self._seq_shapes[2]
-        full = self._seq_work is not None
-        self._pair_shape, self._multi_shapes = (H, W, 3), [tuple(r) + (3,) for r in rshapes]
-        keep, lv = self._multi_levels_arrays()
-        adims = keep["adims"]
-        if full:
-            for l in range(5):
-                lv.result[l] = None
-            del keep["result"]
-        keep["ab_blend"] = [np.zeros((2, d[0] * d[1], 3)) for d in adims[:levels]]
-        keep["tau_map"] = [np.zeros(d) for d in adims[:levels]]
-        keep["motion"] = [np.zeros(d + (2,), np.int16) for d in adims[:levels]]
-        keep["free_label"] = [np.zeros(d, np.uint8) for d in adims[:levels]]
-        keep["margin"] = [np.zeros(d) for d in adims[:levels]]
-        sl, hl = SeqLevels(), SeqHoldLevels()
-        for l in range(levels):
-            sl.ab_blend[l] = keep["ab_blend"][l].ctypes.data; sl.tau_map[l] = keep["tau_map"][l].ctypes.data; sl.motion[l] = keep["motion"][l].ctypes.data
-            hl.free_label[l] = keep["free_label"][l].ctypes.data; hl.margin[l] = keep["margin"][l].ctypes.data
-        more, rl, pl = self._ref_region_arrays(adims, keep["bdims"], levels, H, W)
-        keep.update(more)
-        out = np.empty_like(s)
-        tm = PairTiming()
-        self._chk(self._l.nct_seq_frame_ref_region_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv), None, C.addressof(sl), C.addressof(hl),
-                                                          C.addressof(rl), C.addressof(pl)))
-        keep["timing"] = tm.as_dict()
-        return out, keep
+        s, q = self._seq_frame_arg(src_bgr, "seq_frame_ref_region_levels"), self._seq_record("seq_frame_ref_region_levels", "seq_begin")
+        self._pair_shape, self._multi_shapes = q.work + (3,), [r + (3,) for r in q.ref_work]
+        keep, (lv, sl, hl, rl, pl) = self._seq_multi_reports(RefRegionLevels, SeqPullLevels)
+        return self._seq_frame_call("nct_seq_frame_ref_region_levels", s, keep, lv, None, sl, hl, rl, pl)
 
     def seq_frame_propagate_ref_region_levels(self, src_bgr):
         """nct_seq_frame_propagate_ref_region_levels -> (result, dict): seq_frame_propagate_levels' dict plus "p_held" per level that ran and, for the last level run only
         (zeros elsewhere), "mask", "mask_full" and "ab_mix" maps"""
-        s = self._seq_frame_arg(src_bgr, "seq_frame_propagate_ref_region_levels")
-        if getattr(self, "_seq_multi", None) is None:
-            raise NctError(-5, "seq_frame_propagate_ref_region_levels: no sequence is open (seq_begin first)")
-        (H, W), rshapes = self._seq_multi
-        levels = self._seq_shapes[2]
-        adims, bdims = [], [[] for _ in rshapes]
-        h, w, rs = H, W, [tuple(r) for r in rshapes]
-        for _ in range(5):
-            adims.insert(0, (h, w))
-            for k, r in enumerate(rs):
-                bdims[k].insert(0, r)
-            h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-            rs = [((r[0] - 1) // 2 + 1, (r[1] - 1) // 2 + 1) for r in rs]
-        keep = {"ab_blend": [np.zeros((2, d[0] * d[1], 3)) for d in adims[:levels]], "tau_map": [np.zeros(d) for d in adims[:levels]],
-                "motion": [np.zeros(d + (2,), np.int16) for d in adims[:levels]], "dims": adims}
-        sl = SeqLevels()
-        for l in range(levels):
-            sl.ab_blend[l] = keep["ab_blend"][l].ctypes.data; sl.tau_map[l] = keep["tau_map"][l].ctypes.data; sl.motion[l] = keep["motion"][l].ctypes.data
-        more, rl, pl = self._ref_region_arrays(adims, bdims, levels, H, W)
-        keep.update(more)
-        out = np.empty_like(s)
-        tm = PairTiming()
-        self._chk(self._l.nct_seq_frame_propagate_ref_region_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(sl), C.addressof(rl), C.addressof(pl)))
-        keep["timing"] = tm.as_dict()
-        return out, keep
+        s, q = self._seq_frame_arg(src_bgr, "seq_frame_propagate_ref_region_levels"), self._seq_record("seq_frame_propagate_ref_region_levels", "seq_begin")
+        g = self._seq_grids()
+        keep, structs = _reports(g, q.levels, SeqLevels, RefRegionLevels, SeqPullLevels)
+        keep["dims"] = g.src
+        return self._seq_frame_call("nct_seq_frame_propagate_ref_region_levels", s, keep, *structs)
 
     # ---- region tracking (SPEC §6.14)
     def seq_matte_warp(self, mask, field, dev=False, alias=False):
@@ -1567,8 +1554,7 @@ class Context:
 
     def seq_get_region(self):
         """nct_seq_get_region -> (the matte in force at the size frames arrive, its age in frames)"""
-        shp = getattr(self, "_seq_shapes", None)
-        out = np.zeros(tuple(shp[0]) if shp is not None else (1, 1), np.uint8)      # no open sequence: the library refuses; nothing is written
+        out = np.zeros(self._seq.arrive if self._seq is not None else (1, 1), np.uint8)      # no open sequence: the library refuses; nothing is written
         age = C.c_int(-1)
         self._chk(self._l.nct_seq_get_region(self._h, out.ctypes.data, C.addressof(age)))
         return out, age.value
@@ -1671,8 +1657,7 @@ class Context:
     def seq_select_region(self, frame_bgr, strokes, params=None, protect=None):
         """nct_seq_select_region on the open sequence: region_select on frame_bgr (a frame of the sequence's size), then seq_set_region with the matte"""
         f, t = np.ascontiguousarray(frame_bgr, np.uint8), np.ascontiguousarray(strokes, np.uint8)
-        shp = getattr(self, "_seq_shapes", None)
-        if shp is not None and (tuple(f.shape[:2]) != tuple(shp[0]) or t.shape != tuple(shp[0])):
+        if self._seq is not None and (tuple(f.shape[:2]) != self._seq.arrive or t.shape != self._seq.arrive):
             raise NctError(-2, "seq_select_region: the frame and the strokes must have the size the sequence was begun for")
         rg = _region_params(protect)
         self._chk(self._l.nct_seq_select_region(self._h, f.ctypes.data, t.ctypes.data, C.addressof(params) if params is not None else None, C.addressof(rg)))
@@ -1764,85 +1749,35 @@ class Context:
         (zeros elsewhere) and the level masks that were built (that level and finer; zeros elsewhere)"""
         return self.seq_frame_propagate_levels(src_bgr, _region=True)
 
-    def _region_levels_arrays(self, dims, levels):
-        rl = RegionLevels()
-        ab_mix = [np.zeros((2, d[0] * d[1], 3)) for d in dims[:levels]]
-        mask = [np.zeros((d[0], d[1]), np.uint8) for d in dims]
-        for l in range(levels):
-            rl.ab_mix[l] = ab_mix[l].ctypes.data
-        for l in range(5):
-            rl.mask[l] = mask[l].ctypes.data
-        return rl, ab_mix, mask
+    def _seq_region_call(self, name, s, keep, g, levels, region, *first):
+        """the end of the two single-reference frame reports: SeqLevels for the levels that run and, with region, RegionLevels go behind the structs in `first`.
+        nct_region_levels takes a mask for all five levels; "mask" reports those that ran"""
+        more, structs = _reports(g, levels, SeqLevels, *([RegionLevels] if region else []))
+        keep.update(more)
+        out, keep = self._seq_frame_call(name, s, keep, *first, *structs)
+        if region:
+            keep["mask"] = keep["mask"][:levels]
+        return out, keep
 
     def seq_frame_levels(self, src_bgr, want_color=True, want_levels=None, _region=False):
         """nct_seq_frame_levels -> (result, dict): pair_run_levels' per-level lists ("ann" … "result", with want_color "color" and "labels"), plus "ab_blend" and "tau_map"
         per level that ran (X'_t [2, h*w, 3] and tau_p [h, w]; a frame without a blend reports X_t and zeros), "motion" (SPEC §6.4: the level's field, int16 [h, w, 2] of
         (my, mx); zeros without motion or without a blend) and "timing"."""
-        s = np.ascontiguousarray(src_bgr, np.uint8)
-        (H, W), (RH, RW), levels = self._seq_shapes
-        if tuple(s.shape[:2]) != (H, W):
-            raise NctError(-2, "seq_frame_levels: the frame is %dx%d, the sequence was begun for %dx%d" % (s.shape[1], s.shape[0], W, H))
+        s, q = self._seq_frame_arg(src_bgr, "seq_frame_levels"), self._seq_record("seq_frame_levels", "seq_begin")
         # a full-resolution sequence (SPEC §6.9 rule 5) reports the working-size maps through "ab_blend" / "tau_map" / "motion" only: nct_pair_levels stays NULL
         # unless want_levels forces it (which the library refuses)
-        work = getattr(self, "_seq_work", None)
-        if work is not None:
-            (H, W), (RH, RW) = work
         if want_levels is None:
-            want_levels = work is None
-        want_color = want_color and want_levels
-        dims = []
-        h, w, h2, w2 = H, W, RH, RW
-        for _ in range(5):
-            dims.insert(0, (h, w, h2, w2))
-            h, w, h2, w2 = (h - 1) // 2 + 1, (w - 1) // 2 + 1, (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
-        keep = {"ann": [], "bnn": [], "annd": [], "bnnd": [], "guide": [], "err": [], "result": []}
-        for (ah, aw, bh, bw) in dims:
-            keep["ann"].append(np.zeros((ah, aw), np.uint32)); keep["bnn"].append(np.zeros((bh, bw), np.uint32))
-            keep["annd"].append(np.zeros((ah, aw), np.float32)); keep["bnnd"].append(np.zeros((bh, bw), np.float32))
-            keep["guide"].append(np.zeros((ah, aw, 3), np.uint8)); keep["err"].append(np.zeros((ah, aw), np.float32))
-            keep["result"].append(np.zeros((H, W, 3), np.uint8))
-        lv = PairLevels()
-        for k in keep:
-            setattr(lv, k, (C.c_void_p * 5)(*[a.ctypes.data for a in keep[k]]))
-        if want_color:
-            color, structs = [], []
-            for (ah, aw, _, _) in dims:
-                d = {"ab_local": np.empty((2, ah * aw, 3)), "ab_nonlocal": np.empty((2, ah * aw, 3)), "ab_up": np.empty((2, H * W, 3)),
-                     "roughness": np.empty(H * W), "ab_wls": np.empty((2, H * W, 3)), "cg_iters": np.zeros(3, np.int32), "wls_iters": np.zeros(6, np.int32)}
-                color.append(d)
-                structs.append(ColorStages(*[d[k].ctypes.data for k in ("ab_local", "ab_nonlocal", "ab_up", "roughness", "ab_wls", "cg_iters", "wls_iters")]))
-            lv.color = (C.c_void_p * 5)(*[C.addressof(st) if i < levels else None for i, st in enumerate(structs)])
-            labels = np.zeros(dims[0][:2], np.int32)
-            lv.labels = labels.ctypes.data
-        ab_blend = [np.zeros((2, ah * aw, 3)) for (ah, aw, _, _) in dims[:levels]]
-        tau_map = [np.zeros((ah, aw)) for (ah, aw, _, _) in dims[:levels]]
-        motion = [np.zeros((ah, aw, 2), np.int16) for (ah, aw, _, _) in dims[:levels]]
-        sl = SeqLevels()
-        for l in range(levels):
-            sl.ab_blend[l] = ab_blend[l].ctypes.data; sl.tau_map[l] = tau_map[l].ctypes.data; sl.motion[l] = motion[l].ctypes.data
-        out = np.empty_like(s)
-        tm = PairTiming()
-        if _region:
-            rl, ab_mix, mask = self._region_levels_arrays(dims, levels)
-            self._chk(self._l.nct_seq_frame_region_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv) if want_levels else None, C.addressof(sl),
-                                                          C.addressof(rl)))
-        else:
-            self._chk(self._l.nct_seq_frame_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(lv) if want_levels else None, C.addressof(sl)))
+            want_levels = q.finish is None
+        g = self._seq_grids()
+        keep, lv, hold = _pair_report(g, q.levels, want_color and want_levels)
         if not want_levels:
-            keep = {}
-        if _region:
-            keep["ab_mix"] = ab_mix; keep["mask"] = mask[:levels]
-        if want_color:
-            keep["color"] = color; keep["labels"] = labels
-        keep["ab_blend"] = ab_blend; keep["tau_map"] = tau_map; keep["motion"] = motion
-        keep["timing"] = tm.as_dict(); keep["dims"] = dims
-        return out, keep
+            keep, lv = {"dims": keep["dims"]}, None
+        return self._seq_region_call("nct_seq_frame_region_levels" if _region else "nct_seq_frame_levels", s, keep, g, q.levels, _region, lv)
 
     def _seq_frame_arg(self, src_bgr, what):
         s = np.ascontiguousarray(src_bgr, np.uint8)
-        shp = getattr(self, "_seq_shapes", None)
-        if shp is not None and tuple(s.shape[:2]) != tuple(shp[0]):
-            raise NctError(-2, "%s: the frame is %dx%d, the sequence was begun for %dx%d" % (what, s.shape[1], s.shape[0], shp[0][1], shp[0][0]))
+        if self._seq is not None and tuple(s.shape[:2]) != self._seq.arrive:
+            raise NctError(-2, "%s: the frame is %dx%d, the sequence was begun for %dx%d" % (what, s.shape[1], s.shape[0], self._seq.arrive[1], self._seq.arrive[0]))
         return s
 
     def seq_frame_propagate(self, src_bgr, want_timing=False):
@@ -1856,32 +1791,10 @@ class Context:
     def seq_frame_propagate_levels(self, src_bgr, _region=False):
         """nct_seq_frame_propagate_levels -> (result, dict): per level that ran "ab_blend" (X'_t [2, h*w, 3]), "motion" (int16 [h, w, 2]; zeros with motion off) and
         "tau_map" (1.0 everywhere), plus "timing" and "dims" (the source's level grids)"""
-        s = self._seq_frame_arg(src_bgr, "seq_frame_propagate_levels")
-        shp = getattr(self, "_seq_shapes", None)
-        if shp is None:                                        # no open sequence: the library refuses; the maps are never written
-            shp = (s.shape[:2], None, 0)
-        levels = shp[2]
-        dims = []
-        h, w = s.shape[:2]
-        if getattr(self, "_seq_work", None) is not None:       # a full-resolution sequence keeps its state on the working-size grids
-            h, w = self._seq_work[0]
-        for _ in range(5):
-            dims.insert(0, (h, w))
-            h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-        ab_blend = [np.zeros((2, ah * aw, 3)) for (ah, aw) in dims[:levels]]
-        tau_map = [np.zeros((ah, aw)) for (ah, aw) in dims[:levels]]
-        motion = [np.zeros((ah, aw, 2), np.int16) for (ah, aw) in dims[:levels]]
-        sl = SeqLevels()
-        for l in range(levels):
-            sl.ab_blend[l] = ab_blend[l].ctypes.data; sl.tau_map[l] = tau_map[l].ctypes.data; sl.motion[l] = motion[l].ctypes.data
-        out = np.empty_like(s)
-        tm = PairTiming()
-        if _region:
-            rl, ab_mix, mask = self._region_levels_arrays(dims, levels)
-            self._chk(self._l.nct_seq_frame_propagate_region_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(sl), C.addressof(rl)))
-            return out, {"ab_blend": ab_blend, "tau_map": tau_map, "motion": motion, "timing": tm.as_dict(), "dims": dims, "ab_mix": ab_mix, "mask": mask[:levels]}
-        self._chk(self._l.nct_seq_frame_propagate_levels(self._h, s.reshape(-1, 3), out.reshape(-1, 3), C.addressof(tm), C.addressof(sl)))
-        return out, {"ab_blend": ab_blend, "tau_map": tau_map, "motion": motion, "timing": tm.as_dict(), "dims": dims}
+        s, q = self._seq_frame_arg(src_bgr, "seq_frame_propagate_levels"), self._seq
+        g = self._seq_grids() if q is not None else _grids(s.shape, [])        # no open sequence: the library refuses; no level is reported
+        name = "nct_seq_frame_propagate_region_levels" if _region else "nct_seq_frame_propagate_levels"
+        return self._seq_region_call(name, s, {"dims": g.src}, g, q.levels if q is not None else 0, _region)
 
     def seq_warp(self, x_prev, field):
         """nct_seq_warp (SPEC §6.5 rule 3): x_prev [2, h*w, 3] doubles, field int16 [h, w, 2] of (my, mx) -> x_prev read at p + m(p), the 64-bit words copied"""
@@ -2005,10 +1918,7 @@ class Context:
 
     def seq_end(self):
         self._chk(self._l.nct_seq_end(self._h))
-        self._seq_shapes = None
-        self._seq_work = None
-        self._seq_multi = None
-        self._seq_ref_arrive = None
+        self._seq = None
 
     def seq_set_motion(self, radius0=None, radius=None, penalty=None, off=False):
         """nct_seq_set_motion (SPEC §6.4): motion compensation of the open sequence from the next frame on; values left out are nct_seq_motion_default's (3, 1, 1).
@@ -2109,47 +2019,12 @@ class Context:
         self._chk(self._l.nct_pair_run(self._h, C.addressof(prm), C.addressof(tm) if tm is not None else None))
         return tm.as_dict() if want_timing else None
 
-    def _pair_levels_arrays(self, src_shape, ref_shape, prm, want_color):
-        """the host arrays nct_pair_levels points into -> (dict of them + "dims", the PairLevels, what must stay alive until the call returns)"""
-        H, W = src_shape[:2]; RH, RW = ref_shape[:2]
-        dims = []
-        h, w, h2, w2 = H, W, RH, RW
-        for _ in range(5):
-            dims.insert(0, (h, w, h2, w2))
-            h, w, h2, w2 = (h - 1) // 2 + 1, (w - 1) // 2 + 1, (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
-        keep = {"ann": [], "bnn": [], "annd": [], "bnnd": [], "guide": [], "err": [], "result": []}
-        for (ah, aw, bh, bw) in dims:
-            keep["ann"].append(np.zeros((ah, aw), np.uint32)); keep["bnn"].append(np.zeros((bh, bw), np.uint32))
-            keep["annd"].append(np.zeros((ah, aw), np.float32)); keep["bnnd"].append(np.zeros((bh, bw), np.float32))
-            keep["guide"].append(np.zeros((ah, aw, 3), np.uint8)); keep["err"].append(np.zeros((ah, aw), np.float32))
-            keep["result"].append(np.zeros((H, W, 3), np.uint8))
-        lv = PairLevels()
-        for k in keep:
-            setattr(lv, k, (C.c_void_p * 5)(*[a.ctypes.data for a in keep[k]]))
-        structs = []
-        if want_color:
-            color = []
-            for (ah, aw, _, _) in dims:
-                d = {"ab_local": np.empty((2, ah * aw, 3)), "ab_nonlocal": np.empty((2, ah * aw, 3)), "ab_up": np.empty((2, H * W, 3)),
-                     "roughness": np.empty(H * W), "ab_wls": np.empty((2, H * W, 3)), "cg_iters": np.zeros(3, np.int32), "wls_iters": np.zeros(6, np.int32)}
-                color.append(d)
-                structs.append(ColorStages(*[d[k].ctypes.data for k in ("ab_local", "ab_nonlocal", "ab_up", "roughness", "ab_wls", "cg_iters", "wls_iters")]))
-            lv.color = (C.c_void_p * 5)(*[C.addressof(st) if i < prm.levels else None for i, st in enumerate(structs)])
-            labels = np.zeros(dims[0][:2], np.int32)
-            lv.labels = labels.ctypes.data
-            keep["color"] = color; keep["labels"] = labels
-        keep["dims"] = dims
-        return keep, lv, structs
-
     def pair_run_levels(self, src_shape, ref_shape, params=None, want_color=False):
         """nct_pair_run_levels on the uploaded pair -> dict of per-level intermediates (lists indexed by level, 0 = coarsest).
         want_color adds "color" (per level the dict of coefficient maps local_color_transfer(want_stages=True) returns) and "labels"."""
         prm = params or Params.default()
-        keep, lv, hold = self._pair_levels_arrays(src_shape, ref_shape, prm, want_color)
-        tm = PairTiming()
-        self._chk(self._l.nct_pair_run_levels(self._h, C.addressof(prm), C.addressof(tm), C.addressof(lv)))
-        keep["timing"] = tm.as_dict()
-        return keep
+        keep, lv, hold = _pair_report(_grids(src_shape, [ref_shape]), prm.levels, want_color)
+        return self._run_call("nct_pair_run_levels", prm, keep, lv)
 
     # ---- source region masks (SPEC §6.11)
     def resize_u8c1(self, img, dh, dw):
@@ -2222,16 +2097,11 @@ class Context:
     def pair_run_region_levels(self, src_shape, ref_shape, params=None, want_color=True):
         """nct_pair_run_region_levels on the uploaded, masked pair -> pair_run_levels' dict plus per level "mask" [h, w] and "ab_mix" [2, h*w, 3]"""
         prm = params or Params.default()
-        keep, lv, hold = self._pair_levels_arrays(src_shape, ref_shape, prm, want_color)
-        rl = RegionLevels()
-        keep["mask"], keep["ab_mix"] = [], []
-        for l, (ah, aw, _, _) in enumerate(keep["dims"]):
-            keep["mask"].append(np.zeros((ah, aw), np.uint8)); keep["ab_mix"].append(np.zeros((2, ah * aw, 3)))
-            rl.mask[l] = keep["mask"][-1].ctypes.data; rl.ab_mix[l] = keep["ab_mix"][-1].ctypes.data
-        tm = PairTiming()
-        self._chk(self._l.nct_pair_run_region_levels(self._h, C.addressof(prm), C.addressof(tm), C.addressof(lv), C.addressof(rl)))
-        keep["timing"] = tm.as_dict()
-        return keep
+        g = _grids(src_shape, [ref_shape])
+        keep, lv, hold = _pair_report(g, prm.levels, want_color)
+        more, rl = _report(RegionLevels, g)
+        keep.update(more)
+        return self._run_call("nct_pair_run_region_levels", prm, keep, lv, rl)
 
     def process_pair_region(self, src_bgr, mask, ref_bgr, protect=None, params=None, want_timing=False):
         """nct_process_pair_region: process_pair recolouring only where mask ([h, w] bytes of the source; None: process_pair) says so"""
