@@ -874,7 +874,15 @@ int nct_seq_set_region_model(nct_ctx* ctx, const nct_region_model* model, const 
  * immediately; nct_dev_download and nct_synchronize wait. Arena blocks are recycled in the order of THAT stream: use them from another stream (or free them while your own
  * kernels still read them) only after nct_synchronize. nct_dev_free of a pointer that is not a live nct_dev_alloc block of the context returns NCT_ERR_INVALID. Features: channel-last HWC fp32 (nct_chw_to_hwc_dev converts a Caffe blob once); `unit_norm` = 1
  * tells nct_patchmatch_bidir_dev that both maps hold unit vectors (output of nct_feat_normalize_dev), which enables the exact row-wise rejection.
- * Chained like the reference's level loop they reproduce nct_pair_run_levels bit for bit (tests/test_gpu_pipeline.py::test_dev_seams_chain_equals_pipeline). */
+ * Chained like the reference's level loop they reproduce nct_pair_run_levels bit for bit (tests/test_gpu_pipeline.py::test_dev_seams_chain_equals_pipeline).
+ * Limits, each refused with NCT_ERR_INVALID and a message naming the entry point before anything is reserved or enqueued (tests/test_gpu_dev_seams.py::test_refusals):
+ *  - every non-nullable pointer is set (nullable: resp, pw, dims, d_taps_chw, d_taps_hwc and their entries); nnf_half != nnf;
+ *  - maps [C][H][W] / [H][W][C]: C, H, W >= 1 with H * W and C * H * W at most 2^31 - 256; C a multiple of 4 for normalise, matching error, PatchMatch and the feature
+ *    vote, C <= 512 for the feature vote;
+ *  - fields (NNF init / upsample, PatchMatch, both votes): 1 <= ah, aw, bh, bw (and ah_half, aw_half) < 4096, the NNF word holds 12 bits per coordinate; ah, aw >= 2 for
+ *    nct_nnf_init_dev; patch = 3; iters, rs_max >= 0;
+ *  - images: 2 <= h, w < 4096, stride (bytes from one row to the next; rows need no alignment) >= 3 w, deepest_tap in 1..5.
+ * nct_bds_vote_features and nct_bds_vote_image, the host forms of the votes, take the same field dimensions. */
 int nct_dev_alloc(nct_ctx* ctx, size_t bytes, void** out);
 int nct_dev_free(nct_ctx* ctx, void* p);
 int nct_dev_upload(nct_ctx* ctx, void* dst_dev, const void* src_host, size_t bytes);

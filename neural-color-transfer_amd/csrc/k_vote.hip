@@ -381,6 +381,7 @@ static int launch_vote_features(nct_ctx* ctx, hipStream_t s, const InvMap& inv, 
 int nctk_bds_vote_features(nct_ctx* ctx, hipStream_t s, const uint32_t* ann, const uint32_t* bnn, const float* pin_hwc, float* pout_hwc, float* pw,
                            int C, int ah, int aw, int bh, int bw, float w_coh, float w_comp) {
     NCT_REQUIRE(C > 0 && (C & 3) == 0 && C <= 512, "bds_vote_features: C=%d must be a multiple of 4 and <= 512", C);
+    NCT_REQUIRE(nct_nnf_dims_ok(ah, aw, bh, bw), "bds_vote_features: dims out of range (%dx%d vs %dx%d); NNF coordinates are 12-bit", ah, aw, bh, bw);
     InvMap inv(ctx, bh * bw, ah * aw);
     if (!inv.ok()) return NCT_ERR_HIP;
     NCT_TRY(build_inverse(ctx, s, bnn, bh, bw, ah, aw, inv));
@@ -429,6 +430,7 @@ static int launch_vote_image(nct_ctx* ctx, hipStream_t s, const InvMap& inv, con
 }
 int nctk_bds_vote_image(nct_ctx* ctx, hipStream_t s, const uint8_t* b_bgr, const uint32_t* ann, const uint32_t* bnn,
                         int ah, int aw, int bh, int bw, double w_coh, double w_comp, uint8_t* out_bgr) {
+    NCT_REQUIRE(nct_nnf_dims_ok(ah, aw, bh, bw), "bds_vote_image: dims out of range (%dx%d vs %dx%d); NNF coordinates are 12-bit", ah, aw, bh, bw);
     InvMap inv(ctx, bh * bw, ah * aw);
     if (!inv.ok()) return NCT_ERR_HIP;
     NCT_TRY(build_inverse(ctx, s, bnn, bh, bw, ah, aw, inv));

@@ -266,6 +266,8 @@ int nct_bds_vote_features(nct_ctx* ctx, const uint32_t* ann, const uint32_t* bnn
     NCT_REQUIRE(ann && bnn && pin_chw && pout_chw, "bds_vote_features: null pointer");
     NCT_REQUIRE(patch == 3, "bds_vote_features: only patch=3 is supported, got %d", patch);
     NCT_REQUIRE(ah > 0 && aw > 0 && bh > 0 && bw > 0, "bds_vote_features: empty image");
+    NCT_REQUIRE(C > 0 && (C & 3) == 0 && C <= 512, "bds_vote_features: C=%d must be a multiple of 4 and <= 512", C);      // nctk_bds_vote_features' own refusals, in front of the reservations
+    NCT_REQUIRE(nct_nnf_dims_ok(ah, aw, bh, bw), "bds_vote_features: dims out of range (%dx%d vs %dx%d); NNF coordinates are 12-bit", ah, aw, bh, bw);
     const size_t na = (size_t)ah * aw, nb = (size_t)bh * bw;
     DevBuf<float> t(ctx, (size_t)C * (na > nb ? na : nb)), P(ctx, C * nb), O(ctx, C * na), w(ctx, na);
     DevBuf<uint32_t> da(ctx, na), db(ctx, nb);
@@ -513,6 +515,7 @@ int nct_bds_vote_image(nct_ctx* ctx, const uint8_t* a_bgr, int ah, int aw, const
     NCT_REQUIRE(b_bgr && ann && bnn && out_bgr, "bds_vote_image: null pointer");
     NCT_REQUIRE(patch == 3, "bds_vote_image: only patch=3 is supported, got %d", patch);
     NCT_REQUIRE(ah > 0 && aw > 0 && bh > 0 && bw > 0, "bds_vote_image: empty image");
+    NCT_REQUIRE(nct_nnf_dims_ok(ah, aw, bh, bw), "bds_vote_image: dims out of range (%dx%d vs %dx%d); NNF coordinates are 12-bit", ah, aw, bh, bw);
     const size_t na = (size_t)ah * aw, nb = (size_t)bh * bw;
     DevBuf<uint8_t> b(ctx, nb * 3), o(ctx, na * 3);
     DevBuf<uint32_t> da(ctx, na), db(ctx, nb);

@@ -38,27 +38,57 @@ int nct_dev_download(nct_ctx* ctx, void* dst_host, const void* src_dev, size_t b
     return NCT_OK;
 }
 
+// The argument checks of this family (`who` names the entry point in the message): every seam runs its own in front of the launcher, which reserves and enqueues.
+// A map [C][H][W] or [H][W][C]: c_step 4 = the float4 rows of the correspondence kernels, 1 = any C; the sizes fit the launchers' ints
+static int map_check(nct_ctx* ctx, const char* who, int C, int H, int W, int c_step) {
+    NCT_REQUIRE(C > 0 && C % c_step == 0, "%s: C=%d must be a positive multiple of %d", who, C, c_step);
+    NCT_REQUIRE(H > 0 && W > 0, "%s: empty map %dx%d", who, W, H);
+    NCT_REQUIRE((long long)H * W <= NCT_MAX_ELEMS && (long long)C * H * W <= NCT_MAX_ELEMS, "%s: a map of %d x %dx%d elements exceeds 2^31 - 256", who, C, W, H);
+    return NCT_OK;
+}
+// a field between two maps
+static int field_check(nct_ctx* ctx, const char* who, int ah, int aw, int bh, int bw, int patch) {
+    NCT_REQUIRE(patch == 3, "%s: patch must be 3 (Config.h:70), got %d", who, patch);
+    NCT_REQUIRE(nct_nnf_dims_ok(ah, aw, bh, bw), "%s: dims out of range (%dx%d vs %dx%d); NNF coordinates are 12-bit", who, ah, aw, bh, bw);
+    return NCT_OK;
+}
+static int pm_check(nct_ctx* ctx, const char* who, int C, int ah, int aw, int bh, int bw, int patch, int iters, int rs_max) {
+    NCT_REQUIRE(C > 0 && (C & 3) == 0, "%s: C=%d must be a positive multiple of 4", who, C);
+    NCT_TRY(field_check(ctx, who, ah, aw, bh, bw, patch));
+    NCT_REQUIRE(iters >= 0 && rs_max >= 0, "%s: iters/rs_max must be >= 0 (got %d, %d)", who, iters, rs_max);
+    return NCT_OK;
+}
+static int image_check(nct_ctx* ctx, const char* who, const void* d_bgr, int h, int w, int stride, int deepest_tap) {
+    NCT_REQUIRE(d_bgr, "%s: null pointer", who);
+    NCT_REQUIRE(h >= 2 && w >= 2 && h < 4096 && w < 4096, "%s: image size %dx%d out of range", who, w, h);
+    NCT_REQUIRE(stride >= 3 * w, "%s: stride %d is less than a row of %d pixels", who, stride, w);
+    NCT_REQUIRE(deepest_tap >= 1 && deepest_tap <= 5, "%s: deepest_tap must be 1..5 (got %d)", who, deepest_tap);
+    return NCT_OK;
+}
+
 int nct_chw_to_hwc_dev(nct_ctx* ctx, const float* src_chw, float* dst_hwc, int C, int H, int W) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(src_chw && dst_hwc && C > 0 && H > 0 && W > 0, "chw_to_hwc_dev: bad arguments");
+    NCT_REQUIRE(src_chw && dst_hwc, "chw_to_hwc_dev: null pointer");
+    NCT_TRY(map_check(ctx, "chw_to_hwc_dev", C, H, W, 1));
     return nctk_chw_to_hwc(ctx, ctx->stream, src_chw, dst_hwc, C, H * W);
 }
 int nct_hwc_to_chw_dev(nct_ctx* ctx, const float* src_hwc, float* dst_chw, int C, int H, int W) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(src_hwc && dst_chw && C > 0 && H > 0 && W > 0, "hwc_to_chw_dev: bad arguments");
+    NCT_REQUIRE(src_hwc && dst_chw, "hwc_to_chw_dev: null pointer");
+    NCT_TRY(map_check(ctx, "hwc_to_chw_dev", C, H, W, 1));
     return nctk_hwc_to_chw(ctx, ctx->stream, src_hwc, dst_chw, C, H * W);
 }
 
 // V2: Classifier::Predict on a device image; taps in Caffe's CHW layout (d_taps_chw[t] nullable)
 int nct_vgg19_features_dev(nct_ctx* ctx, const uint8_t* d_bgr, int h, int w, int stride, int deepest_tap, float* const* d_taps_chw, int* dims) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(d_bgr && h > 0 && w > 0 && stride >= 3 * w, "vgg19_features_dev: bad image arguments");
+    NCT_TRY(image_check(ctx, "vgg19_features_dev", d_bgr, h, w, stride, deepest_tap));
     return nctk_vgg19_forward(ctx, ctx->stream, d_bgr, h, w, stride, deepest_tap, d_taps_chw, dims);
 }
 
 int nct_vgg19_features_hwc_dev(nct_ctx* ctx, const uint8_t* d_bgr, int h, int w, int stride, int deepest_tap, float* const* d_taps_chw, float* const* d_taps_hwc, int* dims) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(d_bgr && h > 0 && w > 0 && stride >= 3 * w, "vgg19_features_hwc_dev: bad image arguments");
+    NCT_TRY(image_check(ctx, "vgg19_features_hwc_dev", d_bgr, h, w, stride, deepest_tap));
     return nctk_vgg19_forward(ctx, ctx->stream, d_bgr, h, w, stride, deepest_tap, d_taps_chw, dims, d_taps_hwc);
 }
 
@@ -101,20 +131,25 @@ int nct_conv3x3_pair_dev(nct_ctx* ctx, const float* d_in1, int H1, int W1, const
 // N1: norm (main.cu:265,274,313)
 int nct_feat_normalize_dev(nct_ctx* ctx, const float* src_hwc, float* dst_hwc, float* resp, int C, int H, int W) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(src_hwc && dst_hwc && C > 0 && (C & 3) == 0 && H > 0 && W > 0, "feat_normalize_dev: C must be a positive multiple of 4");
+    NCT_REQUIRE(src_hwc && dst_hwc, "feat_normalize_dev: null pointer");
+    NCT_TRY(map_check(ctx, "feat_normalize_dev", C, H, W, 4));
     return nctk_normalize(ctx, ctx->stream, src_hwc, dst_hwc, resp, C, H * W);
 }
 
 // N2: init_Ann_kernel / upSample_kernel (main.cu:232-250)
 int nct_nnf_init_dev(nct_ctx* ctx, uint32_t* nnf, int ah, int aw, int bh, int bw) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(nnf && ah >= 2 && aw >= 2 && bh >= 1 && bw >= 1 && ah < 4096 && aw < 4096 && bh < 4096 && bw < 4096, "nnf_init_dev: dims out of range");
+    NCT_REQUIRE(nnf, "nnf_init_dev: null pointer");
+    NCT_REQUIRE(ah >= 2 && aw >= 2 && nct_nnf_dims_ok(ah, aw, bh, bw), "nnf_init_dev: dims out of range (%dx%d -> %dx%d); the query map needs two rows and columns, NNF coordinates are 12-bit",
+                ah, aw, bh, bw);
     return nctk_nnf_init(ctx, ctx->stream, nnf, ah, aw, bh, bw);
 }
 int nct_nnf_upsample_dev(nct_ctx* ctx, const uint32_t* nnf_half, uint32_t* nnf, int ah, int aw, int bh, int bw, int ah_half, int aw_half) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(nnf_half && nnf && nnf_half != nnf && ah >= 1 && aw >= 1 && bh >= 1 && bw >= 1 && ah_half >= 1 && aw_half >= 1, "nnf_upsample_dev: bad arguments");
-    NCT_REQUIRE(ah < 4096 && aw < 4096 && bh < 4096 && bw < 4096, "nnf_upsample_dev: dims out of range (the NNF word holds 12 bits per coordinate)");
+    NCT_REQUIRE(nnf_half && nnf, "nnf_upsample_dev: null pointer");
+    NCT_REQUIRE(nnf_half != nnf, "nnf_upsample_dev: nnf_half and nnf are the same buffer");
+    NCT_REQUIRE(nct_nnf_dims_ok(ah, aw, bh, bw) && ah_half >= 1 && aw_half >= 1 && ah_half < 4096 && aw_half < 4096,
+                "nnf_upsample_dev: dims out of range (%dx%d from %dx%d -> %dx%d); NNF coordinates are 12-bit", ah, aw, ah_half, aw_half, bh, bw);
     return nctk_nnf_upsample(ctx, ctx->stream, nnf_half, nnf, ah, aw, bh, bw, ah_half, aw_half);
 }
 
@@ -123,14 +158,14 @@ int nct_patchmatch_dev(nct_ctx* ctx, const float* a_hwc, const float* b_hwc, int
                        uint32_t seed, uint32_t* nnf, float* dist) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(a_hwc && b_hwc && nnf && dist, "patchmatch_dev: null pointer");
-    NCT_REQUIRE(patch == 3, "patchmatch_dev: patch must be 3 (Config.h:70), got %d", patch);
+    NCT_TRY(pm_check(ctx, "patchmatch_dev", C, ah, aw, bh, bw, patch, iters, rs_max));
     return nctk_patchmatch(ctx, ctx->stream, a_hwc, b_hwc, C, ah, aw, bh, bw, iters, rs_max, seed, nnf, dist, nullptr);
 }
 int nct_patchmatch_bidir_dev(nct_ctx* ctx, const float* a_hwc, const float* b_hwc, int C, int ah, int aw, int bh, int bw, int patch, int iters, int rs_max,
                              uint32_t seed_ab, uint32_t seed_ba, uint32_t* ann, float* annd, uint32_t* bnn, float* bnnd, int unit_norm) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(a_hwc && b_hwc && ann && annd && bnn && bnnd, "patchmatch_bidir_dev: null pointer");
-    NCT_REQUIRE(patch == 3, "patchmatch_bidir_dev: patch must be 3 (Config.h:70), got %d", patch);
+    NCT_TRY(pm_check(ctx, "patchmatch_bidir_dev", C, ah, aw, bh, bw, patch, iters, rs_max));
     return nctk_patchmatch_bidir(ctx, ctx->stream, a_hwc, b_hwc, nullptr, nullptr, C, ah, aw, bh, bw, iters, rs_max, seed_ab, seed_ba, ann, annd, bnn, bnnd,
                                  unit_norm ? NCT_PM_ROWREJECT : NCT_PM_PLAIN, nullptr);
 }
@@ -140,19 +175,21 @@ int nct_bds_vote_features_dev(nct_ctx* ctx, const uint32_t* ann, const uint32_t*
                               int patch, float w_coherence, float w_complete) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(ann && bnn && pin_hwc && pout_hwc, "bds_vote_features_dev: null pointer");
-    NCT_REQUIRE(patch == 3, "bds_vote_features_dev: patch must be 3, got %d", patch);
+    NCT_REQUIRE(C > 0 && (C & 3) == 0 && C <= 512, "bds_vote_features_dev: C=%d must be a multiple of 4 and <= 512", C);
+    NCT_TRY(field_check(ctx, "bds_vote_features_dev", ah, aw, bh, bw, patch));
     return nctk_bds_vote_features(ctx, ctx->stream, ann, bnn, pin_hwc, pout_hwc, pw, C, ah, aw, bh, bw, w_coherence, w_complete);
 }
 int nct_bds_vote_image_dev(nct_ctx* ctx, const uint8_t* b_bgr, const uint32_t* ann, const uint32_t* bnn, int ah, int aw, int bh, int bw, int patch,
                            double w_coherence, double w_complete, uint8_t* out_bgr) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(b_bgr && ann && bnn && out_bgr, "bds_vote_image_dev: null pointer");
-    NCT_REQUIRE(patch == 3, "bds_vote_image_dev: patch must be 3, got %d", patch);
+    NCT_TRY(field_check(ctx, "bds_vote_image_dev", ah, aw, bh, bw, patch));
     return nctk_bds_vote_image(ctx, ctx->stream, b_bgr, ann, bnn, ah, aw, bh, bw, w_coherence, w_complete, out_bgr);
 }
 int nct_feature_distance_dev(nct_ctx* ctx, const float* a_hwc, const float* b_hwc, float* err, int C, int H, int W) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(a_hwc && b_hwc && err && C > 0 && (C & 3) == 0 && H > 0 && W > 0, "feature_distance_dev: bad arguments");
+    NCT_REQUIRE(a_hwc && b_hwc && err, "feature_distance_dev: null pointer");
+    NCT_TRY(map_check(ctx, "feature_distance_dev", C, H, W, 4));
     return nctk_feature_distance(ctx, ctx->stream, a_hwc, b_hwc, err, C, H * W);
 }
 

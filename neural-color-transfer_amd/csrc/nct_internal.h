@@ -109,6 +109,10 @@ template <typename T> struct DevBuf {
 #define NCT_SYNC() NCT_HIP(hipStreamSynchronize(ctx->stream))
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// the largest element count (C * H * W, H * W) a launcher takes as an int: cdiv rounds it up by at most 255 without leaving the type
+#define NCT_MAX_ELEMS (2147483647LL - 255)
+// the four dimensions of a field between two maps: the NNF word holds 12 bits per coordinate
+static inline bool nct_nnf_dims_ok(int ah, int aw, int bh, int bw) { return ah >= 1 && aw >= 1 && bh >= 1 && bw >= 1 && ah < 4096 && aw < 4096 && bh < 4096 && bw < 4096; }
 // host-side functions and types shared between translation units that stay out of the library's dynamic symbol table
 #define NCT_LOCAL __attribute__((visibility("hidden")))
 // a host copy for level-wise validation (host nullable): enqueued and waited for

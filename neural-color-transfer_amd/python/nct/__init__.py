@@ -949,14 +949,19 @@ class Context:
         bp = (C.c_void_p * n)(*[b.ctypes.data for b in bs])
         self._chk(self._l.nct_vgg19_load_raw(self._h, wp, bp, n))
 
-    def vgg19_features(self, bgr, deepest_tap=5):
-        """-> list of `deepest_tap` CHW fp32 arrays (tap 1 = conv1_1 … tap 5 = conv5_1)."""
+    def vgg19_features(self, bgr, deepest_tap=5, stride=None):
+        """-> list of `deepest_tap` CHW fp32 arrays (tap 1 = conv1_1 … tap 5 = conv5_1). stride: the image is handed over in a buffer with that many bytes from
+        one row to the next (>= 3 w; the bytes between rows are 0xFF) instead of packed."""
         img = np.ascontiguousarray(bgr, np.uint8)
         h, w = img.shape[:2]
+        if stride is not None and stride >= 3 * w:
+            buf = np.full((h, stride), 0xFF, np.uint8)
+            buf[:, :3 * w] = img.reshape(h, 3 * w)
+            img = buf
         outs = [np.empty((self.TAP_C[t],) + hw, np.float32) for t, hw in enumerate(_level_dims(h, w)[::-1][:deepest_tap])]
         ptrs = (C.c_void_p * 5)(*([o.ctypes.data for o in outs] + [None] * (5 - deepest_tap)))
         dims = np.zeros(15, np.int32)
-        self._chk(self._l.nct_vgg19_features(self._h, img, h, w, w * 3, deepest_tap, ptrs, _ptr(dims)))
+        self._chk(self._l.nct_vgg19_features(self._h, img, h, w, w * 3 if stride is None else stride, deepest_tap, ptrs, _ptr(dims)))
         for t, o in enumerate(outs):
             assert tuple(dims[3 * t:3 * t + 3]) == o.shape
         return outs

@@ -105,6 +105,16 @@ def normalize(feat):
         return f / np.sqrt((f * f).sum(0))[None]
 
 
+def response(feat):
+    """The `smooth` output of norm, GeneralizedPatchMatch.cu:257-272: dis, the pixels' L2 norms (:255), shifted by -min (add_scalar, :270) and scaled by
+    1 / (max - min) (scal, :271), in that order. A map whose norms are all equal (one pixel among them) gives 0 * (1 / 0) = NaN at every pixel, as that text
+    does; a dead pixel (min = 0) gives 0 there. feat: [C][h][w]; float64 [h][w]."""
+    f = np.asarray(feat, np.float64)
+    dis = np.sqrt((f * f).sum(0))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (dis - dis.min()) * (np.float64(1.0) / (dis.max() - dis.min()))
+
+
 def nnf_init(ah, aw, bh, bw):
     """init_Ann_kernel, GeneralizedPatchMatch.cu:527-545: bx = min(int(float(ax) / float(aw - 1) * (bw - 1)), bw - 1), by likewise; float arithmetic (the int
     bw - 1 is converted to float for the product), int() truncates. Needs aw, ah >= 2."""

@@ -31,6 +31,19 @@ def _nnf(kind, seed, ah, aw, bh, bw):
     return (y.astype(np.uint32) << 12) | x.astype(np.uint32)
 
 
+def _nnf_pair(kind, seed_a, seed_b, ah, aw, bh, bw):
+    """(ann, bnn) of a vote case. random / border: both fields of that kind; collapsed: ann collapsed, bnn random; collapsed_b: ann random, bnn collapsed —
+    half of R's pixels on each of two S pixels, the lists the vote kernels' hub pass sums (every block of 64 sources beyond a target's first)."""
+    ka, kb = {"collapsed": ("collapsed", "random"), "collapsed_b": ("random", "collapsed")}.get(kind, (kind, kind))
+    return _nnf(ka, seed_a, ah, aw, bh, bw), _nnf(kb, seed_b, bh, bw, ah, aw)
+
+
+def max_in_degree(bnn, ah, aw):
+    """the largest number of R pixels whose match is one S pixel"""
+    bnn = np.asarray(bnn, np.uint32)
+    return int(np.bincount(((bnn >> 12) * aw + (bnn & 0xFFF)).ravel().astype(np.int64), minlength=ah * aw).max())
+
+
 def _ulp_close(got, exp, ulps):
     got, exp = np.asarray(got, np.float64), np.asarray(exp, np.float64)
     return np.all(np.abs(got - exp) <= ulps * np.spacing(np.maximum(np.abs(exp), np.abs(got))))
@@ -91,6 +104,128 @@ def test_vote_image(oracle, weights):
             got = oracle.bds_vote_image(a, b, ann, bnn, wc, wp)
             exp, v = ref64.vote_image(a, b, ann, bnn, wc, wp, want_float=True)
             assert _vote_image_agrees(got, exp, v), (kind, ah, aw, bh, bw)
+
+
+# the vote cases of tests/test_gpu_dev_seams.py: (ah, aw, bh, bw); the second grid gives collapsed_b 486 / 2 sources per target, three hub blocks each
+SEAM_VOTE_GRIDS = [(7, 5, 9, 11), (20, 24, 18, 27)]
+SEAM_VOTE_C = (4, 64, 512)
+
+
+@pytest.mark.parametrize("weights", [(1.0, 2.0), (2.0, 1.0)])
+def test_votes_collapsed_b(oracle, weights):
+    """collapsed_b (a collapsed R -> S field: the hub pass's long source lists) at the seam test's shapes: the oracle, whose summation order is the kernels',
+    stays inside the tolerances test_gpu_vs_ref64.py::test_votes_vs_ref64 gives the other kinds, so that kind needs no bound of its own."""
+    wc, wp = weights
+    for (ah, aw, bh, bw) in SEAM_VOTE_GRIDS:
+        ia, ib = synth.image(1, ah, aw), synth.image(2, bh, bw)
+        ann, bnn = _nnf_pair("collapsed_b", 3, 4, ah, aw, bh, bw)
+        if bh * bw >= 260:
+            assert max_in_degree(bnn, ah, aw) >= 130
+        for C in SEAM_VOTE_C:
+            pin = synth.features(7, C, bh, bw)
+            got, gpw = oracle.bds_vote_features(ann, bnn, pin, wc, wp, want_pw=True)
+            exp, epw = ref64.vote_features(ann, bnn, pin, wc, wp)
+            dev = np.abs(got - exp) / (1e-6 + 1e-5 * np.abs(exp))
+            print("collapsed_b", (ah, aw, bh, bw), C, weights, "vote deviation / tolerance %.3g" % dev.max())
+            assert np.allclose(got, exp, rtol=1e-5, atol=1e-6) and np.allclose(gpw, epw, rtol=1e-5, atol=1e-12)
+        ei, v = ref64.vote_image(ia, ib, ann, bnn, wc, wp, want_float=True)
+        assert _vote_image_agrees(oracle.bds_vote_image(ia, ib, ann, bnn, wc, wp), ei, v)
+
+
+# collapsed_b at 350 x 350 (test_gpu_vs_ref64.py::test_votes_vs_ref64's largest case) puts 61 310 sources on one target: float sums of that length. There the
+# oracle's vote and weight deviate 1.28 and 1.31 times the tolerance of the other kinds (rtol 1e-5; atol 1e-6, 1e-12) from ref64, with either pair of weights
+# (test_votes_collapsed_b_long_lists prints it); up to 3 325 sources (88 x 88 from 70 x 95) it stays below a tenth of it. Four times the measured value, as for
+# NORM_MAP_TOL below, for lists longer than VOTE_LONG_LIST.
+VOTE_LONG_LIST = 10000
+VOTE_LONG_LIST_SCALE = 5.3
+
+
+def vote_tol_scale(bnn, ah, aw):
+    return VOTE_LONG_LIST_SCALE if max_in_degree(bnn, ah, aw) > VOTE_LONG_LIST else 1.0
+
+
+def test_votes_collapsed_b_long_lists(oracle):
+    """the calibration of VOTE_LONG_LIST_SCALE"""
+    C, (ah, aw, bh, bw) = 64, (350, 350, 350, 350)
+    pin = synth.features(7, C, bh, bw)
+    ann, bnn = _nnf_pair("collapsed_b", 3, 4, ah, aw, bh, bw)
+    assert vote_tol_scale(bnn, ah, aw) == VOTE_LONG_LIST_SCALE
+    worst = 0.0
+    for wc, wp in ((1.0, 2.0), (2.0, 1.0)):
+        got, gpw = oracle.bds_vote_features(ann, bnn, pin, wc, wp, want_pw=True)
+        exp, epw = ref64.vote_features(ann, bnn, pin, wc, wp)
+        worst = max(worst, float((np.abs(got - exp) / (1e-6 + 1e-5 * np.abs(exp))).max()), float((np.abs(gpw - epw) / (1e-12 + 1e-5 * np.abs(epw))).max()))
+    print("collapsed_b 350 x 350: deviation / tolerance %.3g" % worst)
+    assert 1.0 < worst and 4 * worst <= VOTE_LONG_LIST_SCALE
+
+
+# ---------------------------------------------------------------- N1 and the matching error alone, at the widths of a 16-lane row
+# C: one lane busy, a partial first round, a partial second round, one full round, a partial third round, eight rounds; HW: one pixel, a block with a dead row,
+# a full block, a second block with one live row (its other rows read the last pixel, clamped), several blocks
+NORM_C = (4, 8, 20, 64, 132, 512)
+NORM_HW = (1, 15, 16, 17, 63)
+# Largest |oracle - ref64| over that table (test_normalize_and_distance_alone prints it; synth.features maps, the dead-pixel map included): 8.11e-8 in the
+# normalised map (values in [0, 1]: one rounding of the norm and one of the quotient) and 1.54e-6 in the response, where the rounding of the norms is divided
+# by their spread (max - min). The bounds are four times that, the margin FEAT16_TOL leaves; the GPU tests import them.
+NORM_MAP_TOL = 3.3e-7
+NORM_RESP_TOL = 6.2e-6
+# the project's bound for the matching error of unit vectors (test_patch_distance)
+FEATURE_DISTANCE_TOL = 1e-5
+
+
+def norm_hw(HW):
+    return (7, 9) if HW == 63 else (1, HW)
+
+
+def norm_map(C, HW, seed=0, dead=False):
+    f = synth.features(100 + seed + C + HW, C, *norm_hw(HW))
+    if dead:
+        f.reshape(C, -1)[:, HW // 2] = 0
+    return f
+
+
+def check_normalize(normalize, C, HW, dead=False):
+    """normalize(f, want_resp=True) against ref64 within NORM_MAP_TOL / NORM_RESP_TOL; NaN exactly over a dead pixel's channels (and, in the response, over the
+    whole map where all norms are equal: HW = 1). Returns the two largest deviations."""
+    f = norm_map(C, HW, dead=dead)
+    got, resp = normalize(f, want_resp=True)
+    exp, eresp = ref64.normalize(f), ref64.response(f)
+    assert np.array_equal(np.isnan(got), np.isnan(exp)) and np.isnan(exp).sum() == (C if dead else 0)
+    assert np.array_equal(np.isnan(resp), np.isnan(eresp)) and np.isnan(eresp).all() == (HW == 1)
+    dm = float(np.nanmax(np.abs(got - exp), initial=0.0))
+    dr = 0.0 if HW == 1 else float(np.abs(resp - eresp).max())
+    assert dm <= NORM_MAP_TOL and dr <= NORM_RESP_TOL, (C, HW, dead, dm, dr)
+    if dead and HW > 1:
+        assert resp.reshape(-1)[HW // 2] == 0
+    return dm, dr
+
+
+def check_feature_distance(normalize, distance, C, HW):
+    a, b = normalize(norm_map(C, HW, 1)), normalize(norm_map(C, HW, 2))
+    d = float(np.abs(distance(a, b) - ref64.feature_distance(a, b)).max())
+    assert d <= FEATURE_DISTANCE_TOL, (C, HW, d)
+    return d
+
+
+def test_normalize_and_distance_alone(oracle):
+    """The calibration of NORM_MAP_TOL and NORM_RESP_TOL: the oracle carries the kernels' summation order bit for bit, and its largest deviation from ref64
+    over the C / HW table (dead-pixel maps from HW = 15 on) is what the constants above record."""
+    worst = np.zeros(3)
+    for C in NORM_C:
+        for HW in NORM_HW:
+            for dead in ((False, True) if HW > 1 else (False,)):
+                worst[:2] = np.maximum(worst[:2], check_normalize(oracle.feat_normalize, C, HW, dead))
+            worst[2] = max(worst[2], check_feature_distance(oracle.feat_normalize, oracle.feature_distance, C, HW))
+    print("oracle vs ref64 alone: map %.3g response %.3g matching error %.3g" % tuple(worst))
+    assert worst[0] * 4 <= NORM_MAP_TOL and worst[1] * 4 <= NORM_RESP_TOL, "the bounds no longer leave the margin of four over the oracle's deviation"
+
+
+def test_response_of_equal_norms_is_nan(oracle):
+    """max = min: the reference's text scales 0 by 1 / 0, so every pixel of the response is NaN (ref64.response); the normalised map is unaffected"""
+    f = np.tile(synth.features(5, 20, 1, 1), (1, 3, 5)) * np.where(np.arange(15).reshape(1, 3, 5) % 2, -1, 1).astype(np.float32)
+    got, resp = oracle.feat_normalize(f, want_resp=True)
+    assert np.isnan(resp).all() and np.isnan(ref64.response(f)).all()
+    assert np.abs(got - ref64.normalize(f)).max() <= NORM_MAP_TOL
 
 
 # ---------------------------------------------------------------- T1, T2
