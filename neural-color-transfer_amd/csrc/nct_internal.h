@@ -83,16 +83,20 @@ struct nct_ctx {
 enum { NCT_ST_OTHER = 0, NCT_ST_VGG, NCT_ST_CLUSTER, NCT_ST_PM, NCT_ST_VOTE, NCT_ST_KNN, NCT_ST_COLOR, NCT_ST_NONLOCAL, NCT_ST_WLS };
 static inline int nct_stage_tag(int stage, int level) { return stage * 8 + level; }
 
-// RAII scratch buffer from the context arena: allocated by its constructor, or empty (a member, an array element) until alloc()
+// The one owner of a block from the context arena, scratch of a call or a member of long-lived state: allocated by its constructor, or empty (a member, an array
+// element) until alloc(). The block goes back when the owner ends, or at reset()
 template <typename T> struct DevBuf {
     nct_ctx* c = nullptr; T* p = nullptr;
     DevBuf() = default;
     DevBuf(nct_ctx* ctx, size_t n) { alloc(ctx, n); }
-    ~DevBuf() { if (p) c->release(p); }
+    ~DevBuf() { reset(); }
     DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
-    bool alloc(nct_ctx* ctx, size_t n) { if (p) c->release(p); c = ctx; p = (T*)ctx->alloc(n * sizeof(T)); return p != nullptr; }
+    bool alloc(nct_ctx* ctx, size_t n) { reset(); c = ctx; p = (T*)ctx->alloc(n * sizeof(T)); return p != nullptr; }
+    bool reserve(nct_ctx* ctx, size_t n) { return p || alloc(ctx, n); }      // a block that is reserved once and then kept: nothing is requested while the owner holds one
+    void reset() { if (p) { c->release(p); p = nullptr; } }
+    void swap(DevBuf& o) { nct_ctx* oc = o.c; T* op = o.p; o.c = c; o.p = p; c = oc; p = op; }
+    void take(DevBuf& o) { reset(); c = o.c; p = o.p; o.p = nullptr; }        // o's block changes owner (what this one held goes back); o is left empty
     operator T*() const { return p; }
-    T* detach() { T* q = p; p = nullptr; return q; }           // the block stays reserved: the caller releases it
     bool ok() const { return p != nullptr; }
 };
 

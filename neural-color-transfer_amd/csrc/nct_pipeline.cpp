@@ -15,24 +15,17 @@ pair_state* pair_of(nct_ctx* ctx) {
     if (!ctx->pair) ctx->pair = new pair_state();
     return (pair_state*)ctx->pair;
 }
-void drop_images(nct_ctx* ctx, pair_state* P) {
-    if (P->src) { ctx->release(P->src); P->src = nullptr; }
-    for (uint8_t*& r : P->ref) if (r) { ctx->release(r); r = nullptr; }
-    if (P->out) { ctx->release(P->out); P->out = nullptr; }
-    if (P->full_src) { ctx->release(P->full_src); P->full_src = nullptr; }
-    if (P->full_out) { ctx->release(P->full_out); P->full_out = nullptr; }
-    if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
-    if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
-    for (uint8_t*& m : P->rmask) if (m) { ctx->release(m); m = nullptr; }
-    if (P->fin_mask) { ctx->release(P->fin_mask); P->fin_mask = nullptr; }
+void drop_images(pair_state* P) {
+    P->src.reset(); P->out.reset(); P->full_src.reset(); P->full_out.reset(); P->mask.reset(); P->full_mask.reset(); P->fin_mask.reset();
+    for (DevBuf<uint8_t>& r : P->ref) r.reset();
+    for (DevBuf<uint8_t>& m : P->rmask) m.reset();
     P->K = 0; P->finished = false; P->protect = 0;
 }
 // the images live in the context arena like every other device buffer (no hipMalloc/hipFree — device-wide synchronisation points —
-// between the pairs of other contexts in flight on the same GPU)
+// between the pairs of other contexts in flight on the same GPU). The sequence's and the images' owners give their blocks back here: the arena still holds them
 void nct_pair_free(nct_ctx* ctx) {
     if (!ctx->pair) return;
-    seq_free(ctx, (pair_state*)ctx->pair);
-    drop_images(ctx, (pair_state*)ctx->pair);
+    seq_free((pair_state*)ctx->pair);
     delete (pair_state*)ctx->pair; ctx->pair = nullptr;
 }
 
@@ -107,6 +100,44 @@ int finish_level(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int
     if (region) return nctk_region_compose(ctx, s, region->s_bgr, s_lab_full, out_lab, region->mask, (size_t)H * W, region->protect, cube, out_bgr);
     return nctk_lab2bgr(ctx, s, out_lab, out_bgr, (size_t)H * W, cube);
 }
+int finish_level_masked(nct_ctx* ctx, hipStream_t s, masked_fin& mf, const double* x_from, DevBuf<double>& x_mix, DevBuf<uint8_t>& m_buf, DevBuf<uint8_t>& f_buf,
+                        DevBuf<uint8_t>& fin_mask, int h, int w, int H, int W, const uint8_t* s_lab_full, uint8_t* out_lab, uint8_t* out_bgr, const full_target* full,
+                        const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube) {
+    const size_t n = (size_t)h * w;
+    const bool exact = full && full->finish == NCT_FINISH_EXACT;          // the upsampling finish composes at the working size (and, in its own pass, on the original)
+    const bool up = mf.p_l && full && !exact;                             // the masked upsampling finish with a reference mask (SPEC §6.19 rule 8)
+    mf.fh = exact ? full->H : H; mf.fw = exact ? full->W : W;
+    mf.f_l = exact ? full->mask : mf.mask_work;
+    full_target up_target;
+    const bool make_m = !mf.m_l;
+    if (make_m) mf.m_l = mf.p_l ? mf.p_l : mf.mask_l;
+    if (mf.p_l) {
+        if (make_m && mf.mask_l) {
+            // SPEC §6.12 rule 4 on one map: M_l = min(P_l, the source's level mask)
+            if (!m_buf.reserve(ctx, n)) return NCT_ERR_HIP;
+            NCT_TRY(nctk_region_merge(ctx, s, &mf.p_l, 1, nullptr, mf.mask_l, (int)n, nullptr, m_buf));
+            mf.m_l = m_buf;
+        }
+        // rule 5: F_l = P_l at the size the finish targets, then the minimum with the source's mask there. The last level's has the size of the result and is kept
+        // (rule 7) — unless the masked upsampling finish keeps F0 there: then F_l is scratch like every other level's
+        const bool keep_f = mf.last && !up;
+        DevBuf<uint8_t>& f = keep_f ? fin_mask : f_buf;
+        if (keep_f ? !f.alloc(ctx, (size_t)mf.fh * mf.fw) : !f.reserve(ctx, (size_t)H * W)) return NCT_ERR_HIP;
+        NCT_TRY(nctk_region_upsize_min(ctx, s, mf.p_l, h, w, mf.f_l, f, mf.fh, mf.fw));
+        mf.f_l = f;
+        if (up) {
+            // the upsampling pass composes on the original with F0 = min(resize(P' -> H0 x W0), M0); it has the result's size and is kept as fin_mask
+            if (!fin_mask.alloc(ctx, (size_t)full->H * full->W)) return NCT_ERR_HIP;
+            NCT_TRY(nctk_region_upsize_min(ctx, s, mf.p_l, h, w, full->mask, fin_mask, full->H, full->W));
+            up_target = *full; up_target.mask = fin_mask; full = &up_target;
+        }
+    }
+    // SPEC §6.11 rule 2: the coefficients move toward the identity by M_l — in place (a run that is no frame of a sequence), or out of place from the kept X'
+    if (!x_mix.reserve(ctx, 6 * n)) return NCT_ERR_HIP;
+    NCT_TRY(nctk_region_mix(ctx, s, x_from, mf.m_l, h, w, x_mix));
+    const region_fin rg{mf.f_l, mf.s_bgr, mf.protect};
+    return finish_level(ctx, s, x_mix, h, w, H, W, s_lab_full, out_lab, out_bgr, full, fl, cp, dbg, cube, &rg);
+}
 
 // what one reference owns during a run (SPEC §6.2): its image pyramid, its five un-normalised taps (HWC, indexed by level), its NNFs of both directions (kept from
 // level to level) and its R -> S distances; with several references also its G_k and E_k
@@ -177,7 +208,7 @@ struct pair_run {
     // The run's masks (neither: the run enqueues and reserves what it always did). mask: the source's region mask (SPEC §6.11; null: none), mpyr / mimg: its level masks —
     // the pyramid's single-channel form. ref_masked: a reference has a region mask (SPEC §6.12); p_merged: P_l of several references (rule 3), m_level: M_l where it is not
     // P_l itself (rule 4: a source mask as well), f_level: F_l of a level that is not the last (the last level's is pair_state's fin_mask).
-    // What a level's colour stage reads of all that (level_masks, color_stage): m_l, the mix mask on the level grid, and f_l, the compose mask at the size its finish targets
+    // What a level's colour stage reads of all that (level_masks, color_stage): p_l and m_l, the mix mask on the level grid; the compose mask is finish_level_masked's
     const uint8_t* mask;                           // a tracked frame of a sequence (SPEC §6.14) carries the matte first: lab_and_pyramids reads the pointer again
     DevBuf<uint8_t> mpyr[4]; const uint8_t* mimg[5] = {};
     const bool ref_masked;
@@ -191,7 +222,7 @@ struct pair_run {
     const bool refind;
     DevBuf<float> tapfeat;
     DevBuf<uint8_t> p_merged, m_level, f_level;
-    const uint8_t *p_l = nullptr, *m_l = nullptr, *f_l = nullptr;
+    const uint8_t *p_l = nullptr, *m_l = nullptr;
     const nct_color_params cp;
 
     pair_run(nct_ctx* c, const nct_params* p, nct_pair_timing* t, const run_extras& x)
@@ -221,18 +252,13 @@ struct pair_run {
     // SPEC §6.11 rule 1: the level masks, each resized from the level above like the image pyramid
     int source_level_masks() {
         mimg[4] = mask;
-        for (int l = 3; l >= 0; --l) {
-            if (!mpyr[l].alloc(ctx, (size_t)ah[l] * aw[l])) return NCT_ERR_HIP;
-            NCT_TRY(nctk_resize_u8c1(ctx, s, mimg[l + 1], ah[l + 1], aw[l + 1], mpyr[l], ah[l], aw[l]));
-            mimg[l] = mpyr[l];
-        }
-        return NCT_OK;
+        return source_mask_levels(ctx, s, mpyr, mimg, ah, aw, 0);
     }
 
     // SPEC §6.17 rules S2-S5: the frame's matte from the tap its own forward has just written, then the level masks of that matte. Its time counts as other_ms
     int refind_masks() {
         NCT_TRY(seq_refind_step(ctx, s, P, seq, tapfeat.ok() ? (const float*)tapfeat : (const float*)sfeat, s_lab_full));
-        if (tapfeat.ok()) ctx->release(tapfeat.detach());
+        tapfeat.reset();                                             // given back early: the level loop's requests come behind it
         mask = P->mask;
         NCT_TRY(source_level_masks());
         MARK(NCT_ST_OTHER, 0);
@@ -339,7 +365,7 @@ struct pair_run {
             if (mask && !m_level.alloc(ctx, N)) return NCT_ERR_HIP;
             if ((nlevels > 1 || up_masked) && !f_level.alloc(ctx, N)) return NCT_ERR_HIP;      // one level: its F is the last level's, pair_state's fin_mask (the masked upsampling finish keeps F0 there)
         }
-        if (!P->out) { P->out = (uint8_t*)ctx->alloc(N * 3); if (!P->out) return NCT_ERR_HIP; }
+        if (!P->out.reserve(ctx, N * 3)) return NCT_ERR_HIP;
         return d2h(lv->labels, labels, sizeof(int) * (size_t)ah[0] * aw[0]);
     }
 
@@ -488,8 +514,8 @@ struct pair_run {
             }
             NCT_TRY(nctk_seq_pull_hold(ctx, s, pulled, K, sel_label, seq->keep_pull[l], hold_lab, seq->keep_lab[l], seq->motion ? seq->field[l] : nullptr, mask ? mimg[l] : nullptr, h, w,
                                        seq->tau, seq->sigma, seq->pull_alt[l], mask ? (uint8_t*)m_level : nullptr, p_merged.ok() ? (uint8_t*)p_merged : nullptr));
-            ctx->release(hold_lab.detach());
-            std::swap(seq->keep_pull[l], seq->pull_alt[l]);
+            hold_lab.reset();                                        // given back early, behind the hold
+            seq->keep_pull[l].swap(seq->pull_alt[l]);
             p_l = seq->keep_pull[l];
             m_l = mask ? (const uint8_t*)m_level : p_l;
         } else {
@@ -549,32 +575,16 @@ struct pair_run {
         // (rule 3), the mask at the size the finish targets. A source mask only: f_l is that mask as it came. A masked frame of a sequence (SPEC §6.13 rule 2) mixes out of
         // place, from the kept X'_t into the level's own map, which the finish then reads: the state is never mixed. With a reference mask (SPEC §6.12 rules 4-5): F_l = P_l at that
         // size, then the minimum with the source's — the last level's is kept for nct_pair_fit_lut (rule 7)
-        const bool masked = mask || ref_masked;
-        full_target up_target;
-        if (masked) {
-            const bool exact = full && full->finish == NCT_FINISH_EXACT;      // the upsampling finish composes at the working size (and, in its own pass, on the original)
-            const int fh = exact ? full->H : H, fw = exact ? full->W : W;
-            f_l = exact ? full->mask : mask;
-            if (ref_masked) {
-                uint8_t* f = f_level;
-                if (l == nlevels - 1 && !up_masked) { if (!(P->fin_mask = (uint8_t*)ctx->alloc((size_t)fh * fw))) return NCT_ERR_HIP; f = P->fin_mask; }
-                NCT_TRY(nctk_region_upsize_min(ctx, s, p_l, ah[l], aw[l], f_l, f, fh, fw));
-                f_l = f;
-                if (full && up_masked) {
-                    // SPEC §6.19 rule 8: the masked upsampling finish composes on the original with F0 = min(resize(P' -> H0 x W0), M0); it has the result's size and is kept as fin_mask
-                    if (!(P->fin_mask = (uint8_t*)ctx->alloc((size_t)full->H * full->W))) return NCT_ERR_HIP;
-                    NCT_TRY(nctk_region_upsize_min(ctx, s, p_l, ah[l], aw[l], full->mask, P->fin_mask, full->H, full->W));
-                    up_target = *full; up_target.mask = P->fin_mask;
-                }
-            }
-            NCT_TRY(nctk_region_mix(ctx, s, seq ? seq->keep_x[l] : (double*)cb.x, m_l, ah[l], aw[l], cb.x));
+        // (finish_level_masked; m_level, f_level and the map come from the run's own requests). Every level reports M_l, F_l and the mixed map
+        if (mask || ref_masked) {
+            masked_fin mf{ref_masked ? p_l : nullptr, mask ? mimg[l] : nullptr, mask, P->src, P->protect, l == nlevels - 1, m_l};
+            NCT_TRY(finish_level_masked(ctx, s, mf, seq ? seq->keep_x[l] : (double*)cb.x, cb.x, m_level, f_level, P->fin_mask, ah[l], aw[l], H, W, s_lab_full, out_lab, P->out, full, fl,
+                                        cp, d, nct_cube_form(*prm)));
             if (qlv) {
-                NCT_TRY(dbg_copy(ctx, s, qlv->ab_mix[l], (double*)cb.x, (size_t)6 * na_px)); NCT_TRY(dbg_copy(ctx, s, qlv->mask[l], m_l, (size_t)na_px));
-                NCT_TRY(dbg_copy(ctx, s, qlv->mask_full[l], f_l, (size_t)fh * fw));
+                NCT_TRY(dbg_copy(ctx, s, qlv->ab_mix[l], (double*)cb.x, (size_t)6 * na_px)); NCT_TRY(dbg_copy(ctx, s, qlv->mask[l], mf.m_l, (size_t)na_px));
+                NCT_TRY(dbg_copy(ctx, s, qlv->mask_full[l], mf.f_l, (size_t)mf.fh * mf.fw));
             }
-        }
-        const region_fin rg{f_l, P->src, P->protect};
-        NCT_TRY(finish_level(ctx, s, seq && !masked ? seq->keep_x[l] : (double*)cb.x, ah[l], aw[l], H, W, s_lab_full, out_lab, P->out, full && up_masked ? &up_target : full, fl, cp, d, nct_cube_form(*prm), masked ? &rg : nullptr));
+        } else NCT_TRY(finish_level(ctx, s, seq ? seq->keep_x[l] : (double*)cb.x, ah[l], aw[l], H, W, s_lab_full, out_lab, P->out, full, fl, cp, d, nct_cube_form(*prm)));
         if (cs && cs->wls_iters) for (int q = 0; q < 6; ++q) cs->wls_iters[q] = wls_it[q];
         if (timing) timing->wls_iters[l] = *std::max_element(wls_it, wls_it + 6);
         MARK(NCT_ST_COLOR, l);
@@ -631,11 +641,9 @@ int process_resident(nct_ctx* ctx, const nct_params* prm, nct_pair_timing* timin
     // a new run on the resident images: an earlier full-resolution run is no longer the last one, and its two original-size images go back to the arena
     // (a full-resolution sequence keeps its two for its whole life: SPEC §6.9 rule 6)
     if (!(x.seq && x.seq->target())) {
-        if (P->full_src) { ctx->release(P->full_src); P->full_src = nullptr; }
-        if (P->full_out) { ctx->release(P->full_out); P->full_out = nullptr; }
-        if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
+        P->full_src.reset(); P->full_out.reset(); P->full_mask.reset();
     }
-    if (P->fin_mask) { ctx->release(P->fin_mask); P->fin_mask = nullptr; }
+    P->fin_mask.reset();
     P->finished = false;
     run_clock clock(ctx, timing, prm->flags);
     pair_run run(ctx, prm, timing, x);
@@ -684,10 +692,9 @@ const char* nct_working_size_rule(int h, int w, int max_side, int* work_h, int* 
 // the source and its K references (checked by the caller) into the arena
 static int upload_images(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, int K, const uint8_t* const* refs_bgr, const int* rh, const int* rw) {
     pair_state* P = pair_of(ctx);
-    drop_images(ctx, P);
-    P->src = (uint8_t*)ctx->alloc((size_t)sh * sw * 3);
-    if (!P->src) return NCT_ERR_HIP;
-    for (int k = 0; k < K; ++k) { P->ref[k] = (uint8_t*)ctx->alloc((size_t)rh[k] * rw[k] * 3); if (!P->ref[k]) return NCT_ERR_HIP; }
+    drop_images(P);
+    if (!P->src.alloc(ctx, (size_t)sh * sw * 3)) return NCT_ERR_HIP;
+    for (int k = 0; k < K; ++k) if (!P->ref[k].alloc(ctx, (size_t)rh[k] * rw[k] * 3)) return NCT_ERR_HIP;
     NCT_H2D(P->src, src_bgr, (size_t)sh * sw * 3);
     for (int k = 0; k < K; ++k) NCT_H2D(P->ref[k], refs_bgr[k], (size_t)rh[k] * rw[k] * 3);
     NCT_SYNC();
@@ -790,11 +797,11 @@ static int pair_set_region_from(nct_ctx* ctx, const uint8_t* mask, const nct_reg
     // the images stay; what an earlier run left is no longer the result of these settings
     P->finished = false;
     if (!mask) {
-        if (P->mask) { NCT_SYNC(); ctx->release(P->mask); P->mask = nullptr; }
+        if (P->mask.ok()) { NCT_SYNC(); P->mask.reset(); }
         P->protect = 0;
         return NCT_OK;
     }
-    if (!P->mask && !(P->mask = (uint8_t*)ctx->alloc((size_t)P->sh * P->sw))) return NCT_ERR_HIP;
+    if (!P->mask.reserve(ctx, (size_t)P->sh * P->sw)) return NCT_ERR_HIP;
     NCT_HIP(hipMemcpyAsync(P->mask, mask, (size_t)P->sh * P->sw, kind, ctx->stream));
     NCT_SYNC();
     P->protect = region ? region->protect : 0;
@@ -823,9 +830,9 @@ int nct_pair_set_ref_region(nct_ctx* ctx, int k, const uint8_t* mask, const nct_
     P->finished = false;
     const size_t n = (size_t)P->rh[k] * P->rw[k];
     if (!mask) {
-        if (P->rmask[k]) { NCT_SYNC(); ctx->release(P->rmask[k]); P->rmask[k] = nullptr; }
+        if (P->rmask[k].ok()) { NCT_SYNC(); P->rmask[k].reset(); }
     } else {
-        if (!P->rmask[k] && !(P->rmask[k] = (uint8_t*)ctx->alloc(n))) return NCT_ERR_HIP;
+        if (!P->rmask[k].reserve(ctx, n)) return NCT_ERR_HIP;
         NCT_H2D(P->rmask[k], mask, n);
         NCT_SYNC();
     }
@@ -915,26 +922,24 @@ static int fullres_run(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, con
     const bool shrunk = wh != sh || ww != sw;
     // the originals go to the arena and are shrunk there (rule 1: nct_resize_u8c3's arithmetic); the pair state holds the working-size pair
     pair_state* P = pair_of(ctx);
-    drop_images(ctx, P);
+    drop_images(P);
     DevBuf<uint8_t> s0(ctx, (size_t)sh * sw * 3);
     if (!s0.ok()) return NCT_ERR_HIP;
-    P->src = (uint8_t*)ctx->alloc((size_t)wh * ww * 3);
-    P->ref[0] = (uint8_t*)ctx->alloc((size_t)rwh * rww * 3);
-    if (!P->src || !P->ref[0]) return NCT_ERR_HIP;
+    if (!P->src.alloc(ctx, (size_t)wh * ww * 3) || !P->ref[0].alloc(ctx, (size_t)rwh * rww * 3)) return NCT_ERR_HIP;
     P->sh = P->sw = P->rh[0] = P->rw[0] = 0;
     NCT_TRY(upload_shrunk(ctx, src_bgr, sh, sw, P->src, wh, ww, s0));
     NCT_TRY(upload_shrunk(ctx, ref_bgr, rh, rw, P->ref[0], rwh, rww));
     DevBuf<uint8_t> m0;
     if (mask0) {
         // rule 5: the mask arrives at the original size; the working mask is its single-channel resize (equal sizes: a copy)
-        if (!m0.alloc(ctx, (size_t)sh * sw) || !(P->mask = (uint8_t*)ctx->alloc((size_t)wh * ww))) return NCT_ERR_HIP;
+        if (!m0.alloc(ctx, (size_t)sh * sw) || !P->mask.alloc(ctx, (size_t)wh * ww)) return NCT_ERR_HIP;
         NCT_H2D(m0, mask0, (size_t)sh * sw);
         NCT_TRY(nctk_resize_u8c1(ctx, ctx->stream, m0, sh, sw, P->mask, wh, ww));
         P->protect = region ? region->protect : 0;
     }
     DevBuf<uint8_t> q0;
     if (ref_mask0) {
-        if (!q0.alloc(ctx, (size_t)rh * rw) || !(P->rmask[0] = (uint8_t*)ctx->alloc((size_t)rwh * rww))) return NCT_ERR_HIP;
+        if (!q0.alloc(ctx, (size_t)rh * rw) || !P->rmask[0].alloc(ctx, (size_t)rwh * rww)) return NCT_ERR_HIP;
         NCT_H2D(q0, ref_mask0, (size_t)rh * rw);
         NCT_TRY(nctk_resize_u8c1(ctx, ctx->stream, q0, rh, rw, P->rmask[0], rwh, rww));
         P->protect = region ? region->protect : 0;
@@ -952,12 +957,12 @@ static int fullres_run(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, con
     run_extras x; x.fin = &fin;
     const int rc = process_resident(ctx, prm, timing, x);
     // the working-size result buffer holds the second-to-last level's image (the upsampling finish: the working-size result, which nobody asked for): no nct_pair_download of it
-    if (P->out) { ctx->release(P->out); P->out = nullptr; }
+    P->out.reset();
     if (rc) return rc;
     NCT_D2H(out_bgr, o0, (size_t)sh * sw * 3);
     NCT_SYNC();
-    P->full_src = s0.detach(); P->full_out = o0.detach(); P->full_h = sh; P->full_w = sw;
-    if (mask0) P->full_mask = m0.detach();
+    P->full_src.take(s0); P->full_out.take(o0); P->full_h = sh; P->full_w = sw;
+    if (mask0) P->full_mask.take(m0);
     return NCT_OK;
 }
 

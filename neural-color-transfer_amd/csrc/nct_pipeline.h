@@ -11,6 +11,8 @@ struct full_target { const uint8_t* src = nullptr; int H = 0, W = 0; uint8_t* ou
 // An open frame sequence (SPEC ยง6.3): what nct_seq_begin prepares once and every frame borrows โ the reference's pyramid and its five un-normalised taps (HWC, by
 // level) โ and the state the blend carries from frame to frame, per level X' ([2][h*w][3] doubles) and L (the frame's level image in 8-bit Lab). All of it comes from
 // the context's arena and outlives the runs; the frame and the reference at working size are pair_state's src / ref[0] as for a pair.
+// Every block of the two states has one owner, a DevBuf member: it goes back where the member is reset, and with the state (seq_free, nct_pair_free โ which
+// nct_destroy calls before the arena's blocks are freed). Blocks that change places (X' and warp_x, the kept pull and pull_alt, the matte and matte_alt) swap owners.
 // While motion compensation is on (SPEC ยง6.4, nct_seq_set_motion) it also holds, per level, L packed one word per pixel and the level's field (4 B per level pixel each).
 // A propagated frame (SPEC ยง6.5) with motion on warps X' out of place: warp_x, one map of the largest level run, reserved by the first such frame.
 // A sequence over several references (SPEC ยง6.18, nct_seq_begin_multi) holds the pyramid and the taps once per reference and, per level run, the label map of the last
@@ -28,46 +30,46 @@ struct seq_state {
     long gap = 0;                                              // propagated frames since the last full frame, whichever call ran them
     unsigned long long acc = 0;                                // sum of `changed` over the frames nct_seq_frame_auto propagated since the last full frame
     int ah[5], aw[5], bh[NCT_MAX_REFS][5], bw[NCT_MAX_REFS][5];
-    uint8_t* rpyr[NCT_MAX_REFS][4] = {}; float* rfeat[NCT_MAX_REFS][5] = {};     // per reference (SPEC ยง6.18): nct_seq_begin is the list of one
-    double* keep_x[5] = {}; uint8_t* keep_lab[5] = {};
+    DevBuf<uint8_t> rpyr[NCT_MAX_REFS][4]; DevBuf<float> rfeat[NCT_MAX_REFS][5];     // per reference (SPEC ยง6.18): nct_seq_begin is the list of one
+    DevBuf<double> keep_x[5]; DevBuf<uint8_t> keep_lab[5];
     double hold = 0;                                           // SPEC ยง6.18: the held selection's margin per window tap; plays no part with one reference
-    uint8_t* keep_label[5] = {};                               // several references only: the label map l_t of every level run, one byte per level pixel
+    DevBuf<uint8_t> keep_label[5];                             // several references only: the label map l_t of every level run, one byte per level pixel
     bool motion = false; nct_seq_motion mp = {0, 0, 0};
-    uint32_t* keep_pk[5] = {}; int16_t* field[5] = {};
-    double* warp_x = nullptr;
+    DevBuf<uint32_t> keep_pk[5]; DevBuf<int16_t> field[5];
+    DevBuf<double> warp_x;
     bool tracking = false;                                     // SPEC ยง6.14: carry the matte along the field in front of every frame but the matte's own
     bool matte_fresh = false;                                  // nct_seq_set_region gave a matte that no frame has used yet: the next frame that runs is its own
     long matte_age = 0;                                        // frames run since the matte's own frame while tracking was on
-    uint8_t* matte_alt = nullptr;
+    DevBuf<uint8_t> matte_alt;
     bool snap = false; nct_region_snap_params snap_p = {0, 0, 0};  // SPEC ยง6.15: snap the carried matte to the frame's edges with these parameters
     // SPEC ยง6.17 (nct_seq_set_region_model): the model's rows on the device, [model_n_in + model_n_out][model_C], inside first, held until the model is replaced or removed
     // or the sequence ends; null: no model. model_p: the parameters of the re-find, model_protect: nct_region_params.protect of the re-found matte
-    int16_t* model_rows = nullptr; int model_tap = 0, model_C = 0, model_n_in = 0, model_n_out = 0;
+    DevBuf<int16_t> model_rows; int model_tap = 0, model_C = 0, model_n_in = 0, model_n_out = 0;
     nct_region_refind_params model_p = {0, 0, 0, 0, {0, 0, 0}}; int model_protect = 0;
     // SPEC ยง6.19 (nct_seq_set_ref_region): the masked references' level masks Q_k,l below the working size (Q_k at the working size is pair_state's rmask[k]), built once
     // per set call; per level run the held pull P' of the last frame and the block the next hold or carry writes โ the rule gathers, so the two change places; pull_kept:
     // keep_pull holds a full frame's P' under the masks in force (false after any set, replace or remove). rh0 / rw0: the references' sizes as they arrived
-    uint8_t* rq[NCT_MAX_REFS][4] = {}; uint8_t *keep_pull[5] = {}, *pull_alt[5] = {};
+    DevBuf<uint8_t> rq[NCT_MAX_REFS][4], keep_pull[5], pull_alt[5];
     bool pull_kept = false;
     int rh0[NCT_MAX_REFS] = {}, rw0[NCT_MAX_REFS] = {};
     full_target full;
     const full_target* target() const { return full.H ? &full : nullptr; }
 };
 struct pair_state {
-    uint8_t *src = nullptr, *out = nullptr;                    // device BGR images
+    DevBuf<uint8_t> src, out;                                  // device BGR images
     seq_state* seq = nullptr;
-    uint8_t* ref[NCT_MAX_REFS] = {};                           // the K references (SPEC ยง6.2; a pair: K = 1)
+    DevBuf<uint8_t> ref[NCT_MAX_REFS];                         // the K references (SPEC ยง6.2; a pair: K = 1)
     int K = 0;
     int sh = 0, sw = 0, rh[NCT_MAX_REFS] = {}, rw[NCT_MAX_REFS] = {};
-    uint8_t *full_src = nullptr, *full_out = nullptr;          // a finished full-resolution run (SPEC ยง6.1): the original source and its result, full_h x full_w, kept for nct_pair_fit_lut
+    DevBuf<uint8_t> full_src, full_out;                        // a finished full-resolution run (SPEC ยง6.1): the original source and its result, full_h x full_w, kept for nct_pair_fit_lut
     int full_h = 0, full_w = 0;
-    uint8_t *mask = nullptr, *full_mask = nullptr;             // the source's region mask (SPEC ยง6.11): sh x sw bytes, set by nct_pair_set_region, dropped with the images; after a masked
+    DevBuf<uint8_t> mask, full_mask;                           // the source's region mask (SPEC ยง6.11): sh x sw bytes, set by nct_pair_set_region, dropped with the images; after a masked
     int protect = 0;                                           // full-resolution run also the mask at full_h x full_w, beside full_src / full_out. protect: nct_region_params
                                                                // An open sequence (SPEC ยง6.13): both are nct_seq_set_region's and go back with the sequence (seq_free)
-    uint8_t* rmask[NCT_MAX_REFS] = {};                         // the references' region masks (SPEC ยง6.12): rh[k] x rw[k] bytes, set by nct_pair_set_ref_region, dropped with the images
+    DevBuf<uint8_t> rmask[NCT_MAX_REFS];                       // the references' region masks (SPEC ยง6.12): rh[k] x rw[k] bytes, set by nct_pair_set_ref_region, dropped with the images
                                                                // An open sequence (SPEC ยง6.19): nct_seq_set_ref_region's, at the references' working size
-    uint8_t* fin_mask = nullptr;                               // the last level's target mask F of a run with a reference mask, at the size of its result (rule 7: nct_pair_fit_lut); gone with the next run
-    bool ref_masked() const { for (const uint8_t* m : rmask) if (m) return true; return false; }
+    DevBuf<uint8_t> fin_mask;                                  // the last level's target mask F of a run with a reference mask, at the size of its result (rule 7: nct_pair_fit_lut); gone with the next run
+    bool ref_masked() const { for (const DevBuf<uint8_t>& m : rmask) if (m.ok()) return true; return false; }
     bool finished = false;                                     // the last run on these images ran to its end: `out` (or full_out) holds its result
 };
 
@@ -78,7 +80,7 @@ static const int kTapC[5] = {64, 128, 256, 512, 512};       // tap 1 (conv1_1) โ
 
 // ---- nct_pipeline.cpp
 NCT_LOCAL pair_state* pair_of(nct_ctx* ctx);
-NCT_LOCAL void drop_images(nct_ctx* ctx, pair_state* P);    // drop what the context holds of the last pair / reference list
+NCT_LOCAL void drop_images(pair_state* P);                  // drop what the context holds of the last pair / reference list
 // what a run is asked for beside its result, every member nullable and filled by name (run_extras x; x.fin = โฆ;). lv: host copies of the level intermediates; color (a pair
 // only): [5] the colour stage's coefficient maps per level; fin (K = 1, or a frame of a sequence): the full-resolution finish; seq: the run is a frame of this open sequence, slv: where that
 // frame's X'_t, tau_p and fields go; qlv: where a masked run reports Q_k,l, P_k,l, M_l, F_l and X' (SPEC ยง6.11, ยง6.12: the one report target of both kinds of mask);
@@ -134,6 +136,37 @@ struct NCT_LOCAL full_lab {
 struct region_fin { const uint8_t* mask; const uint8_t* s_bgr; int protect; };
 NCT_LOCAL int finish_level(nct_ctx* ctx, hipStream_t s, const double* x, int h, int w, int H, int W, const uint8_t* s_lab_full, uint8_t* out_lab, uint8_t* out_bgr,
                            const full_target* full, const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube, const region_fin* region = nullptr);
+// The finish of a masked level, the one copy of SPEC ยง6.11 rule 3, ยง6.12 rules 4-5, ยง6.13 rules 2-4 and ยง6.19 rule 8, for a level of a run and for a propagated frame:
+// the mix mask M_l, the compose mask F_l at the size the finish targets, the mix of x_from by M_l into x_mix, finish_level on the mixed map. Without a reference mask
+// (p_l null) M_l is the source's level mask and F_l the source's mask as it came: no launch but the mix. With one, M_l = min(p_l, mask_l) โ made here unless the caller
+// has made it (m_l) โ and F_l = min(resize(p_l), the source's mask at that size); the masked upsampling finish also composes on the original with
+// F0 = min(resize(p_l -> full's size), full->mask), through a copy of the target that names it. F of the last level has the size of the result and is kept as fin_mask
+// for nct_pair_fit_lut (the masked upsampling finish: F0). The owners are filled here where they are empty, in the order m_buf, f_buf or fin_mask, fin_mask (F0), x_mix:
+// a level of a run brings m_buf, f_buf and x_mix from its own requests, a propagated frame brings them empty. The other arguments are finish_level's
+struct masked_fin {
+    const uint8_t* p_l;                            // P_l, or a propagated frame's P', on the level grid; null: no reference mask
+    const uint8_t *mask_l, *mask_work;             // the source's mask on the level grid and at H x W; null: no source mask. At the target's size it is full->mask
+    const uint8_t* s_bgr; int protect;             // the source at H x W and nct_region_params.protect: what the compose reads
+    bool last;                                     // the run's last level: its F is kept
+    const uint8_t* m_l;                            // in: M_l where the caller has made it, else null; out: the mix mask, h x w
+    const uint8_t* f_l = nullptr; int fh = 0, fw = 0;   // out: the compose mask and its size, for the caller's report
+};
+NCT_LOCAL int finish_level_masked(nct_ctx* ctx, hipStream_t s, masked_fin& mf, const double* x_from, DevBuf<double>& x_mix, DevBuf<uint8_t>& m_buf, DevBuf<uint8_t>& f_buf,
+                                  DevBuf<uint8_t>& fin_mask, int h, int w, int H, int W, const uint8_t* s_lab_full, uint8_t* out_lab, uint8_t* out_bgr, const full_target* full,
+                                  const full_lab& fl, const nct_color_params& cp, const nct_color_debug* dbg, int cube);
+// SPEC ยง6.11 rule 1: a source mask's level masks from level 3 down to level `down_to`, each a block of its own resized from the level above like the image pyramid;
+// mimg[4] is the mask at the working size, mimg[l] then names level l's
+static inline int source_mask_levels(nct_ctx* ctx, hipStream_t s, DevBuf<uint8_t>* mpyr, const uint8_t** mimg, const int* lh, const int* lw, int down_to) {
+    for (int l = 3; l >= down_to; --l) {
+        if (!mpyr[l].alloc(ctx, (size_t)lh[l] * lw[l])) return NCT_ERR_HIP;
+        NCT_TRY(nctk_resize_u8c1(ctx, s, mimg[l + 1], lh[l + 1], lw[l + 1], mpyr[l], lh[l], lw[l]));
+        mimg[l] = mpyr[l];
+    }
+    return NCT_OK;
+}
+// the first lines of what acts on the open sequence: P names the context's pair state, refused without one
+#define NCT_OPEN_SEQ(P, who) pair_state* const P = (pair_state*)ctx->pair; \
+    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "%s: no sequence is open (nct_seq_begin first)", who)
 // nct_pair_set_region with the mask already on the device (nct_pair_select_region, SPEC ยง6.16): the same checks, block and state, a device-to-device copy
 NCT_LOCAL int pair_set_region_dev(nct_ctx* ctx, const uint8_t* d_mask, const nct_region_params* region);
 // ---- nct_region_select.cpp, shared with the region models of nct_region_model.cpp (SPEC ยง6.17)
@@ -150,7 +183,7 @@ NCT_LOCAL int select_seed_rows(nct_ctx* ctx, const char* who, const uint8_t* d_s
 // ---- nct_seq.cpp
 // nct_seq_set_region with the mask already on the device, at the size frames arrive (nct_seq_select_region, SPEC ยง6.16)
 NCT_LOCAL int seq_set_region_dev(nct_ctx* ctx, const uint8_t* d_mask, const nct_region_params* region);
-NCT_LOCAL void seq_free(nct_ctx* ctx, pair_state* P);       // what an open sequence holds goes back to the arena
+NCT_LOCAL void seq_free(pair_state* P);                     // what an open sequence holds goes back to the arena, its region mask included
 // SPEC ยง6.4: level l's field from L_t (`lab`) and the kept packed map: the first level run searches radius0 around (0, 0), every other level radius around twice the
 // previous level's vector
 NCT_LOCAL int seq_motion_level(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, const uint8_t* lab);
@@ -164,6 +197,10 @@ NCT_LOCAL int seq_field_chain(nct_ctx* ctx, hipStream_t s, seq_state* q, const u
 // not, to the frame's Lab image at the size frames arrive: lab_work, the working-size frame in Lab that the caller holds, or โ a full-resolution sequence whose
 // frames are larger โ the original frame converted into scratch of this call
 NCT_LOCAL int seq_track_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, const uint8_t* const* simg, const uint8_t* lab_work);
+// The tail of the track step and of the re-find (SPEC ยง6.15 rule 3, ยง6.17 rule S5): `iters` snap passes of the matte in force against the frame's Lab image at the
+// size frames arrive (lab_work, or the original frame converted into scratch of this call), each out of place into matte_alt โ reserved by the caller โ after which
+// the two change places; then a full-resolution sequence shrinks the matte to the working-size one, as nct_seq_set_region makes it
+NCT_LOCAL int seq_matte_snap(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, const uint8_t* lab_work, const nct_region_snap_params& sp, int iters);
 // ---- nct_region_model.cpp
 // SPEC ยง6.17 rules S2-S5, behind a full frame's forward and in front of its level masks: the frame's matte re-found from tap_hwc โ the model's tap of that forward,
 // un-normalised and channel-last on the working-size grid โ with the matte the track step left as the prior (none without a matte or without state), straight to the size

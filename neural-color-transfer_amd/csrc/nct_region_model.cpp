@@ -111,35 +111,20 @@ int seq_refind_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, co
     DevBuf<uint8_t> m(ctx, cells);
     if (!rows.ok() || !m.ok()) return NCT_ERR_HIP;
     NCT_TRY(nctk_feat_quantize(ctx, s, tap_hwc, rows, C, cells));
-    NCT_TRY(nctk_region_score(ctx, s, rows, cells, C, q->model_rows, q->model_n_in, q->model_rows + (size_t)q->model_n_in * C, q->model_n_out, p.sharpness, p.floor_permille, nullptr, m));
+    NCT_TRY(nctk_region_score(ctx, s, rows, cells, C, q->model_rows, q->model_n_in, (int16_t*)q->model_rows + (size_t)q->model_n_in * C, q->model_n_out, p.sharpness, p.floor_permille, nullptr, m));
     // rule S3: the matte the track step left is the prior, unless the sequence has no state — the old shot's matte is not evidence
-    const bool had = P->mask != nullptr, prior = had && q->frames > 0;
-    if (!P->mask && !(P->mask = (uint8_t*)ctx->alloc((size_t)h * w))) return NCT_ERR_HIP;
-    if (full && !P->full_mask && !(P->full_mask = (uint8_t*)ctx->alloc(N))) return NCT_ERR_HIP;
-    uint8_t*& matte = full ? P->full_mask : P->mask;
-    if ((prior || p.snap_iters > 0) && !q->matte_alt && !(q->matte_alt = (uint8_t*)ctx->alloc(N))) return NCT_ERR_HIP;
+    const bool had = P->mask.ok(), prior = had && q->frames > 0;
+    if (!P->mask.reserve(ctx, (size_t)h * w)) return NCT_ERR_HIP;
+    if (full && !P->full_mask.reserve(ctx, N)) return NCT_ERR_HIP;
+    DevBuf<uint8_t>& matte = full ? P->full_mask : P->mask;
+    if ((prior || p.snap_iters > 0) && !q->matte_alt.reserve(ctx, N)) return NCT_ERR_HIP;
     // rule S4: from the working-size tap grid straight to the size frames arrive, out of place where there is a prior; the two matte blocks then change places
     if (prior) {
         NCT_TRY(nctk_region_refind(ctx, s, m, ht, wt, matte, H, W, p.margin, q->matte_alt));
-        std::swap(matte, q->matte_alt);
+        matte.swap(q->matte_alt);
     } else NCT_TRY(nctk_region_refind(ctx, s, m, ht, wt, nullptr, H, W, p.margin, matte));
-    if (p.snap_iters > 0) {
-        DevBuf<uint8_t> lab0;
-        const uint8_t* guide = lab_work;
-        if (H != h || W != w) {
-            if (!lab0.alloc(ctx, N * 3)) return NCT_ERR_HIP;
-            NCT_TRY(nctk_bgr2lab(ctx, s, P->full_src, lab0, N));
-            guide = lab0;
-        }
-        for (int it = 0; it < p.snap_iters; ++it) {
-            NCT_TRY(nctk_region_snap(ctx, s, matte, guide, H, W, &p.snap, q->matte_alt));
-            std::swap(matte, q->matte_alt);
-        }
-    }
-    if (full) {
-        q->full.mask = P->full_mask;
-        NCT_TRY(nctk_resize_u8c1(ctx, s, P->full_mask, H, W, P->mask, h, w));
-    }
+    // rule S5: the model's snap passes, then the shrink of a full-resolution sequence
+    NCT_TRY(seq_matte_snap(ctx, s, P, q, lab_work, p.snap, p.snap_iters));
     P->protect = q->model_protect;
     if (!had) { q->matte_fresh = false; q->matte_age = 0; }      // this frame is the new matte's own
     return NCT_OK;
@@ -297,11 +282,10 @@ int nct_pair_apply_region_model(nct_ctx* ctx, const nct_region_model* model, con
 // SPEC §6.17 rules S1-S6: from the next full frame on the open sequence re-finds the model's object; NULL removes the model
 int nct_seq_set_region_model(nct_ctx* ctx, const nct_region_model* model, const nct_region_refind_params* params, const nct_region_params* region) {
     NCT_CTX_ENTER();
-    pair_state* P = (pair_state*)ctx->pair;
-    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_set_region_model: no sequence is open (nct_seq_begin first)");
+    NCT_OPEN_SEQ(P, "seq_set_region_model");
     seq_state* q = P->seq;
     if (!model) {
-        if (q->model_rows) { NCT_SYNC(); ctx->release(q->model_rows); q->model_rows = nullptr; }
+        if (q->model_rows.ok()) { NCT_SYNC(); q->model_rows.reset(); }
         return NCT_OK;
     }
     NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "seq_set_region_model: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
@@ -313,8 +297,7 @@ int nct_seq_set_region_model(nct_ctx* ctx, const nct_region_model* model, const 
     NCT_H2D(rows, model->in.data(), sizeof(int16_t) * model->in.size());
     if (!model->out.empty()) NCT_H2D((int16_t*)rows + model->in.size(), model->out.data(), sizeof(int16_t) * model->out.size());
     NCT_SYNC();
-    if (q->model_rows) ctx->release(q->model_rows);
-    q->model_rows = rows.detach();
+    q->model_rows.take(rows);
     q->model_tap = model->tap; q->model_C = model->C; q->model_n_in = (int)(model->in.size() / model->C); q->model_n_out = (int)(model->out.size() / model->C);
     q->model_p = p; q->model_protect = region ? region->protect : 0;
     P->finished = false;                                         // what the last frame left is no longer the result of these settings

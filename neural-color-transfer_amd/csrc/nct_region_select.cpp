@@ -212,8 +212,7 @@ int nct_pair_select_region(nct_ctx* ctx, const uint8_t* strokes, const nct_regio
 // nct_region_select on a frame of the open sequence's size, then nct_seq_set_region with the matte where it is
 int nct_seq_select_region(nct_ctx* ctx, const uint8_t* frame_bgr, const uint8_t* strokes, const nct_region_select_params* params, const nct_region_params* region) {
     NCT_CTX_ENTER();
-    pair_state* P = (pair_state*)ctx->pair;
-    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_select_region: no sequence is open (nct_seq_begin first)");
+    NCT_OPEN_SEQ(P, "seq_select_region");
     if (P->seq->target())
         return ctx->fail(NCT_ERR_STATE, "seq_select_region: not defined in a full-resolution sequence (select on the frame with nct_region_select, then nct_seq_set_region)");
     NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "seq_select_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);

@@ -5,39 +5,22 @@
 #include <algorithm>
 
 // what motion compensation holds goes back to the arena
-static void seq_motion_free(nct_ctx* ctx, seq_state* q) {
-    for (int l = 0; l < 5; ++l) {
-        if (q->keep_pk[l]) { ctx->release(q->keep_pk[l]); q->keep_pk[l] = nullptr; }
-        if (q->field[l]) { ctx->release(q->field[l]); q->field[l] = nullptr; }
-    }
-    if (q->warp_x) { ctx->release(q->warp_x); q->warp_x = nullptr; }
+static void seq_motion_free(seq_state* q) {
+    for (int l = 0; l < 5; ++l) { q->keep_pk[l].reset(); q->field[l].reset(); }
+    q->warp_x.reset();
     q->motion = false;
 }
-// what an open sequence holds goes back to the arena
-void seq_free(nct_ctx* ctx, pair_state* P) {
-    seq_state* q = P->seq;
-    if (!q) return;
-    seq_motion_free(ctx, q);
-    for (int l = 0; l < 5; ++l) {
-        for (int k = 0; k < NCT_MAX_REFS; ++k) {
-            if (l < 4 && q->rpyr[k][l]) ctx->release(q->rpyr[k][l]);
-            if (q->rfeat[k][l]) ctx->release(q->rfeat[k][l]);
-        }
-        if (q->keep_x[l]) ctx->release(q->keep_x[l]);
-        if (q->keep_lab[l]) ctx->release(q->keep_lab[l]);
-        if (q->keep_label[l]) ctx->release(q->keep_label[l]);
-        // the reference masks' level masks and the kept pull (SPEC §6.19) end with the sequence; the masks at the working size go back with the images (drop_images)
-        for (int k = 0; k < NCT_MAX_REFS; ++k) if (l < 4 && q->rq[k][l]) ctx->release(q->rq[k][l]);
-        if (q->keep_pull[l]) ctx->release(q->keep_pull[l]);
-        if (q->pull_alt[l]) ctx->release(q->pull_alt[l]);
-    }
-    // the sequence's region mask (SPEC §6.13 rule 1) ends with it
-    if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
-    if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
-    if (q->matte_alt) { ctx->release(q->matte_alt); q->matte_alt = nullptr; }
-    if (q->model_rows) { ctx->release(q->model_rows); q->model_rows = nullptr; }     // the region model's rows (SPEC §6.17)
-    P->protect = 0;
-    delete q; P->seq = nullptr;
+// the sequence's matte blocks go back to the arena (the caller has waited for the stream)
+static void seq_mask_drop(pair_state* P, seq_state* q) {
+    P->mask.reset(); P->full_mask.reset(); q->matte_alt.reset();
+    q->full.mask = nullptr; P->protect = 0; q->matte_fresh = false; q->matte_age = 0;
+}
+// what an open sequence holds goes back to the arena: its region mask (SPEC §6.13 rule 1), which lives in the pair state, ends with it; everything else is the
+// state's own and goes back with it. The reference masks at the working size go back with the images (drop_images)
+void seq_free(pair_state* P) {
+    if (!P->seq) return;
+    seq_mask_drop(P, P->seq);
+    delete P->seq; P->seq = nullptr;
 }
 
 int seq_motion_level(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, const uint8_t* lab) {
@@ -92,15 +75,21 @@ int seq_track_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, con
         DevBuf<uint8_t> lab[5];
         NCT_TRY(seq_field_chain(ctx, s, q, simg, top, lab));
     }
-    uint8_t*& matte = q->target() ? P->full_mask : P->mask;
+    DevBuf<uint8_t>& matte = q->target() ? P->full_mask : P->mask;
     const int H = q->target() ? q->full.H : P->sh, W = q->target() ? q->full.W : P->sw;
-    if (!q->matte_alt && !(q->matte_alt = (uint8_t*)ctx->alloc((size_t)H * W))) return NCT_ERR_HIP;
+    if (!q->matte_alt.reserve(ctx, (size_t)H * W)) return NCT_ERR_HIP;
     if (q->motion) {
         NCT_TRY(nctk_seq_matte_warp(ctx, s, matte, H, W, q->field[top], q->ah[top], q->aw[top], q->matte_alt));
-        std::swap(matte, q->matte_alt);
+        matte.swap(q->matte_alt);
     }
-    if (q->snap) {
-        // SPEC §6.15 rule 3: the guide is the frame in Lab at the size frames arrive; the block the carry has left takes the snapped matte
+    // SPEC §6.15 rule 3: one pass; the block the carry has left takes the snapped matte
+    return seq_matte_snap(ctx, s, P, q, lab_work, q->snap_p, q->snap ? 1 : 0);
+}
+
+int seq_matte_snap(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, const uint8_t* lab_work, const nct_region_snap_params& sp, int iters) {
+    DevBuf<uint8_t>& matte = q->target() ? P->full_mask : P->mask;
+    const int H = q->target() ? q->full.H : P->sh, W = q->target() ? q->full.W : P->sw;
+    if (iters > 0) {
         DevBuf<uint8_t> lab0;
         const uint8_t* guide = lab_work;
         if (H != P->sh || W != P->sw) {
@@ -108,11 +97,13 @@ int seq_track_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, con
             NCT_TRY(nctk_bgr2lab(ctx, s, P->full_src, lab0, (size_t)H * W));
             guide = lab0;
         }
-        NCT_TRY(nctk_region_snap(ctx, s, matte, guide, H, W, &q->snap_p, q->matte_alt));
-        std::swap(matte, q->matte_alt);
+        for (int it = 0; it < iters; ++it) {
+            NCT_TRY(nctk_region_snap(ctx, s, matte, guide, H, W, &sp, q->matte_alt));
+            matte.swap(q->matte_alt);
+        }
     }
     if (q->target()) {
-        // the carry and the snap ran at the original size; the working-size matte is the shrink of their result, as nct_seq_set_region makes it
+        // the carry, the re-find and the snap ran at the original size; the working-size matte is the shrink of their result
         q->full.mask = P->full_mask;
         NCT_TRY(nctk_resize_u8c1(ctx, s, P->full_mask, H, W, P->mask, P->sh, P->sw));
     }
@@ -132,8 +123,8 @@ int nct_seq_end(nct_ctx* ctx) {
     pair_state* P = (pair_state*)ctx->pair;
     if (!P || !P->seq) return NCT_OK;
     NCT_SYNC();
-    seq_free(ctx, P);
-    drop_images(ctx, P);
+    seq_free(P);
+    drop_images(P);
     return NCT_OK;
 }
 
@@ -146,8 +137,7 @@ void nct_seq_motion_default(nct_seq_motion* p) {
 // a sequence that already has frames; turning it off gives them back
 int nct_seq_set_motion(nct_ctx* ctx, const nct_seq_motion* mp) {
     NCT_CTX_ENTER();
-    pair_state* P = (pair_state*)ctx->pair;
-    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_set_motion: no sequence is open (nct_seq_begin first)");
+    NCT_OPEN_SEQ(P, "seq_set_motion");
     seq_state* q = P->seq;
     if (mp) {
         NCT_REQUIRE(mp->radius0 >= 0 && mp->radius0 <= 8, "seq_set_motion: radius0 must be in [0, 8] (got %d)", mp->radius0);
@@ -156,21 +146,20 @@ int nct_seq_set_motion(nct_ctx* ctx, const nct_seq_motion* mp) {
     }
     const bool on = mp && (mp->radius0 > 0 || mp->radius > 0);
     if (!on) {
-        if (q->motion) { NCT_SYNC(); seq_motion_free(ctx, q); }
+        if (q->motion) { NCT_SYNC(); seq_motion_free(q); }
         return NCT_OK;
     }
     q->mp = *mp;
     if (q->motion) return NCT_OK;
     for (int l = 0; l < q->prm.levels; ++l) {
         const size_t n = (size_t)q->ah[l] * q->aw[l];
-        q->keep_pk[l] = (uint32_t*)ctx->alloc(sizeof(uint32_t) * n); q->field[l] = (int16_t*)ctx->alloc(sizeof(int16_t) * 2 * n);
-        if (!q->keep_pk[l] || !q->field[l]) { seq_motion_free(ctx, q); return NCT_ERR_HIP; }
+        if (!q->keep_pk[l].alloc(ctx, n) || !q->field[l].alloc(ctx, 2 * n)) { seq_motion_free(q); return NCT_ERR_HIP; }
     }
     q->motion = true;
     if (q->frames > 0) {
         for (int l = 0; l < q->prm.levels; ++l) {
             const int rc = nctk_seq_pack(ctx, ctx->stream, q->keep_lab[l], q->ah[l] * q->aw[l], q->keep_pk[l]);
-            if (rc) { seq_motion_free(ctx, q); return rc; }
+            if (rc) { seq_motion_free(q); return rc; }
         }
     }
     return NCT_OK;
@@ -178,27 +167,18 @@ int nct_seq_set_motion(nct_ctx* ctx, const nct_seq_motion* mp) {
 
 int nct_seq_reset(nct_ctx* ctx) {
     NCT_CTX_ENTER();
-    pair_state* P = (pair_state*)ctx->pair;
-    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_reset: no sequence is open (nct_seq_begin first)");
+    NCT_OPEN_SEQ(P, "seq_reset");
     P->seq->frames = 0; P->seq->gap = 0; P->seq->acc = 0;
     return NCT_OK;
-}
-
-// the sequence's matte blocks go back to the arena (the caller has waited for the stream)
-static void seq_mask_drop(nct_ctx* ctx, pair_state* P, seq_state* q) {
-    if (P->mask) { ctx->release(P->mask); P->mask = nullptr; }
-    if (P->full_mask) { ctx->release(P->full_mask); P->full_mask = nullptr; }
-    if (q->matte_alt) { ctx->release(q->matte_alt); q->matte_alt = nullptr; }
-    q->full.mask = nullptr; P->protect = 0; q->matte_fresh = false; q->matte_age = 0;
 }
 
 // the mask of nct_seq_set_region onto the device, into blocks the sequence keeps until the mask is removed: at the size it came, and (a full-resolution sequence) shrunk
 static int seq_mask_upload(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* mask, hipMemcpyKind kind) {
     const size_t n = (size_t)P->sh * P->sw;
-    if (!P->mask && !(P->mask = (uint8_t*)ctx->alloc(n))) return NCT_ERR_HIP;
+    if (!P->mask.reserve(ctx, n)) return NCT_ERR_HIP;
     if (q->target()) {
         const size_t n0 = (size_t)q->full.H * q->full.W;
-        if (!P->full_mask && !(P->full_mask = (uint8_t*)ctx->alloc(n0))) return NCT_ERR_HIP;
+        if (!P->full_mask.reserve(ctx, n0)) return NCT_ERR_HIP;
         NCT_HIP(hipMemcpyAsync(P->full_mask, mask, n0, kind, ctx->stream));
         NCT_TRY(nctk_resize_u8c1(ctx, ctx->stream, P->full_mask, q->full.H, q->full.W, P->mask, P->sh, P->sw));
         q->full.mask = P->full_mask;
@@ -212,22 +192,21 @@ static int seq_mask_upload(nct_ctx* ctx, pair_state* P, seq_state* q, const uint
 // kind: where `mask` lives — the caller's memory (nct_seq_set_region) or the device (seq_set_region_dev)
 static int seq_set_region_from(nct_ctx* ctx, const uint8_t* mask, const nct_region_params* region, hipMemcpyKind kind) {
     NCT_CTX_ENTER();
-    pair_state* P = (pair_state*)ctx->pair;
-    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_set_region: no sequence is open (nct_seq_begin first)");
+    NCT_OPEN_SEQ(P, "seq_set_region");
     NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "seq_set_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
     seq_state* q = P->seq;
     // the state stays; what the last frame left is no longer the result of these settings
     P->finished = false;
     if (!mask) {
-        if (P->mask || P->full_mask) NCT_SYNC();
-        seq_mask_drop(ctx, P, q);
+        if (P->mask.ok() || P->full_mask.ok()) NCT_SYNC();
+        seq_mask_drop(P, q);
         return NCT_OK;
     }
     const int rc = seq_mask_upload(ctx, P, q, mask, kind);
     if (rc) {
         // a device error half way: no mask is better than a block of unknown bytes
         (void)hipStreamSynchronize(ctx->stream);
-        seq_mask_drop(ctx, P, q);
+        seq_mask_drop(P, q);
         return rc;
     }
     P->protect = region ? region->protect : 0;
@@ -240,8 +219,7 @@ int nct_seq_set_region(nct_ctx* ctx, const uint8_t* mask, const nct_region_param
 // SPEC §6.14 rule 2: from the next frame on the matte in force follows the motion field (1), or stays where it is as a sticky §6.13 matte (0)
 int nct_seq_set_region_tracking(nct_ctx* ctx, int on) {
     NCT_CTX_ENTER();
-    pair_state* P = (pair_state*)ctx->pair;
-    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_set_region_tracking: no sequence is open (nct_seq_begin first)");
+    NCT_OPEN_SEQ(P, "seq_set_region_tracking");
     NCT_REQUIRE(on == 0 || on == 1, "seq_set_region_tracking: on must be 0 or 1 (got %d)", on);
     P->seq->tracking = on == 1;
     return NCT_OK;
@@ -250,8 +228,7 @@ int nct_seq_set_region_tracking(nct_ctx* ctx, int on) {
 // SPEC §6.15 rule 3: from the next frame on a tracked matte is snapped to its frame's edges behind the carry (non-null: with these parameters), or not (null)
 int nct_seq_set_region_snap(nct_ctx* ctx, const nct_region_snap_params* params) {
     NCT_CTX_ENTER();
-    pair_state* P = (pair_state*)ctx->pair;
-    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_set_region_snap: no sequence is open (nct_seq_begin first)");
+    NCT_OPEN_SEQ(P, "seq_set_region_snap");
     NCT_TRY(nct_region_snap_params_check(ctx, "seq_set_region_snap", params));
     P->seq->snap = params != nullptr;
     if (params) P->seq->snap_p = *params;
@@ -261,8 +238,7 @@ int nct_seq_set_region_snap(nct_ctx* ctx, const nct_region_snap_params* params) 
 // the matte in force at the size frames arrive, and how many frames it has been carried or kept since its own
 int nct_seq_get_region(nct_ctx* ctx, uint8_t* mask_out, int* age) {
     NCT_CTX_ENTER();
-    pair_state* P = (pair_state*)ctx->pair;
-    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_get_region: no sequence is open (nct_seq_begin first)");
+    NCT_OPEN_SEQ(P, "seq_get_region");
     if (!P->mask) return ctx->fail(NCT_ERR_STATE, "seq_get_region: no region mask is set (nct_seq_set_region first)");
     NCT_REQUIRE(mask_out, "seq_get_region: null mask_out");
     const seq_state* q = P->seq;
@@ -274,26 +250,22 @@ int nct_seq_get_region(nct_ctx* ctx, uint8_t* mask_out, int* age) {
 }
 
 // what the sequence holds of reference k's mask goes back to the arena, and with the last mask the kept pull (the caller has waited for the stream)
-static void seq_ref_mask_drop(nct_ctx* ctx, pair_state* P, seq_state* q, int k) {
-    if (P->rmask[k]) { ctx->release(P->rmask[k]); P->rmask[k] = nullptr; }
-    for (int l = 0; l < 4; ++l) if (q->rq[k][l]) { ctx->release(q->rq[k][l]); q->rq[k][l] = nullptr; }
+static void seq_ref_mask_drop(pair_state* P, seq_state* q, int k) {
+    P->rmask[k].reset();
+    for (int l = 0; l < 4; ++l) q->rq[k][l].reset();
     if (P->ref_masked()) return;
-    for (int l = 0; l < 5; ++l) {
-        if (q->keep_pull[l]) { ctx->release(q->keep_pull[l]); q->keep_pull[l] = nullptr; }
-        if (q->pull_alt[l]) { ctx->release(q->pull_alt[l]); q->pull_alt[l] = nullptr; }
-    }
+    for (int l = 0; l < 5; ++l) { q->keep_pull[l].reset(); q->pull_alt[l].reset(); }
 }
 
 // reference k's mask onto the device at the reference's working size (a full-resolution sequence: uploaded as it came and shrunk there, as its image was), its level
 // masks by SPEC §6.12 rule 1 on the reference's level grids, and — with the first mask — the two maps per level run of the kept pull
 static int seq_ref_mask_upload(nct_ctx* ctx, pair_state* P, seq_state* q, int k, const uint8_t* mask) {
     const hipStream_t s = ctx->stream;
-    if (!P->rmask[k] && !(P->rmask[k] = (uint8_t*)ctx->alloc((size_t)P->rh[k] * P->rw[k]))) return NCT_ERR_HIP;
-    for (int l = 0; l < 4; ++l) if (!q->rq[k][l] && !(q->rq[k][l] = (uint8_t*)ctx->alloc((size_t)q->bh[k][l] * q->bw[k][l]))) return NCT_ERR_HIP;
+    if (!P->rmask[k].reserve(ctx, (size_t)P->rh[k] * P->rw[k])) return NCT_ERR_HIP;
+    for (int l = 0; l < 4; ++l) if (!q->rq[k][l].reserve(ctx, (size_t)q->bh[k][l] * q->bw[k][l])) return NCT_ERR_HIP;
     for (int l = 0; l < q->prm.levels; ++l) {
         const size_t n = (size_t)q->ah[l] * q->aw[l];
-        if (!q->keep_pull[l] && !(q->keep_pull[l] = (uint8_t*)ctx->alloc(n))) return NCT_ERR_HIP;
-        if (!q->pull_alt[l] && !(q->pull_alt[l] = (uint8_t*)ctx->alloc(n))) return NCT_ERR_HIP;
+        if (!q->keep_pull[l].reserve(ctx, n) || !q->pull_alt[l].reserve(ctx, n)) return NCT_ERR_HIP;
     }
     if (q->rh0[k] == P->rh[k] && q->rw0[k] == P->rw[k]) NCT_H2D(P->rmask[k], mask, (size_t)P->rh[k] * P->rw[k]);
     else {
@@ -315,8 +287,7 @@ static int seq_ref_mask_upload(nct_ctx* ctx, pair_state* P, seq_state* q, int k,
 // keeps its merged pull as it is, and a propagated frame before that is refused
 int nct_seq_set_ref_region(nct_ctx* ctx, int k, const uint8_t* mask, const nct_region_params* region) {
     NCT_CTX_ENTER();
-    pair_state* P = (pair_state*)ctx->pair;
-    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_set_ref_region: no sequence is open (nct_seq_begin first)");
+    NCT_OPEN_SEQ(P, "seq_set_ref_region");
     NCT_REQUIRE(k >= 0 && k < P->K, "seq_set_ref_region: k = %d is not one of the sequence's %d references", k, P->K);
     NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "seq_set_ref_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
     seq_state* q = P->seq;
@@ -324,14 +295,14 @@ int nct_seq_set_ref_region(nct_ctx* ctx, int k, const uint8_t* mask, const nct_r
     P->finished = false;
     q->pull_kept = false;
     NCT_SYNC();
-    if (P->fin_mask) { ctx->release(P->fin_mask); P->fin_mask = nullptr; }
-    if (!mask) seq_ref_mask_drop(ctx, P, q, k);
+    P->fin_mask.reset();
+    if (!mask) seq_ref_mask_drop(P, q, k);
     else {
         const int rc = seq_ref_mask_upload(ctx, P, q, k, mask);
         if (rc) {
             // a device error half way: no mask is better than a block of unknown bytes
             (void)hipStreamSynchronize(ctx->stream);
-            seq_ref_mask_drop(ctx, P, q, k);
+            seq_ref_mask_drop(P, q, k);
             return rc;
         }
     }
@@ -346,21 +317,20 @@ static int seq_prepare(nct_ctx* ctx, pair_state* P, seq_state* q, int K, const u
     hipStream_t s = ctx->stream;
     level_sizes(sh, sw, q->ah, q->aw);
     for (int k = 0; k < K; ++k) level_sizes(rh[k], rw[k], q->bh[k], q->bw[k]);
-    P->src = (uint8_t*)ctx->alloc((size_t)sh * sw * 3);
-    if (!P->src) return NCT_ERR_HIP;
-    for (int k = 0; k < K; ++k) if (!(P->ref[k] = (uint8_t*)ctx->alloc((size_t)rh[k] * rw[k] * 3))) return NCT_ERR_HIP;
+    if (!P->src.alloc(ctx, (size_t)sh * sw * 3)) return NCT_ERR_HIP;
+    for (int k = 0; k < K; ++k) if (!P->ref[k].alloc(ctx, (size_t)rh[k] * rw[k] * 3)) return NCT_ERR_HIP;
     P->sh = sh; P->sw = sw; P->K = K;
     for (int k = 0; k < K; ++k) { P->rh[k] = rh[k]; P->rw[k] = rw[k]; q->rh0[k] = rh0[k]; q->rw0[k] = rw0[k]; }
     for (int l = 0; l < 5; ++l) {
         const size_t n = (size_t)q->ah[l] * q->aw[l];
         for (int k = 0; k < K; ++k) {
             const size_t nr = (size_t)q->bh[k][l] * q->bw[k][l];
-            if (l < 4 && !(q->rpyr[k][l] = (uint8_t*)ctx->alloc(nr * 3))) return NCT_ERR_HIP;
-            if (!(q->rfeat[k][l] = (float*)ctx->alloc(sizeof(float) * kTapC[4 - l] * nr))) return NCT_ERR_HIP;
+            if (l < 4 && !q->rpyr[k][l].alloc(ctx, nr * 3)) return NCT_ERR_HIP;
+            if (!q->rfeat[k][l].alloc(ctx, kTapC[4 - l] * nr)) return NCT_ERR_HIP;
         }
         if (l < q->prm.levels) {
-            if (!(q->keep_x[l] = (double*)ctx->alloc(sizeof(double) * 6 * n)) || !(q->keep_lab[l] = (uint8_t*)ctx->alloc(n * 3))) return NCT_ERR_HIP;
-            if (K > 1 && !(q->keep_label[l] = (uint8_t*)ctx->alloc(n))) return NCT_ERR_HIP;
+            if (!q->keep_x[l].alloc(ctx, 6 * n) || !q->keep_lab[l].alloc(ctx, n * 3)) return NCT_ERR_HIP;
+            if (K > 1 && !q->keep_label[l].alloc(ctx, n)) return NCT_ERR_HIP;
         }
     }
     for (int k = 0; k < K; ++k) {
@@ -368,8 +338,8 @@ static int seq_prepare(nct_ctx* ctx, pair_state* P, seq_state* q, int K, const u
         else NCT_TRY(upload_shrunk(ctx, refs_bgr[k], rh0[k], rw0[k], P->ref[k], rh[k], rw[k]));
     }
     if (q->target()) {
-        q->full.src = P->full_src = (uint8_t*)ctx->alloc((size_t)q->full.H * q->full.W * 3); q->full.out = P->full_out = (uint8_t*)ctx->alloc((size_t)q->full.H * q->full.W * 3);
-        if (!P->full_src || !P->full_out) return NCT_ERR_HIP;
+        if (!P->full_src.alloc(ctx, (size_t)q->full.H * q->full.W * 3) || !P->full_out.alloc(ctx, (size_t)q->full.H * q->full.W * 3)) return NCT_ERR_HIP;
+        q->full.src = P->full_src; q->full.out = P->full_out;
         P->full_h = q->full.H; P->full_w = q->full.W;
     }
     for (int k = 0; k < K; ++k) {
@@ -399,13 +369,13 @@ static int seq_open(nct_ctx* ctx, const char* who, int K, const uint8_t* const* 
     NCT_REQUIRE(nct_seq_hold_ok(hp.hold), "%s: hold must be finite and in [0, 2] (got %g)", who, hp.hold);
     NCT_TRY(nct_seq_end(ctx));                                   // a sequence that is still open is closed first
     pair_state* P = pair_of(ctx);
-    drop_images(ctx, P);
+    drop_images(P);
     seq_state* q = new seq_state();
     q->prm = *prm; q->tau = sp->tau; q->sigma = sp->sigma; q->hold = hp.hold;
     if (full) q->full = *full;
     P->seq = q;
     const int rc = seq_prepare(ctx, P, q, K, refs_bgr, rh0, rw0, rh, rw, sh, sw);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); seq_free(ctx, P); drop_images(ctx, P); }
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); seq_free(P); drop_images(P); }
     return rc;
 }
 
@@ -484,8 +454,7 @@ static int seq_frame_run(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr,
                          bool as_pair, const nct_seq_levels* seq_levels, const nct_region_levels* region_levels, const nct_seq_hold_levels* hold_levels,
                          const nct_ref_region_levels* ref_region_levels = nullptr, const nct_seq_pull_levels* pull_levels = nullptr) {
     NCT_CTX_ENTER();
-    pair_state* P = (pair_state*)ctx->pair;
-    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_frame: no sequence is open (nct_seq_begin first)");
+    NCT_OPEN_SEQ(P, "seq_frame");
     NCT_REQUIRE(src_bgr && out_bgr, "seq_frame: null image");
     seq_state* q = P->seq;
     NCT_REQUIRE(!(q->target() && as_pair), "seq_frame_levels: levels must be NULL in a full-resolution sequence (its result[] arrays have no single size); seq_levels reports the working-size maps");
@@ -499,7 +468,7 @@ static int seq_frame_run(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr,
     run_extras x; x.fin = q->target(); x.seq = q; x.slv = seq_levels; x.lv = mlv; x.color = color; x.hlv = hold_levels;
     nct_ref_region_levels qlv;
     if (region_levels) { qlv = ref_region_levels_of(*region_levels); x.qlv = &qlv; }
-    if (region_levels && !P->mask && !q->model_rows) x.refusal = "seq_frame: region levels asked for, but no region mask is set (nct_seq_set_region first)";
+    if (region_levels && !P->mask.ok() && !q->model_rows.ok()) x.refusal = "seq_frame: region levels asked for, but no region mask is set (nct_seq_set_region first)";
     if (ref_region_levels) x.qlv = ref_region_levels;
     x.plv = pull_levels;
     if ((ref_region_levels || pull_levels) && !P->ref_masked()) x.refusal = "seq_frame: reference region levels asked for, but no reference mask is set (nct_seq_set_ref_region first)";
@@ -560,7 +529,7 @@ static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out
                          const nct_seq_pull_levels* plv) {
     const hipStream_t s = ctx->stream;
     const bool ref_masked = P->ref_masked();
-    if (P->fin_mask) { ctx->release(P->fin_mask); P->fin_mask = nullptr; }
+    P->fin_mask.reset();
     const nct_params& prm = q->prm;
     const int H = P->sh, W = P->sw, top = prm.levels - 1;
     const size_t N = (size_t)H * W;
@@ -571,8 +540,8 @@ static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out
     const uint8_t* simg[5]; simg[4] = P->src;
     for (int l = 3; l >= 0; --l) NCT_TRY(pyramid_level(ctx, s, spyr[l], simg, q->ah, q->aw, l));
     MARK(NCT_ST_OTHER, 0);
-    if (q->motion && !q->warp_x && !(q->warp_x = (double*)ctx->alloc(sizeof(double) * 6 * (size_t)q->ah[top] * q->aw[top]))) return NCT_ERR_HIP;
-    if (!P->out) { P->out = (uint8_t*)ctx->alloc(N * 3); if (!P->out) return NCT_ERR_HIP; }
+    if (q->motion && !q->warp_x.reserve(ctx, 6 * (size_t)q->ah[top] * q->aw[top])) return NCT_ERR_HIP;
+    if (!P->out.reserve(ctx, N * 3)) return NCT_ERR_HIP;
     for (int l = 0; l <= top; ++l) {
         const int h = q->ah[l], w = q->aw[l];
         const size_t n = (size_t)h * w;
@@ -581,7 +550,7 @@ static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out
             NCT_TRY(seq_motion_level(ctx, s, q, l, q->keep_lab[l]));
             NCT_TRY(nctk_seq_warp(ctx, s, q->keep_x[l], h, w, q->field[l], q->warp_x));
             // the scratch has the last level's size: there the two maps change places, elsewhere the warped map is copied back
-            if (l == top) std::swap(q->keep_x[l], q->warp_x);
+            if (l == top) q->keep_x[l].swap(q->warp_x);
             else NCT_HIP(hipMemcpyAsync(q->keep_x[l], q->warp_x, sizeof(double) * 6 * n, hipMemcpyDeviceToDevice, s));
             NCT_TRY(nctk_seq_pack(ctx, s, q->keep_lab[l], (int)n, q->keep_pk[l]));
             if (q->keep_label[l]) {
@@ -594,7 +563,7 @@ static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out
             if (ref_masked) {
                 // SPEC §6.19: the kept pull follows the field as well — the same byte gather, into the sequence's second map; the two change places
                 NCT_TRY(nctk_label_carry(ctx, s, q->keep_pull[l], h, w, q->field[l], q->pull_alt[l]));
-                std::swap(q->keep_pull[l], q->pull_alt[l]);
+                q->keep_pull[l].swap(q->pull_alt[l]);
             }
         }
         if (ref_masked && plv) NCT_TRY(dbg_copy(ctx, s, plv->p_held[l], q->keep_pull[l], n));
@@ -619,59 +588,26 @@ static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out
     const nct_color_debug dbg{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, wls_it};
     full_lab fl;
     NCT_TRY(fl.open(ctx, s, q->target()));
-    const double* x_fin = q->keep_x[top];
-    DevBuf<uint8_t> mpyr[4]; DevBuf<double> x_mix;
-    const bool exact = q->target() && q->full.finish == NCT_FINISH_EXACT;
-    region_fin rg{exact ? q->full.mask : P->mask, P->src, P->protect};
-    const uint8_t* mimg[5] = {};
-    if (P->mask) {
-        mimg[4] = P->mask;
-        for (int l = 3; l >= top; --l) {
-            if (!mpyr[l].alloc(ctx, (size_t)q->ah[l] * q->aw[l])) return NCT_ERR_HIP;
-            NCT_TRY(nctk_resize_u8c1(ctx, s, mimg[l + 1], q->ah[l + 1], q->aw[l + 1], mpyr[l], q->ah[l], q->aw[l]));
-            mimg[l] = mpyr[l];
-        }
-    }
-    DevBuf<uint8_t> m_top, f_work;
-    full_target up_target;
-    const full_target* target = q->target();
+    const int h = q->ah[top], w = q->aw[top];
+    const nct_color_debug* const d = timing ? &dbg : nullptr;
     if (P->mask || ref_masked) {
-        const int h = q->ah[top], w = q->aw[top];
-        const size_t n = (size_t)h * w;
-        const uint8_t* m_l = mimg[top];
-        if (ref_masked) {
-            const uint8_t* const p_top = q->keep_pull[top];
-            m_l = p_top;
-            if (P->mask) {
-                if (!m_top.alloc(ctx, n)) return NCT_ERR_HIP;
-                NCT_TRY(nctk_region_merge(ctx, s, &p_top, 1, nullptr, mimg[top], (int)n, nullptr, m_top));
-                m_l = m_top;
-            }
-            const bool up = target && !exact;
-            const int fh = exact ? q->full.H : H, fw = exact ? q->full.W : W;
-            uint8_t* f = nullptr;
-            if (up) { if (!f_work.alloc(ctx, N)) return NCT_ERR_HIP; f = f_work; }
-            else { if (!(P->fin_mask = (uint8_t*)ctx->alloc((size_t)fh * fw))) return NCT_ERR_HIP; f = P->fin_mask; }
-            NCT_TRY(nctk_region_upsize_min(ctx, s, p_top, h, w, rg.mask, f, fh, fw));
-            rg.mask = f;
-            if (up) {
-                if (!(P->fin_mask = (uint8_t*)ctx->alloc((size_t)q->full.H * q->full.W))) return NCT_ERR_HIP;
-                NCT_TRY(nctk_region_upsize_min(ctx, s, p_top, h, w, q->full.mask, P->fin_mask, q->full.H, q->full.W));
-                up_target = q->full; up_target.mask = P->fin_mask; target = &up_target;
-            }
-            if (rlv) NCT_TRY(dbg_copy(ctx, s, rlv->mask_full[top], rg.mask, (size_t)fh * fw));
-        }
-        if (!x_mix.alloc(ctx, 6 * n)) return NCT_ERR_HIP;
-        NCT_TRY(nctk_region_mix(ctx, s, q->keep_x[top], m_l, h, w, x_mix));
-        x_fin = x_mix;
+        // only the source's level masks down to the last level run are built; m_top, the F scratch and the mixed map are scratch of this call, requested by the step
+        DevBuf<uint8_t> mpyr[4], m_top, f_work; DevBuf<double> x_mix;
+        const uint8_t* mimg[5] = {};
+        mimg[4] = P->mask;
+        if (P->mask) NCT_TRY(source_mask_levels(ctx, s, mpyr, mimg, q->ah, q->aw, top));
+        masked_fin mf{ref_masked ? (const uint8_t*)q->keep_pull[top] : nullptr, mimg[top], P->mask, P->src, P->protect, true, nullptr};
+        NCT_TRY(finish_level_masked(ctx, s, mf, q->keep_x[top], x_mix, m_top, f_work, P->fin_mask, h, w, H, W, s_lab_full, out_lab, P->out, q->target(), fl, nct_color_params_of(prm), d,
+                                    nct_cube_form(prm)));
+        // the report: the last level run only; with a source mask alone also the level masks that were built
         if (rlv) {
+            const size_t n = (size_t)h * w;
+            if (ref_masked) NCT_TRY(dbg_copy(ctx, s, rlv->mask_full[top], mf.f_l, (size_t)mf.fh * mf.fw));
             NCT_TRY(dbg_copy(ctx, s, rlv->ab_mix[top], (double*)x_mix, 6 * n));
-            if (ref_masked) NCT_TRY(dbg_copy(ctx, s, rlv->mask[top], m_l, n));
+            if (ref_masked) NCT_TRY(dbg_copy(ctx, s, rlv->mask[top], mf.m_l, n));
             else for (int l = top; l < 5; ++l) NCT_TRY(dbg_copy(ctx, s, rlv->mask[l], mimg[l], (size_t)q->ah[l] * q->aw[l]));
         }
-    }
-    NCT_TRY(finish_level(ctx, s, x_fin, q->ah[top], q->aw[top], H, W, s_lab_full, out_lab, P->out, target, fl, nct_color_params_of(prm), timing ? &dbg : nullptr, nct_cube_form(prm),
-                         P->mask || ref_masked ? &rg : nullptr));
+    } else NCT_TRY(finish_level(ctx, s, q->keep_x[top], h, w, H, W, s_lab_full, out_lab, P->out, q->target(), fl, nct_color_params_of(prm), d, nct_cube_form(prm)));
     if (timing) timing->wls_iters[top] = *std::max_element(wls_it, wls_it + 6);
     MARK(NCT_ST_COLOR, top);
     if (q->target()) NCT_D2H(out_bgr, P->full_out, (size_t)q->full.H * q->full.W * 3);
@@ -688,8 +624,7 @@ int nct_seq_frame_propagate_levels(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t
 static int seq_propagate_form(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr, nct_pair_timing* timing, const nct_seq_levels* seq_levels, const nct_region_levels* region_levels,
                               const nct_ref_region_levels* ref_region_levels, const nct_seq_pull_levels* pull_levels) {
     NCT_CTX_ENTER();
-    pair_state* P = (pair_state*)ctx->pair;
-    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "seq_frame_propagate: no sequence is open (nct_seq_begin first)");
+    NCT_OPEN_SEQ(P, "seq_frame_propagate");
     seq_state* q = P->seq;
     if (q->frames == 0) return ctx->fail(NCT_ERR_STATE, "seq_frame_propagate: the sequence has no state to propagate (the first frame after nct_seq_begin / nct_seq_reset is nct_seq_frame's)");
     NCT_REQUIRE(src_bgr && out_bgr, "seq_frame_propagate: null image");
@@ -771,8 +706,7 @@ static int probe_run(nct_ctx* ctx, pair_state* P, seq_state* q, const uint8_t* s
 
 // the checks of nct_seq_probe / nct_seq_frame_auto, then the probe and the decision; first_ok: a sequence without state is NCT_SEQ_FIRST, not an error
 static int seq_probe_decide(nct_ctx* ctx, const char* who, const uint8_t* src_bgr, const nct_seq_auto* a, bool first_ok, nct_seq_auto* used, nct_seq_decision* d) {
-    pair_state* P = (pair_state*)ctx->pair;
-    if (!P || !P->seq) return ctx->fail(NCT_ERR_STATE, "%s: no sequence is open (nct_seq_begin first)", who);
+    NCT_OPEN_SEQ(P, who);
     seq_state* q = P->seq;
     if (q->frames == 0 && !first_ok)
         return ctx->fail(NCT_ERR_STATE, "%s: the sequence has no state to compare with (the first frame after nct_seq_begin / nct_seq_reset is nct_seq_frame's)", who);
