@@ -1,5 +1,5 @@
 // nct_api.cpp — C-ABI entry points (host-pointer variants) + context / arena management.
-// Every function here is a thin marshalling layer: upload, call the device launcher (nctk_*), download.
+// Every entry point here is a thin marshalling layer: upload, call the device launcher (nctk_*), download — the traffic and the blocks through one HostCall (nct_internal.h).
 #include <atomic>
 #include "nct_internal.h"
 #include <chrono>
@@ -75,6 +75,19 @@ int nct_ctx::kt_end(hipStream_t s) {
 void nct_ctx::release(void* p) {
     if (defer_release) { deferred.push_back(p); return; }
     for (auto& b : blocks) if (b.p == p) { b.used = false; return; }
+}
+
+int nct_seq_blend_check(nct_ctx* ctx, const void* x, const void* x_prev, const void* lab, const void* lab_prev, int h, int w, const void* x_out, const void* field) {
+    NCT_REQUIRE(x && x_prev && lab && lab_prev && x_out, "seq_blend: null pointer");
+    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_blend: grid %dx%d out of range", w, h);
+    NCT_REQUIRE(!field || x_out != x_prev, "seq_blend: with a motion field x_out must not alias x_prev");
+    return NCT_OK;
+}
+int nct_seq_motion_field_check(nct_ctx* ctx, const char* who, const void* lab, const void* lab_prev, int h, int w, const void* parent, int ph, int pw, const void* m_out) {
+    NCT_REQUIRE(lab && lab_prev && m_out, "%s: null pointer", who);
+    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "%s: grid %dx%d out of range", who, w, h);
+    NCT_REQUIRE(!parent || (ph >= 1 && pw >= 1 && ph <= 4096 && pw <= 4096), "%s: parent grid %dx%d out of range", who, pw, ph);
+    return NCT_OK;
 }
 
 extern "C" {
@@ -194,9 +207,13 @@ int nct_synchronize(nct_ctx* ctx) {
 }
 
 
-// upload a CHW host tensor and return it in HWC device layout
-static int upload_hwc(nct_ctx* ctx, const float* chw, float* d_tmp, float* d_hwc, int C, int HW) {
-    NCT_H2D(d_tmp, chw, sizeof(float) * (size_t)C * HW);
+// The host-pointer entry points below, and those of nct_color.cpp, nct_lut.cpp, nct_region_select.cpp, nct_region_model.cpp and nct_vgg.cpp, have one shape: the argument
+// checks; one HostCall line per array (in / out / inout / scratch, in the order the blocks are requested); NCT_TRY(hc.ready()) and the launchers; return hc.finish().
+
+// a CHW host tensor through the staging block d_tmp (which several tensors of a call share) into HWC device layout
+static int upload_hwc(nct_ctx* ctx, HostCall& hc, const float* chw, float* d_tmp, float* d_hwc, int C, int HW) {
+    hc.put(d_tmp, chw, (size_t)C * HW);
+    NCT_TRY(hc.ready());
     return nctk_chw_to_hwc(ctx, ctx->stream, d_tmp, d_hwc, C, HW);
 }
 
@@ -204,40 +221,37 @@ int nct_feat_normalize(nct_ctx* ctx, const float* src_chw, float* dst_chw, float
     NCT_CTX_ENTER();
     NCT_REQUIRE(src_chw && dst_chw && H > 0 && W > 0, "feat_normalize: null pointer or empty image");
     const int HW = H * W; const size_t n = (size_t)C * HW;
-    DevBuf<float> t(ctx, n), x(ctx, n), y(ctx, n), r(ctx, HW);
-    if (!t.ok() || !x.ok() || !y.ok() || !r.ok()) return NCT_ERR_HIP;
-    NCT_TRY(upload_hwc(ctx, src_chw, t, x, C, HW));
-    NCT_TRY(nctk_normalize(ctx, ctx->stream, x, y, resp ? (float*)r : nullptr, C, HW));
+    HostCall hc(ctx);
+    float* t = hc.inout(src_chw, dst_chw, n);                  // Caffe's layout on the way in and on the way out
+    float *x = hc.scratch<float>(n), *y = hc.scratch<float>(n), *r = hc.out(resp, HW);
+    NCT_TRY(hc.ready());
+    NCT_TRY(nctk_chw_to_hwc(ctx, ctx->stream, t, x, C, HW));
+    NCT_TRY(nctk_normalize(ctx, ctx->stream, x, y, r, C, HW));
     NCT_TRY(nctk_hwc_to_chw(ctx, ctx->stream, y, t, C, HW));
-    NCT_D2H(dst_chw, t, sizeof(float) * n);
-    if (resp) NCT_D2H(resp, r, sizeof(float) * HW);
-    NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 int nct_nnf_init(nct_ctx* ctx, uint32_t* nnf, int ah, int aw, int bh, int bw) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(nnf, "nnf_init: null pointer");
     NCT_REQUIRE(ah > 0 && aw > 0, "nnf_init: empty query image");
-    DevBuf<uint32_t> d(ctx, (size_t)ah * aw);
-    if (!d.ok()) return NCT_ERR_HIP;
+    HostCall hc(ctx);
+    uint32_t* d = hc.out(nnf, (size_t)ah * aw);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_nnf_init(ctx, ctx->stream, d, ah, aw, bh, bw));
-    NCT_D2H(nnf, d, sizeof(uint32_t) * (size_t)ah * aw);
-    NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 int nct_nnf_upsample(nct_ctx* ctx, const uint32_t* nnf_half, uint32_t* nnf, int ah, int aw, int bh, int bw, int ah_half, int aw_half) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(nnf_half && nnf, "nnf_upsample: null pointer");
     NCT_REQUIRE(ah > 0 && aw > 0 && ah_half > 0 && aw_half > 0, "nnf_upsample: empty image");
-    DevBuf<uint32_t> h(ctx, (size_t)ah_half * aw_half), d(ctx, (size_t)ah * aw);
-    if (!h.ok() || !d.ok()) return NCT_ERR_HIP;
-    NCT_H2D(h, nnf_half, sizeof(uint32_t) * (size_t)ah_half * aw_half);
+    HostCall hc(ctx);
+    const uint32_t* h = hc.in(nnf_half, (size_t)ah_half * aw_half);
+    uint32_t* d = hc.out(nnf, (size_t)ah * aw);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_nnf_upsample(ctx, ctx->stream, h, d, ah, aw, bh, bw, ah_half, aw_half));
-    NCT_D2H(nnf, d, sizeof(uint32_t) * (size_t)ah * aw);
-    NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 int nct_patchmatch(nct_ctx* ctx, const float* a_chw, const float* b_chw, int C, int ah, int aw, int bh, int bw,
@@ -247,17 +261,14 @@ int nct_patchmatch(nct_ctx* ctx, const float* a_chw, const float* b_chw, int C, 
     NCT_REQUIRE(patch == 3, "patchmatch: only patch=3 is supported (Config.h:70), got %d", patch);
     NCT_REQUIRE(ah > 0 && aw > 0 && bh > 0 && bw > 0, "patchmatch: empty image");
     const size_t na = (size_t)ah * aw, nb = (size_t)bh * bw;
-    DevBuf<float> t(ctx, (size_t)C * (na > nb ? na : nb)), A(ctx, C * na), B(ctx, C * nb), d(ctx, na);
-    DevBuf<uint32_t> n(ctx, na);
-    if (!t.ok() || !A.ok() || !B.ok() || !d.ok() || !n.ok()) return NCT_ERR_HIP;
-    NCT_TRY(upload_hwc(ctx, a_chw, t, A, C, (int)na));
-    NCT_TRY(upload_hwc(ctx, b_chw, t, B, C, (int)nb));
-    NCT_H2D(n, nnf, sizeof(uint32_t) * na);
+    HostCall hc(ctx);
+    float *t = hc.scratch<float>((size_t)C * (na > nb ? na : nb)), *A = hc.scratch<float>(C * na), *B = hc.scratch<float>(C * nb), *d = hc.out(dist, na);
+    uint32_t* n = hc.inout(nnf, nnf, na);
+    NCT_TRY(hc.ready());
+    NCT_TRY(upload_hwc(ctx, hc, a_chw, t, A, C, (int)na));
+    NCT_TRY(upload_hwc(ctx, hc, b_chw, t, B, C, (int)nb));
     NCT_TRY(nctk_patchmatch(ctx, ctx->stream, A, B, C, ah, aw, bh, bw, iters, rs_max, seed, n, d, nullptr));
-    NCT_D2H(nnf, n, sizeof(uint32_t) * na);
-    NCT_D2H(dist, d, sizeof(float) * na);
-    NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 int nct_bds_vote_features(nct_ctx* ctx, const uint32_t* ann, const uint32_t* bnn, const float* pin_chw, float* pout_chw, float* pw,
@@ -269,32 +280,44 @@ int nct_bds_vote_features(nct_ctx* ctx, const uint32_t* ann, const uint32_t* bnn
     NCT_REQUIRE(C > 0 && (C & 3) == 0 && C <= 512, "bds_vote_features: C=%d must be a multiple of 4 and <= 512", C);      // nctk_bds_vote_features' own refusals, in front of the reservations
     NCT_REQUIRE(nct_nnf_dims_ok(ah, aw, bh, bw), "bds_vote_features: dims out of range (%dx%d vs %dx%d); NNF coordinates are 12-bit", ah, aw, bh, bw);
     const size_t na = (size_t)ah * aw, nb = (size_t)bh * bw;
-    DevBuf<float> t(ctx, (size_t)C * (na > nb ? na : nb)), P(ctx, C * nb), O(ctx, C * na), w(ctx, na);
-    DevBuf<uint32_t> da(ctx, na), db(ctx, nb);
-    if (!t.ok() || !P.ok() || !O.ok() || !w.ok() || !da.ok() || !db.ok()) return NCT_ERR_HIP;
-    NCT_TRY(upload_hwc(ctx, pin_chw, t, P, C, (int)nb));
-    NCT_H2D(da, ann, sizeof(uint32_t) * na);
-    NCT_H2D(db, bnn, sizeof(uint32_t) * nb);
+    HostCall hc(ctx);
+    float *t = hc.scratch<float>((size_t)C * (na > nb ? na : nb)), *P = hc.scratch<float>(C * nb), *O = hc.scratch<float>(C * na), *w = hc.out(pw, na);
+    const uint32_t *da = hc.in(ann, na), *db = hc.in(bnn, nb);
+    NCT_TRY(hc.ready());
+    NCT_TRY(upload_hwc(ctx, hc, pin_chw, t, P, C, (int)nb));
     NCT_TRY(nctk_bds_vote_features(ctx, ctx->stream, da, db, P, O, w, C, ah, aw, bh, bw, w_coherence, w_complete));
     NCT_TRY(nctk_hwc_to_chw(ctx, ctx->stream, O, t, C, (int)na));
-    NCT_D2H(pout_chw, t, sizeof(float) * C * na);
-    if (pw) NCT_D2H(pw, w, sizeof(float) * na);
-    NCT_SYNC();
-    return NCT_OK;
+    hc.get(pout_chw, t, C * na);
+    return hc.finish();
 }
 
 int nct_feature_distance(nct_ctx* ctx, const float* a_chw, const float* b_chw, float* err, int C, int H, int W) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(a_chw && b_chw && err && H > 0 && W > 0, "feature_distance: null pointer or empty image");
     const size_t n = (size_t)H * W;
-    DevBuf<float> t(ctx, C * n), A(ctx, C * n), B(ctx, C * n), e(ctx, n);
-    if (!t.ok() || !A.ok() || !B.ok() || !e.ok()) return NCT_ERR_HIP;
-    NCT_TRY(upload_hwc(ctx, a_chw, t, A, C, (int)n));
-    NCT_TRY(upload_hwc(ctx, b_chw, t, B, C, (int)n));
+    HostCall hc(ctx);
+    float *t = hc.scratch<float>(C * n), *A = hc.scratch<float>(C * n), *B = hc.scratch<float>(C * n), *e = hc.out(err, n);
+    NCT_TRY(hc.ready());
+    NCT_TRY(upload_hwc(ctx, hc, a_chw, t, A, C, (int)n));
+    NCT_TRY(upload_hwc(ctx, hc, b_chw, t, B, C, (int)n));
     NCT_TRY(nctk_feature_distance(ctx, ctx->stream, A, B, e, C, (int)n));
-    NCT_D2H(err, e, sizeof(float) * n);
-    NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
+}
+
+// What the two selections stage alike: the K error maps and — only where a merged guide is asked for — the K guidance images up, each list in one block, and the blocks
+// of the outputs that were asked for. d.err / d.guide: the lists the launcher takes
+struct select_blocks { const float* err[NCT_MAX_REFS]; const uint8_t* guide[NCT_MAX_REFS]; float* err_out; uint8_t *guide_out, *label; };
+static void select_stage(HostCall& hc, const float* const* err, const uint8_t* const* guide_bgr, int K, size_t n, uint8_t* label, uint8_t* guide_out, float* err_out, select_blocks& d) {
+    float* e = hc.scratch<float>(n * K);
+    d.err_out = hc.out(err_out, n);
+    uint8_t* g = guide_out ? hc.scratch<uint8_t>(n * 3 * K) : nullptr;
+    d.guide_out = hc.out(guide_out, n * 3); d.label = hc.out(label, n);
+    if (hc.ready() != NCT_OK) return;
+    for (int k = 0; k < K; ++k) {
+        d.err[k] = e + n * k; d.guide[k] = g ? g + n * 3 * k : nullptr;
+        hc.put(e + n * k, err[k], n);
+        if (g) hc.put(g + n * 3 * k, guide_bgr[k], n * 3);
+    }
 }
 
 // SPEC §6.2 rules 2-3 on host maps: K error maps and guidance images up, one k_select_reference launch, label / merged guidance / merged error down
@@ -304,22 +327,12 @@ int nct_select_reference(nct_ctx* ctx, const float* const* err, const uint8_t* c
     NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "select_reference: grid %dx%d out of range", w, h);
     NCT_REQUIRE(err && (guide_bgr || !guide_out), "select_reference: null map list");
     for (int k = 0; k < K; ++k) NCT_REQUIRE(err[k] && (!guide_out || guide_bgr[k]), "select_reference: null map of reference %d", k);
-    const size_t n = (size_t)h * w;
-    DevBuf<float> e(ctx, n * K), eo(ctx, n);
-    DevBuf<uint8_t> g(ctx, guide_out ? n * 3 * K : 16), go(ctx, n * 3), lab(ctx, n);
-    if (!e.ok() || !eo.ok() || !g.ok() || !go.ok() || !lab.ok()) return NCT_ERR_HIP;
-    const float* de[NCT_MAX_REFS]; const uint8_t* dg[NCT_MAX_REFS];
-    for (int k = 0; k < K; ++k) {
-        de[k] = e + n * k; dg[k] = guide_out ? g + n * 3 * k : nullptr;
-        NCT_H2D(e + n * k, err[k], sizeof(float) * n);
-        if (guide_out) NCT_H2D(g + n * 3 * k, guide_bgr[k], n * 3);
-    }
-    NCT_TRY(nctk_select_reference(ctx, ctx->stream, de, guide_out ? dg : nullptr, K, h, w, lab, guide_out ? (uint8_t*)go : nullptr, eo));
-    if (label) NCT_D2H(label, lab, n);
-    if (guide_out) NCT_D2H(guide_out, go, n * 3);
-    if (err_out) NCT_D2H(err_out, eo, sizeof(float) * n);
-    NCT_SYNC();
-    return NCT_OK;
+    HostCall hc(ctx);
+    select_blocks d;
+    select_stage(hc, err, guide_bgr, K, (size_t)h * w, label, guide_out, err_out, d);
+    NCT_TRY(hc.ready());
+    NCT_TRY(nctk_select_reference(ctx, ctx->stream, d.err, guide_out ? d.guide : nullptr, K, h, w, d.label, d.guide_out, d.err_out));
+    return hc.finish();
 }
 
 // SPEC §6.18 rules 1-6 on host maps: the K error maps and guidance images, the kept labels, the two Lab level images and the field up, one k_select_hold launch, the
@@ -330,28 +343,17 @@ int nct_select_reference_hold(nct_ctx* ctx, const float* const* err, const uint8
     NCT_CTX_ENTER();
     NCT_TRY(nct_select_hold_check(ctx, "select_reference_hold", (const void* const*)err, (const void* const*)guide_bgr, K, h, w, prev_label, lab, lab_prev, hold, sigma, guide_out));
     const size_t n = (size_t)h * w;
-    DevBuf<float> e(ctx, n * K), eo(ctx, n);
-    DevBuf<uint8_t> g(ctx, guide_out ? n * 3 * K : 16), go(ctx, n * 3), lbl(ctx, n), prev(ctx, n), fr(ctx, n), l1(ctx, n * 3), l0(ctx, n * 3);
-    DevBuf<int16_t> fld(ctx, field ? n * 2 : 8);
-    DevBuf<double> mg(ctx, n);
-    if (!e.ok() || !eo.ok() || !g.ok() || !go.ok() || !lbl.ok() || !prev.ok() || !fr.ok() || !l1.ok() || !l0.ok() || !fld.ok() || !mg.ok()) return NCT_ERR_HIP;
-    const float* de[NCT_MAX_REFS]; const uint8_t* dg[NCT_MAX_REFS];
-    for (int k = 0; k < K; ++k) {
-        de[k] = e + n * k; dg[k] = guide_out ? g + n * 3 * k : nullptr;
-        NCT_H2D(e + n * k, err[k], sizeof(float) * n);
-        if (guide_out) NCT_H2D(g + n * 3 * k, guide_bgr[k], n * 3);
-    }
-    NCT_H2D(prev, prev_label, n); NCT_H2D(l1, lab, n * 3); NCT_H2D(l0, lab_prev, n * 3);
-    if (field) NCT_H2D(fld, field, sizeof(int16_t) * 2 * n);
-    NCT_TRY(nctk_select_hold(ctx, ctx->stream, de, guide_out ? dg : nullptr, K, h, w, prev, l1, l0, field ? (const int16_t*)fld : nullptr, hold, sigma, lbl,
-                             guide_out ? (uint8_t*)go : nullptr, eo, free_label ? (uint8_t*)fr : nullptr, margin ? (double*)mg : nullptr));
-    if (label) NCT_D2H(label, lbl, n);
-    if (guide_out) NCT_D2H(guide_out, go, n * 3);
-    if (err_out) NCT_D2H(err_out, eo, sizeof(float) * n);
-    if (free_label) NCT_D2H(free_label, fr, n);
-    if (margin) NCT_D2H(margin, mg, sizeof(double) * n);
-    NCT_SYNC();
-    return NCT_OK;
+    HostCall hc(ctx);
+    select_blocks d;
+    select_stage(hc, err, guide_bgr, K, n, label, guide_out, err_out, d);
+    const uint8_t* prev = hc.in(prev_label, n);
+    uint8_t* fr = hc.out(free_label, n);
+    const uint8_t *l1 = hc.in(lab, n * 3), *l0 = hc.in(lab_prev, n * 3);
+    const int16_t* fld = hc.in(field, 2 * n);
+    double* mg = hc.out(margin, n);
+    NCT_TRY(hc.ready());
+    NCT_TRY(nctk_select_hold(ctx, ctx->stream, d.err, guide_out ? d.guide : nullptr, K, h, w, prev, l1, l0, fld, hold, sigma, d.label, d.guide_out, d.err_out, fr, mg));
+    return hc.finish();
 }
 
 // SPEC §6.19 rules 2-4 on host maps: the pulled masks, the label map, the kept map, the two Lab level images, the field and the source mask up, one k_seq_pull_hold
@@ -361,86 +363,57 @@ int nct_seq_pull_hold(nct_ctx* ctx, const uint8_t* const* pulled, int K, const u
     NCT_CTX_ENTER();
     NCT_TRY(nct_seq_pull_hold_check(ctx, "seq_pull_hold", (const void* const*)pulled, K, label, prev, lab, lab_prev, h, w, tau, sigma, p_out));
     const size_t n = (size_t)h * w;
-    DevBuf<uint8_t> pk(ctx, n * K), lbl(ctx, n), pv(ctx, n), l1(ctx, n * 3), l0(ctx, n * 3), ms(ctx, n), po(ctx, n), mo(ctx, n), pf(ctx, n);
-    DevBuf<int16_t> fld(ctx, field ? n * 2 : 8);
-    if (!pk.ok() || !lbl.ok() || !pv.ok() || !l1.ok() || !l0.ok() || !ms.ok() || !po.ok() || !mo.ok() || !pf.ok() || !fld.ok()) return NCT_ERR_HIP;
+    HostCall hc(ctx);
+    uint8_t* pk = hc.scratch<uint8_t>(n * K);                  // the K pulled masks in one block; a null one leaves its part unused
+    const uint8_t *lbl = hc.in(label, n), *pv = hc.in(prev, n), *l1 = hc.in(lab, n * 3), *l0 = hc.in(lab_prev, n * 3), *ms = hc.in(src_mask, n);
+    uint8_t *po = hc.out(p_out, n), *mo = hc.out(m_out, n), *pf = hc.out(p_free, n);
+    const int16_t* fld = hc.in(field, 2 * n);
+    NCT_TRY(hc.ready());
     const uint8_t* dp[NCT_MAX_REFS];
     for (int k = 0; k < K; ++k) {
         dp[k] = pulled[k] ? pk + n * k : nullptr;
-        if (pulled[k]) NCT_H2D(pk + n * k, pulled[k], n);
+        hc.put(pk + n * k, pulled[k], n);
     }
-    if (label) NCT_H2D(lbl, label, n);
-    NCT_H2D(pv, prev, n); NCT_H2D(l1, lab, n * 3); NCT_H2D(l0, lab_prev, n * 3);
-    if (field) NCT_H2D(fld, field, sizeof(int16_t) * 2 * n);
-    if (src_mask) NCT_H2D(ms, src_mask, n);
-    NCT_TRY(nctk_seq_pull_hold(ctx, ctx->stream, dp, K, label ? (const uint8_t*)lbl : nullptr, pv, l1, l0, field ? (const int16_t*)fld : nullptr,
-                               src_mask ? (const uint8_t*)ms : nullptr, h, w, tau, sigma, po, m_out ? (uint8_t*)mo : nullptr, p_free ? (uint8_t*)pf : nullptr));
-    NCT_D2H(p_out, po, n);
-    if (m_out) NCT_D2H(m_out, mo, n);
-    if (p_free) NCT_D2H(p_free, pf, n);
-    NCT_SYNC();
-    return NCT_OK;
+    NCT_TRY(nctk_seq_pull_hold(ctx, ctx->stream, dp, K, lbl, pv, l1, l0, fld, ms, h, w, tau, sigma, po, mo, pf));
+    return hc.finish();
 }
 
 // SPEC §6.3 rule 3 on host maps: the two coefficient maps and the two Lab level images up, one k_seq_blend launch, X' (and the tau_p map) down
 int nct_seq_blend(nct_ctx* ctx, const double* x, const double* x_prev, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, double tau, double sigma,
                   double* x_out, double* tau_map) {
-    NCT_CTX_ENTER();
-    NCT_REQUIRE(x && x_prev && lab && lab_prev && x_out, "seq_blend: null pointer");
-    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_blend: grid %dx%d out of range", w, h);
-    const size_t n = (size_t)h * w;
-    DevBuf<double> dx(ctx, 6 * n), dp(ctx, 6 * n), dt(ctx, n);
-    DevBuf<uint8_t> dl(ctx, 3 * n), dlp(ctx, 3 * n);
-    if (!dx.ok() || !dp.ok() || !dt.ok() || !dl.ok() || !dlp.ok()) return NCT_ERR_HIP;
-    NCT_H2D(dx, x, sizeof(double) * 6 * n); NCT_H2D(dp, x_prev, sizeof(double) * 6 * n);
-    NCT_H2D(dl, lab, 3 * n); NCT_H2D(dlp, lab_prev, 3 * n);
-    NCT_TRY(nctk_seq_blend(ctx, ctx->stream, dx, dp, dl, dlp, h, w, tau, sigma, dp, tau_map ? (double*)dt : nullptr));      // in place into the previous state, as a frame does it
-    NCT_D2H(x_out, dp, sizeof(double) * 6 * n);
-    if (tau_map) NCT_D2H(tau_map, dt, sizeof(double) * n);
-    NCT_SYNC();
-    return NCT_OK;
+    return nct_seq_blend_mc(ctx, x, x_prev, lab, lab_prev, h, w, tau, sigma, x_out, tau_map, nullptr);
 }
 
-// SPEC §6.4 rule 4 on host maps; without a field it is nct_seq_blend
+// SPEC §6.4 rule 4 on host maps; without a field it is SPEC §6.3 rule 3. The two blend where a frame does: without a field in place into the previous state's copy,
+// with one into S1's own map
 int nct_seq_blend_mc(nct_ctx* ctx, const double* x, const double* x_prev, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, double tau, double sigma,
                      double* x_out, double* tau_map, const int16_t* field) {
-    if (!field) return nct_seq_blend(ctx, x, x_prev, lab, lab_prev, h, w, tau, sigma, x_out, tau_map);
     NCT_CTX_ENTER();
-    NCT_REQUIRE(x && x_prev && lab && lab_prev && x_out, "seq_blend: null pointer");
-    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_blend: grid %dx%d out of range", w, h);
-    NCT_REQUIRE(x_out != x_prev, "seq_blend: with a motion field x_out must not alias x_prev");
+    NCT_TRY(nct_seq_blend_check(ctx, x, x_prev, lab, lab_prev, h, w, x_out, field));
     const size_t n = (size_t)h * w;
-    DevBuf<double> dx(ctx, 6 * n), dp(ctx, 6 * n), dt(ctx, n);
-    DevBuf<uint8_t> dl(ctx, 3 * n), dlp(ctx, 3 * n);
-    DevBuf<int16_t> df(ctx, 2 * n);
-    if (!dx.ok() || !dp.ok() || !dt.ok() || !dl.ok() || !dlp.ok() || !df.ok()) return NCT_ERR_HIP;
-    NCT_H2D(dx, x, sizeof(double) * 6 * n); NCT_H2D(dp, x_prev, sizeof(double) * 6 * n);
-    NCT_H2D(dl, lab, 3 * n); NCT_H2D(dlp, lab_prev, 3 * n); NCT_H2D(df, field, sizeof(int16_t) * 2 * n);
-    NCT_TRY(nctk_seq_blend(ctx, ctx->stream, dx, dp, dl, dlp, h, w, tau, sigma, dx, tau_map ? (double*)dt : nullptr, df));   // into S1's own map, as a frame does it
-    NCT_D2H(x_out, dx, sizeof(double) * 6 * n);
-    if (tau_map) NCT_D2H(tau_map, dt, sizeof(double) * n);
-    NCT_SYNC();
-    return NCT_OK;
+    HostCall hc(ctx);
+    double *dx = hc.inout(x, field ? x_out : nullptr, 6 * n), *dp = hc.inout(x_prev, field ? nullptr : x_out, 6 * n), *dt = hc.out(tau_map, n);
+    const uint8_t *dl = hc.in(lab, 3 * n), *dlp = hc.in(lab_prev, 3 * n);
+    const int16_t* df = hc.in(field, 2 * n);
+    NCT_TRY(hc.ready());
+    NCT_TRY(nctk_seq_blend(ctx, ctx->stream, dx, dp, dl, dlp, h, w, tau, sigma, field ? dx : dp, dt, df));
+    return hc.finish();
 }
 
 // SPEC §6.4 rules 1-3 on host maps: the two Lab level images (and the coarser level's field) up, L_(t-1) packed, one k_seq_motion launch, the field down
 int nct_seq_motion_field(nct_ctx* ctx, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, const int16_t* parent, int ph, int pw, int R, int penalty, int16_t* m_out) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(lab && lab_prev && m_out, "seq_motion_field: null pointer");
-    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_motion_field: grid %dx%d out of range", w, h);
-    NCT_REQUIRE(!parent || (ph >= 1 && pw >= 1 && ph <= 4096 && pw <= 4096), "seq_motion_field: parent grid %dx%d out of range", pw, ph);
-    const size_t n = (size_t)h * w, np = parent ? (size_t)ph * pw : 1;
-    DevBuf<uint8_t> dl(ctx, 3 * n), dlp(ctx, 3 * n);
-    DevBuf<uint32_t> pk(ctx, n);
-    DevBuf<int16_t> dpar(ctx, 2 * np), dm(ctx, 2 * n);
-    if (!dl.ok() || !dlp.ok() || !pk.ok() || !dpar.ok() || !dm.ok()) return NCT_ERR_HIP;
-    NCT_H2D(dl, lab, 3 * n); NCT_H2D(dlp, lab_prev, 3 * n);
-    if (parent) NCT_H2D(dpar, parent, sizeof(int16_t) * 2 * np);
+    NCT_TRY(nct_seq_motion_field_check(ctx, "seq_motion_field", lab, lab_prev, h, w, parent, ph, pw, m_out));
+    const size_t n = (size_t)h * w;
+    HostCall hc(ctx);
+    const uint8_t *dl = hc.in(lab, 3 * n), *dlp = hc.in(lab_prev, 3 * n);
+    uint32_t* pk = hc.scratch<uint32_t>(n);
+    const int16_t* dpar = hc.in(parent, 2 * (size_t)ph * pw);
+    int16_t* dm = hc.out(m_out, 2 * n);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_seq_pack(ctx, ctx->stream, dlp, (int)n, pk));
-    NCT_TRY(nctk_seq_motion(ctx, ctx->stream, dl, pk, h, w, parent ? (const int16_t*)dpar : nullptr, ph, pw, R, penalty, dm));
-    NCT_D2H(m_out, dm, sizeof(int16_t) * 2 * n);
-    NCT_SYNC();
-    return NCT_OK;
+    NCT_TRY(nctk_seq_motion(ctx, ctx->stream, dl, pk, h, w, dpar, ph, pw, R, penalty, dm));
+    return hc.finish();
 }
 
 // SPEC §6.5 rule 3 on host maps: the kept coefficients and the field up, one k_seq_warp launch out of place, the warped map down
@@ -449,14 +422,13 @@ int nct_seq_warp(nct_ctx* ctx, const double* x_prev, int h, int w, const int16_t
     NCT_REQUIRE(x_prev && field && x_out, "seq_warp: null pointer");
     NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_warp: grid %dx%d out of range", w, h);
     const size_t n = (size_t)h * w;
-    DevBuf<double> dp(ctx, 6 * n), dx(ctx, 6 * n);
-    DevBuf<int16_t> df(ctx, 2 * n);
-    if (!dp.ok() || !dx.ok() || !df.ok()) return NCT_ERR_HIP;
-    NCT_H2D(dp, x_prev, sizeof(double) * 6 * n); NCT_H2D(df, field, sizeof(int16_t) * 2 * n);
+    HostCall hc(ctx);
+    const double* dp = hc.in(x_prev, 6 * n);
+    double* dx = hc.out(x_out, 6 * n);
+    const int16_t* df = hc.in(field, 2 * n);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_seq_warp(ctx, ctx->stream, dp, h, w, df, dx));
-    NCT_D2H(x_out, dx, sizeof(double) * 6 * n);
-    NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 // SPEC §6.14 rule 1 on host arrays: the matte and the field up, one k_seq_matte_warp launch out of place, the carried matte down
@@ -464,14 +436,13 @@ int nct_seq_matte_warp(nct_ctx* ctx, const uint8_t* mask_prev, int H, int W, con
     NCT_CTX_ENTER();
     NCT_TRY(nct_seq_matte_warp_check(ctx, "seq_matte_warp", mask_prev, H, W, field, h, w, mask_out));
     const size_t N = (size_t)H * W, n = (size_t)h * w;
-    DevBuf<uint8_t> dp(ctx, N), dm(ctx, N);
-    DevBuf<int16_t> df(ctx, 2 * n);
-    if (!dp.ok() || !dm.ok() || !df.ok()) return NCT_ERR_HIP;
-    NCT_H2D(dp, mask_prev, N); NCT_H2D(df, field, sizeof(int16_t) * 2 * n);
+    HostCall hc(ctx);
+    const uint8_t* dp = hc.in(mask_prev, N);
+    uint8_t* dm = hc.out(mask_out, N);
+    const int16_t* df = hc.in(field, 2 * n);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_seq_matte_warp(ctx, ctx->stream, dp, H, W, df, h, w, dm));
-    NCT_D2H(mask_out, dm, N);
-    NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 // SPEC §6.15 rule 1 on host arrays: the matte and the guide up, one k_region_snap launch out of place, the snapped matte down
@@ -479,13 +450,12 @@ int nct_region_snap(nct_ctx* ctx, const uint8_t* mask, const uint8_t* lab, int H
     NCT_CTX_ENTER();
     NCT_TRY(nct_region_snap_check(ctx, "region_snap", mask, lab, H, W, params, mask_out));
     const size_t N = (size_t)H * W;
-    DevBuf<uint8_t> dm(ctx, N), dl(ctx, N * 3), dout(ctx, N);
-    if (!dm.ok() || !dl.ok() || !dout.ok()) return NCT_ERR_HIP;
-    NCT_H2D(dm, mask, N); NCT_H2D(dl, lab, N * 3);
+    HostCall hc(ctx);
+    const uint8_t *dm = hc.in(mask, N), *dl = hc.in(lab, N * 3);
+    uint8_t* dout = hc.out(mask_out, N);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_region_snap(ctx, ctx->stream, dm, dl, H, W, params, dout));
-    NCT_D2H(mask_out, dout, N);
-    NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 // SPEC §6.7 rule 1 on host maps: the two Lab level images (and the field) up, one k_seq_change launch, the 16-byte record down
@@ -496,16 +466,13 @@ int nct_seq_change(nct_ctx* ctx, const uint8_t* lab, const uint8_t* lab_prev, in
     NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_change: grid %dx%d out of range", w, h);
     NCT_REQUIRE(threshold >= 0 && threshold <= 765, "seq_change: the threshold must be in [0, 765] (got %d)", threshold);
     const size_t n = (size_t)h * w;
-    DevBuf<uint8_t> dl(ctx, 3 * n), dlp(ctx, 3 * n);
-    DevBuf<int16_t> df(ctx, field ? 2 * n : 8);
-    DevBuf<nct_seq_change_rec> dr(ctx, 1);
-    if (!dl.ok() || !dlp.ok() || !df.ok() || !dr.ok()) return NCT_ERR_HIP;
-    NCT_H2D(dl, lab, 3 * n); NCT_H2D(dlp, lab_prev, 3 * n);
-    if (field) NCT_H2D(df, field, sizeof(int16_t) * 2 * n);
-    NCT_TRY(nctk_seq_change(ctx, ctx->stream, dl, dlp, h, w, field ? (const int16_t*)df : nullptr, threshold, dr));
-    NCT_D2H(out, dr, sizeof *out);
-    NCT_SYNC();
-    return NCT_OK;
+    HostCall hc(ctx);
+    const uint8_t *dl = hc.in(lab, 3 * n), *dlp = hc.in(lab_prev, 3 * n);
+    const int16_t* df = hc.in(field, 2 * n);
+    nct_seq_change_rec* dr = hc.out(out, 1);
+    NCT_TRY(hc.ready());
+    NCT_TRY(nctk_seq_change(ctx, ctx->stream, dl, dlp, h, w, df, threshold, dr));
+    return hc.finish();
 }
 
 int nct_bds_vote_image(nct_ctx* ctx, const uint8_t* a_bgr, int ah, int aw, const uint8_t* b_bgr, int bh, int bw,
@@ -517,16 +484,13 @@ int nct_bds_vote_image(nct_ctx* ctx, const uint8_t* a_bgr, int ah, int aw, const
     NCT_REQUIRE(ah > 0 && aw > 0 && bh > 0 && bw > 0, "bds_vote_image: empty image");
     NCT_REQUIRE(nct_nnf_dims_ok(ah, aw, bh, bw), "bds_vote_image: dims out of range (%dx%d vs %dx%d); NNF coordinates are 12-bit", ah, aw, bh, bw);
     const size_t na = (size_t)ah * aw, nb = (size_t)bh * bw;
-    DevBuf<uint8_t> b(ctx, nb * 3), o(ctx, na * 3);
-    DevBuf<uint32_t> da(ctx, na), db(ctx, nb);
-    if (!b.ok() || !o.ok() || !da.ok() || !db.ok()) return NCT_ERR_HIP;
-    NCT_H2D(b, b_bgr, nb * 3);
-    NCT_H2D(da, ann, sizeof(uint32_t) * na);
-    NCT_H2D(db, bnn, sizeof(uint32_t) * nb);
+    HostCall hc(ctx);
+    const uint8_t* b = hc.in(b_bgr, nb * 3);
+    uint8_t* o = hc.out(out_bgr, na * 3);
+    const uint32_t *da = hc.in(ann, na), *db = hc.in(bnn, nb);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_bds_vote_image(ctx, ctx->stream, b, da, db, ah, aw, bh, bw, w_coherence, w_complete, o));
-    NCT_D2H(out_bgr, o, na * 3);
-    NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 // ---------------------------------------------------------------- measurement hooks
@@ -544,13 +508,14 @@ int nct_pm_bench_setup(nct_ctx* ctx, const float* a_chw, const float* b_chw, int
     NCT_HIP(hipMalloc(&ctx->bench_bh16, 2 * (size_t)C * nb));
     if (!ctx->d_counter) NCT_HIP(hipMalloc(&ctx->d_counter, 32 * sizeof(unsigned long long)));
     {
-        DevBuf<float> t(ctx, (size_t)C * (na > nb ? na : nb)), x(ctx, (size_t)C * (na > nb ? na : nb));
-        if (!t.ok() || !x.ok()) return NCT_ERR_HIP;
-        NCT_TRY(upload_hwc(ctx, a_chw, t, x, C, (int)na));
+        HostCall hc(ctx);
+        float *t = hc.scratch<float>((size_t)C * (na > nb ? na : nb)), *x = hc.scratch<float>((size_t)C * (na > nb ? na : nb));
+        NCT_TRY(hc.ready());
+        NCT_TRY(upload_hwc(ctx, hc, a_chw, t, x, C, (int)na));
         NCT_TRY(nctk_normalize(ctx, ctx->stream, x, ctx->bench_a, nullptr, C, (int)na, ctx->bench_ah16));
-        NCT_TRY(upload_hwc(ctx, b_chw, t, x, C, (int)nb));
+        NCT_TRY(upload_hwc(ctx, hc, b_chw, t, x, C, (int)nb));
         NCT_TRY(nctk_normalize(ctx, ctx->stream, x, ctx->bench_b, nullptr, C, (int)nb, ctx->bench_bh16));
-        NCT_SYNC();
+        NCT_TRY(hc.finish());
     }
     ctx->bench_C = C; ctx->bench_ah = ah; ctx->bench_aw = aw; ctx->bench_bh = bh; ctx->bench_bw = bw;
     return NCT_OK;
@@ -561,9 +526,9 @@ int nct_pm_bench_run(nct_ctx* ctx, int iters, int rs_max, uint32_t seed, float* 
     if (!ctx->bench_a) return ctx->fail(NCT_ERR_STATE, "pm_bench_run: call nct_pm_bench_setup first");
     const int C = ctx->bench_C, ah = ctx->bench_ah, aw = ctx->bench_aw, bh = ctx->bench_bh, bw = ctx->bench_bw;
     const size_t na = (size_t)ah * aw;
-    DevBuf<uint32_t> n(ctx, na);
-    DevBuf<float> d(ctx, na);
-    if (!n.ok() || !d.ok()) return NCT_ERR_HIP;
+    DevBuf<uint32_t> n;
+    DevBuf<float> d;
+    if (!n.alloc(ctx, na) || !d.alloc(ctx, na)) return NCT_ERR_HIP;
     NCT_TRY(nctk_nnf_init(ctx, ctx->stream, n, ah, aw, bh, bw));
     unsigned long long* counter = evals ? ctx->d_counter : nullptr;
     if (counter) NCT_HIP(hipMemsetAsync(counter, 0, 4 * sizeof(unsigned long long), ctx->stream));
@@ -587,9 +552,9 @@ int nct_pm_bench_run_bidir(nct_ctx* ctx, int iters, int rs_max, uint32_t seed, i
     NCT_REQUIRE(pm_mode >= NCT_PM_PLAIN && pm_mode <= NCT_PM_FP16, "pm_bench_run_bidir: pm_mode must be 0 (fp32), 1 (fp32 + row rejection) or 2 (fp16)");
     const int C = ctx->bench_C, ah = ctx->bench_ah, aw = ctx->bench_aw, bh = ctx->bench_bh, bw = ctx->bench_bw;
     const size_t na = (size_t)ah * aw, nb = (size_t)bh * bw;
-    DevBuf<uint32_t> an(ctx, na), bn(ctx, nb);
-    DevBuf<float> ad(ctx, na), bd(ctx, nb);
-    if (!an.ok() || !bn.ok() || !ad.ok() || !bd.ok()) return NCT_ERR_HIP;
+    DevBuf<uint32_t> an, bn;
+    DevBuf<float> ad, bd;
+    if (!an.alloc(ctx, na) || !bn.alloc(ctx, nb) || !ad.alloc(ctx, na) || !bd.alloc(ctx, nb)) return NCT_ERR_HIP;
     NCT_TRY(nctk_nnf_init(ctx, ctx->stream, an, ah, aw, bh, bw));
     NCT_TRY(nctk_nnf_init(ctx, ctx->stream, bn, bh, bw, ah, aw));
     unsigned long long* counter = counters ? ctx->d_counter : nullptr;

@@ -18,71 +18,71 @@ void nct_params_default(nct_params* p) {
 int nct_bgr2lab_u8(nct_ctx* ctx, const uint8_t* bgr, size_t npix, uint8_t* lab) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(bgr && lab && npix > 0, "bgr2lab: bad arguments");
-    DevBuf<uint8_t> a(ctx, npix * 3), b(ctx, npix * 3);
-    if (!a.ok() || !b.ok()) return NCT_ERR_HIP;
-    NCT_H2D(a, bgr, npix * 3);
+    HostCall hc(ctx);
+    const uint8_t* a = hc.in(bgr, npix * 3);
+    uint8_t* b = hc.out(lab, npix * 3);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_bgr2lab(ctx, ctx->stream, a, b, npix));
-    NCT_D2H(lab, b, npix * 3); NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 int nct_lab2bgr_u8(nct_ctx* ctx, const uint8_t* lab, size_t npix, uint8_t* bgr) { return nct_lab2bgr_u8_form(ctx, lab, npix, bgr, NCT_LAB2BGR_PIECEWISE); }
 int nct_lab2bgr_u8_form(nct_ctx* ctx, const uint8_t* lab, size_t npix, uint8_t* bgr, int form) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(bgr && lab && npix > 0, "lab2bgr: bad arguments");
     NCT_REQUIRE(form == NCT_LAB2BGR_CUBE || form == NCT_LAB2BGR_PIECEWISE, "lab2bgr: unknown form %d", form);
-    DevBuf<uint8_t> a(ctx, npix * 3), b(ctx, npix * 3);
-    if (!a.ok() || !b.ok()) return NCT_ERR_HIP;
-    NCT_H2D(a, lab, npix * 3);
+    HostCall hc(ctx);
+    const uint8_t* a = hc.in(lab, npix * 3);
+    uint8_t* b = hc.out(bgr, npix * 3);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_lab2bgr(ctx, ctx->stream, a, b, npix, form));
-    NCT_D2H(bgr, b, npix * 3); NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 int nct_resize_u8c3(nct_ctx* ctx, const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(src && dst && sh > 0 && sw > 0 && dh > 0 && dw > 0, "resize_u8c3: bad arguments");
-    DevBuf<uint8_t> a(ctx, (size_t)sh * sw * 3), b(ctx, (size_t)dh * dw * 3);
-    if (!a.ok() || !b.ok()) return NCT_ERR_HIP;
-    NCT_H2D(a, src, (size_t)sh * sw * 3);
+    HostCall hc(ctx);
+    const uint8_t* a = hc.in(src, (size_t)sh * sw * 3);
+    uint8_t* b = hc.out(dst, (size_t)dh * dw * 3);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_resize_u8c3(ctx, ctx->stream, a, sh, sw, b, dh, dw));
-    NCT_D2H(dst, b, (size_t)dh * dw * 3); NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 // ---- source region masks (SPEC §6.11): the three steps alone, on host maps
 int nct_resize_u8c1(nct_ctx* ctx, const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(src && dst, "resize_u8c1: null pointer");
-    NCT_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0 && sh <= 16384 && sw <= 16384 && dh <= 16384 && dw <= 16384 && (long long)sh * sw <= (1LL << 26) && (long long)dh * dw <= (1LL << 26),
-                "resize_u8c1: size %dx%d -> %dx%d out of range", sw, sh, dw, dh);
-    DevBuf<uint8_t> a(ctx, (size_t)sh * sw), b(ctx, (size_t)dh * dw);
-    if (!a.ok() || !b.ok()) return NCT_ERR_HIP;
-    NCT_H2D(a, src, (size_t)sh * sw);
+    NCT_TRY(nct_resize_u8c1_check(ctx, "resize_u8c1", src, sh, sw, dst, dh, dw));
+    HostCall hc(ctx);
+    const uint8_t* a = hc.in(src, (size_t)sh * sw);
+    uint8_t* b = hc.out(dst, (size_t)dh * dw);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_resize_u8c1(ctx, ctx->stream, a, sh, sw, b, dh, dw));
-    NCT_D2H(dst, b, (size_t)dh * dw); NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 int nct_region_mix(nct_ctx* ctx, const double* x, const uint8_t* mask, int h, int w, double* x_out) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(x && mask && x_out, "region_mix: null pointer");
     NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "region_mix: grid %dx%d out of range", w, h);
     const size_t n = (size_t)h * w;
-    DevBuf<double> dx(ctx, 6 * n); DevBuf<uint8_t> dm(ctx, n);
-    if (!dx.ok() || !dm.ok()) return NCT_ERR_HIP;
-    NCT_H2D(dx, x, sizeof(double) * 6 * n); NCT_H2D(dm, mask, n);
+    HostCall hc(ctx);
+    double* dx = hc.inout(x, x_out, 6 * n);
+    const uint8_t* dm = hc.in(mask, n);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_region_mix(ctx, ctx->stream, dx, dm, h, w, dx));          // in place, as a level does it
-    NCT_D2H(x_out, dx, sizeof(double) * 6 * n); NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 int nct_region_compose(nct_ctx* ctx, const uint8_t* s_bgr, const uint8_t* lab_out, const uint8_t* mask, size_t npix, const nct_region_params* region, const nct_params* prm,
                        uint8_t* out_bgr) {
     NCT_CTX_ENTER();
     NCT_TRY(nct_region_compose_check(ctx, "region_compose", s_bgr, lab_out, mask, npix, region, prm, out_bgr));
-    DevBuf<uint8_t> ds(ctx, npix * 3), dls(ctx, npix * 3), dlo(ctx, npix * 3), dm(ctx, npix), dout(ctx, npix * 3);
-    if (!ds.ok() || !dls.ok() || !dlo.ok() || !dm.ok() || !dout.ok()) return NCT_ERR_HIP;
-    NCT_H2D(ds, s_bgr, npix * 3); NCT_H2D(dlo, lab_out, npix * 3); NCT_H2D(dm, mask, npix);
+    HostCall hc(ctx);
+    const uint8_t* ds = hc.in(s_bgr, npix * 3);
+    uint8_t* dls = hc.scratch<uint8_t>(npix * 3);
+    const uint8_t *dlo = hc.in(lab_out, npix * 3), *dm = hc.in(mask, npix);
+    uint8_t* dout = hc.out(out_bgr, npix * 3);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_bgr2lab(ctx, ctx->stream, ds, dls, npix));
     NCT_TRY(nctk_region_compose(ctx, ctx->stream, ds, dls, dlo, dm, npix, region ? region->protect : 0, nct_cube_form(*prm), dout));
-    NCT_D2H(out_bgr, dout, npix * 3); NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 // ---- reference region masks (SPEC §6.12 rule 2): the pull alone, on host maps
@@ -91,38 +91,39 @@ int nct_region_pull(nct_ctx* ctx, const uint8_t* q_mask, int bh, int bw, const u
     NCT_CTX_ENTER();
     NCT_TRY(nct_region_pull_check(ctx, "region_pull", q_mask, bh, bw, ann, bnn, ah, aw, out));
     const size_t na = (size_t)ah * aw, nb = (size_t)bh * bw;
-    DevBuf<uint8_t> dq(ctx, nb), dout(ctx, na); DevBuf<uint32_t> da(ctx, na), db(ctx, nb);
-    if (!dq.ok() || !dout.ok() || !da.ok() || !db.ok()) return NCT_ERR_HIP;
-    NCT_H2D(dq, q_mask, nb); NCT_H2D(da, ann, sizeof(uint32_t) * na); NCT_H2D(db, bnn, sizeof(uint32_t) * nb);
+    HostCall hc(ctx);
+    const uint8_t* dq = hc.in(q_mask, nb);
+    uint8_t* dout = hc.out(out, na);
+    const uint32_t *da = hc.in(ann, na), *db = hc.in(bnn, nb);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_region_pull(ctx, ctx->stream, dq, bh, bw, da, db, ah, aw, w_coherence, w_complete, dout));
-    NCT_D2H(out, dout, na); NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 int nct_resize_f64c3(nct_ctx* ctx, const double* src, int sh, int sw, double* dst, int dh, int dw) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(src && dst && sh > 0 && sw > 0 && dh > 0 && dw > 0, "resize_f64c3: bad arguments");
-    DevBuf<double> a(ctx, (size_t)sh * sw * 3), b(ctx, (size_t)dh * dw * 3);
-    if (!a.ok() || !b.ok()) return NCT_ERR_HIP;
-    NCT_H2D(a, src, sizeof(double) * sh * sw * 3);
+    HostCall hc(ctx);
+    const double* a = hc.in(src, (size_t)sh * sw * 3);
+    double* b = hc.out(dst, (size_t)dh * dw * 3);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_resize_f64c3(ctx, ctx->stream, a, sh, sw, b, dh, dw));
-    NCT_D2H(dst, b, sizeof(double) * dh * dw * 3); NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 int nct_cluster_features(nct_ctx* ctx, const float* feat_chw, int C, int h, int w, int K, int iters, uint64_t seed, int* labels, int* nlabels) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(feat_chw && labels && nlabels && h > 0 && w > 0 && (C & 3) == 0, "cluster_features: bad arguments");
     const int n = h * w;
-    DevBuf<float> t(ctx, (size_t)C * n), f(ctx, (size_t)C * n), fn(ctx, (size_t)C * n);
-    DevBuf<int> lab(ctx, n), nl(ctx, 1);
-    if (!t.ok() || !f.ok() || !fn.ok() || !lab.ok() || !nl.ok()) return NCT_ERR_HIP;
-    NCT_H2D(t, feat_chw, sizeof(float) * C * n);
+    HostCall hc(ctx);
+    const float* t = hc.in(feat_chw, (size_t)C * n);
+    float *f = hc.scratch<float>((size_t)C * n), *fn = hc.scratch<float>((size_t)C * n);
+    int *lab = hc.out(labels, n), *nl = hc.out(nlabels, 1);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_chw_to_hwc(ctx, ctx->stream, t, f, C, n));
     NCT_TRY(nctk_normalize(ctx, ctx->stream, f, fn, nullptr, C, n));          // main.cu:139-165 (per-pixel L2 normalise, HWC)
     NCT_TRY(nctk_kmeans_labels(ctx, ctx->stream, fn, n, C, K, iters, seed, lab, nl));
-    NCT_D2H(labels, lab, sizeof(int) * n); NCT_D2H(nlabels, nl, sizeof(int)); NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 int nct_knn_graph(nct_ctx* ctx, const uint8_t* lab_u8, int h, int w, const int* labels, int lh, int lw, int nlabels, int samples, int k,
@@ -131,14 +132,14 @@ int nct_knn_graph(nct_ctx* ctx, const uint8_t* lab_u8, int h, int w, const int* 
     NCT_REQUIRE(lab_u8 && labels && knn_id && knn_w && h > 0 && w > 0 && lh > 0 && lw > 0 && samples > 0, "knn_graph: bad arguments");
     NCT_REQUIRE(k == 8, "knn_graph: only k=8 is supported (Config.h:68), got %d", k);
     const int n = h * w;
-    DevBuf<uint8_t> l(ctx, (size_t)n * 3);
-    DevBuf<int> lb(ctx, (size_t)lh * lw), id(ctx, (size_t)n * 8);
-    DevBuf<double> kw(ctx, (size_t)n * 8);
-    if (!l.ok() || !lb.ok() || !id.ok() || !kw.ok()) return NCT_ERR_HIP;
-    NCT_H2D(l, lab_u8, (size_t)n * 3); NCT_H2D(lb, labels, sizeof(int) * lh * lw);
+    HostCall hc(ctx);
+    const uint8_t* l = hc.in(lab_u8, (size_t)n * 3);
+    const int* lb = hc.in(labels, (size_t)lh * lw);
+    int* id = hc.out(knn_id, (size_t)n * 8);
+    double* kw = hc.out(knn_w, (size_t)n * 8);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_knn_graph(ctx, ctx->stream, l, h, w, lb, lh, lw, nlabels, nullptr, samples, id, kw));
-    NCT_D2H(knn_id, id, sizeof(int) * n * 8); NCT_D2H(knn_w, kw, sizeof(double) * n * 8); NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 int nct_local_color_transfer(nct_ctx* ctx, const float* err, const uint8_t* s_bgr_level, const uint8_t* g_bgr_level, const uint8_t* s_bgr_full,
@@ -149,13 +150,13 @@ int nct_local_color_transfer(nct_ctx* ctx, const float* err, const uint8_t* s_bg
     NCT_REQUIRE(h > 0 && w > 0 && H >= h && W >= w && layer >= 0 && layer <= 4, "local_color_transfer: bad geometry");
     NCT_TRY(nct_params_check(ctx, "local_color_transfer", *prm));
     const size_t n = (size_t)h * w, N = (size_t)H * W;
-    DevBuf<float> derr(ctx, n);
-    DevBuf<uint8_t> sl(ctx, n * 3), gl(ctx, n * 3), sf(ctx, N * 3), slab(ctx, n * 3), glab(ctx, n * 3), sflab(ctx, N * 3), olab(ctx, N * 3), obgr(ctx, N * 3);
-    DevBuf<int> id(ctx, n * 8);
-    DevBuf<double> kw(ctx, n * 8);
-    if (!derr.ok() || !sl.ok() || !gl.ok() || !sf.ok() || !slab.ok() || !glab.ok() || !sflab.ok() || !olab.ok() || !obgr.ok() || !id.ok() || !kw.ok()) return NCT_ERR_HIP;
-    NCT_H2D(derr, err, sizeof(float) * n); NCT_H2D(sl, s_bgr_level, n * 3); NCT_H2D(gl, g_bgr_level, n * 3); NCT_H2D(sf, s_bgr_full, N * 3);
-    NCT_H2D(id, knn_id, sizeof(int) * n * 8); NCT_H2D(kw, knn_w, sizeof(double) * n * 8);
+    HostCall hc(ctx);
+    const float* derr = hc.in(err, n);
+    const uint8_t *sl = hc.in(s_bgr_level, n * 3), *gl = hc.in(g_bgr_level, n * 3), *sf = hc.in(s_bgr_full, N * 3);
+    uint8_t *slab = hc.scratch<uint8_t>(n * 3), *glab = hc.scratch<uint8_t>(n * 3), *sflab = hc.scratch<uint8_t>(N * 3), *olab = hc.scratch<uint8_t>(N * 3), *obgr = hc.out(out_bgr_full, N * 3);
+    const int* id = hc.in(knn_id, n * 8);
+    const double* kw = hc.in(knn_w, n * 8);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_bgr2lab(ctx, ctx->stream, sl, slab, n));          // main.cu:351-352
     NCT_TRY(nctk_bgr2lab(ctx, ctx->stream, gl, glab, n));          // main.cu:370-371
     NCT_TRY(nctk_bgr2lab(ctx, ctx->stream, sf, sflab, N));         // ColorTransfer.h:58
@@ -169,8 +170,7 @@ int nct_local_color_transfer(nct_ctx* ctx, const float* err, const uint8_t* s_bg
         NCT_TRY(nctk_color_finish(ctx, ctx->stream, cb.x, h, w, H, W, sflab, H, W, cp, olab, stages ? &dbg : nullptr));
     }
     NCT_TRY(nctk_lab2bgr(ctx, ctx->stream, olab, obgr, N, nct_cube_form(*prm)));        // ColorTransfer.cpp:1469
-    NCT_D2H(out_bgr_full, obgr, N * 3); NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 // the finish alone (SPEC §6.1): U1 / roughness / S2 / A1 of S1's coefficients onto s_bgr_full, which may be larger than the working size
@@ -182,10 +182,11 @@ int nct_color_finish(nct_ctx* ctx, const double* ab, int h, int w, int work_h, i
     NCT_REQUIRE(H <= NCT_FINISH_MAX_SIDE && W <= NCT_FINISH_MAX_SIDE && (long long)H * W <= NCT_FINISH_MAX_PIXELS, "color_finish: target %dx%d above 16384 per side or 2^26 pixels", W, H);
     NCT_TRY(nct_params_check(ctx, "color_finish", *prm));
     const size_t n = (size_t)h * w, N = (size_t)H * W;
-    DevBuf<double> x(ctx, 6 * n);
-    DevBuf<uint8_t> sf(ctx, N * 3), sflab(ctx, N * 3), olab(ctx, N * 3), obgr(ctx, N * 3);
-    if (!x.ok() || !sf.ok() || !sflab.ok() || !olab.ok() || !obgr.ok()) return NCT_ERR_HIP;
-    NCT_H2D(x, ab, sizeof(double) * 6 * n); NCT_H2D(sf, s_bgr_full, N * 3);
+    HostCall hc(ctx);
+    const double* x = hc.in(ab, 6 * n);
+    const uint8_t* sf = hc.in(s_bgr_full, N * 3);
+    uint8_t *sflab = hc.scratch<uint8_t>(N * 3), *olab = hc.scratch<uint8_t>(N * 3), *obgr = hc.out(out_bgr_full, N * 3);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_bgr2lab(ctx, ctx->stream, sf, sflab, N));
     const nct_color_params cp = nct_color_params_of(*prm);
     nct_color_debug dbg{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -193,8 +194,7 @@ int nct_color_finish(nct_ctx* ctx, const double* ab, int h, int w, int work_h, i
     ctx->wls_split = (prm->flags & NCT_FLAG_LATENCY) ? 1 : 0;
     NCT_TRY(nctk_color_finish(ctx, ctx->stream, x, h, w, work_h, work_w, sflab, H, W, cp, olab, stages ? &dbg : nullptr));
     NCT_TRY(nctk_lab2bgr(ctx, ctx->stream, olab, obgr, N, nct_cube_form(*prm)));
-    NCT_D2H(out_bgr_full, obgr, N * 3); NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 // ---- the upsampling finish alone, on host pointers, in its four forms (k_finish_up.hip): the working-size S2 output upsampled and applied to the original source in one
@@ -207,17 +207,14 @@ static int finish_up_host(nct_ctx* ctx, bool is_guided, const double* ab_wls, co
     const nct_finish_up host{s_bgr_full, H, W, out_bgr_full, nct_cube_form(*prm), is_guided ? guided->sigma : 0.0, mask, region ? region->protect : 0};
     NCT_TRY(nctk_finish_up_check(ctx, is_guided, ab_wls, lab_work, h, w, host));      // before anything is reserved
     const size_t n = (size_t)h * w, N = (size_t)H * W;
-    DevBuf<double> x(ctx, 6 * n);
-    DevBuf<uint8_t> lw, sf, dm, obgr;
-    if (!x.ok() || (is_guided && !lw.alloc(ctx, n * 3)) || !sf.alloc(ctx, N * 3) || (mask && !dm.alloc(ctx, N)) || !obgr.alloc(ctx, N * 3)) return NCT_ERR_HIP;
-    NCT_H2D(x, ab_wls, sizeof(double) * 6 * n);
-    if (is_guided) NCT_H2D(lw, lab_work, n * 3);
-    NCT_H2D(sf, s_bgr_full, N * 3);
-    if (mask) NCT_H2D(dm, mask, N);
-    nct_finish_up up = host; up.s_bgr = sf; up.mask = dm; up.out_bgr = obgr;          // the same call on the device copies
+    HostCall hc(ctx);
+    const double* x = hc.in(ab_wls, 6 * n);
+    const uint8_t* lw = is_guided ? hc.in(lab_work, n * 3) : nullptr;
+    nct_finish_up up = host;                                                          // the same call on the device copies
+    up.s_bgr = hc.in(s_bgr_full, N * 3); up.mask = hc.in(mask, N); up.out_bgr = hc.out(out_bgr_full, N * 3);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_finish_up(ctx, ctx->stream, x, lw, h, w, up));
-    NCT_D2H(out_bgr_full, obgr, N * 3); NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 int nct_color_finish_upsample(nct_ctx* ctx, const double* ab_wls, int h, int w, const uint8_t* s_bgr_full, int H, int W, const nct_params* prm, uint8_t* out_bgr_full) {

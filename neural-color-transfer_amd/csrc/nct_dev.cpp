@@ -248,8 +248,7 @@ int nct_seq_change_dev(nct_ctx* ctx, const uint8_t* d_lab, const uint8_t* d_lab_
 int nct_seq_motion_field_dev(nct_ctx* ctx, const uint8_t* d_lab, const uint8_t* d_lab_prev, int h, int w, const int16_t* d_parent, int ph, int pw, int R, int penalty,
                              int16_t* d_m_out) {                                                                                                      /* SPEC §6.4 rules 1-3 */
     NCT_CTX_ENTER();
-    NCT_REQUIRE(d_lab && d_lab_prev && d_m_out, "seq_motion_field_dev: null pointer");
-    NCT_REQUIRE(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seq_motion_field_dev: grid %dx%d out of range", w, h);
+    NCT_TRY(nct_seq_motion_field_check(ctx, "seq_motion_field_dev", d_lab, d_lab_prev, h, w, d_parent, ph, pw, d_m_out));
     DevBuf<uint32_t> pk(ctx, (size_t)h * w);                     // L_(t-1) one word per pixel; the block goes back in stream order
     if (!pk.ok()) return NCT_ERR_HIP;
     NCT_TRY(nctk_seq_pack(ctx, ctx->stream, d_lab_prev, h * w, pk));
@@ -259,9 +258,7 @@ int nct_seq_motion_field_dev(nct_ctx* ctx, const uint8_t* d_lab, const uint8_t* 
 // ---- SPEC §6.11 on device pointers
 int nct_resize_u8c1_dev(nct_ctx* ctx, const uint8_t* d_src, int sh, int sw, uint8_t* d_dst, int dh, int dw) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(d_src && d_dst, "resize_u8c1_dev: null pointer");
-    NCT_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0 && sh <= 16384 && sw <= 16384 && dh <= 16384 && dw <= 16384 && (long long)sh * sw <= (1LL << 26) && (long long)dh * dw <= (1LL << 26),
-                "resize_u8c1_dev: size %dx%d -> %dx%d out of range", sw, sh, dw, dh);
+    NCT_TRY(nct_resize_u8c1_check(ctx, "resize_u8c1_dev", d_src, sh, sw, d_dst, dh, dw));
     return nctk_resize_u8c1(ctx, ctx->stream, d_src, sh, sw, d_dst, dh, dw);
 }
 

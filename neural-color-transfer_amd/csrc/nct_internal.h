@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdarg>
 #include <cmath>
+#include <deque>
 #include <string>
 #include <vector>
 #include "../../include/nct.h"
@@ -111,6 +112,52 @@ template <typename T> struct DevBuf {
 #define NCT_H2D(dst, src, bytes) NCT_HIP(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, ctx->stream))
 #define NCT_D2H(dst, src, bytes) NCT_HIP(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, ctx->stream))
 #define NCT_SYNC() NCT_HIP(hipStreamSynchronize(ctx->stream))
+
+// One host-pointer entry point's traffic on the main stream: the call's arena blocks, its uploads (enqueued at once) and its downloads (enqueued by finish(), in the
+// order they were asked for, in front of the call's one wait). The first failed reservation or copy sticks: what follows it does nothing and returns null, and the
+// entry point tests ready() once before its first launcher. The blocks are DevBufs: they go back when the call ends — behind the wait where it succeeds; where it fails
+// after a copy was enqueued the destructor waits first (its own error is dropped: the call has its code and message), so that no call returns while a copy from or
+// to the caller's memory is still queued
+struct HostCall {
+    nct_ctx* ctx; int rc = NCT_OK; bool queued = false, waited = false;
+    struct Down { void* host; const void* dev; size_t bytes; };
+    std::vector<Down> downs;
+    std::deque<DevBuf<char>> blocks;
+    explicit HostCall(nct_ctx* c) : ctx(c) {}
+    HostCall(const HostCall&) = delete; HostCall& operator=(const HostCall&) = delete;
+    ~HostCall() { if (queued && !waited) (void)hipStreamSynchronize(ctx->stream); }
+    template <typename T> T* scratch(size_t n) {                                  // a block of n elements that nobody copies
+        if (rc) return nullptr;
+        blocks.emplace_back();
+        if (!blocks.back().alloc(ctx, n * sizeof(T))) rc = NCT_ERR_HIP;
+        return (T*)blocks.back().p;
+    }
+    // the copies alone, for a block that holds several arrays or is used twice (a null side: nothing)
+    template <typename T> void put(T* dev, const T* host, size_t n) { if (!rc && dev && host) copy(dev, host, n * sizeof(T), hipMemcpyHostToDevice); }
+    template <typename T> void get(T* host, const T* dev, size_t n) { if (!rc && dev && host) downs.push_back({host, dev, n * sizeof(T)}); }
+    // an argument of the call: a null host array reserves nothing and gives the launcher null
+    template <typename T> T* in(const T* host, size_t n) { return inout(host, (T*)nullptr, n); }
+    template <typename T> T* out(T* host, size_t n) { return inout((const T*)nullptr, host, n); }
+    template <typename T> T* inout(const T* src, T* dst, size_t n) {              // up now, down at finish(): a seam that runs in place
+        if (!src && !dst) return nullptr;
+        T* d = scratch<T>(n);
+        put(d, src, n); get(dst, d, n);
+        return rc ? nullptr : d;
+    }
+    int ready() const { return rc; }                                              // the first failure so far (its message is in ctx->err), else NCT_OK
+    int finish() {
+        for (size_t i = 0; i < downs.size() && !rc; ++i) copy(downs[i].host, downs[i].dev, downs[i].bytes, hipMemcpyDeviceToHost);
+        if (rc) return rc;
+        waited = true;
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        return e == hipSuccess ? NCT_OK : (rc = ctx->fail(NCT_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e)));
+    }
+    void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+        queued = true;
+        const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, ctx->stream);
+        if (e != hipSuccess) rc = ctx->fail(NCT_ERR_HIP, "hipMemcpyAsync (%s, %zu bytes) failed: %s", kind == hipMemcpyHostToDevice ? "host to device" : "device to host", bytes, hipGetErrorString(e));
+    }
+};
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // the largest element count (C * H * W, H * W) a launcher takes as an int: cdiv rounds it up by at most 255 without leaving the type
@@ -272,10 +319,14 @@ int nct_seq_pull_hold_check(nct_ctx* ctx, const char* who, const void* const* pu
 // field (nullable, [h*w][2] int16 (my, mx)): SPEC §6.4 rule 4 — L_(t-1) and x_prev are read at p + m(p); x_out may then alias x only
 int nctk_seq_blend(nct_ctx* ctx, hipStream_t s, const double* x, const double* x_prev, const uint8_t* lab, const uint8_t* lab_prev, int h, int w, double tau, double sigma,
                    double* x_out, double* tau_map, const int16_t* field = nullptr);
+// the argument checks of nct_seq_blend and nct_seq_blend_mc (one message for both: a blend without a field is the first), in front of their reservations
+int nct_seq_blend_check(nct_ctx* ctx, const void* x, const void* x_prev, const void* lab, const void* lab_prev, int h, int w, const void* x_out, const void* field);
 // SPEC §6.4 rules 1-3: the level's motion field from L_t ([n][3] bytes) and L_(t-1) packed by nctk_seq_pack ([n] words L | a << 8 | b << 16); parent nullable
 int nctk_seq_pack(nct_ctx* ctx, hipStream_t s, const uint8_t* lab, int n, uint32_t* out);
 int nctk_seq_motion(nct_ctx* ctx, hipStream_t s, const uint8_t* lab, const uint32_t* prev_packed, int h, int w, const int16_t* parent, int ph, int pw, int R, int penalty,
                     int16_t* m_out);
+// the argument checks of nct_seq_motion_field[_dev] (`who` names the entry point in the message), in front of the block of the packed image
+int nct_seq_motion_field_check(nct_ctx* ctx, const char* who, const void* lab, const void* lab_prev, int h, int w, const void* parent, int ph, int pw, const void* m_out);
 // SPEC §6.5 rule 3: x_out(p) = x_prev(p + m(p)), the 64-bit words copied, a vector that leaves the grid clamped to it; x_out must not overlap x_prev
 int nctk_seq_warp(nct_ctx* ctx, hipStream_t s, const double* x_prev, int h, int w, const int16_t* field, double* x_out);
 // SPEC §6.7 rule 1: sad = sum_p r(p), changed = #{p : r(p) > threshold}, pixels = h * w, r(p) the three-byte SAD of lab(p) and lab_prev(p + m(p)); field nullable (m = 0).
@@ -298,6 +349,8 @@ int nct_region_snap_params_check(nct_ctx* ctx, const char* who, const nct_region
 // max_seeds): the cell codes of nct_region_select_stages.cell, the kept seeds' cells idx [k_in + k_out] (inside first) and their rows of q, seeds [k_in + k_out][C].
 // nctk_region_score: rule 4 — code (nullable): the seed-cell overwrite by those codes. nctk_sel_stamp: rule 6's stamp in place
 int nctk_feat_quantize(nct_ctx* ctx, hipStream_t s, const float* src_hwc, int16_t* dst, int C, int HW);
+// the argument checks of nct_feat_quantize[_dev] (`who` names the entry point in the message, src_name / dst_name its two arrays, which the two forms call differently)
+int nct_feat_quantize_check(nct_ctx* ctx, const char* who, const void* src, const char* src_name, const void* dst, const char* dst_name, int C, int H, int W);
 int nctk_sel_cells(nct_ctx* ctx, hipStream_t s, const uint8_t* strokes, int h, int w, int tap, unsigned* flags, unsigned long long* pre);
 int nctk_sel_seeds(nct_ctx* ctx, hipStream_t s, const int16_t* q, const unsigned* flags, const unsigned long long* pre, int cells, int C, unsigned n_in, unsigned n_out,
                    unsigned k_in, unsigned k_out, uint8_t* code, int* idx, int16_t* seeds);
@@ -333,6 +386,13 @@ int nct_lut_fit_enqueue_masked(nct_ctx* ctx, const char* what, const uint8_t* d_
 // k_region.hip — source region masks (SPEC §6.11). The single-channel form of nctk_resize_u8c3; the mix of coefficients x ([2][h*w][3]) toward the identity by the level
 // mask (x_out may be x); the compose of a finish's Lab result o_lab with the source (BGR and Lab) by the mask at that size, Lab -> BGR in `form` included
 int nctk_resize_u8c1(nct_ctx* ctx, hipStream_t s, const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw);
+// the argument checks of nct_resize_u8c1[_dev] (`what` names the entry point in the message)
+static inline int nct_resize_u8c1_check(nct_ctx* ctx, const char* what, const void* src, int sh, int sw, const void* dst, int dh, int dw) {
+    NCT_REQUIRE(src && dst, "%s: null pointer", what);
+    NCT_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0 && sh <= 16384 && sw <= 16384 && dh <= 16384 && dw <= 16384 && (long long)sh * sw <= (1LL << 26) && (long long)dh * dw <= (1LL << 26),
+                "%s: size %dx%d -> %dx%d out of range", what, sw, sh, dw, dh);
+    return NCT_OK;
+}
 int nctk_region_mix(nct_ctx* ctx, hipStream_t s, const double* x, const uint8_t* mask, int h, int w, double* x_out);
 // the argument checks of nct_region_compose[_dev] (`what` names the entry point in the message)
 static inline int nct_region_compose_check(nct_ctx* ctx, const char* what, const void* s_bgr, const void* lab_out, const void* mask, size_t npix, const nct_region_params* region, const nct_params* prm,

@@ -25,8 +25,8 @@ static int lut_fit_run(nct_ctx* ctx, const char* what, const uint8_t* d_src, con
     if (!R) { if (!r.alloc(ctx, n3 * 3)) return NCT_ERR_HIP; R = r; }
     if (!D) { if (!d.alloc(ctx, n3 * 3)) return NCT_ERR_HIP; D = d; }
     if (d_mask) {
-        DevBuf<uint64_t> kept(ctx, 1);
-        if (!kept.ok()) return NCT_ERR_HIP;
+        DevBuf<uint64_t> kept;
+        if (!kept.alloc(ctx, 1)) return NCT_ERR_HIP;
         NCT_TRY(nctk_lut_splat_masked(ctx, s, d_src, d_res, d_mask, (long)npix, N, W, R, kept));
         uint64_t nkept = 0;
         NCT_D2H(&nkept, kept, sizeof nkept);
@@ -59,22 +59,7 @@ void nct_lut_params_default(nct_lut_params* p) {
 }
 
 int nct_lut_fit(nct_ctx* ctx, const uint8_t* src_bgr, const uint8_t* res_bgr, size_t npix, const nct_lut_params* prm, float* lut_out, nct_lut_stages* stages) {
-    NCT_CTX_ENTER();
-    NCT_TRY(nct_lut_fit_check(ctx, "lut_fit", src_bgr, res_bgr, npix, prm, lut_out));
-    const size_t n3 = (size_t)prm->size * prm->size * prm->size;
-    DevBuf<uint8_t> ds(ctx, npix * 3), dr(ctx, npix * 3);
-    DevBuf<float> dl(ctx, n3 * 3);
-    DevBuf<uint64_t> w(ctx, n3); DevBuf<int64_t> r(ctx, n3 * 3); DevBuf<double> d(ctx, n3 * 3);
-    if (!ds.ok() || !dr.ok() || !dl.ok() || !w.ok() || !r.ok() || !d.ok()) return NCT_ERR_HIP;
-    NCT_H2D(ds, src_bgr, npix * 3); NCT_H2D(dr, res_bgr, npix * 3);
-    const nct_lut_stages dst{w, r, d};
-    NCT_TRY(nct_lut_fit_enqueue(ctx, ds, dr, npix, prm, dl, &dst));
-    NCT_D2H(lut_out, dl, sizeof(float) * n3 * 3);
-    if (stages && stages->weight) NCT_D2H(stages->weight, w, sizeof(uint64_t) * n3);
-    if (stages && stages->resid) NCT_D2H(stages->resid, r, sizeof(int64_t) * n3 * 3);
-    if (stages && stages->disp) NCT_D2H(stages->disp, d, sizeof(double) * n3 * 3);
-    NCT_SYNC();
-    return NCT_OK;
+    return nct_lut_fit_masked(ctx, src_bgr, res_bgr, nullptr, npix, prm, lut_out, stages);
 }
 
 int nct_lut_fit_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, const uint8_t* d_res_bgr, size_t npix, const nct_lut_params* prm, float* d_lut_out, nct_lut_stages* d_stages) {
@@ -85,23 +70,20 @@ int nct_lut_fit_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, const uint8_t* d_res
 
 // SPEC §6.11 rule 7: the fit over the pixels with mask >= 128; mask NULL: nct_lut_fit
 int nct_lut_fit_masked(nct_ctx* ctx, const uint8_t* src_bgr, const uint8_t* res_bgr, const uint8_t* mask, size_t npix, const nct_lut_params* prm, float* lut_out, nct_lut_stages* stages) {
-    if (!mask) return nct_lut_fit(ctx, src_bgr, res_bgr, npix, prm, lut_out, stages);
     NCT_CTX_ENTER();
-    NCT_TRY(nct_lut_fit_check(ctx, "lut_fit_masked", src_bgr, res_bgr, npix, prm, lut_out));
+    const char* what = mask ? "lut_fit_masked" : "lut_fit";
+    NCT_TRY(nct_lut_fit_check(ctx, what, src_bgr, res_bgr, npix, prm, lut_out));
     const size_t n3 = (size_t)prm->size * prm->size * prm->size;
-    DevBuf<uint8_t> ds(ctx, npix * 3), dr(ctx, npix * 3), dm(ctx, npix);
-    DevBuf<float> dl(ctx, n3 * 3);
-    DevBuf<uint64_t> w(ctx, n3); DevBuf<int64_t> r(ctx, n3 * 3); DevBuf<double> d(ctx, n3 * 3);
-    if (!ds.ok() || !dr.ok() || !dm.ok() || !dl.ok() || !w.ok() || !r.ok() || !d.ok()) return NCT_ERR_HIP;
-    NCT_H2D(ds, src_bgr, npix * 3); NCT_H2D(dr, res_bgr, npix * 3); NCT_H2D(dm, mask, npix);
+    HostCall hc(ctx);
+    const uint8_t *ds = hc.in(src_bgr, npix * 3), *dr = hc.in(res_bgr, npix * 3), *dm = hc.in(mask, npix);
+    float* dl = hc.out(lut_out, n3 * 3);
+    // the three stages are computed in blocks of this call and come down where they are asked for
+    uint64_t* w = hc.scratch<uint64_t>(n3); int64_t* r = hc.scratch<int64_t>(n3 * 3); double* d = hc.scratch<double>(n3 * 3);
+    if (stages) { hc.get(stages->weight, w, n3); hc.get(stages->resid, r, n3 * 3); hc.get(stages->disp, d, n3 * 3); }
+    NCT_TRY(hc.ready());
     const nct_lut_stages dst{w, r, d};
-    NCT_TRY(nct_lut_fit_enqueue_masked(ctx, "lut_fit_masked", ds, dr, dm, npix, prm, dl, &dst));
-    NCT_D2H(lut_out, dl, sizeof(float) * n3 * 3);
-    if (stages && stages->weight) NCT_D2H(stages->weight, w, sizeof(uint64_t) * n3);
-    if (stages && stages->resid) NCT_D2H(stages->resid, r, sizeof(int64_t) * n3 * 3);
-    if (stages && stages->disp) NCT_D2H(stages->disp, d, sizeof(double) * n3 * 3);
-    NCT_SYNC();
-    return NCT_OK;
+    NCT_TRY(lut_fit_run(ctx, what, ds, dr, dm, npix, prm, dl, &dst));
+    return hc.finish();
 }
 
 int nct_lut_fit_masked_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, const uint8_t* d_res_bgr, const uint8_t* d_mask, size_t npix, const nct_lut_params* prm, float* d_lut_out,
@@ -117,14 +99,13 @@ int nct_lut_apply(nct_ctx* ctx, const float* lut, int size, const uint8_t* bgr, 
     NCT_TRY(lut_apply_check(ctx, "lut_apply", lut, size, bgr, npix, out_bgr));
     const size_t n = (size_t)size * size * size * 3;
     for (size_t i = 0; i < n; ++i) NCT_REQUIRE(std::isfinite(lut[i]), "lut_apply: the table has a non-finite entry (node %zu, channel %zu)", i / 3, i % 3);
-    DevBuf<float> dl(ctx, n);
-    DevBuf<uint8_t> di(ctx, npix * 3), dout(ctx, npix * 3);
-    if (!dl.ok() || !di.ok() || !dout.ok()) return NCT_ERR_HIP;
-    NCT_H2D(dl, lut, sizeof(float) * n); NCT_H2D(di, bgr, npix * 3);
+    HostCall hc(ctx);
+    const float* dl = hc.in(lut, n);
+    const uint8_t* di = hc.in(bgr, npix * 3);
+    uint8_t* dout = hc.out(out_bgr, npix * 3);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_lut_apply(ctx, ctx->stream, dl, size, di, (long)npix, dout));
-    NCT_D2H(out_bgr, dout, npix * 3);
-    NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 int nct_lut_apply_dev(nct_ctx* ctx, const float* d_lut, int size, const uint8_t* d_bgr, size_t npix, uint8_t* d_out_bgr) {

@@ -24,17 +24,16 @@ static int model_rows_of(nct_ctx* ctx, const char* who, const uint8_t* src_bgr, 
     NCT_TRY(select_check(ctx, who, src_bgr, h, w, strokes, params, /* no matte is written */ src_bgr, &p));
     const size_t N = (size_t)h * w;
     const int C = kTapC[p.tap - 1];
-    DevBuf<uint8_t> ds(ctx, N * 3), dt(ctx, N);
-    if (!ds.ok() || !dt.ok()) return NCT_ERR_HIP;
-    NCT_H2D(ds, src_bgr, N * 3); NCT_H2D(dt, strokes, N);
-    select_rows r;
+    select_rows r;                                               // outlives the call's wait: its rows come down in finish()
+    HostCall hc(ctx);
+    const uint8_t *ds = hc.in(src_bgr, N * 3), *dt = hc.in(strokes, N);
+    NCT_TRY(hc.ready());
     NCT_TRY(select_seed_rows(ctx, who, ds, h, w, dt, p, nullptr, false, r));
     rows_in.resize((size_t)r.k_in * C); rows_out.resize((size_t)r.k_out * C);
-    NCT_D2H(rows_in.data(), (int16_t*)r.seeds, sizeof(int16_t) * rows_in.size());
-    if (r.k_out) NCT_D2H(rows_out.data(), (int16_t*)r.seeds + rows_in.size(), sizeof(int16_t) * rows_out.size());
-    NCT_SYNC();
+    hc.get(rows_in.data(), (const int16_t*)r.seeds, rows_in.size());
+    if (r.k_out) hc.get(rows_out.data(), (const int16_t*)r.seeds + rows_in.size(), rows_out.size());
     *tap = p.tap;
-    return NCT_OK;
+    return hc.finish();
 }
 
 static int refind_params_check(nct_ctx* ctx, const char* who, const nct_region_refind_params* params, nct_region_refind_params* p) {
@@ -69,19 +68,19 @@ static int apply_enqueue(nct_ctx* ctx, const nct_region_model* M, const uint8_t*
     const int n_in = (int)(M->in.size() / C), n_out = (int)(M->out.size() / C);
     const size_t N = (size_t)h * w;
     // the model's rows go up first and are waited for, while the stream is still short: the model may be changed or freed as soon as the call returns
-    DevBuf<int16_t> rows(ctx, M->in.size() + M->out.size());
-    if (!rows.ok()) return NCT_ERR_HIP;
+    DevBuf<int16_t> rows;
+    if (!rows.alloc(ctx, M->in.size() + M->out.size())) return NCT_ERR_HIP;
     NCT_H2D(rows, M->in.data(), sizeof(int16_t) * M->in.size());
     if (n_out) NCT_H2D((int16_t*)rows + M->in.size(), M->out.data(), sizeof(int16_t) * M->out.size());
     NCT_SYNC();
     // A1
-    DevBuf<int16_t> q(ctx, (size_t)cells * C);
-    if (!q.ok()) return NCT_ERR_HIP;
+    DevBuf<int16_t> q;
+    if (!q.alloc(ctx, (size_t)cells * C)) return NCT_ERR_HIP;
     NCT_TRY(select_quantised_tap(ctx, s, d_src, h, w, tap, q));
     if (st) NCT_TRY(dbg_copy(ctx, s, st->q, q, (size_t)cells * C));
     // A2: no cell of this image is a seed cell, nothing is overwritten
-    DevBuf<uint8_t> m(ctx, cells);
-    if (!m.ok()) return NCT_ERR_HIP;
+    DevBuf<uint8_t> m;
+    if (!m.alloc(ctx, cells)) return NCT_ERR_HIP;
     NCT_TRY(nctk_region_score(ctx, s, q, cells, C, rows, n_in, (int16_t*)rows + M->in.size(), n_out, p.sharpness, p.floor_permille, nullptr, m));
     if (st) NCT_TRY(dbg_copy(ctx, s, st->score, m, (size_t)cells));
     // A3 and A4: every snap pass runs out of place between d_out and one block of scratch; the re-found matte goes where the last pass ends in d_out
@@ -107,13 +106,13 @@ int seq_refind_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, co
     const size_t N = (size_t)H * W;
     const nct_region_refind_params& p = q->model_p;
     // A1 and A2 on the tap the frame's forward wrote
-    DevBuf<int16_t> rows(ctx, (size_t)cells * C);
-    DevBuf<uint8_t> m(ctx, cells);
-    if (!rows.ok() || !m.ok()) return NCT_ERR_HIP;
+    DevBuf<int16_t> rows;
+    DevBuf<uint8_t> m;
+    if (!rows.alloc(ctx, (size_t)cells * C) || !m.alloc(ctx, cells)) return NCT_ERR_HIP;
     NCT_TRY(nctk_feat_quantize(ctx, s, tap_hwc, rows, C, cells));
     NCT_TRY(nctk_region_score(ctx, s, rows, cells, C, q->model_rows, q->model_n_in, (int16_t*)q->model_rows + (size_t)q->model_n_in * C, q->model_n_out, p.sharpness, p.floor_permille, nullptr, m));
     // rule S3: the matte the track step left is the prior, unless the sequence has no state — the old shot's matte is not evidence
-    const bool had = P->mask.ok(), prior = had && q->frames > 0;
+    const bool had = P->mask != nullptr, prior = had && q->frames > 0;
     if (!P->mask.reserve(ctx, (size_t)h * w)) return NCT_ERR_HIP;
     if (full && !P->full_mask.reserve(ctx, N)) return NCT_ERR_HIP;
     DevBuf<uint8_t>& matte = full ? P->full_mask : P->mask;
@@ -206,14 +205,13 @@ int nct_region_refind(nct_ctx* ctx, const uint8_t* score, int ht, int wt, const 
     NCT_CTX_ENTER();
     NCT_TRY(nct_region_refind_check(ctx, "region_refind", score, ht, wt, H, W, margin, out));
     const size_t N = (size_t)H * W, n = (size_t)ht * wt;
-    DevBuf<uint8_t> dm(ctx, n), dp, dout(ctx, N);
-    if (!dm.ok() || !dout.ok() || (prior && !dp.alloc(ctx, N))) return NCT_ERR_HIP;
-    NCT_H2D(dm, score, n);
-    if (prior) NCT_H2D(dp, prior, N);
-    NCT_TRY(nctk_region_refind(ctx, ctx->stream, dm, ht, wt, prior ? (uint8_t*)dp : nullptr, H, W, margin, dout));
-    NCT_D2H(out, dout, N);
-    NCT_SYNC();
-    return NCT_OK;
+    HostCall hc(ctx);
+    const uint8_t* dm = hc.in(score, n);
+    uint8_t* dout = hc.out(out, N);
+    const uint8_t* dp = hc.in(prior, N);
+    NCT_TRY(hc.ready());
+    NCT_TRY(nctk_region_refind(ctx, ctx->stream, dm, ht, wt, dp, H, W, margin, dout));
+    return hc.finish();
 }
 
 int nct_region_refind_dev(nct_ctx* ctx, const uint8_t* d_score, int ht, int wt, const uint8_t* d_prior, int H, int W, int margin, uint8_t* d_out) {
@@ -243,14 +241,13 @@ int nct_region_model_apply(nct_ctx* ctx, const nct_region_model* model, const ui
     nct_region_refind_params p;
     NCT_TRY(apply_check(ctx, "region_model_apply", model, src_bgr, h, w, params, mask_out, &p));
     const size_t N = (size_t)h * w;
-    DevBuf<uint8_t> ds(ctx, N * 3), dp, dm(ctx, N);
-    if (!ds.ok() || !dm.ok() || (prior && !dp.alloc(ctx, N))) return NCT_ERR_HIP;
-    NCT_H2D(ds, src_bgr, N * 3);
-    if (prior) NCT_H2D(dp, prior, N);
-    NCT_TRY(apply_enqueue(ctx, model, ds, h, w, prior ? (uint8_t*)dp : nullptr, p, dm, stages));
-    NCT_D2H(mask_out, dm, N);
-    NCT_SYNC();
-    return NCT_OK;
+    HostCall hc(ctx);
+    const uint8_t* ds = hc.in(src_bgr, N * 3);
+    uint8_t* dm = hc.out(mask_out, N);
+    const uint8_t* dp = hc.in(prior, N);
+    NCT_TRY(hc.ready());
+    NCT_TRY(apply_enqueue(ctx, model, ds, h, w, dp, p, dm, stages));
+    return hc.finish();
 }
 
 int nct_region_model_apply_dev(nct_ctx* ctx, const nct_region_model* model, const uint8_t* d_src_bgr, int h, int w, const uint8_t* d_prior, const nct_region_refind_params* params,
@@ -271,8 +268,8 @@ int nct_pair_apply_region_model(nct_ctx* ctx, const nct_region_model* model, con
     if (P && P->seq) return ctx->fail(NCT_ERR_STATE, "pair_apply_region_model: a sequence is open on this context (nct_seq_end closes it)");
     if (!P || !P->src || P->sh < 1) return ctx->fail(NCT_ERR_STATE, "pair_apply_region_model: no source uploaded (nct_pair_upload or nct_multi_upload first)");
     NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "pair_apply_region_model: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
-    DevBuf<uint8_t> dm(ctx, (size_t)P->sh * P->sw);
-    if (!dm.ok()) return NCT_ERR_HIP;
+    DevBuf<uint8_t> dm;
+    if (!dm.alloc(ctx, (size_t)P->sh * P->sw)) return NCT_ERR_HIP;
     nct_region_refind_params p;
     NCT_TRY(apply_check(ctx, "pair_apply_region_model", model, P->src, P->sh, P->sw, params, (uint8_t*)dm, &p));
     NCT_TRY(apply_enqueue(ctx, model, P->src, P->sh, P->sw, nullptr, p, dm, nullptr));
@@ -285,15 +282,15 @@ int nct_seq_set_region_model(nct_ctx* ctx, const nct_region_model* model, const 
     NCT_OPEN_SEQ(P, "seq_set_region_model");
     seq_state* q = P->seq;
     if (!model) {
-        if (q->model_rows.ok()) { NCT_SYNC(); q->model_rows.reset(); }
+        if (q->model_rows) { NCT_SYNC(); q->model_rows.reset(); }
         return NCT_OK;
     }
     NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "seq_set_region_model: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
     nct_region_refind_params p;
     NCT_TRY(refind_params_check(ctx, "seq_set_region_model", params, &p));
     // the rows go up once, into a block the sequence keeps; the wait also covers the last frame's use of the rows they replace
-    DevBuf<int16_t> rows(ctx, model->in.size() + model->out.size());
-    if (!rows.ok()) return NCT_ERR_HIP;
+    DevBuf<int16_t> rows;
+    if (!rows.alloc(ctx, model->in.size() + model->out.size())) return NCT_ERR_HIP;
     NCT_H2D(rows, model->in.data(), sizeof(int16_t) * model->in.size());
     if (!model->out.empty()) NCT_H2D((int16_t*)rows + model->in.size(), model->out.data(), sizeof(int16_t) * model->out.size());
     NCT_SYNC();

@@ -60,8 +60,8 @@ int select_seed_rows(nct_ctx* ctx, const char* who, const uint8_t* d_src, int h,
 // rules 1 and 2: the forward stops at the tap, whose own epilogue writes it channel-last; N1 is fused into the quantise pass. q: [cells][C], the caller's
 int select_quantised_tap(nct_ctx* ctx, hipStream_t s, const uint8_t* d_src, int h, int w, int tap, int16_t* q) {
     const int C = kTapC[tap - 1], cells = (((h - 1) >> (tap - 1)) + 1) * (((w - 1) >> (tap - 1)) + 1);
-    DevBuf<float> feat(ctx, (size_t)cells * C);
-    if (!feat.ok()) return NCT_ERR_HIP;
+    DevBuf<float> feat;
+    if (!feat.alloc(ctx, (size_t)cells * C)) return NCT_ERR_HIP;
     float* taps[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     taps[tap - 1] = feat;
     NCT_TRY(nctk_vgg19_forward(ctx, s, d_src, h, w, 3 * w, tap, nullptr, nullptr, taps));
@@ -99,6 +99,14 @@ static int select_enqueue(nct_ctx* ctx, const char* who, const uint8_t* d_src, i
     return NCT_OK;
 }
 
+int nct_feat_quantize_check(nct_ctx* ctx, const char* who, const void* src, const char* src_name, const void* dst, const char* dst_name, int C, int H, int W) {
+    NCT_REQUIRE(src, "%s: null %s", who, src_name);
+    NCT_REQUIRE(dst, "%s: null %s", who, dst_name);
+    NCT_REQUIRE(C > 0 && (C & 3) == 0 && C <= 4096, "%s: C must be a positive multiple of 4, at most 4096 (got %d)", who, C);
+    NCT_REQUIRE(H >= 1 && W >= 1 && H <= 4096 && W <= 4096, "%s: grid %dx%d out of range", who, W, H);
+    return NCT_OK;
+}
+
 extern "C" {
 
 int nct_region_select_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, int h, int w, const uint8_t* d_strokes, const nct_region_select_params* params, uint8_t* d_mask_out) {
@@ -114,40 +122,32 @@ int nct_region_select(nct_ctx* ctx, const uint8_t* src_bgr, int h, int w, const 
     nct_region_select_params p;
     NCT_TRY(select_check(ctx, "region_select", src_bgr, h, w, strokes, params, mask_out, &p));
     const size_t N = (size_t)h * w;
-    DevBuf<uint8_t> ds(ctx, N * 3), dt(ctx, N), dm(ctx, N);
-    if (!ds.ok() || !dt.ok() || !dm.ok()) return NCT_ERR_HIP;
-    NCT_H2D(ds, src_bgr, N * 3); NCT_H2D(dt, strokes, N);
+    HostCall hc(ctx);
+    const uint8_t *ds = hc.in(src_bgr, N * 3), *dt = hc.in(strokes, N);
+    uint8_t* dm = hc.out(mask_out, N);
+    NCT_TRY(hc.ready());
     NCT_TRY(select_enqueue(ctx, "region_select", ds, h, w, dt, p, dm, stages));
-    NCT_D2H(mask_out, dm, N);
-    NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 // rule 2 alone on a host blob in Caffe's layout: up, to channel-last, one k_feat_quantize launch, the rows down
 int nct_feat_quantize(nct_ctx* ctx, const float* src_chw, int16_t* dst, int C, int H, int W) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(src_chw, "feat_quantize: null src_chw");
-    NCT_REQUIRE(dst, "feat_quantize: null dst");
-    NCT_REQUIRE(C > 0 && (C & 3) == 0 && C <= 4096, "feat_quantize: C must be a positive multiple of 4, at most 4096 (got %d)", C);
-    NCT_REQUIRE(H >= 1 && W >= 1 && H <= 4096 && W <= 4096, "feat_quantize: grid %dx%d out of range", W, H);
+    NCT_TRY(nct_feat_quantize_check(ctx, "feat_quantize", src_chw, "src_chw", dst, "dst", C, H, W));
     const int HW = H * W; const size_t n = (size_t)C * HW;
-    DevBuf<float> t(ctx, n), x(ctx, n);
-    DevBuf<int16_t> y(ctx, n);
-    if (!t.ok() || !x.ok() || !y.ok()) return NCT_ERR_HIP;
-    NCT_H2D(t, src_chw, sizeof(float) * n);
+    HostCall hc(ctx);
+    const float* t = hc.in(src_chw, n);
+    float* x = hc.scratch<float>(n);
+    int16_t* y = hc.out(dst, n);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_chw_to_hwc(ctx, ctx->stream, t, x, C, HW));
     NCT_TRY(nctk_feat_quantize(ctx, ctx->stream, x, y, C, HW));
-    NCT_D2H(dst, y, sizeof(int16_t) * n);
-    NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 int nct_feat_quantize_dev(nct_ctx* ctx, const float* d_src_hwc, int16_t* d_dst, int C, int H, int W) {
     NCT_CTX_ENTER();
-    NCT_REQUIRE(d_src_hwc, "feat_quantize_dev: null d_src_hwc");
-    NCT_REQUIRE(d_dst, "feat_quantize_dev: null d_dst");
-    NCT_REQUIRE(C > 0 && (C & 3) == 0 && C <= 4096, "feat_quantize_dev: C must be a positive multiple of 4, at most 4096 (got %d)", C);
-    NCT_REQUIRE(H >= 1 && W >= 1 && H <= 4096 && W <= 4096, "feat_quantize_dev: grid %dx%d out of range", W, H);
+    NCT_TRY(nct_feat_quantize_check(ctx, "feat_quantize_dev", d_src_hwc, "d_src_hwc", d_dst, "d_dst", C, H, W));
     return nctk_feat_quantize(ctx, ctx->stream, d_src_hwc, d_dst, C, H * W);
 }
 
@@ -156,16 +156,13 @@ int nct_region_score(nct_ctx* ctx, const int16_t* q, int cells, int C, const int
                      uint8_t* score_out) {
     NCT_CTX_ENTER();
     NCT_TRY(nct_region_score_check(ctx, "region_score", q, cells, C, seeds_in, n_in, seeds_out, n_out, sharpness, floor_permille, score_out));
-    DevBuf<int16_t> dq(ctx, (size_t)cells * C), di(ctx, (size_t)n_in * C), dn(ctx, (size_t)n_out * C);
-    DevBuf<uint8_t> dm(ctx, cells);
-    if (!dq.ok() || !di.ok() || !dn.ok() || !dm.ok()) return NCT_ERR_HIP;
-    NCT_H2D(dq, q, sizeof(int16_t) * (size_t)cells * C);
-    NCT_H2D(di, seeds_in, sizeof(int16_t) * (size_t)n_in * C);
-    if (n_out > 0) NCT_H2D(dn, seeds_out, sizeof(int16_t) * (size_t)n_out * C);
+    HostCall hc(ctx);
+    const int16_t *dq = hc.in(q, (size_t)cells * C), *di = hc.in(seeds_in, (size_t)n_in * C);
+    const int16_t* dn = n_out > 0 ? hc.in(seeds_out, (size_t)n_out * C) : nullptr;          // no outside rows: the launcher never reads the list
+    uint8_t* dm = hc.out(score_out, cells);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_region_score(ctx, ctx->stream, dq, cells, C, di, n_in, dn, n_out, sharpness, floor_permille, nullptr, dm));
-    NCT_D2H(score_out, dm, (size_t)cells);
-    NCT_SYNC();
-    return NCT_OK;
+    return hc.finish();
 }
 
 int nct_region_score_dev(nct_ctx* ctx, const int16_t* d_q, int cells, int C, const int16_t* d_seeds_in, int n_in, const int16_t* d_seeds_out, int n_out, int sharpness,
@@ -200,8 +197,8 @@ int nct_pair_select_region(nct_ctx* ctx, const uint8_t* strokes, const nct_regio
     if (!P || !P->src || P->sh < 1) return ctx->fail(NCT_ERR_STATE, "pair_select_region: no source uploaded (nct_pair_upload or nct_multi_upload first)");
     NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "pair_select_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
     const size_t N = (size_t)P->sh * P->sw;
-    DevBuf<uint8_t> dt(ctx, N), dm(ctx, N);
-    if (!dt.ok() || !dm.ok()) return NCT_ERR_HIP;
+    DevBuf<uint8_t> dt, dm;
+    if (!dt.alloc(ctx, N) || !dm.alloc(ctx, N)) return NCT_ERR_HIP;
     nct_region_select_params p;
     NCT_TRY(select_check(ctx, "pair_select_region", P->src, P->sh, P->sw, strokes, params, (uint8_t*)dm, &p));
     NCT_H2D(dt, strokes, N);
@@ -218,8 +215,8 @@ int nct_seq_select_region(nct_ctx* ctx, const uint8_t* frame_bgr, const uint8_t*
     NCT_REQUIRE(!region || region->protect == 0 || region->protect == 1, "seq_select_region: region protect must be 0 or 1 (got %d)", region ? region->protect : 0);
     NCT_REQUIRE(frame_bgr, "seq_select_region: null frame_bgr");
     const size_t N = (size_t)P->sh * P->sw;
-    DevBuf<uint8_t> ds(ctx, N * 3), dt(ctx, N), dm(ctx, N);
-    if (!ds.ok() || !dt.ok() || !dm.ok()) return NCT_ERR_HIP;
+    DevBuf<uint8_t> ds, dt, dm;
+    if (!ds.alloc(ctx, N * 3) || !dt.alloc(ctx, N) || !dm.alloc(ctx, N)) return NCT_ERR_HIP;
     nct_region_select_params p;
     NCT_TRY(select_check(ctx, "seq_select_region", frame_bgr, P->sh, P->sw, strokes, params, (uint8_t*)dm, &p));
     NCT_H2D(ds, frame_bgr, N * 3); NCT_H2D(dt, strokes, N);

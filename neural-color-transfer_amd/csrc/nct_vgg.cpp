@@ -61,8 +61,8 @@ static int upload_layer(nct_ctx* ctx, int i, const float* w, const float* b) {
     const size_t nw = (size_t)kCout[i] * kCin[i] * 9;
     if (!v->wp[i]) { NCT_HIP(hipMalloc(&v->wp[i], sizeof(float) * (size_t)cin_pad * 9 * kCout[i])); v->bytes += sizeof(float) * (size_t)cin_pad * 9 * kCout[i]; }
     if (!v->bias[i]) { NCT_HIP(hipMalloc(&v->bias[i], sizeof(float) * kCout[i])); v->bytes += sizeof(float) * kCout[i]; }
-    DevBuf<float> tmp(ctx, nw);
-    if (!tmp.ok()) return NCT_ERR_HIP;
+    DevBuf<float> tmp;
+    if (!tmp.alloc(ctx, nw)) return NCT_ERR_HIP;
     NCT_HIP(hipMemcpyAsync(tmp, w, sizeof(float) * nw, hipMemcpyHostToDevice, ctx->stream));
     NCT_TRY(nctk_pack_weights(ctx, ctx->stream, tmp, v->wp[i], kCout[i], kCin[i], cin_pad));
     NCT_HIP(hipMemcpyAsync(v->bias[i], b, sizeof(float) * kCout[i], hipMemcpyHostToDevice, ctx->stream));
@@ -380,8 +380,8 @@ static int vgg19_forward_impl(nct_ctx* ctx, hipStream_t s, const uint8_t* d_bgr,
     NCT_REQUIRE(deepest_tap >= 1 && deepest_tap <= 5, "vgg19: deepest_tap must be 1..5");
     NCT_REQUIRE(H >= 2 && W >= 2 && H < 4096 && W < 4096, "vgg19: image size %dx%d out of range", W, H);
     const size_t big = (size_t)64 * H * W;
-    DevBuf<float> pp0(ctx, big), pp1(ctx, big);
-    if (!pp0.ok() || !pp1.ok()) return NCT_ERR_HIP;
+    DevBuf<float> pp0, pp1;
+    if (!pp0.alloc(ctx, big) || !pp1.alloc(ctx, big)) return NCT_ERR_HIP;
     float* pp[2] = {pp0, pp1};
     int h = H, w = W;
     NCT_TRY(nctk_vgg_preprocess(ctx, s, d_bgr, stride, pp[0], H, W));
@@ -420,8 +420,8 @@ int nctk_vgg19_forward_pair(nct_ctx* ctx, hipStream_t s, const uint8_t* d_bgr1, 
                             const uint8_t* d_bgr2, int H2, int W2, int stride2, float* const* taps_hwc2) {
     NCT_REQUIRE(taps_hwc1 && taps_hwc2 && taps_hwc1[4] && taps_hwc2[4], "vgg19 pair: both conv5_1 maps are needed");
     auto pooled4 = [](int n) { for (int k = 0; k < 4; ++k) n = (n - 1) / 2 + 1; return n; };
-    DevBuf<float> p1(ctx, (size_t)512 * pooled4(H1) * pooled4(W1)), p2(ctx, (size_t)512 * pooled4(H2) * pooled4(W2));
-    if (!p1.ok() || !p2.ok()) return NCT_ERR_HIP;
+    DevBuf<float> p1, p2;
+    if (!p1.alloc(ctx, (size_t)512 * pooled4(H1) * pooled4(W1)) || !p2.alloc(ctx, (size_t)512 * pooled4(H2) * pooled4(W2))) return NCT_ERR_HIP;
     int h1 = 0, w1 = 0, h2 = 0, w2 = 0;
     NCT_TRY(vgg19_forward_impl(ctx, s, d_bgr1, H1, W1, stride1, 5, nullptr, nullptr, taps_hwc1, p1, &h1, &w1));
     NCT_TRY(vgg19_forward_impl(ctx, s, d_bgr2, H2, W2, stride2, 5, nullptr, nullptr, taps_hwc2, p2, &h2, &w2));
@@ -436,26 +436,19 @@ int nct_vgg19_features(nct_ctx* ctx, const uint8_t* bgr, int h, int w, int strid
     NCT_CTX_ENTER();
     NCT_REQUIRE(bgr && h > 0 && w > 0 && stride >= 3 * w, "vgg19_features: bad image arguments");
     NCT_REQUIRE(deepest_tap >= 1 && deepest_tap <= 5, "vgg19_features: deepest_tap must be 1..5");
-    DevBuf<uint8_t> img(ctx, (size_t)stride * h);
-    if (!img.ok()) return NCT_ERR_HIP;
-    NCT_HIP(hipMemcpyAsync(img, bgr, (size_t)stride * h, hipMemcpyHostToDevice, ctx->stream));
+    HostCall hc(ctx);
+    const uint8_t* img = hc.in(bgr, (size_t)stride * h);
     // tap buffers
     int hh = h, ww = w; size_t sizes[5]; int td[5][3];
     for (int t = 0; t < 5; ++t) { const int C = kCout[kTapConv[t]]; td[t][0] = C; td[t][1] = hh; td[t][2] = ww; sizes[t] = (size_t)C * hh * ww; hh = (hh - 1) / 2 + 1; ww = (ww - 1) / 2 + 1; }
     float* d_taps[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    DevBuf<float> bufs[5];
-    int rc = 0;
-    for (int t = 0; t < deepest_tap && rc == 0; ++t)
-        if (taps_chw && taps_chw[t]) { if (!bufs[t].alloc(ctx, sizes[t])) rc = NCT_ERR_HIP; d_taps[t] = bufs[t]; }
+    for (int t = 0; t < deepest_tap; ++t)
+        if (taps_chw) d_taps[t] = hc.out(taps_chw[t], sizes[t]);
     int ldims[15] = {0};
+    int rc = hc.ready();
     if (rc == 0) rc = nctk_vgg19_forward(ctx, ctx->stream, img, h, w, stride, deepest_tap, d_taps, ldims);
-    if (rc == 0)
-        for (int t = 0; t < deepest_tap; ++t)
-            if (d_taps[t]) { hipError_t e = hipMemcpyAsync(taps_chw[t], d_taps[t], sizeof(float) * sizes[t], hipMemcpyDeviceToHost, ctx->stream);
-                             if (e != hipSuccess) { rc = ctx->fail(NCT_ERR_HIP, "D2H of tap %d failed: %s", t + 1, hipGetErrorString(e)); break; } }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (rc == 0 && e != hipSuccess) rc = ctx->fail(NCT_ERR_HIP, "vgg19_features: %s", hipGetErrorString(e));
-    if (dims) for (int t = 0; t < 5; ++t) for (int k = 0; k < 3; ++k) dims[t * 3 + k] = t < deepest_tap ? td[t][k] : 0;
+    if (rc == 0) rc = hc.finish();
+    if (dims) for (int t = 0; t < 5; ++t) for (int k = 0; k < 3; ++k) dims[t * 3 + k] = t < deepest_tap ? td[t][k] : 0;          // the sizes, whatever became of the call
     return rc;
 }
 
@@ -467,30 +460,30 @@ int nct_conv3x3_relu(nct_ctx* ctx, const float* in_chw, int Cin, int H, int W, c
     NCT_REQUIRE(Cin >= 1 && (Cout & 63) == 0 && H >= 2 && W >= 2, "conv3x3_relu: need Cout %% 64 == 0, H,W >= 2");
     const int cin_pad = (Cin + 1) & ~1;
     const size_t hw = (size_t)H * W;
-    DevBuf<float> din(ctx, cin_pad * hw), dw(ctx, (size_t)Cout * Cin * 9), dwp(ctx, (size_t)cin_pad * 9 * Cout), db(ctx, Cout), dout(ctx, Cout * hw);
-    if (!din.ok() || !dw.ok() || !dwp.ok() || !db.ok() || !dout.ok()) return NCT_ERR_HIP;
+    HostCall hc(ctx);
+    float* din = hc.scratch<float>(cin_pad * hw);                // Cin planes and, for an odd Cin, the zero plane behind them
+    const float* dw = hc.in(weights, (size_t)Cout * Cin * 9);
+    float* dwp = hc.scratch<float>((size_t)cin_pad * 9 * Cout);
+    const float* db = hc.in(bias, Cout);
+    float* dout = hc.out(out_chw, Cout * hw);
+    NCT_TRY(hc.ready());
     NCT_HIP(hipMemsetAsync(din, 0, sizeof(float) * cin_pad * hw, ctx->stream));
-    NCT_HIP(hipMemcpyAsync(din, in_chw, sizeof(float) * Cin * hw, hipMemcpyHostToDevice, ctx->stream));
-    NCT_HIP(hipMemcpyAsync(dw, weights, sizeof(float) * (size_t)Cout * Cin * 9, hipMemcpyHostToDevice, ctx->stream));
-    NCT_HIP(hipMemcpyAsync(db, bias, sizeof(float) * Cout, hipMemcpyHostToDevice, ctx->stream));
+    hc.put(din, in_chw, Cin * hw);
     NCT_TRY(nctk_pack_weights(ctx, ctx->stream, dw, dwp, Cout, Cin, cin_pad));
     NCT_TRY(nctk_conv3x3(ctx, ctx->stream, din, dwp, db, dout, cin_pad, Cout, H, W, relu, 0));
-    NCT_HIP(hipMemcpyAsync(out_chw, dout, sizeof(float) * Cout * hw, hipMemcpyDeviceToHost, ctx->stream));
-    NCT_HIP(hipStreamSynchronize(ctx->stream));
-    return NCT_OK;
+    return hc.finish();
 }
 
 int nct_maxpool2x2(nct_ctx* ctx, const float* in_chw, int C, int H, int W, float* out_chw) {
     NCT_CTX_ENTER();
     NCT_REQUIRE(in_chw && out_chw && C >= 1 && H >= 2 && W >= 2, "maxpool2x2: bad arguments");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    DevBuf<float> din(ctx, (size_t)C * H * W), dout(ctx, (size_t)C * Ho * Wo);
-    if (!din.ok() || !dout.ok()) return NCT_ERR_HIP;
-    NCT_HIP(hipMemcpyAsync(din, in_chw, sizeof(float) * C * H * W, hipMemcpyHostToDevice, ctx->stream));
+    HostCall hc(ctx);
+    const float* din = hc.in(in_chw, (size_t)C * H * W);
+    float* dout = hc.out(out_chw, (size_t)C * Ho * Wo);
+    NCT_TRY(hc.ready());
     NCT_TRY(nctk_maxpool2x2(ctx, ctx->stream, din, dout, C, H, W));
-    NCT_HIP(hipMemcpyAsync(out_chw, dout, sizeof(float) * C * Ho * Wo, hipMemcpyDeviceToHost, ctx->stream));
-    NCT_HIP(hipStreamSynchronize(ctx->stream));
-    return NCT_OK;
+    return hc.finish();
 }
 
 }  // extern "C"
