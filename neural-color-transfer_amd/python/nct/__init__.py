@@ -8,6 +8,8 @@ Function names and argument meaning mirror include/nct.h, which cites the refere
 import collections
 import contextlib
 import ctypes as C
+import functools
+import math
 import os
 import numpy as np
 
@@ -94,18 +96,12 @@ SIGNATURES = {
     "nct_process_pair_fullres": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p]),
     "nct_color_finish": (C.c_int, [C.c_void_p, _f64p] + [C.c_int] * 4 + [_u8p, C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p]),
     "nct_process_pair_fullres_finish": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p]),
-    "nct_color_finish_upsample": (C.c_int, [C.c_void_p, _f64p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_void_p, _u8p]),
-    "nct_color_finish_upsample_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nct_guided_params_default": (None, [C.c_void_p]),
-    "nct_color_finish_guided": (C.c_int, [C.c_void_p, _f64p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _u8p]),
-    "nct_color_finish_guided_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_set_finish_guided": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nct_pair_upload": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int]),
     "nct_pair_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_pair_run_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_pair_download": (C.c_int, [C.c_void_p, _u8p]),
-    "nct_select_reference": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nct_select_reference_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_multi_upload": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nct_multi_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_multi_run_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -119,76 +115,38 @@ SIGNATURES = {
                                               C.c_void_p, C.c_void_p]),
     "nct_seq_frame_multi_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_multi_stage_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nct_select_reference_hold": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nct_select_reference_hold_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p]),
     "nct_seq_frame_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_propagate": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p]),
     "nct_seq_frame_propagate_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p]),
-    "nct_seq_warp": (C.c_int, [C.c_void_p, _f64p, C.c_int, C.c_int, C.c_void_p, _f64p]),
-    "nct_seq_warp_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nct_seq_reset": (C.c_int, [C.c_void_p]),
     "nct_seq_end": (C.c_int, [C.c_void_p]),
-    "nct_seq_blend": (C.c_int, [C.c_void_p, _f64p, _f64p, _u8p, _u8p, C.c_int, C.c_int, C.c_double, C.c_double, _f64p, C.c_void_p]),
-    "nct_seq_blend_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "nct_seq_motion_default": (None, [C.c_void_p]),
     "nct_seq_set_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "nct_seq_motion_field": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "nct_seq_motion_field_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "nct_seq_blend_mc": (C.c_int, [C.c_void_p, _f64p, _f64p, _u8p, _u8p, C.c_int, C.c_int, C.c_double, C.c_double, _f64p, C.c_void_p, C.c_void_p]),
-    "nct_seq_blend_mc_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_auto_default": (None, [C.c_void_p]),
-    "nct_seq_change": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-    "nct_seq_change_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "nct_seq_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_auto": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_lut_params_default": (None, [C.c_void_p]),
-    "nct_lut_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nct_lut_fit_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nct_lut_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "nct_lut_apply_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "nct_pair_fit_lut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_region_params_default": (None, [C.c_void_p]),
-    "nct_resize_u8c1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
-    "nct_resize_u8c1_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
-    "nct_region_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "nct_region_mix_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "nct_region_compose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nct_region_compose_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_pair_set_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_pair_run_region_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_process_pair_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_process_pair_fullres_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_process_pair_fullres_finish_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                          C.c_void_p]),
-    "nct_lut_fit_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nct_lut_fit_masked_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_set_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_set_ref_region": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "nct_seq_pull_hold": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                    C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nct_seq_pull_hold_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                        C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_ref_region_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_propagate_ref_region_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_region_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nct_seq_matte_warp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "nct_seq_matte_warp_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "nct_seq_set_region_tracking": (C.c_int, [C.c_void_p, C.c_int]),
     "nct_seq_get_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_region_snap_params_default": (None, [C.c_void_p]),
-    "nct_region_snap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "nct_region_snap_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nct_seq_set_region_snap": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nct_region_select_params_default": (None, [C.c_void_p]),
     "nct_region_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_region_select_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nct_feat_quantize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "nct_feat_quantize_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "nct_region_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "nct_region_score_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "nct_region_score_bench": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                          C.POINTER(C.c_float)]),
     "nct_pair_select_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -200,21 +158,12 @@ SIGNATURES = {
     "nct_region_model_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "nct_region_model_from_rows": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "nct_region_model_free": (None, [C.c_void_p]),
-    "nct_region_refind": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "nct_region_refind_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "nct_region_refind_bench": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "nct_region_model_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_region_model_apply_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_pair_apply_region_model": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_set_region_model": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_propagate_region_levels": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nct_color_finish_upsample_region": (C.c_int, [C.c_void_p, _f64p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _u8p]),
-    "nct_color_finish_upsample_region_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nct_color_finish_guided_region": (C.c_int, [C.c_void_p, _f64p, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u8p]),
-    "nct_color_finish_guided_region_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                    C.c_void_p]),
-    "nct_region_pull": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
-    "nct_region_pull_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "nct_pair_set_ref_region": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "nct_multi_run_ref_region_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_pair_run_ref_region_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -245,6 +194,47 @@ SIGNATURES = {
     "nct_pm_bench_run": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]),
     "nct_pm_bench_run_bidir": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+
+
+class _voidp(C.c_void_p):
+    """void* as an argument type: an address, None, or the array that stands there (no dtype is checked: the host and the device form of a seam share their row)"""
+
+    @classmethod
+    def from_param(cls, v):
+        return C.c_void_p(v.ctypes.data) if isinstance(v, np.ndarray) else C.c_void_p.from_param(v)
+
+
+_P, _I, _D, _N, _L = _voidp, C.c_int, C.c_double, C.c_size_t, C.POINTER(C.c_void_p)
+# the seams whose nct_X and nct_X_dev take the same list, pointers to host memory in one and to arena blocks in the other: one row, both names (nct_region_select and
+# nct_region_model_apply, whose host forms take a stages struct more, keep two rows above)
+_TWINS = {
+    "nct_color_finish_upsample": [_P, _I, _I, _P, _I, _I, _P, _P],
+    "nct_color_finish_guided": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P],
+    "nct_color_finish_upsample_region": [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P],
+    "nct_color_finish_guided_region": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P],
+    "nct_select_reference": [_L, _L, _I, _I, _I, _P, _P, _P],
+    "nct_select_reference_hold": [_L, _L, _I, _I, _I, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P],
+    "nct_region_pull": [_P, _I, _I, _P, _P, _I, _I, _D, _D, _P],
+    "nct_seq_warp": [_P, _I, _I, _P, _P],
+    "nct_seq_blend": [_P, _P, _P, _P, _I, _I, _D, _D, _P, _P],
+    "nct_seq_blend_mc": [_P, _P, _P, _P, _I, _I, _D, _D, _P, _P, _P],
+    "nct_seq_motion_field": [_P, _P, _I, _I, _P, _I, _I, _I, _I, _P],
+    "nct_seq_change": [_P, _P, _I, _I, _P, _I, _P],
+    "nct_seq_pull_hold": [_L, _I, _P, _P, _P, _P, _P, _P, _I, _I, _D, _D, _P, _P, _P],
+    "nct_seq_matte_warp": [_P, _I, _I, _P, _I, _I, _P],
+    "nct_lut_fit": [_P, _P, _N, _P, _P, _P],
+    "nct_lut_fit_masked": [_P, _P, _P, _N, _P, _P, _P],
+    "nct_lut_apply": [_P, _I, _P, _N, _P],
+    "nct_resize_u8c1": [_P, _I, _I, _P, _I, _I],
+    "nct_region_mix": [_P, _P, _I, _I, _P],
+    "nct_region_compose": [_P, _P, _P, _N, _P, _P, _P],
+    "nct_region_snap": [_P, _P, _I, _I, _P, _P],
+    "nct_feat_quantize": [_P, _P, _I, _I, _I],
+    "nct_region_score": [_P, _I, _I, _P, _I, _P, _I, _I, _I, _P],
+    "nct_region_refind": [_P, _I, _I, _P, _I, _I, _I, _P],
+}
+for _name, _args in _TWINS.items():
+    SIGNATURES[_name] = SIGNATURES[_name + "_dev"] = (C.c_int, [C.c_void_p] + _args)
 
 
 def _declare(l):
@@ -772,6 +762,78 @@ def _pair_report(g, levels, want_color):
 _Seq = collections.namedtuple("_Seq", "arrive ref_arrive work ref_work levels finish")
 
 
+class _Blocks:
+    """what Context.blocks() hands out: the arena blocks taken through it, in `held`"""
+
+    def __init__(self, ctx):
+        self._c, self.held = ctx, []
+
+    def up(self, a):
+        self.held.append(self._c.dev_upload(a)); return self.held[-1]
+
+    def new(self, nbytes):
+        self.held.append(self._c.dev_alloc(nbytes)); return self.held[-1]
+
+    def free(self, p):
+        self.held.remove(p); self._c.dev_free(p)
+
+
+# an array a seam call has staged: ptr goes into the call (a host address, or an arena block); arr is the host array (None for a block that was only reserved); shape and
+# dtype are what get() hands back
+_Staged = collections.namedtuple("_Staged", "ptr arr shape dtype")
+
+
+class _Seam:
+    """The binding's counterpart of HostCall (csrc/nct_internal.h): the staging of one call of a seam that exists as nct_X and nct_X_dev, so that the seam's method is
+    written once for both forms. Host form (blocks None): an input is kept alive and its address handed over, an output is an np.empty. Device form: an input goes
+    through dev_upload, an output is a dev_alloc of its byte size, get() is a dev_download. The arena is asked for blocks in the order of the put() / new() calls. Where
+    the two forms differ today, the difference is an argument here (upload, dev_shape, nbytes, fill, over(), host_only), never a second body"""
+
+    def __init__(self, ctx, name, blocks):
+        self._c, self._name, self._b = ctx, name, blocks
+
+    def put(self, a, upload=None):
+        """an input (None: None, nothing reserved). upload: the array the device form uploads in its place"""
+        if a is None:
+            return None
+        if self._b is None:
+            return _Staged(a.ctypes.data, a, a.shape, a.dtype)
+        a = a if upload is None else upload
+        return _Staged(self._b.up(a), a, a.shape, a.dtype)
+
+    def new(self, shape, dtype, dev_shape=None, nbytes=None, fill=None):
+        """an output of that shape and dtype. dev_shape: what the device form reserves and hands back where that is another shape; nbytes: the size of its block where
+        that is not the array's; fill: the byte its block holds before the call (the host form's array then holds zeros)"""
+        if self._b is None:
+            arr = np.empty(shape, dtype) if fill is None else np.zeros(shape, dtype)
+            return _Staged(arr.ctypes.data, arr, arr.shape, arr.dtype)
+        shape = tuple(shape if dev_shape is None else dev_shape)
+        if fill is not None:
+            return _Staged(self._b.up(np.full(shape, fill, dtype)), None, shape, dtype)
+        return _Staged(self._b.new(math.prod(shape) * np.dtype(dtype).itemsize if nbytes is None else nbytes), None, shape, dtype)
+
+    def over(self, out, inp):
+        """where a call writes under an alias or in-place switch: `out`, or in the device form the block of the input `inp` (None: the switch is off). The host form
+        has no such switch and writes `out`"""
+        return out if self._b is None or inp is None else inp
+
+    @staticmethod
+    def list(staged):
+        """a void*[K] of staged arrays (None entries: NULL; None: NULL)"""
+        return None if staged is None else (C.c_void_p * max(len(staged), 1))(*[None if s is None else s.ptr for s in staged])
+
+    def call(self, *args, host_only=()):
+        """nct_<name>[_dev](ctx, *args), a staged array as its pointer; host_only: what only the host form takes behind them"""
+        fn = getattr(self._c._l, "nct_" + self._name + ("_dev" if self._b is not None else ""))
+        self._c._chk(fn(self._c._h, *[a.ptr if isinstance(a, _Staged) else a for a in args + (tuple(host_only) if self._b is None else ())]))
+
+    def get(self, s):
+        """a staged array after the call: the host array, or the download of its block (None: None)"""
+        if s is None:
+            return None
+        return s.arr if self._b is None else self._c.dev_download(s.ptr, s.shape, s.dtype)
+
+
 class Context:
     """One context per GPU / process (include/nct.h: not thread-safe)."""
 
@@ -901,14 +963,25 @@ class Context:
         self._chk(self._l.nct_dev_free(self._h, p))
 
     @contextlib.contextmanager
-    def _blocks(self, ptrs):
-        """around the calls of a *_dev wrapper on the arena blocks it took (dev_upload, dev_alloc): on every way out the stream is synchronised, then they go back"""
+    def blocks(self, held=()):
+        """the arena blocks of a piece of work -> a _Blocks: up(array) uploads into a new block, new(nbytes) takes one, free(p) gives one back early. On every way
+        out the stream is synchronised, then the blocks still held go back. held: blocks taken before (dev_upload, dev_alloc), which go back with them"""
+        b = _Blocks(self)
+        b.held.extend(held)
         try:
-            yield
+            yield b
         finally:
             self.synchronize()
-            for p in ptrs:
+            for p in b.held:
                 self.dev_free(p)
+
+    _blocks = blocks                                               # the name blocks(held) had while it was private: callers written against it keep working
+
+    @contextlib.contextmanager
+    def _seam(self, name, dev):
+        """one call of the seam nct_<name> in its host form or (dev) in its device form on arena blocks -> a _Seam; the blocks go back as blocks() gives them back"""
+        with (self.blocks() if dev else contextlib.nullcontext()) as b:
+            yield _Seam(self, name, b)
 
     def dev_upload(self, arr):
         a = np.ascontiguousarray(arr)
@@ -1075,92 +1148,41 @@ class Context:
             return self._process("nct_process_pair_fullres", src_bgr, [*self._image(ref_bgr), max_side], params, want_timing)
         return self._process("nct_process_pair_fullres_finish", src_bgr, [*self._image(ref_bgr), max_side, int(finish)], params, want_timing)
 
-    def color_finish_upsample(self, ab_wls, h, w, s_full, params=None):
-        """nct_color_finish_upsample (SPEC §6.8): ab_wls ([2][h*w][3], the working-size finish's S2 output) upsampled and applied to s_full (H x W x 3 BGR)"""
-        a = np.ascontiguousarray(ab_wls, np.float64).reshape(-1)
-        assert a.size == 6 * h * w
-        s_full = np.ascontiguousarray(s_full, np.uint8)
-        H, W = s_full.shape[:2]
-        prm = params or Params.default()
-        out = np.empty((H, W, 3), np.uint8)
-        self._chk(self._l.nct_color_finish_upsample(self._h, a, h, w, s_full.reshape(-1, 3), H, W, C.addressof(prm), out.reshape(-1, 3)))
-        return out
+    def color_finish_upsample(self, ab_wls, h, w, s_full, params=None, *, dev=False):
+        """nct_color_finish_upsample[_dev] (SPEC §6.8): ab_wls ([2][h*w][3], the working-size finish's S2 output) upsampled and applied to s_full (H x W x 3 BGR)"""
+        return self._finish(ab_wls, None, h, w, s_full, params, dev)
 
-    def color_finish_upsample_dev(self, ab_wls, h, w, s_full, params=None):
-        """the same through nct_color_finish_upsample_dev on arena blocks"""
-        a = np.ascontiguousarray(ab_wls, np.float64).reshape(-1)
-        assert a.size == 6 * h * w
-        s_full = np.ascontiguousarray(s_full, np.uint8)
-        H, W = s_full.shape[:2]
-        prm = params or Params.default()
-        blocks = [self.dev_upload(a), self.dev_upload(s_full), self.dev_alloc(s_full.size)]
-        with self._blocks(blocks):
-            self._chk(self._l.nct_color_finish_upsample_dev(self._h, blocks[0], h, w, blocks[1], H, W, C.addressof(prm), blocks[2]))
-            return self.dev_download(blocks[2], (H, W, 3), np.uint8)
+    def color_finish_guided(self, ab_wls, lab_work, h, w, s_full, sigma=None, params=None, *, dev=False):
+        """nct_color_finish_guided[_dev] (SPEC §6.10): the upsampling finish with joint-bilateral weights; lab_work (h x w x 3): the 8-bit Lab image of the working-size
+        source; sigma None = the library's default"""
+        return self._finish(ab_wls, np.ascontiguousarray(lab_work, np.uint8), h, w, s_full, params, dev, _guided_params(sigma))
 
-    def color_finish_guided(self, ab_wls, lab_work, h, w, s_full, sigma=None, params=None):
-        """nct_color_finish_guided (SPEC §6.10): the upsampling finish with joint-bilateral weights; lab_work (h x w x 3): the 8-bit Lab image of the working-size source;
-        sigma None = the library's default"""
-        a = np.ascontiguousarray(ab_wls, np.float64).reshape(-1)
-        lw = np.ascontiguousarray(lab_work, np.uint8)
-        assert a.size == 6 * h * w and lw.size == 3 * h * w
-        s_full = np.ascontiguousarray(s_full, np.uint8)
-        H, W = s_full.shape[:2]
-        prm, gp = params or Params.default(), _guided_params(sigma)
-        out = np.empty((H, W, 3), np.uint8)
-        self._chk(self._l.nct_color_finish_guided(self._h, a, lw.reshape(-1, 3), h, w, s_full.reshape(-1, 3), H, W, C.addressof(gp), C.addressof(prm), out.reshape(-1, 3)))
-        return out
-
-    def color_finish_guided_dev(self, ab_wls, lab_work, h, w, s_full, sigma=None, params=None):
-        """the same through nct_color_finish_guided_dev on arena blocks"""
-        a = np.ascontiguousarray(ab_wls, np.float64).reshape(-1)
-        lw = np.ascontiguousarray(lab_work, np.uint8)
-        assert a.size == 6 * h * w and lw.size == 3 * h * w
-        s_full = np.ascontiguousarray(s_full, np.uint8)
-        H, W = s_full.shape[:2]
-        prm, gp = params or Params.default(), _guided_params(sigma)
-        blocks = [self.dev_upload(a), self.dev_upload(lw), self.dev_upload(s_full), self.dev_alloc(s_full.size)]
-        with self._blocks(blocks):
-            self._chk(self._l.nct_color_finish_guided_dev(self._h, blocks[0], blocks[1], h, w, blocks[2], H, W, C.addressof(gp), C.addressof(prm), blocks[3]))
-            return self.dev_download(blocks[3], (H, W, 3), np.uint8)
-
-    def color_finish_upsample_region(self, ab_wls, h, w, s_full, mask, protect=None, params=None, dev=False):
+    def color_finish_upsample_region(self, ab_wls, h, w, s_full, mask, protect=None, params=None, *, dev=False):
         """nct_color_finish_upsample_region[_dev] (SPEC §6.13 rule 4): color_finish_upsample with §6.11's compose in its pass; mask [H, W] bytes of s_full, None: the
         unmasked call"""
-        return self._finish_region(ab_wls, None, h, w, s_full, mask, protect, None, params, dev)
+        return self._finish(ab_wls, None, h, w, s_full, params, dev, None, (mask, protect))
 
-    def color_finish_upsample_region_dev(self, ab_wls, h, w, s_full, mask, protect=None, params=None):
-        return self._finish_region(ab_wls, None, h, w, s_full, mask, protect, None, params, True)
-
-    def color_finish_guided_region(self, ab_wls, lab_work, h, w, s_full, mask, protect=None, sigma=None, params=None, dev=False):
+    def color_finish_guided_region(self, ab_wls, lab_work, h, w, s_full, mask, protect=None, sigma=None, params=None, *, dev=False):
         """nct_color_finish_guided_region[_dev] (SPEC §6.13 rule 4): color_finish_guided with §6.11's compose in its pass"""
-        return self._finish_region(ab_wls, np.ascontiguousarray(lab_work, np.uint8), h, w, s_full, mask, protect, _guided_params(sigma), params, dev)
+        return self._finish(ab_wls, np.ascontiguousarray(lab_work, np.uint8), h, w, s_full, params, dev, _guided_params(sigma), (mask, protect))
 
-    def color_finish_guided_region_dev(self, ab_wls, lab_work, h, w, s_full, mask, protect=None, sigma=None, params=None):
-        return self._finish_region(ab_wls, np.ascontiguousarray(lab_work, np.uint8), h, w, s_full, mask, protect, _guided_params(sigma), params, True)
-
-    def _finish_region(self, ab_wls, lw, h, w, s_full, mask, protect, gp, params, dev):
-        """the four masked finish seams: lw / gp None = the plain upsampling finish, else the guided one"""
+    def _finish(self, ab_wls, lw, h, w, s_full, params, dev, gp=None, region=None):
+        """the four upsampling finish seams: lw / gp None = the plain finish, else the guided one; region None = the unmasked entry point, else (mask, protect) of the
+        masked one"""
         a = np.ascontiguousarray(ab_wls, np.float64).reshape(-1)
         assert a.size == 6 * h * w and (lw is None or lw.size == 3 * h * w)
         s_full = np.ascontiguousarray(s_full, np.uint8)
         H, W = s_full.shape[:2]
-        name = "nct_color_finish_upsample_region" if lw is None else "nct_color_finish_guided_region"
-        m = None if mask is None else _mask_arg(mask, s_full.shape, name[4:])
+        name = "color_finish_" + ("upsample" if lw is None else "guided") + ("" if region is None else "_region")
+        mask, protect = region or (None, None)
+        m = None if mask is None else _mask_arg(mask, s_full.shape, name)
         prm, rg = params or Params.default(), _region_params(protect)
-        tail = [C.addressof(rg)] + ([C.addressof(gp)] if lw is not None else []) + [C.addressof(prm)]
-        if not dev:
-            out = np.empty((H, W, 3), np.uint8)
-            mid = [a] + ([lw.reshape(-1, 3)] if lw is not None else [])
-            self._chk(getattr(self._l, name)(self._h, *mid, h, w, s_full.reshape(-1, 3), H, W, m.ctypes.data if m is not None else None, *tail, out.reshape(-1, 3)))
-            return out
-        blocks = [self.dev_upload(a)] + ([self.dev_upload(lw)] if lw is not None else []) + [self.dev_upload(s_full), self.dev_alloc(s_full.size)]
-        if m is not None:
-            blocks.append(self.dev_upload(m))
-        with self._blocks(blocks):
-            nin = 1 if lw is None else 2
-            self._chk(getattr(self._l, name + "_dev")(self._h, *blocks[:nin], h, w, blocks[nin], H, W, blocks[nin + 2] if m is not None else None, *tail, blocks[nin + 1]))
-            return self.dev_download(blocks[nin + 1], (H, W, 3), np.uint8)
+        tail = ([] if region is None else [C.addressof(rg)]) + ([] if lw is None else [C.addressof(gp)]) + [C.addressof(prm)]
+        with self._seam(name, dev) as s:
+            ins = [s.put(a)] + ([] if lw is None else [s.put(lw)])
+            src, out = s.put(s_full), s.new((H, W, 3), np.uint8)
+            s.call(*ins, h, w, src, H, W, *([] if region is None else [s.put(m)]), *tail, out)         # the mask goes up behind the output block
+            return s.get(out)
 
     def set_finish_guided(self, sigma):
         """nct_set_finish_guided: a sigma turns the guided modifier of the upsampling finish on for this context, None turns it off (the default)"""
@@ -1197,32 +1219,17 @@ class Context:
         ws = (C.c_int * max(K, 1))(*[0 if a is None else a.shape[1] for a in arrs])
         return K, arrs, ptrs, hs, ws
 
-    def select_reference(self, errs, guides=None):
-        """nct_select_reference: K error maps (h x w fp32) and, optionally, K guidance images (h x w x 3) -> (label, merged guide or None, merged err)"""
+    def select_reference(self, errs, guides=None, *, dev=False):
+        """nct_select_reference[_dev]: K error maps (h x w fp32) and, optionally, K guidance images (h x w x 3) -> (label, merged guide or None, merged err)"""
         es = [np.ascontiguousarray(e, np.float32) for e in errs]
         gs = None if guides is None else [np.ascontiguousarray(g, np.uint8) for g in guides]
         K = len(es)
         h, w = es[0].shape if K else (1, 1)
-        ep = (C.c_void_p * max(K, 1))(*[e.ctypes.data for e in es])
-        gp = None if gs is None else (C.c_void_p * max(K, 1))(*[g.ctypes.data for g in gs])
-        label = np.empty((h, w), np.uint8)
-        gout = None if gs is None else np.empty((h, w, 3), np.uint8)
-        eout = np.empty((h, w), np.float32)
-        self._chk(self._l.nct_select_reference(self._h, ep, gp, K, h, w, _ptr(label), _ptr(gout), _ptr(eout)))
-        return label, gout, eout
-
-    def select_reference_dev(self, errs, guides):
-        """the same through nct_select_reference_dev: maps uploaded to arena blocks, the launch enqueued on the context's stream, results downloaded"""
-        es = [np.ascontiguousarray(e, np.float32) for e in errs]
-        gs = [np.ascontiguousarray(g, np.uint8) for g in guides]
-        K = len(es)
-        h, w = es[0].shape
-        de = [self.dev_upload(e) for e in es]
-        dg = [self.dev_upload(g) for g in gs]
-        dl, dgo, deo = self.dev_alloc(h * w), self.dev_alloc(h * w * 3), self.dev_alloc(h * w * 4)
-        with self._blocks(de + dg + [dl, dgo, deo]):
-            self._chk(self._l.nct_select_reference_dev(self._h, (C.c_void_p * K)(*de), (C.c_void_p * K)(*dg), K, h, w, dl, dgo, deo))
-            return self.dev_download(dl, (h, w), np.uint8), self.dev_download(dgo, (h, w, 3), np.uint8), self.dev_download(deo, (h, w), np.float32)
+        with self._seam("select_reference", dev) as s:
+            ep, gp = [s.put(e) for e in es], None if gs is None else [s.put(g) for g in gs]
+            label, gout, eout = s.new((h, w), np.uint8), None if gs is None else s.new((h, w, 3), np.uint8), s.new((h, w), np.float32)
+            s.call(s.list(ep), s.list(gp), K, h, w, label, gout, eout)
+            return s.get(label), s.get(gout), s.get(eout)
 
     def process_multi(self, src_bgr, refs_bgr, params=None, want_timing=False):
         """nct_process_multi: one source, a list of references -> the result at the source's size"""
@@ -1257,24 +1264,15 @@ class Context:
         return keep
 
     # ---- reference region masks (SPEC §6.12)
-    def region_pull(self, q_mask, ann, bnn, w_coh=1.0, w_comp=2.0):
-        """nct_region_pull (SPEC §6.12 rule 2): q_mask [bh, bw] bytes, ann [ah, aw] and bnn [bh, bw] NNF words -> the pulled mask [ah, aw]"""
+    def region_pull(self, q_mask, ann, bnn, w_coh=1.0, w_comp=2.0, *, dev=False):
+        """nct_region_pull[_dev] (SPEC §6.12 rule 2): q_mask [bh, bw] bytes, ann [ah, aw] and bnn [bh, bw] NNF words -> the pulled mask [ah, aw]"""
         q, a, b = np.ascontiguousarray(q_mask, np.uint8), np.ascontiguousarray(ann, np.uint32), np.ascontiguousarray(bnn, np.uint32)
         if q.shape != b.shape:
             raise NctError(-2, f"region_pull: mask is {q.shape}, bnn {b.shape}")
-        out = np.empty(a.shape, np.uint8)
-        self._chk(self._l.nct_region_pull(self._h, q.ctypes.data, q.shape[0], q.shape[1], a.ctypes.data, b.ctypes.data, a.shape[0], a.shape[1], w_coh, w_comp, out.ctypes.data))
-        return out
-
-    def region_pull_dev(self, q_mask, ann, bnn, w_coh=1.0, w_comp=2.0):
-        """the same through nct_region_pull_dev on arena blocks"""
-        q, a, b = np.ascontiguousarray(q_mask, np.uint8), np.ascontiguousarray(ann, np.uint32), np.ascontiguousarray(bnn, np.uint32)
-        if q.shape != b.shape:
-            raise NctError(-2, f"region_pull_dev: mask is {q.shape}, bnn {b.shape}")
-        blocks = [self.dev_upload(q), self.dev_upload(a), self.dev_upload(b), self.dev_alloc(a.size)]
-        with self._blocks(blocks):
-            self._chk(self._l.nct_region_pull_dev(self._h, blocks[0], q.shape[0], q.shape[1], blocks[1], blocks[2], a.shape[0], a.shape[1], w_coh, w_comp, blocks[3]))
-            return self.dev_download(blocks[3], a.shape, np.uint8)
+        with self._seam("region_pull", dev) as s:
+            qs, as_, bs, out = s.put(q), s.put(a), s.put(b), s.new(a.shape, np.uint8)
+            s.call(qs, q.shape[0], q.shape[1], as_, bs, a.shape[0], a.shape[1], w_coh, w_comp, out)
+            return s.get(out)
 
     def pair_set_ref_region(self, k, mask, protect=None):
         """nct_pair_set_ref_region on the uploaded references: reference k's mask [rh, rw] bytes, or None to remove it; protect None leaves the run's protect as it is"""
@@ -1424,9 +1422,9 @@ class Context:
         keep["color"], cptr, stages = _color_stages(self._seq_grids(), q.levels, q.levels)
         return self._seq_frame_call("nct_seq_frame_multi_stage_levels", s, keep, lv, cptr, sl, hl)
 
-    def select_reference_hold(self, errs, guides, prev_label, lab, lab_prev, field=None, hold=0.0, sigma=10.0, dev=False, want=("label", "guide", "err", "free_label", "margin")):
-        """nct_select_reference_hold (dev: its _dev form on arena blocks): K error maps [h, w] fp32, K guidance images [h, w, 3] (or None), the kept labels [h, w], the two
-        frames' 8-bit Lab level images, a field int16 [h, w, 2] or None -> dict of the outputs named in `want` (the others are passed as NULL)"""
+    def select_reference_hold(self, errs, guides, prev_label, lab, lab_prev, field=None, hold=0.0, sigma=10.0, *, dev=False, want=("label", "guide", "err", "free_label", "margin")):
+        """nct_select_reference_hold[_dev]: K error maps [h, w] fp32, K guidance images [h, w, 3] (or None), the kept labels [h, w], the two frames' 8-bit Lab level
+        images, a field int16 [h, w, 2] or None -> dict of the outputs named in `want` (the others are passed as NULL)"""
         es = [np.ascontiguousarray(e, np.float32) for e in errs]
         gs = None if guides is None else [np.ascontiguousarray(g, np.uint8) for g in guides]
         K = len(es)
@@ -1435,22 +1433,12 @@ class Context:
         f = None if field is None else np.ascontiguousarray(field, np.int16)
         want = [k for k in want if not (k == "guide" and gs is None)]
         spec = {"label": ((h, w), np.uint8), "guide": ((h, w, 3), np.uint8), "err": ((h, w), np.float32), "free_label": ((h, w), np.uint8), "margin": ((h, w), np.float64)}
-        order = ("label", "guide", "err", "free_label", "margin")
-        if not dev:
-            ep = (C.c_void_p * max(K, 1))(*[e.ctypes.data for e in es])
-            gp = None if gs is None else (C.c_void_p * max(K, 1))(*[g.ctypes.data for g in gs])
-            outs = {k: np.empty(*spec[k]) for k in want}
-            self._chk(self._l.nct_select_reference_hold(self._h, ep, gp, K, h, w, pl.ctypes.data, l1.ctypes.data, l0.ctypes.data, None if f is None else f.ctypes.data,
-                                                        float(hold), float(sigma), *[_ptr(outs.get(k)) for k in order]))
-            return outs
-        de = [self.dev_upload(e) for e in es]
-        dg = [] if gs is None else [self.dev_upload(g) for g in gs]
-        ins = [self.dev_upload(pl), self.dev_upload(l1), self.dev_upload(l0)] + ([] if f is None else [self.dev_upload(f)])
-        dout = {k: self.dev_alloc(int(np.prod(spec[k][0])) * np.dtype(spec[k][1]).itemsize) for k in want}
-        with self._blocks(de + dg + ins + list(dout.values())):
-            self._chk(self._l.nct_select_reference_hold_dev(self._h, (C.c_void_p * max(K, 1))(*de), None if gs is None else (C.c_void_p * max(K, 1))(*dg), K, h, w, ins[0], ins[1],
-                                                            ins[2], None if f is None else ins[3], float(hold), float(sigma), *[dout.get(k) for k in order]))
-            return {k: self.dev_download(dout[k], *spec[k]) for k in want}
+        with self._seam("select_reference_hold", dev) as s:
+            ep, gp = [s.put(e) for e in es], None if gs is None else [s.put(g) for g in gs]
+            ins = [s.put(pl), s.put(l1), s.put(l0), s.put(f)]
+            outs = {k: s.new(*spec[k]) for k in want}
+            s.call(s.list(ep), s.list(gp), K, h, w, *ins, float(hold), float(sigma), *[outs.get(k) for k in ("label", "guide", "err", "free_label", "margin")])
+            return {k: s.get(outs[k]) for k in want}
 
     def seq_frame(self, src_bgr, want_timing=False):
         s = self._seq_frame_arg(src_bgr, "seq_frame")
@@ -1485,10 +1473,10 @@ class Context:
             m = _mask_arg(mask, shapes[k], "seq_set_ref_region")
         self._chk(self._l.nct_seq_set_ref_region(self._h, int(k), m.ctypes.data, None if rg is None else C.addressof(rg)))
 
-    def seq_pull_hold(self, pulled, label, prev, lab, lab_prev, field=None, src_mask=None, tau=0.7, sigma=10.0, dev=False, alias=False, want=("p", "m", "p_free"), shape=None):
-        """nct_seq_pull_hold (dev: its _dev form on arena blocks; alias: p_out is prev's block, which is an error): K pulled masks [h, w] bytes (None entries: 255), the label
-        map [h, w] (None with one reference), the kept map, the two frames' 8-bit Lab level images, a field int16 [h, w, 2] or None, the source level mask or None ->
-        dict of the outputs named in `want` ("p" is always written). shape: the grid, where no array gives it"""
+    def seq_pull_hold(self, pulled, label, prev, lab, lab_prev, field=None, src_mask=None, tau=0.7, sigma=10.0, *, dev=False, alias=False, want=("p", "m", "p_free"), shape=None):
+        """nct_seq_pull_hold[_dev]: K pulled masks [h, w] bytes (None entries: 255), the label map [h, w] (None with one reference), the kept map, the two frames' 8-bit
+        Lab level images, a field int16 [h, w, 2] or None, the source level mask or None -> dict of the outputs named in `want` ("p" is always written). shape: the
+        grid, where no array gives it. alias (device form): p_out is prev's block, which is an error"""
         ps = [None if q is None else np.ascontiguousarray(q, np.uint8) for q in pulled]
         K = len(ps)
         pv, l1, l0 = np.ascontiguousarray(prev, np.uint8), np.ascontiguousarray(lab, np.uint8), np.ascontiguousarray(lab_prev, np.uint8)
@@ -1498,24 +1486,14 @@ class Context:
         ms = None if src_mask is None else np.ascontiguousarray(src_mask, np.uint8)
         order = ("p", "m", "p_free")
         want = [k for k in order if k in want or k == "p"]
-        if not dev:
-            pp = (C.c_void_p * max(K, 1))(*[_ptr(q) for q in ps])
-            outs = {k: np.empty((h, w), np.uint8) for k in want}
-            self._chk(self._l.nct_seq_pull_hold(self._h, pp, K, _ptr(lb), pv.ctypes.data, l1.ctypes.data, l0.ctypes.data, _ptr(f), _ptr(ms), int(h), int(w), float(tau), float(sigma),
-                                                *[_ptr(outs.get(k)) for k in order]))
-            return outs
-        dp = [None if q is None else self.dev_upload(q) for q in ps]
-        opt = {"label": lb, "field": f, "ms": ms}
-        dopt = {k: (None if a is None else self.dev_upload(a)) for k, a in opt.items()}
-        ins = [self.dev_upload(pv), self.dev_upload(l1), self.dev_upload(l0)]
-        dout = {k: self.dev_alloc(int(h) * int(w)) for k in want}
-        with self._blocks([b for b in dp if b is not None] + [b for b in dopt.values() if b is not None] + ins + list(dout.values())):
-            outp = [dout.get(k) for k in order]
-            if alias:
-                outp[0] = ins[0]
-            self._chk(self._l.nct_seq_pull_hold_dev(self._h, (C.c_void_p * max(K, 1))(*dp), K, dopt["label"], ins[0], ins[1], ins[2], dopt["field"], dopt["ms"], int(h), int(w),
-                                                    float(tau), float(sigma), *outp))
-            return {k: self.dev_download(dout[k], (h, w), np.uint8) for k in want}
+        with self._seam("seq_pull_hold", dev) as s:
+            pp = [s.put(q) for q in ps]
+            lbs, fs, mss = s.put(lb), s.put(f), s.put(ms)
+            pvs, l1s, l0s = s.put(pv), s.put(l1), s.put(l0)
+            outs = {k: s.new((int(h), int(w)), np.uint8) for k in want}
+            p_out = s.over(outs["p"], pvs if alias else None)
+            s.call(s.list(pp), K, lbs, pvs, l1s, l0s, fs, mss, int(h), int(w), float(tau), float(sigma), p_out, outs.get("m"), outs.get("p_free"))
+            return {k: s.get(outs[k]) for k in want}
 
     def seq_frame_ref_region_levels(self, src_bgr):
         """nct_seq_frame_ref_region_levels -> (result, dict): seq_frame_multi_levels' dict without "color", plus per level that ran "ref_mask" and "pulled" ([k][l]; unmasked
@@ -1535,23 +1513,18 @@ class Context:
         return self._seq_frame_call("nct_seq_frame_propagate_ref_region_levels", s, keep, *structs)
 
     # ---- region tracking (SPEC §6.14)
-    def seq_matte_warp(self, mask, field, dev=False, alias=False):
+    def seq_matte_warp(self, mask, field, *, dev=False, alias=False):
         """nct_seq_matte_warp[_dev] (SPEC §6.14 rule 1): mask [H, W] bytes, field int16 [h, w, 2] of (my, mx) on a level grid -> the matte read at p + d(p), d the field
-        interpolated at p in target pixels. dev: on arena blocks, into a block of its own (alias: into the matte's block, which is an error)"""
+        interpolated at p in target pixels. alias (device form): into the matte's block, which is an error"""
         m = np.ascontiguousarray(mask, np.uint8)
         f = np.ascontiguousarray(field, np.int16)
         if m.ndim != 2 or f.ndim != 3 or f.shape[2] != 2:
             raise NctError(-2, "seq_matte_warp: mask must be [H, W] bytes and field [h, w, 2] int16")
         (H, W), (h, w) = m.shape, f.shape[:2]
-        if not dev:
-            out = np.empty_like(m)
-            self._chk(self._l.nct_seq_matte_warp(self._h, m.ctypes.data, H, W, f.ctypes.data, h, w, out.ctypes.data))
-            return out
-        ins = [self.dev_upload(m), self.dev_upload(f)]
-        do = self.dev_alloc(m.size)
-        with self._blocks(ins + [do]):
-            self._chk(self._l.nct_seq_matte_warp_dev(self._h, ins[0], H, W, ins[1], h, w, ins[0] if alias else do))
-            return self.dev_download(do, (H, W), np.uint8)
+        with self._seam("seq_matte_warp", dev) as s:
+            ms, fs, out = s.put(m), s.put(f), s.new((H, W), np.uint8)
+            s.call(ms, H, W, fs, h, w, s.over(out, ms if alias else None))
+            return s.get(out)
 
     def seq_set_region_tracking(self, on):
         """nct_seq_set_region_tracking: from the next frame on the open sequence's matte follows the motion field (True) or stays sticky (False)"""
@@ -1565,24 +1538,18 @@ class Context:
         return out, age.value
 
     # ---- matte snapping (SPEC §6.15)
-    def region_snap(self, mask, lab, radius=None, sigma=None, binary=None, dev=False, alias=None):
+    def region_snap(self, mask, lab, radius=None, sigma=None, binary=None, *, dev=False, alias=None):
         """nct_region_snap[_dev] (SPEC §6.15 rule 1): mask [H, W] bytes, lab [H, W, 3] the same frame in 8-bit Lab -> the matte re-fitted to the guide's edges; a
-        parameter left None keeps its default (radius 3, sigma 10, binary 1). dev: on arena blocks, into a block of its own (alias "mask" / "lab": into that input's
-        block, which is an error)"""
+        parameter left None keeps its default (radius 3, sigma 10, binary 1). alias "mask" / "lab" (device form): into that input's block, which is an error"""
         m, g = np.ascontiguousarray(mask, np.uint8), np.ascontiguousarray(lab, np.uint8)
         if m.ndim != 2 or g.shape != m.shape + (3,):
             raise NctError(-2, "region_snap: mask must be [H, W] bytes and lab [H, W, 3] bytes")
         H, W = m.shape
         sp = _snap_params(radius, sigma, binary)
-        if not dev:
-            out = np.empty_like(m)
-            self._chk(self._l.nct_region_snap(self._h, m.ctypes.data, g.ctypes.data, H, W, C.addressof(sp), out.ctypes.data))
-            return out
-        ins = [self.dev_upload(m), self.dev_upload(g)]
-        do = self.dev_alloc(m.size)
-        with self._blocks(ins + [do]):
-            self._chk(self._l.nct_region_snap_dev(self._h, ins[0], ins[1], H, W, C.addressof(sp), {None: do, "mask": ins[0], "lab": ins[1]}[alias]))
-            return self.dev_download(do, (H, W), np.uint8)
+        with self._seam("region_snap", dev) as s:
+            ms, gs, out = s.put(m), s.put(g), s.new((H, W), np.uint8)
+            s.call(ms, gs, H, W, C.addressof(sp), s.over(out, {None: None, "mask": ms, "lab": gs}[alias]))
+            return s.get(out)
 
     def seq_set_region_snap(self, on=True, radius=None, sigma=None, binary=None):
         """nct_seq_set_region_snap: from the next frame on the open sequence's tracked matte is snapped to its frame's edges behind the carry (on; a parameter left
@@ -1594,64 +1561,49 @@ class Context:
         self._chk(self._l.nct_seq_set_region_snap(self._h, C.addressof(sp)))
 
     # ---- region selection from strokes (SPEC §6.16)
-    def region_select(self, src_bgr, strokes, params=None, want_stages=False, dev=False):
+    def region_select(self, src_bgr, strokes, params=None, want_stages=False, *, dev=False):
         """nct_region_select[_dev] (SPEC §6.16): src_bgr [h, w, 3], strokes [h, w] bytes (STROKE_IN inside, STROKE_OUT outside, else unmarked) -> the matte [h, w];
-        params: region_select_params(...) or None for the defaults. want_stages (host form only): -> (matte, {"q" [cells, C] int16, "cell", "score" [h_t, w_t], "up" [h, w]})"""
-        s, t = np.ascontiguousarray(src_bgr, np.uint8), np.ascontiguousarray(strokes, np.uint8)
-        if s.ndim != 3 or s.shape[2] != 3 or t.shape != s.shape[:2]:
+        params: region_select_params(...) or None for the defaults. want_stages (host form only; refused with dev): -> (matte, {"q" [cells, C] int16, "cell", "score"
+        [h_t, w_t], "up" [h, w]})"""
+        s_, t = np.ascontiguousarray(src_bgr, np.uint8), np.ascontiguousarray(strokes, np.uint8)
+        if s_.ndim != 3 or s_.shape[2] != 3 or t.shape != s_.shape[:2]:
             raise NctError(-2, "region_select: src_bgr must be [h, w, 3] bytes and strokes [h, w] bytes")
+        if want_stages and dev:
+            raise NctError(-2, "region_select: want_stages is host-only (nct_region_select_dev reports no stages)")
         h, w = t.shape
-        pp = C.addressof(params) if params is not None else None
-        if dev:
-            ins = [self.dev_upload(s), self.dev_upload(t)]
-            do = self.dev_alloc(t.size)
-            with self._blocks(ins + [do]):
-                self._chk(self._l.nct_region_select_dev(self._h, ins[0], h, w, ins[1], pp, do))
-                return self.dev_download(do, (h, w), np.uint8)
-        out = np.empty((h, w), np.uint8)
-        if not want_stages:
-            self._chk(self._l.nct_region_select(self._h, s.ctypes.data, h, w, t.ctypes.data, pp, out.ctypes.data, None))
-            return out
-        tap = params.tap if params is not None else RegionSelectParams.default().tap
-        if not 1 <= tap <= 5:                                  # the library refuses; the stage arrays are never written
-            tap = 1
-        ht, wt = ((h - 1) >> (tap - 1)) + 1, ((w - 1) >> (tap - 1)) + 1
-        st = {"q": np.zeros((ht * wt, self.TAP_C[tap - 1]), np.int16), "cell": np.zeros((ht, wt), np.uint8), "score": np.zeros((ht, wt), np.uint8),
-              "up": np.zeros((h, w), np.uint8)}
-        cs = RegionSelectStages(*[st[k].ctypes.data for k in ("q", "cell", "score", "up")])
-        self._chk(self._l.nct_region_select(self._h, s.ctypes.data, h, w, t.ctypes.data, pp, out.ctypes.data, C.addressof(cs)))
-        return out, st
+        st, cs = None, None
+        if want_stages:
+            tap = params.tap if params is not None else RegionSelectParams.default().tap
+            if not 1 <= tap <= 5:                                  # the library refuses; the stage arrays are never written
+                tap = 1
+            ht, wt = ((h - 1) >> (tap - 1)) + 1, ((w - 1) >> (tap - 1)) + 1
+            st = {"q": np.zeros((ht * wt, self.TAP_C[tap - 1]), np.int16), "cell": np.zeros((ht, wt), np.uint8), "score": np.zeros((ht, wt), np.uint8),
+                  "up": np.zeros((h, w), np.uint8)}
+            cs = RegionSelectStages(*[st[k].ctypes.data for k in ("q", "cell", "score", "up")])
+        with self._seam("region_select", dev) as s:
+            ss, ts, out = s.put(s_), s.put(t), s.new((h, w), np.uint8)
+            s.call(ss, h, w, ts, C.addressof(params) if params is not None else None, out, host_only=[C.addressof(cs) if cs is not None else None])
+            return (s.get(out), st) if want_stages else s.get(out)
 
-    def feat_quantize(self, src_chw, dev=False):
-        """nct_feat_quantize[_dev] (SPEC §6.16 rule 2): CHW fp32 features -> [H*W, C] int16 rows rint(N1(F) * 32767); dev: through the channel-last device form"""
+    def feat_quantize(self, src_chw, *, dev=False):
+        """nct_feat_quantize[_dev] (SPEC §6.16 rule 2): CHW fp32 features -> [H*W, C] int16 rows rint(N1(F) * 32767); the device form takes the map channel-last"""
         src = np.ascontiguousarray(src_chw, np.float32)
         Cc, H, W = src.shape
-        if not dev:
-            out = np.empty((H * W, Cc), np.int16)
-            self._chk(self._l.nct_feat_quantize(self._h, src.ctypes.data, out.ctypes.data, Cc, H, W))
-            return out
-        ins = [self.dev_upload(np.ascontiguousarray(src.reshape(Cc, H * W).T))]
-        do = self.dev_alloc(2 * src.size)
-        with self._blocks(ins + [do]):
-            self._chk(self._l.nct_feat_quantize_dev(self._h, ins[0], do, Cc, H, W))
-            return self.dev_download(do, (H * W, Cc), np.int16)
+        with self._seam("feat_quantize", dev) as s:
+            ins, out = s.put(src, upload=np.ascontiguousarray(src.reshape(Cc, H * W).T)), s.new((H * W, Cc), np.int16)
+            s.call(ins, out, Cc, H, W)
+            return s.get(out)
 
-    def region_score(self, q, seeds_in, seeds_out=None, sharpness=1024, floor_permille=700, dev=False):
+    def region_score(self, q, seeds_in, seeds_out=None, sharpness=1024, floor_permille=700, *, dev=False):
         """nct_region_score[_dev] (SPEC §6.16 rule 4 without the seed-cell overwrite): q [cells, C], seeds_in [n_in, C], seeds_out [n_out, C] or None, int16 -> [cells] bytes"""
         qq, si = np.ascontiguousarray(q, np.int16), np.ascontiguousarray(seeds_in, np.int16)
         so = None if seeds_out is None or len(seeds_out) == 0 else np.ascontiguousarray(seeds_out, np.int16)
         cells, Cc = qq.shape
         n_in, n_out = si.shape[0], 0 if so is None else so.shape[0]
-        if not dev:
-            out = np.empty(cells, np.uint8)
-            self._chk(self._l.nct_region_score(self._h, qq.ctypes.data, cells, Cc, si.ctypes.data, n_in, None if so is None else so.ctypes.data, n_out, int(sharpness),
-                                               int(floor_permille), out.ctypes.data))
-            return out
-        ins = [self.dev_upload(qq), self.dev_upload(si)] + ([] if so is None else [self.dev_upload(so)])
-        do = self.dev_alloc(cells)
-        with self._blocks(ins + [do]):
-            self._chk(self._l.nct_region_score_dev(self._h, ins[0], cells, Cc, ins[1], n_in, None if so is None else ins[2], n_out, int(sharpness), int(floor_permille), do))
-            return self.dev_download(do, (cells,), np.uint8)
+        with self._seam("region_score", dev) as s:
+            qs, sis, sos, out = s.put(qq), s.put(si), s.put(so), s.new((cells,), np.uint8)
+            s.call(qs, cells, Cc, sis, n_in, sos, n_out, int(sharpness), int(floor_permille), out)
+            return s.get(out)
 
     def pair_select_region(self, strokes, params=None, protect=None):
         """nct_pair_select_region: region_select on the uploaded source, then pair_set_region with the matte, which stays on the device"""
@@ -1684,52 +1636,42 @@ class Context:
             raise NctError(-2, "region_model_add: src_bgr must be [h, w, 3] bytes and strokes [h, w] bytes")
         self._chk(self._l.nct_region_model_add(self._h, model._m, s.ctypes.data, t.shape[0], t.shape[1], t.ctypes.data, C.addressof(params) if params is not None else None))
 
-    def region_refind(self, score, shape, prior=None, margin=32, dev=False, alias=None):
+    def region_refind(self, score, shape, prior=None, margin=32, *, dev=False, alias=None):
         """nct_region_refind[_dev] (SPEC §6.17 rules R1 to R3): score [ht, wt] bytes on the tap grid, shape (H, W), prior [H, W] bytes or None -> the matte [H, W].
-        dev: on arena blocks, into a block of its own (alias "score" / "prior": into that input's block, which is an error)"""
+        alias "score" / "prior" (device form): into that input's block, which is an error"""
         m = np.ascontiguousarray(score, np.uint8)
         pr = None if prior is None else np.ascontiguousarray(prior, np.uint8)
         H, W = int(shape[0]), int(shape[1])
         if m.ndim != 2 or (pr is not None and pr.shape != (H, W)):
             raise NctError(-2, "region_refind: score must be [ht, wt] bytes and prior [H, W] bytes or None")
         ht, wt = m.shape
-        if not dev:
-            out = np.empty((max(H, 1), max(W, 1)), np.uint8)
-            self._chk(self._l.nct_region_refind(self._h, m.ctypes.data, ht, wt, None if pr is None else pr.ctypes.data, H, W, int(margin), out.ctypes.data))
-            return out
-        ins = [self.dev_upload(m)] + ([] if pr is None else [self.dev_upload(pr)])
-        do = self.dev_alloc(max(H * W, max(m.size, 1)))
-        with self._blocks(ins + [do]):
-            dst = {None: do, "score": ins[0], "prior": ins[-1]}[alias]
-            self._chk(self._l.nct_region_refind_dev(self._h, ins[0], ht, wt, None if pr is None else ins[1], H, W, int(margin), dst))
-            return self.dev_download(do, (H, W), np.uint8)
+        with self._seam("region_refind", dev) as s:
+            ms, ps = s.put(m), s.put(pr)
+            out = s.new((max(H, 1), max(W, 1)), np.uint8, dev_shape=(H, W), nbytes=max(H * W, max(m.size, 1)))      # a refused size never reaches the host array
+            s.call(ms, ht, wt, ps, H, W, int(margin), s.over(out, {None: None, "score": ms, "prior": ps or ms}[alias]))
+            return s.get(out)
 
-    def region_model_apply(self, model, src_bgr, prior=None, params=None, want_stages=False, dev=False):
+    def region_model_apply(self, model, src_bgr, prior=None, params=None, want_stages=False, *, dev=False):
         """nct_region_model_apply[_dev] (SPEC §6.17 rules A1 to A4): the model's object re-found on src_bgr [h, w, 3] -> the matte [h, w]; prior [h, w] bytes or None;
-        params: region_refind_params(...) or None for the defaults. want_stages (host form only): -> (matte, {"q" [cells, C] int16, "score" [h_t, w_t], "refound" [h, w]})"""
-        s = np.ascontiguousarray(src_bgr, np.uint8)
+        params: region_refind_params(...) or None for the defaults. want_stages (host form only; refused with dev): -> (matte, {"q" [cells, C] int16, "score"
+        [h_t, w_t], "refound" [h, w]})"""
+        s_ = np.ascontiguousarray(src_bgr, np.uint8)
         pr = None if prior is None else np.ascontiguousarray(prior, np.uint8)
-        if s.ndim != 3 or s.shape[2] != 3 or (pr is not None and pr.shape != s.shape[:2]):
+        if s_.ndim != 3 or s_.shape[2] != 3 or (pr is not None and pr.shape != s_.shape[:2]):
             raise NctError(-2, "region_model_apply: src_bgr must be [h, w, 3] bytes and prior [h, w] bytes or None")
-        h, w = s.shape[:2]
-        pp = C.addressof(params) if params is not None else None
-        if dev:
-            ins = [self.dev_upload(s)] + ([] if pr is None else [self.dev_upload(pr)])
-            do = self.dev_alloc(h * w)
-            with self._blocks(ins + [do]):
-                self._chk(self._l.nct_region_model_apply_dev(self._h, model._m, ins[0], h, w, None if pr is None else ins[1], pp, do))
-                return self.dev_download(do, (h, w), np.uint8)
-        out = np.empty((h, w), np.uint8)
-        prp = None if pr is None else pr.ctypes.data
-        if not want_stages:
-            self._chk(self._l.nct_region_model_apply(self._h, model._m, s.ctypes.data, h, w, prp, pp, out.ctypes.data, None))
-            return out
-        tap, Cc, _, _ = model.info()
-        ht, wt = ((h - 1) >> (tap - 1)) + 1, ((w - 1) >> (tap - 1)) + 1
-        st = {"q": np.zeros((ht * wt, Cc), np.int16), "score": np.zeros((ht, wt), np.uint8), "refound": np.zeros((h, w), np.uint8)}
-        cs = RegionApplyStages(*[st[k].ctypes.data for k in ("q", "score", "refound")])
-        self._chk(self._l.nct_region_model_apply(self._h, model._m, s.ctypes.data, h, w, prp, pp, out.ctypes.data, C.addressof(cs)))
-        return out, st
+        if want_stages and dev:
+            raise NctError(-2, "region_model_apply: want_stages is host-only (nct_region_model_apply_dev reports no stages)")
+        h, w = s_.shape[:2]
+        st, cs = None, None
+        if want_stages:
+            tap, Cc, _, _ = model.info()
+            ht, wt = ((h - 1) >> (tap - 1)) + 1, ((w - 1) >> (tap - 1)) + 1
+            st = {"q": np.zeros((ht * wt, Cc), np.int16), "score": np.zeros((ht, wt), np.uint8), "refound": np.zeros((h, w), np.uint8)}
+            cs = RegionApplyStages(*[st[k].ctypes.data for k in ("q", "score", "refound")])
+        with self._seam("region_model_apply", dev) as s:
+            ss, ps, out = s.put(s_), s.put(pr), s.new((h, w), np.uint8)
+            s.call(model._m, ss, h, w, ps, C.addressof(params) if params is not None else None, out, host_only=[C.addressof(cs) if cs is not None else None])
+            return (s.get(out), st) if want_stages else s.get(out)
 
     def pair_apply_region_model(self, model, params=None, protect=None):
         """nct_pair_apply_region_model: region_model_apply without a prior on the uploaded source, then pair_set_region with the matte, which stays on the device"""
@@ -1801,49 +1743,32 @@ class Context:
         name = "nct_seq_frame_propagate_region_levels" if _region else "nct_seq_frame_propagate_levels"
         return self._seq_region_call(name, s, {"dims": g.src}, g, q.levels if q is not None else 0, _region)
 
-    def seq_warp(self, x_prev, field):
-        """nct_seq_warp (SPEC §6.5 rule 3): x_prev [2, h*w, 3] doubles, field int16 [h, w, 2] of (my, mx) -> x_prev read at p + m(p), the 64-bit words copied"""
+    def seq_warp(self, x_prev, field, *, dev=False, alias=False):
+        """nct_seq_warp[_dev] (SPEC §6.5 rule 3): x_prev [2, h*w, 3] doubles, field int16 [h, w, 2] of (my, mx) -> x_prev read at p + m(p), the 64-bit words copied.
+        alias (device form): into x_prev's block, which is an error"""
         f = np.ascontiguousarray(field, np.int16)
         h, w = f.shape[:2]
         a = np.ascontiguousarray(x_prev, np.float64).reshape(-1)
         assert a.size == 6 * h * w and f.size == 2 * h * w
-        out = np.empty((2, h * w, 3))
-        self._chk(self._l.nct_seq_warp(self._h, a, h, w, f.ctypes.data, out.reshape(-1)))
-        return out
+        with self._seam("seq_warp", dev) as s:
+            xs, fs, out = s.put(a), s.put(f), s.new((2, h * w, 3), np.float64)
+            s.call(xs, h, w, fs, s.over(out, xs if alias else None))
+            return s.get(out)
 
-    def seq_warp_dev(self, x_prev, field, alias=False):
-        """the same through nct_seq_warp_dev on arena blocks, into a block of its own (alias: into x_prev's block, which is an error)"""
-        f = np.ascontiguousarray(field, np.int16)
-        h, w = f.shape[:2]
-        n = h * w
-        ins = [self.dev_upload(np.ascontiguousarray(x_prev, np.float64).reshape(-1)), self.dev_upload(f)]
-        do = self.dev_alloc(48 * n)
-        with self._blocks(ins + [do]):
-            self._chk(self._l.nct_seq_warp_dev(self._h, ins[0], h, w, ins[1], ins[0] if alias else do))
-            return self.dev_download(do, (2, n, 3), np.float64)
 
     # ---- adaptive key frames (SPEC §6.7)
-    def seq_change(self, lab, lab_prev, field=None, threshold=24):
-        """nct_seq_change (SPEC §6.7 rule 1): lab / lab_prev h x w x 3 8-bit Lab, field None or int16 [h, w, 2] of (my, mx) -> {"sad", "changed", "pixels"}"""
+    def seq_change(self, lab, lab_prev, field=None, threshold=24, *, dev=False):
+        """nct_seq_change[_dev] (SPEC §6.7 rule 1): lab / lab_prev h x w x 3 8-bit Lab, field None or int16 [h, w, 2] of (my, mx) -> {"sad", "changed", "pixels"}.
+        The device form's record block holds 0xff bytes before the call"""
         a = np.ascontiguousarray(lab, np.uint8)
         b = np.ascontiguousarray(lab_prev, np.uint8)
         h, w = a.shape[:2]
         f = None if field is None else np.ascontiguousarray(field, np.int16)
         assert b.shape == a.shape and (f is None or f.size == 2 * h * w)
-        rec = SeqChange()
-        self._chk(self._l.nct_seq_change(self._h, a.ctypes.data, b.ctypes.data, h, w, _ptr(f), int(threshold), C.addressof(rec)))
-        return rec.as_dict()
-
-    def seq_change_dev(self, lab, lab_prev, field=None, threshold=24):
-        """the same through nct_seq_change_dev on arena blocks; the record's block holds 0xff bytes before the call"""
-        a = np.ascontiguousarray(lab, np.uint8)
-        h, w = a.shape[:2]
-        ins = [self.dev_upload(a), self.dev_upload(np.ascontiguousarray(lab_prev, np.uint8))] + ([] if field is None else [self.dev_upload(np.ascontiguousarray(field, np.int16))])
-        do = self.dev_upload(np.full(16, 0xff, np.uint8))
-        with self._blocks(ins + [do]):
-            self._chk(self._l.nct_seq_change_dev(self._h, ins[0], ins[1], h, w, None if field is None else ins[2], int(threshold), do))
-            raw = self.dev_download(do, (16,), np.uint8)
-            return SeqChange.from_buffer_copy(raw.tobytes()).as_dict()
+        with self._seam("seq_change", dev) as s:
+            as_, bs, fs, rec = s.put(a), s.put(b), s.put(f), s.new((C.sizeof(SeqChange),), np.uint8, fill=0xff)
+            s.call(as_, bs, h, w, fs, int(threshold), rec)
+            return SeqChange.from_buffer_copy(s.get(rec).tobytes()).as_dict()
 
     def seq_probe(self, src_bgr, auto=None):
         """nct_seq_probe (SPEC §6.7 rule 2): the decision the frame would get on the open sequence, nothing changed -> dict (SeqDecision.as_dict); auto: a SeqAuto or
@@ -1864,51 +1789,43 @@ class Context:
         return (out, d.as_dict(), tm.as_dict()) if want_timing else (out, d.as_dict())
 
     # ---- 3D colour look-up tables (SPEC §6.6)
-    def lut_fit(self, src, res, size=None, lam=None, want_stages=False):
-        """nct_lut_fit: source and result images (any shape [..., 3], uint8 BGR) -> table float32 [N, N, N, 3] (+ {"weight", "resid", "disp"}); size / lam left
+    def lut_fit(self, src, res, size=None, lam=None, want_stages=False, *, dev=False):
+        """nct_lut_fit[_dev]: source and result images (any shape [..., 3], uint8 BGR) -> table float32 [N, N, N, 3] (+ {"weight", "resid", "disp"}); size / lam left
         out are nct_lut_params_default's"""
-        s, r = np.ascontiguousarray(src, np.uint8).reshape(-1, 3), np.ascontiguousarray(res, np.uint8).reshape(-1, 3)
-        assert s.shape == r.shape
-        prm = _lut_params(size, lam)
-        N = prm.size if 0 < prm.size <= 65 else 1                      # a refused size never reaches the arrays
-        lut = np.empty((N, N, N, 3), np.float32)
-        st = {"weight": np.empty(N ** 3, np.uint64), "resid": np.empty((N ** 3, 3), np.int64), "disp": np.empty((N ** 3, 3), np.float64)}
-        cs = LutStages(*(st[k].ctypes.data for k in ("weight", "resid", "disp")))
-        self._chk(self._l.nct_lut_fit(self._h, s.ctypes.data, r.ctypes.data, len(s), C.addressof(prm), lut.ctypes.data, C.addressof(cs) if want_stages else None))
-        return (lut, st) if want_stages else lut
+        return self._lut_fit("lut_fit", src, res, None, size, lam, want_stages, dev)
 
-    def lut_fit_dev(self, src, res, size=None, lam=None, want_stages=False):
-        """the same through nct_lut_fit_dev on arena blocks"""
-        s, r = np.ascontiguousarray(src, np.uint8).reshape(-1, 3), np.ascontiguousarray(res, np.uint8).reshape(-1, 3)
-        prm = _lut_params(size, lam)
-        n3 = prm.size ** 3
-        blocks = [self.dev_upload(s), self.dev_upload(r), self.dev_alloc(12 * n3), self.dev_alloc(8 * n3), self.dev_alloc(24 * n3), self.dev_alloc(24 * n3)]
-        with self._blocks(blocks):
-            cs = LutStages(blocks[3], blocks[4], blocks[5])
-            self._chk(self._l.nct_lut_fit_dev(self._h, blocks[0], blocks[1], len(s), C.addressof(prm), blocks[2], C.addressof(cs) if want_stages else None))
-            lut = self.dev_download(blocks[2], (prm.size,) * 3 + (3,), np.float32)
-            if not want_stages:
-                return lut
-            return lut, {"weight": self.dev_download(blocks[3], (n3,), np.uint64), "resid": self.dev_download(blocks[4], (n3, 3), np.int64),
-                         "disp": self.dev_download(blocks[5], (n3, 3), np.float64)}
+    def lut_fit_masked(self, src, res, mask, size=None, lam=None, want_stages=False, *, dev=False):
+        """nct_lut_fit_masked[_dev] (SPEC §6.11 rule 7): lut_fit over the pixels with mask >= 128 (mask None: lut_fit)"""
+        return self._lut_fit("lut_fit_masked", src, res, mask, size, lam, want_stages, dev)
 
-    def lut_apply(self, lut, img):
-        """nct_lut_apply: table [N, N, N, 3] float32 on an image [..., 3] uint8 BGR -> the image of the same shape"""
+    def _lut_fit(self, name, src, res, mask, size, lam, want_stages, dev):
+        """the two fits: the unmasked one is the masked one without a mask, through its own entry point"""
+        s_, r = np.ascontiguousarray(src, np.uint8).reshape(-1, 3), np.ascontiguousarray(res, np.uint8).reshape(-1, 3)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        assert s_.shape == r.shape and (m is None or len(m) == len(s_))
+        prm = _lut_params(size, lam)
+        n = prm.size
+        N = n if 0 < n <= 65 else 1                                # a refused size never reaches the host arrays; the device form asks for it as it stands
+        spec = {"weight": ((), np.uint64), "resid": ((3,), np.int64), "disp": ((3,), np.float64)}
+        with self._seam(name, dev) as s:
+            ss, rs = s.put(s_), s.put(r)
+            lut = s.new((N, N, N, 3), np.float32, dev_shape=(n, n, n, 3))
+            st = {k: s.new((N ** 3,) + tail, t, dev_shape=(n ** 3,) + tail) for k, (tail, t) in spec.items()}
+            ms = [s.put(m)] if name == "lut_fit_masked" else []        # the mask goes up behind the four output blocks
+            cs = LutStages(*(st[k].ptr for k in ("weight", "resid", "disp")))
+            s.call(ss, rs, *ms, len(s_), C.addressof(prm), lut, C.addressof(cs) if want_stages else None)
+            return (s.get(lut), {k: s.get(v) for k, v in st.items()}) if want_stages else s.get(lut)
+
+    def lut_apply(self, lut, img, *, dev=False, in_place=False):
+        """nct_lut_apply[_dev]: table [N, N, N, 3] float32 on an image [..., 3] uint8 BGR -> the image of the same shape. in_place (device form): the output over
+        the input"""
         t = np.ascontiguousarray(lut, np.float32)
         a = np.ascontiguousarray(img, np.uint8)
-        out = np.empty_like(a)
-        self._chk(self._l.nct_lut_apply(self._h, t.ctypes.data, t.shape[0], a.ctypes.data, a.size // 3, out.ctypes.data))
-        return out
-
-    def lut_apply_dev(self, lut, img, in_place=False):
-        """the same through nct_lut_apply_dev on arena blocks (in_place: the output over the input)"""
-        t = np.ascontiguousarray(lut, np.float32)
-        a = np.ascontiguousarray(img, np.uint8)
-        blocks = [self.dev_upload(t), self.dev_upload(a), self.dev_alloc(a.size)]
-        with self._blocks(blocks):
-            dst = blocks[1] if in_place else blocks[2]
-            self._chk(self._l.nct_lut_apply_dev(self._h, blocks[0], t.shape[0], blocks[1], a.size // 3, dst))
-            return self.dev_download(dst, a.shape, np.uint8)
+        with self._seam("lut_apply", dev) as s:
+            ts, as_, out = s.put(t), s.put(a), s.new(a.shape, np.uint8)
+            dst = s.over(out, as_ if in_place else None)
+            s.call(ts, t.shape[0], as_, a.size // 3, dst)
+            return s.get(dst)
 
     def pair_fit_lut(self, size=None, lam=None):
         """nct_pair_fit_lut: the table of the context's last finished run, from the images it holds on the device"""
@@ -1937,79 +1854,41 @@ class Context:
                 setattr(mp, k, int(v))
         self._chk(self._l.nct_seq_set_motion(self._h, C.addressof(mp)))
 
-    def seq_motion_field(self, lab, lab_prev, parent, R, penalty):
-        """nct_seq_motion_field (SPEC §6.4 rules 1-3): lab / lab_prev h x w x 3 8-bit Lab, parent None or the coarser level's field int16 [ph, pw, 2] -> int16 [h, w, 2] of (my, mx)"""
-        lab = np.ascontiguousarray(lab, np.uint8)
+    def seq_motion_field(self, lab, lab_prev, parent, R, penalty, *, dev=False):
+        """nct_seq_motion_field[_dev] (SPEC §6.4 rules 1-3): lab / lab_prev h x w x 3 8-bit Lab, parent None or the coarser level's field int16 [ph, pw, 2] -> int16
+        [h, w, 2] of (my, mx)"""
+        lab, lp = np.ascontiguousarray(lab, np.uint8), np.ascontiguousarray(lab_prev, np.uint8)
         h, w = lab.shape[:2]
         par = None if parent is None else np.ascontiguousarray(parent, np.int16)
         ph, pw = (0, 0) if par is None else par.shape[:2]
-        out = np.empty((h, w, 2), np.int16)
-        self._chk(self._l.nct_seq_motion_field(self._h, lab.reshape(-1, 3), np.ascontiguousarray(lab_prev, np.uint8).reshape(-1, 3), h, w, _ptr(par), ph, pw, int(R), int(penalty), out.ctypes.data))
-        return out
+        with self._seam("seq_motion_field", dev) as s:
+            ls, lps, pars, out = s.put(lab), s.put(lp), s.put(par), s.new((h, w, 2), np.int16)
+            s.call(ls, lps, h, w, pars, ph, pw, int(R), int(penalty), out)
+            return s.get(out)
 
-    def seq_motion_field_dev(self, lab, lab_prev, parent, R, penalty):
-        """the same through nct_seq_motion_field_dev on arena blocks"""
-        lab = np.ascontiguousarray(lab, np.uint8)
-        h, w = lab.shape[:2]
-        par = None if parent is None else np.ascontiguousarray(parent, np.int16)
-        ph, pw = (0, 0) if par is None else par.shape[:2]
-        ins = [self.dev_upload(lab), self.dev_upload(np.ascontiguousarray(lab_prev, np.uint8))] + ([] if par is None else [self.dev_upload(par)])
-        do = self.dev_alloc(4 * h * w)
-        with self._blocks(ins + [do]):
-            self._chk(self._l.nct_seq_motion_field_dev(self._h, ins[0], ins[1], h, w, None if par is None else ins[2], ph, pw, int(R), int(penalty), do))
-            return self.dev_download(do, (h, w, 2), np.int16)
+    def seq_blend(self, x, x_prev, lab, lab_prev, tau, sigma, want_tau_map=True, *, dev=False):
+        """nct_seq_blend[_dev] (SPEC §6.3 rule 3): x, x_prev [2, h*w, 3] doubles, lab / lab_prev h x w x 3 8-bit Lab -> (X', tau_p map [h, w] or None)"""
+        return self._blend("seq_blend", x, x_prev, lab, lab_prev, tau, sigma, None, want_tau_map, False, dev)
 
-    def seq_blend_mc(self, x, x_prev, lab, lab_prev, tau, sigma, field, want_tau_map=True):
-        """nct_seq_blend_mc (SPEC §6.4 rule 4): seq_blend with L_(t-1) and x_prev read through field (int16 [h, w, 2], or None: seq_blend)"""
-        lab = np.ascontiguousarray(lab, np.uint8)
+    def seq_blend_mc(self, x, x_prev, lab, lab_prev, tau, sigma, field, want_tau_map=True, *, dev=False, alias_prev=False):
+        """nct_seq_blend_mc[_dev] (SPEC §6.4 rule 4): seq_blend with L_(t-1) and x_prev read through field (int16 [h, w, 2], or None: seq_blend). alias_prev (device
+        form): into x_prev's block, which a field makes an error"""
+        return self._blend("seq_blend_mc", x, x_prev, lab, lab_prev, tau, sigma, field, want_tau_map, alias_prev, dev)
+
+    def _blend(self, name, x, x_prev, lab, lab_prev, tau, sigma, field, want_tau_map, alias_prev, dev):
+        """the two blends: nct_seq_blend_mc takes the field (or NULL) behind nct_seq_blend's list"""
+        lab, lp = np.ascontiguousarray(lab, np.uint8), np.ascontiguousarray(lab_prev, np.uint8)
         h, w = lab.shape[:2]
         a = np.ascontiguousarray(x, np.float64).reshape(-1)
         b = np.ascontiguousarray(x_prev, np.float64).reshape(-1)
-        assert a.size == 6 * h * w and b.size == 6 * h * w
         f = None if field is None else np.ascontiguousarray(field, np.int16)
-        assert f is None or f.size == 2 * h * w
-        out = np.empty((2, h * w, 3))
-        tm = np.empty((h, w)) if want_tau_map else None
-        self._chk(self._l.nct_seq_blend_mc(self._h, a, b, lab.reshape(-1, 3), np.ascontiguousarray(lab_prev, np.uint8).reshape(-1, 3), h, w, tau, sigma, out.reshape(-1), _ptr(tm), _ptr(f)))
-        return out, tm
-
-    def seq_blend_mc_dev(self, x, x_prev, lab, lab_prev, tau, sigma, field, alias_prev=False):
-        """the same through nct_seq_blend_mc_dev on arena blocks, into a block of its own (alias_prev: into x_prev's block, which a field makes an error)"""
-        lab = np.ascontiguousarray(lab, np.uint8)
-        h, w = lab.shape[:2]
-        n = h * w
-        ins = [self.dev_upload(np.ascontiguousarray(x, np.float64).reshape(-1)), self.dev_upload(np.ascontiguousarray(x_prev, np.float64).reshape(-1)),
-               self.dev_upload(lab), self.dev_upload(np.ascontiguousarray(lab_prev, np.uint8))]
-        if field is not None:
-            ins.append(self.dev_upload(np.ascontiguousarray(field, np.int16)))
-        do, dt = self.dev_alloc(48 * n), self.dev_alloc(8 * n)
-        with self._blocks(ins + [do, dt]):
-            self._chk(self._l.nct_seq_blend_mc_dev(self._h, ins[0], ins[1], ins[2], ins[3], h, w, tau, sigma, ins[1] if alias_prev else do, dt, ins[4] if field is not None else None))
-            return self.dev_download(ins[1] if alias_prev else do, (2, n, 3), np.float64), self.dev_download(dt, (h, w), np.float64)
-
-    def seq_blend(self, x, x_prev, lab, lab_prev, tau, sigma, want_tau_map=True):
-        """nct_seq_blend (SPEC §6.3 rule 3): x, x_prev [2, h*w, 3] doubles, lab / lab_prev h x w x 3 8-bit Lab -> (X', tau_p map [h, w] or None)"""
-        lab = np.ascontiguousarray(lab, np.uint8)
-        h, w = lab.shape[:2]
-        a = np.ascontiguousarray(x, np.float64).reshape(-1)
-        b = np.ascontiguousarray(x_prev, np.float64).reshape(-1)
-        assert a.size == 6 * h * w and b.size == 6 * h * w
-        out = np.empty((2, h * w, 3))
-        tm = np.empty((h, w)) if want_tau_map else None
-        self._chk(self._l.nct_seq_blend(self._h, a, b, lab.reshape(-1, 3), np.ascontiguousarray(lab_prev, np.uint8).reshape(-1, 3), h, w, tau, sigma, out.reshape(-1), _ptr(tm)))
-        return out, tm
-
-    def seq_blend_dev(self, x, x_prev, lab, lab_prev, tau, sigma):
-        """the same through nct_seq_blend_dev: maps uploaded to arena blocks, the launch enqueued on the context's stream (into a block of its own), results downloaded"""
-        lab = np.ascontiguousarray(lab, np.uint8)
-        h, w = lab.shape[:2]
-        n = h * w
-        ins = [self.dev_upload(np.ascontiguousarray(x, np.float64).reshape(-1)), self.dev_upload(np.ascontiguousarray(x_prev, np.float64).reshape(-1)),
-               self.dev_upload(lab), self.dev_upload(np.ascontiguousarray(lab_prev, np.uint8))]
-        do, dt = self.dev_alloc(48 * n), self.dev_alloc(8 * n)
-        with self._blocks(ins + [do, dt]):
-            self._chk(self._l.nct_seq_blend_dev(self._h, ins[0], ins[1], ins[2], ins[3], h, w, tau, sigma, do, dt))
-            return self.dev_download(do, (2, n, 3), np.float64), self.dev_download(dt, (h, w), np.float64)
+        assert a.size == 6 * h * w and b.size == 6 * h * w and (f is None or f.size == 2 * h * w)
+        with self._seam(name, dev) as s:
+            ins, fs = [s.put(a), s.put(b), s.put(lab), s.put(lp)], s.put(f)
+            out, tm = s.new((2, h * w, 3), np.float64), s.new((h, w), np.float64) if want_tau_map else None
+            dst = s.over(out, ins[1] if alias_prev else None)
+            s.call(*ins, h, w, tau, sigma, dst, tm, *([fs] if name == "seq_blend_mc" else []))
+            return s.get(dst).reshape(2, h * w, 3), s.get(tm)
 
     def pair_upload(self, src_bgr, ref_bgr):
         s = np.ascontiguousarray(src_bgr, np.uint8)
@@ -2032,63 +1911,36 @@ class Context:
         return self._run_call("nct_pair_run_levels", prm, keep, lv)
 
     # ---- source region masks (SPEC §6.11)
-    def resize_u8c1(self, img, dh, dw):
-        """nct_resize_u8c1: one-channel uint8 image [h, w] -> [dh, dw]"""
+    def resize_u8c1(self, img, dh, dw, *, dev=False):
+        """nct_resize_u8c1[_dev]: one-channel uint8 image [h, w] -> [dh, dw]"""
         a = np.ascontiguousarray(img, np.uint8)
-        out = np.empty((dh, dw), np.uint8)
-        self._chk(self._l.nct_resize_u8c1(self._h, a.ctypes.data, a.shape[0], a.shape[1], out.ctypes.data, dh, dw))
-        return out
+        with self._seam("resize_u8c1", dev) as s:
+            as_, out = s.put(a), s.new((dh, dw), np.uint8)
+            s.call(as_, a.shape[0], a.shape[1], out, dh, dw)
+            return s.get(out)
 
-    def resize_u8c1_dev(self, img, dh, dw):
-        """the same through nct_resize_u8c1_dev on arena blocks"""
-        a = np.ascontiguousarray(img, np.uint8)
-        blocks = [self.dev_upload(a), self.dev_alloc(dh * dw)]
-        with self._blocks(blocks):
-            self._chk(self._l.nct_resize_u8c1_dev(self._h, blocks[0], a.shape[0], a.shape[1], blocks[1], dh, dw))
-            return self.dev_download(blocks[1], (dh, dw), np.uint8)
-
-    def region_mix(self, x, mask):
-        """nct_region_mix (SPEC §6.11 rule 2): x [2, h*w, 3] doubles, mask [h, w] bytes -> X'"""
+    def region_mix(self, x, mask, *, dev=False, in_place=False):
+        """nct_region_mix[_dev] (SPEC §6.11 rule 2): x [2, h*w, 3] doubles, mask [h, w] bytes -> X'. in_place (device form): over x"""
         m = np.ascontiguousarray(mask, np.uint8)
         h, w = m.shape
         a = np.ascontiguousarray(x, np.float64).reshape(-1)
         assert a.size == 6 * h * w
-        out = np.empty((2, h * w, 3))
-        self._chk(self._l.nct_region_mix(self._h, a.ctypes.data, m.ctypes.data, h, w, out.ctypes.data))
-        return out
+        with self._seam("region_mix", dev) as s:
+            as_, ms, out = s.put(a), s.put(m), s.new((2, h * w, 3), np.float64)
+            dst = s.over(out, as_ if in_place else None)
+            s.call(as_, ms, h, w, dst)
+            return s.get(dst).reshape(2, h * w, 3)
 
-    def region_mix_dev(self, x, mask, in_place=False):
-        """the same through nct_region_mix_dev on arena blocks, into a block of its own (in_place: over x)"""
-        m = np.ascontiguousarray(mask, np.uint8)
-        h, w = m.shape
-        a = np.ascontiguousarray(x, np.float64).reshape(-1)
-        assert a.size == 6 * h * w
-        blocks = [self.dev_upload(a), self.dev_upload(m), self.dev_alloc(48 * h * w)]
-        with self._blocks(blocks):
-            dst = blocks[0] if in_place else blocks[2]
-            self._chk(self._l.nct_region_mix_dev(self._h, blocks[0], blocks[1], h, w, dst))
-            return self.dev_download(dst, (2, h * w, 3), np.float64)
-
-    def region_compose(self, s_bgr, lab_out, mask, protect=None, params=None):
-        """nct_region_compose (SPEC §6.11 rule 3): the source, a finish's 8-bit Lab result and the mask at that size -> the composed BGR image"""
-        s = np.ascontiguousarray(s_bgr, np.uint8)
+    def region_compose(self, s_bgr, lab_out, mask, protect=None, params=None, *, dev=False):
+        """nct_region_compose[_dev] (SPEC §6.11 rule 3): the source, a finish's 8-bit Lab result and the mask at that size -> the composed BGR image"""
+        s_ = np.ascontiguousarray(s_bgr, np.uint8)
         lo, m = np.ascontiguousarray(lab_out, np.uint8), np.ascontiguousarray(mask, np.uint8)
-        assert lo.size == s.size and m.size * 3 == s.size
+        assert lo.size == s_.size and m.size * 3 == s_.size
         prm, rg = params or Params.default(), _region_params(protect)
-        out = np.empty_like(s)
-        self._chk(self._l.nct_region_compose(self._h, s.ctypes.data, lo.ctypes.data, m.ctypes.data, m.size, C.addressof(rg), C.addressof(prm), out.ctypes.data))
-        return out
-
-    def region_compose_dev(self, s_bgr, lab_out, mask, protect=None, params=None):
-        """the same through nct_region_compose_dev on arena blocks"""
-        s = np.ascontiguousarray(s_bgr, np.uint8)
-        lo, m = np.ascontiguousarray(lab_out, np.uint8), np.ascontiguousarray(mask, np.uint8)
-        assert lo.size == s.size and m.size * 3 == s.size
-        prm, rg = params or Params.default(), _region_params(protect)
-        blocks = [self.dev_upload(s), self.dev_upload(lo), self.dev_upload(m), self.dev_alloc(s.size)]
-        with self._blocks(blocks):
-            self._chk(self._l.nct_region_compose_dev(self._h, blocks[0], blocks[1], blocks[2], m.size, C.addressof(rg), C.addressof(prm), blocks[3]))
-            return self.dev_download(blocks[3], s.shape, np.uint8)
+        with self._seam("region_compose", dev) as s:
+            ss, los, ms, out = s.put(s_), s.put(lo), s.put(m), s.new(s_.shape, np.uint8)
+            s.call(ss, los, ms, m.size, C.addressof(rg), C.addressof(prm), out)
+            return s.get(out)
 
     def pair_set_region(self, mask, protect=None):
         """nct_pair_set_region on the uploaded source: mask [h, w] bytes, or None to remove it"""
@@ -2122,35 +1974,6 @@ class Context:
         if finish == FINISH_EXACT:
             return self._process("nct_process_pair_fullres_region", src_bgr, [m, *self._image(ref_bgr), max_side, C.addressof(rg)], params, want_timing)
         return self._process("nct_process_pair_fullres_finish_region", src_bgr, [m, *self._image(ref_bgr), max_side, int(finish), C.addressof(rg)], params, want_timing)
-
-    def lut_fit_masked(self, src, res, mask, size=None, lam=None, want_stages=False):
-        """nct_lut_fit_masked (SPEC §6.11 rule 7): lut_fit over the pixels with mask >= 128 (mask None: lut_fit)"""
-        s, r = np.ascontiguousarray(src, np.uint8).reshape(-1, 3), np.ascontiguousarray(res, np.uint8).reshape(-1, 3)
-        m = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
-        assert s.shape == r.shape and (m is None or len(m) == len(s))
-        prm = _lut_params(size, lam)
-        N = prm.size if 0 < prm.size <= 65 else 1
-        lut = np.empty((N, N, N, 3), np.float32)
-        st = {"weight": np.empty(N ** 3, np.uint64), "resid": np.empty((N ** 3, 3), np.int64), "disp": np.empty((N ** 3, 3), np.float64)}
-        cs = LutStages(*(st[k].ctypes.data for k in ("weight", "resid", "disp")))
-        self._chk(self._l.nct_lut_fit_masked(self._h, s.ctypes.data, r.ctypes.data, _ptr(m), len(s), C.addressof(prm), lut.ctypes.data, C.addressof(cs) if want_stages else None))
-        return (lut, st) if want_stages else lut
-
-    def lut_fit_masked_dev(self, src, res, mask, size=None, lam=None, want_stages=False):
-        """the same through nct_lut_fit_masked_dev on arena blocks"""
-        s, r = np.ascontiguousarray(src, np.uint8).reshape(-1, 3), np.ascontiguousarray(res, np.uint8).reshape(-1, 3)
-        m = np.ascontiguousarray(mask, np.uint8).reshape(-1)
-        prm = _lut_params(size, lam)
-        n3 = prm.size ** 3
-        blocks = [self.dev_upload(s), self.dev_upload(r), self.dev_alloc(12 * n3), self.dev_alloc(8 * n3), self.dev_alloc(24 * n3), self.dev_alloc(24 * n3), self.dev_upload(m)]
-        with self._blocks(blocks):
-            cs = LutStages(blocks[3], blocks[4], blocks[5])
-            self._chk(self._l.nct_lut_fit_masked_dev(self._h, blocks[0], blocks[1], blocks[6], len(s), C.addressof(prm), blocks[2], C.addressof(cs) if want_stages else None))
-            lut = self.dev_download(blocks[2], (prm.size,) * 3 + (3,), np.float32)
-            if not want_stages:
-                return lut
-            return lut, {"weight": self.dev_download(blocks[3], (n3,), np.uint64), "resid": self.dev_download(blocks[4], (n3, 3), np.int64),
-                         "disp": self.dev_download(blocks[5], (n3, 3), np.float64)}
 
     def pair_download(self):
         out = np.empty(self._pair_shape, np.uint8)
@@ -2192,3 +2015,10 @@ class Context:
                                                  _ptr(ann), _ptr(annd), _ptr(bnn), _ptr(bnnd)))
         r = (ms.value, (list(cnt) if count else None), ann, annd)
         return r + (bnn, bnnd) if both else r
+
+
+# the seams whose device form also has a method of its own, X_dev(...) = X(..., dev=True); a new seam gets one body and, only if it needs this spelling, a row here
+_DEV_SPELLING = ("color_finish_upsample", "color_finish_guided", "color_finish_upsample_region", "color_finish_guided_region", "select_reference", "region_pull", "seq_warp",
+                 "seq_blend", "seq_blend_mc", "seq_motion_field", "seq_change", "lut_fit", "lut_fit_masked", "lut_apply", "resize_u8c1", "region_mix", "region_compose")
+for _name in _DEV_SPELLING:
+    setattr(Context, _name + "_dev", functools.partialmethod(getattr(Context, _name), dev=True))

@@ -21,7 +21,6 @@ grids, every nullable argument in both of its forms, the row stride, stream orde
 
 Not here: pointers off their natural alignment. The maps are read as float4 rows and the NNFs as words, so their alignment is part of the contract; the one
 operand without any, the image rows of the VGG seams, is what test_row_stride misaligns."""
-import contextlib
 import ctypes as C
 
 import numpy as np
@@ -53,28 +52,6 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(bits(a), bits(b))
 
 
-@contextlib.contextmanager
-def blocks(c):
-    """the arena blocks of a test: on every way out the stream is synchronised, then those still held go back"""
-    held = []
-
-    class B:
-        def up(self, a):
-            held.append(c.dev_upload(a)); return held[-1]
-
-        def new(self, nbytes):
-            held.append(c.dev_alloc(nbytes)); return held[-1]
-
-        def free(self, p):
-            held.remove(p); c.dev_free(p)
-    try:
-        yield B()
-    finally:
-        c.synchronize()
-        for p in held:
-            c.dev_free(p)
-
-
 # ---------------------------------------------------------------- layout
 # one element; odd everything; one channel tile with a part-filled pixel tile; two channel tiles, the second with one channel; several tiles each way; C past 512;
 # and the long axis: 1025 * 2049 pixels are 65 633 tiles of 32, which nct_hwc_to_chw_dev's launch carries on grid.y — past 65 535; the runtime takes it
@@ -90,7 +67,7 @@ def test_layout(ctx, shape):
     x = np.random.default_rng(n).integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
     special = np.array([0x80000000, 0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00001, 0x7F800001, 0x7FFFFFFF, 0x00000001], np.uint32)   # -0, +-inf, quiet / signalling NaNs, a denormal
     x[np.arange(special.size) * 7 % n] = special
-    with blocks(ctx) as b:
+    with ctx.blocks() as b:
         src, dst = b.up(x), b.new(4 * n)
         ctx.dev_call("chw_to_hwc", src, dst, Cc, H, W)
         assert np.array_equal(ctx.dev_download(dst, (H, W, Cc), np.uint32), np.transpose(x.reshape(Cc, H, W), (1, 2, 0)))
@@ -102,7 +79,7 @@ def test_layout(ctx, shape):
 def dev_normalize(c, f, want_resp=False):
     """nct_feat_normalize_dev on a CHW host map -> CHW (and the response), in the host form's shape"""
     Cc, H, W = f.shape
-    with blocks(c) as b:
+    with c.blocks() as b:
         src, dst, rp = b.up(to_hwc(f)), b.new(4 * f.size), b.new(4 * H * W) if want_resp else None
         c.dev_call("feat_normalize", src, dst, rp, Cc, H, W)
         out = to_chw(c.dev_download(dst, (H, W, Cc), np.float32))
@@ -111,7 +88,7 @@ def dev_normalize(c, f, want_resp=False):
 
 def dev_feature_distance(c, a, bmap):
     Cc, H, W = a.shape
-    with blocks(c) as b:
+    with c.blocks() as b:
         pa, pb, err = b.up(to_hwc(a)), b.up(to_hwc(bmap)), b.new(4 * H * W)
         c.dev_call("feature_distance", pa, pb, err, Cc, H, W)
         return c.dev_download(err, (H, W), np.float32)
@@ -157,7 +134,7 @@ def test_feature_distance(ctx, Cc):
 @pytest.mark.parametrize("dims", [(2, 2, 5, 3), (2, 2, 1, 1), (17, 23, 31, 17)])
 def test_nnf_init(ctx, dims):
     ah, aw, bh, bw = dims
-    with blocks(ctx) as b:
+    with ctx.blocks() as b:
         nnf = b.new(4 * ah * aw)
         ctx.dev_call("nnf_init", nnf, ah, aw, bh, bw)
         got = ctx.dev_download(nnf, (ah, aw), np.uint32)
@@ -170,7 +147,7 @@ def test_nnf_init(ctx, dims):
 def test_nnf_upsample(ctx, dims):
     ahh, awh, ah, aw, bh, bw = dims
     half = synth.random_nnf(5, ahh, awh, (bh + 1) // 2, (bw + 1) // 2)
-    with blocks(ctx) as b:
+    with ctx.blocks() as b:
         ph, nnf = b.up(half), b.new(4 * ah * aw)
         ctx.dev_call("nnf_upsample", ph, nnf, ah, aw, bh, bw, ahh, awh)
         got = ctx.dev_download(nnf, (ah, aw), np.uint32)
@@ -204,7 +181,7 @@ def test_patchmatch(ctx, Cc):
     The 17 x 23 grid has dead feature pixels in both maps."""
     for dims in PM_GRIDS:
         ah, aw, bh, bw = dims
-        with blocks(ctx) as b:
+        with ctx.blocks() as b:
             pa, a, pb, bm = pm_maps(ctx, b, Cc, dims, dead=dims == PM_GRIDS[2])
             nnf0 = synth.random_nnf(11, ah, aw, bh, bw)
             pn, pd = b.up(nnf0), b.new(4 * ah * aw)
@@ -225,7 +202,7 @@ def test_patchmatch_bidir(ctx, oracle, Cc, dims):
     sa, sb = 77, 77 ^ 0x5bd1e995
     ann0, bnn0 = synth.random_nnf(1, ah, aw, bh, bw), synth.random_nnf(2, bh, bw, ah, aw)
     runs = []
-    with blocks(ctx) as b:
+    with ctx.blocks() as b:
         pa, a, pb, bm = pm_maps(ctx, b, Cc, dims)
         for unit in (0, 1):
             an, bn, ad, bd = b.up(ann0), b.up(bnn0), b.new(4 * ah * aw), b.new(4 * bh * bw)
@@ -256,7 +233,7 @@ def test_votes(ctx, Cc, weights):
             ann, bnn = _nnf_pair(kind, 3, 4, ah, aw, bh, bw)
             if kind == "collapsed_b" and bh * bw >= 260:
                 assert max_in_degree(bnn, ah, aw) >= 130
-            with blocks(ctx) as b:
+            with ctx.blocks() as b:
                 pa, pb, pp, pi = b.up(ann), b.up(bnn), b.up(to_hwc(pin)), b.up(ib)
                 out, out2, pw, img = b.new(4 * Cc * ah * aw), b.new(4 * Cc * ah * aw), b.new(4 * ah * aw), b.new(3 * ah * aw)
                 ctx.dev_call("bds_vote_features", pa, pb, pp, out, None, Cc, ah, aw, bh, bw, 3, wc, wp)
@@ -296,7 +273,7 @@ def test_row_stride(ctx, vgg):
         assert same_bits(t, e)
     buf = np.full((h, stride), 0xFF, np.uint8)
     buf[:, :3 * w] = img.reshape(h, 3 * w)
-    with blocks(ctx) as b:
+    with ctx.blocks() as b:
         d_img = b.up(buf)
         chw, hwc, chw2 = ([b.new(4 * int(np.prod(s))) for s in shapes] for _ in range(3))
         arr = lambda ps: (C.c_void_p * 5)(*(ps + [None] * 3))
@@ -344,9 +321,9 @@ def test_stream_order(ctx):
 
     alone = []
     for chain in (chain1, chain2):
-        with blocks(ctx) as b:
+        with ctx.blocks() as b:
             alone.append(chain(b, uploads(b))())
-    with blocks(ctx) as b:
+    with ctx.blocks() as b:
         u = uploads(b)                                            # every upload waits for the stream: all of them in front of the chains
         get1 = chain1(b, u)
         get2 = chain2(b, u)
@@ -429,7 +406,7 @@ def test_refusals(vgg):
     n_refused = 0
     with nct.Context(0) as c:
         c.vgg19_load_raw(*vgg)
-        with blocks(c) as b:
+        with c.blocks() as b:
             dev = {k: b.up(v) for k, v in host.items()}
             dev.update({k: b.new(n) for k, n in out_bytes.items()})
             dev["taps"] = (C.c_void_p * 5)(dev["tap0"], None, None, None, None)

@@ -87,8 +87,8 @@ def test_region_refind_dev_unaligned_and_neighbours(ctx, oracle):
     exp = rm.refind(oracle, score, (56, 64), prior, 32)
     n = 56 * 64
     for so, sp in ((0, 0), (1, 0), (0, 2), (3, 1), (4, 4)):
-        blocks = [ctx.dev_upload(score), ctx.dev_upload(np.concatenate([np.zeros(sp, np.uint8), prior.ravel(), np.zeros(8, np.uint8)])), ctx.dev_upload(np.full(n + 16, 0x5a, np.uint8))]
-        with ctx._blocks(blocks):
+        with ctx.blocks() as b:
+            blocks = [b.up(score), b.up(np.concatenate([np.zeros(sp, np.uint8), prior.ravel(), np.zeros(8, np.uint8)])), b.up(np.full(n + 16, 0x5a, np.uint8))]
             ctx._chk(ctx._l.nct_region_refind_dev(ctx._h, blocks[0], 28, 32, blocks[1] + sp, 56, 64, 32, blocks[2] + so))
             whole = ctx.dev_download(blocks[2], (n + 16,), np.uint8)
             assert np.array_equal(whole[so:so + n].reshape(56, 64), exp), (so, sp)
@@ -101,9 +101,9 @@ def test_region_refind_bench_hook(ctx, oracle):
     """the measurement hook runs the same kernel: its output is the rule's, its time positive, its refusals named"""
     case = ((29, 34), (57, 67))
     score, prior = rm.refind_inputs(case, "random", 32)
-    blocks = [ctx.dev_upload(score), ctx.dev_upload(prior), ctx.dev_alloc(57 * 67)]
     ms = C.c_float(-1)
-    with ctx._blocks(blocks):
+    with ctx.blocks() as b:
+        blocks = [b.up(score), b.up(prior), b.new(57 * 67)]
         args = [blocks[0], 29, 34, blocks[1], 57, 67, 32, blocks[2]]
         ctx._chk(ctx._l.nct_region_refind_bench(ctx._h, *args, 3, C.byref(ms)))
         assert ms.value > 0 and np.array_equal(ctx.dev_download(blocks[2], (57, 67), np.uint8), rm.refind(oracle, score, (57, 67), prior, 32))
@@ -290,8 +290,8 @@ def test_region_model_apply_refusals(wctx, weights, sources):
         raw_refused(wctx, "nct_region_model_apply", args + [None], INVALID, word)
         raw_refused(wctx, "nct_region_model_apply_dev", args, INVALID, word)
     # the device form refuses a mask_out that overlaps an input
-    blocks = [wctx.dev_upload(nxt), wctx.dev_upload(out)]
-    with wctx._blocks(blocks):
+    with wctx.blocks() as b:
+        blocks = [b.up(nxt), b.up(out)]
         raw_refused(wctx, "nct_region_model_apply_dev", [model._m, blocks[0], H, W, blocks[1], None, blocks[1]], INVALID, "overlap prior")
         raw_refused(wctx, "nct_region_model_apply_dev", [model._m, blocks[0], H, W, None, None, blocks[0]], INVALID, "overlap src_bgr")
     ref = synth.image(2000, 48, 60)

@@ -146,9 +146,9 @@ def test_region_score_bench_hook(ctx):
     """the measurement hook runs the same kernel: its output is the rule's, its time positive, its refusals named"""
     rng = np.random.default_rng(3)
     q, si, so = unit_rows(rng, 300, 128), unit_rows(rng, 70, 128), unit_rows(rng, 9, 128)
-    blocks = [ctx.dev_upload(q), ctx.dev_upload(si), ctx.dev_upload(so), ctx.dev_alloc(300)]
     ms = C.c_float(-1)
-    with ctx._blocks(blocks):
+    with ctx.blocks() as b:
+        blocks = [b.up(q), b.up(si), b.up(so), b.new(300)]
         args = [blocks[0], 300, 128, blocks[1], 70, blocks[2], 9, 1024, 700, blocks[3]]
         ctx._chk(ctx._l.nct_region_score_bench(ctx._h, *args, 3, C.byref(ms)))
         assert ms.value > 0 and np.array_equal(ctx.dev_download(blocks[3], (300,), np.uint8), sel.score(q, si, so))

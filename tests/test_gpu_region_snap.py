@@ -96,8 +96,8 @@ def snap_dev_checked(ctx, mask, lab, r, sigma, binary, shift=0):
     Hh, Ww = mask.shape
     sp = nct.RegionSnapParams.default()
     sp.radius, sp.sigma, sp.binary = r, sigma, binary
-    blocks = [ctx.dev_upload(mask), ctx.dev_upload(lab), ctx.dev_upload(np.full(mask.size + 8, 0x5a, np.uint8))]
-    with ctx._blocks(blocks):
+    with ctx.blocks() as b:
+        blocks = [b.up(mask), b.up(lab), b.up(np.full(mask.size + 8, 0x5a, np.uint8))]
         ctx._chk(ctx._l.nct_region_snap_dev(ctx._h, blocks[0], blocks[1], Hh, Ww, C.addressof(sp), blocks[2] + shift))
         whole = ctx.dev_download(blocks[2], (mask.size + 8,), np.uint8)
         return whole, ctx.dev_download(blocks[0], mask.shape, np.uint8), ctx.dev_download(blocks[1], lab.shape, np.uint8)
