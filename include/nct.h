@@ -37,7 +37,8 @@ extern "C" {
  * nct_seq_set_region_snap, and with region selection from strokes, nct_region_select[_dev], nct_feat_quantize[_dev], nct_region_score[_dev], nct_pair_select_region and
  * nct_seq_select_region, and with region models, nct_region_model_*, nct_region_refind[_dev], nct_pair_apply_region_model and nct_seq_set_region_model, and with sequences
  * over several references, nct_seq_begin_multi[_fullres], nct_seq_frame_multi[_stage]_levels, nct_seq_hold, nct_seq_hold_levels and nct_select_reference_hold[_dev], and with reference
- * region masks in sequences, nct_seq_set_ref_region, nct_seq_pull_hold[_dev], nct_seq_pull_levels and nct_seq_frame[_propagate]_ref_region_levels).
+ * region masks in sequences, nct_seq_set_ref_region, nct_seq_pull_hold[_dev], nct_seq_pull_levels and nct_seq_frame[_propagate]_ref_region_levels, and with shot look-up tables and the 16-bit apply,
+ * nct_lut_accum_* and nct_lut_apply_u16[_dev]).
  * A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
 #define NCT_VERSION 118
@@ -529,6 +530,35 @@ int nct_lut_fit_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, const uint8_t* d_res
 int nct_lut_apply(nct_ctx* ctx, const float* lut, int size, const uint8_t* bgr, size_t npix, uint8_t* out_bgr);
 int nct_lut_apply_dev(nct_ctx* ctx, const float* d_lut, int size, const uint8_t* d_bgr, size_t npix, uint8_t* d_out_bgr);
 int nct_pair_fit_lut(nct_ctx* ctx, const nct_lut_params* prm, float* lut_out);
+
+/* ---- shot look-up tables and the 16-bit apply (SPEC §6.20; an extension of §6.6). One table for a whole shot, fitted over many frames, and a table put onto originals
+ * deeper than 8 bits. C ABI and python binding only: no console option.
+ * nct_lut_apply_u16: the table of §6.6 on 16-bit pixels ([npix][3] uint16 BGR, tightly packed), a value v standing for the grey level v / 257. Per axis t = v (N - 1),
+ * i = min(t / 65535, N - 2), f = t - 65535 i, integer weights (65535 - f, f); out_c = the sum over the eight corners of w LUT[c] in double, / 65535^3, * 257, clamped to
+ * [0, 65535] (a NaN becomes 0) and rounded to nearest even. The identity table returns every input; on 257 u the result is within half a 16-bit step plus half an 8-bit
+ * one of 257 times nct_lut_apply's on u. out_bgr16 may be bgr16. The host form refuses a table with a non-finite entry; the _dev form does not look. Refusals as
+ * nct_lut_apply's.
+ * nct_lut_accum_*: one accumulator per context, owned by it from begin to end (device blocks, zeroed at begin), independent of pairs and sequences: it survives
+ * nct_pair_upload, every run, nct_seq_begin / _end / _reset, and goes with nct_destroy. After the adds (S_1, O_1, M_1) ... (S_k, O_k, M_k) its W and R are §6.6 rule 3's
+ * sums over all offered pixels with M >= 128 (mask NULL: every pixel), so nct_lut_accum_solve(lambda) — rules 4-8 on them — gives the table, and in stages W, R and D,
+ * of nct_lut_fit_masked on the arrays laid end to end, bit for bit, in any order of the adds. An add is one splat launch; one whose mask keeps no pixel changes neither
+ * the sums nor pixels_kept. add_dev is enqueued on the context's stream and does not wait. add_run offers the images nct_pair_fit_lut would read after the context's last
+ * finished run (its mask included), from where they lie on the device; without a finished run: NCT_ERR_STATE, nothing changes. solve does not consume: more adds and
+ * another solve give the fit over everything so far. With nothing kept solve returns NCT_ERR_INVALID; solve_dev waits for that one number (only when a masked add
+ * was made) before it enqueues. info: pointers nullable; it waits for the stream where pixels_kept is asked for and a masked add was made.
+ * Limits: 1 <= npix <= 2^26 per add, at most 2^30 pixels offered between begin and end (R stays below 2^62, W below 2^54): the add that would pass it is refused with
+ * NCT_ERR_INVALID from the host-side count, before anything is enqueued. begin while one is open, and every other call without one: NCT_ERR_STATE. A size outside the
+ * set, a lambda that is not finite and greater than 0, a null src / res / lut_out: NCT_ERR_INVALID. */
+int nct_lut_apply_u16(nct_ctx* ctx, const float* lut, int size, const uint16_t* bgr16, size_t npix, uint16_t* out_bgr16);
+int nct_lut_apply_u16_dev(nct_ctx* ctx, const float* d_lut, int size, const uint16_t* d_bgr16, size_t npix, uint16_t* d_out_bgr16);
+int nct_lut_accum_begin(nct_ctx* ctx, int size);
+int nct_lut_accum_add(nct_ctx* ctx, const uint8_t* src_bgr, const uint8_t* res_bgr, const uint8_t* mask /* nullable */, size_t npix);
+int nct_lut_accum_add_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, const uint8_t* d_res_bgr, const uint8_t* d_mask /* nullable */, size_t npix);
+int nct_lut_accum_add_run(nct_ctx* ctx);
+int nct_lut_accum_info(nct_ctx* ctx, int* size, uint64_t* adds, uint64_t* pixels_offered, uint64_t* pixels_kept);
+int nct_lut_accum_solve(nct_ctx* ctx, double lambda, float* lut_out, nct_lut_stages* stages);
+int nct_lut_accum_solve_dev(nct_ctx* ctx, double lambda, float* d_lut_out, nct_lut_stages* d_stages);
+int nct_lut_accum_end(nct_ctx* ctx);
 
 /* ---- source region masks (SPEC §6.11; an extension): recolour only part of the source. A mask M has one byte per SOURCE pixel: 0 keeps the source, 255 is the full
  * transfer, values between are partial. The level masks are the single-channel form of the image pyramid: M_top = M at the working size, M_l = nct_resize_u8c1 of

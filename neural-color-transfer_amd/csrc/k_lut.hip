@@ -1,5 +1,6 @@
 // k_lut.hip — 3D colour look-up tables (SPEC §6.6): the integer splat of a (source, result) pair onto an N^3 lattice, the multigrid solve of the
-// displacement field, the table, and the trilinear apply. tests/lut_ref.py is the numpy form of every operation here, in the same order.
+// displacement field, the table, and the trilinear apply. tests/lut_ref.py is the numpy form of every operation here, in the same order. The apply on 16-bit pixels
+// (SPEC §6.20): tests/lut16_ref.py.
 #include "nct_internal.h"
 
 #define LUT_W3 16581375.0                   // 255^3: the sum of a pixel's eight integer weights
@@ -365,14 +366,83 @@ __global__ __launch_bounds__(256) void k_lut_apply(const float* __restrict__ lut
     }
 }
 
+// ================================================================= 16-bit apply (SPEC §6.20)
+// The table of rule 9 at a 16-bit position: a value v stands for the grey level v / 257, the axis weights are (65535 - f, f), the eight corner weights integers below
+// 2^48 — exact as doubles however they are formed, so the (db, dg) products are hoisted. 6 B in and 6 B out per pixel, four pixels (three 8-byte words) per thread.
+#define LUT16_W3 281462092005375.0          // 65535^3: the sum of a pixel's eight integer weights
+__device__ __forceinline__ void lut_axis16(int v, int N, int& i, int& f) {
+    const int t = v * (N - 1);              // at most 65535 * 64
+    i = min(t / 65535, N - 2);
+    f = t - 65535 * i;
+}
+// pixels p0 .. p0 + 3 of a tightly packed 6-byte image as three 8-byte words (base 8-byte aligned, p0 a multiple of 4), else element by element; cnt <= 4 pixels are valid
+__device__ __forceinline__ void lut_load4x16(const uint16_t* img, long p0, int cnt, bool packed, u64 w[3]) {
+    if (packed && cnt == 4) {
+        const u64* q = (const u64*)(img + p0 * 3);
+        w[0] = q[0]; w[1] = q[1]; w[2] = q[2];
+    } else {
+        w[0] = w[1] = w[2] = 0ull;
+        for (int k = 0; k < cnt * 3; ++k) w[k >> 2] |= (u64)img[p0 * 3 + k] << (16 * (k & 3));
+    }
+}
+__device__ __forceinline__ int lut_half(const u64 w[3], int k) { return (int)((w[k >> 2] >> (16 * (k & 3))) & 65535ull); }
+
+template <bool IN_LDS>
+__global__ __launch_bounds__(256) void k_lut_apply16(const float* __restrict__ lut, int N, const uint16_t* in, long npix, int packed, uint16_t* out) {   // out may be in
+    __shared__ float sl[IN_LDS ? LUT_LDS_FLOATS : 1];
+    const float* tab = lut;
+    if (IN_LDS) {
+        for (int i = threadIdx.x; i < N * N * N * 3; i += 256) sl[i] = lut[i];
+        __syncthreads();
+        tab = sl;
+    }
+    const long groups = (npix + 3) / 4;
+    for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long)gridDim.x * 256) {
+        const long p0 = g * 4;
+        const int cnt = (int)min(4L, npix - p0);
+        u64 w[3], o[3] = {0ull, 0ull, 0ull};
+        lut_load4x16(in, p0, cnt, packed != 0, w);
+        for (int j = 0; j < cnt; ++j) {
+            int ib, fb, ig, fg, ir, fr;
+            lut_axis16(lut_half(w, 3 * j), N, ib, fb); lut_axis16(lut_half(w, 3 * j + 1), N, ig, fg); lut_axis16(lut_half(w, 3 * j + 2), N, ir, fr);
+            const double wr[2] = {(double)(65535 - fr), (double)fr};
+            double acc[3] = {0.0, 0.0, 0.0};
+            for (int pair = 0; pair < 4; ++pair) {
+                const int db = pair >> 1, dg = pair & 1;
+                const double wbg = (double)(db ? fb : 65535 - fb) * (double)(dg ? fg : 65535 - fg);      // below 2^32: exact
+                const float* t = tab + (size_t)(((ib + db) * N + ig + dg) * N + ir) * 3;
+                for (int dr = 0; dr < 2; ++dr) {
+                    const double wt = wbg * wr[dr];                                                       // below 2^48: exact
+                    for (int c = 0; c < 3; ++c) acc[c] += wt * (double)t[3 * dr + c];
+                }
+            }
+            for (int c = 0; c < 3; ++c) {
+                double v = acc[c] / LUT16_W3;
+                v = v * 257.0;
+                v = v > 0.0 ? v : 0.0; v = v < 65535.0 ? v : 65535.0;                   // A1's cast: clamp, then round to nearest even
+                const int k = 3 * j + c;
+                o[k >> 2] |= (u64)(unsigned)(int)rint(v) << (16 * (k & 3));
+            }
+        }
+        if (packed && cnt == 4) { u64* q = (u64*)(out + p0 * 3); q[0] = o[0]; q[1] = o[1]; q[2] = o[2]; }
+        else for (int k = 0; k < cnt * 3; ++k) out[p0 * 3 + k] = (uint16_t)((o[k >> 2] >> (16 * (k & 3))) & 65535ull);
+    }
+}
+
 // ================================================================= launchers
 bool nct_lut_size_ok(int N) { return N == 3 || N == 5 || N == 9 || N == 17 || N == 33 || N == 65; }
 
-int nctk_lut_splat(nct_ctx* ctx, hipStream_t s, const uint8_t* src, const uint8_t* res, long npix, int N, uint64_t* W, int64_t* R) {
+int nctk_lut_accum_zero(nct_ctx* ctx, hipStream_t s, int N, uint64_t* W, int64_t* R, uint64_t* kept) {
     const size_t n3 = (size_t)N * N * N;
-    // the arena clears nothing: the accumulators are zeroed on the stream in front of the splat
     NCT_HIP(hipMemsetAsync(W, 0, n3 * sizeof(uint64_t), s));
     NCT_HIP(hipMemsetAsync(R, 0, n3 * 3 * sizeof(int64_t), s));
+    if (kept) NCT_HIP(hipMemsetAsync(kept, 0, sizeof(uint64_t), s));
+    return NCT_OK;
+}
+
+int nctk_lut_splat(nct_ctx* ctx, hipStream_t s, const uint8_t* src, const uint8_t* res, long npix, int N, uint64_t* W, int64_t* R, bool accumulate) {
+    // the arena clears nothing: the accumulators are zeroed on the stream in front of the splat (accumulate: they hold the sums of earlier splats, SPEC §6.20)
+    if (!accumulate) NCT_TRY(nctk_lut_accum_zero(ctx, s, N, W, R, nullptr));
     long chunk = (npix + 1023) / 1024;                       // at most 1024 workgroups, each a contiguous run of at least 1024 pixels
     chunk = chunk < 1024 ? 1024 : (chunk + 3) / 4 * 4;
     const int grid = (int)((npix + chunk - 1) / chunk);
@@ -382,11 +452,9 @@ int nctk_lut_splat(nct_ctx* ctx, hipStream_t s, const uint8_t* src, const uint8_
     return NCT_OK;
 }
 
-int nctk_lut_splat_masked(nct_ctx* ctx, hipStream_t s, const uint8_t* src, const uint8_t* res, const uint8_t* mask, long npix, int N, uint64_t* W, int64_t* R, uint64_t* kept) {
-    const size_t n3 = (size_t)N * N * N;
-    NCT_HIP(hipMemsetAsync(W, 0, n3 * sizeof(uint64_t), s));
-    NCT_HIP(hipMemsetAsync(R, 0, n3 * 3 * sizeof(int64_t), s));
-    NCT_HIP(hipMemsetAsync(kept, 0, sizeof(uint64_t), s));
+int nctk_lut_splat_masked(nct_ctx* ctx, hipStream_t s, const uint8_t* src, const uint8_t* res, const uint8_t* mask, long npix, int N, uint64_t* W, int64_t* R, uint64_t* kept,
+                          bool accumulate) {
+    if (!accumulate) NCT_TRY(nctk_lut_accum_zero(ctx, s, N, W, R, kept));
     long chunk = (npix + 1023) / 1024;                       // the grid of nctk_lut_splat
     chunk = chunk < 1024 ? 1024 : (chunk + 3) / 4 * 4;
     const int grid = (int)((npix + chunk - 1) / chunk);
@@ -461,6 +529,21 @@ int nctk_lut_apply(nct_ctx* ctx, hipStream_t s, const float* lut, int N, const u
     } else {
         if (grid > 8192) grid = 8192;
         k_lut_apply<false><<<(int)grid, 256, 0, s>>>(lut, N, in, npix, packed, out);
+    }
+    NCT_LAUNCH_CHECK();
+    return NCT_OK;
+}
+
+int nctk_lut_apply16(nct_ctx* ctx, hipStream_t s, const float* lut, int N, const uint16_t* in, long npix, uint16_t* out) {
+    const long groups = (npix + 3) / 4;
+    const int packed = (((uintptr_t)in | (uintptr_t)out) & 7) == 0;
+    long grid = (groups + 255) / 256;                               // the grids of nctk_lut_apply
+    if (N <= 17) {
+        if (grid > 1024) grid = 1024;
+        k_lut_apply16<true><<<(int)grid, 256, 0, s>>>(lut, N, in, npix, packed, out);
+    } else {
+        if (grid > 8192) grid = 8192;
+        k_lut_apply16<false><<<(int)grid, 256, 0, s>>>(lut, N, in, npix, packed, out);
     }
     NCT_LAUNCH_CHECK();
     return NCT_OK;

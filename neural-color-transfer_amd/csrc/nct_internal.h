@@ -31,6 +31,7 @@ struct nct_ctx {
     void* vgg = nullptr;              // struct vgg_weights* (nct_vgg.cpp)
     void* cvt = nullptr;              // struct cvt_dev* (k_cvt.hip): colour-conversion LUTs on the device
     void* pair = nullptr;             // struct pair_state* (nct_pipeline.h): device-resident source/reference/result images
+    void* lut_accum = nullptr;        // struct lut_accum* (nct_lut.cpp): the shot accumulator between nct_lut_accum_begin and _end (SPEC §6.20)
     unsigned long long* d_counter = nullptr;   // device counters of the pm kernels (NCT_FLAG_COUNT_EVALS): [0] distance evaluations performed, [1] accepted candidates;
                                                 // 4 slots per pyramid level in pair runs (nct_pipeline.cpp reads [4 l] and [4 l + 1])
     int home_xcd = 0;                           // the XCD this context's single-XCD launches aim at (k_s1.hip: small S1 levels); contexts of a process count round-robin (nct_create)
@@ -370,17 +371,29 @@ int nct_region_refind_check(nct_ctx* ctx, const char* who, const void* score, in
 #define NCT_LUT_CYCLES 17
 #define NCT_LUT_MAX_PIXELS (1L << 26)
 bool nct_lut_size_ok(int N);
-int nctk_lut_splat(nct_ctx* ctx, hipStream_t s, const uint8_t* src, const uint8_t* res, long npix, int N, uint64_t* W, int64_t* R);
+// accumulate (SPEC §6.20, the shot accumulator): the splat adds to what W and R (and kept) hold — nothing is zeroed; nctk_lut_accum_zero is that zeroing alone (kept nullable)
+int nctk_lut_accum_zero(nct_ctx* ctx, hipStream_t s, int N, uint64_t* W, int64_t* R, uint64_t* kept);
+int nctk_lut_splat(nct_ctx* ctx, hipStream_t s, const uint8_t* src, const uint8_t* res, long npix, int N, uint64_t* W, int64_t* R, bool accumulate = false);
 int nctk_lut_solve(nct_ctx* ctx, hipStream_t s, const uint64_t* W, const int64_t* R, int N, double lambda, double* D);
 int nctk_lut_table(nct_ctx* ctx, hipStream_t s, const double* D, int N, float* lut);
 int nctk_lut_apply(nct_ctx* ctx, hipStream_t s, const float* lut, int N, const uint8_t* in, long npix, uint8_t* out);
+// SPEC §6.20: the table on 16-bit pixels ([npix][3] uint16, a value v standing for the grey level v / 257); in / out may be the same buffer
+int nctk_lut_apply16(nct_ctx* ctx, hipStream_t s, const float* lut, int N, const uint16_t* in, long npix, uint16_t* out);
+// the shot accumulator's cap on the pixels offered between begin and end: R stays below 2^62, W below 2^54 (SPEC §6.20)
+#define NCT_LUT_ACCUM_MAX_PIXELS (1ULL << 30)
+void nct_lut_accum_free(nct_ctx* ctx);   // nct_lut.cpp
+// nct_pipeline.cpp — the images nct_pair_fit_lut reads after the context's last finished run (SPEC §6.6 rule 10), on the device; mask (null: every pixel) at their size.
+// false: no finished run
+struct nct_lut_images { const uint8_t *src, *res, *mask; size_t npix; };
+bool nct_pair_lut_images(nct_ctx* ctx, nct_lut_images* im);
 // nct_lut.cpp: the checks of nct_lut_fit's arguments (`what` names the entry point in the message), and splat + solve + table on device pointers, enqueued on the
 // main stream; stages (nullable, its arrays nullable): DEVICE pointers
 int nct_lut_fit_check(nct_ctx* ctx, const char* what, const void* src, const void* res, size_t npix, const nct_lut_params* prm, const void* lut_out);
 int nct_lut_fit_enqueue(nct_ctx* ctx, const uint8_t* d_src, const uint8_t* d_res, size_t npix, const nct_lut_params* prm, float* d_lut, const nct_lut_stages* d_stages);
 // SPEC §6.11 rule 7: the splat over the pixels with mask >= 128; kept (8 bytes on the device, zeroed on s): how many there were. nct_lut_fit_enqueue_masked: the fit with
 // that splat (d_mask non-null); it waits for the splat to learn whether any pixel was kept and refuses an empty fit with NCT_ERR_INVALID (`what` names the entry point)
-int nctk_lut_splat_masked(nct_ctx* ctx, hipStream_t s, const uint8_t* src, const uint8_t* res, const uint8_t* mask, long npix, int N, uint64_t* W, int64_t* R, uint64_t* kept);
+int nctk_lut_splat_masked(nct_ctx* ctx, hipStream_t s, const uint8_t* src, const uint8_t* res, const uint8_t* mask, long npix, int N, uint64_t* W, int64_t* R, uint64_t* kept,
+                          bool accumulate = false);
 int nct_lut_fit_enqueue_masked(nct_ctx* ctx, const char* what, const uint8_t* d_src, const uint8_t* d_res, const uint8_t* d_mask, size_t npix, const nct_lut_params* prm, float* d_lut,
                                const nct_lut_stages* d_stages);
 // k_region.hip — source region masks (SPEC §6.11). The single-channel form of nctk_resize_u8c3; the mix of coefficients x ([2][h*w][3]) toward the identity by the level

@@ -969,26 +969,32 @@ static int fullres_run(nct_ctx* ctx, const uint8_t* src_bgr, int sh, int sw, con
 // SPEC §6.6 rule 10: the table of the last finished run, from the images the context still holds on the device
 int nct_pair_fit_lut(nct_ctx* ctx, const nct_lut_params* prm, float* lut_out) {
     NCT_CTX_ENTER();
-    pair_state* P = (pair_state*)ctx->pair;
-    const uint8_t *src = nullptr, *res = nullptr, *mask = nullptr; size_t npix = 0;
-    if (P && !P->finished) P = nullptr;
-    // a masked run's table is fitted over its region (SPEC §6.11 rule 7), with the mask at the size of the images it reads
-    if (P && P->full_src && P->full_out) { src = P->full_src; res = P->full_out; mask = P->full_mask; npix = (size_t)P->full_h * P->full_w; }
-    else if (P && P->src && P->out && P->sh > 0) { src = P->src; res = P->out; mask = P->mask; npix = (size_t)P->sh * P->sw; }
-    // a run with a reference mask: its last level's target mask, which has the size of the result (SPEC §6.12 rule 7)
-    if (src && P->fin_mask) mask = P->fin_mask;
-    if (!src) return ctx->fail(NCT_ERR_STATE, "pair_fit_lut: no finished run on this context (nct_pair_run first)");
-    NCT_TRY(nct_lut_fit_check(ctx, "pair_fit_lut", src, res, npix, prm, lut_out));
+    nct_lut_images im;
+    if (!nct_pair_lut_images(ctx, &im)) return ctx->fail(NCT_ERR_STATE, "pair_fit_lut: no finished run on this context (nct_pair_run first)");
+    NCT_TRY(nct_lut_fit_check(ctx, "pair_fit_lut", im.src, im.res, im.npix, prm, lut_out));
     const size_t n = (size_t)prm->size * prm->size * prm->size * 3;
     DevBuf<float> dl(ctx, n);
     if (!dl.ok()) return NCT_ERR_HIP;
-    if (mask) NCT_TRY(nct_lut_fit_enqueue_masked(ctx, "pair_fit_lut", src, res, mask, npix, prm, dl, nullptr));
-    else NCT_TRY(nct_lut_fit_enqueue(ctx, src, res, npix, prm, dl, nullptr));
+    if (im.mask) NCT_TRY(nct_lut_fit_enqueue_masked(ctx, "pair_fit_lut", im.src, im.res, im.mask, im.npix, prm, dl, nullptr));
+    else NCT_TRY(nct_lut_fit_enqueue(ctx, im.src, im.res, im.npix, prm, dl, nullptr));
     NCT_D2H(lut_out, dl, sizeof(float) * n);
     NCT_SYNC();
     return NCT_OK;
 }
 
 }  // extern "C"
+
+// what nct_pair_fit_lut and nct_lut_accum_add_run read: the source and the result of the last finished run, and the mask of a masked one
+bool nct_pair_lut_images(nct_ctx* ctx, nct_lut_images* im) {
+    pair_state* P = (pair_state*)ctx->pair;
+    *im = nct_lut_images{nullptr, nullptr, nullptr, 0};
+    if (!P || !P->finished) return false;
+    // a masked run's table is fitted over its region (SPEC §6.11 rule 7), with the mask at the size of the images it reads
+    if (P->full_src && P->full_out) *im = nct_lut_images{P->full_src, P->full_out, P->full_mask, (size_t)P->full_h * P->full_w};
+    else if (P->src && P->out && P->sh > 0) *im = nct_lut_images{P->src, P->out, P->mask, (size_t)P->sh * P->sw};
+    // a run with a reference mask: its last level's target mask, which has the size of the result (SPEC §6.12 rule 7)
+    if (im->src && P->fin_mask) im->mask = P->fin_mask;
+    return im->src != nullptr;
+}
 
 int pair_set_region_dev(nct_ctx* ctx, const uint8_t* d_mask, const nct_region_params* region) { return pair_set_region_from(ctx, d_mask, region, hipMemcpyDeviceToDevice); }

@@ -128,6 +128,10 @@ SIGNATURES = {
     "nct_seq_frame_auto": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_lut_params_default": (None, [C.c_void_p]),
     "nct_pair_fit_lut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_lut_accum_begin": (C.c_int, [C.c_void_p, C.c_int]),
+    "nct_lut_accum_add_run": (C.c_int, [C.c_void_p]),
+    "nct_lut_accum_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_lut_accum_end": (C.c_int, [C.c_void_p]),
     "nct_region_params_default": (None, [C.c_void_p]),
     "nct_pair_set_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_pair_run_region_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -225,6 +229,9 @@ _TWINS = {
     "nct_lut_fit": [_P, _P, _N, _P, _P, _P],
     "nct_lut_fit_masked": [_P, _P, _P, _N, _P, _P, _P],
     "nct_lut_apply": [_P, _I, _P, _N, _P],
+    "nct_lut_apply_u16": [_P, _I, _P, _N, _P],
+    "nct_lut_accum_add": [_P, _P, _P, _N],
+    "nct_lut_accum_solve": [_D, _P, _P],
     "nct_resize_u8c1": [_P, _I, _I, _P, _I, _I],
     "nct_region_mix": [_P, _P, _I, _I, _P],
     "nct_region_compose": [_P, _P, _P, _N, _P, _P, _P],
@@ -1806,26 +1813,79 @@ class Context:
         prm = _lut_params(size, lam)
         n = prm.size
         N = n if 0 < n <= 65 else 1                                # a refused size never reaches the host arrays; the device form asks for it as it stands
-        spec = {"weight": ((), np.uint64), "resid": ((3,), np.int64), "disp": ((3,), np.float64)}
         with self._seam(name, dev) as s:
             ss, rs = s.put(s_), s.put(r)
-            lut = s.new((N, N, N, 3), np.float32, dev_shape=(n, n, n, 3))
-            st = {k: s.new((N ** 3,) + tail, t, dev_shape=(n ** 3,) + tail) for k, (tail, t) in spec.items()}
+            lut, st, cs = self._lut_outputs(s, N, n)
             ms = [s.put(m)] if name == "lut_fit_masked" else []        # the mask goes up behind the four output blocks
-            cs = LutStages(*(st[k].ptr for k in ("weight", "resid", "disp")))
             s.call(ss, rs, *ms, len(s_), C.addressof(prm), lut, C.addressof(cs) if want_stages else None)
             return (s.get(lut), {k: s.get(v) for k, v in st.items()}) if want_stages else s.get(lut)
+
+    @staticmethod
+    def _lut_outputs(s, N, n):
+        """what a fit or a solve writes, staged on the seam s: the table, the three stages by name and the struct of their pointers. N: the side of the host arrays,
+        n: the side the device form reserves"""
+        spec = {"weight": ((), np.uint64), "resid": ((3,), np.int64), "disp": ((3,), np.float64)}
+        lut = s.new((N, N, N, 3), np.float32, dev_shape=(n, n, n, 3))
+        st = {k: s.new((N ** 3,) + tail, t, dev_shape=(n ** 3,) + tail) for k, (tail, t) in spec.items()}
+        return lut, st, LutStages(*(st[k].ptr for k in ("weight", "resid", "disp")))
 
     def lut_apply(self, lut, img, *, dev=False, in_place=False):
         """nct_lut_apply[_dev]: table [N, N, N, 3] float32 on an image [..., 3] uint8 BGR -> the image of the same shape. in_place (device form): the output over
         the input"""
+        return self._lut_apply("lut_apply", np.uint8, lut, img, dev, in_place)
+
+    def lut_apply_u16(self, lut, img16, *, dev=False, in_place=False):
+        """nct_lut_apply_u16[_dev] (SPEC §6.20): lut_apply on an image [..., 3] uint16 BGR, a value v standing for the grey level v / 257"""
+        return self._lut_apply("lut_apply_u16", np.uint16, lut, img16, dev, in_place)
+
+    def _lut_apply(self, name, dtype, lut, img, dev, in_place):
+        """the two applies: the same call on pixels of another depth"""
         t = np.ascontiguousarray(lut, np.float32)
-        a = np.ascontiguousarray(img, np.uint8)
-        with self._seam("lut_apply", dev) as s:
-            ts, as_, out = s.put(t), s.put(a), s.new(a.shape, np.uint8)
+        a = np.ascontiguousarray(img, dtype)
+        with self._seam(name, dev) as s:
+            ts, as_, out = s.put(t), s.put(a), s.new(a.shape, dtype)
             dst = s.over(out, as_ if in_place else None)
             s.call(ts, t.shape[0], as_, a.size // 3, dst)
             return s.get(dst)
+
+    # ---- the shot accumulator (SPEC §6.20): one table over many frames
+    def lut_accum_begin(self, size):
+        """nct_lut_accum_begin: open the context's accumulator for tables of that lattice size"""
+        self._chk(self._l.nct_lut_accum_begin(self._h, int(size)))
+        self._lut_accum_size = int(size)
+
+    def lut_accum_add(self, src, res, mask=None, *, dev=False):
+        """nct_lut_accum_add[_dev]: offer source and result images (any shape [..., 3], uint8 BGR); mask (bytes, one per pixel): only the pixels with mask >= 128"""
+        s_, r = np.ascontiguousarray(src, np.uint8).reshape(-1, 3), np.ascontiguousarray(res, np.uint8).reshape(-1, 3)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        assert s_.shape == r.shape and (m is None or len(m) == len(s_))
+        with self._seam("lut_accum_add", dev) as s:
+            s.call(s.put(s_), s.put(r), s.put(m), len(s_))
+
+    def lut_accum_add_run(self):
+        """nct_lut_accum_add_run: offer the images pair_fit_lut would read after the context's last finished run, from where they lie on the device"""
+        self._chk(self._l.nct_lut_accum_add_run(self._h))
+
+    def lut_accum_info(self):
+        """nct_lut_accum_info -> {"size", "adds", "pixels_offered", "pixels_kept"}"""
+        size, rest = C.c_int(), [C.c_uint64() for _ in range(3)]
+        self._chk(self._l.nct_lut_accum_info(self._h, C.byref(size), *[C.byref(v) for v in rest]))
+        return dict(zip(("size", "adds", "pixels_offered", "pixels_kept"), [size.value] + [v.value for v in rest]))
+
+    def lut_accum_solve(self, lam=None, want_stages=False, *, dev=False):
+        """nct_lut_accum_solve[_dev]: the table float32 [N, N, N, 3] over everything added so far (+ {"weight", "resid", "disp"}); lam left out is
+        nct_lut_params_default's. The accumulator stays as it is"""
+        n = getattr(self, "_lut_accum_size", 1)                    # without an accumulator nothing is written: the library refuses first
+        lam = LutParams.default().lambda_ if lam is None else float(lam)
+        with self._seam("lut_accum_solve", dev) as s:
+            lut, st, cs = self._lut_outputs(s, n, n)
+            s.call(lam, lut, C.addressof(cs) if want_stages else None)
+            return (s.get(lut), {k: s.get(v) for k, v in st.items()}) if want_stages else s.get(lut)
+
+    def lut_accum_end(self):
+        """nct_lut_accum_end: the accumulator's blocks go back"""
+        self._chk(self._l.nct_lut_accum_end(self._h))
+        self._lut_accum_size = 1
 
     def pair_fit_lut(self, size=None, lam=None):
         """nct_pair_fit_lut: the table of the context's last finished run, from the images it holds on the device"""
