@@ -20,6 +20,8 @@
 // 63/47/34/27/27 (rtol 1e-6) at ~150 us each. Roofline: Infinity-Cache/HBM streaming at 700^2 and 350^2, launch latency below.
 #include "nct_internal.h"
 #include "nct_wls_schedule.h"
+#include "nct_wls_plan.h"
+#include "nct_reduce.h"
 #include <chrono>
 #include <atomic>
 #include <cstdlib>
@@ -76,87 +78,6 @@ struct Lvl { int H, W, n, nine;                                  // nine: 9-poin
 // reads st[k & 1] and (workgroup 0) writes st[(k + 1) & 1]. nactive = number of systems still iterating: the host polls it only every
 // few iterations, and every kernel of an iteration enqueued past convergence returns at once when it is 0.
 struct PState { double gam[6], alp[6], bb[6]; int active[6]; int iters[6]; int nactive; int seq; double rho[6]; };   // rho: r.r the last iteration saw (host-side convergence forecast only); seq: publication number of a host-visible copy (pcg_publish)
-
-// Fixed 256-wide tree s[t] += s[t + off], off = 128 … 1 (the order the oracle mirrors), evaluated with two barriers instead of nine: the two
-// cross-wave steps go through LDS, the six steps inside the first wave are lane shifts (a lane t < off adds the value lane t + off held BEFORE
-// the step, exactly as the array form does; what lanes >= off compute is never used).
-template <int NV>
-__device__ __forceinline__ void mg_block_reduce(double (&v)[NV], double* __restrict__ partial, int lb = -1 /* logical block whose slot receives the sums (default: blockIdx.x) */) {
-    __shared__ double s_red[128 * NV];
-    const int t = threadIdx.x;
-    if (t >= 128) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) s_red[q * 128 + t - 128] = v[q];
-    }
-    __syncthreads();
-    if (t < 128) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) v[q] += s_red[q * 128 + t];            // off = 128
-    }
-    __syncthreads();
-    if (t >= 64 && t < 128) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) s_red[q * 128 + t - 64] = v[q];
-    }
-    __syncthreads();
-    if (t < 64) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) {
-            double x = v[q] + s_red[q * 128 + t];                          // off = 64
-            x += __shfl_down(x, 32); x += __shfl_down(x, 16); x += __shfl_down(x, 8);
-            x += __shfl_down(x, 4); x += __shfl_down(x, 2); x += __shfl_down(x, 1);
-            if (t == 0) partial[(size_t)(lb < 0 ? (int)blockIdx.x : lb) * NV + q] = x;
-        }
-    }
-}
-template <int NV>
-__device__ __forceinline__ void mg_final_reduce(const double* __restrict__ partial, int nb, double (&out)[NV]) {
-    __shared__ double s_fin[256 * NV];
-    const int t = threadIdx.x;
-    double acc[NV];
-#pragma unroll
-    for (int q = 0; q < NV; ++q) acc[q] = 0.0;
-    for (int b = t; b < nb; b += 256)
-#pragma unroll
-        for (int q = 0; q < NV; ++q) acc[q] += partial[(size_t)b * NV + q];
-#pragma unroll
-    for (int q = 0; q < NV; ++q) s_fin[q * 256 + t] = acc[q];
-    __syncthreads();
-    for (int off = 128; off >= 1; off >>= 1) {
-        if (t < off)
-#pragma unroll
-            for (int q = 0; q < NV; ++q) s_fin[q * 256 + t] += s_fin[q * 256 + t + off];
-        __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < NV; ++q) out[q] = s_fin[q * 256];
-    __syncthreads();
-}
-
-// same fixed order over one group of NV values inside records of `stride` doubles
-template <int NV>
-__device__ __forceinline__ void mg_final_reduce_strided(const double* __restrict__ partial, int nb, int stride, double (&out)[NV]) {
-    __shared__ double s_fin2[256 * NV];
-    const int t = threadIdx.x;
-    double acc[NV];
-#pragma unroll
-    for (int q = 0; q < NV; ++q) acc[q] = 0.0;
-    for (int b = t; b < nb; b += 256)
-#pragma unroll
-        for (int q = 0; q < NV; ++q) acc[q] += partial[(size_t)b * stride + q];
-#pragma unroll
-    for (int q = 0; q < NV; ++q) s_fin2[q * 256 + t] = acc[q];
-    __syncthreads();
-    for (int off = 128; off >= 1; off >>= 1) {
-        if (t < off)
-#pragma unroll
-            for (int q = 0; q < NV; ++q) s_fin2[q * 256 + t] += s_fin2[q * 256 + t + off];
-        __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < NV; ++q) out[q] = s_fin2[q * 256];
-    __syncthreads();
-}
 
 // y = M v at pixel i of the FINE level (5-point: diag*v - sum_w w*v_nbr, neighbour order +x, -x, +y, -y)
 template <int NQ, typename F>
@@ -353,9 +274,7 @@ __global__ void k_mg_finish(Lvl L) {
 
 // The small levels of the hierarchy in ONE launch: one 1024-thread workgroup walks levels l0 .. nl-1 (coarse level of at most MG_TAIL_N points each) through
 // the same five stages with the same per-point functions; a stage boundary is a workgroup barrier instead of a kernel boundary (5 launches of ~5 us of dependent
-// latency each per level before: 24 launches and ~0.12 ms per solve at 700x700). Needs pa / pb of level l0 - 1 (k_mg_weights) done.
-constexpr int MG_TAIL_N = 512;
-constexpr int MG_MAXL = 12;
+// latency each per level before: 24 launches and ~0.12 ms per solve at 700x700). Needs pa / pb of level l0 - 1 (k_mg_weights) done. (MG_TAIL_N, MG_MAXL: nct_wls_plan.h)
 struct LvlPack { Lvl lv[MG_MAXL]; };
 __global__ __launch_bounds__(1024) void k_mg_setup_tail(LvlPack P, int l0, int nl, double* pst) {
     const int t = threadIdx.x;
@@ -577,7 +496,7 @@ __global__ __launch_bounds__(mg_threads(TX, TY)) void k_mg_up(const PState* __re
 // block's own system. Point Jacobi cannot smooth along the runs of exactly flat neighbour pairs a photograph has next to its edges (couplings 10^4 apart); the line solves can
 // (PCG iterations 19 -> 13 on the synthetic pair, 35 -> 19 / 44 -> 23 on photographs). Thomas factors: fp64 at set-up, rounded once (k_mg_lines_setup); the
 // solves are fp32 in the oracle's order:  y(0) = r(0), y(i) = r(i) + lm(i) y(i-1);  e(last) = y(last) lp(last), e(i) = (y(i) + w(i, i+1) e(i+1)) lp(i).
-constexpr int LBX = 32, LBY = 16, LBP = LBX + 1, LBN = LBY * LBP + 1;      // block, padded row pitch and plane size in LDS
+constexpr int LBP = LBX + 1, LBN = LBY * LBP + 1;      // padded row pitch and plane size in LDS of a block (LBX x LBY: nct_wls_plan.h)
 constexpr float LINE_OM = 0.9f;
 // lm(i) = w(i-1, i) / p(i-1) (0 at the start of a line), lp(i) = 1 / p(i), p(i) = d(i) - w(i-1, i) lm(i): one thread per line piece
 __global__ void k_mg_lines_setup(Lvl L) {
@@ -743,15 +662,9 @@ __global__ __launch_bounds__(LBX * LBY, 8) void k_mg_block(const PState* __restr
 // — DESIGN.md §9 — a single workgroup has nothing to hide a global round trip with.)
 // Same expressions and operation order as k_mg_down / k_mg_up (stencil E, W, S, N, SE, SW, NE, NW; restriction over the 3x3 block row-major;
 // prolongation over the parents NW, NE, SW, SE), so the cycle is bit-identical to the tile-fused launches it replaces. lv[0] is the first fused
-// level: its rhs lv[0].b was written by the restriction above it, its correction goes to lv[0].x2. The coarsest grid (n <= 64) is solved by
+// level: its rhs lv[0].b was written by the restriction above it, its correction goes to lv[0].x2. The coarsest grid (n <= MG_COARSEST_N) is solved by
 // `sweeps` damped-Jacobi sweeps from zero by one wave (one lane per unknown, the iterate in a register, neighbours through ds_bpermute).
-// P0 = pixels per thread of the first fused level: 1 or 2 (<= 2048 pixels: 44x44 at 700x700; 63x63 at 1000x1000 stays on tile launches — four pixels per thread measured slower)
-constexpr int MID_MAXP0 = 2;      // largest first fused level, in units of 1024 pixels (1 or 2): 2 = the 44x44 level of a 700x700 pair rides in k_mg_mid (same time as its two tile launches, 186 launches fewer per pair)
-static_assert(MID_MAXP0 == 1 || MID_MAXP0 == 2, "k_mg_mid is instantiated for one or two pixels per thread at its first level (four measured slower: DESIGN.md 9)");
-constexpr int MID_T = 1024, MID_P1 = 1, MID_N1 = MID_T * MID_P1, MID_LV = 5;
-// largest level at depth d >= 1 (the first fused level: P0 * 1024); levels shrink ~4x per depth. The levels below the first park their 10 coefficients and 4 prolongation
-// weights per pixel in LDS for the way back up (a workgroup has the CU to itself: 79 KB of the 160 KB), so only right-hand side and iterate stay in registers across the recursion
-constexpr int mid_cap(int d) { return d == 1 ? 1024 : (d == 2 ? 256 : 64); }
+// (the sizes of the fused levels — MID_T, MID_MAXP0, MID_LV, mid_cap — are in nct_wls_plan.h)
 constexpr int mid_stash_off(int d) { return d <= 1 ? 0 : mid_stash_off(d - 1) + 14 * mid_cap(d - 1); }
 constexpr int MID_STASH = mid_stash_off(MID_LV);
 constexpr int mid_ppt(int P0, int D) { return D == 0 ? P0 : (D == 1 ? MID_P1 : 1); }      // pixels per thread at depth D of the fused sub-cycle
@@ -984,11 +897,11 @@ __global__ __launch_bounds__(256) void k_pcg_start(Lvl L, const double* __restri
             acc[q] = rv * rv; acc[NQ + q] = bq * bq;
         }
     }
-    mg_block_reduce<2 * NQ>(acc, partial);
+    block_reduce_store<2 * NQ>(acc, partial);
 }
 template <int NQ>
 __global__ void k_pcg_start_fin(const double* __restrict__ partial, int nb, PState* __restrict__ st, double rtol2, PState* __restrict__ host_out, int seq) {
-    double s[2 * NQ]; mg_final_reduce<2 * NQ>(partial, nb, s);
+    double s[2 * NQ]; final_reduce<2 * NQ>(partial, nb, s);
     if (threadIdx.x < NQ) { const int q = threadIdx.x; st->bb[q] = s[NQ + q]; st->gam[q] = 0; st->alp[q] = 0; st->iters[q] = 0; st->rho[q] = s[q];
                             st->active[q] = (s[q] > rtol2 * s[NQ + q]) ? 1 : 0; }
     __syncthreads();
@@ -1028,13 +941,13 @@ __global__ __launch_bounds__(256) void k_cg_apply(const PState* __restrict__ st,
             acc[q] = rv * u; acc[NQ + q] = y[q] * u; acc[2 * NQ + q] = rv * rv;
         }
     }
-    mg_block_reduce<3 * NQ>(acc, partial, lb);
+    block_reduce_store<3 * NQ>(acc, partial, lb);
 }
 // three workgroups: workgroup j reduces gamma (0), delta (1), rho (2) of all 6 systems in the fixed order
 template <int NQ>
 __global__ void k_cg_fin(const PState* __restrict__ st, const double* __restrict__ partial, int nb, double* __restrict__ sums) {
     if (st->nactive == 0) return;
-    double s[NQ]; mg_final_reduce_strided<NQ>(partial + blockIdx.x * NQ, nb, 3 * NQ, s);
+    double s[NQ]; final_reduce<NQ>(partial + blockIdx.x * NQ, nb, s, 3 * NQ);
     if (threadIdx.x < NQ) sums[blockIdx.x * NQ + threadIdx.x] = s[threadIdx.x];
 }
 // scalars + all four vector recurrences; every workgroup derives the scalars itself, workgroup 0 publishes the next state
@@ -1111,42 +1024,32 @@ struct PartBufs {
     double *x6, *r, *p, *sv, *w, *partial, *sums; PState* st;      // Krylov vectors [NQ][N], reduction scratch, double-buffered state
     vf* rf;                                                         // the residual rounded to fp32: what the V-cycle's finest level reads (written next to r by k_pcg_start / k_cg_update)
     std::vector<Lvl> lv;                                            // the shared operator hierarchy with THIS part's V-cycle vectors (b, x, x2)
+    const WlsPlan* plan;                                            // which kernel cycles through which level, on which grid
     PState* hst;                                                    // two page-locked slots the solver state is published to
     const double* rough;                                            // the data term (right-hand side = rough * x0)
     nct_ctx* kt;                                                    // kernel clock (NCT_FLAG_TIME_KERNELS, unsplit solves only), else null
     const nct_ctx* cfg;                                             // the solve's settings, read only: wls_maxit, wls_forecast, wls_lines, wls_trace
     int iters[NQMAX];
 };
-// The kernel form of a V-cycle leg. Tile shapes: bandwidth-bound levels use TXB x TYB tiles; below 100k pixels the legs are latency bound, so a 16x8 tile keeps the
-// dependent load chains short and spreads over more CUs. Grid (1-D: mg_tile_of_block maps block -> tile) and block follow from the tile shape.
-constexpr int TXB = 32, TYB = 16;
-dim3 mg_grid(const Lvl& L, int tx, int ty) { return dim3(cdiv(L.W, tx) * cdiv(L.H, ty)); }
-// down leg of level F, right-hand side b. X0: from the block step's iterate x1 instead of zero: one more halo pixel per side, so 32 x 14 tiles (41 x 23 = 943 threads)
+// The kernel form of a V-cycle leg: the plan (nct_wls_plan.h) says which of the two tile shapes a level uses (`big`) and how many tiles that makes (the grid is 1-D:
+// mg_tile_of_block maps block -> tile); the block follows from the tile shape.
+// down leg of level F, right-hand side b. X0: from the block step's iterate x1 instead of zero
 template <int NQ, bool NINE, bool X0>
-void launch_down(hipStream_t s, const PState* st, const Lvl& F, const vf* b, const Lvl& C, const vf* x1) {
-    constexpr int TYL = X0 ? TYB - 2 : TYB;
-    if (F.n >= 100000) hipLaunchKernelGGL((k_mg_down<NQ, TXB, TYL, vf, NINE, X0>), mg_grid(F, TXB, TYL), dim3(mg_threads(TXB, TYL, X0)), 0, s, st, F, b, F.x, C, C.b, x1);
-    else               hipLaunchKernelGGL((k_mg_down<NQ, 16, 8, vf, NINE, X0>), mg_grid(F, 16, 8), dim3(mg_threads(16, 8, X0)), 0, s, st, F, b, F.x, C, C.b, x1);
+void launch_down(hipStream_t s, const PState* st, bool big, const WlsLeg& g, const Lvl& F, const vf* b, const Lvl& C, const vf* x1) {
+    constexpr int TYL = X0 ? TYB_X0 : TYB;
+    if (big) hipLaunchKernelGGL((k_mg_down<NQ, TXB, TYL, vf, NINE, X0>), dim3(g.tiles), dim3(mg_threads(TXB, TYL, X0)), 0, s, st, F, b, F.x, C, C.b, x1);
+    else     hipLaunchKernelGGL((k_mg_down<NQ, TXS, TYS, vf, NINE, X0>), dim3(g.tiles), dim3(mg_threads(TXS, TYS, X0)), 0, s, st, F, b, F.x, C, C.b, x1);
 }
 // up leg of level L, right-hand side b, coarse correction C.x2; L.x2 = where level L's correction ends up (the leg cannot write in place: neighbouring tiles still read L.x)
 template <int NQ, bool NINE>
-void launch_up(hipStream_t s, const PState* st, const Lvl& L, const vf* b, const Lvl& C) {
-    if (L.n >= 100000) hipLaunchKernelGGL((k_mg_up<NQ, TXB, TYB, vf, NINE>), mg_grid(L, TXB, TYB), dim3(mg_threads(TXB, TYB)), 0, s, st, L, b, (const vf*)L.x, C.W, C.n, (const vf*)C.x2, L.x2);
-    else               hipLaunchKernelGGL((k_mg_up<NQ, 16, 8, vf, NINE>), mg_grid(L, 16, 8), dim3(mg_threads(16, 8)), 0, s, st, L, b, (const vf*)L.x, C.W, C.n, (const vf*)C.x2, L.x2);
+void launch_up(hipStream_t s, const PState* st, bool big, const WlsLeg& g, const Lvl& L, const vf* b, const Lvl& C) {
+    if (big) hipLaunchKernelGGL((k_mg_up<NQ, TXB, TYB, vf, NINE>), dim3(g.tiles), dim3(mg_threads(TXB, TYB)), 0, s, st, L, b, (const vf*)L.x, C.W, C.n, (const vf*)C.x2, L.x2);
+    else     hipLaunchKernelGGL((k_mg_up<NQ, TXS, TYS, vf, NINE>), dim3(g.tiles), dim3(mg_threads(TXS, TYS)), 0, s, st, L, b, (const vf*)L.x, C.W, C.n, (const vf*)C.x2, L.x2);
 }
-// The levels of the fused middle + tail (k_mg_mid), tail0 = nl - pack.nl to nl - 1: the deepest run of levels whose first has <= 4096 pixels and the others
-// <= MID_N1, at most MID_LV of them; never the fine level (its right-hand side is the fp64 PCG residual and its tiles fill the chip)
-MidPack mid_levels(const std::vector<Lvl>& lv) {
-    const int nl = (int)lv.size();
-    auto mid_fits = [&](int first) {                     // levels first .. nl-1 as depths 0 .. of k_mg_mid
-        if (nl - first > MID_LV) return false;
-        for (int l = first; l < nl; ++l) { const int d = l - first; if (lv[l].n > (d == 0 ? MID_MAXP0 * MID_T : mid_cap(d))) return false; }
-        return true;
-    };
-    int tail0 = nl - 1;
-    while (tail0 > 1 && mid_fits(tail0 - 1)) --tail0;
-    MidPack pack; memset(&pack, 0, sizeof pack); pack.nl = nl - tail0;
-    for (int l = tail0; l < nl; ++l) pack.lv[l - tail0] = lv[l];
+// The levels of the fused middle + tail (k_mg_mid): the plan's tail0 .. nl - 1
+MidPack mid_levels(const WlsPlan& P, const std::vector<Lvl>& lv) {
+    MidPack pack; memset(&pack, 0, sizeof pack); pack.nl = P.pack_nl;
+    for (int l = P.tail0; l < P.nl; ++l) pack.lv[l - P.tail0] = lv[l];
     return pack;
 }
 // Convergence is polled without draining the stream: the update kernel of the last iteration of every batch publishes the solver
@@ -1167,6 +1070,7 @@ int wait_published(ErrSink* ctx, hipStream_t s, const PState* slot, int want_seq
 template <int NQ>
 int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(s) */, PartBufs& B, double rtol) {
     const std::vector<Lvl>& lv = B.lv;
+    const WlsPlan& P = *B.plan;
     const Lvl& F = lv[0];
     const int N = F.n, nb = cdiv(N, 256);
     const PState* cur = B.st;                             // B.st[0] / B.st[1]; `cur` = the state the iteration being enqueued reads
@@ -1177,22 +1081,22 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
     hipLaunchKernelGGL(k_pcg_start_fin<NQ>, dim3(1), dim3(256), 0, s, (const double*)B.partial, nb, B.st, rtol2, &B.hst[0], seq_of_slot[0]); LCHK();
     // z = Vcycle(r). Levels 0..nl-2 run the tile-fused down/up legs (2 launches per level), the coarsest grid one wave per right-hand side.
     auto down = [&](int l) {
-        if (l == 0 && lines) launch_down<NQ, false, true>(s, cur, lv[0], B.rf, lv[1], lv[0].x2);
-        else if (l == 0)       launch_down<NQ, false, false>(s, cur, lv[0], B.rf, lv[1], nullptr);
-        else                   launch_down<NQ, true, false>(s, cur, lv[l], lv[l].b, lv[l + 1], nullptr);
+        if (l == 0 && lines) launch_down<NQ, false, true>(s, cur, P.big[0], P.down_x0, lv[0], B.rf, lv[1], lv[0].x2);
+        else if (l == 0)       launch_down<NQ, false, false>(s, cur, P.big[0], P.down[0], lv[0], B.rf, lv[1], nullptr);
+        else                   launch_down<NQ, true, false>(s, cur, P.big[l], P.down[l], lv[l], lv[l].b, lv[l + 1], nullptr);
     };
     // the block step (finest level): from zero into x2 in front of the down leg; mirrored, x2 -> x (the pre-smoothed iterate there is dead by then), behind the up leg
     auto block_step = [&](bool post) {
-        const dim3 gl(cdiv(lv[0].W, LBX) * cdiv(lv[0].H, LBY));
+        const dim3 gl(P.blocks);
         if (!post) hipLaunchKernelGGL((k_mg_block<NQ, false>), gl, dim3(LBX * LBY), 0, s, cur, lv[0], (const vf*)B.rf, (const vf*)nullptr, lv[0].x2);
         else       hipLaunchKernelGGL((k_mg_block<NQ, true>), gl, dim3(LBX * LBY), 0, s, cur, lv[0], (const vf*)B.rf, (const vf*)lv[0].x2, lv[0].x);
     };
     auto up = [&](int l) {                                 // (down, block_step, up: the kernels' order of first use, which is their order in the code object)
-        if (l == 0) launch_up<NQ, false>(s, cur, lv[0], B.rf, lv[1]);
-        else        launch_up<NQ, true>(s, cur, lv[l], lv[l].b, lv[l + 1]);
+        if (l == 0) launch_up<NQ, false>(s, cur, P.big[0], P.up[0], lv[0], B.rf, lv[1]);
+        else        launch_up<NQ, true>(s, cur, P.big[l], P.up[l], lv[l], lv[l].b, lv[l + 1]);
     };
-    const MidPack pack = mid_levels(lv);
-    const int tail0 = (int)lv.size() - pack.nl;           // levels tail0 .. run in k_mg_mid
+    const MidPack pack = mid_levels(P, lv);
+    const int tail0 = P.tail0;                            // levels tail0 .. run in k_mg_mid
     bool ktime = false;                                   // this iteration's launches are timed one by one (NCT_FLAG_TIME_KERNELS); kt_b / kt_e do nothing otherwise
     auto kt_b = [&](int id) -> int { if (ktime && B.kt->kt_begin(s, id)) return ctx->fail(NCT_ERR_HIP, "%s", B.kt->err.c_str()); return 0; };
     auto kt_e = [&]() -> int { if (ktime && B.kt->kt_end(s)) return ctx->fail(NCT_ERR_HIP, "%s", B.kt->err.c_str()); return 0; };
@@ -1201,8 +1105,8 @@ int pcg_part(ErrSink* ctx, hipStream_t s, double* X /* this part's [N][3] block(
         NCT_TRY(kt_b(NCT_KT_WLS_DOWN)); down(0); LCHK(); NCT_TRY(kt_e());
         NCT_TRY(kt_b(NCT_KT_WLS_COARSE));
         for (int l = 1; l < tail0; ++l) { down(l); LCHK(); }
-        if (lv[tail0].n <= MID_T) hipLaunchKernelGGL(k_mg_mid<1>, dim3(NQ), dim3(MID_T), 0, s, cur, pack, 60);
-        else                      hipLaunchKernelGGL(k_mg_mid<2>, dim3(NQ), dim3(MID_T), 0, s, cur, pack, 60);
+        if (P.mid_p0 == 1) hipLaunchKernelGGL(k_mg_mid<1>, dim3(NQ), dim3(MID_T), 0, s, cur, pack, 60);
+        else               hipLaunchKernelGGL(k_mg_mid<2>, dim3(NQ), dim3(MID_T), 0, s, cur, pack, 60);
         LCHK();
         for (int l = tail0 - 1; l >= 1; --l) { up(l); LCHK(); }
         NCT_TRY(kt_e());
@@ -1260,12 +1164,12 @@ struct SolveBlocks {
     double* newd(size_t n) { return get<double>(n); }
     vf* newf(size_t n) { return get<vf>(n); }
 };
-// Step 1: the levels — H x W, halved (rounded up) until <= 64 points — with their operator arrays and the first part's V-cycle vectors.
-int mg_alloc_levels(nct_ctx* ctx, SolveBlocks& A, std::vector<Lvl>& lv, int H, int W, int nq0, const double* wx, const double* wy) {
-    int h = H, w = W;
-    for (int l = 0;; ++l) {
-        Lvl L; memset(&L, 0, sizeof L); L.H = h; L.W = w; L.n = h * w; L.nine = l > 0 ? 1 : 0;
-        const bool last = L.n <= 64 || (h <= 8 && w <= 8) || l >= 15;
+// Step 1: the plan's levels with their operator arrays and the first part's V-cycle vectors.
+int mg_alloc_levels(nct_ctx* ctx, SolveBlocks& A, const WlsPlan& P, std::vector<Lvl>& lv, int nq0, const double* wx, const double* wy) {
+    for (int l = 0; l < P.nl; ++l) {
+        const int h = P.H[l], w = P.W[l];
+        Lvl L; memset(&L, 0, sizeof L); L.H = h; L.W = w; L.n = P.n[l]; L.nine = l > 0 ? 1 : 0;
+        const bool last = l == P.nl - 1;
         if (l == 0) { L.wE = (double*)wx; L.wS = (double*)wy; }
         else { L.wE = A.newd(L.n); L.wS = A.newd(L.n); L.wSE = A.newd(L.n); L.wSW = A.newd(L.n); L.fSE = A.newf(L.n); L.fSW = A.newf(L.n); }
         L.d = A.newd(L.n); L.fd = A.newf(L.n); L.fdinv = A.newf(L.n); L.fE = A.newf(L.n); L.fS = A.newf(L.n);
@@ -1275,22 +1179,16 @@ int mg_alloc_levels(nct_ctx* ctx, SolveBlocks& A, std::vector<Lvl>& lv, int H, i
         if (l == 0 && ctx->wls_lines) { L.lxm = A.newf(L.n); L.lxp = A.newf(L.n); L.lym = A.newf(L.n); L.lyp = A.newf(L.n); }
         if (A.failed) return NCT_ERR_HIP;
         lv.push_back(L);
-        if (last) break;
-        h = (h + 1) / 2; w = (w + 1) / 2;
     }
-    if (lv.back().n > 64 || lv.size() < 2) return ctx->fail(NCT_ERR_INVALID, "wls: unsupported grid %dx%d (coarsest level %d)", W, H, lv.back().n);
     return 0;
 }
-// Step 2: the operators of all levels, enqueued on s.
-int mg_build_hierarchy(nct_ctx* ctx, hipStream_t s, SolveBlocks& A, const std::vector<Lvl>& lv, const double* rough) {
-    const int nl = (int)lv.size();
+// Step 2: the operators of all levels, enqueued on s. Levels 1 .. l_tail - 1 take a launch per stage, the rest one launch (k_mg_setup_tail).
+int mg_build_hierarchy(nct_ctx* ctx, hipStream_t s, SolveBlocks& A, const WlsPlan& P, const std::vector<Lvl>& lv, const double* rough) {
+    const int nl = P.nl, l_tail = P.l_tail;
     double* pst = A.get<double>((size_t)lv[1].n * 9);             // columns of P as 3x3 blocks, reused level by level
     if (A.failed) return NCT_ERR_HIP;
     hipLaunchKernelGGL(k_mg_diag, dim3(cdiv(lv[0].n, 256)), dim3(256), 0, s, lv[0], rough); LCHK();
     if (ctx->wls_lines) { hipLaunchKernelGGL(k_mg_lines_setup, dim3(cdiv(lv[0].H * cdiv(lv[0].W, LBX) + lv[0].W * cdiv(lv[0].H, LBY), 128)), dim3(128), 0, s, lv[0]); LCHK(); }
-    int l_tail = nl;                                            // first level built by k_mg_setup_tail
-    for (int l = 1; l < nl; ++l) if (lv[l].n <= MG_TAIL_N) { l_tail = l; break; }
-    if (nl > MG_MAXL) l_tail = nl;
     for (int l = 0; l < l_tail; ++l) {
         const dim3 g(cdiv(lv[l].n, 256));
         if (l > 0) {
@@ -1302,15 +1200,13 @@ int mg_build_hierarchy(nct_ctx* ctx, hipStream_t s, SolveBlocks& A, const std::v
         }
         if (l + 1 < nl) { hipLaunchKernelGGL(k_mg_weights, g, dim3(256), 0, s, lv[l]); LCHK(); }
     }
-    if (l_tail < nl) {
-        LvlPack P;
-        for (int l = 0; l < nl; ++l) P.lv[l] = lv[l];
-        hipLaunchKernelGGL(k_mg_setup_tail, dim3(1), dim3(1024), 0, s, P, l_tail, nl, pst); LCHK();
-    }
+    LvlPack pack;                                               // (l_tail < nl <= MG_MAXL: nct_wls_plan.h)
+    for (int l = 0; l < nl; ++l) pack.lv[l] = lv[l];
+    hipLaunchKernelGGL(k_mg_setup_tail, dim3(1), dim3(1024), 0, s, pack, l_tail, nl, pst); LCHK();
     return 0;
 }
 // Step 3: what part h (of the split solve: 0 = the a-half, 1 = the b-half) owns. The second part gets V-cycle vectors of its own beside the shared operators.
-int mg_alloc_part(nct_ctx* ctx, SolveBlocks& A, PartBufs& B, int h, const std::vector<Lvl>& lv, int nq0, const double* rough) {
+int mg_alloc_part(nct_ctx* ctx, SolveBlocks& A, PartBufs& B, int h, const WlsPlan& P, const std::vector<Lvl>& lv, int nq0, const double* rough) {
     const size_t v = (size_t)lv[0].n * nq0;
     B.rf = A.newf(v);
     B.x6 = A.newd(v); B.r = A.newd(v); B.p = A.newd(v); B.sv = A.newd(v); B.w = A.newd(v); B.partial = A.newd((size_t)cdiv(lv[0].n, 256) * 3 * nq0); B.sums = A.newd(3 * nq0);
@@ -1322,7 +1218,7 @@ int mg_alloc_part(nct_ctx* ctx, SolveBlocks& A, PartBufs& B, int h, const std::v
     }
     static_assert(4 * sizeof(PState) <= 4096, "pinned read-back area too small");
     B.hst = (PState*)ctx->pinned + 2 * h;
-    B.cfg = ctx; B.rough = rough;
+    B.cfg = ctx; B.rough = rough; B.plan = &P;
     B.kt = (ctx->kt_on && !ctx->wls_split) ? ctx : nullptr;
     memset(B.iters, 0, sizeof B.iters);
     return A.failed ? NCT_ERR_HIP : 0;
@@ -1338,12 +1234,14 @@ int nctk_wls_solve_mg(nct_ctx* ctx, hipStream_t s, double* X, const double* roug
                       double rtol, int* iters_out /*host[6], nullable*/) {
     const bool split = ctx->wls_split != 0;
     const int nq0 = split ? 3 : 6;
+    WlsPlan plan;
+    if (!wls_plan(H, W, plan)) return ctx->fail(NCT_ERR_INVALID, "wls: unsupported grid %dx%d (coarsest level %d)", W, H, plan.n[plan.nl - 1]);
     SolveBlocks blocks{ctx};
     std::vector<Lvl> lv;
-    NCT_TRY(mg_alloc_levels(ctx, blocks, lv, H, W, nq0, wx, wy));
-    NCT_TRY(mg_build_hierarchy(ctx, s, blocks, lv, rough));
+    NCT_TRY(mg_alloc_levels(ctx, blocks, plan, lv, nq0, wx, wy));
+    NCT_TRY(mg_build_hierarchy(ctx, s, blocks, plan, lv, rough));
     PartBufs part[2];                                          // both parts' buffers before anything runs: the helper thread must not touch the arena
-    for (int h = 0; h < (split ? 2 : 1); ++h) NCT_TRY(mg_alloc_part(ctx, blocks, part[h], h, lv, nq0, rough));
+    for (int h = 0; h < (split ? 2 : 1); ++h) NCT_TRY(mg_alloc_part(ctx, blocks, part[h], h, plan, lv, nq0, rough));
     ErrSink sink[2]; int rc[2] = {0, 0};
     hipError_t e1 = hipSuccess, e2 = hipSuccess;
     if (!split) rc[0] = pcg_part<6>(&sink[0], s, X, part[0], rtol);

@@ -259,7 +259,7 @@ static inline int nct_params_check(nct_ctx* ctx, const char* who, const nct_para
     return NCT_OK;
 }
 struct nct_color_debug { double *ab_local, *ab_nonlocal, *ab_up, *rough, *ab_wls; int* cg_iters; int* wls_iters; };   // host pointers, all nullable
-// the largest finish target: S2's hierarchy stays within MG_MAXL levels (k_wls_mg.hip) and each of its arrays below 4 GB (6 fp64 right-hand sides: 3.2 GB)
+// the largest finish target: S2's hierarchy stays within MG_MAXL levels (nct_wls_plan.h) and each of its arrays below 4 GB (6 fp64 right-hand sides: 3.2 GB)
 #define NCT_FINISH_MAX_SIDE 16384
 #define NCT_FINISH_MAX_PIXELS (1LL << 26)
 // the upsampling finish behind a working-size finish (SPEC §6.8): the original source in BGR at H x W, where its result goes, the Lab -> BGR form

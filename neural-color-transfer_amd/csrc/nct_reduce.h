@@ -1,4 +1,4 @@
-// nct_reduce.h — deterministic reductions of fp64 values shared by the colour-stage kernels (k_colorsolve.hip, k_s1.hip). Device code only.
+// nct_reduce.h — deterministic reductions of fp64 values shared by the colour-stage kernels (k_colorsolve.hip, k_s1.hip, k_wls_mg.hip). Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,9 +44,10 @@ __device__ __forceinline__ void block_reduce_store(double (&v)[NQ], double* __re
         for (int q = 0; q < NQ; ++q) partial[b * NQ + q] = v[q];
     }
 }
-// sum partial[nb][NQ] in a fixed order (single block of 256 threads): thread t adds its partials b = t, t + 256, … in ascending order, then the same tree
+// sum partial[nb][NQ] in a fixed order (single block of 256 threads): thread t adds its partials b = t, t + 256, … in ascending order, then the same tree.
+// stride: doubles per record, where the NQ values are one group inside a longer record
 template <int NQ>
-__device__ __forceinline__ void final_reduce(const double* __restrict__ partial, int nb, double (&out)[NQ]) {
+__device__ __forceinline__ void final_reduce(const double* __restrict__ partial, int nb, double (&out)[NQ], int stride = NQ) {
     __shared__ double s_fin[128 * NQ];
     __shared__ double s_out[NQ];
     const int t = threadIdx.x;
@@ -55,7 +56,7 @@ __device__ __forceinline__ void final_reduce(const double* __restrict__ partial,
     for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
     for (int b = t; b < nb; b += 256)
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) acc[q] += partial[(size_t)b * NQ + q];
+        for (int q = 0; q < NQ; ++q) acc[q] += partial[(size_t)b * stride + q];
     tree256<NQ>(acc, s_fin);
     if (t == 0) {
 #pragma unroll

@@ -1,24 +1,26 @@
-"""S2's multigrid hierarchy restated in Python, and the grid shapes that change which code of k_wls_mg.hip runs.
+"""S2's multigrid hierarchy restated and checked in Python, and the grid shapes that change which code of k_wls_mg.hip runs.
 Shared by tests/test_s2_shapes.py (CPU: the mirror oracle/orc_wls_mg.c against the exact solve) and tests/test_gpu_s2_shapes.py (the kernels against the mirror).
 
-describe(H, W) restates the host logic of mg_alloc_levels, mg_build_hierarchy, mid_levels and the launchers; FEATURES are predicates on what it returns, so the
-coverage test (test_s2_shapes.py::test_every_feature_has_a_shape) fails when a constant below moves and a feature loses its last shape."""
+describe(H, W) restates the solver's plan (csrc/nct_wls_plan.h: wls_plan, which mg_alloc_levels, mg_build_hierarchy, mid_levels and the launchers read) on its own;
+test_s2_shapes.py::test_describe_equals_the_plan holds it and the constants below against the header, field for field. FEATURES are predicates on what it returns, so the
+coverage test (test_s2_shapes.py::test_every_feature_has_a_shape) fails when a constant moves and a feature loses its last shape."""
 import functools
 import numpy as np
 
 import synth
 from fullres_ref import oracle_finish, smooth_ab
 
-# The shape-dependent constants of neural-color-transfer_amd/csrc/k_wls_mg.hip, restated once:
-COARSEST_N = 64        # mg_alloc_levels: `last = L.n <= 64 || ...` — the levels are halved (rounded up) until one holds at most 64 points
-MG_TAIL_N = 512        # `constexpr int MG_TAIL_N = 512;` — k_mg_setup_tail builds every level from the first one with n <= 512 (mg_build_hierarchy's l_tail)
-MG_MAXL = 12           # `constexpr int MG_MAXL = 12;` — levels k_mg_setup_tail's LvlPack holds
-MID_LV = 5             # `constexpr int MID_T = 1024, MID_P1 = 1, MID_N1 = MID_T * MID_P1, MID_LV = 5;` — depths of k_mg_mid
+# The shape-dependent constants of neural-color-transfer_amd/csrc/nct_wls_plan.h, restated once:
+COARSEST_N = 64        # MG_COARSEST_N — the levels are halved (rounded up) until one holds at most 64 points
+MG_TAIL_N = 512        # k_mg_setup_tail builds every level from the first one with n <= 512 (l_tail)
+MG_MAXL = 12           # levels a hierarchy may have (k_mg_setup_tail's LvlPack); a grid that would need more is refused
+MID_LV = 5             # depths of k_mg_mid
 MID_T = 1024
-MID_MAXP0 = 2          # `constexpr int MID_MAXP0 = 2;` — largest first fused level in units of MID_T pixels (k_mg_mid<1> / k_mg_mid<2>)
-TILE_SWITCH_N = 100000  # launch_down / launch_up: `if (F.n >= 100000)` — 32x16 (up), 32x14 (down behind the block step) tiles, else 16x8
-TXB, TYB, TYB_X0 = 32, 16, 14   # `constexpr int TXB = 32, TYB = 16;`, `TYL = X0 ? TYB - 2 : TYB`
-LBX, LBY = 32, 16      # `constexpr int LBX = 32, LBY = 16` — blocks of the block step (k_mg_block, k_mg_lines_setup)
+MID_MAXP0 = 2          # largest first fused level in units of MID_T pixels (k_mg_mid<1> / k_mg_mid<2>)
+TILE_SWITCH_N = 100000  # MG_TILE_SWITCH_N — from here on a level's legs use 32x16 (up), 32x14 (level 0's down leg behind the block step) tiles, else 16x8
+TXB, TYB, TYB_X0 = 32, 16, 14
+TXS, TYS = 16, 8
+LBX, LBY = 32, 16      # blocks of the block step (k_mg_block, k_mg_lines_setup)
 FINISH_MAX_SIDE, FINISH_MAX_PIXELS = 16384, 1 << 26     # nct.h: NCT_FINISH_MAX_SIDE, NCT_FINISH_MAX_PIXELS
 PAIR_SIDE = (17, 4000)  # sides of a legal pair source (nct_working_size)
 
@@ -33,25 +35,24 @@ def _cdiv(a, b):
 
 
 def level_sizes(H, W):
-    """mg_alloc_levels' loop: [(h, w)] from the finest level down"""
+    """the level loop: [(h, w)] from the finest level down, MG_MAXL of them at the most"""
     out, h, w = [], H, W
     while True:
         out.append((h, w))
-        if h * w <= COARSEST_N or (h <= 8 and w <= 8) or len(out) - 1 >= 15:
+        if h * w <= COARSEST_N or (h <= 8 and w <= 8) or len(out) == MG_MAXL:
             return out
         h, w = (h + 1) // 2, (w + 1) // 2
 
 
 def describe(H, W):
-    """What the host code of k_wls_mg.hip decides for an H x W grid. None: mg_alloc_levels refuses it ("wls: unsupported grid")."""
+    """What the host code of k_wls_mg.hip decides for an H x W grid. None: it refuses the grid ("wls: unsupported grid") — a single level, or still above COARSEST_N
+    points at level MG_MAXL - 1."""
     lv = level_sizes(H, W)
     n = [h * w for h, w in lv]
     nl = len(lv)
     if n[-1] > COARSEST_N or nl < 2:
         return None
-    l_tail = next(l for l in range(1, nl) if n[l] <= MG_TAIL_N)              # mg_build_hierarchy (the coarsest level always qualifies)
-    if nl > MG_MAXL:
-        l_tail = nl
+    l_tail = next(l for l in range(1, nl) if n[l] <= MG_TAIL_N)              # the coarsest level always qualifies
 
     def mid_fits(first):                                                       # mid_levels
         if nl - first > MID_LV:
@@ -71,10 +72,17 @@ def describe(H, W):
     else:
         stop = "cap"
     big = n[0] >= TILE_SWITCH_N
-    return {"H": H, "W": W, "levels": lv, "n": n, "nl": nl, "l_tail": l_tail, "tail0": tail0, "pack_nl": nl - tail0, "mid_p0": 1 if n[tail0] <= MID_T else 2, "mid_stop": stop,
+
+    def leg(l, tx, ty):                                                        # (tile width, tile height, tiles) of a leg of level l
+        return (tx, ty, _cdiv(lv[l][0], ty) * _cdiv(lv[l][1], tx))
+
+    # per tile-launched level: (big tiles, down leg, up leg); level 0's down leg behind the block step is "down_x0"
+    legs = [(True, leg(l, TXB, TYB), leg(l, TXB, TYB)) if n[l] >= TILE_SWITCH_N else (False, leg(l, TXS, TYS), leg(l, TXS, TYS)) for l in range(tail0)]
+    return {"legs": legs, "down_x0": leg(0, TXB, TYB_X0) if big else leg(0, TXS, TYS),
+            "H": H, "W": W, "levels": lv, "n": n, "nl": nl, "l_tail": l_tail, "tail0": tail0, "pack_nl": nl - tail0, "mid_p0": 1 if n[tail0] <= MID_T else 2, "mid_stop": stop,
             "tiles_big": big,
             "tiles_up": (_cdiv(H, TYB), _cdiv(W, TXB)), "tiles_down": (_cdiv(H, TYB_X0), _cdiv(W, TXB)),           # (tile rows, tile columns) of level 0's 32x16 / 32x14 legs
-            "tiles_small": (_cdiv(H, 8), _cdiv(W, 16)), "blocks": (_cdiv(H, LBY), _cdiv(W, LBX))}
+            "tiles_small": (_cdiv(H, TYS), _cdiv(W, TXS)), "blocks": (_cdiv(H, LBY), _cdiv(W, LBX))}
 
 
 def _coarsened(d):
@@ -145,9 +153,9 @@ SHAPES = [
 HW = [(H, W) for H, W, _ in SHAPES]
 # one, two or three pixels high or wide, and the legal sources with a one-pixel level: the second pass (flat sources), the block step off, the split solve
 THIN = [(H, W) for H, W in HW if min(H, W) <= 3 or (H, W) in ((17, 520), (520, 17))]
-# grids mg_alloc_levels refuses (64 points or fewer)
+# grids the solver refuses (64 points or fewer)
 REFUSED = [(8, 8), (1, 64), (4, 16), (1, 1)]
-# No grid within the finish limits has more than MG_MAXL levels, so the `l >= 15` and `nl > MG_MAXL` branches never run: level 11 of an H x W grid holds at most
+# No grid within the finish limits needs more than MG_MAXL levels, so none is refused for its level count: level 11 of an H x W grid holds at most
 # (H / 2048 + 1) (W / 2048 + 1) <= 2^26 / 2^22 + (16384 + 4096) / 2048 + 1 = 27 points, under COARSEST_N. Exactly MG_MAXL levels — k_mg_setup_tail's LvlPack filled to its
 # last slot — are reached only next to the pixel limit: 8193 x 8191 ends 9x8 (72 points), 5x4. test_s2_shapes.py asserts this on the list below; none of it is solved.
 EXTREMES = [(16384, 4096), (4096, 16384), (16384, 1), (1, 16384), (16383, 4095), (8192, 8192), (8193, 8191), (8191, 8193)]

@@ -14,11 +14,11 @@ Read before the first run, once with H == 1 and once with W == 1 in mind, for an
  * k_mg_lines_setup / k_mg_block: pieces of length 1 take line_solve's general path (y(0) = r(0), e(0) = y(0) lp(0), no read at k >= len); the cross terms test
    ly + 1 < bh, ly > 0, lx + 1 < bw, lx > 0; the post step's halo tile is filled and read behind the same image-border tests.
  * mg_tile_of_block: a bijection of [0, ntiles) for every ntiles, fewer than eight included (q = 0: the identity).
- * k_mg_mid: mid_levels admits depth d only up to mid_cap(d) points, which is what sA / sB / sC and the stash offsets are sized for, at a 2x shrink as at 4x (the caps
+ * k_mg_mid: the plan (nct_wls_plan.h) admits depth d only up to mid_cap(d) points, which is what sA / sB / sC and the stash offsets are sized for, at a 2x shrink as at 4x (the caps
    bind earlier and more levels stay on tile launches); depth 3 is capped at 64 points, i.e. it is always the coarsest grid, so the run has at most four levels.
    mid_op, mid_restrict and mid_prolong index behind existence tests. The coarsest wave's lane index (i + dy W + dx) & 63 is used only behind the existence bit.
- * k_mg_setup_tail: strides of 1024 over n of either level; LvlPack holds MG_MAXL = 12 levels and no accepted grid has more; pst is sized for level 1, the largest.
- * mg_alloc_levels refuses a grid of 64 points or fewer after reserving its arrays and before any S2 kernel: what has run by then is the Lab conversion, the copy or
+ * k_mg_setup_tail: strides of 1024 over n of either level; LvlPack holds MG_MAXL = 12 levels and the plan refuses a grid that needs more; pst is sized for level 1, the largest.
+ * nctk_wls_solve_mg refuses a grid of 64 points or fewer from its plan, before it reserves an array or starts an S2 kernel: what has run by then is the Lab conversion, the copy or
    resize, k_roughness, k_gradient_weights and k_wls_system, all one thread per pixel behind i < n (and, for nct_local_color_transfer, T1 / T2 / S1, whose
    operator walks pixels linearly and tests x, y against w, h). lin_coef clamps its source index into [0, size - 1], so U1 from a one-row or one-column grid stays inside.
 """
@@ -137,8 +137,8 @@ def _lct_args(h, w):
 
 
 def test_refused_grids_leave_the_context_usable():
-    """64 points or fewer, through both entry points: NCT_ERR_INVALID with "unsupported grid" — a return of mg_alloc_levels in front of every S2 kernel — and the
-    next valid call (17x17) gives a fresh context's bits: the refused solve's arena blocks went back"""
+    """64 points or fewer, through both entry points: NCT_ERR_INVALID with "unsupported grid" — a return of nctk_wls_solve_mg in front of every S2 kernel — and the
+    next valid call (17x17) gives a fresh context's bits: the refused call's arena blocks went back"""
     with nct.Context(0) as fresh:
         want, want_st = _run(fresh, 17, 17)
     with nct.Context(0) as c:

@@ -2,9 +2,14 @@
 (oracle/orc_wls_mg.c, which the kernels must equal bit for bit: tests/test_gpu_s2_shapes.py) solves the system at every one of them — against the exact float64
 solve within the project's S2 bound and within s2_shapes.MIRROR_DEV_BOUND, four times the largest deviation measured here."""
 import functools
+import os
+import random
+import subprocess
+
 import numpy as np
 import pytest
 
+import nct
 import ref64
 import s2_shapes as S
 from fullres_ref import s2_levels
@@ -51,9 +56,68 @@ def test_every_feature_has_a_shape():
     assert S.describe(17, 520)["levels"][4] == (2, 33) and [lv for lv, _ in S.UPSAMPLE] == [(2, 33), (1, 8), (5, 1)]
 
 
+def _plan_lines(tmp_path, grids):
+    """tests/wls_plan_check.cpp under AddressSanitizer + UBSan on `grids` -> (the header's constants {name: text}, [the words of each grid's line])"""
+    exe = str(tmp_path / "wls_plan_check")
+    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(nct.PKG_ROOT, "csrc"),
+                        os.path.join(os.path.dirname(__file__), "wls_plan_check.cpp"), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([exe], input="".join(f"{H} {W}\n" for H, W in grids), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and not r.stderr, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln.split() for ln in r.stdout.splitlines()]
+    assert lines[0][0] == "const" and len(lines) == 1 + len(grids)
+    return dict(w.split("=") for w in lines[0][1:]), lines[1:]
+
+
+def _describe_words(H, W):
+    """describe(H, W) in the words of wls_plan_check's line"""
+    d = S.describe(H, W)
+    if d is None:
+        lv = S.level_sizes(H, W)
+        return [str(H), str(W), "refused", f"nl={len(lv)}", f"coarsest={lv[-1][0] * lv[-1][1]}"]
+    assert len(d["legs"]) == d["tail0"] and d["legs"][0][0] == d["tiles_big"] and d["n"] == [h * w for h, w in d["levels"]]
+    # the (rows, columns) forms the features read are the same legs
+    up0 = d["tiles_up"] if d["tiles_big"] else d["tiles_small"]
+    down0 = d["tiles_down"] if d["tiles_big"] else d["tiles_small"]
+    assert d["legs"][0][2][2] == up0[0] * up0[1] and d["down_x0"][2] == down0[0] * down0[1]
+    leg = "{}={}x{}:{}".format
+    out = [str(H), str(W), f"nl={d['nl']}", "levels=" + ",".join(f"{h}x{w}:{h * w}" for h, w in d["levels"]), f"l_tail={d['l_tail']}", f"tail0={d['tail0']}",
+           f"pack_nl={d['pack_nl']}", f"mid_p0={d['mid_p0']}", f"blocks={d['blocks'][0] * d['blocks'][1]}", leg("down_x0", *d["down_x0"])]
+    for big, down, up in d["legs"]:
+        out += [f"big={int(big)}", leg("down", *down), leg("up", *up)]
+    return out
+
+
+def test_describe_equals_the_plan(tmp_path):
+    """the constants of s2_shapes.py and describe(H, W) against csrc/nct_wls_plan.h — what k_wls_mg.hip reads — field for field: every grid up to 96 x 96, the shape lists,
+    the two benchmark sizes and 500 sizes drawn inside the finish limits. None of them is refused for its level count, none has a fused run of MID_LV levels."""
+    rng = random.Random(20240611)
+    drawn = []
+    while len(drawn) < 500:                                 # sides log-uniform in [1, FINISH_MAX_SIDE], the pixel limit applied
+        H, W = (int(round(2 ** rng.uniform(0, 14))) for _ in range(2))
+        if H * W <= S.FINISH_MAX_PIXELS:
+            drawn.append((H, W))
+    grids = [(H, W) for H in range(1, 97) for W in range(1, 97)] + S.HW + S.EXTREMES + S.REFUSED + [t for _, t in S.UPSAMPLE] + [lv for lv, _ in S.UPSAMPLE]
+    grids += [(700, 700), (1000, 1000)] + drawn
+    const, lines = _plan_lines(tmp_path, grids)
+    mine = {"COARSEST_N": S.COARSEST_N, "MG_TAIL_N": S.MG_TAIL_N, "MG_MAXL": S.MG_MAXL, "MID_LV": S.MID_LV, "MID_T": S.MID_T, "MID_MAXP0": S.MID_MAXP0,
+            "TILE_SWITCH_N": S.TILE_SWITCH_N, "TXB": S.TXB, "TYB": S.TYB, "TYB_X0": S.TYB_X0, "TXS": S.TXS, "TYS": S.TYS, "LBX": S.LBX, "LBY": S.LBY,
+            "mid_cap": ",".join(str(S.mid_cap(d)) for d in (1, 2, 3, 4))}
+    for k, v in mine.items():
+        assert const[k] == str(v), (k, const[k], v)
+    assert max(H for H, _ in drawn) > 4000 and sum(H * W >= S.TILE_SWITCH_N for H, W in drawn) > 100 and sum(H * W < S.TILE_SWITCH_N for H, W in drawn) > 100
+    for (H, W), words in zip(grids, lines):
+        assert words == _describe_words(H, W), (H, W)
+        d = S.describe(H, W)
+        if d is None:
+            assert H * W <= S.COARSEST_N, (H, W)            # refused for a single level, never for the level count
+        else:
+            assert d["nl"] <= S.MG_MAXL and d["pack_nl"] < S.MID_LV, (H, W)
+
+
 def test_no_accepted_grid_reaches_the_deep_branches():
-    """within the finish limits no hierarchy has more than MG_MAXL levels (the `l >= 15` and `nl > MG_MAXL` branches of mg_alloc_levels / mg_build_hierarchy never run;
-    8193 x 8191 has exactly MG_MAXL), and no fused run has MID_LV levels (depth 3 is capped at 64 points, which ends the hierarchy): described only, not solved"""
+    """within the finish limits no hierarchy needs more than MG_MAXL levels (so the refusal of deeper hierarchies meets no accepted size; 8193 x 8191 has exactly
+    MG_MAXL), and no fused run has MID_LV levels (depth 3 is capped at 64 points, which ends the hierarchy): described only, not solved"""
     for H, W in S.EXTREMES:
         assert H <= S.FINISH_MAX_SIDE and W <= S.FINISH_MAX_SIDE and H * W <= S.FINISH_MAX_PIXELS
         d = S.describe(H, W)
