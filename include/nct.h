@@ -898,6 +898,51 @@ int nct_region_model_apply_dev(nct_ctx* ctx, const nct_region_model* model, cons
 int nct_pair_apply_region_model(nct_ctx* ctx, const nct_region_model* model, const nct_region_refind_params* params, const nct_region_params* region);
 int nct_seq_set_region_model(nct_ctx* ctx, const nct_region_model* model, const nct_region_refind_params* params, const nct_region_params* region);
 
+/* ---- reference libraries (SPEC §6.21; an extension): which of many graded stills suit a source. Every multi-reference call above begins with the caller naming the
+ * references; a reference with nothing in it that matches the source is the usual way the method fails. A library holds, per still, the int8 descriptors of one VGG19
+ * tap; ranking a source against it is one dense integer GEMM with a max epilogue per entry, on the int8 matrix cores, exact in every bit.
+ * (D1) F = tap `tap` (1 … 5) of nct_vgg19_features(image), C channels, on the grid h_t x w_t of §6.16 rule 1; cells = h_t w_t must lie in [1, 65536].
+ * (D2) g(p) = F(p) - mu in fp32 (mu: the library's centre, fp32 [C], or none), u = N1(g) with nct_feat_normalize's summation, d(p)[c] = (int8) rint(u(p)[c] * 127), the
+ *      product in fp32; a non-finite u gives 0.
+ * (D3) P = A B^T in int32 for the source's rows A [na][C] and an entry's rows B [nb][C]; fwd = sum_p max_q P[p][q], bwd = sum_q max_p P[p][q], both int64.
+ * (D4) key = wf floor(fwd 1024 / na) + wb floor(bwd 1024 / nb) in int64, wf and wb integers in [0, 16], not both 0 (default 1, 1: coherence and completeness, as in the
+ *      BDS vote); the order is by descending key, the lower index first on a tie.
+ * nct_feat_quantize8[_dev]: (D2) alone. src_chw: a Caffe blob [C][H][W] (the _dev form: channel-last [H*W][C]); center: [C] or NULL; dst: [H*W][C] int8. C a multiple
+ * of 16 in [16, 4096], H, W in [1, 4096].
+ * nct_descriptor_match[_dev]: (D3) alone. a: [na][C]; rows: the entries' rows end to end, entry k the rows offsets[k] … offsets[k + 1] - 1 (offsets: int32 [N + 1],
+ * offsets[0] = 0); fwd, bwd: int64 [N]. 1 <= na <= 65536, every entry 1 … 65536 rows, N in [1, 4096], C as above, all rows at most 2^31 bytes. In the _dev form a and
+ * rows are device pointers aligned to 16 bytes, fwd and bwd device pointers aligned to 8, and offsets stays a HOST array: the limits are checked on it, then it goes
+ * up and is waited for, the launches are enqueued on the context's stream.
+ * nct_reflib is a host object without a context, like nct_region_model: tap, C, the centre (copied) and the entries' rows with their offsets.
+ * nct_reflib_create: an empty library; C must be the tap's channel count. nct_reflib_add: (D1) and (D2) on bgr (h x w x 3, sides in nct_pair_upload's range [17, 4000]) —
+ * one forward to the tap —, the rows appended as a new entry; NCT_ERR_STATE without weights. nct_reflib_info: tap, C, N, the total rows, whether centred (each
+ * nullable). nct_reflib_rows: host pointers to the rows, the offsets and the centre (NULL without), valid until the next nct_reflib_add or nct_reflib_free.
+ * nct_reflib_from_rows: a library from rows the caller holds (a saved library); needs no context; everything is copied. The calls without a context report a refusal
+ * through nct_last_error(NULL).
+ * nct_reflib_rank: one forward of src_bgr (sides in [17, 4000]) to the library's tap, (D2) with the library's centre, (D3) against every entry, (D4). order: int32 [N];
+ * key, fwd, bwd: int64 [N], each nullable. params NULL: wf 1, wb 1. The context keeps the library's rows on the device in arena blocks, keyed by the library and a
+ * revision counter every add bumps: a second rank against an unchanged library uploads nothing. nct_reflib_release, a rank against another library and nct_destroy give
+ * the blocks back. It works with a pair uploaded or a sequence open and touches neither. Synchronous.
+ * Every refusal is NCT_ERR_INVALID (NCT_ERR_STATE: no weights) with a message that names the argument, before anything is reserved or enqueued.
+ * THE RULE RANKED FIVE ONE-TEXTURE STILLS CORRECTLY WITH SYNTHETIC WEIGHTS, AND CENTRING ON THE LIBRARY'S MEAN TAP VECTOR WIDENED THE MARGINS. Nobody has
+ * measured the rule with the Oxford weights or on photographs. */
+typedef struct nct_reflib nct_reflib;
+typedef struct nct_reflib_params { int wf, wb; } nct_reflib_params;
+void nct_reflib_params_default(nct_reflib_params* p);                   /* 1, 1 */
+int nct_feat_quantize8(nct_ctx* ctx, const float* src_chw, const float* center /* [C], nullable */, int8_t* dst, int C, int H, int W);
+int nct_feat_quantize8_dev(nct_ctx* ctx, const float* d_src_hwc, const float* d_center, int8_t* d_dst, int C, int H, int W);
+int nct_descriptor_match(nct_ctx* ctx, const int8_t* a, int na, int C, const int8_t* rows, const int32_t* offsets /* [N + 1] */, int N, int64_t* fwd, int64_t* bwd);
+int nct_descriptor_match_dev(nct_ctx* ctx, const int8_t* d_a, int na, int C, const int8_t* d_rows, const int32_t* offsets /* HOST, [N + 1] */, int N, int64_t* d_fwd, int64_t* d_bwd);
+int nct_reflib_create(int tap, int C, const float* center /* [C], nullable */, nct_reflib** lib);
+int nct_reflib_add(nct_ctx* ctx, nct_reflib* lib, const uint8_t* bgr, int h, int w);
+int nct_reflib_info(const nct_reflib* lib, int* tap, int* C, int* N, int64_t* total_rows, int* centred);
+int nct_reflib_rows(const nct_reflib* lib, const int8_t** rows, const int32_t** offsets, const float** center);
+int nct_reflib_from_rows(int tap, int C, const float* center /* [C], nullable */, const int8_t* rows, const int32_t* offsets /* [N + 1] */, int N, nct_reflib** lib);
+void nct_reflib_free(nct_reflib* lib);
+int nct_reflib_rank(nct_ctx* ctx, const nct_reflib* lib, const uint8_t* src_bgr, int h, int w, const nct_reflib_params* params, int32_t* order, int64_t* key, int64_t* fwd,
+                    int64_t* bwd);
+int nct_reflib_release(nct_ctx* ctx);
+
 /* ---- device-pointer seams: the same operations on buffers that stay in HBM between calls (main.cu:204-316 keeps Ndata_C1, ann_device, ... on the device
  * across these kernels; an integrator replacing single seams should not pay H2D + D2H + a synchronise per call). Buffers come from the context's arena
  * (nct_dev_alloc / nct_dev_free; any device pointer of the context's GPU works as an operand). Calls are enqueued on the context's stream in call order and return
@@ -965,6 +1010,11 @@ int nct_region_score_bench(nct_ctx* ctx, const int16_t* d_q, int cells, int C, c
 /* the re-find kernel alone (SPEC §6.17 rules R1-R3; scripts/region_refind_times.py): nct_region_refind_dev's arguments; one warm-up launch, then `reps` launches
  * (1 … 1000) between two HIP events on the library's own stream; kernel_ms receives the mean device time of one launch. Synchronous. */
 int nct_region_refind_bench(nct_ctx* ctx, const uint8_t* d_score, int ht, int wt, const uint8_t* d_prior, int H, int W, int margin, uint8_t* d_out, int reps, float* kernel_ms);
+/* the match of reference libraries alone (SPEC §6.21 rule D3; scripts/reflib_times.py): nct_descriptor_match_dev's arguments; one warm-up, then `reps` times (1 … 1000)
+ * its three launches (the fill of the column maxima, the match, the sums) between two HIP events on the library's own stream; kernel_ms receives the mean device time
+ * of one. Synchronous. */
+int nct_descriptor_match_bench(nct_ctx* ctx, const int8_t* d_a, int na, int C, const int8_t* d_rows, const int32_t* offsets, int N, int64_t* d_fwd, int64_t* d_bwd, int reps,
+                               float* kernel_ms);
 
 #ifdef __cplusplus
 }

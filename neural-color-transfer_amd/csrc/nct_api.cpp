@@ -170,6 +170,7 @@ void nct_destroy(nct_ctx* ctx) {
     nct_cvt_free(ctx);
     nct_pair_free(ctx);
     nct_lut_accum_free(ctx);
+    nct_reflib_ctx_free(ctx);
     for (auto& b : ctx->blocks) if (b.p) (void)hipFree(b.p);
     if (ctx->bench_a) (void)hipFree(ctx->bench_a);
     if (ctx->bench_b) (void)hipFree(ctx->bench_b);

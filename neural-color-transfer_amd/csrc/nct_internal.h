@@ -32,6 +32,7 @@ struct nct_ctx {
     void* cvt = nullptr;              // struct cvt_dev* (k_cvt.hip): colour-conversion LUTs on the device
     void* pair = nullptr;             // struct pair_state* (nct_pipeline.h): device-resident source/reference/result images
     void* lut_accum = nullptr;        // struct lut_accum* (nct_lut.cpp): the shot accumulator between nct_lut_accum_begin and _end (SPEC §6.20)
+    void* reflib = nullptr;           // struct reflib_dev* (nct_reflib.cpp): the device copy of the library nct_reflib_rank last ranked against (SPEC §6.21)
     unsigned long long* d_counter = nullptr;   // device counters of the pm kernels (NCT_FLAG_COUNT_EVALS): [0] distance evaluations performed, [1] accepted candidates;
                                                 // 4 slots per pyramid level in pair runs (nct_pipeline.cpp reads [4 l] and [4 l + 1])
     int home_xcd = 0;                           // the XCD this context's single-XCD launches aim at (k_s1.hip: small S1 levels); contexts of a process count round-robin (nct_create)
@@ -366,6 +367,12 @@ int nctk_sel_stamp(nct_ctx* ctx, hipStream_t s, const uint8_t* strokes, size_t n
 int nctk_region_refind(nct_ctx* ctx, hipStream_t s, const uint8_t* score, int ht, int wt, const uint8_t* prior, int H, int W, int margin, uint8_t* out);
 // its argument checks (`who` names the entry point in the message), for the host form to run before it moves anything
 int nct_region_refind_check(nct_ctx* ctx, const char* who, const void* score, int ht, int wt, int H, int W, int margin, const void* out);
+// k_reflib.hip — reference libraries (SPEC §6.21). nctk_feat_quantize8: rule D2 from the raw HWC tap, center ([C] on the device) nullable, int8 rows [HW][C].
+// nctk_descriptor_match: rule D3 — a [na][C], rows (the entries end to end), offsets ([N + 1] on the device; total = offsets[N], which the host knows), fwd / bwd [N]
+// int64; its two transients come from the arena. The limits are the callers' (nct_reflib_host.h: reflib_table_check)
+int nctk_feat_quantize8(nct_ctx* ctx, hipStream_t s, const float* src_hwc, const float* center, int8_t* dst, int C, int HW);
+int nctk_descriptor_match(nct_ctx* ctx, hipStream_t s, const int8_t* a, int na, int C, const int8_t* rows, const int* offsets, int N, int total, long long* fwd, long long* bwd);
+void nct_reflib_ctx_free(nct_ctx* ctx);   // nct_reflib.cpp
 // k_lut.hip — 3D colour look-up tables (SPEC §6.6). W [N^3] / R [N^3][3]: the splat's integer sums (zeroed on s by the splat itself); D [N^3][3]: the displacement
 // field after NCT_LUT_CYCLES V(2,2) cycles; lut [N^3][3] fp32. in / out of the apply may be the same buffer
 #define NCT_LUT_CYCLES 17

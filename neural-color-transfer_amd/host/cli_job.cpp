@@ -1,10 +1,13 @@
 #include "cli_job.h"
+#include <dirent.h>
+#include <algorithm>
 #include <mutex>
 #include "cube_io.h"
 #include "jpeg_io.h"
 
 namespace {
 std::mutex g_print, g_status;
+const RefLibrary* g_library = nullptr;                // -reflib: set by build_reference_library before the workers start, read-only afterwards
 
 std::string stem(const std::string& path) {          // main.cu:524-531 (find_last_of on both separators, strip the extension)
     const size_t pos = path.find_last_of("\\/") + 1;
@@ -86,6 +89,7 @@ void split_refs(Pair& p) {
 // the line's own fault, or an option it cannot be combined with
 std::string refusal(const Config& cfg, const Pair& p) {
     if (!p.err.empty()) return p.err;
+    if (is_auto(p) && cfg.reflib_dir.empty()) return "the reference \"auto\" needs -reflib <dir>";
     if (cfg.fullres && p.refs.size() > 1) return cfg.fullres == 2 ? "-fullres 2 cannot be combined with several references" : "-fullres 1 cannot be combined with several references";
     return "";
 }
@@ -126,6 +130,22 @@ void job_lut(nct_ctx* ctx, const Config& cfg, Job& j) {
     j.say("Look-up table: %d x %d x %d, lambda = %g.\n", lp.size, lp.size, lp.size, lp.lambda);
 }
 
+// the line's reference images, names under `dir`, and with -refmask their masks; false: the job has failed
+static bool load_refs(const Config& cfg, Job& j, const std::string& dir) {
+    std::string err;
+    j.refs.resize(j.p.refs.size());
+    for (size_t k = 0; k < j.refs.size(); ++k) {
+        const std::string refStr = dir + "/" + j.p.refs[k];
+        if (!imgio::read(refStr, j.refs[k], err)) { j.fail("Fail reading style image: " + refStr, "cannot read style image: " + err); return false; }
+        j.say("Read style file: %s, w = %d, h = %d\n", refStr.c_str(), j.refs[k].w, j.refs[k].h);
+    }
+    if (cfg.refmask_dir.empty()) return true;
+    j.refmask.resize(j.refs.size());
+    for (size_t k = 0; k < j.refs.size(); ++k)
+        if (!load_mask(j, cfg.refmask_dir, dir + "/" + j.p.refs[k], j.refs[k], "-refmask", "style", "reference mask", j.refmask[k])) return false;
+    return true;
+}
+
 // in_seq: the line is a frame of a sequence (-seq 1) — its resume check and its reference belong to the sequence, not to the line
 void load_pair(const Config& cfg, Job& j, bool in_seq) {
     j.t0 = std::chrono::steady_clock::now();
@@ -134,8 +154,8 @@ void load_pair(const Config& cfg, Job& j, bool in_seq) {
     const std::string why = refusal(cfg, j.p);
     if (!why.empty()) { j.fail(why); return; }
     const std::string cntStr = cfg.input_dir + "/" + j.p.cnt;
-    j.name = output_name(cfg, j.p);
-    if (!in_seq && cfg.resume && outputs_complete(cfg, j.name)) {           // a truncated file (killed run, full disk) is redone, not skipped
+    j.name = output_name(cfg, j.p);                                         // a line with "auto": until its references are chosen
+    if (!in_seq && !is_auto(j.p) && cfg.resume && outputs_complete(cfg, j.name)) {           // a truncated file (killed run, full disk) is redone, not skipped
         j.say("Skipping (-resume): %s exists.\n\n", j.name.c_str());
         j.state = Job::SKIPPED; return;
     }
@@ -144,16 +164,8 @@ void load_pair(const Config& cfg, Job& j, bool in_seq) {
     j.say("\n**Read content file: %s, w = %d, h = %d\n", cntStr.c_str(), j.cnt.w, j.cnt.h);
     if (in_seq) return;
     if (!cfg.mask_dir.empty() && !load_mask(j, cfg.mask_dir, cntStr, j.cnt, "-mask", "content", "mask", j.mask)) return;
-    j.refs.resize(j.p.refs.size());
-    for (size_t k = 0; k < j.refs.size(); ++k) {
-        const std::string refStr = cfg.input_dir + "/" + j.p.refs[k];
-        if (!imgio::read(refStr, j.refs[k], err)) { j.fail("Fail reading style image: " + refStr, "cannot read style image: " + err); return; }
-        j.say("Read style file: %s, w = %d, h = %d\n", refStr.c_str(), j.refs[k].w, j.refs[k].h);
-    }
-    if (cfg.refmask_dir.empty()) return;
-    j.refmask.resize(j.refs.size());
-    for (size_t k = 0; k < j.refs.size(); ++k)
-        if (!load_mask(j, cfg.refmask_dir, cfg.input_dir + "/" + j.p.refs[k], j.refs[k], "-refmask", "style", "reference mask", j.refmask[k])) return;
+    if (is_auto(j.p)) return;                                               // its references are chosen on the GPU worker: choose_references
+    load_refs(cfg, j, cfg.input_dir);
 }
 
 // the reference's per-level lines (main.cu:331; ColorTransfer.cpp:1373,1434), then its total (main.cu:453); the decoded inputs are dropped
@@ -168,7 +180,86 @@ void log_times(Job& j, const nct_params& prm, const nct_pair_timing& tm) {
     j.refs.clear(); j.refs.shrink_to_fit();
     j.cnt.px.clear(); j.cnt.px.shrink_to_fit();                 // the store stage needs only cnt.h / cnt.w
 }
+// -reflib (SPEC §6.21): the library's images in byte order of their names
+std::string list_reference_library(const Config& cfg, RefLibrary& L) {
+    L.dir = cfg.reflib_dir;
+    DIR* d = opendir(L.dir.c_str());
+    if (!d) return "-reflib: cannot open the directory " + L.dir + ".";
+    while (const dirent* e = readdir(d)) {
+        const std::string n(e->d_name);
+        const size_t dot = n.find_last_of('.');
+        std::string ext = dot == std::string::npos || dot == 0 ? "" : n.substr(dot);
+        std::transform(ext.begin(), ext.end(), ext.begin(), [](unsigned char c) { return (char)tolower(c); });
+        if (ext == ".png" || ext == ".jpg" || ext == ".jpeg") L.names.push_back(n);
+    }
+    closedir(d);
+    std::sort(L.names.begin(), L.names.end());                  // std::string orders by unsigned bytes
+    if (L.names.empty()) return "-reflib: " + L.dir + " holds no image (.png, .jpg).";
+    if (L.names.size() > 4096) return "-reflib: " + L.dir + " holds " + std::to_string(L.names.size()) + " images, a library holds at most 4096.";
+    return "";
+}
+
+// pass 1 (with -refcenter 1): every image's tap through nct_vgg19_features, its channel sums accumulated in double, image after image, in raster order — the centre
+// is their mean as fp32. Pass 2: nct_reflib_add per image
+std::string build_reference_library(nct_ctx* ctx, const Config& cfg, RefLibrary& L) {
+    static const int tapC[5] = {64, 128, 256, 512, 512};
+    const int tap = cfg.reftap, C = tapC[tap - 1];
+    std::vector<ImageBGR> imgs(L.names.size());
+    std::string err;
+    for (size_t k = 0; k < imgs.size(); ++k) {
+        const std::string path = L.dir + "/" + L.names[k];
+        if (!imgio::read(path, imgs[k], err)) return "-reflib: cannot read " + path + ": " + err;
+        if (!shrink(ctx, imgs[k])) return "-reflib: " + path + ": " + nct_last_error(ctx);
+    }
+    std::vector<float> center;
+    if (cfg.refcenter) {
+        std::vector<double> acc((size_t)C, 0.0);
+        double cells = 0.0;
+        std::vector<float> F;
+        for (size_t k = 0; k < imgs.size(); ++k) {
+            const int ht = ((imgs[k].h - 1) >> (tap - 1)) + 1, wt = ((imgs[k].w - 1) >> (tap - 1)) + 1;
+            const size_t n = (size_t)ht * wt;
+            F.resize(n * C);
+            float* taps[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+            taps[tap - 1] = F.data();
+            if (nct_vgg19_features(ctx, imgs[k].px.data(), imgs[k].h, imgs[k].w, 3 * imgs[k].w, tap, taps, nullptr) != NCT_OK)
+                return "-reflib: " + L.dir + "/" + L.names[k] + ": " + nct_last_error(ctx);
+            for (int c = 0; c < C; ++c) for (size_t i = 0; i < n; ++i) acc[c] += (double)F[(size_t)c * n + i];
+            cells += (double)n;
+        }
+        center.resize((size_t)C);
+        for (int c = 0; c < C; ++c) center[c] = (float)(acc[c] / cells);
+    }
+    if (nct_reflib_create(tap, C, cfg.refcenter ? center.data() : nullptr, &L.lib) != NCT_OK) return std::string("-reflib: ") + nct_last_error(nullptr);
+    for (size_t k = 0; k < imgs.size(); ++k)
+        if (nct_reflib_add(ctx, L.lib, imgs[k].px.data(), imgs[k].h, imgs[k].w) != NCT_OK) return "-reflib: " + L.dir + "/" + L.names[k] + ": " + nct_last_error(ctx);
+    printf("Reference library: %zu image(s) of %s at tap %d, %s.\n", L.names.size(), L.dir.c_str(), tap, cfg.refcenter ? "centred on their mean tap vector" : "not centred");
+    g_library = &L;
+    return "";
+}
+
+// a line with "auto": its content image, shrunk as the run will shrink it, is ranked against the library; the first -refk entries become the line's references
+static bool choose_references(nct_ctx* ctx, const Config& cfg, Job& j) {
+    const RefLibrary& L = *g_library;
+    ImageBGR work = j.cnt;
+    if (!shrink(ctx, work)) { j.fail(std::string("resize failed: ") + nct_last_error(ctx), nct_last_error(ctx)); return false; }
+    const size_t N = L.names.size(), K = std::min((size_t)cfg.refk, N);
+    std::vector<int32_t> order(N); std::vector<int64_t> key(N);
+    if (nct_reflib_rank(ctx, L.lib, work.px.data(), work.h, work.w, nullptr, order.data(), key.data(), nullptr, nullptr) != NCT_OK) { j.fail(nct_last_error(ctx)); return false; }
+    j.p.refs.clear(); j.p.stl.clear();
+    std::string chosen;
+    for (size_t k = 0; k < K; ++k) {
+        j.p.refs.push_back(L.names[order[k]]);
+        j.p.stl += (k ? "," : "") + L.names[order[k]];
+        chosen += (k ? ", " : "") + L.names[order[k]] + " (key " + std::to_string((long long)key[order[k]]) + ")";
+    }
+    j.say("Reference library: chose %s of %zu.\n", chosen.c_str(), N);
+    j.name = output_name(cfg, j.p);
+    return load_refs(cfg, j, L.dir);
+}
+
 void run_pair(nct_ctx* ctx, const Config& cfg, Job& j) {
+    if (is_auto(j.p) && !choose_references(ctx, cfg, j)) return;
     nct_params prm = cfg.prm;
     prm.bds_weight = j.p.bds;                                   // the per-line weight overrides -bds (main.cu:475)
     nct_pair_timing tm;                                         // stage times come from stream events: asking for them adds no host synchronisation

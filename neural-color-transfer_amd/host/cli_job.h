@@ -33,6 +33,12 @@ struct Job {
     void fail(const std::string& text) { fail(text, text); }
     double secs() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 };
+// -reflib <dir> (SPEC §6.21): the run's reference library. names: the image files of <dir> in byte order; lib: their descriptors, entry k = names[k]. Listed and
+// built once per process, before the workers start, which then share it read-only: a line whose style field is "auto" ranks its content image against it
+struct RefLibrary { std::string dir; std::vector<std::string> names; nct_reflib* lib = nullptr; };
+std::string list_reference_library(const Config& cfg, RefLibrary& L);                  // the files (no GPU); the text behind "Error: ", or empty
+std::string build_reference_library(nct_ctx* ctx, const Config& cfg, RefLibrary& L);   // the descriptors, on a context with weights; the same. The workers use L from here on
+inline bool is_auto(const Pair& p) { return p.refs.size() == 1 && p.refs[0] == "auto"; }
 void split_refs(Pair& p);                                        // fills p.refs (and p.err) from p.stl
 std::string refusal(const Config& cfg, const Pair& p);           // why this run does not take the line; empty: it runs
 std::string output_name(const Config& cfg, const Pair& p);

@@ -52,6 +52,10 @@ void add_options(CmdLine& cl, Config& cfg) {
     cl.add("mask", cfg.mask_dir, "[extension] directory of region masks (SPEC 6.11): a content image in/x.png is recoloured only where <dir>/x.png (or .jpg; its first channel, the content image's size) is not 0 — 255 = the full transfer, between = partial; a line without a mask file runs as without -mask; works with -fullres 1, several references, -lut, -lutfull and -vis 1; not with -fullres 2 or -seq 1.");
     cl.add("refmask", cfg.refmask_dir, "[extension] directory of reference region masks (SPEC 6.12): colours are taken only from where <dir>/y.png (or .jpg; its first channel, the style image's size) of a style image in/y.png is not 0 — 255 = allowed, between = partial; a style image without a mask file counts as allowed everywhere; combines with -mask, -maskprotect, -fullres 1, several references, -lut, -lutfull and -vis 1; not with -fullres 2 or -seq 1.");
     cl.add("maskprotect", cfg.maskprotect, "[extension] -mask / -refmask: 1 = a pixel whose mask is 0 never changes (default 0: the transition follows the image's own edges and may reach such pixels).");
+    cl.add("reflib", cfg.reflib_dir, "[extension] directory of graded stills, the reference library (SPEC 6.21): a pairs.txt line whose style field is the word auto ranks its content image against every image of <dir> (.png / .jpg, taken in byte order of their names, shrunk like content images) and runs with the best -refk of them; the output name is that of the same line with those files written out; not with -seq 1; -resume does not skip such a line (its name is known only once it is ranked)."); cl.unlisted();
+    cl.add("refk", cfg.refk, "[extension] -reflib: how many of the library's images a line with auto runs with, in [1, 8]; 1 runs as a pair, more as several references."); cl.unlisted();
+    cl.add("reftap", cfg.reftap, "[extension] -reflib: the VGG19 tap the images are compared at, 1 (conv1_1) to 5 (conv5_1)."); cl.unlisted();
+    cl.add("refcenter", cfg.refcenter, "[extension] -reflib: 1 = the library's mean tap vector is subtracted from every descriptor before it is normalised (wider margins between candidates); 0 = not."); cl.unlisted();
     cl.add("lutfull", cfg.lutfull, "[extension] -lut N: 1 = also write <name>_lut.png, the table applied to the content image at its original size; not with -fullres 1.");
 }
 
@@ -94,6 +98,11 @@ std::string option_refusal(const Config& c, bool lutlambda_given) {
     if (refmask && c.seq) return "-refmask cannot be combined with -seq 1 (sequences with a reference mask are not defined, SPEC 6.12).";
     if (mask && c.fullres == 2) return "-mask cannot be combined with -fullres 2 (a mask with the upsampling finish is not defined, SPEC 6.11); use -fullres 1.";
     if (mask && c.seq) return "-mask cannot be combined with -seq 1 (sequences with a region mask are not defined, SPEC 6.11).";
+    if (outside(c.refk, 1, NCT_MAX_REFS)) return text("-refk %d is not in [1, %d].", c.refk, NCT_MAX_REFS);
+    if (outside(c.reftap, 1, 5)) return text("-reftap %d is not in [1, 5].", c.reftap);
+    if (outside(c.refcenter, 0, 1)) return text("-refcenter %d is not one of 0, 1.", c.refcenter);
+    if (!c.reflib_dir.empty() && c.seq) return "-reflib cannot be combined with -seq 1 (a sequence keeps one reference; rank its first frame on its own and name the result).";
+    if (!c.reflib_dir.empty() && c.fullres && c.refk > 1) return text("-refk %d cannot be combined with -fullres %d (several references at full resolution are not defined).", c.refk, c.fullres);
     if (c.lut != 0 && c.lut != 3 && c.lut != 5 && c.lut != 9 && c.lut != 17 && c.lut != 33 && c.lut != 65) return text("-lut %d is not one of 3, 5, 9, 17, 33, 65.", c.lut);
     if (lutlambda_given && !c.lut) return "-lutlambda needs -lut N.";
     if (lutlambda_given && !finite_positive(c.lut_lambda)) return text("-lutlambda %g is not finite and greater than 0.", c.lut_lambda);

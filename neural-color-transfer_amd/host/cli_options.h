@@ -7,7 +7,7 @@
 #include "nct.h"
 
 constexpr int MAX_SIZE = 1000;                 // Config.h:5
-struct Param { std::string flag, comment; enum { STR, INT, DBL } kind; void* dst; };
+struct Param { std::string flag, comment; enum { STR, INT, DBL } kind; void* dst; bool listed = true; };   // listed: the help prints it
 // Utility::CmdLine (CmdLine.h:58-69,132-147; CmdLine.cpp:21-56,93-109) re-created; pinned against the reference's own parser compiled unmodified
 // (oracle/ref_cmdline.cpp -> tests/golden/cmdline_ref.json -> tests/test_cli.py). The rules, all the reference's:
 //  * a token is an "argument" when it starts with '-' or '/' (Parameter::IsArg) — "-5" and "/x" included; any other token is a positional file (collected, unused);
@@ -23,6 +23,9 @@ struct CmdLine {
     void add(const char* flag, std::string& v, const char* c) { params.push_back({flag, c, Param::STR, &v}); }
     void add(const char* flag, int& v, const char* c) { params.push_back({flag, c, Param::INT, &v}); }
     void add(const char* flag, double& v, const char* c) { params.push_back({flag, c, Param::DBL, &v}); }
+    // parsed like every other parameter, but not printed by the help: the help's text is recorded byte for byte (tests/golden/cli_messages.json) and stays what it
+    // was; such parameters are described in README.md and SPEC.md
+    void unlisted() { params.back().listed = false; }
     static bool is_arg(const char* a) { return a && (a[0] == '-' || a[0] == '/'); }                       // Parameter::IsArg, CmdLine.h:68-70
     static bool is_help(const std::string& a) { return a == "h" || a == "?" || a == "help"; }              // CmdLine.cpp:93-100
     bool names_a_parameter(const char* a) const {
@@ -40,6 +43,7 @@ struct CmdLine {
     void help(const char* prog) const {
         std::cout << "Running: " << prog << std::endl;
         for (const auto& p : params) {                                          // TParm::Print, CmdLine.h:140-142
+            if (!p.listed) continue;
             std::cout << "-" << p.flag << ": " << "(default=";
             if (p.kind == Param::STR) std::cout << *(const std::string*)p.dst;
             else if (p.kind == Param::INT) std::cout << *(const int*)p.dst;
@@ -86,6 +90,7 @@ struct Config {
     int autokey = 0; nct_seq_auto ap;                  // -autokey 1, -keythr, -keycut, -keychange, -keygap: key frames chosen per frame (SPEC §6.7)
     int lut = 0, lutfull = 0; double lut_lambda = 0.0; // -lut N (0 = off), -lutfull 1, -lutlambda (0 = the library's default) (SPEC §6.6)
     std::string mask_dir, refmask_dir; int maskprotect = 0;   // -mask / -refmask <dir>: region masks by content / reference file name (SPEC §6.11 / §6.12), -maskprotect 0 / 1
+    std::string reflib_dir; int refk = 1, reftap = 5, refcenter = 1;   // -reflib <dir>, -refk K, -reftap t, -refcenter 0 / 1: a line whose reference is "auto" takes the K best of the library (SPEC §6.21)
 };
 void add_options(CmdLine& cl, Config& cfg);            // the option table, in the help's order
 // the first rule the parsed options break, as the text behind "Error: " (empty: accepted). lutlambda_given: "-lutlambda" was on the command line

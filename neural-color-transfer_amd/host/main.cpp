@@ -91,6 +91,11 @@ int main(int argc, char** argv) {
     while (fscanf(fp, "%259s %259s %f\n", a, b, &w) == 3) { pairs.push_back({a, b, w, {}, ""}); split_refs(pairs.back()); }
     fclose(fp);
     const std::vector<Group> groups = cfg.seq ? plan_groups(pairs) : std::vector<Group>();
+    RefLibrary reflib;                                                       // -reflib <dir>: listed here, built once the first context has its weights
+    if (!cfg.reflib_dir.empty()) {
+        const std::string why = list_reference_library(cfg, reflib);
+        if (!why.empty()) { printf("Error: %s\n", why.c_str()); return -1; }
+    }
     if (plan_only) {
         std::vector<std::string> seq_of(pairs.size());               // -seq 1: " seq=<sequence>:<index>" behind the lines that are frames, -key N: " prop" behind the propagated ones; -autokey 1: " auto" behind every frame but a sequence's first (what it becomes is known only when it runs)
         for (const Group& g : groups)
@@ -139,6 +144,10 @@ int main(int argc, char** argv) {
     nct_model_free(host_model);
     { size_t wb = 0; nct_vgg19_weights_info(ctxs[0], nullptr, &wb, nullptr);
       printf("VGG19 weights: parsed once, %d device cop%s of %.1f MB shared by %d context(s).\n", uploads, uploads == 1 ? "y" : "ies", wb / 1e6, nworkers); }
+    if (!cfg.reflib_dir.empty()) {                                           // once per process; the workers share it read-only, each context keeps its own device copy of the rows
+        const std::string why = build_reference_library(ctxs[0], cfg, reflib);
+        if (!why.empty()) { printf("Error: %s\n", why.c_str()); return -1; }
+    }
 
     // NUMA placement: the CPUs next to each GPU (sysfs), for its workers and its share of the I/O pool
     std::vector<affinity::GpuLocality> loc(ngpus);
@@ -189,5 +198,6 @@ int main(int argc, char** argv) {
         rg.finish(rccl_id_path);
     }
     for (auto* c : ctxs) nct_destroy(c);
+    nct_reflib_free(reflib.lib);
     return 0;
 }

@@ -162,6 +162,16 @@ SIGNATURES = {
     "nct_region_model_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "nct_region_model_from_rows": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "nct_region_model_free": (None, [C.c_void_p]),
+    "nct_reflib_params_default": (None, [C.c_void_p]),
+    "nct_reflib_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "nct_reflib_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "nct_reflib_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "nct_reflib_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "nct_reflib_from_rows": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "nct_reflib_free": (None, [C.c_void_p]),
+    "nct_reflib_rank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nct_reflib_release": (C.c_int, [C.c_void_p]),
+    "nct_descriptor_match_bench": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "nct_region_refind_bench": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "nct_region_model_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_region_model_apply_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -239,6 +249,8 @@ _TWINS = {
     "nct_feat_quantize": [_P, _P, _I, _I, _I],
     "nct_region_score": [_P, _I, _I, _P, _I, _P, _I, _I, _I, _P],
     "nct_region_refind": [_P, _I, _I, _P, _I, _I, _I, _P],
+    "nct_feat_quantize8": [_P, _P, _P, _I, _I, _I],
+    "nct_descriptor_match": [_P, _I, _I, _P, _P, _I, _P, _P],              # offsets: a host array in both forms
 }
 for _name, _args in _TWINS.items():
     SIGNATURES[_name] = SIGNATURES[_name + "_dev"] = (C.c_int, [C.c_void_p] + _args)
@@ -545,6 +557,84 @@ class RegionModel:
     def close(self):
         if self._m:
             lib().nct_region_model_free(self._m); self._m = None
+
+    def __del__(self):
+        self.close()
+
+
+class RefLibParams(C.Structure):
+    """struct nct_reflib_params (include/nct.h)."""
+    _fields_ = [("wf", C.c_int), ("wb", C.c_int)]
+
+    @staticmethod
+    def default():
+        p = RefLibParams()
+        lib().nct_reflib_params_default(C.byref(p))
+        return p
+
+
+class RefLib:
+    """nct_reflib (SPEC §6.21): the int8 tap descriptors of a library's entries, a host object without a context. RefLib(tap, center=None) is empty
+    (nct_reflib_create; C is the tap's channel count); RefLib.from_rows(tap, rows, offsets, center=None) holds rows the caller has (nct_reflib_from_rows)."""
+
+    TAP_C = (64, 128, 256, 512, 512)
+
+    def __init__(self, tap, center=None, C_=None, _handle=None):
+        self._m = None
+        if _handle is not None:
+            self._m = _handle
+            return
+        mu = None if center is None else np.ascontiguousarray(center, np.float32)
+        Cc = int(C_) if C_ is not None else (self.TAP_C[tap - 1] if 1 <= tap <= 5 else 0)
+        if mu is not None and mu.shape != (Cc,):
+            raise NctError(-2, "RefLib: center must be [C] fp32")
+        m = C.c_void_p()
+        rc = lib().nct_reflib_create(int(tap), Cc, None if mu is None else mu.ctypes.data, C.byref(m))
+        if rc != 0:
+            raise NctError(rc, (lib().nct_last_error(None) or b"").decode())
+        self._m = m
+
+    @classmethod
+    def from_rows(cls, tap, rows, offsets, center=None):
+        r, o = np.ascontiguousarray(rows, np.int8), np.ascontiguousarray(offsets, np.int32)
+        mu = None if center is None else np.ascontiguousarray(center, np.float32)
+        if r.ndim != 2 or o.ndim != 1 or o.size < 1 or (mu is not None and mu.shape != (r.shape[1],)):
+            raise NctError(-2, "RefLib.from_rows: rows must be [total, C] int8, offsets [N + 1] int32 and center [C] fp32 or None")
+        m = C.c_void_p()
+        rc = lib().nct_reflib_from_rows(int(tap), r.shape[1], None if mu is None else mu.ctypes.data, r.ctypes.data, o.ctypes.data, o.size - 1, C.byref(m))
+        if rc != 0:
+            raise NctError(rc, (lib().nct_last_error(None) or b"").decode())
+        return cls(tap, _handle=m)
+
+    def info(self):
+        """nct_reflib_info -> (tap, C, N, total rows, centred)"""
+        tap, Cc, N, tot, cen = C.c_int(), C.c_int(), C.c_int(), C.c_int64(), C.c_int()
+        rc = lib().nct_reflib_info(self._m, C.byref(tap), C.byref(Cc), C.byref(N), C.byref(tot), C.byref(cen))
+        if rc != 0:
+            raise NctError(rc, (lib().nct_last_error(None) or b"").decode())
+        return tap.value, Cc.value, N.value, tot.value, bool(cen.value)
+
+    def rows(self):
+        """nct_reflib_rows -> (rows [total, C] int8, offsets [N + 1] int32, center [C] fp32 or None) as numpy copies"""
+        _, Cc, N, tot, cen = self.info()
+        r, o, mu = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rc = lib().nct_reflib_rows(self._m, C.byref(r), C.byref(o), C.byref(mu))
+        if rc != 0:
+            raise NctError(rc, (lib().nct_last_error(None) or b"").decode())
+        rows = np.ctypeslib.as_array(C.cast(r, C.POINTER(C.c_int8)), (tot, Cc)).copy() if tot else np.zeros((0, Cc), np.int8)
+        offs = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_int32)), (N + 1,)).copy()
+        return rows, offs, (np.ctypeslib.as_array(C.cast(mu, C.POINTER(C.c_float)), (Cc,)).copy() if cen else None)
+
+    def add(self, ctx, bgr):
+        """nct_reflib_add: bgr [h, w, 3] becomes the next entry (one forward to the tap on ctx, rule D2)"""
+        img = np.ascontiguousarray(bgr, np.uint8)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise NctError(-2, "RefLib.add: bgr must be [h, w, 3] bytes")
+        ctx._chk(ctx._l.nct_reflib_add(ctx._h, self._m, img.ctypes.data, img.shape[0], img.shape[1]))
+
+    def close(self):
+        if self._m:
+            lib().nct_reflib_free(self._m); self._m = None
 
     def __del__(self):
         self.close()
@@ -1611,6 +1701,56 @@ class Context:
             qs, sis, sos, out = s.put(qq), s.put(si), s.put(so), s.new((cells,), np.uint8)
             s.call(qs, cells, Cc, sis, n_in, sos, n_out, int(sharpness), int(floor_permille), out)
             return s.get(out)
+
+    # ---- reference libraries (SPEC §6.21)
+    def feat_quantize8(self, src_chw, center=None, *, dev=False):
+        """nct_feat_quantize8[_dev] (SPEC §6.21 rule D2): CHW fp32 features, center [C] or None -> [H*W, C] int8 rows rint(N1(F - center) * 127); the device form takes
+        the map channel-last"""
+        src = np.ascontiguousarray(src_chw, np.float32)
+        mu = None if center is None else np.ascontiguousarray(center, np.float32)
+        Cc, H, W = src.shape
+        with self._seam("feat_quantize8", dev) as s:
+            ins, mus, out = s.put(src, upload=np.ascontiguousarray(src.reshape(Cc, H * W).T)), s.put(mu), s.new((H * W, Cc), np.int8)
+            s.call(ins, mus, out, Cc, H, W)
+            return s.get(out)
+
+    def descriptor_match(self, a, entries, *, dev=False):
+        """nct_descriptor_match[_dev] (SPEC §6.21 rule D3): a [na, C] int8 and a list of entries [n_k, C] int8 -> (fwd [N], bwd [N]) int64"""
+        aa = np.ascontiguousarray(a, np.int8)
+        ents = [np.ascontiguousarray(e, np.int8) for e in entries]
+        na, Cc = aa.shape
+        rows = np.ascontiguousarray(np.concatenate(ents, axis=0)) if ents else np.zeros((0, Cc), np.int8)
+        offs = np.concatenate([[0], np.cumsum([e.shape[0] for e in ents])]).astype(np.int32)
+        with self._seam("descriptor_match", dev) as s:
+            as_, rs, f, b = s.put(aa), s.put(rows), s.new((len(ents),), np.int64), s.new((len(ents),), np.int64)
+            s.call(as_, na, Cc, rs, offs, len(ents), f, b)
+            return s.get(f), s.get(b)
+
+    def reflib_rank(self, reflib, src_bgr, wf=None, wb=None):
+        """nct_reflib_rank (SPEC §6.21): src_bgr [h, w, 3] against every entry of the RefLib -> (order [N] int32, key, fwd, bwd [N] int64); wf / wb None: 1, 1"""
+        img = np.ascontiguousarray(src_bgr, np.uint8)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise NctError(-2, "reflib_rank: src_bgr must be [h, w, 3] bytes")
+        N = reflib.info()[2]
+        prm = None
+        if wf is not None or wb is not None:
+            prm = RefLibParams.default()
+            prm.wf, prm.wb = int(prm.wf if wf is None else wf), int(prm.wb if wb is None else wb)
+        order, key, fwd, bwd = np.zeros(max(N, 1), np.int32), np.zeros(max(N, 1), np.int64), np.zeros(max(N, 1), np.int64), np.zeros(max(N, 1), np.int64)
+        self._chk(self._l.nct_reflib_rank(self._h, reflib._m, img.ctypes.data, img.shape[0], img.shape[1], C.addressof(prm) if prm is not None else None,
+                                          order.ctypes.data, key.ctypes.data, fwd.ctypes.data, bwd.ctypes.data))
+        return order[:N], key[:N], fwd[:N], bwd[:N]
+
+    def reflib_release(self):
+        """nct_reflib_release: the device copy of the library last ranked against goes back to the arena"""
+        self._chk(self._l.nct_reflib_release(self._h))
+
+    def descriptor_match_bench(self, d_a, na, Cc, d_rows, offsets, d_fwd, d_bwd, reps=20):
+        """nct_descriptor_match_bench on device pointers (offsets: a host int32 array) -> the mean device time of one match in ms"""
+        offs = np.ascontiguousarray(offsets, np.int32)
+        ms = C.c_float()
+        self._chk(self._l.nct_descriptor_match_bench(self._h, d_a, na, Cc, d_rows, offs.ctypes.data, offs.size - 1, d_fwd, d_bwd, reps, C.byref(ms)))
+        return ms.value
 
     def pair_select_region(self, strokes, params=None, protect=None):
         """nct_pair_select_region: region_select on the uploaded source, then pair_set_region with the matte, which stays on the device"""
