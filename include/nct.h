@@ -38,7 +38,7 @@ extern "C" {
  * nct_seq_select_region, and with region models, nct_region_model_*, nct_region_refind[_dev], nct_pair_apply_region_model and nct_seq_set_region_model, and with sequences
  * over several references, nct_seq_begin_multi[_fullres], nct_seq_frame_multi[_stage]_levels, nct_seq_hold, nct_seq_hold_levels and nct_select_reference_hold[_dev], and with reference
  * region masks in sequences, nct_seq_set_ref_region, nct_seq_pull_hold[_dev], nct_seq_pull_levels and nct_seq_frame[_propagate]_ref_region_levels, and with shot look-up tables and the 16-bit apply,
- * nct_lut_accum_* and nct_lut_apply_u16[_dev]).
+ * nct_lut_accum_* and nct_lut_apply_u16[_dev], and with local colour grids, nct_grid_* and nct_pair_fit_grid).
  * A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
 #define NCT_VERSION 118
@@ -559,6 +559,34 @@ int nct_lut_accum_info(nct_ctx* ctx, int* size, uint64_t* adds, uint64_t* pixels
 int nct_lut_accum_solve(nct_ctx* ctx, double lambda, float* lut_out, nct_lut_stages* stages);
 int nct_lut_accum_solve_dev(nct_ctx* ctx, double lambda, float* d_lut_out, nct_lut_stages* d_stages);
 int nct_lut_accum_end(nct_ctx* ctx);
+
+/* ---- local colour grids (SPEC §6.22; an extension): the spatial counterpart of the table — a bilateral grid of affine colour maps (Chen et al., Bilateral Guided
+ * Upsampling; HDRnet's slicing layer). A grid is double[gy][gx][gz][3][4] over (row, column, luma), gy, gx in [2, 64], gz in [2, 32]; a node holds a 3 x 4 map of BGR
+ * as a DISPLACEMENT in grey levels, output channel c in B, G, R, input term j in B, G, R, 1: out_c = s_c + X_c . (s_B, s_G, s_R, 1). The all-zero grid is the identity.
+ * It works in BGR grey levels throughout: no Lab conversion. Positions depend on relative position only (row y of h: t = (2y + 1)(gy - 1) over 2h; luma
+ * Y = (29 B + 150 G + 77 R + 128) >> 8: t = Y (gz - 1) over 255 or 65535), so a grid fitted at one size applies to any picture of the same framing.
+ * nct_grid_fit: from two 8-bit images of h x w pixels, a source S and a result O (BGR, tightly packed). (1) splat: per node, over the pixels whose NEAREST node it
+ * is, the 22 int64 sums — the 10 distinct sums s_j s_k over (B, G, R, 1), [9] the count, then the 12 sums s_j (O_c - S_c), [10 + 4c + j]; (2) one integer [1 2 1]
+ * pass along each axis, out-of-grid taps dropped; (3) per node with a count, the 4 x 4 system (blurred Gram matrix, lambda * count added to the three linear
+ * diagonal entries) solved by L D L^T for the three channels; a node without a count gets 0. stages (nullable, its arrays nullable) receives the sums of (1) and (2),
+ * [gy*gx*gz][22] each. lambda is finite and in [1/16, 65536].
+ * nct_grid_apply / nct_grid_apply_u16: per pixel the eight corner weights as integers, the 12 coefficients interpolated in double in a fixed order,
+ * v = s_c + (((a_0 B + a_1 G) + a_2 R) + a_3 K) / (2h * 2w * Z), K = 1 and Z = 255 for 8 bits, K = 257 and Z = 65535 for 16 bits (a value v standing for the grey
+ * level v / 257), clamped to [0, Z] (a NaN becomes 0) and rounded to nearest even. out may be the input. The host forms refuse a grid with a non-finite entry; the
+ * _dev forms do not look. Host forms are synchronous, _dev forms are enqueued on the context's stream.
+ * nct_pair_fit_grid: the fit from the images nct_pair_fit_lut would read after the context's last finished run; a run's mask is not read (kept pixels fit a zero
+ * displacement). Without a finished run: NCT_ERR_STATE.
+ * A null pointer, h or w outside [1, 16384], more than 2^26 pixels, a node count out of range, a bad lambda: NCT_ERR_INVALID with a message naming the argument. */
+typedef struct nct_grid_params { int gy, gx, gz; double lambda; } nct_grid_params;
+void nct_grid_params_default(nct_grid_params* p);   /* 16, 16, 16, lambda 16 */
+typedef struct nct_grid_stages { int64_t* sums; int64_t* blurred; } nct_grid_stages;
+int nct_grid_fit(nct_ctx* ctx, const uint8_t* src_bgr, const uint8_t* res_bgr, int h, int w, const nct_grid_params* prm, double* grid_out, nct_grid_stages* stages);
+int nct_grid_fit_dev(nct_ctx* ctx, const uint8_t* d_src_bgr, const uint8_t* d_res_bgr, int h, int w, const nct_grid_params* prm, double* d_grid_out, nct_grid_stages* d_stages);
+int nct_grid_apply(nct_ctx* ctx, const double* grid, int gy, int gx, int gz, const uint8_t* bgr, int h, int w, uint8_t* out_bgr);
+int nct_grid_apply_dev(nct_ctx* ctx, const double* d_grid, int gy, int gx, int gz, const uint8_t* d_bgr, int h, int w, uint8_t* d_out_bgr);
+int nct_grid_apply_u16(nct_ctx* ctx, const double* grid, int gy, int gx, int gz, const uint16_t* bgr16, int h, int w, uint16_t* out_bgr16);
+int nct_grid_apply_u16_dev(nct_ctx* ctx, const double* d_grid, int gy, int gx, int gz, const uint16_t* d_bgr16, int h, int w, uint16_t* d_out_bgr16);
+int nct_pair_fit_grid(nct_ctx* ctx, const nct_grid_params* prm, double* grid_out);
 
 /* ---- source region masks (SPEC §6.11; an extension): recolour only part of the source. A mask M has one byte per SOURCE pixel: 0 keeps the source, 255 is the full
  * transfer, values between are partial. The level masks are the single-channel form of the image pyramid: M_top = M at the working size, M_l = nct_resize_u8c1 of

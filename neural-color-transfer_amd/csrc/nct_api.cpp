@@ -209,7 +209,7 @@ int nct_synchronize(nct_ctx* ctx) {
 }
 
 
-// The host-pointer entry points below, and those of nct_color.cpp, nct_lut.cpp, nct_region_select.cpp, nct_region_model.cpp and nct_vgg.cpp, have one shape: the argument
+// The host-pointer entry points below, and those of nct_color.cpp, nct_lut.cpp, nct_grid.cpp, nct_region_select.cpp, nct_region_model.cpp and nct_vgg.cpp, have one shape: the argument
 // checks; one HostCall line per array (in / out / inout / scratch, in the order the blocks are requested); NCT_TRY(hc.ready()) and the launchers; return hc.finish().
 
 // a CHW host tensor through the staging block d_tmp (which several tensors of a call share) into HWC device layout

@@ -391,8 +391,19 @@ int nctk_lut_apply16(nct_ctx* ctx, hipStream_t s, const float* lut, int N, const
 void nct_lut_accum_free(nct_ctx* ctx);   // nct_lut.cpp
 // nct_pipeline.cpp — the images nct_pair_fit_lut reads after the context's last finished run (SPEC §6.6 rule 10), on the device; mask (null: every pixel) at their size.
 // false: no finished run
-struct nct_lut_images { const uint8_t *src, *res, *mask; size_t npix; };
+struct nct_lut_images { const uint8_t *src, *res, *mask; size_t npix; int h, w; };
 bool nct_pair_lut_images(nct_ctx* ctx, nct_lut_images* im);
+// k_grid.hip — local colour grids (SPEC §6.22). sums / blurred [gy*gx*gz][22] int64 (sums zeroed on s by the splat itself); X [gy*gx*gz][3][4] double. in / out of an
+// apply may be the same buffer
+#define NCT_GRID_MAX_SIDE 16384
+int nctk_grid_splat(nct_ctx* ctx, hipStream_t s, const uint8_t* src, const uint8_t* res, int H, int W, int gy, int gx, int gz, int64_t* sums);
+int nctk_grid_solve(nct_ctx* ctx, hipStream_t s, const int64_t* sums, int gy, int gx, int gz, double lambda, int64_t* blurred, double* X);
+int nctk_grid_apply(nct_ctx* ctx, hipStream_t s, const double* X, int gy, int gx, int gz, const uint8_t* in, int H, int W, uint8_t* out);
+int nctk_grid_apply16(nct_ctx* ctx, hipStream_t s, const double* X, int gy, int gx, int gz, const uint16_t* in, int H, int W, uint16_t* out);
+// nct_grid.cpp: the checks of nct_grid_fit's arguments (`what` names the entry point in the message), and splat + solve on device pointers, enqueued on the main
+// stream; stages (nullable, its arrays nullable): DEVICE pointers
+int nct_grid_fit_check(nct_ctx* ctx, const char* what, const void* src, const void* res, int h, int w, const nct_grid_params* prm, const void* grid_out);
+int nct_grid_fit_enqueue(nct_ctx* ctx, const uint8_t* d_src, const uint8_t* d_res, int h, int w, const nct_grid_params* prm, double* d_grid, const nct_grid_stages* d_stages);
 // nct_lut.cpp: the checks of nct_lut_fit's arguments (`what` names the entry point in the message), and splat + solve + table on device pointers, enqueued on the
 // main stream; stages (nullable, its arrays nullable): DEVICE pointers
 int nct_lut_fit_check(nct_ctx* ctx, const char* what, const void* src, const void* res, size_t npix, const nct_lut_params* prm, const void* lut_out);

@@ -982,16 +982,31 @@ int nct_pair_fit_lut(nct_ctx* ctx, const nct_lut_params* prm, float* lut_out) {
     return NCT_OK;
 }
 
+// SPEC §6.22 rule 7: the local colour grid of the last finished run, from the same images; a run's mask is not read (kept pixels fit a zero displacement)
+int nct_pair_fit_grid(nct_ctx* ctx, const nct_grid_params* prm, double* grid_out) {
+    NCT_CTX_ENTER();
+    nct_lut_images im;
+    if (!nct_pair_lut_images(ctx, &im)) return ctx->fail(NCT_ERR_STATE, "pair_fit_grid: no finished run on this context (nct_pair_run first)");
+    NCT_TRY(nct_grid_fit_check(ctx, "pair_fit_grid", im.src, im.res, im.h, im.w, prm, grid_out));
+    const size_t n = (size_t)prm->gy * prm->gx * prm->gz * 12;
+    DevBuf<double> dg(ctx, n);
+    if (!dg.ok()) return NCT_ERR_HIP;
+    NCT_TRY(nct_grid_fit_enqueue(ctx, im.src, im.res, im.h, im.w, prm, dg, nullptr));
+    NCT_D2H(grid_out, dg, sizeof(double) * n);
+    NCT_SYNC();
+    return NCT_OK;
+}
+
 }  // extern "C"
 
 // what nct_pair_fit_lut and nct_lut_accum_add_run read: the source and the result of the last finished run, and the mask of a masked one
 bool nct_pair_lut_images(nct_ctx* ctx, nct_lut_images* im) {
     pair_state* P = (pair_state*)ctx->pair;
-    *im = nct_lut_images{nullptr, nullptr, nullptr, 0};
+    *im = nct_lut_images{nullptr, nullptr, nullptr, 0, 0, 0};
     if (!P || !P->finished) return false;
     // a masked run's table is fitted over its region (SPEC §6.11 rule 7), with the mask at the size of the images it reads
-    if (P->full_src && P->full_out) *im = nct_lut_images{P->full_src, P->full_out, P->full_mask, (size_t)P->full_h * P->full_w};
-    else if (P->src && P->out && P->sh > 0) *im = nct_lut_images{P->src, P->out, P->mask, (size_t)P->sh * P->sw};
+    if (P->full_src && P->full_out) *im = nct_lut_images{P->full_src, P->full_out, P->full_mask, (size_t)P->full_h * P->full_w, P->full_h, P->full_w};
+    else if (P->src && P->out && P->sh > 0) *im = nct_lut_images{P->src, P->out, P->mask, (size_t)P->sh * P->sw, P->sh, P->sw};
     // a run with a reference mask: its last level's target mask, which has the size of the result (SPEC §6.12 rule 7)
     if (im->src && P->fin_mask) im->mask = P->fin_mask;
     return im->src != nullptr;

@@ -33,6 +33,7 @@ void write_status(const Config& cfg, const Job& j) {
 // what a job writes beside <name>.png: <name>.cube with -lut N, <name>_lut.png with -lutfull 1
 std::string cube_name(const std::string& png) { return png.substr(0, png.size() - 4) + ".cube"; }
 std::string lutfull_name(const std::string& png) { return png.substr(0, png.size() - 4) + "_lut.png"; }
+std::string grid_name(const std::string& png) { return png.substr(0, png.size() - 4) + "_grid.png"; }      // -grid G
 // -mask / -refmask <dir>: the image in/x.png uses <dir>/x.png (or .jpg) where it exists; the mask has the image's size as decoded and is its file's first channel.
 // flag, whose, what: the words by which the two kinds' messages differ. mask stays empty where there is no file; false: the job has failed
 bool load_mask(Job& j, const std::string& dir, const std::string& image_path, const ImageBGR& img, const char* flag, const char* whose, const char* what, std::vector<uint8_t>& mask) {
@@ -103,12 +104,33 @@ std::string output_name(const Config& cfg, const Pair& p) {
 }
 // -resume: every file of the job's output is there and complete
 bool outputs_complete(const Config& cfg, const std::string& png) {
-    return pngio::looks_complete(png) && (!cfg.lut || cubeio::looks_complete(cube_name(png), cfg.lut)) && (!cfg.lutfull || pngio::looks_complete(lutfull_name(png)));
+    return pngio::looks_complete(png) && (!cfg.lut || cubeio::looks_complete(cube_name(png), cfg.lut)) && (!cfg.lutfull || pngio::looks_complete(lutfull_name(png))) &&
+           (!cfg.grid || pngio::looks_complete(grid_name(png)));
+}
+
+// -grid G: the local colour grid of a finished job (SPEC §6.22), fitted from the equal-sized source and result the job holds and applied to the content image at its
+// original size. G nodes along the longer side, the shorter side in proportion, 16 along luma. A grid that cannot be made does not take the result with it
+static void job_grid(nct_ctx* ctx, const Config& cfg, Job& j) {
+    nct_grid_params gp; nct_grid_params_default(&gp);
+    const int h = j.cnt.h, w = j.cnt.w, lng = std::max(h, w), sht = std::min(h, w);
+    const int other = std::max(2, (int)((2LL * cfg.grid * sht + lng) / (2LL * lng)));      // round(G * short / long), halves up
+    gp.gy = h >= w ? cfg.grid : other; gp.gx = h >= w ? other : cfg.grid; gp.gz = 16;
+    if (cfg.grid_lambda > 0.0) gp.lambda = cfg.grid_lambda;
+    std::vector<double> grid((size_t)gp.gy * gp.gx * gp.gz * 12);
+    int rc = nct_grid_fit(ctx, j.cnt.px.data(), j.out.data(), h, w, &gp, grid.data(), nullptr);
+    if (rc == NCT_OK) {
+        j.grid_out.resize(j.orig.px.size());
+        rc = nct_grid_apply(ctx, grid.data(), gp.gy, gp.gx, gp.gz, j.orig.px.data(), j.orig.h, j.orig.w, j.grid_out.data());
+    }
+    if (rc != NCT_OK) { j.grid_err = nct_last_error(ctx); j.grid_out.clear(); return; }
+    j.say("Local colour grid: %d x %d x %d, lambda = %g.\n", gp.gy, gp.gx, gp.gz, gp.lambda);
 }
 
 // -lut N: the table of a finished job (SPEC §6.6), fitted through the host-pointer call from the equal-sized source and result the job holds; -lutfull 1: that table
-// on the content image at its original size. Before log_times, which drops the inputs
+// on the content image at its original size. Before log_times, which drops the inputs. With -grid G the job's grid comes first, from the same images
 void job_lut(nct_ctx* ctx, const Config& cfg, Job& j) {
+    if (cfg.grid) job_grid(ctx, cfg, j);
+    if (cfg.grid && !cfg.lutfull) { j.orig.px.clear(); j.orig.px.shrink_to_fit(); }
     if (!cfg.lut) return;
     nct_lut_params lp; nct_lut_params_default(&lp);
     lp.size = cfg.lut;
@@ -277,7 +299,7 @@ void run_pair(nct_ctx* ctx, const Config& cfg, Job& j) {
         else { job_lut(ctx, cfg, j); log_times(j, prm, tm); }
         return;
     }
-    if (cfg.lutfull) j.orig = j.cnt;
+    if (cfg.lutfull || cfg.grid) j.orig = j.cnt;
     const int cnt_h = j.cnt.h, cnt_w = j.cnt.w;                 // as decoded: the mask's size until it is shrunk too
     bool shrunk = shrink(ctx, j.cnt);
     // a mask shrinks with its image, by the same routine on the replicated three-channel image (= the single-channel resize, SPEC §6.11 rule 1)
@@ -332,8 +354,13 @@ void store_pair(Job& j) {
         if (!pngio::write(lutfull_name(j.name), j.lut_out.data(), j.orig.h, j.orig.w, err)) { j.fail("cannot write " + lutfull_name(j.name) + ": " + err, "cannot write output: " + err); return; }
         j.say("Look-up table on the original: %s.\n", lutfull_name(j.name).c_str());
     }
+    if (!j.grid_out.empty()) {
+        if (!pngio::write(grid_name(j.name), j.grid_out.data(), j.orig.h, j.orig.w, err)) { j.fail("cannot write " + grid_name(j.name) + ": " + err, "cannot write output: " + err); return; }
+        j.say("Local colour grid on the original: %s.\n", grid_name(j.name).c_str());
+    }
     j.say("Final output file: %s.\n\n", j.name.c_str());
     if (!j.lut_err.empty()) { j.fail("no look-up table: " + j.lut_err); return; }
+    if (!j.grid_err.empty()) { j.fail("no local colour grid: " + j.grid_err); return; }
     j.state = Job::DONE;
 }
 void run_line(nct_ctx* ctx, const Config& cfg, const Pair& p, size_t index) {

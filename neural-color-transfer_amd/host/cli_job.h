@@ -17,7 +17,8 @@ struct Pair { std::string cnt, stl; float bds; std::vector<std::string> refs; st
 struct Job {
     size_t index = 0; Pair p; std::string name, log, err;
     ImageBGR cnt; std::vector<uint8_t> out;
-    ImageBGR orig;                                               // -lutfull 1: the content image as decoded, before the shrink to MAX_SIZE
+    ImageBGR orig;                                               // -lutfull 1, -grid G: the content image as decoded, before the shrink to MAX_SIZE
+    std::vector<uint8_t> grid_out; std::string grid_err;        // -grid G: the job's local colour grid on `orig`; why the job has none (its result image is written all the same)
     std::vector<float> lut; std::vector<uint8_t> lut_out;       // -lut N: the job's table; -lutfull 1: the table on `orig`
     std::vector<std::vector<uint8_t>> refmask;                   // -refmask: per reference its region mask, one byte per pixel of refs[k] (empty: that reference has none)
     bool ref_masked() const { for (const auto& q : refmask) if (!q.empty()) return true; return false; }

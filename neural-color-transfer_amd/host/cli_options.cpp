@@ -57,6 +57,8 @@ void add_options(CmdLine& cl, Config& cfg) {
     cl.add("reftap", cfg.reftap, "[extension] -reflib: the VGG19 tap the images are compared at, 1 (conv1_1) to 5 (conv5_1)."); cl.unlisted();
     cl.add("refcenter", cfg.refcenter, "[extension] -reflib: 1 = the library's mean tap vector is subtracted from every descriptor before it is normalised (wider margins between candidates); 0 = not."); cl.unlisted();
     cl.add("lutfull", cfg.lutfull, "[extension] -lut N: 1 = also write <name>_lut.png, the table applied to the content image at its original size; not with -fullres 1.");
+    cl.add("grid", cfg.grid, "[extension] G in [2, 64]: beside each result image write <same name>_grid.png, a local colour grid (SPEC 6.22) of G nodes along the longer side (the shorter side in proportion, 16 along luma) fitted from the source and the result and applied to the content image at its original size; not with -fullres or -seqfull."); cl.unlisted();
+    cl.add("gridlambda", cfg.grid_lambda, "[extension] -grid G: ridge weight of the grid's fit, in [1/16, 65536] (default: the library's, 16)."); cl.unlisted();
 }
 
 __attribute__((format(printf, 1, 2))) static std::string text(const char* fmt, ...) {
@@ -64,7 +66,7 @@ __attribute__((format(printf, 1, 2))) static std::string text(const char* fmt, .
     return t;
 }
 
-std::string option_refusal(const Config& c, bool lutlambda_given) {
+std::string option_refusal(const Config& c, bool lutlambda_given, bool gridlambda_given) {
     const bool mask = !c.mask_dir.empty(), refmask = !c.refmask_dir.empty();
     auto finite_positive = [](double v) { return v > 0.0 && v <= 1.7976931348623157e308; };
     auto outside = [](int v, int lo, int hi) { return v < lo || v > hi; };
@@ -109,6 +111,11 @@ std::string option_refusal(const Config& c, bool lutlambda_given) {
     if (c.lutfull && !c.lut) return "-lutfull 1 needs -lut N.";
     if (c.lutfull && c.fullres) return text("-lutfull 1 cannot be combined with -fullres %d (the result already has the original size).", c.fullres);
     if (c.lutfull && c.seqfull) return text("-lutfull 1 cannot be combined with -seqfull %d (the results already have the original size).", c.seqfull);
+    if (c.grid != 0 && outside(c.grid, 2, 64)) return text("-grid %d is not in [2, 64].", c.grid);
+    if (gridlambda_given && !c.grid) return "-gridlambda needs -grid G.";
+    if (gridlambda_given && !(c.grid_lambda >= 1.0 / 16.0 && c.grid_lambda <= 65536.0)) return text("-gridlambda %g is not in [1/16, 65536].", c.grid_lambda);
+    if (c.grid && c.fullres) return text("-grid %d cannot be combined with -fullres %d (the result already has the original size).", c.grid, c.fullres);
+    if (c.grid && c.seqfull) return text("-grid %d cannot be combined with -seqfull %d (the results already have the original size).", c.grid, c.seqfull);
     return "";
 }
 

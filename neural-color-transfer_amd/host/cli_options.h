@@ -91,9 +91,11 @@ struct Config {
     int lut = 0, lutfull = 0; double lut_lambda = 0.0; // -lut N (0 = off), -lutfull 1, -lutlambda (0 = the library's default) (SPEC §6.6)
     std::string mask_dir, refmask_dir; int maskprotect = 0;   // -mask / -refmask <dir>: region masks by content / reference file name (SPEC §6.11 / §6.12), -maskprotect 0 / 1
     std::string reflib_dir; int refk = 1, reftap = 5, refcenter = 1;   // -reflib <dir>, -refk K, -reftap t, -refcenter 0 / 1: a line whose reference is "auto" takes the K best of the library (SPEC §6.21)
+    int grid = 0; double grid_lambda = 0.0;            // -grid G (0 = off): nodes along the longer side of a local colour grid, -gridlambda (0 = the library's default) (SPEC §6.22)
 };
 void add_options(CmdLine& cl, Config& cfg);            // the option table, in the help's order
-// the first rule the parsed options break, as the text behind "Error: " (empty: accepted). lutlambda_given: "-lutlambda" was on the command line
-std::string option_refusal(const Config& cfg, bool lutlambda_given);
+// the first rule the parsed options break, as the text behind "Error: " (empty: accepted). lutlambda_given, gridlambda_given: "-lutlambda" / "-gridlambda" was on the
+// command line
+std::string option_refusal(const Config& cfg, bool lutlambda_given, bool gridlambda_given = false);
 // after the checks (and -procs' fork, which changes -gpus): seed, levels and flags into prm, the clamps of -gpus, -inflight and -io
 void settle(Config& cfg);

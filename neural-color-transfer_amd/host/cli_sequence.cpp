@@ -49,7 +49,7 @@ size_t run_sequence(nct_ctx* ctx, const Config& cfg, const std::vector<Pair>& pa
             }
         }
         if (j.state == Job::LOADED && ref.px.empty()) { j.err = "cannot read style image: " + ref_err; j.state = Job::FAILED; }      // logged once, at the frame that tried
-        if (j.state == Job::LOADED && cfg.lutfull) j.orig = j.cnt;
+        if (j.state == Job::LOADED && (cfg.lutfull || cfg.grid)) j.orig = j.cnt;
         if (j.state == Job::LOADED && !cfg.seqfull && !shrink(ctx, j.cnt)) j.fail(std::string("resize failed: ") + nct_last_error(ctx), nct_last_error(ctx));
         if (j.state == Job::LOADED) {
             int rc = NCT_OK;

@@ -132,6 +132,8 @@ SIGNATURES = {
     "nct_lut_accum_add_run": (C.c_int, [C.c_void_p]),
     "nct_lut_accum_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_lut_accum_end": (C.c_int, [C.c_void_p]),
+    "nct_grid_params_default": (None, [C.c_void_p]),
+    "nct_pair_fit_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_region_params_default": (None, [C.c_void_p]),
     "nct_pair_set_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_pair_run_region_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -242,6 +244,9 @@ _TWINS = {
     "nct_lut_apply_u16": [_P, _I, _P, _N, _P],
     "nct_lut_accum_add": [_P, _P, _P, _N],
     "nct_lut_accum_solve": [_D, _P, _P],
+    "nct_grid_fit": [_P, _P, _I, _I, _P, _P, _P],
+    "nct_grid_apply": [_P, _I, _I, _I, _P, _I, _I, _P],
+    "nct_grid_apply_u16": [_P, _I, _I, _I, _P, _I, _I, _P],
     "nct_resize_u8c1": [_P, _I, _I, _P, _I, _I],
     "nct_region_mix": [_P, _P, _I, _I, _P],
     "nct_region_compose": [_P, _P, _P, _N, _P, _P, _P],
@@ -385,6 +390,36 @@ def _lut_params(size, lam):
     if lam is not None:
         p.lambda_ = float(lam)
     return p
+
+
+class GridParams(C.Structure):
+    """struct nct_grid_params (include/nct.h)."""
+    _fields_ = [("gy", C.c_int), ("gx", C.c_int), ("gz", C.c_int), ("lambda_", C.c_double)]
+
+    @staticmethod
+    def default():
+        p = GridParams()
+        lib().nct_grid_params_default(C.byref(p))
+        return p
+
+
+class GridStages(C.Structure):
+    """struct nct_grid_stages (include/nct.h)."""
+    _fields_ = [("sums", C.c_void_p), ("blurred", C.c_void_p)]
+
+
+def _grid_params(shape, lam):
+    p = GridParams.default()
+    if shape is not None:
+        p.gy, p.gx, p.gz = (int(v) for v in shape)
+    if lam is not None:
+        p.lambda_ = float(lam)
+    return p
+
+
+def _grid_host_shape(gy, gx, gz):
+    """the shape of the host arrays of a grid: a refused node count never reaches them, so it only has to exist"""
+    return (gy, gx, gz) if 0 < gy <= 64 and 0 < gx <= 64 and 0 < gz <= 32 else (1, 1, 1)
 
 
 class GuidedParams(C.Structure):
@@ -2034,6 +2069,51 @@ class Context:
         lut = np.empty((N, N, N, 3), np.float32)
         self._chk(self._l.nct_pair_fit_lut(self._h, C.addressof(prm), lut.ctypes.data))
         return lut
+
+    # ---- local colour grids (SPEC §6.22)
+    def grid_fit(self, src, res, shape=None, lam=None, want_stages=False, *, dev=False):
+        """nct_grid_fit[_dev]: source and result images [h, w, 3] uint8 BGR -> grid float64 [gy, gx, gz, 3, 4] (+ {"sums", "blurred"}, int64 [nodes, 22] each);
+        shape = (gy, gx, gz) / lam left out are nct_grid_params_default's"""
+        s_, r = np.ascontiguousarray(src, np.uint8), np.ascontiguousarray(res, np.uint8)
+        assert s_.ndim == 3 and s_.shape[2] == 3 and s_.shape == r.shape
+        prm = _grid_params(shape, lam)
+        g = (prm.gy, prm.gx, prm.gz)
+        G = _grid_host_shape(*g)
+        dg = tuple(max(v, 1) for v in g)                           # the device form reserves what is asked for; the library refuses before it writes
+        with self._seam("grid_fit", dev) as s:
+            ss, rs = s.put(s_), s.put(r)
+            grid = s.new(G + (3, 4), np.float64, dev_shape=dg + (3, 4))
+            st = {k: s.new((math.prod(G), 22), np.int64, dev_shape=(math.prod(dg), 22)) for k in ("sums", "blurred")}
+            cs = GridStages(st["sums"].ptr, st["blurred"].ptr)
+            s.call(ss, rs, s_.shape[0], s_.shape[1], C.addressof(prm), grid, C.addressof(cs) if want_stages else None)
+            return (s.get(grid), {k: s.get(v) for k, v in st.items()}) if want_stages else s.get(grid)
+
+    def grid_apply(self, grid, img, *, dev=False, in_place=False):
+        """nct_grid_apply[_dev]: grid [gy, gx, gz, 3, 4] float64 on an image [h, w, 3] uint8 BGR of any size -> the image of the same shape. in_place (device
+        form): the output over the input"""
+        return self._grid_apply("grid_apply", np.uint8, grid, img, dev, in_place)
+
+    def grid_apply_u16(self, grid, img16, *, dev=False, in_place=False):
+        """nct_grid_apply_u16[_dev]: grid_apply on an image [h, w, 3] uint16 BGR, a value v standing for the grey level v / 257"""
+        return self._grid_apply("grid_apply_u16", np.uint16, grid, img16, dev, in_place)
+
+    def _grid_apply(self, name, dtype, grid, img, dev, in_place):
+        """the two applies: the same call on pixels of another depth"""
+        t = np.ascontiguousarray(grid, np.float64)
+        a = np.ascontiguousarray(img, dtype)
+        assert t.ndim == 5 and t.shape[3:] == (3, 4) and a.ndim == 3 and a.shape[2] == 3
+        with self._seam(name, dev) as s:
+            ts, as_, out = s.put(t), s.put(a), s.new(a.shape, dtype)
+            dst = s.over(out, as_ if in_place else None)
+            s.call(ts, t.shape[0], t.shape[1], t.shape[2], as_, a.shape[0], a.shape[1], dst)
+            return s.get(dst)
+
+    def pair_fit_grid(self, shape=None, lam=None):
+        """nct_pair_fit_grid: the grid of the context's last finished run, from the images it holds on the device"""
+        prm = _grid_params(shape, lam)
+        grid = np.empty(_grid_host_shape(prm.gy, prm.gx, prm.gz) + (3, 4), np.float64)
+        self._chk(self._l.nct_pair_fit_grid(self._h, C.addressof(prm), grid.ctypes.data))
+        return grid
 
     def seq_reset(self):
         self._chk(self._l.nct_seq_reset(self._h))
