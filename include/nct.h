@@ -38,7 +38,8 @@ extern "C" {
  * nct_seq_select_region, and with region models, nct_region_model_*, nct_region_refind[_dev], nct_pair_apply_region_model and nct_seq_set_region_model, and with sequences
  * over several references, nct_seq_begin_multi[_fullres], nct_seq_frame_multi[_stage]_levels, nct_seq_hold, nct_seq_hold_levels and nct_select_reference_hold[_dev], and with reference
  * region masks in sequences, nct_seq_set_ref_region, nct_seq_pull_hold[_dev], nct_seq_pull_levels and nct_seq_frame[_propagate]_ref_region_levels, and with shot look-up tables and the 16-bit apply,
- * nct_lut_accum_* and nct_lut_apply_u16[_dev], and with local colour grids, nct_grid_* and nct_pair_fit_grid).
+ * nct_lut_accum_* and nct_lut_apply_u16[_dev], and with local colour grids, nct_grid_* and nct_pair_fit_grid, and
+ * with the correspondence carry of sequences, nct_seq_set_carry, nct_seq_get_carry and nct_nnf_{carry,forward_map,remap,merge}[_dev]).
  * A caller checks `nct_version() == NCT_VERSION` before it passes any struct: the CLI
  * and the python binding do. */
 #define NCT_VERSION 118
@@ -1018,6 +1019,39 @@ int nct_conv3x3_dev(nct_ctx* ctx, const float* d_in, const float* d_weights, con
                     float* d_out_chw, float* d_out_hwc);
 int nct_conv3x3_pair_dev(nct_ctx* ctx, const float* d_in1, int H1, int W1, const float* d_in2, int H2, int W2, const float* d_weights, const float* d_bias, int Cin, int Cout,
                          int relu, float* d_out1, float* d_out2, float* d_hwc1, float* d_hwc2);
+
+/* ---- correspondence carry in frame sequences (SPEC §6.23) ----
+ * A full frame of a sequence starts every level's PatchMatch from nct_nnf_init or the upsampled coarser field. With the carry on, the sequence also keeps the final
+ * fields of every level run (per reference) of its last full frame, moves them along the level's backward motion field on every frame (with motion off they stay where
+ * they are), and a full frame merges them into the level's start field: per query the kept match replaces the ordinary start where its step-0 patch distance is
+ * strictly smaller (fp32; a NaN keeps the ordinary start). The level's PatchMatch then runs unchanged on that start field, with `iters` iterations on a frame that
+ * merged. The first frame, and the first after nct_seq_reset or a cut of nct_seq_frame_auto, has nothing to merge and is the frame the sequence gives without the carry.
+ * nct_seq_set_carry: on in {0, 1}; iters in [0, 64], or -1 for the sequence's pm_iters. Turning the carry on reserves the kept fields, the forward map and one scratch
+ * field; turning it off gives them back. No open sequence: NCT_ERR_STATE; a value out of range: NCT_ERR_INVALID; a refused call changes nothing. A sequence that never
+ * calls it keeps its bytes, launches and arena exactly. NCT_VERSION stays 118: entry points were only added.
+ * nct_seq_get_carry: the kept fields of reference k at level run l — ann [ah_l*aw_l] on the source's level grid, bnn [bh_l*bw_l] on the reference's, either pointer
+ * nullable — as the last frame left them; NCT_ERR_STATE where the sequence holds none (carry off, before the first full frame, after a reset or cut).
+ * The seams, on host arrays (synchronous) and as _dev forms on device pointers (enqueued). Fields are int16 [h*w][2] of (my, mx); NNF words are (y << 12) | x:
+ *   nct_nnf_carry        nnf_out(p) = nnf_prev(p + m(p)), the vector clamped component-wise so that p + m is inside.
+ *   nct_nnf_forward_map  fwd_out(s) = min { word(p) : p + m(p) = s } with the same clamp, and word(clamp(s - m(s))) where no p lands on s.
+ *   nct_nnf_remap        bnn_out(q) = fwd(bnn_prev(q)) on the grid bh x bw, fwd on h x w; a word whose coordinates leave h x w is clamped to it.
+ *   nct_nnf_merge        one direction of the merge: a / b normalised features (host form: [C][ah][aw] and [C][bh][bw] as nct_patchmatch takes them; _dev: channel-last),
+ *                        z the ordinary start field and c the moved kept field, both [ah*aw] words into b's grid; start_out [ah*aw]; dz_out / dc_out (nullable) the two
+ *                        step-0 distances, bit for bit what nct_patchmatch(iters = 0) returns for z and c. patch must be 3.
+ * The _dev forms gather on the caller's blocks and refuse (NCT_ERR_INVALID) an output block that overlaps an input block: nnf_out and nnf_prev, fwd_out and field,
+ * bnn_out and bnn_prev or fwd, start_out and z or c. The host forms stage every array in device blocks of their own and never look at how the host arrays lie. */
+int nct_seq_set_carry(nct_ctx* ctx, int on, int iters);
+int nct_seq_get_carry(nct_ctx* ctx, int k, int l, uint32_t* ann, uint32_t* bnn);
+int nct_nnf_carry(nct_ctx* ctx, const uint32_t* nnf_prev, int h, int w, const int16_t* field, uint32_t* nnf_out);
+int nct_nnf_carry_dev(nct_ctx* ctx, const uint32_t* d_nnf_prev, int h, int w, const int16_t* d_field, uint32_t* d_nnf_out);
+int nct_nnf_forward_map(nct_ctx* ctx, const int16_t* field, int h, int w, uint32_t* fwd_out);
+int nct_nnf_forward_map_dev(nct_ctx* ctx, const int16_t* d_field, int h, int w, uint32_t* d_fwd_out);
+int nct_nnf_remap(nct_ctx* ctx, const uint32_t* bnn_prev, int bh, int bw, const uint32_t* fwd, int h, int w, uint32_t* bnn_out);
+int nct_nnf_remap_dev(nct_ctx* ctx, const uint32_t* d_bnn_prev, int bh, int bw, const uint32_t* d_fwd, int h, int w, uint32_t* d_bnn_out);
+int nct_nnf_merge(nct_ctx* ctx, const float* a_chw, const float* b_chw, int C, int ah, int aw, int bh, int bw, int patch, const uint32_t* z, const uint32_t* c,
+                  uint32_t* start_out, float* dz_out, float* dc_out);
+int nct_nnf_merge_dev(nct_ctx* ctx, const float* d_a_hwc, const float* d_b_hwc, int C, int ah, int aw, int bh, int bw, int patch, const uint32_t* d_z, const uint32_t* d_c,
+                      uint32_t* d_start_out, float* d_dz_out, float* d_dc_out);
 
 /* ---- measurement hooks (bench.py / rocprof): device-resident PatchMatch on synthetic features ----
  * nct_pm_bench_setup uploads + normalises two CHW feature maps once; nct_pm_bench_run re-initialises the NNF

@@ -447,6 +447,61 @@ int nct_seq_matte_warp(nct_ctx* ctx, const uint8_t* mask_prev, int H, int W, con
     return hc.finish();
 }
 
+// SPEC §6.23 rules 3, 4 and 6 on host arrays: the inputs up, the launches of the rule out of place, the output down
+int nct_nnf_carry(nct_ctx* ctx, const uint32_t* nnf_prev, int h, int w, const int16_t* field, uint32_t* nnf_out) {
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_nnf_carry_check(ctx, "nnf_carry", nnf_prev, h, w, field, nnf_out));
+    const size_t n = (size_t)h * w;
+    HostCall hc(ctx);
+    const uint32_t* dp = hc.in(nnf_prev, n);
+    const int16_t* df = hc.in(field, 2 * n);
+    uint32_t* dout = hc.out(nnf_out, n);
+    NCT_TRY(hc.ready());
+    NCT_TRY(nctk_nnf_carry(ctx, ctx->stream, dp, h, w, df, dout));
+    return hc.finish();
+}
+
+int nct_nnf_forward_map(nct_ctx* ctx, const int16_t* field, int h, int w, uint32_t* fwd_out) {
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_nnf_forward_map_check(ctx, "nnf_forward_map", field, h, w, fwd_out));
+    const size_t n = (size_t)h * w;
+    HostCall hc(ctx);
+    const int16_t* df = hc.in(field, 2 * n);
+    uint32_t* dout = hc.out(fwd_out, n);
+    NCT_TRY(hc.ready());
+    NCT_TRY(nctk_nnf_forward_map(ctx, ctx->stream, df, h, w, dout));
+    return hc.finish();
+}
+
+int nct_nnf_remap(nct_ctx* ctx, const uint32_t* bnn_prev, int bh, int bw, const uint32_t* fwd, int h, int w, uint32_t* bnn_out) {
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_nnf_remap_check(ctx, "nnf_remap", bnn_prev, bh, bw, fwd, h, w, bnn_out));
+    const size_t nb = (size_t)bh * bw;
+    HostCall hc(ctx);
+    const uint32_t *db = hc.in(bnn_prev, nb), *dfw = hc.in(fwd, (size_t)h * w);
+    uint32_t* dout = hc.out(bnn_out, nb);
+    NCT_TRY(hc.ready());
+    NCT_TRY(nctk_nnf_remap(ctx, ctx->stream, db, bh, bw, dfw, h, w, dout));
+    return hc.finish();
+}
+
+int nct_nnf_merge(nct_ctx* ctx, const float* a_chw, const float* b_chw, int C, int ah, int aw, int bh, int bw, int patch, const uint32_t* z, const uint32_t* c,
+                  uint32_t* start_out, float* dz_out, float* dc_out) {
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_nnf_merge_check(ctx, "nnf_merge", a_chw, b_chw, C, ah, aw, bh, bw, patch, z, c, start_out));
+    const size_t na = (size_t)ah * aw, nb = (size_t)bh * bw;
+    HostCall hc(ctx);
+    float *t = hc.scratch<float>((size_t)C * (na > nb ? na : nb)), *A = hc.scratch<float>(C * na), *B = hc.scratch<float>(C * nb);
+    uint32_t* ds = hc.inout(z, start_out, na);                   // Z goes up into the block the merge writes in place
+    const uint32_t* dc = hc.in(c, na);
+    float *ddz = hc.out(dz_out, na), *ddc = hc.out(dc_out, na);
+    NCT_TRY(hc.ready());
+    NCT_TRY(upload_hwc(ctx, hc, a_chw, t, A, C, (int)na));
+    NCT_TRY(upload_hwc(ctx, hc, b_chw, t, B, C, (int)nb));
+    NCT_TRY(nctk_nnf_merge(ctx, ctx->stream, A, B, nullptr, nullptr, C, ah, aw, bh, bw, NCT_PM_PLAIN, ds, dc, ddz, ddc, nullptr, nullptr, nullptr, nullptr));
+    return hc.finish();
+}
+
 // SPEC §6.15 rule 1 on host arrays: the matte and the guide up, one k_region_snap launch out of place, the snapped matte down
 int nct_region_snap(nct_ctx* ctx, const uint8_t* mask, const uint8_t* lab, int H, int W, const nct_region_snap_params* params, uint8_t* mask_out) {
     NCT_CTX_ENTER();

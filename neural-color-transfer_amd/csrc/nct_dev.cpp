@@ -255,6 +255,34 @@ int nct_seq_motion_field_dev(nct_ctx* ctx, const uint8_t* d_lab, const uint8_t* 
     return nctk_seq_motion(ctx, ctx->stream, d_lab, pk, h, w, d_parent, ph, pw, R, penalty, d_m_out);
 }
 
+// ---- SPEC §6.23 rules 3, 4 and 6 on device pointers
+int nct_nnf_carry_dev(nct_ctx* ctx, const uint32_t* d_nnf_prev, int h, int w, const int16_t* d_field, uint32_t* d_nnf_out) {
+    NCT_CTX_ENTER();
+    return nctk_nnf_carry(ctx, ctx->stream, d_nnf_prev, h, w, d_field, d_nnf_out);
+}
+
+int nct_nnf_forward_map_dev(nct_ctx* ctx, const int16_t* d_field, int h, int w, uint32_t* d_fwd_out) {
+    NCT_CTX_ENTER();
+    return nctk_nnf_forward_map(ctx, ctx->stream, d_field, h, w, d_fwd_out);
+}
+
+int nct_nnf_remap_dev(nct_ctx* ctx, const uint32_t* d_bnn_prev, int bh, int bw, const uint32_t* d_fwd, int h, int w, uint32_t* d_bnn_out) {
+    NCT_CTX_ENTER();
+    return nctk_nnf_remap(ctx, ctx->stream, d_bnn_prev, bh, bw, d_fwd, h, w, d_bnn_out);
+}
+
+int nct_nnf_merge_dev(nct_ctx* ctx, const float* d_a_hwc, const float* d_b_hwc, int C, int ah, int aw, int bh, int bw, int patch, const uint32_t* d_z, const uint32_t* d_c,
+                      uint32_t* d_start_out, float* d_dz_out, float* d_dc_out) {
+    NCT_CTX_ENTER();
+    NCT_TRY(nct_nnf_merge_check(ctx, "nnf_merge_dev", d_a_hwc, d_b_hwc, C, ah, aw, bh, bw, patch, d_z, d_c, d_start_out));
+    const size_t bytes = sizeof(uint32_t) * (size_t)ah * aw;
+    const auto apart = [bytes](const void* p, const void* q) { return (const char*)p + bytes <= (const char*)q || (const char*)q + bytes <= (const char*)p; };
+    NCT_REQUIRE(apart(d_start_out, d_z) && apart(d_start_out, d_c), "nnf_merge_dev: start_out must not alias z or c");
+    // Z into the output, which the launcher then merges in place
+    NCT_HIP(hipMemcpyAsync(d_start_out, d_z, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return nctk_nnf_merge(ctx, ctx->stream, d_a_hwc, d_b_hwc, nullptr, nullptr, C, ah, aw, bh, bw, NCT_PM_PLAIN, d_start_out, d_c, d_dz_out, d_dc_out, nullptr, nullptr, nullptr, nullptr);
+}
+
 // ---- SPEC §6.11 on device pointers
 int nct_resize_u8c1_dev(nct_ctx* ctx, const uint8_t* d_src, int sh, int sw, uint8_t* d_dst, int dh, int dw) {
     NCT_CTX_ENTER();

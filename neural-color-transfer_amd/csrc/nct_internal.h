@@ -339,6 +339,22 @@ int nctk_seq_change(nct_ctx* ctx, hipStream_t s, const uint8_t* lab, const uint8
 int nctk_seq_matte_warp(nct_ctx* ctx, hipStream_t s, const uint8_t* mask_prev, int H, int W, const int16_t* field, int h, int w, uint8_t* mask_out);
 // its argument checks (`who` names the entry point in the message), for the host form to run before it moves anything
 int nct_seq_matte_warp_check(nct_ctx* ctx, const char* who, const void* mask_prev, int H, int W, const void* field, int h, int w, const void* mask_out);
+// k_seq_carry.hip — correspondence carry (SPEC §6.23). nctk_nnf_carry: rule 3, nnf_out(p) = nnf_prev(p + m(p)) on 32-bit words, the vector clamped component-wise;
+// nnf_out must not overlap nnf_prev. nctk_nnf_forward_map: rule 4's F ([h*w] words (y << 12) | x) of a backward field — a fill, the minimum pass, the hole pass.
+// nctk_nnf_remap: rule 4, bnn_out(q) = fwd(bnn_prev(q)) on the grid bh x bw, the word's coordinates clamped to fwd's grid h x w; bnn_out overlaps neither input.
+// nctk_nnf_merge: rule 6 on normalised HWC maps — ann (and bnn; null: one direction, evaluated as nct_patchmatch does) hold Z and receive start, ca / cb are the moved
+// kept fields, d* (nullable: scratch) receive the step-0 distances of Z and C. pm_mode and the fp16 shadows are nctk_patchmatch_bidir's
+int nctk_nnf_carry(nct_ctx* ctx, hipStream_t s, const uint32_t* nnf_prev, int h, int w, const int16_t* field, uint32_t* nnf_out);
+int nctk_nnf_forward_map(nct_ctx* ctx, hipStream_t s, const int16_t* field, int h, int w, uint32_t* fwd_out);
+int nctk_nnf_remap(nct_ctx* ctx, hipStream_t s, const uint32_t* bnn_prev, int bh, int bw, const uint32_t* fwd, int h, int w, uint32_t* bnn_out);
+int nctk_nnf_merge(nct_ctx* ctx, hipStream_t s, const float* a_hwc, const float* b_hwc, const void* a_h16, const void* b_h16, int C, int ah, int aw, int bh, int bw, int pm_mode,
+                   uint32_t* ann, const uint32_t* ca, float* dza, float* dca, uint32_t* bnn, const uint32_t* cb, float* dzb, float* dcb);
+// their argument checks (`who` names the entry point in the message), for the host forms to run before they move anything
+int nct_nnf_carry_check(nct_ctx* ctx, const char* who, const void* nnf_prev, int h, int w, const void* field, const void* nnf_out);
+int nct_nnf_forward_map_check(nct_ctx* ctx, const char* who, const void* field, int h, int w, const void* fwd_out);
+int nct_nnf_remap_check(nct_ctx* ctx, const char* who, const void* bnn_prev, int bh, int bw, const void* fwd, int h, int w, const void* bnn_out);
+int nct_nnf_merge_check(nct_ctx* ctx, const char* who, const void* a, const void* b, int C, int ah, int aw, int bh, int bw, int patch, const void* z, const void* c,
+                        const void* start_out);
 // k_region_snap.hip — SPEC §6.15 rule 1: mask_out(p) = the mean of mask over p's (2 radius + 1)^2 window inside the image, weighted with max(0, 3 sigma^2 - |lab(p) - lab(q)|^2)
 // and rounded half up (binary: cut at 128 to 0 / 255); lab: the frame's 8-bit Lab image [H*W][3]; params null: the defaults; mask_out must overlap neither input
 int nctk_region_snap(nct_ctx* ctx, hipStream_t s, const uint8_t* mask, const uint8_t* lab, int H, int W, const nct_region_snap_params* params, uint8_t* mask_out);

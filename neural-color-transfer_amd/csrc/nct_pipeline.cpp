@@ -205,6 +205,8 @@ struct pair_run {
     // frame runs rule 2 as it stands; both keep their label map in the sequence. field_found: the level's field was found in front of the selection, the blend reads it
     const bool held;
     bool field_found = false;
+    // SPEC §6.23: carry_keep — this frame of a carrying sequence keeps every level's final fields; carry_merge — it also has kept fields to move and merge
+    const bool carry_keep, carry_merge;
     // The run's masks (neither: the run enqueues and reserves what it always did). mask: the source's region mask (SPEC §6.11; null: none), mpyr / mimg: its level masks —
     // the pyramid's single-channel form. ref_masked: a reference has a region mask (SPEC §6.12); p_merged: P_l of several references (rule 3), m_level: M_l where it is not
     // P_l itself (rule 4: a source mask as well), f_level: F_l of a level that is not the last (the last level's is pair_state's fin_mask).
@@ -227,7 +229,8 @@ struct pair_run {
 
     pair_run(nct_ctx* c, const nct_params* p, nct_pair_timing* t, const run_extras& x)
         : ctx(c), prm(p), timing(t), lv(x.lv ? x.lv : &kNoLevels), color(x.color), fin(x.fin), seq(x.seq), slv(x.slv), qlv(x.qlv), hlv(x.hlv), plv(x.plv), P((pair_state*)c->pair), s(c->stream), H(P->sh), W(P->sw), K(P->K),
-          nlevels(p->levels), N((size_t)H * W), feat16((p->flags & NCT_FLAG_FEAT16) != 0), count(t && (p->flags & NCT_FLAG_COUNT_EVALS)), side(c), held(x.seq && P->K > 1 && x.seq->frames > 0 && x.seq->tau > 0.0 && x.seq->hold > 0.0), mask(P->mask),
+          nlevels(p->levels), N((size_t)H * W), feat16((p->flags & NCT_FLAG_FEAT16) != 0), count(t && (p->flags & NCT_FLAG_COUNT_EVALS)), side(c), held(x.seq && P->K > 1 && x.seq->frames > 0 && x.seq->tau > 0.0 && x.seq->hold > 0.0),
+          carry_keep(x.seq && x.seq->carry), carry_merge(x.seq && x.seq->carry && x.seq->carry_kept && x.seq->frames > 0), mask(P->mask),
           ref_masked(P->ref_masked()), pull_hold(ref_masked && x.seq && x.seq->frames > 0 && x.seq->tau > 0.0 && x.seq->pull_kept),
           up_masked(ref_masked && x.fin && x.fin->finish == NCT_FINISH_UPSAMPLE), refind(x.seq && x.seq->model_rows && !(P->mask && x.seq->matte_fresh)), cp(nct_color_params_of(*p)) {}
 
@@ -420,13 +423,27 @@ struct pair_run {
         NCT_TRY(nctk_normalize(ctx, s, R[k].featp[l], nb, nullptr, C, nb_px, feat16 ? (uint16_t*)nb_h : nullptr));
         MARK(NCT_ST_OTHER, l);
         const uint32_t seed_ab = prm->seed ^ (0x9E3779B9u * (uint32_t)(2 * l + 1)), seed_ba = prm->seed ^ (0x9E3779B9u * (uint32_t)(2 * l + 2));
+        const int pm_mode = (feat16 && C >= 256) ? NCT_PM_FP16 : NCT_PM_ROWREJECT;
+        // SPEC §6.23 rules 5-6 (a frame of a carrying sequence that holds kept fields; false everywhere else): the kept fields of this reference follow the level's field,
+        // then replace the start field where their step-0 distance is strictly smaller; annd / bnnd take d_Z and are PatchMatch's to overwrite. The level then runs
+        // carry_iters iterations. Both count as PatchMatch time
+        const int pm_it = carry_merge ? seq_carry_iters(seq) : prm->pm_iters;
+        if (carry_merge) {
+            NCT_TRY(seq_carry_move(ctx, s, seq, l, k));
+            NCT_TRY(nctk_nnf_merge(ctx, s, na, nb, (const uint16_t*)na_h, (const uint16_t*)nb_h, C, ah[l], aw[l], bh[l], bw[l], pm_mode, ann, seq->keep_ann[k][l], annd, nullptr,
+                                   bnn, seq->keep_bnn[k][l], bnnd, nullptr));
+        }
         // na, nb are unit vectors: the row-wise rejection is exact (and worth a third of the finest level: 15.7 vs 24.1 ms with NCT_PM_PLAIN). The fp16 tiles pay from C = 128 on (11-37 % per level); the C = 64 level is
         // latency bound, not byte bound (fp16 tiles: 15.8 vs 16.0 ms), and stays fp32
-        const int pm_mode = (feat16 && C >= 256) ? NCT_PM_FP16 : NCT_PM_ROWREJECT;
-        NCT_TRY(nctk_patchmatch_bidir(ctx, s, na, nb, (const uint16_t*)na_h, (const uint16_t*)nb_h, C, ah[l], aw[l], bh[l], bw[l], prm->pm_iters, R[k].rs_range[l], seed_ab, seed_ba,
+        NCT_TRY(nctk_patchmatch_bidir(ctx, s, na, nb, (const uint16_t*)na_h, (const uint16_t*)nb_h, C, ah[l], aw[l], bh[l], bw[l], pm_it, R[k].rs_range[l], seed_ab, seed_ba,
                                       ann, annd, bnn, bnnd, pm_mode, count ? ctx->d_counter + 4 * l : nullptr));
+        if (carry_keep) {
+            // SPEC §6.23 rule 1: the level's final fields are the sequence's kept fields from here on
+            NCT_HIP(hipMemcpyAsync(seq->keep_ann[k][l], ann, sizeof(uint32_t) * na_px, hipMemcpyDeviceToDevice, s));
+            NCT_HIP(hipMemcpyAsync(seq->keep_bnn[k][l], bnn, sizeof(uint32_t) * nb_px, hipMemcpyDeviceToDevice, s));
+        }
         MARK(NCT_ST_PM, l);
-        if (timing) timing->pm_level_launches[l] += 1 + 4 * prm->pm_iters;
+        if (timing) timing->pm_level_launches[l] += 1 + 4 * pm_it;
         NCT_TRY(d2h(lv->ann[k][l], ann, sizeof(uint32_t) * na_px));
         NCT_TRY(d2h(lv->bnn[k][l], bnn, sizeof(uint32_t) * nb_px));
         NCT_TRY(d2h(lv->annd[k][l], annd, sizeof(float) * na_px));
@@ -444,6 +461,16 @@ struct pair_run {
     // the correspondence of the level, once per reference in index order on the main stream (SPEC §6.2 rule 1; a pair runs the body once), then what the colour stage reads: G and E
     int correspondences(int l) {
         const int na_px = ah[l] * aw[l];
+        field_found = false;
+        if (carry_merge && seq->motion) {
+            // SPEC §6.23 rule 2: the level's field in front of its correspondence, on the main stream, whether or not the frame blends; every later reader of the level
+            // (the held selection, the held pull, the blend) uses this one
+            DevBuf<uint8_t> lab_l(ctx, (size_t)na_px * 3);
+            if (!lab_l.ok()) return NCT_ERR_HIP;
+            NCT_TRY(nctk_bgr2lab(ctx, s, simg[l], lab_l, (size_t)na_px));
+            NCT_TRY(seq_motion_level(ctx, s, seq, l, lab_l));
+            field_found = true;
+        }
         for (int k = 0; k < K; ++k) {
             NCT_TRY(correspondence(l, k));
             if (K > 1 && k == K - 1) {
@@ -486,7 +513,7 @@ struct pair_run {
         if (hlv && hlv->free_label[l] && !free_l.alloc(ctx, n)) return NCT_ERR_HIP;
         if (hlv && hlv->margin[l] && !margin_l.alloc(ctx, n)) return NCT_ERR_HIP;
         NCT_TRY(nctk_bgr2lab(ctx, s, simg[l], lab_l, n));
-        if (seq->motion) { NCT_TRY(seq_motion_level(ctx, s, seq, l, lab_l)); field_found = true; }
+        if (seq->motion && !field_found) { NCT_TRY(seq_motion_level(ctx, s, seq, l, lab_l)); field_found = true; }
         NCT_TRY(nctk_select_hold(ctx, s, errs, guides, K, h, w, seq->keep_label[l], lab_l, seq->keep_lab[l], seq->motion ? seq->field[l] : nullptr, seq->hold, seq->sigma,
                                  sel_label, guide, err, free_l, margin_l));
         if (free_l.ok()) NCT_TRY(dbg_copy(ctx, s, hlv->free_label[l], (uint8_t*)free_l, n));
@@ -510,7 +537,7 @@ struct pair_run {
             if (!held) {
                 if (!hold_lab.alloc(ctx, (size_t)na_px * 3)) return NCT_ERR_HIP;
                 NCT_TRY(nctk_bgr2lab(ctx, s, simg[l], hold_lab, (size_t)na_px));
-                if (seq->motion) { NCT_TRY(seq_motion_level(ctx, s, seq, l, hold_lab)); field_found = true; }
+                if (seq->motion && !field_found) { NCT_TRY(seq_motion_level(ctx, s, seq, l, hold_lab)); field_found = true; }
             }
             NCT_TRY(nctk_seq_pull_hold(ctx, s, pulled, K, sel_label, seq->keep_pull[l], hold_lab, seq->keep_lab[l], seq->motion ? seq->field[l] : nullptr, mask ? mimg[l] : nullptr, h, w,
                                        seq->tau, seq->sigma, seq->pull_alt[l], mask ? (uint8_t*)m_level : nullptr, p_merged.ok() ? (uint8_t*)p_merged : nullptr));

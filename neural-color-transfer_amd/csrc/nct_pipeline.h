@@ -24,6 +24,8 @@ struct full_target { const uint8_t* src = nullptr; int H = 0, W = 0; uint8_t* ou
 // place into matte_alt, a second block of the size frames arrive, reserved by the first carry; then the two change places. The flags and the age are host values.
 // Matte snapping (SPEC §6.15, nct_seq_set_region_snap): behind the carry the matte is snapped to the frame's Lab image, again out of place into matte_alt — the block
 // the carry has just left — and the two change places once more; a frame that snaps without a carry (motion off) reserves the block the same way.
+// Correspondence carry (SPEC §6.23, nct_seq_set_carry): while it is on the sequence also holds, per reference and level run, the two final NNFs of the last full frame
+// (4 B per source and per reference level pixel), one forward map and one scratch field of the largest level run; a sequence that never turns it on holds none of it.
 struct seq_state {
     nct_params prm; double tau = 0, sigma = 0;
     long frames = 0;                                           // frames since nct_seq_begin / nct_seq_reset: 0 = the next one is a first frame
@@ -52,6 +54,12 @@ struct seq_state {
     DevBuf<uint8_t> rq[NCT_MAX_REFS][4], keep_pull[5], pull_alt[5];
     bool pull_kept = false;
     int rh0[NCT_MAX_REFS] = {}, rw0[NCT_MAX_REFS] = {};
+    // SPEC §6.23 (nct_seq_set_carry): per reference and level run the final fields of the last full frame, moved along every later frame's field — A on the source's
+    // level grid, B on the reference's; the forward map of the level's field and one scratch field (the moves gather), both of the largest level run. All reserved
+    // when the carry is turned on and given back when it is turned off. carry_kept: the fields hold a full frame's result (false before the first one and after
+    // nct_seq_reset, a cut or a failed frame). carry_iters: PatchMatch iterations of a frame that merged, -1 = prm.pm_iters
+    bool carry = false, carry_kept = false; int carry_iters = -1;
+    DevBuf<uint32_t> keep_ann[NCT_MAX_REFS][5], keep_bnn[NCT_MAX_REFS][5], carry_fwd, carry_tmp;
     full_target full;
     const full_target* target() const { return full.H ? &full : nullptr; }
 };
@@ -201,6 +209,10 @@ NCT_LOCAL int seq_track_step(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_sta
 // size frames arrive (lab_work, or the original frame converted into scratch of this call), each out of place into matte_alt — reserved by the caller — after which
 // the two change places; then a full-resolution sequence shrinks the matte to the working-size one, as nct_seq_set_region makes it
 NCT_LOCAL int seq_matte_snap(nct_ctx* ctx, hipStream_t s, pair_state* P, seq_state* q, const uint8_t* lab_work, const nct_region_snap_params& sp, int iters);
+// SPEC §6.23 rules 3-5: the kept fields of reference k at level run l follow the level's field q->field[l], which the caller has found — A through the word gather, B
+// through the forward map, which is built with k == 0 and serves the level's other references. Each goes through the scratch field and back. Motion off: nothing
+NCT_LOCAL int seq_carry_move(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, int k);
+static inline int seq_carry_iters(const seq_state* q) { return q->carry_iters < 0 ? q->prm.pm_iters : q->carry_iters; }
 // ---- nct_region_model.cpp
 // SPEC §6.17 rules S2-S5, behind a full frame's forward and in front of its level masks: the frame's matte re-found from tap_hwc — the model's tap of that forward,
 // un-normalised and channel-last on the working-size grid — with the matte the track step left as the prior (none without a matte or without state), straight to the size

@@ -1,4 +1,4 @@
-// nct_seq.cpp — frame sequences (SPEC §6.3-§6.9, their region mask §6.13, its tracking §6.14, the snap §6.15, several references §6.18 and their region masks §6.19): the state an open sequence keeps in the context's arena, what a level of a frame does between S1 and the finish,
+// nct_seq.cpp — frame sequences (SPEC §6.3-§6.9, their region mask §6.13, its tracking §6.14, the snap §6.15, several references §6.18, their region masks §6.19 and the correspondence carry §6.23): the state an open sequence keeps in the context's arena, what a level of a frame does between S1 and the finish,
 // the frame entry points — a full frame is a run of nct_pipeline.cpp's level loop — the propagated frame, the probe and the key-frame decision.
 #include "nct_pipeline.h"
 #include <cstring>
@@ -48,6 +48,24 @@ int seq_level_step(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, const uint8
     if (q->motion) NCT_TRY(nctk_seq_pack(ctx, s, lab, n, q->keep_pk[l]));
     if (slv) NCT_TRY(dbg_copy(ctx, s, slv->ab_blend[l], keep_x, (size_t)6 * n));
     if (tmap.ok()) NCT_TRY(dbg_copy(ctx, s, slv->tau_map[l], (double*)tmap, n));
+    return NCT_OK;
+}
+
+// what the correspondence carry holds goes back to the arena (the caller has waited for the stream)
+static void seq_carry_free(seq_state* q) {
+    for (int k = 0; k < NCT_MAX_REFS; ++k) for (int l = 0; l < 5; ++l) { q->keep_ann[k][l].reset(); q->keep_bnn[k][l].reset(); }
+    q->carry_fwd.reset(); q->carry_tmp.reset();
+    q->carry = false; q->carry_kept = false; q->carry_iters = -1;
+}
+
+int seq_carry_move(nct_ctx* ctx, hipStream_t s, seq_state* q, int l, int k) {
+    if (!q->motion) return NCT_OK;                               // m = 0: both moves are the identity and enqueue nothing
+    const int h = q->ah[l], w = q->aw[l], bh = q->bh[k][l], bw = q->bw[k][l];
+    NCT_TRY(nctk_nnf_carry(ctx, s, q->keep_ann[k][l], h, w, q->field[l], q->carry_tmp));
+    NCT_HIP(hipMemcpyAsync(q->keep_ann[k][l], q->carry_tmp, sizeof(uint32_t) * (size_t)h * w, hipMemcpyDeviceToDevice, s));
+    if (k == 0) NCT_TRY(nctk_nnf_forward_map(ctx, s, q->field[l], h, w, q->carry_fwd));
+    NCT_TRY(nctk_nnf_remap(ctx, s, q->keep_bnn[k][l], bh, bw, q->carry_fwd, h, w, q->carry_tmp));
+    NCT_HIP(hipMemcpyAsync(q->keep_bnn[k][l], q->carry_tmp, sizeof(uint32_t) * (size_t)bh * bw, hipMemcpyDeviceToDevice, s));
     return NCT_OK;
 }
 
@@ -169,6 +187,51 @@ int nct_seq_reset(nct_ctx* ctx) {
     NCT_CTX_ENTER();
     NCT_OPEN_SEQ(P, "seq_reset");
     P->seq->frames = 0; P->seq->gap = 0; P->seq->acc = 0;
+    P->seq->carry_kept = false;                                  // SPEC §6.23 rule 1: the kept fields belong to a shot that is over
+    return NCT_OK;
+}
+
+// SPEC §6.23: the correspondence carry of the open sequence on (from the next full frame) or off. Turning it on reserves the kept fields of every reference and level
+// run, the forward map and the scratch field; turning it off gives them back
+int nct_seq_set_carry(nct_ctx* ctx, int on, int iters) {
+    NCT_CTX_ENTER();
+    NCT_OPEN_SEQ(P, "seq_set_carry");
+    NCT_REQUIRE(on == 0 || on == 1, "seq_set_carry: on must be 0 or 1 (got %d)", on);
+    NCT_REQUIRE(iters >= -1 && iters <= 64, "seq_set_carry: iters must be in [0, 64], or -1 for the sequence's pm_iters (got %d)", iters);
+    seq_state* q = P->seq;
+    if (!on) {
+        if (q->carry) { NCT_SYNC(); seq_carry_free(q); }
+        return NCT_OK;
+    }
+    if (q->carry) { q->carry_iters = iters; return NCT_OK; }
+    size_t big = 0;
+    bool ok = true;
+    for (int l = 0; l < q->prm.levels && ok; ++l) {
+        const size_t n = (size_t)q->ah[l] * q->aw[l];
+        big = std::max(big, n);
+        for (int k = 0; k < P->K && ok; ++k) {
+            const size_t nr = (size_t)q->bh[k][l] * q->bw[k][l];
+            big = std::max(big, nr);
+            ok = q->keep_ann[k][l].alloc(ctx, n) && q->keep_bnn[k][l].alloc(ctx, nr);
+        }
+    }
+    const int top = q->prm.levels - 1;
+    ok = ok && q->carry_fwd.alloc(ctx, (size_t)q->ah[top] * q->aw[top]) && q->carry_tmp.alloc(ctx, big);
+    if (!ok) { seq_carry_free(q); return NCT_ERR_HIP; }
+    q->carry = true; q->carry_kept = false; q->carry_iters = iters;
+    return NCT_OK;
+}
+
+int nct_seq_get_carry(nct_ctx* ctx, int k, int l, uint32_t* ann, uint32_t* bnn) {
+    NCT_CTX_ENTER();
+    NCT_OPEN_SEQ(P, "seq_get_carry");
+    const seq_state* q = P->seq;
+    NCT_REQUIRE(k >= 0 && k < P->K, "seq_get_carry: k = %d is not one of the sequence's %d references", k, P->K);
+    NCT_REQUIRE(l >= 0 && l < q->prm.levels, "seq_get_carry: l = %d is not one of the sequence's %d level runs", l, q->prm.levels);
+    if (!q->carry || !q->carry_kept) return ctx->fail(NCT_ERR_STATE, "seq_get_carry: the sequence holds no kept fields (nct_seq_set_carry, then a full frame)");
+    if (ann) NCT_D2H(ann, q->keep_ann[k][l], sizeof(uint32_t) * (size_t)q->ah[l] * q->aw[l]);
+    if (bnn) NCT_D2H(bnn, q->keep_bnn[k][l], sizeof(uint32_t) * (size_t)q->bh[k][l] * q->bw[k][l]);
+    NCT_SYNC();
     return NCT_OK;
 }
 
@@ -475,8 +538,9 @@ static int seq_frame_run(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out_bgr,
     if (rc == NCT_OK) rc = process_resident(ctx, &q->prm, timing, x);
     // a frame that failed may have replaced the state of some levels only: the next frame starts over
     q->gap = 0; q->acc = 0;                                      // a full frame (and a failed one: the next is a first frame) starts the count over
-    if (rc) { q->frames = 0; return rc; }
+    if (rc) { q->frames = 0; q->carry_kept = false; return rc; }
     q->frames += 1;
+    q->carry_kept = q->carry;                                    // SPEC §6.23 rule 1: every level run now keeps this frame's final fields
     q->pull_kept = P->ref_masked();                              // SPEC §6.19: every level run now keeps this frame's P'
     if (!q->target()) return nct_pair_download(ctx, out_bgr);
     NCT_D2H(out_bgr, P->full_out, (size_t)q->full.H * q->full.W * 3);
@@ -565,6 +629,8 @@ static int propagate_run(nct_ctx* ctx, pair_state* P, seq_state* q, uint8_t* out
                 NCT_TRY(nctk_label_carry(ctx, s, q->keep_pull[l], h, w, q->field[l], q->pull_alt[l]));
                 q->keep_pull[l].swap(q->pull_alt[l]);
             }
+            // SPEC §6.23 rule 5: the kept fields of every reference follow the field too, so that they always refer to the newest frame
+            if (q->carry && q->carry_kept) for (int k = 0; k < P->K; ++k) NCT_TRY(seq_carry_move(ctx, s, q, l, k));
         }
         if (ref_masked && plv) NCT_TRY(dbg_copy(ctx, s, plv->p_held[l], q->keep_pull[l], n));
         if (slv) {
@@ -642,7 +708,7 @@ static int seq_propagate_form(nct_ctx* ctx, const uint8_t* src_bgr, uint8_t* out
     if (rc == NCT_OK) P->finished = true;                        // nct_seq_set_region cleared it: this frame is the result of the new settings
     clock.stop();
     // a frame that failed may have replaced the state of some levels only: the next frame starts over
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); q->frames = 0; q->gap = 0; q->acc = 0; return rc; }
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); q->frames = 0; q->gap = 0; q->acc = 0; q->carry_kept = false; return rc; }
     q->frames += 1; q->gap += 1;
     return clock.read(false);
 }

@@ -58,6 +58,8 @@ void add_options(CmdLine& cl, Config& cfg) {
     cl.add("refcenter", cfg.refcenter, "[extension] -reflib: 1 = the library's mean tap vector is subtracted from every descriptor before it is normalised (wider margins between candidates); 0 = not."); cl.unlisted();
     cl.add("lutfull", cfg.lutfull, "[extension] -lut N: 1 = also write <name>_lut.png, the table applied to the content image at its original size; not with -fullres 1.");
     cl.add("grid", cfg.grid, "[extension] G in [2, 64]: beside each result image write <same name>_grid.png, a local colour grid (SPEC 6.22) of G nodes along the longer side (the shorter side in proportion, 16 along luma) fitted from the source and the result and applied to the content image at its original size; not with -fullres or -seqfull."); cl.unlisted();
+    cl.add("carry", cfg.carry, "[extension] -seq 1: 1 = correspondence carry (SPEC 6.23): every full frame after a sequence's first starts each level's PatchMatch from the better of its ordinary start field and the previous frame's match, moved along the motion field."); cl.unlisted();
+    cl.add("carryiters", cfg.carryiters, "[extension] -carry 1: PatchMatch iterations of the frames that start from the previous frame's match, in [0, 64] (default: as every other frame)."); cl.unlisted();
     cl.add("gridlambda", cfg.grid_lambda, "[extension] -grid G: ridge weight of the grid's fit, in [1/16, 65536] (default: the library's, 16)."); cl.unlisted();
 }
 
@@ -66,7 +68,7 @@ __attribute__((format(printf, 1, 2))) static std::string text(const char* fmt, .
     return t;
 }
 
-std::string option_refusal(const Config& c, bool lutlambda_given, bool gridlambda_given) {
+std::string option_refusal(const Config& c, bool lutlambda_given, bool gridlambda_given, bool carryiters_given) {
     const bool mask = !c.mask_dir.empty(), refmask = !c.refmask_dir.empty();
     auto finite_positive = [](double v) { return v > 0.0 && v <= 1.7976931348623157e308; };
     auto outside = [](int v, int lo, int hi) { return v < lo || v > hi; };
@@ -86,6 +88,10 @@ std::string option_refusal(const Config& c, bool lutlambda_given, bool gridlambd
     if (c.motion && outside(c.mp.radius0, 0, 8)) return text("-mr0 %d is not in [0, 8].", c.mp.radius0);
     if (c.motion && outside(c.mp.radius, 0, 3)) return text("-mr %d is not in [0, 3].", c.mp.radius);
     if (c.motion && outside(c.mp.penalty, 0, 255)) return text("-mpen %d is not in [0, 255].", c.mp.penalty);
+    if (outside(c.carry, 0, 1)) return text("-carry %d is not one of 0, 1.", c.carry);
+    if (c.carry && !c.seq) return "-carry 1 needs -seq 1 (the correspondence carry belongs to a sequence).";
+    if (carryiters_given && !c.carry) return text("-carryiters %d needs -carry 1.", c.carryiters);
+    if (carryiters_given && outside(c.carryiters, 0, 64)) return text("-carryiters %d is not in [0, 64].", c.carryiters);
     if (outside(c.key, 1, 1000)) return text("-key %d is not in [1, 1000].", c.key);
     if (c.key > 1 && !c.seq) return text("-key %d needs -seq 1 (propagated frames belong to a sequence).", c.key);
     if (c.autokey && !c.seq) return "-autokey 1 needs -seq 1 (key frames belong to a sequence).";

@@ -87,6 +87,7 @@ struct Config {
     int upguide = 0; nct_guided_params gp;             // -upguide 1, -upsigma: the guided modifier of the upsampling finish (SPEC §6.10), set on every context
     int motion = 0; nct_seq_motion mp;                 // -motion 1, -mr0, -mr, -mpen: motion-compensated blend (SPEC §6.4)
     int key = 1;                                       // -key N: every N-th frame of a sequence is a full one (SPEC §6.5)
+    int carry = 0, carryiters = -1;                    // -carry 1, -carryiters n: correspondence carry (SPEC §6.23); -1 (only where -carryiters is not given): the sequence's own iterations
     int autokey = 0; nct_seq_auto ap;                  // -autokey 1, -keythr, -keycut, -keychange, -keygap: key frames chosen per frame (SPEC §6.7)
     int lut = 0, lutfull = 0; double lut_lambda = 0.0; // -lut N (0 = off), -lutfull 1, -lutlambda (0 = the library's default) (SPEC §6.6)
     std::string mask_dir, refmask_dir; int maskprotect = 0;   // -mask / -refmask <dir>: region masks by content / reference file name (SPEC §6.11 / §6.12), -maskprotect 0 / 1
@@ -94,8 +95,8 @@ struct Config {
     int grid = 0; double grid_lambda = 0.0;            // -grid G (0 = off): nodes along the longer side of a local colour grid, -gridlambda (0 = the library's default) (SPEC §6.22)
 };
 void add_options(CmdLine& cl, Config& cfg);            // the option table, in the help's order
-// the first rule the parsed options break, as the text behind "Error: " (empty: accepted). lutlambda_given, gridlambda_given: "-lutlambda" / "-gridlambda" was on the
+// the first rule the parsed options break, as the text behind "Error: " (empty: accepted). lutlambda_given, gridlambda_given, carryiters_given: "-lutlambda" / "-gridlambda" / "-carryiters" was on the
 // command line
-std::string option_refusal(const Config& cfg, bool lutlambda_given, bool gridlambda_given = false);
+std::string option_refusal(const Config& cfg, bool lutlambda_given, bool gridlambda_given = false, bool carryiters_given = false);
 // after the checks (and -procs' fork, which changes -gpus): seed, levels and flags into prm, the clamps of -gpus, -inflight and -io
 void settle(Config& cfg);

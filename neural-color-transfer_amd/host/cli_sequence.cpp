@@ -64,6 +64,11 @@ size_t run_sequence(nct_ctx* ctx, const Config& cfg, const std::vector<Pair>& pa
                     if (rc == NCT_OK) j.say("Sequence %ld: motion compensation (radius0 = %d, radius = %d, penalty = %d).\n", g.seq, cfg.mp.radius0, cfg.mp.radius, cfg.mp.penalty);
                     else { nct_seq_end(ctx); open = false; }               // no plain sequence where -motion 1 was asked: the next frame begins again
                 }
+                if (open && cfg.carry) {
+                    rc = nct_seq_set_carry(ctx, 1, cfg.carryiters);
+                    if (rc == NCT_OK) j.say("Sequence %ld: correspondence carry (%d iterations on frames that merge; -1 = as every frame).\n", g.seq, cfg.carryiters);
+                    else { nct_seq_end(ctx); open = false; }               // no plain sequence where -carry 1 was asked: the next frame begins again
+                }
             }
             nct_pair_timing tm;
             j.out.resize((size_t)j.cnt.h * j.cnt.w * 3);

@@ -53,10 +53,12 @@ int main(int argc, char** argv) {
     if (!parsed) return -1;
     const bool lutlambda_given = std::any_of(argv + 1, argv + argc, [](const char* a) { return !strcmp(a, "-lutlambda"); });
     const bool gridlambda_given = std::any_of(argv + 1, argv + argc, [](const char* a) { return !strcmp(a, "-gridlambda"); });
-    const std::string refused = option_refusal(cfg, lutlambda_given, gridlambda_given);
+    const bool carryiters_given = std::any_of(argv + 1, argv + argc, [](const char* a) { return !strcmp(a, "-carryiters"); });
+    const std::string refused = option_refusal(cfg, lutlambda_given, gridlambda_given, carryiters_given);
     if (!refused.empty()) { printf("Error: %s\n", refused.c_str()); return -1; }
     if (!lutlambda_given) cfg.lut_lambda = 0.0;                             // a value that came in another spelling of the flag does not count
     if (!gridlambda_given) cfg.grid_lambda = 0.0;
+    if (!carryiters_given) cfg.carryiters = -1;
     if (!plan_only) mkdir(cfg.output_dir.c_str(), 0777);                    // main.cu:458
     uint64_t run_token = getenv("NCT_RUN_TOKEN") ? strtoull(getenv("NCT_RUN_TOKEN"), nullptr, 0) : 0;      // hand-started ranks of one run share it (and remove <output>/.rccl_id between runs)
     const std::string tickets_path = cfg.output_dir + "/.tickets";

@@ -123,6 +123,8 @@ SIGNATURES = {
     "nct_seq_end": (C.c_int, [C.c_void_p]),
     "nct_seq_motion_default": (None, [C.c_void_p]),
     "nct_seq_set_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "nct_seq_set_carry": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "nct_seq_get_carry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nct_seq_auto_default": (None, [C.c_void_p]),
     "nct_seq_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nct_seq_frame_auto": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -256,6 +258,10 @@ _TWINS = {
     "nct_region_refind": [_P, _I, _I, _P, _I, _I, _I, _P],
     "nct_feat_quantize8": [_P, _P, _P, _I, _I, _I],
     "nct_descriptor_match": [_P, _I, _I, _P, _P, _I, _P, _P],              # offsets: a host array in both forms
+    "nct_nnf_carry": [_P, _I, _I, _P, _P],
+    "nct_nnf_forward_map": [_P, _I, _I, _P],
+    "nct_nnf_remap": [_P, _I, _I, _P, _I, _I, _P],
+    "nct_nnf_merge": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
 }
 for _name, _args in _TWINS.items():
     SIGNATURES[_name] = SIGNATURES[_name + "_dev"] = (C.c_int, [C.c_void_p] + _args)
@@ -1657,6 +1663,67 @@ class Context:
             ms, fs, out = s.put(m), s.put(f), s.new((H, W), np.uint8)
             s.call(ms, H, W, fs, h, w, s.over(out, ms if alias else None))
             return s.get(out)
+
+    # ---- correspondence carry (SPEC §6.23)
+    def seq_set_carry(self, on=True, iters=-1):
+        """nct_seq_set_carry: from the next full frame on the open sequence starts every level's PatchMatch from the merge of its ordinary start field and the kept
+        fields of the last frame (True), or as it always did (False). iters: PatchMatch iterations of a frame that merged, -1 = the sequence's pm_iters"""
+        self._chk(self._l.nct_seq_set_carry(self._h, int(on), int(iters)))
+
+    def seq_get_carry(self, k=0, l=0):
+        """nct_seq_get_carry -> (ann [ah_l, aw_l], bnn [bh_l, bw_l]) uint32: the kept fields of reference k at level run l as the last frame left them"""
+        q = self._seq_record("seq_get_carry", "seq_begin")
+        g = self._seq_grids()
+        if not (0 <= k < len(g.ref) and 0 <= l < q.levels):      # the library refuses; nothing is written
+            self._chk(self._l.nct_seq_get_carry(self._h, int(k), int(l), None, None))
+        ann, bnn = np.empty(g.src[l], np.uint32), np.empty(g.ref[k][l], np.uint32)
+        self._chk(self._l.nct_seq_get_carry(self._h, int(k), int(l), ann.ctypes.data, bnn.ctypes.data))
+        return ann, bnn
+
+    def nnf_carry(self, nnf_prev, field, *, dev=False, alias=False):
+        """nct_nnf_carry[_dev] (SPEC §6.23 rule 3): nnf_prev [h, w] uint32, field int16 [h, w, 2] of (my, mx) -> nnf_prev read at the clamped p + m(p). alias (device
+        form): into nnf_prev's block, which is an error"""
+        f = np.ascontiguousarray(field, np.int16)
+        h, w = f.shape[:2]
+        a = np.ascontiguousarray(nnf_prev, np.uint32)
+        assert a.size == h * w and f.size == 2 * h * w
+        with self._seam("nnf_carry", dev) as s:
+            as_, fs, out = s.put(a), s.put(f), s.new((h, w), np.uint32)
+            s.call(as_, h, w, fs, s.over(out, as_ if alias else None))
+            return s.get(out)
+
+    def nnf_forward_map(self, field, *, dev=False, alias=False):
+        """nct_nnf_forward_map[_dev] (SPEC §6.23 rule 4): field int16 [h, w, 2] -> F [h, w] uint32. alias (device form): into the field's block, which is an error"""
+        f = np.ascontiguousarray(field, np.int16)
+        h, w = f.shape[:2]
+        with self._seam("nnf_forward_map", dev) as s:
+            fs, out = s.put(f), s.new((h, w), np.uint32)
+            s.call(fs, h, w, s.over(out, fs if alias else None))
+            return s.get(out)
+
+    def nnf_remap(self, bnn_prev, fwd, *, dev=False, alias=False):
+        """nct_nnf_remap[_dev] (SPEC §6.23 rule 4): bnn_prev [bh, bw] uint32, fwd [h, w] uint32 -> fwd read at bnn_prev's words. alias (device form): into bnn_prev's
+        block, which is an error"""
+        b, fw = np.ascontiguousarray(bnn_prev, np.uint32), np.ascontiguousarray(fwd, np.uint32)
+        (bh, bw), (h, w) = b.shape, fw.shape
+        with self._seam("nnf_remap", dev) as s:
+            bs, fs, out = s.put(b), s.put(fw), s.new((bh, bw), np.uint32)
+            s.call(bs, bh, bw, fs, h, w, s.over(out, bs if alias else None))
+            return s.get(out)
+
+    def nnf_merge(self, a_chw, b_chw, z, c, *, dev=False, alias=False, want_dist=True, patch=3):
+        """nct_nnf_merge[_dev] (SPEC §6.23 rule 6, one direction): normalised features a [C, ah, aw] and b [C, bh, bw] (the device form uploads them channel-last), the
+        ordinary start field z and the moved kept field c, [ah, aw] uint32 -> (start, d_z, d_c), or start alone. alias (device form): into z's block, which is an error"""
+        a, b = np.ascontiguousarray(a_chw, np.float32), np.ascontiguousarray(b_chw, np.float32)
+        (Cc, ah, aw), (_, bh, bw) = a.shape, b.shape
+        z_, c_ = np.ascontiguousarray(z, np.uint32).reshape(ah, aw), np.ascontiguousarray(c, np.uint32).reshape(ah, aw)
+        hwc = lambda m: np.ascontiguousarray(m.reshape(m.shape[0], -1).T)
+        with self._seam("nnf_merge", dev) as s:
+            as_, bs = s.put(a, upload=hwc(a)), s.put(b, upload=hwc(b))
+            zs, cs, out = s.put(z_), s.put(c_), s.new((ah, aw), np.uint32)
+            dz, dc = (s.new((ah, aw), np.float32), s.new((ah, aw), np.float32)) if want_dist else (None, None)
+            s.call(as_, bs, Cc, ah, aw, bh, bw, int(patch), zs, cs, s.over(out, zs if alias else None), dz, dc)
+            return (s.get(out), s.get(dz), s.get(dc)) if want_dist else s.get(out)
 
     def seq_set_region_tracking(self, on):
         """nct_seq_set_region_tracking: from the next frame on the open sequence's matte follows the motion field (True) or stays sticky (False)"""
